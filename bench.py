@@ -2,6 +2,7 @@
 """Benchmark of the hot path: events/s for a fused kinematics + full-detector batch.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--events E] [--workload o16aa]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of E synthetic events per GPU
 (default: the BASELINE.json headline, 1e6-event two-step 16O(a,a')16O* -> a + 12C with the
@@ -21,8 +22,15 @@ and the MAX over ranks is taken.
 The JSON line also carries
   roofline     -- algorithmic HBM bytes of the dominant kernel's launches / its measured
                   average launch duration (HIP events on the engine's stream) vs 8 TB/s
+and, with --full only (a plain run does nothing beyond what the headline figure needs):
+  delivered    -- the same events with their clouds / Spyral rows delivered to host arrays, N = 1
   cpu_baseline -- the CPU oracle (plain-C restatement of the reference algorithm, OpenMP
                   over events) timed on this host's cores on a bounded sample, rank 0, N = 1
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step computed as DIR/<name>.npy
+(float64): the step's counts and checksums over ALL of its events, and the arrays a caller of Engine.run(fetch=True)
+receives for a fixed, seeded sample of that step's event ids (recomputed from the same ids and seed; every draw
+is keyed by the global event id), each event's cloud rows in a canonical order.  At most 64 MB in all.
 """
 from __future__ import annotations
 
@@ -45,6 +53,8 @@ N_CUS, SIMDS_PER_CU, N_XCDS = 256, 4, 8
 # MI355X_MICROARCH.md "LDS"), one LDS pipeline per CU -> at most CLOCK / 2 wave-level atomics per CU and second
 LDS_ATOMIC_PEAK_PER_S = N_CUS * CLOCK_HZ / 2.0
 PMC_PROFILE = "r03_pmc.json"
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together
+DUMP_EVENTS, DUMP_BLOCK = 64, 8  # --dump-outputs: sampled events, in blocks of consecutive ids (one engine call each)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -59,8 +69,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--workload", default="o16aa")
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--chunk-events", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-delivered", action="store_true", help="skip the delivered-to-host leg (clouds over PCIe)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the delivered-to-host rates and the CPU baseline "
+                         "(single GPU; each can still be left out with --no-delivered / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-delivered", action="store_true",
+                    help="with --full: skip the delivered-to-host leg (clouds over PCIe)")
     ap.add_argument("--delivered-events", type=int, default=60_000)
     ap.add_argument("--hint", action="store_true",
                     help="announce the next step to the engine (attpc_sim_hint_next): its first track batch is then integrated "
@@ -77,6 +93,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -309,17 +327,97 @@ def main(argv=None) -> int:
             **issue,
         },
     }
-    if world_size == 1 and not args.no_delivered and config is not None and not args.stub_engine:
+    if args.dump_outputs:
+        last_first, last_n = step_range(args.steps - 1)
+        dump_outputs(Path(args.dump_outputs), engine, args.seed, last_first, last_n, stats, cloud=not args.stub_engine)
+    if args.full and world_size == 1 and not args.no_delivered and config is not None and not args.stub_engine:
         try:
             # (bounded by the rows as well: 60 000 events of configs[4] would be 100 GB of cloud)
             n_deliver = min(args.delivered_events, step_events, max(1000, int(4.5e8 / max(p_event, 1.0))))
             line["delivered"] = delivered(engine, n_deliver, args.seed, bytes_per_event, p_event)
         except Exception as exc:  # the headline line must not depend on this leg
             line["delivered"] = {"error": f"{type(exc).__name__}: {exc}"}
-    if world_size == 1 and not args.no_cpu_baseline and not args.stub_engine:
+    if args.full and world_size == 1 and not args.no_cpu_baseline and not args.stub_engine:
         line["cpu_baseline"] = cpu_baseline(args.workload, args.seed)
     print(json.dumps(line), flush=True)
     return 0
+
+
+DUMP_COUNTS = ("n_points", "n_track_samples", "n_failed", "n_sample_limit", "n_tracks_capped")
+
+
+def dump_outputs(out_dir: Path, engine, seed: int, first: int, n: int, stats: dict, cloud: bool = True) -> None:
+    """--dump-outputs: what the last timed step (this rank's events first .. first + n - 1) computed, as float64
+    arrays in out_dir/<name>.npy --
+      step_counts  [events, n_points, n_track_samples, n_failed, n_sample_limit, n_tracks_capped, charge_checksum
+                   low / high 32 bits, key_checksum low / high 32 bits] of the whole step, from its own statistics;
+      event_ids, vertex, p4, status, offsets, points, labels -- what Engine.run(fetch=True) returns for a fixed
+                   sample of the step's ids (DUMP_EVENTS of them in blocks of DUMP_BLOCK consecutive ids, drawn by a
+                   generator seeded with the arguments), recomputed from the same ids and seed, which gives the same
+                   events; offsets are the CSR of the sample and every event's rows are sorted by (pad, time bucket,
+                   charge, label), so that two runs compare row for row.
+    Events are added while the files stay within DUMP_LIMIT_BYTES; should the first event's cloud alone not fit,
+    a seeded sample of its rows is written instead."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    halves = []
+    for key in ("charge_checksum", "key_checksum"):
+        v = int(stats[key]) % (1 << 64)
+        halves += [v & 0xFFFFFFFF, v >> 32]
+    arrays = {"step_counts": np.array([n] + [stats[k] for k in DUMP_COUNTS] + halves, dtype=np.float64)}
+    if cloud:
+        arrays.update(_sample_clouds(engine, seed, first, n, DUMP_LIMIT_BYTES - (64 << 10)))  # (room for headers)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}")
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+    print(f"bench.py: {len(arrays)} arrays of the last timed step ({total / 1e6:.1f} MB) written to {out_dir}",
+          file=sys.stderr)
+
+
+def _sample_clouds(engine, seed: int, first: int, n: int, budget: int) -> dict:
+    import numpy as np
+
+    rng = np.random.default_rng([seed % (1 << 64), first, n])
+    if n <= DUMP_EVENTS:
+        starts, size = [first], n
+    else:
+        picks = np.sort(rng.choice(n // DUMP_BLOCK, size=DUMP_EVENTS // DUMP_BLOCK, replace=False))
+        starts, size = [first + DUMP_BLOCK * int(b) for b in picks], DUMP_BLOCK
+    fixed = 8 * (1 + 3 + 4 * engine.n_rows + 1 + 1)  # bytes per event: id, vertex, p4, status, offset
+    ids, vertex, p4, status, points, labels = [], [], [], [], [], []
+    used, room = 8, True  # (the leading offset)
+    for start in starts:
+        res = engine.run(size, seed=seed, first_event=start, fetch=True)
+        for e in range(size):
+            lo, hi = int(res["offsets"][e]), int(res["offsets"][e + 1])
+            pts, lab = res["points"][lo:hi], res["labels"][lo:hi]
+            order = np.lexsort((lab, pts[:, 2], pts[:, 1], pts[:, 0]))
+            pts, lab = pts[order], lab[order]
+            if used + fixed + 32 * len(pts) > budget:  # 3 coordinates + label per row
+                room = False
+                if ids:
+                    break
+                keep = np.sort(rng.choice(len(pts), size=max(0, (budget - used - fixed) // 32), replace=False))
+                pts, lab = pts[keep], lab[keep]
+            used += fixed + 32 * len(pts)
+            ids.append(start + e)
+            vertex.append(res["vertex"][e])
+            p4.append(res["p4"][e])
+            status.append(res["status"][e])
+            points.append(pts)
+            labels.append(lab)
+            if not room:
+                break
+        if not room:
+            break
+    counts = np.array([len(p) for p in points], dtype=np.int64)
+    return {"event_ids": np.array(ids, dtype=np.float64), "vertex": np.array(vertex, dtype=np.float64),
+            "p4": np.array(p4, dtype=np.float64), "status": np.array(status, dtype=np.float64),
+            "offsets": np.concatenate([[0], np.cumsum(counts)]).astype(np.float64),
+            "points": np.concatenate(points).astype(np.float64), "labels": np.concatenate(labels).astype(np.float64)}
 
 
 def _pmc(workload: str, kernel: str):

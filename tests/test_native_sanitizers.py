@@ -4,6 +4,7 @@ AddressSanitizer + UBSan driving the golden-vector tests, and the host-only expo
 pools) under ASan + UBSan and under ThreadSanitizer.  Never run on the GPU box (GPU sanitizers are not available
 there, and these need none)."""
 import os
+import platform
 import shutil
 import subprocess
 import sys
@@ -22,6 +23,19 @@ def _gxx():
     return exe
 
 
+def _without_aslr(cmd: list[str]) -> list[str]:
+    """`cmd` with address-space randomisation off for that one process (setarch -R: a personality flag of the child,
+    no system setting).  GCC's ThreadSanitizer expects a PIE executable in a fixed address window and stops with
+    "unexpected memory mapping" on kernels that randomise with more bits than that window allows."""
+    setarch = shutil.which("setarch")
+    if setarch is None:
+        return cmd
+    arch = platform.machine()
+    if subprocess.run([setarch, arch, "-R", "true"], capture_output=True).returncode != 0:
+        return cmd
+    return [setarch, arch, "-R"] + cmd
+
+
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("name,flags", [
     ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]),
@@ -37,7 +51,8 @@ def test_unpack_threads_under_sanitizers(tmp_path, name, flags):
     assert build.returncode == 0, build.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
                TSAN_OPTIONS="halt_on_error=1")
-    run = subprocess.run([str(exe), "300000"], capture_output=True, text=True, env=env)
+    run = subprocess.run(_without_aslr([str(exe), "300000"]) if name == "tsan" else [str(exe), "300000"],
+                         capture_output=True, text=True, env=env)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-4000:])
     assert "mismatches 0" in run.stdout
     assert "ERROR" not in run.stderr and "WARNING: ThreadSanitizer" not in run.stderr, run.stderr[-4000:]

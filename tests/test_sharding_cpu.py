@@ -128,3 +128,30 @@ def test_bench_fails_when_a_rank_fails():
     """A rank that dies makes the launcher exit non-zero (here: an unknown workload raises in every rank)."""
     rc, lines, _ = _run_bench(["--gpus", "2", "--workload", "no_such_workload"])
     assert rc != 0 and not lines
+
+
+@pytest.mark.timeout(240)
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run times exactly --steps steps and carries no leg that only --full runs; --dump-outputs writes the
+    last timed step's counts and checksums (stub engine: no cloud to sample) as float64, the same from run to run."""
+    from bench import StubEngine
+
+    runs = []
+    for tag in ("a", "b"):
+        rc, lines, err = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--events", "500",
+                                     "--dump-outputs", str(tmp_path / tag)])
+        assert rc == 0 and len(lines) == 1, err
+        runs.append(np.load(tmp_path / tag / "step_counts.npy"))
+        line = lines[0]
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert "cpu_baseline" not in line and "delivered" not in line
+        assert sorted(p.name for p in (tmp_path / tag).iterdir()) == ["step_counts.npy"]
+    assert runs[0].dtype == np.float64 and np.array_equal(runs[0], runs[1])
+    last = StubEngine(0).run(500, seed=3, first_event=2 * 500)["stats"]  # step 2 of 3 covers ids [1000, 1500)
+    assert runs[0][:2].tolist() == [500, last["n_points"]]
+    charge = int(runs[0][6]) + (int(runs[0][7]) << 32)
+    assert charge == last["charge_checksum"]
+    rc, lines, err = _run_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--events", "100", "--full"])
+    assert rc == 0 and len(lines) == 1 and lines[0]["steps"] == 1, err
+    rc, lines, _ = _run_bench(["--steps", "0"])
+    assert rc != 0 and not lines
