@@ -129,6 +129,25 @@ class RunStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+U64 = 1 << 64
+
+
+def check_id_range(seed, first_event, n_events) -> tuple[int, int, int]:
+    """``(seed, first_event, n_events)`` as the C ABI takes them (three u64), or ``ValueError``: ctypes would wrap a
+    negative or too large value silently (``seed=-1`` -> 2^64 - 1).  Seeds are ``0 <= seed < 2^64``; the event ids
+    ``first_event .. first_event + n_events - 1`` must lie in ``[0, 2^64)`` (include/attpc_engine.h)."""
+    seed, first_event, n_events = int(seed), int(first_event), int(n_events)
+    if not 0 <= seed < U64:
+        raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+    if not 0 <= first_event < U64:
+        raise ValueError(f"first_event must be in [0, 2^64), got {first_event}")
+    if n_events < 0:
+        raise ValueError(f"n_events must be >= 0, got {n_events}")
+    if first_event + n_events > U64:
+        raise ValueError(f"event ids {first_event} .. {first_event} + {n_events} - 1 pass 2^64")
+    return seed, first_event, n_events
+
+
 class EngineUnavailable(RuntimeError):
     """The HIP library or a HIP device is missing -- there is no CPU fallback."""
 

@@ -265,6 +265,15 @@ void pick_track_stream(attpc_ctx* ctx) {
   ctx->stream_t = serial ? ctx->stream : ctx->stream_t_own;
 }
 
+// event ids first_event .. first_event + n_events - 1 must all lie in [0, 2^64) (include/attpc_engine.h): a range that
+// wraps would silently reuse the streams of events 0, 1, ...
+int32_t validate_id_range(attpc_ctx* ctx, uint64_t first_event, uint64_t n_events) {
+  if (n_events != 0 && n_events - 1 > ~0ull - first_event)
+    return fail(ctx, ATTPC_E_INVALID, "event ids %llu + %llu events pass 2^64", (unsigned long long)first_event,
+                (unsigned long long)n_events);
+  return ATTPC_OK;
+}
+
 int32_t validate_layout(attpc_ctx* ctx, const attpc_event_layout* lay, bool with_species) {
   if (!lay || lay->n_rows < 1 || lay->n_rows > ATTPC_MAX_ROWS || lay->n_sim < 0 || lay->n_sim > ATTPC_MAX_SIM)
     return fail(ctx, ATTPC_E_INVALID, "bad event layout");
@@ -1134,6 +1143,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
 int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events, const attpc_event_layout& lay,
                    const RunSource& src, const RunSink& sink, attpc_cloud_out* out, bool spyral, attpc_run_stats* stats) {
   int32_t rc;
+  if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
   UnpackDrain drain(ctx);
   attpc_run_stats st{};
   st.n_events = n_events;
@@ -1510,6 +1520,7 @@ int32_t attpc_kin_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint6
                       double* vertex, int32_t* status, uint32_t* attempts) {
   if (!ctx) return ATTPC_E_INVALID;
   if (!ctx->kin_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_kin_configure has not been called");
+  if (validate_id_range(ctx, first_event, n_events)) return ATTPC_E_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int n_rows = 4 + 2 * (ctx->kin.n_steps - 1);
   // buffers of its own (ctx->scratch): the track sets are sized by the largest track batch met so far
@@ -1733,8 +1744,9 @@ int32_t attpc_sim_hint_next(attpc_ctx* ctx, uint64_t seed, uint64_t first_event,
   ctx->hint_valid = false;
   if (!layout || n_events == 0) return ATTPC_OK;  // "nothing known about the next call"
   if (!ctx->kin_ready || !ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_sim_hint_next before the configure calls");
-  int32_t rc = validate_layout(ctx, layout, true);
+  int32_t rc = validate_id_range(ctx, first_event, n_events);
   if (rc) return rc;
+  if ((rc = validate_layout(ctx, layout, true))) return rc;
   if (layout->n_rows != 4 + 2 * (ctx->kin.n_steps - 1)) return fail(ctx, ATTPC_E_INVALID, "layout.n_rows does not match the pipeline");
   ctx->hint_valid = true;
   ctx->hint_seed = seed;
@@ -1784,6 +1796,7 @@ int32_t attpc_det_tracks(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, ui
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc = validate_layout(ctx, layout, true);
   if (rc) return rc;
+  if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
   if (n_events > (uint64_t)ctx->chunk_events) return fail(ctx, ATTPC_E_INVALID, "attpc_det_tracks handles at most one chunk");
   if ((rc = drop_prefetch(ctx))) return rc;
   const uint32_t n = (uint32_t)n_events;
@@ -1826,6 +1839,7 @@ int32_t attpc_det_scatter(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, u
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc = validate_layout(ctx, layout, false);
   if (rc) return rc;
+  if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
   if (n_events > (uint64_t)ctx->chunk_events) return fail(ctx, ATTPC_E_INVALID, "attpc_det_scatter handles at most one chunk");
   if ((rc = drop_prefetch(ctx))) return rc;
   const uint32_t n = (uint32_t)n_events;

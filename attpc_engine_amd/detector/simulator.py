@@ -98,6 +98,7 @@ def simulate_batch(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, ma
     momenta = np.ascontiguousarray(momenta, dtype=np.float64)
     vertices = np.ascontiguousarray(vertices, dtype=np.float64)
     n = momenta.shape[0]
+    seed, first_event, n = _abi.check_id_range(seed, first_event, n)
     keys = species_for(proton_numbers, mass_numbers, indices)
     configure_detector(config, keys, ctx)
     layout = build_layout(proton_numbers, mass_numbers, indices, keys)
@@ -134,6 +135,7 @@ def simulate_batch_spyral(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     momenta = np.ascontiguousarray(momenta, dtype=np.float64)
     vertices = np.ascontiguousarray(vertices, dtype=np.float64)
     n = momenta.shape[0]
+    seed, first_event, n = _abi.check_id_range(seed, first_event, n)
     keys = species_for(proton_numbers, mass_numbers, indices)
     configure_detector(config, keys, ctx)
     configure_spyral(config, ctx, response)

@@ -59,6 +59,7 @@ class Engine:
         """Announce the ``run`` / ``run_spyral`` call after the next one (``attpc_sim_hint_next``): the next call then
         queues that call's first kinematics + track batch behind its own last scatter launches.  A scheduling hint
         only -- results never depend on it; ``n_events = 0`` withdraws it."""
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         ctx = self.ctx
         ctx.check(ctx.lib.attpc_sim_hint_next(ctx.handle, int(seed), int(first_event), int(n_events), self.layout),
                   "attpc_sim_hint_next")
@@ -73,6 +74,7 @@ class Engine:
         arrays in page-locked host memory (the copy is PCIe bound), ``reuse_buffers`` reuses them
         from call to call (a consumer that is done with one batch before it asks for the next).
         Raises ``DataLossError`` if an event lost charge (``n_failed`` / ``n_inconsistent``)."""
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         ctx = self.ctx
         stats = _abi.RunStats()
         if not fetch:
@@ -118,6 +120,7 @@ class Engine:
         pad scale) in CSR form, the rows of every event in ascending z (reference writer.py:232-238), and
         ``event_points`` [n] = cloud rows of every event before the threshold (an event is "empty" for
         the writer only if that is 0, simulator.py:204-205)."""
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         if not getattr(self, "_spyral_configured", False):
             self.configure_spyral()
         ctx = self.ctx

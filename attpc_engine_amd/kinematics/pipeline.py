@@ -183,12 +183,12 @@ class KinematicsPipeline:
         Returns ``(vertex [n,3], p4 [n,N,4])`` (+ ``(status, attempts)`` if asked).  Raises
         ``PipelineError`` if any event exhausts ``event_sample_limit`` (reference
         pipeline.py:316-319) unless ``return_status`` is set."""
+        seed, first_event, n_events = _abi.check_id_range(self.seed if seed is None else seed, first_event, n_events)
         if not is_device_samplable(self):
             return self._run_many_host_sampled(n_events, return_status)
         ctx = self.context
         if not self._configured or getattr(ctx, "_kin_owner", None) != id(self):
             self.configure_device()
-        seed = self.seed if seed is None else int(seed)
         n_rows = len(self.result)
         p4 = np.empty((n_events, n_rows, 4), dtype=np.float64)
         vertex = np.empty((n_events, 3), dtype=np.float64)

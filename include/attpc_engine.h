@@ -20,6 +20,10 @@
  *     event[39:32] << 24 | tb << 14 | pad) and key word = seed[31:0] ^ rotl(seed[63:32], 13) ^ 0x100
  *     -- every draw a pure function of (seed, global event id, ...): results do not depend on
  *     batch / chunk / GPU count.
+ *   - seeds are any u64.  A call's event ids first_event .. first_event + n_events - 1 must all lie in
+ *     [0, 2^64): a range that would wrap past 2^64 is ATTPC_E_INVALID (attpc_kin_run, attpc_det_run,
+ *     attpc_sim_run, their _spyral forms, attpc_det_tracks, attpc_det_scatter, attpc_sim_hint_next).
+ *     Ids 2^40 apart share their jitter streams (the jitter counter holds event[39:0]) and nothing else.
  */
 #ifndef ATTPC_ENGINE_H
 #define ATTPC_ENGINE_H

@@ -644,6 +644,13 @@ void orc_transport_track(const orc_det_desc* det, const double* xyt, const int64
   transport_track_ex(det, xyt, electrons, n, points, label, 0, 0, 0);
 }
 
+/* the same at a given seed / event: sample_base = entries of the event's earlier tracks (numbers the Monte-Carlo
+ * streams of the extension as one event's tracks are numbered) */
+void orc_transport_track_at(const orc_det_desc* det, const double* xyt, const int64_t* electrons, int32_t n,
+                            orc_dict* points, int64_t label, uint64_t seed, uint64_t event, int64_t sample_base) {
+  transport_track_ex(det, xyt, electrons, n, points, label, seed, event, sample_base);
+}
+
 /* detector/solver.py:350-413 */
 static int32_t generate_point_cloud_ex(const orc_det_desc* det, const orc_species_desc* sp, const double mom[4],
                                       const double vertex[3], uint64_t seed, uint64_t event, int64_t label,

@@ -133,6 +133,10 @@ void orc_dict_item(const orc_dict* d, int64_t i, int64_t* key, int64_t* charge, 
 
 void orc_transport_track(const orc_det_desc* det, const double* track_xyt /*[n][3] x,y,time*/,
                          const int64_t* electrons, int32_t n, orc_dict* points, int64_t label);
+/* the same at a given seed / event (only the Monte-Carlo diffusion extension draws here); sample_base = entries of the
+ * event's earlier tracks */
+void orc_transport_track_at(const orc_det_desc* det, const double* xyt, const int64_t* electrons, int32_t n,
+                            orc_dict* points, int64_t label, uint64_t seed, uint64_t event, int64_t sample_base);
 /* samples out (optional): rows (x, y, time bucket, electrons*gain) of kept samples */
 int32_t orc_generate_point_cloud(const orc_det_desc* det, const orc_species_desc* sp,
                                  const double momentum[4], const double vertex[3], uint64_t seed,

@@ -81,6 +81,9 @@ def lib() -> C.CDLL:
     L.orc_dict_item.restype = None
     L.orc_transport_track.argtypes = [C.POINTER(_abi.DetDesc), _dp, _i64p, C.c_int32, C.c_void_p, C.c_int64]
     L.orc_transport_track.restype = None
+    L.orc_transport_track_at.argtypes = [C.POINTER(_abi.DetDesc), _dp, _i64p, C.c_int32, C.c_void_p, C.c_int64,
+                                         C.c_uint64, C.c_uint64, C.c_int64]
+    L.orc_transport_track_at.restype = None
     L.orc_generate_point_cloud.argtypes = [C.POINTER(_abi.DetDesc), C.POINTER(_abi.SpeciesDesc), _dp, _dp,
                                            C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, _dp, _i32p]
     L.orc_simulate.argtypes = [C.POINTER(_abi.DetDesc), C.POINTER(_abi.EventLayout), C.c_uint64, C.c_uint64,
@@ -187,15 +190,19 @@ def electrons(det: _abi.DetDesc, species_index: int, track: np.ndarray, seed: in
     return out
 
 
-def transport(det: _abi.DetDesc, cases):
+def transport(det: _abi.DetDesc, cases, seed: int = 0, event: int = 0):
     """cases: list of (xyt [n,3], electrons [n] int64, label) -> (keys, charge, labels) in
-    dictionary insertion order."""
+    dictionary insertion order.  ``seed`` / ``event`` key the Monte-Carlo diffusion draws (extension); its entries
+    are numbered across the cases as one event's tracks are."""
     L = lib()
     handle = L.orc_dict_new()
+    base = 0
     for xyt, elec, label in cases:
         xyt = np.ascontiguousarray(xyt, dtype=np.float64)
         elec = np.ascontiguousarray(elec, dtype=np.int64)
-        L.orc_transport_track(det, d(xyt), elec.ctypes.data_as(_i64p), len(xyt), handle, int(label))
+        L.orc_transport_track_at(det, d(xyt), elec.ctypes.data_as(_i64p), len(xyt), handle, int(label), int(seed),
+                                 int(event), base)
+        base += len(xyt)
     n = L.orc_dict_len(handle)
     keys = np.empty(n, dtype=np.int64)
     charge = np.empty(n, dtype=np.int64)

@@ -86,13 +86,16 @@ def _sorted(pad, tb, charge, label):
     return pad[order], tb[order], charge[order], label[order]
 
 
-def _compare_with_dict(points, labels, tb_ref, pad_ref, charge_ref, label_ref):
-    """Device cloud vs a reference dictionary (keys in any order): the 0 <= tb < 512 mask of
-    simulator.py:111-113 applied to the reference side."""
+def _compare_with_dict(points, labels, tb_ref, pad_ref, charge_ref, label_ref, seed, event):
+    """Device cloud of event ``event`` (global id) at ``seed`` vs a reference dictionary (keys in any order): the
+    0 <= tb < 512 mask of simulator.py:111-113 applied to the reference side; the jitter of every point exact."""
+    from oracle import pyoracle
     keep = (tb_ref >= 0) & (tb_ref < 512) & (pad_ref >= 0)
     ref = _sorted(pad_ref[keep], tb_ref[keep], charge_ref[keep], label_ref[keep])
     tb_dev = np.floor(points[:, 1]).astype(np.int64)
     assert ((points[:, 1] - tb_dev) >= 0).all() and ((points[:, 1] - tb_dev) < 1).all()  # jitter in [0, 1)
+    jitter = np.array([pyoracle.jitter_uniform(seed, event, (int(t) << 14) | int(p)) for t, p in zip(tb_dev, points[:, 0])])
+    np.testing.assert_array_equal(points[:, 1], tb_dev + jitter)  # (seed, event, tb << 14 | pad) -> Philox2x32-7
     dev = _sorted(points[:, 0].astype(np.int64), tb_dev, points[:, 2].astype(np.int64), labels)
     np.testing.assert_array_equal(dev[0], ref[0])
     np.testing.assert_array_equal(dev[1], ref[1])
@@ -117,14 +120,15 @@ def test_scatter_kernel_vs_reference_transport(golden_dir, ctx, name):
         ctx.set_option("scatter_variant", variant)
         (cloud,), stats = device_scatter(ctx, [cases])
         tbpad = g[f"{name}_tbpad"]
-        worst, exact = _compare_with_dict(cloud[0], cloud[1], tbpad[:, 0], tbpad[:, 1], g[f"{name}_charge"], g[f"{name}_labels"])
+        worst, exact = _compare_with_dict(cloud[0], cloud[1], tbpad[:, 0], tbpad[:, 1], g[f"{name}_charge"], g[f"{name}_labels"],
+                                          11, 0)
         assert exact > 0.999 and stats["n_failed"] == 0 and stats["n_inconsistent"] == 0
         print(name, "variant", variant, "points", len(cloud[0]), "max |dq|", worst, "exact fraction", exact)
     ctx.set_option("scatter_variant", 0)
     if name == "mixed":  # dict_to_points (simulator.py:19-49) of the reference on the same dictionary
         pa = g["mixed_point_array"]
         _compare_with_dict(cloud[0], cloud[1], pa[:, 1].astype(np.int64), pa[:, 0].astype(np.int64),
-                           pa[:, 2].astype(np.int64), g["mixed_label_array"])
+                           pa[:, 2].astype(np.int64), g["mixed_label_array"], 11, 0)
 
 
 def test_track_kernel_vs_reference_radau(golden_dir, ctx):
@@ -201,14 +205,14 @@ def test_reference_tracks_through_scatter_vs_oracle(golden_dir, ctx, orc):
         events.append([(xyt, el[keep_rows] * cfg.det_params.mpgd_gain, 2)])
     clouds, stats = device_scatter(ctx, events)
     total = 0
-    for ev, (pts, lab) in zip(events, clouds):
+    for e, (ev, (pts, lab)) in enumerate(zip(events, clouds)):
         keys, charge, labels = orc.transport(raw, ev)
         tb = np.empty(len(keys), dtype=np.int64)
         pad = np.empty(len(keys), dtype=np.int64)
         for k, key in enumerate(keys):
             t, p = orc.unpair(int(key))
             tb[k], pad[k] = t, p
-        _compare_with_dict(pts, lab, tb, pad, charge, labels)
+        _compare_with_dict(pts, lab, tb, pad, charge, labels, 11, e)
         total += len(pts)
     assert total > 500 and stats["n_failed"] == 0
 
@@ -244,10 +248,10 @@ def test_lone_time_bucket_larger_than_the_lds_table(ctx, orc, variant, must_be_l
         ctx.set_option("scatter_variant", 0)
     assert stats["n_failed"] == 0 and stats["n_inconsistent"] == 0
     assert stats["n_lone_buckets"] >= 1 or not must_be_lone
-    for ev, (pts, lab) in zip([small, big, small], clouds):
+    for e, (ev, (pts, lab)) in enumerate(zip([small, big, small], clouds)):
         keys, charge, labels = orc.transport(raw, ev)
         tb, pad = np.array([orc.unpair(int(k)) for k in keys], dtype=np.int64).T
-        _compare_with_dict(pts, lab, tb, pad, charge, labels)
+        _compare_with_dict(pts, lab, tb, pad, charge, labels, 11, e)
     lit = len(clouds[1][0])
     assert lit > 8192, lit
     print("variant", variant, "pads lit in the lone bucket:", lit, "lone buckets:", stats["n_lone_buckets"])
