@@ -103,6 +103,19 @@ __device__ __forceinline__ double normal_from(double ua, double ub) {
   return sqrt(-2.0 * log(1.0 - ua)) * cos(TWO_PI * ub);
 }
 
+// a * b + c with the product rounded before the sum, as numpy (and the -ffp-contract=off oracle) computes it.  hipcc
+// contracts `a * b + c` into one v_fma_f64 by default, and __dmul_rn / __dadd_rn do not stop it (without
+// OCML_BASIC_ROUNDED_OPERATIONS they are the plain operators); the pragma does.  Every float -> integer decision of
+// the scatter (the whole-mm cell of a mesh line, the time bucket of a slice) takes its position through this:
+//   c -+ 3 sigma     = mul_add_rn(-+3.0, sigma, c)      (transporter.py:221-222)
+//   linspace(lo, hi, n)[i] = mul_add_rn((double)i, step, lo), i < n - 1; the last element is hi itself
+// A fused line sits up to an ulp off the reference's and crosses a cell edge now and then
+// (tests/test_gpu_boundaries.py).
+__device__ __forceinline__ double mul_add_rn(double a, double b, double c) {
+#pragma clang fp contract(off)
+  return a * b + c;
+}
+
 // stopping-power table on the binade grid (include/attpc_engine.h): pure bit arithmetic on
 // the f64 -- exponent selects the binade, the top 5 mantissa bits the sub-bin, the remaining
 // 47 bits are the interpolation weight.

@@ -102,8 +102,8 @@ __global__ __launch_bounds__(LONE_THREADS) void lone_bucket_kernel(ScatterArgs a
       double ts = tm;
       if (n_slices > 1) {  // numpy.linspace(t - 3 sigma_l, t + 3 sigma_l, 5)[sl], as in scatter.hip
         const double sigma_l = sqrt(2.0 * a.det.longitudinal_diffusion * a.det.dv * tm / a.det.efield) / a.det.dv;
-        const double lo = tm - 3.0 * sigma_l, hi = tm + 3.0 * sigma_l;
-        ts = sl == n_slices - 1 ? hi : (double)sl * ((hi - lo) / (double)(n_slices - 1)) + lo;
+        const double lo = mul_add_rn(-3.0, sigma_l, tm), hi = mul_add_rn(3.0, sigma_l, tm);
+        ts = sl == n_slices - 1 ? hi : mul_add_rn((double)sl, (hi - lo) / (double)(n_slices - 1), lo);
       }
       if (!(ts >= 0.0 && ts < (double)ATTPC_NUM_TB) || (int)ts != tb) continue;
       const double sigma = sqrt(2.0 * a.det.diffusion * a.det.dv * tm / a.det.efield);  // transporter.py:301
@@ -117,8 +117,8 @@ __global__ __launch_bounds__(LONE_THREADS) void lone_bucket_kernel(ScatterArgs a
           const double rad = sqrt(-2.0 * log(1.0 - ua));
           double sn, cn;
           sincos(TWO_PI * ub, &sn, &cn);
-          const double x = __dadd_rn(x0, __dmul_rn(sigma, __dmul_rn(rad, cn)));
-          const double y = __dadd_rn(y0, __dmul_rn(sigma, __dmul_rn(rad, sn)));
+          const double x = mul_add_rn(sigma, rad * cn, x0);
+          const double y = mul_add_rn(sigma, rad * sn, y0);
           add((int)lut[lut_index(x) * (lut_n + 1) + lut_index(y)], q, isim);
         }
       } else {
@@ -127,12 +127,13 @@ __global__ __launch_bounds__(LONE_THREADS) void lone_bucket_kernel(ScatterArgs a
           add((int)lut[lut_index(x0) * (lut_n + 1) + lut_index(y0)], (unsigned long long)n_w, isim);
           continue;
         }
-        const double xlo = x0 - 3.0 * sigma, xhi = x0 + 3.0 * sigma, ylo = y0 - 3.0 * sigma, yhi = y0 + 3.0 * sigma;
+        const double xlo = mul_add_rn(-3.0, sigma, x0), xhi = mul_add_rn(3.0, sigma, x0);
+        const double ylo = mul_add_rn(-3.0, sigma, y0), yhi = mul_add_rn(3.0, sigma, y0);
         const double sx = (xhi - xlo) / (double)(MESH - 1), sy = (yhi - ylo) / (double)(MESH - 1);
         for (int j = 0; j < MESH; ++j) {    // x mesh lines (numpy.linspace, :221-227)
-          const int ixx = lut_index(j == MESH - 1 ? xhi : (double)j * sx + xlo);
+          const int ixx = lut_index(j == MESH - 1 ? xhi : mul_add_rn((double)j, sx, xlo));
           for (int i = 0; i < MESH; ++i) {  // y mesh lines
-            const int iyy = lut_index(i == MESH - 1 ? yhi : (double)i * sy + ylo);
+            const int iyy = lut_index(i == MESH - 1 ? yhi : mul_add_rn((double)i, sy, ylo));
             add((int)lut[ixx * (lut_n + 1) + iyy], (unsigned long long)(sh.wtab[i * MESH + j] * n_w), isim);
           }
         }

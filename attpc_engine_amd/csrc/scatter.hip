@@ -175,8 +175,8 @@ static_assert(2 * MAX_CHUNKS * sizeof(uint32_t) <= SORT_CAP * sizeof(unsigned sh
 __device__ __forceinline__ double slice_time(const DetDev& det, double t, int sl, int n_slices) {
   if (n_slices == 1) return t;
   const double sigma_l = sqrt(2.0 * det.longitudinal_diffusion * det.dv * t / det.efield) / det.dv;
-  const double lo = t - 3.0 * sigma_l, hi = t + 3.0 * sigma_l;
-  return sl == n_slices - 1 ? hi : (double)sl * ((hi - lo) / (double)(n_slices - 1)) + lo;
+  const double lo = mul_add_rn(-3.0, sigma_l, t), hi = mul_add_rn(3.0, sigma_l, t);
+  return sl == n_slices - 1 ? hi : mul_add_rn((double)sl, (hi - lo) / (double)(n_slices - 1), lo);
 }
 
 // Estimated distinct keys a sample adds: its mesh is 6 sigma_t wide, pads have a ~4.9 mm pitch,
@@ -1140,8 +1140,8 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
               double sn, cs;
               sincos(TWO_PI * ub, &sn, &cs);
               // no FMA contraction: the oracle rounds the product before the sum
-              const double x = __dadd_rn(m.x, __dmul_rn(m.sigma, __dmul_rn(rad, cs)));
-              const double y = __dadd_rn(m.y, __dmul_rn(m.sigma, __dmul_rn(rad, sn)));
+              const double x = mul_add_rn(m.sigma, rad * cs, m.x);
+              const double y = mul_add_rn(m.sigma, rad * sn, m.y);
               const double fx = floor(x * 1000.0), fy = floor(y * 1000.0);
               const int ixx = (fx >= lo_mm && fx < hi_mm) ? (int)fx - lut_lo : lut_n;
               const int iyy = (fy >= lo_mm && fy < hi_mm) ? (int)fy - lut_lo : lut_n;
@@ -1507,18 +1507,19 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
           // numpy.linspace(c - 3 sigma, c + 3 sigma, 10) (:221-227) and position_to_index
           // (:107-118: whole-mm floor, low edge inclusive, high edge exclusive) per mesh line
           const bool sane = sigma >= 0.0;  // (a NaN would convert to 0, the middle of the table: sent far outside instead)
-          const double xlo = sane ? xy.x - 3.0 * sigma : 1.0e300, xhi = sane ? xy.x + 3.0 * sigma : 1.0e300;
-          const double ylo = sane ? xy.y - 3.0 * sigma : 1.0e300, yhi = sane ? xy.y + 3.0 * sigma : 1.0e300;
+          const double xlo = sane ? mul_add_rn(-3.0, sigma, xy.x) : 1.0e300, xhi = sane ? mul_add_rn(3.0, sigma, xy.x) : 1.0e300;
+          const double ylo = sane ? mul_add_rn(-3.0, sigma, xy.y) : 1.0e300, yhi = sane ? mul_add_rn(3.0, sigma, xy.y) : 1.0e300;
           const double sx = (xhi - xlo) / (double)(MESH - 1), sy = (yhi - ylo) / (double)(MESH - 1);
           auto mesh_line = [&](int i) {
-            const double x = (i == MESH - 1) ? xhi : (double)i * sx + xlo;
-            const double y = (i == MESH - 1) ? yhi : (double)i * sy + ylo;
+            const double x = (i == MESH - 1) ? xhi : mul_add_rn((double)i, sx, xlo);
+            const double y = (i == MESH - 1) ? yhi : mul_add_rn((double)i, sy, ylo);
             // lanes are mesh lines of constant y that step through x: 8 % fewer runs than the other way
             // round on the AT-TPC pad plane (the weights are symmetric, so the pixels are the same).
             // The range test is made on the whole number (v_cvt saturates: a floor outside int32 stays outside the
-            // table; unsigned, so below the low edge is above the high one): two instructions instead of five.
-            const short vy = (short)min((unsigned int)((int)floor(x * 1000.0) - lut_lo), (unsigned int)lut_n);
-            const short vx = (short)min((unsigned int)((int)floor(y * 1000.0) - lut_lo), (unsigned int)lut_n);
+            // table; the difference is taken unsigned, so below the low edge is above the high one and a saturated
+            // value does not overflow a signed int): two instructions instead of five.
+            const short vy = (short)min((unsigned int)(int)floor(x * 1000.0) - (unsigned int)lut_lo, (unsigned int)lut_n);
+            const short vx = (short)min((unsigned int)(int)floor(y * 1000.0) - (unsigned int)lut_lo, (unsigned int)lut_n);
             if constexpr (MERGE) {
               const MergeStage ms = merge_stage(sh);
               ms.iy[slot][i] = vy;
@@ -1560,16 +1561,16 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
           const double sigma = sqrt(sh.sigma_k[0] * tn.x / sh.sigma_k[1]);  // :301 (2 D dv t / E, left to right)
           const double c = axis ? xy.y : xy.x;
           const bool sane = sigma >= 0.0;  // (a NaN would convert to 0, the middle of the table: sent far outside instead)
-          const double lo = sane ? c - 3.0 * sigma : 1.0e300, hi = sane ? c + 3.0 * sigma : 1.0e300;
+          const double lo = sane ? mul_add_rn(-3.0, sigma, c) : 1.0e300, hi = sane ? mul_add_rn(3.0, sigma, c) : 1.0e300;
           const double step = (hi - lo) / (double)(MESH - 1);  // numpy.linspace(c - 3 sigma, c + 3 sigma, 10) (:221-227)
           // x lines are the ones a lane of the rows phase steps through (iy), its own line is a y line (ix): stage_entry()
           short* __restrict__ out = axis ? &ms.ix[slot][0] : &ms.iy[slot][0];
           auto line = [&](int i, double v) {
-            const int k = (int)floor(v * 1000.0) - lut_lo;  // position_to_index (:107-118): whole-mm floor
-            out[i] = (short)min((unsigned int)k, (unsigned int)lut_n);  // low edge inclusive, high edge exclusive
+            const unsigned int k = (unsigned int)(int)floor(v * 1000.0) - (unsigned int)lut_lo;  // position_to_index (:107-118): whole-mm floor
+            out[i] = (short)min(k, (unsigned int)lut_n);  // low edge inclusive, high edge exclusive
           };
 #pragma unroll 1
-          for (int i = 0; i < MESH - 1; ++i) line(i, (double)i * step + lo);
+          for (int i = 0; i < MESH - 1; ++i) line(i, mul_add_rn((double)i, step, lo));
           line(MESH - 1, hi);
           if (axis == 0) {
             ms.n[slot] = (ns == 1 ? 1.0 : sh.long_w[sl]) * tn.y;  // x 1.0 is exact

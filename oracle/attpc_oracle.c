@@ -613,8 +613,10 @@ static void transport_track_ex(const orc_det_desc* det, const double* xyt, const
   const int n_slices = det->longitudinal_diffusion > 0.0 ? 5 : 1;
   for (int32_t i = 0; i < n; ++i) {
     double time = xyt[3 * i + 2];
+    /* time < 0 is undefined behaviour in the reference (sigma_t NaN): dropped, as on the device -- also a negative
+     * time so small that 2 D dv t / E underflows to -0 (there the reference would make a point in time bucket 0) */
+    if (!(time >= 0.0)) continue;
     double sigma_t = sqrt(2.0 * det->diffusion * dv * time / det->efield);
-    if (!(sigma_t == sigma_t)) continue; /* NaN (time < 0) is undefined behaviour in the reference: dropped */
     if (det->longitudinal_diffusion > 0.0) {
       /* EXTENSION: 5 time slices over +-3 sigma_l (numpy.linspace semantics), weight long_weights[s] */
       double sigma_l = sqrt(2.0 * det->longitudinal_diffusion * dv * time / det->efield) / dv;

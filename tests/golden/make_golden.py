@@ -389,6 +389,41 @@ def main() -> None:
                                     config.pad_centers, config.pad_sizes)
     np.savez_compressed(OUT / "response.npz", response=resp, points=pts, rows=rows)
     print("response max", resp.max(), "argmax", int(resp.argmax()), "sum", resp.sum())
+
+    # ---- G8 samples on the scatter's rounding edges (tests/boundary_cases.py), ONE sample per dictionary ----
+    # Inputs and the reference's transport_track output of classes A (mesh lines), C (t >= 0) and D (far off the
+    # plane); class B (extension) and the negative times (undefined in the reference) as inputs only.
+    from tests import boundary_cases as bc
+
+    d1, d10 = bc.Detector(0.277), bc.Detector(2.77)
+    groups = {
+        "mesh": (d1, bc.mesh_cases(d1, 120, 1)),
+        "mesh10": (d10, bc.mesh_cases(d10, 100, 2)),
+        "mesh_lone": (d1, bc.mesh_cases(d1, 24, 3, t_range=(500.0, 501.0))),  # all in time bucket 500
+        "lut_edge": (d1, bc.lut_edge_cases(d1)),
+        "time": (d1, bc.time_edge_cases()),
+        "far": (d1, bc.far_cases()),
+    }
+    bd = {}
+    for name, (bdet, case) in groups.items():
+        xyt, electrons = case[0], case[1]
+        parts = [run_transport([(row[None], np.array([el]), bc.LABEL)], bdet.diffusion) for row, el in zip(xyt, electrons)]
+        bd[f"{name}_diffusion"] = bdet.diffusion
+        bd[f"{name}_xyt"] = xyt
+        bd[f"{name}_electrons"] = electrons
+        if len(case) > 2:
+            bd[f"{name}_meta"] = case[2]
+        bd[f"{name}_offsets"] = np.concatenate([[0], np.cumsum([len(p[0]) for p in parts])]).astype(np.int64)
+        bd[f"{name}_keys"] = np.concatenate([p[0] for p in parts]).astype(np.int64)
+        bd[f"{name}_tbpad"] = np.concatenate([p[1].reshape(-1, 2) for p in parts]).astype(np.int64)
+        bd[f"{name}_charge"] = np.concatenate([p[2] for p in parts]).astype(np.int64)
+        bd[f"{name}_labels"] = np.concatenate([p[3] for p in parts]).astype(np.int64)
+        print("boundary", name, "samples", len(xyt), "points", len(bd[f"{name}_keys"]))
+    bd["slice_xyt"], bd["slice_electrons"], bd["slice_meta"] = bc.slice_cases(d1)
+    bd["slice_longitudinal_diffusion"] = bc.LONG_DIFFUSION
+    bd["negtime_xyt"], bd["negtime_electrons"] = bc.time_edge_cases(negative=True)
+    print("boundary slice samples", len(bd["slice_xyt"]))
+    np.savez_compressed(OUT / "boundary.npz", **bd)
     print("wrote fixtures to", OUT)
 
 
