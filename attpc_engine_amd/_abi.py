@@ -21,6 +21,7 @@ DEDX_EMAX = 14
 DEDX_SUB = 32
 DEDX_NODES = (DEDX_EMAX - DEDX_EMIN) * DEDX_SUB + 1
 NUM_TB = 512
+NUM_PADS = 10240
 TIME_SAMPLES = 10001
 LONG_STEPS = 5
 
@@ -113,6 +114,24 @@ class SpyralDesc(C.Structure):
     ]
 
 
+class TraceDesc(C.Structure):
+    _fields_ = [("response", _dp), ("adc_threshold", C.c_double), ("offset", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TraceOut(C.Structure):
+    _fields_ = [
+        ("capacity", C.c_int64),
+        ("offsets", C.POINTER(C.c_int64)),
+        ("pads", C.POINTER(C.c_int32)),
+        ("samples", C.POINTER(C.c_int16)),
+        ("labels", C.POINTER(C.c_int64)),
+        ("event_points", C.POINTER(C.c_int64)),
+        ("n_rows", C.c_int64),
+        ("sample_checksum", C.c_uint64),
+        ("pad_checksum", C.c_uint64),
+    ]
+
+
 class RunStats(C.Structure):
     _fields_ = [
         ("n_events", C.c_uint64), ("n_points", C.c_uint64), ("n_track_samples", C.c_uint64),
@@ -186,6 +205,7 @@ EXPORTED_SYMBOLS = (
     "attpc_sim_run", "attpc_det_tracks", "attpc_spyral_rows", "attpc_spyral_configure", "attpc_sim_run_spyral",
     "attpc_set_option", "attpc_host_alloc", "attpc_host_free", "attpc_det_scatter", "attpc_unpack_rows",
     "attpc_unpack_spyral_rows", "attpc_det_run_spyral", "attpc_sim_hint_next", "attpc_unpack_rows8",
+    "attpc_trace_configure", "attpc_sim_run_traces", "attpc_det_run_traces", "attpc_traces",
 )
 
 _lib = None
@@ -241,6 +261,16 @@ def load_library() -> C.CDLL:
     lib.attpc_det_run_spyral.argtypes = lib.attpc_det_run.argtypes
     lib.attpc_sim_hint_next.argtypes = [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout)]
     lib.attpc_spyral_configure.argtypes = [ctxp, C.POINTER(SpyralDesc)]
+    lib.attpc_trace_configure.argtypes = [ctxp, C.POINTER(TraceDesc)]
+    lib.attpc_sim_run_traces.argtypes = [
+        ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
+        C.POINTER(C.c_int32), C.POINTER(TraceOut), C.POINTER(RunStats),
+    ]
+    lib.attpc_det_run_traces.argtypes = [
+        ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
+        C.POINTER(TraceOut), C.POINTER(RunStats),
+    ]
+    lib.attpc_traces.argtypes = [ctxp, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(TraceOut)]
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

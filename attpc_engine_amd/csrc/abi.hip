@@ -47,6 +47,7 @@ constexpr int CTRL_WORDS = 40;         // u64 control words per scatter launch (
 constexpr uint32_t LONE_CAPACITY = 65536;
 constexpr int64_t CLOUD_BUDGET_BYTES = 24ll << 30;  // points + labels of one chunk
 constexpr int64_t DELIVER_CHUNK_ROWS = 96ll << 20;  // cloud rows of a chunk whose cloud is delivered (3 GB: ~60 ms of PCIe)
+constexpr int64_t TRACE_CHUNK_ROWS = 4ll << 20;     // kept pad rows of a chunk of a trace run (4 GiB of samples)
 constexpr uint64_t ARENA_BUDGET_BYTES = 24ull << 30;
 
 struct DevBuf {
@@ -62,8 +63,11 @@ struct TrackSet {  // kinematics + tracks of one track batch
   bool timed_kin = false;
 };
 
-struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows
+struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its pad traces
   DevBuf ev_start, points, labels, kept, kept_start, sp_rows, sp_labels;
+  DevBuf tr_scratch, tr_info, tr_pads, tr_samples, tr_labels;  // pad traces (traces.hip)
+  size_t tr_cap = 0;  // kept pad rows the trace outputs are kept at (grown with headroom)
+  hipEvent_t traced = nullptr;  // the chunk's traces are written (the copies on C wait for it)
   size_t row_cap = 0;  // rows the row-sized buffers of the set are kept at (grown with headroom: a launch's row
                        // capacity follows the observed rows per event and moves by fractions of a percent)
   int64_t* h_start = nullptr;  // pinned [h_start_len]: CSR offsets of the chunk (n + 1 entries)
@@ -159,6 +163,11 @@ struct attpc_ctx {
 
   bool spyral_ready = false;
   SpyralDev spyral{};
+  bool trace_ready = false;
+  TraceDev trace{};
+  std::vector<void*> trace_allocs;
+  DevBuf trace_sums;               // [2] sample / pad checksums of the trace run in progress
+  double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
   std::vector<void*> spyral_allocs;
   std::vector<double> h_pad_centers, h_pad_sizes;  // host copies: the expansion of compact Spyral records needs them
   DevBuf scratch[8];
@@ -765,12 +774,88 @@ int32_t ensure_pinned_start(attpc_ctx* ctx, AsmSet& as, size_t len) {
   return ATTPC_OK;
 }
 
+// What a run delivers: clouds (attpc_sim_run / attpc_det_run), Spyral rows (_spyral) or pad traces (_traces).
+enum class OutMode { cloud, spyral, traces };
+
+TraceScratch trace_scratch(AsmSet& as, size_t cap) {
+  TraceScratch sc;
+  uint32_t* base = static_cast<uint32_t*>(as.tr_scratch.p);
+  sc.row = base;
+  sc.hit = base + cap;
+  sc.hit_start = base + 2 * cap;
+  sc.rank = reinterpret_cast<int32_t*>(base + 3 * cap);
+  sc.info = static_cast<uint32_t*>(as.tr_info.p);
+  return sc;
+}
+
+// Trace count pass of the n events whose event-ordered cloud is in `as` (ev_start / points / labels, `cap` rows at
+// most), the scan of the kept rows and the copy of their CSR offsets to as.h_start, on S.
+int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap) {
+  int32_t rc;
+  if ((rc = ensure(ctx, as.kept, std::max<size_t>(n, 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, as.kept_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, as.tr_scratch, std::max<size_t>(cap, 1) * 4 * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, as.tr_info, std::max<size_t>(n, 1) * 2 * sizeof(uint32_t)))) return rc;
+  if (n) {
+    launch_trace_count(ctx->stream, ctx->trace, n, static_cast<const int64_t*>(as.ev_start.p),
+                       static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p),
+                       trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t))), static_cast<uint32_t*>(as.kept.p));
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(as.kept.p), n,
+                     static_cast<int64_t*>(as.kept_start.p), static_cast<int64_t*>(nullptr),
+                     static_cast<const unsigned long long*>(nullptr));
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(as.h_start, as.kept_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  return ATTPC_OK;
+}
+
+// The counted chunk in `as` has `total` kept rows (as.h_start[n], read by the host): size the trace outputs, queue the
+// write pass on S (checksums into ctx->trace_sums) and record as.traced behind it.
+int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t total, uint64_t first_event) {
+  int32_t rc;
+  if (total > 0) {
+    if ((size_t)total > as.tr_cap) as.tr_cap = (size_t)total + (size_t)total / 8;
+    if ((rc = ensure(ctx, as.tr_pads, as.tr_cap * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(ctx, as.tr_samples, as.tr_cap * ATTPC_NUM_TB * sizeof(int16_t)))) return rc;
+    if ((rc = ensure(ctx, as.tr_labels, as.tr_cap * sizeof(int64_t)))) return rc;
+    launch_trace_write(ctx->stream, ctx->trace, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
+                       static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p),
+                       trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t))),
+                       static_cast<const int64_t*>(as.kept_start.p), static_cast<int32_t*>(as.tr_pads.p),
+                       static_cast<int16_t*>(as.tr_samples.p), static_cast<int64_t*>(as.tr_labels.p),
+                       static_cast<unsigned long long*>(ctx->trace_sums.p));
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
+  return ATTPC_OK;
+}
+
+// Queue the copies of the written traces of `as` (rows base .. base + total of the caller's arrays; any array may be
+// NULL) on C behind as.traced, then record as.copied.
+int32_t copy_traces(attpc_ctx* ctx, AsmSet& as, int64_t total, int64_t base, const attpc_trace_out* out, bool fits) {
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
+  if (total > 0 && fits) {
+    if (out->pads)
+      HIP_TRY(ctx, hipMemcpyAsync(out->pads + base, as.tr_pads.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream_c));
+    if (out->samples)
+      HIP_TRY(ctx, hipMemcpyAsync(out->samples + base * ATTPC_NUM_TB, as.tr_samples.p, (size_t)total * ATTPC_NUM_TB * sizeof(int16_t),
+                                  hipMemcpyDeviceToHost, ctx->stream_c));
+    if (out->labels)
+      HIP_TRY(ctx, hipMemcpyAsync(out->labels + base, as.tr_labels.p, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream_c));
+  }
+  HIP_TRY(ctx, hipEventRecord(as.copied, ctx->stream_c));
+  return ATTPC_OK;
+}
+
 // Queue, behind the scatter of slot `slot` on S, the assembly of its cloud into `as`: CSR offsets by a
 // device scan of the per-event row counts, rows gathered into event order; for Spyral output also the
-// kept-row counts, their scan and the converted, thresholded, z-sorted rows.  The row totals and the
-// offsets are copied to pinned memory; as.ready is recorded at the end.  `rows_bound` >= the rows the
+// kept-row counts, their scan and the converted, thresholded, z-sorted rows; for traces the count pass and the scan
+// of the kept pad rows (the write pass follows once the host knows their number, deliver_traces).  The row totals and
+// the offsets are copied to pinned memory; as.ready is recorded at the end.  `rows_bound` >= the rows the
 // launch can have produced (the reservation capacity).
-int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, bool spyral) {
+int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMode mode) {
+  const bool spyral = mode == OutMode::spyral;
   int32_t rc;
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, as.copied, 0));  // the set's previous contents have left
   // rows of the scatter launch queued just before (same stream, same slot), kept with 12 % headroom
@@ -790,7 +875,9 @@ int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, bool 
                      static_cast<double*>(as.points.p), static_cast<int64_t*>(as.labels.p));
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(as.h_ev_rows, ctx->ev_rows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (!spyral) {
+  if (mode == OutMode::traces) {
+    if ((rc = enqueue_trace_count(ctx, as, n, cap))) return rc;
+  } else if (!spyral) {
     HIP_TRY(ctx, hipMemcpyAsync(as.h_start, as.ev_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->opt_compact) {
       if ((rc = ensure(ctx, as.packed, cap * sizeof(PackedRow) + 2 * sizeof(int64_t)))) return rc;
@@ -900,9 +987,28 @@ struct UnpackDrain {
   }
 };
 
+// The counted traces of the chunk in `as` (as.ready has fired): write its offsets, queue the write pass and the copies.
+int32_t deliver_traces(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_first_local, attpc_trace_out* out,
+                       int64_t* row_cursor, bool* over_capacity, uint64_t chunk_first_global) {
+  const int64_t base = *row_cursor;
+  const int64_t total = as.h_start[n];
+  if (out->offsets)
+    for (uint32_t i = 0; i <= n; ++i) out->offsets[chunk_first_local + i] = base + as.h_start[i];
+  if (out->event_points)
+    for (uint32_t i = 0; i < n; ++i) out->event_points[chunk_first_local + i] = (int64_t)as.h_ev_rows[i];
+  *row_cursor = base + total;
+  if (n) ctx->trace_rows_per_event = std::max((double)total / (double)n, 1.0e-3);
+  const bool wanted = out->pads || out->samples || out->labels;
+  if (wanted && *row_cursor > out->capacity) *over_capacity = true;
+  int32_t rc;
+  if ((rc = enqueue_trace_write(ctx, as, n, total, chunk_first_global))) return rc;
+  return copy_traces(ctx, as, total, base, out, wanted && *row_cursor <= out->capacity);
+}
+
 // The chunk in `as` is ready on the device: write its offsets, queue its copy to the caller's arrays on C.
-int32_t deliver_chunk(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_first_local, bool spyral, attpc_cloud_out* out,
+int32_t deliver_chunk(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_first_local, OutMode mode, attpc_cloud_out* out,
                       int64_t* row_cursor, bool* over_capacity, uint64_t seed, uint64_t chunk_first_global) {
+  const bool spyral = mode == OutMode::spyral;
   const int64_t base = *row_cursor;
   const int64_t total = as.h_start[n];
   if (out->offsets)
@@ -1030,7 +1136,8 @@ int32_t queue_batch(attpc_ctx* ctx, TrackSet& ts, TrackLaunch& tl, const attpc_e
 template <typename QueueNext>
 int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const TrackBuffers& trk, uint64_t seed,
                          uint64_t batch_first_global, uint64_t batch_first_local, uint32_t nb, attpc_cloud_out* out,
-                         bool spyral, attpc_run_stats* st, int64_t* row_cursor, bool* over, QueueNext queue_next) {
+                         attpc_trace_out* tout, OutMode mode, attpc_run_stats* st, int64_t* row_cursor, bool* over,
+                         QueueNext queue_next) {
   int32_t rc;
   bool next_queued = false;
   auto queue_next_once = [&]() -> int32_t {
@@ -1044,6 +1151,10 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
       for (uint32_t i = 0; i <= nb; ++i) out->offsets[batch_first_local + i] = *row_cursor;
     if (out && out->event_points)
       for (uint32_t i = 0; i < nb; ++i) out->event_points[batch_first_local + i] = 0;
+    if (tout && tout->offsets)
+      for (uint32_t i = 0; i <= nb; ++i) tout->offsets[batch_first_local + i] = *row_cursor;
+    if (tout && tout->event_points)
+      for (uint32_t i = 0; i < nb; ++i) tout->event_points[batch_first_local + i] = 0;
     return ATTPC_OK;
   }
   if ((rc = ensure(ctx, ctx->out_ctrl, (size_t)MAX_SLOTS * CTRL_WORDS * sizeof(unsigned long long)))) return rc;
@@ -1058,7 +1169,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     ctx->lone_ready = true;
   }
   struct Chunk { uint32_t e0, n; int slot; };
-  if (!out) {
+  if (!out && mode != OutMode::traces) {
     // device resident: queue up to MAX_SLOTS chunks back to back, read their control words once
     uint32_t e0 = 0;
     while (e0 < nb) {
@@ -1102,13 +1213,15 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     for (int attempt = 0; r.overflow && attempt < 8; ++attempt) {
       int32_t rc2;
       if ((rc2 = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + c.e0, c.e0, c.n, min_rows, min_segs))) return rc2;
-      if ((rc2 = enqueue_assembly(ctx, c.slot, as, c.n, spyral))) return rc2;
+      if ((rc2 = enqueue_assembly(ctx, c.slot, as, c.n, mode))) return rc2;
       HIP_TRY(ctx, hipEventSynchronize(as.ready));
       read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
     }
     if (r.overflow) return fail(ctx, ATTPC_E_HIP, "point cloud did not fit after repeated buffer growth");
     accumulate(st, r);
-    return deliver_chunk(ctx, as, c.n, batch_first_local + c.e0, spyral, out, row_cursor, over, seed, batch_first_global + c.e0);
+    if (mode == OutMode::traces)
+      return deliver_traces(ctx, as, c.n, batch_first_local + c.e0, tout, row_cursor, over, batch_first_global + c.e0);
+    return deliver_chunk(ctx, as, c.n, batch_first_local + c.e0, mode, out, row_cursor, over, seed, batch_first_global + c.e0);
   };
   while (e0 < nb) {
     const bool pilot = ctx->rows_per_event <= 0.0;  // only ever true with nothing in flight
@@ -1119,11 +1232,13 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     uint32_t n = std::min<uint32_t>(next_chunk_events(ctx, nb - e0), (uint32_t)ctx->opt_deliver_chunk);
     if (ctx->rows_per_event > 0.0)
       n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)DELIVER_CHUNK_ROWS / ctx->rows_per_event));
+    if (mode == OutMode::traces && ctx->trace_rows_per_event > 0.0)  // 1 KiB of samples per kept pad row
+      n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)TRACE_CHUNK_ROWS / ctx->trace_rows_per_event));
     const Chunk c{e0, n, seq % MAX_SLOTS};
     const int set = seq & 1;
     // an overflow of the chunk in flight is repaired inside complete(); queue this one behind it
     if ((rc = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + e0, e0, n, 0, 0))) return rc;
-    if ((rc = enqueue_assembly(ctx, c.slot, ctx->aset[set], n, spyral))) return rc;
+    if ((rc = enqueue_assembly(ctx, c.slot, ctx->aset[set], n, mode))) return rc;
     if ((rc = queue_next_once())) return rc;
     if (prev.slot >= 0 && (rc = complete(prev, prev_set))) return rc;
     prev = c;
@@ -1141,9 +1256,16 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
 }
 
 int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events, const attpc_event_layout& lay,
-                   const RunSource& src, const RunSink& sink, attpc_cloud_out* out, bool spyral, attpc_run_stats* stats) {
+                   const RunSource& src, const RunSink& sink, attpc_cloud_out* out, OutMode mode, attpc_run_stats* stats,
+                   attpc_trace_out* tout = nullptr) {
+  const bool spyral = mode == OutMode::spyral;
   int32_t rc;
   if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
+  if (mode == OutMode::traces) {
+    if ((rc = ensure(ctx, ctx->trace_sums, 2 * sizeof(unsigned long long)))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->trace_sums.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    if (tout->offsets) tout->offsets[0] = 0;
+  }
   UnpackDrain drain(ctx);
   attpc_run_stats st{};
   st.n_events = n_events;
@@ -1237,7 +1359,8 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
     if (sink.status) HIP_TRY(ctx, hipMemcpyAsync(sink.status + b0, ts.status.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (sink.p4) HIP_TRY(ctx, hipMemcpyAsync(sink.p4 + b0 * n_rows * 4, ts.p4.p, (size_t)nb * n_rows * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (sink.vertex) HIP_TRY(ctx, hipMemcpyAsync(sink.vertex + b0 * 3, ts.vertex.p, (size_t)nb * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = run_batch_chunks(ctx, lay, trk, seed, first_event + b0, b0, nb, out, spyral, &st, &row_cursor, &over, queue_next))) return rc;
+    if ((rc = run_batch_chunks(ctx, lay, trk, seed, first_event + b0, b0, nb, out, tout, mode, &st, &row_cursor, &over, queue_next)))
+      return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // this set's readers are done before it is refilled
     b0 = next_b0;
     nb = next_nb;
@@ -1245,9 +1368,19 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
   if (spyral) st.n_points = (uint64_t)row_cursor;  // rows that survive the threshold
+  if (mode == OutMode::traces) {  // (the cloud's meaning stays in st)
+    unsigned long long sums[2] = {0ull, 0ull};
+    HIP_TRY(ctx, hipMemcpyAsync(sums, ctx->trace_sums.p, sizeof sums, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    tout->n_rows = row_cursor;
+    tout->sample_checksum = sums[0];
+    tout->pad_checksum = sums[1];
+  }
   st.n_buffer_growths = ctx->n_growths - growths_before;
   st.device_bytes = ctx->device_bytes;
   if (stats) *stats = st;
+  if (over && mode == OutMode::traces)
+    return fail(ctx, ATTPC_E_CAPACITY, "traces need %lld rows, capacity %lld", (long long)row_cursor, (long long)tout->capacity);
   if (over) return fail(ctx, ATTPC_E_CAPACITY, "cloud needs %lld rows, capacity %lld", (long long)row_cursor, (long long)out->capacity);
   if (st.n_failed || st.n_inconsistent)
     return fail(ctx, ATTPC_E_DATALOSS, "%llu events lost a time bucket (n_failed), %u table self-check failures (n_inconsistent) in %llu events",
@@ -1293,7 +1426,7 @@ int32_t attpc_ctx_create(int32_t device, attpc_ctx** out) {
   }
   for (int i = 0; i < MAX_SLOTS; ++i) { make_event(&ctx->s0[i]); make_event(&ctx->s1[i]); }
   for (AsmSet& as : ctx->aset) {
-    make_event(&as.ready); make_event(&as.copied);
+    make_event(&as.ready); make_event(&as.copied); make_event(&as.traced);
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&as.h_total), 2 * sizeof(int64_t), hipHostMallocDefault) == hipSuccess;
   }
   ok = ok && hipHostMalloc(reinterpret_cast<void**>(&ctx->h_out_ctrl), (size_t)MAX_SLOTS * CTRL_WORDS * sizeof(unsigned long long),
@@ -1321,9 +1454,10 @@ int32_t attpc_ctx_destroy(attpc_ctx* ctx) {
   free_all(ctx->kin_allocs);
   free_all(ctx->det_allocs);
   free_all(ctx->spyral_allocs);
+  free_all(ctx->trace_allocs);
   std::vector<DevBuf*> bufs = {&ctx->points, &ctx->labels, &ctx->segments, &ctx->ev_rows, &ctx->lone_list, &ctx->lone_chg,
                                &ctx->lone_mask, &ctx->out_ctrl, &ctx->merge_scratch,
-                               &ctx->sort_idx, &ctx->sort_key};
+                               &ctx->sort_idx, &ctx->sort_key, &ctx->trace_sums};
   for (TrackSet& ts : ctx->tset) {
     for (DevBuf* b : {&ts.p4, &ts.vertex, &ts.status, &ts.attempts, &ts.arena, &ts.block_table, &ts.counts, &ts.n_steps, &ts.ctrl})
       bufs.push_back(b);
@@ -1332,9 +1466,10 @@ int32_t attpc_ctx_destroy(attpc_ctx* ctx) {
     if (ts.h_ctrl) (void)hipHostFree(ts.h_ctrl);
   }
   for (AsmSet& as : ctx->aset) {
-    for (DevBuf* b : {&as.ev_start, &as.points, &as.labels, &as.kept, &as.kept_start, &as.sp_rows, &as.sp_labels, &as.packed}) bufs.push_back(b);
+    for (DevBuf* b : {&as.ev_start, &as.points, &as.labels, &as.kept, &as.kept_start, &as.sp_rows, &as.sp_labels, &as.packed,
+                      &as.tr_scratch, &as.tr_info, &as.tr_pads, &as.tr_samples, &as.tr_labels}) bufs.push_back(b);
     if (as.h_packed) (void)hipHostFree(as.h_packed);
-    for (hipEvent_t e : {as.ready, as.copied})
+    for (hipEvent_t e : {as.ready, as.copied, as.traced})
       if (e) (void)hipEventDestroy(e);
     if (as.h_start) (void)hipHostFree(as.h_start);
     if (as.h_ev_rows) (void)hipHostFree(as.h_ev_rows);
@@ -1685,7 +1820,7 @@ int32_t attpc_det_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint6
   RunSource src;
   src.h_p4 = p4;
   src.h_vertex = vertex;
-  return run_events(ctx, seed, first_event, n_events, *layout, src, RunSink{}, out, false, stats);
+  return run_events(ctx, seed, first_event, n_events, *layout, src, RunSink{}, out, OutMode::cloud, stats);
 }
 
 int32_t attpc_det_run_spyral(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
@@ -1701,13 +1836,15 @@ int32_t attpc_det_run_spyral(attpc_ctx* ctx, uint64_t seed, uint64_t first_event
   RunSource src;
   src.h_p4 = p4;
   src.h_vertex = vertex;
-  return run_events(ctx, seed, first_event, n_events, *layout, src, RunSink{}, out, true, stats);
+  return run_events(ctx, seed, first_event, n_events, *layout, src, RunSink{}, out, OutMode::spyral, stats);
 }
 
 static int32_t sim_run_impl(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                             const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
-                            attpc_cloud_out* out, attpc_run_stats* stats, bool spyral) {
+                            attpc_cloud_out* out, attpc_run_stats* stats, OutMode mode, attpc_trace_out* tout = nullptr) {
   if (!ctx) return ATTPC_E_INVALID;
+  const bool spyral = mode == OutMode::spyral;
+  if (mode == OutMode::traces && !ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
   if (spyral && !ctx->spyral_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_spyral_configure has not been called");
   if (!ctx->kin_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_kin_configure has not been called");
   if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_det_configure has not been called");
@@ -1722,20 +1859,138 @@ static int32_t sim_run_impl(attpc_ctx* ctx, uint64_t seed, uint64_t first_event,
   sink.p4 = p4;
   sink.vertex = vertex;
   sink.status = kin_status;
-  return run_events(ctx, seed, first_event, n_events, *layout, src, sink, out, spyral, stats);
+  if (mode == OutMode::traces && (rc = drop_prefetch(ctx))) return rc;  // a trace call is never the announced one
+  return run_events(ctx, seed, first_event, n_events, *layout, src, sink, out, mode, stats, tout);
 }
 
 int32_t attpc_sim_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                       const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
                       attpc_cloud_out* out, attpc_run_stats* stats) {
-  return sim_run_impl(ctx, seed, first_event, n_events, layout, p4, vertex, kin_status, out, stats, false);
+  return sim_run_impl(ctx, seed, first_event, n_events, layout, p4, vertex, kin_status, out, stats, OutMode::cloud);
 }
 
 int32_t attpc_sim_run_spyral(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                              const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
                              attpc_cloud_out* out, attpc_run_stats* stats) {
   if (!out) return fail(ctx, ATTPC_E_INVALID, "attpc_sim_run_spyral needs output buffers");
-  return sim_run_impl(ctx, seed, first_event, n_events, layout, p4, vertex, kin_status, out, stats, true);
+  return sim_run_impl(ctx, seed, first_event, n_events, layout, p4, vertex, kin_status, out, stats, OutMode::spyral);
+}
+
+// ---- digitised pad traces (traces.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure(attpc_ctx* ctx, const attpc_trace_desc* d) {
+  if (!ctx || !d || !d->response) return ATTPC_E_INVALID;
+  if (d->offset < 0 || d->offset >= ATTPC_NUM_TB) return fail(ctx, ATTPC_E_INVALID, "trace offset %d outside 0..511", d->offset);
+  if (std::isnan(d->adc_threshold)) return fail(ctx, ATTPC_E_INVALID, "trace threshold is NaN");
+  for (int j = 0; j < ATTPC_NUM_TB; ++j)
+    if (!(d->response[j] >= 0.0) || std::isinf(d->response[j]))
+      return fail(ctx, ATTPC_E_INVALID, "response[%d] = %g: the trace response must be finite and >= 0", j, d->response[j]);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  free_all(ctx->trace_allocs);
+  ctx->trace_ready = false;
+  TraceDev tr{};
+  int32_t rc;
+  if ((rc = upload(ctx, ctx->trace_allocs, d->response, (size_t)ATTPC_NUM_TB, &tr.response))) return rc;
+  tr.threshold = d->adc_threshold;
+  tr.offset = d->offset;
+  ctx->trace = tr;
+  ctx->trace_ready = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_sim_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                             const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
+                             attpc_trace_out* out, attpc_run_stats* stats) {
+  if (!out) return fail(ctx, ATTPC_E_INVALID, "attpc_sim_run_traces needs an attpc_trace_out");
+  return sim_run_impl(ctx, seed, first_event, n_events, layout, p4, vertex, kin_status, nullptr, stats, OutMode::traces, out);
+}
+
+int32_t attpc_det_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                             const attpc_event_layout* layout, const double* p4, const double* vertex,
+                             attpc_trace_out* out, attpc_run_stats* stats) {
+  if (!ctx || !p4 || !vertex) return ATTPC_E_INVALID;
+  if (!out) return fail(ctx, ATTPC_E_INVALID, "attpc_det_run_traces needs an attpc_trace_out");
+  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_det_configure has not been called");
+  if (!ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc = validate_layout(ctx, layout, true);
+  if (rc) return rc;
+  if ((rc = drop_prefetch(ctx))) return rc;
+  RunSource src;
+  src.h_p4 = p4;
+  src.h_vertex = vertex;
+  return run_events(ctx, seed, first_event, n_events, *layout, src, RunSink{}, nullptr, OutMode::traces, stats, out);
+}
+
+int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points, const int64_t* labels,
+                     attpc_trace_out* out) {
+  if (!ctx || !out || n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
+  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_traces takes at most 2^31 - 1 events per call");
+  if (!ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
+  const uint32_t n = (uint32_t)n_events;
+  const int64_t first = n ? offsets[0] : 0;
+  for (uint32_t e = 0; e < n; ++e)
+    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %u", e);
+  if (first < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
+  const int64_t rows = n ? offsets[n] - first : 0;
+  if (rows > 0 && (!points || !labels)) return ATTPC_E_INVALID;
+  if (rows > (int64_t)UINT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_traces takes fewer than 2^32 rows per call");
+  {  // the contract's rows: integer pad in range, 0 <= tau < 512, finite electrons >= 0, a (pad, t) of their own
+    std::vector<uint32_t> keys;
+    for (uint32_t e = 0; e < n; ++e) {
+      keys.clear();
+      for (int64_t r = offsets[e]; r < offsets[e + 1]; ++r) {
+        const double padf = points[3 * r], tb = points[3 * r + 1], q = points[3 * r + 2];
+        if (!(padf >= 0.0 && padf < (double)ATTPC_NUM_PADS) || padf != std::floor(padf))
+          return fail(ctx, ATTPC_E_INVALID, "row %lld: pad %g is not an integer in [0, %d)", (long long)r, padf, ATTPC_NUM_PADS);
+        if (!(tb >= 0.0 && tb < (double)ATTPC_NUM_TB))
+          return fail(ctx, ATTPC_E_INVALID, "row %lld: time bucket %g outside [0, 512)", (long long)r, tb);
+        if (!(q >= 0.0) || std::isinf(q)) return fail(ctx, ATTPC_E_INVALID, "row %lld: electrons %g", (long long)r, q);
+        keys.push_back((uint32_t)padf * ATTPC_NUM_TB + (uint32_t)std::floor(tb));
+      }
+      std::sort(keys.begin(), keys.end());
+      if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
+        return fail(ctx, ATTPC_E_INVALID, "event %u has two rows on one pad and time bucket", e);
+    }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = drop_prefetch(ctx))) return rc;
+  if ((rc = sync_all(ctx))) return rc;
+  AsmSet& as = ctx->aset[0];
+  const size_t cap = (size_t)std::max<int64_t>(rows, 1);
+  if ((rc = ensure(ctx, as.ev_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, as.points, cap * 3 * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, as.labels, cap * sizeof(int64_t)))) return rc;
+  if ((rc = ensure_pinned_start(ctx, as, (size_t)n + 1))) return rc;
+  if ((rc = ensure(ctx, ctx->trace_sums, 2 * sizeof(unsigned long long)))) return rc;
+  std::vector<int64_t> start((size_t)n + 1, 0);
+  for (uint32_t e = 0; e <= n; ++e) start[e] = offsets[e] - first;
+  HIP_TRY(ctx, hipMemcpyAsync(as.ev_start.p, start.data(), start.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  if (rows > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(as.points.p, points + 3 * first, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(as.labels.p, labels + first, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIP_TRY(ctx, hipMemsetAsync(ctx->trace_sums.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  if ((rc = enqueue_trace_count(ctx, as, n, cap))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the copies above read pageable memory: nothing of it stays in flight)
+  const int64_t total = as.h_start[n];
+  if (out->offsets)
+    for (uint32_t e = 0; e <= n; ++e) out->offsets[e] = as.h_start[e];
+  if (out->event_points)
+    for (uint32_t e = 0; e < n; ++e) out->event_points[e] = offsets[e + 1] - offsets[e];
+  const bool wanted = out->pads || out->samples || out->labels;
+  const bool fits = !wanted || total <= out->capacity;
+  if ((rc = enqueue_trace_write(ctx, as, n, total, 0))) return rc;
+  if ((rc = copy_traces(ctx, as, total, 0, out, fits))) return rc;
+  unsigned long long sums[2] = {0ull, 0ull};
+  HIP_TRY(ctx, hipMemcpyAsync(sums, ctx->trace_sums.p, sizeof sums, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = sync_all(ctx))) return rc;
+  out->n_rows = total;
+  out->sample_checksum = sums[0];
+  out->pad_checksum = sums[1];
+  if (!fits) return fail(ctx, ATTPC_E_CAPACITY, "traces need %lld rows, capacity %lld", (long long)total, (long long)out->capacity);
+  return ATTPC_OK;
 }
 
 int32_t attpc_sim_hint_next(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
@@ -1887,7 +2142,7 @@ int32_t attpc_det_scatter(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, u
   if (out && out->offsets) out->offsets[0] = 0;
   const double keep_rows = ctx->rows_per_event, keep_segs = ctx->segs_per_event;
   ctx->rows_per_event = ctx->segs_per_event = 0.0;  // explicit samples say nothing about the configured workload
-  rc = run_batch_chunks(ctx, *layout, trk, seed, first_event, 0, n, out, false, &st, &row_cursor, &over, []() -> int32_t { return ATTPC_OK; });
+  rc = run_batch_chunks(ctx, *layout, trk, seed, first_event, 0, n, out, nullptr, OutMode::cloud, &st, &row_cursor, &over, []() -> int32_t { return ATTPC_OK; });
   ctx->rows_per_event = keep_rows;
   ctx->segs_per_event = keep_segs;
   if (rc) return rc;

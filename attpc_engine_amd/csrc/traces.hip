@@ -1,0 +1,288 @@
+// traces.hip -- digitised GET pad traces on the device, run on the event-ordered cloud of a chunk before D2H
+// (EXTENSION: the reference stops at point clouds; the contract is written out in include/attpc_engine.h).
+//
+// One workgroup per event, two passes with a device scan in between (as spyral.hip):
+//   count: LDS counting sort of the event's rows by pad (10 240 pads x 4 B), the pad-grouped row list and the list of
+//          hit pads (ascending) into a global scratch range of the event's own cloud rows; then one wave per hit pad
+//          works out the pad's trace and keeps the verdict max > threshold; a block scan turns the verdicts into each
+//          kept pad's rank inside the event.
+//   write: one wave per kept pad works the trace out again and writes pad, label and 512 samples (1 KiB, coalesced) at
+//          kept_start[event] + rank; checksums are summed per workgroup, one global atomic per event.
+// A pad's trace: its rows are scattered into a 512-entry LDS table q[t] (0 where no row exists), the non-zero entries
+// are walked in ascending t, 64 at a time by ballot, and every lane keeps the samples j = lane + 64 s (s = 0..7) as 8 f64
+// accumulators, reading R from LDS.  The dense walk gives the same bits as the sparse ordered sum of the contract: the
+// terms it skips would add +0.0 to an accumulator that starts at +0.0 and never becomes -0.0.
+// Bound: the latency of the per-row LDS reads (the row's charge, then 8 ds_read_b64 of R per lane) at 16 waves per CU --
+// not LDS bandwidth, FP64 issue or HBM (profiles/r04_trace_rate.md).
+#include "tracks_args.hpp"
+
+namespace attpc {
+
+constexpr int TR_THREADS = 512;
+constexpr int TR_WAVES = TR_THREADS / 64;
+constexpr int TR_PADS_PER_THREAD = ATTPC_NUM_PADS / TR_THREADS;  // 20
+static_assert(ATTPC_NUM_PADS % TR_THREADS == 0, "the pad table is split evenly over the threads");
+static_assert(ATTPC_NUM_TB == 512, "a lane keeps 8 samples");
+
+// Product rounded, then added: no contraction into a fused multiply-add (tests/test_traces_cpu.py checks the code).
+__device__ __forceinline__ double mul_then_add(double acc, double q, double r) {
+#pragma clang fp contract(off)
+  const double prod = q * r;
+  return acc + prod;
+}
+
+struct PadTrace {
+  int v[8];       // trace samples j = lane + 64 s
+  int max;        // over the pad's 512 samples (wave-uniform)
+  long long label;
+};
+
+// The trace of the k-th hit pad of the event, worked out by one whole wave.  `qt`: the wave's 512-entry LDS table.
+__device__ __forceinline__ PadTrace pad_trace(const TraceDev& tr, const double* resp, double* qt, int lane,
+                                              const double* __restrict__ points, const int64_t* __restrict__ labels,
+                                              const uint32_t* __restrict__ row, int64_t lo, uint32_t start, uint32_t end) {
+  for (int s = 0; s < 8; ++s) qt[lane + 64 * s] = 0.0;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  double best_q = -1.0;
+  int best_t = ATTPC_NUM_TB;
+  long long best_label = 0;
+  for (uint32_t i = start + (uint32_t)lane; i < end; i += 64u) {
+    const int64_t r = lo + row[lo + i];
+    const int t = (int)floor(points[3 * r + 1]);  // in 0..511: rows outside were never placed
+    const double q = points[3 * r + 2];
+    qt[t] = q;
+    if (q > best_q || (q == best_q && t < best_t)) {
+      best_q = q;
+      best_t = t;
+      best_label = labels[r];
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {  // the largest q, the smallest t on a tie
+    const double oq = __shfl_xor(best_q, off);
+    const int ot = __shfl_xor(best_t, off);
+    const long long ol = __shfl_xor(best_label, off);
+    if (oq > best_q || (oq == best_q && ot < best_t)) {
+      best_q = oq;
+      best_t = ot;
+      best_label = ol;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  double acc[8];
+  for (int s = 0; s < 8; ++s) acc[s] = 0.0;
+  for (int c = 0; c < 8; ++c) {
+    const double qc = qt[64 * c + lane];
+    unsigned long long mask = __ballot(qc != 0.0);
+    while (mask) {
+      const int b = __builtin_ctzll(mask);
+      mask &= mask - 1ull;
+      const double q = __shfl(qc, b);
+      const int k0 = lane + tr.offset - (64 * c + b);  // response index of sample j = lane: k = j + offset - t
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int k = k0 + 64 * s;
+        if ((unsigned)k < (unsigned)ATTPC_NUM_TB) acc[s] = mul_then_add(acc[s], q, resp[k]);
+      }
+    }
+  }
+  PadTrace out;
+  int m = 0;
+  for (int s = 0; s < 8; ++s) {
+    const double a = acc[s] < 4095.0 ? acc[s] : 4095.0;
+    out.v[s] = (int)rint(a);  // half to even
+    m = out.v[s] > m ? out.v[s] : m;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const int o = __shfl_xor(m, off);
+    m = o > m ? o : m;
+  }
+  out.max = m;
+  out.label = best_label;
+  return out;
+}
+
+__device__ __forceinline__ bool trace_row_ok(double padf, double tb) {
+  return padf >= 0.0 && padf < (double)ATTPC_NUM_PADS && tb >= 0.0 && tb < (double)ATTPC_NUM_TB;
+}
+
+__global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, const int64_t* __restrict__ event_start,
+                                                                 const double* __restrict__ points,
+                                                                 const int64_t* __restrict__ labels, TraceScratch sc,
+                                                                 uint32_t* __restrict__ kept) {
+  __shared__ uint32_t cursor[ATTPC_NUM_PADS];  // counts, then the next free place of every pad's group
+  __shared__ double resp[ATTPC_NUM_TB];
+  __shared__ double qtab[TR_WAVES][ATTPC_NUM_TB];
+  __shared__ uint32_t wave_rows[TR_WAVES], wave_hits[TR_WAVES];
+  __shared__ uint32_t n_hits, n_placed, kept_run;
+  const uint32_t e = blockIdx.x;
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t lo = event_start[e], hi = event_start[e + 1];
+  if (hi <= lo) {  // uniform
+    if (t == 0) {
+      kept[e] = 0u;
+      sc.info[2 * e] = 0u;
+      sc.info[2 * e + 1] = 0u;
+    }
+    return;
+  }
+  for (int p = t; p < ATTPC_NUM_PADS; p += TR_THREADS) cursor[p] = 0u;
+  for (int j = t; j < ATTPC_NUM_TB; j += TR_THREADS) resp[j] = tr.response[j];
+  if (t == 0) kept_run = 0u;
+  block_sync();
+  for (int64_t r = lo + t; r < hi; r += TR_THREADS) {
+    const double padf = points[3 * r], tb = points[3 * r + 1];
+    if (trace_row_ok(padf, tb)) atomicAdd(&cursor[(int)padf], 1u);
+  }
+  block_sync();
+  {  // exclusive prefix over the pads (rows and hit pads): 20 consecutive pads per thread, wave scan, wave offsets
+    uint32_t rows = 0u, hits = 0u;
+    for (int k = 0; k < TR_PADS_PER_THREAD; ++k) {
+      const uint32_t c = cursor[t * TR_PADS_PER_THREAD + k];
+      rows += c;
+      hits += c ? 1u : 0u;
+    }
+    uint32_t rows_incl = rows, hits_incl = hits;
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t ur = __shfl_up(rows_incl, off), uh = __shfl_up(hits_incl, off);
+      rows_incl += lane >= off ? ur : 0u;
+      hits_incl += lane >= off ? uh : 0u;
+    }
+    if (lane == 63) {
+      wave_rows[wave] = rows_incl;
+      wave_hits[wave] = hits_incl;
+    }
+    block_sync();
+    uint32_t run = rows_incl - rows, hrun = hits_incl - hits;
+    for (int w = 0; w < wave; ++w) {
+      run += wave_rows[w];
+      hrun += wave_hits[w];
+    }
+    for (int k = 0; k < TR_PADS_PER_THREAD; ++k) {
+      const int p = t * TR_PADS_PER_THREAD + k;
+      const uint32_t c = cursor[p];
+      if (c) {
+        sc.hit[lo + hrun] = (uint32_t)p;
+        sc.hit_start[lo + hrun] = run;
+        ++hrun;
+      }
+      cursor[p] = run;
+      run += c;
+    }
+    if (t == TR_THREADS - 1) {
+      n_hits = hrun;
+      n_placed = run;
+    }
+  }
+  block_sync();
+  for (int64_t r = lo + t; r < hi; r += TR_THREADS) {
+    const double padf = points[3 * r], tb = points[3 * r + 1];
+    if (trace_row_ok(padf, tb)) sc.row[lo + atomicAdd(&cursor[(int)padf], 1u)] = (uint32_t)(r - lo);
+  }
+  // workgroup scope is enough: the lists are written and read by this workgroup only (as spyral_write_kernel)
+  __threadfence_block();
+  block_sync();
+  const uint32_t H = n_hits, V = n_placed;
+  for (uint32_t k = (uint32_t)wave; k < H; k += TR_WAVES) {
+    const uint32_t start = sc.hit_start[lo + k], end = k + 1 < H ? sc.hit_start[lo + k + 1] : V;
+    const PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
+    if (lane == 0) sc.rank[lo + k] = (double)pt.max > tr.threshold ? 1 : 0;
+  }
+  __threadfence_block();
+  block_sync();
+  // verdicts -> ranks among the kept pads (ascending pad), TR_THREADS hit pads at a time
+  for (uint32_t base = 0; base < H; base += TR_THREADS) {
+    const uint32_t k = base + (uint32_t)t;
+    const bool keep = k < H && sc.rank[lo + k] != 0;
+    const unsigned long long m = __ballot(keep);
+    const uint32_t below = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_hits[wave] = (uint32_t)__popcll(m);
+    block_sync();
+    uint32_t before = kept_run;
+    for (int w = 0; w < wave; ++w) before += wave_hits[w];
+    if (k < H) sc.rank[lo + k] = keep ? (int32_t)(before + below) : -1;
+    block_sync();
+    if (t == 0) {
+      uint32_t all = 0u;
+      for (int w = 0; w < TR_WAVES; ++w) all += wave_hits[w];
+      kept_run += all;
+    }
+    block_sync();
+  }
+  if (t == 0) {
+    kept[e] = kept_run;
+    sc.info[2 * e] = H;
+    sc.info[2 * e + 1] = V;
+  }
+}
+
+__global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, uint64_t first_event,
+                                                                 const int64_t* __restrict__ event_start,
+                                                                 const double* __restrict__ points,
+                                                                 const int64_t* __restrict__ labels, TraceScratch sc,
+                                                                 const int64_t* __restrict__ kept_start,
+                                                                 int32_t* __restrict__ pads, int16_t* __restrict__ samples,
+                                                                 int64_t* __restrict__ out_labels,
+                                                                 unsigned long long* __restrict__ sums) {
+  __shared__ double resp[ATTPC_NUM_TB];
+  __shared__ double qtab[TR_WAVES][ATTPC_NUM_TB];
+  __shared__ unsigned long long wave_sum[TR_WAVES][2];
+  const uint32_t e = blockIdx.x;
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t out0 = kept_start[e];
+  if (kept_start[e + 1] == out0) return;  // uniform
+  const int64_t lo = event_start[e];
+  const uint32_t H = sc.info[2 * e], V = sc.info[2 * e + 1];
+  for (int j = t; j < ATTPC_NUM_TB; j += TR_THREADS) resp[j] = tr.response[j];
+  block_sync();
+  const unsigned long long event = first_event + e;
+  unsigned long long sample_sum = 0ull, pad_sum = 0ull;  // lane parts
+  for (uint32_t k = (uint32_t)wave; k < H; k += TR_WAVES) {
+    const int32_t rank = sc.rank[lo + k];
+    if (rank < 0) continue;  // uniform
+    const uint32_t start = sc.hit_start[lo + k], end = k + 1 < H ? sc.hit_start[lo + k + 1] : V;
+    const PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
+    const int64_t o = out0 + rank;
+    const uint32_t pad = sc.hit[lo + k];
+    int16_t* dst = samples + o * ATTPC_NUM_TB;
+    for (int s = 0; s < 8; ++s) {
+      const int j = lane + 64 * s;
+      dst[j] = (int16_t)pt.v[s];
+      sample_sum += (unsigned long long)(long long)pt.v[s] * (unsigned long long)(j + 1);
+    }
+    if (lane == 0) {
+      pads[o] = (int32_t)pad;
+      out_labels[o] = pt.label;
+      pad_sum += (event << 14) + (unsigned long long)pad;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    sample_sum += __shfl_xor(sample_sum, off);
+    pad_sum += __shfl_xor(pad_sum, off);
+  }
+  if (lane == 0) {
+    wave_sum[wave][0] = sample_sum;
+    wave_sum[wave][1] = pad_sum;
+  }
+  block_sync();
+  if (t < 2) {
+    unsigned long long v = 0ull;
+    for (int w = 0; w < TR_WAVES; ++w) v += wave_sum[w][t];
+    atomicAdd(sums + t, v);
+  }
+}
+
+void launch_trace_count(hipStream_t s, const TraceDev& tr, uint32_t n_events, const int64_t* event_start,
+                        const double* points, const int64_t* labels, TraceScratch sc, uint32_t* kept) {
+  hipLaunchKernelGGL(trace_count_kernel, dim3(n_events), dim3(TR_THREADS), 0, s, tr, event_start, points, labels, sc, kept);
+}
+void launch_trace_write(hipStream_t s, const TraceDev& tr, uint32_t n_events, uint64_t first_event,
+                        const int64_t* event_start, const double* points, const int64_t* labels, TraceScratch sc,
+                        const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
+                        unsigned long long* sums) {
+  hipLaunchKernelGGL(trace_write_kernel, dim3(n_events), dim3(TR_THREADS), 0, s, tr, first_event, event_start, points,
+                     labels, sc, kept_start, pads, samples, out_labels, sums);
+}
+
+}  // namespace attpc

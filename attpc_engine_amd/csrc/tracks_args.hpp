@@ -74,4 +74,27 @@ void launch_spyral_write(hipStream_t s, const SpyralDev& sp, uint32_t n_events, 
                          const int64_t* kept_start, const double* points, const int64_t* labels, double* rows,
                          int64_t* out_labels, uint32_t* sort_idx, double* sort_key, SpyralPacked* packed, int64_t* pack_flag);
 
+// digitised pad traces on device (traces.hip; the contract is in include/attpc_engine.h)
+struct TraceDev {
+  const double* response;  // [512]
+  double threshold;
+  int32_t offset;
+};
+// per-event working lists in global memory, ranges of the event's own cloud rows (rows lo .. hi of the chunk)
+struct TraceScratch {
+  uint32_t* row;        // [rows] the event's row numbers grouped by pad, pads ascending
+  uint32_t* hit;        // [rows] k-th hit pad of the event
+  uint32_t* hit_start;  // [rows] first entry of that pad's group in `row`
+  int32_t* rank;        // [rows] rank of that pad among the event's kept pads, -1 = dropped
+  uint32_t* info;       // [2 * events] hit pads, rows placed
+};
+// kept[e]: kept pad rows of event e (the count pass works out every trace, keeps the ranks in scratch)
+void launch_trace_count(hipStream_t s, const TraceDev& tr, uint32_t n_events, const int64_t* event_start,
+                        const double* points, const int64_t* labels, TraceScratch sc, uint32_t* kept);
+// the kept rows at kept_start[e] + rank; sums[0] += sample checksum, sums[1] += pad checksum (event = first_event + e)
+void launch_trace_write(hipStream_t s, const TraceDev& tr, uint32_t n_events, uint64_t first_event,
+                        const int64_t* event_start, const double* points, const int64_t* labels, TraceScratch sc,
+                        const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
+                        unsigned long long* sums);
+
 }  // namespace attpc

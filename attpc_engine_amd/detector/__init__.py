@@ -2,12 +2,14 @@
 ``detector/__init__.py:13-21``) plus the batch entry points, device backed."""
 from . import parameters as _parameters
 from . import simulator as _simulator
+from . import traces as _traces
 from . import writer as _writer
 
 _EXPORTS = {
     _parameters: ("Config", "DetectorParams", "ElectronicsParams", "PadParams"),
     _simulator: ("run_simulation", "simulate", "simulate_batch"),
-    _writer: ("SimulationWriter", "SpyralWriter"),
+    _traces: ("configure_traces", "simulate_batch_traces", "clouds_to_traces"),
+    _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter"),
 }
 __all__ = []
 for _module, _names in _EXPORTS.items():

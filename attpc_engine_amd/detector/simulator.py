@@ -184,7 +184,9 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     closed.  A writer that offers ``write_rows`` (SpyralWriter) receives its rows ready to store: the response
     scaling, row conversion, ADC threshold and z-sort it would do per event in ``write`` (writer.py:194-238) run on
     the device, fused behind the scatter, before anything crosses PCIe (``attpc_det_run_spyral``) -- the same
-    datasets as ``write`` produces, without one GPU round trip per event.  Any other SimulationWriter gets
+    datasets as ``write`` produces, without one GPU round trip per event.  A writer that offers ``write_traces``
+    (TraceWriter) receives every non-empty event's pad traces, made on the device (``attpc_det_run_traces``).  Any other
+    SimulationWriter gets
     ``write(points, labels, config, event)`` exactly as in the reference."""
     from ..io import KinematicsFileReader
 
@@ -199,9 +201,23 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     rng = default_rng(seed)
     run_seed = int(rng.integers(0, 1 << 63))
     fused = callable(getattr(writer, "write_rows", None))
+    traces = callable(getattr(writer, "write_traces", None))
     for start in range(0, n_events, batch_size):
         stop = min(n_events, start + batch_size)
         vertices, momenta = reader.read(start, stop)
+        if traces:  # TraceWriter: the pad traces are made on the device behind the scatter (attpc_det_run_traces)
+            from .traces import simulate_batch_traces
+
+            offsets, pads, samples, labels, raw_points, _ = simulate_batch_traces(
+                momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim, first_event=start,
+                response=writer.response, threshold=writer.threshold, offset=writer.offset,
+            )
+            for i in range(stop - start):
+                if raw_points[i] == 0:
+                    continue  # simulator.py:204-205
+                lo, hi = offsets[i], offsets[i + 1]
+                writer.write_traces(pads[lo:hi], samples[lo:hi], labels[lo:hi], start + i)
+            continue
         if fused:
             offsets, rows, labels, raw_points, _ = simulate_batch_spyral(
                 momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim,

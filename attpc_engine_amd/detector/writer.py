@@ -57,26 +57,27 @@ def convert_to_spyral(points: np.ndarray, window_edge: int, mm_edge: int, length
 class _NpzRunFile:
     """Fallback container when h5py is absent: same dataset names/attrs, one npz per run."""
 
-    def __init__(self, path: Path):
+    def __init__(self, path: Path, group: str = "cloud"):
         self.path = path.with_suffix(".npz")
+        self.group = group
         self.arrays: dict[str, np.ndarray] = {}
 
     def create_dataset(self, name: str, data: np.ndarray, attrs: dict | None = None) -> None:
-        self.arrays[f"cloud/{name}"] = np.asarray(data)
+        self.arrays[f"{self.group}/{name}"] = np.asarray(data)
         for key, value in (attrs or {}).items():
-            self.arrays[f"cloud/{name}@{key}"] = np.asarray(value)
+            self.arrays[f"{self.group}/{name}@{key}"] = np.asarray(value)
 
     def set_attr(self, key: str, value) -> None:
-        self.arrays[f"cloud@{key}"] = np.asarray(value)
+        self.arrays[f"{self.group}@{key}"] = np.asarray(value)
 
     def close(self) -> None:
         np.savez_compressed(self.path, **self.arrays)
 
 
 class _H5RunFile:
-    def __init__(self, path: Path, h5):
+    def __init__(self, path: Path, h5, group: str = "cloud"):
         self.file = h5.File(path, "w")
-        self.group = self.file.create_group("cloud")
+        self.group = self.file.create_group(group)
 
     def create_dataset(self, name: str, data: np.ndarray, attrs: dict | None = None) -> None:
         dset = self.group.create_dataset(name, data=data)
@@ -148,6 +149,77 @@ class SpyralWriter:
              "ic_multiplicity": -1.0, "ic_integral": -1.0, "ic_centroid": -1.0},
         )
         self.file.create_dataset(f"labels_{event_number}", labels)
+        self.last_event = event_number
+        self.events_written += 1
+
+    def set_number_of_events(self) -> None:
+        self.file.set_attr("min_event", self.starting_event)
+        self.file.set_attr("max_event", self.last_event)
+
+    def get_directory_name(self) -> Path:
+        return self.directory_path
+
+    def close(self) -> None:
+        self.set_number_of_events()
+        self.file.close()
+
+
+class TraceWriter:
+    """Digitised GET pad traces (EXTENSION: the reference writes point clouds only) split into files of
+    ``max_events_per_file`` events, with SpyralWriter's roll-over and ``.npz`` fallback: ``run_%04d.h5`` / group
+    ``trace`` / per event ``trace_{event}`` [R,512] int16, ``pads_{event}`` [R] int32, ``labels_{event}`` [R] int64
+    (attrs orig_run, orig_event), and min_event / max_event on the group.  ``response`` (default get_response(config)),
+    ``threshold`` (default the ADC threshold) and ``offset`` are those of the trace contract, include/attpc_engine.h."""
+
+    def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
+                 first_run_number: int = 0, npz_fallback: bool = True, response: np.ndarray | None = None,
+                 threshold: float | None = None, offset: int = 0):
+        from .traces import trace_settings
+
+        self.directory_path = Path(directory_path)
+        self.npz_fallback = npz_fallback
+        self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
+        self.response = self.response.copy()
+        self.max_events_per_file = max_events_per_file
+        self.run_number = first_run_number
+        self.starting_event = 0
+        self.last_event = 0
+        self.events_written = 0
+        self.file = self._open(self.run_number)
+
+    def _open(self, run_number: int):
+        from ..io import hdf5_or_fallback
+
+        path = self.directory_path / f"run_{run_number:04d}.h5"
+        h5py = hdf5_or_fallback(path, self.npz_fallback)
+        return _H5RunFile(path, h5py, "trace") if h5py is not None else _NpzRunFile(path, "trace")
+
+    def create_next_file(self) -> None:
+        self.run_number += 1
+        self.file = self._open(self.run_number)
+
+    def write(self, data: np.ndarray, labels: np.ndarray, config: Config, event_number: int) -> None:
+        """One event's cloud [P,3] -> its traces on the device (``clouds_to_traces``) -> datasets."""
+        from .traces import clouds_to_traces, configure_traces
+
+        ctx = _abi.default_context()
+        configure_traces(config, ctx, self.response, self.threshold, self.offset)
+        data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
+        _, pads, samples, out_labels, _ = clouds_to_traces(np.array([0, len(data)], dtype=np.int64), data, labels, ctx)
+        self.write_traces(pads, samples, out_labels, event_number)
+
+    def write_traces(self, pads: np.ndarray, samples: np.ndarray, labels: np.ndarray, event_number: int) -> None:
+        """One event's kept pad rows, as the device makes them (``Engine.run_traces``, ``simulate_batch_traces``):
+        file roll-over, datasets and attributes."""
+        if self.events_written == self.max_events_per_file:
+            self.close()
+            self.create_next_file()
+            self.starting_event = event_number
+            self.events_written = 0
+        self.file.create_dataset(f"trace_{event_number}", np.asarray(samples, dtype=np.int16).reshape(-1, _abi.NUM_TB),
+                                 {"orig_run": self.run_number, "orig_event": event_number})
+        self.file.create_dataset(f"pads_{event_number}", np.asarray(pads, dtype=np.int32))
+        self.file.create_dataset(f"labels_{event_number}", np.asarray(labels, dtype=np.int64))
         self.last_event = event_number
         self.events_written += 1
 

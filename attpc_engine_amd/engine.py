@@ -145,6 +145,52 @@ class Engine:
         return {"vertex": vertex, "p4": p4, "status": status, "offsets": offsets, "rows": rows[:total],
                 "labels": labels[:total], "event_points": event_points, "stats": stats.as_dict()}
 
+    # ---------------------------------------------------------------- digitised pad traces on the device
+    def configure_traces(self, config=None, response=None, threshold=None, offset: int = 0) -> None:
+        """Upload the trace settings (include/attpc_engine.h): the GET response (default get_response(config)), the ADC
+        threshold (default ``ElectronicsParams.adc_threshold``; < 0 keeps every hit pad) and the sample offset (0 =
+        causal, argmax(response) = peak on the arrival bucket)."""
+        from .detector.traces import configure_traces
+
+        configure_traces(config or self.config, self.ctx, response, threshold, offset)
+        self._traces_configured = True
+
+    def run_traces(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
+                   capacity_per_event: int = 1024) -> dict:
+        """Fused kinematics + detector + the digitised pad traces of every event, made on the device before anything
+        crosses PCIe (``attpc_sim_run_traces``).  ``fetch=True``: offsets [n+1], pads [R] i32, samples [R,512] i16,
+        labels [R] i64 (``pinned``: page-locked arrays), event_points [n] = cloud rows before the suppression, and the
+        kinematics; ``fetch=False``: the traces stay on the device, only ``trace`` (n_rows and both checksums) and the
+        cloud's ``stats`` come back."""
+        from .detector.traces import TraceArrays, call_with_capacity
+
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
+        if not getattr(self, "_traces_configured", False):
+            self.configure_traces()
+        ctx = self.ctx
+        stats = _abi.RunStats()
+        if not fetch:
+            out = _abi.TraceOut()
+            ctx.check(ctx.lib.attpc_sim_run_traces(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
+                                                   None, None, None, out, stats), "attpc_sim_run_traces")
+            return {"stats": stats.as_dict(), "trace": {"n_rows": int(out.n_rows),
+                                                        "sample_checksum": int(out.sample_checksum),
+                                                        "pad_checksum": int(out.pad_checksum)}}
+        p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
+        vertex = np.empty((n_events, 3), dtype=np.float64)
+        status = np.empty(n_events, dtype=np.int32)
+
+        def call(out):
+            return ctx.lib.attpc_sim_run_traces(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
+                                                _abi.dptr(p4), _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32), out,
+                                                stats)
+
+        arrays = call_with_capacity(ctx, int(n_events), max(1024, int(capacity_per_event) * int(n_events)), call,
+                                    "attpc_sim_run_traces", ctx.pinned_empty if pinned else None)
+        offsets, pads, samples, labels = arrays.result()
+        return {"vertex": vertex, "p4": p4, "status": status, "offsets": offsets, "pads": pads, "samples": samples,
+                "labels": labels, "event_points": arrays.event_points, "stats": stats.as_dict(), "trace": arrays.sums()}
+
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
               batch_size: int = 65536, context: _abi.Context | None = None) -> None:
@@ -153,10 +199,24 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
     below the ADC threshold is still written, with 0 rows, and counts towards the file roll-over exactly
     as in run_simulation + SpyralWriter.write), in event order,
-    ``writer.write_rows(rows, labels, event_number, presorted=True)``, then ``close()``."""
+    ``writer.write_rows(rows, labels, event_number, presorted=True)``, then ``close()``.  A writer that offers
+    ``write_traces`` (TraceWriter) gets ``write_traces(pads, samples, labels, event_number)`` per such event instead,
+    the traces made on the device (``Engine.run_traces``)."""
     engine = Engine(pipeline, config, indices, context=context)
-    engine.configure_spyral(config)
     seed = pipeline.seed if seed is None else int(seed)
+    if callable(getattr(writer, "write_traces", None)):  # TraceWriter: the pad traces of every non-empty event
+        engine.configure_traces(config, writer.response, writer.threshold, writer.offset)
+        for start in range(0, n_events, batch_size):
+            n = min(batch_size, n_events - start)
+            res = engine.run_traces(n, seed=seed, first_event=start)
+            off, raw = res["offsets"], res["event_points"]
+            for i in range(n):
+                if raw[i] > 0:
+                    writer.write_traces(res["pads"][off[i]:off[i + 1]], res["samples"][off[i]:off[i + 1]],
+                                        res["labels"][off[i]:off[i + 1]], start + i)
+        writer.close()
+        return
+    engine.configure_spyral(config)
     for start in range(0, n_events, batch_size):
         n = min(batch_size, n_events - start)
         res = engine.run_spyral(n, seed=seed, first_event=start)

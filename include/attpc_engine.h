@@ -400,6 +400,65 @@ ATTPC_API int32_t attpc_det_run_spyral(attpc_ctx* ctx, uint64_t seed, uint64_t f
                                        const attpc_event_layout* layout, const double* p4, const double* vertex,
                                        attpc_cloud_out* out, attpc_run_stats* stats);
 
+/* ---- digitised GET pad traces (EXTENSION: the reference stops at point clouds, docs/user_guide/detector/index.md
+ * "Why Point clouds") ----
+ * The contract, for one event's cloud rows (pad p, jittered time bucket tau, electrons q, label l) as attpc_sim_run
+ * produces them, a response R[512] (default get_response(config), detector/response.py:8-32), an ADC threshold thr and
+ * an integer offset >= 0:
+ *   - t = floor(tau): the GET digitises whole buckets, the jitter plays no part.  Rows of one event have distinct (pad, t).
+ *   - for every pad p hit in the event and j in 0..511
+ *       A_p[j] = sum over the rows r of pad p with 0 <= j + offset - t_r < 512, in ascending t_r, of q_r * R[j + offset - t_r]
+ *     in f64 from +0.0, every product rounded and then added (no fused multiply-add); R is indexed by sample number,
+ *     as the reference's apply_response indexes its linspace(0, 512, 512) array.
+ *   - trace_p[j] = (int16) rint(min(A_p[j], 4095.0)), rint rounding half to even: the SUMMED signal saturates (pile-up on
+ *     one pad saturates as the electronics would; unlike the Spyral row's per-point clip, response.py:35-57).
+ *   - a pad row is kept iff max_j trace_p[j] > thr (strict, as writer.py:232); thr < 0 keeps every hit pad, all-zero
+ *     traces included.
+ *   - a kept row carries pad (i32), samples[512] (i16) and label (i64): the label of the pad's row with the largest q, the
+ *     smallest t on a tie.  Rows of an event come out in ascending pad, events in id order with CSR offsets.
+ *   - offset = 0 is the causal response (response sample k lands at bucket t + k); offset = argmax(R) puts the peak on the
+ *     arrival bucket.
+ * attpc_run_stats keeps its cloud meaning in every trace entry point (the counts and checksums attpc_sim_run reports for
+ * the same ids).  The id-range rules at the top apply; a pending attpc_sim_hint_next is dropped. */
+#define ATTPC_NUM_PADS 10240
+
+typedef struct attpc_trace_desc {
+  const double* response; /* [ATTPC_NUM_TB] ADC counts per electron by sample number */
+  double adc_threshold;   /* rows with max sample <= threshold are dropped; < 0 keeps every hit pad */
+  int32_t offset;         /* >= 0; sample j reads R[j + offset - t] */
+  int32_t reserved;
+} attpc_trace_desc;
+
+ATTPC_API int32_t attpc_trace_configure(attpc_ctx* ctx, const attpc_trace_desc* desc);
+
+/* Host output buffers of a trace run; any array may be NULL (that output then stays on the device). */
+typedef struct attpc_trace_out {
+  int64_t capacity;        /* rows available in pads / samples / labels */
+  int64_t* offsets;        /* [n_events + 1] CSR offsets of the kept rows */
+  int32_t* pads;           /* [capacity] */
+  int16_t* samples;        /* [capacity, ATTPC_NUM_TB] */
+  int64_t* labels;         /* [capacity] */
+  int64_t* event_points;   /* [n_events]: cloud rows of every event before the suppression (simulator.py:204-205) */
+  int64_t n_rows;          /* written: kept rows of the call (the capacity needed on ATTPC_E_CAPACITY) */
+  uint64_t sample_checksum; /* written: sum over rows, j of trace[j] * (j + 1) mod 2^64 */
+  uint64_t pad_checksum;   /* written: sum over rows of (event * 2^14 + pad) mod 2^64; event = the global event id
+                              (attpc_traces: the index of the event in the call) */
+} attpc_trace_out;
+
+/* attpc_sim_run, then the traces of every event on the device before anything crosses PCIe. */
+ATTPC_API int32_t attpc_sim_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                       const attpc_event_layout* layout, double* p4, double* vertex,
+                                       int32_t* kin_status, attpc_trace_out* out, attpc_run_stats* stats);
+/* attpc_det_run (kinematics from host p4 [n, n_rows, 4] / vertex [n, 3], the file-driven flow), then the traces. */
+ATTPC_API int32_t attpc_det_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                       const attpc_event_layout* layout, const double* p4, const double* vertex,
+                                       attpc_trace_out* out, attpc_run_stats* stats);
+/* Traces of any host cloud: offsets [n_events + 1] (nondecreasing), points [rows, 3] (pad, tau, electrons), labels
+ * [rows].  Every row needs an integer pad in [0, ATTPC_NUM_PADS), 0 <= tau < 512, finite electrons >= 0 and a (pad, t)
+ * of its own within the event, else ATTPC_E_INVALID. */
+ATTPC_API int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                               const int64_t* labels, attpc_trace_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,90 @@
+"""Rate of the digitised pad traces (attpc_sim_run_traces) on one GPU, for the headline workload (o16aa) and be10dp:
+device-resident events/s (the traces are written to HBM and stay there; only the checksums come back), and delivered
+events/s and GB/s into page-locked host arrays (pads, 1 KiB of samples and the label of every kept pad row).  Prints
+one JSON line per workload with kept trace rows and bytes per event.
+
+    python tools/trace_rate.py [--events N] [--deliver-events M] [--reps K] [--workloads o16aa,be10dp]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--events", type=int, default=262144, help="events per device-resident call")
+    ap.add_argument("--deliver-events", type=int, default=16384, help="events per delivered call")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--workloads", default="o16aa,be10dp")
+    args = ap.parse_args()
+
+    import numpy as np
+
+    import __graft_entry__ as entry
+
+    entry.build()
+    from attpc_engine_amd import _abi, workloads
+    from attpc_engine_amd.detector.traces import TraceArrays
+    from attpc_engine_amd.engine import Engine
+
+    ctx = _abi.Context(0)
+    for name in args.workloads.split(","):
+        pipeline, config, indices = workloads.WORKLOADS[name]()
+        eng = Engine(pipeline, config, indices, context=ctx)
+        eng.configure_traces(config)
+        lib, seed = ctx.lib, 1
+
+        def resident(first):
+            out, stats = _abi.TraceOut(), _abi.RunStats()
+            ctx.check(lib.attpc_sim_run_traces(ctx.handle, seed, first, args.events, eng.layout, None, None, None, out,
+                                               stats), "attpc_sim_run_traces")
+            return out, stats
+
+        resident(0)  # warm-up: buffers settle
+        times, rows = [], 0
+        for rep in range(args.reps):
+            t0 = time.perf_counter()
+            out, stats = resident((rep + 1) * args.events)
+            times.append(time.perf_counter() - t0)
+            rows += out.n_rows
+        t_res = float(np.median(times))
+        rows_per_event = rows / (args.reps * args.events)
+
+        n = args.deliver_events
+        cap = int(rows_per_event * n * 1.3) + 4096
+        arrays = TraceArrays(n, cap, ctx.pinned_empty)
+        stats = _abi.RunStats()
+
+        def delivered(first):
+            rc = lib.attpc_sim_run_traces(ctx.handle, seed, first, n, eng.layout, None, None, None, arrays.out, stats)
+            ctx.check(rc, "attpc_sim_run_traces")
+            return int(arrays.out.n_rows)
+
+        delivered(0)
+        d_times, d_rows = [], 0
+        for rep in range(args.reps):
+            t0 = time.perf_counter()
+            d_rows += delivered((rep + 1) * n)
+            d_times.append(time.perf_counter() - t0)
+        t_del = float(np.median(d_times))
+        row_bytes = 512 * 2 + 4 + 8
+        d_bytes = d_rows / args.reps * row_bytes + 16 * n  # rows + offsets / event points
+        print(json.dumps({
+            "workload": name, "resident_events": args.events, "resident_events_per_s": args.events / t_res,
+            "resident_s": times, "trace_rows_per_event": rows_per_event,
+            "bytes_written_per_event": rows_per_event * row_bytes,
+            "cloud_rows_per_event": stats.n_points / n,
+            "delivered_events": n, "delivered_events_per_s": n / t_del, "delivered_GB_per_s": d_bytes / t_del / 1e9,
+            "delivered_s": d_times, "device_bytes": int(stats.device_bytes)}), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
