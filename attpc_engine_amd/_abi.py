@@ -22,6 +22,7 @@ DEDX_SUB = 32
 DEDX_NODES = (DEDX_EMAX - DEDX_EMIN) * DEDX_SUB + 1
 NUM_TB = 512
 NUM_PADS = 10240
+MAX_NOISE_LEVELS = 512
 TIME_SAMPLES = 10001
 LONG_STEPS = 5
 
@@ -118,6 +119,13 @@ class TraceDesc(C.Structure):
     _fields_ = [("response", _dp), ("adc_threshold", C.c_double), ("offset", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TraceNoiseDesc(C.Structure):
+    _fields_ = [
+        ("cdf", C.POINTER(C.c_uint32)), ("n_levels", C.c_int32), ("min_level", C.c_int32),
+        ("pedestals", C.POINTER(C.c_int16)), ("stream", C.c_uint32), ("reserved", C.c_int32),
+    ]
+
+
 class TraceOut(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64),
@@ -206,6 +214,7 @@ EXPORTED_SYMBOLS = (
     "attpc_set_option", "attpc_host_alloc", "attpc_host_free", "attpc_det_scatter", "attpc_unpack_rows",
     "attpc_unpack_spyral_rows", "attpc_det_run_spyral", "attpc_sim_hint_next", "attpc_unpack_rows8",
     "attpc_trace_configure", "attpc_sim_run_traces", "attpc_det_run_traces", "attpc_traces",
+    "attpc_trace_configure_noise", "attpc_traces_at",
 )
 
 _lib = None
@@ -271,6 +280,9 @@ def load_library() -> C.CDLL:
         C.POINTER(TraceOut), C.POINTER(RunStats),
     ]
     lib.attpc_traces.argtypes = [ctxp, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(TraceOut)]
+    lib.attpc_trace_configure_noise.argtypes = [ctxp, C.POINTER(TraceNoiseDesc)]
+    lib.attpc_traces_at.argtypes = [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64), _dp,
+                                    C.POINTER(C.c_int64), C.POINTER(TraceOut)]
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -166,6 +166,9 @@ struct attpc_ctx {
   bool trace_ready = false;
   TraceDev trace{};
   std::vector<void*> trace_allocs;
+  bool noise_on = false;           // attpc_trace_configure_noise: noise and / or pedestals on (the NOISE kernels)
+  TraceNoiseDev noise{};
+  std::vector<void*> noise_allocs;
   DevBuf trace_sums;               // [2] sample / pad checksums of the trace run in progress
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
   std::vector<void*> spyral_allocs;
@@ -788,16 +791,20 @@ TraceScratch trace_scratch(AsmSet& as, size_t cap) {
   return sc;
 }
 
+// The noise of the trace kernels: nullptr = the noiseless kernels.
+const TraceNoiseDev* trace_noise(const attpc_ctx* ctx) { return ctx->noise_on ? &ctx->noise : nullptr; }
+
 // Trace count pass of the n events whose event-ordered cloud is in `as` (ev_start / points / labels, `cap` rows at
-// most), the scan of the kept rows and the copy of their CSR offsets to as.h_start, on S.
-int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap) {
+// most; global ids first_event .. first_event + n - 1), the scan of the kept rows and the copy of their CSR offsets to
+// as.h_start, on S.
+int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap, uint64_t seed, uint64_t first_event) {
   int32_t rc;
   if ((rc = ensure(ctx, as.kept, std::max<size_t>(n, 1) * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, as.kept_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
   if ((rc = ensure(ctx, as.tr_scratch, std::max<size_t>(cap, 1) * 4 * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, as.tr_info, std::max<size_t>(n, 1) * 2 * sizeof(uint32_t)))) return rc;
   if (n) {
-    launch_trace_count(ctx->stream, ctx->trace, n, static_cast<const int64_t*>(as.ev_start.p),
+    launch_trace_count(ctx->stream, ctx->trace, trace_noise(ctx), seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
                        static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p),
                        trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t))), static_cast<uint32_t*>(as.kept.p));
     HIP_TRY(ctx, hipGetLastError());
@@ -812,14 +819,14 @@ int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap) 
 
 // The counted chunk in `as` has `total` kept rows (as.h_start[n], read by the host): size the trace outputs, queue the
 // write pass on S (checksums into ctx->trace_sums) and record as.traced behind it.
-int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t total, uint64_t first_event) {
+int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t total, uint64_t seed, uint64_t first_event) {
   int32_t rc;
   if (total > 0) {
     if ((size_t)total > as.tr_cap) as.tr_cap = (size_t)total + (size_t)total / 8;
     if ((rc = ensure(ctx, as.tr_pads, as.tr_cap * sizeof(int32_t)))) return rc;
     if ((rc = ensure(ctx, as.tr_samples, as.tr_cap * ATTPC_NUM_TB * sizeof(int16_t)))) return rc;
     if ((rc = ensure(ctx, as.tr_labels, as.tr_cap * sizeof(int64_t)))) return rc;
-    launch_trace_write(ctx->stream, ctx->trace, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
+    launch_trace_write(ctx->stream, ctx->trace, trace_noise(ctx), seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
                        static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p),
                        trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t))),
                        static_cast<const int64_t*>(as.kept_start.p), static_cast<int32_t*>(as.tr_pads.p),
@@ -853,8 +860,9 @@ int32_t copy_traces(attpc_ctx* ctx, AsmSet& as, int64_t total, int64_t base, con
 // kept-row counts, their scan and the converted, thresholded, z-sorted rows; for traces the count pass and the scan
 // of the kept pad rows (the write pass follows once the host knows their number, deliver_traces).  The row totals and
 // the offsets are copied to pinned memory; as.ready is recorded at the end.  `rows_bound` >= the rows the
-// launch can have produced (the reservation capacity).
-int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMode mode) {
+// launch can have produced (the reservation capacity).  `seed` / `first_global`: the run's seed and the chunk's first
+// global event id (the noise of the traces).
+int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMode mode, uint64_t seed, uint64_t first_global) {
   const bool spyral = mode == OutMode::spyral;
   int32_t rc;
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, as.copied, 0));  // the set's previous contents have left
@@ -876,7 +884,7 @@ int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMo
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(as.h_ev_rows, ctx->ev_rows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   if (mode == OutMode::traces) {
-    if ((rc = enqueue_trace_count(ctx, as, n, cap))) return rc;
+    if ((rc = enqueue_trace_count(ctx, as, n, cap, seed, first_global))) return rc;
   } else if (!spyral) {
     HIP_TRY(ctx, hipMemcpyAsync(as.h_start, as.ev_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->opt_compact) {
@@ -989,7 +997,7 @@ struct UnpackDrain {
 
 // The counted traces of the chunk in `as` (as.ready has fired): write its offsets, queue the write pass and the copies.
 int32_t deliver_traces(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_first_local, attpc_trace_out* out,
-                       int64_t* row_cursor, bool* over_capacity, uint64_t chunk_first_global) {
+                       int64_t* row_cursor, bool* over_capacity, uint64_t seed, uint64_t chunk_first_global) {
   const int64_t base = *row_cursor;
   const int64_t total = as.h_start[n];
   if (out->offsets)
@@ -1001,7 +1009,7 @@ int32_t deliver_traces(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_fi
   const bool wanted = out->pads || out->samples || out->labels;
   if (wanted && *row_cursor > out->capacity) *over_capacity = true;
   int32_t rc;
-  if ((rc = enqueue_trace_write(ctx, as, n, total, chunk_first_global))) return rc;
+  if ((rc = enqueue_trace_write(ctx, as, n, total, seed, chunk_first_global))) return rc;
   return copy_traces(ctx, as, total, base, out, wanted && *row_cursor <= out->capacity);
 }
 
@@ -1213,14 +1221,14 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     for (int attempt = 0; r.overflow && attempt < 8; ++attempt) {
       int32_t rc2;
       if ((rc2 = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + c.e0, c.e0, c.n, min_rows, min_segs))) return rc2;
-      if ((rc2 = enqueue_assembly(ctx, c.slot, as, c.n, mode))) return rc2;
+      if ((rc2 = enqueue_assembly(ctx, c.slot, as, c.n, mode, seed, batch_first_global + c.e0))) return rc2;
       HIP_TRY(ctx, hipEventSynchronize(as.ready));
       read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
     }
     if (r.overflow) return fail(ctx, ATTPC_E_HIP, "point cloud did not fit after repeated buffer growth");
     accumulate(st, r);
     if (mode == OutMode::traces)
-      return deliver_traces(ctx, as, c.n, batch_first_local + c.e0, tout, row_cursor, over, batch_first_global + c.e0);
+      return deliver_traces(ctx, as, c.n, batch_first_local + c.e0, tout, row_cursor, over, seed, batch_first_global + c.e0);
     return deliver_chunk(ctx, as, c.n, batch_first_local + c.e0, mode, out, row_cursor, over, seed, batch_first_global + c.e0);
   };
   while (e0 < nb) {
@@ -1238,7 +1246,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     const int set = seq & 1;
     // an overflow of the chunk in flight is repaired inside complete(); queue this one behind it
     if ((rc = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + e0, e0, n, 0, 0))) return rc;
-    if ((rc = enqueue_assembly(ctx, c.slot, ctx->aset[set], n, mode))) return rc;
+    if ((rc = enqueue_assembly(ctx, c.slot, ctx->aset[set], n, mode, seed, batch_first_global + e0))) return rc;
     if ((rc = queue_next_once())) return rc;
     if (prev.slot >= 0 && (rc = complete(prev, prev_set))) return rc;
     prev = c;
@@ -1455,6 +1463,7 @@ int32_t attpc_ctx_destroy(attpc_ctx* ctx) {
   free_all(ctx->det_allocs);
   free_all(ctx->spyral_allocs);
   free_all(ctx->trace_allocs);
+  free_all(ctx->noise_allocs);
   std::vector<DevBuf*> bufs = {&ctx->points, &ctx->labels, &ctx->segments, &ctx->ev_rows, &ctx->lone_list, &ctx->lone_chg,
                                &ctx->lone_mask, &ctx->out_ctrl, &ctx->merge_scratch,
                                &ctx->sort_idx, &ctx->sort_key, &ctx->trace_sums};
@@ -1898,6 +1907,51 @@ int32_t attpc_trace_configure(attpc_ctx* ctx, const attpc_trace_desc* d) {
   return ATTPC_OK;
 }
 
+int32_t attpc_trace_configure_noise(attpc_ctx* ctx, const attpc_trace_noise_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d) {
+    if (d->n_levels < 0 || d->n_levels > ATTPC_MAX_NOISE_LEVELS)
+      return fail(ctx, ATTPC_E_INVALID, "noise table of %d levels: 0 .. %d", d->n_levels, ATTPC_MAX_NOISE_LEVELS);
+    if (d->min_level < -4095 || d->min_level > 4095)
+      return fail(ctx, ATTPC_E_INVALID, "noise min_level %d outside -4095 .. 4095", d->min_level);
+    if (d->n_levels > 1 && !d->cdf) return fail(ctx, ATTPC_E_INVALID, "noise table of %d levels without a cdf", d->n_levels);
+    for (int k = 1; k < d->n_levels - 1; ++k)
+      if (d->cdf[k] < d->cdf[k - 1]) return fail(ctx, ATTPC_E_INVALID, "noise cdf decreases at entry %d", k);
+    if (d->pedestals)
+      for (int p = 0; p < ATTPC_NUM_PADS; ++p)
+        if (d->pedestals[p] < 0 || d->pedestals[p] > 4095)
+          return fail(ctx, ATTPC_E_INVALID, "pedestal of pad %d is %d, outside 0 .. 4095", p, (int)d->pedestals[p]);
+    if (d->stream >= 0x80000000u) return fail(ctx, ATTPC_E_INVALID, "noise stream %u >= 2^31", d->stream);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  free_all(ctx->noise_allocs);
+  ctx->noise_on = false;
+  ctx->noise = TraceNoiseDev{};
+  if (!d || (d->n_levels == 0 && !d->pedestals)) return ATTPC_OK;  // the noiseless contract
+  // the cdf padded to the full table (the kernels copy all of it to LDS) and the guide: the search for u starts at
+  // #{k : cdf[k] <= (u >> 24) << 24}
+  const int n_cdf = std::max(d->n_levels - 1, 0);
+  std::vector<uint32_t> cdf(ATTPC_MAX_NOISE_LEVELS, 0xFFFFFFFFu);
+  for (int k = 0; k < n_cdf; ++k) cdf[k] = d->cdf[k];
+  std::vector<uint16_t> guide(256);
+  for (int b = 0, k = 0; b < 256; ++b) {
+    while (k < n_cdf && cdf[k] <= (uint32_t)b << 24) ++k;
+    guide[b] = (uint16_t)k;
+  }
+  TraceNoiseDev nz{};
+  int32_t rc;
+  if ((rc = upload(ctx, ctx->noise_allocs, cdf.data(), cdf.size(), &nz.cdf))) return rc;
+  if ((rc = upload(ctx, ctx->noise_allocs, guide.data(), guide.size(), &nz.guide))) return rc;
+  if (d->pedestals && (rc = upload(ctx, ctx->noise_allocs, d->pedestals, (size_t)ATTPC_NUM_PADS, &nz.pedestals))) return rc;
+  nz.n_levels = d->n_levels;
+  nz.min_level = d->min_level;
+  nz.domain = DOMAIN_TRACE_NOISE | d->stream;
+  ctx->noise = nz;
+  ctx->noise_on = true;
+  return ATTPC_OK;
+}
+
 int32_t attpc_sim_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                              const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
                              attpc_trace_out* out, attpc_run_stats* stats) {
@@ -1924,8 +1978,14 @@ int32_t attpc_det_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t first_event
 
 int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points, const int64_t* labels,
                      attpc_trace_out* out) {
+  return attpc_traces_at(ctx, 0, 0, n_events, offsets, points, labels, out);
+}
+
+int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
+                        const double* points, const int64_t* labels, attpc_trace_out* out) {
   if (!ctx || !out || n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
   if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_traces takes at most 2^31 - 1 events per call");
+  if (validate_id_range(ctx, first_event, (uint64_t)n_events)) return ATTPC_E_INVALID;
   if (!ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
   const uint32_t n = (uint32_t)n_events;
   const int64_t first = n ? offsets[0] : 0;
@@ -1972,7 +2032,7 @@ int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, c
     HIP_TRY(ctx, hipMemcpyAsync(as.labels.p, labels + first, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
   }
   HIP_TRY(ctx, hipMemsetAsync(ctx->trace_sums.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
-  if ((rc = enqueue_trace_count(ctx, as, n, cap))) return rc;
+  if ((rc = enqueue_trace_count(ctx, as, n, cap, seed, first_event))) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the copies above read pageable memory: nothing of it stays in flight)
   const int64_t total = as.h_start[n];
   if (out->offsets)
@@ -1981,7 +2041,7 @@ int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, c
     for (uint32_t e = 0; e < n; ++e) out->event_points[e] = offsets[e + 1] - offsets[e];
   const bool wanted = out->pads || out->samples || out->labels;
   const bool fits = !wanted || total <= out->capacity;
-  if ((rc = enqueue_trace_write(ctx, as, n, total, 0))) return rc;
+  if ((rc = enqueue_trace_write(ctx, as, n, total, seed, first_event))) return rc;
   if ((rc = copy_traces(ctx, as, total, 0, out, fits))) return rc;
   unsigned long long sums[2] = {0ull, 0ull};
   HIP_TRY(ctx, hipMemcpyAsync(sums, ctx->trace_sums.p, sizeof sums, hipMemcpyDeviceToHost, ctx->stream));

@@ -14,6 +14,10 @@
 // terms it skips would add +0.0 to an accumulator that starts at +0.0 and never becomes -0.0.
 // Bound: the latency of the per-row LDS reads (the row's charge, then 8 ds_read_b64 of R per lane) at 16 waves per CU --
 // not LDS bandwidth, FP64 issue or HBM (profiles/r04_trace_rate.md).
+// Electronic noise and pedestals (attpc_trace_configure_noise): both kernels are templated on NOISE; the NOISE = false
+// instantiations are the noiseless code.  With NOISE, a pad's samples get its pedestal and one table-driven noise draw
+// each (add_noise), both passes draw the same numbers, and the count pass's verdict is taken above the pedestal.  The
+// noise table (2 KiB of cdf, 0.5 KiB of guide) sits in LDS: the count pass stays at two workgroups per CU.
 #include "tracks_args.hpp"
 
 namespace attpc {
@@ -103,16 +107,59 @@ __device__ __forceinline__ PadTrace pad_trace(const TraceDev& tr, const double* 
   return out;
 }
 
+// The noise and the pedestal of one pad (include/attpc_engine.h): sample j = lane + 64 s takes word s % 4 of Philox
+// call h = s / 4, counter (event, pad * 128 + 2 * lane + h, domain), so a lane makes two calls per pad.  The level
+// index #{k : cdf[k] <= u} starts at the guide entry of u's top byte and walks the few cdf entries inside that byte.
+// Afterwards pt.max = max_j (trace_p[j] - ped_p), the quantity the threshold is taken on.
+__device__ __forceinline__ void add_noise(PadTrace& pt, const TraceNoiseDev& nz, const uint32_t* cdf,
+                                          const uint16_t* guide, uint64_t seed, uint64_t event, uint32_t pad, int lane) {
+  const int ped = nz.pedestals ? (int)nz.pedestals[pad] : 0;
+  int n[8];
+  for (int s = 0; s < 8; ++s) n[s] = 0;
+  if (nz.n_levels > 0) {  // uniform
+    const int n_cdf = nz.n_levels - 1;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      uint32_t u[4];
+      philox4x32<10>((uint32_t)event, (uint32_t)(event >> 32), pad * 128u + 2u * (uint32_t)lane + (uint32_t)h, nz.domain,
+                     (uint32_t)seed, (uint32_t)(seed >> 32), u);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        int i = guide[u[w] >> 24];
+        while (i < n_cdf && cdf[i] <= u[w]) ++i;
+        n[4 * h + w] = nz.min_level + i;
+      }
+    }
+  }
+  int m = -4096;  // below any trace_p[j] - ped_p (>= -4095)
+  for (int s = 0; s < 8; ++s) {
+    int v = pt.v[s] + ped + n[s];
+    v = v < 0 ? 0 : (v > 4095 ? 4095 : v);
+    pt.v[s] = v;
+    m = v - ped > m ? v - ped : m;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const int o = __shfl_xor(m, off);
+    m = o > m ? o : m;
+  }
+  pt.max = m;
+}
+
 __device__ __forceinline__ bool trace_row_ok(double padf, double tb) {
   return padf >= 0.0 && padf < (double)ATTPC_NUM_PADS && tb >= 0.0 && tb < (double)ATTPC_NUM_TB;
 }
 
-__global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, const int64_t* __restrict__ event_start,
+template <bool NOISE>
+__global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, TraceNoiseDev nz, uint64_t seed,
+                                                                 uint64_t first_event,
+                                                                 const int64_t* __restrict__ event_start,
                                                                  const double* __restrict__ points,
                                                                  const int64_t* __restrict__ labels, TraceScratch sc,
                                                                  uint32_t* __restrict__ kept) {
   __shared__ uint32_t cursor[ATTPC_NUM_PADS];  // counts, then the next free place of every pad's group
   __shared__ double resp[ATTPC_NUM_TB];
+  __shared__ uint32_t noise_cdf[ATTPC_MAX_NOISE_LEVELS];  // (NOISE only: the noiseless kernel never names them)
+  __shared__ uint16_t noise_guide[256];
   __shared__ double qtab[TR_WAVES][ATTPC_NUM_TB];
   __shared__ uint32_t wave_rows[TR_WAVES], wave_hits[TR_WAVES];
   __shared__ uint32_t n_hits, n_placed, kept_run;
@@ -129,6 +176,10 @@ __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, co
   }
   for (int p = t; p < ATTPC_NUM_PADS; p += TR_THREADS) cursor[p] = 0u;
   for (int j = t; j < ATTPC_NUM_TB; j += TR_THREADS) resp[j] = tr.response[j];
+  if constexpr (NOISE) {
+    for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += TR_THREADS) noise_cdf[i] = nz.cdf[i];
+    if (t < 256) noise_guide[t] = nz.guide[t];
+  }
   if (t == 0) kept_run = 0u;
   block_sync();
   for (int64_t r = lo + t; r < hi; r += TR_THREADS) {
@@ -186,7 +237,8 @@ __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, co
   const uint32_t H = n_hits, V = n_placed;
   for (uint32_t k = (uint32_t)wave; k < H; k += TR_WAVES) {
     const uint32_t start = sc.hit_start[lo + k], end = k + 1 < H ? sc.hit_start[lo + k + 1] : V;
-    const PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
+    PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
+    if constexpr (NOISE) add_noise(pt, nz, noise_cdf, noise_guide, seed, first_event + e, sc.hit[lo + k], lane);
     if (lane == 0) sc.rank[lo + k] = (double)pt.max > tr.threshold ? 1 : 0;
   }
   __threadfence_block();
@@ -217,7 +269,9 @@ __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, co
   }
 }
 
-__global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, uint64_t first_event,
+template <bool NOISE>
+__global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, TraceNoiseDev nz, uint64_t seed,
+                                                                 uint64_t first_event,
                                                                  const int64_t* __restrict__ event_start,
                                                                  const double* __restrict__ points,
                                                                  const int64_t* __restrict__ labels, TraceScratch sc,
@@ -228,6 +282,8 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, ui
   __shared__ double resp[ATTPC_NUM_TB];
   __shared__ double qtab[TR_WAVES][ATTPC_NUM_TB];
   __shared__ unsigned long long wave_sum[TR_WAVES][2];
+  __shared__ uint32_t noise_cdf[ATTPC_MAX_NOISE_LEVELS];  // (NOISE only)
+  __shared__ uint16_t noise_guide[256];
   const uint32_t e = blockIdx.x;
   const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
   const int64_t out0 = kept_start[e];
@@ -235,6 +291,10 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, ui
   const int64_t lo = event_start[e];
   const uint32_t H = sc.info[2 * e], V = sc.info[2 * e + 1];
   for (int j = t; j < ATTPC_NUM_TB; j += TR_THREADS) resp[j] = tr.response[j];
+  if constexpr (NOISE) {
+    for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += TR_THREADS) noise_cdf[i] = nz.cdf[i];
+    if (t < 256) noise_guide[t] = nz.guide[t];
+  }
   block_sync();
   const unsigned long long event = first_event + e;
   unsigned long long sample_sum = 0ull, pad_sum = 0ull;  // lane parts
@@ -242,9 +302,10 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, ui
     const int32_t rank = sc.rank[lo + k];
     if (rank < 0) continue;  // uniform
     const uint32_t start = sc.hit_start[lo + k], end = k + 1 < H ? sc.hit_start[lo + k + 1] : V;
-    const PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
+    PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
     const int64_t o = out0 + rank;
     const uint32_t pad = sc.hit[lo + k];
+    if constexpr (NOISE) add_noise(pt, nz, noise_cdf, noise_guide, seed, event, pad, lane);
     int16_t* dst = samples + o * ATTPC_NUM_TB;
     for (int s = 0; s < 8; ++s) {
       const int j = lane + 64 * s;
@@ -273,16 +334,26 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, ui
   }
 }
 
-void launch_trace_count(hipStream_t s, const TraceDev& tr, uint32_t n_events, const int64_t* event_start,
-                        const double* points, const int64_t* labels, TraceScratch sc, uint32_t* kept) {
-  hipLaunchKernelGGL(trace_count_kernel, dim3(n_events), dim3(TR_THREADS), 0, s, tr, event_start, points, labels, sc, kept);
+void launch_trace_count(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
+                        uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
+                        TraceScratch sc, uint32_t* kept) {
+  if (noise)
+    hipLaunchKernelGGL(trace_count_kernel<true>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, *noise, seed, first_event,
+                       event_start, points, labels, sc, kept);
+  else
+    hipLaunchKernelGGL(trace_count_kernel<false>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, TraceNoiseDev{}, seed,
+                       first_event, event_start, points, labels, sc, kept);
 }
-void launch_trace_write(hipStream_t s, const TraceDev& tr, uint32_t n_events, uint64_t first_event,
-                        const int64_t* event_start, const double* points, const int64_t* labels, TraceScratch sc,
-                        const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
+void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
+                        uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
+                        TraceScratch sc, const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
                         unsigned long long* sums) {
-  hipLaunchKernelGGL(trace_write_kernel, dim3(n_events), dim3(TR_THREADS), 0, s, tr, first_event, event_start, points,
-                     labels, sc, kept_start, pads, samples, out_labels, sums);
+  if (noise)
+    hipLaunchKernelGGL(trace_write_kernel<true>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, *noise, seed, first_event,
+                       event_start, points, labels, sc, kept_start, pads, samples, out_labels, sums);
+  else
+    hipLaunchKernelGGL(trace_write_kernel<false>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, TraceNoiseDev{}, seed,
+                       first_event, event_start, points, labels, sc, kept_start, pads, samples, out_labels, sums);
 }
 
 }  // namespace attpc

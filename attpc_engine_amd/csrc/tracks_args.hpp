@@ -88,13 +88,25 @@ struct TraceScratch {
   int32_t* rank;        // [rows] rank of that pad among the event's kept pads, -1 = dropped
   uint32_t* info;       // [2 * events] hit pads, rows placed
 };
-// kept[e]: kept pad rows of event e (the count pass works out every trace, keeps the ranks in scratch)
-void launch_trace_count(hipStream_t s, const TraceDev& tr, uint32_t n_events, const int64_t* event_start,
-                        const double* points, const int64_t* labels, TraceScratch sc, uint32_t* kept);
+// electronic noise and pedestals of the traces (attpc_trace_configure_noise); the noise of event e of a launch is keyed
+// on (seed, first_event + e)
+struct TraceNoiseDev {
+  const uint32_t* cdf;        // [n_levels - 1], padded to ATTPC_MAX_NOISE_LEVELS
+  const uint16_t* guide;      // [256]: #{k : cdf[k] <= b << 24}, where the search for u with u >> 24 == b starts
+  const int16_t* pedestals;   // [ATTPC_NUM_PADS] or nullptr (zeros)
+  int32_t n_levels;           // 0 = no noise draw (pedestals only)
+  int32_t min_level;
+  uint32_t domain;            // DOMAIN_TRACE_NOISE | stream
+};
+// kept[e]: kept pad rows of event e (the count pass works out every trace, keeps the ranks in scratch).
+// noise == nullptr: the noiseless kernels
+void launch_trace_count(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
+                        uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
+                        TraceScratch sc, uint32_t* kept);
 // the kept rows at kept_start[e] + rank; sums[0] += sample checksum, sums[1] += pad checksum (event = first_event + e)
-void launch_trace_write(hipStream_t s, const TraceDev& tr, uint32_t n_events, uint64_t first_event,
-                        const int64_t* event_start, const double* points, const int64_t* labels, TraceScratch sc,
-                        const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
+void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
+                        uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
+                        TraceScratch sc, const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
                         unsigned long long* sums);
 
 }  // namespace attpc

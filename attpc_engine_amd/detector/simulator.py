@@ -185,7 +185,8 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     scaling, row conversion, ADC threshold and z-sort it would do per event in ``write`` (writer.py:194-238) run on
     the device, fused behind the scatter, before anything crosses PCIe (``attpc_det_run_spyral``) -- the same
     datasets as ``write`` produces, without one GPU round trip per event.  A writer that offers ``write_traces``
-    (TraceWriter) receives every non-empty event's pad traces, made on the device (``attpc_det_run_traces``).  Any other
+    (TraceWriter) receives every non-empty event's pad traces, made on the device (``attpc_det_run_traces``, with the
+    writer's noise settings, the noise keyed on the run's seed and the global event ids).  Any other
     SimulationWriter gets
     ``write(points, labels, config, event)`` exactly as in the reference."""
     from ..io import KinematicsFileReader
@@ -210,7 +211,7 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
 
             offsets, pads, samples, labels, raw_points, _ = simulate_batch_traces(
                 momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim, first_event=start,
-                response=writer.response, threshold=writer.threshold, offset=writer.offset,
+                response=writer.response, threshold=writer.threshold, offset=writer.offset, **writer.noise_kwargs(),
             )
             for i in range(stop - start):
                 if raw_points[i] == 0:

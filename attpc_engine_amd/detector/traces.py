@@ -4,9 +4,16 @@ clouds").  The contract -- integer time bucket of every row, f64 sum of q * R in
 largest charge -- is written out in include/attpc_engine.h; ``tests/trace_reference.py`` restates it in numpy.
 
 ``simulate_batch_traces`` is ``simulate_batch`` with the traces made on the device behind the scatter
-(``attpc_det_run_traces``); ``clouds_to_traces`` turns any host cloud into traces (``attpc_traces``).
+(``attpc_det_run_traces``); ``clouds_to_traces`` turns any host cloud into traces (``attpc_traces_at``).
+
+Electronic noise and per-pad pedestals are opt-in (``noise_sigma`` or ``noise_table``, ``pedestals``, ``noise_stream``):
+every sample gets its pad's pedestal and one draw from a discrete noise table, a pure function of (seed, global event id,
+pad, sample), and the threshold is taken above the pedestal (include/attpc_engine.h; ``tests/trace_noise_reference.py``
+restates it).  ``gaussian_noise_table`` builds the table of a discretised Gaussian.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
@@ -27,16 +34,105 @@ def trace_settings(config: Config, response=None, threshold=None, offset: int = 
     return response, threshold, int(offset)
 
 
-def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold=None, offset: int = 0) -> None:
-    """Upload the response, ADC threshold and sample offset of the traces unless this ctx already holds the same ones
-    (decided on their content, as configure_spyral)."""
-    response, threshold, offset = trace_settings(config, response, threshold, offset)
-    token = (response.tobytes(), threshold, offset)
-    if getattr(ctx, "_trace_token", None) == token:
+def gaussian_noise_table(sigma: float) -> tuple[np.ndarray, int]:
+    """Noise table (cdf [2L] u32, min_level = -L) of rint(sigma * z), z standard normal, on the levels -L .. L with
+    L = ceil(8 sigma); the tails beyond are folded into the end levels.  The cdf entry below level m + 1 is
+    2^32 P(sigma z < m + 0.5), the lower half from ``math.erfc`` and the upper half its mirror image, so the level masses
+    are exactly symmetric (each end level keeps at least 2^-32).  ``sigma = 0``: no noise (an empty cdf, min_level 0).
+    ValueError for a negative or non-finite sigma and for L > 255 (more than ATTPC_MAX_NOISE_LEVELS levels)."""
+    sigma = float(sigma)
+    if not (sigma >= 0.0 and math.isfinite(sigma)):
+        raise ValueError(f"noise sigma must be finite and >= 0, got {sigma}")
+    if sigma == 0.0:
+        return np.zeros(0, dtype=np.uint32), 0
+    half = math.ceil(8.0 * sigma)
+    if 2 * half + 1 > _abi.MAX_NOISE_LEVELS:
+        raise ValueError(f"noise sigma {sigma} needs {2 * half + 1} levels, at most {_abi.MAX_NOISE_LEVELS}")
+    scale = sigma * math.sqrt(2.0)
+    lower = [max(1, round(0.5 * math.erfc((half - k - 0.5) / scale) * 2.0 ** 32)) for k in range(half)]
+    cdf = lower + [(1 << 32) - c for c in reversed(lower)]
+    return np.array(cdf, dtype=np.uint32), -half
+
+
+class NoiseSettings:
+    """The validated noise of a trace configuration: cdf [n_levels - 1] u32, min_level, n_levels (0 = no noise draw),
+    pedestals [ATTPC_NUM_PADS] i16 or None, stream, sigma (NaN for a custom table, 0 without noise)."""
+
+    def __init__(self, noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0):
+        if noise_table is not None and float(noise_sigma) != 0.0:
+            raise ValueError("give noise_sigma or noise_table, not both")
+        if noise_table is None:
+            cdf, min_level = gaussian_noise_table(noise_sigma)
+            self.sigma = float(noise_sigma)
+        else:
+            cdf, min_level = noise_table
+            self.sigma = math.nan
+        cdf = np.asarray(cdf)
+        if cdf.ndim != 1 or (cdf.size and (cdf.dtype.kind not in "iu" or cdf.min() < 0 or cdf.max() >= 1 << 32)):
+            raise ValueError("the noise cdf must be a 1-D array of integers in [0, 2^32)")
+        if cdf.size + 1 > _abi.MAX_NOISE_LEVELS:
+            raise ValueError(f"a noise table of {cdf.size + 1} levels: at most {_abi.MAX_NOISE_LEVELS}")
+        self.cdf = np.ascontiguousarray(cdf, dtype=np.uint32)
+        if np.any(np.diff(self.cdf.astype(np.int64)) < 0):
+            raise ValueError("the noise cdf decreases")
+        if int(min_level) != min_level or not -4095 <= int(min_level) <= 4095:
+            raise ValueError(f"noise min_level must be an integer in -4095 .. 4095, got {min_level}")
+        self.min_level = int(min_level)
+        self.n_levels = self.cdf.size + 1 if (self.cdf.size or self.min_level) else 0
+        if self.n_levels == 0:
+            self.sigma = 0.0
+        if pedestals is not None:
+            ped = np.broadcast_to(np.asarray(pedestals), (_abi.NUM_PADS,))
+            if ped.dtype.kind not in "iu" or ped.min() < 0 or ped.max() > 4095:
+                raise ValueError(f"pedestals must be {_abi.NUM_PADS} integers in 0 .. 4095")
+            pedestals = np.ascontiguousarray(ped, dtype=np.int16)
+        self.pedestals = pedestals
+        if int(noise_stream) != noise_stream or not 0 <= int(noise_stream) < 1 << 31:
+            raise ValueError(f"noise_stream must be an integer in [0, 2^31), got {noise_stream}")
+        self.stream = int(noise_stream)
+
+    @property
+    def on(self) -> bool:
+        """Anything added to the noiseless samples."""
+        return self.n_levels > 0 or self.pedestals is not None
+
+    def token(self):
+        if not self.on:
+            return None
+        return (self.cdf.tobytes(), self.min_level, self.n_levels, None if self.pedestals is None else
+                self.pedestals.tobytes(), self.stream)
+
+
+def configure_noise(ctx: _abi.Context, noise: NoiseSettings) -> None:
+    """``attpc_trace_configure_noise`` unless this ctx already holds the same noise (decided on its content)."""
+    token = noise.token()
+    if getattr(ctx, "_trace_noise_token", None) == token:
         return
-    desc = _abi.TraceDesc(_abi.dptr(response), threshold, offset, 0)
-    ctx.check(ctx.lib.attpc_trace_configure(ctx.handle, desc), "attpc_trace_configure")
-    ctx._trace_token = token
+    if token is None:
+        ctx.check(ctx.lib.attpc_trace_configure_noise(ctx.handle, None), "attpc_trace_configure_noise")
+    else:
+        desc = _abi.TraceNoiseDesc(_abi.iptr(noise.cdf, _abi.C.c_uint32), noise.n_levels, noise.min_level,
+                                   None if noise.pedestals is None else _abi.iptr(noise.pedestals, _abi.C.c_int16),
+                                   noise.stream, 0)
+        ctx.check(ctx.lib.attpc_trace_configure_noise(ctx.handle, desc), "attpc_trace_configure_noise")
+    ctx._trace_noise_token = token
+
+
+def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold=None, offset: int = 0,
+                     noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0) -> None:
+    """Upload the response, ADC threshold and sample offset of the traces, and their noise (off by default), unless this
+    ctx already holds the same ones (decided on their content, as configure_spyral).  ``noise_table``: (cdf, min_level)
+    instead of the Gaussian of ``noise_sigma``; ``pedestals``: [ATTPC_NUM_PADS] (or one value for every pad) in
+    0 .. 4095; ``noise_stream`` in [0, 2^31) draws another noise realisation.  Everything is validated before the first
+    call to the library."""
+    response, threshold, offset = trace_settings(config, response, threshold, offset)
+    noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
+    token = (response.tobytes(), threshold, offset)
+    if getattr(ctx, "_trace_token", None) != token:
+        desc = _abi.TraceDesc(_abi.dptr(response), threshold, offset, 0)
+        ctx.check(ctx.lib.attpc_trace_configure(ctx.handle, desc), "attpc_trace_configure")
+        ctx._trace_token = token
+    configure_noise(ctx, noise)
 
 
 class TraceArrays:
@@ -77,8 +173,10 @@ def call_with_capacity(ctx: _abi.Context, n_events: int, capacity: int, call, wh
 
 def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
                           seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
-                          response=None, threshold=None, offset: int = 0, capacity_per_event: int = 1024):
-    """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``) ->
+                          response=None, threshold=None, offset: int = 0, capacity_per_event: int = 1024,
+                          noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0):
+    """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``; the noise keyed on
+    ``seed`` and the global event ids) ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
     before the suppression, stats dict: the cloud's run statistics plus ``n_rows`` / ``sample_checksum`` /
     ``pad_checksum`` of the traces)."""
@@ -91,7 +189,7 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     seed, first_event, n = _abi.check_id_range(seed, first_event, n)
     keys = species_for(proton_numbers, mass_numbers, indices)
     configure_detector(config, keys, ctx)
-    configure_traces(config, ctx, response, threshold, offset)
+    configure_traces(config, ctx, response, threshold, offset, noise_sigma, noise_table, pedestals, noise_stream)
     layout = build_layout(proton_numbers, mass_numbers, indices, keys)
     stats = _abi.RunStats()
 
@@ -104,24 +202,27 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     return offsets, pads, samples, labels, arrays.event_points, {**stats.as_dict(), **arrays.sums()}
 
 
-def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context):
-    """Pad traces of any host cloud in CSR form (``attpc_traces``; ``ctx`` configured with ``configure_traces``):
+def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,
+                     first_event: int = 0):
+    """Pad traces of any host cloud in CSR form (``attpc_traces_at``; ``ctx`` configured with ``configure_traces``):
     offsets [n+1], points [P,3] (pad, time bucket, electrons), labels [P] ->
-    (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, {n_rows, sample_checksum, pad_checksum}),
-    the pad checksum taken over the events' indices 0 .. n-1."""
+    (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, {n_rows, sample_checksum, pad_checksum}).
+    Event i of the call is the global event ``first_event + i``: its noise is keyed on (seed, first_event + i), and the
+    pad checksum counts events from ``first_event``."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     labels = np.ascontiguousarray(labels, dtype=np.int64)
     n = len(offsets) - 1
     if n < 0:
         raise ValueError("offsets needs n_events + 1 entries")
+    seed, first_event, _ = _abi.check_id_range(seed, first_event, n)
     if len(points) != len(labels) or (n and offsets[-1] > len(points)):
         raise ValueError("points / labels do not hold the rows the offsets name")
 
     def call(out):
-        return ctx.lib.attpc_traces(ctx.handle, n, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(points),
-                                    _abi.iptr(labels, _abi.C.c_int64), out)
+        return ctx.lib.attpc_traces_at(ctx.handle, seed, first_event, n, _abi.iptr(offsets, _abi.C.c_int64),
+                                       _abi.dptr(points), _abi.iptr(labels, _abi.C.c_int64), out)
 
     rows = int(offsets[-1] - offsets[0]) if n else 0
-    arrays = call_with_capacity(ctx, n, max(16, rows), call, "attpc_traces")
+    arrays = call_with_capacity(ctx, n, max(16, rows), call, "attpc_traces_at")
     return (*arrays.result(), arrays.sums())

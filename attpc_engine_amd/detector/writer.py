@@ -169,17 +169,25 @@ class TraceWriter:
     ``max_events_per_file`` events, with SpyralWriter's roll-over and ``.npz`` fallback: ``run_%04d.h5`` / group
     ``trace`` / per event ``trace_{event}`` [R,512] int16, ``pads_{event}`` [R] int32, ``labels_{event}`` [R] int64
     (attrs orig_run, orig_event), and min_event / max_event on the group.  ``response`` (default get_response(config)),
-    ``threshold`` (default the ADC threshold) and ``offset`` are those of the trace contract, include/attpc_engine.h."""
+    ``threshold`` (default the ADC threshold) and ``offset`` are those of the trace contract, include/attpc_engine.h.
+    ``noise_sigma`` / ``noise_table``, ``pedestals`` and ``noise_stream`` add electronic noise and pedestals (off by
+    default; ``detector.traces.configure_traces``); ``noise_seed`` keys the noise of ``write`` (event ``event_number``),
+    the runs that call ``write_traces`` key it on their own seed.  Every file of a writer with noise records it on the
+    group: attributes noise_stream, noise_sigma (NaN for a custom table) and noise_min_level and the dataset noise_cdf;
+    the dataset pedestals when pedestals are given.  Without noise the files are those of the noiseless writer."""
 
     def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
                  first_run_number: int = 0, npz_fallback: bool = True, response: np.ndarray | None = None,
-                 threshold: float | None = None, offset: int = 0):
-        from .traces import trace_settings
+                 threshold: float | None = None, offset: int = 0, noise_sigma: float = 0.0, noise_table=None,
+                 pedestals=None, noise_stream: int = 0, noise_seed: int = 0):
+        from .traces import NoiseSettings, trace_settings
 
         self.directory_path = Path(directory_path)
         self.npz_fallback = npz_fallback
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.response = self.response.copy()
+        self.noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
+        self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
         self.max_events_per_file = max_events_per_file
         self.run_number = first_run_number
         self.starting_event = 0
@@ -192,7 +200,21 @@ class TraceWriter:
 
         path = self.directory_path / f"run_{run_number:04d}.h5"
         h5py = hdf5_or_fallback(path, self.npz_fallback)
-        return _H5RunFile(path, h5py, "trace") if h5py is not None else _NpzRunFile(path, "trace")
+        f = _H5RunFile(path, h5py, "trace") if h5py is not None else _NpzRunFile(path, "trace")
+        if self.noise.n_levels:
+            f.set_attr("noise_stream", self.noise.stream)
+            f.set_attr("noise_sigma", self.noise.sigma)
+            f.set_attr("noise_min_level", self.noise.min_level)
+            f.create_dataset("noise_cdf", self.noise.cdf)
+        if self.noise.pedestals is not None:
+            f.create_dataset("pedestals", self.noise.pedestals)
+        return f
+
+    def noise_kwargs(self) -> dict:
+        """The noise settings as ``configure_traces`` takes them."""
+        n = self.noise
+        return {"noise_table": (n.cdf, n.min_level) if n.n_levels else None, "pedestals": n.pedestals,
+                "noise_stream": n.stream}
 
     def create_next_file(self) -> None:
         self.run_number += 1
@@ -203,9 +225,10 @@ class TraceWriter:
         from .traces import clouds_to_traces, configure_traces
 
         ctx = _abi.default_context()
-        configure_traces(config, ctx, self.response, self.threshold, self.offset)
+        configure_traces(config, ctx, self.response, self.threshold, self.offset, **self.noise_kwargs())
         data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
-        _, pads, samples, out_labels, _ = clouds_to_traces(np.array([0, len(data)], dtype=np.int64), data, labels, ctx)
+        _, pads, samples, out_labels, _ = clouds_to_traces(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
+                                                           seed=self.noise_seed, first_event=event_number)
         self.write_traces(pads, samples, out_labels, event_number)
 
     def write_traces(self, pads: np.ndarray, samples: np.ndarray, labels: np.ndarray, event_number: int) -> None:

@@ -146,13 +146,18 @@ class Engine:
                 "labels": labels[:total], "event_points": event_points, "stats": stats.as_dict()}
 
     # ---------------------------------------------------------------- digitised pad traces on the device
-    def configure_traces(self, config=None, response=None, threshold=None, offset: int = 0) -> None:
+    def configure_traces(self, config=None, response=None, threshold=None, offset: int = 0, noise_sigma: float = 0.0,
+                         noise_table=None, pedestals=None, noise_stream: int = 0) -> None:
         """Upload the trace settings (include/attpc_engine.h): the GET response (default get_response(config)), the ADC
-        threshold (default ``ElectronicsParams.adc_threshold``; < 0 keeps every hit pad) and the sample offset (0 =
-        causal, argmax(response) = peak on the arrival bucket)."""
+        threshold (default ``ElectronicsParams.adc_threshold``; < 0 keeps every hit pad), the sample offset (0 =
+        causal, argmax(response) = peak on the arrival bucket) and the electronic noise and pedestals (off by default:
+        ``noise_sigma`` ADC counts of Gaussian noise or a ``noise_table`` (cdf, min_level), ``pedestals`` per pad,
+        ``noise_stream``; see ``detector.traces.configure_traces``).  The noise of ``run_traces`` is keyed on its seed
+        and the global event ids."""
         from .detector.traces import configure_traces
 
-        configure_traces(config or self.config, self.ctx, response, threshold, offset)
+        configure_traces(config or self.config, self.ctx, response, threshold, offset, noise_sigma, noise_table,
+                         pedestals, noise_stream)
         self._traces_configured = True
 
     def run_traces(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
@@ -201,11 +206,11 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     as in run_simulation + SpyralWriter.write), in event order,
     ``writer.write_rows(rows, labels, event_number, presorted=True)``, then ``close()``.  A writer that offers
     ``write_traces`` (TraceWriter) gets ``write_traces(pads, samples, labels, event_number)`` per such event instead,
-    the traces made on the device (``Engine.run_traces``)."""
+    the traces made on the device (``Engine.run_traces``) with the writer's noise settings."""
     engine = Engine(pipeline, config, indices, context=context)
     seed = pipeline.seed if seed is None else int(seed)
     if callable(getattr(writer, "write_traces", None)):  # TraceWriter: the pad traces of every non-empty event
-        engine.configure_traces(config, writer.response, writer.threshold, writer.offset)
+        engine.configure_traces(config, writer.response, writer.threshold, writer.offset, **writer.noise_kwargs())
         for start in range(0, n_events, batch_size):
             n = min(batch_size, n_events - start)
             res = engine.run_traces(n, seed=seed, first_event=start)

@@ -22,7 +22,8 @@
  *     batch / chunk / GPU count.
  *   - seeds are any u64.  A call's event ids first_event .. first_event + n_events - 1 must all lie in
  *     [0, 2^64): a range that would wrap past 2^64 is ATTPC_E_INVALID (attpc_kin_run, attpc_det_run,
- *     attpc_sim_run, their _spyral forms, attpc_det_tracks, attpc_det_scatter, attpc_sim_hint_next).
+ *     attpc_sim_run, their _spyral and _traces forms, attpc_det_tracks, attpc_det_scatter, attpc_sim_hint_next,
+ *     attpc_traces_at).
  *     Ids 2^40 apart share their jitter streams (the jitter counter holds event[39:0]) and nothing else.
  */
 #ifndef ATTPC_ENGINE_H
@@ -455,9 +456,50 @@ ATTPC_API int32_t attpc_det_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t f
                                        attpc_trace_out* out, attpc_run_stats* stats);
 /* Traces of any host cloud: offsets [n_events + 1] (nondecreasing), points [rows, 3] (pad, tau, electrons), labels
  * [rows].  Every row needs an integer pad in [0, ATTPC_NUM_PADS), 0 <= tau < 512, finite electrons >= 0 and a (pad, t)
- * of its own within the event, else ATTPC_E_INVALID. */
+ * of its own within the event, else ATTPC_E_INVALID.  = attpc_traces_at(ctx, 0, 0, ...). */
 ATTPC_API int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
                                const int64_t* labels, attpc_trace_out* out);
+
+/* ---- electronic noise and per-pad pedestals of the traces (opt-in; off, every trace output is the contract above) ----
+ * Notation: s_p[j] = rint(min(A_p[j], 4095)), the noiseless sample above (an integer in [0, 4095]); e the global event
+ * id; seed the run's 64-bit seed.
+ *   - noise table: n_levels in 0..ATTPC_MAX_NOISE_LEVELS, an integer min_level with |min_level| <= 4095 and
+ *     cdf[n_levels - 1], non-decreasing u32.  n_levels = 0 is no noise (n = 0).
+ *   - draw of sample j of pad p:
+ *       out = Philox4x32-10(counter = (e[31:0], e[63:32], p * 128 + 2 * (j mod 64) + (j div 256), 0x80000000 | stream),
+ *                           key = (seed[31:0], seed[63:32])),   u = out[(j div 64) mod 4]
+ *     (the lane holding samples j = lane + 64 s needs two Philox calls per pad).  The domain 0x80000000 | stream is
+ *     disjoint from every other draw's (0, 1 + row, 0x200 + entry, and the jitter's own generator); stream < 2^31
+ *     draws another noise realisation on the same physics.
+ *   - noise value n_p[j] = min_level + #{k : cdf[k] <= u}  (numpy.searchsorted(cdf, u, side="right")).
+ *   - sample trace_p[j] = min(max(s_p[j] + ped_p + n_p[j], 0), 4095); ped_p the pad's pedestal, an int16 in [0, 4095],
+ *     0 without a pedestal array.  Everything after s_p is integer arithmetic.
+ *   - a pad row is kept iff max_j (trace_p[j] - ped_p) > thr (strict; thr < 0 keeps every hit pad).
+ *   - unchanged: only pads with at least one cloud row get a trace (noise-only pads are not read out), the label rule,
+ *     row and event order, the CSR offsets, and the definitions of sample_checksum and pad_checksum (taken over the
+ *     noisy samples).
+ * With n_levels = 0 and no pedestals the result is the noiseless contract exactly (s_p[j] is already in [0, 4095]).
+ * attpc_sim_run_traces and attpc_det_run_traces key the noise on the run's seed and the global event ids. */
+#define ATTPC_MAX_NOISE_LEVELS 512
+
+typedef struct attpc_trace_noise_desc {
+  const uint32_t* cdf;       /* [n_levels - 1] */
+  int32_t n_levels;
+  int32_t min_level;
+  const int16_t* pedestals;  /* [ATTPC_NUM_PADS], NULL = zeros */
+  uint32_t stream;
+  int32_t reserved;
+} attpc_trace_noise_desc;
+
+/* desc == NULL turns noise and pedestals off.  Independent of attpc_trace_configure: neither call resets the other.
+ * ATTPC_E_INVALID for a decreasing cdf, more than ATTPC_MAX_NOISE_LEVELS levels, |min_level| > 4095, a pedestal
+ * outside [0, 4095] or stream >= 2^31. */
+ATTPC_API int32_t attpc_trace_configure_noise(attpc_ctx* ctx, const attpc_trace_noise_desc* desc);
+/* attpc_traces with the noise keyed on (seed, first_event + i) for the i-th event of the call; the pad checksum counts
+ * events from first_event.  The id-range rules at the top apply. */
+ATTPC_API int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events,
+                                  const int64_t* offsets, const double* points, const int64_t* labels,
+                                  attpc_trace_out* out);
 
 #ifdef __cplusplus
 }

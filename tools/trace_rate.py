@@ -1,9 +1,11 @@
 """Rate of the digitised pad traces (attpc_sim_run_traces) on one GPU, for the headline workload (o16aa) and be10dp:
 device-resident events/s (the traces are written to HBM and stay there; only the checksums come back), and delivered
 events/s and GB/s into page-locked host arrays (pads, 1 KiB of samples and the label of every kept pad row).  Prints
-one JSON line per workload with kept trace rows and bytes per event.
+one JSON line per workload with kept trace rows and bytes per event.  ``--noise-sigma S`` adds S ADC counts of
+Gaussian electronic noise, ``--pedestal P`` a pedestal of P counts on every pad (both off by default).
 
     python tools/trace_rate.py [--events N] [--deliver-events M] [--reps K] [--workloads o16aa,be10dp]
+                               [--noise-sigma S] [--pedestal P]
 """
 from __future__ import annotations
 
@@ -23,6 +25,8 @@ def main() -> None:
     ap.add_argument("--deliver-events", type=int, default=16384, help="events per delivered call")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--workloads", default="o16aa,be10dp")
+    ap.add_argument("--noise-sigma", type=float, default=0.0, help="Gaussian electronic noise, ADC counts (0 = off)")
+    ap.add_argument("--pedestal", type=int, default=None, help="pedestal of every pad, ADC counts (default none)")
     args = ap.parse_args()
 
     import numpy as np
@@ -38,7 +42,7 @@ def main() -> None:
     for name in args.workloads.split(","):
         pipeline, config, indices = workloads.WORKLOADS[name]()
         eng = Engine(pipeline, config, indices, context=ctx)
-        eng.configure_traces(config)
+        eng.configure_traces(config, noise_sigma=args.noise_sigma, pedestals=args.pedestal)
         lib, seed = ctx.lib, 1
 
         def resident(first):
@@ -77,7 +81,8 @@ def main() -> None:
         row_bytes = 512 * 2 + 4 + 8
         d_bytes = d_rows / args.reps * row_bytes + 16 * n  # rows + offsets / event points
         print(json.dumps({
-            "workload": name, "resident_events": args.events, "resident_events_per_s": args.events / t_res,
+            "workload": name, "noise_sigma": args.noise_sigma, "pedestal": args.pedestal,
+            "resident_events": args.events, "resident_events_per_s": args.events / t_res,
             "resident_s": times, "trace_rows_per_event": rows_per_event,
             "bytes_written_per_event": rows_per_event * row_bytes,
             "cloud_rows_per_event": stats.n_points / n,
