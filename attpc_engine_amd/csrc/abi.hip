@@ -29,6 +29,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "tracks_args.hpp"
@@ -50,15 +51,30 @@ constexpr int64_t DELIVER_CHUNK_ROWS = 96ll << 20;  // cloud rows of a chunk who
 constexpr int64_t TRACE_CHUNK_ROWS = 4ll << 20;     // kept pad rows of a chunk of a trace run (4 GiB of samples)
 constexpr uint64_t ARENA_BUDGET_BYTES = 24ull << 30;
 
-struct DevBuf {
+struct DevBuf {  // grow-only device buffer (ensure()), freed with its owner
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p), std::swap(bytes, o.bytes); return *this; }  // (o frees ours)
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+template <typename T>
+struct Pinned {  // page-locked host array of the library, grow-only (ensure_pinned), freed with its owner
+  T* p = nullptr;
+  size_t n = 0;
+  Pinned() = default;
+  Pinned(const Pinned&) = delete;
+  Pinned& operator=(const Pinned&) = delete;
+  ~Pinned() { if (p) (void)hipHostFree(p); }
+  T& operator[](size_t i) const { return p[i]; }
 };
 
 struct TrackSet {  // kinematics + tracks of one track batch
   DevBuf p4, vertex, status, attempts, arena, block_table, counts, n_steps, ctrl;
   size_t arena_blocks = 0;
-  uint32_t* h_ctrl = nullptr;  // pinned [16]
+  Pinned<uint32_t> h_ctrl;  // [16]
   hipEvent_t done = nullptr, k0 = nullptr, k1 = nullptr, t0 = nullptr, t1 = nullptr;
   bool timed_kin = false;
 };
@@ -70,16 +86,14 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   hipEvent_t traced = nullptr;  // the chunk's traces are written (the copies on C wait for it)
   size_t row_cap = 0;  // rows the row-sized buffers of the set are kept at (grown with headroom: a launch's row
                        // capacity follows the observed rows per event and moves by fractions of a percent)
-  int64_t* h_start = nullptr;  // pinned [h_start_len]: CSR offsets of the chunk (n + 1 entries)
-  size_t h_start_len = 0;
-  uint32_t* h_ev_rows = nullptr;  // pinned [h_start_len]: cloud rows of every event before any threshold
-  int64_t* h_total = nullptr;  // pinned [2]: [0] != 0: a row of the chunk does not fit the 16-byte transfer record
+  Pinned<int64_t> h_start;     // CSR offsets of the chunk (n + 1 entries)
+  Pinned<uint32_t> h_ev_rows;  // cloud rows of every event before any threshold
+  Pinned<int64_t> h_total;     // [2]: [0] != 0: a row of the chunk does not fit the 16-byte transfer record
   hipEvent_t ready = nullptr, copied = nullptr;
   // compact transfer: the chunk's rows as 16-byte records, device and (pinned, library-owned) host side, and the
   // expansion into the caller's arrays that is still to be done once the copy has arrived
   DevBuf packed;
-  void* h_packed = nullptr;
-  size_t h_packed_bytes = 0;
+  Pinned<char> h_packed;
   uint64_t unpack_ticket = 0;  // number of the expansion job that last used h_packed (0: none)
 };
 
@@ -131,7 +145,7 @@ struct attpc_ctx {
   TrackSet tset[2];
   // cloud of one chunk
   DevBuf points, labels, segments, ev_rows, lone_list, lone_chg, lone_mask, out_ctrl, merge_scratch;
-  unsigned long long* h_out_ctrl = nullptr;  // pinned [MAX_SLOTS][CTRL_WORDS]
+  Pinned<unsigned long long> h_out_ctrl;  // [MAX_SLOTS][CTRL_WORDS]
   hipEvent_t s0[MAX_SLOTS] = {}, s1[MAX_SLOTS] = {};
   int64_t cloud_capacity = 0, seg_capacity = 0;
   AsmSet aset[2];
@@ -185,6 +199,12 @@ struct attpc_ctx {
   std::deque<UnpackJob> unpack_jobs;
   uint64_t unpack_submitted = 0, unpack_done = 0;
   bool unpack_stop = false, unpack_failed = false;
+
+  ~attpc_ctx() {  // (attpc_ctx_destroy has stopped everything first; the DevBuf / Pinned members free themselves)
+    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs})
+      for (void* p : *v) (void)hipFree(p);
+    for (void* p : host_allocs) (void)hipHostFree(p);
+  }
 };
 
 namespace {
@@ -222,6 +242,20 @@ int32_t ensure(attpc_ctx* ctx, DevBuf& b, size_t bytes) {
   HIP_TRY(ctx, hipMalloc(&b.p, bytes));
   b.bytes = bytes;
   ctx->device_bytes += bytes;
+  return ATTPC_OK;
+}
+
+// grow-only pinned host array: at least `n` elements, re-allocated at `alloc` (with headroom, if larger) when it grows;
+// the caller makes sure no copy in flight uses it then
+template <typename T>
+int32_t ensure_pinned(attpc_ctx* ctx, Pinned<T>& b, size_t n, size_t alloc = 0) {
+  if (n <= b.n) return ATTPC_OK;
+  if (b.p) HIP_TRY(ctx, hipHostFree(b.p));
+  b.p = nullptr;
+  b.n = 0;
+  alloc = std::max(alloc, n);
+  HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&b.p), alloc * sizeof(T), hipHostMallocDefault));
+  b.n = alloc;
   return ATTPC_OK;
 }
 
@@ -297,6 +331,9 @@ int32_t validate_layout(attpc_ctx* ctx, const attpc_event_layout* lay, bool with
   }
   return ATTPC_OK;
 }
+
+// momentum rows per event of the configured kinematics
+int kin_rows(const attpc_ctx* ctx) { return 4 + 2 * (ctx->kin.n_steps - 1); }
 
 struct ChunkResult {
   unsigned long long rows = 0, reserved = 0, segs = 0, charge = 0, keys = 0, failed = 0, retried = 0, samples = 0,
@@ -505,7 +542,7 @@ int32_t launch_tracks(attpc_ctx* ctx, TrackSet& ts, const TrackLaunch& tl) {
                        static_cast<const int32_t*>(ts.status.p), tl.n, static_cast<uint32_t*>(ts.ctrl.p) + 3);
     HIP_TRY(ctx, hipGetLastError());
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ts.h_ctrl, ts.ctrl.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream_t));
+  HIP_TRY(ctx, hipMemcpyAsync(ts.h_ctrl.p, ts.ctrl.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream_t));
   HIP_TRY(ctx, hipEventRecord(ts.done, ctx->stream_t));
   return ATTPC_OK;
 }
@@ -688,11 +725,11 @@ int32_t enqueue_scatter(attpc_ctx* ctx, int slot, const attpc_event_layout& lay,
   HIP_TRY(ctx, hipEventRecord(ctx->s1[slot], ctx->stream));
   launch_lone_bucket_kernel((uint32_t)LONE_WORKGROUPS, ctx->stream, sa);  // exits at once without lone buckets
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_out_ctrl + (size_t)slot * CTRL_WORDS, d_ctrl, CTRL_WORDS * sizeof(unsigned long long),
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_out_ctrl.p + (size_t)slot * CTRL_WORDS, d_ctrl, CTRL_WORDS * sizeof(unsigned long long),
                               hipMemcpyDeviceToHost, ctx->stream));
 #ifdef ATTPC_PHASE_TIMERS
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const unsigned long long* octrl = ctx->h_out_ctrl + (size_t)slot * CTRL_WORDS;
+  const unsigned long long* octrl = ctx->h_out_ctrl.p + (size_t)slot * CTRL_WORDS;
   fprintf(stderr, "[attpc phase cycles] init %llu hist %llu select %llu stage %llu items %llu insert-calls %llu insert-trips %llu flushcount %llu flushwrite %llu (events %u)\n",
           octrl[8], octrl[9], octrl[10], octrl[11], octrl[12], octrl[13] >> 32, octrl[13] & 0xffffffffull, octrl[14], octrl[15], n);
   fprintf(stderr, "[attpc rows-phase cycles] gathers %llu runs %llu scan+queue %llu drain %llu\n", octrl[16], octrl[17], octrl[18], octrl[19]);
@@ -712,7 +749,7 @@ int32_t enqueue_scatter(attpc_ctx* ctx, int slot, const attpc_event_layout& lay,
 // Read the control words of slot `slot` (its copy has completed).  Updates the context's size
 // estimates; r->overflow says the launch has to be repeated with at least min_rows / min_segs.
 void read_scatter(attpc_ctx* ctx, int slot, uint32_t n, ChunkResult* r, int64_t* min_rows, int64_t* min_segs) {
-  const unsigned long long* o = ctx->h_out_ctrl + (size_t)slot * CTRL_WORDS;
+  const unsigned long long* o = ctx->h_out_ctrl.p + (size_t)slot * CTRL_WORDS;
   float ms = 0;
   if (hipEventElapsedTime(&ms, ctx->s0[slot], ctx->s1[slot]) == hipSuccess) r->ms_scatter += ms;
   r->overflow = o[6] != 0;
@@ -764,21 +801,35 @@ void accumulate(attpc_run_stats* st, const ChunkResult& r) {
 }
 
 // ------------------------------------------------------------------ assembly (delivered clouds) ----
-int32_t ensure_pinned_start(attpc_ctx* ctx, AsmSet& as, size_t len) {
-  if (len <= as.h_start_len) return ATTPC_OK;
-  if (as.h_start) HIP_TRY(ctx, hipHostFree(as.h_start));
-  if (as.h_ev_rows) HIP_TRY(ctx, hipHostFree(as.h_ev_rows));
-  as.h_start = nullptr;
-  as.h_ev_rows = nullptr;
-  as.h_start_len = 0;
-  HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&as.h_start), len * sizeof(int64_t), hipHostMallocDefault));
-  HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&as.h_ev_rows), len * sizeof(uint32_t), hipHostMallocDefault));
-  as.h_start_len = len;
-  return ATTPC_OK;
-}
-
 // What a run delivers: clouds (attpc_sim_run / attpc_det_run), Spyral rows (_spyral) or pad traces (_traces).
 enum class OutMode { cloud, spyral, traces };
+
+// A run's output: the mode, the caller's output struct of that mode (neither: a device-resident run of clouds), and
+// how far the delivery into it has come.
+struct RunOut {
+  OutMode mode = OutMode::cloud;
+  attpc_cloud_out* cloud = nullptr;  // cloud, spyral
+  attpc_trace_out* trace = nullptr;  // traces
+  int64_t rows = 0;                  // row cursor: rows of the chunks delivered so far
+  bool over = false;                 // ... more than the caller's capacity
+  bool resident() const { return !cloud && !trace; }
+  int64_t* offsets() const { return cloud ? cloud->offsets : trace ? trace->offsets : nullptr; }
+  int64_t* event_points() const { return cloud ? cloud->event_points : trace ? trace->event_points : nullptr; }
+  int64_t capacity() const { return cloud ? cloud->capacity : trace->capacity; }
+  // the capacity binds clouds always, traces when any of their row arrays is wanted
+  bool bounded() const { return cloud || (trace && (trace->pads || trace->samples || trace->labels)); }
+};
+
+// The event-ordered cloud of a chunk of `n` events and `cap` rows in `as`, and the pinned copies of its CSR offsets and
+// rows per event (exact size).
+int32_t ensure_asm_cloud(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap) {
+  int32_t rc;
+  if ((rc = ensure(ctx, as.ev_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, as.points, cap * 3 * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, as.labels, cap * sizeof(int64_t)))) return rc;
+  if ((rc = ensure_pinned(ctx, as.h_start, (size_t)n + 1))) return rc;
+  return ensure_pinned(ctx, as.h_ev_rows, (size_t)n + 1);
+}
 
 TraceScratch trace_scratch(AsmSet& as, size_t cap) {
   TraceScratch sc;
@@ -813,7 +864,7 @@ int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap, 
                      static_cast<int64_t*>(as.kept_start.p), static_cast<int64_t*>(nullptr),
                      static_cast<const unsigned long long*>(nullptr));
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(as.h_start, as.kept_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(as.h_start.p, as.kept_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   return ATTPC_OK;
 }
 
@@ -855,24 +906,89 @@ int32_t copy_traces(attpc_ctx* ctx, AsmSet& as, int64_t total, int64_t base, con
   return ATTPC_OK;
 }
 
-// Queue, behind the scatter of slot `slot` on S, the assembly of its cloud into `as`: CSR offsets by a
-// device scan of the per-event row counts, rows gathered into event order; for Spyral output also the
-// kept-row counts, their scan and the converted, thresholded, z-sorted rows; for traces the count pass and the scan
-// of the kept pad rows (the write pass follows once the host knows their number, deliver_traces).  The row totals and
-// the offsets are copied to pinned memory; as.ready is recorded at the end.  `rows_bound` >= the rows the
-// launch can have produced (the reservation capacity).  `seed` / `first_global`: the run's seed and the chunk's first
-// global event id (the noise of the traces).
+// The flags pack_rows_kernel / launch_spyral_write leave behind the transfer records (of `record` bytes) of `as`.
+int64_t* packed_flag(const AsmSet& as, size_t record) {
+  return reinterpret_cast<int64_t*>(static_cast<char*>(as.packed.p) + as.row_cap * record);
+}
+
+// pack_rows_kernel on S: the event-ordered cloud of `as` into its transfer records (8-byte ones when `tight`).
+int32_t launch_pack_rows(attpc_ctx* ctx, AsmSet& as, uint32_t n, int tight) {
+  hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)ctx->n_cus * 8u), dim3(256), 0, ctx->stream,
+                     static_cast<const int64_t*>(as.ev_start.p), n, static_cast<const double*>(as.points.p),
+                     static_cast<const int64_t*>(as.labels.p), static_cast<PackedRow*>(as.packed.p),
+                     packed_flag(as, sizeof(PackedRow)), tight);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// The Spyral write pass on S: the event-ordered cloud of `as` as converted, thresholded, z-sorted rows into
+// sp_rows / sp_labels, or into records (`packed`, with their flag) when those are given.
+int32_t launch_spyral_rows(attpc_ctx* ctx, AsmSet& as, uint32_t n, SpyralPacked* packed, int64_t* flag) {
+  launch_spyral_write(ctx->stream, ctx->spyral, n, static_cast<const int64_t*>(as.ev_start.p),
+                      static_cast<const int64_t*>(as.kept_start.p), static_cast<const double*>(as.points.p),
+                      static_cast<const int64_t*>(as.labels.p), static_cast<double*>(as.sp_rows.p),
+                      static_cast<int64_t*>(as.sp_labels.p), static_cast<uint32_t*>(ctx->sort_idx.p),
+                      static_cast<double*>(ctx->sort_key.p), packed, flag);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// Assembly tail of clouds: the CSR offsets to pinned memory, and for a compact transfer the rows packed into records.
+int32_t assemble_cloud(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
+  HIP_TRY(ctx, hipMemcpyAsync(as.h_start.p, as.ev_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (!ctx->opt_compact) return ATTPC_OK;
+  int32_t rc;
+  if ((rc = ensure(ctx, as.packed, as.row_cap * sizeof(PackedRow) + 2 * sizeof(int64_t)))) return rc;
+  int64_t* d_flag = packed_flag(as, sizeof(PackedRow));
+  HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 2 * sizeof(int64_t), ctx->stream));
+  if ((rc = launch_pack_rows(ctx, as, n, ctx->opt_compact == 2 ? 1 : 0))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(as.h_total.p, d_flag, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  return ATTPC_OK;
+}
+
+// Assembly tail of Spyral rows: the kept-row counts, their scan, the converted, thresholded, z-sorted rows (or their
+// records), and the CSR offsets of the kept rows to pinned memory.
+int32_t assemble_spyral(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
+  const size_t cap = as.row_cap;
+  int32_t rc;
+  if ((rc = ensure(ctx, as.kept, (size_t)n * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, as.kept_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, as.sp_rows, cap * 8 * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, as.sp_labels, cap * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, ctx->sort_idx, cap * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, ctx->sort_key, cap * sizeof(double)))) return rc;
+  launch_spyral_count(ctx->stream, ctx->spyral, n, static_cast<const int64_t*>(as.ev_start.p),
+                      static_cast<const double*>(as.points.p), static_cast<uint32_t*>(as.kept.p));
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(as.kept.p), n,
+                     static_cast<int64_t*>(as.kept_start.p), static_cast<int64_t*>(nullptr),
+                     static_cast<const unsigned long long*>(nullptr));
+  HIP_TRY(ctx, hipGetLastError());
+  SpyralPacked* d_packed = nullptr;
+  int64_t* d_flag = nullptr;
+  if (ctx->opt_compact) {  // 24-byte records instead of rows of 8 doubles + label; the flag sits behind them
+    if ((rc = ensure(ctx, as.packed, cap * sizeof(SpyralPacked) + 2 * sizeof(int64_t)))) return rc;
+    d_packed = static_cast<SpyralPacked*>(as.packed.p);
+    d_flag = packed_flag(as, sizeof(SpyralPacked));
+    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 2 * sizeof(int64_t), ctx->stream));
+  }
+  if ((rc = launch_spyral_rows(ctx, as, n, d_packed, d_flag))) return rc;
+  if (ctx->opt_compact) HIP_TRY(ctx, hipMemcpyAsync(as.h_total.p, d_flag, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(as.h_start.p, as.kept_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  return ATTPC_OK;
+}
+
+// Queue, behind the scatter of slot `slot` on S, the assembly of its cloud into `as`: CSR offsets by a device scan of
+// the per-event row counts, rows gathered into event order, the row counts copied to pinned memory, then the tail of
+// the mode (assemble_cloud, assemble_spyral, or for traces the count pass and the scan of the kept pad rows -- the
+// write pass follows once the host knows their number, deliver); as.ready is recorded at the end.  `seed` /
+// `first_global`: the run's seed and the chunk's first global event id (the noise of the traces).
 int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMode mode, uint64_t seed, uint64_t first_global) {
-  const bool spyral = mode == OutMode::spyral;
   int32_t rc;
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, as.copied, 0));  // the set's previous contents have left
   // rows of the scatter launch queued just before (same stream, same slot), kept with 12 % headroom
   if ((size_t)ctx->launch_row_cap > as.row_cap) as.row_cap = (size_t)ctx->launch_row_cap + (size_t)ctx->launch_row_cap / 8;
-  const size_t cap = as.row_cap;
-  if ((rc = ensure(ctx, as.ev_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(ctx, as.points, cap * 3 * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, as.labels, cap * sizeof(int64_t)))) return rc;
-  if ((rc = ensure_pinned_start(ctx, as, (size_t)n + 1))) return rc;
+  if ((rc = ensure_asm_cloud(ctx, as, n, as.row_cap))) return rc;
   const unsigned long long* d_ctrl = static_cast<const unsigned long long*>(ctx->out_ctrl.p) + (size_t)slot * CTRL_WORDS;
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(ctx->ev_rows.p), n,
                      static_cast<int64_t*>(as.ev_start.p), static_cast<int64_t*>(nullptr), d_ctrl);
@@ -882,53 +998,11 @@ int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMo
                      static_cast<const double*>(ctx->points.p), static_cast<const int64_t*>(ctx->labels.p),
                      static_cast<double*>(as.points.p), static_cast<int64_t*>(as.labels.p));
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(as.h_ev_rows, ctx->ev_rows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (mode == OutMode::traces) {
-    if ((rc = enqueue_trace_count(ctx, as, n, cap, seed, first_global))) return rc;
-  } else if (!spyral) {
-    HIP_TRY(ctx, hipMemcpyAsync(as.h_start, as.ev_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->opt_compact) {
-      if ((rc = ensure(ctx, as.packed, cap * sizeof(PackedRow) + 2 * sizeof(int64_t)))) return rc;
-      int64_t* d_flag = reinterpret_cast<int64_t*>(static_cast<char*>(as.packed.p) + cap * sizeof(PackedRow));
-      HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 2 * sizeof(int64_t), ctx->stream));
-      hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)ctx->n_cus * 8u), dim3(256), 0, ctx->stream,
-                         static_cast<const int64_t*>(as.ev_start.p), n, static_cast<const double*>(as.points.p),
-                         static_cast<const int64_t*>(as.labels.p), static_cast<PackedRow*>(as.packed.p), d_flag,
-                         ctx->opt_compact == 2 ? 1 : 0);
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipMemcpyAsync(as.h_total, d_flag, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-  } else {
-    if ((rc = ensure(ctx, as.kept, (size_t)n * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, as.kept_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, as.sp_rows, cap * 8 * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, as.sp_labels, cap * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_idx, cap * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_key, cap * sizeof(double)))) return rc;
-    launch_spyral_count(ctx->stream, ctx->spyral, n, static_cast<const int64_t*>(as.ev_start.p),
-                        static_cast<const double*>(as.points.p), static_cast<uint32_t*>(as.kept.p));
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(as.kept.p), n,
-                       static_cast<int64_t*>(as.kept_start.p), static_cast<int64_t*>(nullptr),
-                       static_cast<const unsigned long long*>(nullptr));
-    HIP_TRY(ctx, hipGetLastError());
-    SpyralPacked* d_packed = nullptr;
-    int64_t* d_flag = nullptr;
-    if (ctx->opt_compact) {  // 24-byte records instead of rows of 8 doubles + label; the flag sits behind them
-      if ((rc = ensure(ctx, as.packed, cap * sizeof(SpyralPacked) + 2 * sizeof(int64_t)))) return rc;
-      d_packed = static_cast<SpyralPacked*>(as.packed.p);
-      d_flag = reinterpret_cast<int64_t*>(static_cast<char*>(as.packed.p) + cap * sizeof(SpyralPacked));
-      HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 2 * sizeof(int64_t), ctx->stream));
-    }
-    launch_spyral_write(ctx->stream, ctx->spyral, n, static_cast<const int64_t*>(as.ev_start.p),
-                        static_cast<const int64_t*>(as.kept_start.p), static_cast<const double*>(as.points.p),
-                        static_cast<const int64_t*>(as.labels.p), static_cast<double*>(as.sp_rows.p),
-                        static_cast<int64_t*>(as.sp_labels.p), static_cast<uint32_t*>(ctx->sort_idx.p),
-                        static_cast<double*>(ctx->sort_key.p), d_packed, d_flag);
-    HIP_TRY(ctx, hipGetLastError());
-    if (ctx->opt_compact) HIP_TRY(ctx, hipMemcpyAsync(as.h_total, d_flag, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(as.h_start, as.kept_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  }
+  HIP_TRY(ctx, hipMemcpyAsync(as.h_ev_rows.p, ctx->ev_rows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (mode == OutMode::traces) rc = enqueue_trace_count(ctx, as, n, as.row_cap, seed, first_global);
+  else if (mode == OutMode::spyral) rc = assemble_spyral(ctx, as, n);
+  else rc = assemble_cloud(ctx, as, n);
+  if (rc) return rc;
   HIP_TRY(ctx, hipEventRecord(as.ready, ctx->stream));
   return ATTPC_OK;
 }
@@ -995,79 +1069,40 @@ struct UnpackDrain {
   }
 };
 
-// The counted traces of the chunk in `as` (as.ready has fired): write its offsets, queue the write pass and the copies.
-int32_t deliver_traces(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_first_local, attpc_trace_out* out,
-                       int64_t* row_cursor, bool* over_capacity, uint64_t seed, uint64_t chunk_first_global) {
-  const int64_t base = *row_cursor;
-  const int64_t total = as.h_start[n];
-  if (out->offsets)
-    for (uint32_t i = 0; i <= n; ++i) out->offsets[chunk_first_local + i] = base + as.h_start[i];
-  if (out->event_points)
-    for (uint32_t i = 0; i < n; ++i) out->event_points[chunk_first_local + i] = (int64_t)as.h_ev_rows[i];
-  *row_cursor = base + total;
-  if (n) ctx->trace_rows_per_event = std::max((double)total / (double)n, 1.0e-3);
-  const bool wanted = out->pads || out->samples || out->labels;
-  if (wanted && *row_cursor > out->capacity) *over_capacity = true;
-  int32_t rc;
-  if ((rc = enqueue_trace_write(ctx, as, n, total, seed, chunk_first_global))) return rc;
-  return copy_traces(ctx, as, total, base, out, wanted && *row_cursor <= out->capacity);
-}
-
-// The chunk in `as` is ready on the device: write its offsets, queue its copy to the caller's arrays on C.
-int32_t deliver_chunk(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_first_local, OutMode mode, attpc_cloud_out* out,
-                      int64_t* row_cursor, bool* over_capacity, uint64_t seed, uint64_t chunk_first_global) {
-  const bool spyral = mode == OutMode::spyral;
-  const int64_t base = *row_cursor;
-  const int64_t total = as.h_start[n];
-  if (out->offsets)
-    for (uint32_t i = 0; i <= n; ++i) out->offsets[chunk_first_local + i] = base + as.h_start[i];
-  if (out->event_points)
-    for (uint32_t i = 0; i < n; ++i) out->event_points[chunk_first_local + i] = (int64_t)as.h_ev_rows[i];
-  *row_cursor = base + total;
-  if (!out->points || !out->labels || *row_cursor > out->capacity) {
-    if (*row_cursor > out->capacity) *over_capacity = true;
+// Queue the copy of the chunk's cloud or Spyral rows in `as` (`total` rows, to rows base .. of the caller's arrays) on
+// C -- as compact records that the unpacker thread expands, or as they are -- and record as.copied.  `fits`: the rows
+// fit the caller's capacity (else nothing is copied).
+int32_t copy_rows(attpc_ctx* ctx, AsmSet& as, uint32_t n, const RunOut& o, int64_t base, int64_t total, bool fits,
+                  uint64_t seed, uint64_t chunk_first_global) {
+  const bool spyral = o.mode == OutMode::spyral;
+  attpc_cloud_out* out = o.cloud;
+  if (!fits || !out->points || !out->labels) {
     HIP_TRY(ctx, hipEventRecord(as.copied, ctx->stream_c));
     return ATTPC_OK;
   }
   const bool compact = ctx->opt_compact && as.h_total[0] == 0;  // [0]: a row of the chunk does not fit the record
   const bool tight = compact && !spyral && ctx->opt_compact == 2 && as.h_total[1] == 0;  // [1]: ... the 8-byte record
+  int32_t rc;
   if (total > 0 && compact && !spyral && ctx->opt_compact == 2 && !tight) {
     // the pack kernel wrote 8-byte records and one of them does not hold its row: pack again, 16 bytes per row (rare)
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)ctx->n_cus * 8u), dim3(256), 0, ctx->stream,
-                       static_cast<const int64_t*>(as.ev_start.p), n, static_cast<const double*>(as.points.p),
-                       static_cast<const int64_t*>(as.labels.p), static_cast<PackedRow*>(as.packed.p),
-                       reinterpret_cast<int64_t*>(static_cast<char*>(as.packed.p) + as.row_cap * sizeof(PackedRow)), 0);
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = launch_pack_rows(ctx, as, n, 0))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   if (total > 0 && spyral && ctx->opt_compact && !compact) {
     // the write kernel produced records only: produce the rows themselves for the plain copy below (rare)
-    launch_spyral_write(ctx->stream, ctx->spyral, n, static_cast<const int64_t*>(as.ev_start.p),
-                        static_cast<const int64_t*>(as.kept_start.p), static_cast<const double*>(as.points.p),
-                        static_cast<const int64_t*>(as.labels.p), static_cast<double*>(as.sp_rows.p),
-                        static_cast<int64_t*>(as.sp_labels.p), static_cast<uint32_t*>(ctx->sort_idx.p),
-                        static_cast<double*>(ctx->sort_key.p), nullptr, nullptr);
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = launch_spyral_rows(ctx, as, n, nullptr, nullptr))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   if (total > 0 && compact) {
     const size_t bytes = (size_t)total * (spyral ? sizeof(SpyralPacked) : (tight ? sizeof(unsigned long long) : sizeof(PackedRow)));
-    {  // the staging's previous occupant (two chunks back) must have been expanded
-      int32_t rcw = wait_unpacked(ctx, as.unpack_ticket);
-      if (rcw) return rcw;
-    }
-    if (bytes > as.h_packed_bytes) {  // library-owned pinned staging, grow-only with headroom
-      if (as.h_packed) HIP_TRY(ctx, hipHostFree(as.h_packed));
-      as.h_packed = nullptr;
-      as.h_packed_bytes = 0;
-      HIP_TRY(ctx, hipHostMalloc(&as.h_packed, bytes + bytes / 4, hipHostMallocDefault));
-      as.h_packed_bytes = bytes + bytes / 4;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(as.h_packed, as.packed.p, bytes, hipMemcpyDeviceToHost, ctx->stream_c));
+    // the staging's previous occupant (two chunks back) must have been expanded; it grows with 25 % headroom
+    if ((rc = wait_unpacked(ctx, as.unpack_ticket))) return rc;
+    if ((rc = ensure_pinned(ctx, as.h_packed, bytes, bytes + bytes / 4))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(as.h_packed.p, as.packed.p, bytes, hipMemcpyDeviceToHost, ctx->stream_c));
     HIP_TRY(ctx, hipEventRecord(as.copied, ctx->stream_c));
     UnpackJob job;
     job.copied = as.copied;
-    job.src = as.h_packed;
+    job.src = as.h_packed.p;
     job.rows = total;
     job.points = out->points + base * (spyral ? 8 : 3);
     job.labels = out->labels + base;
@@ -1076,7 +1111,7 @@ int32_t deliver_chunk(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_fir
       job.tight = true;
       job.seed = seed;
       job.first_event = chunk_first_global;
-      job.offsets.assign(as.h_start, as.h_start + n + 1);
+      job.offsets.assign(as.h_start.p, as.h_start.p + n + 1);
     }
     as.unpack_ticket = submit_unpack(ctx, job);
     return ATTPC_OK;
@@ -1089,6 +1124,26 @@ int32_t deliver_chunk(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t chunk_fir
   }
   HIP_TRY(ctx, hipEventRecord(as.copied, ctx->stream_c));
   return ATTPC_OK;
+}
+
+// The chunk of `n` events in `as` is assembled and its offsets are in as.h_start (as.ready has fired; its events are
+// first_local .. of the call, first_global .. globally): write its offsets and event_points into the caller's arrays,
+// move the row cursor past it and queue its copy on C (traces: behind their write pass on S).  A chunk beyond the
+// caller's capacity sets o.over and is not copied.
+int32_t deliver(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t first_local, uint64_t seed, uint64_t first_global) {
+  const int64_t base = o.rows, total = as.h_start[n];
+  if (int64_t* offsets = o.offsets())
+    for (uint32_t i = 0; i <= n; ++i) offsets[first_local + i] = base + as.h_start[i];
+  if (int64_t* event_points = o.event_points())
+    for (uint32_t i = 0; i < n; ++i) event_points[first_local + i] = (int64_t)as.h_ev_rows[i];
+  o.rows = base + total;
+  const bool fits = !o.bounded() || o.rows <= o.capacity();
+  if (!fits) o.over = true;
+  if (o.mode != OutMode::traces) return copy_rows(ctx, as, n, o, base, total, fits, seed, first_global);
+  if (n) ctx->trace_rows_per_event = std::max((double)total / (double)n, 1.0e-3);
+  int32_t rc;
+  if ((rc = enqueue_trace_write(ctx, as, n, total, seed, first_global))) return rc;
+  return copy_traces(ctx, as, total, base, o.trace, fits);
 }
 
 // Wait until expansion job `ticket` (and every earlier one) is done: the staging it read is free again and its
@@ -1143,9 +1198,8 @@ int32_t queue_batch(attpc_ctx* ctx, TrackSet& ts, TrackLaunch& tl, const attpc_e
 // workgroups only take the compute units the persistent scatter workgroups leave.
 template <typename QueueNext>
 int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const TrackBuffers& trk, uint64_t seed,
-                         uint64_t batch_first_global, uint64_t batch_first_local, uint32_t nb, attpc_cloud_out* out,
-                         attpc_trace_out* tout, OutMode mode, attpc_run_stats* st, int64_t* row_cursor, bool* over,
-                         QueueNext queue_next) {
+                         uint64_t batch_first_global, uint64_t batch_first_local, uint32_t nb, RunOut& o,
+                         attpc_run_stats* st, QueueNext queue_next) {
   int32_t rc;
   bool next_queued = false;
   auto queue_next_once = [&]() -> int32_t {
@@ -1155,14 +1209,8 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   };
   if (lay.n_sim == 0 || nb == 0) {  // nothing to scatter: empty clouds
     if ((rc = queue_next_once())) return rc;
-    if (out && out->offsets)
-      for (uint32_t i = 0; i <= nb; ++i) out->offsets[batch_first_local + i] = *row_cursor;
-    if (out && out->event_points)
-      for (uint32_t i = 0; i < nb; ++i) out->event_points[batch_first_local + i] = 0;
-    if (tout && tout->offsets)
-      for (uint32_t i = 0; i <= nb; ++i) tout->offsets[batch_first_local + i] = *row_cursor;
-    if (tout && tout->event_points)
-      for (uint32_t i = 0; i < nb; ++i) tout->event_points[batch_first_local + i] = 0;
+    if (int64_t* offsets = o.offsets()) std::fill(offsets + batch_first_local, offsets + batch_first_local + nb + 1, o.rows);
+    if (int64_t* event_points = o.event_points()) std::fill(event_points + batch_first_local, event_points + batch_first_local + nb, 0);
     return ATTPC_OK;
   }
   if ((rc = ensure(ctx, ctx->out_ctrl, (size_t)MAX_SLOTS * CTRL_WORDS * sizeof(unsigned long long)))) return rc;
@@ -1177,7 +1225,28 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     ctx->lone_ready = true;
   }
   struct Chunk { uint32_t e0, n; int slot; };
-  if (!out && mode != OutMode::traces) {
+  // The scatter of chunk c (and its assembly into `as`, when delivered) has completed: read its control words, and
+  // while the launch ran out of room, queue it again with larger buffers (and the assembly behind it) and read again.
+  auto settle = [&](const Chunk& c, AsmSet* as) -> int32_t {
+    ChunkResult r;
+    int64_t min_rows = 0, min_segs = 0;
+    read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
+    for (int attempt = 0; r.overflow && attempt < 8; ++attempt) {  // too small: run this chunk again
+      int32_t rc2;
+      if ((rc2 = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + c.e0, c.e0, c.n, min_rows, min_segs))) return rc2;
+      if (as) {
+        if ((rc2 = enqueue_assembly(ctx, c.slot, *as, c.n, o.mode, seed, batch_first_global + c.e0))) return rc2;
+        HIP_TRY(ctx, hipEventSynchronize(as->ready));
+      } else {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      }
+      read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
+    }
+    if (r.overflow) return fail(ctx, ATTPC_E_HIP, "point cloud did not fit after repeated buffer growth");
+    accumulate(st, r);
+    return ATTPC_OK;
+  };
+  if (o.resident()) {
     // device resident: queue up to MAX_SLOTS chunks back to back, read their control words once
     uint32_t e0 = 0;
     while (e0 < nb) {
@@ -1192,18 +1261,8 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
       }
       if ((rc = queue_next_once())) return rc;
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      for (const Chunk& c : group) {
-        ChunkResult r;
-        int64_t min_rows = 0, min_segs = 0;
-        read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
-        for (int attempt = 0; r.overflow && attempt < 8; ++attempt) {  // too small: run this chunk again
-          if ((rc = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + c.e0, c.e0, c.n, min_rows, min_segs))) return rc;
-          HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-          read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
-        }
-        if (r.overflow) return fail(ctx, ATTPC_E_HIP, "point cloud did not fit after repeated buffer growth");
-        accumulate(st, r);
-      }
+      for (const Chunk& c : group)
+        if ((rc = settle(c, nullptr))) return rc;
     }
     return ATTPC_OK;
   }
@@ -1215,21 +1274,8 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   auto complete = [&](const Chunk& c, int set) -> int32_t {
     AsmSet& as = ctx->aset[set];
     HIP_TRY(ctx, hipEventSynchronize(as.ready));
-    ChunkResult r;
-    int64_t min_rows = 0, min_segs = 0;
-    read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
-    for (int attempt = 0; r.overflow && attempt < 8; ++attempt) {
-      int32_t rc2;
-      if ((rc2 = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + c.e0, c.e0, c.n, min_rows, min_segs))) return rc2;
-      if ((rc2 = enqueue_assembly(ctx, c.slot, as, c.n, mode, seed, batch_first_global + c.e0))) return rc2;
-      HIP_TRY(ctx, hipEventSynchronize(as.ready));
-      read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
-    }
-    if (r.overflow) return fail(ctx, ATTPC_E_HIP, "point cloud did not fit after repeated buffer growth");
-    accumulate(st, r);
-    if (mode == OutMode::traces)
-      return deliver_traces(ctx, as, c.n, batch_first_local + c.e0, tout, row_cursor, over, seed, batch_first_global + c.e0);
-    return deliver_chunk(ctx, as, c.n, batch_first_local + c.e0, mode, out, row_cursor, over, seed, batch_first_global + c.e0);
+    int32_t rc2 = settle(c, &as);
+    return rc2 ? rc2 : deliver(ctx, o, as, c.n, batch_first_local + c.e0, seed, batch_first_global + c.e0);
   };
   while (e0 < nb) {
     const bool pilot = ctx->rows_per_event <= 0.0;  // only ever true with nothing in flight
@@ -1240,13 +1286,13 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     uint32_t n = std::min<uint32_t>(next_chunk_events(ctx, nb - e0), (uint32_t)ctx->opt_deliver_chunk);
     if (ctx->rows_per_event > 0.0)
       n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)DELIVER_CHUNK_ROWS / ctx->rows_per_event));
-    if (mode == OutMode::traces && ctx->trace_rows_per_event > 0.0)  // 1 KiB of samples per kept pad row
+    if (o.mode == OutMode::traces && ctx->trace_rows_per_event > 0.0)  // 1 KiB of samples per kept pad row
       n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)TRACE_CHUNK_ROWS / ctx->trace_rows_per_event));
     const Chunk c{e0, n, seq % MAX_SLOTS};
     const int set = seq & 1;
     // an overflow of the chunk in flight is repaired inside complete(); queue this one behind it
     if ((rc = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + e0, e0, n, 0, 0))) return rc;
-    if ((rc = enqueue_assembly(ctx, c.slot, ctx->aset[set], n, mode, seed, batch_first_global + e0))) return rc;
+    if ((rc = enqueue_assembly(ctx, c.slot, ctx->aset[set], n, o.mode, seed, batch_first_global + e0))) return rc;
     if ((rc = queue_next_once())) return rc;
     if (prev.slot >= 0 && (rc = complete(prev, prev_set))) return rc;
     prev = c;
@@ -1263,25 +1309,48 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   return queue_next_once();
 }
 
+// The trace checksums of a run start at zero (queued on S).
+int32_t reset_trace_sums(attpc_ctx* ctx) {
+  int32_t rc;
+  if ((rc = ensure(ctx, ctx->trace_sums, 2 * sizeof(unsigned long long)))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->trace_sums.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  return ATTPC_OK;
+}
+
+// The end of a trace run whose copies have all arrived: its kept rows and checksums into the caller's attpc_trace_out.
+int32_t read_trace_sums(attpc_ctx* ctx, const RunOut& o) {
+  unsigned long long sums[2] = {0ull, 0ull};
+  HIP_TRY(ctx, hipMemcpyAsync(sums, ctx->trace_sums.p, sizeof sums, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  o.trace->n_rows = o.rows;
+  o.trace->sample_checksum = sums[0];
+  o.trace->pad_checksum = sums[1];
+  return ATTPC_OK;
+}
+
+// The end of a run: its statistics to the caller, then the verdicts on the capacity and on lost charge.
+int32_t run_status(attpc_ctx* ctx, const attpc_run_stats& st, attpc_run_stats* stats, const RunOut& o) {
+  if (stats) *stats = st;
+  if (o.over)
+    return fail(ctx, ATTPC_E_CAPACITY, "%s %lld rows, capacity %lld", o.mode == OutMode::traces ? "traces need" : "cloud needs",
+                (long long)o.rows, (long long)o.capacity());
+  if (st.n_failed || st.n_inconsistent)
+    return fail(ctx, ATTPC_E_DATALOSS, "%llu events lost a time bucket (n_failed), %u table self-check failures (n_inconsistent) in %llu events",
+                (unsigned long long)st.n_failed, st.n_inconsistent, (unsigned long long)st.n_events);
+  return ATTPC_OK;
+}
+
 int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events, const attpc_event_layout& lay,
-                   const RunSource& src, const RunSink& sink, attpc_cloud_out* out, OutMode mode, attpc_run_stats* stats,
-                   attpc_trace_out* tout = nullptr) {
-  const bool spyral = mode == OutMode::spyral;
+                   const RunSource& src, const RunSink& sink, RunOut o, attpc_run_stats* stats) {
   int32_t rc;
   if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
-  if (mode == OutMode::traces) {
-    if ((rc = ensure(ctx, ctx->trace_sums, 2 * sizeof(unsigned long long)))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->trace_sums.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    if (tout->offsets) tout->offsets[0] = 0;
-  }
+  if (o.mode == OutMode::traces && (rc = reset_trace_sums(ctx))) return rc;
   UnpackDrain drain(ctx);
   attpc_run_stats st{};
   st.n_events = n_events;
   const uint64_t growths_before = ctx->n_growths;
   const int n_rows = lay.n_rows;
-  int64_t row_cursor = 0;
-  bool over = false;
-  if (out && out->offsets) out->offsets[0] = 0;
+  if (int64_t* offsets = o.offsets()) offsets[0] = 0;
   // batches of up to MAX_SLOTS chunks (a small pilot batch while the arena need per track is unknown),
   // each integrated on T while the previous batch is scattered on S
   uint64_t b0 = 0;
@@ -1367,33 +1436,38 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
     if (sink.status) HIP_TRY(ctx, hipMemcpyAsync(sink.status + b0, ts.status.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (sink.p4) HIP_TRY(ctx, hipMemcpyAsync(sink.p4 + b0 * n_rows * 4, ts.p4.p, (size_t)nb * n_rows * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (sink.vertex) HIP_TRY(ctx, hipMemcpyAsync(sink.vertex + b0 * 3, ts.vertex.p, (size_t)nb * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = run_batch_chunks(ctx, lay, trk, seed, first_event + b0, b0, nb, out, tout, mode, &st, &row_cursor, &over, queue_next)))
-      return rc;
+    if ((rc = run_batch_chunks(ctx, lay, trk, seed, first_event + b0, b0, nb, o, &st, queue_next))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // this set's readers are done before it is refilled
     b0 = next_b0;
     nb = next_nb;
     cur ^= 1;
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
-  if (spyral) st.n_points = (uint64_t)row_cursor;  // rows that survive the threshold
-  if (mode == OutMode::traces) {  // (the cloud's meaning stays in st)
-    unsigned long long sums[2] = {0ull, 0ull};
-    HIP_TRY(ctx, hipMemcpyAsync(sums, ctx->trace_sums.p, sizeof sums, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    tout->n_rows = row_cursor;
-    tout->sample_checksum = sums[0];
-    tout->pad_checksum = sums[1];
-  }
+  if (o.mode == OutMode::spyral) st.n_points = (uint64_t)o.rows;  // rows that survive the threshold
+  if (o.mode == OutMode::traces && (rc = read_trace_sums(ctx, o))) return rc;  // (the cloud's meaning stays in st)
   st.n_buffer_growths = ctx->n_growths - growths_before;
   st.device_bytes = ctx->device_bytes;
-  if (stats) *stats = st;
-  if (over && mode == OutMode::traces)
-    return fail(ctx, ATTPC_E_CAPACITY, "traces need %lld rows, capacity %lld", (long long)row_cursor, (long long)tout->capacity);
-  if (over) return fail(ctx, ATTPC_E_CAPACITY, "cloud needs %lld rows, capacity %lld", (long long)row_cursor, (long long)out->capacity);
-  if (st.n_failed || st.n_inconsistent)
-    return fail(ctx, ATTPC_E_DATALOSS, "%llu events lost a time bucket (n_failed), %u table self-check failures (n_inconsistent) in %llu events",
-                (unsigned long long)st.n_failed, st.n_inconsistent, (unsigned long long)n_events);
-  return ATTPC_OK;
+  return run_status(ctx, st, stats, o);
+}
+
+// The six run entry points (attpc_det_run*, attpc_sim_run*; `name`) after their checks: the kinematics come from the
+// host (src.h_p4 / h_vertex) or from the kinematics kernel (src.from_kernel), the output is `o`.
+int32_t run_entry(const char* name, attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                  const attpc_event_layout* layout, const RunSource& src, const RunSink& sink, RunOut o, attpc_run_stats* stats) {
+  if (!ctx || (!src.from_kernel && (!src.h_p4 || !src.h_vertex))) return ATTPC_E_INVALID;
+  if (o.mode == OutMode::traces && !o.trace) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_trace_out", name);
+  if (o.mode == OutMode::spyral && !o.cloud) return fail(ctx, ATTPC_E_INVALID, "%s needs output buffers", name);
+  if (src.from_kernel && !ctx->kin_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_kin_configure has not been called");
+  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_det_configure has not been called");
+  if (o.mode == OutMode::spyral && !ctx->spyral_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_spyral_configure has not been called");
+  if (o.mode == OutMode::traces && !ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc = validate_layout(ctx, layout, true);
+  if (rc) return rc;
+  if (src.from_kernel && layout->n_rows != kin_rows(ctx))
+    return fail(ctx, ATTPC_E_INVALID, "layout.n_rows=%d but the pipeline has %d rows", layout->n_rows, kin_rows(ctx));
+  if (o.mode == OutMode::traces && (rc = drop_prefetch(ctx))) return rc;  // a trace call is never the announced one
+  return run_events(ctx, seed, first_event, n_events, *layout, src, sink, o, stats);
 }
 
 }  // namespace
@@ -1430,15 +1504,14 @@ int32_t attpc_ctx_create(int32_t device, attpc_ctx** out) {
   auto make_event = [&](hipEvent_t* e) { ok = ok && hipEventCreate(e) == hipSuccess; };
   for (TrackSet& ts : ctx->tset) {
     make_event(&ts.done); make_event(&ts.k0); make_event(&ts.k1); make_event(&ts.t0); make_event(&ts.t1);
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&ts.h_ctrl), 16 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
+    ok = ok && ensure_pinned(ctx, ts.h_ctrl, 16) == ATTPC_OK;
   }
   for (int i = 0; i < MAX_SLOTS; ++i) { make_event(&ctx->s0[i]); make_event(&ctx->s1[i]); }
   for (AsmSet& as : ctx->aset) {
     make_event(&as.ready); make_event(&as.copied); make_event(&as.traced);
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&as.h_total), 2 * sizeof(int64_t), hipHostMallocDefault) == hipSuccess;
+    ok = ok && ensure_pinned(ctx, as.h_total, 2) == ATTPC_OK;
   }
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&ctx->h_out_ctrl), (size_t)MAX_SLOTS * CTRL_WORDS * sizeof(unsigned long long),
-                           hipHostMallocDefault) == hipSuccess;
+  ok = ok && ensure_pinned(ctx, ctx->h_out_ctrl, (size_t)MAX_SLOTS * CTRL_WORDS) == ATTPC_OK;
   if (!ok) {
     attpc_ctx_destroy(ctx);
     return ATTPC_E_HIP;
@@ -1459,45 +1532,17 @@ int32_t attpc_ctx_destroy(attpc_ctx* ctx) {
   if (ctx->stream_t_own) (void)hipStreamSynchronize(ctx->stream_t_own);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->stream_c) (void)hipStreamSynchronize(ctx->stream_c);
-  free_all(ctx->kin_allocs);
-  free_all(ctx->det_allocs);
-  free_all(ctx->spyral_allocs);
-  free_all(ctx->trace_allocs);
-  free_all(ctx->noise_allocs);
-  std::vector<DevBuf*> bufs = {&ctx->points, &ctx->labels, &ctx->segments, &ctx->ev_rows, &ctx->lone_list, &ctx->lone_chg,
-                               &ctx->lone_mask, &ctx->out_ctrl, &ctx->merge_scratch,
-                               &ctx->sort_idx, &ctx->sort_key, &ctx->trace_sums};
-  for (TrackSet& ts : ctx->tset) {
-    for (DevBuf* b : {&ts.p4, &ts.vertex, &ts.status, &ts.attempts, &ts.arena, &ts.block_table, &ts.counts, &ts.n_steps, &ts.ctrl})
-      bufs.push_back(b);
-    for (hipEvent_t e : {ts.done, ts.k0, ts.k1, ts.t0, ts.t1})
+  auto destroy = [](std::initializer_list<hipEvent_t> events) {
+    for (hipEvent_t e : events)
       if (e) (void)hipEventDestroy(e);
-    if (ts.h_ctrl) (void)hipHostFree(ts.h_ctrl);
-  }
-  for (AsmSet& as : ctx->aset) {
-    for (DevBuf* b : {&as.ev_start, &as.points, &as.labels, &as.kept, &as.kept_start, &as.sp_rows, &as.sp_labels, &as.packed,
-                      &as.tr_scratch, &as.tr_info, &as.tr_pads, &as.tr_samples, &as.tr_labels}) bufs.push_back(b);
-    if (as.h_packed) (void)hipHostFree(as.h_packed);
-    for (hipEvent_t e : {as.ready, as.copied, as.traced})
-      if (e) (void)hipEventDestroy(e);
-    if (as.h_start) (void)hipHostFree(as.h_start);
-    if (as.h_ev_rows) (void)hipHostFree(as.h_ev_rows);
-    if (as.h_total) (void)hipHostFree(as.h_total);
-  }
-  for (DevBuf* b : bufs)
-    if (b->p) (void)hipFree(b->p);
-  for (auto& b : ctx->scratch)
-    if (b.p) (void)hipFree(b.p);
-  for (int i = 0; i < MAX_SLOTS; ++i) {
-    if (ctx->s0[i]) (void)hipEventDestroy(ctx->s0[i]);
-    if (ctx->s1[i]) (void)hipEventDestroy(ctx->s1[i]);
-  }
-  if (ctx->h_out_ctrl) (void)hipHostFree(ctx->h_out_ctrl);
-  for (void* p : ctx->host_allocs) (void)hipHostFree(p);
+  };
+  for (TrackSet& ts : ctx->tset) destroy({ts.done, ts.k0, ts.k1, ts.t0, ts.t1});
+  for (AsmSet& as : ctx->aset) destroy({as.ready, as.copied, as.traced});
+  for (int i = 0; i < MAX_SLOTS; ++i) destroy({ctx->s0[i], ctx->s1[i]});
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream_t_own) (void)hipStreamDestroy(ctx->stream_t_own);
   if (ctx->stream_c) (void)hipStreamDestroy(ctx->stream_c);
-  delete ctx;
+  delete ctx;  // (frees the buffers)
   return ATTPC_OK;
 }
 
@@ -1666,7 +1711,7 @@ int32_t attpc_kin_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint6
   if (!ctx->kin_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_kin_configure has not been called");
   if (validate_id_range(ctx, first_event, n_events)) return ATTPC_E_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int n_rows = 4 + 2 * (ctx->kin.n_steps - 1);
+  const int n_rows = kin_rows(ctx);
   // buffers of its own (ctx->scratch): the track sets are sized by the largest track batch met so far
   // (max_batch_events), and a kinematics-only call of 4 chunks per launch must not set that mark for every later
   // detector run; and nothing a failed earlier run may have left queued on any stream is overtaken
@@ -1701,7 +1746,7 @@ int32_t attpc_kin_calculate(attpc_ctx* ctx, uint64_t n, const double* beam_energ
   if (!ctx->kin_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_kin_configure has not been called");
   if (n == 0) return ATTPC_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int ns = ctx->kin.n_steps, n_rows = 4 + 2 * (ns - 1);
+  const int ns = ctx->kin.n_steps, n_rows = kin_rows(ctx);
   int32_t rc;
   if ((rc = ensure(ctx, ctx->scratch[0], n * sizeof(double)))) return rc;
   for (int i = 1; i <= 3; ++i)
@@ -1821,68 +1866,29 @@ int32_t attpc_det_configure(attpc_ctx* ctx, const attpc_det_desc* d) {
 int32_t attpc_det_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                       const attpc_event_layout* layout, const double* p4, const double* vertex,
                       attpc_cloud_out* out, attpc_run_stats* stats) {
-  if (!ctx || !p4 || !vertex) return ATTPC_E_INVALID;
-  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_det_configure has not been called");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int32_t rc = validate_layout(ctx, layout, true);
-  if (rc) return rc;
-  RunSource src;
-  src.h_p4 = p4;
-  src.h_vertex = vertex;
-  return run_events(ctx, seed, first_event, n_events, *layout, src, RunSink{}, out, OutMode::cloud, stats);
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{},
+                   RunOut{OutMode::cloud, out}, stats);
 }
 
 int32_t attpc_det_run_spyral(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                              const attpc_event_layout* layout, const double* p4, const double* vertex,
                              attpc_cloud_out* out, attpc_run_stats* stats) {
-  if (!ctx || !p4 || !vertex) return ATTPC_E_INVALID;
-  if (!out) return fail(ctx, ATTPC_E_INVALID, "attpc_det_run_spyral needs output buffers");
-  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_det_configure has not been called");
-  if (!ctx->spyral_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_spyral_configure has not been called");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int32_t rc = validate_layout(ctx, layout, true);
-  if (rc) return rc;
-  RunSource src;
-  src.h_p4 = p4;
-  src.h_vertex = vertex;
-  return run_events(ctx, seed, first_event, n_events, *layout, src, RunSink{}, out, OutMode::spyral, stats);
-}
-
-static int32_t sim_run_impl(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
-                            const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
-                            attpc_cloud_out* out, attpc_run_stats* stats, OutMode mode, attpc_trace_out* tout = nullptr) {
-  if (!ctx) return ATTPC_E_INVALID;
-  const bool spyral = mode == OutMode::spyral;
-  if (mode == OutMode::traces && !ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
-  if (spyral && !ctx->spyral_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_spyral_configure has not been called");
-  if (!ctx->kin_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_kin_configure has not been called");
-  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_det_configure has not been called");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int32_t rc = validate_layout(ctx, layout, true);
-  if (rc) return rc;
-  const int n_rows = 4 + 2 * (ctx->kin.n_steps - 1);
-  if (layout->n_rows != n_rows) return fail(ctx, ATTPC_E_INVALID, "layout.n_rows=%d but the pipeline has %d rows", layout->n_rows, n_rows);
-  RunSource src;
-  src.from_kernel = true;
-  RunSink sink;
-  sink.p4 = p4;
-  sink.vertex = vertex;
-  sink.status = kin_status;
-  if (mode == OutMode::traces && (rc = drop_prefetch(ctx))) return rc;  // a trace call is never the announced one
-  return run_events(ctx, seed, first_event, n_events, *layout, src, sink, out, mode, stats, tout);
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{},
+                   RunOut{OutMode::spyral, out}, stats);
 }
 
 int32_t attpc_sim_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                       const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
                       attpc_cloud_out* out, attpc_run_stats* stats) {
-  return sim_run_impl(ctx, seed, first_event, n_events, layout, p4, vertex, kin_status, out, stats, OutMode::cloud);
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{true}, RunSink{p4, vertex, kin_status},
+                   RunOut{OutMode::cloud, out}, stats);
 }
 
 int32_t attpc_sim_run_spyral(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                              const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
                              attpc_cloud_out* out, attpc_run_stats* stats) {
-  if (!out) return fail(ctx, ATTPC_E_INVALID, "attpc_sim_run_spyral needs output buffers");
-  return sim_run_impl(ctx, seed, first_event, n_events, layout, p4, vertex, kin_status, out, stats, OutMode::spyral);
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{true}, RunSink{p4, vertex, kin_status},
+                   RunOut{OutMode::spyral, out}, stats);
 }
 
 // ---- digitised pad traces (traces.hip; the contract is in include/attpc_engine.h) ----
@@ -1955,25 +1961,15 @@ int32_t attpc_trace_configure_noise(attpc_ctx* ctx, const attpc_trace_noise_desc
 int32_t attpc_sim_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                              const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
                              attpc_trace_out* out, attpc_run_stats* stats) {
-  if (!out) return fail(ctx, ATTPC_E_INVALID, "attpc_sim_run_traces needs an attpc_trace_out");
-  return sim_run_impl(ctx, seed, first_event, n_events, layout, p4, vertex, kin_status, nullptr, stats, OutMode::traces, out);
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{true}, RunSink{p4, vertex, kin_status},
+                   RunOut{OutMode::traces, nullptr, out}, stats);
 }
 
 int32_t attpc_det_run_traces(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                              const attpc_event_layout* layout, const double* p4, const double* vertex,
                              attpc_trace_out* out, attpc_run_stats* stats) {
-  if (!ctx || !p4 || !vertex) return ATTPC_E_INVALID;
-  if (!out) return fail(ctx, ATTPC_E_INVALID, "attpc_det_run_traces needs an attpc_trace_out");
-  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_det_configure has not been called");
-  if (!ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int32_t rc = validate_layout(ctx, layout, true);
-  if (rc) return rc;
-  if ((rc = drop_prefetch(ctx))) return rc;
-  RunSource src;
-  src.h_p4 = p4;
-  src.h_vertex = vertex;
-  return run_events(ctx, seed, first_event, n_events, *layout, src, RunSink{}, nullptr, OutMode::traces, stats, out);
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{},
+                   RunOut{OutMode::traces, nullptr, out}, stats);
 }
 
 int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points, const int64_t* labels,
@@ -2019,11 +2015,7 @@ int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
   if ((rc = sync_all(ctx))) return rc;
   AsmSet& as = ctx->aset[0];
   const size_t cap = (size_t)std::max<int64_t>(rows, 1);
-  if ((rc = ensure(ctx, as.ev_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(ctx, as.points, cap * 3 * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, as.labels, cap * sizeof(int64_t)))) return rc;
-  if ((rc = ensure_pinned_start(ctx, as, (size_t)n + 1))) return rc;
-  if ((rc = ensure(ctx, ctx->trace_sums, 2 * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure_asm_cloud(ctx, as, n, cap))) return rc;
   std::vector<int64_t> start((size_t)n + 1, 0);
   for (uint32_t e = 0; e <= n; ++e) start[e] = offsets[e] - first;
   HIP_TRY(ctx, hipMemcpyAsync(as.ev_start.p, start.data(), start.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
@@ -2031,26 +2023,18 @@ int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
     HIP_TRY(ctx, hipMemcpyAsync(as.points.p, points + 3 * first, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(as.labels.p, labels + first, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
   }
-  HIP_TRY(ctx, hipMemsetAsync(ctx->trace_sums.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  if ((rc = reset_trace_sums(ctx))) return rc;
   if ((rc = enqueue_trace_count(ctx, as, n, cap, seed, first_event))) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the copies above read pageable memory: nothing of it stays in flight)
-  const int64_t total = as.h_start[n];
-  if (out->offsets)
-    for (uint32_t e = 0; e <= n; ++e) out->offsets[e] = as.h_start[e];
-  if (out->event_points)
-    for (uint32_t e = 0; e < n; ++e) out->event_points[e] = offsets[e + 1] - offsets[e];
-  const bool wanted = out->pads || out->samples || out->labels;
-  const bool fits = !wanted || total <= out->capacity;
-  if ((rc = enqueue_trace_write(ctx, as, n, total, seed, first_event))) return rc;
-  if ((rc = copy_traces(ctx, as, total, 0, out, fits))) return rc;
-  unsigned long long sums[2] = {0ull, 0ull};
-  HIP_TRY(ctx, hipMemcpyAsync(sums, ctx->trace_sums.p, sizeof sums, hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = sync_all(ctx))) return rc;
-  out->n_rows = total;
-  out->sample_checksum = sums[0];
-  out->pad_checksum = sums[1];
-  if (!fits) return fail(ctx, ATTPC_E_CAPACITY, "traces need %lld rows, capacity %lld", (long long)total, (long long)out->capacity);
-  return ATTPC_OK;
+  for (uint32_t e = 0; e < n; ++e) as.h_ev_rows[e] = (uint32_t)(offsets[e + 1] - offsets[e]);  // event_points: the caller's
+  RunOut o{OutMode::traces, nullptr, out};
+  const double keep = ctx->trace_rows_per_event;  // a host cloud says nothing about the configured workload
+  rc = deliver(ctx, o, as, n, 0, seed, first_event);
+  ctx->trace_rows_per_event = keep;
+  if (rc) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
+  if ((rc = read_trace_sums(ctx, o))) return rc;
+  return run_status(ctx, attpc_run_stats{}, nullptr, o);
 }
 
 int32_t attpc_sim_hint_next(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
@@ -2062,7 +2046,7 @@ int32_t attpc_sim_hint_next(attpc_ctx* ctx, uint64_t seed, uint64_t first_event,
   int32_t rc = validate_id_range(ctx, first_event, n_events);
   if (rc) return rc;
   if ((rc = validate_layout(ctx, layout, true))) return rc;
-  if (layout->n_rows != 4 + 2 * (ctx->kin.n_steps - 1)) return fail(ctx, ATTPC_E_INVALID, "layout.n_rows does not match the pipeline");
+  if (layout->n_rows != kin_rows(ctx)) return fail(ctx, ATTPC_E_INVALID, "layout.n_rows does not match the pipeline");
   ctx->hint_valid = true;
   ctx->hint_seed = seed;
   ctx->hint_first = first_event;
@@ -2197,22 +2181,16 @@ int32_t attpc_det_scatter(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, u
   UnpackDrain drain(ctx);
   attpc_run_stats st{};
   st.n_events = n_events;
-  int64_t row_cursor = 0;
-  bool over = false;
-  if (out && out->offsets) out->offsets[0] = 0;
+  RunOut o{OutMode::cloud, out};
+  if (int64_t* offsets = o.offsets()) offsets[0] = 0;
   const double keep_rows = ctx->rows_per_event, keep_segs = ctx->segs_per_event;
   ctx->rows_per_event = ctx->segs_per_event = 0.0;  // explicit samples say nothing about the configured workload
-  rc = run_batch_chunks(ctx, *layout, trk, seed, first_event, 0, n, out, nullptr, OutMode::cloud, &st, &row_cursor, &over, []() -> int32_t { return ATTPC_OK; });
+  rc = run_batch_chunks(ctx, *layout, trk, seed, first_event, 0, n, o, &st, []() -> int32_t { return ATTPC_OK; });
   ctx->rows_per_event = keep_rows;
   ctx->segs_per_event = keep_segs;
   if (rc) return rc;
   if ((rc = sync_all(ctx))) return rc;
-  if (stats) *stats = st;
-  if (over) return fail(ctx, ATTPC_E_CAPACITY, "cloud needs %lld rows, capacity %lld", (long long)row_cursor, (long long)out->capacity);
-  if (st.n_failed || st.n_inconsistent)
-    return fail(ctx, ATTPC_E_DATALOSS, "%llu events lost a time bucket (n_failed), %u table self-check failures (n_inconsistent)",
-                (unsigned long long)st.n_failed, st.n_inconsistent);
-  return ATTPC_OK;
+  return run_status(ctx, st, stats, o);
 }
 
 }  // extern "C"

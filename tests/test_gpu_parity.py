@@ -399,6 +399,13 @@ def test_multichunk_assembly_and_buffer_growth(orc):
                        *sort_cloud(ref["points"][lo:hi], ref["labels"][lo:hi]))
     assert res["stats"]["n_failed"] == 0
     fresh.close()
+    # the same ids device resident on a fresh undersized context: the overflow retry of the resident loop
+    resident_ctx = _abi.Context(0)
+    resident_ctx.set_option("tiny_buffers", 1)
+    resident = _engine(inp, resident_ctx, chunk_events=7).run(n, seed=31, first_event=9, fetch=False)["stats"]
+    for key in ("n_points", "charge_checksum", "key_checksum"):
+        assert resident[key] == res["stats"][key], key
+    resident_ctx.close()
 
 
 @pytest.mark.parametrize("name,n", [("o16aa", 50_000), ("be10dp", 50_000), ("b10chain", 1_500)])

@@ -194,6 +194,14 @@ def test_split_chunk_and_capacity_invariance(ctx):
     small.configure_traces(inp.config)
     got, _ = _sim_traces(small, 96, 4, 10)
     _assert_same(got, whole)
+    # undersized buffers on a fresh context: the chunk's assembly is queued again behind its re-scatter
+    tiny_ctx = _abi.Context(0)
+    tiny_ctx.set_option("tiny_buffers", 1)
+    tiny = _engine(inp, tiny_ctx)
+    tiny.configure_traces(inp.config)
+    got, _ = _sim_traces(tiny, 96, 4, 10)
+    _assert_same(got, whole)
+    tiny_ctx.close()
     ctx.check(ctx.lib.attpc_set_chunk_events(ctx.handle, 0), "attpc_set_chunk_events")
     # too small a capacity: E_CAPACITY with the exact row count, then success
     from attpc_engine_amd.detector.traces import TraceArrays
