@@ -191,17 +191,9 @@ def main() -> None:
         "be10dp_inverse": ([(1, 2), (4, 10), (1, 1)], [], 96.0),
     }
     kin = {}
-    for name, (rx, decs, e0) in chains.items():
-        reaction = Reaction(*[nmap.get_data(z, a) for z, a in rx])
-        decays = [Decay(nmap.get_data(*par), nmap.get_data(*r1)) for par, r1 in decs]
-        n_steps = 1 + len(decays)
-        n = 160
-        beam = e0 * rng.uniform(0.6, 1.1, n)
-        ex = np.abs(rng.normal(0.0, 2.0, (n, n_steps)))
-        ex[:, 0] = rng.uniform(0.0, 0.55 * e0, n)  # spans allowed and forbidden excitations
-        ex[::7] = 0.0
-        th = np.arccos(rng.uniform(-1, 1, (n, n_steps)))
-        ph = rng.uniform(0, 2 * np.pi, (n, n_steps))
+
+    def kin_case(name, reaction, decays, beam, ex, th, ph):
+        n = len(beam)
         n_rows = 4 + 2 * len(decays)
         p4 = np.full((n, n_rows, 4), np.nan)
         status = np.zeros(n, dtype=np.int32)
@@ -236,7 +228,43 @@ def main() -> None:
         kin[f"{name}_ph"] = ph
         kin[f"{name}_p4"] = p4
         kin[f"{name}_status"] = status
-        print(name, "allowed", int((status == 0).sum()), "of", n)
+        print(name, "allowed", int((status == 0).sum()), "of", n, "failed at steps", sorted(set(status[status > 1])))
+
+    for name, (rx, decs, e0) in chains.items():
+        reaction = Reaction(*[nmap.get_data(z, a) for z, a in rx])
+        decays = [Decay(nmap.get_data(*par), nmap.get_data(*r1)) for par, r1 in decs]
+        n_steps = 1 + len(decays)
+        n = 160
+        beam = e0 * rng.uniform(0.6, 1.1, n)
+        ex = np.abs(rng.normal(0.0, 2.0, (n, n_steps)))
+        ex[:, 0] = rng.uniform(0.0, 0.55 * e0, n)  # spans allowed and forbidden excitations
+        ex[::7] = 0.0
+        th = np.arccos(rng.uniform(-1, 1, (n, n_steps)))
+        ph = rng.uniform(0, 2 * np.pi, (n, n_steps))
+        kin_case(name, reaction, decays, beam, ex, th, ph)
+
+    # the longest chain the layout holds (8 steps, 18 rows: tests/helpers.py chain8): 4He(24Mg,d)26Al*, then
+    # p, n, a, t, p, a, a down to 8Be.  Its own generator: the shared `rng` feeds every later fixture.  Excitations
+    # around the cascade's nominal values; in about one event of three one step asks for more than its parent can
+    # give (status 1 at the reaction, status s + 2 at decay s).
+    long_rng = np.random.default_rng(20261016)
+    reaction = Reaction(nmap.get_data(2, 4), nmap.get_data(12, 24), nmap.get_data(1, 2))
+    decays = [Decay(nmap.get_data(*par), nmap.get_data(*r1)) for par, r1 in
+              [((13, 26), (1, 1)), ((12, 25), (0, 1)), ((12, 24), (2, 4)), ((10, 20), (1, 3)), ((9, 17), (1, 1)),
+               ((8, 16), (2, 4)), ((6, 12), (2, 4))]]
+    nominal = np.array([86.0, 76.0, 65.0, 51.0, 24.0, 20.0, 10.0, 0.0])
+    n = 48
+    beam = 800.0 * long_rng.uniform(0.98, 1.05, n)
+    ex = np.abs(nominal + long_rng.normal(0.0, 0.5, (n, 8)))
+    ex[:, 7] = 0.0
+    fail_at = np.where(long_rng.uniform(0.0, 1.0, n) < 0.35, long_rng.integers(0, 8, n), -1)
+    fail_at[:8] = np.arange(8)  # every step fails somewhere
+    for i, s in enumerate(fail_at):
+        if s >= 0:  # 30 MeV more than the step's parent has (the reaction: beyond the kinematic limit)
+            ex[i, s] = 400.0 if s == 0 else ex[i, s - 1] + 30.0
+    th = np.arccos(long_rng.uniform(-1, 1, (n, 8)))
+    ph = long_rng.uniform(0, 2 * np.pi, (n, 8))
+    kin_case("mg24_chain8", reaction, decays, beam, ex, th, ph)
     np.savez_compressed(OUT / "kinematics.npz", lise_ke=lise, pair_tb=tbs, pair_pad=pads, pair_id=ids,
                         unpair=back, **kin)
 

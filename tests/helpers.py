@@ -4,17 +4,23 @@ from __future__ import annotations
 
 import numpy as np
 
-from attpc_engine_amd import _abi, nuclear_map, workloads
+from attpc_engine_amd import GasTarget, _abi, nuclear_map, workloads
 from attpc_engine_amd.detector.luts import build_det_desc, build_layout, species_for
+from attpc_engine_amd.detector.simulator import default_indices
+from attpc_engine_amd.kinematics import (
+    Decay, ExcitationGaussian, KinematicsPipeline, KinematicsTargetMaterial, PolarUniform, Reaction,
+)
 
 
 class Inputs:
-    """Descriptors of one workload.  ``det`` has the beam pads folded (product), ``det_raw``
-    has the unfolded LUT (the oracle applies the beam-pad list itself)."""
+    """Descriptors of one workload: a ``workloads.WORKLOADS`` name or a builder of the same signature (such as
+    ``chain7`` below).  ``det`` has the beam pads folded (product), ``det_raw`` has the unfolded LUT (the oracle
+    applies the beam-pad list itself)."""
 
-    def __init__(self, name: str, ode_substeps: int = 1, **kw):
+    def __init__(self, name, ode_substeps: int = 1, **kw):
         det_overrides = {k: kw.pop(k) for k in ("path_step",) if k in kw}  # DetectorParams fields, any workload
-        self.pipeline, self.config, self.indices = workloads.WORKLOADS[name](**kw)
+        builder = workloads.WORKLOADS[name] if isinstance(name, str) else name
+        self.pipeline, self.config, self.indices = builder(**kw)
         for key, value in det_overrides.items():
             setattr(self.config.det_params, key, value)
         self.kin, self._k1 = self.pipeline.device_desc()
@@ -27,6 +33,68 @@ class Inputs:
             self.det, self._k2 = build_det_desc(self.config, nuclei, ode_substeps, fold_beam=True)
             self.det_raw, self._k3 = build_det_desc(self.config, nuclei, ode_substeps, fold_beam=False)
             self.layout = build_layout(self.z, self.a, self.indices, self.species)
+
+
+# ---------------------------------------------------------------- long decay chains: the layout limits ----
+# ATTPC_MAX_STEPS = 8 steps (18 rows) and ATTPC_MAX_SIM = 8 simulated nuclei.  A 700 / 800 MeV 24Mg beam on the
+# o16aa gas makes 26Al* by (a,d); the compound nucleus then evaporates one particle per step down to 12C (chain7) or
+# 8Be (chain8).  The excitations sit above each step's separation energy, so every event is allowed; the products
+# are forward-focused and start at one vertex, so 3 and more nuclei light the same (pad, time bucket) near it.
+_CHAIN_DECAYS = [((13, 26), (1, 1)), ((12, 25), (0, 1)), ((12, 24), (2, 4)), ((10, 20), (1, 3)), ((9, 17), (1, 1)),
+                 ((8, 16), (2, 4)), ((6, 12), (2, 4))]
+
+
+def _long_chain(n_decays: int, beam_energy: float, excitations, indices, seed: int, **kw):
+    nm = nuclear_map
+    gas = GasTarget([(2, 4, 1)], 600.0, nm)
+    steps = [Reaction(target=nm.get_data(2, 4), projectile=nm.get_data(12, 24), ejectile=nm.get_data(1, 2))]
+    steps += [Decay(parent=nm.get_data(*par), residual_1=nm.get_data(*r1)) for par, r1 in _CHAIN_DECAYS[:n_decays]]
+    pipeline = KinematicsPipeline(
+        steps, [ExcitationGaussian(c, w) for c, w in excitations], [PolarUniform(0.0, np.pi)] * len(steps),
+        beam_energy=beam_energy, target_material=KinematicsTargetMaterial(gas, (0.0, 1.0), 0.007), seed=seed, **kw)
+    return pipeline, workloads.detector_config(gas), indices
+
+
+def chain7(seed: int = 7, **kw):
+    """7 steps, 16 rows: 4He(24Mg,d)26Al* ->p 25Mg* ->n 24Mg* ->a 20Ne* ->t 17F* ->p 16O* ->a 12C, 700 MeV beam.
+    The reference's default indices [2, 4, 6, 8, 10, 12, 14, 15]: 8 nuclei (isim 0..7), species d, p, a, t, 12C;
+    row 6 is the neutron (species -1, a dead track in the middle of the layout)."""
+    ex = [(76.0, 1.0), (66.0, 1.0), (55.0, 1.0), (42.0, 3.0), (15.0, 1.0), (11.0, 0.5), (0.0, 0.0)]
+    return _long_chain(6, 700.0, ex, default_indices(16), seed, **kw)
+
+
+CHAIN8_INDICES = [17, 3, 16, 2, 9, 12, 5, 14]  # non-ascending: the last writer is the largest isim, not the largest row
+
+
+def chain8(seed: int = 8, **kw):
+    """8 steps, 18 rows: chain7 at 800 MeV with 12C* ->a 8Be added (rows 16, 17).  Indices ``CHAIN8_INDICES``: 8
+    nuclei of 7 species (8Be, 26Al, a, d, 20Ne, p, 25Mg); labels 16 and 17 set the top bits of every label field."""
+    ex = [(86.0, 1.0), (76.0, 1.0), (65.0, 1.0), (51.0, 1.0), (24.0, 1.0), (20.0, 1.0), (10.0, 0.5), (0.0, 0.0)]
+    return _long_chain(7, 800.0, ex, list(CHAIN8_INDICES), seed, **kw)
+
+
+LONG_CHAINS = {"chain7": chain7, "chain8": chain8}
+
+
+def overlap_counts(orc, inp, p4, vertex, seed, first):
+    """Oracle clouds of the events -> (points won by each position isim, keys lit by >= 3 nuclei, labels seen).  The
+    nuclei touching a key come from one oracle run per nucleus alone (a nucleus' draws do not depend on the others).
+    ``orc``: the oracle module (oracle/pyoracle.py)."""
+    wins = np.zeros(_abi.MAX_SIM, dtype=np.int64)
+    shared3, labels = 0, set()
+    for e in range(len(p4)):
+        pts, lab, _ = orc.simulate(inp.det_raw, inp.layout, seed, first + e, p4[e], vertex[e], capacity=1 << 20)
+        labels |= set(lab.tolist())
+        for isim, row in enumerate(inp.indices):
+            wins[isim] += int((lab == row).sum())
+        touched: dict[int, int] = {}
+        for row in inp.indices:
+            alone = build_layout(inp.z, inp.a, [row], inp.species)
+            p1, _, _ = orc.simulate(inp.det_raw, alone, seed, first + e, p4[e], vertex[e], capacity=1 << 20)
+            for k in (p1[:, 0].astype(np.int64) << 10 | np.floor(p1[:, 1]).astype(np.int64)).tolist():
+                touched[k] = touched.get(k, 0) + 1
+        shared3 += sum(1 for c in touched.values() if c >= 3)
+    return wins, shared3, labels
 
 
 def sort_cloud(points: np.ndarray, labels: np.ndarray):

@@ -96,7 +96,7 @@ def test_decay_api():
 
 
 # ---------------------------------------------------------------- kinematics ---------------
-@pytest.mark.parametrize("chain", ["c12dp", "o16aa_a12c", "b10_3he_chain", "be10dp_inverse"])
+@pytest.mark.parametrize("chain", ["c12dp", "o16aa_a12c", "b10_3he_chain", "be10dp_inverse", "mg24_chain8"])
 def test_kin_calculate_golden(golden_dir, ctx, chain):
     g = np.load(golden_dir / "kinematics.npz")
     masses = g[f"{chain}_masses"]

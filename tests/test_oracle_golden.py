@@ -86,7 +86,7 @@ def test_lise_known_answer():
     assert np.round(ke, 3) == 18.391
 
 
-@pytest.mark.parametrize("chain", ["c12dp", "o16aa_a12c", "b10_3he_chain", "be10dp_inverse"])
+@pytest.mark.parametrize("chain", ["c12dp", "o16aa_a12c", "b10_3he_chain", "be10dp_inverse", "mg24_chain8"])
 def test_kinematics_golden(golden_dir, chain):
     g = np.load(golden_dir / "kinematics.npz")
     desc = _kin_desc(g[f"{chain}_masses"])
