@@ -23,6 +23,7 @@ DEDX_NODES = (DEDX_EMAX - DEDX_EMIN) * DEDX_SUB + 1
 NUM_TB = 512
 NUM_PADS = 10240
 MAX_NOISE_LEVELS = 512
+READOUT_HIT, READOUT_PARTIAL, READOUT_FULL = 0, 1, 2
 TIME_SAMPLES = 10001
 LONG_STEPS = 5
 
@@ -126,6 +127,10 @@ class TraceNoiseDesc(C.Structure):
     ]
 
 
+class TraceReadoutDesc(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("channels", C.POINTER(C.c_uint8))]
+
+
 class TraceOut(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64),
@@ -214,7 +219,7 @@ EXPORTED_SYMBOLS = (
     "attpc_set_option", "attpc_host_alloc", "attpc_host_free", "attpc_det_scatter", "attpc_unpack_rows",
     "attpc_unpack_spyral_rows", "attpc_det_run_spyral", "attpc_sim_hint_next", "attpc_unpack_rows8",
     "attpc_trace_configure", "attpc_sim_run_traces", "attpc_det_run_traces", "attpc_traces",
-    "attpc_trace_configure_noise", "attpc_traces_at",
+    "attpc_trace_configure_noise", "attpc_traces_at", "attpc_trace_configure_readout",
 )
 
 _lib = None
@@ -283,6 +288,7 @@ def load_library() -> C.CDLL:
     lib.attpc_trace_configure_noise.argtypes = [ctxp, C.POINTER(TraceNoiseDesc)]
     lib.attpc_traces_at.argtypes = [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64), _dp,
                                     C.POINTER(C.c_int64), C.POINTER(TraceOut)]
+    lib.attpc_trace_configure_readout.argtypes = [ctxp, C.POINTER(TraceReadoutDesc)]
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

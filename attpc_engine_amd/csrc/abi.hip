@@ -49,6 +49,7 @@ constexpr uint32_t LONE_CAPACITY = 65536;
 constexpr int64_t CLOUD_BUDGET_BYTES = 24ll << 30;  // points + labels of one chunk
 constexpr int64_t DELIVER_CHUNK_ROWS = 96ll << 20;  // cloud rows of a chunk whose cloud is delivered (3 GB: ~60 ms of PCIe)
 constexpr int64_t TRACE_CHUNK_ROWS = 4ll << 20;     // kept pad rows of a chunk of a trace run (4 GiB of samples)
+                                                    // (readout modes too: their first chunk is sized by |S| per event)
 constexpr uint64_t ARENA_BUDGET_BYTES = 24ull << 30;
 
 struct DevBuf {  // grow-only device buffer (ensure()), freed with its owner
@@ -82,6 +83,7 @@ struct TrackSet {  // kinematics + tracks of one track batch
 struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its pad traces
   DevBuf ev_start, points, labels, kept, kept_start, sp_rows, sp_labels;
   DevBuf tr_scratch, tr_info, tr_pads, tr_samples, tr_labels;  // pad traces (traces.hip)
+  DevBuf tr_maps;     // readout of noise-only pads: TraceMaps, 3 x TR_MAP_WORDS words per event
   size_t tr_cap = 0;  // kept pad rows the trace outputs are kept at (grown with headroom)
   hipEvent_t traced = nullptr;  // the chunk's traces are written (the copies on C wait for it)
   size_t row_cap = 0;  // rows the row-sized buffers of the set are kept at (grown with headroom: a launch's row
@@ -183,6 +185,11 @@ struct attpc_ctx {
   bool noise_on = false;           // attpc_trace_configure_noise: noise and / or pedestals on (the NOISE kernels)
   TraceNoiseDev noise{};
   std::vector<void*> noise_allocs;
+  std::vector<uint32_t> noise_cdf;  // host copy of the noise cdf [n_levels - 1] (the readout's cutoff)
+  int32_t readout_mode = ATTPC_READOUT_HIT;  // attpc_trace_configure_readout
+  int64_t readout_pads = 0;        // |S|
+  const uint32_t* readout_channels = nullptr;  // [TR_MAP_WORDS] bitmap of S on the device
+  std::vector<void*> readout_allocs;
   DevBuf trace_sums;               // [2] sample / pad checksums of the trace run in progress
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
   std::vector<void*> spyral_allocs;
@@ -201,7 +208,7 @@ struct attpc_ctx {
   bool unpack_stop = false, unpack_failed = false;
 
   ~attpc_ctx() {  // (attpc_ctx_destroy has stopped everything first; the DevBuf / Pinned members free themselves)
-    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs})
+    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs, &readout_allocs})
       for (void* p : *v) (void)hipFree(p);
     for (void* p : host_allocs) (void)hipHostFree(p);
   }
@@ -845,6 +852,40 @@ TraceScratch trace_scratch(AsmSet& as, size_t cap) {
 // The noise of the trace kernels: nullptr = the noiseless kernels.
 const TraceNoiseDev* trace_noise(const attpc_ctx* ctx) { return ctx->noise_on ? &ctx->noise : nullptr; }
 
+// The readout of the trace kernels (ro.channels == nullptr: hit mode) with the cutoff of the decision rule for the
+// configured threshold and noise table: c = floor(thr) + 1 - min_level; c <= 0 always, c > n_levels - 1 never (no
+// table: the one level 0), else u_j >= cdf[c - 1].
+TraceReadoutDev trace_readout(const attpc_ctx* ctx) {
+  TraceReadoutDev ro{};
+  if (ctx->readout_mode == ATTPC_READOUT_HIT) return ro;
+  ro.channels = ctx->readout_channels;
+  ro.full = ctx->readout_mode == ATTPC_READOUT_FULL ? 1 : 0;
+  const bool table = ctx->noise_on && ctx->noise.n_levels > 0;
+  const int64_t n_levels = table ? ctx->noise.n_levels : 1, min_level = table ? ctx->noise.min_level : 0;
+  const double thr = std::min(std::max(ctx->trace.threshold, -16384.0), 16384.0);  // levels lie in -4095 .. 4606
+  const int64_t c = (int64_t)std::floor(thr) + 1 - min_level;
+  if (c <= 0) ro.cut_kind = TRACE_CUT_ALWAYS;
+  else if (c > n_levels - 1) ro.cut_kind = TRACE_CUT_NEVER;
+  else {
+    ro.cut_kind = TRACE_CUT_DRAW;
+    ro.cut = ctx->noise_cdf[(size_t)(c - 1)];
+  }
+  return ro;
+}
+
+// Does a readout run need the scan and the noise-only write?  Not in hit mode, nor in PARTIAL when the decision rule
+// keeps no noise-only pad (thr >= 0 and a cutoff above the table): the count pass's ranks are then the union's.
+bool readout_scan(const attpc_ctx* ctx, const TraceReadoutDev& ro) {
+  if (!ro.channels) return false;
+  return ro.full || !(ro.cut_kind == TRACE_CUT_NEVER && ctx->trace.threshold >= 0.0);
+}
+
+TraceMaps trace_maps(AsmSet& as, uint32_t n) {
+  uint32_t* base = static_cast<uint32_t*>(as.tr_maps.p);
+  const size_t words = (size_t)n * TR_MAP_WORDS;
+  return TraceMaps{base, base + words, base + 2 * words};
+}
+
 // Trace count pass of the n events whose event-ordered cloud is in `as` (ev_start / points / labels, `cap` rows at
 // most; global ids first_event .. first_event + n - 1), the scan of the kept rows and the copy of their CSR offsets to
 // as.h_start, on S.
@@ -854,11 +895,19 @@ int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap, 
   if ((rc = ensure(ctx, as.kept_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
   if ((rc = ensure(ctx, as.tr_scratch, std::max<size_t>(cap, 1) * 4 * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, as.tr_info, std::max<size_t>(n, 1) * 2 * sizeof(uint32_t)))) return rc;
+  const TraceReadoutDev ro = trace_readout(ctx);
   if (n) {
+    const TraceScratch sc = trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t)));
     launch_trace_count(ctx->stream, ctx->trace, trace_noise(ctx), seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
-                       static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p),
-                       trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t))), static_cast<uint32_t*>(as.kept.p));
+                       static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p), sc,
+                       static_cast<uint32_t*>(as.kept.p), ro.channels ? &ro : nullptr);
     HIP_TRY(ctx, hipGetLastError());
+    if (readout_scan(ctx, ro)) {
+      if ((rc = ensure(ctx, as.tr_maps, (size_t)n * 3 * TR_MAP_WORDS * sizeof(uint32_t)))) return rc;
+      launch_trace_scan(ctx->stream, ctx->trace, trace_noise(ctx), ro, seed, n, first_event,
+                        static_cast<const int64_t*>(as.ev_start.p), sc, static_cast<uint32_t*>(as.kept.p), trace_maps(as, n));
+      HIP_TRY(ctx, hipGetLastError());
+    }
   }
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(as.kept.p), n,
                      static_cast<int64_t*>(as.kept_start.p), static_cast<int64_t*>(nullptr),
@@ -884,6 +933,13 @@ int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t tota
                        static_cast<int16_t*>(as.tr_samples.p), static_cast<int64_t*>(as.tr_labels.p),
                        static_cast<unsigned long long*>(ctx->trace_sums.p));
     HIP_TRY(ctx, hipGetLastError());
+    if (readout_scan(ctx, trace_readout(ctx))) {  // the noise-only rows between them
+      launch_trace_noise_write(ctx->stream, trace_noise(ctx), seed, n, first_event, trace_maps(as, n),
+                               static_cast<const int64_t*>(as.kept_start.p), static_cast<int32_t*>(as.tr_pads.p),
+                               static_cast<int16_t*>(as.tr_samples.p), static_cast<int64_t*>(as.tr_labels.p),
+                               static_cast<unsigned long long*>(ctx->trace_sums.p));
+      HIP_TRY(ctx, hipGetLastError());
+    }
   }
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   return ATTPC_OK;
@@ -1146,6 +1202,44 @@ int32_t deliver(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t firs
   return copy_traces(ctx, as, total, base, o.trace, fits);
 }
 
+// The traces of n host-side events (attpc_traces_at; a run's batch with nothing to scatter in a readout mode) on
+// assembly set 0, delivered into o as events first_local .. of the call, global ids first_event ..: `offsets` [n + 1]
+// their rows in points / labels (nullptr: n events without rows).  In a readout mode a chunk holds at most
+// TRACE_CHUNK_ROWS / |S| events, so the device output stays bounded whatever n is; in hit mode the n events are one
+// chunk (their kept rows are bounded by the rows given).
+int32_t trace_host_events(attpc_ctx* ctx, RunOut& o, uint64_t first_local, uint32_t n, const int64_t* offsets,
+                          const double* points, const int64_t* labels, uint64_t seed, uint64_t first_event) {
+  AsmSet& as = ctx->aset[0];
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the set's previous contents have left
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
+  const uint32_t step = ctx->readout_mode != ATTPC_READOUT_HIT && ctx->readout_pads > 0
+                            ? (uint32_t)std::max<int64_t>(1, TRACE_CHUNK_ROWS / ctx->readout_pads)
+                            : std::max<uint32_t>(n, 1);
+  uint32_t e0 = 0;
+  do {
+    const uint32_t m = std::min(step, n - e0);
+    const int64_t lo = offsets ? offsets[e0] : 0, rows = offsets ? offsets[e0 + m] - lo : 0;
+    const size_t cap = (size_t)std::max<int64_t>(rows, 1);
+    int32_t rc;
+    if ((rc = ensure_asm_cloud(ctx, as, m, cap))) return rc;
+    std::vector<int64_t> start((size_t)m + 1, 0);
+    if (offsets)
+      for (uint32_t e = 0; e <= m; ++e) start[e] = offsets[e0 + e] - lo;
+    HIP_TRY(ctx, hipMemcpyAsync(as.ev_start.p, start.data(), start.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (rows > 0) {
+      HIP_TRY(ctx, hipMemcpyAsync(as.points.p, points + 3 * lo, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(as.labels.p, labels + lo, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = enqueue_trace_count(ctx, as, m, cap, seed, first_event + e0))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the copies above read pageable memory: nothing of it stays in flight)
+    for (uint32_t e = 0; e < m; ++e) as.h_ev_rows[e] = (uint32_t)(start[e + 1] - start[e]);  // event_points: the caller's
+    if ((rc = deliver(ctx, o, as, m, first_local + e0, seed, first_event + e0))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));  // the next chunk overwrites the set
+    e0 += m;
+  } while (e0 < n);
+  return ATTPC_OK;
+}
+
 // Wait until expansion job `ticket` (and every earlier one) is done: the staging it read is free again and its
 // rows are in the caller's arrays.
 int32_t wait_unpacked(attpc_ctx* ctx, uint64_t ticket) {
@@ -1209,6 +1303,8 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   };
   if (lay.n_sim == 0 || nb == 0) {  // nothing to scatter: empty clouds
     if ((rc = queue_next_once())) return rc;
+    if (o.mode == OutMode::traces && ctx->readout_mode != ATTPC_READOUT_HIT && nb)  // their noise-only rows
+      return trace_host_events(ctx, o, batch_first_local, nb, nullptr, nullptr, nullptr, seed, batch_first_global);
     if (int64_t* offsets = o.offsets()) std::fill(offsets + batch_first_local, offsets + batch_first_local + nb + 1, o.rows);
     if (int64_t* event_points = o.event_points()) std::fill(event_points + batch_first_local, event_points + batch_first_local + nb, 0);
     return ATTPC_OK;
@@ -1286,7 +1382,11 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     uint32_t n = std::min<uint32_t>(next_chunk_events(ctx, nb - e0), (uint32_t)ctx->opt_deliver_chunk);
     if (ctx->rows_per_event > 0.0)
       n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)DELIVER_CHUNK_ROWS / ctx->rows_per_event));
-    if (o.mode == OutMode::traces && ctx->trace_rows_per_event > 0.0)  // 1 KiB of samples per kept pad row
+    if (o.mode == OutMode::traces && ctx->readout_mode != ATTPC_READOUT_HIT) {  // the first chunk too: |S| rows per event
+      const double rows = ctx->readout_mode == ATTPC_READOUT_FULL || ctx->trace_rows_per_event <= 0.0
+                              ? (double)ctx->readout_pads : ctx->trace_rows_per_event;
+      if (rows > 0.0) n = std::min<uint32_t>(n, (uint32_t)std::max(1.0, (double)TRACE_CHUNK_ROWS / rows));
+    } else if (o.mode == OutMode::traces && ctx->trace_rows_per_event > 0.0)  // 1 KiB of samples per kept pad row
       n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)TRACE_CHUNK_ROWS / ctx->trace_rows_per_event));
     const Chunk c{e0, n, seq % MAX_SLOTS};
     const int set = seq & 1;
@@ -1345,6 +1445,9 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   int32_t rc;
   if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
   if (o.mode == OutMode::traces && (rc = reset_trace_sums(ctx))) return rc;
+  // a readout run sizes its trace chunks for |S| rows per event until it has seen its own rate: the rate of an earlier
+  // run says nothing once the threshold, the noise or the workload has changed (hit mode keeps the context's rate)
+  if (o.mode == OutMode::traces && ctx->readout_mode != ATTPC_READOUT_HIT) ctx->trace_rows_per_event = 0.0;
   UnpackDrain drain(ctx);
   attpc_run_stats st{};
   st.n_events = n_events;
@@ -1934,12 +2037,14 @@ int32_t attpc_trace_configure_noise(attpc_ctx* ctx, const attpc_trace_noise_desc
   free_all(ctx->noise_allocs);
   ctx->noise_on = false;
   ctx->noise = TraceNoiseDev{};
+  ctx->noise_cdf.clear();
   if (!d || (d->n_levels == 0 && !d->pedestals)) return ATTPC_OK;  // the noiseless contract
   // the cdf padded to the full table (the kernels copy all of it to LDS) and the guide: the search for u starts at
   // #{k : cdf[k] <= (u >> 24) << 24}
   const int n_cdf = std::max(d->n_levels - 1, 0);
   std::vector<uint32_t> cdf(ATTPC_MAX_NOISE_LEVELS, 0xFFFFFFFFu);
   for (int k = 0; k < n_cdf; ++k) cdf[k] = d->cdf[k];
+  ctx->noise_cdf.assign(cdf.begin(), cdf.begin() + n_cdf);
   std::vector<uint16_t> guide(256);
   for (int b = 0, k = 0; b < 256; ++b) {
     while (k < n_cdf && cdf[k] <= (uint32_t)b << 24) ++k;
@@ -1955,6 +2060,32 @@ int32_t attpc_trace_configure_noise(attpc_ctx* ctx, const attpc_trace_noise_desc
   nz.domain = DOMAIN_TRACE_NOISE | d->stream;
   ctx->noise = nz;
   ctx->noise_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_trace_configure_readout(attpc_ctx* ctx, const attpc_trace_readout_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d && d->mode != ATTPC_READOUT_HIT && d->mode != ATTPC_READOUT_PARTIAL && d->mode != ATTPC_READOUT_FULL)
+    return fail(ctx, ATTPC_E_INVALID, "trace readout mode %d: 0 (hit), 1 (partial) or 2 (full)", d->mode);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  free_all(ctx->readout_allocs);
+  ctx->readout_mode = ATTPC_READOUT_HIT;
+  ctx->readout_pads = 0;
+  ctx->readout_channels = nullptr;
+  ctx->trace_rows_per_event = 0.0;  // the kept rows of another readout say nothing about this one
+  if (!d || d->mode == ATTPC_READOUT_HIT) return ATTPC_OK;
+  std::vector<uint32_t> words(TR_MAP_WORDS, 0u);
+  int64_t count = 0;
+  for (int p = 0; p < ATTPC_NUM_PADS; ++p)
+    if (!d->channels || d->channels[p]) {
+      words[p >> 5] |= 1u << (p & 31);
+      ++count;
+    }
+  int32_t rc;
+  if ((rc = upload(ctx, ctx->readout_allocs, words.data(), words.size(), &ctx->readout_channels))) return rc;
+  ctx->readout_pads = count;
+  ctx->readout_mode = d->mode;
   return ATTPC_OK;
 }
 
@@ -2013,26 +2144,12 @@ int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
   int32_t rc;
   if ((rc = drop_prefetch(ctx))) return rc;
   if ((rc = sync_all(ctx))) return rc;
-  AsmSet& as = ctx->aset[0];
-  const size_t cap = (size_t)std::max<int64_t>(rows, 1);
-  if ((rc = ensure_asm_cloud(ctx, as, n, cap))) return rc;
-  std::vector<int64_t> start((size_t)n + 1, 0);
-  for (uint32_t e = 0; e <= n; ++e) start[e] = offsets[e] - first;
-  HIP_TRY(ctx, hipMemcpyAsync(as.ev_start.p, start.data(), start.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-  if (rows > 0) {
-    HIP_TRY(ctx, hipMemcpyAsync(as.points.p, points + 3 * first, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(as.labels.p, labels + first, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-  }
   if ((rc = reset_trace_sums(ctx))) return rc;
-  if ((rc = enqueue_trace_count(ctx, as, n, cap, seed, first_event))) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the copies above read pageable memory: nothing of it stays in flight)
-  for (uint32_t e = 0; e < n; ++e) as.h_ev_rows[e] = (uint32_t)(offsets[e + 1] - offsets[e]);  // event_points: the caller's
   RunOut o{OutMode::traces, nullptr, out};
   const double keep = ctx->trace_rows_per_event;  // a host cloud says nothing about the configured workload
-  rc = deliver(ctx, o, as, n, 0, seed, first_event);
+  rc = trace_host_events(ctx, o, 0, n, offsets, points, labels, seed, first_event);
   ctx->trace_rows_per_event = keep;
   if (rc) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
   if ((rc = read_trace_sums(ctx, o))) return rc;
   return run_status(ctx, attpc_run_stats{}, nullptr, o);
 }

@@ -18,6 +18,16 @@
 // instantiations are the noiseless code.  With NOISE, a pad's samples get its pedestal and one table-driven noise draw
 // each (add_noise), both passes draw the same numbers, and the count pass's verdict is taken above the pedestal.  The
 // noise table (2 KiB of cdf, 0.5 KiB of guide) sits in LDS: the count pass stays at two workgroups per CU.
+// Readout of noise-only pads (attpc_trace_configure_readout, PARTIAL / FULL): the count pass is templated on RO as well
+// (the RO = false instantiations are the hit-mode code); with RO it drops the rows of pads outside the readout set S and
+// in FULL keeps every hit pad of S.  Two kernels of their own follow it:
+//   scan:  one workgroup per event, empty events included; one wave per candidate pad (in S, no rows) takes the
+//          contract's two Philox calls per lane, compares the 8 words with the cutoff u32 of the decision rule and
+//          ballots; the kept bitmap (hit and noise-only) gets a popcount prefix per word, which gives every kept pad its
+//          rank in the event and overwrites the hit pads' ranks of the count pass.  No LDS tables: full occupancy.
+//   noise write: one wave per kept noise-only pad writes pad, label -1 and the clamped pedestal plus noise.
+// The scan is skipped when the decision rule keeps no noise-only pad (PARTIAL, thr >= 0 and a cutoff above the table):
+// the count pass's ranks are then already those of the union.
 #include "tracks_args.hpp"
 
 namespace attpc {
@@ -111,10 +121,9 @@ __device__ __forceinline__ PadTrace pad_trace(const TraceDev& tr, const double* 
 // call h = s / 4, counter (event, pad * 128 + 2 * lane + h, domain), so a lane makes two calls per pad.  The level
 // index #{k : cdf[k] <= u} starts at the guide entry of u's top byte and walks the few cdf entries inside that byte.
 // Afterwards pt.max = max_j (trace_p[j] - ped_p), the quantity the threshold is taken on.
-__device__ __forceinline__ void add_noise(PadTrace& pt, const TraceNoiseDev& nz, const uint32_t* cdf,
-                                          const uint16_t* guide, uint64_t seed, uint64_t event, uint32_t pad, int lane) {
-  const int ped = nz.pedestals ? (int)nz.pedestals[pad] : 0;
-  int n[8];
+__device__ __forceinline__ void noise_values(int n[8], const TraceNoiseDev& nz, const uint32_t* cdf,
+                                             const uint16_t* guide, uint64_t seed, uint64_t event, uint32_t pad,
+                                             int lane) {
   for (int s = 0; s < 8; ++s) n[s] = 0;
   if (nz.n_levels > 0) {  // uniform
     const int n_cdf = nz.n_levels - 1;
@@ -131,6 +140,13 @@ __device__ __forceinline__ void add_noise(PadTrace& pt, const TraceNoiseDev& nz,
       }
     }
   }
+}
+
+__device__ __forceinline__ void add_noise(PadTrace& pt, const TraceNoiseDev& nz, const uint32_t* cdf,
+                                          const uint16_t* guide, uint64_t seed, uint64_t event, uint32_t pad, int lane) {
+  const int ped = nz.pedestals ? (int)nz.pedestals[pad] : 0;
+  int n[8];
+  noise_values(n, nz, cdf, guide, seed, event, pad, lane);
   int m = -4096;  // below any trace_p[j] - ped_p (>= -4095)
   for (int s = 0; s < 8; ++s) {
     int v = pt.v[s] + ped + n[s];
@@ -149,13 +165,20 @@ __device__ __forceinline__ bool trace_row_ok(double padf, double tb) {
   return padf >= 0.0 && padf < (double)ATTPC_NUM_PADS && tb >= 0.0 && tb < (double)ATTPC_NUM_TB;
 }
 
-template <bool NOISE>
+// A row of the count pass with readout RO: in range and on a pad of the readout set (rows elsewhere are dropped).
+template <bool RO>
+__device__ __forceinline__ bool trace_row_read(double padf, double tb, const TraceReadoutDev& ro) {
+  if constexpr (RO) return trace_row_ok(padf, tb) && ((ro.channels[(int)padf >> 5] >> ((int)padf & 31)) & 1u);
+  return trace_row_ok(padf, tb);
+}
+
+template <bool NOISE, bool RO>
 __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, TraceNoiseDev nz, uint64_t seed,
                                                                  uint64_t first_event,
                                                                  const int64_t* __restrict__ event_start,
                                                                  const double* __restrict__ points,
                                                                  const int64_t* __restrict__ labels, TraceScratch sc,
-                                                                 uint32_t* __restrict__ kept) {
+                                                                 uint32_t* __restrict__ kept, TraceReadoutDev ro) {
   __shared__ uint32_t cursor[ATTPC_NUM_PADS];  // counts, then the next free place of every pad's group
   __shared__ double resp[ATTPC_NUM_TB];
   __shared__ uint32_t noise_cdf[ATTPC_MAX_NOISE_LEVELS];  // (NOISE only: the noiseless kernel never names them)
@@ -184,7 +207,7 @@ __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, Tr
   block_sync();
   for (int64_t r = lo + t; r < hi; r += TR_THREADS) {
     const double padf = points[3 * r], tb = points[3 * r + 1];
-    if (trace_row_ok(padf, tb)) atomicAdd(&cursor[(int)padf], 1u);
+    if (trace_row_read<RO>(padf, tb, ro)) atomicAdd(&cursor[(int)padf], 1u);
   }
   block_sync();
   {  // exclusive prefix over the pads (rows and hit pads): 20 consecutive pads per thread, wave scan, wave offsets
@@ -229,13 +252,19 @@ __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, Tr
   block_sync();
   for (int64_t r = lo + t; r < hi; r += TR_THREADS) {
     const double padf = points[3 * r], tb = points[3 * r + 1];
-    if (trace_row_ok(padf, tb)) sc.row[lo + atomicAdd(&cursor[(int)padf], 1u)] = (uint32_t)(r - lo);
+    if (trace_row_read<RO>(padf, tb, ro)) sc.row[lo + atomicAdd(&cursor[(int)padf], 1u)] = (uint32_t)(r - lo);
   }
   // workgroup scope is enough: the lists are written and read by this workgroup only (as spyral_write_kernel)
   __threadfence_block();
   block_sync();
   const uint32_t H = n_hits, V = n_placed;
   for (uint32_t k = (uint32_t)wave; k < H; k += TR_WAVES) {
+    if constexpr (RO) {
+      if (ro.full) {  // uniform: every pad of S is read out
+        if (lane == 0) sc.rank[lo + k] = 1;
+        continue;
+      }
+    }
     const uint32_t start = sc.hit_start[lo + k], end = k + 1 < H ? sc.hit_start[lo + k + 1] : V;
     PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
     if constexpr (NOISE) add_noise(pt, nz, noise_cdf, noise_guide, seed, first_event + e, sc.hit[lo + k], lane);
@@ -334,15 +363,23 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, Tr
   }
 }
 
+template <bool NOISE, bool RO>
+void launch_count(hipStream_t s, const TraceDev& tr, const TraceNoiseDev& nz, uint64_t seed, uint32_t n_events,
+                  uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
+                  TraceScratch sc, uint32_t* kept, const TraceReadoutDev& ro) {
+  hipLaunchKernelGGL((trace_count_kernel<NOISE, RO>), dim3(n_events), dim3(TR_THREADS), 0, s, tr, nz, seed, first_event,
+                     event_start, points, labels, sc, kept, ro);
+}
+
 void launch_trace_count(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
-                        TraceScratch sc, uint32_t* kept) {
-  if (noise)
-    hipLaunchKernelGGL(trace_count_kernel<true>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, *noise, seed, first_event,
-                       event_start, points, labels, sc, kept);
-  else
-    hipLaunchKernelGGL(trace_count_kernel<false>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, TraceNoiseDev{}, seed,
-                       first_event, event_start, points, labels, sc, kept);
+                        TraceScratch sc, uint32_t* kept, const TraceReadoutDev* ro) {
+  const TraceNoiseDev nz = noise ? *noise : TraceNoiseDev{};
+  const TraceReadoutDev rd = ro ? *ro : TraceReadoutDev{};
+  if (noise && ro) launch_count<true, true>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd);
+  else if (noise) launch_count<true, false>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd);
+  else if (ro) launch_count<false, true>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd);
+  else launch_count<false, false>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd);
 }
 void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
@@ -354,6 +391,177 @@ void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* 
   else
     hipLaunchKernelGGL(trace_write_kernel<false>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, TraceNoiseDev{}, seed,
                        first_event, event_start, points, labels, sc, kept_start, pads, samples, out_labels, sums);
+}
+
+
+// ---- readout of noise-only pads (the scan and the noise-only write) ----
+constexpr int RO_THREADS = 512;
+constexpr int RO_WAVES = RO_THREADS / 64;
+static_assert(TR_MAP_WORDS <= RO_THREADS, "a thread holds at most one word of the kept bitmap in the prefix");
+
+// The verdict of noise-only pad `pad` of S in PARTIAL readout (wave-uniform), the decision rule of include/attpc_engine.h:
+// kept iff 4095 - ped > thr and (-ped > thr or max_j n_j > thr), and max_j n_j > thr iff some u_j >= cdf[c - 1].
+__device__ __forceinline__ bool noise_only_kept(const TraceDev& tr, const TraceNoiseDev& nz, const TraceReadoutDev& ro,
+                                                uint64_t seed, uint64_t event, uint32_t pad, int lane) {
+  const int ped = nz.pedestals ? (int)nz.pedestals[pad] : 0;
+  if (!((double)(4095 - ped) > tr.threshold)) return false;
+  if ((double)(-ped) > tr.threshold || ro.cut_kind == TRACE_CUT_ALWAYS) return true;
+  if (ro.cut_kind == TRACE_CUT_NEVER) return false;
+  bool over = false;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    uint32_t u[4];
+    philox4x32<10>((uint32_t)event, (uint32_t)(event >> 32), pad * 128u + 2u * (uint32_t)lane + (uint32_t)h, nz.domain,
+                   (uint32_t)seed, (uint32_t)(seed >> 32), u);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) over |= u[w] >= ro.cut;
+  }
+  return __ballot(over) != 0ull;
+}
+
+__global__ __launch_bounds__(RO_THREADS) void trace_scan_kernel(TraceDev tr, TraceNoiseDev nz, TraceReadoutDev ro,
+                                                                uint64_t seed, uint64_t first_event,
+                                                                const int64_t* __restrict__ event_start, TraceScratch sc,
+                                                                uint32_t* __restrict__ kept, TraceMaps maps) {
+  __shared__ uint32_t hit_w[TR_MAP_WORDS], kept_w[TR_MAP_WORDS], before_w[TR_MAP_WORDS];
+  __shared__ uint32_t wave_total[RO_WAVES];
+  const uint32_t e = blockIdx.x;
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  for (int w = t; w < TR_MAP_WORDS; w += RO_THREADS) {
+    hit_w[w] = 0u;
+    kept_w[w] = 0u;
+  }
+  block_sync();
+  const int64_t lo = event_start[e];
+  const uint32_t H = sc.info[2 * e];  // hit pads of S (0 for an event without rows)
+  for (uint32_t k = (uint32_t)t; k < H; k += RO_THREADS) {
+    const uint32_t p = sc.hit[lo + k], bit = 1u << (p & 31u);
+    atomicOr(&hit_w[p >> 5], bit);
+    if (sc.rank[lo + k] >= 0) atomicOr(&kept_w[p >> 5], bit);
+  }
+  block_sync();
+  const uint64_t event = first_event + e;
+  uint32_t* noise_w = maps.noise + (size_t)e * TR_MAP_WORDS;
+  for (int w = wave; w < TR_MAP_WORDS; w += RO_WAVES) {
+    uint32_t cand = ro.channels[w] & ~hit_w[w];  // the noise-only pads of S in this word
+    uint32_t nw = 0u;
+    if (ro.full) {
+      nw = cand;
+    } else {
+      while (cand) {  // uniform
+        const int b = __builtin_ctz(cand);
+        cand &= cand - 1u;
+        if (noise_only_kept(tr, nz, ro, seed, event, 32u * (uint32_t)w + (uint32_t)b, lane)) nw |= 1u << b;
+      }
+    }
+    if (lane == 0) {
+      noise_w[w] = nw;
+      kept_w[w] |= nw;
+    }
+  }
+  block_sync();
+  // exclusive prefix of the words' popcounts: the kept pads of the event below word w
+  const uint32_t c = t < TR_MAP_WORDS ? (uint32_t)__popc(kept_w[t]) : 0u;
+  uint32_t incl = c;
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t up = __shfl_up(incl, off);
+    incl += lane >= off ? up : 0u;
+  }
+  if (lane == 63) wave_total[wave] = incl;
+  block_sync();
+  uint32_t before = incl - c;
+  for (int w = 0; w < wave; ++w) before += wave_total[w];
+  if (t < TR_MAP_WORDS) {
+    before_w[t] = before;
+    maps.kept[(size_t)e * TR_MAP_WORDS + t] = kept_w[t];
+    maps.before[(size_t)e * TR_MAP_WORDS + t] = before;
+  }
+  if (t == RO_THREADS - 1) kept[e] = before + c;
+  block_sync();
+  // the hit pads' ranks among all kept pads of the event (ascending pad, hit and noise-only interleaved)
+  for (uint32_t k = (uint32_t)t; k < H; k += RO_THREADS) {
+    if (sc.rank[lo + k] < 0) continue;
+    const uint32_t p = sc.hit[lo + k];
+    sc.rank[lo + k] = (int32_t)(before_w[p >> 5] + (uint32_t)__popc(kept_w[p >> 5] & ((1u << (p & 31u)) - 1u)));
+  }
+}
+
+__global__ __launch_bounds__(RO_THREADS) void trace_noise_write_kernel(TraceNoiseDev nz, uint64_t seed,
+                                                                       uint64_t first_event, TraceMaps maps,
+                                                                       const int64_t* __restrict__ kept_start,
+                                                                       int32_t* __restrict__ pads,
+                                                                       int16_t* __restrict__ samples,
+                                                                       int64_t* __restrict__ out_labels,
+                                                                       unsigned long long* __restrict__ sums) {
+  __shared__ uint32_t noise_cdf[ATTPC_MAX_NOISE_LEVELS];
+  __shared__ uint16_t noise_guide[256];
+  __shared__ unsigned long long wave_sum[RO_WAVES][2];
+  const uint32_t e = blockIdx.x;
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t out0 = kept_start[e];
+  if (kept_start[e + 1] == out0) return;  // uniform
+  if (nz.n_levels > 0) {                  // uniform
+    for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += RO_THREADS) noise_cdf[i] = nz.cdf[i];
+    if (t < 256) noise_guide[t] = nz.guide[t];
+  }
+  block_sync();
+  const unsigned long long event = first_event + e;
+  const size_t m0 = (size_t)e * TR_MAP_WORDS;
+  unsigned long long sample_sum = 0ull, pad_sum = 0ull;  // lane parts
+  for (int w = wave; w < TR_MAP_WORDS; w += RO_WAVES) {
+    uint32_t bits = maps.noise[m0 + w];
+    if (!bits) continue;  // uniform
+    const uint32_t kw = maps.kept[m0 + w], base = maps.before[m0 + w];
+    while (bits) {  // uniform
+      const int b = __builtin_ctz(bits);
+      bits &= bits - 1u;
+      const uint32_t pad = 32u * (uint32_t)w + (uint32_t)b;
+      const int64_t o = out0 + base + __popc(kw & ((1u << b) - 1u));
+      const int ped = nz.pedestals ? (int)nz.pedestals[pad] : 0;
+      int n[8];
+      noise_values(n, nz, noise_cdf, noise_guide, seed, event, pad, lane);
+      int16_t* dst = samples + o * ATTPC_NUM_TB;
+      for (int s = 0; s < 8; ++s) {
+        const int j = lane + 64 * s;
+        int v = ped + n[s];  // s_p[j] = 0
+        v = v < 0 ? 0 : (v > 4095 ? 4095 : v);
+        dst[j] = (int16_t)v;
+        sample_sum += (unsigned long long)(long long)v * (unsigned long long)(j + 1);
+      }
+      if (lane == 0) {
+        pads[o] = (int32_t)pad;
+        out_labels[o] = -1;
+        pad_sum += (event << 14) + (unsigned long long)pad;
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    sample_sum += __shfl_xor(sample_sum, off);
+    pad_sum += __shfl_xor(pad_sum, off);
+  }
+  if (lane == 0) {
+    wave_sum[wave][0] = sample_sum;
+    wave_sum[wave][1] = pad_sum;
+  }
+  block_sync();
+  if (t < 2) {
+    unsigned long long v = 0ull;
+    for (int w = 0; w < RO_WAVES; ++w) v += wave_sum[w][t];
+    atomicAdd(sums + t, v);
+  }
+}
+
+void launch_trace_scan(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, const TraceReadoutDev& ro,
+                       uint64_t seed, uint32_t n_events, uint64_t first_event, const int64_t* event_start, TraceScratch sc,
+                       uint32_t* kept, TraceMaps maps) {
+  hipLaunchKernelGGL(trace_scan_kernel, dim3(n_events), dim3(RO_THREADS), 0, s, tr, noise ? *noise : TraceNoiseDev{}, ro,
+                     seed, first_event, event_start, sc, kept, maps);
+}
+void launch_trace_noise_write(hipStream_t s, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
+                              uint64_t first_event, TraceMaps maps, const int64_t* kept_start, int32_t* pads,
+                              int16_t* samples, int64_t* out_labels, unsigned long long* sums) {
+  hipLaunchKernelGGL(trace_noise_write_kernel, dim3(n_events), dim3(RO_THREADS), 0, s, noise ? *noise : TraceNoiseDev{},
+                     seed, first_event, maps, kept_start, pads, samples, out_labels, sums);
 }
 
 }  // namespace attpc

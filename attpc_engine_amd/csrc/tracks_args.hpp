@@ -98,11 +98,38 @@ struct TraceNoiseDev {
   int32_t min_level;
   uint32_t domain;            // DOMAIN_TRACE_NOISE | stream
 };
+// readout of noise-only pads (attpc_trace_configure_readout, PARTIAL / FULL)
+constexpr int TR_MAP_WORDS = ATTPC_NUM_PADS / 32;  // words of a per-event pad bitmap
+constexpr int32_t TRACE_CUT_DRAW = 0;    // a noise-only pad of PARTIAL is kept iff some u_j >= cut
+constexpr int32_t TRACE_CUT_ALWAYS = 1;  // ... always (c <= 0)
+constexpr int32_t TRACE_CUT_NEVER = 2;   // ... never (c > n_levels - 1, or no noise table)
+struct TraceReadoutDev {
+  const uint32_t* channels;  // [TR_MAP_WORDS] bit p % 32 of word p / 32: pad p is in the readout set S
+  int32_t full;              // ATTPC_READOUT_FULL: every pad of S is kept
+  int32_t cut_kind;          // TRACE_CUT_* (the pedestal terms of the decision rule come on top)
+  uint32_t cut;              // cdf[c - 1] (TRACE_CUT_DRAW)
+};
+// per-event bitmaps of a chunk in readout ([events][TR_MAP_WORDS] each): the noise-only kept pads, every kept pad, and
+// the number of kept pads below each word
+struct TraceMaps {
+  uint32_t* noise;
+  uint32_t* kept;
+  uint32_t* before;
+};
 // kept[e]: kept pad rows of event e (the count pass works out every trace, keeps the ranks in scratch).
-// noise == nullptr: the noiseless kernels
+// noise == nullptr: the noiseless kernels; ro == nullptr: hit-mode readout
 void launch_trace_count(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
-                        TraceScratch sc, uint32_t* kept);
+                        TraceScratch sc, uint32_t* kept, const TraceReadoutDev* ro);
+// behind the count pass with ro: the noise-only verdicts of every event (empty ones included), kept[e] and the hit pads'
+// ranks over the union of kept pads, the maps of the noise write
+void launch_trace_scan(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, const TraceReadoutDev& ro,
+                       uint64_t seed, uint32_t n_events, uint64_t first_event, const int64_t* event_start, TraceScratch sc,
+                       uint32_t* kept, TraceMaps maps);
+// the noise-only rows (label -1) at kept_start[e] + rank; the checksums as launch_trace_write
+void launch_trace_noise_write(hipStream_t s, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
+                              uint64_t first_event, TraceMaps maps, const int64_t* kept_start, int32_t* pads,
+                              int16_t* samples, int64_t* out_labels, unsigned long long* sums);
 // the kept rows at kept_start[e] + rank; sums[0] += sample checksum, sums[1] += pad checksum (event = first_event + e)
 void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,

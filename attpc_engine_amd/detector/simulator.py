@@ -212,6 +212,7 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
             offsets, pads, samples, labels, raw_points, _ = simulate_batch_traces(
                 momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim, first_event=start,
                 response=writer.response, threshold=writer.threshold, offset=writer.offset, **writer.noise_kwargs(),
+                **writer.readout_kwargs(),
             )
             for i in range(stop - start):
                 if raw_points[i] == 0:

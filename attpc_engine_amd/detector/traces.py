@@ -10,6 +10,11 @@ Electronic noise and per-pad pedestals are opt-in (``noise_sigma`` or ``noise_ta
 every sample gets its pad's pedestal and one draw from a discrete noise table, a pure function of (seed, global event id,
 pad, sample), and the threshold is taken above the pedestal (include/attpc_engine.h; ``tests/trace_noise_reference.py``
 restates it).  ``gaussian_noise_table`` builds the table of a discretised Gaussian.
+
+The readout of noise-only pads is opt-in too (``readout="partial"`` or ``"full"``, ``readout_pads``): in partial readout
+(zero suppression) every pad of the readout set whose noise crosses the threshold is read out as well, with label -1;
+in full readout every pad of the set is (include/attpc_engine.h; ``tests/readout_reference.py`` restates it).
+``expected_noise_pads`` gives the mean number of noise-only pads a partial readout keeps per event.
 """
 from __future__ import annotations
 
@@ -118,21 +123,128 @@ def configure_noise(ctx: _abi.Context, noise: NoiseSettings) -> None:
     ctx._trace_noise_token = token
 
 
+READOUT_MODES = {"hit": _abi.READOUT_HIT, "partial": _abi.READOUT_PARTIAL, "full": _abi.READOUT_FULL}
+
+
+def readout_mask(readout_pads=None) -> np.ndarray:
+    """The readout set as a uint8 mask [ATTPC_NUM_PADS]: ``None`` = every pad not in BEAM_PADS (the reference drops
+    their charge, transporter.py:164, 237), a boolean mask of ATTPC_NUM_PADS entries, or unique pad ids."""
+    from .beam_pads import BEAM_PADS_ARRAY
+
+    if readout_pads is None:
+        mask = np.ones(_abi.NUM_PADS, dtype=np.uint8)
+        mask[BEAM_PADS_ARRAY] = 0
+        return mask
+    pads = np.asarray(readout_pads)
+    if pads.dtype == np.bool_:
+        if pads.shape != (_abi.NUM_PADS,):
+            raise ValueError(f"a readout_pads mask needs {_abi.NUM_PADS} entries, got shape {pads.shape}")
+        return pads.astype(np.uint8)
+    if pads.ndim != 1 or (pads.size and pads.dtype.kind not in "iu"):
+        raise ValueError("readout_pads must be a boolean mask or a 1-D array of pad ids")
+    if pads.size and (pads.min() < 0 or pads.max() >= _abi.NUM_PADS):
+        raise ValueError(f"readout_pads ids must lie in 0 .. {_abi.NUM_PADS - 1}")
+    if np.unique(pads).size != pads.size:
+        raise ValueError("readout_pads ids repeat")
+    mask = np.zeros(_abi.NUM_PADS, dtype=np.uint8)
+    mask[pads.astype(np.int64)] = 1
+    return mask
+
+
+class ReadoutSettings:
+    """The validated readout of a trace configuration: ``name`` ("hit", "partial", "full"), ``mode``
+    (ATTPC_READOUT_*), ``channels`` uint8 [ATTPC_NUM_PADS] (the readout set S, ignored in hit mode)."""
+
+    def __init__(self, readout: str = "hit", readout_pads=None):
+        if readout not in READOUT_MODES:
+            raise ValueError(f"readout must be one of {sorted(READOUT_MODES)}, got {readout!r}")
+        self.name = readout
+        self.mode = READOUT_MODES[readout]
+        self.channels = np.ascontiguousarray(readout_mask(readout_pads))
+
+    @property
+    def pads(self) -> np.ndarray:
+        """The pad ids of S, ascending."""
+        return np.flatnonzero(self.channels).astype(np.int32)
+
+    def rows_per_event(self) -> int:
+        """Kept rows of every event when known in advance: |S| in full readout, else 0."""
+        return int(self.channels.sum()) if self.mode == _abi.READOUT_FULL else 0
+
+    def token(self):
+        return None if self.mode == _abi.READOUT_HIT else (self.mode, self.channels.tobytes())
+
+
+def configure_readout(ctx: _abi.Context, readout: ReadoutSettings) -> None:
+    """``attpc_trace_configure_readout`` unless this ctx already holds the same readout (decided on its content)."""
+    token = readout.token()
+    if getattr(ctx, "_trace_readout_token", None) == token:
+        return
+    if token is None:
+        ctx.check(ctx.lib.attpc_trace_configure_readout(ctx.handle, None), "attpc_trace_configure_readout")
+    else:
+        desc = _abi.TraceReadoutDesc(readout.mode, 0, _abi.iptr(readout.channels, _abi.C.c_uint8))
+        ctx.check(ctx.lib.attpc_trace_configure_readout(ctx.handle, desc), "attpc_trace_configure_readout")
+    ctx._trace_readout_token = token
+    ctx._trace_readout_rows = readout.rows_per_event()
+
+
+def readout_cutoff(cdf, min_level: int, threshold: float):
+    """The cutoff of the readout's decision rule (include/attpc_engine.h) -> ("always" | "never" | "draw", cut): with
+    c = floor(thr) + 1 - min_level, max_j n_j > thr always (c <= 0), never (c > n_levels - 1; no table: the one level
+    0) or iff some u_j >= cut = cdf[c - 1]."""
+    cdf = np.asarray(cdf, dtype=np.uint32)
+    n_levels = cdf.size + 1 if (cdf.size or min_level) else 1
+    thr = min(max(float(threshold), -16384.0), 16384.0)
+    c = math.floor(thr) + 1 - int(min_level)
+    if c <= 0:
+        return "always", 0
+    if c > n_levels - 1:
+        return "never", 0
+    return "draw", int(cdf[c - 1])
+
+
+def expected_noise_pads(noise_table, threshold: float, readout_pads=None, pedestals=None) -> float:
+    """The mean number of noise-only pads a partial readout keeps per event: sum over the pads p of the readout set of
+    1 - (1 - q_p)^512, q_p the exact probability 2^-32 (2^32 - cut) that one draw reaches the cutoff of the decision
+    rule, with its pedestal terms (a pad with 4095 - ped_p <= thr is never kept, one with -ped_p > thr always).
+    ``noise_table``: (cdf, min_level), or None for no noise; ``readout_pads`` and ``pedestals`` as configure_traces
+    takes them."""
+    cdf, min_level = (np.zeros(0, dtype=np.uint32), 0) if noise_table is None else noise_table
+    noise = NoiseSettings(noise_table=(cdf, min_level), pedestals=pedestals)
+    mask = readout_mask(readout_pads).astype(bool)
+    ped = np.zeros(_abi.NUM_PADS, dtype=np.int64) if noise.pedestals is None else noise.pedestals.astype(np.int64)
+    thr = float(threshold)
+    kind, cut = readout_cutoff(noise.cdf, noise.min_level, thr)
+    if kind == "draw":
+        q = (2.0 ** 32 - cut) / 2.0 ** 32
+        p_draw = -math.expm1(_abi.NUM_TB * math.log1p(-q)) if q < 1.0 else 1.0
+    else:
+        p_draw = 1.0 if kind == "always" else 0.0
+    p = np.where(4095 - ped > thr, np.where(-ped > thr, 1.0, p_draw), 0.0)
+    return float(p[mask].sum())
+
+
 def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold=None, offset: int = 0,
-                     noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0) -> None:
+                     noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
+                     readout: str = "hit", readout_pads=None) -> None:
     """Upload the response, ADC threshold and sample offset of the traces, and their noise (off by default), unless this
     ctx already holds the same ones (decided on their content, as configure_spyral).  ``noise_table``: (cdf, min_level)
     instead of the Gaussian of ``noise_sigma``; ``pedestals``: [ATTPC_NUM_PADS] (or one value for every pad) in
-    0 .. 4095; ``noise_stream`` in [0, 2^31) draws another noise realisation.  Everything is validated before the first
-    call to the library."""
+    0 .. 4095; ``noise_stream`` in [0, 2^31) draws another noise realisation.  ``readout``: "hit" (default: only pads
+    with cloud rows), "partial" (noise-only pads of ``readout_pads`` that cross the threshold too) or "full" (every pad
+    of ``readout_pads``); ``readout_pads``: None = every pad not in BEAM_PADS, a boolean mask [ATTPC_NUM_PADS] or
+    unique pad ids.  Everything is validated before the first call to the library."""
     response, threshold, offset = trace_settings(config, response, threshold, offset)
     noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
+    readout = ReadoutSettings(readout, readout_pads)
     token = (response.tobytes(), threshold, offset)
     if getattr(ctx, "_trace_token", None) != token:
         desc = _abi.TraceDesc(_abi.dptr(response), threshold, offset, 0)
         ctx.check(ctx.lib.attpc_trace_configure(ctx.handle, desc), "attpc_trace_configure")
         ctx._trace_token = token
     configure_noise(ctx, noise)
+    configure_readout(ctx, readout)
 
 
 class TraceArrays:
@@ -174,9 +286,10 @@ def call_with_capacity(ctx: _abi.Context, n_events: int, capacity: int, call, wh
 def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
                           seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
                           response=None, threshold=None, offset: int = 0, capacity_per_event: int = 1024,
-                          noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0):
+                          noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
+                          readout: str = "hit", readout_pads=None):
     """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``; the noise keyed on
-    ``seed`` and the global event ids) ->
+    ``seed`` and the global event ids; ``readout`` / ``readout_pads`` as configure_traces) ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
     before the suppression, stats dict: the cloud's run statistics plus ``n_rows`` / ``sample_checksum`` /
     ``pad_checksum`` of the traces)."""
@@ -188,8 +301,10 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     n = momenta.shape[0]
     seed, first_event, n = _abi.check_id_range(seed, first_event, n)
     keys = species_for(proton_numbers, mass_numbers, indices)
+    ReadoutSettings(readout, readout_pads)  # (validated before the first library call)
     configure_detector(config, keys, ctx)
-    configure_traces(config, ctx, response, threshold, offset, noise_sigma, noise_table, pedestals, noise_stream)
+    configure_traces(config, ctx, response, threshold, offset, noise_sigma, noise_table, pedestals, noise_stream,
+                     readout, readout_pads)
     layout = build_layout(proton_numbers, mass_numbers, indices, keys)
     stats = _abi.RunStats()
 
@@ -197,7 +312,8 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
         return ctx.lib.attpc_det_run_traces(ctx.handle, int(seed), int(first_event), n, layout, _abi.dptr(momenta),
                                             _abi.dptr(vertices), out, stats)
 
-    arrays = call_with_capacity(ctx, n, max(1024, int(capacity_per_event) * n), call, "attpc_det_run_traces")
+    per_event = max(int(capacity_per_event), getattr(ctx, "_trace_readout_rows", 0))
+    arrays = call_with_capacity(ctx, n, max(1024, per_event * n), call, "attpc_det_run_traces")
     offsets, pads, samples, labels = arrays.result()
     return offsets, pads, samples, labels, arrays.event_points, {**stats.as_dict(), **arrays.sums()}
 
@@ -224,5 +340,6 @@ def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray
                                        _abi.dptr(points), _abi.iptr(labels, _abi.C.c_int64), out)
 
     rows = int(offsets[-1] - offsets[0]) if n else 0
+    rows = max(rows, getattr(ctx, "_trace_readout_rows", 0) * n)  # full readout: |S| rows per event
     arrays = call_with_capacity(ctx, n, max(16, rows), call, "attpc_traces_at")
     return (*arrays.result(), arrays.sums())

@@ -174,19 +174,24 @@ class TraceWriter:
     default; ``detector.traces.configure_traces``); ``noise_seed`` keys the noise of ``write`` (event ``event_number``),
     the runs that call ``write_traces`` key it on their own seed.  Every file of a writer with noise records it on the
     group: attributes noise_stream, noise_sigma (NaN for a custom table) and noise_min_level and the dataset noise_cdf;
-    the dataset pedestals when pedestals are given.  Without noise the files are those of the noiseless writer."""
+    the dataset pedestals when pedestals are given.  Without noise the files are those of the noiseless writer.
+    ``readout`` ("hit", "partial" or "full") and ``readout_pads`` read out noise-only pads as well (label -1;
+    ``detector.traces.configure_traces``); off hit mode every file records the attribute readout and the dataset
+    readout_pads (the pad ids of the readout set), in hit mode the files are those of a writer without them."""
 
     def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
                  first_run_number: int = 0, npz_fallback: bool = True, response: np.ndarray | None = None,
                  threshold: float | None = None, offset: int = 0, noise_sigma: float = 0.0, noise_table=None,
-                 pedestals=None, noise_stream: int = 0, noise_seed: int = 0):
-        from .traces import NoiseSettings, trace_settings
+                 pedestals=None, noise_stream: int = 0, noise_seed: int = 0, readout: str = "hit",
+                 readout_pads=None):
+        from .traces import NoiseSettings, ReadoutSettings, trace_settings
 
         self.directory_path = Path(directory_path)
         self.npz_fallback = npz_fallback
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.response = self.response.copy()
         self.noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
+        self.readout = ReadoutSettings(readout, readout_pads)
         self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
         self.max_events_per_file = max_events_per_file
         self.run_number = first_run_number
@@ -208,6 +213,9 @@ class TraceWriter:
             f.create_dataset("noise_cdf", self.noise.cdf)
         if self.noise.pedestals is not None:
             f.create_dataset("pedestals", self.noise.pedestals)
+        if self.readout.token() is not None:
+            f.set_attr("readout", self.readout.name)
+            f.create_dataset("readout_pads", self.readout.pads)
         return f
 
     def noise_kwargs(self) -> dict:
@@ -215,6 +223,10 @@ class TraceWriter:
         n = self.noise
         return {"noise_table": (n.cdf, n.min_level) if n.n_levels else None, "pedestals": n.pedestals,
                 "noise_stream": n.stream}
+
+    def readout_kwargs(self) -> dict:
+        """The readout settings as ``configure_traces`` takes them."""
+        return {"readout": self.readout.name, "readout_pads": self.readout.channels.astype(bool)}
 
     def create_next_file(self) -> None:
         self.run_number += 1
@@ -225,7 +237,8 @@ class TraceWriter:
         from .traces import clouds_to_traces, configure_traces
 
         ctx = _abi.default_context()
-        configure_traces(config, ctx, self.response, self.threshold, self.offset, **self.noise_kwargs())
+        configure_traces(config, ctx, self.response, self.threshold, self.offset, **self.noise_kwargs(),
+                         **self.readout_kwargs())
         data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
         _, pads, samples, out_labels, _ = clouds_to_traces(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
                                                            seed=self.noise_seed, first_event=event_number)

@@ -147,17 +147,19 @@ class Engine:
 
     # ---------------------------------------------------------------- digitised pad traces on the device
     def configure_traces(self, config=None, response=None, threshold=None, offset: int = 0, noise_sigma: float = 0.0,
-                         noise_table=None, pedestals=None, noise_stream: int = 0) -> None:
+                         noise_table=None, pedestals=None, noise_stream: int = 0, readout: str = "hit",
+                         readout_pads=None) -> None:
         """Upload the trace settings (include/attpc_engine.h): the GET response (default get_response(config)), the ADC
         threshold (default ``ElectronicsParams.adc_threshold``; < 0 keeps every hit pad), the sample offset (0 =
         causal, argmax(response) = peak on the arrival bucket) and the electronic noise and pedestals (off by default:
         ``noise_sigma`` ADC counts of Gaussian noise or a ``noise_table`` (cdf, min_level), ``pedestals`` per pad,
-        ``noise_stream``; see ``detector.traces.configure_traces``).  The noise of ``run_traces`` is keyed on its seed
-        and the global event ids."""
+        ``noise_stream``; see ``detector.traces.configure_traces``) and the readout ("hit" by default, "partial" or
+        "full" of the pads ``readout_pads``, default every pad not in BEAM_PADS).  The noise of ``run_traces`` is keyed
+        on its seed and the global event ids."""
         from .detector.traces import configure_traces
 
         configure_traces(config or self.config, self.ctx, response, threshold, offset, noise_sigma, noise_table,
-                         pedestals, noise_stream)
+                         pedestals, noise_stream, readout, readout_pads)
         self._traces_configured = True
 
     def run_traces(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
@@ -190,7 +192,8 @@ class Engine:
                                                 _abi.dptr(p4), _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32), out,
                                                 stats)
 
-        arrays = call_with_capacity(ctx, int(n_events), max(1024, int(capacity_per_event) * int(n_events)), call,
+        per_event = max(int(capacity_per_event), getattr(ctx, "_trace_readout_rows", 0))  # full readout: |S|
+        arrays = call_with_capacity(ctx, int(n_events), max(1024, per_event * int(n_events)), call,
                                     "attpc_sim_run_traces", ctx.pinned_empty if pinned else None)
         offsets, pads, samples, labels = arrays.result()
         return {"vertex": vertex, "p4": p4, "status": status, "offsets": offsets, "pads": pads, "samples": samples,
@@ -210,7 +213,8 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     engine = Engine(pipeline, config, indices, context=context)
     seed = pipeline.seed if seed is None else int(seed)
     if callable(getattr(writer, "write_traces", None)):  # TraceWriter: the pad traces of every non-empty event
-        engine.configure_traces(config, writer.response, writer.threshold, writer.offset, **writer.noise_kwargs())
+        engine.configure_traces(config, writer.response, writer.threshold, writer.offset, **writer.noise_kwargs(),
+                                **writer.readout_kwargs())
         for start in range(0, n_events, batch_size):
             n = min(batch_size, n_events - start)
             res = engine.run_traces(n, seed=seed, first_event=start)

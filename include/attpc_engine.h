@@ -475,7 +475,8 @@ ATTPC_API int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* 
  *   - sample trace_p[j] = min(max(s_p[j] + ped_p + n_p[j], 0), 4095); ped_p the pad's pedestal, an int16 in [0, 4095],
  *     0 without a pedestal array.  Everything after s_p is integer arithmetic.
  *   - a pad row is kept iff max_j (trace_p[j] - ped_p) > thr (strict; thr < 0 keeps every hit pad).
- *   - unchanged: only pads with at least one cloud row get a trace (noise-only pads are not read out), the label rule,
+ *   - unchanged: only pads with at least one cloud row get a trace (noise-only pads are read out only in the readout modes
+ *     of attpc_trace_configure_readout below), the label rule,
  *     row and event order, the CSR offsets, and the definitions of sample_checksum and pad_checksum (taken over the
  *     noisy samples).
  * With n_levels = 0 and no pedestals the result is the noiseless contract exactly (s_p[j] is already in [0, 4095]).
@@ -500,6 +501,50 @@ ATTPC_API int32_t attpc_trace_configure_noise(attpc_ctx* ctx, const attpc_trace_
 ATTPC_API int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events,
                                   const int64_t* offsets, const double* points, const int64_t* labels,
                                   attpc_trace_out* out);
+
+/* ---- readout of noise-only pads: partial (zero-suppressed) and full readout of the GET electronics (opt-in; the
+ * default ATTPC_READOUT_HIT is every trace contract above exactly) ----
+ * A readout mode and a readout set S, a subset of 0 .. ATTPC_NUM_PADS - 1: the pads that have an electronics channel.
+ * Notation as in the noise contract (s_p, ped_p, n_p, thr); without noise n_p = 0 and ped_p = 0.
+ *   - ATTPC_READOUT_HIT: the contracts above; S is ignored.
+ *   - ATTPC_READOUT_PARTIAL: every pad of S is a candidate in every event.  A pad of S with cloud rows keeps its s_p; a
+ *     pad of S without rows is noise-only, s_p[j] = 0.  Both get trace_p[j] = min(max(s_p[j] + ped_p + n_p[j], 0), 4095)
+ *     with the same (seed, e, p, j) draw, and a pad is kept iff max_j (trace_p[j] - ped_p) > thr (strict, as above).
+ *     Cloud rows on pads outside S are dropped (a dead channel).
+ *   - ATTPC_READOUT_FULL: every pad of S is kept; every event has exactly |S| rows.  The traces are those of PARTIAL.
+ *   - both: noise-only rows carry label -1.  Rows come in ascending pad within an event, hit and noise-only rows
+ *     interleaved; events in id order with CSR offsets.  sample_checksum and pad_checksum keep their definitions over
+ *     every kept row; event_points and attpc_run_stats keep their meaning.  An event with no cloud rows still gets its
+ *     noise-only rows -- a host cloud's empty events in attpc_traces_at too, so a call on empty events in full readout
+ *     is a simulated pedestal run.  Callers that follow the reference's empty-event rule (simulator.py:204-205) skip
+ *     the events with event_points == 0, as run_simulation and run_fused do.
+ *   - decision rule (a consequence of the above, what the kernels evaluate): with N = max_j n_j, a noise-only pad of
+ *     PARTIAL is kept iff 4095 - ped_p > thr and (-ped_p > thr or N > thr).  N > thr iff some u_j >= cdf[c - 1], where
+ *     c = floor(thr) + 1 - min_level; c <= 0 makes it always true; c > n_levels - 1, or no noise table (N = 0 then:
+ *     c = floor(thr) + 1 against the one level 0), makes it false.  So for thr >= 0 a noise-only pad is kept iff
+ *     4095 - ped_p > thr and some u_j >= cdf[c - 1]: one u32 compare per sample, no table search; with thr >= 0 and
+ *     c > n_levels - 1 (the default threshold 40 with gaussian_noise_table(5), whose levels end at +-40) no noise-only
+ *     pad is ever kept.  For thr < 0 every pad of S with ped_p < -thr is kept, and any other one with a draw N > thr
+ *     (with a table that has levels >= 0, all but never-seen draws).
+ * Device storage of a readout chunk: 3 x 1 280 B of bitmaps per event beside the trace outputs.  Every readout run
+ * sizes its trace chunks for |S| kept rows per event (about 4 GiB of samples a chunk) until it has seen its own rate
+ * (FULL: always |S|); attpc_traces_at takes its events in chunks of the same size, so a pedestal run of any number of
+ * events holds at most two chunks of outputs on the device.  A run whose events have nothing to scatter (a layout
+ * without simulated nuclei) still gets the noise-only rows of every event. */
+#define ATTPC_READOUT_HIT 0
+#define ATTPC_READOUT_PARTIAL 1
+#define ATTPC_READOUT_FULL 2
+
+typedef struct attpc_trace_readout_desc {
+  int32_t mode;              /* ATTPC_READOUT_* */
+  int32_t reserved;
+  const uint8_t* channels;   /* [ATTPC_NUM_PADS], nonzero = in S; NULL = all pads */
+} attpc_trace_readout_desc;
+
+/* desc == NULL restores ATTPC_READOUT_HIT.  Independent of attpc_trace_configure and attpc_trace_configure_noise: no
+ * call resets another.  ATTPC_E_INVALID for an unknown mode.  Enables the readout in attpc_sim_run_traces,
+ * attpc_det_run_traces, attpc_traces_at and attpc_traces. */
+ATTPC_API int32_t attpc_trace_configure_readout(attpc_ctx* ctx, const attpc_trace_readout_desc* desc);
 
 #ifdef __cplusplus
 }

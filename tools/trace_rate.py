@@ -3,9 +3,11 @@ device-resident events/s (the traces are written to HBM and stay there; only the
 events/s and GB/s into page-locked host arrays (pads, 1 KiB of samples and the label of every kept pad row).  Prints
 one JSON line per workload with kept trace rows and bytes per event.  ``--noise-sigma S`` adds S ADC counts of
 Gaussian electronic noise, ``--pedestal P`` a pedestal of P counts on every pad (both off by default).
+``--readout partial|full`` reads out the noise-only pads of every pad not in BEAM_PADS as well (default hit),
+``--threshold T`` sets the ADC threshold (default the workload's).
 
     python tools/trace_rate.py [--events N] [--deliver-events M] [--reps K] [--workloads o16aa,be10dp]
-                               [--noise-sigma S] [--pedestal P]
+                               [--noise-sigma S] [--pedestal P] [--readout hit|partial|full] [--threshold T]
 """
 from __future__ import annotations
 
@@ -27,6 +29,8 @@ def main() -> None:
     ap.add_argument("--workloads", default="o16aa,be10dp")
     ap.add_argument("--noise-sigma", type=float, default=0.0, help="Gaussian electronic noise, ADC counts (0 = off)")
     ap.add_argument("--pedestal", type=int, default=None, help="pedestal of every pad, ADC counts (default none)")
+    ap.add_argument("--readout", default="hit", choices=["hit", "partial", "full"], help="readout of noise-only pads")
+    ap.add_argument("--threshold", type=float, default=None, help="ADC threshold (default the workload's)")
     args = ap.parse_args()
 
     import numpy as np
@@ -42,7 +46,8 @@ def main() -> None:
     for name in args.workloads.split(","):
         pipeline, config, indices = workloads.WORKLOADS[name]()
         eng = Engine(pipeline, config, indices, context=ctx)
-        eng.configure_traces(config, noise_sigma=args.noise_sigma, pedestals=args.pedestal)
+        eng.configure_traces(config, threshold=args.threshold, noise_sigma=args.noise_sigma, pedestals=args.pedestal,
+                             readout=args.readout)
         lib, seed = ctx.lib, 1
 
         def resident(first):
@@ -62,7 +67,7 @@ def main() -> None:
         rows_per_event = rows / (args.reps * args.events)
 
         n = args.deliver_events
-        cap = int(rows_per_event * n * 1.3) + 4096
+        cap = int(rows_per_event * n * (1.0 if args.readout == "full" else 1.3)) + 4096
         arrays = TraceArrays(n, cap, ctx.pinned_empty)
         stats = _abi.RunStats()
 
@@ -81,7 +86,8 @@ def main() -> None:
         row_bytes = 512 * 2 + 4 + 8
         d_bytes = d_rows / args.reps * row_bytes + 16 * n  # rows + offsets / event points
         print(json.dumps({
-            "workload": name, "noise_sigma": args.noise_sigma, "pedestal": args.pedestal,
+            "workload": name, "noise_sigma": args.noise_sigma, "pedestal": args.pedestal, "readout": args.readout,
+            "threshold": float(config.elec_params.adc_threshold if args.threshold is None else args.threshold),
             "resident_events": args.events, "resident_events_per_s": args.events / t_res,
             "resident_s": times, "trace_rows_per_event": rows_per_event,
             "bytes_written_per_event": rows_per_event * row_bytes,
