@@ -316,6 +316,9 @@ def load_library() -> C.CDLL:
     return lib
 
 
+CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout")
+
+
 class Context:
     """One engine context == one HIP device (single-threaded, like the reference objects)."""
 
@@ -333,6 +336,25 @@ class Context:
         self.handle = handle
         self.device = device
         self._keepalive: list = []  # host arrays referenced by descriptors during configure
+        # what the device holds, as far as this shim uploaded it: a content token per configure slot (None = unknown),
+        self._tokens: dict = dict.fromkeys(CONFIGURE_SLOTS)
+        self._kin_owner: int | None = None  # id() of the KinematicsPipeline whose tables attpc_kin_configure got,
+        self._trace_readout_rows = 0  # and the rows every event keeps in a full trace readout (|S|, else 0)
+
+    def configure(self, slot: str, token, call: str, desc) -> None:
+        """``lib.<call>(handle, desc)`` unless ``slot`` already holds the content ``token`` (a context that was never
+        configured holds None, which is also the token of "off" for the noise and the readout)."""
+        if self._tokens[slot] == token:
+            return
+        self.check(getattr(self.lib, call)(self.handle, desc), call)
+        self._tokens[slot] = token
+
+    def forget(self, slot: str) -> None:
+        """Drop the token of ``slot``: for whoever configures through the C ABI directly, after which the token no
+        longer describes the device.  KeyError for a name that is not one of CONFIGURE_SLOTS."""
+        if slot not in self._tokens:
+            raise KeyError(slot)
+        self._tokens[slot] = None
 
     def check(self, status: int, what: str) -> None:
         if status != OK:

@@ -13,6 +13,7 @@ import numpy as np
 from numpy.random import Generator, default_rng
 
 from .. import _abi
+from ..outputs import RowArrays, call_with_capacity
 from .luts import build_det_desc, build_layout, species_for
 from .parameters import Config
 from .writer import SimulationWriter
@@ -61,10 +62,7 @@ def configure_detector(config: Config, species_keys: list[tuple[int, int]], ctx:
     # (the tables are memoised on their inputs' content, luts.py: their keys stand for them; a table without a key --
     #  a target object that cannot be compared by value -- is hashed itself)
     token = (_digest(desc, [arr for arr, key in zip(keep, keys) if key is None]), tuple(keys))
-    if getattr(ctx, "_det_token", None) == token:
-        return
-    ctx.check(ctx.lib.attpc_det_configure(ctx.handle, desc), "attpc_det_configure")
-    ctx._det_token = token
+    ctx.configure("det", token, "attpc_det_configure", desc)
     del keep
 
 
@@ -82,11 +80,31 @@ def configure_spyral(config: Config, ctx: _abi.Context, response: np.ndarray | N
     desc = _abi.SpyralDesc(_abi.dptr(response), _abi.dptr(centers), _abi.dptr(sizes), len(sizes),
                            int(config.elec_params.windows_edge), int(config.elec_params.micromegas_edge), 0,
                            float(config.det_params.length), float(config.elec_params.adc_threshold))
-    token = _digest(desc, [response, centers, sizes])
-    if getattr(ctx, "_spyral_token", None) == token:
-        return
-    ctx.check(ctx.lib.attpc_spyral_configure(ctx.handle, desc), "attpc_spyral_configure")
-    ctx._spyral_token = token
+    ctx.configure("spyral", _digest(desc, [response, centers, sizes]), "attpc_spyral_configure", desc)
+
+
+def run_batch(call: str, momenta, vertices, proton_numbers, mass_numbers, config: Config, seed, indices, first_event,
+              ctx: _abi.Context | None, capacity_per_event: int, configure=None, **how):
+    """What simulate_batch, simulate_batch_spyral and simulate_batch_traces share: the inputs as the C ABI takes them,
+    the detector on ``ctx`` (``configure_detector``), then the mode's own settings (``configure(ctx)``, which may return
+    the rows per event the mode is known to need), the layout and ``lib.<call>`` under ``call_with_capacity(**how)``
+    -> (the output holder, the run's RunStats)."""
+    ctx = ctx or _abi.default_context()
+    momenta = np.ascontiguousarray(momenta, dtype=np.float64)
+    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+    seed, first_event, n = _abi.check_id_range(seed, first_event, momenta.shape[0])
+    keys = species_for(proton_numbers, mass_numbers, indices)
+    configure_detector(config, keys, ctx)
+    known = configure(ctx) if configure else None
+    per_event = max(int(capacity_per_event), known or 0)
+    layout = build_layout(proton_numbers, mass_numbers, indices, keys)
+    stats = _abi.RunStats()
+
+    def run(out):
+        return getattr(ctx.lib, call)(ctx.handle, seed, first_event, n, layout, _abi.dptr(momenta), _abi.dptr(vertices),
+                                      out, stats)
+
+    return call_with_capacity(ctx, n, max(1024, per_event * n), run, call, stats, **how), stats
 
 
 def simulate_batch(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers,
@@ -94,33 +112,10 @@ def simulate_batch(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, ma
                    ctx: _abi.Context | None = None, capacity_per_event: int = 16384):
     """simulate() for n events: momenta [n,N,4], vertices [n,3] ->
     (offsets [n+1], points [P,3], labels [P], stats dict)."""
-    ctx = ctx or _abi.default_context()
-    momenta = np.ascontiguousarray(momenta, dtype=np.float64)
-    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
-    n = momenta.shape[0]
-    seed, first_event, n = _abi.check_id_range(seed, first_event, n)
-    keys = species_for(proton_numbers, mass_numbers, indices)
-    configure_detector(config, keys, ctx)
-    layout = build_layout(proton_numbers, mass_numbers, indices, keys)
-    capacity = max(1024, int(capacity_per_event) * n)
-    while True:
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        points = np.empty((capacity, 3), dtype=np.float64)
-        labels = np.empty(capacity, dtype=np.int64)
-        out = _abi.CloudOut(capacity, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(points),
-                            _abi.iptr(labels, _abi.C.c_int64))
-        stats = _abi.RunStats()
-        status = ctx.lib.attpc_det_run(
-            ctx.handle, int(seed), int(first_event), n, layout, _abi.dptr(momenta),
-            _abi.dptr(vertices), out, stats,
-        )
-        if status == _abi.E_CAPACITY:
-            capacity = int(stats.n_points) + 1024
-            continue
-        ctx.check(status, "attpc_det_run")
-        break
-    total = int(offsets[n])
-    return offsets, points[:total], labels[:total], stats.as_dict()
+    arrays, stats = run_batch("attpc_det_run", momenta, vertices, proton_numbers, mass_numbers, config, seed, indices,
+                              first_event, ctx, capacity_per_event, holder=RowArrays, width=3, event_points=False,
+                              slack=1024)
+    return (*arrays.result(), stats.as_dict())
 
 
 def simulate_batch_spyral(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers,
@@ -131,35 +126,11 @@ def simulate_batch_spyral(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     writer.py:194-238) for n events in one launch sequence, all on the device (``attpc_det_run_spyral``) ->
     (offsets [n+1], rows [P',8], labels [P'], event_points [n] = cloud rows of every event BEFORE the threshold,
     stats dict)."""
-    ctx = ctx or _abi.default_context()
-    momenta = np.ascontiguousarray(momenta, dtype=np.float64)
-    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
-    n = momenta.shape[0]
-    seed, first_event, n = _abi.check_id_range(seed, first_event, n)
-    keys = species_for(proton_numbers, mass_numbers, indices)
-    configure_detector(config, keys, ctx)
-    configure_spyral(config, ctx, response)
-    layout = build_layout(proton_numbers, mass_numbers, indices, keys)
-    capacity = max(1024, int(capacity_per_event) * n)
-    while True:
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        rows = np.empty((capacity, 8), dtype=np.float64)
-        labels = np.empty(capacity, dtype=np.int64)
-        event_points = np.zeros(n, dtype=np.int64)
-        out = _abi.CloudOut(capacity, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(rows),
-                            _abi.iptr(labels, _abi.C.c_int64), _abi.iptr(event_points, _abi.C.c_int64))
-        stats = _abi.RunStats()
-        status = ctx.lib.attpc_det_run_spyral(
-            ctx.handle, int(seed), int(first_event), n, layout, _abi.dptr(momenta),
-            _abi.dptr(vertices), out, stats,
-        )
-        if status == _abi.E_CAPACITY:
-            capacity = int(stats.n_points) + 1024
-            continue
-        ctx.check(status, "attpc_det_run_spyral")
-        break
-    total = int(offsets[n])
-    return offsets, rows[:total], labels[:total], event_points, stats.as_dict()
+    arrays, stats = run_batch("attpc_det_run_spyral", momenta, vertices, proton_numbers, mass_numbers, config, seed,
+                              indices, first_event, ctx, capacity_per_event,
+                              configure=lambda ctx: configure_spyral(config, ctx, response), holder=RowArrays, width=8,
+                              slack=1024)
+    return (*arrays.result(), arrays.event_points, stats.as_dict())
 
 
 def simulate(momenta: np.ndarray, vertex: np.ndarray, proton_numbers: np.ndarray,
@@ -174,6 +145,34 @@ def simulate(momenta: np.ndarray, vertex: np.ndarray, proton_numbers: np.ndarray
     _, points, labels, _ = simulate_batch(momenta, vertex, proton_numbers, mass_numbers, config,
                                           seed, list(indices))
     return points, labels
+
+
+def delivery_of(writer, config: Config):
+    """What a run hands ``writer`` per event, chosen once from what the writer offers -> (kind, emit): "traces" with
+    ``emit(pads, samples, labels, event)`` (TraceWriter.write_traces), "rows" with ``emit(rows, labels, event)``
+    (presorted rows to SpyralWriter.write_rows) or "cloud" with ``emit(points, labels, event)`` (the plain ``write`` of
+    any SimulationWriter)."""
+    if callable(getattr(writer, "write_traces", None)):
+        return "traces", writer.write_traces
+    if callable(getattr(writer, "write_rows", None)):
+        return "rows", lambda rows, labels, event: writer.write_rows(rows, labels, event, presorted=True)
+    return "cloud", lambda points, labels, event: writer.write(points, labels, config, event)
+
+
+def deliver_events(writer, n_events: int, batch_size: int, batch, emit) -> None:
+    """The event loop of run_simulation and run_fused: ``batch(start, stop)`` -> (offsets, event_points, *arrays) of
+    the events start .. stop - 1 in CSR form; every non-empty event's slices go to ``emit`` in event order, then the
+    writer is closed.  Empty (simulator.py:204-205) is decided on the cloud BEFORE any threshold, ``event_points[i] ==
+    0``; a batch without event_points (None: a plain cloud) on its rows."""
+    for start in range(0, n_events, batch_size):
+        stop = min(n_events, start + batch_size)
+        offsets, event_points, *arrays = batch(start, stop)
+        for i in range(stop - start):
+            lo, hi = offsets[i], offsets[i + 1]
+            if (hi == lo) if event_points is None else (event_points[i] == 0):
+                continue
+            emit(*(a[lo:hi] for a in arrays), start + i)
+    writer.close()
 
 
 def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
@@ -201,45 +200,25 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     print(f"Output will be written to {writer.get_directory_name()}.")
     rng = default_rng(seed)
     run_seed = int(rng.integers(0, 1 << 63))
-    fused = callable(getattr(writer, "write_rows", None))
-    traces = callable(getattr(writer, "write_traces", None))
-    for start in range(0, n_events, batch_size):
-        stop = min(n_events, start + batch_size)
+    kind, emit = delivery_of(writer, config)
+
+    def batch(start, stop):
         vertices, momenta = reader.read(start, stop)
-        if traces:  # TraceWriter: the pad traces are made on the device behind the scatter (attpc_det_run_traces)
+        args = (momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim)
+        if kind == "traces":  # the pad traces are made on the device behind the scatter (attpc_det_run_traces)
             from .traces import simulate_batch_traces
 
             offsets, pads, samples, labels, raw_points, _ = simulate_batch_traces(
-                momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim, first_event=start,
-                response=writer.response, threshold=writer.threshold, offset=writer.offset, **writer.noise_kwargs(),
-                **writer.readout_kwargs(),
-            )
-            for i in range(stop - start):
-                if raw_points[i] == 0:
-                    continue  # simulator.py:204-205
-                lo, hi = offsets[i], offsets[i + 1]
-                writer.write_traces(pads[lo:hi], samples[lo:hi], labels[lo:hi], start + i)
-            continue
-        if fused:
+                *args, first_event=start, response=writer.response, threshold=writer.threshold, offset=writer.offset,
+                **writer.noise_kwargs(), **writer.readout_kwargs())
+            return offsets, raw_points, pads, samples, labels
+        if kind == "rows":
             offsets, rows, labels, raw_points, _ = simulate_batch_spyral(
-                momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim,
-                first_event=start, response=getattr(writer, "response", None),
-            )
-            for i in range(stop - start):
-                if raw_points[i] == 0:
-                    continue  # simulator.py:204-205: decided on the cloud BEFORE the threshold
-                writer.write_rows(rows[offsets[i]:offsets[i + 1]], labels[offsets[i]:offsets[i + 1]], start + i,
-                                  presorted=True)
-            continue
-        offsets, points, labels, _ = simulate_batch(
-            momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim,
-            first_event=start,
-        )
-        for i in range(stop - start):
-            lo, hi = offsets[i], offsets[i + 1]
-            if hi == lo:
-                continue  # simulator.py:204-205
-            writer.write(points[lo:hi], labels[lo:hi], config, start + i)
-    writer.close()
+                *args, first_event=start, response=getattr(writer, "response", None))
+            return offsets, raw_points, rows, labels
+        offsets, points, labels, _ = simulate_batch(*args, first_event=start)
+        return offsets, None, points, labels
+
+    deliver_events(writer, n_events, batch_size, batch, emit)
     print("Done.")
     print("----------------------------------------")

@@ -23,7 +23,7 @@ import math
 import numpy as np
 
 from .. import _abi
-from .luts import build_layout, species_for
+from ..outputs import TraceArrays, call_with_capacity  # noqa: F401 (TraceArrays stays importable from here)
 from .parameters import Config
 
 
@@ -110,17 +110,12 @@ class NoiseSettings:
 
 def configure_noise(ctx: _abi.Context, noise: NoiseSettings) -> None:
     """``attpc_trace_configure_noise`` unless this ctx already holds the same noise (decided on its content)."""
-    token = noise.token()
-    if getattr(ctx, "_trace_noise_token", None) == token:
-        return
-    if token is None:
-        ctx.check(ctx.lib.attpc_trace_configure_noise(ctx.handle, None), "attpc_trace_configure_noise")
-    else:
+    desc = None
+    if noise.on:
         desc = _abi.TraceNoiseDesc(_abi.iptr(noise.cdf, _abi.C.c_uint32), noise.n_levels, noise.min_level,
                                    None if noise.pedestals is None else _abi.iptr(noise.pedestals, _abi.C.c_int16),
                                    noise.stream, 0)
-        ctx.check(ctx.lib.attpc_trace_configure_noise(ctx.handle, desc), "attpc_trace_configure_noise")
-    ctx._trace_noise_token = token
+    ctx.configure("trace_noise", noise.token(), "attpc_trace_configure_noise", desc)
 
 
 READOUT_MODES = {"hit": _abi.READOUT_HIT, "partial": _abi.READOUT_PARTIAL, "full": _abi.READOUT_FULL}
@@ -177,15 +172,10 @@ class ReadoutSettings:
 
 def configure_readout(ctx: _abi.Context, readout: ReadoutSettings) -> None:
     """``attpc_trace_configure_readout`` unless this ctx already holds the same readout (decided on its content)."""
-    token = readout.token()
-    if getattr(ctx, "_trace_readout_token", None) == token:
-        return
-    if token is None:
-        ctx.check(ctx.lib.attpc_trace_configure_readout(ctx.handle, None), "attpc_trace_configure_readout")
-    else:
+    token, desc = readout.token(), None
+    if token is not None:
         desc = _abi.TraceReadoutDesc(readout.mode, 0, _abi.iptr(readout.channels, _abi.C.c_uint8))
-        ctx.check(ctx.lib.attpc_trace_configure_readout(ctx.handle, desc), "attpc_trace_configure_readout")
-    ctx._trace_readout_token = token
+    ctx.configure("trace_readout", token, "attpc_trace_configure_readout", desc)
     ctx._trace_readout_rows = readout.rows_per_event()
 
 
@@ -238,49 +228,10 @@ def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold
     response, threshold, offset = trace_settings(config, response, threshold, offset)
     noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
     readout = ReadoutSettings(readout, readout_pads)
-    token = (response.tobytes(), threshold, offset)
-    if getattr(ctx, "_trace_token", None) != token:
-        desc = _abi.TraceDesc(_abi.dptr(response), threshold, offset, 0)
-        ctx.check(ctx.lib.attpc_trace_configure(ctx.handle, desc), "attpc_trace_configure")
-        ctx._trace_token = token
+    ctx.configure("trace", (response.tobytes(), threshold, offset), "attpc_trace_configure",
+                  _abi.TraceDesc(_abi.dptr(response), threshold, offset, 0))
     configure_noise(ctx, noise)
     configure_readout(ctx, readout)
-
-
-class TraceArrays:
-    """Caller arrays of one trace call and the ``attpc_trace_out`` that points at them.  ``make``: allocator
-    ``(shape, dtype) -> array`` (page-locked memory for ``Engine.run_traces(pinned=True)``)."""
-
-    def __init__(self, n_events: int, capacity: int, make=None):
-        make = make or (lambda shape, dtype: np.empty(shape, dtype=dtype))
-        self.offsets = np.zeros(n_events + 1, dtype=np.int64)
-        self.pads = make((capacity,), np.int32)
-        self.samples = make((capacity, _abi.NUM_TB), np.int16)
-        self.labels = make((capacity,), np.int64)
-        self.event_points = np.zeros(n_events, dtype=np.int64)
-        self.out = _abi.TraceOut(capacity, _abi.iptr(self.offsets, _abi.C.c_int64), _abi.iptr(self.pads, _abi.C.c_int32),
-                                 _abi.iptr(self.samples, _abi.C.c_int16), _abi.iptr(self.labels, _abi.C.c_int64),
-                                 _abi.iptr(self.event_points, _abi.C.c_int64))
-
-    def sums(self) -> dict:
-        return {"n_rows": int(self.out.n_rows), "sample_checksum": int(self.out.sample_checksum),
-                "pad_checksum": int(self.out.pad_checksum)}
-
-    def result(self):
-        total = int(self.out.n_rows)
-        return self.offsets, self.pads[:total], self.samples[:total], self.labels[:total]
-
-
-def call_with_capacity(ctx: _abi.Context, n_events: int, capacity: int, call, what: str, make=None) -> TraceArrays:
-    """Run ``call(out)`` with arrays of ``capacity`` rows; on ATTPC_E_CAPACITY once more with the exact row count."""
-    while True:
-        arrays = TraceArrays(n_events, max(1, int(capacity)), make)
-        status = call(arrays.out)
-        if status == _abi.E_CAPACITY and arrays.out.n_rows > capacity:
-            capacity = int(arrays.out.n_rows)
-            continue
-        ctx.check(status, what)
-        return arrays
 
 
 def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
@@ -293,29 +244,18 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
     before the suppression, stats dict: the cloud's run statistics plus ``n_rows`` / ``sample_checksum`` /
     ``pad_checksum`` of the traces)."""
-    from .simulator import configure_detector
+    from .simulator import run_batch
 
-    ctx = ctx or _abi.default_context()
-    momenta = np.ascontiguousarray(momenta, dtype=np.float64)
-    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
-    n = momenta.shape[0]
-    seed, first_event, n = _abi.check_id_range(seed, first_event, n)
-    keys = species_for(proton_numbers, mass_numbers, indices)
     ReadoutSettings(readout, readout_pads)  # (validated before the first library call)
-    configure_detector(config, keys, ctx)
-    configure_traces(config, ctx, response, threshold, offset, noise_sigma, noise_table, pedestals, noise_stream,
-                     readout, readout_pads)
-    layout = build_layout(proton_numbers, mass_numbers, indices, keys)
-    stats = _abi.RunStats()
 
-    def call(out):
-        return ctx.lib.attpc_det_run_traces(ctx.handle, int(seed), int(first_event), n, layout, _abi.dptr(momenta),
-                                            _abi.dptr(vertices), out, stats)
+    def configure(ctx):
+        configure_traces(config, ctx, response, threshold, offset, noise_sigma, noise_table, pedestals, noise_stream,
+                         readout, readout_pads)
+        return ctx._trace_readout_rows  # full readout: |S| rows per event
 
-    per_event = max(int(capacity_per_event), getattr(ctx, "_trace_readout_rows", 0))
-    arrays = call_with_capacity(ctx, n, max(1024, per_event * n), call, "attpc_det_run_traces")
-    offsets, pads, samples, labels = arrays.result()
-    return offsets, pads, samples, labels, arrays.event_points, {**stats.as_dict(), **arrays.sums()}
+    arrays, stats = run_batch("attpc_det_run_traces", momenta, vertices, proton_numbers, mass_numbers, config, seed,
+                              indices, first_event, ctx, capacity_per_event, configure)
+    return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **arrays.sums()})
 
 
 def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,
@@ -340,6 +280,6 @@ def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray
                                        _abi.dptr(points), _abi.iptr(labels, _abi.C.c_int64), out)
 
     rows = int(offsets[-1] - offsets[0]) if n else 0
-    rows = max(rows, getattr(ctx, "_trace_readout_rows", 0) * n)  # full readout: |S| rows per event
+    rows = max(rows, ctx._trace_readout_rows * n)  # full readout: |S| rows per event
     arrays = call_with_capacity(ctx, n, max(16, rows), call, "attpc_traces_at")
     return (*arrays.result(), arrays.sums())

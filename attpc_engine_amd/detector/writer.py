@@ -91,17 +91,16 @@ class _H5RunFile:
         self.file.close()
 
 
-class SpyralWriter:
-    """Spyral-format output split into files of ``max_events_per_file`` events
-    (reference writer.py:115-281): ``run_%04d.h5`` / group ``cloud`` / ``cloud_{event}``
-    [P,8] + ``labels_{event}``, attrs orig_run, orig_event, ic_* = -1, and min_event /
-    max_event on the group."""
+class _RollingWriter:
+    """The file-rolling part of SpyralWriter and TraceWriter: ``run_%04d.h5`` (or ``.npz`` without h5py) with one group
+    named ``group``, a new file after ``max_events_per_file`` events (reference writer.py:214-218), and min_event /
+    max_event on the group when a file is closed."""
 
-    def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
-                 first_run_number: int = 0, npz_fallback: bool = True):
+    group = "cloud"
+
+    def __init__(self, directory_path: Path, max_events_per_file: int, first_run_number: int, npz_fallback: bool):
         self.directory_path = Path(directory_path)
         self.npz_fallback = npz_fallback  # without h5py: warn and write .npz (True) or raise (False)
-        self.response = get_response(config).copy()
         self.max_events_per_file = max_events_per_file
         self.run_number = first_run_number
         self.starting_event = 0
@@ -114,11 +113,46 @@ class SpyralWriter:
 
         path = self.directory_path / f"run_{run_number:04d}.h5"
         h5py = hdf5_or_fallback(path, self.npz_fallback)
-        return _H5RunFile(path, h5py) if h5py is not None else _NpzRunFile(path)
+        return _H5RunFile(path, h5py, self.group) if h5py is not None else _NpzRunFile(path, self.group)
 
     def create_next_file(self) -> None:
         self.run_number += 1
         self.file = self._open(self.run_number)
+
+    def _begin_event(self, event_number: int) -> None:
+        """Roll over to the next file if this one is full."""
+        if self.events_written == self.max_events_per_file:
+            self.close()
+            self.create_next_file()
+            self.starting_event = event_number
+            self.events_written = 0
+
+    def _end_event(self, event_number: int) -> None:
+        self.last_event = event_number
+        self.events_written += 1
+
+    def set_number_of_events(self) -> None:
+        self.file.set_attr("min_event", self.starting_event)
+        self.file.set_attr("max_event", self.last_event)
+
+    def get_directory_name(self) -> Path:
+        return self.directory_path
+
+    def close(self) -> None:
+        self.set_number_of_events()
+        self.file.close()
+
+
+class SpyralWriter(_RollingWriter):
+    """Spyral-format output split into files of ``max_events_per_file`` events
+    (reference writer.py:115-281): ``run_%04d.h5`` / group ``cloud`` / ``cloud_{event}``
+    [P,8] + ``labels_{event}``, attrs orig_run, orig_event, ic_* = -1, and min_event /
+    max_event on the group."""
+
+    def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
+                 first_run_number: int = 0, npz_fallback: bool = True):
+        self.response = get_response(config).copy()
+        super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)
 
     def write(self, data: np.ndarray, labels: np.ndarray, config: Config, event_number: int) -> None:
         """[P,3] cloud -> Spyral rows (device), ADC threshold, z-sort, datasets (writer.py:194-255)."""
@@ -135,11 +169,7 @@ class SpyralWriter:
         """Already converted and thresholded rows [P',8]: z-sort (writer.py:236-238) unless the rows
         come ``presorted`` from the device (``Engine.run_spyral``), file roll-over (:214-218), datasets
         and attributes (:240-251)."""
-        if self.events_written == self.max_events_per_file:
-            self.close()
-            self.create_next_file()
-            self.starting_event = event_number
-            self.events_written = 0
+        self._begin_event(event_number)
         if not presorted:
             order = np.argsort(rows[:, 2])
             rows, labels = rows[order], labels[order]
@@ -149,22 +179,10 @@ class SpyralWriter:
              "ic_multiplicity": -1.0, "ic_integral": -1.0, "ic_centroid": -1.0},
         )
         self.file.create_dataset(f"labels_{event_number}", labels)
-        self.last_event = event_number
-        self.events_written += 1
-
-    def set_number_of_events(self) -> None:
-        self.file.set_attr("min_event", self.starting_event)
-        self.file.set_attr("max_event", self.last_event)
-
-    def get_directory_name(self) -> Path:
-        return self.directory_path
-
-    def close(self) -> None:
-        self.set_number_of_events()
-        self.file.close()
+        self._end_event(event_number)
 
 
-class TraceWriter:
+class TraceWriter(_RollingWriter):
     """Digitised GET pad traces (EXTENSION: the reference writes point clouds only) split into files of
     ``max_events_per_file`` events, with SpyralWriter's roll-over and ``.npz`` fallback: ``run_%04d.h5`` / group
     ``trace`` / per event ``trace_{event}`` [R,512] int16, ``pads_{event}`` [R] int32, ``labels_{event}`` [R] int64
@@ -179,6 +197,8 @@ class TraceWriter:
     ``detector.traces.configure_traces``); off hit mode every file records the attribute readout and the dataset
     readout_pads (the pad ids of the readout set), in hit mode the files are those of a writer without them."""
 
+    group = "trace"
+
     def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
                  first_run_number: int = 0, npz_fallback: bool = True, response: np.ndarray | None = None,
                  threshold: float | None = None, offset: int = 0, noise_sigma: float = 0.0, noise_table=None,
@@ -186,26 +206,15 @@ class TraceWriter:
                  readout_pads=None):
         from .traces import NoiseSettings, ReadoutSettings, trace_settings
 
-        self.directory_path = Path(directory_path)
-        self.npz_fallback = npz_fallback
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.response = self.response.copy()
         self.noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
         self.readout = ReadoutSettings(readout, readout_pads)
         self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
-        self.max_events_per_file = max_events_per_file
-        self.run_number = first_run_number
-        self.starting_event = 0
-        self.last_event = 0
-        self.events_written = 0
-        self.file = self._open(self.run_number)
+        super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)
 
     def _open(self, run_number: int):
-        from ..io import hdf5_or_fallback
-
-        path = self.directory_path / f"run_{run_number:04d}.h5"
-        h5py = hdf5_or_fallback(path, self.npz_fallback)
-        f = _H5RunFile(path, h5py, "trace") if h5py is not None else _NpzRunFile(path, "trace")
+        f = super()._open(run_number)
         if self.noise.n_levels:
             f.set_attr("noise_stream", self.noise.stream)
             f.set_attr("noise_sigma", self.noise.sigma)
@@ -228,10 +237,6 @@ class TraceWriter:
         """The readout settings as ``configure_traces`` takes them."""
         return {"readout": self.readout.name, "readout_pads": self.readout.channels.astype(bool)}
 
-    def create_next_file(self) -> None:
-        self.run_number += 1
-        self.file = self._open(self.run_number)
-
     def write(self, data: np.ndarray, labels: np.ndarray, config: Config, event_number: int) -> None:
         """One event's cloud [P,3] -> its traces on the device (``clouds_to_traces``) -> datasets."""
         from .traces import clouds_to_traces, configure_traces
@@ -247,25 +252,9 @@ class TraceWriter:
     def write_traces(self, pads: np.ndarray, samples: np.ndarray, labels: np.ndarray, event_number: int) -> None:
         """One event's kept pad rows, as the device makes them (``Engine.run_traces``, ``simulate_batch_traces``):
         file roll-over, datasets and attributes."""
-        if self.events_written == self.max_events_per_file:
-            self.close()
-            self.create_next_file()
-            self.starting_event = event_number
-            self.events_written = 0
+        self._begin_event(event_number)
         self.file.create_dataset(f"trace_{event_number}", np.asarray(samples, dtype=np.int16).reshape(-1, _abi.NUM_TB),
                                  {"orig_run": self.run_number, "orig_event": event_number})
         self.file.create_dataset(f"pads_{event_number}", np.asarray(pads, dtype=np.int32))
         self.file.create_dataset(f"labels_{event_number}", np.asarray(labels, dtype=np.int64))
-        self.last_event = event_number
-        self.events_written += 1
-
-    def set_number_of_events(self) -> None:
-        self.file.set_attr("min_event", self.starting_event)
-        self.file.set_attr("max_event", self.last_event)
-
-    def get_directory_name(self) -> Path:
-        return self.directory_path
-
-    def close(self) -> None:
-        self.set_number_of_events()
-        self.file.close()
+        self._end_event(event_number)

@@ -13,7 +13,8 @@ import numpy as np
 
 from . import _abi, nuclear_map
 from .detector.luts import build_det_desc, build_layout, species_for
-from .detector.simulator import default_indices
+from .detector.simulator import default_indices, deliver_events, delivery_of
+from .outputs import RowArrays, call_with_capacity
 
 
 class Engine:
@@ -27,6 +28,8 @@ class Engine:
         self.a = pipeline.get_mass_numbers()
         self.n_rows = len(self.z)
         self.indices = list(indices) if indices is not None else default_indices(self.n_rows)
+        self._out_cache = None  # (key, arrays) of the last run with reuse_buffers (call_with_capacity)
+        self._spyral_configured = self._traces_configured = False
         ctx = self.ctx
         kin, keep_k = pipeline.device_desc()
         ctx.check(ctx.lib.attpc_kin_configure(ctx.handle, kin), "attpc_kin_configure")
@@ -35,25 +38,27 @@ class Engine:
         nuclei = [nuclear_map.get_data(z, a) for z, a in self.species]
         det, keep_d = build_det_desc(config, nuclei, ode_substeps=ode_substeps)
         ctx.check(ctx.lib.attpc_det_configure(ctx.handle, det), "attpc_det_configure")
-        ctx._det_token = None
+        ctx.forget("det")  # (what configure_detector last uploaded is no longer what the device holds)
         self.layout = build_layout(self.z, self.a, self.indices, self.species)
         if chunk_events:
             ctx.check(ctx.lib.attpc_set_chunk_events(ctx.handle, int(chunk_events)), "attpc_set_chunk_events")
         del keep_k, keep_d
 
-    def _out_arrays(self, n_events: int, capacity: int, width: int, pinned: bool, reuse: bool):
-        """Output arrays of a delivered run: (offsets, rows [capacity, width], labels, event_points).
-        ``pinned``: page-locked memory (PCIe-rate copies).  ``reuse``: keep them for the next call of
-        the same shape -- the previous call's arrays are then overwritten."""
-        key = (n_events, capacity, width, pinned)
-        cached = getattr(self, "_out_cache", None)
-        if reuse and cached is not None and cached[0] == key:
-            return cached[1]
-        make = self.ctx.pinned_empty if pinned else (lambda shape, dtype: np.empty(shape, dtype=dtype))
-        arrays = (np.zeros(n_events + 1, dtype=np.int64), make((capacity, width), np.float64),
-                  make((capacity,), np.int64), np.zeros(n_events, dtype=np.int64))
-        self._out_cache = (key, arrays) if reuse else None
-        return arrays
+    def _deliver(self, call: str, n_events: int, seed: int, first_event: int, capacity: int, pinned: bool, **how):
+        """One fetched run of ``lib.<call>`` -> (its output holder, the part of the result dict every mode has).
+        ``how``: what call_with_capacity needs to know about the mode (holder, slack, reuse)."""
+        ctx, stats = self.ctx, _abi.RunStats()
+        p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
+        vertex = np.empty((n_events, 3), dtype=np.float64)
+        status = np.empty(n_events, dtype=np.int32)
+
+        def run(out):
+            return getattr(ctx.lib, call)(ctx.handle, seed, first_event, n_events, self.layout, _abi.dptr(p4),
+                                          _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32), out, stats)
+
+        arrays = call_with_capacity(ctx, n_events, capacity, run, call, stats, pinned=pinned, **how)
+        return arrays, {"vertex": vertex, "p4": p4, "status": status, "offsets": arrays.offsets,
+                        "labels": arrays.result()[-1], "event_points": arrays.event_points, "stats": stats.as_dict()}
 
     def hint_next(self, n_events: int, seed: int = 0, first_event: int = 0) -> None:
         """Announce the ``run`` / ``run_spyral`` call after the next one (``attpc_sim_hint_next``): the next call then
@@ -84,25 +89,10 @@ class Engine:
                 "attpc_sim_run",
             )
             return {"stats": stats.as_dict()}
-        p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
-        vertex = np.empty((n_events, 3), dtype=np.float64)
-        status = np.empty(n_events, dtype=np.int32)
-        capacity = max(4096, int(capacity_per_event) * int(n_events))
-        while True:
-            offsets, points, labels, event_points = self._out_arrays(n_events, capacity, 3, pinned, reuse_buffers)
-            out = _abi.CloudOut(capacity, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(points),
-                                _abi.iptr(labels, _abi.C.c_int64), _abi.iptr(event_points, _abi.C.c_int64))
-            rc = ctx.lib.attpc_sim_run(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
-                                       _abi.dptr(p4), _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32),
-                                       out, stats)
-            if rc == _abi.E_CAPACITY:
-                capacity = int(stats.n_points) + 4096
-                continue
-            ctx.check(rc, "attpc_sim_run")
-            break
-        total = int(offsets[-1])
-        return {"vertex": vertex, "p4": p4, "status": status, "offsets": offsets, "points": points[:total],
-                "labels": labels[:total], "event_points": event_points, "stats": stats.as_dict()}
+        arrays, res = self._deliver("attpc_sim_run", n_events, seed, first_event,
+                                    max(4096, int(capacity_per_event) * n_events), pinned, holder=RowArrays, width=3,
+                                    slack=4096, cache=self, reuse=reuse_buffers)
+        return {**res, "points": arrays.result()[1]}
 
     # ---------------------------------------------------------------- Spyral rows on the device
     def configure_spyral(self, config=None) -> None:
@@ -121,29 +111,12 @@ class Engine:
         ``event_points`` [n] = cloud rows of every event before the threshold (an event is "empty" for
         the writer only if that is 0, simulator.py:204-205)."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
-        if not getattr(self, "_spyral_configured", False):
+        if not self._spyral_configured:
             self.configure_spyral()
-        ctx = self.ctx
-        stats = _abi.RunStats()
-        p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
-        vertex = np.empty((n_events, 3), dtype=np.float64)
-        status = np.empty(n_events, dtype=np.int32)
-        capacity = max(4096, int(capacity_per_event) * int(n_events))
-        while True:
-            offsets, rows, labels, event_points = self._out_arrays(n_events, capacity, 8, pinned, reuse_buffers)
-            out = _abi.CloudOut(capacity, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(rows),
-                                _abi.iptr(labels, _abi.C.c_int64), _abi.iptr(event_points, _abi.C.c_int64))
-            rc = ctx.lib.attpc_sim_run_spyral(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
-                                              _abi.dptr(p4), _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32),
-                                              out, stats)
-            if rc == _abi.E_CAPACITY:
-                capacity = int(stats.n_points) + 4096
-                continue
-            ctx.check(rc, "attpc_sim_run_spyral")
-            break
-        total = int(offsets[-1])
-        return {"vertex": vertex, "p4": p4, "status": status, "offsets": offsets, "rows": rows[:total],
-                "labels": labels[:total], "event_points": event_points, "stats": stats.as_dict()}
+        arrays, res = self._deliver("attpc_sim_run_spyral", n_events, seed, first_event,
+                                    max(4096, int(capacity_per_event) * n_events), pinned, holder=RowArrays, width=8,
+                                    slack=4096, cache=self, reuse=reuse_buffers)
+        return {**res, "rows": arrays.result()[1]}
 
     # ---------------------------------------------------------------- digitised pad traces on the device
     def configure_traces(self, config=None, response=None, threshold=None, offset: int = 0, noise_sigma: float = 0.0,
@@ -169,10 +142,8 @@ class Engine:
         labels [R] i64 (``pinned``: page-locked arrays), event_points [n] = cloud rows before the suppression, and the
         kinematics; ``fetch=False``: the traces stay on the device, only ``trace`` (n_rows and both checksums) and the
         cloud's ``stats`` come back."""
-        from .detector.traces import TraceArrays, call_with_capacity
-
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
-        if not getattr(self, "_traces_configured", False):
+        if not self._traces_configured:
             self.configure_traces()
         ctx = self.ctx
         stats = _abi.RunStats()
@@ -183,21 +154,11 @@ class Engine:
             return {"stats": stats.as_dict(), "trace": {"n_rows": int(out.n_rows),
                                                         "sample_checksum": int(out.sample_checksum),
                                                         "pad_checksum": int(out.pad_checksum)}}
-        p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
-        vertex = np.empty((n_events, 3), dtype=np.float64)
-        status = np.empty(n_events, dtype=np.int32)
-
-        def call(out):
-            return ctx.lib.attpc_sim_run_traces(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
-                                                _abi.dptr(p4), _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32), out,
-                                                stats)
-
-        per_event = max(int(capacity_per_event), getattr(ctx, "_trace_readout_rows", 0))  # full readout: |S|
-        arrays = call_with_capacity(ctx, int(n_events), max(1024, per_event * int(n_events)), call,
-                                    "attpc_sim_run_traces", ctx.pinned_empty if pinned else None)
-        offsets, pads, samples, labels = arrays.result()
-        return {"vertex": vertex, "p4": p4, "status": status, "offsets": offsets, "pads": pads, "samples": samples,
-                "labels": labels, "event_points": arrays.event_points, "stats": stats.as_dict(), "trace": arrays.sums()}
+        per_event = max(int(capacity_per_event), ctx._trace_readout_rows)  # full readout: |S|
+        arrays, res = self._deliver("attpc_sim_run_traces", n_events, seed, first_event, max(1024, per_event * n_events),
+                                    pinned)
+        _, pads, samples, _ = arrays.result()
+        return {**res, "pads": pads, "samples": samples, "trace": arrays.sums()}
 
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
@@ -212,26 +173,20 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     the traces made on the device (``Engine.run_traces``) with the writer's noise settings."""
     engine = Engine(pipeline, config, indices, context=context)
     seed = pipeline.seed if seed is None else int(seed)
-    if callable(getattr(writer, "write_traces", None)):  # TraceWriter: the pad traces of every non-empty event
+    kind, emit = delivery_of(writer, config)
+    if kind == "traces":
         engine.configure_traces(config, writer.response, writer.threshold, writer.offset, **writer.noise_kwargs(),
                                 **writer.readout_kwargs())
-        for start in range(0, n_events, batch_size):
-            n = min(batch_size, n_events - start)
-            res = engine.run_traces(n, seed=seed, first_event=start)
-            off, raw = res["offsets"], res["event_points"]
-            for i in range(n):
-                if raw[i] > 0:
-                    writer.write_traces(res["pads"][off[i]:off[i + 1]], res["samples"][off[i]:off[i + 1]],
-                                        res["labels"][off[i]:off[i + 1]], start + i)
-        writer.close()
-        return
-    engine.configure_spyral(config)
-    for start in range(0, n_events, batch_size):
-        n = min(batch_size, n_events - start)
-        res = engine.run_spyral(n, seed=seed, first_event=start)
-        off, raw = res["offsets"], res["event_points"]
-        for i in range(n):
-            if raw[i] > 0:
-                writer.write_rows(res["rows"][off[i]:off[i + 1]], res["labels"][off[i]:off[i + 1]], start + i,
-                                  presorted=True)
-    writer.close()
+    elif kind == "rows":
+        engine.configure_spyral(config)
+    else:
+        raise AttributeError("run_fused needs a writer that offers write_rows or write_traces")
+
+    def batch(start, stop):
+        if kind == "traces":
+            res = engine.run_traces(stop - start, seed=seed, first_event=start)
+            return res["offsets"], res["event_points"], res["pads"], res["samples"], res["labels"]
+        res = engine.run_spyral(stop - start, seed=seed, first_event=start)
+        return res["offsets"], res["event_points"], res["rows"], res["labels"]
+
+    deliver_events(writer, n_events, batch_size, batch, emit)

@@ -187,7 +187,7 @@ class KinematicsPipeline:
         if not is_device_samplable(self):
             return self._run_many_host_sampled(n_events, return_status)
         ctx = self.context
-        if not self._configured or getattr(ctx, "_kin_owner", None) != id(self):
+        if not self._configured or ctx._kin_owner != id(self):
             self.configure_device()
         n_rows = len(self.result)
         p4 = np.empty((n_events, n_rows, 4), dtype=np.float64)

@@ -1,0 +1,93 @@
+"""Caller-side output arrays of a delivered run, and the one capacity retry over them.
+
+A run that delivers clouds, Spyral rows or pad traces writes into arrays the caller owns (``attpc_cloud_out`` /
+``attpc_trace_out``, include/attpc_engine.h) and answers ATTPC_E_CAPACITY, with the rows it needs, when they are too
+small.  ``RowArrays`` and ``TraceArrays`` hold such arrays together with the struct that points at them;
+``call_with_capacity`` is the only place that allocates them, calls and allocates again.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _abi
+
+
+def _host_empty(shape, dtype):
+    return np.empty(shape, dtype=dtype)
+
+
+class RowArrays:
+    """Caller arrays of one cloud (``width`` 3) or Spyral row (``width`` 8) call and the ``attpc_cloud_out`` that
+    points at them.  ``make`` as for TraceArrays; ``event_points=False`` hands the library NULL there."""
+
+    def __init__(self, n_events: int, capacity: int, make=None, width: int = 3, event_points: bool = True):
+        make = make or _host_empty
+        self.offsets = np.zeros(n_events + 1, dtype=np.int64)
+        self.rows = make((capacity, width), np.float64)
+        self.labels = make((capacity,), np.int64)
+        self.event_points = np.zeros(n_events, dtype=np.int64) if event_points else None
+        self.out = _abi.CloudOut(capacity, _abi.iptr(self.offsets, _abi.C.c_int64), _abi.dptr(self.rows),
+                                 _abi.iptr(self.labels, _abi.C.c_int64), _abi.iptr(self.event_points, _abi.C.c_int64))
+
+    def needed(self, stats) -> int:
+        """Rows the last call wanted to deliver: a cloud call reports them in its run statistics."""
+        return int(stats.n_points)
+
+    def result(self):
+        total = int(self.offsets[-1])
+        return self.offsets, self.rows[:total], self.labels[:total]
+
+
+class TraceArrays:
+    """Caller arrays of one trace call and the ``attpc_trace_out`` that points at them.  ``make``: allocator
+    ``(shape, dtype) -> array`` (page-locked memory for ``Engine.run_traces(pinned=True)``)."""
+
+    def __init__(self, n_events: int, capacity: int, make=None):
+        make = make or _host_empty
+        self.offsets = np.zeros(n_events + 1, dtype=np.int64)
+        self.pads = make((capacity,), np.int32)
+        self.samples = make((capacity, _abi.NUM_TB), np.int16)
+        self.labels = make((capacity,), np.int64)
+        self.event_points = np.zeros(n_events, dtype=np.int64)
+        self.out = _abi.TraceOut(capacity, _abi.iptr(self.offsets, _abi.C.c_int64), _abi.iptr(self.pads, _abi.C.c_int32),
+                                 _abi.iptr(self.samples, _abi.C.c_int16), _abi.iptr(self.labels, _abi.C.c_int64),
+                                 _abi.iptr(self.event_points, _abi.C.c_int64))
+
+    def needed(self, stats) -> int:
+        """Rows the last call wanted to deliver: a trace call reports them in its own out struct."""
+        return int(self.out.n_rows)
+
+    def sums(self) -> dict:
+        return {"n_rows": int(self.out.n_rows), "sample_checksum": int(self.out.sample_checksum),
+                "pad_checksum": int(self.out.pad_checksum)}
+
+    def result(self):
+        total = int(self.out.n_rows)
+        return self.offsets, self.pads[:total], self.samples[:total], self.labels[:total]
+
+
+def call_with_capacity(ctx: _abi.Context, n_events: int, capacity: int, call, what: str, stats=None,
+                       holder=TraceArrays, slack: int = 0, pinned: bool = False, cache=None, reuse: bool = False, **shape):
+    """Run ``call(out)`` with ``holder(n_events, capacity, **shape)`` arrays; on ATTPC_E_CAPACITY once more with the
+    rows the call reported (``holder.needed(stats)``, ``stats`` the RunStats that ``call`` fills) plus ``slack``.
+    ``pinned``: the row arrays in page-locked memory (PCIe-rate copies).  ``cache``: an object whose ``_out_cache``
+    attribute keeps the arrays, if ``reuse``, for its next call of the same shape -- the previous call's arrays are
+    then overwritten -- and is emptied otherwise; assigning None to the attribute drops them.  Returns the holder of
+    the call that went through."""
+    make = ctx.pinned_empty if pinned else None
+    while True:
+        capacity = max(1, int(capacity))
+        key = (holder, n_events, capacity, pinned, *sorted(shape.items()))
+        cached = cache._out_cache if reuse else None
+        if cached is not None and cached[0] == key:
+            arrays = cached[1]
+        else:
+            arrays = holder(n_events, capacity, make, **shape)
+            if cache is not None:
+                cache._out_cache = (key, arrays) if reuse else None
+        status = call(arrays.out)
+        if status == _abi.E_CAPACITY and arrays.needed(stats) > capacity:
+            capacity = arrays.needed(stats) + slack
+            continue
+        ctx.check(status, what)
+        return arrays

@@ -83,7 +83,7 @@ def test_kin_run_vs_oracle(ctx, orc, name):
 
 # ---------------------------------------------------------------- tracks --------------------------------------------
 def _device_tracks(ctx, det, layout, p4, vertex, seed, first):
-    ctx._det_token = None  # configured through the C ABI directly: the shim's cache no longer describes the device
+    ctx.forget("det")  # configured through the C ABI directly: the shim's cache no longer describes the device
     ctx.check(ctx.lib.attpc_det_configure(ctx.handle, det), "det_configure")
     nt = len(p4) * layout.n_sim
     samples = np.zeros((nt, _abi.TIME_SAMPLES, 4))
@@ -312,7 +312,7 @@ OTHER_SPECIES = [(1, 3), (2, 3), (3, 6), (5, 10), (6, 12), (8, 16)]
 
 
 def _det_run(ctx, det, layout, p4, vertex, seed, first):
-    ctx._det_token = None
+    ctx.forget("det")
     ctx.check(ctx.lib.attpc_det_configure(ctx.handle, det), "det_configure")
     n = len(p4)
     capacity = 1 << 20
@@ -353,7 +353,7 @@ def test_thirteen_stopping_power_tables(ctx, orc):
     assert offsets[-1] > 10_000
     # 14 tables do not fit: refused, and the context keeps the 13-table configuration it had
     det14, keep14 = build_det_desc(inp.config, nuclei + [nuclear_map.get_data(7, 14)], 1, fold_beam=True)
-    ctx._det_token = None
+    ctx.forget("det")
     rc = ctx.lib.attpc_det_configure(ctx.handle, det14)
     assert rc == _abi.E_INVALID and b"do not fit LDS" in ctx.lib.attpc_last_error(ctx.handle)
     again = _det_run(ctx, det, layout, p4, vertex, seed, first)

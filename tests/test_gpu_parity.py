@@ -165,7 +165,7 @@ def test_kin_sample_limit_and_samplers(ctx, orc):
 # ---------------------------------------------------------------- detector -----------------
 def _device_tracks(ctx, inp, p4, vertex, seed, first):
     from attpc_engine_amd.detector.simulator import configure_detector
-    ctx._det_token = None  # configured through the C ABI directly: the shim's cache no longer describes the device
+    ctx.forget("det")  # configured through the C ABI directly: the shim's cache no longer describes the device
     ctx.check(ctx.lib.attpc_det_configure(ctx.handle, inp.det), "det_configure")
     n = len(p4)
     nt = n * inp.layout.n_sim

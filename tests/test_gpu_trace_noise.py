@@ -39,7 +39,7 @@ def _noise(sigma, ped, stream=0):
 def _configure_noise_off_in_c(ctx):
     """attpc_trace_configure_noise(ctx, NULL) straight through the ABI (and forget the Python-side token)."""
     ctx.check(ctx.lib.attpc_trace_configure_noise(ctx.handle, None), "attpc_trace_configure_noise")
-    ctx._trace_noise_token = None
+    ctx.forget("trace_noise")
 
 
 @pytest.mark.parametrize("sigma", [1.0, 6.0])

@@ -39,7 +39,7 @@ def main() -> None:
 
     entry.build()
     from attpc_engine_amd import _abi, workloads
-    from attpc_engine_amd.detector.traces import TraceArrays
+    from attpc_engine_amd.outputs import TraceArrays
     from attpc_engine_amd.engine import Engine
 
     ctx = _abi.Context(0)
