@@ -131,6 +131,11 @@ class TraceReadoutDesc(C.Structure):
     _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("channels", C.POINTER(C.c_uint8))]
 
 
+class PeakDesc(C.Structure):
+    _fields_ = [("separation", C.c_double), ("prominence", C.c_double), ("min_width", C.c_double),
+                ("max_width", C.c_double), ("rel_height", C.c_double), ("threshold", C.c_double)]
+
+
 class TraceOut(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64),
@@ -220,7 +225,15 @@ EXPORTED_SYMBOLS = (
     "attpc_unpack_spyral_rows", "attpc_det_run_spyral", "attpc_sim_hint_next", "attpc_unpack_rows8",
     "attpc_trace_configure", "attpc_sim_run_traces", "attpc_det_run_traces", "attpc_traces",
     "attpc_trace_configure_noise", "attpc_traces_at", "attpc_trace_configure_readout",
+    "attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows", "attpc_trace_rows_at",
+    "attpc_trace_rows_last",
 )
+
+# The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
+# ATTPC_HIP_LIBRARY -- the yardstick of tools/trace_rows_rate.py -- may lack them: it loads, and a call of a missing
+# entry point is the AttributeError ctypes raises.  The package's own library must have every symbol.
+TRACE_ROW_SYMBOLS = ("attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows",
+                     "attpc_trace_rows_at", "attpc_trace_rows_last")
 
 _lib = None
 
@@ -289,6 +302,18 @@ def load_library() -> C.CDLL:
     lib.attpc_traces_at.argtypes = [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64), _dp,
                                     C.POINTER(C.c_int64), C.POINTER(TraceOut)]
     lib.attpc_trace_configure_readout.argtypes = [ctxp, C.POINTER(TraceReadoutDesc)]
+    trace_rows = {
+        "attpc_trace_configure_peaks": [ctxp, C.POINTER(PeakDesc)],
+        "attpc_sim_run_trace_rows": lib.attpc_sim_run.argtypes,
+        "attpc_det_run_trace_rows": lib.attpc_det_run.argtypes,
+        "attpc_trace_rows_at": [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64),
+                                C.POINTER(CloudOut)],
+        "attpc_trace_rows_last": [ctxp, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)],
+    }
+    older = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in TRACE_ROW_SYMBOLS)
+    for name, argtypes in trace_rows.items():
+        if not older:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -309,6 +334,8 @@ def load_library() -> C.CDLL:
         ctxp, C.c_int64, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, _dp,
     ]
     for name in EXPORTED_SYMBOLS:
+        if older and name in TRACE_ROW_SYMBOLS:
+            continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
             fn.restype = C.c_int32
@@ -316,7 +343,7 @@ def load_library() -> C.CDLL:
     return lib
 
 
-CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout")
+CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks")
 
 
 class Context:
@@ -367,6 +394,12 @@ class Context:
             if status == E_DATALOSS:
                 raise DataLossError(f"{what}: {text}")
             raise RuntimeError(f"{what} failed with status {status}: {text}")
+
+    def trace_rows_last(self) -> dict:
+        """Rows and row checksum of this context's last trace-row call (``attpc_trace_rows_last``)."""
+        n_rows, checksum = C.c_int64(), C.c_uint64()
+        self.check(self.lib.attpc_trace_rows_last(self.handle, C.byref(n_rows), C.byref(checksum)), "attpc_trace_rows_last")
+        return {"n_rows": int(n_rows.value), "row_checksum": int(checksum.value)}
 
     def set_option(self, name: str, value: int) -> None:
         """Tuning / test switches of the context (``attpc_set_option``)."""

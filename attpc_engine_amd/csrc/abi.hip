@@ -86,6 +86,12 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf tr_maps;     // readout of noise-only pads: TraceMaps, 3 x TR_MAP_WORDS words per event
   size_t tr_cap = 0;  // kept pad rows the trace outputs are kept at (grown with headroom)
   hipEvent_t traced = nullptr;  // the chunk's traces are written (the copies on C wait for it)
+  hipEvent_t counted = nullptr; // trace rows: the chunk's points per event are in h_pk_start (the host waits for it)
+  // trace rows (peaks.hip): the point map and count of every kept trace row, the scanned offsets of the trace rows and
+  // of the events, the points' records and centroids; the rows themselves go to sp_rows / sp_labels
+  DevBuf pk_maps, pk_counts, pk_row_start, pk_block_sums, pk_block_start, pk_ev_start, pk_records, pk_centroid;
+  size_t pk_cap = 0;           // points the point-sized buffers are kept at (grown with headroom)
+  Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
   size_t row_cap = 0;  // rows the row-sized buffers of the set are kept at (grown with headroom: a launch's row
                        // capacity follows the observed rows per event and moves by fractions of a percent)
   Pinned<int64_t> h_start;     // CSR offsets of the chunk (n + 1 entries)
@@ -191,6 +197,11 @@ struct attpc_ctx {
   const uint32_t* readout_channels = nullptr;  // [TR_MAP_WORDS] bitmap of S on the device
   std::vector<void*> readout_allocs;
   DevBuf trace_sums;               // [2] sample / pad checksums of the trace run in progress
+  bool peaks_on = false;           // attpc_trace_configure_peaks
+  PeakDev peaks{};
+  DevBuf peak_sums;                // [1] row checksum of the trace-row run in progress
+  int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
+  uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
   std::vector<void*> spyral_allocs;
   std::vector<double> h_pad_centers, h_pad_sizes;  // host copies: the expansion of compact Spyral records needs them
@@ -809,13 +820,16 @@ void accumulate(attpc_run_stats* st, const ChunkResult& r) {
 
 // ------------------------------------------------------------------ assembly (delivered clouds) ----
 // What a run delivers: clouds (attpc_sim_run / attpc_det_run), Spyral rows (_spyral) or pad traces (_traces).
-enum class OutMode { cloud, spyral, traces };
+// trace_rows: the traces as in `traces`, kept on the device, and their peaks as Spyral rows (_trace_rows).
+enum class OutMode { cloud, spyral, traces, trace_rows };
+// the modes whose chunks go through the trace kernels
+bool makes_traces(OutMode mode) { return mode == OutMode::traces || mode == OutMode::trace_rows; }
 
 // A run's output: the mode, the caller's output struct of that mode (neither: a device-resident run of clouds), and
 // how far the delivery into it has come.
 struct RunOut {
   OutMode mode = OutMode::cloud;
-  attpc_cloud_out* cloud = nullptr;  // cloud, spyral
+  attpc_cloud_out* cloud = nullptr;  // cloud, spyral, trace_rows
   attpc_trace_out* trace = nullptr;  // traces
   int64_t rows = 0;                  // row cursor: rows of the chunks delivered so far
   bool over = false;                 // ... more than the caller's capacity
@@ -824,7 +838,11 @@ struct RunOut {
   int64_t* event_points() const { return cloud ? cloud->event_points : trace ? trace->event_points : nullptr; }
   int64_t capacity() const { return cloud ? cloud->capacity : trace->capacity; }
   // the capacity binds clouds always, traces when any of their row arrays is wanted
-  bool bounded() const { return cloud || (trace && (trace->pads || trace->samples || trace->labels)); }
+  // (trace rows: when their rows or labels are)
+  bool bounded() const {
+    if (mode == OutMode::trace_rows) return cloud->points || cloud->labels;
+    return cloud || (trace && (trace->pads || trace->samples || trace->labels));
+  }
 };
 
 // The event-ordered cloud of a chunk of `n` events and `cap` rows in `as`, and the pinned copies of its CSR offsets and
@@ -1055,7 +1073,7 @@ int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMo
                      static_cast<double*>(as.points.p), static_cast<int64_t*>(as.labels.p));
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(as.h_ev_rows.p, ctx->ev_rows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (mode == OutMode::traces) rc = enqueue_trace_count(ctx, as, n, as.row_cap, seed, first_global);
+  if (makes_traces(mode)) rc = enqueue_trace_count(ctx, as, n, as.row_cap, seed, first_global);
   else if (mode == OutMode::spyral) rc = assemble_spyral(ctx, as, n);
   else rc = assemble_cloud(ctx, as, n);
   if (rc) return rc;
@@ -1186,7 +1204,11 @@ int32_t copy_rows(attpc_ctx* ctx, AsmSet& as, uint32_t n, const RunOut& o, int64
 // first_local .. of the call, first_global .. globally): write its offsets and event_points into the caller's arrays,
 // move the row cursor past it and queue its copy on C (traces: behind their write pass on S).  A chunk beyond the
 // caller's capacity sets o.over and is not copied.
+int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t first_local, uint64_t seed,
+                           uint64_t first_global);
+
 int32_t deliver(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t first_local, uint64_t seed, uint64_t first_global) {
+  if (o.mode == OutMode::trace_rows) return deliver_trace_rows(ctx, o, as, n, first_local, seed, first_global);
   const int64_t base = o.rows, total = as.h_start[n];
   if (int64_t* offsets = o.offsets())
     for (uint32_t i = 0; i <= n; ++i) offsets[first_local + i] = base + as.h_start[i];
@@ -1200,6 +1222,88 @@ int32_t deliver(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t firs
   int32_t rc;
   if ((rc = enqueue_trace_write(ctx, as, n, total, seed, first_global))) return rc;
   return copy_traces(ctx, as, total, base, o.trace, fits);
+}
+
+// deliver() of trace rows: the chunk's traces are counted (as.h_start) but not written.  Queue on S their write pass and
+// behind it the peak count pass, the scans of the points per trace row and per event and the copy of the latter to
+// pinned memory; wait for that copy alone (an event: the one host round trip of the stage -- the number of points
+// sizes what follows and the caller's offsets need it -- does not drain what else is queued on S); then queue the record pass and the per-event sort into rows, and their copy on C.
+int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t first_local, uint64_t seed,
+                           uint64_t first_global) {
+  const int64_t base = o.rows, traces = as.h_start[n];
+  if (n) ctx->trace_rows_per_event = std::max((double)traces / (double)n, 1.0e-3);
+  int32_t rc;
+  if ((rc = enqueue_trace_write(ctx, as, n, traces, seed, first_global))) return rc;
+  const size_t tr = (size_t)std::max<int64_t>(traces, 1);
+  if ((rc = ensure(ctx, as.pk_maps, tr * 64))) return rc;
+  if ((rc = ensure(ctx, as.pk_counts, tr * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, as.pk_row_start, (tr + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, as.pk_ev_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure_pinned(ctx, as.h_pk_start, (size_t)n + 1))) return rc;
+  const int16_t* pedestals = ctx->noise_on ? ctx->noise.pedestals : nullptr;
+  const int32_t* d_pads = static_cast<const int32_t*>(as.tr_pads.p);
+  const int16_t* d_samples = static_cast<const int16_t*>(as.tr_samples.p);
+  if (traces > 0) {
+    launch_peak_count(ctx->stream, ctx->peaks, pedestals, (uint32_t)traces, d_pads, d_samples,
+                      static_cast<uint8_t*>(as.pk_maps.p), static_cast<uint32_t*>(as.pk_counts.p));
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  if (traces > 0) {
+    const size_t blocks = peak_scan_blocks((uint32_t)traces);
+    if ((rc = ensure(ctx, as.pk_block_sums, blocks * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(ctx, as.pk_block_start, (blocks + 1) * sizeof(int64_t)))) return rc;
+    launch_peak_scan(ctx->stream, static_cast<const uint32_t*>(as.pk_counts.p), (uint32_t)traces,
+                     static_cast<int64_t*>(as.pk_row_start.p), static_cast<uint32_t*>(as.pk_block_sums.p),
+                     static_cast<int64_t*>(as.pk_block_start.p));
+  } else {
+    HIP_TRY(ctx, hipMemsetAsync(as.pk_row_start.p, 0, sizeof(int64_t), ctx->stream));
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  launch_peak_event_start(ctx->stream, n, static_cast<const int64_t*>(as.kept_start.p),
+                          static_cast<const int64_t*>(as.pk_row_start.p), static_cast<int64_t*>(as.pk_ev_start.p));
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(as.h_pk_start.p, as.pk_ev_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipEventRecord(as.counted, ctx->stream));
+  HIP_TRY(ctx, hipEventSynchronize(as.counted));
+  const int64_t total = as.h_pk_start[n];
+  if (int64_t* offsets = o.offsets())
+    for (uint32_t i = 0; i <= n; ++i) offsets[first_local + i] = base + as.h_pk_start[i];
+  if (int64_t* event_points = o.event_points())
+    for (uint32_t i = 0; i < n; ++i) event_points[first_local + i] = (int64_t)as.h_ev_rows[i];
+  o.rows = base + total;
+  const bool fits = !o.bounded() || o.rows <= o.capacity();
+  if (!fits) o.over = true;
+  if (total > 0) {
+    if ((size_t)total > as.pk_cap) as.pk_cap = (size_t)total + (size_t)total / 8;
+    if ((rc = ensure(ctx, as.pk_records, as.pk_cap * sizeof(uint4)))) return rc;
+    if ((rc = ensure(ctx, as.pk_centroid, as.pk_cap * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->sort_idx, as.pk_cap * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->sort_key, as.pk_cap * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, as.sp_rows, as.pk_cap * 8 * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, as.sp_labels, as.pk_cap * sizeof(int64_t)))) return rc;
+    launch_peak_write(ctx->stream, ctx->peaks, pedestals, (uint32_t)traces, d_pads, d_samples,
+                      static_cast<const uint8_t*>(as.pk_maps.p), static_cast<const int64_t*>(as.pk_row_start.p),
+                      static_cast<uint4*>(as.pk_records.p));
+    HIP_TRY(ctx, hipGetLastError());
+    launch_peak_rows(ctx->stream, ctx->spyral, seed, n, first_global, static_cast<const int64_t*>(as.pk_ev_start.p),
+                     static_cast<const uint4*>(as.pk_records.p), d_pads, static_cast<const int64_t*>(as.tr_labels.p),
+                     static_cast<double*>(as.pk_centroid.p), static_cast<uint32_t*>(ctx->sort_idx.p),
+                     static_cast<double*>(ctx->sort_key.p), static_cast<double*>(as.sp_rows.p),
+                     static_cast<int64_t*>(as.sp_labels.p), static_cast<unsigned long long*>(ctx->peak_sums.p));
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
+  if (total > 0 && fits) {
+    if (o.cloud->points)
+      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->points + base * 8, as.sp_rows.p, (size_t)total * 8 * sizeof(double), hipMemcpyDeviceToHost,
+                                  ctx->stream_c));
+    if (o.cloud->labels)
+      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->labels + base, as.sp_labels.p, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                  ctx->stream_c));
+  }
+  HIP_TRY(ctx, hipEventRecord(as.copied, ctx->stream_c));
+  return ATTPC_OK;
 }
 
 // The traces of n host-side events (attpc_traces_at; a run's batch with nothing to scatter in a readout mode) on
@@ -1303,7 +1407,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   };
   if (lay.n_sim == 0 || nb == 0) {  // nothing to scatter: empty clouds
     if ((rc = queue_next_once())) return rc;
-    if (o.mode == OutMode::traces && ctx->readout_mode != ATTPC_READOUT_HIT && nb)  // their noise-only rows
+    if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT && nb)  // their noise-only rows
       return trace_host_events(ctx, o, batch_first_local, nb, nullptr, nullptr, nullptr, seed, batch_first_global);
     if (int64_t* offsets = o.offsets()) std::fill(offsets + batch_first_local, offsets + batch_first_local + nb + 1, o.rows);
     if (int64_t* event_points = o.event_points()) std::fill(event_points + batch_first_local, event_points + batch_first_local + nb, 0);
@@ -1382,11 +1486,11 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     uint32_t n = std::min<uint32_t>(next_chunk_events(ctx, nb - e0), (uint32_t)ctx->opt_deliver_chunk);
     if (ctx->rows_per_event > 0.0)
       n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)DELIVER_CHUNK_ROWS / ctx->rows_per_event));
-    if (o.mode == OutMode::traces && ctx->readout_mode != ATTPC_READOUT_HIT) {  // the first chunk too: |S| rows per event
+    if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT) {  // the first chunk too: |S| rows per event
       const double rows = ctx->readout_mode == ATTPC_READOUT_FULL || ctx->trace_rows_per_event <= 0.0
                               ? (double)ctx->readout_pads : ctx->trace_rows_per_event;
       if (rows > 0.0) n = std::min<uint32_t>(n, (uint32_t)std::max(1.0, (double)TRACE_CHUNK_ROWS / rows));
-    } else if (o.mode == OutMode::traces && ctx->trace_rows_per_event > 0.0)  // 1 KiB of samples per kept pad row
+    } else if (makes_traces(o.mode) && ctx->trace_rows_per_event > 0.0)  // 1 KiB of samples per kept pad row
       n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)TRACE_CHUNK_ROWS / ctx->trace_rows_per_event));
     const Chunk c{e0, n, seq % MAX_SLOTS};
     const int set = seq & 1;
@@ -1409,11 +1513,24 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   return queue_next_once();
 }
 
-// The trace checksums of a run start at zero (queued on S).
-int32_t reset_trace_sums(attpc_ctx* ctx) {
+// The trace checksums of a run, and for trace rows their row checksum, start at zero (queued on S).
+int32_t reset_trace_sums(attpc_ctx* ctx, OutMode mode) {
   int32_t rc;
   if ((rc = ensure(ctx, ctx->trace_sums, 2 * sizeof(unsigned long long)))) return rc;
   HIP_TRY(ctx, hipMemsetAsync(ctx->trace_sums.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  if (mode != OutMode::trace_rows) return ATTPC_OK;
+  if ((rc = ensure(ctx, ctx->peak_sums, sizeof(unsigned long long)))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->peak_sums.p, 0, sizeof(unsigned long long), ctx->stream));
+  return ATTPC_OK;
+}
+
+// The end of a trace-row run whose copies have all arrived: its rows and row checksum for attpc_trace_rows_last.
+int32_t read_peak_sums(attpc_ctx* ctx, const RunOut& o) {
+  unsigned long long sum = 0ull;
+  HIP_TRY(ctx, hipMemcpyAsync(&sum, ctx->peak_sums.p, sizeof sum, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->last_rows = o.rows;
+  ctx->last_row_checksum = sum;
   return ATTPC_OK;
 }
 
@@ -1432,7 +1549,8 @@ int32_t read_trace_sums(attpc_ctx* ctx, const RunOut& o) {
 int32_t run_status(attpc_ctx* ctx, const attpc_run_stats& st, attpc_run_stats* stats, const RunOut& o) {
   if (stats) *stats = st;
   if (o.over)
-    return fail(ctx, ATTPC_E_CAPACITY, "%s %lld rows, capacity %lld", o.mode == OutMode::traces ? "traces need" : "cloud needs",
+    return fail(ctx, ATTPC_E_CAPACITY, "%s %lld rows, capacity %lld",
+                o.mode == OutMode::traces ? "traces need" : o.mode == OutMode::trace_rows ? "trace rows need" : "cloud needs",
                 (long long)o.rows, (long long)o.capacity());
   if (st.n_failed || st.n_inconsistent)
     return fail(ctx, ATTPC_E_DATALOSS, "%llu events lost a time bucket (n_failed), %u table self-check failures (n_inconsistent) in %llu events",
@@ -1444,10 +1562,10 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
                    const RunSource& src, const RunSink& sink, RunOut o, attpc_run_stats* stats) {
   int32_t rc;
   if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
-  if (o.mode == OutMode::traces && (rc = reset_trace_sums(ctx))) return rc;
+  if (makes_traces(o.mode) && (rc = reset_trace_sums(ctx, o.mode))) return rc;
   // a readout run sizes its trace chunks for |S| rows per event until it has seen its own rate: the rate of an earlier
   // run says nothing once the threshold, the noise or the workload has changed (hit mode keeps the context's rate)
-  if (o.mode == OutMode::traces && ctx->readout_mode != ATTPC_READOUT_HIT) ctx->trace_rows_per_event = 0.0;
+  if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT) ctx->trace_rows_per_event = 0.0;
   UnpackDrain drain(ctx);
   attpc_run_stats st{};
   st.n_events = n_events;
@@ -1548,28 +1666,48 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
   if (o.mode == OutMode::spyral) st.n_points = (uint64_t)o.rows;  // rows that survive the threshold
   if (o.mode == OutMode::traces && (rc = read_trace_sums(ctx, o))) return rc;  // (the cloud's meaning stays in st)
+  if (o.mode == OutMode::trace_rows) {
+    st.n_points = (uint64_t)o.rows;  // the rows of the call, as in the Spyral mode
+    if ((rc = read_peak_sums(ctx, o))) return rc;
+  }
   st.n_buffer_growths = ctx->n_growths - growths_before;
   st.device_bytes = ctx->device_bytes;
   return run_status(ctx, st, stats, o);
 }
 
-// The six run entry points (attpc_det_run*, attpc_sim_run*; `name`) after their checks: the kinematics come from the
+// What a trace-row call needs beside the detector: the trace settings, the Spyral geometry and the peak parameters.
+int32_t trace_rows_ready(attpc_ctx* ctx, const char* name) {
+  if (!ctx->trace_ready) return fail(ctx, ATTPC_E_INVALID, "%s: attpc_trace_configure has not been called", name);
+  if (!ctx->spyral_ready) return fail(ctx, ATTPC_E_INVALID, "%s: attpc_spyral_configure has not been called (the geometry of the rows)", name);
+  if (ctx->spyral.n_pads < ATTPC_NUM_PADS)
+    return fail(ctx, ATTPC_E_INVALID, "%s: the Spyral geometry has %d pads, the traces name pads up to %d", name, ctx->spyral.n_pads,
+                ATTPC_NUM_PADS - 1);
+  if (ctx->spyral.window_edge == ctx->spyral.mm_edge) return fail(ctx, ATTPC_E_INVALID, "%s: windows_edge == micromegas_edge", name);
+  if (!ctx->peaks_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "%s: attpc_trace_configure_peaks has not been called", name);
+  return ATTPC_OK;
+}
+
+// The eight run entry points (attpc_det_run*, attpc_sim_run*; `name`) after their checks: the kinematics come from the
 // host (src.h_p4 / h_vertex) or from the kinematics kernel (src.from_kernel), the output is `o`.
 int32_t run_entry(const char* name, attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                   const attpc_event_layout* layout, const RunSource& src, const RunSink& sink, RunOut o, attpc_run_stats* stats) {
   if (!ctx || (!src.from_kernel && (!src.h_p4 || !src.h_vertex))) return ATTPC_E_INVALID;
   if (o.mode == OutMode::traces && !o.trace) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_trace_out", name);
-  if (o.mode == OutMode::spyral && !o.cloud) return fail(ctx, ATTPC_E_INVALID, "%s needs output buffers", name);
+  if ((o.mode == OutMode::spyral || o.mode == OutMode::trace_rows) && !o.cloud) return fail(ctx, ATTPC_E_INVALID, "%s needs output buffers", name);
   if (src.from_kernel && !ctx->kin_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_kin_configure has not been called");
   if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_det_configure has not been called");
   if (o.mode == OutMode::spyral && !ctx->spyral_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_spyral_configure has not been called");
   if (o.mode == OutMode::traces && !ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
+  if (o.mode == OutMode::trace_rows) {
+    const int32_t rc0 = trace_rows_ready(ctx, name);
+    if (rc0) return rc0;
+  }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc = validate_layout(ctx, layout, true);
   if (rc) return rc;
   if (src.from_kernel && layout->n_rows != kin_rows(ctx))
     return fail(ctx, ATTPC_E_INVALID, "layout.n_rows=%d but the pipeline has %d rows", layout->n_rows, kin_rows(ctx));
-  if (o.mode == OutMode::traces && (rc = drop_prefetch(ctx))) return rc;  // a trace call is never the announced one
+  if (makes_traces(o.mode) && (rc = drop_prefetch(ctx))) return rc;  // a trace call is never the announced one
   return run_events(ctx, seed, first_event, n_events, *layout, src, sink, o, stats);
 }
 
@@ -1611,7 +1749,7 @@ int32_t attpc_ctx_create(int32_t device, attpc_ctx** out) {
   }
   for (int i = 0; i < MAX_SLOTS; ++i) { make_event(&ctx->s0[i]); make_event(&ctx->s1[i]); }
   for (AsmSet& as : ctx->aset) {
-    make_event(&as.ready); make_event(&as.copied); make_event(&as.traced);
+    make_event(&as.ready); make_event(&as.copied); make_event(&as.traced); make_event(&as.counted);
     ok = ok && ensure_pinned(ctx, as.h_total, 2) == ATTPC_OK;
   }
   ok = ok && ensure_pinned(ctx, ctx->h_out_ctrl, (size_t)MAX_SLOTS * CTRL_WORDS) == ATTPC_OK;
@@ -1640,7 +1778,7 @@ int32_t attpc_ctx_destroy(attpc_ctx* ctx) {
       if (e) (void)hipEventDestroy(e);
   };
   for (TrackSet& ts : ctx->tset) destroy({ts.done, ts.k0, ts.k1, ts.t0, ts.t1});
-  for (AsmSet& as : ctx->aset) destroy({as.ready, as.copied, as.traced});
+  for (AsmSet& as : ctx->aset) destroy({as.ready, as.copied, as.traced, as.counted});
   for (int i = 0; i < MAX_SLOTS; ++i) destroy({ctx->s0[i], ctx->s1[i]});
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream_t_own) (void)hipStreamDestroy(ctx->stream_t_own);
@@ -2108,9 +2246,12 @@ int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, c
   return attpc_traces_at(ctx, 0, 0, n_events, offsets, points, labels, out);
 }
 
-int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
-                        const double* points, const int64_t* labels, attpc_trace_out* out) {
-  if (!ctx || !out || n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
+namespace {
+// attpc_traces_at and attpc_trace_rows_at: the checks of the host cloud, then its events through trace_host_events
+// into `o`.
+int32_t host_cloud_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
+                       const double* points, const int64_t* labels, RunOut& o) {
+  if (n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
   if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_traces takes at most 2^31 - 1 events per call");
   if (validate_id_range(ctx, first_event, (uint64_t)n_events)) return ATTPC_E_INVALID;
   if (!ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
@@ -2144,14 +2285,82 @@ int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
   int32_t rc;
   if ((rc = drop_prefetch(ctx))) return rc;
   if ((rc = sync_all(ctx))) return rc;
-  if ((rc = reset_trace_sums(ctx))) return rc;
-  RunOut o{OutMode::traces, nullptr, out};
+  if ((rc = reset_trace_sums(ctx, o.mode))) return rc;
   const double keep = ctx->trace_rows_per_event;  // a host cloud says nothing about the configured workload
   rc = trace_host_events(ctx, o, 0, n, offsets, points, labels, seed, first_event);
   ctx->trace_rows_per_event = keep;
-  if (rc) return rc;
+  return rc;
+}
+}  // namespace
+
+int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
+                        const double* points, const int64_t* labels, attpc_trace_out* out) {
+  if (!ctx || !out) return ATTPC_E_INVALID;
+  RunOut o{OutMode::traces, nullptr, out};
+  int32_t rc;
+  if ((rc = host_cloud_run(ctx, seed, first_event, n_events, offsets, points, labels, o))) return rc;
   if ((rc = read_trace_sums(ctx, o))) return rc;
   return run_status(ctx, attpc_run_stats{}, nullptr, o);
+}
+
+// ---- trace rows (peaks.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_peaks(attpc_ctx* ctx, const attpc_peak_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d) {
+    if (!(d->separation >= 1.0)) return fail(ctx, ATTPC_E_INVALID, "peak separation %g: >= 1", d->separation);
+    if (!(d->prominence >= 0.0)) return fail(ctx, ATTPC_E_INVALID, "peak prominence %g: >= 0", d->prominence);
+    if (!(d->min_width >= 0.0 && d->max_width >= d->min_width))
+      return fail(ctx, ATTPC_E_INVALID, "peak widths %g .. %g: 0 <= min_width <= max_width", d->min_width, d->max_width);
+    if (!(d->rel_height > 0.0 && d->rel_height <= 1.0)) return fail(ctx, ATTPC_E_INVALID, "peak rel_height %g: in (0, 1]", d->rel_height);
+    if (std::isnan(d->threshold)) return fail(ctx, ATTPC_E_INVALID, "peak threshold is NaN");
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  ctx->peaks_on = false;
+  if (!d) return ATTPC_OK;
+  PeakDev pk{};
+  pk.distance = (int32_t)std::min(std::ceil(d->separation), (double)ATTPC_NUM_TB);  // (512 samples apart: one candidate a row)
+  pk.prominence = d->prominence;
+  pk.min_width = d->min_width;
+  pk.max_width = d->max_width;
+  pk.rel_height = d->rel_height;
+  pk.threshold = d->threshold;
+  ctx->peaks = pk;
+  ctx->peaks_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_sim_run_trace_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                 const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
+                                 attpc_cloud_out* out, attpc_run_stats* stats) {
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{true}, RunSink{p4, vertex, kin_status},
+                   RunOut{OutMode::trace_rows, out}, stats);
+}
+
+int32_t attpc_det_run_trace_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                 const attpc_event_layout* layout, const double* p4, const double* vertex,
+                                 attpc_cloud_out* out, attpc_run_stats* stats) {
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{},
+                   RunOut{OutMode::trace_rows, out}, stats);
+}
+
+int32_t attpc_trace_rows_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
+                            const double* points, const int64_t* labels, attpc_cloud_out* out) {
+  if (!ctx || !out) return ATTPC_E_INVALID;
+  int32_t rc;
+  if ((rc = trace_rows_ready(ctx, __func__))) return rc;
+  RunOut o{OutMode::trace_rows, out};
+  if (out->offsets) out->offsets[0] = 0;
+  if ((rc = host_cloud_run(ctx, seed, first_event, n_events, offsets, points, labels, o))) return rc;
+  if ((rc = read_peak_sums(ctx, o))) return rc;
+  return run_status(ctx, attpc_run_stats{}, nullptr, o);
+}
+
+int32_t attpc_trace_rows_last(attpc_ctx* ctx, int64_t* n_rows, uint64_t* row_checksum) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (n_rows) *n_rows = ctx->last_rows;
+  if (row_checksum) *row_checksum = ctx->last_row_checksum;
+  return ATTPC_OK;
 }
 
 int32_t attpc_sim_hint_next(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,

@@ -22,6 +22,7 @@ constexpr uint32_t DOMAIN_KIN = 0u;       // index = attempt * 64 + slot
 constexpr uint32_t DOMAIN_FANO0 = 1u;     // + row of the nucleus; index = sample >> 1
 constexpr uint32_t DOMAIN_JITTER = 0x100u; // folded into the key word of jitter_uniform() (Philox2x32-7)
 constexpr uint32_t DOMAIN_MC = 0x200u;     // + entry number of the event; index = primary electron
+constexpr uint32_t DOMAIN_PEAK_JITTER = 0x300u;  // as DOMAIN_JITTER, for the centroid of a trace peak (peaks.hip): key = sample << 14 | pad
 constexpr uint32_t DOMAIN_TRACE_NOISE = 0x80000000u;  // | noise stream; index = pad * 128 + 2 * (j % 64) + j / 256
 constexpr uint32_t KIN_SLOTS = 64u;
 

@@ -136,4 +136,32 @@ void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* 
                         TraceScratch sc, const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
                         unsigned long long* sums);
 
+// peaks of the kept trace rows -> Spyral rows (peaks.hip; attpc_trace_configure_peaks, the contract is in
+// include/attpc_engine.h).  The geometry is SpyralDev's.
+struct PeakDev {
+  int32_t distance;  // ceil(separation), at most ATTPC_NUM_TB
+  double prominence, min_width, max_width, rel_height, threshold;
+};
+// per kept trace row (pads / samples as the trace write pass left them; pedestals nullptr = zeros): maps [rows][64],
+// bit s of byte l = sample 8 l + s is a point; counts [rows] their number
+void launch_peak_count(hipStream_t s, const PeakDev& pk, const int16_t* pedestals, uint32_t n_rows, const int32_t* pads,
+                       const int16_t* samples, uint8_t* maps, uint32_t* counts);
+// row_start [n_rows + 1] = exclusive scan of counts [n_rows], n_rows > 0; block_sums [peak_scan_blocks(n_rows)] and
+// block_start [peak_scan_blocks(n_rows) + 1]: scratch
+uint32_t peak_scan_blocks(uint32_t n_rows);
+void launch_peak_scan(hipStream_t s, const uint32_t* counts, uint32_t n_rows, int64_t* row_start, uint32_t* block_sums,
+                      int64_t* block_start);
+// ev_start[e] = row_start[kept_start[e]], e = 0 .. n_events
+void launch_peak_event_start(hipStream_t s, uint32_t n_events, const int64_t* kept_start, const int64_t* row_start,
+                             int64_t* ev_start);
+// records [points]: (trace row, sample, amplitude, integral) of every point, at row_start[row] in ascending sample
+void launch_peak_write(hipStream_t s, const PeakDev& pk, const int16_t* pedestals, uint32_t n_rows, const int32_t* pads,
+                       const int16_t* samples, const uint8_t* maps, const int64_t* row_start, uint4* records);
+// rows [points][8] / out_labels in the contract's order per event (ev_start: CSR offsets of the events' points);
+// centroid / sort_idx / sort_key: scratch of one entry per point; sums[0] += the row checksum (event = first_event + e)
+void launch_peak_rows(hipStream_t s, const SpyralDev& sp, uint64_t seed, uint32_t n_events, uint64_t first_event,
+                      const int64_t* ev_start, const uint4* records, const int32_t* pads, const int64_t* labels,
+                      double* centroid, uint32_t* sort_idx, double* sort_key, double* rows, int64_t* out_labels,
+                      unsigned long long* sums);
+
 }  // namespace attpc

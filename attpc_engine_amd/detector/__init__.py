@@ -8,7 +8,8 @@ from . import writer as _writer
 _EXPORTS = {
     _parameters: ("Config", "DetectorParams", "ElectronicsParams", "PadParams"),
     _simulator: ("run_simulation", "simulate", "simulate_batch"),
-    _traces: ("configure_traces", "simulate_batch_traces", "clouds_to_traces"),
+    _traces: ("configure_traces", "simulate_batch_traces", "clouds_to_traces", "PeakSettings", "configure_trace_rows",
+              "simulate_batch_trace_rows", "clouds_to_trace_rows"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter"),
 }
 __all__ = []

@@ -150,10 +150,14 @@ def simulate(momenta: np.ndarray, vertex: np.ndarray, proton_numbers: np.ndarray
 def delivery_of(writer, config: Config):
     """What a run hands ``writer`` per event, chosen once from what the writer offers -> (kind, emit): "traces" with
     ``emit(pads, samples, labels, event)`` (TraceWriter.write_traces), "rows" with ``emit(rows, labels, event)``
-    (presorted rows to SpyralWriter.write_rows) or "cloud" with ``emit(points, labels, event)`` (the plain ``write`` of
+    (presorted rows to SpyralWriter.write_rows), "trace_rows" with the same ``emit`` (a SpyralWriter with ``peaks``:
+    its rows are the peaks of the pad traces) or "cloud" with ``emit(points, labels, event)`` (the plain ``write`` of
     any SimulationWriter)."""
     if callable(getattr(writer, "write_traces", None)):
         return "traces", writer.write_traces
+    if callable(getattr(writer, "write_rows", None)) and getattr(writer, "peaks", None) is not None:
+        # (SpyralWriter(peaks=...): the rows are the peaks of the event's pad traces, made on the device)
+        return "trace_rows", lambda rows, labels, event: writer.write_rows(rows, labels, event, presorted=True)
     if callable(getattr(writer, "write_rows", None)):
         return "rows", lambda rows, labels, event: writer.write_rows(rows, labels, event, presorted=True)
     return "cloud", lambda points, labels, event: writer.write(points, labels, config, event)
@@ -212,6 +216,12 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
                 *args, first_event=start, response=writer.response, threshold=writer.threshold, offset=writer.offset,
                 **writer.noise_kwargs(), **writer.readout_kwargs())
             return offsets, raw_points, pads, samples, labels
+        if kind == "trace_rows":  # ... and their peaks as Spyral rows behind them (attpc_det_run_trace_rows)
+            from .traces import simulate_batch_trace_rows
+
+            offsets, rows, labels, raw_points, _ = simulate_batch_trace_rows(*args, first_event=start, peaks=writer.peaks,
+                                                                             **writer.trace_kwargs())
+            return offsets, raw_points, rows, labels
         if kind == "rows":
             offsets, rows, labels, raw_points, _ = simulate_batch_spyral(
                 *args, first_event=start, response=getattr(writer, "response", None))

@@ -15,6 +15,11 @@ The readout of noise-only pads is opt-in too (``readout="partial"`` or ``"full"`
 (zero suppression) every pad of the readout set whose noise crosses the threshold is read out as well, with label -1;
 in full readout every pad of the set is (include/attpc_engine.h; ``tests/readout_reference.py`` restates it).
 ``expected_noise_pads`` gives the mean number of noise-only pads a partial readout keeps per event.
+
+Trace rows are the step after the traces, still on the device (``PeakSettings``, ``simulate_batch_trace_rows``,
+``clouds_to_trace_rows``): the peaks of every kept pad trace above its pedestal -- separation, prominence, width and
+amplitude threshold as in the first phase of Spyral -- as Spyral rows of eight columns in ascending z
+(include/attpc_engine.h; ``tests/peaks_reference.py`` restates it).  Every trace setting above composes with them.
 """
 from __future__ import annotations
 
@@ -23,7 +28,7 @@ import math
 import numpy as np
 
 from .. import _abi
-from ..outputs import TraceArrays, call_with_capacity  # noqa: F401 (TraceArrays stays importable from here)
+from ..outputs import RowArrays, TraceArrays, call_with_capacity  # noqa: F401 (TraceArrays stays importable from here)
 from .parameters import Config
 
 
@@ -234,6 +239,22 @@ def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold
     configure_readout(ctx, readout)
 
 
+TRACE_KWARGS = ("response", "threshold", "offset", "noise_sigma", "noise_table", "pedestals", "noise_stream", "readout",
+                "readout_pads")
+
+
+def validate_trace_kwargs(config: Config, trace_kwargs: dict) -> None:
+    """The trace settings a caller passes on as keywords (``configure_traces``'s, TRACE_KWARGS), checked before any
+    library call: TypeError for a name configure_traces does not take, ValueError for a value it would refuse."""
+    unknown = set(trace_kwargs) - set(TRACE_KWARGS)
+    if unknown:
+        raise TypeError(f"unexpected trace settings {sorted(unknown)}: configure_traces takes {list(TRACE_KWARGS)}")
+    get = trace_kwargs.get
+    trace_settings(config, get("response"), get("threshold"), get("offset", 0))
+    NoiseSettings(get("noise_sigma", 0.0), get("noise_table"), get("pedestals"), get("noise_stream", 0))
+    ReadoutSettings(get("readout", "hit"), get("readout_pads"))
+
+
 def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
                           seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
                           response=None, threshold=None, offset: int = 0, capacity_per_event: int = 1024,
@@ -283,3 +304,100 @@ def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray
     rows = max(rows, ctx._trace_readout_rows * n)  # full readout: |S| rows per event
     arrays = call_with_capacity(ctx, n, max(16, rows), call, "attpc_traces_at")
     return (*arrays.result(), arrays.sums())
+
+
+class PeakSettings:
+    """The validated peak parameters of the trace rows (``attpc_peak_desc``, include/attpc_engine.h): ``separation``
+    (>= 1 samples between kept peaks), ``prominence`` (>= 0), ``min_width`` <= ``max_width`` (>= 0, samples at
+    ``rel_height`` in (0, 1] of the prominence) and the amplitude ``threshold`` above the pedestal.  The defaults are
+    this project's (they fit its GET response: a lone arrival is one peak 15.5 samples wide)."""
+
+    def __init__(self, separation: float = 50.0, prominence: float = 20.0, min_width: float = 1.0,
+                 max_width: float = 50.0, rel_height: float = 0.95, threshold: float = 40.0):
+        values = [float(v) for v in (separation, prominence, min_width, max_width, rel_height, threshold)]
+        self.separation, self.prominence, self.min_width, self.max_width, self.rel_height, self.threshold = values
+        if not self.separation >= 1.0:
+            raise ValueError(f"peak separation must be >= 1, got {separation}")
+        if not self.prominence >= 0.0:
+            raise ValueError(f"peak prominence must be >= 0, got {prominence}")
+        if not 0.0 <= self.min_width <= self.max_width:
+            raise ValueError(f"peak widths must be 0 <= min_width <= max_width, got {min_width}, {max_width}")
+        if not 0.0 < self.rel_height <= 1.0:
+            raise ValueError(f"peak rel_height must be in (0, 1], got {rel_height}")
+        if math.isnan(self.threshold):
+            raise ValueError("peak threshold is NaN")
+
+    def token(self):
+        return (self.separation, self.prominence, self.min_width, self.max_width, self.rel_height, self.threshold)
+
+    def desc(self) -> _abi.PeakDesc:
+        return _abi.PeakDesc(*self.token())
+
+
+def configure_peaks(ctx: _abi.Context, peaks: PeakSettings | None) -> None:
+    """``attpc_trace_configure_peaks`` unless this ctx already holds the same parameters (``None``: the stage off)."""
+    if peaks is None:
+        ctx.configure("peaks", None, "attpc_trace_configure_peaks", None)
+    else:
+        ctx.configure("peaks", peaks.token(), "attpc_trace_configure_peaks", peaks.desc())
+
+
+def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None, **trace_kwargs) -> None:
+    """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
+    the geometry of the rows (``configure_spyral``) and the peak parameters (default ``PeakSettings()``)."""
+    from .simulator import configure_spyral
+
+    peaks = PeakSettings() if peaks is None else peaks
+    configure_traces(config, ctx, **trace_kwargs)
+    configure_spyral(config, ctx)
+    configure_peaks(ctx, peaks)
+
+
+def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
+                              seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
+                              peaks: PeakSettings | None = None, capacity_per_event: int = 2048, **trace_kwargs):
+    """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
+    (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them) ->
+    (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
+    before any suppression, stats dict: the cloud's run statistics with ``n_points`` = the rows, plus ``n_rows`` /
+    ``row_checksum``)."""
+    from .simulator import run_batch
+
+    peaks = PeakSettings() if peaks is None else peaks
+    validate_trace_kwargs(config, trace_kwargs)  # (before the first library call)
+    ctx = ctx or _abi.default_context()
+    arrays, stats = run_batch("attpc_det_run_trace_rows", momenta, vertices, proton_numbers, mass_numbers, config, seed,
+                              indices, first_event, ctx, capacity_per_event,
+                              configure=lambda c: configure_trace_rows(config, c, peaks, **trace_kwargs),
+                              holder=RowArrays, width=8, slack=1024)
+    return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **ctx.trace_rows_last()})
+
+
+def clouds_to_trace_rows(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,
+                         first_event: int = 0):
+    """Trace rows of any host cloud in CSR form (``attpc_trace_rows_at``; ``ctx`` configured with
+    ``configure_trace_rows``): offsets [n+1], points [P,3] (pad, time bucket, electrons), labels [P] ->
+    (offsets [n+1], rows [R,8], labels [R], {n_rows, row_checksum}).  Event i of the call is the global event
+    ``first_event + i`` (noise, centroid jitter and checksum)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    labels = np.ascontiguousarray(labels, dtype=np.int64)
+    n = len(offsets) - 1
+    if n < 0:
+        raise ValueError("offsets needs n_events + 1 entries")
+    seed, first_event, _ = _abi.check_id_range(seed, first_event, n)
+    if len(points) != len(labels) or (n and offsets[-1] > len(points)):
+        raise ValueError("points / labels do not hold the rows the offsets name")
+    needed = _abi.RunStats()  # (the host-cloud call has no statistics: its rows come from attpc_trace_rows_last)
+
+    def call(out):
+        status = ctx.lib.attpc_trace_rows_at(ctx.handle, seed, first_event, n, _abi.iptr(offsets, _abi.C.c_int64),
+                                             _abi.dptr(points), _abi.iptr(labels, _abi.C.c_int64), out)
+        if status in (_abi.OK, _abi.E_CAPACITY):
+            needed.n_points = ctx.trace_rows_last()["n_rows"]
+        return status
+
+    rows = int(offsets[-1] - offsets[0]) if n else 0
+    arrays = call_with_capacity(ctx, n, max(16, rows, 4 * ctx._trace_readout_rows * n), call, "attpc_trace_rows_at", needed,
+                                holder=RowArrays, width=8, slack=16)
+    return (*arrays.result(), ctx.trace_rows_last())

@@ -150,14 +150,45 @@ class SpyralWriter(_RollingWriter):
     max_event on the group."""
 
     def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
-                 first_run_number: int = 0, npz_fallback: bool = True):
+                 first_run_number: int = 0, npz_fallback: bool = True, *, peaks=None, noise_seed: int = 0,
+                 **trace_kwargs):
+        """``peaks`` (keyword only; a ``detector.traces.PeakSettings``, default None = the reference's writer: one row
+        per cloud point): the rows are the peaks of the event's digitised pad traces instead (EXTENSION, trace rows of
+        include/attpc_engine.h), made on the device with the trace settings ``trace_kwargs`` (response, threshold,
+        offset, noise_sigma / noise_table, pedestals, noise_stream, readout, readout_pads as
+        ``detector.traces.configure_traces`` takes them); ``noise_seed`` keys the draws of ``write``, a run keys them on
+        its own seed.  The files have the same datasets either way."""
         self.response = get_response(config).copy()
+        self.peaks = peaks
+        if peaks is None and (trace_kwargs or noise_seed):
+            raise TypeError(f"SpyralWriter takes trace settings only with peaks=: {sorted(trace_kwargs) or ['noise_seed']}")
+        if peaks is not None:
+            from .traces import validate_trace_kwargs
+
+            validate_trace_kwargs(config, trace_kwargs)
+            self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
+        self._trace_kwargs = dict(trace_kwargs)
         super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)
 
+    def trace_kwargs(self) -> dict:
+        """The trace settings of a writer with ``peaks``, as ``configure_traces`` takes them."""
+        return dict(self._trace_kwargs)
+
     def write(self, data: np.ndarray, labels: np.ndarray, config: Config, event_number: int) -> None:
-        """[P,3] cloud -> Spyral rows (device), ADC threshold, z-sort, datasets (writer.py:194-255)."""
+        """[P,3] cloud -> Spyral rows (device), ADC threshold, z-sort, datasets (writer.py:194-255).  With ``peaks``:
+        the cloud's traces and their peaks on the device (``clouds_to_trace_rows``) -> datasets."""
         if config.pad_centers is None:
             raise ValueError("Pad centers are not assigned at write!")
+        if self.peaks is not None:
+            from .traces import clouds_to_trace_rows, configure_trace_rows
+
+            ctx = _abi.default_context()
+            configure_trace_rows(config, ctx, self.peaks, **self.trace_kwargs())
+            data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
+            _, rows, out_labels, _ = clouds_to_trace_rows(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
+                                                          seed=self.noise_seed, first_event=event_number)
+            self.write_rows(rows, out_labels, event_number, presorted=True)
+            return
         rows = convert_to_spyral(
             data, config.elec_params.windows_edge, config.elec_params.micromegas_edge,
             config.det_params.length, self.response, config.pad_centers, config.pad_sizes,

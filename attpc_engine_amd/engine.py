@@ -29,7 +29,7 @@ class Engine:
         self.n_rows = len(self.z)
         self.indices = list(indices) if indices is not None else default_indices(self.n_rows)
         self._out_cache = None  # (key, arrays) of the last run with reuse_buffers (call_with_capacity)
-        self._spyral_configured = self._traces_configured = False
+        self._spyral_configured = self._traces_configured = self._peaks_configured = False
         ctx = self.ctx
         kin, keep_k = pipeline.device_desc()
         ctx.check(ctx.lib.attpc_kin_configure(ctx.handle, kin), "attpc_kin_configure")
@@ -161,6 +161,44 @@ class Engine:
         return {**res, "pads": pads, "samples": samples, "trace": arrays.sums()}
 
 
+    # ---------------------------------------------------------------- trace rows: peaks of the traces as Spyral rows
+    def configure_peaks(self, peaks=None, **parameters) -> None:
+        """Upload the peak parameters of the trace rows: a ``detector.traces.PeakSettings`` or its keywords
+        (separation, prominence, min_width, max_width, rel_height, threshold; include/attpc_engine.h)."""
+        from .detector.traces import PeakSettings, configure_peaks
+
+        if peaks is not None and parameters:
+            raise TypeError("give a PeakSettings or its keywords, not both")
+        configure_peaks(self.ctx, PeakSettings(**parameters) if peaks is None else peaks)
+        self._peaks_configured = True
+
+    def run_trace_rows(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
+                       capacity_per_event: int = 2048) -> dict:
+        """Fused kinematics + detector + pad traces + the peaks of every kept trace as Spyral rows, all on the device
+        (``attpc_sim_run_trace_rows``; the traces as ``configure_traces`` set them, the geometry of
+        ``configure_spyral``, the peaks of ``configure_peaks``, each with its defaults if not called).  ``fetch=True``:
+        offsets [n+1], rows [P,8] (x mm, y mm, z mm, amplitude, integral, pad, centroid, pad scale; every event in
+        ascending z), labels [P], event_points [n] and the kinematics; ``fetch=False``: the rows stay on the device.
+        Both: ``trace_rows`` = {n_rows, row_checksum} and the cloud's ``stats`` (``n_points`` = the rows)."""
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
+        if not self._traces_configured:
+            self.configure_traces()
+        if not self._spyral_configured:
+            self.configure_spyral()
+        if not self._peaks_configured:
+            self.configure_peaks()
+        ctx = self.ctx
+        if not fetch:
+            stats, out = _abi.RunStats(), _abi.CloudOut()
+            ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
+                                                       None, None, None, out, stats), "attpc_sim_run_trace_rows")
+            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last()}
+        per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
+        arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
+                                    pinned, holder=RowArrays, width=8, slack=1024)
+        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last()}
+
+
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
               batch_size: int = 65536, context: _abi.Context | None = None) -> None:
     """run_kinematics_pipeline + run_simulation + SpyralWriter without the kinematics file and with
@@ -168,7 +206,8 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
     below the ADC threshold is still written, with 0 rows, and counts towards the file roll-over exactly
     as in run_simulation + SpyralWriter.write), in event order,
-    ``writer.write_rows(rows, labels, event_number, presorted=True)``, then ``close()``.  A writer that offers
+    ``writer.write_rows(rows, labels, event_number, presorted=True)``, then ``close()``.  A SpyralWriter with ``peaks``
+    gets the peaks of the event's pad traces as its rows (``Engine.run_trace_rows``).  A writer that offers
     ``write_traces`` (TraceWriter) gets ``write_traces(pads, samples, labels, event_number)`` per such event instead,
     the traces made on the device (``Engine.run_traces``) with the writer's noise settings."""
     engine = Engine(pipeline, config, indices, context=context)
@@ -177,6 +216,10 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     if kind == "traces":
         engine.configure_traces(config, writer.response, writer.threshold, writer.offset, **writer.noise_kwargs(),
                                 **writer.readout_kwargs())
+    elif kind == "trace_rows":
+        engine.configure_traces(config, **writer.trace_kwargs())
+        engine.configure_spyral(config)
+        engine.configure_peaks(writer.peaks)
     elif kind == "rows":
         engine.configure_spyral(config)
     else:
@@ -186,7 +229,10 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
         if kind == "traces":
             res = engine.run_traces(stop - start, seed=seed, first_event=start)
             return res["offsets"], res["event_points"], res["pads"], res["samples"], res["labels"]
-        res = engine.run_spyral(stop - start, seed=seed, first_event=start)
+        if kind == "trace_rows":
+            res = engine.run_trace_rows(stop - start, seed=seed, first_event=start)
+        else:
+            res = engine.run_spyral(stop - start, seed=seed, first_event=start)
         return res["offsets"], res["event_points"], res["rows"], res["labels"]
 
     deliver_events(writer, n_events, batch_size, batch, emit)

@@ -22,8 +22,8 @@
  *     batch / chunk / GPU count.
  *   - seeds are any u64.  A call's event ids first_event .. first_event + n_events - 1 must all lie in
  *     [0, 2^64): a range that would wrap past 2^64 is ATTPC_E_INVALID (attpc_kin_run, attpc_det_run,
- *     attpc_sim_run, their _spyral and _traces forms, attpc_det_tracks, attpc_det_scatter, attpc_sim_hint_next,
- *     attpc_traces_at).
+ *     attpc_sim_run, their _spyral, _traces and _trace_rows forms, attpc_det_tracks, attpc_det_scatter,
+ *     attpc_sim_hint_next, attpc_traces_at, attpc_trace_rows_at).
  *     Ids 2^40 apart share their jitter streams (the jitter counter holds event[39:0]) and nothing else.
  */
 #ifndef ATTPC_ENGINE_H
@@ -545,6 +545,82 @@ typedef struct attpc_trace_readout_desc {
  * call resets another.  ATTPC_E_INVALID for an unknown mode.  Enables the readout in attpc_sim_run_traces,
  * attpc_det_run_traces, attpc_traces_at and attpc_traces. */
 ATTPC_API int32_t attpc_trace_configure_readout(attpc_ctx* ctx, const attpc_trace_readout_desc* desc);
+
+/* ---- trace rows: peaks of the kept pad traces as Spyral rows, on the device (opt-in: without a call of the entry
+ * points below every output of every other entry point is what it is without this section) ----
+ * The first phase of Spyral's analysis (baseline, peak finding, point per peak), run on the chunk's traces in HBM
+ * behind the trace write pass, before anything crosses PCIe.
+ * Input: the kept trace rows of an event exactly as the trace contracts above define them -- hit, partial or full
+ * readout, with or without noise and pedestals, kept by the adc_threshold rule of attpc_trace_configure.  Every trace
+ * mode therefore composes with this stage as it is.
+ * Parameters (attpc_peak_desc, all f64): separation >= 1, prominence >= 0, 0 <= min_width <= max_width, rel_height in
+ * (0, 1], threshold.
+ * For a kept row of pad p in event e (global id) with samples trace[0..511]:
+ *   1. y[j] = trace[j] - ped_p, an integer (ped_p = 0 without pedestals).  The baseline is the configured pedestal.
+ *   2. Candidates: the strict local maxima of y, a flat top counted once at (first + last) div 2, never sample 0 or
+ *      511 (scipy.signal.find_peaks(y) without a condition).
+ *   3. Separation: a candidate closer than ceil(separation) samples to a kept candidate of higher priority is dropped;
+ *      priority = height y[k], and of two candidates of equal height the LATER one has priority.  Processed from the
+ *      highest priority down (scipy's `distance` rule with its tie made definite).
+ *   4. Prominence of each survivor on the whole of y: walk left from the peak while y[i] <= y[peak], keeping the
+ *      minimum (updated only by a strictly lower sample: of equal minima the one nearest the peak is the base), stop
+ *      at a higher sample or the edge; the same to the right; prominence = y[peak] - max(left_min, right_min);
+ *      kept iff prominence >= desc.prominence (scipy.signal.peak_prominences).
+ *   5. Width at h = (double)y[peak] - (double)prominence * rel_height (the product rounded, then subtracted): walk
+ *      left from the peak while i > left_base && h < y[i], then left_ip = i + (h - y[i]) / (y[i+1] - y[i]) if
+ *      y[i] < h, else i; mirrored for right_ip; kept iff min_width <= right_ip - left_ip <= max_width
+ *      (scipy.signal.peak_widths; f64, one rounding per operation).
+ *   6. A surviving peak k is a point iff y[k] > threshold (strict).  amplitude = y[k]; integral = the sum of |y[j]|
+ *      over j = floor(left_ip) .. ceil(right_ip) - 1; centroid = (double)k + u with u the Philox2x32-7 jitter
+ *      generator of the conventions at the top on counter (e[31:0], e[39:32] << 24 | k << 14 | p) and key word
+ *      seed[31:0] ^ rotl(seed[63:32], 13) ^ 0x300: a stream of its own beside the cloud's (0x100) and, like every
+ *      draw, a pure function of (seed, global event id, pad, sample).
+ *   7. Row of 8 f64 in the layout of convert_to_spyral (detector/writer.py:97-110): pad_centers[p] (x, y),
+ *      z = (windows_edge - centroid) / (windows_edge - micromegas_edge) * length * 1000.0 evaluated left to right
+ *      with every operation rounded, amplitude, integral, p, centroid, pad_sizes[p]; label (i64) = the trace row's
+ *      label (-1 for a noise-only row).  Geometry and edges are those of attpc_spyral_configure (its response and
+ *      threshold play no part); windows_edge != micromegas_edge and n_pads >= ATTPC_NUM_PADS, else ATTPC_E_INVALID.
+ *   8. An event's rows come in ascending z, i.e. descending centroid, equal centroids in ascending pad; events in id
+ *      order with CSR offsets.  event_points keeps its meaning (cloud rows before any suppression).
+ * With offset = argmax(R) in attpc_trace_configure a lone arrival at bucket t peaks at sample t, so its point's z is
+ * the arrival's z; with offset = 0 every point sits argmax(R) buckets late.
+ * The baseline is not fitted (Spyral's Fourier filter is for baselines that wander; these do not), and Spyral's later
+ * phases (clustering, fitting) are not part of this.
+ * Results of a call: rows of EIGHT doubles in out->points (capacity counts rows), out->labels, out->offsets,
+ * out->event_points; any of them may be NULL, and with points and labels both NULL the capacity does not bind: the
+ * rows stay on the device.  stats->n_points is the number of rows of the call (as attpc_sim_run_spyral reports its
+ * rows; the capacity needed on ATTPC_E_CAPACITY), every other field of stats keeps its cloud meaning.
+ * attpc_trace_rows_last gives the rows and the row checksum of the context's last trace-row call:
+ *   row_checksum = sum over the rows of (event * 2^23 + pad * 2^9 + k) mod 2^64, event the global event id. */
+typedef struct attpc_peak_desc {
+  double separation;  /* >= 1: candidates closer than ceil(separation) samples to a higher one are dropped */
+  double prominence;  /* >= 0 */
+  double min_width;   /* 0 <= min_width <= max_width, in samples at rel_height */
+  double max_width;
+  double rel_height;  /* in (0, 1] */
+  double threshold;   /* points have amplitude > threshold */
+} attpc_peak_desc;
+
+/* desc == NULL turns the stage off (the trace-row entry points then answer ATTPC_E_NOTCONFIGURED).  Independent of
+ * attpc_trace_configure, attpc_trace_configure_noise and attpc_trace_configure_readout: no call resets another.
+ * ATTPC_E_INVALID for a parameter outside the ranges above (NaN included). */
+ATTPC_API int32_t attpc_trace_configure_peaks(attpc_ctx* ctx, const attpc_peak_desc* desc);
+/* attpc_sim_run_traces, then the rows of every event's traces.  ATTPC_E_INVALID without attpc_spyral_configure or
+ * attpc_trace_configure. */
+ATTPC_API int32_t attpc_sim_run_trace_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                           const attpc_event_layout* layout, double* p4, double* vertex,
+                                           int32_t* kin_status, attpc_cloud_out* out, attpc_run_stats* stats);
+/* attpc_det_run_traces (kinematics from host arrays), then the rows. */
+ATTPC_API int32_t attpc_det_run_trace_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                           const attpc_event_layout* layout, const double* p4, const double* vertex,
+                                           attpc_cloud_out* out, attpc_run_stats* stats);
+/* attpc_traces_at (any host cloud; its rules for the rows), then the rows of its traces.  out->event_points receives
+ * the cloud rows of every event as given. */
+ATTPC_API int32_t attpc_trace_rows_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events,
+                                      const int64_t* offsets, const double* points, const int64_t* labels,
+                                      attpc_cloud_out* out);
+/* Rows and row checksum of the context's last trace-row call (either pointer may be NULL). */
+ATTPC_API int32_t attpc_trace_rows_last(attpc_ctx* ctx, int64_t* n_rows, uint64_t* row_checksum);
 
 #ifdef __cplusplus
 }
