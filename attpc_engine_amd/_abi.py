@@ -136,6 +136,35 @@ class PeakDesc(C.Structure):
                 ("max_width", C.c_double), ("rel_height", C.c_double), ("threshold", C.c_double)]
 
 
+class EventSummary(C.Structure):
+    _fields_ = [("n_points", C.c_uint32), ("n_kept", C.c_uint32), ("n_pads", C.c_uint32), ("tb_min", C.c_int32),
+                ("tb_max", C.c_int32), ("reserved", C.c_int32), ("charge", C.c_int64)]
+
+
+class TrackSummary(C.Structure):
+    _fields_ = [("n_points", C.c_uint32), ("n_kept", C.c_uint32), ("n_pads", C.c_uint32), ("tb_min", C.c_int32),
+                ("tb_max", C.c_int32), ("reserved", C.c_int32), ("charge", C.c_int64), ("rho2_max", C.c_double),
+                ("n_steps", C.c_int32), ("n_samples", C.c_int32), ("electrons", C.c_int64),
+                ("end_x", C.c_double), ("end_y", C.c_double), ("end_tb", C.c_double)]
+
+
+# the two records as numpy structured dtypes: itemsize and field offsets are those of include/attpc_engine.h
+EVENT_SUMMARY_DTYPE = np.dtype([("n_points", "<u4"), ("n_kept", "<u4"), ("n_pads", "<u4"), ("tb_min", "<i4"),
+                                ("tb_max", "<i4"), ("reserved", "<i4"), ("charge", "<i8")], align=True)
+TRACK_SUMMARY_DTYPE = np.dtype([("n_points", "<u4"), ("n_kept", "<u4"), ("n_pads", "<u4"), ("tb_min", "<i4"),
+                                ("tb_max", "<i4"), ("reserved", "<i4"), ("charge", "<i8"), ("rho2_max", "<f8"),
+                                ("n_steps", "<i4"), ("n_samples", "<i4"), ("electrons", "<i8"),
+                                ("end_x", "<f8"), ("end_y", "<f8"), ("end_tb", "<f8")], align=True)
+
+
+class SummaryDesc(C.Structure):
+    _fields_ = [("min_electrons", C.c_int64), ("pad_centers", _dp), ("n_pads", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SummaryOut(C.Structure):
+    _fields_ = [("events", C.POINTER(EventSummary)), ("tracks", C.POINTER(TrackSummary))]
+
+
 class TraceOut(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64),
@@ -227,6 +256,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_noise", "attpc_traces_at", "attpc_trace_configure_readout",
     "attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows", "attpc_trace_rows_at",
     "attpc_trace_rows_last",
+    "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -234,6 +264,9 @@ EXPORTED_SYMBOLS = (
 # entry point is the AttributeError ctypes raises.  The package's own library must have every symbol.
 TRACE_ROW_SYMBOLS = ("attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows",
                      "attpc_trace_rows_at", "attpc_trace_rows_last")
+
+# The summary entry points were added under ABI version 3 as well, after the trace rows: the same rule.
+SUMMARY_SYMBOLS = ("attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary")
 
 _lib = None
 
@@ -314,6 +347,19 @@ def load_library() -> C.CDLL:
     for name, argtypes in trace_rows.items():
         if not older:
             getattr(lib, name).argtypes = argtypes
+    summary = {
+        "attpc_summary_configure": [ctxp, C.POINTER(SummaryDesc)],
+        "attpc_sim_run_summary": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
+                                  C.POINTER(C.c_int32), C.POINTER(SummaryOut), C.POINTER(RunStats)],
+        "attpc_det_run_summary": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
+                                  C.POINTER(SummaryOut), C.POINTER(RunStats)],
+        "attpc_cloud_summary": [ctxp, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(EventLayout),
+                                C.POINTER(SummaryOut)],
+    }
+    no_summary = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in SUMMARY_SYMBOLS)
+    for name, argtypes in summary.items():
+        if not no_summary:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -334,7 +380,7 @@ def load_library() -> C.CDLL:
         ctxp, C.c_int64, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, _dp,
     ]
     for name in EXPORTED_SYMBOLS:
-        if older and name in TRACE_ROW_SYMBOLS:
+        if (older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -343,7 +389,7 @@ def load_library() -> C.CDLL:
     return lib
 
 
-CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks")
+CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks", "summary")
 
 
 class Context:

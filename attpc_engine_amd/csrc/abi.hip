@@ -200,6 +200,12 @@ struct attpc_ctx {
   bool peaks_on = false;           // attpc_trace_configure_peaks
   PeakDev peaks{};
   DevBuf peak_sums;                // [1] row checksum of the trace-row run in progress
+  bool summary_on = false;         // attpc_summary_configure
+  double summary_min = 0.0;        // min_electrons (kept: q >= it)
+  const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
+  std::vector<void*> summary_allocs;
+  // summaries of a batch (summary.hip): the records, and per chunk the segments grouped by event
+  DevBuf sm_events, sm_tracks, sm_seg_count, sm_seg_rank, sm_seg_start, sm_seg_list, sm_host_segs, sm_host_ctrl;
   int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
   uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
@@ -219,7 +225,7 @@ struct attpc_ctx {
   bool unpack_stop = false, unpack_failed = false;
 
   ~attpc_ctx() {  // (attpc_ctx_destroy has stopped everything first; the DevBuf / Pinned members free themselves)
-    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs, &readout_allocs})
+    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs, &readout_allocs, &summary_allocs})
       for (void* p : *v) (void)hipFree(p);
     for (void* p : host_allocs) (void)hipHostFree(p);
   }
@@ -821,7 +827,8 @@ void accumulate(attpc_run_stats* st, const ChunkResult& r) {
 // ------------------------------------------------------------------ assembly (delivered clouds) ----
 // What a run delivers: clouds (attpc_sim_run / attpc_det_run), Spyral rows (_spyral) or pad traces (_traces).
 // trace_rows: the traces as in `traces`, kept on the device, and their peaks as Spyral rows (_trace_rows).
-enum class OutMode { cloud, spyral, traces, trace_rows };
+// summary: a device-resident run whose chunks are reduced to event and track records behind their scatter (_summary).
+enum class OutMode { cloud, spyral, traces, trace_rows, summary };
 // the modes whose chunks go through the trace kernels
 bool makes_traces(OutMode mode) { return mode == OutMode::traces || mode == OutMode::trace_rows; }
 
@@ -833,6 +840,7 @@ struct RunOut {
   attpc_trace_out* trace = nullptr;  // traces
   int64_t rows = 0;                  // row cursor: rows of the chunks delivered so far
   bool over = false;                 // ... more than the caller's capacity
+  attpc_summary_out* summary = nullptr;  // summary (a resident run: neither cloud nor trace)
   bool resident() const { return !cloud && !trace; }
   int64_t* offsets() const { return cloud ? cloud->offsets : trace ? trace->offsets : nullptr; }
   int64_t* event_points() const { return cloud ? cloud->event_points : trace ? trace->event_points : nullptr; }
@@ -1353,6 +1361,91 @@ int32_t wait_unpacked(attpc_ctx* ctx, uint64_t ticket) {
   return ATTPC_OK;
 }
 
+// ------------------------------------------------------------------ summaries (summary.hip) ----
+// ensure() for a buffer that launches already queued on S may use: S is drained before it is re-allocated
+int32_t ensure_idle(attpc_ctx* ctx, DevBuf& b, size_t bytes) {
+  if (bytes <= b.bytes) return ATTPC_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return ensure(ctx, b, bytes);
+}
+
+attpc_event_summary empty_event_summary() {
+  attpc_event_summary r{};
+  r.tb_min = r.tb_max = -1;
+  return r;
+}
+
+// The records of `n` events of a batch (its events e0 ..), queued on S behind the launch that wrote the cloud
+// `points` / `labels` / `segs` with control words `d_ctrl`.  trk == nullptr: no tracks, the empty track parts.
+int32_t enqueue_summary(attpc_ctx* ctx, const unsigned long long* d_ctrl, const double* points, const int64_t* labels,
+                        const Segment* segs, int64_t seg_capacity, int64_t row_capacity, const attpc_event_layout& lay,
+                        const TrackBuffers* trk, uint32_t e0, uint32_t n) {
+  int32_t rc;
+  if (n == 0) return ATTPC_OK;
+  const size_t n_alloc = std::max<size_t>(n, (size_t)std::max(1, ctx->chunk_events));
+  if ((rc = ensure_idle(ctx, ctx->sm_seg_count, n_alloc * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure_idle(ctx, ctx->sm_seg_start, (n_alloc + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure_idle(ctx, ctx->sm_seg_rank, (size_t)std::max<int64_t>(seg_capacity, 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure_idle(ctx, ctx->sm_seg_list, (size_t)std::max<int64_t>(seg_capacity, 1) * sizeof(uint32_t)))) return rc;
+  SummaryArgs a{};
+  a.points = points;
+  a.labels = labels;
+  a.segments = segs;
+  a.ctrl = d_ctrl;
+  a.seg_capacity = seg_capacity;
+  a.row_capacity = row_capacity;
+  a.n_events = n;
+  a.event0 = e0;
+  a.seg_count = static_cast<uint32_t*>(ctx->sm_seg_count.p);
+  a.seg_rank = static_cast<uint32_t*>(ctx->sm_seg_rank.p);
+  a.seg_start = static_cast<const int64_t*>(ctx->sm_seg_start.p);
+  a.seg_list = static_cast<uint32_t*>(ctx->sm_seg_list.p);
+  if (trk) a.trk = *trk;
+  a.n_sim = lay.n_sim;
+  a.slot_nibbles[0] = a.slot_nibbles[1] = ~0ull;  // 15 = no position
+  for (int label = 0; label < ATTPC_MAX_ROWS; ++label)
+    for (int s = 0; s < lay.n_sim; ++s)
+      if (lay.indices[s] == label) {  // the first position that holds the label
+        uint64_t& word = a.slot_nibbles[label / 16];
+        word = (word & ~(15ull << (4 * (label % 16)))) | ((uint64_t)s << (4 * (label % 16)));
+        break;
+      }
+  a.min_electrons = ctx->summary_min;
+  a.pad_centers = ctx->summary_centers;
+  a.events = static_cast<attpc_event_summary*>(ctx->sm_events.p);
+  a.tracks = lay.n_sim ? static_cast<attpc_track_summary*>(ctx->sm_tracks.p) : nullptr;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->sm_seg_count.p, 0, (size_t)n * sizeof(uint32_t), ctx->stream));
+  const uint32_t seg_wgs = (uint32_t)std::min<int64_t>((int64_t)ctx->n_cus * 4, (std::max<int64_t>(seg_capacity, 1) + 255) / 256);
+  launch_summary_count(ctx->stream, a, seg_wgs);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(ctx->sm_seg_count.p), n,
+                     static_cast<int64_t*>(ctx->sm_seg_start.p), static_cast<int64_t*>(nullptr), d_ctrl);
+  HIP_TRY(ctx, hipGetLastError());
+  launch_summary_fill(ctx->stream, a, seg_wgs);
+  HIP_TRY(ctx, hipGetLastError());
+  launch_summary_events(ctx->stream, a, std::min<uint32_t>(n, (uint32_t)ctx->n_cus * 8u));
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// the record buffers of a batch of nb events
+int32_t ensure_summary_records(attpc_ctx* ctx, uint32_t nb, int n_sim) {
+  int32_t rc;
+  if ((rc = ensure_idle(ctx, ctx->sm_events, std::max<size_t>(nb, 1) * sizeof(attpc_event_summary)))) return rc;
+  return ensure_idle(ctx, ctx->sm_tracks, std::max<size_t>((size_t)nb * (size_t)std::max(n_sim, 1), 1) * sizeof(attpc_track_summary));
+}
+
+// The settled records of a batch (on the device) to the caller's arrays, as events first_local .. of the call (queued on S).
+int32_t copy_summary(attpc_ctx* ctx, const attpc_summary_out* out, uint64_t first_local, uint32_t nb, int n_sim) {
+  if (out->events && nb)
+    HIP_TRY(ctx, hipMemcpyAsync(out->events + first_local, ctx->sm_events.p, (size_t)nb * sizeof(attpc_event_summary),
+                                hipMemcpyDeviceToHost, ctx->stream));
+  if (out->tracks && nb && n_sim)
+    HIP_TRY(ctx, hipMemcpyAsync(out->tracks + first_local * (uint64_t)n_sim, ctx->sm_tracks.p,
+                                (size_t)nb * (size_t)n_sim * sizeof(attpc_track_summary), hipMemcpyDeviceToHost, ctx->stream));
+  return ATTPC_OK;
+}
+
 // ------------------------------------------------------------------ the run loop ----
 struct RunSource {   // where a batch's kinematics come from
   bool from_kernel = false;        // attpc_sim_run: kin_run_kernel on T
@@ -1409,6 +1502,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     if ((rc = queue_next_once())) return rc;
     if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT && nb)  // their noise-only rows
       return trace_host_events(ctx, o, batch_first_local, nb, nullptr, nullptr, nullptr, seed, batch_first_global);
+    if (o.summary && o.summary->events) std::fill(o.summary->events + batch_first_local, o.summary->events + batch_first_local + nb, empty_event_summary());
     if (int64_t* offsets = o.offsets()) std::fill(offsets + batch_first_local, offsets + batch_first_local + nb + 1, o.rows);
     if (int64_t* event_points = o.event_points()) std::fill(event_points + batch_first_local, event_points + batch_first_local + nb, 0);
     return ATTPC_OK;
@@ -1425,6 +1519,14 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     ctx->lone_ready = true;
   }
   struct Chunk { uint32_t e0, n; int slot; };
+  // summary mode: the records of chunk c, queued directly behind its scatter (the next chunk overwrites the cloud)
+  auto summarise = [&](const Chunk& c) -> int32_t {
+    if (!o.summary) return ATTPC_OK;
+    return enqueue_summary(ctx, static_cast<const unsigned long long*>(ctx->out_ctrl.p) + (size_t)c.slot * CTRL_WORDS,
+                           static_cast<const double*>(ctx->points.p), static_cast<const int64_t*>(ctx->labels.p),
+                           static_cast<const Segment*>(ctx->segments.p), ctx->seg_capacity, ctx->cloud_capacity, lay, &trk, c.e0, c.n);
+  };
+  if (o.summary && (rc = ensure_summary_records(ctx, nb, lay.n_sim))) return rc;
   // The scatter of chunk c (and its assembly into `as`, when delivered) has completed: read its control words, and
   // while the launch ran out of room, queue it again with larger buffers (and the assembly behind it) and read again.
   auto settle = [&](const Chunk& c, AsmSet* as) -> int32_t {
@@ -1438,6 +1540,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
         if ((rc2 = enqueue_assembly(ctx, c.slot, *as, c.n, o.mode, seed, batch_first_global + c.e0))) return rc2;
         HIP_TRY(ctx, hipEventSynchronize(as->ready));
       } else {
+        if ((rc2 = summarise(c))) return rc2;  // (a repeated chunk overwrites its records)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       }
       read_scatter(ctx, c.slot, c.n, &r, &min_rows, &min_segs);
@@ -1455,6 +1558,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
         const uint32_t n = next_chunk_events(ctx, nb - e0);
         const Chunk c{e0, n, (int)group.size()};
         if ((rc = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + e0, e0, n, 0, 0))) return rc;
+        if ((rc = summarise(c))) return rc;
         group.push_back(c);
         e0 += n;
         if (ctx->rows_per_event <= 0.0) break;  // pilot chunk: size the rest from what it produced
@@ -1464,7 +1568,8 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
       for (const Chunk& c : group)
         if ((rc = settle(c, nullptr))) return rc;
     }
-    return ATTPC_OK;
+    // every chunk of the batch has settled: its records are final
+    return o.summary ? copy_summary(ctx, o.summary, batch_first_local, nb, lay.n_sim) : ATTPC_OK;
   }
   // delivered clouds: chunk c+1 is scattered and assembled while chunk c crosses PCIe
   Chunk prev{0, 0, -1};
@@ -1702,12 +1807,16 @@ int32_t run_entry(const char* name, attpc_ctx* ctx, uint64_t seed, uint64_t firs
     const int32_t rc0 = trace_rows_ready(ctx, name);
     if (rc0) return rc0;
   }
+  if (o.mode == OutMode::summary) {
+    if (!o.summary) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_summary_out", name);
+    if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
+  }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc = validate_layout(ctx, layout, true);
   if (rc) return rc;
   if (src.from_kernel && layout->n_rows != kin_rows(ctx))
     return fail(ctx, ATTPC_E_INVALID, "layout.n_rows=%d but the pipeline has %d rows", layout->n_rows, kin_rows(ctx));
-  if (makes_traces(o.mode) && (rc = drop_prefetch(ctx))) return rc;  // a trace call is never the announced one
+  if ((makes_traces(o.mode) || o.mode == OutMode::summary) && (rc = drop_prefetch(ctx))) return rc;  // a trace or summary call is never the announced one
   return run_events(ctx, seed, first_event, n_events, *layout, src, sink, o, stats);
 }
 
@@ -2301,6 +2410,97 @@ int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
   if ((rc = host_cloud_run(ctx, seed, first_event, n_events, offsets, points, labels, o))) return rc;
   if ((rc = read_trace_sums(ctx, o))) return rc;
   return run_status(ctx, attpc_run_stats{}, nullptr, o);
+}
+
+// ---- event and track summaries (summary.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_summary_configure(attpc_ctx* ctx, const attpc_summary_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d) {
+    if (d->min_electrons < 0) return fail(ctx, ATTPC_E_INVALID, "summary min_electrons %lld < 0", (long long)d->min_electrons);
+    if (d->n_pads < ATTPC_NUM_PADS) return fail(ctx, ATTPC_E_INVALID, "summary geometry of %d pads, the clouds name pads up to %d", d->n_pads, ATTPC_NUM_PADS - 1);
+    if (!d->pad_centers) return fail(ctx, ATTPC_E_INVALID, "summary geometry without pad centres");
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  free_all(ctx->summary_allocs);
+  ctx->summary_on = false;
+  ctx->summary_centers = nullptr;
+  if (!d) return ATTPC_OK;
+  int32_t rc;
+  if ((rc = upload(ctx, ctx->summary_allocs, d->pad_centers, (size_t)d->n_pads * 2, &ctx->summary_centers))) return rc;
+  ctx->summary_min = (double)d->min_electrons;
+  ctx->summary_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_sim_run_summary(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                              const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
+                              attpc_summary_out* out, attpc_run_stats* stats) {
+  RunOut o{OutMode::summary};
+  o.summary = out;
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{true}, RunSink{p4, vertex, kin_status}, o, stats);
+}
+
+int32_t attpc_det_run_summary(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                              const attpc_event_layout* layout, const double* p4, const double* vertex,
+                              attpc_summary_out* out, attpc_run_stats* stats) {
+  RunOut o{OutMode::summary};
+  o.summary = out;
+  return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{}, o, stats);
+}
+
+int32_t attpc_cloud_summary(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                            const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out) {
+  if (!ctx || !out) return ATTPC_E_INVALID;
+  if (n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
+  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_cloud_summary takes at most 2^31 - 1 events per call");
+  if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
+  int32_t rc;
+  if ((rc = validate_layout(ctx, layout, false))) return rc;
+  const uint32_t n = (uint32_t)n_events;
+  const int64_t first = n ? offsets[0] : 0;
+  if (first < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
+  for (uint32_t e = 0; e < n; ++e) {
+    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %u", e);
+    if (offsets[e + 1] - offsets[e] > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "event %u has 2^31 rows or more", e);
+  }
+  const int64_t rows = n ? offsets[n] - first : 0;
+  if (rows > 0 && (!points || !labels)) return ATTPC_E_INVALID;
+  for (int64_t r = first; r < first + rows; ++r) {  // the contract's rows
+    const double padf = points[3 * r], tb = points[3 * r + 1], q = points[3 * r + 2];
+    if (!(padf >= 0.0 && padf < (double)ATTPC_NUM_PADS) || padf != std::floor(padf))
+      return fail(ctx, ATTPC_E_INVALID, "row %lld: pad %g is not an integer in [0, %d)", (long long)r, padf, ATTPC_NUM_PADS);
+    if (!(tb >= 0.0 && tb < (double)ATTPC_NUM_TB))
+      return fail(ctx, ATTPC_E_INVALID, "row %lld: time bucket %g outside [0, 512)", (long long)r, tb);
+    if (!(q >= 0.0) || std::isinf(q)) return fail(ctx, ATTPC_E_INVALID, "row %lld: electrons %g", (long long)r, q);
+  }
+  if (n == 0) return ATTPC_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if ((rc = drop_prefetch(ctx))) return rc;
+  if ((rc = sync_all(ctx))) return rc;
+  // the cloud on the device as the kernels of the fused path find it: rows in place, one segment per event
+  AsmSet& as = ctx->aset[0];
+  const size_t cap = (size_t)std::max<int64_t>(rows, 1);
+  if ((rc = ensure(ctx, as.points, cap * 3 * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, as.labels, cap * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, ctx->sm_host_segs, (size_t)n * sizeof(Segment)))) return rc;
+  if ((rc = ensure(ctx, ctx->sm_host_ctrl, 8 * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure_summary_records(ctx, n, layout->n_sim))) return rc;
+  std::vector<Segment> segs(n);
+  for (uint32_t e = 0; e < n; ++e) segs[e] = Segment{(int32_t)e, (int32_t)(offsets[e + 1] - offsets[e]), offsets[e] - first, 0};
+  const unsigned long long ctrl[8] = {(unsigned long long)rows, (unsigned long long)n, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(ctx, hipMemcpy(ctx->sm_host_segs.p, segs.data(), segs.size() * sizeof(Segment), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->sm_host_ctrl.p, ctrl, sizeof ctrl, hipMemcpyHostToDevice));
+  if (rows > 0) {
+    HIP_TRY(ctx, hipMemcpy(as.points.p, points + 3 * first, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(as.labels.p, labels + first, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice));
+  }
+  if ((rc = enqueue_summary(ctx, static_cast<const unsigned long long*>(ctx->sm_host_ctrl.p), static_cast<const double*>(as.points.p),
+                            static_cast<const int64_t*>(as.labels.p), static_cast<const Segment*>(ctx->sm_host_segs.p), (int64_t)n,
+                            rows, *layout, nullptr, 0, n))) return rc;
+  if ((rc = copy_summary(ctx, out, 0, n, layout->n_sim))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return ATTPC_OK;
 }
 
 // ---- trace rows (peaks.hip; the contract is in include/attpc_engine.h) ----

@@ -164,4 +164,34 @@ void launch_peak_rows(hipStream_t s, const SpyralDev& sp, uint64_t seed, uint32_
                       double* centroid, uint32_t* sort_idx, double* sort_key, double* rows, int64_t* out_labels,
                       unsigned long long* sums);
 
+// event and track summaries of a scattered chunk (summary.hip; attpc_summary_configure, the contract is in
+// include/attpc_engine.h).  The rows are read in place through the launch's segment list.
+struct SummaryArgs {
+  const double* points;            // the chunk's cloud as the scatter left it: [row_capacity][3], with holes
+  const int64_t* labels;           // [row_capacity]
+  const Segment* segments;
+  const unsigned long long* ctrl;  // the scatter launch's control words: [1] segments, [6] out of capacity
+  int64_t seg_capacity;
+  int64_t row_capacity;
+  uint32_t n_events;               // events of the chunk
+  uint32_t event0;                 // first event of the chunk within the track batch (tracks, records)
+  uint32_t* seg_count;             // [n_events] segments of every event, zero before summary_count_kernel
+  uint32_t* seg_rank;              // [seg_capacity] place of a segment among its event's
+  const int64_t* seg_start;        // [n_events + 1] exclusive scan of seg_count
+  uint32_t* seg_list;              // [seg_capacity] segment numbers grouped by event
+  TrackBuffers trk;                // trk.counts == nullptr: no tracks (attpc_cloud_summary), empty track parts
+  int32_t n_sim;
+  uint64_t slot_nibbles[2];        // 4 bits per label (16 labels a word): its first position in layout->indices, 15 = none
+  double min_electrons;
+  const double* pad_centers;       // [>= ATTPC_NUM_PADS][2]
+  attpc_event_summary* events;     // [batch events] or nullptr
+  attpc_track_summary* tracks;     // [batch events][n_sim] or nullptr
+};
+// seg_count / seg_rank of the launch's segments (seg_count zeroed by the caller on the same stream)
+void launch_summary_count(hipStream_t s, const SummaryArgs& a, uint32_t n_workgroups);
+// seg_list from seg_start and seg_rank
+void launch_summary_fill(hipStream_t s, const SummaryArgs& a, uint32_t n_workgroups);
+// the records of events event0 .. event0 + n_events - 1, plain stores: a repeated chunk overwrites them
+void launch_summary_events(hipStream_t s, const SummaryArgs& a, uint32_t n_workgroups);
+
 }  // namespace attpc

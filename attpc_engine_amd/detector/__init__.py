@@ -2,6 +2,7 @@
 ``detector/__init__.py:13-21``) plus the batch entry points, device backed."""
 from . import parameters as _parameters
 from . import simulator as _simulator
+from . import summary as _summary
 from . import traces as _traces
 from . import writer as _writer
 
@@ -10,6 +11,8 @@ _EXPORTS = {
     _simulator: ("run_simulation", "simulate", "simulate_batch"),
     _traces: ("configure_traces", "simulate_batch_traces", "clouds_to_traces", "PeakSettings", "configure_trace_rows",
               "simulate_batch_trace_rows", "clouds_to_trace_rows"),
+    _summary: ("SummarySettings", "configure_summary", "simulate_batch_summary", "clouds_to_summary",
+               "electrons_above_threshold"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter"),
 }
 __all__ = []

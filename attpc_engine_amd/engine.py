@@ -14,7 +14,7 @@ import numpy as np
 from . import _abi, nuclear_map
 from .detector.luts import build_det_desc, build_layout, species_for
 from .detector.simulator import default_indices, deliver_events, delivery_of
-from .outputs import RowArrays, call_with_capacity
+from .outputs import RowArrays, SummaryArrays, call_with_capacity
 
 
 class Engine:
@@ -29,7 +29,7 @@ class Engine:
         self.n_rows = len(self.z)
         self.indices = list(indices) if indices is not None else default_indices(self.n_rows)
         self._out_cache = None  # (key, arrays) of the last run with reuse_buffers (call_with_capacity)
-        self._spyral_configured = self._traces_configured = self._peaks_configured = False
+        self._spyral_configured = self._traces_configured = self._peaks_configured = self._summary_configured = False
         ctx = self.ctx
         kin, keep_k = pipeline.device_desc()
         ctx.check(ctx.lib.attpc_kin_configure(ctx.handle, kin), "attpc_kin_configure")
@@ -197,6 +197,38 @@ class Engine:
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last()}
+
+
+    # ---------------------------------------------------------------- event and track summaries of a resident run
+    def configure_summary(self, config=None, min_electrons: int | None = None) -> None:
+        """Upload the summary settings (include/attpc_engine.h): ``min_electrons`` -- a cloud row is kept iff its
+        electrons reach it; default ``detector.summary.electrons_above_threshold(config)``: the row survives the ADC
+        threshold as a Spyral row -- and the pad centres (the geometry of ``rho2_max``)."""
+        from .detector.summary import configure_summary
+
+        configure_summary(config or self.config, self.ctx, min_electrons)
+        self._summary_configured = True
+
+    def run_summary(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
+        """A device-resident run (``run(fetch=False)``: nothing of the clouds crosses PCIe) that reduces every chunk's
+        cloud and track samples on the device, behind its scatter, to one record per event and one per (event,
+        simulated nucleus) (``attpc_sim_run_summary``): ``events`` [n] and ``tracks`` [n, n_sim], numpy structured
+        arrays (``_abi.EVENT_SUMMARY_DTYPE`` / ``_abi.TRACK_SUMMARY_DTYPE``; the fields are defined in
+        include/attpc_engine.h), ``indices`` (the nucleus of every track position), the kinematics and the cloud's
+        ``stats``.  Configures with the defaults if ``configure_summary`` was not called."""
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
+        if not self._summary_configured:
+            self.configure_summary()
+        ctx, stats = self.ctx, _abi.RunStats()
+        p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
+        vertex = np.empty((n_events, 3), dtype=np.float64)
+        status = np.empty(n_events, dtype=np.int32)
+        arrays = SummaryArrays(n_events, n_sim=len(self.indices))
+        ctx.check(ctx.lib.attpc_sim_run_summary(ctx.handle, seed, first_event, n_events, self.layout, _abi.dptr(p4),
+                                                _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32), arrays.out, stats),
+                  "attpc_sim_run_summary")
+        return {"events": arrays.events, "tracks": arrays.tracks, "indices": list(self.indices), "vertex": vertex,
+                "p4": p4, "status": status, "stats": stats.as_dict()}
 
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,

@@ -2,7 +2,8 @@
 
 A run that delivers clouds, Spyral rows or pad traces writes into arrays the caller owns (``attpc_cloud_out`` /
 ``attpc_trace_out``, include/attpc_engine.h) and answers ATTPC_E_CAPACITY, with the rows it needs, when they are too
-small.  ``RowArrays`` and ``TraceArrays`` hold such arrays together with the struct that points at them;
+small.  ``RowArrays`` and ``TraceArrays`` hold such arrays together with the struct that points at them (``SummaryArrays``: the
+fixed-size records of a summary run, ``attpc_summary_out``, which have no capacity);
 ``call_with_capacity`` is the only place that allocates them, calls and allocates again.
 """
 from __future__ import annotations
@@ -64,6 +65,25 @@ class TraceArrays:
     def result(self):
         total = int(self.out.n_rows)
         return self.offsets, self.pads[:total], self.samples[:total], self.labels[:total]
+
+
+class SummaryArrays:
+    """Caller arrays of one summary call -- ``events`` [n] and ``tracks`` [n, n_sim], structured
+    (``_abi.EVENT_SUMMARY_DTYPE`` / ``_abi.TRACK_SUMMARY_DTYPE``) -- and the ``attpc_summary_out`` that points at them.
+    The sizes are known: ``capacity`` plays no part and ATTPC_E_CAPACITY never comes."""
+
+    def __init__(self, n_events: int, capacity: int = 0, make=None, n_sim: int = 0):
+        make = make or _host_empty
+        self.events = make((n_events,), _abi.EVENT_SUMMARY_DTYPE)
+        self.tracks = make((n_events, n_sim), _abi.TRACK_SUMMARY_DTYPE)
+        self.out = _abi.SummaryOut(self.events.ctypes.data_as(_abi.C.POINTER(_abi.EventSummary)),
+                                   self.tracks.ctypes.data_as(_abi.C.POINTER(_abi.TrackSummary)))
+
+    def needed(self, stats) -> int:
+        return 0
+
+    def result(self):
+        return self.events, self.tracks
 
 
 def call_with_capacity(ctx: _abi.Context, n_events: int, capacity: int, call, what: str, stats=None,

@@ -22,7 +22,7 @@
  *     batch / chunk / GPU count.
  *   - seeds are any u64.  A call's event ids first_event .. first_event + n_events - 1 must all lie in
  *     [0, 2^64): a range that would wrap past 2^64 is ATTPC_E_INVALID (attpc_kin_run, attpc_det_run,
- *     attpc_sim_run, their _spyral, _traces and _trace_rows forms, attpc_det_tracks, attpc_det_scatter,
+ *     attpc_sim_run, their _spyral, _traces, _trace_rows and _summary forms, attpc_det_tracks, attpc_det_scatter,
  *     attpc_sim_hint_next, attpc_traces_at, attpc_trace_rows_at).
  *     Ids 2^40 apart share their jitter streams (the jitter counter holds event[39:0]) and nothing else.
  */
@@ -621,6 +621,97 @@ ATTPC_API int32_t attpc_trace_rows_at(attpc_ctx* ctx, uint64_t seed, uint64_t fi
                                       attpc_cloud_out* out);
 /* Rows and row checksum of the context's last trace-row call (either pointer may be NULL). */
 ATTPC_API int32_t attpc_trace_rows_last(attpc_ctx* ctx, int64_t* n_rows, uint64_t* row_checksum);
+
+/* ---- event and track summaries of a device-resident run (opt-in: without a call of the entry points below every
+ * output of every other entry point is what it is without this section) ----
+ * A summary run is a device-resident run (attpc_sim_run with out == NULL: same chunks, no event-ordered copy of the
+ * cloud) that reduces every chunk's cloud and track samples, in place and right behind its scatter, to one fixed-size
+ * record per event and one per (event, simulated nucleus): a few hundred bytes per event cross the link instead of
+ * the cloud.
+ * Settings (attpc_summary_desc): min_electrons >= 0 -- a cloud row is KEPT iff its electrons q >= min_electrons (0
+ * keeps every row) -- and pad_centers [n_pads, 2] (mm), n_pads >= ATTPC_NUM_PADS: the geometry of rho2_max, a copy of
+ * the mode's own.
+ * For the event with global id e, over its cloud rows (pad p, tau, q, label l) exactly as attpc_sim_run / attpc_det_run
+ * produce them for the same seed and id (every extension included), t = floor(tau):
+ *   - event record: n_points = all rows (what event_points reports); n_kept = kept rows; n_pads = distinct pads among
+ *     the kept rows; tb_min / tb_max = smallest / largest t over the kept rows, -1 / -1 without one; charge = sum of q
+ *     over ALL rows (whole numbers: the event's share of charge_checksum).
+ *   - track record, one per event and position s of layout->indices ([n_events][n_sim]), over the rows with
+ *     l == indices[s]: the same six fields, and rho2_max = max over the kept rows of x * x + y * y with
+ *     (x, y) = pad_centers[p], each product rounded and then added (no fused multiply-add), -1.0 without a kept row.
+ *     A cloud row carries the label of the nucleus that touched its (pad, time bucket) cell LAST
+ *     (detector/simulator.py:40-47): a cell shared by two tracks counts, charge and all, for the later one.
+ *     The track part: n_steps = ODE samples recorded for the track and n_samples = track samples with >= 1 electron
+ *     (n_steps / counts of attpc_det_tracks); electrons = sum of the samples' fourth column (electrons x gain: what
+ *     the track put into the gas, before the pad plane lost any of it); end_x, end_y, end_tb = columns 0..2 of the
+ *     last sample with >= 1 electron (m, m, time bucket), NaN with n_samples == 0.
+ *   - a position whose species is skipped (species_of_row == -1) has an all-empty record.  A row that occurs twice in
+ *     indices: the cloud part of its label goes to the first position that holds it, later positions get the empty
+ *     cloud part; the track part is per position either way.
+ * Every field is a count, an integer sum, a minimum or a maximum: a pure function of (seed, global event id) that does
+ * not depend on chunking, on how a call's id range is split, on the scatter build or on the order in which workgroups
+ * run.  attpc_run_stats keeps its cloud meaning (what attpc_sim_run reports for the same ids); the id-range rules at
+ * the top apply; a pending attpc_sim_hint_next is dropped.  The sizes are known: there is no capacity. */
+typedef struct attpc_event_summary {
+  uint32_t n_points;
+  uint32_t n_kept;
+  uint32_t n_pads;
+  int32_t tb_min;
+  int32_t tb_max;
+  int32_t reserved;   /* 0 */
+  int64_t charge;
+} attpc_event_summary;  /* 32 bytes */
+
+typedef struct attpc_track_summary {
+  uint32_t n_points;
+  uint32_t n_kept;
+  uint32_t n_pads;
+  int32_t tb_min;
+  int32_t tb_max;
+  int32_t reserved;   /* 0 */
+  int64_t charge;
+  double rho2_max;    /* mm^2 */
+  int32_t n_steps;
+  int32_t n_samples;
+  int64_t electrons;
+  double end_x;       /* m */
+  double end_y;       /* m */
+  double end_tb;      /* time bucket */
+} attpc_track_summary;  /* 80 bytes */
+
+typedef struct attpc_summary_desc {
+  int64_t min_electrons;     /* >= 0 */
+  const double* pad_centers; /* [n_pads, 2] mm */
+  int32_t n_pads;            /* >= ATTPC_NUM_PADS */
+  int32_t reserved;
+} attpc_summary_desc;
+
+/* Host output of a summary call; either array may be NULL. */
+typedef struct attpc_summary_out {
+  attpc_event_summary* events; /* [n_events] */
+  attpc_track_summary* tracks; /* [n_events * n_sim] */
+} attpc_summary_out;
+
+/* desc == NULL turns the mode off (the entry points below then answer ATTPC_E_NOTCONFIGURED).  Independent of
+ * attpc_spyral_configure, the attpc_trace_configure* calls and the peak stage: no call resets another.
+ * ATTPC_E_INVALID for min_electrons < 0, n_pads < ATTPC_NUM_PADS or pad_centers == NULL. */
+ATTPC_API int32_t attpc_summary_configure(attpc_ctx* ctx, const attpc_summary_desc* desc);
+/* attpc_sim_run with out == NULL, plus the records of every event and track. */
+ATTPC_API int32_t attpc_sim_run_summary(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                        const attpc_event_layout* layout, double* p4, double* vertex,
+                                        int32_t* kin_status, attpc_summary_out* out, attpc_run_stats* stats);
+/* The same with kinematics from host arrays p4 [n, n_rows, 4] / vertex [n, 3] (the file-driven flow). */
+ATTPC_API int32_t attpc_det_run_summary(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                        const attpc_event_layout* layout, const double* p4, const double* vertex,
+                                        attpc_summary_out* out, attpc_run_stats* stats);
+/* The cloud part for any host cloud in CSR form, through the kernel of the fused path: offsets [n_events + 1]
+ * (nondecreasing), points [rows, 3] (pad, tau, electrons), labels [rows].  Every row needs an integer pad in
+ * [0, ATTPC_NUM_PADS), 0 <= tau < 512 and finite electrons >= 0, else ATTPC_E_INVALID; distinct (pad, t) is neither
+ * required nor checked.  Rows whose label is not in layout->indices count for the event record only.  The track part of
+ * every record is the empty one (n_steps = n_samples = 0, electrons = 0, ends NaN).  Needs attpc_summary_configure
+ * only (layout->species_of_row is ignored). */
+ATTPC_API int32_t attpc_cloud_summary(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                                      const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out);
 
 #ifdef __cplusplus
 }
