@@ -165,6 +165,29 @@ class SummaryOut(C.Structure):
     _fields_ = [("events", C.POINTER(EventSummary)), ("tracks", C.POINTER(TrackSummary))]
 
 
+class SelectDesc(C.Structure):
+    _fields_ = [("n_kept_lo", C.c_uint32), ("n_kept_hi", C.c_uint32), ("n_pads_lo", C.c_uint32), ("n_pads_hi", C.c_uint32),
+                ("tb_span_lo", C.c_uint32), ("tb_span_hi", C.c_uint32), ("charge_lo", C.c_int64), ("charge_hi", C.c_int64),
+                ("track_mask", C.c_uint32), ("min_tracks", C.c_uint32),
+                ("track_n_kept_lo", C.c_uint32), ("track_n_kept_hi", C.c_uint32),
+                ("track_n_pads_lo", C.c_uint32), ("track_n_pads_hi", C.c_uint32),
+                ("track_n_samples_lo", C.c_uint32), ("track_n_samples_hi", C.c_uint32),
+                ("track_rho2_max_lo", C.c_double), ("track_rho2_max_hi", C.c_double),
+                ("track_end_tb_lo", C.c_double), ("track_end_tb_hi", C.c_double),
+                ("track_end_rho2_lo", C.c_double), ("track_end_rho2_hi", C.c_double)]
+
+
+SELECT_CLOUD, SELECT_SPYRAL = 0, 1
+
+
+class SelectOut(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("capacity", C.c_int64),
+                ("offsets", C.POINTER(C.c_int64)), ("points", _dp), ("labels", C.POINTER(C.c_int64)),
+                ("event_points", C.POINTER(C.c_int64)), ("passed", C.POINTER(C.c_uint8)),
+                ("events", C.POINTER(EventSummary)), ("tracks", C.POINTER(TrackSummary)),
+                ("n_passed", C.c_int64), ("n_rows", C.c_int64)]
+
+
 class TraceOut(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64),
@@ -257,6 +280,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows", "attpc_trace_rows_at",
     "attpc_trace_rows_last",
     "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
+    "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -267,6 +291,9 @@ TRACE_ROW_SYMBOLS = ("attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", 
 
 # The summary entry points were added under ABI version 3 as well, after the trace rows: the same rule.
 SUMMARY_SYMBOLS = ("attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary")
+
+# ... and the selected delivery after the summaries: the same rule.
+SELECT_SYMBOLS = ("attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select")
 
 _lib = None
 
@@ -360,6 +387,19 @@ def load_library() -> C.CDLL:
     for name, argtypes in summary.items():
         if not no_summary:
             getattr(lib, name).argtypes = argtypes
+    select = {
+        "attpc_select_configure": [ctxp, C.POINTER(SelectDesc)],
+        "attpc_sim_run_selected": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
+                                   C.POINTER(C.c_int32), C.POINTER(SelectOut), C.POINTER(RunStats)],
+        "attpc_det_run_selected": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
+                                   C.POINTER(SelectOut), C.POINTER(RunStats)],
+        "attpc_cloud_select": [ctxp, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(EventLayout),
+                               C.POINTER(SummaryOut), C.POINTER(C.c_uint8)],
+    }
+    no_select = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in SELECT_SYMBOLS)
+    for name, argtypes in select.items():
+        if not no_select:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -380,7 +420,8 @@ def load_library() -> C.CDLL:
         ctxp, C.c_int64, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, _dp,
     ]
     for name in EXPORTED_SYMBOLS:
-        if (older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS):
+        if ((older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS)
+                or (no_select and name in SELECT_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -389,7 +430,7 @@ def load_library() -> C.CDLL:
     return lib
 
 
-CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks", "summary")
+CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks", "summary", "select")
 
 
 class Context:

@@ -206,6 +206,12 @@ struct attpc_ctx {
   std::vector<void*> summary_allocs;
   // summaries of a batch (summary.hip): the records, and per chunk the segments grouped by event
   DevBuf sm_events, sm_tracks, sm_seg_count, sm_seg_rank, sm_seg_start, sm_seg_list, sm_host_segs, sm_host_ctrl;
+  bool select_on = false;          // attpc_select_configure
+  attpc_select_desc select{};
+  // selected delivery (select.hip): passed of a batch's events, the selected rows of a chunk's events, and passed of
+  // a call's events on the host (counted there, then copied to the caller's array if there is one)
+  DevBuf sel_passed, sel_rows;
+  std::vector<uint8_t> sel_host;
   int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
   uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
@@ -841,6 +847,7 @@ struct RunOut {
   int64_t rows = 0;                  // row cursor: rows of the chunks delivered so far
   bool over = false;                 // ... more than the caller's capacity
   attpc_summary_out* summary = nullptr;  // summary (a resident run: neither cloud nor trace)
+  attpc_select_out* select = nullptr;    // a selected run: cloud and summary are views of it (mode cloud or spyral)
   bool resident() const { return !cloud && !trace; }
   int64_t* offsets() const { return cloud ? cloud->offsets : trace ? trace->offsets : nullptr; }
   int64_t* event_points() const { return cloud ? cloud->event_points : trace ? trace->event_points : nullptr; }
@@ -848,6 +855,7 @@ struct RunOut {
   // the capacity binds clouds always, traces when any of their row arrays is wanted
   // (trace rows: when their rows or labels are)
   bool bounded() const {
+    if (select) return cloud->points && cloud->labels;  // (nothing of the rows is copied otherwise)
     if (mode == OutMode::trace_rows) return cloud->points || cloud->labels;
     return cloud || (trace && (trace->pads || trace->samples || trace->labels));
   }
@@ -1065,20 +1073,42 @@ int32_t assemble_spyral(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
 // the mode (assemble_cloud, assemble_spyral, or for traces the count pass and the scan of the kept pad rows -- the
 // write pass follows once the host knows their number, deliver); as.ready is recorded at the end.  `seed` /
 // `first_global`: the run's seed and the chunk's first global event id (the noise of the traces).
-int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMode mode, uint64_t seed, uint64_t first_global) {
+// `selected`: the chunk (events e0 .. of its batch) went through enqueue_select -- the offsets come from sel_rows and the
+// gather skips the segments of the events that did not pass (select.hip).
+int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMode mode, uint64_t seed, uint64_t first_global,
+                         bool selected = false, uint32_t e0 = 0) {
   int32_t rc;
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, as.copied, 0));  // the set's previous contents have left
   // rows of the scatter launch queued just before (same stream, same slot), kept with 12 % headroom
   if ((size_t)ctx->launch_row_cap > as.row_cap) as.row_cap = (size_t)ctx->launch_row_cap + (size_t)ctx->launch_row_cap / 8;
   if ((rc = ensure_asm_cloud(ctx, as, n, as.row_cap))) return rc;
   const unsigned long long* d_ctrl = static_cast<const unsigned long long*>(ctx->out_ctrl.p) + (size_t)slot * CTRL_WORDS;
-  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(ctx->ev_rows.p), n,
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream,
+                     static_cast<const uint32_t*>(selected ? ctx->sel_rows.p : ctx->ev_rows.p), n,
                      static_cast<int64_t*>(as.ev_start.p), static_cast<int64_t*>(nullptr), d_ctrl);
   HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(gather_segments_kernel, dim3(4096), dim3(256), 0, ctx->stream, static_cast<const Segment*>(ctx->segments.p),
-                     d_ctrl, ctx->seg_capacity, static_cast<const int64_t*>(as.ev_start.p),
-                     static_cast<const double*>(ctx->points.p), static_cast<const int64_t*>(ctx->labels.p),
-                     static_cast<double*>(as.points.p), static_cast<int64_t*>(as.labels.p));
+  if (selected) {
+    GatherSelectedArgs g{};
+    g.segments = static_cast<const Segment*>(ctx->segments.p);
+    g.ctrl = d_ctrl;
+    g.seg_capacity = ctx->seg_capacity;
+    g.row_capacity = ctx->cloud_capacity;
+    g.out_capacity = (int64_t)as.row_cap;
+    g.n_events = n;
+    g.event0 = e0;
+    g.passed = static_cast<const uint8_t*>(ctx->sel_passed.p);
+    g.ev_start = static_cast<const int64_t*>(as.ev_start.p);
+    g.points = static_cast<const double*>(ctx->points.p);
+    g.labels = static_cast<const int64_t*>(ctx->labels.p);
+    g.out_points = static_cast<double*>(as.points.p);
+    g.out_labels = static_cast<int64_t*>(as.labels.p);
+    launch_gather_selected(ctx->stream, g, 4096);
+  } else {
+    hipLaunchKernelGGL(gather_segments_kernel, dim3(4096), dim3(256), 0, ctx->stream, static_cast<const Segment*>(ctx->segments.p),
+                       d_ctrl, ctx->seg_capacity, static_cast<const int64_t*>(as.ev_start.p),
+                       static_cast<const double*>(ctx->points.p), static_cast<const int64_t*>(ctx->labels.p),
+                       static_cast<double*>(as.points.p), static_cast<int64_t*>(as.labels.p));
+  }
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(as.h_ev_rows.p, ctx->ev_rows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   if (makes_traces(mode)) rc = enqueue_trace_count(ctx, as, n, as.row_cap, seed, first_global);
@@ -1446,6 +1476,36 @@ int32_t copy_summary(attpc_ctx* ctx, const attpc_summary_out* out, uint64_t firs
   return ATTPC_OK;
 }
 
+// ------------------------------------------------------------------ selected delivery (select.hip) ----
+// The predicate on the records of `n` events of a batch (its events e0 ..), queued on S behind their summary kernels:
+// passed of the batch's events, and with `ev_rows` (the chunk's rows per event) the selected rows in ctx->sel_rows.
+int32_t enqueue_select(attpc_ctx* ctx, const unsigned long long* d_ctrl, int n_sim, uint32_t e0, uint32_t n, const uint32_t* ev_rows) {
+  if (n == 0) return ATTPC_OK;
+  int32_t rc;
+  if ((rc = ensure_idle(ctx, ctx->sel_rows, std::max<size_t>(n, (size_t)std::max(1, ctx->chunk_events)) * sizeof(uint32_t)))) return rc;
+  SelectArgs a{};
+  a.desc = ctx->select;
+  a.ctrl = d_ctrl;
+  a.events = static_cast<const attpc_event_summary*>(ctx->sm_events.p);
+  a.tracks = n_sim ? static_cast<const attpc_track_summary*>(ctx->sm_tracks.p) : nullptr;
+  a.n_sim = n_sim;
+  a.n_events = n;
+  a.event0 = e0;
+  a.ev_rows = ev_rows;
+  a.passed = static_cast<uint8_t*>(ctx->sel_passed.p);
+  a.sel_rows = ev_rows ? static_cast<uint32_t*>(ctx->sel_rows.p) : nullptr;
+  launch_select(ctx->stream, a);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// mask bits of the configured selection at or above a call's n_sim
+int32_t validate_select_mask(attpc_ctx* ctx, const char* name, int n_sim) {
+  if (ctx->select.track_mask >> n_sim)
+    return fail(ctx, ATTPC_E_INVALID, "%s: track_mask 0x%x names positions at or above n_sim = %d", name, ctx->select.track_mask, n_sim);
+  return ATTPC_OK;
+}
+
 // ------------------------------------------------------------------ the run loop ----
 struct RunSource {   // where a batch's kinematics come from
   bool from_kernel = false;        // attpc_sim_run: kin_run_kernel on T
@@ -1503,6 +1563,10 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT && nb)  // their noise-only rows
       return trace_host_events(ctx, o, batch_first_local, nb, nullptr, nullptr, nullptr, seed, batch_first_global);
     if (o.summary && o.summary->events) std::fill(o.summary->events + batch_first_local, o.summary->events + batch_first_local + nb, empty_event_summary());
+    if (o.select && nb) {  // the predicate on the empty records (n_sim == 0: no position to cut on)
+      const uint8_t pass = select_passes(ctx->select, empty_event_summary(), nullptr, 0) ? 1 : 0;
+      std::fill(ctx->sel_host.begin() + batch_first_local, ctx->sel_host.begin() + batch_first_local + nb, pass);
+    }
     if (int64_t* offsets = o.offsets()) std::fill(offsets + batch_first_local, offsets + batch_first_local + nb + 1, o.rows);
     if (int64_t* event_points = o.event_points()) std::fill(event_points + batch_first_local, event_points + batch_first_local + nb, 0);
     return ATTPC_OK;
@@ -1527,6 +1591,18 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
                            static_cast<const Segment*>(ctx->segments.p), ctx->seg_capacity, ctx->cloud_capacity, lay, &trk, c.e0, c.n);
   };
   if (o.summary && (rc = ensure_summary_records(ctx, nb, lay.n_sim))) return rc;
+  if (o.select && (rc = ensure_idle(ctx, ctx->sel_passed, std::max<size_t>(nb, 1)))) return rc;
+  // The assembly of chunk c into `as`; a selected chunk first gets its records and the predicate on them, where its rows
+  // lie, and only the rows of the events that pass are put in event order.
+  auto assemble = [&](const Chunk& c, AsmSet& as) -> int32_t {
+    int32_t rc2;
+    if (o.select) {
+      if ((rc2 = summarise(c))) return rc2;
+      if ((rc2 = enqueue_select(ctx, static_cast<const unsigned long long*>(ctx->out_ctrl.p) + (size_t)c.slot * CTRL_WORDS, lay.n_sim,
+                                c.e0, c.n, static_cast<const uint32_t*>(ctx->ev_rows.p)))) return rc2;
+    }
+    return enqueue_assembly(ctx, c.slot, as, c.n, o.mode, seed, batch_first_global + c.e0, o.select != nullptr, c.e0);
+  };
   // The scatter of chunk c (and its assembly into `as`, when delivered) has completed: read its control words, and
   // while the launch ran out of room, queue it again with larger buffers (and the assembly behind it) and read again.
   auto settle = [&](const Chunk& c, AsmSet* as) -> int32_t {
@@ -1537,7 +1613,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
       int32_t rc2;
       if ((rc2 = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + c.e0, c.e0, c.n, min_rows, min_segs))) return rc2;
       if (as) {
-        if ((rc2 = enqueue_assembly(ctx, c.slot, *as, c.n, o.mode, seed, batch_first_global + c.e0))) return rc2;
+        if ((rc2 = assemble(c, *as))) return rc2;  // (a repeated chunk overwrites its records, passed and selected rows)
         HIP_TRY(ctx, hipEventSynchronize(as->ready));
       } else {
         if ((rc2 = summarise(c))) return rc2;  // (a repeated chunk overwrites its records)
@@ -1601,7 +1677,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     const int set = seq & 1;
     // an overflow of the chunk in flight is repaired inside complete(); queue this one behind it
     if ((rc = enqueue_scatter(ctx, c.slot, lay, trk, seed, batch_first_global + e0, e0, n, 0, 0))) return rc;
-    if ((rc = enqueue_assembly(ctx, c.slot, ctx->aset[set], n, o.mode, seed, batch_first_global + e0))) return rc;
+    if ((rc = assemble(c, ctx->aset[set]))) return rc;
     if ((rc = queue_next_once())) return rc;
     if (prev.slot >= 0 && (rc = complete(prev, prev_set))) return rc;
     prev = c;
@@ -1615,6 +1691,10 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   }
   if (prev.slot >= 0 && (rc = complete(prev, prev_set))) return rc;
   if ((rc = wait_unpacked(ctx, ctx->unpack_submitted))) return rc;  // every row is in the caller's arrays
+  if (o.select) {  // every chunk of the batch has settled: its records and passed are final
+    if ((rc = copy_summary(ctx, o.summary, batch_first_local, nb, lay.n_sim))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sel_host.data() + batch_first_local, ctx->sel_passed.p, nb, hipMemcpyDeviceToHost, ctx->stream));
+  }
   return queue_next_once();
 }
 
@@ -1677,6 +1757,7 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   const uint64_t growths_before = ctx->n_growths;
   const int n_rows = lay.n_rows;
   if (int64_t* offsets = o.offsets()) offsets[0] = 0;
+  if (o.select) ctx->sel_host.assign((size_t)n_events, 0);
   // batches of up to MAX_SLOTS chunks (a small pilot batch while the arena need per track is unknown),
   // each integrated on T while the previous batch is scattered on S
   uint64_t b0 = 0;
@@ -1769,7 +1850,13 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
     cur ^= 1;
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
-  if (o.mode == OutMode::spyral) st.n_points = (uint64_t)o.rows;  // rows that survive the threshold
+  if (o.select) {  // (st keeps its cloud meaning over all events)
+    int64_t n_passed = 0;
+    for (uint8_t p : ctx->sel_host) n_passed += p;
+    if (o.select->passed && n_events) std::memcpy(o.select->passed, ctx->sel_host.data(), (size_t)n_events);
+    o.select->n_passed = n_passed;
+    o.select->n_rows = o.rows;
+  } else if (o.mode == OutMode::spyral) st.n_points = (uint64_t)o.rows;  // rows that survive the threshold
   if (o.mode == OutMode::traces && (rc = read_trace_sums(ctx, o))) return rc;  // (the cloud's meaning stays in st)
   if (o.mode == OutMode::trace_rows) {
     st.n_points = (uint64_t)o.rows;  // the rows of the call, as in the Spyral mode
@@ -1811,12 +1898,18 @@ int32_t run_entry(const char* name, attpc_ctx* ctx, uint64_t seed, uint64_t firs
     if (!o.summary) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_summary_out", name);
     if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
   }
+  if (o.select) {
+    if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
+    if (!ctx->select_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_select_configure has not been called");
+    if (n_events > (uint64_t)INT64_MAX) return fail(ctx, ATTPC_E_INVALID, "%s: too many events", name);
+  }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc = validate_layout(ctx, layout, true);
   if (rc) return rc;
+  if (o.select && (rc = validate_select_mask(ctx, name, layout->n_sim))) return rc;
   if (src.from_kernel && layout->n_rows != kin_rows(ctx))
     return fail(ctx, ATTPC_E_INVALID, "layout.n_rows=%d but the pipeline has %d rows", layout->n_rows, kin_rows(ctx));
-  if ((makes_traces(o.mode) || o.mode == OutMode::summary) && (rc = drop_prefetch(ctx))) return rc;  // a trace or summary call is never the announced one
+  if ((makes_traces(o.mode) || o.mode == OutMode::summary || o.select) && (rc = drop_prefetch(ctx))) return rc;  // a trace, summary or selected call is never the announced one
   return run_events(ctx, seed, first_event, n_events, *layout, src, sink, o, stats);
 }
 
@@ -2449,14 +2542,18 @@ int32_t attpc_det_run_summary(attpc_ctx* ctx, uint64_t seed, uint64_t first_even
   return run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{}, o, stats);
 }
 
-int32_t attpc_cloud_summary(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
-                            const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out) {
-  if (!ctx || !out) return ATTPC_E_INVALID;
+namespace {
+// attpc_cloud_summary, and with `passed` attpc_cloud_select: the records of a host cloud (to `out`, if given), then the
+// configured selection on them.
+int32_t host_cloud_records(const char* name, attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                           const int64_t* labels, const attpc_event_layout* layout, const attpc_summary_out* out, uint8_t* passed) {
   if (n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
-  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_cloud_summary takes at most 2^31 - 1 events per call");
+  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes at most 2^31 - 1 events per call", name);
   if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
+  if (passed && !ctx->select_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_select_configure has not been called");
   int32_t rc;
   if ((rc = validate_layout(ctx, layout, false))) return rc;
+  if (passed && (rc = validate_select_mask(ctx, name, layout->n_sim))) return rc;
   const uint32_t n = (uint32_t)n_events;
   const int64_t first = n ? offsets[0] : 0;
   if (first < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
@@ -2498,9 +2595,84 @@ int32_t attpc_cloud_summary(attpc_ctx* ctx, int64_t n_events, const int64_t* off
   if ((rc = enqueue_summary(ctx, static_cast<const unsigned long long*>(ctx->sm_host_ctrl.p), static_cast<const double*>(as.points.p),
                             static_cast<const int64_t*>(as.labels.p), static_cast<const Segment*>(ctx->sm_host_segs.p), (int64_t)n,
                             rows, *layout, nullptr, 0, n))) return rc;
-  if ((rc = copy_summary(ctx, out, 0, n, layout->n_sim))) return rc;
+  if (out && (rc = copy_summary(ctx, out, 0, n, layout->n_sim))) return rc;
+  if (passed) {
+    if ((rc = ensure_idle(ctx, ctx->sel_passed, n))) return rc;
+    if ((rc = enqueue_select(ctx, static_cast<const unsigned long long*>(ctx->sm_host_ctrl.p), layout->n_sim, 0, n, nullptr))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(passed, ctx->sel_passed.p, n, hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return ATTPC_OK;
+}
+}  // namespace
+
+int32_t attpc_cloud_summary(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                            const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out) {
+  if (!ctx || !out) return ATTPC_E_INVALID;
+  return host_cloud_records(__func__, ctx, n_events, offsets, points, labels, layout, out, nullptr);
+}
+
+// ---- selected delivery (select.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_select_configure(attpc_ctx* ctx, const attpc_select_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d) {
+    const struct { const char* name; double lo, hi; } f64[] = {{"track_rho2_max", d->track_rho2_max_lo, d->track_rho2_max_hi},
+                                                               {"track_end_tb", d->track_end_tb_lo, d->track_end_tb_hi},
+                                                               {"track_end_rho2", d->track_end_rho2_lo, d->track_end_rho2_hi}};
+    for (const auto& r : f64)
+      if (std::isnan(r.lo) || std::isnan(r.hi) || r.lo > r.hi) return fail(ctx, ATTPC_E_INVALID, "selection: %s range [%g, %g]", r.name, r.lo, r.hi);
+    const struct { const char* name; uint32_t lo, hi; } u32[] = {
+        {"n_kept", d->n_kept_lo, d->n_kept_hi}, {"n_pads", d->n_pads_lo, d->n_pads_hi}, {"tb_span", d->tb_span_lo, d->tb_span_hi},
+        {"track_n_kept", d->track_n_kept_lo, d->track_n_kept_hi}, {"track_n_pads", d->track_n_pads_lo, d->track_n_pads_hi},
+        {"track_n_samples", d->track_n_samples_lo, d->track_n_samples_hi}};
+    for (const auto& r : u32)
+      if (r.lo > r.hi) return fail(ctx, ATTPC_E_INVALID, "selection: %s range [%u, %u]", r.name, r.lo, r.hi);
+    if (d->charge_lo > d->charge_hi) return fail(ctx, ATTPC_E_INVALID, "selection: charge range [%lld, %lld]", (long long)d->charge_lo, (long long)d->charge_hi);
+    if (d->track_mask >> ATTPC_MAX_SIM) return fail(ctx, ATTPC_E_INVALID, "selection: track_mask 0x%x has bits at or above %d", d->track_mask, ATTPC_MAX_SIM);
+    if (d->min_tracks > (uint32_t)__builtin_popcount(d->track_mask))
+      return fail(ctx, ATTPC_E_INVALID, "selection: min_tracks %u above the %d masked positions", d->min_tracks, __builtin_popcount(d->track_mask));
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  ctx->select_on = d != nullptr;
+  if (d) ctx->select = *d;
+  return ATTPC_OK;
+}
+
+namespace {
+// The two selected entry points: `out` seen as the cloud output of its kind and as a summary output.
+int32_t run_selected(const char* name, attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                     const attpc_event_layout* layout, const RunSource& src, const RunSink& sink, attpc_select_out* out,
+                     attpc_run_stats* stats) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (!out) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_select_out", name);
+  if (out->kind != ATTPC_SELECT_CLOUD && out->kind != ATTPC_SELECT_SPYRAL) return fail(ctx, ATTPC_E_INVALID, "%s: kind %d", name, out->kind);
+  out->n_passed = out->n_rows = 0;
+  attpc_cloud_out cloud{out->capacity, out->offsets, out->points, out->labels, out->event_points};
+  attpc_summary_out records{out->events, out->tracks};
+  RunOut o{out->kind == ATTPC_SELECT_SPYRAL ? OutMode::spyral : OutMode::cloud, &cloud};
+  o.summary = &records;
+  o.select = out;
+  return run_entry(name, ctx, seed, first_event, n_events, layout, src, sink, o, stats);
+}
+}  // namespace
+
+int32_t attpc_sim_run_selected(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                               const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
+                               attpc_select_out* out, attpc_run_stats* stats) {
+  return run_selected(__func__, ctx, seed, first_event, n_events, layout, RunSource{true}, RunSink{p4, vertex, kin_status}, out, stats);
+}
+
+int32_t attpc_det_run_selected(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                               const attpc_event_layout* layout, const double* p4, const double* vertex,
+                               attpc_select_out* out, attpc_run_stats* stats) {
+  return run_selected(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{}, out, stats);
+}
+
+int32_t attpc_cloud_select(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                           const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out, uint8_t* passed) {
+  if (!ctx || !passed) return ATTPC_E_INVALID;
+  return host_cloud_records(__func__, ctx, n_events, offsets, points, labels, layout, out, passed);
 }
 
 // ---- trace rows (peaks.hip; the contract is in include/attpc_engine.h) ----

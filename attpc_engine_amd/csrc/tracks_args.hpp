@@ -194,4 +194,73 @@ void launch_summary_fill(hipStream_t s, const SummaryArgs& a, uint32_t n_workgro
 // the records of events event0 .. event0 + n_events - 1, plain stores: a repeated chunk overwrites them
 void launch_summary_events(hipStream_t s, const SummaryArgs& a, uint32_t n_workgroups);
 
+// selected delivery (select.hip; attpc_select_configure, the contract is in include/attpc_engine.h): the predicate on a
+// chunk's records, and the gather that leaves out the segments of the events that failed it.
+// The contract's predicate itself, for the device (select_kernel) and for the host (a batch with nothing to scatter).
+// A range whose bounds are both open is not evaluated; an evaluated one is lo <= v && v <= hi (false for NaN).
+__host__ __device__ inline bool select_in_u32(uint32_t lo, uint32_t hi, int64_t v) {
+  return (lo == 0u && hi == 0xffffffffu) || ((int64_t)lo <= v && v <= (int64_t)hi);
+}
+__host__ __device__ inline bool select_in_f64(double lo, double hi, double v) {
+  return (lo == -__builtin_inf() && hi == __builtin_inf()) || (lo <= v && v <= hi);
+}
+__host__ __device__ inline bool select_passes(const attpc_select_desc& d, const attpc_event_summary& ev,
+                                              const attpc_track_summary* tracks, int n_sim) {
+#pragma clang fp contract(off)
+  const int64_t span = ev.n_kept ? (int64_t)ev.tb_max - (int64_t)ev.tb_min + 1 : 0;
+  bool ok = select_in_u32(d.n_kept_lo, d.n_kept_hi, (int64_t)ev.n_kept) &&
+            select_in_u32(d.n_pads_lo, d.n_pads_hi, (int64_t)ev.n_pads) &&
+            select_in_u32(d.tb_span_lo, d.tb_span_hi, span);
+  const bool charge_open = d.charge_lo == INT64_MIN && d.charge_hi == INT64_MAX;
+  ok = ok && (charge_open || (d.charge_lo <= ev.charge && ev.charge <= d.charge_hi));
+  uint32_t good = 0u;
+  for (int s = 0; s < n_sim && tracks != nullptr; ++s) {
+    if (!((d.track_mask >> s) & 1u)) continue;
+    const attpc_track_summary& t = tracks[s];
+    const double xx = t.end_x * t.end_x, yy = t.end_y * t.end_y;  // each product rounded, then added
+    const double end_rho2 = xx + yy;
+    const bool pass = select_in_u32(d.track_n_kept_lo, d.track_n_kept_hi, (int64_t)t.n_kept) &&
+                      select_in_u32(d.track_n_pads_lo, d.track_n_pads_hi, (int64_t)t.n_pads) &&
+                      select_in_u32(d.track_n_samples_lo, d.track_n_samples_hi, (int64_t)t.n_samples) &&
+                      select_in_f64(d.track_rho2_max_lo, d.track_rho2_max_hi, t.rho2_max) &&
+                      select_in_f64(d.track_end_tb_lo, d.track_end_tb_hi, t.end_tb) &&
+                      select_in_f64(d.track_end_rho2_lo, d.track_end_rho2_hi, end_rho2);
+    good += pass ? 1u : 0u;
+  }
+  return ok && good >= d.min_tracks;
+}
+
+struct SelectArgs {
+  attpc_select_desc desc;
+  const unsigned long long* ctrl;     // the scatter launch's control words: [6] out of capacity
+  const attpc_event_summary* events;  // [batch events]
+  const attpc_track_summary* tracks;  // [batch events][n_sim] or nullptr (n_sim == 0)
+  int32_t n_sim;
+  uint32_t n_events;                  // events of the chunk
+  uint32_t event0;                    // first event of the chunk within the batch (records, passed)
+  const uint32_t* ev_rows;            // [n_events] cloud rows of the chunk's events, or nullptr
+  uint8_t* passed;                    // [batch events]
+  uint32_t* sel_rows;                 // [n_events] passed ? ev_rows : 0, or nullptr
+};
+// passed and sel_rows of events event0 .. event0 + n_events - 1, one lane per event
+void launch_select(hipStream_t s, const SelectArgs& a);
+
+struct GatherSelectedArgs {
+  const Segment* segments;
+  const unsigned long long* ctrl;  // [1] segments, [6] out of capacity
+  int64_t seg_capacity;
+  int64_t row_capacity;            // rows of points / labels
+  int64_t out_capacity;            // rows of out_points / out_labels
+  uint32_t n_events;
+  uint32_t event0;
+  const uint8_t* passed;           // [batch events]
+  const int64_t* ev_start;         // [n_events + 1] exclusive scan of sel_rows
+  const double* points;
+  const int64_t* labels;
+  double* out_points;
+  int64_t* out_labels;
+};
+// gather_segments_kernel of abi.hip for a selected chunk: the segments of events that did not pass are skipped
+void launch_gather_selected(hipStream_t s, const GatherSelectedArgs& a, uint32_t n_workgroups);
+
 }  // namespace attpc

@@ -1,6 +1,7 @@
 """Detector effects: same public names as the reference package (reference
 ``detector/__init__.py:13-21``) plus the batch entry points, device backed."""
 from . import parameters as _parameters
+from . import selection as _selection
 from . import simulator as _simulator
 from . import summary as _summary
 from . import traces as _traces
@@ -13,6 +14,7 @@ _EXPORTS = {
               "simulate_batch_trace_rows", "clouds_to_trace_rows"),
     _summary: ("SummarySettings", "configure_summary", "simulate_batch_summary", "clouds_to_summary",
                "electrons_above_threshold"),
+    _selection: ("Selection", "configure_selection", "simulate_batch_selected", "clouds_to_selection"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter"),
 }
 __all__ = []

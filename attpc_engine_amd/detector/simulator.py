@@ -181,7 +181,7 @@ def deliver_events(writer, n_events: int, batch_size: int, batch, emit) -> None:
 
 def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
                    indices: list[int] | None = None, batch_size: int = 16384,
-                   seed: int | None = None):
+                   seed: int | None = None, selection=None):
     """Apply the detector simulation to every event of a kinematics file (reference
     simulator.py:118-210): the writer is called once per event with a non-empty cloud, in event order, then
     closed.  A writer that offers ``write_rows`` (SpyralWriter) receives its rows ready to store: the response
@@ -191,7 +191,10 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     (TraceWriter) receives every non-empty event's pad traces, made on the device (``attpc_det_run_traces``, with the
     writer's noise settings, the noise keyed on the run's seed and the global event ids).  Any other
     SimulationWriter gets
-    ``write(points, labels, config, event)`` exactly as in the reference."""
+    ``write(points, labels, config, event)`` exactly as in the reference.  ``selection`` (a
+    ``detector.selection.Selection``): only the events that pass it reach the writer (``attpc_det_run_selected``: the
+    others are not assembled, converted or copied), with their original event numbers; a trace writer raises
+    ValueError."""
     from ..io import KinematicsFileReader
 
     print("------- AT-TPC Simulation Engine (MI355X) -------")
@@ -205,10 +208,20 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     rng = default_rng(seed)
     run_seed = int(rng.integers(0, 1 << 63))
     kind, emit = delivery_of(writer, config)
+    if selection is not None and kind not in ("rows", "cloud"):
+        raise ValueError("a selection delivers Spyral rows or clouds: trace writers are not supported")
 
     def batch(start, stop):
         vertices, momenta = reader.read(start, stop)
         args = (momenta, vertices, proton_numbers, mass_numbers, config, run_seed, nuclei_to_sim)
+        if selection is not None:
+            from .selection import simulate_batch_selected
+
+            res = simulate_batch_selected(*args, selection, kind="spyral" if kind == "rows" else "cloud", first_event=start,
+                                          response=getattr(writer, "response", None))
+            # event_points masked by passed: the loop of deliver_events skips the rejected events as the empty ones
+            return (res["offsets"], np.where(res["passed"], res["event_points"], 0),
+                    res["rows" if kind == "rows" else "points"], res["labels"])
         if kind == "traces":  # the pad traces are made on the device behind the scatter (attpc_det_run_traces)
             from .traces import simulate_batch_traces
 

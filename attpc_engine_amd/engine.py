@@ -14,7 +14,7 @@ import numpy as np
 from . import _abi, nuclear_map
 from .detector.luts import build_det_desc, build_layout, species_for
 from .detector.simulator import default_indices, deliver_events, delivery_of
-from .outputs import RowArrays, SummaryArrays, call_with_capacity
+from .outputs import RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
 class Engine:
@@ -30,6 +30,7 @@ class Engine:
         self.indices = list(indices) if indices is not None else default_indices(self.n_rows)
         self._out_cache = None  # (key, arrays) of the last run with reuse_buffers (call_with_capacity)
         self._spyral_configured = self._traces_configured = self._peaks_configured = self._summary_configured = False
+        self._selection = None  # the Selection configure_selection uploaded
         ctx = self.ctx
         kin, keep_k = pipeline.device_desc()
         ctx.check(ctx.lib.attpc_kin_configure(ctx.handle, kin), "attpc_kin_configure")
@@ -231,8 +232,59 @@ class Engine:
                 "p4": p4, "status": status, "stats": stats.as_dict()}
 
 
+    # ---------------------------------------------------------------- selected delivery
+    def configure_selection(self, selection=None, **cuts) -> None:
+        """Upload the selection of ``run_selected``: a ``detector.selection.Selection`` or its keyword cuts (n_kept,
+        n_pads, tb_span, charge; tracks / track_mask, min_tracks, track_n_kept, track_n_pads, track_n_samples,
+        track_rho2_max, track_end_tb, track_end_rho2; include/attpc_engine.h)."""
+        from .detector.selection import configure_selection
+
+        selection = configure_selection(self.ctx, selection, **cuts)
+        selection.check_positions(len(self.indices))
+        self._selection = selection
+
+    def run_selected(self, n_events: int, seed: int = 0, first_event: int = 0, rows: str = "cloud", fetch: bool = True,
+                     pinned: bool = False, capacity_per_event: int | None = None, reuse_buffers: bool = False) -> dict:
+        """The delivered run ``run(fetch=True)`` (``rows="cloud"``) or ``run_spyral`` (``rows="spyral"``) of the events
+        that pass the configured selection (``attpc_sim_run_selected``): every chunk is reduced to its summary records
+        on the device, the predicate is evaluated there, and only the rows of the events that pass are put in event
+        order, converted and copied.  Returns ``passed`` [n] bool, ``n_passed``, ``n_rows``, ``events`` [n] and
+        ``tracks`` [n, n_sim] (the records of ALL events, as ``run_summary``), ``indices``, ``offsets`` [n+1] (a rejected
+        event is an empty range), ``points`` [P,3] or ``rows`` [P',8], ``labels``, ``event_points`` [n] (cloud rows of
+        every event before selection and threshold), the kinematics and the cloud's ``stats`` over all events.
+        ``fetch=False``: no row arrays -- points / rows and labels are None, everything else is what the fetched call
+        returns (what the selection would deliver).  ``pinned`` / ``reuse_buffers`` as in ``run``.  Configures the summary (and for Spyral rows the Spyral stage) with
+        the defaults if they were not configured; raises if no selection was configured."""
+        from .detector.selection import ROW_KINDS, selected_result
+
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
+        if rows not in ROW_KINDS:
+            raise ValueError(f"rows must be one of {sorted(ROW_KINDS)}, got {rows!r}")
+        if self._selection is None:
+            raise RuntimeError("run_selected needs a selection: call configure_selection first")
+        if not self._summary_configured:
+            self.configure_summary()
+        if rows == "spyral" and not self._spyral_configured:
+            self.configure_spyral()
+        # (the token of the context may have been replaced through another engine of the same context)
+        self.configure_selection(self._selection)
+        if capacity_per_event is None:
+            capacity_per_event = 12288 if rows == "cloud" else 6144
+        capacity = max(4096, int(capacity_per_event) * n_events) if fetch else 1
+        arrays, res = self._deliver("attpc_sim_run_selected", n_events, seed, first_event, capacity, pinned and fetch,
+                                    holder=SelectedArrays, width=ROW_KINDS[rows], n_sim=len(self.indices), rows=fetch,
+                                    slack=4096, cache=self, reuse=reuse_buffers)
+        return {**res, **selected_result(arrays, rows, res["stats"]), "indices": list(self.indices)}
+
+
+def _selected_batch(res: dict, key: str):
+    """A selected call's result as ``deliver_events`` takes a batch: event_points masked by passed, so that its loop
+    skips the rejected events as it skips the empty ones."""
+    return res["offsets"], np.where(res["passed"], res["event_points"], 0), res[key], res["labels"]
+
+
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
-              batch_size: int = 65536, context: _abi.Context | None = None) -> None:
+              batch_size: int = 65536, context: _abi.Context | None = None, selection=None) -> None:
     """run_kinematics_pipeline + run_simulation + SpyralWriter without the kinematics file and with
     the response / threshold / row conversion / z-sort done on the GPU: per event with a non-empty
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
@@ -241,10 +293,26 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     ``writer.write_rows(rows, labels, event_number, presorted=True)``, then ``close()``.  A SpyralWriter with ``peaks``
     gets the peaks of the event's pad traces as its rows (``Engine.run_trace_rows``).  A writer that offers
     ``write_traces`` (TraceWriter) gets ``write_traces(pads, samples, labels, event_number)`` per such event instead,
-    the traces made on the device (``Engine.run_traces``) with the writer's noise settings."""
+    the traces made on the device (``Engine.run_traces``) with the writer's noise settings.  ``selection`` (a
+    ``detector.selection.Selection``): only the events that pass it reach the writer (``Engine.run_selected``; rows or
+    plain clouds, a trace writer raises ValueError); event numbers stay the global ones, the file roll-over counts
+    written events."""
     engine = Engine(pipeline, config, indices, context=context)
     seed = pipeline.seed if seed is None else int(seed)
     kind, emit = delivery_of(writer, config)
+    if selection is not None:
+        if kind not in ("rows", "cloud"):
+            raise ValueError("a selection delivers Spyral rows or clouds: trace writers are not supported")
+        engine.configure_selection(selection)
+        if kind == "rows":
+            engine.configure_spyral(config)
+
+        def selected(start, stop):
+            res = engine.run_selected(stop - start, seed=seed, first_event=start, rows="spyral" if kind == "rows" else "cloud")
+            return _selected_batch(res, "rows" if kind == "rows" else "points")
+
+        deliver_events(writer, n_events, batch_size, selected, emit)
+        return
     if kind == "traces":
         engine.configure_traces(config, writer.response, writer.threshold, writer.offset, **writer.noise_kwargs(),
                                 **writer.readout_kwargs())

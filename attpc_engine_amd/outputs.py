@@ -3,7 +3,8 @@
 A run that delivers clouds, Spyral rows or pad traces writes into arrays the caller owns (``attpc_cloud_out`` /
 ``attpc_trace_out``, include/attpc_engine.h) and answers ATTPC_E_CAPACITY, with the rows it needs, when they are too
 small.  ``RowArrays`` and ``TraceArrays`` hold such arrays together with the struct that points at them (``SummaryArrays``: the
-fixed-size records of a summary run, ``attpc_summary_out``, which have no capacity);
+fixed-size records of a summary run, ``attpc_summary_out``, which have no capacity; ``SelectedArrays``: the rows of the
+events that pass a selection, ``passed`` and the records of all events, ``attpc_select_out``);
 ``call_with_capacity`` is the only place that allocates them, calls and allocates again.
 """
 from __future__ import annotations
@@ -84,6 +85,40 @@ class SummaryArrays:
 
     def result(self):
         return self.events, self.tracks
+
+
+class SelectedArrays:
+    """Caller arrays of one selected call -- the row arrays of its kind (``width`` 3: cloud rows, 8: Spyral rows),
+    ``passed`` [n] u8 and the records of all events (``events`` [n], ``tracks`` [n, n_sim], as in SummaryArrays) -- and
+    the ``attpc_select_out`` that points at them.  ``rows=False``: no row arrays (the library gets NULL there, copies
+    nothing of the rows and still reports what the selection would deliver)."""
+
+    def __init__(self, n_events: int, capacity: int, make=None, width: int = 3, n_sim: int = 0, rows: bool = True):
+        make = make or _host_empty
+        self.offsets = np.zeros(n_events + 1, dtype=np.int64)
+        self.rows = make((capacity, width), np.float64) if rows else None
+        self.labels = make((capacity,), np.int64) if rows else None
+        self.event_points = np.zeros(n_events, dtype=np.int64)
+        self.passed = np.zeros(n_events, dtype=np.uint8)
+        self.events = np.empty((n_events,), _abi.EVENT_SUMMARY_DTYPE)
+        self.tracks = np.empty((n_events, n_sim), _abi.TRACK_SUMMARY_DTYPE)
+        i64 = _abi.C.c_int64
+        self.out = _abi.SelectOut(_abi.SELECT_SPYRAL if width == 8 else _abi.SELECT_CLOUD, 0, capacity,
+                                  _abi.iptr(self.offsets, i64), _abi.dptr(self.rows), _abi.iptr(self.labels, i64),
+                                  _abi.iptr(self.event_points, i64), _abi.iptr(self.passed, _abi.C.c_uint8),
+                                  self.events.ctypes.data_as(_abi.C.POINTER(_abi.EventSummary)),
+                                  self.tracks.ctypes.data_as(_abi.C.POINTER(_abi.TrackSummary)), 0, 0)
+
+    def needed(self, stats) -> int:
+        """Rows the last call wanted to deliver: the selected rows, which the call reports in its own out struct
+        (the run statistics keep the cloud's rows of all events)."""
+        return int(self.out.n_rows)
+
+    def result(self):
+        total = int(self.offsets[-1])
+        if self.rows is None:
+            return self.offsets, None, None
+        return self.offsets, self.rows[:total], self.labels[:total]
 
 
 def call_with_capacity(ctx: _abi.Context, n_events: int, capacity: int, call, what: str, stats=None,

@@ -713,6 +713,90 @@ ATTPC_API int32_t attpc_det_run_summary(attpc_ctx* ctx, uint64_t seed, uint64_t 
 ATTPC_API int32_t attpc_cloud_summary(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
                                       const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out);
 
+/* ---- selected delivery: only the events that pass a selection on their summary records are delivered (opt-in and
+ * additive under ABI version 3: without a call of the entry points below every output of every other entry point is
+ * what it is without this section) ----
+ * A selected run is the delivered run attpc_sim_run / attpc_det_run (kind ATTPC_SELECT_CLOUD) or attpc_sim_run_spyral /
+ * attpc_det_run_spyral (kind ATTPC_SELECT_SPYRAL) that, behind every chunk's scatter and before its assembly, reduces
+ * the chunk to the records of the section above and evaluates a predicate on them: the rows of an event that fails it
+ * are not put in event order, not converted and not copied.
+ * The predicate, passed = f(event record E, track records T[0 .. n_sim), desc), on exactly the records
+ * attpc_sim_run_summary produces for the same seed, global event id, min_electrons and pad centres:
+ *   - event cuts, each an inclusive range [lo, hi]: E.n_kept; E.n_pads; the time-bucket span E.tb_max - E.tb_min + 1
+ *     (0 when E.n_kept == 0); E.charge.
+ *   - track cuts, on every position s of layout->indices whose bit s is set in track_mask: T[s].n_kept; T[s].n_pads;
+ *     T[s].n_samples; T[s].rho2_max (mm^2; the record's -1.0 for "no kept row" compares as -1.0); T[s].end_tb; and
+ *     end_rho2 = fl(fl(end_x * end_x) + fl(end_y * end_y)) in m^2: both products rounded, then added (no fused
+ *     multiply-add), as for rho2_max.  A masked position passes iff all of its evaluated cuts hold.
+ *   - the event passes iff its event cuts hold and at least min_tracks masked positions pass: popcount(track_mask) asks
+ *     for all of them, 1 for any, 0 for no track cut at all.
+ *   - a range whose two bounds are both at their open values (0 / UINT32_MAX, INT64_MIN / INT64_MAX, -inf / +inf) is
+ *     NOT evaluated: an absent cut lets a NaN end point through.  An evaluated range is lo <= v && v <= hi, false for
+ *     NaN.
+ * f is a pure function of the records and desc, so passed does not depend on chunking, on how a call's id range is
+ * split, on the scatter build or on the number of GPUs, as the records do not. */
+typedef struct attpc_select_desc {
+  uint32_t n_kept_lo, n_kept_hi;             /* event cuts */
+  uint32_t n_pads_lo, n_pads_hi;
+  uint32_t tb_span_lo, tb_span_hi;
+  int64_t charge_lo, charge_hi;
+  uint32_t track_mask;                       /* bit s: position s of layout->indices is cut on; bits >= ATTPC_MAX_SIM
+                                                are ATTPC_E_INVALID */
+  uint32_t min_tracks;                       /* <= popcount(track_mask) */
+  uint32_t track_n_kept_lo, track_n_kept_hi; /* track cuts */
+  uint32_t track_n_pads_lo, track_n_pads_hi;
+  uint32_t track_n_samples_lo, track_n_samples_hi;
+  double track_rho2_max_lo, track_rho2_max_hi; /* mm^2 */
+  double track_end_tb_lo, track_end_tb_hi;     /* time bucket */
+  double track_end_rho2_lo, track_end_rho2_hi; /* m^2 */
+} attpc_select_desc;  /* 120 bytes */
+
+#define ATTPC_SELECT_CLOUD 0   /* rows as attpc_sim_run delivers them: points [capacity, 3] */
+#define ATTPC_SELECT_SPYRAL 1  /* rows as attpc_sim_run_spyral delivers them: points [capacity, 8] */
+
+/* Host output of a selected run.  offsets has n_events + 1 entries whatever passed: a rejected event is an empty
+ * range, so position e is global id first_event + e as in every other run.  event_points[e] keeps its meaning (the
+ * cloud rows of event e before selection and threshold).  events / tracks: the records of ALL events (either may be
+ * NULL).  capacity binds the SELECTED rows, and only when points and labels are both given: with either NULL nothing of
+ * the rows is copied and everything else (offsets, passed, records, n_passed, n_rows) is still produced -- what a
+ * selection would deliver.  ATTPC_E_CAPACITY: n_rows says what is needed (stats.n_points is the cloud's). */
+typedef struct attpc_select_out {
+  int32_t kind;          /* in: ATTPC_SELECT_CLOUD / ATTPC_SELECT_SPYRAL */
+  int32_t reserved;      /* 0 */
+  int64_t capacity;      /* in: rows available in points / labels */
+  int64_t* offsets;      /* [n_events + 1] or NULL */
+  double* points;        /* [capacity, 3 or 8] or NULL */
+  int64_t* labels;       /* [capacity] or NULL */
+  int64_t* event_points; /* [n_events] or NULL */
+  uint8_t* passed;       /* [n_events] or NULL: 1 = the event passed */
+  attpc_event_summary* events; /* [n_events] or NULL */
+  attpc_track_summary* tracks; /* [n_events * n_sim] or NULL */
+  int64_t n_passed;      /* out: events that passed */
+  int64_t n_rows;        /* out: rows of the passed events (Spyral kind: those above the threshold) */
+} attpc_select_out;
+
+/* desc == NULL turns the mode off.  Independent of every other *_configure: no call resets another.  ATTPC_E_INVALID
+ * for lo > hi in any range, a NaN bound, min_tracks > popcount(track_mask) or mask bits at or above ATTPC_MAX_SIM. */
+ATTPC_API int32_t attpc_select_configure(attpc_ctx* ctx, const attpc_select_desc* desc);
+/* attpc_sim_run / attpc_sim_run_spyral (out->kind) of the events that pass.  Needs attpc_summary_configure and
+ * attpc_select_configure, the Spyral kind attpc_spyral_configure as well (else ATTPC_E_NOTCONFIGURED); a mask bit at or
+ * above layout->n_sim is ATTPC_E_INVALID.  attpc_run_stats keeps its cloud meaning over ALL events (n_points: every
+ * cloud row, in either kind), the kinematics outputs cover all events; a pending attpc_sim_hint_next is dropped. */
+ATTPC_API int32_t attpc_sim_run_selected(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                         const attpc_event_layout* layout, double* p4, double* vertex,
+                                         int32_t* kin_status, attpc_select_out* out, attpc_run_stats* stats);
+/* The same with kinematics from host arrays p4 [n, n_rows, 4] / vertex [n, 3] (the file-driven flow). */
+ATTPC_API int32_t attpc_det_run_selected(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                         const attpc_event_layout* layout, const double* p4, const double* vertex,
+                                         attpc_select_out* out, attpc_run_stats* stats);
+/* The predicate on any host cloud through the same kernels: attpc_cloud_summary (same arguments, same checks; out may
+ * be NULL) followed by the selection.  The track part of the records is the empty one (n_samples = 0, ends NaN), so a
+ * present cut on an end point rejects and an absent one passes.  passed [n_events].  A mask bit at or above
+ * layout->n_sim is ATTPC_E_INVALID. */
+ATTPC_API int32_t attpc_cloud_select(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                                     const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out,
+                                     uint8_t* passed);
+
 #ifdef __cplusplus
 }
 #endif
