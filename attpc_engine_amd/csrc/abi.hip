@@ -40,11 +40,6 @@ namespace {
 using namespace attpc;
 
 constexpr int MAX_SLOTS = 8;           // scatter chunks per track batch
-#ifdef ATTPC_PHASE_TIMERS
-constexpr int CTRL_WORDS = 64;         // (diagnostic build: + per-wave timers in 40..63)
-#else
-constexpr int CTRL_WORDS = 40;         // u64 control words per scatter launch (scatter.hip: 0..32 used)
-#endif
 constexpr uint32_t LONE_CAPACITY = 65536;
 constexpr int64_t CLOUD_BUDGET_BYTES = 24ll << 30;  // points + labels of one chunk
 constexpr int64_t DELIVER_CHUNK_ROWS = 96ll << 20;  // cloud rows of a chunk whose cloud is delivered (3 GB: ~60 ms of PCIe)
@@ -75,7 +70,7 @@ struct Pinned {  // page-locked host array of the library, grow-only (ensure_pin
 struct TrackSet {  // kinematics + tracks of one track batch
   DevBuf p4, vertex, status, attempts, arena, block_table, counts, n_steps, ctrl;
   size_t arena_blocks = 0;
-  Pinned<uint32_t> h_ctrl;  // [16]
+  Pinned<uint32_t> h_ctrl;  // [TRK_WORDS]
   hipEvent_t done = nullptr, k0 = nullptr, k1 = nullptr, t0 = nullptr, t1 = nullptr;
   bool timed_kin = false;
 };
@@ -164,7 +159,7 @@ struct attpc_ctx {
   double blocks_per_track = 0.0;   // observed arena blocks per track
   bool prefer_big = false;         // sticky: the small scatter variant met too many lone buckets
   bool prefer_wide = false;        // sticky: u32 sums per table slot are not enough for this detector (scatter_wide.hip)
-  bool slot_wide[8] = {};          // per control-word slot: the launch queued last used the wide build
+  bool slot_wide[MAX_SLOTS] = {};        // per control-word slot: the launch queued last used the wide build
   bool lone_ready = false;         // lone_bucket_kernel's tables are allocated AND their zeroing has been queued
   uint64_t n_growths = 0;          // device buffers (re)allocated so far (a steady workload stops growing)
   uint64_t device_bytes = 0;       // bytes of the grow-only device buffers (ensure()) held right now
@@ -372,117 +367,6 @@ struct ChunkResult {
   float ms_scatter = 0;
 };
 
-// ------------------------------------------------------------------ small device helpers ----
-// out[i] = sum of in[0..i), i = 0..n (one workgroup; n is a chunk's event count), *total = out[n].
-// `ctrl` (may be null): control words of the scatter launch that produced the counts -- if that launch ran
-// out of cloud or segment capacity (ctrl[6]) its rows were not all written and its segment list has
-// unwritten slots, so every offset becomes 0: the kernels behind this one then see empty events and touch
-// nothing, and the host repeats the launch with larger buffers.
-__global__ __launch_bounds__(1024) void exclusive_scan_kernel(const uint32_t* __restrict__ in, uint32_t n,
-                                                              int64_t* __restrict__ out, int64_t* __restrict__ total,
-                                                              const unsigned long long* __restrict__ ctrl) {
-  __shared__ long long wave_sum[16];
-  __shared__ long long carry;
-  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-  const bool dead = ctrl != nullptr && ctrl[6] != 0ull;
-  if (t == 0) carry = 0;
-  block_sync();
-  for (uint32_t base = 0; base < n; base += 1024u) {
-    const uint32_t i = base + (uint32_t)t;
-    const long long v = (i < n && !dead) ? (long long)in[i] : 0ll;
-    long long incl = v;
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long up = __shfl_up(incl, off);
-      incl += lane >= off ? up : 0ll;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    block_sync();
-    long long before = carry;
-    for (int w = 0; w < wave; ++w) before += wave_sum[w];
-    if (i < n) out[i] = before + incl - v;
-    block_sync();
-    if (t == 1023) carry = before + incl;
-    block_sync();
-  }
-  if (t == 0) {
-    out[n] = carry;
-    if (total) *total = carry;
-  }
-}
-
-// Device-side CSR assembly: segment s (one flushed window of one event) is copied to rows
-// ev_start[event] + ev_offset of the event-ordered arrays.  n_segs is read from the launch's control
-// words (the host never sees the segment list).
-__global__ __launch_bounds__(256) void gather_segments_kernel(const Segment* __restrict__ segs,
-                                                              const unsigned long long* __restrict__ ctrl,
-                                                              int64_t seg_capacity,
-                                                              const int64_t* __restrict__ ev_start,
-                                                              const double* __restrict__ points,
-                                                              const int64_t* __restrict__ labels,
-                                                              double* __restrict__ out_points,
-                                                              int64_t* __restrict__ out_labels) {
-  if (ctrl[6] != 0ull) return;  // the launch ran out of capacity: unwritten segment slots, see exclusive_scan_kernel
-  const unsigned long long n_all = ctrl[1];
-  const uint32_t n_segs = (uint32_t)(n_all < (unsigned long long)seg_capacity ? n_all : (unsigned long long)seg_capacity);
-  for (uint32_t s = blockIdx.x; s < n_segs; s += gridDim.x) {
-    const Segment sg = segs[s];
-    if (sg.count <= 0) continue;
-    const int64_t dst = ev_start[sg.event] + sg.ev_offset;
-    const double* src_p = points + sg.offset * 3;
-    double* dst_p = out_points + dst * 3;
-    for (int i = threadIdx.x; i < sg.count * 3; i += 256) dst_p[i] = src_p[i];
-    const int64_t* src_l = labels + sg.offset;
-    int64_t* dst_l = out_labels + dst;
-    for (int i = threadIdx.x; i < sg.count; i += 256) dst_l[i] = src_l[i];
-  }
-}
-
-// ---- compact transfer of delivered clouds ----
-// The delivered path is PCIe bound (234 KB per event in the reference's dtypes), so a chunk crosses the link as 16-byte
-// records (PackedRow, unpack_host.hpp) into library-owned pinned staging and host threads expand it into the caller's
-// arrays -- which then need not be page-locked either.  A chunk with a row that does not fit (charge >= 2^45,
-// label >= 32) goes the plain way.
-// tight != 0: the 8-byte record (PackedRow8, unpack_host.hpp) -- the jitter is not sent at all: it is a pure function of
-// (seed, event, time bucket, pad), and the host regenerates it with the same Philox2x32-7.  flag[0] != 0: a row does not fit
-// the 16-byte record; flag[1] != 0: a row does not fit the 8-byte one (charge >= 2^36, or a jittered time bucket that
-// is a whole number -- tb + U rounded up to tb + 1, about one row in 1e13 -- from which the bucket cannot be read back).
-__global__ __launch_bounds__(256) void pack_rows_kernel(const int64_t* __restrict__ ev_start, uint32_t n_events,
-                                                        const double* __restrict__ points, const int64_t* __restrict__ labels,
-                                                        PackedRow* __restrict__ packed, int64_t* __restrict__ flag, int tight) {
-  const int64_t total = ev_start[n_events];
-  bool bad = false, bad8 = false;
-  unsigned long long* __restrict__ packed8 = reinterpret_cast<unsigned long long*>(packed);
-  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < total; r += (int64_t)gridDim.x * 256) {
-    const double padf = points[3 * r], tbj = points[3 * r + 1], q = points[3 * r + 2];
-    const long long label = labels[r];
-    const unsigned long long charge = (unsigned long long)q, pad = (unsigned long long)padf;
-    bad = bad || !(q >= 0.0) || charge >= (1ull << PACK_CHARGE_BITS) || pad >= (1ull << PACK_PAD_BITS) || label < 0 || label >= 32;
-    if (tight) {
-      const double tbf = floor(tbj);
-      bad8 = bad8 || charge >= (1ull << PACK8_CHARGE_BITS) || !(tbf >= 0.0) || tbf >= (double)(1 << PACK8_TB_BITS) || tbf == tbj;
-      packed8[r] = (charge & ((1ull << PACK8_CHARGE_BITS) - 1)) | ((unsigned long long)tbf << PACK8_CHARGE_BITS) |
-                   (pad << (PACK8_CHARGE_BITS + PACK8_TB_BITS)) |
-                   ((unsigned long long)label << (PACK8_CHARGE_BITS + PACK8_TB_BITS + PACK_PAD_BITS));
-    } else {
-      PackedRow row;
-      row.tb = tbj;
-      row.bits = (charge & ((1ull << PACK_CHARGE_BITS) - 1)) | (pad << PACK_CHARGE_BITS) |
-                 ((unsigned long long)label << (PACK_CHARGE_BITS + PACK_PAD_BITS));
-      packed[r] = row;
-    }
-  }
-  if (__any(bad) && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(flag), 1ull);
-  if (__any(bad8 || bad) && (threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned long long*>(flag) + 1, 1ull);
-}
-
-__global__ __launch_bounds__(256) void count_status_kernel(const int32_t* __restrict__ status, uint32_t n,
-                                                           uint32_t* __restrict__ counter) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  const bool bad = i < n && status[i] != 0;
-  const unsigned long long m = __ballot(bad);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(counter, (uint32_t)__popcll(m));
-}
-
 // ------------------------------------------------------------------ tracks ----
 int32_t ensure_kin_buffers(attpc_ctx* ctx, TrackSet& ts, uint32_t n, int n_rows) {
   int32_t rc;
@@ -492,8 +376,14 @@ int32_t ensure_kin_buffers(attpc_ctx* ctx, TrackSet& ts, uint32_t n, int n_rows)
   if ((rc = ensure(ctx, ts.vertex, (size_t)n * 3 * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, ts.status, (size_t)n * sizeof(int32_t)))) return rc;
   if ((rc = ensure(ctx, ts.attempts, (size_t)n * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, ts.ctrl, 16 * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, ts.ctrl, TRK_WORDS * sizeof(uint32_t)))) return rc;
   return ATTPC_OK;
+}
+
+TrackBuffers track_buffers(const TrackSet& ts) {  // the device view of a track set
+  return TrackBuffers{static_cast<double*>(ts.arena.p), static_cast<int32_t*>(ts.block_table.p), static_cast<int32_t*>(ts.counts.p),
+                      static_cast<int32_t*>(ts.n_steps.p), static_cast<uint32_t*>(ts.ctrl.p),
+                      (uint32_t)std::min<size_t>(ts.arena_blocks, 0xFFFFFFFFu)};
 }
 
 struct TrackLaunch {  // what launch_tracks queued, for finish_tracks
@@ -510,8 +400,8 @@ struct TrackLaunch {  // what launch_tracks queued, for finish_tracks
 int32_t launch_tracks(attpc_ctx* ctx, TrackSet& ts, const TrackLaunch& tl) {
   const uint32_t n_tracks = tl.n * (uint32_t)tl.lay.n_sim;
   int32_t rc;
-  if ((rc = ensure(ctx, ts.ctrl, 16 * sizeof(uint32_t)))) return rc;
-  HIP_TRY(ctx, hipMemsetAsync(ts.ctrl.p, 0, 16 * sizeof(uint32_t), ctx->stream_t));
+  if ((rc = ensure(ctx, ts.ctrl, TRK_WORDS * sizeof(uint32_t)))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ts.ctrl.p, 0, TRK_WORDS * sizeof(uint32_t), ctx->stream_t));
   if (n_tracks) {
     ctx->max_batch_events = std::max(ctx->max_batch_events, tl.n);
     const size_t alloc_tracks = (size_t)ctx->max_batch_events * (size_t)tl.lay.n_sim;
@@ -537,12 +427,7 @@ int32_t launch_tracks(attpc_ctx* ctx, TrackSet& ts, const TrackLaunch& tl) {
     TrackArgs ta;
     ta.det = ctx->det;
     ta.layout = tl.lay;
-    ta.buf.arena = static_cast<double*>(ts.arena.p);
-    ta.buf.block_table = static_cast<int32_t*>(ts.block_table.p);
-    ta.buf.counts = static_cast<int32_t*>(ts.counts.p);
-    ta.buf.n_steps = static_cast<int32_t*>(ts.n_steps.p);
-    ta.buf.ctrl = static_cast<uint32_t*>(ts.ctrl.p);
-    ta.buf.arena_blocks = (uint32_t)std::min<size_t>(want_blocks, 0xFFFFFFFFu);
+    ta.buf = track_buffers(ts);
     ta.p4 = static_cast<const double*>(ts.p4.p);
     ta.vertex = static_cast<const double*>(ts.vertex.p);
     ta.kin_status = tl.use_status ? static_cast<const int32_t*>(ts.status.p) : nullptr;
@@ -567,12 +452,11 @@ int32_t launch_tracks(attpc_ctx* ctx, TrackSet& ts, const TrackLaunch& tl) {
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ts.t1, ctx->stream_t));
   }
-  if (tl.use_status && tl.n) {  // events that hit event_sample_limit -> ctrl[3]
-    hipLaunchKernelGGL(count_status_kernel, dim3((tl.n + 255) / 256), dim3(256), 0, ctx->stream_t,
-                       static_cast<const int32_t*>(ts.status.p), tl.n, static_cast<uint32_t*>(ts.ctrl.p) + 3);
+  if (tl.use_status && tl.n) {  // events that hit event_sample_limit
+    launch_count_status(ctx->stream_t, static_cast<const int32_t*>(ts.status.p), tl.n, static_cast<uint32_t*>(ts.ctrl.p) + TRK_AT_LIMIT);
     HIP_TRY(ctx, hipGetLastError());
   }
-  HIP_TRY(ctx, hipMemcpyAsync(ts.h_ctrl.p, ts.ctrl.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream_t));
+  HIP_TRY(ctx, hipMemcpyAsync(ts.h_ctrl.p, ts.ctrl.p, TRK_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream_t));
   HIP_TRY(ctx, hipEventRecord(ts.done, ctx->stream_t));
   return ATTPC_OK;
 }
@@ -589,21 +473,15 @@ int32_t finish_tracks(attpc_ctx* ctx, TrackSet& ts, const TrackLaunch& tl, Track
       HIP_TRY(ctx, hipEventElapsedTime(&ms_t, ts.t0, ts.t1));
       *ms_tracks += ms_t;  // timings of discarded attempts stay counted: they were spent
     }
-    if (ts.h_ctrl[2] == 0) {  // no sample was refused
-      if (n_tracks) ctx->blocks_per_track = (double)ts.h_ctrl[1] / (double)n_tracks;
-      if (n_limit) *n_limit += ts.h_ctrl[3];
-      if (n_capped) *n_capped += ts.h_ctrl[4];
-      *out = TrackBuffers{};
-      out->arena = static_cast<double*>(ts.arena.p);
-      out->block_table = static_cast<int32_t*>(ts.block_table.p);
-      out->counts = static_cast<int32_t*>(ts.counts.p);
-      out->n_steps = static_cast<int32_t*>(ts.n_steps.p);
-      out->ctrl = static_cast<uint32_t*>(ts.ctrl.p);
-      out->arena_blocks = (uint32_t)std::min<size_t>(ts.arena_blocks, 0xFFFFFFFFu);
+    if (ts.h_ctrl[TRK_OVERFLOW] == 0) {  // no sample was refused
+      if (n_tracks) ctx->blocks_per_track = (double)ts.h_ctrl[TRK_NEXT_BLOCK] / (double)n_tracks;
+      if (n_limit) *n_limit += ts.h_ctrl[TRK_AT_LIMIT];
+      if (n_capped) *n_capped += ts.h_ctrl[TRK_CAPPED];
+      *out = track_buffers(ts);
       return ATTPC_OK;
     }
     // arena exhausted (the block counter kept counting): grow and run the batch again
-    const size_t want = std::max<size_t>((size_t)ts.h_ctrl[1] + (size_t)ts.h_ctrl[1] / 8 + 1024, ts.arena_blocks * 2);
+    const size_t want = std::max<size_t>((size_t)ts.h_ctrl[TRK_NEXT_BLOCK] + (size_t)ts.h_ctrl[TRK_NEXT_BLOCK] / 8 + 1024, ts.arena_blocks * 2);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_t));
     ts.arena_blocks = std::max(ts.arena_blocks, want);
     int32_t rc = launch_tracks(ctx, ts, tl);
@@ -686,6 +564,15 @@ ScatterPlan plan_scatter(const attpc_ctx* ctx, uint32_t n) {
   return p;
 }
 
+// the device control words of slot `slot`, and the chunk its launch scattered as the kernels behind it read it
+unsigned long long* slot_words(const attpc_ctx* ctx, int slot) {
+  return static_cast<unsigned long long*>(ctx->out_ctrl.p) + (size_t)slot * CTRL_WORDS;
+}
+ChunkView chunk_view(const attpc_ctx* ctx, int slot) {
+  return ChunkView{static_cast<const double*>(ctx->points.p), static_cast<const int64_t*>(ctx->labels.p),
+                   static_cast<const Segment*>(ctx->segments.p), slot_words(ctx, slot), ctx->seg_capacity, ctx->cloud_capacity};
+}
+
 // Queue the scatter of the `n` events starting at event `e0` of a track batch (global id
 // `first_event` = batch first + e0) on stream S, control words in slot `slot`.  `grow` may enlarge the
 // cloud (the caller guarantees S is idle then).
@@ -717,7 +604,7 @@ int32_t enqueue_scatter(attpc_ctx* ctx, int slot, const attpc_event_layout& lay,
     // out of capacity) cannot go unnoticed on freshly allocated, zero-filled memory
     if (ctx->opt_tiny) HIP_TRY(ctx, hipMemsetAsync(ctx->segments.p, 0x7f, ctx->segments.bytes, ctx->stream));
   }
-  unsigned long long* d_ctrl = static_cast<unsigned long long*>(ctx->out_ctrl.p) + (size_t)slot * CTRL_WORDS;
+  unsigned long long* d_ctrl = slot_words(ctx, slot);
   HIP_TRY(ctx, hipMemsetAsync(d_ctrl, 0, CTRL_WORDS * sizeof(unsigned long long), ctx->stream));
   ScatterArgs sa;
   sa.det = ctx->det;
@@ -760,17 +647,18 @@ int32_t enqueue_scatter(attpc_ctx* ctx, int slot, const attpc_event_layout& lay,
 #ifdef ATTPC_PHASE_TIMERS
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   const unsigned long long* octrl = ctx->h_out_ctrl.p + (size_t)slot * CTRL_WORDS;
+  const unsigned long long* ph = octrl + CTRL_PHASE;  // the CTRL_PHASE_WORDS phase words, numbered as PHASE_MARK / PHASE_COUNT do
   fprintf(stderr, "[attpc phase cycles] init %llu hist %llu select %llu stage %llu items %llu insert-calls %llu insert-trips %llu flushcount %llu flushwrite %llu (events %u)\n",
-          octrl[8], octrl[9], octrl[10], octrl[11], octrl[12], octrl[13] >> 32, octrl[13] & 0xffffffffull, octrl[14], octrl[15], n);
-  fprintf(stderr, "[attpc rows-phase cycles] gathers %llu runs %llu scan+queue %llu drain %llu\n", octrl[16], octrl[17], octrl[18], octrl[19]);
-  fprintf(stderr, "[attpc rounds] rows-rounds %llu staged %llu busiest-wave passes %llu\n", octrl[20], octrl[21], octrl[22]);
-  fprintf(stderr, "[attpc flush cycles] to-barrier %llu to-compacted %llu atomics-wait %llu segment %llu select %llu barrier %llu\n", octrl[27], octrl[23], octrl[24], octrl[25], octrl[26], octrl[14]);
-  fprintf(stderr, "[attpc ctrl] rows %llu segments %llu failed %llu retried %llu samples %llu\n", octrl[0], octrl[1],
-          octrl[4], octrl[5], octrl[7]);
+          ph[0], ph[1], ph[2], ph[3], ph[4], ph[5] >> 32, ph[5] & 0xffffffffull, ph[6], ph[7], n);
+  fprintf(stderr, "[attpc rows-phase cycles] gathers %llu runs %llu scan+queue %llu drain %llu\n", ph[8], ph[9], ph[10], ph[11]);
+  fprintf(stderr, "[attpc rounds] rows-rounds %llu staged %llu busiest-wave passes %llu\n", ph[12], ph[13], ph[14]);
+  fprintf(stderr, "[attpc flush cycles] to-barrier %llu to-compacted %llu atomics-wait %llu segment %llu select %llu barrier %llu\n", ph[19], ph[15], ph[16], ph[17], ph[18], ph[6]);
+  fprintf(stderr, "[attpc ctrl] rows %llu segments %llu failed %llu retried %llu samples %llu\n", octrl[CTRL_ROW_CURSOR], octrl[CTRL_SEG_CURSOR],
+          octrl[CTRL_FAILED], octrl[CTRL_RETRIED], octrl[CTRL_SAMPLES]);
   fprintf(stderr, "[attpc per-wave wait at the window's last barrier]");
-  for (int w = 0; w < 16; ++w) fprintf(stderr, " %llu", octrl[40 + w]);
+  for (int w = 0; w < CTRL_WAVE_WORDS; ++w) fprintf(stderr, " %llu", octrl[CTRL_WAVE_WAIT + w]);
   fprintf(stderr, "\n[attpc staging, even waves]");
-  for (int w = 0; w < 8; ++w) fprintf(stderr, " %llu", octrl[56 + w]);
+  for (int w = 0; w < CTRL_STAGING_WORDS; ++w) fprintf(stderr, " %llu", octrl[CTRL_STAGING + w]);
   fprintf(stderr, "\n");
 #endif
   return ATTPC_OK;
@@ -782,15 +670,15 @@ void read_scatter(attpc_ctx* ctx, int slot, uint32_t n, ChunkResult* r, int64_t*
   const unsigned long long* o = ctx->h_out_ctrl.p + (size_t)slot * CTRL_WORDS;
   float ms = 0;
   if (hipEventElapsedTime(&ms, ctx->s0[slot], ctx->s1[slot]) == hipSuccess) r->ms_scatter += ms;
-  r->overflow = o[6] != 0;
-  r->reserved = o[0];
-  r->segs = o[1];
-  r->danger = o[32];
+  r->overflow = o[CTRL_OVERFLOW] != 0;
+  r->reserved = o[CTRL_ROW_CURSOR];
+  r->segs = o[CTRL_SEG_CURSOR];
+  r->danger = o[CTRL_DANGER];
   // Windows whose u32 sums could have wrapped were done again by lone_bucket_kernel, one time bucket at a time: exact,
   // but meant for the odd window.  Where they are many (more than one per 64 events), or the list of lone buckets ran
   // over because of them, this detector needs u64 sums: the context switches to the wide build for good and this
   // launch is repeated with it (results do not depend on the build).
-  if (!ctx->slot_wide[slot] && ctx->opt_variant == 0 && r->danger && (r->danger * 64ull > (unsigned long long)n || o[4] != 0)) {
+  if (!ctx->slot_wide[slot] && ctx->opt_variant == 0 && r->danger && (r->danger * 64ull > (unsigned long long)n || o[CTRL_FAILED] != 0)) {
     ctx->prefer_wide = true;
     r->overflow = true;
     *min_rows = std::max<int64_t>(*min_rows, ctx->launch_row_cap);
@@ -798,18 +686,18 @@ void read_scatter(attpc_ctx* ctx, int slot, uint32_t n, ChunkResult* r, int64_t*
     return;
   }
   if (r->overflow) {  // cloud / segment capacity exceeded (the cursors kept counting)
-    *min_rows = (int64_t)(o[0] + o[0] / 8) + 65536;
-    *min_segs = (int64_t)(o[1] + o[1] / 8) + 4096;
+    *min_rows = (int64_t)(r->reserved + r->reserved / 8) + 65536;
+    *min_segs = (int64_t)(r->segs + r->segs / 8) + 4096;
     return;
   }
-  r->rows = o[30];  // rows written; o[0] is the reservation cursor (holes included)
-  r->charge = o[2];
-  r->keys = o[3];
-  r->failed = o[4];
-  r->retried = o[5];
-  r->samples = o[7];
-  r->mismatch = o[31];
-  r->lone = std::min<unsigned long long>(o[29], LONE_CAPACITY);
+  r->rows = o[CTRL_ROWS];  // rows written; r->reserved is the reservation cursor (holes included)
+  r->charge = o[CTRL_CHARGE_SUM];
+  r->keys = o[CTRL_KEY_SUM];
+  r->failed = o[CTRL_FAILED];
+  r->retried = o[CTRL_RETRIED];
+  r->samples = o[CTRL_SAMPLES];
+  r->mismatch = o[CTRL_MISMATCH];
+  r->lone = std::min<unsigned long long>(o[CTRL_LONE], LONE_CAPACITY);
   if (n) {
     ctx->rows_per_event = std::max((double)r->rows / (double)n, 1.0e-3);  // > 0 = known
     ctx->segs_per_event = (double)r->segs / (double)n;
@@ -943,9 +831,7 @@ int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap, 
       HIP_TRY(ctx, hipGetLastError());
     }
   }
-  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(as.kept.p), n,
-                     static_cast<int64_t*>(as.kept_start.p), static_cast<int64_t*>(nullptr),
-                     static_cast<const unsigned long long*>(nullptr));
+  launch_exclusive_scan(ctx->stream, static_cast<const uint32_t*>(as.kept.p), n, static_cast<int64_t*>(as.kept_start.p), nullptr);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(as.h_start.p, as.kept_start.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   return ATTPC_OK;
@@ -1003,10 +889,9 @@ int64_t* packed_flag(const AsmSet& as, size_t record) {
 
 // pack_rows_kernel on S: the event-ordered cloud of `as` into its transfer records (8-byte ones when `tight`).
 int32_t launch_pack_rows(attpc_ctx* ctx, AsmSet& as, uint32_t n, int tight) {
-  hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)ctx->n_cus * 8u), dim3(256), 0, ctx->stream,
-                     static_cast<const int64_t*>(as.ev_start.p), n, static_cast<const double*>(as.points.p),
-                     static_cast<const int64_t*>(as.labels.p), static_cast<PackedRow*>(as.packed.p),
-                     packed_flag(as, sizeof(PackedRow)), tight);
+  launch_pack_rows_kernel(ctx->stream, (uint32_t)ctx->n_cus * 8u, static_cast<const int64_t*>(as.ev_start.p), n,
+                          static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p),
+                          static_cast<PackedRow*>(as.packed.p), packed_flag(as, sizeof(PackedRow)), tight);
   HIP_TRY(ctx, hipGetLastError());
   return ATTPC_OK;
 }
@@ -1050,9 +935,7 @@ int32_t assemble_spyral(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
   launch_spyral_count(ctx->stream, ctx->spyral, n, static_cast<const int64_t*>(as.ev_start.p),
                       static_cast<const double*>(as.points.p), static_cast<uint32_t*>(as.kept.p));
   HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(as.kept.p), n,
-                     static_cast<int64_t*>(as.kept_start.p), static_cast<int64_t*>(nullptr),
-                     static_cast<const unsigned long long*>(nullptr));
+  launch_exclusive_scan(ctx->stream, static_cast<const uint32_t*>(as.kept.p), n, static_cast<int64_t*>(as.kept_start.p), nullptr);
   HIP_TRY(ctx, hipGetLastError());
   SpyralPacked* d_packed = nullptr;
   int64_t* d_flag = nullptr;
@@ -1082,33 +965,19 @@ int32_t enqueue_assembly(attpc_ctx* ctx, int slot, AsmSet& as, uint32_t n, OutMo
   // rows of the scatter launch queued just before (same stream, same slot), kept with 12 % headroom
   if ((size_t)ctx->launch_row_cap > as.row_cap) as.row_cap = (size_t)ctx->launch_row_cap + (size_t)ctx->launch_row_cap / 8;
   if ((rc = ensure_asm_cloud(ctx, as, n, as.row_cap))) return rc;
-  const unsigned long long* d_ctrl = static_cast<const unsigned long long*>(ctx->out_ctrl.p) + (size_t)slot * CTRL_WORDS;
-  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream,
-                     static_cast<const uint32_t*>(selected ? ctx->sel_rows.p : ctx->ev_rows.p), n,
-                     static_cast<int64_t*>(as.ev_start.p), static_cast<int64_t*>(nullptr), d_ctrl);
+  GatherArgs g{};
+  g.chunk = chunk_view(ctx, slot);
+  g.out_capacity = (int64_t)as.row_cap;
+  g.n_events = n;
+  g.event0 = e0;
+  g.passed = selected ? static_cast<const uint8_t*>(ctx->sel_passed.p) : nullptr;
+  g.ev_start = static_cast<const int64_t*>(as.ev_start.p);
+  g.out_points = static_cast<double*>(as.points.p);
+  g.out_labels = static_cast<int64_t*>(as.labels.p);
+  launch_exclusive_scan(ctx->stream, static_cast<const uint32_t*>(selected ? ctx->sel_rows.p : ctx->ev_rows.p), n,
+                        static_cast<int64_t*>(as.ev_start.p), g.chunk.ctrl);
   HIP_TRY(ctx, hipGetLastError());
-  if (selected) {
-    GatherSelectedArgs g{};
-    g.segments = static_cast<const Segment*>(ctx->segments.p);
-    g.ctrl = d_ctrl;
-    g.seg_capacity = ctx->seg_capacity;
-    g.row_capacity = ctx->cloud_capacity;
-    g.out_capacity = (int64_t)as.row_cap;
-    g.n_events = n;
-    g.event0 = e0;
-    g.passed = static_cast<const uint8_t*>(ctx->sel_passed.p);
-    g.ev_start = static_cast<const int64_t*>(as.ev_start.p);
-    g.points = static_cast<const double*>(ctx->points.p);
-    g.labels = static_cast<const int64_t*>(ctx->labels.p);
-    g.out_points = static_cast<double*>(as.points.p);
-    g.out_labels = static_cast<int64_t*>(as.labels.p);
-    launch_gather_selected(ctx->stream, g, 4096);
-  } else {
-    hipLaunchKernelGGL(gather_segments_kernel, dim3(4096), dim3(256), 0, ctx->stream, static_cast<const Segment*>(ctx->segments.p),
-                       d_ctrl, ctx->seg_capacity, static_cast<const int64_t*>(as.ev_start.p),
-                       static_cast<const double*>(ctx->points.p), static_cast<const int64_t*>(ctx->labels.p),
-                       static_cast<double*>(as.points.p), static_cast<int64_t*>(as.labels.p));
-  }
+  launch_gather(ctx->stream, g, selected, 4096);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(as.h_ev_rows.p, ctx->ev_rows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   if (makes_traces(mode)) rc = enqueue_trace_count(ctx, as, n, as.row_cap, seed, first_global);
@@ -1406,24 +1275,18 @@ attpc_event_summary empty_event_summary() {
 }
 
 // The records of `n` events of a batch (its events e0 ..), queued on S behind the launch that wrote the cloud
-// `points` / `labels` / `segs` with control words `d_ctrl`.  trk == nullptr: no tracks, the empty track parts.
-int32_t enqueue_summary(attpc_ctx* ctx, const unsigned long long* d_ctrl, const double* points, const int64_t* labels,
-                        const Segment* segs, int64_t seg_capacity, int64_t row_capacity, const attpc_event_layout& lay,
-                        const TrackBuffers* trk, uint32_t e0, uint32_t n) {
+// `chunk`.  trk == nullptr: no tracks, the empty track parts.
+int32_t enqueue_summary(attpc_ctx* ctx, const ChunkView& chunk, const attpc_event_layout& lay, const TrackBuffers* trk,
+                        uint32_t e0, uint32_t n) {
   int32_t rc;
   if (n == 0) return ATTPC_OK;
   const size_t n_alloc = std::max<size_t>(n, (size_t)std::max(1, ctx->chunk_events));
   if ((rc = ensure_idle(ctx, ctx->sm_seg_count, n_alloc * sizeof(uint32_t)))) return rc;
   if ((rc = ensure_idle(ctx, ctx->sm_seg_start, (n_alloc + 1) * sizeof(int64_t)))) return rc;
-  if ((rc = ensure_idle(ctx, ctx->sm_seg_rank, (size_t)std::max<int64_t>(seg_capacity, 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure_idle(ctx, ctx->sm_seg_list, (size_t)std::max<int64_t>(seg_capacity, 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure_idle(ctx, ctx->sm_seg_rank, (size_t)std::max<int64_t>(chunk.seg_capacity, 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure_idle(ctx, ctx->sm_seg_list, (size_t)std::max<int64_t>(chunk.seg_capacity, 1) * sizeof(uint32_t)))) return rc;
   SummaryArgs a{};
-  a.points = points;
-  a.labels = labels;
-  a.segments = segs;
-  a.ctrl = d_ctrl;
-  a.seg_capacity = seg_capacity;
-  a.row_capacity = row_capacity;
+  a.chunk = chunk;
   a.n_events = n;
   a.event0 = e0;
   a.seg_count = static_cast<uint32_t*>(ctx->sm_seg_count.p);
@@ -1445,11 +1308,10 @@ int32_t enqueue_summary(attpc_ctx* ctx, const unsigned long long* d_ctrl, const 
   a.events = static_cast<attpc_event_summary*>(ctx->sm_events.p);
   a.tracks = lay.n_sim ? static_cast<attpc_track_summary*>(ctx->sm_tracks.p) : nullptr;
   HIP_TRY(ctx, hipMemsetAsync(ctx->sm_seg_count.p, 0, (size_t)n * sizeof(uint32_t), ctx->stream));
-  const uint32_t seg_wgs = (uint32_t)std::min<int64_t>((int64_t)ctx->n_cus * 4, (std::max<int64_t>(seg_capacity, 1) + 255) / 256);
+  const uint32_t seg_wgs = (uint32_t)std::min<int64_t>((int64_t)ctx->n_cus * 4, (std::max<int64_t>(chunk.seg_capacity, 1) + 255) / 256);
   launch_summary_count(ctx->stream, a, seg_wgs);
   HIP_TRY(ctx, hipGetLastError());
-  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const uint32_t*>(ctx->sm_seg_count.p), n,
-                     static_cast<int64_t*>(ctx->sm_seg_start.p), static_cast<int64_t*>(nullptr), d_ctrl);
+  launch_exclusive_scan(ctx->stream, static_cast<const uint32_t*>(ctx->sm_seg_count.p), n, static_cast<int64_t*>(ctx->sm_seg_start.p), chunk.ctrl);
   HIP_TRY(ctx, hipGetLastError());
   launch_summary_fill(ctx->stream, a, seg_wgs);
   HIP_TRY(ctx, hipGetLastError());
@@ -1586,9 +1448,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   // summary mode: the records of chunk c, queued directly behind its scatter (the next chunk overwrites the cloud)
   auto summarise = [&](const Chunk& c) -> int32_t {
     if (!o.summary) return ATTPC_OK;
-    return enqueue_summary(ctx, static_cast<const unsigned long long*>(ctx->out_ctrl.p) + (size_t)c.slot * CTRL_WORDS,
-                           static_cast<const double*>(ctx->points.p), static_cast<const int64_t*>(ctx->labels.p),
-                           static_cast<const Segment*>(ctx->segments.p), ctx->seg_capacity, ctx->cloud_capacity, lay, &trk, c.e0, c.n);
+    return enqueue_summary(ctx, chunk_view(ctx, c.slot), lay, &trk, c.e0, c.n);
   };
   if (o.summary && (rc = ensure_summary_records(ctx, nb, lay.n_sim))) return rc;
   if (o.select && (rc = ensure_idle(ctx, ctx->sel_passed, std::max<size_t>(nb, 1)))) return rc;
@@ -1598,8 +1458,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     int32_t rc2;
     if (o.select) {
       if ((rc2 = summarise(c))) return rc2;
-      if ((rc2 = enqueue_select(ctx, static_cast<const unsigned long long*>(ctx->out_ctrl.p) + (size_t)c.slot * CTRL_WORDS, lay.n_sim,
-                                c.e0, c.n, static_cast<const uint32_t*>(ctx->ev_rows.p)))) return rc2;
+      if ((rc2 = enqueue_select(ctx, slot_words(ctx, c.slot), lay.n_sim, c.e0, c.n, static_cast<const uint32_t*>(ctx->ev_rows.p)))) return rc2;
     }
     return enqueue_assembly(ctx, c.slot, as, c.n, o.mode, seed, batch_first_global + c.e0, o.select != nullptr, c.e0);
   };
@@ -1947,7 +1806,7 @@ int32_t attpc_ctx_create(int32_t device, attpc_ctx** out) {
   auto make_event = [&](hipEvent_t* e) { ok = ok && hipEventCreate(e) == hipSuccess; };
   for (TrackSet& ts : ctx->tset) {
     make_event(&ts.done); make_event(&ts.k0); make_event(&ts.k1); make_event(&ts.t0); make_event(&ts.t1);
-    ok = ok && ensure_pinned(ctx, ts.h_ctrl, 16) == ATTPC_OK;
+    ok = ok && ensure_pinned(ctx, ts.h_ctrl, TRK_WORDS) == ATTPC_OK;
   }
   for (int i = 0; i < MAX_SLOTS; ++i) { make_event(&ctx->s0[i]); make_event(&ctx->s1[i]); }
   for (AsmSet& as : ctx->aset) {
@@ -2581,24 +2440,26 @@ int32_t host_cloud_records(const char* name, attpc_ctx* ctx, int64_t n_events, c
   if ((rc = ensure(ctx, as.points, cap * 3 * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, as.labels, cap * sizeof(int64_t)))) return rc;
   if ((rc = ensure(ctx, ctx->sm_host_segs, (size_t)n * sizeof(Segment)))) return rc;
-  if ((rc = ensure(ctx, ctx->sm_host_ctrl, 8 * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(ctx, ctx->sm_host_ctrl, CTRL_WORDS * sizeof(unsigned long long)))) return rc;
   if ((rc = ensure_summary_records(ctx, n, layout->n_sim))) return rc;
   std::vector<Segment> segs(n);
   for (uint32_t e = 0; e < n; ++e) segs[e] = Segment{(int32_t)e, (int32_t)(offsets[e + 1] - offsets[e]), offsets[e] - first, 0};
-  const unsigned long long ctrl[8] = {(unsigned long long)rows, (unsigned long long)n, 0, 0, 0, 0, 0, 0};
+  unsigned long long words[CTRL_WORDS] = {};  // of a launch that wrote these rows and segments and did not run out of room
+  words[CTRL_ROW_CURSOR] = (unsigned long long)rows, words[CTRL_SEG_CURSOR] = (unsigned long long)n;
   HIP_TRY(ctx, hipMemcpy(ctx->sm_host_segs.p, segs.data(), segs.size() * sizeof(Segment), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->sm_host_ctrl.p, ctrl, sizeof ctrl, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->sm_host_ctrl.p, words, sizeof words, hipMemcpyHostToDevice));
   if (rows > 0) {
     HIP_TRY(ctx, hipMemcpy(as.points.p, points + 3 * first, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(as.labels.p, labels + first, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice));
   }
-  if ((rc = enqueue_summary(ctx, static_cast<const unsigned long long*>(ctx->sm_host_ctrl.p), static_cast<const double*>(as.points.p),
-                            static_cast<const int64_t*>(as.labels.p), static_cast<const Segment*>(ctx->sm_host_segs.p), (int64_t)n,
-                            rows, *layout, nullptr, 0, n))) return rc;
+  const ChunkView chunk{static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p),
+                        static_cast<const Segment*>(ctx->sm_host_segs.p), static_cast<const unsigned long long*>(ctx->sm_host_ctrl.p),
+                        (int64_t)n, rows};
+  if ((rc = enqueue_summary(ctx, chunk, *layout, nullptr, 0, n))) return rc;
   if (out && (rc = copy_summary(ctx, out, 0, n, layout->n_sim))) return rc;
   if (passed) {
     if ((rc = ensure_idle(ctx, ctx->sel_passed, n))) return rc;
-    if ((rc = enqueue_select(ctx, static_cast<const unsigned long long*>(ctx->sm_host_ctrl.p), layout->n_sim, 0, n, nullptr))) return rc;
+    if ((rc = enqueue_select(ctx, chunk.ctrl, layout->n_sim, 0, n, nullptr))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(passed, ctx->sel_passed.p, n, hipMemcpyDeviceToHost, ctx->stream));
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2813,8 +2674,8 @@ int32_t attpc_det_tracks(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, ui
   HIP_TRY(ctx, hipMemcpy(counts, ts.counts.p, (size_t)n_tracks * sizeof(int32_t), hipMemcpyDeviceToHost));
   HIP_TRY(ctx, hipMemcpy(n_steps, ts.n_steps.p, (size_t)n_tracks * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (samples) {
-    // h_ctrl[1] counts reserved blocks (waves reserve pools), all below arena_blocks after a good run
-    std::vector<double> arena(std::min<size_t>(ts.h_ctrl[1], ts.arena_blocks) * ARENA_BLK * 4);
+    // TRK_NEXT_BLOCK counts reserved blocks (waves reserve pools), all below arena_blocks after a good run
+    std::vector<double> arena(std::min<size_t>(ts.h_ctrl[TRK_NEXT_BLOCK], ts.arena_blocks) * ARENA_BLK * 4);
     if (!arena.empty()) HIP_TRY(ctx, hipMemcpy(arena.data(), ts.arena.p, arena.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (uint32_t t = 0; t < n_tracks; ++t) {
       const int64_t c = std::min<int64_t>(counts[t], max_samples_per_track);
@@ -2871,11 +2732,7 @@ int32_t attpc_det_scatter(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, u
     HIP_TRY(ctx, hipMemcpy(ts.block_table.p, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ts.counts.p, counts, (size_t)n_tracks * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  TrackBuffers trk{};
-  trk.arena = static_cast<double*>(ts.arena.p);
-  trk.block_table = static_cast<int32_t*>(ts.block_table.p);
-  trk.counts = static_cast<int32_t*>(ts.counts.p);
-  trk.arena_blocks = (uint32_t)ts.arena_blocks;
+  const TrackBuffers trk = track_buffers(ts);  // (the scatter reads arena, block_table and counts only)
   UnpackDrain drain(ctx);
   attpc_run_stats st{};
   st.n_events = n_events;
@@ -2893,43 +2750,7 @@ int32_t attpc_det_scatter(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, u
 
 }  // extern "C"
 
-// ---- response + Spyral rows ("next" row 1) ----
-namespace attpc {
-// detector/response.py:35-57 (clip each of the 512 samples at 4095, max and sum) and
-// detector/writer.py:61-112 (row layout).  One lane = one point.
-__global__ __launch_bounds__(256) void spyral_rows_kernel(int64_t n, const double* __restrict__ points,
-                                                          const double* __restrict__ response,
-                                                          const double* __restrict__ centers,
-                                                          const double* __restrict__ sizes, int32_t n_pads,
-                                                          double window_edge, double mm_edge, double length,
-                                                          double* __restrict__ rows) {
-  __shared__ double resp[ATTPC_NUM_TB];
-  for (int i = threadIdx.x; i < ATTPC_NUM_TB; i += 256) resp[i] = response[i];
-  block_sync();
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double padf = points[3 * i], tb = points[3 * i + 1], q = points[3 * i + 2];
-  int pad = (int)padf;
-  pad = pad < 0 ? 0 : (pad >= n_pads ? n_pads - 1 : pad);
-  double amp = -1.0 / 0.0, integral = 0.0;
-  for (int k = 0; k < ATTPC_NUM_TB; ++k) {
-    double v = resp[k] * q;
-    v = v > 4095.0 ? 4095.0 : v;
-    amp = v > amp ? v : amp;
-    integral += v;
-  }
-  double* r = rows + 8 * i;
-  r[0] = centers[2 * pad];
-  r[1] = centers[2 * pad + 1];
-  r[2] = (window_edge - tb) / (window_edge - mm_edge) * length * 1000.0;
-  r[3] = amp;
-  r[4] = integral;
-  r[5] = padf;
-  r[6] = tb;
-  r[7] = sizes[pad];
-}
-}  // namespace attpc
-
+// ---- response + Spyral rows ("next" row 1; spyral_rows_kernel of spyral.hip) ----
 extern "C" int32_t attpc_spyral_rows(attpc_ctx* ctx, int64_t n_points, const double* points, const double* response,
                                      const double* pad_centers, const double* pad_sizes, int32_t n_pads,
                                      int32_t windows_edge, int32_t micromegas_edge, double length, double* rows) {
@@ -2947,11 +2768,9 @@ extern "C" int32_t attpc_spyral_rows(attpc_ctx* ctx, int64_t n_points, const dou
   HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, response, ATTPC_NUM_TB * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, pad_centers, (size_t)n_pads * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[3].p, pad_sizes, (size_t)n_pads * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(attpc::spyral_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                     n_points, static_cast<const double*>(ctx->scratch[0].p),
-                     static_cast<const double*>(ctx->scratch[1].p), static_cast<const double*>(ctx->scratch[2].p),
-                     static_cast<const double*>(ctx->scratch[3].p), n_pads, (double)windows_edge,
-                     (double)micromegas_edge, length, static_cast<double*>(ctx->scratch[4].p));
+  attpc::launch_spyral_rows_kernel(ctx->stream, n_points, static_cast<const double*>(ctx->scratch[0].p), static_cast<const double*>(ctx->scratch[1].p),
+                                   static_cast<const double*>(ctx->scratch[2].p), static_cast<const double*>(ctx->scratch[3].p), n_pads,
+                                   (double)windows_edge, (double)micromegas_edge, length, static_cast<double*>(ctx->scratch[4].p));
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(rows, ctx->scratch[4].p, n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -174,13 +174,22 @@ struct DetDev {
 constexpr int ARENA_BLK = 128;
 constexpr int MAX_BLOCKS_PER_TRACK = (ATTPC_TIME_SAMPLES + ARENA_BLK - 1) / ARENA_BLK;  // 79
 
+// The u32 control words of a track launch (TrackBuffers::ctrl), zero before it.
+enum TrackWord : int {
+  TRK_NEXT_TRACK = 0, TRK_NEXT_BLOCK = 1,  // next unassigned track / arena block (keeps counting past arena_blocks)
+  TRK_OVERFLOW = 2,     // != 0: the arena ran out, the host repeats the batch with a larger one
+  TRK_AT_LIMIT = 3,     // events at the sample limit (count_status_kernel)
+  TRK_CAPPED = 4,       // tracks ended by the sample cap (path-length step)
+  TRK_WORDS = 16
+};
+static_assert(TRK_CAPPED < TRK_WORDS, "track control words");
+
 struct TrackBuffers {
   double* arena;          // [arena_blocks][ARENA_BLK][4]
   int32_t* block_table;   // [n_tracks][MAX_BLOCKS_PER_TRACK]
   int32_t* counts;        // [n_tracks] samples with >= 1 electron
   int32_t* n_steps;       // [n_tracks] ODE rows recorded (reference track length)
-  uint32_t* ctrl;         // [0] next track, [1] next arena block, [2] arena overflow flag, [3] events at the sample
-                          // limit (count_status_kernel), [4] tracks ended by the sample cap (path-length step)
+  uint32_t* ctrl;         // [TRK_WORDS] control words of the launch (TrackWord)
   uint32_t arena_blocks;
 };
 
@@ -202,15 +211,58 @@ struct LoneBucket {
   uint32_t tb;      // time bucket
 };
 
+// The u64 control words of a scatter launch (CloudBuffers::ctrl), zero before it: what scatter_kernel and
+// lone_bucket_kernel leave for the kernels behind them and, copied to pinned memory, for the host.
+enum ScatterWord : int {
+  CTRL_ROW_CURSOR = 0, CTRL_SEG_CURSOR = 1,  // rows (holes included) / segments reserved; both keep counting past the capacity
+  CTRL_CHARGE_SUM = 2, CTRL_KEY_SUM = 3,     // checksums: electrons / keys of all rows
+  CTRL_FAILED = 4, CTRL_RETRIED = 5,         // failed events, overflow windows retried
+  CTRL_OVERFLOW = 6,     // != 0: out of cloud or segment capacity, the host repeats the launch with larger buffers
+  CTRL_SAMPLES = 7,      // track samples read
+  CTRL_PHASE = 8,        // diagnostic build (ATTPC_PHASE_TIMERS): CTRL_PHASE_WORDS phase timers and counters
+  CTRL_NEXT_EVENT = 28,  // next unassigned event of the launch
+  CTRL_LONE = 29,        // time buckets left to lone_bucket_kernel (entries of lone_list; keeps counting past its capacity)
+  CTRL_ROWS = 30,        // rows actually written (CTRL_ROW_CURSOR is the reservation cursor)
+  CTRL_MISMATCH = 31,    // windows whose occupied-slot count differed from the claimed keys
+  CTRL_DANGER = 32,      // windows given to lone_bucket_kernel because a u32 sum could have wrapped
+  CTRL_WAVE_WAIT = 40, CTRL_STAGING = 56,  // diagnostic build: per-wave waits at the window's last barrier, staging times
+#ifdef ATTPC_PHASE_TIMERS
+  CTRL_WORDS = 64
+#else
+  CTRL_WORDS = 40
+#endif
+};
+constexpr int CTRL_PHASE_WORDS = 20, CTRL_WAVE_WORDS = 16, CTRL_STAGING_WORDS = 8;
+static_assert(CTRL_SAMPLES < CTRL_PHASE && CTRL_PHASE + CTRL_PHASE_WORDS <= CTRL_NEXT_EVENT, "phase words overlap the named ones");
+static_assert(CTRL_DANGER < CTRL_WORDS && CTRL_DANGER < CTRL_WAVE_WAIT && CTRL_WAVE_WAIT + CTRL_WAVE_WORDS <= CTRL_STAGING, "named words");
+static_assert(CTRL_WORDS == 40 || CTRL_STAGING + CTRL_STAGING_WORDS <= CTRL_WORDS, "the diagnostic build's words");
+
+// A scattered chunk as the kernels behind the launch read it: the rows where they lie, found through the segment list.
+struct ChunkView {
+  const double* points;            // [row_capacity][3], with holes
+  const int64_t* labels;           // [row_capacity]
+  const Segment* segments;         // [seg_capacity]
+  const unsigned long long* ctrl;  // the launch's control words
+  int64_t seg_capacity;
+  int64_t row_capacity;
+};
+
+// "this launch ran out of capacity": rows were not all written and the segment list has unwritten slots, so every
+// kernel behind the launch leaves its outputs alone and the host repeats the launch
+__device__ __forceinline__ bool launch_overflowed(const unsigned long long* ctrl) { return ctrl[CTRL_OVERFLOW] != 0ull; }
+// segments the launch wrote: the cursor, clamped to the list's capacity
+__device__ __forceinline__ uint32_t launch_segments(const ChunkView& c) {
+  const unsigned long long n_all = c.ctrl[CTRL_SEG_CURSOR];
+  return (uint32_t)(n_all < (unsigned long long)c.seg_capacity ? n_all : (unsigned long long)c.seg_capacity);
+}
+
 struct CloudBuffers {
   double* points;         // [capacity][3]
   int64_t* labels;        // [capacity]
   Segment* segments;
-  unsigned long long* ctrl;  // [0] row cursor, [1] segment cursor, [2] charge sum, [3] key sum,
-                             // [4] failed events, [5] overflow windows retried, [6] out-of-capacity flag,
-                             // [7] samples, [29] lone-bucket windows (global-memory table)
+  unsigned long long* ctrl;  // [CTRL_WORDS] control words of the launch (ScatterWord)
   uint32_t* ev_rows;         // [n_events] cloud rows of every event of the launch
-  LoneBucket* lone_list;     // [lone_capacity] time buckets left to lone_bucket_kernel, count in ctrl[29]
+  LoneBucket* lone_list;     // [lone_capacity] time buckets left to lone_bucket_kernel, count in ctrl[CTRL_LONE]
   uint32_t lone_capacity;
   unsigned long long* lone_chg;  // [LONE_WORKGROUPS][LONE_PADS]      lone_bucket_kernel's tables, all 0 between uses
   uint32_t* lone_mask;           // [LONE_WORKGROUPS][LONE_PADS / 4]

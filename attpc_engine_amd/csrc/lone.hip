@@ -23,8 +23,6 @@
 namespace attpc {
 
 constexpr int LONE_THREADS = 256;
-constexpr int LN_CTRL_LONE = 29;   // the same out.ctrl[] slots as scatter.hip
-constexpr int LN_CTRL_ROWS = 30;
 
 struct LoneShared {
   double wtab[ATTPC_MESH_STEPS * ATTPC_MESH_STEPS];
@@ -38,7 +36,7 @@ template <bool MC>
 __global__ __launch_bounds__(LONE_THREADS) void lone_bucket_kernel(ScatterArgs a) {
   __shared__ LoneShared sh;
   const int t = (int)threadIdx.x;
-  const unsigned long long n_listed = a.out.ctrl[LN_CTRL_LONE];
+  const unsigned long long n_listed = a.out.ctrl[CTRL_LONE];
   const uint32_t n_lone = (uint32_t)(n_listed < (unsigned long long)a.out.lone_capacity ? n_listed : a.out.lone_capacity);
   if (n_lone == 0u) return;
   constexpr int MESH = ATTPC_MESH_STEPS;
@@ -150,11 +148,11 @@ __global__ __launch_bounds__(LONE_THREADS) void lone_bucket_kernel(ScatterArgs a
     if (t == 0) {
       unsigned long long base = ~0ull;
       if (n_rows) {
-        const unsigned long long g_base = atomicAdd(&a.out.ctrl[0], (unsigned long long)n_rows);
-        const unsigned long long g_seg = atomicAdd(&a.out.ctrl[1], 1ull);
+        const unsigned long long g_base = atomicAdd(&a.out.ctrl[CTRL_ROW_CURSOR], (unsigned long long)n_rows);
+        const unsigned long long g_seg = atomicAdd(&a.out.ctrl[CTRL_SEG_CURSOR], 1ull);
         const uint32_t before = atomicAdd(&a.out.ev_rows[e_local], n_rows);  // scatter_kernel's total is final
         if (g_base + n_rows > (unsigned long long)a.out.capacity || g_seg >= (unsigned long long)a.out.seg_capacity) {
-          a.out.ctrl[6] = 1ull;  // out of capacity: the host re-runs the chunk with larger buffers
+          a.out.ctrl[CTRL_OVERFLOW] = 1ull;  // out of capacity: the host re-runs the chunk with larger buffers
         } else {
           base = g_base;
           Segment sg;
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(LONE_THREADS) void lone_bucket_kernel(ScatterArgs a
           sg.ev_offset = (int64_t)before;
           a.out.segments[g_seg] = sg;
         }
-        atomicAdd(&a.out.ctrl[LN_CTRL_ROWS], (unsigned long long)n_rows);
+        atomicAdd(&a.out.ctrl[CTRL_ROWS], (unsigned long long)n_rows);
       }
       sh.base = base;
     }
@@ -196,8 +194,8 @@ __global__ __launch_bounds__(LONE_THREADS) void lone_bucket_kernel(ScatterArgs a
     block_sync();
   }
   if (t == 0) {
-    if (sh.charge_sum) atomicAdd(&a.out.ctrl[2], sh.charge_sum);
-    if (sh.key_sum) atomicAdd(&a.out.ctrl[3], sh.key_sum);
+    if (sh.charge_sum) atomicAdd(&a.out.ctrl[CTRL_CHARGE_SUM], sh.charge_sum);
+    if (sh.key_sum) atomicAdd(&a.out.ctrl[CTRL_KEY_SUM], sh.key_sum);
   }
 }
 

@@ -7,10 +7,10 @@
 // :78-120 (position_to_index: floor to whole mm), pairing.py (key), beam_pads.py (folded
 // into the LUT), simulator.py:19-49 (dict_to_points), :108-113 (tb jitter, 0 <= tb < 512).
 //
-// Execution model: persistent workgroups (1024 threads and 8192 table slots, one per compute unit; or,
-// built through scatter_small.hip, 512 threads and 4096 slots, two per compute unit) take events from
+// Execution model: persistent workgroups (1024 threads and 12 288 table slots, one per compute unit; or,
+// built through scatter_small.hip, 512 threads and 6 144 slots, two per compute unit) take events from
 // a global counter; one event at a time, its dictionary is an open-addressing hash table in LDS
-// (u32 key|label word + u64 charge per slot, buckets of 4 keys).
+// (u32 key|label word + u32 charge per slot, buckets of 4 keys; scatter_wide.hip: 8 192 slots with u64 charge).
 // Per event: the entries (samples x slices) are histogrammed by time bucket, prefix-summed and
 // sorted by time bucket once (up to SORT_CAP entries; longer events rank their entry list chunk by chunk
 // and remember every chunk's time-bucket range); events with more keys than the table should hold are cut into
@@ -24,7 +24,7 @@
 //          merged in registers, runs (key|label, charge) written to the wave's LDS queue at positions
 //          from a ballot prefix
 //   insert (same wave) the queued runs as a stream, one probe step per lane and trip: ds_read_b128 bucket
-//          probe, ds_cmpst_b32 to claim a slot, ds_max_u32 for the label, ds_add_u64 for the charge; a lane
+//          probe, ds_cmpst_b32 to claim a slot, ds_max_u32 for the label, ds_add_rtn_u32 (wide: ds_add_u64) for the charge; a lane
 //          that is done takes the next run at once (the loop is written in gfx950 assembly, stream_insert())
 //   flush  occupied slots compacted per wave, rows written (with the Philox time-bucket jitter) to a
 //          range of the output block this workgroup reserved, slots reset on the way
@@ -57,9 +57,9 @@ namespace attpc {
 namespace ATTPC_SC_CAT(sc_, ATTPC_SC_VARIANT) {
 
 // Diagnostic build only (-DATTPC_PHASE_TIMERS): thread 0 of every workgroup accumulates
-// s_memtime deltas per phase into out.ctrl[8 + phase]; never compiled into the shipped library.
+// s_memtime deltas per phase into out.ctrl[CTRL_PHASE + phase]; never compiled into the shipped library.
 #ifdef ATTPC_PHASE_TIMERS
-#define PHASE_DECL unsigned long long ph_t0 = __builtin_amdgcn_s_memtime(), ph_acc[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
+#define PHASE_DECL unsigned long long ph_t0 = __builtin_amdgcn_s_memtime(), ph_acc[CTRL_PHASE_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
 #define PHASE_MARK(k)                                               \
   do {                                                              \
     const unsigned long long ph_now = __builtin_amdgcn_s_memtime(); \
@@ -71,10 +71,10 @@ namespace ATTPC_SC_CAT(sc_, ATTPC_SC_VARIANT) {
 #define PHASE_FLUSH                                                          \
   do {                                                                       \
     if (tid == 0)                                                            \
-      for (int k = 0; k < 20; ++k) atomicAdd(&a.out.ctrl[8 + k], ph_acc[k]); \
-    if (lane == 0 && (tid >> 6) < 16) {  /* per wave: wait at the window's last barrier, staging */ \
-      atomicAdd(&a.out.ctrl[40 + (tid >> 6)], ph_acc[4]);                    \
-      if (((tid >> 6) & 1) == 0) atomicAdd(&a.out.ctrl[56 + (tid >> 7)], ph_acc[3]); \
+      for (int k = 0; k < CTRL_PHASE_WORDS; ++k) atomicAdd(&a.out.ctrl[CTRL_PHASE + k], ph_acc[k]); \
+    if (lane == 0 && (tid >> 6) < CTRL_WAVE_WORDS) {  /* per wave: wait at the window's last barrier, staging */ \
+      atomicAdd(&a.out.ctrl[CTRL_WAVE_WAIT + (tid >> 6)], ph_acc[4]);        \
+      if (((tid >> 6) & 1) == 0) atomicAdd(&a.out.ctrl[CTRL_STAGING + (tid >> 7)], ph_acc[3]); \
     }                                                                        \
   } while (0)
 #else
@@ -146,11 +146,6 @@ constexpr int BINS_PER_THREAD = (ATTPC_NUM_TB + SC_THREADS - 1) / SC_THREADS;
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t KEY_MASK = 0x00FFFFFFu;
 constexpr int SEG_BLOCK = 16;        // segment slots reserved at a time
-constexpr int CTRL_NEXT_EVENT = 28;  // out.ctrl[]: next unassigned event of the launch
-constexpr int CTRL_LONE = 29;        // out.ctrl[]: time buckets left to lone_bucket_kernel (entries of out.lone_list)
-constexpr int CTRL_ROWS = 30;        // out.ctrl[]: rows actually written ([0] is the reservation cursor)
-constexpr int CTRL_MISMATCH = 31;    // out.ctrl[]: windows whose occupied-slot count differed from the claimed keys
-constexpr int CTRL_DANGER = 32;      // out.ctrl[]: windows given to lone_bucket_kernel because a u32 sum could have wrapped
 // merge variant (scatter_kernel<false, true>): a wave works on MERGE_SEQ_PER_WAVE sequences of consecutive entries of
 // the window at a time, ten lanes (the mesh lines of constant y) per sequence; MERGE_G entries of every sequence are
 // staged per round
@@ -1830,13 +1825,13 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
             asm volatile("" : "+v"(zero));  // opaque: keeps LLVM's atomic optimizer (readfirstlane) away
             if (sh.row_cur + n_rows > sh.row_end) {
               const unsigned long long need = max((unsigned long long)a.row_block, (unsigned long long)n_rows);
-              sh.row_cur = atomicAdd(&a.out.ctrl[zero], need);
+              sh.row_cur = atomicAdd(&a.out.ctrl[CTRL_ROW_CURSOR + zero], need);
               sh.row_end = sh.row_cur + need;
             }
             g_base = sh.row_cur;
             sh.row_cur += n_rows;
             if (sh.seg_cur >= sh.seg_end) {
-              sh.seg_cur = atomicAdd(&a.out.ctrl[zero + 1], (unsigned long long)SEG_BLOCK);
+              sh.seg_cur = atomicAdd(&a.out.ctrl[CTRL_SEG_CURSOR + zero], (unsigned long long)SEG_BLOCK);
               sh.seg_end = sh.seg_cur + SEG_BLOCK;
             }
             g_seg = sh.seg_cur++;
@@ -1899,7 +1894,7 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
             PHASE_MARK(16);  // global atomics returned
 #endif
             if (base + n_rows > (unsigned long long)a.out.capacity || g_seg >= (unsigned long long)a.out.seg_capacity) {
-              a.out.ctrl[6] = 1ull;  // out of capacity: host re-runs the chunk with larger buffers
+              a.out.ctrl[CTRL_OVERFLOW] = 1ull;  // out of capacity: host re-runs the chunk with larger buffers
               base = ~0ull;
             } else {
               Segment sg;
@@ -1989,12 +1984,12 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
   }
   block_sync();
   if (tid == 0) {
-    if (sh.wg_samples) atomicAdd(&a.out.ctrl[7], sh.wg_samples);
+    if (sh.wg_samples) atomicAdd(&a.out.ctrl[CTRL_SAMPLES], sh.wg_samples);
     if (sh.wg_rows) atomicAdd(&a.out.ctrl[CTRL_ROWS], sh.wg_rows);
-    if (sh.charge_sum) atomicAdd(&a.out.ctrl[2], sh.charge_sum);
-    if (sh.key_sum) atomicAdd(&a.out.ctrl[3], sh.key_sum);
-    if (sh.failed) atomicAdd(&a.out.ctrl[4], (unsigned long long)sh.failed);
-    if (sh.retried) atomicAdd(&a.out.ctrl[5], (unsigned long long)sh.retried);
+    if (sh.charge_sum) atomicAdd(&a.out.ctrl[CTRL_CHARGE_SUM], sh.charge_sum);
+    if (sh.key_sum) atomicAdd(&a.out.ctrl[CTRL_KEY_SUM], sh.key_sum);
+    if (sh.failed) atomicAdd(&a.out.ctrl[CTRL_FAILED], (unsigned long long)sh.failed);
+    if (sh.retried) atomicAdd(&a.out.ctrl[CTRL_RETRIED], (unsigned long long)sh.retried);
     // reserved but unused segment slots read as empty segments
     Segment none;
     none.event = 0; none.count = 0; none.offset = 0; none.ev_offset = 0;

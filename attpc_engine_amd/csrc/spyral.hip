@@ -171,6 +171,43 @@ __global__ __launch_bounds__(SP_THREADS) void spyral_write_kernel(SpyralDev sp, 
   }
 }
 
+// detector/response.py:35-57 (clip each of the 512 samples at 4095, max and sum) and
+// detector/writer.py:61-112 (row layout).  One lane = one point.
+__global__ __launch_bounds__(256) void spyral_rows_kernel(int64_t n, const double* __restrict__ points, const double* __restrict__ response,
+                                                          const double* __restrict__ centers, const double* __restrict__ sizes, int32_t n_pads,
+                                                          double window_edge, double mm_edge, double length, double* __restrict__ rows) {
+  __shared__ double resp[ATTPC_NUM_TB];
+  for (int i = threadIdx.x; i < ATTPC_NUM_TB; i += 256) resp[i] = response[i];
+  block_sync();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double padf = points[3 * i], tb = points[3 * i + 1], q = points[3 * i + 2];
+  int pad = (int)padf;
+  pad = pad < 0 ? 0 : (pad >= n_pads ? n_pads - 1 : pad);
+  double amp = -1.0 / 0.0, integral = 0.0;
+  for (int k = 0; k < ATTPC_NUM_TB; ++k) {
+    double v = resp[k] * q;
+    v = v > 4095.0 ? 4095.0 : v;
+    amp = v > amp ? v : amp;
+    integral += v;
+  }
+  double* r = rows + 8 * i;
+  r[0] = centers[2 * pad];
+  r[1] = centers[2 * pad + 1];
+  r[2] = (window_edge - tb) / (window_edge - mm_edge) * length * 1000.0;
+  r[3] = amp;
+  r[4] = integral;
+  r[5] = padf;
+  r[6] = tb;
+  r[7] = sizes[pad];
+}
+
+void launch_spyral_rows_kernel(hipStream_t s, int64_t n, const double* points, const double* response, const double* centers,
+                               const double* sizes, int32_t n_pads, double window_edge, double mm_edge, double length, double* rows) {
+  hipLaunchKernelGGL(spyral_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, points, response, centers, sizes,
+                     n_pads, window_edge, mm_edge, length, rows);
+}
+
 void launch_spyral_count(hipStream_t s, const SpyralDev& sp, uint32_t n_events, const int64_t* event_start,
                          const double* points, uint32_t* kept) {
   hipLaunchKernelGGL(spyral_count_kernel, dim3(n_events), dim3(SP_THREADS), 0, s, sp, event_start, points, kept);

@@ -4,7 +4,7 @@
 // segment list (one segment per flushed window of one event, plus lone buckets).  The rows are reduced where they lie:
 //   1. summary_count_kernel   segments per event (one integer atomic per segment, which also gives the segment its
 //                             place among its event's),
-//   2. an exclusive scan of those counts (the host queues exclusive_scan_kernel of abi.hip),
+//   2. an exclusive scan of those counts (the host queues exclusive_scan_kernel of assemble.hip),
 //   3. summary_fill_kernel    the segment numbers grouped by event,
 //   4. summary_event_kernel   one workgroup per event: every thread folds the rows it reads into accumulators of its
 //                             own in LDS (one set per position of layout->indices plus one for every other label), the
@@ -13,7 +13,7 @@
 // Shape (b) of the two that fit: no record is ever accumulated into across workgroups, so a chunk that is scattered
 // again (its buffers were too small) simply overwrites its records, nothing has to be zeroed but the per-event segment
 // counts, and no result depends on the order of anything: counts, integer sums, minima and maxima only.
-// A launch that ran out of room (control word 6) left segment slots unwritten: every kernel here returns at once then,
+// A launch that ran out of room (CTRL_OVERFLOW) left segment slots unwritten: every kernel here returns at once then,
 // as gather_segments_kernel does, and the host repeats scatter and summary.
 #include "tracks_args.hpp"
 
@@ -23,26 +23,21 @@ constexpr int SM_THREADS = 128;                 // threads of summary_event_kern
 constexpr int SM_WORDS = ATTPC_NUM_PADS / 32;   // words of a pad bitmap
 constexpr int SM_NO_SLOT = 15;
 
-__device__ __forceinline__ uint32_t summary_segments(const SummaryArgs& a) {
-  const unsigned long long n_all = a.ctrl[1];
-  return (uint32_t)(n_all < (unsigned long long)a.seg_capacity ? n_all : (unsigned long long)a.seg_capacity);
-}
-
 __global__ __launch_bounds__(256) void summary_count_kernel(SummaryArgs a) {
-  if (a.ctrl[6] != 0ull) return;
-  const uint32_t n_segs = summary_segments(a);
+  if (launch_overflowed(a.chunk.ctrl)) return;
+  const uint32_t n_segs = launch_segments(a.chunk);
   for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < n_segs; s += gridDim.x * 256u) {
-    const Segment sg = a.segments[s];
+    const Segment sg = a.chunk.segments[s];
     if (sg.count <= 0 || (uint32_t)sg.event >= a.n_events) continue;
     a.seg_rank[s] = atomicAdd(&a.seg_count[sg.event], 1u);
   }
 }
 
 __global__ __launch_bounds__(256) void summary_fill_kernel(SummaryArgs a) {
-  if (a.ctrl[6] != 0ull) return;
-  const uint32_t n_segs = summary_segments(a);
+  if (launch_overflowed(a.chunk.ctrl)) return;
+  const uint32_t n_segs = launch_segments(a.chunk);
   for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < n_segs; s += gridDim.x * 256u) {
-    const Segment sg = a.segments[s];
+    const Segment sg = a.chunk.segments[s];
     if (sg.count <= 0 || (uint32_t)sg.event >= a.n_events) continue;
     const int64_t at = a.seg_start[sg.event] + (int64_t)a.seg_rank[s];
     if (at >= 0 && at < (int64_t)n_segs) a.seg_list[at] = s;
@@ -87,7 +82,7 @@ __host__ __device__ constexpr size_t summary_lds_bytes(int n_slots) {
 
 __global__ __launch_bounds__(SM_THREADS) void summary_event_kernel(SummaryArgs a) {
   extern __shared__ unsigned long long sm_raw[];
-  if (a.ctrl[6] != 0ull) return;
+  if (launch_overflowed(a.chunk.ctrl)) return;
   const int n_sim = a.n_sim, n_slots = n_sim + 1;
   const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
   const int cells = n_slots * SM_THREADS;
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(SM_THREADS) void summary_event_kernel(SummaryArgs a
   int32_t* res_tmax = res_tmin + n_slots;
   uint32_t* res_pads = reinterpret_cast<uint32_t*>(res_tmax + n_slots);  // [n_slots + 1]: the last one is the event's
 
-  const uint32_t n_segs = summary_segments(a);
+  const uint32_t n_segs = launch_segments(a.chunk);
   const uint64_t nib_lo = a.slot_nibbles[0], nib_hi = a.slot_nibbles[1];
   const double min_q = a.min_electrons;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
@@ -133,10 +128,10 @@ __global__ __launch_bounds__(SM_THREADS) void summary_event_kernel(SummaryArgs a
     for (int64_t k = k0; k < k1; ++k) {
       const uint32_t s = a.seg_list[k];
       if (s >= n_segs) continue;
-      const Segment sg = a.segments[s];
-      if (sg.count <= 0 || sg.offset < 0 || sg.offset + (int64_t)sg.count > a.row_capacity) continue;
-      const double* __restrict__ rows = a.points + sg.offset * 3;
-      const int64_t* __restrict__ labs = a.labels + sg.offset;
+      const Segment sg = a.chunk.segments[s];
+      if (sg.count <= 0 || sg.offset < 0 || sg.offset + (int64_t)sg.count > a.chunk.row_capacity) continue;
+      const double* __restrict__ rows = a.chunk.points + sg.offset * 3;
+      const int64_t* __restrict__ labs = a.chunk.labels + sg.offset;
       for (int i = t; i < sg.count; i += SM_THREADS) {
         const double padf = rows[(size_t)3 * i], tau = rows[(size_t)3 * i + 1], q = rows[(size_t)3 * i + 2];
         const long long lab = labs[i];

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
         const uint32_t left = ids_end - ids_next;
         const int leader = __ffsll((long long)need) - 1;
         uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&a.buf.ctrl[0], (uint32_t)TRACK_ID_BATCH);
+        if (lane == leader) base = atomicAdd(&a.buf.ctrl[TRK_NEXT_TRACK], (uint32_t)TRACK_ID_BATCH);
         base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
         next_id = rank < left ? ids_next + rank : base + (rank - left);
         ids_next = base + (want - left);
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
           const uint32_t left = pool_end - pool_next;
           const int leader = __ffsll((long long)blk_mask) - 1;
           uint32_t base = 0;
-          if (lane == leader) base = atomicAdd(&a.buf.ctrl[1], (uint32_t)BLOCK_POOL);
+          if (lane == leader) base = atomicAdd(&a.buf.ctrl[TRK_NEXT_BLOCK], (uint32_t)BLOCK_POOL);
           base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
           blk = rank < left ? pool_next + rank : base + (rank - left);
           pool_next = base + (want - left);
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
             a.buf.block_table[(size_t)tid * MAX_BLOCKS_PER_TRACK + (count / ARENA_BLK)] = (int32_t)blk;
           } else {
             blk_ptr = nullptr;
-            a.buf.ctrl[2] = 1u;  // arena exhausted: host re-runs the chunk with a larger arena
+            a.buf.ctrl[TRK_OVERFLOW] = 1u;  // arena exhausted: host re-runs the chunk with a larger arena
           }
         }
         if (blk_ptr != nullptr) {
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
           stop = true;
           // path-length step: the sample cap came before the end of the 1 us window -- the track is cut short
           // (at 0.1 mm about 1 m of arc length); counted, attpc_run_stats.n_tracks_capped
-          if constexpr (PATH) atomicAdd(&a.buf.ctrl[4], 1u);
+          if constexpr (PATH) atomicAdd(&a.buf.ctrl[TRK_CAPPED], 1u);
         }
         if (stop) {
           a.buf.counts[tid] = count;

@@ -65,6 +65,9 @@ struct SpyralDev {
   double r_max, total;
   double window_edge, mm_edge, length, threshold;
 };
+// plain row conversion of `n` cloud points, nothing dropped or sorted (attpc_spyral_rows): rows [n][8]
+void launch_spyral_rows_kernel(hipStream_t s, int64_t n, const double* points, const double* response, const double* centers,
+                               const double* sizes, int32_t n_pads, double window_edge, double mm_edge, double length, double* rows);
 void launch_spyral_count(hipStream_t s, const SpyralDev& sp, uint32_t n_events, const int64_t* event_start,
                          const double* points, uint32_t* kept);
 // rows of every event sorted by z (writer.py:236-238); sort_scratch: one u32 + one f64 per cloud row of the chunk
@@ -167,12 +170,7 @@ void launch_peak_rows(hipStream_t s, const SpyralDev& sp, uint64_t seed, uint32_
 // event and track summaries of a scattered chunk (summary.hip; attpc_summary_configure, the contract is in
 // include/attpc_engine.h).  The rows are read in place through the launch's segment list.
 struct SummaryArgs {
-  const double* points;            // the chunk's cloud as the scatter left it: [row_capacity][3], with holes
-  const int64_t* labels;           // [row_capacity]
-  const Segment* segments;
-  const unsigned long long* ctrl;  // the scatter launch's control words: [1] segments, [6] out of capacity
-  int64_t seg_capacity;
-  int64_t row_capacity;
+  ChunkView chunk;                 // the chunk's cloud as the scatter left it
   uint32_t n_events;               // events of the chunk
   uint32_t event0;                 // first event of the chunk within the track batch (tracks, records)
   uint32_t* seg_count;             // [n_events] segments of every event, zero before summary_count_kernel
@@ -232,7 +230,7 @@ __host__ __device__ inline bool select_passes(const attpc_select_desc& d, const 
 
 struct SelectArgs {
   attpc_select_desc desc;
-  const unsigned long long* ctrl;     // the scatter launch's control words: [6] out of capacity
+  const unsigned long long* ctrl;     // the scatter launch's control words (ScatterWord)
   const attpc_event_summary* events;  // [batch events]
   const attpc_track_summary* tracks;  // [batch events][n_sim] or nullptr (n_sim == 0)
   int32_t n_sim;
@@ -245,22 +243,24 @@ struct SelectArgs {
 // passed and sel_rows of events event0 .. event0 + n_events - 1, one lane per event
 void launch_select(hipStream_t s, const SelectArgs& a);
 
-struct GatherSelectedArgs {
-  const Segment* segments;
-  const unsigned long long* ctrl;  // [1] segments, [6] out of capacity
-  int64_t seg_capacity;
-  int64_t row_capacity;            // rows of points / labels
+// assembly of a scattered chunk and the small kernels of the host pipeline (assemble.hip)
+// out[i] = sum of in[0..i), i = 0 .. n.  ctrl (may be null): the scatter launch that produced the counts; all 0 if it overflowed
+void launch_exclusive_scan(hipStream_t s, const uint32_t* in, uint32_t n, int64_t* out, const unsigned long long* ctrl);
+struct GatherArgs {
+  ChunkView chunk;
   int64_t out_capacity;            // rows of out_points / out_labels
   uint32_t n_events;
-  uint32_t event0;
-  const uint8_t* passed;           // [batch events]
-  const int64_t* ev_start;         // [n_events + 1] exclusive scan of sel_rows
-  const double* points;
-  const int64_t* labels;
+  uint32_t event0;                 // first event of the chunk within the batch (passed)
+  const uint8_t* passed;           // [batch events] (gather_selected_kernel only)
+  const int64_t* ev_start;         // [n_events + 1] CSR offsets of the event-ordered arrays
   double* out_points;
   int64_t* out_labels;
 };
-// gather_segments_kernel of abi.hip for a selected chunk: the segments of events that did not pass are skipped
-void launch_gather_selected(hipStream_t s, const GatherSelectedArgs& a, uint32_t n_workgroups);
+// segment s to rows ev_start[event] + ev_offset of the event-ordered arrays; `selected`: not those of events that failed
+void launch_gather(hipStream_t s, const GatherArgs& a, bool selected, uint32_t n_workgroups);
+// the event-ordered cloud as transfer records (PackedRow, or PackedRow8 when `tight`); flag[0] / [1]: a row does not fit
+void launch_pack_rows_kernel(hipStream_t s, uint32_t n_workgroups, const int64_t* ev_start, uint32_t n_events,
+                             const double* points, const int64_t* labels, PackedRow* packed, int64_t* flag, int tight);
+void launch_count_status(hipStream_t s, const int32_t* status, uint32_t n, uint32_t* counter);  // *counter += #{status[i] != 0}
 
 }  // namespace attpc

@@ -1,6 +1,6 @@
 """Same-session A/B of library builds (run on the GPU box):
-    python tools/ab_scatter.py libA.so libB.so ... [--events N] [--workloads o16aa,be10dp]
-Each library runs in its own child process (ATTPC_HIP_LIBRARY), twice in alternation, and prints
+    python tools/ab_scatter.py libA.so libB.so ... [--events N] [--workloads o16aa,be10dp] [--reps K]
+Each library runs in its own child process (ATTPC_HIP_LIBRARY), K times (default twice) in alternation, and prints
 events/s, kernel milliseconds and the charge / key checksums (which must not change)."""
 import json
 import os
@@ -44,16 +44,18 @@ if __name__ == "__main__":
     if args and args[0] == "--child":
         child(args[1], int(args[2]))
         sys.exit(0)
-    n, wl, libs = 200_000, "o16aa", []
+    n, wl, libs, reps = 200_000, "o16aa", [], 2
     i = 0
     while i < len(args):
         if args[i] == "--events":
             n = int(args[i + 1]); i += 2
         elif args[i] == "--workloads":
             wl = args[i + 1]; i += 2
+        elif args[i] == "--reps":
+            reps = int(args[i + 1]); i += 2
         else:
             libs.append(args[i]); i += 1
-    for rep in range(2):
+    for rep in range(reps):
         for lib in libs:
             env = dict(os.environ, ATTPC_HIP_LIBRARY=str((ROOT / lib).resolve()))
             proc = subprocess.run([sys.executable, __file__, "--child", wl, str(n)], env=env, capture_output=True, text=True)
