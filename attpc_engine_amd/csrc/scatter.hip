@@ -670,6 +670,27 @@ __device__ __forceinline__ bool stream_insert(ScatterShared& sh, const uint2* __
 }
 #endif
 
+// The ten pixel charges of mesh line i from five weights.  wtab[i][j] = C exp(-(2/9)(di^2 + dj^2)) with dj = j - 4.5:
+// dj^2 is the same number for j and 9 - j (squares of +-0.5 .. +-4.5 are exact), so the argument of exp, the weight and
+// the truncated product with the entry's electrons are the same bit pattern for both: el[9 - j] == el[j], for every n.
+// Half the weights (40 bytes of LDS reads), f64 multiplies and f64 -> u32 conversions give all ten values.
+static_assert(MESH == 10, "five weights mirrored into ten pixels");
+__device__ __forceinline__ void mirror_weights(const double* __restrict__ wrow, double (&w)[MESH / 2]) {
+  const double2 w01 = reinterpret_cast<const double2*>(wrow)[0], w23 = reinterpret_cast<const double2*>(wrow)[1];
+  w[0] = w01.x;
+  w[1] = w01.y;
+  w[2] = w23.x;
+  w[3] = w23.y;
+  w[4] = wrow[4];
+}
+__device__ __forceinline__ void mirror_electrons(const double (&w)[MESH / 2], double n_el, uint32_t (&el)[MESH]) {
+#pragma unroll
+  for (int j = 0; j < MESH / 2; ++j) {
+    el[j] = (uint32_t)(w[j] * n_el);  // cvt truncates
+    el[MESH - 1 - j] = el[j];
+  }
+}
+
 // Ten runs per lane at most -> the wave's queue: pixel j's run (key, electrons) goes to LDS address `at` + 8 x (lanes
 // below in mask[j]) on the lanes of mask[j]; `at` = scalar address of the queue's next free entry, advanced past the
 // pixels' runs in turn.  The masks go to exec as they are (an `if` on a mask that crossed a branch is rebuilt by the
@@ -681,9 +702,10 @@ __device__ __forceinline__ void queue_put(uint32_t at, const unsigned long long 
   for (int j = 0; j < MESH; ++j) {
     const unsigned long long mk = mask[j];
     const uint32_t e = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-    asm("" : "+s"(at));  // (kept a scalar of its own: folded into the lane's count it costs a vector add)
     addr[j] = 8u * e + at;
-    at += 8u * (uint32_t)__popcll(mk);
+    // at += 8 x the pixel's runs, as one scalar instruction (the compiler's shift + add pair is two); being an asm it
+    // also keeps `at` a scalar of its own: folded into the lane's count it costs a vector add
+    asm("s_lshl3_add_u32 %0, %1, %0" : "+s"(at) : "s"((uint32_t)__popcll(mk)) : "scc");
   }
   static_assert(MESH == 10, "two blocks of five writes");
 #pragma unroll
@@ -1170,35 +1192,40 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
                       // VALU-bound row phases of the others
           if (wave >= N_WAVES / 2) __builtin_amdgcn_s_sleep(ATTPC_SC_SKEW);
 #endif
-          for (int row0 = wave * 64; row0 < n_rows; row0 += SC_THREADS) {  // wave-uniform trip count
-            const int row = min(row0 + lane, n_rows - 1);
-            const bool have = row0 + lane < n_rows;
-            const int st = row / MESH;
-            const int i = row - st * MESH;
+          // (row0 through readfirstlane: `wave` comes out of the opaque fresh_tid(), and a loop the compiler cannot see
+          //  to be wave uniform gets an exec-mask back-edge -- the `ok` mask rebuilt and the carried scalars copied every
+          //  iteration -- instead of a scalar branch)
+          for (int row0 = __builtin_amdgcn_readfirstlane(wave * 64); row0 < n_rows; row0 += SC_THREADS) {
+            const int row_lane = row0 + lane;
+            const int row = min(row_lane, n_rows - 1);
+            const bool have = row_lane < n_rows;
+            // row / MESH as a full-rate 24-bit multiply and a shift (exact below 16 384 rows) instead of the 32-bit
+            // multiply-high of a division by a constant
+            static_assert(MESH == 10 && STAGE * MESH < 16384, "row * 6554 >> 16 == row / 10");
+            const int st = (int)(__umul24((unsigned int)row, 6554u) >> 16);
+            const int i = row - (int)__umul24((unsigned int)st, (unsigned int)MESH);
             const int tbw = sh.st_tb[st];
             const bool point = (tbw & (1 << 30)) != 0;
             const uint32_t word_hi = ((uint32_t)(tbw & 0x3ff) << 14) | ((uint32_t)((tbw >> 24) & 7) << 24);
             const double n_el = sh.st_n[st];
-            const int ix = sh.st_ix[st][i];
-            // the row's 10 iy indices (5 dwords) and weights (5 x 16 bytes)
+            static_assert(sizeof(sh.st_ix) == sizeof(short) * STAGE * MESH, "st_ix is dense: [st][i] sits at the flat index row");
+            const int ix = (&sh.st_ix[0][0])[row];  // st_ix[st][i]
+            // the row's 10 iy indices (5 dwords) and the first 5 of its weights (2 x 16 bytes + 8)
             const uint32_t* __restrict__ iy32 = reinterpret_cast<const uint32_t*>(&sh.st_iy[st][0]);
-            const double2* __restrict__ w2 = reinterpret_cast<const double2*>(&sh.wtab[i * MESH]);
+            const double* __restrict__ wrow = &sh.wtab[__umul24((unsigned int)i, (unsigned int)MESH)];
             unsigned int iy[MESH];
-            double w[MESH];
+            double w[MESH / 2];
 #pragma unroll
             for (int j = 0; j < MESH; j += 2) {
               const uint32_t pair = iy32[j >> 1];
               iy[j] = pair & 0xffffu;
               iy[j + 1] = pair >> 16;
-              const double2 ww = w2[j >> 1];
-              w[j] = ww.x;
-              w[j + 1] = ww.y;
             }
+            mirror_weights(wrow, w);
             // per-pixel electrons int(pdf h^2 n) (transporter.py:240-246) as u32; the centre pixel is the
             // largest of the row, so one check bounds every run total of the row below 2^32
             uint32_t el[MESH];
-#pragma unroll
-            for (int j = 0; j < MESH; ++j) el[j] = (uint32_t)(w[j] * n_el);  // cvt truncates
+            mirror_electrons(w, n_el, el);
             const bool big = el[MESH / 2] >= (1u << 28);
             // point_transport (transporter.py:123-169, sigma == 0: all electrons straight down, row 0 /
             // pixel 0 stand for the sample) and rows too large for u32 go pixel by pixel into the table
@@ -1373,21 +1400,17 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
             const double n_el = have ? ms.n[st] : 0.0;
             const int ix = ms.ix[st][i];
             const uint32_t* __restrict__ iy32 = reinterpret_cast<const uint32_t*>(&ms.iy[st][0]);
-            const double2* __restrict__ w2 = reinterpret_cast<const double2*>(&sh.wtab[i * MESH]);
             unsigned int iy[MESH];
-            double w[MESH];
+            double w[MESH / 2];
 #pragma unroll
             for (int j = 0; j < MESH; j += 2) {
               const uint32_t pair = iy32[j >> 1];
               iy[j] = pair & 0xffffu;
               iy[j + 1] = pair >> 16;
-              const double2 ww = w2[j >> 1];
-              w[j] = ww.x;
-              w[j + 1] = ww.y;
             }
+            mirror_weights(&sh.wtab[i * MESH], w);
             uint32_t el[MESH];
-#pragma unroll
-            for (int j = 0; j < MESH; ++j) el[j] = (uint32_t)(w[j] * n_el);  // cvt truncates (transporter.py:240-246)
+            mirror_electrons(w, n_el, el);  // (transporter.py:240-246)
             const bool big = el[MESH / 2] >= (1u << 28);
             const bool slow = have && ix != lut_n && (point || big);  // as in rows_round(): straight into the table
             int pad[MESH];
