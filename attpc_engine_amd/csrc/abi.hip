@@ -34,6 +34,7 @@
 
 #include "tracks_args.hpp"
 #include "unpack_host.hpp"
+#include "spyral_integral.hpp"  // (behind the HIP runtime header)
 
 namespace {
 
@@ -2622,21 +2623,19 @@ int32_t attpc_spyral_configure(attpc_ctx* ctx, const attpc_spyral_desc* d) {
   free_all(ctx->spyral_allocs);
   ctx->spyral_ready = false;
   SpyralDev sp{};
-  std::vector<double> sorted(d->response, d->response + ATTPC_NUM_TB);
-  std::sort(sorted.begin(), sorted.end(), [](double a, double b) { return a > b; });
-  std::vector<double> prefix(ATTPC_NUM_TB + 1, 0.0);
-  for (int i = 0; i < ATTPC_NUM_TB; ++i) prefix[i + 1] = prefix[i] + sorted[i];
+  static_assert(SPYRAL_SAMPLES == ATTPC_NUM_TB, "spyral_integral.hpp: one table entry per response sample");
+  std::vector<double> sorted(ATTPC_NUM_TB), tail(ATTPC_NUM_TB + 1);
+  spyral_integral_tables(d->response, sorted.data(), tail.data());
   int32_t rc;
   if ((rc = upload(ctx, ctx->spyral_allocs, d->response, (size_t)ATTPC_NUM_TB, &sp.response))) return rc;
   if ((rc = upload(ctx, ctx->spyral_allocs, sorted.data(), sorted.size(), &sp.sorted_desc))) return rc;
-  if ((rc = upload(ctx, ctx->spyral_allocs, prefix.data(), prefix.size(), &sp.prefix))) return rc;
+  if ((rc = upload(ctx, ctx->spyral_allocs, tail.data(), tail.size(), &sp.tail))) return rc;
   if ((rc = upload(ctx, ctx->spyral_allocs, d->pad_centers, (size_t)d->n_pads * 2, &sp.pad_centers))) return rc;
   if ((rc = upload(ctx, ctx->spyral_allocs, d->pad_sizes, (size_t)d->n_pads, &sp.pad_sizes))) return rc;
   ctx->h_pad_centers.assign(d->pad_centers, d->pad_centers + (size_t)d->n_pads * 2);
   ctx->h_pad_sizes.assign(d->pad_sizes, d->pad_sizes + (size_t)d->n_pads);
   sp.n_pads = d->n_pads;
   sp.r_max = sorted[0];
-  sp.total = prefix[ATTPC_NUM_TB];
   sp.window_edge = (double)d->windows_edge;
   sp.mm_edge = (double)d->micromegas_edge;
   sp.length = d->length;

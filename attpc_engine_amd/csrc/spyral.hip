@@ -6,14 +6,18 @@
 // integral = sum), writer.py:61-112 (convert_to_spyral row layout), writer.py:232-234 (rows with
 // amplitude <= adc_threshold are dropped).
 //
-// The clipped sum has a closed form: with the response samples sorted descending (r_(1) >= r_(2) ...)
-// and k = #{i : r_i q > 4095},  integral = 4095 k + q (total - sum of the k largest).  k comes from a
-// binary search; sum order differs from the reference's sequential loop, i.e. last-bit differences.
+// The clipped sum has a closed form (spyral_integral.hpp): with the response samples sorted descending
+// (r_(1) >= r_(2) ...) and k = #{i : r_i q > 4095},  integral = 4095 k + q tail[k], tail[k] = the sum of all but the
+// k largest samples, accumulated from the smallest upwards when the response is uploaded -- never a difference of
+// two sums, so its error is a few ulp of the larger of the two terms at any charge.  k comes from a binary search,
+// tail[k] is the one table read per row; sum order differs from the reference's sequential loop, i.e. last-bit
+// differences.
 //
 // One workgroup per event; the kept rows are written in ascending z (the z-sort of writer.py:236-238 on
 // the device: counting sort over time bucket x sixteenths of the jitter + rank inside the bin).
 // Bound: HBM (32 B read per cloud row, twice; 72 B written per kept row).
 #include "tracks_args.hpp"
+#include "spyral_integral.hpp"
 
 namespace attpc {
 
@@ -25,13 +29,7 @@ __device__ __forceinline__ double amplitude(const SpyralDev& sp, double q) {
 }
 
 __device__ __forceinline__ double clipped_integral(const SpyralDev& sp, double q) {
-  // k = number of samples with r*q > 4095  (sorted_desc is descending)
-  int lo = 0, hi = ATTPC_NUM_TB;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (sp.sorted_desc[mid] * q > 4095.0) lo = mid + 1; else hi = mid;
-  }
-  return 4095.0 * (double)lo + q * (sp.total - sp.prefix[lo]);
+  return spyral_clipped_integral(sp.sorted_desc, sp.tail, q);
 }
 
 __global__ __launch_bounds__(SP_THREADS) void spyral_count_kernel(SpyralDev sp, const int64_t* __restrict__ event_start,

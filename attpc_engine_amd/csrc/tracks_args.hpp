@@ -58,11 +58,11 @@ void launch_lone_bucket_kernel(uint32_t n_workgroups, hipStream_t s, const Scatt
 struct SpyralDev {
   const double* response;      // [512]
   const double* sorted_desc;   // [512] response sorted descending
-  const double* prefix;        // [513] prefix sums of sorted_desc (prefix[k] = sum of the k largest)
+  const double* tail;          // [513] tail[k] = sum of all but the k largest samples (spyral_integral.hpp)
   const double* pad_centers;   // [n_pads][2]
   const double* pad_sizes;     // [n_pads]
   int32_t n_pads;
-  double r_max, total;
+  double r_max;
   double window_edge, mm_edge, length, threshold;
 };
 // plain row conversion of `n` cloud points, nothing dropped or sorted (attpc_spyral_rows): rows [n][8]

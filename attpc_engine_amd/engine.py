@@ -96,12 +96,13 @@ class Engine:
         return {**res, "points": arrays.result()[1]}
 
     # ---------------------------------------------------------------- Spyral rows on the device
-    def configure_spyral(self, config=None) -> None:
+    def configure_spyral(self, config=None, response=None) -> None:
         """Upload what SpyralWriter needs (reference writer.py:164-181, 220-234): the GET response of
-        the electronics, pad centres / sizes, ADC threshold and time-bucket edges."""
+        the electronics (``response``, default get_response(config)), pad centres / sizes, ADC threshold and
+        time-bucket edges."""
         from .detector.simulator import configure_spyral
 
-        configure_spyral(config or self.config, self.ctx)
+        configure_spyral(config or self.config, self.ctx, response)
         self._spyral_configured = True
 
     def run_spyral(self, n_events: int, seed: int = 0, first_event: int = 0, capacity_per_event: int = 6144,
