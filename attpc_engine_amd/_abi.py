@@ -136,6 +136,10 @@ class PeakDesc(C.Structure):
                 ("max_width", C.c_double), ("rel_height", C.c_double), ("threshold", C.c_double)]
 
 
+class BaselineDesc(C.Structure):
+    _fields_ = [("window_scale", C.c_double)]
+
+
 class EventSummary(C.Structure):
     _fields_ = [("n_points", C.c_uint32), ("n_kept", C.c_uint32), ("n_pads", C.c_uint32), ("tb_min", C.c_int32),
                 ("tb_max", C.c_int32), ("reserved", C.c_int32), ("charge", C.c_int64)]
@@ -278,7 +282,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure", "attpc_sim_run_traces", "attpc_det_run_traces", "attpc_traces",
     "attpc_trace_configure_noise", "attpc_traces_at", "attpc_trace_configure_readout",
     "attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows", "attpc_trace_rows_at",
-    "attpc_trace_rows_last",
+    "attpc_trace_rows_last", "attpc_trace_configure_baseline", "attpc_trace_baseline",
     "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
     "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
 )
@@ -294,6 +298,9 @@ SUMMARY_SYMBOLS = ("attpc_summary_configure", "attpc_sim_run_summary", "attpc_de
 
 # ... and the selected delivery after the summaries: the same rule.
 SELECT_SYMBOLS = ("attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select")
+
+# ... and the Fourier baseline of the trace rows after the selected delivery: the same rule.
+BASELINE_SYMBOLS = ("attpc_trace_configure_baseline", "attpc_trace_baseline")
 
 _lib = None
 
@@ -400,6 +407,14 @@ def load_library() -> C.CDLL:
     for name, argtypes in select.items():
         if not no_select:
             getattr(lib, name).argtypes = argtypes
+    baseline = {
+        "attpc_trace_configure_baseline": [ctxp, C.POINTER(BaselineDesc)],
+        "attpc_trace_baseline": [ctxp, C.c_int64, C.POINTER(C.c_int16), C.c_double, C.POINTER(C.c_int16), _dp],
+    }
+    no_baseline = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in BASELINE_SYMBOLS)
+    for name, argtypes in baseline.items():
+        if not no_baseline:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -421,7 +436,7 @@ def load_library() -> C.CDLL:
     ]
     for name in EXPORTED_SYMBOLS:
         if ((older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS)
-                or (no_select and name in SELECT_SYMBOLS)):
+                or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -430,7 +445,7 @@ def load_library() -> C.CDLL:
     return lib
 
 
-CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks", "summary", "select")
+CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks", "baseline", "summary", "select")
 
 
 class Context:

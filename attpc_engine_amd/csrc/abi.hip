@@ -87,6 +87,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   // of the events, the points' records and centroids; the rows themselves go to sp_rows / sp_labels
   DevBuf pk_maps, pk_counts, pk_row_start, pk_block_sums, pk_block_start, pk_ev_start, pk_records, pk_centroid;
   size_t pk_cap = 0;           // points the point-sized buffers are kept at (grown with headroom)
+  DevBuf pk_y;                 // Fourier baseline on (baseline.hip): the y rows the peak kernels read, int16 [traces][512]
   Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
   size_t row_cap = 0;  // rows the row-sized buffers of the set are kept at (grown with headroom: a launch's row
                        // capacity follows the observed rows per event and moves by fractions of a percent)
@@ -196,6 +197,11 @@ struct attpc_ctx {
   bool peaks_on = false;           // attpc_trace_configure_peaks
   PeakDev peaks{};
   DevBuf peak_sums;                // [1] row checksum of the trace-row run in progress
+  bool baseline_on = false;        // attpc_trace_configure_baseline
+  DevBuf bl_twiddle;               // [512] (cos, sin) of 2 pi j / 512, uploaded once (baseline.hip)
+  DevBuf bl_filter;                // [512] the configured filter in the transform's order
+  DevBuf bl_op_filter;             // [512] the filter of attpc_trace_baseline's last call,
+  double bl_op_scale = 0.0;        // and its window scale (0: none yet): a call with the same scale uploads nothing
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -298,6 +304,38 @@ int32_t upload(attpc_ctx* ctx, std::vector<void*>& owner, const T* host, size_t 
 void free_all(std::vector<void*>& v) {
   for (void* p : v) (void)hipFree(p);
   v.clear();
+}
+
+// The tables of baseline.hip.  filter: F[k] = sinc(w_k / scale), w_k = k below 256 and k - 512 from there on, divided by
+// 512 (the inverse transform's factor: exact) and in the order the kernel's lanes hold the spectrum.
+void baseline_filter(double scale, double* filter) {
+  const long double pi = 3.14159265358979323846264338327950288L;
+  for (int k = 0; k < ATTPC_NUM_TB; ++k) {
+    const long double t = (long double)(k < ATTPC_NUM_TB / 2 ? k : k - ATTPC_NUM_TB) / (long double)scale;
+    const long double f = t == 0.0L ? 1.0L : std::sin(pi * t) / (pi * t);
+    const int k0 = k & 7, k1 = (k >> 3) & 7, k2 = k >> 6;
+    filter[64 * k2 + 8 * k0 + k1] = (double)f / (double)ATTPC_NUM_TB;
+  }
+}
+
+// twiddle / filter on the device: the former once per context, the latter `scale`'s into `buf`
+int32_t upload_baseline_tables(attpc_ctx* ctx, DevBuf& buf, double scale) {
+  int32_t rc;
+  if (!ctx->bl_twiddle.p) {
+    const long double pi = 3.14159265358979323846264338327950288L;
+    std::vector<double> tw(2 * ATTPC_NUM_TB);
+    for (int j = 0; j < ATTPC_NUM_TB; ++j) {
+      tw[2 * j] = (double)std::cos(2.0L * pi * (long double)j / (long double)ATTPC_NUM_TB);
+      tw[2 * j + 1] = (double)std::sin(2.0L * pi * (long double)j / (long double)ATTPC_NUM_TB);
+    }
+    if ((rc = ensure(ctx, ctx->bl_twiddle, tw.size() * sizeof(double)))) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->bl_twiddle.p, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  std::vector<double> filter(ATTPC_NUM_TB);
+  baseline_filter(scale, filter.data());
+  if ((rc = ensure(ctx, buf, filter.size() * sizeof(double)))) return rc;
+  HIP_TRY(ctx, hipMemcpy(buf.p, filter.data(), filter.size() * sizeof(double), hipMemcpyHostToDevice));
+  return ATTPC_OK;
 }
 
 int32_t sync_all(attpc_ctx* ctx) {
@@ -1151,6 +1189,16 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
   const int16_t* pedestals = ctx->noise_on ? ctx->noise.pedestals : nullptr;
   const int32_t* d_pads = static_cast<const int32_t*>(as.tr_pads.p);
   const int16_t* d_samples = static_cast<const int16_t*>(as.tr_samples.p);
+  if (ctx->baseline_on) {  // step 1 of the contract is the fitted baseline: the peak kernels read y rows, no pedestal
+    if ((rc = ensure(ctx, as.pk_y, tr * ATTPC_NUM_TB * sizeof(int16_t)))) return rc;
+    if (traces > 0) {
+      launch_baseline(ctx->stream, (uint32_t)traces, d_samples, static_cast<const double2*>(ctx->bl_twiddle.p),
+                      static_cast<const double*>(ctx->bl_filter.p), static_cast<int16_t*>(as.pk_y.p), nullptr);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    d_samples = static_cast<const int16_t*>(as.pk_y.p);
+    pedestals = nullptr;
+  }
   if (traces > 0) {
     launch_peak_count(ctx->stream, ctx->peaks, pedestals, (uint32_t)traces, d_pads, d_samples,
                       static_cast<uint8_t*>(as.pk_maps.p), static_cast<uint32_t*>(as.pk_counts.p));
@@ -2561,6 +2609,61 @@ int32_t attpc_trace_configure_peaks(attpc_ctx* ctx, const attpc_peak_desc* d) {
   pk.threshold = d->threshold;
   ctx->peaks = pk;
   ctx->peaks_on = true;
+  return ATTPC_OK;
+}
+
+// ---- Fourier baseline of the trace rows (baseline.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_baseline(attpc_ctx* ctx, const attpc_baseline_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d && !(std::isfinite(d->window_scale) && d->window_scale > 0.0))
+    return fail(ctx, ATTPC_E_INVALID, "baseline window_scale %g: finite and > 0", d->window_scale);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  ctx->baseline_on = false;
+  if (!d) return ATTPC_OK;
+  int32_t rc;
+  if ((rc = upload_baseline_tables(ctx, ctx->bl_filter, d->window_scale))) return rc;
+  ctx->baseline_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_trace_baseline(attpc_ctx* ctx, int64_t n_rows, const int16_t* samples, double window_scale, int16_t* y,
+                             double* baseline) {
+  if (!ctx || n_rows < 0) return ATTPC_E_INVALID;
+  if (!(std::isfinite(window_scale) && window_scale > 0.0))
+    return fail(ctx, ATTPC_E_INVALID, "baseline window_scale %g: finite and > 0", window_scale);
+  if (n_rows == 0) return ATTPC_OK;
+  if (!samples || !y) return ATTPC_E_INVALID;
+  for (int64_t i = 0; i < n_rows * ATTPC_NUM_TB; ++i)
+    if (samples[i] < 0 || samples[i] > 4095)
+      return fail(ctx, ATTPC_E_INVALID, "sample %lld of row %lld is %d: 0 .. 4095", (long long)(i % ATTPC_NUM_TB),
+                  (long long)(i / ATTPC_NUM_TB), (int)samples[i]);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  if (ctx->bl_op_scale != window_scale) {
+    ctx->bl_op_scale = 0.0;
+    if ((rc = upload_baseline_tables(ctx, ctx->bl_op_filter, window_scale))) return rc;
+    ctx->bl_op_scale = window_scale;
+  }
+  constexpr int64_t CHUNK = 16384;  // rows: 16 MiB of samples, 16 MiB of y and 64 MiB of baseline on the device
+  const size_t rows = (size_t)std::min(n_rows, CHUNK), row_bytes = ATTPC_NUM_TB * sizeof(int16_t);
+  if ((rc = ensure(ctx, ctx->scratch[0], rows * row_bytes))) return rc;
+  if ((rc = ensure(ctx, ctx->scratch[1], rows * row_bytes))) return rc;
+  if (baseline && (rc = ensure(ctx, ctx->scratch[2], rows * ATTPC_NUM_TB * sizeof(double)))) return rc;
+  for (int64_t first = 0; first < n_rows; first += CHUNK) {
+    const size_t n = (size_t)std::min(CHUNK, n_rows - first);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, samples + first * ATTPC_NUM_TB, n * row_bytes, hipMemcpyHostToDevice, ctx->stream));
+    launch_baseline(ctx->stream, (uint32_t)n, static_cast<const int16_t*>(ctx->scratch[0].p),
+                    static_cast<const double2*>(ctx->bl_twiddle.p), static_cast<const double*>(ctx->bl_op_filter.p),
+                    static_cast<int16_t*>(ctx->scratch[1].p), baseline ? static_cast<double*>(ctx->scratch[2].p) : nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(y + first * ATTPC_NUM_TB, ctx->scratch[1].p, n * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (baseline)
+      HIP_TRY(ctx, hipMemcpyAsync(baseline + first * ATTPC_NUM_TB, ctx->scratch[2].p, n * ATTPC_NUM_TB * sizeof(double),
+                                  hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
   return ATTPC_OK;
 }
 

@@ -167,6 +167,12 @@ void launch_peak_rows(hipStream_t s, const SpyralDev& sp, uint64_t seed, uint32_
                       double* centroid, uint32_t* sort_idx, double* sort_key, double* rows, int64_t* out_labels,
                       unsigned long long* sums);
 
+// Fourier baseline removal of trace rows (baseline.hip; the contract is in include/attpc_engine.h): samples / y
+// [n_rows][512] int16, twiddle [512] (cos, sin) of 2 pi j / 512, filter [512] = F / 512 in the transform's order
+// (entry 64 k2 + 8 k0 + k1 is F[k0 + 8 k1 + 64 k2]), baseline [n_rows][512] f64 or nullptr
+void launch_baseline(hipStream_t s, uint32_t n_rows, const int16_t* samples, const double2* twiddle, const double* filter,
+                     int16_t* y, double* baseline);
+
 // event and track summaries of a scattered chunk (summary.hip; attpc_summary_configure, the contract is in
 // include/attpc_engine.h).  The rows are read in place through the launch's segment list.
 struct SummaryArgs {

@@ -233,6 +233,7 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
             from .traces import simulate_batch_trace_rows
 
             offsets, rows, labels, raw_points, _ = simulate_batch_trace_rows(*args, first_event=start, peaks=writer.peaks,
+                                                                             baseline=getattr(writer, "baseline", None),
                                                                              **writer.trace_kwargs())
             return offsets, raw_points, rows, labels
         if kind == "rows":

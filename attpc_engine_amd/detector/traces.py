@@ -20,6 +20,12 @@ Trace rows are the step after the traces, still on the device (``PeakSettings``,
 ``clouds_to_trace_rows``): the peaks of every kept pad trace above its pedestal -- separation, prominence, width and
 amplitude threshold as in the first phase of Spyral -- as Spyral rows of eight columns in ascending z
 (include/attpc_engine.h; ``tests/peaks_reference.py`` restates it).  Every trace setting above composes with them.
+
+The Fourier baseline is opt-in on top of them (``BaselineSettings``, ``baseline=`` beside ``peaks=``): instead of being
+handed every pad's true pedestal, the peak stage gets Spyral's own estimate of the baseline -- a low-pass filter of the
+trace with its peaks masked out, which takes part of a wide pulse for baseline -- made on the device
+(include/attpc_engine.h; ``tests/baseline_reference.py`` restates it).  ``remove_baseline`` is that stage alone on any
+host rows.
 """
 from __future__ import annotations
 
@@ -342,22 +348,71 @@ def configure_peaks(ctx: _abi.Context, peaks: PeakSettings | None) -> None:
         ctx.configure("peaks", peaks.token(), "attpc_trace_configure_peaks", peaks.desc())
 
 
-def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None, **trace_kwargs) -> None:
+class BaselineSettings:
+    """The validated Fourier baseline of the trace rows (``attpc_baseline_desc``, include/attpc_engine.h):
+    ``window_scale`` (finite, > 0), Spyral's ``GetParameters.baseline_window_scale`` and its default."""
+
+    def __init__(self, window_scale: float = 20.0):
+        self.window_scale = float(window_scale)
+        if not (math.isfinite(self.window_scale) and self.window_scale > 0.0):
+            raise ValueError(f"baseline window_scale must be finite and > 0, got {window_scale}")
+
+    def token(self):
+        return (self.window_scale,)
+
+    def desc(self) -> _abi.BaselineDesc:
+        return _abi.BaselineDesc(*self.token())
+
+
+def configure_baseline(ctx: _abi.Context, baseline: BaselineSettings | None) -> None:
+    """``attpc_trace_configure_baseline`` unless this ctx already holds the same setting (``None``: the stage off, which
+    is also what a new context holds)."""
+    if baseline is None:
+        ctx.configure("baseline", None, "attpc_trace_configure_baseline", None)
+    else:
+        ctx.configure("baseline", baseline.token(), "attpc_trace_configure_baseline", baseline.desc())
+
+
+def remove_baseline(traces, window_scale: float = 20.0, ctx: _abi.Context | None = None, return_baseline: bool = False):
+    """The Fourier baseline stage alone on any host rows (``attpc_trace_baseline``; the kernel of the fused path, no
+    other configuration needed): traces [R,512] integers in 0 .. 4095 -> y [R,512] i16, and with ``return_baseline``
+    (y, baseline [R,512] f64)."""
+    window_scale = BaselineSettings(window_scale).window_scale
+    traces = np.asarray(traces)
+    if traces.ndim != 2 or traces.shape[1] != _abi.NUM_TB or traces.dtype.kind not in "iu":
+        raise ValueError(f"traces must be integers of shape [rows, {_abi.NUM_TB}], got {traces.dtype} {traces.shape}")
+    if traces.size and (traces.min() < 0 or traces.max() > 4095):
+        raise ValueError("trace samples must lie in 0 .. 4095")
+    samples = np.ascontiguousarray(traces, dtype=np.int16)
+    ctx = ctx or _abi.default_context()
+    y = np.empty_like(samples)
+    baseline = np.empty(samples.shape, dtype=np.float64) if return_baseline else None
+    i16 = _abi.C.c_int16
+    ctx.check(ctx.lib.attpc_trace_baseline(ctx.handle, len(samples), _abi.iptr(samples, i16), window_scale,
+                                           _abi.iptr(y, i16), _abi.dptr(baseline)), "attpc_trace_baseline")
+    return (y, baseline) if return_baseline else y
+
+
+def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
+                         baseline: BaselineSettings | None = None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
-    the geometry of the rows (``configure_spyral``) and the peak parameters (default ``PeakSettings()``)."""
+    the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``) and the Fourier
+    baseline (default None: off, the peaks stand on the configured pedestals)."""
     from .simulator import configure_spyral
 
     peaks = PeakSettings() if peaks is None else peaks
     configure_traces(config, ctx, **trace_kwargs)
     configure_spyral(config, ctx)
     configure_peaks(ctx, peaks)
+    configure_baseline(ctx, baseline)
 
 
 def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
                               seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
-                              peaks: PeakSettings | None = None, capacity_per_event: int = 2048, **trace_kwargs):
+                              peaks: PeakSettings | None = None, capacity_per_event: int = 2048,
+                              baseline: BaselineSettings | None = None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
-    (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them) ->
+    (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
     before any suppression, stats dict: the cloud's run statistics with ``n_points`` = the rows, plus ``n_rows`` /
     ``row_checksum``)."""
@@ -368,7 +423,7 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     ctx = ctx or _abi.default_context()
     arrays, stats = run_batch("attpc_det_run_trace_rows", momenta, vertices, proton_numbers, mass_numbers, config, seed,
                               indices, first_event, ctx, capacity_per_event,
-                              configure=lambda c: configure_trace_rows(config, c, peaks, **trace_kwargs),
+                              configure=lambda c: configure_trace_rows(config, c, peaks, baseline, **trace_kwargs),
                               holder=RowArrays, width=8, slack=1024)
     return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **ctx.trace_rows_last()})
 

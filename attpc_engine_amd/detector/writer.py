@@ -150,18 +150,22 @@ class SpyralWriter(_RollingWriter):
     max_event on the group."""
 
     def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
-                 first_run_number: int = 0, npz_fallback: bool = True, *, peaks=None, noise_seed: int = 0,
-                 **trace_kwargs):
+                 first_run_number: int = 0, npz_fallback: bool = True, *, peaks=None, baseline=None,
+                 noise_seed: int = 0, **trace_kwargs):
         """``peaks`` (keyword only; a ``detector.traces.PeakSettings``, default None = the reference's writer: one row
         per cloud point): the rows are the peaks of the event's digitised pad traces instead (EXTENSION, trace rows of
         include/attpc_engine.h), made on the device with the trace settings ``trace_kwargs`` (response, threshold,
         offset, noise_sigma / noise_table, pedestals, noise_stream, readout, readout_pads as
         ``detector.traces.configure_traces`` takes them); ``noise_seed`` keys the draws of ``write``, a run keys them on
-        its own seed.  The files have the same datasets either way."""
+        its own seed.  ``baseline`` (a ``detector.traces.BaselineSettings``, default None = the peaks stand on the
+        configured pedestals): Spyral's Fourier baseline is removed from the traces first.  The files have the same
+        datasets either way."""
         self.response = get_response(config).copy()
         self.peaks = peaks
-        if peaks is None and (trace_kwargs or noise_seed):
-            raise TypeError(f"SpyralWriter takes trace settings only with peaks=: {sorted(trace_kwargs) or ['noise_seed']}")
+        self.baseline = baseline
+        if peaks is None and (trace_kwargs or noise_seed or baseline is not None):
+            given = sorted(trace_kwargs) + (["noise_seed"] if noise_seed else []) + (["baseline"] if baseline is not None else [])
+            raise TypeError(f"SpyralWriter takes trace settings only with peaks=: {given}")
         if peaks is not None:
             from .traces import validate_trace_kwargs
 
@@ -183,7 +187,7 @@ class SpyralWriter(_RollingWriter):
             from .traces import clouds_to_trace_rows, configure_trace_rows
 
             ctx = _abi.default_context()
-            configure_trace_rows(config, ctx, self.peaks, **self.trace_kwargs())
+            configure_trace_rows(config, ctx, self.peaks, self.baseline, **self.trace_kwargs())
             data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
             _, rows, out_labels, _ = clouds_to_trace_rows(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
                                                           seed=self.noise_seed, first_event=event_number)

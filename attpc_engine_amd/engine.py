@@ -174,11 +174,24 @@ class Engine:
         configure_peaks(self.ctx, PeakSettings(**parameters) if peaks is None else peaks)
         self._peaks_configured = True
 
+    def configure_baseline(self, baseline=None, window_scale: float | None = None) -> None:
+        """The Fourier baseline of the trace rows (include/attpc_engine.h): a ``detector.traces.BaselineSettings`` or
+        its ``window_scale`` turns it on -- the peaks of ``run_trace_rows`` then stand on Spyral's own estimate of the
+        baseline instead of the configured pedestals --, neither turns it off (the default)."""
+        from .detector.traces import BaselineSettings, configure_baseline
+
+        if baseline is not None and window_scale is not None:
+            raise TypeError("give a BaselineSettings or its window_scale, not both")
+        if window_scale is not None:
+            baseline = BaselineSettings(window_scale)
+        configure_baseline(self.ctx, baseline)
+
     def run_trace_rows(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
                        capacity_per_event: int = 2048) -> dict:
         """Fused kinematics + detector + pad traces + the peaks of every kept trace as Spyral rows, all on the device
         (``attpc_sim_run_trace_rows``; the traces as ``configure_traces`` set them, the geometry of
-        ``configure_spyral``, the peaks of ``configure_peaks``, each with its defaults if not called).  ``fetch=True``:
+        ``configure_spyral``, the peaks of ``configure_peaks``, each with its defaults if not called; the Fourier baseline
+        of ``configure_baseline`` if that turned it on).  ``fetch=True``:
         offsets [n+1], rows [P,8] (x mm, y mm, z mm, amplitude, integral, pad, centroid, pad scale; every event in
         ascending z), labels [P], event_points [n] and the kinematics; ``fetch=False``: the rows stay on the device.
         Both: ``trace_rows`` = {n_rows, row_checksum} and the cloud's ``stats`` (``n_points`` = the rows)."""
@@ -321,6 +334,7 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
         engine.configure_traces(config, **writer.trace_kwargs())
         engine.configure_spyral(config)
         engine.configure_peaks(writer.peaks)
+        engine.configure_baseline(getattr(writer, "baseline", None))
     elif kind == "rows":
         engine.configure_spyral(config)
     else:

@@ -556,7 +556,8 @@ ATTPC_API int32_t attpc_trace_configure_readout(attpc_ctx* ctx, const attpc_trac
  * Parameters (attpc_peak_desc, all f64): separation >= 1, prominence >= 0, 0 <= min_width <= max_width, rel_height in
  * (0, 1], threshold.
  * For a kept row of pad p in event e (global id) with samples trace[0..511]:
- *   1. y[j] = trace[j] - ped_p, an integer (ped_p = 0 without pedestals).  The baseline is the configured pedestal.
+ *   1. y[j] = trace[j] - ped_p, an integer (ped_p = 0 without pedestals).  The baseline is the configured pedestal
+ *      -- unless attpc_trace_configure_baseline has turned the Fourier baseline on, which replaces this step (below).
  *   2. Candidates: the strict local maxima of y, a flat top counted once at (first + last) div 2, never sample 0 or
  *      511 (scipy.signal.find_peaks(y) without a condition).
  *   3. Separation: a candidate closer than ceil(separation) samples to a kept candidate of higher priority is dropped;
@@ -584,8 +585,9 @@ ATTPC_API int32_t attpc_trace_configure_readout(attpc_ctx* ctx, const attpc_trac
  *      order with CSR offsets.  event_points keeps its meaning (cloud rows before any suppression).
  * With offset = argmax(R) in attpc_trace_configure a lone arrival at bucket t peaks at sample t, so its point's z is
  * the arrival's z; with offset = 0 every point sits argmax(R) buckets late.
- * The baseline is not fitted (Spyral's Fourier filter is for baselines that wander; these do not), and Spyral's later
- * phases (clustering, fitting) are not part of this.
+ * By default the baseline is not fitted: the analysis is handed every pad's true pedestal.  Spyral has to estimate
+ * it, with a Fourier low-pass filter that takes part of a wide pulse for baseline; attpc_trace_configure_baseline
+ * (below) runs that estimate in place of step 1.  Spyral's later phases (clustering, fitting) are not part of this.
  * Results of a call: rows of EIGHT doubles in out->points (capacity counts rows), out->labels, out->offsets,
  * out->event_points; any of them may be NULL, and with points and labels both NULL the capacity does not bind: the
  * rows stay on the device.  stats->n_points is the number of rows of the call (as attpc_sim_run_spyral reports its
@@ -621,6 +623,51 @@ ATTPC_API int32_t attpc_trace_rows_at(attpc_ctx* ctx, uint64_t seed, uint64_t fi
                                       attpc_cloud_out* out);
 /* Rows and row checksum of the context's last trace-row call (either pointer may be NULL). */
 ATTPC_API int32_t attpc_trace_rows_last(attpc_ctx* ctx, int64_t* n_rows, uint64_t* row_checksum);
+
+/* ---- Fourier baseline of the trace rows (opt-in: off by default, and with it off every output of every entry point
+ * is bit for bit what it is without this section) ----
+ * Replaces Spyral's preprocess_traces / GetParameters.baseline_window_scale (the reference stops at point clouds and
+ * has no counterpart: parity is unpinned there).  With the stage on it replaces step 1 of the trace-row contract
+ * above.  For a kept trace row with samples trace[0..511] (int16, 0..4095) and scale = window_scale:
+ *   a. Edges: x[j] = trace[j], then x[0] = x[1] and x[511] = x[510] (Spyral's edge fix).  It is part of x from here
+ *      on, in the result as well.
+ *   b. Peak mask, in integers: S = sum x, Q = sum x^2, d_j = 512 x[j] - S.  Sample j is masked iff d_j > 0 and
+ *      4 d_j^2 > 9 (512 Q - S^2): x - mean > 1.5 std with the population std, made exact (everything fits i64).
+ *   c. Replacement: if any sample is masked, m = (double)(sum of the unmasked x) / (double)(their number), one
+ *      rounding (the unmasked set is never empty); b[j] = m if j is masked, else (double)x[j].
+ *   d. Filter: F[k] = sinc(w_k / scale) with w_k = k for k < 256 and k - 512 otherwise, sinc(t) = sin(pi t) / (pi t),
+ *      sinc(0) = 1 -- ifftshift(sinc(arange(-256, 256) / scale)) -- built on the host when the stage is configured;
+ *      baseline = Re(IDFT_512(DFT_512(b) * F)) in f64.
+ *   e. Result: y[j] = clamp(x[j] - (int)rint(baseline[j]), -4095, 4095) as int16 (the clamp keeps the priority key of
+ *      step 3, (height + 4096) << 9, inside its domain; |y| could pass 4095 by about 1.6 % at scale 20 in theory, no
+ *      realistic row does).
+ *   f. Steps 2 to 8 of the trace-row contract run on this y.  Pedestals are NOT subtracted: the analysis does not
+ *      know them.  What keeps a trace row is unchanged: that rule is the hardware's zero suppression and still uses
+ *      the pedestal.
+ *   g. Purity: the y of a row and its f64 baseline are functions of that row's 512 samples and of scale alone, bit
+ *      for bit whatever rows share the launch, chunk or call: every row has a transform of its own (two rows are
+ *      never packed into the real and imaginary part of one), and within one build of the library the transform has
+ *      one fixed order of operations.
+ *   h. Exactness: steps a to c and e are exact.  Step d is floating point (fused multiply-adds allowed), so two
+ *      implementations may differ where baseline[j] lies within 1e-6 of a half-integer: there y may differ by 1, and
+ *      nowhere else.  (A forward-error bound for two 512-point f64 transforms of data below 4095 is about 1e-9.)
+ * tests/baseline_reference.py restates a to e in numpy.  The stage costs 1 KiB of device memory per kept trace row of
+ * a chunk while it is on. */
+typedef struct attpc_baseline_desc {
+  double window_scale;  /* finite and > 0; Spyral's default is 20 */
+} attpc_baseline_desc;
+
+/* desc == NULL turns the stage off (the default).  Independent of every other configure call: no call resets another.
+ * ATTPC_E_INVALID unless window_scale is finite and > 0.  Takes effect in attpc_sim_run_trace_rows,
+ * attpc_det_run_trace_rows and attpc_trace_rows_at; no other entry point's output changes. */
+ATTPC_API int32_t attpc_trace_configure_baseline(attpc_ctx* ctx, const attpc_baseline_desc* desc);
+/* The stage alone on any host rows, in the manner of attpc_spyral_rows / attpc_traces: samples [n_rows][512] ->
+ * y [n_rows][512] and, unless NULL, baseline [n_rows][512] (f64, step d).  The same kernel as the fused path; needs no
+ * other configuration and leaves the configured stage as it is.  n_rows = 0 is ATTPC_OK; ATTPC_E_INVALID for a sample
+ * outside 0..4095 or a window_scale that is not finite and > 0.  Any n_rows: the rows go through the device in bounded
+ * chunks. */
+ATTPC_API int32_t attpc_trace_baseline(attpc_ctx* ctx, int64_t n_rows, const int16_t* samples, double window_scale,
+                                       int16_t* y, double* baseline);
 
 /* ---- event and track summaries of a device-resident run (opt-in: without a call of the entry points below every
  * output of every other entry point is what it is without this section) ----

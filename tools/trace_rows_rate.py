@@ -11,11 +11,20 @@ the median of ``--reps`` single timed calls, its spread their minimum and maximu
 per workload and mode, the median and the spread (min .. max) of every leg and the two verdicts:
   (i)  run_traces of this build stays within the spread of the yardstick's, resident and delivered;
   (ii) run_trace_rows delivered is faster than the yardstick's run_traces delivered by more than the spread.
+A library with the Fourier baseline (attpc_trace_configure_baseline) gets one more leg: run_trace_rows resident with
+the stage on (``--baseline-scale``), beside the same call with it off: off before on in the even repeats, on before
+off in the odd ones (``--baseline-first``), so that order, clock and warm-up do not all fall on one side.  When the yardstick has the trace rows too
+(the parent commit of the baseline stage) the driver adds
+  (iii) run_trace_rows resident with the stage off stays within the spread of the yardstick's;
+  and the cost of the stage per event, 1 / rate(on) - 1 / rate(off), from the medians.
+``--modes`` picks the trace modes, ``--resident-only`` leaves the delivered legs out.
 ``--out FILE`` appends the children's JSON lines.
 
     python tools/trace_rows_rate.py [--yardstick attpc_engine_amd/_lib/libattpc_parent.so] [--events N]
                                     [--deliver-events M] [--reps K] [--workloads o16aa,be10dp] [--out FILE]
-    python tools/trace_rows_rate.py --child WORKLOAD   (one measurement of the library ATTPC_HIP_LIBRARY names)
+                                    [--modes hit,partial] [--resident-only] [--baseline-scale S]
+    python tools/trace_rows_rate.py --child WORKLOAD   (one measurement of the library ATTPC_HIP_LIBRARY names, or of
+                                                        the package's own without it)
 """
 from __future__ import annotations
 
@@ -39,7 +48,8 @@ TRACE_ROW_BYTES = 512 * 2 + 4 + 8
 ROW_BYTES = 8 * 8 + 8
 
 
-def child(name: str, events: int, deliver_events: int) -> None:
+def child(name: str, events: int, deliver_events: int, modes, resident_only: bool, baseline_scale: float,
+          baseline_first: bool) -> None:
     from attpc_engine_amd import _abi, workloads
     from attpc_engine_amd.engine import Engine
     from attpc_engine_amd.outputs import RowArrays, TraceArrays
@@ -48,6 +58,7 @@ def child(name: str, events: int, deliver_events: int) -> None:
     lib, seed = ctx.lib, 1
     # (the yardstick is a build of the same ABI version from before the trace rows: the binding loads it without them)
     has_rows = all(hasattr(lib, name) for name in _abi.TRACE_ROW_SYMBOLS)
+    has_baseline = has_rows and all(hasattr(lib, name) for name in _abi.BASELINE_SYMBOLS)
     pipeline, config, indices = workloads.WORKLOADS[name]()
     eng = Engine(pipeline, config, indices, context=ctx)
     if has_rows:
@@ -61,9 +72,10 @@ def child(name: str, events: int, deliver_events: int) -> None:
         result = call(n, n)
         return time.perf_counter() - t0, result
 
-    for mode, kw in MODES.items():
+    for mode in modes:
+        kw = MODES[mode]
         eng.configure_traces(config, **kw)
-        line = {"library": Path(os.environ["ATTPC_HIP_LIBRARY"]).name, "workload": name, "mode": mode,
+        line = {"library": _abi.library_path().name, "workload": name, "mode": mode,
                 "resident_events": events, "delivered_events": deliver_events}
 
         def traces_resident(first, n):
@@ -76,18 +88,19 @@ def child(name: str, events: int, deliver_events: int) -> None:
         per_event = rows / events
         line.update(traces_resident_events_per_s=events / t, trace_rows_per_event=per_event,
                     trace_bytes_per_event=per_event * TRACE_ROW_BYTES)
-        arrays = TraceArrays(deliver_events, int(per_event * deliver_events * 1.3) + 4096, ctx.pinned_empty)
+        if not resident_only:
+            arrays = TraceArrays(deliver_events, int(per_event * deliver_events * 1.3) + 4096, ctx.pinned_empty)
 
-        def traces_delivered(first, n):
-            stats = _abi.RunStats()
-            ctx.check(lib.attpc_sim_run_traces(ctx.handle, seed, first, n, eng.layout, None, None, None, arrays.out, stats),
-                      "attpc_sim_run_traces")
-            return int(arrays.out.n_rows)
+            def traces_delivered(first, n):
+                stats = _abi.RunStats()
+                ctx.check(lib.attpc_sim_run_traces(ctx.handle, seed, first, n, eng.layout, None, None, None, arrays.out, stats),
+                          "attpc_sim_run_traces")
+                return int(arrays.out.n_rows)
 
-        t, rows = timed(traces_delivered, deliver_events)
-        line.update(traces_delivered_events_per_s=deliver_events / t,
-                    traces_delivered_GB_per_s=rows * TRACE_ROW_BYTES / t / 1e9)
-        del arrays
+            t, rows = timed(traces_delivered, deliver_events)
+            line.update(traces_delivered_events_per_s=deliver_events / t,
+                        traces_delivered_GB_per_s=rows * TRACE_ROW_BYTES / t / 1e9)
+            del arrays
         if has_rows:
             def rows_resident(first, n):
                 out, stats = _abi.CloudOut(), _abi.RunStats()
@@ -95,21 +108,33 @@ def child(name: str, events: int, deliver_events: int) -> None:
                           "attpc_sim_run_trace_rows")
                 return int(stats.n_points)
 
+            def baseline_leg():  # the same call with the Fourier baseline on, then off again for what follows
+                eng.configure_baseline(window_scale=baseline_scale)
+                t, rows = timed(rows_resident, events)
+                eng.configure_baseline(None)
+                line.update(rows_baseline_resident_events_per_s=events / t, rows_baseline_per_event=rows / events,
+                            baseline_scale=baseline_scale, baseline_first=baseline_first)
+
+            if has_baseline and baseline_first:
+                baseline_leg()
             t, rows = timed(rows_resident, events)
             per_event = rows / events
             line.update(rows_resident_events_per_s=events / t, rows_per_event=per_event,
                         row_bytes_per_event=per_event * ROW_BYTES)
-            row_arrays = RowArrays(deliver_events, int(per_event * deliver_events * 1.3) + 4096, ctx.pinned_empty, width=8)
+            if has_baseline and not baseline_first:
+                baseline_leg()
+            if not resident_only:
+                row_arrays = RowArrays(deliver_events, int(per_event * deliver_events * 1.3) + 4096, ctx.pinned_empty, width=8)
 
-            def rows_delivered(first, n):
-                stats = _abi.RunStats()
-                ctx.check(lib.attpc_sim_run_trace_rows(ctx.handle, seed, first, n, eng.layout, None, None, None,
-                                                       row_arrays.out, stats), "attpc_sim_run_trace_rows")
-                return int(stats.n_points)
+                def rows_delivered(first, n):
+                    stats = _abi.RunStats()
+                    ctx.check(lib.attpc_sim_run_trace_rows(ctx.handle, seed, first, n, eng.layout, None, None, None,
+                                                           row_arrays.out, stats), "attpc_sim_run_trace_rows")
+                    return int(stats.n_points)
 
-            t, rows = timed(rows_delivered, deliver_events)
-            line.update(rows_delivered_events_per_s=deliver_events / t, rows_delivered_GB_per_s=rows * ROW_BYTES / t / 1e9)
-            del row_arrays
+                t, rows = timed(rows_delivered, deliver_events)
+                line.update(rows_delivered_events_per_s=deliver_events / t, rows_delivered_GB_per_s=rows * ROW_BYTES / t / 1e9)
+                del row_arrays
         print(json.dumps(line), flush=True)
     ctx.close()
 
@@ -128,9 +153,17 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--workloads", default="o16aa,be10dp")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--modes", default=",".join(MODES))
+    ap.add_argument("--resident-only", action="store_true")
+    ap.add_argument("--baseline-scale", type=float, default=20.0)
+    ap.add_argument("--baseline-first", action="store_true", help="child: the baseline leg before the leg without it")
     args = ap.parse_args()
+    modes = args.modes.split(",")
+    if any(m not in MODES for m in modes):
+        raise SystemExit(f"--modes takes {list(MODES)}")
     if args.child:
-        child(args.child, args.events, args.deliver_events)
+        child(args.child, args.events, args.deliver_events, modes, args.resident_only, args.baseline_scale,
+              args.baseline_first)
         return
 
     new = ROOT / "attpc_engine_amd" / "_lib" / "libattpc_hip.so"
@@ -144,14 +177,18 @@ def main() -> None:
             for name in args.workloads.split(","):
                 env = dict(os.environ, ATTPC_HIP_LIBRARY=str(lib))
                 proc = subprocess.run([sys.executable, __file__, "--child", name, "--events", str(args.events),
-                                       "--deliver-events", str(args.deliver_events)], env=env, capture_output=True,
+                                       "--deliver-events", str(args.deliver_events), "--modes", args.modes,
+                                       "--baseline-scale", str(args.baseline_scale)]
+                                      + (["--resident-only"] if args.resident_only else [])
+                                      + (["--baseline-first"] if rep % 2 else []), env=env, capture_output=True,
                                       text=True, timeout=300)
                 if proc.returncode != 0:  # nothing more is started on the GPU after a failure
                     sys.stderr.write(proc.stdout + proc.stderr)
                     raise SystemExit(f"{lib.name} / {name} ended with status {proc.returncode}")
                 for text in proc.stdout.splitlines():
                     if text.startswith("{"):
-                        line = dict(json.loads(text), rep=rep)
+                        # (the side, not the file name, tells the libraries apart: both may be a libattpc_hip.so)
+                        line = dict(json.loads(text), rep=rep, side="yardstick" if lib is libraries[0] else "new")
                         lines.append(line)
                         print(json.dumps(line), flush=True)
     if args.out:
@@ -161,24 +198,34 @@ def main() -> None:
     yard = libraries[0].name
     print(f"\nmedian (min .. max) of {args.reps} alternating repeats, events/s; yardstick = {yard}")
     for name in args.workloads.split(","):
-        for mode in MODES:
+        for mode in modes:
             def leg(lib, key):
-                return [ln[key] for ln in lines if (ln["library"], ln["workload"], ln["mode"]) == (lib, name, mode)]
+                return [ln[key] for ln in lines if (ln["side"], ln["workload"], ln["mode"]) == (lib, name, mode)
+                        and key in ln]
 
-            some = next(ln for ln in lines if (ln["library"], ln["workload"], ln["mode"]) == (new.name, name, mode))
+            some = next(ln for ln in lines if (ln["side"], ln["workload"], ln["mode"]) == ("new", name, mode))
             print(f"{name} / {mode}: {some['trace_rows_per_event']:.1f} trace rows = {some['trace_bytes_per_event'] / 1e3:.1f} KB"
                   f" per event; {some['rows_per_event']:.1f} rows = {some['row_bytes_per_event'] / 1e3:.1f} KB per event")
             verdicts = []
-            for what in ("resident", "delivered"):
+            for what in ("resident",) if args.resident_only else ("resident", "delivered"):
                 key = f"traces_{what}_events_per_s"
-                (ym, ylo, yhi), (nm, nlo, nhi) = _spread(leg(yard, key)), _spread(leg(new.name, key))
-                rm, rlo, rhi = _spread(leg(new.name, f"rows_{what}_events_per_s"))
+                (ym, ylo, yhi), (nm, nlo, nhi) = _spread(leg("yardstick", key)), _spread(leg("new", key))
+                rm, rlo, rhi = _spread(leg("new", f"rows_{what}_events_per_s"))
                 print(f"  {what:9s} traces yardstick {ym:10.0f} ({ylo:.0f} .. {yhi:.0f})   traces {nm:10.0f} ({nlo:.0f} .. {nhi:.0f})"
                       f"   rows {rm:10.0f} ({rlo:.0f} .. {rhi:.0f})")
                 verdicts.append(f"(i) {what}: {'within' if nhi >= ylo and nlo <= yhi else 'OUTSIDE'} the spread")
                 if what == "delivered":
                     verdicts.append(f"(ii) rows delivered {'faster than' if rlo > yhi else 'NOT faster than'} the yardstick's"
                                     f" traces delivered by more than the spread ({rm / ym:.2f}x)")
+            off, on = leg("new", "rows_resident_events_per_s"), leg("new", "rows_baseline_resident_events_per_s")
+            yard_rows = leg("yardstick", "rows_resident_events_per_s")
+            if yard_rows:
+                (ym, ylo, yhi), (nm, nlo, nhi) = _spread(yard_rows), _spread(off)
+                print(f"  resident  rows yardstick {ym:10.0f} ({ylo:.0f} .. {yhi:.0f})   rows, baseline off {nm:10.0f} ({nlo:.0f} .. {nhi:.0f})")
+                verdicts.append(f"(iii) rows resident, baseline off: {'within' if nhi >= ylo and nlo <= yhi else 'OUTSIDE'} the spread")
+            if on:
+                (fm, flo, fhi), (nm, _, _) = _spread(on), _spread(off)
+                print(f"  resident  rows, baseline on {fm:10.0f} ({flo:.0f} .. {fhi:.0f}): {1e6 / fm - 1e6 / nm:+.2f} us per event")
             print("  " + "; ".join(verdicts))
 
 
