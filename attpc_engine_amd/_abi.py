@@ -140,6 +140,25 @@ class BaselineDesc(C.Structure):
     _fields_ = [("window_scale", C.c_double)]
 
 
+class TriggerDesc(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("window", C.c_int32), ("group_multiplicity", C.c_int32),
+                ("min_groups", C.c_int32), ("groups", C.POINTER(C.c_uint8)), ("gate", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TriggerRecord(C.Structure):
+    _fields_ = [("fired", C.c_int32), ("sample", C.c_int32), ("groups", C.c_uint32), ("n_rows", C.c_int32),
+                ("n_hit_pads", C.c_int32), ("peak_group_sum", C.c_int32), ("peak_sum", C.c_int32),
+                ("peak_sample", C.c_int32)]
+
+
+# the trigger record as a numpy structured dtype: itemsize and field offsets are those of include/attpc_engine.h
+TRIGGER_DTYPE = np.dtype([("fired", "<i4"), ("sample", "<i4"), ("groups", "<u4"), ("n_rows", "<i4"), ("n_hit_pads", "<i4"),
+                          ("peak_group_sum", "<i4"), ("peak_sum", "<i4"), ("peak_sample", "<i4")], align=True)
+assert TRIGGER_DTYPE.itemsize == C.sizeof(TriggerRecord) == 32
+assert all(TRIGGER_DTYPE.fields[name][1] == getattr(TriggerRecord, name).offset for name, _ in TriggerRecord._fields_)
+MAX_TRIGGER_GROUPS = 16
+
+
 class EventSummary(C.Structure):
     _fields_ = [("n_points", C.c_uint32), ("n_kept", C.c_uint32), ("n_pads", C.c_uint32), ("tb_min", C.c_int32),
                 ("tb_max", C.c_int32), ("reserved", C.c_int32), ("charge", C.c_int64)]
@@ -283,6 +302,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_noise", "attpc_traces_at", "attpc_trace_configure_readout",
     "attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows", "attpc_trace_rows_at",
     "attpc_trace_rows_last", "attpc_trace_configure_baseline", "attpc_trace_baseline",
+    "attpc_trace_configure_trigger", "attpc_trigger_last", "attpc_trigger_rows",
     "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
     "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
 )
@@ -301,6 +321,9 @@ SELECT_SYMBOLS = ("attpc_select_configure", "attpc_sim_run_selected", "attpc_det
 
 # ... and the Fourier baseline of the trace rows after the selected delivery: the same rule.
 BASELINE_SYMBOLS = ("attpc_trace_configure_baseline", "attpc_trace_baseline")
+
+# ... and the multiplicity trigger of the traces after the Fourier baseline: the same rule.
+TRIGGER_SYMBOLS = ("attpc_trace_configure_trigger", "attpc_trigger_last", "attpc_trigger_rows")
 
 _lib = None
 
@@ -415,6 +438,16 @@ def load_library() -> C.CDLL:
     for name, argtypes in baseline.items():
         if not no_baseline:
             getattr(lib, name).argtypes = argtypes
+    trigger = {
+        "attpc_trace_configure_trigger": [ctxp, C.POINTER(TriggerDesc)],
+        "attpc_trigger_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(TriggerRecord)],
+        "attpc_trigger_rows": [ctxp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int16),
+                               C.POINTER(C.c_int16), C.POINTER(TriggerDesc), C.POINTER(TriggerRecord)],
+    }
+    no_trigger = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in TRIGGER_SYMBOLS)
+    for name, argtypes in trigger.items():
+        if not no_trigger:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -436,7 +469,8 @@ def load_library() -> C.CDLL:
     ]
     for name in EXPORTED_SYMBOLS:
         if ((older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS)
-                or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)):
+                or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)
+                or (no_trigger and name in TRIGGER_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -445,7 +479,7 @@ def load_library() -> C.CDLL:
     return lib
 
 
-CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks", "baseline", "summary", "select")
+CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks", "baseline", "trigger", "summary", "select")
 
 
 class Context:
@@ -502,6 +536,13 @@ class Context:
         n_rows, checksum = C.c_int64(), C.c_uint64()
         self.check(self.lib.attpc_trace_rows_last(self.handle, C.byref(n_rows), C.byref(checksum)), "attpc_trace_rows_last")
         return {"n_rows": int(n_rows.value), "row_checksum": int(checksum.value)}
+
+    def trigger_last(self, n_events: int) -> np.ndarray:
+        """The trigger records [n_events] (``TRIGGER_DTYPE``) of this context's last trace or trace-row call
+        (``attpc_trigger_last``); RuntimeError if no trigger was configured for it."""
+        records = np.empty(int(n_events), dtype=TRIGGER_DTYPE)
+        self.check(self.lib.attpc_trigger_last(self.handle, 0, len(records), iptr(records, TriggerRecord)), "attpc_trigger_last")
+        return records
 
     def set_option(self, name: str, value: int) -> None:
         """Tuning / test switches of the context (``attpc_set_option``)."""

@@ -88,6 +88,8 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf pk_maps, pk_counts, pk_row_start, pk_block_sums, pk_block_start, pk_ev_start, pk_records, pk_centroid;
   size_t pk_cap = 0;           // points the point-sized buffers are kept at (grown with headroom)
   DevBuf pk_y;                 // Fourier baseline on (baseline.hip): the y rows the peak kernels read, int16 [traces][512]
+  DevBuf tg_records;           // trigger on (trigger.hip): the chunk's records, attpc_trigger_record [events]
+  DevBuf tg_row_pass;          // ... with its gate, trace rows: fired of every kept trace row's event, uint8 [traces]
   Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
   size_t row_cap = 0;  // rows the row-sized buffers of the set are kept at (grown with headroom: a launch's row
                        // capacity follows the observed rows per event and moves by fractions of a percent)
@@ -202,6 +204,13 @@ struct attpc_ctx {
   DevBuf bl_filter;                // [512] the configured filter in the transform's order
   DevBuf bl_op_filter;             // [512] the filter of attpc_trace_baseline's last call,
   double bl_op_scale = 0.0;        // and its window scale (0: none yet): a call with the same scale uploads nothing
+  bool trigger_on = false;         // attpc_trace_configure_trigger
+  TriggerDev trigger{};
+  bool trigger_gate = false;
+  DevBuf tg_groups;                // [ATTPC_NUM_PADS] the configured group map (trigger.groups points here, or is nullptr)
+  DevBuf tg_op_groups;             // [ATTPC_NUM_PADS] the map of attpc_trigger_rows' last call
+  Pinned<attpc_trigger_record> h_trigger;  // records of the last trace or trace-row call, in its event order
+  int64_t trigger_call_events = -1;        // events of that call, -1: it had no trigger configured (or there was none)
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -904,6 +913,42 @@ int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t tota
   return ATTPC_OK;
 }
 
+// The start of a trace or trace-row call of `n` events: room for its trigger records (attpc_trigger_last), if a trigger
+// is configured.  Nothing of an earlier call is in flight.
+int32_t begin_trigger_call(attpc_ctx* ctx, uint64_t n) {
+  ctx->trigger_call_events = -1;
+  if (!ctx->trigger_on) return ATTPC_OK;
+  const int32_t rc = ensure_pinned(ctx, ctx->h_trigger, std::max<size_t>((size_t)n, 1));
+  if (rc) return rc;
+  ctx->trigger_call_events = (int64_t)n;
+  return ATTPC_OK;
+}
+
+// The trigger of the chunk in `as` (n events, `total` kept rows, written: directly behind enqueue_trace_write) on S --
+// with `gate` the pass byte of every kept row too --, as.traced recorded again behind it, and the copy of the records
+// to events first_local .. of the call's pinned array on C.
+int32_t enqueue_trigger(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t total, uint64_t first_local, bool gate) {
+  if (!n) return ATTPC_OK;
+  int32_t rc;
+  if ((rc = ensure(ctx, as.tg_records, (size_t)n * sizeof(attpc_trigger_record)))) return rc;
+  if (gate && (rc = ensure(ctx, as.tg_row_pass, std::max<size_t>(as.tr_cap, (size_t)std::max<int64_t>(total, 1))))) return rc;
+  TriggerArgs a{};
+  a.tg = ctx->trigger;
+  a.pedestals = ctx->noise_on ? ctx->noise.pedestals : nullptr;
+  a.kept_start = static_cast<const int64_t*>(as.kept_start.p);
+  a.pads = static_cast<const int32_t*>(as.tr_pads.p);
+  a.samples = static_cast<const int16_t*>(as.tr_samples.p);
+  a.records = static_cast<attpc_trigger_record*>(as.tg_records.p);
+  a.row_pass = gate ? static_cast<uint8_t*>(as.tg_row_pass.p) : nullptr;
+  launch_trigger(ctx->stream, n, a);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_trigger.p + first_local, as.tg_records.p, (size_t)n * sizeof(attpc_trigger_record),
+                              hipMemcpyDeviceToHost, ctx->stream_c));
+  return ATTPC_OK;
+}
+
 // Queue the copies of the written traces of `as` (rows base .. base + total of the caller's arrays; any array may be
 // NULL) on C behind as.traced, then record as.copied.
 int32_t copy_traces(attpc_ctx* ctx, AsmSet& as, int64_t total, int64_t base, const attpc_trace_out* out, bool fits) {
@@ -1167,6 +1212,7 @@ int32_t deliver(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t firs
   if (n) ctx->trace_rows_per_event = std::max((double)total / (double)n, 1.0e-3);
   int32_t rc;
   if ((rc = enqueue_trace_write(ctx, as, n, total, seed, first_global))) return rc;
+  if (ctx->trigger_on && (rc = enqueue_trigger(ctx, as, n, total, first_local, false))) return rc;
   return copy_traces(ctx, as, total, base, o.trace, fits);
 }
 
@@ -1180,6 +1226,9 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
   if (n) ctx->trace_rows_per_event = std::max((double)traces / (double)n, 1.0e-3);
   int32_t rc;
   if ((rc = enqueue_trace_write(ctx, as, n, traces, seed, first_global))) return rc;
+  const bool gated = ctx->trigger_on && ctx->trigger_gate;
+  if (ctx->trigger_on && (rc = enqueue_trigger(ctx, as, n, traces, first_local, gated))) return rc;
+  const uint8_t* row_pass = gated ? static_cast<const uint8_t*>(as.tg_row_pass.p) : nullptr;
   const size_t tr = (size_t)std::max<int64_t>(traces, 1);
   if ((rc = ensure(ctx, as.pk_maps, tr * 64))) return rc;
   if ((rc = ensure(ctx, as.pk_counts, tr * sizeof(uint32_t)))) return rc;
@@ -1201,7 +1250,7 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
   }
   if (traces > 0) {
     launch_peak_count(ctx->stream, ctx->peaks, pedestals, (uint32_t)traces, d_pads, d_samples,
-                      static_cast<uint8_t*>(as.pk_maps.p), static_cast<uint32_t*>(as.pk_counts.p));
+                      static_cast<uint8_t*>(as.pk_maps.p), static_cast<uint32_t*>(as.pk_counts.p), row_pass);
     HIP_TRY(ctx, hipGetLastError());
   }
   if (traces > 0) {
@@ -1239,7 +1288,7 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
     if ((rc = ensure(ctx, as.sp_labels, as.pk_cap * sizeof(int64_t)))) return rc;
     launch_peak_write(ctx->stream, ctx->peaks, pedestals, (uint32_t)traces, d_pads, d_samples,
                       static_cast<const uint8_t*>(as.pk_maps.p), static_cast<const int64_t*>(as.pk_row_start.p),
-                      static_cast<uint4*>(as.pk_records.p));
+                      static_cast<uint4*>(as.pk_records.p), row_pass);
     HIP_TRY(ctx, hipGetLastError());
     launch_peak_rows(ctx->stream, ctx->spyral, seed, n, first_global, static_cast<const int64_t*>(as.pk_ev_start.p),
                      static_cast<const uint4*>(as.pk_records.p), d_pads, static_cast<const int64_t*>(as.tr_labels.p),
@@ -1656,6 +1705,7 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   int32_t rc;
   if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
   if (makes_traces(o.mode) && (rc = reset_trace_sums(ctx, o.mode))) return rc;
+  if (makes_traces(o.mode) && (rc = begin_trigger_call(ctx, n_events))) return rc;
   // a readout run sizes its trace chunks for |S| rows per event until it has seen its own rate: the rate of an earlier
   // run says nothing once the threshold, the noise or the workload has changed (hit mode keeps the context's rate)
   if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT) ctx->trace_rows_per_event = 0.0;
@@ -2396,6 +2446,7 @@ int32_t host_cloud_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int6
   if ((rc = drop_prefetch(ctx))) return rc;
   if ((rc = sync_all(ctx))) return rc;
   if ((rc = reset_trace_sums(ctx, o.mode))) return rc;
+  if ((rc = begin_trigger_call(ctx, n))) return rc;
   const double keep = ctx->trace_rows_per_event;  // a host cloud says nothing about the configured workload
   rc = trace_host_events(ctx, o, 0, n, offsets, points, labels, seed, first_event);
   ctx->trace_rows_per_event = keep;
@@ -2663,6 +2714,132 @@ int32_t attpc_trace_baseline(attpc_ctx* ctx, int64_t n_rows, const int16_t* samp
       HIP_TRY(ctx, hipMemcpyAsync(baseline + first * ATTPC_NUM_TB, ctx->scratch[2].p, n * ATTPC_NUM_TB * sizeof(double),
                                   hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return ATTPC_OK;
+}
+
+// ---- multiplicity trigger on the pad traces (trigger.hip; the contract is in include/attpc_engine.h) ----
+namespace {
+// The checks of an attpc_trigger_desc, and its group map on the device in `buf`: the kernel's parameters in *tg.
+int32_t upload_trigger(attpc_ctx* ctx, const attpc_trigger_desc* d, DevBuf& buf, TriggerDev* tg) {
+  if (d->threshold < 0 || d->threshold > 4095) return fail(ctx, ATTPC_E_INVALID, "trigger threshold %d: 0 .. 4095", d->threshold);
+  if (d->window < 1 || d->window > ATTPC_NUM_TB) return fail(ctx, ATTPC_E_INVALID, "trigger window %d: 1 .. %d", d->window, ATTPC_NUM_TB);
+  if (d->group_multiplicity < 1) return fail(ctx, ATTPC_E_INVALID, "trigger group_multiplicity %d: >= 1", d->group_multiplicity);
+  if (d->min_groups < 1 || d->min_groups > ATTPC_MAX_TRIGGER_GROUPS)
+    return fail(ctx, ATTPC_E_INVALID, "trigger min_groups %d: 1 .. %d", d->min_groups, ATTPC_MAX_TRIGGER_GROUPS);
+  if (d->gate != 0 && d->gate != 1) return fail(ctx, ATTPC_E_INVALID, "trigger gate %d: 0 or 1", d->gate);
+  if (d->reserved != 0) return fail(ctx, ATTPC_E_INVALID, "trigger reserved %d: 0", d->reserved);
+  int n_groups = 1;
+  if (d->groups)
+    for (int p = 0; p < ATTPC_NUM_PADS; ++p) {
+      const int g = d->groups[p];
+      if (g >= ATTPC_MAX_TRIGGER_GROUPS && g != 255)
+        return fail(ctx, ATTPC_E_INVALID, "trigger group %d of pad %d: below %d, or 255", g, p, ATTPC_MAX_TRIGGER_GROUPS);
+      if (g != 255) n_groups = std::max(n_groups, g + 1);
+    }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  if (d->groups) {
+    if ((rc = ensure(ctx, buf, ATTPC_NUM_PADS))) return rc;
+    HIP_TRY(ctx, hipMemcpy(buf.p, d->groups, ATTPC_NUM_PADS, hipMemcpyHostToDevice));
+  }
+  *tg = TriggerDev{d->threshold, d->window, d->group_multiplicity, d->min_groups, n_groups,
+                   d->groups ? static_cast<const uint8_t*>(buf.p) : nullptr};
+  return ATTPC_OK;
+}
+}  // namespace
+
+int32_t attpc_trace_configure_trigger(attpc_ctx* ctx, const attpc_trigger_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (!d) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+    ctx->trigger_on = false;
+    return ATTPC_OK;
+  }
+  TriggerDev tg{};
+  const int32_t rc = upload_trigger(ctx, d, ctx->tg_groups, &tg);  // (a refused desc leaves the configured one as it is:
+  if (rc) return rc;                                               //  the checks come before the upload)
+  ctx->trigger = tg;
+  ctx->trigger_gate = d->gate != 0;
+  ctx->trigger_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_trigger_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_trigger_record* out) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->trigger_call_events < 0)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trigger_last: no trigger was configured for the last trace call");
+  if (first < 0 || count < 0 || first > ctx->trigger_call_events || count > ctx->trigger_call_events - first)
+    return fail(ctx, ATTPC_E_INVALID, "attpc_trigger_last: records %lld .. + %lld of a call of %lld events", (long long)first,
+                (long long)count, (long long)ctx->trigger_call_events);
+  if (count == 0) return ATTPC_OK;
+  if (!out) return ATTPC_E_INVALID;
+  std::memcpy(out, ctx->h_trigger.p + first, (size_t)count * sizeof(attpc_trigger_record));
+  return ATTPC_OK;
+}
+
+int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const int32_t* pads, const int16_t* samples,
+                           const int16_t* pedestals, const attpc_trigger_desc* d, attpc_trigger_record* out) {
+  if (!ctx || n_events < 0 || !d) return ATTPC_E_INVALID;
+  if (n_events > 0 && (!offsets || !out)) return ATTPC_E_INVALID;
+  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_trigger_rows takes at most 2^31 - 1 events per call");
+  if (n_events > 0 && offsets[0] < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
+  for (int64_t e = 0; e < n_events; ++e) {
+    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %lld", (long long)e);
+    if (offsets[e + 1] - offsets[e] > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "event %lld has 2^31 rows or more", (long long)e);
+  }
+  const int64_t r0 = n_events ? offsets[0] : 0, r1 = n_events ? offsets[n_events] : 0;
+  if (r1 > r0 && (!pads || !samples)) return ATTPC_E_INVALID;
+  for (int64_t r = r0; r < r1; ++r)
+    if (pads[r] < 0 || pads[r] >= ATTPC_NUM_PADS)
+      return fail(ctx, ATTPC_E_INVALID, "row %lld: pad %d outside 0 .. %d", (long long)r, pads[r], ATTPC_NUM_PADS - 1);
+  for (int64_t i = r0 * ATTPC_NUM_TB; i < r1 * ATTPC_NUM_TB; ++i)
+    if (samples[i] < 0 || samples[i] > 4095)
+      return fail(ctx, ATTPC_E_INVALID, "sample %lld of row %lld is %d: 0 .. 4095", (long long)(i % ATTPC_NUM_TB),
+                  (long long)(i / ATTPC_NUM_TB), (int)samples[i]);
+  if (pedestals)
+    for (int p = 0; p < ATTPC_NUM_PADS; ++p)
+      if (pedestals[p] < 0 || pedestals[p] > 4095)
+        return fail(ctx, ATTPC_E_INVALID, "pedestal %d of pad %d: 0 .. 4095", (int)pedestals[p], p);
+  TriggerArgs a{};
+  int32_t rc;
+  if ((rc = upload_trigger(ctx, d, ctx->tg_op_groups, &a.tg))) return rc;  // (checks, device, sync_all)
+  if (n_events == 0) return ATTPC_OK;
+  if (pedestals) {
+    if ((rc = ensure(ctx, ctx->scratch[4], ATTPC_NUM_PADS * sizeof(int16_t)))) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->scratch[4].p, pedestals, ATTPC_NUM_PADS * sizeof(int16_t), hipMemcpyHostToDevice));
+    a.pedestals = static_cast<const int16_t*>(ctx->scratch[4].p);
+  }
+  constexpr int64_t CHUNK_ROWS = 16384, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
+  std::vector<int64_t> start;
+  for (int64_t e0 = 0; e0 < n_events;) {
+    int64_t e1 = e0 + 1;
+    while (e1 < n_events && e1 - e0 < CHUNK_EVENTS && offsets[e1 + 1] - offsets[e0] <= CHUNK_ROWS) ++e1;
+    const size_t m = (size_t)(e1 - e0), rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(rows, 1);
+    start.resize(m + 1);
+    for (size_t e = 0; e <= m; ++e) start[e] = offsets[e0 + (int64_t)e] - offsets[e0];
+    if ((rc = ensure(ctx, ctx->scratch[0], cap * ATTPC_NUM_TB * sizeof(int16_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[1], cap * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[2], (m + 1) * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[3], m * sizeof(attpc_trigger_record)))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, start.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (rows) {
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, samples + offsets[e0] * ATTPC_NUM_TB, rows * ATTPC_NUM_TB * sizeof(int16_t),
+                                  hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, pads + offsets[e0], rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    a.kept_start = static_cast<const int64_t*>(ctx->scratch[2].p);
+    a.pads = static_cast<const int32_t*>(ctx->scratch[1].p);
+    a.samples = static_cast<const int16_t*>(ctx->scratch[0].p);
+    a.records = static_cast<attpc_trigger_record*>(ctx->scratch[3].p);
+    a.row_pass = nullptr;
+    launch_trigger(ctx->stream, (uint32_t)m, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out + e0, ctx->scratch[3].p, m * sizeof(attpc_trigger_record), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    e0 = e1;
   }
   return ATTPC_OK;
 }

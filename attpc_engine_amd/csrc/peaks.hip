@@ -126,12 +126,18 @@ __device__ __forceinline__ bool peak_passes(const short* y, const int (&v)[8], i
 __global__ __launch_bounds__(64) void peak_count_kernel(PeakDev pk, const int16_t* __restrict__ pedestals,
                                                          const int32_t* __restrict__ pads,
                                                          const int16_t* __restrict__ samples, uint8_t* __restrict__ maps,
-                                                         uint32_t* __restrict__ counts) {
+                                                         uint32_t* __restrict__ counts,
+                                                         const uint8_t* __restrict__ row_pass) {
   __shared__ short y[ATTPC_NUM_TB];
   __shared__ int prio[ATTPC_NUM_TB];  // candidate at sample j: (height + 4096) << 9 | j (| PK_KEPT), else 0
   __shared__ int block_max[64];       // the largest entry of every lane's eight
   const int64_t row = blockIdx.x;
   const int lane = (int)threadIdx.x;
+  if (row_pass && !row_pass[row]) {  // uniform: the row's event did not fire (the trigger's gate), no points
+    maps[row * 64 + lane] = 0;
+    if (lane == 0) counts[row] = 0u;
+    return;
+  }
   const int ped = pedestals ? (int)pedestals[pads[row]] : 0;
   load_row(y, samples, row, ped, lane);
 #pragma unroll
@@ -216,10 +222,12 @@ __global__ __launch_bounds__(64) void peak_write_kernel(PeakDev pk, const int16_
                                                          const int32_t* __restrict__ pads,
                                                          const int16_t* __restrict__ samples,
                                                          const uint8_t* __restrict__ maps,
-                                                         const int64_t* __restrict__ row_start, uint4* __restrict__ records) {
+                                                         const int64_t* __restrict__ row_start, uint4* __restrict__ records,
+                                                         const uint8_t* __restrict__ row_pass) {
   __shared__ short y[ATTPC_NUM_TB];
   const int64_t row = blockIdx.x;
   const int lane = (int)threadIdx.x;
+  if (row_pass && !row_pass[row]) return;  // uniform (such a row has no points either: the count pass left none)
   int64_t o = row_start[row];
   if (row_start[row + 1] == o) return;  // uniform
   const int ped = pedestals ? (int)pedestals[pads[row]] : 0;
@@ -433,8 +441,8 @@ __global__ __launch_bounds__(PK_ROWS_THREADS) void peak_rows_kernel(SpyralDev sp
 }
 
 void launch_peak_count(hipStream_t s, const PeakDev& pk, const int16_t* pedestals, uint32_t n_rows, const int32_t* pads,
-                       const int16_t* samples, uint8_t* maps, uint32_t* counts) {
-  hipLaunchKernelGGL(peak_count_kernel, dim3(n_rows), dim3(64), 0, s, pk, pedestals, pads, samples, maps, counts);
+                       const int16_t* samples, uint8_t* maps, uint32_t* counts, const uint8_t* row_pass) {
+  hipLaunchKernelGGL(peak_count_kernel, dim3(n_rows), dim3(64), 0, s, pk, pedestals, pads, samples, maps, counts, row_pass);
 }
 uint32_t peak_scan_blocks(uint32_t n_rows) { return (n_rows + (uint32_t)PK_SCAN_ITEMS - 1u) / (uint32_t)PK_SCAN_ITEMS; }
 void launch_peak_scan(hipStream_t s, const uint32_t* counts, uint32_t n_rows, int64_t* row_start, uint32_t* block_sums,
@@ -450,8 +458,10 @@ void launch_peak_event_start(hipStream_t s, uint32_t n_events, const int64_t* ke
                      ev_start);
 }
 void launch_peak_write(hipStream_t s, const PeakDev& pk, const int16_t* pedestals, uint32_t n_rows, const int32_t* pads,
-                       const int16_t* samples, const uint8_t* maps, const int64_t* row_start, uint4* records) {
-  hipLaunchKernelGGL(peak_write_kernel, dim3(n_rows), dim3(64), 0, s, pk, pedestals, pads, samples, maps, row_start, records);
+                       const int16_t* samples, const uint8_t* maps, const int64_t* row_start, uint4* records,
+                       const uint8_t* row_pass) {
+  hipLaunchKernelGGL(peak_write_kernel, dim3(n_rows), dim3(64), 0, s, pk, pedestals, pads, samples, maps, row_start, records,
+                     row_pass);
 }
 void launch_peak_rows(hipStream_t s, const SpyralDev& sp, uint64_t seed, uint32_t n_events, uint64_t first_event,
                       const int64_t* ev_start, const uint4* records, const int32_t* pads, const int64_t* labels,

@@ -146,9 +146,10 @@ struct PeakDev {
   double prominence, min_width, max_width, rel_height, threshold;
 };
 // per kept trace row (pads / samples as the trace write pass left them; pedestals nullptr = zeros): maps [rows][64],
-// bit s of byte l = sample 8 l + s is a point; counts [rows] their number
+// bit s of byte l = sample 8 l + s is a point; counts [rows] their number.  row_pass [rows] (the trigger's gate,
+// trigger.hip): a row whose byte is 0 has no points; nullptr = every row
 void launch_peak_count(hipStream_t s, const PeakDev& pk, const int16_t* pedestals, uint32_t n_rows, const int32_t* pads,
-                       const int16_t* samples, uint8_t* maps, uint32_t* counts);
+                       const int16_t* samples, uint8_t* maps, uint32_t* counts, const uint8_t* row_pass = nullptr);
 // row_start [n_rows + 1] = exclusive scan of counts [n_rows], n_rows > 0; block_sums [peak_scan_blocks(n_rows)] and
 // block_start [peak_scan_blocks(n_rows) + 1]: scratch
 uint32_t peak_scan_blocks(uint32_t n_rows);
@@ -159,7 +160,8 @@ void launch_peak_event_start(hipStream_t s, uint32_t n_events, const int64_t* ke
                              int64_t* ev_start);
 // records [points]: (trace row, sample, amplitude, integral) of every point, at row_start[row] in ascending sample
 void launch_peak_write(hipStream_t s, const PeakDev& pk, const int16_t* pedestals, uint32_t n_rows, const int32_t* pads,
-                       const int16_t* samples, const uint8_t* maps, const int64_t* row_start, uint4* records);
+                       const int16_t* samples, const uint8_t* maps, const int64_t* row_start, uint4* records,
+                       const uint8_t* row_pass = nullptr);
 // rows [points][8] / out_labels in the contract's order per event (ev_start: CSR offsets of the events' points);
 // centroid / sort_idx / sort_key: scratch of one entry per point; sums[0] += the row checksum (event = first_event + e)
 void launch_peak_rows(hipStream_t s, const SpyralDev& sp, uint64_t seed, uint32_t n_events, uint64_t first_event,
@@ -172,6 +174,25 @@ void launch_peak_rows(hipStream_t s, const SpyralDev& sp, uint64_t seed, uint32_
 // (entry 64 k2 + 8 k0 + k1 is F[k0 + 8 k1 + 64 k2]), baseline [n_rows][512] f64 or nullptr
 void launch_baseline(hipStream_t s, uint32_t n_rows, const int16_t* samples, const double2* twiddle, const double* filter,
                      int16_t* y, double* baseline);
+
+// multiplicity trigger on the kept trace rows (trigger.hip; attpc_trace_configure_trigger, the contract is in
+// include/attpc_engine.h)
+struct TriggerDev {
+  int32_t threshold, window, group_multiplicity, min_groups;
+  int32_t n_groups;       // 1 + the highest group of the map (1 without a map): what the kernel clears and scans
+  const uint8_t* groups;  // [ATTPC_NUM_PADS] on the device, or nullptr = every pad in group 0
+};
+struct TriggerArgs {
+  TriggerDev tg;
+  const int16_t* pedestals;       // [ATTPC_NUM_PADS] or nullptr = zeros
+  const int64_t* kept_start;      // [n_events + 1] CSR offsets of the events' rows
+  const int32_t* pads;            // [rows]
+  const int16_t* samples;         // [rows][512]
+  attpc_trigger_record* records;  // [n_events]
+  uint8_t* row_pass;              // [rows] fired of the row's event (the gate of the peak passes), or nullptr
+};
+// one workgroup per event, empty events included
+void launch_trigger(hipStream_t s, uint32_t n_events, const TriggerArgs& a);
 
 // event and track summaries of a scattered chunk (summary.hip; attpc_summary_configure, the contract is in
 // include/attpc_engine.h).  The rows are read in place through the launch's segment list.

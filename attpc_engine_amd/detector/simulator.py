@@ -163,11 +163,22 @@ def delivery_of(writer, config: Config):
     return "cloud", lambda points, labels, event: writer.write(points, labels, config, event)
 
 
+def fired_events(offsets, event_points, records, *arrays):
+    """A triggered trace call's result as ``deliver_events`` takes a batch: event_points masked by ``records["fired"]``
+    (the trigger records of the batch, None = no trigger), so that its loop skips the events that did not fire as it
+    skips the empty ones."""
+    if records is not None:
+        event_points = np.where(records["fired"] != 0, event_points, 0)
+    return (offsets, event_points, *arrays)
+
+
 def deliver_events(writer, n_events: int, batch_size: int, batch, emit) -> None:
     """The event loop of run_simulation and run_fused: ``batch(start, stop)`` -> (offsets, event_points, *arrays) of
     the events start .. stop - 1 in CSR form; every non-empty event's slices go to ``emit`` in event order, then the
     writer is closed.  Empty (simulator.py:204-205) is decided on the cloud BEFORE any threshold, ``event_points[i] ==
-    0``; a batch without event_points (None: a plain cloud) on its rows."""
+    0``; a batch without event_points (None: a plain cloud) on its rows.  A selection or a trigger reaches this loop as
+    event_points set to 0 for the events it rejects (``fired_events``): they are skipped, the others keep their
+    numbers."""
     for start in range(0, n_events, batch_size):
         stop = min(n_events, start + batch_size)
         offsets, event_points, *arrays = batch(start, stop)
@@ -181,7 +192,7 @@ def deliver_events(writer, n_events: int, batch_size: int, batch, emit) -> None:
 
 def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
                    indices: list[int] | None = None, batch_size: int = 16384,
-                   seed: int | None = None, selection=None):
+                   seed: int | None = None, selection=None, trigger=None):
     """Apply the detector simulation to every event of a kinematics file (reference
     simulator.py:118-210): the writer is called once per event with a non-empty cloud, in event order, then
     closed.  A writer that offers ``write_rows`` (SpyralWriter) receives its rows ready to store: the response
@@ -194,7 +205,9 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     ``write(points, labels, config, event)`` exactly as in the reference.  ``selection`` (a
     ``detector.selection.Selection``): only the events that pass it reach the writer (``attpc_det_run_selected``: the
     others are not assembled, converted or copied), with their original event numbers; a trace writer raises
-    ValueError."""
+    ValueError.  ``trigger`` (a ``detector.traces.TriggerSettings``): only the events the multiplicity trigger fires on
+    reach the writer, with their original event numbers -- a writer that receives traces or trace rows (for the latter
+    the device skips the peak work of the others too); any other raises ValueError."""
     from ..io import KinematicsFileReader
 
     print("------- AT-TPC Simulation Engine (MI355X) -------")
@@ -210,6 +223,8 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     kind, emit = delivery_of(writer, config)
     if selection is not None and kind not in ("rows", "cloud"):
         raise ValueError("a selection delivers Spyral rows or clouds: trace writers are not supported")
+    if trigger is not None and kind not in ("traces", "trace_rows"):
+        raise ValueError("a trigger delivers traces or trace rows: writers of Spyral rows or clouds are not supported")
 
     def batch(start, stop):
         vertices, momenta = reader.read(start, stop)
@@ -225,17 +240,17 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
         if kind == "traces":  # the pad traces are made on the device behind the scatter (attpc_det_run_traces)
             from .traces import simulate_batch_traces
 
-            offsets, pads, samples, labels, raw_points, _ = simulate_batch_traces(
+            offsets, pads, samples, labels, raw_points, stats = simulate_batch_traces(
                 *args, first_event=start, response=writer.response, threshold=writer.threshold, offset=writer.offset,
-                **writer.noise_kwargs(), **writer.readout_kwargs())
-            return offsets, raw_points, pads, samples, labels
+                **writer.noise_kwargs(), **writer.readout_kwargs(), trigger=trigger)
+            return fired_events(offsets, raw_points, stats.get("trigger"), pads, samples, labels)
         if kind == "trace_rows":  # ... and their peaks as Spyral rows behind them (attpc_det_run_trace_rows)
             from .traces import simulate_batch_trace_rows
 
-            offsets, rows, labels, raw_points, _ = simulate_batch_trace_rows(*args, first_event=start, peaks=writer.peaks,
-                                                                             baseline=getattr(writer, "baseline", None),
-                                                                             **writer.trace_kwargs())
-            return offsets, raw_points, rows, labels
+            offsets, rows, labels, raw_points, stats = simulate_batch_trace_rows(
+                *args, first_event=start, peaks=writer.peaks, baseline=getattr(writer, "baseline", None),
+                trigger=None if trigger is None else trigger.gated(), **writer.trace_kwargs())
+            return fired_events(offsets, raw_points, stats.get("trigger"), rows, labels)
         if kind == "rows":
             offsets, rows, labels, raw_points, _ = simulate_batch_spyral(
                 *args, first_event=start, response=getattr(writer, "response", None))

@@ -26,6 +26,12 @@ handed every pad's true pedestal, the peak stage gets Spyral's own estimate of t
 trace with its peaks masked out, which takes part of a wide pulse for baseline -- made on the device
 (include/attpc_engine.h; ``tests/baseline_reference.py`` restates it).  ``remove_baseline`` is that stage alone on any
 host rows.
+
+The multiplicity trigger is opt-in beside all of them (``TriggerSettings``, ``trigger=``): would the GET electronics
+have triggered on the event, and when -- a discriminator per pad, the multiplicity of every trigger group summed over a
+sliding window, a number of groups required --, evaluated on the device on the kept traces; one 32-byte record per
+event comes back (``TRIGGER_DTYPE``; include/attpc_engine.h; ``tests/trigger_reference.py`` restates it).
+``traces_to_trigger`` is that stage alone on any host rows.
 """
 from __future__ import annotations
 
@@ -265,31 +271,36 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
                           seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
                           response=None, threshold=None, offset: int = 0, capacity_per_event: int = 1024,
                           noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
-                          readout: str = "hit", readout_pads=None):
+                          readout: str = "hit", readout_pads=None, trigger: TriggerSettings | None = None):
     """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``; the noise keyed on
     ``seed`` and the global event ids; ``readout`` / ``readout_pads`` as configure_traces) ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
     before the suppression, stats dict: the cloud's run statistics plus ``n_rows`` / ``sample_checksum`` /
-    ``pad_checksum`` of the traces)."""
+    ``pad_checksum`` of the traces, and with ``trigger`` (a ``TriggerSettings``; None = off) its records [n] under
+    ``"trigger"``)."""
     from .simulator import run_batch
 
     ReadoutSettings(readout, readout_pads)  # (validated before the first library call)
+    ctx = ctx or _abi.default_context()
 
     def configure(ctx):
         configure_traces(config, ctx, response, threshold, offset, noise_sigma, noise_table, pedestals, noise_stream,
                          readout, readout_pads)
+        configure_trigger(ctx, trigger)
         return ctx._trace_readout_rows  # full readout: |S| rows per event
 
     arrays, stats = run_batch("attpc_det_run_traces", momenta, vertices, proton_numbers, mass_numbers, config, seed,
                               indices, first_event, ctx, capacity_per_event, configure)
-    return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **arrays.sums()})
+    extra = {} if trigger is None else {"trigger": ctx.trigger_last(len(arrays.offsets) - 1)}
+    return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **arrays.sums(), **extra})
 
 
 def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,
                      first_event: int = 0):
     """Pad traces of any host cloud in CSR form (``attpc_traces_at``; ``ctx`` configured with ``configure_traces``):
     offsets [n+1], points [P,3] (pad, time bucket, electrons), labels [P] ->
-    (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, {n_rows, sample_checksum, pad_checksum}).
+    (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, {n_rows, sample_checksum, pad_checksum}; when
+    the ctx holds a trigger (``configure_trigger``) its records [n] too, under ``"trigger"``).
     Event i of the call is the global event ``first_event + i``: its noise is keyed on (seed, first_event + i), and the
     pad checksum counts events from ``first_event``."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -309,7 +320,8 @@ def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray
     rows = int(offsets[-1] - offsets[0]) if n else 0
     rows = max(rows, ctx._trace_readout_rows * n)  # full readout: |S| rows per event
     arrays = call_with_capacity(ctx, n, max(16, rows), call, "attpc_traces_at")
-    return (*arrays.result(), arrays.sums())
+    records = trigger_records(ctx, n)
+    return (*arrays.result(), {**arrays.sums(), **({} if records is None else {"trigger": records})})
 
 
 class PeakSettings:
@@ -393,6 +405,102 @@ def remove_baseline(traces, window_scale: float = 20.0, ctx: _abi.Context | None
     return (y, baseline) if return_baseline else y
 
 
+TRIGGER_DTYPE = _abi.TRIGGER_DTYPE
+
+
+class TriggerSettings:
+    """The validated multiplicity trigger of the traces (``attpc_trigger_desc``, include/attpc_engine.h): ``threshold``
+    (integer in 0 .. 4095, the discriminator level above the pedestal), ``window`` (1 .. 512 samples),
+    ``group_multiplicity`` (>= 1: the windowed sum a group must reach), ``min_groups`` (1 .. 16 groups that must assert
+    together), ``groups`` ([ATTPC_NUM_PADS] integers: below 16 the pad's trigger group -- its CoBo; the map is the
+    caller's --, 255 = the pad takes no part; None = every pad in group 0) and ``gate`` (trace rows only: an event that
+    did not fire gets no rows)."""
+
+    def __init__(self, threshold, window: int = 64, group_multiplicity: int = 1, min_groups: int = 1, groups=None,
+                 gate: bool = False):
+        def integer(name, value, lo, hi):
+            if isinstance(value, (bool, np.bool_)) or int(value) != value or not lo <= int(value) <= hi:
+                raise ValueError(f"trigger {name} must be an integer in {lo} .. {hi}, got {value!r}")
+            return int(value)
+
+        self.threshold = integer("threshold", threshold, 0, 4095)
+        self.window = integer("window", window, 1, _abi.NUM_TB)
+        self.group_multiplicity = integer("group_multiplicity", group_multiplicity, 1, 2 ** 31 - 1)
+        self.min_groups = integer("min_groups", min_groups, 1, _abi.MAX_TRIGGER_GROUPS)
+        if groups is not None:
+            g = np.asarray(groups)
+            if g.shape != (_abi.NUM_PADS,) or g.dtype.kind not in "iu":
+                raise ValueError(f"trigger groups must be {_abi.NUM_PADS} integers, got {g.dtype} {g.shape}")
+            if np.any(((g < 0) | (g >= _abi.MAX_TRIGGER_GROUPS)) & (g != 255)):
+                raise ValueError(f"a trigger group must lie in 0 .. {_abi.MAX_TRIGGER_GROUPS - 1} or be 255 (no part)")
+            groups = np.ascontiguousarray(g, dtype=np.uint8)
+        self.groups = groups
+        if not isinstance(gate, (bool, np.bool_)) and gate not in (0, 1):
+            raise ValueError(f"trigger gate must be a bool, got {gate!r}")
+        self.gate = bool(gate)
+
+    def gated(self, gate: bool = True) -> "TriggerSettings":
+        """The same trigger with ``gate`` set."""
+        return TriggerSettings(self.threshold, self.window, self.group_multiplicity, self.min_groups, self.groups, gate)
+
+    def token(self):
+        return (self.threshold, self.window, self.group_multiplicity, self.min_groups,
+                None if self.groups is None else self.groups.tobytes(), self.gate)
+
+    def desc(self) -> _abi.TriggerDesc:
+        """(the descriptor points into ``self.groups``: keep the settings alive over the call)"""
+        return _abi.TriggerDesc(self.threshold, self.window, self.group_multiplicity, self.min_groups,
+                                _abi.iptr(self.groups, _abi.C.c_uint8), int(self.gate), 0)
+
+
+def configure_trigger(ctx: _abi.Context, trigger: TriggerSettings | None) -> None:
+    """``attpc_trace_configure_trigger`` unless this ctx already holds the same setting (``None``: the stage off, which
+    is also what a new context holds)."""
+    if trigger is None:
+        ctx.configure("trigger", None, "attpc_trace_configure_trigger", None)
+    else:
+        ctx.configure("trigger", trigger.token(), "attpc_trace_configure_trigger", trigger.desc())
+
+
+def trigger_records(ctx: _abi.Context, n_events: int):
+    """The records of ctx's last trace or trace-row call if the ctx holds a trigger, else None."""
+    return ctx.trigger_last(n_events) if ctx._tokens["trigger"] is not None else None
+
+
+def traces_to_trigger(offsets, pads, samples, trigger: TriggerSettings, pedestals=None, ctx: _abi.Context | None = None):
+    """The trigger stage alone on any host rows in CSR form (``attpc_trigger_rows``; the kernel of the fused path, no
+    other configuration needed): offsets [n+1], pads [R] in 0 .. 10239, samples [R,512] integers in 0 .. 4095,
+    ``pedestals`` [ATTPC_NUM_PADS] (or one value for every pad) in 0 .. 4095 or None -> records [n]
+    (``TRIGGER_DTYPE``)."""
+    if not isinstance(trigger, TriggerSettings):
+        raise TypeError("trigger must be a TriggerSettings")
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(offsets) - 1
+    if offsets.ndim != 1 or n < 0:
+        raise ValueError("offsets needs n_events + 1 entries")
+    pads, samples = np.asarray(pads), np.asarray(samples)
+    if pads.ndim != 1 or (pads.size and pads.dtype.kind not in "iu"):
+        raise ValueError("pads must be a 1-D array of integers")
+    if samples.shape != (len(pads), _abi.NUM_TB) or (samples.size and samples.dtype.kind not in "iu"):
+        raise ValueError(f"samples must be integers of shape [{len(pads)}, {_abi.NUM_TB}], got {samples.dtype} {samples.shape}")
+    if n and (offsets[0] < 0 or np.any(np.diff(offsets) < 0) or offsets[-1] > len(pads)):
+        raise ValueError("offsets must not decrease and must lie within the rows given")
+    if pads.size and (pads.min() < 0 or pads.max() >= _abi.NUM_PADS):
+        raise ValueError(f"pads must lie in 0 .. {_abi.NUM_PADS - 1}")
+    if samples.size and (samples.min() < 0 or samples.max() > 4095):
+        raise ValueError("trace samples must lie in 0 .. 4095")
+    pads = np.ascontiguousarray(pads, dtype=np.int32)
+    samples = np.ascontiguousarray(samples, dtype=np.int16)
+    pedestals = NoiseSettings(pedestals=pedestals).pedestals
+    ctx = ctx or _abi.default_context()
+    records = np.empty(n, dtype=TRIGGER_DTYPE)
+    i16 = _abi.C.c_int16
+    ctx.check(ctx.lib.attpc_trigger_rows(ctx.handle, n, _abi.iptr(offsets, _abi.C.c_int64), _abi.iptr(pads, _abi.C.c_int32),
+                                         _abi.iptr(samples, i16), _abi.iptr(pedestals, i16), trigger.desc(),
+                                         _abi.iptr(records, _abi.TriggerRecord)), "attpc_trigger_rows")
+    return records
+
+
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
                          baseline: BaselineSettings | None = None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
@@ -410,30 +518,38 @@ def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings 
 def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
                               seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
                               peaks: PeakSettings | None = None, capacity_per_event: int = 2048,
-                              baseline: BaselineSettings | None = None, **trace_kwargs):
+                              baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
+                              **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
     before any suppression, stats dict: the cloud's run statistics with ``n_points`` = the rows, plus ``n_rows`` /
-    ``row_checksum``)."""
+    ``row_checksum``, and with ``trigger`` (a ``TriggerSettings``; None = off; its ``gate`` leaves the events that did
+    not fire without rows) its records [n] under ``"trigger"``)."""
     from .simulator import run_batch
 
     peaks = PeakSettings() if peaks is None else peaks
     validate_trace_kwargs(config, trace_kwargs)  # (before the first library call)
     ctx = ctx or _abi.default_context()
+
+    def configure(c):
+        configure_trace_rows(config, c, peaks, baseline, **trace_kwargs)
+        configure_trigger(c, trigger)
+
     arrays, stats = run_batch("attpc_det_run_trace_rows", momenta, vertices, proton_numbers, mass_numbers, config, seed,
                               indices, first_event, ctx, capacity_per_event,
-                              configure=lambda c: configure_trace_rows(config, c, peaks, baseline, **trace_kwargs),
-                              holder=RowArrays, width=8, slack=1024)
-    return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **ctx.trace_rows_last()})
+                              configure=configure, holder=RowArrays, width=8, slack=1024)
+    extra = {} if trigger is None else {"trigger": ctx.trigger_last(len(arrays.offsets) - 1)}
+    return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **ctx.trace_rows_last(), **extra})
 
 
 def clouds_to_trace_rows(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,
                          first_event: int = 0):
     """Trace rows of any host cloud in CSR form (``attpc_trace_rows_at``; ``ctx`` configured with
     ``configure_trace_rows``): offsets [n+1], points [P,3] (pad, time bucket, electrons), labels [P] ->
-    (offsets [n+1], rows [R,8], labels [R], {n_rows, row_checksum}).  Event i of the call is the global event
-    ``first_event + i`` (noise, centroid jitter and checksum)."""
+    (offsets [n+1], rows [R,8], labels [R], {n_rows, row_checksum; when the ctx holds a trigger its records [n] too,
+    under ``"trigger"``}).  Event i of the call is the global event ``first_event + i`` (noise, centroid jitter and
+    checksum)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     labels = np.ascontiguousarray(labels, dtype=np.int64)
@@ -455,4 +571,5 @@ def clouds_to_trace_rows(offsets: np.ndarray, points: np.ndarray, labels: np.nda
     rows = int(offsets[-1] - offsets[0]) if n else 0
     arrays = call_with_capacity(ctx, n, max(16, rows, 4 * ctx._trace_readout_rows * n), call, "attpc_trace_rows_at", needed,
                                 holder=RowArrays, width=8, slack=16)
-    return (*arrays.result(), ctx.trace_rows_last())
+    records = trigger_records(ctx, n)
+    return (*arrays.result(), {**ctx.trace_rows_last(), **({} if records is None else {"trigger": records})})

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi, nuclear_map
 from .detector.luts import build_det_desc, build_layout, species_for
-from .detector.simulator import default_indices, deliver_events, delivery_of
+from .detector.simulator import default_indices, deliver_events, delivery_of, fired_events
 from .outputs import RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -143,7 +143,8 @@ class Engine:
         crosses PCIe (``attpc_sim_run_traces``).  ``fetch=True``: offsets [n+1], pads [R] i32, samples [R,512] i16,
         labels [R] i64 (``pinned``: page-locked arrays), event_points [n] = cloud rows before the suppression, and the
         kinematics; ``fetch=False``: the traces stay on the device, only ``trace`` (n_rows and both checksums) and the
-        cloud's ``stats`` come back."""
+        cloud's ``stats`` come back.  Both: with a trigger configured (``configure_trigger``) its records [n] under
+        ``trigger``."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         if not self._traces_configured:
             self.configure_traces()
@@ -155,12 +156,42 @@ class Engine:
                                                    None, None, None, out, stats), "attpc_sim_run_traces")
             return {"stats": stats.as_dict(), "trace": {"n_rows": int(out.n_rows),
                                                         "sample_checksum": int(out.sample_checksum),
-                                                        "pad_checksum": int(out.pad_checksum)}}
+                                                        "pad_checksum": int(out.pad_checksum)},
+                    **self._trigger_result(n_events)}
         per_event = max(int(capacity_per_event), ctx._trace_readout_rows)  # full readout: |S|
         arrays, res = self._deliver("attpc_sim_run_traces", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned)
         _, pads, samples, _ = arrays.result()
-        return {**res, "pads": pads, "samples": samples, "trace": arrays.sums()}
+        return {**res, "pads": pads, "samples": samples, "trace": arrays.sums(), **self._trigger_result(n_events)}
+
+    # ---------------------------------------------------------------- multiplicity trigger on the pad traces
+    def configure_trigger(self, trigger=None, **parameters) -> None:
+        """The multiplicity trigger of the traces (include/attpc_engine.h): a ``detector.traces.TriggerSettings`` or its
+        keywords (threshold, window, group_multiplicity, min_groups, groups, gate) turn it on -- ``run_traces``,
+        ``run_trace_rows`` and ``run_trigger`` then return one record per event under ``trigger``; with ``gate`` the
+        events that did not fire get no trace rows --, neither turns it off (the default)."""
+        from .detector.traces import TriggerSettings, configure_trigger
+
+        if trigger is not None and parameters:
+            raise TypeError("give a TriggerSettings or its keywords, not both")
+        if parameters:
+            trigger = TriggerSettings(**parameters)
+        configure_trigger(self.ctx, trigger)
+
+    def _trigger_result(self, n_events: int) -> dict:
+        """``{"trigger": records [n]}`` of the trace call just made if a trigger is configured, else nothing."""
+        from .detector.traces import trigger_records
+
+        records = trigger_records(self.ctx, n_events)
+        return {} if records is None else {"trigger": records}
+
+    def run_trigger(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
+        """``run_traces(fetch=False)`` for its trigger records: the traces are made, triggered on and left on the
+        device, 32 bytes per event cross PCIe (``trigger`` [n], ``detector.traces.TRIGGER_DTYPE``; ``trace`` and
+        ``stats`` as ``run_traces``).  Raises if no trigger is configured."""
+        if self.ctx._tokens["trigger"] is None:
+            raise RuntimeError("run_trigger needs a trigger: call configure_trigger first")
+        return self.run_traces(n_events, seed=seed, first_event=first_event, fetch=False)
 
 
     # ---------------------------------------------------------------- trace rows: peaks of the traces as Spyral rows
@@ -194,7 +225,9 @@ class Engine:
         of ``configure_baseline`` if that turned it on).  ``fetch=True``:
         offsets [n+1], rows [P,8] (x mm, y mm, z mm, amplitude, integral, pad, centroid, pad scale; every event in
         ascending z), labels [P], event_points [n] and the kinematics; ``fetch=False``: the rows stay on the device.
-        Both: ``trace_rows`` = {n_rows, row_checksum} and the cloud's ``stats`` (``n_points`` = the rows)."""
+        Both: ``trace_rows`` = {n_rows, row_checksum}, the cloud's ``stats`` (``n_points`` = the rows) and, with a
+        trigger configured (``configure_trigger``), its records [n] under ``trigger`` (with its ``gate`` an event that
+        did not fire is an empty range of the offsets)."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         if not self._traces_configured:
             self.configure_traces()
@@ -207,11 +240,11 @@ class Engine:
             stats, out = _abi.RunStats(), _abi.CloudOut()
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
-            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last()}
+            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **self._trigger_result(n_events)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
-        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last()}
+        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **self._trigger_result(n_events)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run
@@ -298,7 +331,7 @@ def _selected_batch(res: dict, key: str):
 
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
-              batch_size: int = 65536, context: _abi.Context | None = None, selection=None) -> None:
+              batch_size: int = 65536, context: _abi.Context | None = None, selection=None, trigger=None) -> None:
     """run_kinematics_pipeline + run_simulation + SpyralWriter without the kinematics file and with
     the response / threshold / row conversion / z-sort done on the GPU: per event with a non-empty
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
@@ -310,10 +343,14 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     the traces made on the device (``Engine.run_traces``) with the writer's noise settings.  ``selection`` (a
     ``detector.selection.Selection``): only the events that pass it reach the writer (``Engine.run_selected``; rows or
     plain clouds, a trace writer raises ValueError); event numbers stay the global ones, the file roll-over counts
-    written events."""
+    written events.  ``trigger`` (a ``detector.traces.TriggerSettings``): only the events the multiplicity trigger fires
+    on reach the writer, under their own event numbers -- a writer that receives traces or trace rows (for the latter
+    the device skips the peak work of the others too), any other raises ValueError."""
     engine = Engine(pipeline, config, indices, context=context)
     seed = pipeline.seed if seed is None else int(seed)
     kind, emit = delivery_of(writer, config)
+    if trigger is not None and kind not in ("traces", "trace_rows"):
+        raise ValueError("a trigger delivers traces or trace rows: writers of Spyral rows or clouds are not supported")
     if selection is not None:
         if kind not in ("rows", "cloud"):
             raise ValueError("a selection delivers Spyral rows or clouds: trace writers are not supported")
@@ -339,15 +376,17 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
         engine.configure_spyral(config)
     else:
         raise AttributeError("run_fused needs a writer that offers write_rows or write_traces")
+    if kind in ("traces", "trace_rows"):  # (None: whatever an earlier use of the context left is turned off)
+        engine.configure_trigger(trigger if trigger is None or kind == "traces" else trigger.gated())
 
     def batch(start, stop):
         if kind == "traces":
             res = engine.run_traces(stop - start, seed=seed, first_event=start)
-            return res["offsets"], res["event_points"], res["pads"], res["samples"], res["labels"]
+            return fired_events(res["offsets"], res["event_points"], res.get("trigger"), res["pads"], res["samples"], res["labels"])
         if kind == "trace_rows":
             res = engine.run_trace_rows(stop - start, seed=seed, first_event=start)
-        else:
-            res = engine.run_spyral(stop - start, seed=seed, first_event=start)
+            return fired_events(res["offsets"], res["event_points"], res.get("trigger"), res["rows"], res["labels"])
+        res = engine.run_spyral(stop - start, seed=seed, first_event=start)
         return res["offsets"], res["event_points"], res["rows"], res["labels"]
 
     deliver_events(writer, n_events, batch_size, batch, emit)

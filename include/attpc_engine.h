@@ -669,6 +669,80 @@ ATTPC_API int32_t attpc_trace_configure_baseline(attpc_ctx* ctx, const attpc_bas
 ATTPC_API int32_t attpc_trace_baseline(attpc_ctx* ctx, int64_t n_rows, const int16_t* samples, double window_scale,
                                        int16_t* y, double* baseline);
 
+/* ---- multiplicity trigger on the pad traces (opt-in: off by default, and with it off every output of every entry
+ * point is bit for bit what it is without this section and no buffer of the stage is allocated) ----
+ * Would the electronics have triggered on this event, and when?  The AT-TPC's GET electronics run self-triggered on pad
+ * multiplicity: every channel has a discriminator, every CoBo integrates the multiplicity of its channels over a
+ * sliding window and compares it with a threshold, and MuTanT requires a number of CoBos.  This stage evaluates that on
+ * the chunk's traces in HBM behind the trace write pass and leaves one 32-byte record per event.  The reference has no
+ * counterpart (parity is unpinned there, as for the traces themselves); tests/trigger_reference.py restates it in numpy.
+ * Input: the kept trace rows of event e exactly as the trace contracts above define them -- pad p, trace_p[0..511] --
+ * and the pad's pedestal ped_p (0 without pedestals), whatever the readout mode, the noise or a configured Fourier
+ * baseline: the discriminator sits on the raw channel above its own pedestal, the baseline stage plays no part.
+ * y_p[j] = trace_p[j] - ped_p, an integer.
+ * Parameters (attpc_trigger_desc): threshold in 0..4095, window W in 1..512, group_multiplicity Mg >= 1, min_groups in
+ * 1..ATTPC_MAX_TRIGGER_GROUPS, groups [ATTPC_NUM_PADS] (NULL: every pad in group 0; a value below
+ * ATTPC_MAX_TRIGGER_GROUPS is the pad's trigger group, its CoBo; 255: the pad takes no part; anything else is
+ * ATTPC_E_INVALID), gate (0 / 1, below).  The map from pads to CoBos is the caller's: the library has no table of it.
+ *   hit_p[j]  = y_p[j] > threshold (strict; time over threshold)
+ *   m_g[j]    = the number of kept rows of the event on pads of group g with hit_p[j]
+ *   s_g[j]    = sum of m_g[i] over i = max(0, j - W + 1) .. j
+ *   group g asserts at j iff s_g[j] >= Mg;  A[j] = the number of asserting groups
+ *   the event fires iff some j has A[j] >= min_groups
+ * Record (attpc_trigger_record, one per event): fired; sample = the first j with A[j] >= min_groups, else -1; groups =
+ * bit g set iff group g asserts at any sample; n_rows = kept trace rows of the event, excluded pads included;
+ * n_hit_pads = rows on participating pads with at least one hit; peak_group_sum = max over g, j of s_g[j] (with
+ * min_groups = 1 an event fires iff this is >= Mg: one run gives the efficiency curve over Mg); peak_sum = max over j
+ * of the sum over g of s_g[j]; peak_sample = the first j attaining peak_sum, -1 when that is 0.  An event without kept
+ * rows gets zeros and -1s.  Every sum is at most 10240 * 512 and fits int32; every field is a count, sum, minimum or
+ * maximum of integers and a pure function of (seed, global event id), independent of chunking and GPU count.
+ * Only kept rows can hit.  With threshold >= the adc_threshold of attpc_trace_configure, in partial or full readout,
+ * the kept rows contain every channel of the readout set that can hit: the result is that of all its channels.  In hit
+ * mode noise-only pads do not exist, so they cannot contribute.
+ * Gate (trace rows only): with gate = 1 attpc_*_run_trace_rows and attpc_trace_rows_at produce no rows for an event
+ * that did not fire -- the peak passes skip its trace rows; offsets keep one entry per event (an unfired event is an
+ * empty range), event_points and the cloud statistics keep their meaning, row_checksum and n_rows cover the rows
+ * produced.  The trace entry points (attpc_*_run_traces, attpc_traces_at) deliver all rows whatever gate says:
+ * compacting 1 KiB rows before the copy is deliberately out of scope. */
+#define ATTPC_MAX_TRIGGER_GROUPS 16
+typedef struct attpc_trigger_desc {
+  int32_t threshold;           /* 0..4095: discriminator level above the pedestal */
+  int32_t window;              /* W in 1..512 samples */
+  int32_t group_multiplicity;  /* Mg >= 1 */
+  int32_t min_groups;          /* 1..ATTPC_MAX_TRIGGER_GROUPS */
+  const uint8_t* groups;       /* [ATTPC_NUM_PADS] or NULL (host memory, copied by the call) */
+  int32_t gate;                /* 0 / 1 */
+  int32_t reserved;            /* 0 */
+} attpc_trigger_desc;
+
+typedef struct attpc_trigger_record {
+  int32_t fired;
+  int32_t sample;
+  uint32_t groups;
+  int32_t n_rows;
+  int32_t n_hit_pads;
+  int32_t peak_group_sum;
+  int32_t peak_sum;
+  int32_t peak_sample;
+} attpc_trigger_record;
+
+/* desc == NULL turns the stage off (the default).  Independent of every other configure call: no call resets another.
+ * ATTPC_E_INVALID for anything outside the ranges above.  Takes effect in the six trace and trace-row entry points
+ * (attpc_sim_run_traces, attpc_det_run_traces, attpc_traces_at and their *_trace_rows counterparts). */
+ATTPC_API int32_t attpc_trace_configure_trigger(attpc_ctx* ctx, const attpc_trigger_desc* desc);
+/* Records first .. first + count - 1 of the context's last trace or trace-row call, in the call's event order (a call
+ * repeated after ATTPC_E_CAPACITY overwrites them).  ATTPC_E_NOTCONFIGURED if no trigger was configured for that
+ * call, ATTPC_E_INVALID for a range outside it. */
+ATTPC_API int32_t attpc_trigger_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_trigger_record* out);
+/* The stage alone on any host rows in CSR form, through the same kernel (what attpc_trace_baseline is to the baseline
+ * stage): offsets [n_events + 1], pads [rows], samples [rows][512], pedestals [ATTPC_NUM_PADS] or NULL -> out
+ * [n_events].  Needs no other configuration and leaves the configured stage as it is; desc->gate plays no part.
+ * ATTPC_E_INVALID for a pad outside 0..10239, a sample outside 0..4095, a pedestal outside 0..4095, decreasing
+ * offsets or a desc out of range. */
+ATTPC_API int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const int32_t* pads,
+                                     const int16_t* samples, const int16_t* pedestals, const attpc_trigger_desc* desc,
+                                     attpc_trigger_record* out);
+
 /* ---- event and track summaries of a device-resident run (opt-in: without a call of the entry points below every
  * output of every other entry point is what it is without this section) ----
  * A summary run is a device-resident run (attpc_sim_run with out == NULL: same chunks, no event-ordered copy of the
