@@ -159,6 +159,14 @@ assert all(TRIGGER_DTYPE.fields[name][1] == getattr(TriggerRecord, name).offset 
 MAX_TRIGGER_GROUPS = 16
 
 
+class TraceGainDesc(C.Structure):
+    _fields_ = [("rel_variance", C.c_double), ("pad_gain", _dp), ("quantiles", _dp), ("stream", C.c_uint32),
+                ("reserved", C.c_int32)]
+
+
+GAIN_KNOTS = 4097
+
+
 class EventSummary(C.Structure):
     _fields_ = [("n_points", C.c_uint32), ("n_kept", C.c_uint32), ("n_pads", C.c_uint32), ("tb_min", C.c_int32),
                 ("tb_max", C.c_int32), ("reserved", C.c_int32), ("charge", C.c_int64)]
@@ -303,6 +311,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows", "attpc_trace_rows_at",
     "attpc_trace_rows_last", "attpc_trace_configure_baseline", "attpc_trace_baseline",
     "attpc_trace_configure_trigger", "attpc_trigger_last", "attpc_trigger_rows",
+    "attpc_trace_configure_gain", "attpc_gain_rows",
     "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
     "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
 )
@@ -324,6 +333,9 @@ BASELINE_SYMBOLS = ("attpc_trace_configure_baseline", "attpc_trace_baseline")
 
 # ... and the multiplicity trigger of the traces after the Fourier baseline: the same rule.
 TRIGGER_SYMBOLS = ("attpc_trace_configure_trigger", "attpc_trigger_last", "attpc_trigger_rows")
+
+# ... and the micromegas gain of the traces after the trigger: the same rule.
+GAIN_SYMBOLS = ("attpc_trace_configure_gain", "attpc_gain_rows")
 
 _lib = None
 
@@ -448,6 +460,14 @@ def load_library() -> C.CDLL:
     for name, argtypes in trigger.items():
         if not no_trigger:
             getattr(lib, name).argtypes = argtypes
+    gain = {
+        "attpc_trace_configure_gain": [ctxp, C.POINTER(TraceGainDesc)],
+        "attpc_gain_rows": [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64), _dp, _dp],
+    }
+    no_gain = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in GAIN_SYMBOLS)
+    for name, argtypes in gain.items():
+        if not no_gain:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -470,7 +490,7 @@ def load_library() -> C.CDLL:
     for name in EXPORTED_SYMBOLS:
         if ((older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS)
                 or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)
-                or (no_trigger and name in TRIGGER_SYMBOLS)):
+                or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -479,7 +499,8 @@ def load_library() -> C.CDLL:
     return lib
 
 
-CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "peaks", "baseline", "trigger", "summary", "select")
+CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
+                   "select")
 
 
 class Context:

@@ -80,6 +80,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf ev_start, points, labels, kept, kept_start, sp_rows, sp_labels;
   DevBuf tr_scratch, tr_info, tr_pads, tr_samples, tr_labels;  // pad traces (traces.hip)
   DevBuf tr_maps;     // readout of noise-only pads: TraceMaps, 3 x TR_MAP_WORDS words per event
+  DevBuf tr_gained;   // micromegas gain on (gain.hip): the gained charge of every cloud row of the chunk, f64 [rows]
   size_t tr_cap = 0;  // kept pad rows the trace outputs are kept at (grown with headroom)
   hipEvent_t traced = nullptr;  // the chunk's traces are written (the copies on C wait for it)
   hipEvent_t counted = nullptr; // trace rows: the chunk's points per event are in h_pk_start (the host waits for it)
@@ -191,6 +192,9 @@ struct attpc_ctx {
   TraceNoiseDev noise{};
   std::vector<void*> noise_allocs;
   std::vector<uint32_t> noise_cdf;  // host copy of the noise cdf [n_levels - 1] (the readout's cutoff)
+  bool gain_on = false;            // attpc_trace_configure_gain
+  GainDev gain{};
+  std::vector<void*> gain_allocs;
   int32_t readout_mode = ATTPC_READOUT_HIT;  // attpc_trace_configure_readout
   int64_t readout_pads = 0;        // |S|
   const uint32_t* readout_channels = nullptr;  // [TR_MAP_WORDS] bitmap of S on the device
@@ -242,7 +246,7 @@ struct attpc_ctx {
   bool unpack_stop = false, unpack_failed = false;
 
   ~attpc_ctx() {  // (attpc_ctx_destroy has stopped everything first; the DevBuf / Pinned members free themselves)
-    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs, &readout_allocs, &summary_allocs})
+    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs, &gain_allocs, &readout_allocs, &summary_allocs})
       for (void* p : *v) (void)hipFree(p);
     for (void* p : host_allocs) (void)hipHostFree(p);
   }
@@ -819,6 +823,14 @@ TraceScratch trace_scratch(AsmSet& as, size_t cap) {
   return sc;
 }
 
+// The trace settings of the chunk in `as`: with the micromegas gain on, its charges come from as.tr_gained
+// (enqueue_trace_count fills it in front of the count pass; the write pass reads the same array).
+TraceDev trace_dev(const attpc_ctx* ctx, const AsmSet& as) {
+  TraceDev tr = ctx->trace;
+  tr.gained = ctx->gain_on ? static_cast<const double*>(as.tr_gained.p) : nullptr;
+  return tr;
+}
+
 // The noise of the trace kernels: nullptr = the noiseless kernels.
 const TraceNoiseDev* trace_noise(const attpc_ctx* ctx) { return ctx->noise_on ? &ctx->noise : nullptr; }
 
@@ -865,10 +877,16 @@ int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap, 
   if ((rc = ensure(ctx, as.kept_start, ((size_t)n + 1) * sizeof(int64_t)))) return rc;
   if ((rc = ensure(ctx, as.tr_scratch, std::max<size_t>(cap, 1) * 4 * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, as.tr_info, std::max<size_t>(n, 1) * 2 * sizeof(uint32_t)))) return rc;
+  if (ctx->gain_on && (rc = ensure(ctx, as.tr_gained, std::max<size_t>(cap, 1) * sizeof(double)))) return rc;
   const TraceReadoutDev ro = trace_readout(ctx);
   if (n) {
+    if (ctx->gain_on) {  // the gained charges of the chunk's rows, in front of the count pass
+      launch_gain(ctx->stream, ctx->gain, seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
+                  static_cast<const double*>(as.points.p), static_cast<double*>(as.tr_gained.p));
+      HIP_TRY(ctx, hipGetLastError());
+    }
     const TraceScratch sc = trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t)));
-    launch_trace_count(ctx->stream, ctx->trace, trace_noise(ctx), seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
+    launch_trace_count(ctx->stream, trace_dev(ctx, as), trace_noise(ctx), seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
                        static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p), sc,
                        static_cast<uint32_t*>(as.kept.p), ro.channels ? &ro : nullptr);
     HIP_TRY(ctx, hipGetLastError());
@@ -894,7 +912,7 @@ int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t tota
     if ((rc = ensure(ctx, as.tr_pads, as.tr_cap * sizeof(int32_t)))) return rc;
     if ((rc = ensure(ctx, as.tr_samples, as.tr_cap * ATTPC_NUM_TB * sizeof(int16_t)))) return rc;
     if ((rc = ensure(ctx, as.tr_labels, as.tr_cap * sizeof(int64_t)))) return rc;
-    launch_trace_write(ctx->stream, ctx->trace, trace_noise(ctx), seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
+    launch_trace_write(ctx->stream, trace_dev(ctx, as), trace_noise(ctx), seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
                        static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p),
                        trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t))),
                        static_cast<const int64_t*>(as.kept_start.p), static_cast<int32_t*>(as.tr_pads.p),
@@ -2407,6 +2425,40 @@ int32_t attpc_traces(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, c
 }
 
 namespace {
+// The checks of a host cloud in CSR form (attpc_traces_at, attpc_trace_rows_at, attpc_gain_rows; `what` names the entry
+// point): n_events, offsets and the contract's rows -- integer pad in range, 0 <= tau < 512, finite electrons >= 0, a
+// (pad, t) of their own within the event.
+int32_t check_host_cloud(attpc_ctx* ctx, const char* what, int64_t n_events, const int64_t* offsets, const double* points,
+                         bool has_labels) {
+  if (n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
+  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes at most 2^31 - 1 events per call", what);
+  const uint32_t n = (uint32_t)n_events;
+  const int64_t first = n ? offsets[0] : 0;
+  for (uint32_t e = 0; e < n; ++e)
+    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %u", e);
+  if (first < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
+  const int64_t rows = n ? offsets[n] - first : 0;
+  if (rows > 0 && (!points || !has_labels)) return ATTPC_E_INVALID;
+  if (rows > (int64_t)UINT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes fewer than 2^32 rows per call", what);
+  std::vector<uint32_t> keys;
+  for (uint32_t e = 0; e < n; ++e) {
+    keys.clear();
+    for (int64_t r = offsets[e]; r < offsets[e + 1]; ++r) {
+      const double padf = points[3 * r], tb = points[3 * r + 1], q = points[3 * r + 2];
+      if (!(padf >= 0.0 && padf < (double)ATTPC_NUM_PADS) || padf != std::floor(padf))
+        return fail(ctx, ATTPC_E_INVALID, "row %lld: pad %g is not an integer in [0, %d)", (long long)r, padf, ATTPC_NUM_PADS);
+      if (!(tb >= 0.0 && tb < (double)ATTPC_NUM_TB))
+        return fail(ctx, ATTPC_E_INVALID, "row %lld: time bucket %g outside [0, 512)", (long long)r, tb);
+      if (!(q >= 0.0) || std::isinf(q)) return fail(ctx, ATTPC_E_INVALID, "row %lld: electrons %g", (long long)r, q);
+      keys.push_back((uint32_t)padf * ATTPC_NUM_TB + (uint32_t)std::floor(tb));
+    }
+    std::sort(keys.begin(), keys.end());
+    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
+      return fail(ctx, ATTPC_E_INVALID, "event %u has two rows on one pad and time bucket", e);
+  }
+  return ATTPC_OK;
+}
+
 // attpc_traces_at and attpc_trace_rows_at: the checks of the host cloud, then its events through trace_host_events
 // into `o`.
 int32_t host_cloud_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
@@ -2416,31 +2468,7 @@ int32_t host_cloud_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int6
   if (validate_id_range(ctx, first_event, (uint64_t)n_events)) return ATTPC_E_INVALID;
   if (!ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
   const uint32_t n = (uint32_t)n_events;
-  const int64_t first = n ? offsets[0] : 0;
-  for (uint32_t e = 0; e < n; ++e)
-    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %u", e);
-  if (first < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
-  const int64_t rows = n ? offsets[n] - first : 0;
-  if (rows > 0 && (!points || !labels)) return ATTPC_E_INVALID;
-  if (rows > (int64_t)UINT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_traces takes fewer than 2^32 rows per call");
-  {  // the contract's rows: integer pad in range, 0 <= tau < 512, finite electrons >= 0, a (pad, t) of their own
-    std::vector<uint32_t> keys;
-    for (uint32_t e = 0; e < n; ++e) {
-      keys.clear();
-      for (int64_t r = offsets[e]; r < offsets[e + 1]; ++r) {
-        const double padf = points[3 * r], tb = points[3 * r + 1], q = points[3 * r + 2];
-        if (!(padf >= 0.0 && padf < (double)ATTPC_NUM_PADS) || padf != std::floor(padf))
-          return fail(ctx, ATTPC_E_INVALID, "row %lld: pad %g is not an integer in [0, %d)", (long long)r, padf, ATTPC_NUM_PADS);
-        if (!(tb >= 0.0 && tb < (double)ATTPC_NUM_TB))
-          return fail(ctx, ATTPC_E_INVALID, "row %lld: time bucket %g outside [0, 512)", (long long)r, tb);
-        if (!(q >= 0.0) || std::isinf(q)) return fail(ctx, ATTPC_E_INVALID, "row %lld: electrons %g", (long long)r, q);
-        keys.push_back((uint32_t)padf * ATTPC_NUM_TB + (uint32_t)std::floor(tb));
-      }
-      std::sort(keys.begin(), keys.end());
-      if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
-        return fail(ctx, ATTPC_E_INVALID, "event %u has two rows on one pad and time bucket", e);
-    }
-  }
+  if (int32_t bad = check_host_cloud(ctx, "attpc_traces", n_events, offsets, points, labels != nullptr)) return bad;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc;
   if ((rc = drop_prefetch(ctx))) return rc;
@@ -2462,6 +2490,79 @@ int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
   if ((rc = host_cloud_run(ctx, seed, first_event, n_events, offsets, points, labels, o))) return rc;
   if ((rc = read_trace_sums(ctx, o))) return rc;
   return run_status(ctx, attpc_run_stats{}, nullptr, o);
+}
+
+// ---- micromegas gain of the traces (gain.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_gain(attpc_ctx* ctx, const attpc_trace_gain_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d) {
+    if (!(d->rel_variance >= 0.0 && d->rel_variance <= 1.0))
+      return fail(ctx, ATTPC_E_INVALID, "gain rel_variance %g: 0 .. 1", d->rel_variance);
+    if (d->pad_gain)
+      for (int p = 0; p < ATTPC_NUM_PADS; ++p)
+        if (!(d->pad_gain[p] >= 0.0) || std::isinf(d->pad_gain[p]))
+          return fail(ctx, ATTPC_E_INVALID, "gain of pad %d is %g: finite and >= 0", p, d->pad_gain[p]);
+    if (d->rel_variance > 0.0) {
+      if (!d->quantiles) return fail(ctx, ATTPC_E_INVALID, "gain rel_variance %g without a quantile table", d->rel_variance);
+      for (int k = 0; k < ATTPC_GAIN_KNOTS; ++k) {
+        if (!std::isfinite(d->quantiles[k])) return fail(ctx, ATTPC_E_INVALID, "gain quantile %d is not finite", k);
+        if (k && d->quantiles[k] < d->quantiles[k - 1]) return fail(ctx, ATTPC_E_INVALID, "gain quantiles decrease at entry %d", k);
+      }
+    }
+    if (d->stream >= 0x40000000u) return fail(ctx, ATTPC_E_INVALID, "gain stream %u >= 2^30", d->stream);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  free_all(ctx->gain_allocs);
+  ctx->gain_on = false;
+  ctx->gain = GainDev{};
+  if (!d || (d->rel_variance == 0.0 && !d->pad_gain)) return ATTPC_OK;  // q'' = q: the contract without the stage
+  GainDev g{};
+  int32_t rc;
+  if (d->rel_variance > 0.0 && (rc = upload(ctx, ctx->gain_allocs, d->quantiles, (size_t)ATTPC_GAIN_KNOTS, &g.quantiles))) return rc;
+  if (d->pad_gain && (rc = upload(ctx, ctx->gain_allocs, d->pad_gain, (size_t)ATTPC_NUM_PADS, &g.pad_gain))) return rc;
+  g.c = d->rel_variance / 9.0;
+  g.domain = DOMAIN_TRACE_GAIN | d->stream;
+  ctx->gain = g;
+  ctx->gain_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_gain_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
+                        const double* points, double* gained) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (int32_t bad = check_host_cloud(ctx, "attpc_gain_rows", n_events, offsets, points, true)) return bad;
+  if (validate_id_range(ctx, first_event, (uint64_t)n_events)) return ATTPC_E_INVALID;
+  const int64_t all = n_events ? offsets[n_events] - offsets[0] : 0;
+  if (all == 0) return ATTPC_OK;
+  if (!gained) return ATTPC_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  // chunks of whole events: about 4 Mi rows (96 MiB of points) and at most 1 Mi events, one event at the least
+  constexpr int64_t CHUNK_ROWS = 4ll << 20, CHUNK_EVENTS = 1ll << 20;
+  std::vector<int64_t> start;
+  for (int64_t e0 = 0; e0 < n_events;) {
+    int64_t e1 = e0 + 1;
+    while (e1 < n_events && e1 - e0 < CHUNK_EVENTS && offsets[e1 + 1] - offsets[e0] <= CHUNK_ROWS) ++e1;
+    const int64_t lo = offsets[e0], rows = offsets[e1] - lo, m = e1 - e0;
+    if (rows > 0) {
+      start.resize((size_t)m + 1);
+      for (int64_t e = 0; e <= m; ++e) start[(size_t)e] = offsets[e0 + e] - lo;
+      if ((rc = ensure(ctx, ctx->scratch[0], start.size() * sizeof(int64_t)))) return rc;
+      if ((rc = ensure(ctx, ctx->scratch[1], (size_t)rows * 3 * sizeof(double)))) return rc;
+      if ((rc = ensure(ctx, ctx->scratch[2], (size_t)rows * sizeof(double)))) return rc;
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, start.data(), start.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, points + 3 * lo, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      launch_gain(ctx->stream, ctx->gain, seed, (uint32_t)m, first_event + (uint64_t)e0, static_cast<const int64_t*>(ctx->scratch[0].p),
+                  static_cast<const double*>(ctx->scratch[1].p), static_cast<double*>(ctx->scratch[2].p));
+      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemcpyAsync(gained + lo, ctx->scratch[2].p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    e0 = e1;
+  }
+  return ATTPC_OK;
 }
 
 // ---- event and track summaries (summary.hip; the contract is in include/attpc_engine.h) ----

@@ -24,6 +24,8 @@ constexpr uint32_t DOMAIN_JITTER = 0x100u; // folded into the key word of jitter
 constexpr uint32_t DOMAIN_MC = 0x200u;     // + entry number of the event; index = primary electron
 constexpr uint32_t DOMAIN_PEAK_JITTER = 0x300u;  // as DOMAIN_JITTER, for the centroid of a trace peak (peaks.hip): key = sample << 14 | pad
 constexpr uint32_t DOMAIN_TRACE_NOISE = 0x80000000u;  // | noise stream; index = pad * 128 + 2 * (j % 64) + j / 256
+constexpr uint32_t DOMAIN_TRACE_GAIN = 0x40000000u;   // | gain stream (< 2^30); index = pad * 512 + time bucket (gain.hip)
+// (nothing else reaches bit 30: 1 + row and 0x200 + entry stay far below, 0x100 / 0x300 are key words of Philox2x32)
 constexpr uint32_t KIN_SLOTS = 64u;
 
 // Philox4x32-10 (Salmon et al. SC'11), the algorithm of rocRAND's default generator, written

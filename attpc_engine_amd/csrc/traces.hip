@@ -8,7 +8,8 @@
 //          kept pad's rank inside the event.
 //   write: one wave per kept pad works the trace out again and writes pad, label and 512 samples (1 KiB, coalesced) at
 //          kept_start[event] + rank; checksums are summed per workgroup, one global atomic per event.
-// A pad's trace: its rows are scattered into a 512-entry LDS table q[t] (0 where no row exists), the non-zero entries
+// A pad's trace: its rows are scattered into a 512-entry LDS table q[t] (0 where no row exists; with the micromegas
+// gain on, gain.hip, the row's gained charge from TraceDev::gained in place of the cloud's), the non-zero entries
 // are walked in ascending t, 64 at a time by ballot, and every lane keeps the samples j = lane + 64 s (s = 0..7) as 8 f64
 // accumulators, reading R from LDS.  The dense walk gives the same bits as the sparse ordered sum of the contract: the
 // terms it skips would add +0.0 to an accumulator that starts at +0.0 and never becomes -0.0.
@@ -64,8 +65,8 @@ __device__ __forceinline__ PadTrace pad_trace(const TraceDev& tr, const double* 
   for (uint32_t i = start + (uint32_t)lane; i < end; i += 64u) {
     const int64_t r = lo + row[lo + i];
     const int t = (int)floor(points[3 * r + 1]);  // in 0..511: rows outside were never placed
-    const double q = points[3 * r + 2];
-    qt[t] = q;
+    const double q = points[3 * r + 2];  // the label rule stays on the cloud's own charge
+    qt[t] = tr.gained ? tr.gained[r] : q;
     if (q > best_q || (q == best_q && t < best_t)) {
       best_q = q;
       best_t = t;
@@ -159,10 +160,6 @@ __device__ __forceinline__ void add_noise(PadTrace& pt, const TraceNoiseDev& nz,
     m = o > m ? o : m;
   }
   pt.max = m;
-}
-
-__device__ __forceinline__ bool trace_row_ok(double padf, double tb) {
-  return padf >= 0.0 && padf < (double)ATTPC_NUM_PADS && tb >= 0.0 && tb < (double)ATTPC_NUM_TB;
 }
 
 // A row of the count pass with readout RO: in range and on a pad of the readout set (rows elsewhere are dropped).

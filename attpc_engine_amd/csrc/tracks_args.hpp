@@ -82,7 +82,12 @@ struct TraceDev {
   const double* response;  // [512]
   double threshold;
   int32_t offset;
+  const double* gained;    // [rows] the chunk's gained charges q'' (gain.hip), or nullptr: the cloud's own charges
 };
+// a cloud row the traces can place: pad and time bucket in range
+__device__ __forceinline__ bool trace_row_ok(double padf, double tb) {
+  return padf >= 0.0 && padf < (double)ATTPC_NUM_PADS && tb >= 0.0 && tb < (double)ATTPC_NUM_TB;
+}
 // per-event working lists in global memory, ranges of the event's own cloud rows (rows lo .. hi of the chunk)
 struct TraceScratch {
   uint32_t* row;        // [rows] the event's row numbers grouped by pad, pads ascending
@@ -138,6 +143,18 @@ void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* 
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
                         TraceScratch sc, const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
                         unsigned long long* sums);
+
+// micromegas gain of the traces (gain.hip; attpc_trace_configure_gain, the contract is in include/attpc_engine.h)
+struct GainDev {
+  const double* quantiles;  // [ATTPC_GAIN_KNOTS] inverse CDF of the standardised fluctuation, or nullptr: no draw (f = 0)
+  const double* pad_gain;   // [ATTPC_NUM_PADS] or nullptr (1.0 everywhere)
+  double c;                 // rel_variance / 9.0
+  uint32_t domain;          // DOMAIN_TRACE_GAIN | stream
+};
+// gained[r] = q'' of row r of the event-ordered cloud (event e of the launch = global id first_event + e); rows out of
+// the traces' range get 0.  One workgroup per event.
+void launch_gain(hipStream_t s, const GainDev& g, uint64_t seed, uint32_t n_events, uint64_t first_event,
+                 const int64_t* event_start, const double* points, double* gained);
 
 // peaks of the kept trace rows -> Spyral rows (peaks.hip; attpc_trace_configure_peaks, the contract is in
 // include/attpc_engine.h).  The geometry is SpyralDev's.

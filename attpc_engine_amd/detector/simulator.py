@@ -192,7 +192,7 @@ def deliver_events(writer, n_events: int, batch_size: int, batch, emit) -> None:
 
 def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
                    indices: list[int] | None = None, batch_size: int = 16384,
-                   seed: int | None = None, selection=None, trigger=None):
+                   seed: int | None = None, selection=None, trigger=None, gain=None):
     """Apply the detector simulation to every event of a kinematics file (reference
     simulator.py:118-210): the writer is called once per event with a non-empty cloud, in event order, then
     closed.  A writer that offers ``write_rows`` (SpyralWriter) receives its rows ready to store: the response
@@ -207,7 +207,9 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     others are not assembled, converted or copied), with their original event numbers; a trace writer raises
     ValueError.  ``trigger`` (a ``detector.traces.TriggerSettings``): only the events the multiplicity trigger fires on
     reach the writer, with their original event numbers -- a writer that receives traces or trace rows (for the latter
-    the device skips the peak work of the others too); any other raises ValueError."""
+    the device skips the peak work of the others too); any other raises ValueError.  ``gain`` (a
+    ``detector.traces.GainSettings``; default: the writer's own ``gain``, None = off): the micromegas gain of the traces
+    -- again a writer that receives traces or trace rows; any other raises ValueError."""
     from ..io import KinematicsFileReader
 
     print("------- AT-TPC Simulation Engine (MI355X) -------")
@@ -225,6 +227,9 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
         raise ValueError("a selection delivers Spyral rows or clouds: trace writers are not supported")
     if trigger is not None and kind not in ("traces", "trace_rows"):
         raise ValueError("a trigger delivers traces or trace rows: writers of Spyral rows or clouds are not supported")
+    if gain is not None and kind not in ("traces", "trace_rows"):
+        raise ValueError("a gain acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
+    gain = getattr(writer, "gain", None) if gain is None else gain
 
     def batch(start, stop):
         vertices, momenta = reader.read(start, stop)
@@ -242,14 +247,14 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
 
             offsets, pads, samples, labels, raw_points, stats = simulate_batch_traces(
                 *args, first_event=start, response=writer.response, threshold=writer.threshold, offset=writer.offset,
-                **writer.noise_kwargs(), **writer.readout_kwargs(), trigger=trigger)
+                **writer.noise_kwargs(), **writer.readout_kwargs(), trigger=trigger, gain=gain)
             return fired_events(offsets, raw_points, stats.get("trigger"), pads, samples, labels)
         if kind == "trace_rows":  # ... and their peaks as Spyral rows behind them (attpc_det_run_trace_rows)
             from .traces import simulate_batch_trace_rows
 
             offsets, rows, labels, raw_points, stats = simulate_batch_trace_rows(
                 *args, first_event=start, peaks=writer.peaks, baseline=getattr(writer, "baseline", None),
-                trigger=None if trigger is None else trigger.gated(), **writer.trace_kwargs())
+                trigger=None if trigger is None else trigger.gated(), gain=gain, **writer.trace_kwargs())
             return fired_events(offsets, raw_points, stats.get("trigger"), rows, labels)
         if kind == "rows":
             offsets, rows, labels, raw_points, _ = simulate_batch_spyral(

@@ -32,10 +32,18 @@ have triggered on the event, and when -- a discriminator per pad, the multiplici
 sliding window, a number of groups required --, evaluated on the device on the kept traces; one 32-byte record per
 event comes back (``TRIGGER_DTYPE``; include/attpc_engine.h; ``tests/trigger_reference.py`` restates it).
 ``traces_to_trigger`` is that stage alone on any host rows.
+
+The micromegas gain is opt-in in front of all of them (``GainSettings``, ``gain=``): the avalanche statistics of the
+amplification (a Polya single-electron gain of relative variance f = 1 / (1 + theta), so that a bucket of q electrons
+has a relative amplitude spread of sqrt(f / q)) and a per-pad gain map, applied on the device to every cloud row's
+charge before the trace kernels read it -- a pure function of (seed, global event id, pad, time bucket, charge)
+(include/attpc_engine.h; ``tests/gain_reference.py`` restates it).  ``clouds_to_gain`` is that stage alone on any host
+cloud.
 """
 from __future__ import annotations
 
 import math
+import statistics
 
 import numpy as np
 
@@ -255,9 +263,12 @@ TRACE_KWARGS = ("response", "threshold", "offset", "noise_sigma", "noise_table",
                 "readout_pads")
 
 
-def validate_trace_kwargs(config: Config, trace_kwargs: dict) -> None:
+def validate_trace_kwargs(config: Config, trace_kwargs: dict, gain=None) -> None:
     """The trace settings a caller passes on as keywords (``configure_traces``'s, TRACE_KWARGS), checked before any
-    library call: TypeError for a name configure_traces does not take, ValueError for a value it would refuse."""
+    library call: TypeError for a name configure_traces does not take, ValueError for a value it would refuse.
+    ``gain``: the ``GainSettings`` that goes with them (or None), TypeError for anything else."""
+    if gain is not None and not isinstance(gain, GainSettings):
+        raise TypeError("gain must be a GainSettings or None")
     unknown = set(trace_kwargs) - set(TRACE_KWARGS)
     if unknown:
         raise TypeError(f"unexpected trace settings {sorted(unknown)}: configure_traces takes {list(TRACE_KWARGS)}")
@@ -271,22 +282,26 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
                           seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
                           response=None, threshold=None, offset: int = 0, capacity_per_event: int = 1024,
                           noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
-                          readout: str = "hit", readout_pads=None, trigger: TriggerSettings | None = None):
+                          readout: str = "hit", readout_pads=None, trigger: TriggerSettings | None = None,
+                          gain: GainSettings | None = None):
     """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``; the noise keyed on
     ``seed`` and the global event ids; ``readout`` / ``readout_pads`` as configure_traces) ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
     before the suppression, stats dict: the cloud's run statistics plus ``n_rows`` / ``sample_checksum`` /
     ``pad_checksum`` of the traces, and with ``trigger`` (a ``TriggerSettings``; None = off) its records [n] under
-    ``"trigger"``)."""
+    ``"trigger"``).  ``gain`` (a ``GainSettings``; None = off): the micromegas gain of every cloud row's charge, keyed on
+    ``seed`` and the global event ids like the noise."""
     from .simulator import run_batch
 
     ReadoutSettings(readout, readout_pads)  # (validated before the first library call)
+    _checked_gain(gain)
     ctx = ctx or _abi.default_context()
 
     def configure(ctx):
         configure_traces(config, ctx, response, threshold, offset, noise_sigma, noise_table, pedestals, noise_stream,
                          readout, readout_pads)
         configure_trigger(ctx, trigger)
+        configure_gain(ctx, gain)
         return ctx._trace_readout_rows  # full readout: |S| rows per event
 
     arrays, stats = run_batch("attpc_det_run_traces", momenta, vertices, proton_numbers, mass_numbers, config, seed,
@@ -501,11 +516,124 @@ def traces_to_trigger(offsets, pads, samples, trigger: TriggerSettings, pedestal
     return records
 
 
+def polya_rel_variance(theta: float) -> float:
+    """The relative variance f = 1 / (1 + theta) of a Polya-distributed single-electron gain, theta >= 0 (theta = 0:
+    the exponential gain of a parallel-plate avalanche, f = 1)."""
+    theta = float(theta)
+    if not (theta >= 0.0 and math.isfinite(theta)):
+        raise ValueError(f"the Polya parameter theta must be finite and >= 0, got {theta}")
+    return 1.0 / (1.0 + theta)
+
+
+_quantile_table = None
+
+
+def normal_quantile_table() -> np.ndarray:
+    """The quantile table [ATTPC_GAIN_KNOTS] of the gain's standardised fluctuation: Phi^-1((i + 0.5) / 4097) for
+    i = 0 .. 4096 (``statistics.NormalDist``), divided by the standard deviation of the piecewise-linear law the table
+    defines -- a uniformly chosen interval, a uniform position in it: mean 0 by symmetry, variance
+    mean((a^2 + a b + b^2) / 3) over the intervals [a, b], 0.99663 unscaled -- so that law has unit variance."""
+    global _quantile_table
+    if _quantile_table is None:
+        inv = statistics.NormalDist().inv_cdf
+        z = np.array([inv((i + 0.5) / _abi.GAIN_KNOTS) for i in range(_abi.GAIN_KNOTS)], dtype=np.float64)
+        z = 0.5 * (z - z[::-1])  # exactly antisymmetric
+        a, b = z[:-1], z[1:]
+        variance = math.fsum((a * a + a * b + b * b) / 3.0) / (_abi.GAIN_KNOTS - 1)
+        _quantile_table = z / math.sqrt(variance)
+        _quantile_table.setflags(write=False)
+    return _quantile_table
+
+
+class GainSettings:
+    """The validated micromegas gain of the traces (``attpc_trace_gain_desc``, include/attpc_engine.h): exactly one of
+    ``rel_variance`` (f in [0, 1]) and ``theta`` (the Polya parameter, f = 1 / (1 + theta)) -- neither, with a
+    ``pad_gain``, means f = 0: pad gains only --, ``pad_gain`` ([ATTPC_NUM_PADS] finite factors >= 0, or one value for
+    every pad; None = 1.0 everywhere), ``stream`` in [0, 2^30) (another realisation on the same physics).  The
+    fluctuation is drawn through ``normal_quantile_table()``."""
+
+    def __init__(self, rel_variance=None, theta=None, pad_gain=None, stream: int = 0):
+        if rel_variance is not None and theta is not None:
+            raise ValueError("give rel_variance or theta, not both")
+        if rel_variance is None and theta is None and pad_gain is None:
+            raise ValueError("a gain needs rel_variance, theta or pad_gain")
+        if theta is not None:
+            rel_variance = polya_rel_variance(theta)
+        self.rel_variance = 0.0 if rel_variance is None else float(rel_variance)
+        if not 0.0 <= self.rel_variance <= 1.0:
+            raise ValueError(f"gain rel_variance must be in [0, 1], got {rel_variance}")
+        if pad_gain is not None:
+            g = np.asarray(pad_gain, dtype=np.float64)
+            if g.ndim > 1 or (g.ndim == 1 and g.shape != (_abi.NUM_PADS,)):
+                raise ValueError(f"pad_gain must be {_abi.NUM_PADS} factors (or one for every pad), got shape {g.shape}")
+            g = np.broadcast_to(g, (_abi.NUM_PADS,))
+            if not np.all(np.isfinite(g) & (g >= 0.0)):
+                raise ValueError("pad gains must be finite and >= 0")
+            pad_gain = np.ascontiguousarray(g)
+        self.pad_gain = pad_gain
+        if isinstance(stream, (bool, np.bool_)) or int(stream) != stream or not 0 <= int(stream) < 1 << 30:
+            raise ValueError(f"gain stream must be an integer in [0, 2^30), got {stream!r}")
+        self.stream = int(stream)
+        self.quantiles = normal_quantile_table() if self.rel_variance > 0.0 else None
+
+    @property
+    def on(self) -> bool:
+        """Anything that changes a charge."""
+        return self.rel_variance > 0.0 or self.pad_gain is not None
+
+    def token(self):
+        if not self.on:
+            return None
+        return (self.rel_variance, None if self.pad_gain is None else self.pad_gain.tobytes(), self.stream)
+
+    def desc(self) -> _abi.TraceGainDesc:
+        """(the descriptor points into ``self.pad_gain`` and the quantile table: keep the settings alive over the call)"""
+        return _abi.TraceGainDesc(self.rel_variance, _abi.dptr(self.pad_gain), _abi.dptr(self.quantiles), self.stream, 0)
+
+
+def _checked_gain(gain):
+    if gain is not None and not isinstance(gain, GainSettings):
+        raise TypeError("gain must be a GainSettings or None")
+    return gain
+
+
+def configure_gain(ctx: _abi.Context, gain: GainSettings | None) -> None:
+    """``attpc_trace_configure_gain`` unless this ctx already holds the same gain (``None``, or a gain that changes
+    nothing: the stage off, which is also what a new context holds)."""
+    gain = _checked_gain(gain)
+    if gain is None or not gain.on:
+        ctx.configure("trace_gain", None, "attpc_trace_configure_gain", None)
+    else:
+        ctx.configure("trace_gain", gain.token(), "attpc_trace_configure_gain", gain.desc())
+
+
+def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, seed: int = 0, first_event: int = 0,
+                   gain: GainSettings | None = None) -> np.ndarray:
+    """The gain stage alone on any host cloud in CSR form (``attpc_gain_rows``; the kernel of the fused path):
+    offsets [n+1], points [P,3] (pad, time bucket, electrons) -> the gained charge of every row [P] f64 (rows outside
+    the offsets' range keep 0).  ``gain``: configured first (None: the stage off, the charges come back as they are).
+    Event i of the call is the global event ``first_event + i``."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = len(offsets) - 1
+    if n < 0:
+        raise ValueError("offsets needs n_events + 1 entries")
+    seed, first_event, _ = _abi.check_id_range(seed, first_event, n)
+    if n and offsets[-1] > len(points):
+        raise ValueError("points do not hold the rows the offsets name")
+    configure_gain(ctx, gain)
+    gained = np.zeros(len(points), dtype=np.float64)
+    ctx.check(ctx.lib.attpc_gain_rows(ctx.handle, seed, first_event, n, _abi.iptr(offsets, _abi.C.c_int64),
+                                      _abi.dptr(points), _abi.dptr(gained)), "attpc_gain_rows")
+    return gained
+
+
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
-                         baseline: BaselineSettings | None = None, **trace_kwargs) -> None:
+                         baseline: BaselineSettings | None = None, gain: GainSettings | None = None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
-    the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``) and the Fourier
-    baseline (default None: off, the peaks stand on the configured pedestals)."""
+    the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
+    baseline (default None: off, the peaks stand on the configured pedestals) and the micromegas gain (default None:
+    off)."""
     from .simulator import configure_spyral
 
     peaks = PeakSettings() if peaks is None else peaks
@@ -513,27 +641,28 @@ def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings 
     configure_spyral(config, ctx)
     configure_peaks(ctx, peaks)
     configure_baseline(ctx, baseline)
+    configure_gain(ctx, gain)
 
 
 def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
                               seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
                               peaks: PeakSettings | None = None, capacity_per_event: int = 2048,
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
-                              **trace_kwargs):
+                              gain: GainSettings | None = None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
     before any suppression, stats dict: the cloud's run statistics with ``n_points`` = the rows, plus ``n_rows`` /
     ``row_checksum``, and with ``trigger`` (a ``TriggerSettings``; None = off; its ``gate`` leaves the events that did
-    not fire without rows) its records [n] under ``"trigger"``)."""
+    not fire without rows) its records [n] under ``"trigger"``).  ``gain`` as simulate_batch_traces takes it."""
     from .simulator import run_batch
 
     peaks = PeakSettings() if peaks is None else peaks
-    validate_trace_kwargs(config, trace_kwargs)  # (before the first library call)
+    validate_trace_kwargs(config, trace_kwargs, gain)  # (before the first library call)
     ctx = ctx or _abi.default_context()
 
     def configure(c):
-        configure_trace_rows(config, c, peaks, baseline, **trace_kwargs)
+        configure_trace_rows(config, c, peaks, baseline, gain, **trace_kwargs)
         configure_trigger(c, trigger)
 
     arrays, stats = run_batch("attpc_det_run_trace_rows", momenta, vertices, proton_numbers, mass_numbers, config, seed,

@@ -151,25 +151,28 @@ class SpyralWriter(_RollingWriter):
 
     def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
                  first_run_number: int = 0, npz_fallback: bool = True, *, peaks=None, baseline=None,
-                 noise_seed: int = 0, **trace_kwargs):
+                 noise_seed: int = 0, gain=None, **trace_kwargs):
         """``peaks`` (keyword only; a ``detector.traces.PeakSettings``, default None = the reference's writer: one row
         per cloud point): the rows are the peaks of the event's digitised pad traces instead (EXTENSION, trace rows of
         include/attpc_engine.h), made on the device with the trace settings ``trace_kwargs`` (response, threshold,
         offset, noise_sigma / noise_table, pedestals, noise_stream, readout, readout_pads as
         ``detector.traces.configure_traces`` takes them); ``noise_seed`` keys the draws of ``write``, a run keys them on
         its own seed.  ``baseline`` (a ``detector.traces.BaselineSettings``, default None = the peaks stand on the
-        configured pedestals): Spyral's Fourier baseline is removed from the traces first.  The files have the same
-        datasets either way."""
+        configured pedestals): Spyral's Fourier baseline is removed from the traces first.  ``gain`` (a
+        ``detector.traces.GainSettings``, default None = off): the micromegas gain of the traces, keyed like the noise.
+        The files have the same datasets either way."""
         self.response = get_response(config).copy()
         self.peaks = peaks
         self.baseline = baseline
-        if peaks is None and (trace_kwargs or noise_seed or baseline is not None):
-            given = sorted(trace_kwargs) + (["noise_seed"] if noise_seed else []) + (["baseline"] if baseline is not None else [])
+        self.gain = gain
+        if peaks is None and (trace_kwargs or noise_seed or baseline is not None or gain is not None):
+            given = (sorted(trace_kwargs) + (["noise_seed"] if noise_seed else []) + (["baseline"] if baseline is not None else [])
+                     + (["gain"] if gain is not None else []))
             raise TypeError(f"SpyralWriter takes trace settings only with peaks=: {given}")
         if peaks is not None:
             from .traces import validate_trace_kwargs
 
-            validate_trace_kwargs(config, trace_kwargs)
+            validate_trace_kwargs(config, trace_kwargs, gain)
             self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
         self._trace_kwargs = dict(trace_kwargs)
         super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)
@@ -187,7 +190,7 @@ class SpyralWriter(_RollingWriter):
             from .traces import clouds_to_trace_rows, configure_trace_rows
 
             ctx = _abi.default_context()
-            configure_trace_rows(config, ctx, self.peaks, self.baseline, **self.trace_kwargs())
+            configure_trace_rows(config, ctx, self.peaks, self.baseline, self.gain, **self.trace_kwargs())
             data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
             _, rows, out_labels, _ = clouds_to_trace_rows(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
                                                           seed=self.noise_seed, first_event=event_number)
@@ -230,7 +233,10 @@ class TraceWriter(_RollingWriter):
     the dataset pedestals when pedestals are given.  Without noise the files are those of the noiseless writer.
     ``readout`` ("hit", "partial" or "full") and ``readout_pads`` read out noise-only pads as well (label -1;
     ``detector.traces.configure_traces``); off hit mode every file records the attribute readout and the dataset
-    readout_pads (the pad ids of the readout set), in hit mode the files are those of a writer without them."""
+    readout_pads (the pad ids of the readout set), in hit mode the files are those of a writer without them.
+    ``gain`` (a ``detector.traces.GainSettings``, default None = off) is the micromegas gain of the traces, keyed like
+    the noise; every file of a writer with a gain records the attributes gain_rel_variance and gain_stream, and the
+    dataset pad_gain when a gain map is given."""
 
     group = "trace"
 
@@ -238,8 +244,12 @@ class TraceWriter(_RollingWriter):
                  first_run_number: int = 0, npz_fallback: bool = True, response: np.ndarray | None = None,
                  threshold: float | None = None, offset: int = 0, noise_sigma: float = 0.0, noise_table=None,
                  pedestals=None, noise_stream: int = 0, noise_seed: int = 0, readout: str = "hit",
-                 readout_pads=None):
-        from .traces import NoiseSettings, ReadoutSettings, trace_settings
+                 readout_pads=None, gain=None):
+        from .traces import GainSettings, NoiseSettings, ReadoutSettings, trace_settings
+
+        if gain is not None and not isinstance(gain, GainSettings):
+            raise TypeError("gain must be a GainSettings or None")
+        self.gain = gain
 
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.response = self.response.copy()
@@ -260,6 +270,11 @@ class TraceWriter(_RollingWriter):
         if self.readout.token() is not None:
             f.set_attr("readout", self.readout.name)
             f.create_dataset("readout_pads", self.readout.pads)
+        if self.gain is not None and self.gain.on:
+            f.set_attr("gain_rel_variance", self.gain.rel_variance)
+            f.set_attr("gain_stream", self.gain.stream)
+            if self.gain.pad_gain is not None:
+                f.create_dataset("pad_gain", self.gain.pad_gain)
         return f
 
     def noise_kwargs(self) -> dict:
@@ -274,11 +289,12 @@ class TraceWriter(_RollingWriter):
 
     def write(self, data: np.ndarray, labels: np.ndarray, config: Config, event_number: int) -> None:
         """One event's cloud [P,3] -> its traces on the device (``clouds_to_traces``) -> datasets."""
-        from .traces import clouds_to_traces, configure_traces
+        from .traces import clouds_to_traces, configure_gain, configure_traces
 
         ctx = _abi.default_context()
         configure_traces(config, ctx, self.response, self.threshold, self.offset, **self.noise_kwargs(),
                          **self.readout_kwargs())
+        configure_gain(ctx, self.gain)
         data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
         _, pads, samples, out_labels, _ = clouds_to_traces(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
                                                            seed=self.noise_seed, first_event=event_number)

@@ -164,6 +164,21 @@ class Engine:
         _, pads, samples, _ = arrays.result()
         return {**res, "pads": pads, "samples": samples, "trace": arrays.sums(), **self._trigger_result(n_events)}
 
+    # ---------------------------------------------------------------- micromegas gain of the pad traces
+    def configure_gain(self, gain=None, **parameters) -> None:
+        """The micromegas gain of the traces (include/attpc_engine.h): a ``detector.traces.GainSettings`` or its
+        keywords (rel_variance or theta, pad_gain, stream) turn it on -- the traces of ``run_traces``,
+        ``run_trace_rows`` and ``run_trigger`` are then made from every cloud row's gained charge (avalanche
+        fluctuations and the pad's gain factor), keyed on the run's seed and the global event ids --, neither turns it
+        off (the default).  The clouds of ``run`` and the rows of ``run_spyral`` never change."""
+        from .detector.traces import GainSettings, configure_gain
+
+        if gain is not None and parameters:
+            raise TypeError("give a GainSettings or its keywords, not both")
+        if parameters:
+            gain = GainSettings(**parameters)
+        configure_gain(self.ctx, gain)
+
     # ---------------------------------------------------------------- multiplicity trigger on the pad traces
     def configure_trigger(self, trigger=None, **parameters) -> None:
         """The multiplicity trigger of the traces (include/attpc_engine.h): a ``detector.traces.TriggerSettings`` or its
@@ -331,7 +346,8 @@ def _selected_batch(res: dict, key: str):
 
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
-              batch_size: int = 65536, context: _abi.Context | None = None, selection=None, trigger=None) -> None:
+              batch_size: int = 65536, context: _abi.Context | None = None, selection=None, trigger=None,
+              gain=None) -> None:
     """run_kinematics_pipeline + run_simulation + SpyralWriter without the kinematics file and with
     the response / threshold / row conversion / z-sort done on the GPU: per event with a non-empty
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
@@ -345,10 +361,14 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     plain clouds, a trace writer raises ValueError); event numbers stay the global ones, the file roll-over counts
     written events.  ``trigger`` (a ``detector.traces.TriggerSettings``): only the events the multiplicity trigger fires
     on reach the writer, under their own event numbers -- a writer that receives traces or trace rows (for the latter
-    the device skips the peak work of the others too), any other raises ValueError."""
+    the device skips the peak work of the others too), any other raises ValueError.  ``gain`` (a
+    ``detector.traces.GainSettings``; default: the writer's own ``gain``, None = off): the micromegas gain of the traces
+    -- again a writer that receives traces or trace rows, any other raises ValueError."""
     engine = Engine(pipeline, config, indices, context=context)
     seed = pipeline.seed if seed is None else int(seed)
     kind, emit = delivery_of(writer, config)
+    if gain is not None and kind not in ("traces", "trace_rows"):
+        raise ValueError("a gain acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
     if trigger is not None and kind not in ("traces", "trace_rows"):
         raise ValueError("a trigger delivers traces or trace rows: writers of Spyral rows or clouds are not supported")
     if selection is not None:
@@ -378,6 +398,7 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
         raise AttributeError("run_fused needs a writer that offers write_rows or write_traces")
     if kind in ("traces", "trace_rows"):  # (None: whatever an earlier use of the context left is turned off)
         engine.configure_trigger(trigger if trigger is None or kind == "traces" else trigger.gated())
+        engine.configure_gain(getattr(writer, "gain", None) if gain is None else gain)
 
     def batch(start, stop):
         if kind == "traces":

@@ -743,6 +743,67 @@ ATTPC_API int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int
                                      const int16_t* samples, const int16_t* pedestals, const attpc_trigger_desc* desc,
                                      attpc_trigger_record* out);
 
+/* ---- micromegas gain of the traces (opt-in: off by default, and with it off every output of every entry point is bit
+ * for bit what it is without this section and no buffer of the stage is allocated) ----
+ * Without this stage a cloud row of q electrons lands on its pad as exactly q * R[...]: one gain for every electron and
+ * every pad.  The stage puts the detector's own amplitude response between the assembled cloud and the trace kernels:
+ * the avalanche statistics of the micromegas (a Polya-distributed single-electron gain) and pad-to-pad gain differences
+ * (what Spyral's gain-match file corrects).  The reference stops at point clouds and has no counterpart (parity is
+ * unpinned there, as for the traces themselves); tests/gain_reference.py restates the stage in numpy.
+ * Settings (attpc_trace_gain_desc):
+ *   - rel_variance f in [0, 1]: the relative variance of the single-electron gain, 1 / (1 + theta) for a Polya
+ *     parameter theta >= 0; a bucket of q electrons then has a relative amplitude spread of sqrt(f / q).  f = 0: pad
+ *     gains only.
+ *   - pad_gain [ATTPC_NUM_PADS], finite and >= 0; NULL = 1.0 everywhere.
+ *   - stream < 2^30 draws another realisation on the same physics.
+ *   - quantiles Z[0 .. ATTPC_GAIN_KNOTS - 1], finite and non-decreasing doubles: the inverse CDF of the standardised
+ *     fluctuation (mean 0, variance 1) at equally spaced knots.  Required when f > 0, ignored when f = 0.
+ * Gained charge of a cloud row of event e (global id), pad p, t = floor(tau) and electrons q:
+ *   - q == 0: q' = 0.  Otherwise
+ *       u  = word 0 of Philox4x32-10(counter = (e[31:0], e[63:32], p * 512 + t, 0x40000000 | stream),
+ *                                   key = (seed[31:0], seed[63:32]))
+ *       i  = u >> 20,  w = (double)(u & 0xFFFFF) * 2^-20
+ *       z  = Z[i] + (Z[i + 1] - Z[i]) * w
+ *       r  = c / q, with c = f / 9.0 computed once on the host in f64
+ *       s  = sqrt(r)
+ *       x  = max((1.0 - r) + z * s, 0.0)         (a NaN, which only a subnormal q can produce, counts as 0)
+ *       q' = ((q * x) * x) * x
+ *     the Wilson-Hilferty form of Gamma(shape q / f, scale f), the sum of q Polya gains of mean 1.  With f = 0 no draw
+ *     is made and x = 1: q' = q exactly.
+ *   - q'' = q' * pad_gain[p].
+ *   - every operation above is rounded once (no fused multiply-add); / and sqrt are the correctly rounded f64
+ *     operations.
+ * Effect: the trace contract holds with q'' in place of q_r in A_p[j].  The label rule still uses the cloud's own q.
+ * Rows of one event have distinct (pad, t), so every row has a counter of its own; the domain 0x40000000 | stream is
+ * disjoint from every other draw's (0, 1 + row, 0x200 + entry, the noise's 0x80000000 | stream, and the jitter
+ * generators).  q'' is a pure function of (seed, global event id, pad, t, q): it does not depend on chunking, GPU
+ * count or what shares the launch.
+ * Unchanged: every cloud output, attpc_run_stats, event_points, the cloud-based Spyral rows, and the row order.
+ * Device storage: 8 B per cloud row of a chunk while the stage is on. */
+#define ATTPC_GAIN_KNOTS 4097
+
+typedef struct attpc_trace_gain_desc {
+  double rel_variance;      /* f in [0, 1] */
+  const double* pad_gain;   /* [ATTPC_NUM_PADS], NULL = 1.0 everywhere */
+  const double* quantiles;  /* [ATTPC_GAIN_KNOTS]; may be NULL when rel_variance == 0 */
+  uint32_t stream;          /* < 2^30 */
+  int32_t reserved;
+} attpc_trace_gain_desc;
+
+/* desc == NULL turns the stage off (the default); so does rel_variance == 0 without a pad_gain.  Independent of the
+ * other attpc_trace_configure_* calls: no call resets another.  ATTPC_E_INVALID for rel_variance outside [0, 1] or not
+ * finite, a negative or non-finite pad gain, a decreasing or non-finite table, a missing table with rel_variance > 0,
+ * or stream >= 2^30.  With the stage on it acts in attpc_sim_run_traces, attpc_det_run_traces, attpc_traces_at,
+ * attpc_traces and the trace-row entry points (attpc_*_run_trace_rows, attpc_trace_rows_at); through their traces it
+ * reaches the Fourier baseline and the trigger. */
+ATTPC_API int32_t attpc_trace_configure_gain(attpc_ctx* ctx, const attpc_trace_gain_desc* desc);
+/* The stage alone on any host cloud, through the same kernel: offsets [n_events + 1], points [rows, 3] (pad, tau,
+ * electrons) -> gained [rows] (q'' of every row; event i of the call is the global event first_event + i).  The rows
+ * are validated as attpc_traces validates them.  With the stage off gained is the cloud's own charge.  The id-range
+ * rules at the top apply. */
+ATTPC_API int32_t attpc_gain_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events,
+                                  const int64_t* offsets, const double* points, double* gained);
+
 /* ---- event and track summaries of a device-resident run (opt-in: without a call of the entry points below every
  * output of every other entry point is what it is without this section) ----
  * A summary run is a device-resident run (attpc_sim_run with out == NULL: same chunks, no event-ordered copy of the

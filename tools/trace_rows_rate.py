@@ -17,12 +17,16 @@ off in the odd ones (``--baseline-first``), so that order, clock and warm-up do 
 (the parent commit of the baseline stage) the driver adds
   (iii) run_trace_rows resident with the stage off stays within the spread of the yardstick's;
   and the cost of the stage per event, 1 / rate(on) - 1 / rate(off), from the medians.
+A library with the micromegas gain (attpc_trace_configure_gain) gets two more legs: run_traces and run_trace_rows
+resident with the stage on (``--gain-theta``, a Polya gain with a gain map of its own), after the legs with it off in
+the even repeats and before them in the odd ones, as the baseline leg; the driver prints the cost of the stage per
+event from the medians.  (i) and (iii) are the verdicts on the stage being off.
 ``--modes`` picks the trace modes, ``--resident-only`` leaves the delivered legs out.
 ``--out FILE`` appends the children's JSON lines.
 
     python tools/trace_rows_rate.py [--yardstick attpc_engine_amd/_lib/libattpc_parent.so] [--events N]
                                     [--deliver-events M] [--reps K] [--workloads o16aa,be10dp] [--out FILE]
-                                    [--modes hit,partial] [--resident-only] [--baseline-scale S]
+                                    [--modes hit,partial] [--resident-only] [--baseline-scale S] [--gain-theta T]
     python tools/trace_rows_rate.py --child WORKLOAD   (one measurement of the library ATTPC_HIP_LIBRARY names, or of
                                                         the package's own without it)
 """
@@ -49,7 +53,7 @@ ROW_BYTES = 8 * 8 + 8
 
 
 def child(name: str, events: int, deliver_events: int, modes, resident_only: bool, baseline_scale: float,
-          baseline_first: bool) -> None:
+          baseline_first: bool, gain_theta: float) -> None:
     from attpc_engine_amd import _abi, workloads
     from attpc_engine_amd.engine import Engine
     from attpc_engine_amd.outputs import RowArrays, TraceArrays
@@ -59,6 +63,7 @@ def child(name: str, events: int, deliver_events: int, modes, resident_only: boo
     # (the yardstick is a build of the same ABI version from before the trace rows: the binding loads it without them)
     has_rows = all(hasattr(lib, name) for name in _abi.TRACE_ROW_SYMBOLS)
     has_baseline = has_rows and all(hasattr(lib, name) for name in _abi.BASELINE_SYMBOLS)
+    has_gain = has_rows and all(hasattr(lib, name) for name in _abi.GAIN_SYMBOLS)
     pipeline, config, indices = workloads.WORKLOADS[name]()
     eng = Engine(pipeline, config, indices, context=ctx)
     if has_rows:
@@ -84,7 +89,21 @@ def child(name: str, events: int, deliver_events: int, modes, resident_only: boo
                       "attpc_sim_run_traces")
             return int(out.n_rows)
 
+        def gain_leg(call, key):  # the same call with the micromegas gain on, then off again for what follows
+            import numpy as np
+
+            pad_gain = np.random.default_rng(1).uniform(0.8, 1.2, size=_abi.NUM_PADS)
+            eng.configure_gain(theta=gain_theta, pad_gain=pad_gain)
+            t, rows = timed(call, events)
+            eng.configure_gain()
+            line.update({f"{key}_gain_resident_events_per_s": events / t, f"{key}_gain_per_event": rows / events,
+                         "gain_theta": gain_theta, "gain_first": baseline_first})
+
+        if has_gain and baseline_first:
+            gain_leg(traces_resident, "traces")
         t, rows = timed(traces_resident, events)
+        if has_gain and not baseline_first:
+            gain_leg(traces_resident, "traces")
         per_event = rows / events
         line.update(traces_resident_events_per_s=events / t, trace_rows_per_event=per_event,
                     trace_bytes_per_event=per_event * TRACE_ROW_BYTES)
@@ -117,12 +136,16 @@ def child(name: str, events: int, deliver_events: int, modes, resident_only: boo
 
             if has_baseline and baseline_first:
                 baseline_leg()
+            if has_gain and baseline_first:
+                gain_leg(rows_resident, "rows")
             t, rows = timed(rows_resident, events)
             per_event = rows / events
             line.update(rows_resident_events_per_s=events / t, rows_per_event=per_event,
                         row_bytes_per_event=per_event * ROW_BYTES)
             if has_baseline and not baseline_first:
                 baseline_leg()
+            if has_gain and not baseline_first:
+                gain_leg(rows_resident, "rows")
             if not resident_only:
                 row_arrays = RowArrays(deliver_events, int(per_event * deliver_events * 1.3) + 4096, ctx.pinned_empty, width=8)
 
@@ -157,13 +180,14 @@ def main() -> None:
     ap.add_argument("--resident-only", action="store_true")
     ap.add_argument("--baseline-scale", type=float, default=20.0)
     ap.add_argument("--baseline-first", action="store_true", help="child: the baseline leg before the leg without it")
+    ap.add_argument("--gain-theta", type=float, default=0.5, help="Polya parameter of the legs with the micromegas gain on")
     args = ap.parse_args()
     modes = args.modes.split(",")
     if any(m not in MODES for m in modes):
         raise SystemExit(f"--modes takes {list(MODES)}")
     if args.child:
         child(args.child, args.events, args.deliver_events, modes, args.resident_only, args.baseline_scale,
-              args.baseline_first)
+              args.baseline_first, args.gain_theta)
         return
 
     new = ROOT / "attpc_engine_amd" / "_lib" / "libattpc_hip.so"
@@ -178,7 +202,7 @@ def main() -> None:
                 env = dict(os.environ, ATTPC_HIP_LIBRARY=str(lib))
                 proc = subprocess.run([sys.executable, __file__, "--child", name, "--events", str(args.events),
                                        "--deliver-events", str(args.deliver_events), "--modes", args.modes,
-                                       "--baseline-scale", str(args.baseline_scale)]
+                                       "--baseline-scale", str(args.baseline_scale), "--gain-theta", str(args.gain_theta)]
                                       + (["--resident-only"] if args.resident_only else [])
                                       + (["--baseline-first"] if rep % 2 else []), env=env, capture_output=True,
                                       text=True, timeout=300)
@@ -226,6 +250,11 @@ def main() -> None:
             if on:
                 (fm, flo, fhi), (nm, _, _) = _spread(on), _spread(off)
                 print(f"  resident  rows, baseline on {fm:10.0f} ({flo:.0f} .. {fhi:.0f}): {1e6 / fm - 1e6 / nm:+.2f} us per event")
+            for key, plain in (("traces", "traces_resident_events_per_s"), ("rows", "rows_resident_events_per_s")):
+                gained = leg("new", f"{key}_gain_resident_events_per_s")
+                if gained:
+                    (gm, glo, ghi), (nm, _, _) = _spread(gained), _spread(leg("new", plain))
+                    print(f"  resident  {key}, gain on {gm:10.0f} ({glo:.0f} .. {ghi:.0f}): {1e6 / gm - 1e6 / nm:+.2f} us per event")
             print("  " + "; ".join(verdicts))
 
 
