@@ -16,6 +16,7 @@ from .. import _abi
 from ..outputs import RowArrays, call_with_capacity
 from .luts import build_det_desc, build_layout, species_for
 from .parameters import Config
+from .traces import TraceChain
 from .writer import SimulationWriter
 
 
@@ -155,12 +156,44 @@ def delivery_of(writer, config: Config):
     any SimulationWriter)."""
     if callable(getattr(writer, "write_traces", None)):
         return "traces", writer.write_traces
-    if callable(getattr(writer, "write_rows", None)) and getattr(writer, "peaks", None) is not None:
-        # (SpyralWriter(peaks=...): the rows are the peaks of the event's pad traces, made on the device)
-        return "trace_rows", lambda rows, labels, event: writer.write_rows(rows, labels, event, presorted=True)
     if callable(getattr(writer, "write_rows", None)):
-        return "rows", lambda rows, labels, event: writer.write_rows(rows, labels, event, presorted=True)
+        # (SpyralWriter(peaks=...): the rows are the peaks of the event's pad traces, made on the device)
+        kind = "rows" if getattr(writer, "peaks", None) is None else "trace_rows"
+        return kind, lambda rows, labels, event: writer.write_rows(rows, labels, event, presorted=True)
     return "cloud", lambda points, labels, event: writer.write(points, labels, config, event)
+
+
+def plan_delivery(writer, config: Config, selection=None, trigger=None, gain=None, plain_clouds: bool = True):
+    """What run_simulation and run_fused may be asked for with ``writer`` -> (kind, emit, chain): ``delivery_of`` and,
+    for a writer of traces or trace rows, the ``detector.traces.TraceChain`` to run (else None): ``writer.chain`` -- a
+    writer without one: the TraceChain fields it has as attributes (``noise`` and ``readout`` as settings objects), the
+    rest at their defaults -- on the run's ``config`` (it fills in a response or threshold the writer left unset), with
+    ``trigger``, gated for trace rows, and ``gain`` if given, else the writer's.  ValueError for a ``selection`` with a
+    trace writer and for a ``trigger`` or a ``gain`` with any other; AttributeError for plain clouds without a
+    selection unless ``plain_clouds``."""
+    kind, emit = delivery_of(writer, config)
+    traces = kind in ("traces", "trace_rows")
+    if selection is not None and traces:
+        raise ValueError("a selection delivers Spyral rows or clouds: trace writers are not supported")
+    if trigger is not None and not traces:
+        raise ValueError("a trigger delivers traces or trace rows: writers of Spyral rows or clouds are not supported")
+    if gain is not None and not traces:
+        raise ValueError("a gain acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
+    if kind == "cloud" and selection is None and not plain_clouds:
+        raise AttributeError("run_fused needs a writer that offers write_rows or write_traces")
+    if not traces:
+        return kind, emit, None
+    names = ("response", "threshold", "offset", "noise", "readout", "gain", "peaks", "baseline")
+    chain = getattr(writer, "chain", None) or TraceChain(config, **{n: getattr(writer, n) for n in names if hasattr(writer, n)})
+    if trigger is not None and kind == "trace_rows":
+        trigger = trigger.gated()
+    return kind, emit, chain.replace(config=config, trigger=trigger, gain=chain.gain if gain is None else gain)
+
+
+def selected_events(res: dict, key: str):
+    """A selected call's result as ``deliver_events`` takes a batch (``key``: "rows" or "points"): event_points masked
+    by passed, so that its loop skips the rejected events as it skips the empty ones."""
+    return res["offsets"], np.where(res["passed"], res["event_points"], 0), res[key], res["labels"]
 
 
 def fired_events(offsets, event_points, records, *arrays):
@@ -222,14 +255,7 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     print(f"Output will be written to {writer.get_directory_name()}.")
     rng = default_rng(seed)
     run_seed = int(rng.integers(0, 1 << 63))
-    kind, emit = delivery_of(writer, config)
-    if selection is not None and kind not in ("rows", "cloud"):
-        raise ValueError("a selection delivers Spyral rows or clouds: trace writers are not supported")
-    if trigger is not None and kind not in ("traces", "trace_rows"):
-        raise ValueError("a trigger delivers traces or trace rows: writers of Spyral rows or clouds are not supported")
-    if gain is not None and kind not in ("traces", "trace_rows"):
-        raise ValueError("a gain acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
-    gain = getattr(writer, "gain", None) if gain is None else gain
+    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain)
 
     def batch(start, stop):
         vertices, momenta = reader.read(start, stop)
@@ -239,23 +265,11 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
 
             res = simulate_batch_selected(*args, selection, kind="spyral" if kind == "rows" else "cloud", first_event=start,
                                           response=getattr(writer, "response", None))
-            # event_points masked by passed: the loop of deliver_events skips the rejected events as the empty ones
-            return (res["offsets"], np.where(res["passed"], res["event_points"], 0),
-                    res["rows" if kind == "rows" else "points"], res["labels"])
-        if kind == "traces":  # the pad traces are made on the device behind the scatter (attpc_det_run_traces)
-            from .traces import simulate_batch_traces
-
-            offsets, pads, samples, labels, raw_points, stats = simulate_batch_traces(
-                *args, first_event=start, response=writer.response, threshold=writer.threshold, offset=writer.offset,
-                **writer.noise_kwargs(), **writer.readout_kwargs(), trigger=trigger, gain=gain)
-            return fired_events(offsets, raw_points, stats.get("trigger"), pads, samples, labels)
-        if kind == "trace_rows":  # ... and their peaks as Spyral rows behind them (attpc_det_run_trace_rows)
-            from .traces import simulate_batch_trace_rows
-
-            offsets, rows, labels, raw_points, stats = simulate_batch_trace_rows(
-                *args, first_event=start, peaks=writer.peaks, baseline=getattr(writer, "baseline", None),
-                trigger=None if trigger is None else trigger.gated(), gain=gain, **writer.trace_kwargs())
-            return fired_events(offsets, raw_points, stats.get("trigger"), rows, labels)
+            return selected_events(res, "rows" if kind == "rows" else "points")
+        if chain is not None:  # the pad traces, or their peaks as Spyral rows, are made on the device behind the scatter
+            offsets, *arrays, raw_points, stats = chain.run_batch(
+                kind == "trace_rows", momenta, vertices, proton_numbers, mass_numbers, run_seed, nuclei_to_sim, start)
+            return fired_events(offsets, raw_points, stats.get("trigger"), *arrays)
         if kind == "rows":
             offsets, rows, labels, raw_points, _ = simulate_batch_spyral(
                 *args, first_event=start, response=getattr(writer, "response", None))

@@ -39,9 +39,16 @@ has a relative amplitude spread of sqrt(f / q)) and a per-pad gain map, applied 
 charge before the trace kernels read it -- a pure function of (seed, global event id, pad, time bucket, charge)
 (include/attpc_engine.h; ``tests/gain_reference.py`` restates it).  ``clouds_to_gain`` is that stage alone on any host
 cloud.
+
+Every stage is a settings class with its context slot (``slot``), its C call (``call``), ``token()`` -- its content,
+None when the stage changes nothing -- and ``desc()``, the call's descriptor; ``configure_stage`` applies any of them.
+``TraceChain`` is one whole trace configuration, validated once: the entry points build it from their keywords, the
+writers hold one, the runs configure it in one order.  Adding a trace stage: such a settings class, one field of the
+chain, and one line in ``TraceChain.configure``.
 """
 from __future__ import annotations
 
+import copy
 import math
 import statistics
 
@@ -84,9 +91,19 @@ def gaussian_noise_table(sigma: float) -> tuple[np.ndarray, int]:
     return np.array(cdf, dtype=np.uint32), -half
 
 
+def configure_stage(ctx: _abi.Context, stage, settings) -> None:
+    """``lib.<stage.call>`` with the descriptor of ``settings`` (an instance of the settings class ``stage``) unless the
+    ctx's ``stage.slot`` already holds the same content; None, or settings that change nothing (``token()`` None): the
+    stage off, a NULL descriptor, which is also what a new context holds."""
+    token = None if settings is None else settings.token()
+    ctx.configure(stage.slot, token, stage.call, None if token is None else settings.desc())
+
+
 class NoiseSettings:
     """The validated noise of a trace configuration: cdf [n_levels - 1] u32, min_level, n_levels (0 = no noise draw),
     pedestals [ATTPC_NUM_PADS] i16 or None, stream, sigma (NaN for a custom table, 0 without noise)."""
+
+    slot, call = "trace_noise", "attpc_trace_configure_noise"
 
     def __init__(self, noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0):
         if noise_table is not None and float(noise_sigma) != 0.0:
@@ -132,15 +149,15 @@ class NoiseSettings:
         return (self.cdf.tobytes(), self.min_level, self.n_levels, None if self.pedestals is None else
                 self.pedestals.tobytes(), self.stream)
 
+    def desc(self) -> _abi.TraceNoiseDesc:
+        """(the descriptor points into ``self.cdf`` and ``self.pedestals``: keep the settings alive over the call)"""
+        return _abi.TraceNoiseDesc(_abi.iptr(self.cdf, _abi.C.c_uint32), self.n_levels, self.min_level,
+                                   _abi.iptr(self.pedestals, _abi.C.c_int16), self.stream, 0)
+
 
 def configure_noise(ctx: _abi.Context, noise: NoiseSettings) -> None:
     """``attpc_trace_configure_noise`` unless this ctx already holds the same noise (decided on its content)."""
-    desc = None
-    if noise.on:
-        desc = _abi.TraceNoiseDesc(_abi.iptr(noise.cdf, _abi.C.c_uint32), noise.n_levels, noise.min_level,
-                                   None if noise.pedestals is None else _abi.iptr(noise.pedestals, _abi.C.c_int16),
-                                   noise.stream, 0)
-    ctx.configure("trace_noise", noise.token(), "attpc_trace_configure_noise", desc)
+    configure_stage(ctx, NoiseSettings, noise)
 
 
 READOUT_MODES = {"hit": _abi.READOUT_HIT, "partial": _abi.READOUT_PARTIAL, "full": _abi.READOUT_FULL}
@@ -175,6 +192,8 @@ class ReadoutSettings:
     """The validated readout of a trace configuration: ``name`` ("hit", "partial", "full"), ``mode``
     (ATTPC_READOUT_*), ``channels`` uint8 [ATTPC_NUM_PADS] (the readout set S, ignored in hit mode)."""
 
+    slot, call = "trace_readout", "attpc_trace_configure_readout"
+
     def __init__(self, readout: str = "hit", readout_pads=None):
         if readout not in READOUT_MODES:
             raise ValueError(f"readout must be one of {sorted(READOUT_MODES)}, got {readout!r}")
@@ -194,13 +213,14 @@ class ReadoutSettings:
     def token(self):
         return None if self.mode == _abi.READOUT_HIT else (self.mode, self.channels.tobytes())
 
+    def desc(self) -> _abi.TraceReadoutDesc:
+        """(the descriptor points into ``self.channels``: keep the settings alive over the call)"""
+        return _abi.TraceReadoutDesc(self.mode, 0, _abi.iptr(self.channels, _abi.C.c_uint8))
+
 
 def configure_readout(ctx: _abi.Context, readout: ReadoutSettings) -> None:
     """``attpc_trace_configure_readout`` unless this ctx already holds the same readout (decided on its content)."""
-    token, desc = readout.token(), None
-    if token is not None:
-        desc = _abi.TraceReadoutDesc(readout.mode, 0, _abi.iptr(readout.channels, _abi.C.c_uint8))
-    ctx.configure("trace_readout", token, "attpc_trace_configure_readout", desc)
+    configure_stage(ctx, ReadoutSettings, readout)
     ctx._trace_readout_rows = readout.rows_per_event()
 
 
@@ -240,6 +260,89 @@ def expected_noise_pads(noise_table, threshold: float, readout_pads=None, pedest
     return float(p[mask].sum())
 
 
+TRACE_KWARGS = ("response", "threshold", "offset", "noise_sigma", "noise_table", "pedestals", "noise_stream", "readout",
+                "readout_pads")
+
+
+class TraceChain:
+    """One trace configuration, validated here, before any library call: ``config``, the ``response`` [512] f64,
+    ``threshold`` and ``offset`` with their defaults filled in (``trace_settings``), the ``noise`` (a ``NoiseSettings``;
+    None = off) and the ``readout`` (a ``ReadoutSettings``; None = hit pads), and the stages that are None when off:
+    ``gain``, ``peaks`` (trace rows; None = ``PeakSettings()``), ``baseline`` and ``trigger``."""
+
+    def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
+                 gain=None, peaks=None, baseline=None, trigger=None):
+        self.config, self._given = config, (response, threshold)
+        self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
+        self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
+        self.gain, self.peaks, self.baseline, self.trigger = _checked_gain(gain), peaks, baseline, trigger
+
+    @classmethod
+    def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
+        """The chain of the trace settings a caller passes on as keywords (TRACE_KWARGS, as ``configure_traces``
+        describes them): TypeError for any other name, ValueError for a value that is refused."""
+        unknown = set(trace_kwargs) - set(TRACE_KWARGS)
+        if unknown:
+            raise TypeError(f"unexpected trace settings {sorted(unknown)}: configure_traces takes {list(TRACE_KWARGS)}")
+        get = trace_kwargs.get
+        return cls(config, get("response"), get("threshold"), get("offset", 0),
+                   NoiseSettings(get("noise_sigma", 0.0), get("noise_table"), get("pedestals"), get("noise_stream", 0)),
+                   ReadoutSettings(get("readout", "hit"), get("readout_pads")))
+
+    def replace(self, **fields) -> "TraceChain":
+        """The same chain with the given fields (config, gain, peaks, baseline, trigger; TypeError for any other)
+        replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger"}
+        if unknown:
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline and trigger, not {sorted(unknown)}")
+        chain = copy.copy(self)
+        vars(chain).update(fields)
+        if "config" in fields:
+            chain.response, chain.threshold, _ = trace_settings(chain.config, *self._given, self.offset)
+        _checked_gain(chain.gain)
+        return chain
+
+    def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
+        """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
+        trace, noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
+        baseline; trigger; gain.  A stage that is off is turned off, whatever an earlier use of the ctx left -- except
+        those of "trigger" and "gain" that ``keep`` names, which stay as the ctx holds them."""
+        from .simulator import configure_spyral
+
+        ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
+                      _abi.TraceDesc(_abi.dptr(self.response), self.threshold, self.offset, 0))
+        configure_noise(ctx, self.noise)
+        configure_readout(ctx, self.readout)
+        if rows:
+            configure_spyral(self.config, ctx)
+            configure_peaks(ctx, PeakSettings() if self.peaks is None else self.peaks)
+            configure_baseline(ctx, self.baseline)
+        if "trigger" not in keep:
+            configure_trigger(ctx, self.trigger)
+        if "gain" not in keep:
+            configure_gain(ctx, self.gain)
+
+    def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
+                  ctx: _abi.Context | None = None, capacity_per_event: int | None = None):
+        """simulate() + this chain on the device for n events: what ``simulate_batch_trace_rows`` (``rows``) or
+        ``simulate_batch_traces`` returns (``capacity_per_event``: None = the default of that entry point)."""
+        from .simulator import run_batch
+
+        ctx = ctx or _abi.default_context()
+
+        def configure(c):
+            self.configure(c, rows)
+            return 0 if rows else c._trace_readout_rows  # traces in full readout: |S| rows per event
+
+        arrays, stats = run_batch("attpc_det_run_trace_rows" if rows else "attpc_det_run_traces", momenta, vertices,
+                                  proton_numbers, mass_numbers, self.config, seed, indices, first_event, ctx,
+                                  (2048 if rows else 1024) if capacity_per_event is None else capacity_per_event, configure,
+                                  **(dict(holder=RowArrays, width=8, slack=1024) if rows else {}))
+        extra = trigger_result(ctx, len(arrays.offsets) - 1)
+        sums = ctx.trace_rows_last() if rows else arrays.sums()
+        return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
+
+
 def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold=None, offset: int = 0,
                      noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
                      readout: str = "hit", readout_pads=None) -> None:
@@ -249,33 +352,19 @@ def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold
     0 .. 4095; ``noise_stream`` in [0, 2^31) draws another noise realisation.  ``readout``: "hit" (default: only pads
     with cloud rows), "partial" (noise-only pads of ``readout_pads`` that cross the threshold too) or "full" (every pad
     of ``readout_pads``); ``readout_pads``: None = every pad not in BEAM_PADS, a boolean mask [ATTPC_NUM_PADS] or
-    unique pad ids.  Everything is validated before the first call to the library."""
-    response, threshold, offset = trace_settings(config, response, threshold, offset)
-    noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
-    readout = ReadoutSettings(readout, readout_pads)
-    ctx.configure("trace", (response.tobytes(), threshold, offset), "attpc_trace_configure",
-                  _abi.TraceDesc(_abi.dptr(response), threshold, offset, 0))
-    configure_noise(ctx, noise)
-    configure_readout(ctx, readout)
-
-
-TRACE_KWARGS = ("response", "threshold", "offset", "noise_sigma", "noise_table", "pedestals", "noise_stream", "readout",
-                "readout_pads")
+    unique pad ids.  Everything is validated before the first call to the library; the trigger and the gain stay as
+    the ctx holds them."""
+    chain = TraceChain(config, response, threshold, offset, NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream),
+                       ReadoutSettings(readout, readout_pads))
+    chain.configure(ctx, keep=("trigger", "gain"))
 
 
 def validate_trace_kwargs(config: Config, trace_kwargs: dict, gain=None) -> None:
     """The trace settings a caller passes on as keywords (``configure_traces``'s, TRACE_KWARGS), checked before any
     library call: TypeError for a name configure_traces does not take, ValueError for a value it would refuse.
     ``gain``: the ``GainSettings`` that goes with them (or None), TypeError for anything else."""
-    if gain is not None and not isinstance(gain, GainSettings):
-        raise TypeError("gain must be a GainSettings or None")
-    unknown = set(trace_kwargs) - set(TRACE_KWARGS)
-    if unknown:
-        raise TypeError(f"unexpected trace settings {sorted(unknown)}: configure_traces takes {list(TRACE_KWARGS)}")
-    get = trace_kwargs.get
-    trace_settings(config, get("response"), get("threshold"), get("offset", 0))
-    NoiseSettings(get("noise_sigma", 0.0), get("noise_table"), get("pedestals"), get("noise_stream", 0))
-    ReadoutSettings(get("readout", "hit"), get("readout_pads"))
+    _checked_gain(gain)
+    TraceChain.from_kwargs(config, **trace_kwargs)
 
 
 def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
@@ -291,23 +380,26 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     ``pad_checksum`` of the traces, and with ``trigger`` (a ``TriggerSettings``; None = off) its records [n] under
     ``"trigger"``).  ``gain`` (a ``GainSettings``; None = off): the micromegas gain of every cloud row's charge, keyed on
     ``seed`` and the global event ids like the noise."""
-    from .simulator import run_batch
+    chain = TraceChain(config, response, threshold, offset, NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream),
+                       ReadoutSettings(readout, readout_pads), gain, trigger=trigger)
+    return chain.run_batch(False, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
+                           capacity_per_event)
 
-    ReadoutSettings(readout, readout_pads)  # (validated before the first library call)
-    _checked_gain(gain)
-    ctx = ctx or _abi.default_context()
 
-    def configure(ctx):
-        configure_traces(config, ctx, response, threshold, offset, noise_sigma, noise_table, pedestals, noise_stream,
-                         readout, readout_pads)
-        configure_trigger(ctx, trigger)
-        configure_gain(ctx, gain)
-        return ctx._trace_readout_rows  # full readout: |S| rows per event
-
-    arrays, stats = run_batch("attpc_det_run_traces", momenta, vertices, proton_numbers, mass_numbers, config, seed,
-                              indices, first_event, ctx, capacity_per_event, configure)
-    extra = {} if trigger is None else {"trigger": ctx.trigger_last(len(arrays.offsets) - 1)}
-    return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **arrays.sums(), **extra})
+def _host_cloud(offsets, points, labels, seed, first_event):
+    """A host cloud in CSR form as the C ABI takes it, checked: (offsets i64, points [P,3] f64, labels i64 or None,
+    seed, first_event, n events)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = len(offsets) - 1
+    if n < 0:
+        raise ValueError("offsets needs n_events + 1 entries")
+    seed, first_event, _ = _abi.check_id_range(seed, first_event, n)
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+    if (labels is not None and len(points) != len(labels)) or (n and offsets[-1] > len(points)):
+        raise ValueError(f"points{'' if labels is None else ' / labels'} do not hold the rows the offsets name")
+    return offsets, points, labels, seed, first_event, n
 
 
 def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,
@@ -318,15 +410,7 @@ def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray
     the ctx holds a trigger (``configure_trigger``) its records [n] too, under ``"trigger"``).
     Event i of the call is the global event ``first_event + i``: its noise is keyed on (seed, first_event + i), and the
     pad checksum counts events from ``first_event``."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    labels = np.ascontiguousarray(labels, dtype=np.int64)
-    n = len(offsets) - 1
-    if n < 0:
-        raise ValueError("offsets needs n_events + 1 entries")
-    seed, first_event, _ = _abi.check_id_range(seed, first_event, n)
-    if len(points) != len(labels) or (n and offsets[-1] > len(points)):
-        raise ValueError("points / labels do not hold the rows the offsets name")
+    offsets, points, labels, seed, first_event, n = _host_cloud(offsets, points, labels, seed, first_event)
 
     def call(out):
         return ctx.lib.attpc_traces_at(ctx.handle, seed, first_event, n, _abi.iptr(offsets, _abi.C.c_int64),
@@ -335,8 +419,7 @@ def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray
     rows = int(offsets[-1] - offsets[0]) if n else 0
     rows = max(rows, ctx._trace_readout_rows * n)  # full readout: |S| rows per event
     arrays = call_with_capacity(ctx, n, max(16, rows), call, "attpc_traces_at")
-    records = trigger_records(ctx, n)
-    return (*arrays.result(), {**arrays.sums(), **({} if records is None else {"trigger": records})})
+    return (*arrays.result(), {**arrays.sums(), **trigger_result(ctx, n)})
 
 
 class PeakSettings:
@@ -344,6 +427,8 @@ class PeakSettings:
     (>= 1 samples between kept peaks), ``prominence`` (>= 0), ``min_width`` <= ``max_width`` (>= 0, samples at
     ``rel_height`` in (0, 1] of the prominence) and the amplitude ``threshold`` above the pedestal.  The defaults are
     this project's (they fit its GET response: a lone arrival is one peak 15.5 samples wide)."""
+
+    slot, call = "peaks", "attpc_trace_configure_peaks"
 
     def __init__(self, separation: float = 50.0, prominence: float = 20.0, min_width: float = 1.0,
                  max_width: float = 50.0, rel_height: float = 0.95, threshold: float = 40.0):
@@ -369,15 +454,14 @@ class PeakSettings:
 
 def configure_peaks(ctx: _abi.Context, peaks: PeakSettings | None) -> None:
     """``attpc_trace_configure_peaks`` unless this ctx already holds the same parameters (``None``: the stage off)."""
-    if peaks is None:
-        ctx.configure("peaks", None, "attpc_trace_configure_peaks", None)
-    else:
-        ctx.configure("peaks", peaks.token(), "attpc_trace_configure_peaks", peaks.desc())
+    configure_stage(ctx, PeakSettings, peaks)
 
 
 class BaselineSettings:
     """The validated Fourier baseline of the trace rows (``attpc_baseline_desc``, include/attpc_engine.h):
     ``window_scale`` (finite, > 0), Spyral's ``GetParameters.baseline_window_scale`` and its default."""
+
+    slot, call = "baseline", "attpc_trace_configure_baseline"
 
     def __init__(self, window_scale: float = 20.0):
         self.window_scale = float(window_scale)
@@ -392,12 +476,8 @@ class BaselineSettings:
 
 
 def configure_baseline(ctx: _abi.Context, baseline: BaselineSettings | None) -> None:
-    """``attpc_trace_configure_baseline`` unless this ctx already holds the same setting (``None``: the stage off, which
-    is also what a new context holds)."""
-    if baseline is None:
-        ctx.configure("baseline", None, "attpc_trace_configure_baseline", None)
-    else:
-        ctx.configure("baseline", baseline.token(), "attpc_trace_configure_baseline", baseline.desc())
+    """``attpc_trace_configure_baseline`` unless this ctx already holds the same setting (``None``: the stage off)."""
+    configure_stage(ctx, BaselineSettings, baseline)
 
 
 def remove_baseline(traces, window_scale: float = 20.0, ctx: _abi.Context | None = None, return_baseline: bool = False):
@@ -430,6 +510,8 @@ class TriggerSettings:
     together), ``groups`` ([ATTPC_NUM_PADS] integers: below 16 the pad's trigger group -- its CoBo; the map is the
     caller's --, 255 = the pad takes no part; None = every pad in group 0) and ``gate`` (trace rows only: an event that
     did not fire gets no rows)."""
+
+    slot, call = "trigger", "attpc_trace_configure_trigger"
 
     def __init__(self, threshold, window: int = 64, group_multiplicity: int = 1, min_groups: int = 1, groups=None,
                  gate: bool = False):
@@ -469,17 +551,13 @@ class TriggerSettings:
 
 
 def configure_trigger(ctx: _abi.Context, trigger: TriggerSettings | None) -> None:
-    """``attpc_trace_configure_trigger`` unless this ctx already holds the same setting (``None``: the stage off, which
-    is also what a new context holds)."""
-    if trigger is None:
-        ctx.configure("trigger", None, "attpc_trace_configure_trigger", None)
-    else:
-        ctx.configure("trigger", trigger.token(), "attpc_trace_configure_trigger", trigger.desc())
+    """``attpc_trace_configure_trigger`` unless this ctx already holds the same setting (``None``: the stage off)."""
+    configure_stage(ctx, TriggerSettings, trigger)
 
 
-def trigger_records(ctx: _abi.Context, n_events: int):
-    """The records of ctx's last trace or trace-row call if the ctx holds a trigger, else None."""
-    return ctx.trigger_last(n_events) if ctx._tokens["trigger"] is not None else None
+def trigger_result(ctx: _abi.Context, n_events: int) -> dict:
+    """``{"trigger": records [n_events]}`` of ctx's last trace or trace-row call if the ctx holds a trigger, else {}."""
+    return {"trigger": ctx.trigger_last(n_events)} if ctx._tokens["trigger"] is not None else {}
 
 
 def traces_to_trigger(offsets, pads, samples, trigger: TriggerSettings, pedestals=None, ctx: _abi.Context | None = None):
@@ -552,6 +630,8 @@ class GainSettings:
     every pad; None = 1.0 everywhere), ``stream`` in [0, 2^30) (another realisation on the same physics).  The
     fluctuation is drawn through ``normal_quantile_table()``."""
 
+    slot, call = "trace_gain", "attpc_trace_configure_gain"
+
     def __init__(self, rel_variance=None, theta=None, pad_gain=None, stream: int = 0):
         if rel_variance is not None and theta is not None:
             raise ValueError("give rel_variance or theta, not both")
@@ -598,13 +678,8 @@ def _checked_gain(gain):
 
 
 def configure_gain(ctx: _abi.Context, gain: GainSettings | None) -> None:
-    """``attpc_trace_configure_gain`` unless this ctx already holds the same gain (``None``, or a gain that changes
-    nothing: the stage off, which is also what a new context holds)."""
-    gain = _checked_gain(gain)
-    if gain is None or not gain.on:
-        ctx.configure("trace_gain", None, "attpc_trace_configure_gain", None)
-    else:
-        ctx.configure("trace_gain", gain.token(), "attpc_trace_configure_gain", gain.desc())
+    """``attpc_trace_configure_gain`` unless this ctx already holds the same gain (``None``, or one without effect: off)."""
+    configure_stage(ctx, GainSettings, _checked_gain(gain))
 
 
 def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, seed: int = 0, first_event: int = 0,
@@ -613,14 +688,7 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
     offsets [n+1], points [P,3] (pad, time bucket, electrons) -> the gained charge of every row [P] f64 (rows outside
     the offsets' range keep 0).  ``gain``: configured first (None: the stage off, the charges come back as they are).
     Event i of the call is the global event ``first_event + i``."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    n = len(offsets) - 1
-    if n < 0:
-        raise ValueError("offsets needs n_events + 1 entries")
-    seed, first_event, _ = _abi.check_id_range(seed, first_event, n)
-    if n and offsets[-1] > len(points):
-        raise ValueError("points do not hold the rows the offsets name")
+    offsets, points, _, seed, first_event, n = _host_cloud(offsets, points, None, seed, first_event)
     configure_gain(ctx, gain)
     gained = np.zeros(len(points), dtype=np.float64)
     ctx.check(ctx.lib.attpc_gain_rows(ctx.handle, seed, first_event, n, _abi.iptr(offsets, _abi.C.c_int64),
@@ -633,15 +701,9 @@ def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings 
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
     the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
     baseline (default None: off, the peaks stand on the configured pedestals) and the micromegas gain (default None:
-    off)."""
-    from .simulator import configure_spyral
-
-    peaks = PeakSettings() if peaks is None else peaks
-    configure_traces(config, ctx, **trace_kwargs)
-    configure_spyral(config, ctx)
-    configure_peaks(ctx, peaks)
-    configure_baseline(ctx, baseline)
-    configure_gain(ctx, gain)
+    off).  The trigger stays as the ctx holds it."""
+    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain)
+    chain.configure(ctx, rows=True, keep=("trigger",))
 
 
 def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
@@ -655,21 +717,9 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     before any suppression, stats dict: the cloud's run statistics with ``n_points`` = the rows, plus ``n_rows`` /
     ``row_checksum``, and with ``trigger`` (a ``TriggerSettings``; None = off; its ``gate`` leaves the events that did
     not fire without rows) its records [n] under ``"trigger"``).  ``gain`` as simulate_batch_traces takes it."""
-    from .simulator import run_batch
-
-    peaks = PeakSettings() if peaks is None else peaks
-    validate_trace_kwargs(config, trace_kwargs, gain)  # (before the first library call)
-    ctx = ctx or _abi.default_context()
-
-    def configure(c):
-        configure_trace_rows(config, c, peaks, baseline, gain, **trace_kwargs)
-        configure_trigger(c, trigger)
-
-    arrays, stats = run_batch("attpc_det_run_trace_rows", momenta, vertices, proton_numbers, mass_numbers, config, seed,
-                              indices, first_event, ctx, capacity_per_event,
-                              configure=configure, holder=RowArrays, width=8, slack=1024)
-    extra = {} if trigger is None else {"trigger": ctx.trigger_last(len(arrays.offsets) - 1)}
-    return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **ctx.trace_rows_last(), **extra})
+    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain)
+    return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
+                           capacity_per_event)
 
 
 def clouds_to_trace_rows(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,
@@ -679,15 +729,7 @@ def clouds_to_trace_rows(offsets: np.ndarray, points: np.ndarray, labels: np.nda
     (offsets [n+1], rows [R,8], labels [R], {n_rows, row_checksum; when the ctx holds a trigger its records [n] too,
     under ``"trigger"``}).  Event i of the call is the global event ``first_event + i`` (noise, centroid jitter and
     checksum)."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    labels = np.ascontiguousarray(labels, dtype=np.int64)
-    n = len(offsets) - 1
-    if n < 0:
-        raise ValueError("offsets needs n_events + 1 entries")
-    seed, first_event, _ = _abi.check_id_range(seed, first_event, n)
-    if len(points) != len(labels) or (n and offsets[-1] > len(points)):
-        raise ValueError("points / labels do not hold the rows the offsets name")
+    offsets, points, labels, seed, first_event, n = _host_cloud(offsets, points, labels, seed, first_event)
     needed = _abi.RunStats()  # (the host-cloud call has no statistics: its rows come from attpc_trace_rows_last)
 
     def call(out):
@@ -700,5 +742,5 @@ def clouds_to_trace_rows(offsets: np.ndarray, points: np.ndarray, labels: np.nda
     rows = int(offsets[-1] - offsets[0]) if n else 0
     arrays = call_with_capacity(ctx, n, max(16, rows, 4 * ctx._trace_readout_rows * n), call, "attpc_trace_rows_at", needed,
                                 holder=RowArrays, width=8, slack=16)
-    records = trigger_records(ctx, n)
-    return (*arrays.result(), {**ctx.trace_rows_last(), **({} if records is None else {"trigger": records})})
+    extra = trigger_result(ctx, n)
+    return (*arrays.result(), {**ctx.trace_rows_last(), **extra})

@@ -17,6 +17,7 @@ import numpy as np
 from .. import _abi
 from .parameters import Config
 from .response import get_response
+from .traces import NoiseSettings, ReadoutSettings, TraceChain, clouds_to_trace_rows, clouds_to_traces, trace_settings
 
 
 class SimulationWriter(Protocol):
@@ -162,23 +163,19 @@ class SpyralWriter(_RollingWriter):
         ``detector.traces.GainSettings``, default None = off): the micromegas gain of the traces, keyed like the noise.
         The files have the same datasets either way."""
         self.response = get_response(config).copy()
-        self.peaks = peaks
-        self.baseline = baseline
-        self.gain = gain
+        self.peaks, self.baseline, self.gain, self.chain = peaks, baseline, gain, None
         if peaks is None and (trace_kwargs or noise_seed or baseline is not None or gain is not None):
             given = (sorted(trace_kwargs) + (["noise_seed"] if noise_seed else []) + (["baseline"] if baseline is not None else [])
                      + (["gain"] if gain is not None else []))
             raise TypeError(f"SpyralWriter takes trace settings only with peaks=: {given}")
-        if peaks is not None:
-            from .traces import validate_trace_kwargs
-
-            validate_trace_kwargs(config, trace_kwargs, gain)
+        if peaks is not None:  # (the chain of a trace-row run; ``write`` uses it too)
+            self.chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain)
             self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
         self._trace_kwargs = dict(trace_kwargs)
         super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)
 
     def trace_kwargs(self) -> dict:
-        """The trace settings of a writer with ``peaks``, as ``configure_traces`` takes them."""
+        """The trace settings a writer with ``peaks`` was given, as ``configure_traces`` takes them."""
         return dict(self._trace_kwargs)
 
     def write(self, data: np.ndarray, labels: np.ndarray, config: Config, event_number: int) -> None:
@@ -187,10 +184,8 @@ class SpyralWriter(_RollingWriter):
         if config.pad_centers is None:
             raise ValueError("Pad centers are not assigned at write!")
         if self.peaks is not None:
-            from .traces import clouds_to_trace_rows, configure_trace_rows
-
             ctx = _abi.default_context()
-            configure_trace_rows(config, ctx, self.peaks, self.baseline, self.gain, **self.trace_kwargs())
+            self.chain.replace(config=config).configure(ctx, rows=True, keep=("trigger",))
             data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
             _, rows, out_labels, _ = clouds_to_trace_rows(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
                                                           seed=self.noise_seed, first_event=event_number)
@@ -245,16 +240,11 @@ class TraceWriter(_RollingWriter):
                  threshold: float | None = None, offset: int = 0, noise_sigma: float = 0.0, noise_table=None,
                  pedestals=None, noise_stream: int = 0, noise_seed: int = 0, readout: str = "hit",
                  readout_pads=None, gain=None):
-        from .traces import GainSettings, NoiseSettings, ReadoutSettings, trace_settings
-
-        if gain is not None and not isinstance(gain, GainSettings):
-            raise TypeError("gain must be a GainSettings or None")
-        self.gain = gain
-
-        self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
-        self.response = self.response.copy()
-        self.noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
-        self.readout = ReadoutSettings(readout, readout_pads)
+        response, threshold, offset = trace_settings(config, response, threshold, offset)  # (this config's defaults in every run)
+        noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
+        self.chain = chain = TraceChain(config, response.copy(), threshold, offset, noise, ReadoutSettings(readout, readout_pads), gain)
+        self.response, self.threshold, self.offset = chain.response, chain.threshold, chain.offset
+        self.noise, self.readout, self.gain = chain.noise, chain.readout, chain.gain
         self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
         super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)
 
@@ -289,12 +279,8 @@ class TraceWriter(_RollingWriter):
 
     def write(self, data: np.ndarray, labels: np.ndarray, config: Config, event_number: int) -> None:
         """One event's cloud [P,3] -> its traces on the device (``clouds_to_traces``) -> datasets."""
-        from .traces import clouds_to_traces, configure_gain, configure_traces
-
         ctx = _abi.default_context()
-        configure_traces(config, ctx, self.response, self.threshold, self.offset, **self.noise_kwargs(),
-                         **self.readout_kwargs())
-        configure_gain(ctx, self.gain)
+        self.chain.configure(ctx, keep=("trigger",))
         data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
         _, pads, samples, out_labels, _ = clouds_to_traces(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
                                                            seed=self.noise_seed, first_event=event_number)

@@ -13,7 +13,9 @@ import numpy as np
 
 from . import _abi, nuclear_map
 from .detector.luts import build_det_desc, build_layout, species_for
-from .detector.simulator import default_indices, deliver_events, delivery_of, fired_events
+from .detector.simulator import default_indices, deliver_events, fired_events, plan_delivery, selected_events
+from .detector.traces import (BaselineSettings, GainSettings, PeakSettings, TriggerSettings, configure_baseline,
+                              configure_gain, configure_peaks, configure_traces, configure_trigger, trigger_result)
 from .outputs import RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -131,11 +133,16 @@ class Engine:
         ``noise_stream``; see ``detector.traces.configure_traces``) and the readout ("hit" by default, "partial" or
         "full" of the pads ``readout_pads``, default every pad not in BEAM_PADS).  The noise of ``run_traces`` is keyed
         on its seed and the global event ids."""
-        from .detector.traces import configure_traces
-
         configure_traces(config or self.config, self.ctx, response, threshold, offset, noise_sigma, noise_table,
                          pedestals, noise_stream, readout, readout_pads)
         self._traces_configured = True
+
+    def _configure_chain(self, chain, rows: bool = False) -> None:
+        """What ``run_traces`` (``rows``: ``run_trace_rows``) needs, from one ``detector.traces.TraceChain``."""
+        chain.configure(self.ctx, rows)
+        self._traces_configured = True
+        if rows:
+            self._spyral_configured = self._peaks_configured = True
 
     def run_traces(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
                    capacity_per_event: int = 1024) -> dict:
@@ -157,12 +164,12 @@ class Engine:
             return {"stats": stats.as_dict(), "trace": {"n_rows": int(out.n_rows),
                                                         "sample_checksum": int(out.sample_checksum),
                                                         "pad_checksum": int(out.pad_checksum)},
-                    **self._trigger_result(n_events)}
+                    **trigger_result(ctx, n_events)}
         per_event = max(int(capacity_per_event), ctx._trace_readout_rows)  # full readout: |S|
         arrays, res = self._deliver("attpc_sim_run_traces", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned)
         _, pads, samples, _ = arrays.result()
-        return {**res, "pads": pads, "samples": samples, "trace": arrays.sums(), **self._trigger_result(n_events)}
+        return {**res, "pads": pads, "samples": samples, "trace": arrays.sums(), **trigger_result(ctx, n_events)}
 
     # ---------------------------------------------------------------- micromegas gain of the pad traces
     def configure_gain(self, gain=None, **parameters) -> None:
@@ -171,13 +178,7 @@ class Engine:
         ``run_trace_rows`` and ``run_trigger`` are then made from every cloud row's gained charge (avalanche
         fluctuations and the pad's gain factor), keyed on the run's seed and the global event ids --, neither turns it
         off (the default).  The clouds of ``run`` and the rows of ``run_spyral`` never change."""
-        from .detector.traces import GainSettings, configure_gain
-
-        if gain is not None and parameters:
-            raise TypeError("give a GainSettings or its keywords, not both")
-        if parameters:
-            gain = GainSettings(**parameters)
-        configure_gain(self.ctx, gain)
+        configure_gain(self.ctx, _settings(GainSettings, gain, parameters))
 
     # ---------------------------------------------------------------- multiplicity trigger on the pad traces
     def configure_trigger(self, trigger=None, **parameters) -> None:
@@ -185,20 +186,7 @@ class Engine:
         keywords (threshold, window, group_multiplicity, min_groups, groups, gate) turn it on -- ``run_traces``,
         ``run_trace_rows`` and ``run_trigger`` then return one record per event under ``trigger``; with ``gate`` the
         events that did not fire get no trace rows --, neither turns it off (the default)."""
-        from .detector.traces import TriggerSettings, configure_trigger
-
-        if trigger is not None and parameters:
-            raise TypeError("give a TriggerSettings or its keywords, not both")
-        if parameters:
-            trigger = TriggerSettings(**parameters)
-        configure_trigger(self.ctx, trigger)
-
-    def _trigger_result(self, n_events: int) -> dict:
-        """``{"trigger": records [n]}`` of the trace call just made if a trigger is configured, else nothing."""
-        from .detector.traces import trigger_records
-
-        records = trigger_records(self.ctx, n_events)
-        return {} if records is None else {"trigger": records}
+        configure_trigger(self.ctx, _settings(TriggerSettings, trigger, parameters))
 
     def run_trigger(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_traces(fetch=False)`` for its trigger records: the traces are made, triggered on and left on the
@@ -213,24 +201,15 @@ class Engine:
     def configure_peaks(self, peaks=None, **parameters) -> None:
         """Upload the peak parameters of the trace rows: a ``detector.traces.PeakSettings`` or its keywords
         (separation, prominence, min_width, max_width, rel_height, threshold; include/attpc_engine.h)."""
-        from .detector.traces import PeakSettings, configure_peaks
-
-        if peaks is not None and parameters:
-            raise TypeError("give a PeakSettings or its keywords, not both")
-        configure_peaks(self.ctx, PeakSettings(**parameters) if peaks is None else peaks)
+        configure_peaks(self.ctx, _settings(PeakSettings, peaks, parameters) or PeakSettings())
         self._peaks_configured = True
 
     def configure_baseline(self, baseline=None, window_scale: float | None = None) -> None:
         """The Fourier baseline of the trace rows (include/attpc_engine.h): a ``detector.traces.BaselineSettings`` or
         its ``window_scale`` turns it on -- the peaks of ``run_trace_rows`` then stand on Spyral's own estimate of the
         baseline instead of the configured pedestals --, neither turns it off (the default)."""
-        from .detector.traces import BaselineSettings, configure_baseline
-
-        if baseline is not None and window_scale is not None:
-            raise TypeError("give a BaselineSettings or its window_scale, not both")
-        if window_scale is not None:
-            baseline = BaselineSettings(window_scale)
-        configure_baseline(self.ctx, baseline)
+        parameters = {} if window_scale is None else {"window_scale": window_scale}
+        configure_baseline(self.ctx, _settings(BaselineSettings, baseline, parameters, "window_scale"))
 
     def run_trace_rows(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
                        capacity_per_event: int = 2048) -> dict:
@@ -255,11 +234,11 @@ class Engine:
             stats, out = _abi.RunStats(), _abi.CloudOut()
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
-            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **self._trigger_result(n_events)}
+            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
-        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **self._trigger_result(n_events)}
+        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run
@@ -339,10 +318,12 @@ class Engine:
         return {**res, **selected_result(arrays, rows, res["stats"]), "indices": list(self.indices)}
 
 
-def _selected_batch(res: dict, key: str):
-    """A selected call's result as ``deliver_events`` takes a batch: event_points masked by passed, so that its loop
-    skips the rejected events as it skips the empty ones."""
-    return res["offsets"], np.where(res["passed"], res["event_points"], 0), res[key], res["labels"]
+def _settings(cls, given, parameters: dict, what: str = "keywords"):
+    """What the configure methods of the stages take, a settings object or the keywords of its class, not both -> the
+    object (None: neither)."""
+    if given is not None and parameters:
+        raise TypeError(f"give a {cls.__name__} or its {what}, not both")
+    return cls(**parameters) if parameters else given
 
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
@@ -356,58 +337,33 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     ``writer.write_rows(rows, labels, event_number, presorted=True)``, then ``close()``.  A SpyralWriter with ``peaks``
     gets the peaks of the event's pad traces as its rows (``Engine.run_trace_rows``).  A writer that offers
     ``write_traces`` (TraceWriter) gets ``write_traces(pads, samples, labels, event_number)`` per such event instead,
-    the traces made on the device (``Engine.run_traces``) with the writer's noise settings.  ``selection`` (a
-    ``detector.selection.Selection``): only the events that pass it reach the writer (``Engine.run_selected``; rows or
-    plain clouds, a trace writer raises ValueError); event numbers stay the global ones, the file roll-over counts
-    written events.  ``trigger`` (a ``detector.traces.TriggerSettings``): only the events the multiplicity trigger fires
-    on reach the writer, under their own event numbers -- a writer that receives traces or trace rows (for the latter
-    the device skips the peak work of the others too), any other raises ValueError.  ``gain`` (a
-    ``detector.traces.GainSettings``; default: the writer's own ``gain``, None = off): the micromegas gain of the traces
-    -- again a writer that receives traces or trace rows, any other raises ValueError."""
+    the traces made on the device (``Engine.run_traces``) with the writer's own trace settings.  ``selection``
+    (``Engine.run_selected``; rows or plain clouds), ``trigger`` and ``gain``: as ``run_simulation`` takes them, with
+    the same rules about the kinds of writer (``detector.simulator.plan_delivery``); event numbers stay the global
+    ones, the file roll-over counts written events."""
     engine = Engine(pipeline, config, indices, context=context)
     seed = pipeline.seed if seed is None else int(seed)
-    kind, emit = delivery_of(writer, config)
-    if gain is not None and kind not in ("traces", "trace_rows"):
-        raise ValueError("a gain acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
-    if trigger is not None and kind not in ("traces", "trace_rows"):
-        raise ValueError("a trigger delivers traces or trace rows: writers of Spyral rows or clouds are not supported")
+    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, plain_clouds=False)
     if selection is not None:
-        if kind not in ("rows", "cloud"):
-            raise ValueError("a selection delivers Spyral rows or clouds: trace writers are not supported")
         engine.configure_selection(selection)
         if kind == "rows":
             engine.configure_spyral(config)
 
         def selected(start, stop):
             res = engine.run_selected(stop - start, seed=seed, first_event=start, rows="spyral" if kind == "rows" else "cloud")
-            return _selected_batch(res, "rows" if kind == "rows" else "points")
+            return selected_events(res, "rows" if kind == "rows" else "points")
 
         deliver_events(writer, n_events, batch_size, selected, emit)
         return
-    if kind == "traces":
-        engine.configure_traces(config, writer.response, writer.threshold, writer.offset, **writer.noise_kwargs(),
-                                **writer.readout_kwargs())
-    elif kind == "trace_rows":
-        engine.configure_traces(config, **writer.trace_kwargs())
-        engine.configure_spyral(config)
-        engine.configure_peaks(writer.peaks)
-        engine.configure_baseline(getattr(writer, "baseline", None))
-    elif kind == "rows":
+    if chain is None:
         engine.configure_spyral(config)
     else:
-        raise AttributeError("run_fused needs a writer that offers write_rows or write_traces")
-    if kind in ("traces", "trace_rows"):  # (None: whatever an earlier use of the context left is turned off)
-        engine.configure_trigger(trigger if trigger is None or kind == "traces" else trigger.gated())
-        engine.configure_gain(getattr(writer, "gain", None) if gain is None else gain)
+        engine._configure_chain(chain, rows=kind == "trace_rows")
+    run = {"traces": engine.run_traces, "trace_rows": engine.run_trace_rows, "rows": engine.run_spyral}[kind]
 
     def batch(start, stop):
-        if kind == "traces":
-            res = engine.run_traces(stop - start, seed=seed, first_event=start)
-            return fired_events(res["offsets"], res["event_points"], res.get("trigger"), res["pads"], res["samples"], res["labels"])
-        if kind == "trace_rows":
-            res = engine.run_trace_rows(stop - start, seed=seed, first_event=start)
-            return fired_events(res["offsets"], res["event_points"], res.get("trigger"), res["rows"], res["labels"])
-        res = engine.run_spyral(stop - start, seed=seed, first_event=start)
-        return res["offsets"], res["event_points"], res["rows"], res["labels"]
+        res = run(stop - start, seed=seed, first_event=start)
+        arrays = (res["pads"], res["samples"]) if kind == "traces" else (res["rows"],)
+        return fired_events(res["offsets"], res["event_points"], res.get("trigger"), *arrays, res["labels"])
 
     deliver_events(writer, n_events, batch_size, batch, emit)

@@ -320,3 +320,59 @@ def test_run_simulation_and_run_fused_write_the_restatement(ctx, tmp_path, monke
     for e in want:
         for a, b in zip(got[e], want[e]):
             np.testing.assert_array_equal(a, b)
+
+
+def test_every_stage_at_once_three_routes_agree(ctx):
+    """Noise and pedestals, partial readout, gain fluctuations with a pad map, the Fourier baseline and a gated trigger,
+    all on: the trace rows and trigger records of ``Engine.run_trace_rows`` (configured through the engine's methods),
+    of ``simulate_batch_trace_rows`` on the same kinematics and of ``clouds_to_trace_rows`` on the same cloud (its
+    context configured by one ``TraceChain.configure``, every slot forgotten first) are bit for bit the same.  The
+    trigger is the one of tests/test_gpu_trigger.py's gated case: the multiplicity about half of the events reach."""
+    from attpc_engine_amd.detector.traces import (BaselineSettings, GainSettings, PeakSettings, TraceChain, TriggerSettings,
+                                                  clouds_to_trace_rows, simulate_batch_trace_rows)
+    from tests.test_gpu_trigger import _assert_records, _half_multiplicity, _pedestals
+
+    inp = Inputs("be10dp")
+    n, seed = 6, 17
+    trace_kw = {"noise_sigma": 5.0, "threshold": 20.0, "readout": "partial", "pedestals": _pedestals(),
+                "offset": int(np.argmax(get_response(inp.config)))}
+    gain = GainSettings(theta=1.0, pad_gain=0.8 + 0.4 * np.random.default_rng(4).random(_abi.NUM_PADS), stream=2)
+    peaks, baseline = PeakSettings(), BaselineSettings(20.0)
+    eng = _engine(inp, ctx)
+    eng.configure_traces(inp.config, **trace_kw)
+    eng.configure_spyral(inp.config)
+    eng.configure_peaks(peaks)
+    eng.configure_baseline(baseline)
+    eng.configure_gain(gain)
+    try:
+        eng.configure_trigger(threshold=25, window=50, group_multiplicity=1)
+        reach = eng.run_trigger(n, seed=seed)["trigger"]
+        trigger = TriggerSettings(25, window=50, group_multiplicity=_half_multiplicity(reach), gate=True)
+        eng.configure_trigger(trigger)
+        one = eng.run_trace_rows(n, seed=seed)
+        fired = one["trigger"]["fired"] != 0
+        seen = f"peak_group_sum {reach['peak_group_sum'].tolist()}, fired {fired.tolist()}, rows {np.diff(one['offsets']).tolist()}"
+        assert 0 < fired.sum() < n, seen  # the gate is exercised: events of both kinds
+        assert (np.diff(one["offsets"])[~fired] == 0).all() and (np.diff(one["offsets"])[fired] > 0).any(), seen
+        off, rows, labels, raw, stats = simulate_batch_trace_rows(
+            one["p4"], one["vertex"], inp.z, inp.a, inp.config, seed, inp.indices, ctx=ctx, peaks=peaks, baseline=baseline,
+            trigger=trigger, gain=gain, **trace_kw)
+        cloud = eng.run(n, seed=seed, fetch=True)
+        for slot in ("trace", "trace_noise", "trace_readout", "spyral", "peaks", "baseline", "trigger", "trace_gain"):
+            ctx.forget(slot)
+        chain = TraceChain.from_kwargs(inp.config, **trace_kw).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain)
+        chain.configure(ctx, rows=True)
+        host = clouds_to_trace_rows(cloud["offsets"], cloud["points"], cloud["labels"], ctx, seed=seed)
+        routes = {"simulate_batch_trace_rows": (off, rows, labels, stats),
+                  "clouds_to_trace_rows": host}
+        for name, (o, r, lab, sums) in routes.items():
+            np.testing.assert_array_equal(o, one["offsets"], err_msg=name)
+            assert r.tobytes() == one["rows"].tobytes() and r.shape == one["rows"].shape, name
+            np.testing.assert_array_equal(lab, one["labels"], err_msg=name)
+            assert {k: sums[k] for k in ("n_rows", "row_checksum")} == one["trace_rows"], name
+            _assert_records(sums["trigger"], one["trigger"], name)
+        np.testing.assert_array_equal(raw, one["event_points"])
+    finally:
+        eng.configure_trigger()
+        eng.configure_gain()
+        eng.configure_baseline()
