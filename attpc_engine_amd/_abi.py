@@ -167,6 +167,11 @@ class TraceGainDesc(C.Structure):
 GAIN_KNOTS = 4097
 
 
+class TraceCommonDesc(C.Structure):
+    _fields_ = [("groups", C.POINTER(C.c_uint8)), ("cdf", C.POINTER(C.c_uint32)), ("n_levels", C.c_int32),
+                ("min_level", C.c_int32), ("stream", C.c_uint32), ("reserved", C.c_int32)]
+
+
 class EventSummary(C.Structure):
     _fields_ = [("n_points", C.c_uint32), ("n_kept", C.c_uint32), ("n_pads", C.c_uint32), ("tb_min", C.c_int32),
                 ("tb_max", C.c_int32), ("reserved", C.c_int32), ("charge", C.c_int64)]
@@ -312,6 +317,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_rows_last", "attpc_trace_configure_baseline", "attpc_trace_baseline",
     "attpc_trace_configure_trigger", "attpc_trigger_last", "attpc_trigger_rows",
     "attpc_trace_configure_gain", "attpc_gain_rows",
+    "attpc_trace_configure_common_mode", "attpc_common_mode_rows",
     "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
     "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
 )
@@ -336,6 +342,9 @@ TRIGGER_SYMBOLS = ("attpc_trace_configure_trigger", "attpc_trigger_last", "attpc
 
 # ... and the micromegas gain of the traces after the trigger: the same rule.
 GAIN_SYMBOLS = ("attpc_trace_configure_gain", "attpc_gain_rows")
+
+# ... and the common-mode noise of the traces after the gain: the same rule.
+COMMON_SYMBOLS = ("attpc_trace_configure_common_mode", "attpc_common_mode_rows")
 
 _lib = None
 
@@ -468,6 +477,14 @@ def load_library() -> C.CDLL:
     for name, argtypes in gain.items():
         if not no_gain:
             getattr(lib, name).argtypes = argtypes
+    common = {
+        "attpc_trace_configure_common_mode": [ctxp, C.POINTER(TraceCommonDesc)],
+        "attpc_common_mode_rows": [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int16)],
+    }
+    no_common = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in COMMON_SYMBOLS)
+    for name, argtypes in common.items():
+        if not no_common:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -490,7 +507,8 @@ def load_library() -> C.CDLL:
     for name in EXPORTED_SYMBOLS:
         if ((older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS)
                 or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)
-                or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)):
+                or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)
+                or (no_common and name in COMMON_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -499,7 +517,7 @@ def load_library() -> C.CDLL:
     return lib
 
 
-CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
+CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
                    "select")
 
 

@@ -81,6 +81,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf tr_scratch, tr_info, tr_pads, tr_samples, tr_labels;  // pad traces (traces.hip)
   DevBuf tr_maps;     // readout of noise-only pads: TraceMaps, 3 x TR_MAP_WORDS words per event
   DevBuf tr_gained;   // micromegas gain on (gain.hip): the gained charge of every cloud row of the chunk, f64 [rows]
+  DevBuf tr_common;   // common-mode noise on: the values of every (event, group) of the chunk, 1 KiB each (CommonDev)
   size_t tr_cap = 0;  // kept pad rows the trace outputs are kept at (grown with headroom)
   hipEvent_t traced = nullptr;  // the chunk's traces are written (the copies on C wait for it)
   hipEvent_t counted = nullptr; // trace rows: the chunk's points per event are in h_pk_start (the host waits for it)
@@ -195,6 +196,11 @@ struct attpc_ctx {
   bool gain_on = false;            // attpc_trace_configure_gain
   GainDev gain{};
   std::vector<void*> gain_allocs;
+  bool common_on = false;          // attpc_trace_configure_common_mode
+  TraceNoiseDev common_table{};    // the stage's own noise table (no pedestals), domain DOMAIN_TRACE_COMMON | stream
+  const uint8_t* common_groups = nullptr;  // [ATTPC_NUM_PADS] on the device, or nullptr = every pad in group 0
+  int32_t common_n_groups = 0;     // 1 + the highest group of the map
+  std::vector<void*> common_allocs;
   int32_t readout_mode = ATTPC_READOUT_HIT;  // attpc_trace_configure_readout
   int64_t readout_pads = 0;        // |S|
   const uint32_t* readout_channels = nullptr;  // [TR_MAP_WORDS] bitmap of S on the device
@@ -246,7 +252,7 @@ struct attpc_ctx {
   bool unpack_stop = false, unpack_failed = false;
 
   ~attpc_ctx() {  // (attpc_ctx_destroy has stopped everything first; the DevBuf / Pinned members free themselves)
-    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs, &gain_allocs, &readout_allocs, &summary_allocs})
+    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs, &gain_allocs, &common_allocs, &readout_allocs, &summary_allocs})
       for (void* p : *v) (void)hipFree(p);
     for (void* p : host_allocs) (void)hipHostFree(p);
   }
@@ -834,6 +840,22 @@ TraceDev trace_dev(const attpc_ctx* ctx, const AsmSet& as) {
 // The noise of the trace kernels: nullptr = the noiseless kernels.
 const TraceNoiseDev* trace_noise(const attpc_ctx* ctx) { return ctx->noise_on ? &ctx->noise : nullptr; }
 
+// The largest level of a noise table (0 without one: the one level 0).
+int32_t top_level(const TraceNoiseDev& t) { return t.n_levels > 0 ? t.min_level + t.n_levels - 1 : 0; }
+
+// The common-mode noise of the trace kernels for the chunk in `as` (its values in as.tr_common, which
+// enqueue_trace_count fills in front of the count pass): nullptr = the kernels without the term.
+const CommonDev* trace_common(const attpc_ctx* ctx, const AsmSet& as, CommonDev& cm) {
+  if (!ctx->common_on) return nullptr;
+  cm = CommonDev{static_cast<const int16_t*>(as.tr_common.p), ctx->common_groups, ctx->common_n_groups,
+                 top_level(ctx->noise) + top_level(ctx->common_table)};
+  return &cm;
+}
+// Events of a chunk whose common-mode values fill 1 GiB (at least one).
+uint32_t common_chunk_events(const attpc_ctx* ctx) {
+  return (uint32_t)std::max<int64_t>(1, (1ll << 20) / std::max(ctx->common_n_groups, 1));
+}
+
 // The readout of the trace kernels (ro.channels == nullptr: hit mode) with the cutoff of the decision rule for the
 // configured threshold and noise table: c = floor(thr) + 1 - min_level; c <= 0 always, c > n_levels - 1 never (no
 // table: the one level 0), else u_j >= cdf[c - 1].
@@ -856,10 +878,12 @@ TraceReadoutDev trace_readout(const attpc_ctx* ctx) {
 }
 
 // Does a readout run need the scan and the noise-only write?  Not in hit mode, nor in PARTIAL when the decision rule
-// keeps no noise-only pad (thr >= 0 and a cutoff above the table): the count pass's ranks are then the union's.
+// keeps no noise-only pad: thr >= 0 and a cutoff above the pad table -- and, with the common-mode noise on, the largest
+// pad level plus the largest common-mode level <= thr.  The count pass's ranks are then the union's.
 bool readout_scan(const attpc_ctx* ctx, const TraceReadoutDev& ro) {
   if (!ro.channels) return false;
-  return ro.full || !(ro.cut_kind == TRACE_CUT_NEVER && ctx->trace.threshold >= 0.0);
+  if (ro.full || !(ro.cut_kind == TRACE_CUT_NEVER && ctx->trace.threshold >= 0.0)) return true;
+  return ctx->common_on && (double)(top_level(ctx->noise) + top_level(ctx->common_table)) > ctx->trace.threshold;
 }
 
 TraceMaps trace_maps(AsmSet& as, uint32_t n) {
@@ -878,8 +902,18 @@ int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap, 
   if ((rc = ensure(ctx, as.tr_scratch, std::max<size_t>(cap, 1) * 4 * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, as.tr_info, std::max<size_t>(n, 1) * 2 * sizeof(uint32_t)))) return rc;
   if (ctx->gain_on && (rc = ensure(ctx, as.tr_gained, std::max<size_t>(cap, 1) * sizeof(double)))) return rc;
+  if (ctx->common_on && n &&
+      (rc = ensure(ctx, as.tr_common, (size_t)n * (size_t)ctx->common_n_groups * ATTPC_NUM_TB * sizeof(int16_t))))
+    return rc;
   const TraceReadoutDev ro = trace_readout(ctx);
+  CommonDev cm_store{};
+  const CommonDev* cm = trace_common(ctx, as, cm_store);
   if (n) {
+    if (cm) {  // the common-mode values of the chunk's events and groups, in front of the count pass
+      launch_common_mode(ctx->stream, ctx->common_table, seed, n, first_event, (uint32_t)ctx->common_n_groups,
+                         static_cast<int16_t*>(as.tr_common.p));
+      HIP_TRY(ctx, hipGetLastError());
+    }
     if (ctx->gain_on) {  // the gained charges of the chunk's rows, in front of the count pass
       launch_gain(ctx->stream, ctx->gain, seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
                   static_cast<const double*>(as.points.p), static_cast<double*>(as.tr_gained.p));
@@ -888,12 +922,12 @@ int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap, 
     const TraceScratch sc = trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t)));
     launch_trace_count(ctx->stream, trace_dev(ctx, as), trace_noise(ctx), seed, n, first_event, static_cast<const int64_t*>(as.ev_start.p),
                        static_cast<const double*>(as.points.p), static_cast<const int64_t*>(as.labels.p), sc,
-                       static_cast<uint32_t*>(as.kept.p), ro.channels ? &ro : nullptr);
+                       static_cast<uint32_t*>(as.kept.p), ro.channels ? &ro : nullptr, cm);
     HIP_TRY(ctx, hipGetLastError());
     if (readout_scan(ctx, ro)) {
       if ((rc = ensure(ctx, as.tr_maps, (size_t)n * 3 * TR_MAP_WORDS * sizeof(uint32_t)))) return rc;
       launch_trace_scan(ctx->stream, ctx->trace, trace_noise(ctx), ro, seed, n, first_event,
-                        static_cast<const int64_t*>(as.ev_start.p), sc, static_cast<uint32_t*>(as.kept.p), trace_maps(as, n));
+                        static_cast<const int64_t*>(as.ev_start.p), sc, static_cast<uint32_t*>(as.kept.p), trace_maps(as, n), cm);
       HIP_TRY(ctx, hipGetLastError());
     }
   }
@@ -908,6 +942,8 @@ int32_t enqueue_trace_count(attpc_ctx* ctx, AsmSet& as, uint32_t n, size_t cap, 
 int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t total, uint64_t seed, uint64_t first_event) {
   int32_t rc;
   if (total > 0) {
+    CommonDev cm_store{};
+    const CommonDev* cm = trace_common(ctx, as, cm_store);
     if ((size_t)total > as.tr_cap) as.tr_cap = (size_t)total + (size_t)total / 8;
     if ((rc = ensure(ctx, as.tr_pads, as.tr_cap * sizeof(int32_t)))) return rc;
     if ((rc = ensure(ctx, as.tr_samples, as.tr_cap * ATTPC_NUM_TB * sizeof(int16_t)))) return rc;
@@ -917,13 +953,13 @@ int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t tota
                        trace_scratch(as, as.tr_scratch.bytes / (4 * sizeof(uint32_t))),
                        static_cast<const int64_t*>(as.kept_start.p), static_cast<int32_t*>(as.tr_pads.p),
                        static_cast<int16_t*>(as.tr_samples.p), static_cast<int64_t*>(as.tr_labels.p),
-                       static_cast<unsigned long long*>(ctx->trace_sums.p));
+                       static_cast<unsigned long long*>(ctx->trace_sums.p), cm);
     HIP_TRY(ctx, hipGetLastError());
     if (readout_scan(ctx, trace_readout(ctx))) {  // the noise-only rows between them
       launch_trace_noise_write(ctx->stream, trace_noise(ctx), seed, n, first_event, trace_maps(as, n),
                                static_cast<const int64_t*>(as.kept_start.p), static_cast<int32_t*>(as.tr_pads.p),
                                static_cast<int16_t*>(as.tr_samples.p), static_cast<int64_t*>(as.tr_labels.p),
-                               static_cast<unsigned long long*>(ctx->trace_sums.p));
+                               static_cast<unsigned long long*>(ctx->trace_sums.p), cm);
       HIP_TRY(ctx, hipGetLastError());
     }
   }
@@ -1339,9 +1375,10 @@ int32_t trace_host_events(attpc_ctx* ctx, RunOut& o, uint64_t first_local, uint3
   AsmSet& as = ctx->aset[0];
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the set's previous contents have left
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
-  const uint32_t step = ctx->readout_mode != ATTPC_READOUT_HIT && ctx->readout_pads > 0
-                            ? (uint32_t)std::max<int64_t>(1, TRACE_CHUNK_ROWS / ctx->readout_pads)
-                            : std::max<uint32_t>(n, 1);
+  uint32_t step = ctx->readout_mode != ATTPC_READOUT_HIT && ctx->readout_pads > 0
+                      ? (uint32_t)std::max<int64_t>(1, TRACE_CHUNK_ROWS / ctx->readout_pads)
+                      : std::max<uint32_t>(n, 1);
+  if (ctx->common_on) step = std::min(step, common_chunk_events(ctx));  // 1 KiB of values per (event, group)
   uint32_t e0 = 0;
   do {
     const uint32_t m = std::min(step, n - e0);
@@ -1648,6 +1685,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
       if (rows > 0.0) n = std::min<uint32_t>(n, (uint32_t)std::max(1.0, (double)TRACE_CHUNK_ROWS / rows));
     } else if (makes_traces(o.mode) && ctx->trace_rows_per_event > 0.0)  // 1 KiB of samples per kept pad row
       n = std::min<uint32_t>(n, (uint32_t)std::max(256.0, (double)TRACE_CHUNK_ROWS / ctx->trace_rows_per_event));
+    if (makes_traces(o.mode) && ctx->common_on) n = std::min(n, common_chunk_events(ctx));
     const Chunk c{e0, n, seq % MAX_SLOTS};
     const int set = seq & 1;
     // an overflow of the chunk in flight is repaired inside complete(); queue this one behind it
@@ -2561,6 +2599,89 @@ int32_t attpc_gain_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     e0 = e1;
+  }
+  return ATTPC_OK;
+}
+
+// ---- common-mode noise of the traces (traces.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_common_mode(attpc_ctx* ctx, const attpc_trace_common_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  int n_groups = 0;
+  if (d) {
+    if (d->n_levels < 0 || d->n_levels > ATTPC_MAX_NOISE_LEVELS)
+      return fail(ctx, ATTPC_E_INVALID, "common-mode table of %d levels: 0 .. %d", d->n_levels, ATTPC_MAX_NOISE_LEVELS);
+    if (d->min_level < -4095 || d->min_level > 4095)
+      return fail(ctx, ATTPC_E_INVALID, "common-mode min_level %d outside -4095 .. 4095", d->min_level);
+    if (d->n_levels > 1 && !d->cdf) return fail(ctx, ATTPC_E_INVALID, "common-mode table of %d levels without a cdf", d->n_levels);
+    for (int k = 1; k < d->n_levels - 1; ++k)
+      if (d->cdf[k] < d->cdf[k - 1]) return fail(ctx, ATTPC_E_INVALID, "common-mode cdf decreases at entry %d", k);
+    if (d->stream >= 0x20000000u) return fail(ctx, ATTPC_E_INVALID, "common-mode stream %u >= 2^29", d->stream);
+    n_groups = d->groups ? 0 : 1;
+    if (d->groups)
+      for (int p = 0; p < ATTPC_NUM_PADS; ++p)
+        if (d->groups[p] != 255) n_groups = std::max(n_groups, (int)d->groups[p] + 1);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  free_all(ctx->common_allocs);
+  ctx->common_on = false;
+  ctx->common_table = TraceNoiseDev{};
+  ctx->common_groups = nullptr;
+  ctx->common_n_groups = 0;
+  if (!d || d->n_levels == 0 || n_groups == 0) return ATTPC_OK;  // the contract without the stage
+  // the table as attpc_trace_configure_noise lays it out: the cdf padded to the full table, and the guide
+  const int n_cdf = d->n_levels - 1;
+  std::vector<uint32_t> cdf(ATTPC_MAX_NOISE_LEVELS, 0xFFFFFFFFu);
+  for (int k = 0; k < n_cdf; ++k) cdf[k] = d->cdf[k];
+  std::vector<uint16_t> guide(256);
+  for (int b = 0, k = 0; b < 256; ++b) {
+    while (k < n_cdf && cdf[k] <= (uint32_t)b << 24) ++k;
+    guide[b] = (uint16_t)k;
+  }
+  TraceNoiseDev t{};
+  const uint8_t* groups = nullptr;
+  int32_t rc;
+  if ((rc = upload(ctx, ctx->common_allocs, cdf.data(), cdf.size(), &t.cdf))) return rc;
+  if ((rc = upload(ctx, ctx->common_allocs, guide.data(), guide.size(), &t.guide))) return rc;
+  if (d->groups && (rc = upload(ctx, ctx->common_allocs, d->groups, (size_t)ATTPC_NUM_PADS, &groups))) return rc;
+  t.n_levels = d->n_levels;
+  t.min_level = d->min_level;
+  t.domain = DOMAIN_TRACE_COMMON | d->stream;
+  ctx->common_table = t;
+  ctx->common_groups = groups;
+  ctx->common_n_groups = n_groups;
+  ctx->common_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_common_mode_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, int16_t* out) {
+  if (!ctx || n_events < 0) return ATTPC_E_INVALID;
+  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_common_mode_rows takes at most 2^31 - 1 events per call");
+  if (validate_id_range(ctx, first_event, (uint64_t)n_events)) return ATTPC_E_INVALID;
+  if (!ctx->common_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure_common_mode has not turned the stage on");
+  if (n_events == 0) return ATTPC_OK;
+  if (!out) return ATTPC_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  const size_t per_event = (size_t)ctx->common_n_groups * ATTPC_NUM_TB;  // values
+  const int64_t step = (int64_t)common_chunk_events(ctx);
+  std::vector<int16_t> lanes;
+  for (int64_t e0 = 0; e0 < n_events; e0 += step) {
+    const int64_t m = std::min(step, n_events - e0);
+    const size_t count = (size_t)m * per_event;
+    if ((rc = ensure(ctx, ctx->scratch[0], count * sizeof(int16_t)))) return rc;
+    launch_common_mode(ctx->stream, ctx->common_table, seed, (uint32_t)m, first_event + (uint64_t)e0,
+                       (uint32_t)ctx->common_n_groups, static_cast<int16_t*>(ctx->scratch[0].p));
+    HIP_TRY(ctx, hipGetLastError());
+    lanes.resize(count);
+    HIP_TRY(ctx, hipMemcpyAsync(lanes.data(), ctx->scratch[0].p, count * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // the device keeps a group's values in lane order (sample l + 64 s at 8 l + s): sample order for the caller
+    int16_t* dst = out + (size_t)e0 * per_event;
+    for (size_t item = 0; item < (size_t)m * (size_t)ctx->common_n_groups; ++item)
+      for (int l = 0; l < 64; ++l)
+        for (int k = 0; k < 8; ++k) dst[item * ATTPC_NUM_TB + l + 64 * k] = lanes[item * ATTPC_NUM_TB + 8 * l + k];
   }
   return ATTPC_OK;
 }

@@ -25,7 +25,13 @@ constexpr uint32_t DOMAIN_MC = 0x200u;     // + entry number of the event; index
 constexpr uint32_t DOMAIN_PEAK_JITTER = 0x300u;  // as DOMAIN_JITTER, for the centroid of a trace peak (peaks.hip): key = sample << 14 | pad
 constexpr uint32_t DOMAIN_TRACE_NOISE = 0x80000000u;  // | noise stream; index = pad * 128 + 2 * (j % 64) + j / 256
 constexpr uint32_t DOMAIN_TRACE_GAIN = 0x40000000u;   // | gain stream (< 2^30); index = pad * 512 + time bucket (gain.hip)
-// (nothing else reaches bit 30: 1 + row and 0x200 + entry stay far below, 0x100 / 0x300 are key words of Philox2x32)
+constexpr uint32_t DOMAIN_TRACE_COMMON = 0x20000000u; // | common-mode stream (< 2^29); index = group * 128 + 2 * (j % 64) + j / 256
+// (the three trace domains differ in their top set bit: 31, 30, 29.  Nothing else reaches bit 29: 1 + row is at most
+//  the rows of an event layout, a few tens; 0x200 + entry is below 0x200 + ATTPC_MAX_SIM * ATTPC_TIME_SAMPLES *
+//  ATTPC_LONG_STEPS = 0x200 + 400 040 < 2^19, the entries one event can have (scatter.hip, lone.hip); 0x100 / 0x300 are
+//  key words of Philox2x32)
+static_assert(0x200ull + (unsigned long long)ATTPC_MAX_SIM * ATTPC_TIME_SAMPLES * ATTPC_LONG_STEPS < DOMAIN_TRACE_COMMON,
+              "DOMAIN_MC + entry stays below the trace domains");
 constexpr uint32_t KIN_SLOTS = 64u;
 
 // Philox4x32-10 (Salmon et al. SC'11), the algorithm of rocRAND's default generator, written

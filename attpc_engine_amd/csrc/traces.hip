@@ -29,6 +29,13 @@
 //   noise write: one wave per kept noise-only pad writes pad, label -1 and the clamped pedestal plus noise.
 // The scan is skipped when the decision rule keeps no noise-only pad (PARTIAL, thr >= 0 and a cutoff above the table):
 // the count pass's ranks are then already those of the union.
+// Common-mode noise (attpc_trace_configure_common_mode): common_mode_kernel, in front of the count pass, draws the 512
+// values of every (event, group) of the chunk with noise_values -- the stage's own table and domain, the group in the
+// pad's place -- and stores them as int16 in the lanes' own order (lane l: samples l + 64 s, 16 contiguous bytes).  Every
+// kernel that makes samples is templated on CM (the CM = false instantiations are the code without the stage): a wave
+// working on a pad of group g != 255 fetches its group's values with one 16-byte load per lane and adds them to the pad
+// noise before the clamp; the scan's verdict for such a pad makes the pad's own draw and compares the sums.  With CM the
+// NOISE kernels run whether a pad table is configured or not (n_p = 0, ped_p = 0 without one).
 #include "tracks_args.hpp"
 
 namespace attpc {
@@ -143,11 +150,34 @@ __device__ __forceinline__ void noise_values(int n[8], const TraceNoiseDev& nz, 
   }
 }
 
+// The group of a pad in the common-mode map (wave-uniform; 255 = the pad has no common-mode term).
+__device__ __forceinline__ uint32_t common_group(const CommonDev& cm, uint32_t pad) {
+  return cm.groups ? (uint32_t)__builtin_amdgcn_readfirstlane((int)cm.groups[pad]) : 0u;
+}
+
+// n[s] += c_g[lane + 64 s] for group g (!= 255) of event e of the launch: the lane's 8 values are 16 contiguous bytes
+// of the buffer common_mode_kernel wrote, 1 KiB coalesced over the wave.
+struct alignas(16) CommonLane {
+  int16_t v[8];
+};
+__device__ __forceinline__ void add_common(int n[8], const CommonDev& cm, uint32_t e, uint32_t g, int lane) {
+  const CommonLane c =
+      *reinterpret_cast<const CommonLane*>(cm.values + ((size_t)e * (size_t)cm.n_groups + g) * ATTPC_NUM_TB + 8 * lane);
+  for (int s = 0; s < 8; ++s) n[s] += (int)c.v[s];
+}
+
+// (`e`: the event within the launch, which places its common-mode values; `event` its global id)
+template <bool CM>
 __device__ __forceinline__ void add_noise(PadTrace& pt, const TraceNoiseDev& nz, const uint32_t* cdf,
-                                          const uint16_t* guide, uint64_t seed, uint64_t event, uint32_t pad, int lane) {
+                                          const uint16_t* guide, uint64_t seed, uint64_t event, uint32_t pad, int lane,
+                                          const CommonDev& cm, uint32_t e) {
   const int ped = nz.pedestals ? (int)nz.pedestals[pad] : 0;
   int n[8];
   noise_values(n, nz, cdf, guide, seed, event, pad, lane);
+  if constexpr (CM) {
+    const uint32_t g = common_group(cm, pad);
+    if (g != 255u) add_common(n, cm, e, g, lane);  // uniform
+  }
   int m = -4096;  // below any trace_p[j] - ped_p (>= -4095)
   for (int s = 0; s < 8; ++s) {
     int v = pt.v[s] + ped + n[s];
@@ -169,13 +199,15 @@ __device__ __forceinline__ bool trace_row_read(double padf, double tb, const Tra
   return trace_row_ok(padf, tb);
 }
 
-template <bool NOISE, bool RO>
+template <bool NOISE, bool RO, bool CM>
 __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, TraceNoiseDev nz, uint64_t seed,
                                                                  uint64_t first_event,
                                                                  const int64_t* __restrict__ event_start,
                                                                  const double* __restrict__ points,
                                                                  const int64_t* __restrict__ labels, TraceScratch sc,
-                                                                 uint32_t* __restrict__ kept, TraceReadoutDev ro) {
+                                                                 uint32_t* __restrict__ kept, TraceReadoutDev ro,
+                                                                 CommonDev cm) {
+  static_assert(NOISE || !CM, "the common-mode term is added where the pad noise is");
   __shared__ uint32_t cursor[ATTPC_NUM_PADS];  // counts, then the next free place of every pad's group
   __shared__ double resp[ATTPC_NUM_TB];
   __shared__ uint32_t noise_cdf[ATTPC_MAX_NOISE_LEVELS];  // (NOISE only: the noiseless kernel never names them)
@@ -197,8 +229,10 @@ __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, Tr
   for (int p = t; p < ATTPC_NUM_PADS; p += TR_THREADS) cursor[p] = 0u;
   for (int j = t; j < ATTPC_NUM_TB; j += TR_THREADS) resp[j] = tr.response[j];
   if constexpr (NOISE) {
-    for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += TR_THREADS) noise_cdf[i] = nz.cdf[i];
-    if (t < 256) noise_guide[t] = nz.guide[t];
+    if (!CM || nz.n_levels > 0) {  // uniform (with CM the pad table may be off: no table on the device then)
+      for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += TR_THREADS) noise_cdf[i] = nz.cdf[i];
+      if (t < 256) noise_guide[t] = nz.guide[t];
+    }
   }
   if (t == 0) kept_run = 0u;
   block_sync();
@@ -264,7 +298,7 @@ __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, Tr
     }
     const uint32_t start = sc.hit_start[lo + k], end = k + 1 < H ? sc.hit_start[lo + k + 1] : V;
     PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
-    if constexpr (NOISE) add_noise(pt, nz, noise_cdf, noise_guide, seed, first_event + e, sc.hit[lo + k], lane);
+    if constexpr (NOISE) add_noise<CM>(pt, nz, noise_cdf, noise_guide, seed, first_event + e, sc.hit[lo + k], lane, cm, e);
     if (lane == 0) sc.rank[lo + k] = (double)pt.max > tr.threshold ? 1 : 0;
   }
   __threadfence_block();
@@ -295,7 +329,7 @@ __global__ __launch_bounds__(TR_THREADS) void trace_count_kernel(TraceDev tr, Tr
   }
 }
 
-template <bool NOISE>
+template <bool NOISE, bool CM>
 __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, TraceNoiseDev nz, uint64_t seed,
                                                                  uint64_t first_event,
                                                                  const int64_t* __restrict__ event_start,
@@ -304,7 +338,8 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, Tr
                                                                  const int64_t* __restrict__ kept_start,
                                                                  int32_t* __restrict__ pads, int16_t* __restrict__ samples,
                                                                  int64_t* __restrict__ out_labels,
-                                                                 unsigned long long* __restrict__ sums) {
+                                                                 unsigned long long* __restrict__ sums, CommonDev cm) {
+  static_assert(NOISE || !CM, "the common-mode term is added where the pad noise is");
   __shared__ double resp[ATTPC_NUM_TB];
   __shared__ double qtab[TR_WAVES][ATTPC_NUM_TB];
   __shared__ unsigned long long wave_sum[TR_WAVES][2];
@@ -318,8 +353,10 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, Tr
   const uint32_t H = sc.info[2 * e], V = sc.info[2 * e + 1];
   for (int j = t; j < ATTPC_NUM_TB; j += TR_THREADS) resp[j] = tr.response[j];
   if constexpr (NOISE) {
-    for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += TR_THREADS) noise_cdf[i] = nz.cdf[i];
-    if (t < 256) noise_guide[t] = nz.guide[t];
+    if (!CM || nz.n_levels > 0) {  // uniform
+      for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += TR_THREADS) noise_cdf[i] = nz.cdf[i];
+      if (t < 256) noise_guide[t] = nz.guide[t];
+    }
   }
   block_sync();
   const unsigned long long event = first_event + e;
@@ -331,7 +368,7 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, Tr
     PadTrace pt = pad_trace(tr, resp, qtab[wave], lane, points, labels, sc.row, lo, start, end);
     const int64_t o = out0 + rank;
     const uint32_t pad = sc.hit[lo + k];
-    if constexpr (NOISE) add_noise(pt, nz, noise_cdf, noise_guide, seed, event, pad, lane);
+    if constexpr (NOISE) add_noise<CM>(pt, nz, noise_cdf, noise_guide, seed, event, pad, lane, cm, e);
     int16_t* dst = samples + o * ATTPC_NUM_TB;
     for (int s = 0; s < 8; ++s) {
       const int j = lane + 64 * s;
@@ -360,34 +397,41 @@ __global__ __launch_bounds__(TR_THREADS) void trace_write_kernel(TraceDev tr, Tr
   }
 }
 
-template <bool NOISE, bool RO>
+template <bool NOISE, bool RO, bool CM>
 void launch_count(hipStream_t s, const TraceDev& tr, const TraceNoiseDev& nz, uint64_t seed, uint32_t n_events,
                   uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
-                  TraceScratch sc, uint32_t* kept, const TraceReadoutDev& ro) {
-  hipLaunchKernelGGL((trace_count_kernel<NOISE, RO>), dim3(n_events), dim3(TR_THREADS), 0, s, tr, nz, seed, first_event,
-                     event_start, points, labels, sc, kept, ro);
+                  TraceScratch sc, uint32_t* kept, const TraceReadoutDev& ro, const CommonDev& cm) {
+  hipLaunchKernelGGL((trace_count_kernel<NOISE, RO, CM>), dim3(n_events), dim3(TR_THREADS), 0, s, tr, nz, seed,
+                     first_event, event_start, points, labels, sc, kept, ro, cm);
 }
 
 void launch_trace_count(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
-                        TraceScratch sc, uint32_t* kept, const TraceReadoutDev* ro) {
+                        TraceScratch sc, uint32_t* kept, const TraceReadoutDev* ro, const CommonDev* common) {
   const TraceNoiseDev nz = noise ? *noise : TraceNoiseDev{};
   const TraceReadoutDev rd = ro ? *ro : TraceReadoutDev{};
-  if (noise && ro) launch_count<true, true>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd);
-  else if (noise) launch_count<true, false>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd);
-  else if (ro) launch_count<false, true>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd);
-  else launch_count<false, false>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd);
+  const CommonDev cm = common ? *common : CommonDev{};
+  if (common && ro) launch_count<true, true, true>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd, cm);
+  else if (common) launch_count<true, false, true>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd, cm);
+  else if (noise && ro) launch_count<true, true, false>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd, cm);
+  else if (noise) launch_count<true, false, false>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd, cm);
+  else if (ro) launch_count<false, true, false>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd, cm);
+  else launch_count<false, false, false>(s, tr, nz, seed, n_events, first_event, event_start, points, labels, sc, kept, rd, cm);
 }
 void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
                         TraceScratch sc, const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
-                        unsigned long long* sums) {
-  if (noise)
-    hipLaunchKernelGGL(trace_write_kernel<true>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, *noise, seed, first_event,
-                       event_start, points, labels, sc, kept_start, pads, samples, out_labels, sums);
+                        unsigned long long* sums, const CommonDev* common) {
+  const TraceNoiseDev nz = noise ? *noise : TraceNoiseDev{};
+  if (common)
+    hipLaunchKernelGGL((trace_write_kernel<true, true>), dim3(n_events), dim3(TR_THREADS), 0, s, tr, nz, seed, first_event,
+                       event_start, points, labels, sc, kept_start, pads, samples, out_labels, sums, *common);
+  else if (noise)
+    hipLaunchKernelGGL((trace_write_kernel<true, false>), dim3(n_events), dim3(TR_THREADS), 0, s, tr, nz, seed, first_event,
+                       event_start, points, labels, sc, kept_start, pads, samples, out_labels, sums, CommonDev{});
   else
-    hipLaunchKernelGGL(trace_write_kernel<false>, dim3(n_events), dim3(TR_THREADS), 0, s, tr, TraceNoiseDev{}, seed,
-                       first_event, event_start, points, labels, sc, kept_start, pads, samples, out_labels, sums);
+    hipLaunchKernelGGL((trace_write_kernel<false, false>), dim3(n_events), dim3(TR_THREADS), 0, s, tr, nz, seed,
+                       first_event, event_start, points, labels, sc, kept_start, pads, samples, out_labels, sums, CommonDev{});
 }
 
 
@@ -398,10 +442,28 @@ static_assert(TR_MAP_WORDS <= RO_THREADS, "a thread holds at most one word of th
 
 // The verdict of noise-only pad `pad` of S in PARTIAL readout (wave-uniform), the decision rule of include/attpc_engine.h:
 // kept iff 4095 - ped > thr and (-ped > thr or max_j n_j > thr), and max_j n_j > thr iff some u_j >= cdf[c - 1].
+// With CM a pad of group g != 255 has the sums n_j + c_g[j] in place of n_j: the pedestal terms stay, the one-compare
+// cutoff does not hold (it is the pad table's alone), so the pad's own draw is made and every sum compared -- unless no
+// sum of two levels reaches above thr (cm.top <= thr: never).  `cdf` / `guide`: the pad table in LDS (CM only).
+template <bool CM>
 __device__ __forceinline__ bool noise_only_kept(const TraceDev& tr, const TraceNoiseDev& nz, const TraceReadoutDev& ro,
-                                                uint64_t seed, uint64_t event, uint32_t pad, int lane) {
+                                                uint64_t seed, uint64_t event, uint32_t pad, int lane, const uint32_t* cdf,
+                                                const uint16_t* guide, const CommonDev& cm, uint32_t e) {
   const int ped = nz.pedestals ? (int)nz.pedestals[pad] : 0;
   if (!((double)(4095 - ped) > tr.threshold)) return false;
+  if constexpr (CM) {
+    const uint32_t g = common_group(cm, pad);
+    if (g != 255u) {  // uniform
+      if ((double)(-ped) > tr.threshold) return true;
+      if (!((double)cm.top > tr.threshold)) return false;
+      int n[8];
+      noise_values(n, nz, cdf, guide, seed, event, pad, lane);
+      add_common(n, cm, e, g, lane);
+      bool over = false;
+      for (int s = 0; s < 8; ++s) over |= (double)n[s] > tr.threshold;
+      return __ballot(over) != 0ull;
+    }
+  }
   if ((double)(-ped) > tr.threshold || ro.cut_kind == TRACE_CUT_ALWAYS) return true;
   if (ro.cut_kind == TRACE_CUT_NEVER) return false;
   bool over = false;
@@ -416,14 +478,23 @@ __device__ __forceinline__ bool noise_only_kept(const TraceDev& tr, const TraceN
   return __ballot(over) != 0ull;
 }
 
+template <bool CM>
 __global__ __launch_bounds__(RO_THREADS) void trace_scan_kernel(TraceDev tr, TraceNoiseDev nz, TraceReadoutDev ro,
                                                                 uint64_t seed, uint64_t first_event,
                                                                 const int64_t* __restrict__ event_start, TraceScratch sc,
-                                                                uint32_t* __restrict__ kept, TraceMaps maps) {
+                                                                uint32_t* __restrict__ kept, TraceMaps maps, CommonDev cm) {
   __shared__ uint32_t hit_w[TR_MAP_WORDS], kept_w[TR_MAP_WORDS], before_w[TR_MAP_WORDS];
   __shared__ uint32_t wave_total[RO_WAVES];
+  __shared__ uint32_t noise_cdf[ATTPC_MAX_NOISE_LEVELS];  // (CM only: 2.5 KiB, the occupancy stays full)
+  __shared__ uint16_t noise_guide[256];
   const uint32_t e = blockIdx.x;
   const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  if constexpr (CM) {
+    if (nz.n_levels > 0 && !ro.full) {  // uniform
+      for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += RO_THREADS) noise_cdf[i] = nz.cdf[i];
+      if (t < 256) noise_guide[t] = nz.guide[t];
+    }
+  }
   for (int w = t; w < TR_MAP_WORDS; w += RO_THREADS) {
     hit_w[w] = 0u;
     kept_w[w] = 0u;
@@ -448,7 +519,8 @@ __global__ __launch_bounds__(RO_THREADS) void trace_scan_kernel(TraceDev tr, Tra
       while (cand) {  // uniform
         const int b = __builtin_ctz(cand);
         cand &= cand - 1u;
-        if (noise_only_kept(tr, nz, ro, seed, event, 32u * (uint32_t)w + (uint32_t)b, lane)) nw |= 1u << b;
+        if (noise_only_kept<CM>(tr, nz, ro, seed, event, 32u * (uint32_t)w + (uint32_t)b, lane, noise_cdf, noise_guide, cm, e))
+          nw |= 1u << b;
       }
     }
     if (lane == 0) {
@@ -483,13 +555,15 @@ __global__ __launch_bounds__(RO_THREADS) void trace_scan_kernel(TraceDev tr, Tra
   }
 }
 
+template <bool CM>
 __global__ __launch_bounds__(RO_THREADS) void trace_noise_write_kernel(TraceNoiseDev nz, uint64_t seed,
                                                                        uint64_t first_event, TraceMaps maps,
                                                                        const int64_t* __restrict__ kept_start,
                                                                        int32_t* __restrict__ pads,
                                                                        int16_t* __restrict__ samples,
                                                                        int64_t* __restrict__ out_labels,
-                                                                       unsigned long long* __restrict__ sums) {
+                                                                       unsigned long long* __restrict__ sums,
+                                                                       CommonDev cm) {
   __shared__ uint32_t noise_cdf[ATTPC_MAX_NOISE_LEVELS];
   __shared__ uint16_t noise_guide[256];
   __shared__ unsigned long long wave_sum[RO_WAVES][2];
@@ -517,6 +591,10 @@ __global__ __launch_bounds__(RO_THREADS) void trace_noise_write_kernel(TraceNois
       const int ped = nz.pedestals ? (int)nz.pedestals[pad] : 0;
       int n[8];
       noise_values(n, nz, noise_cdf, noise_guide, seed, event, pad, lane);
+      if constexpr (CM) {
+        const uint32_t g = common_group(cm, pad);
+        if (g != 255u) add_common(n, cm, e, g, lane);  // uniform
+      }
       int16_t* dst = samples + o * ATTPC_NUM_TB;
       for (int s = 0; s < 8; ++s) {
         const int j = lane + 64 * s;
@@ -550,15 +628,59 @@ __global__ __launch_bounds__(RO_THREADS) void trace_noise_write_kernel(TraceNois
 
 void launch_trace_scan(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, const TraceReadoutDev& ro,
                        uint64_t seed, uint32_t n_events, uint64_t first_event, const int64_t* event_start, TraceScratch sc,
-                       uint32_t* kept, TraceMaps maps) {
-  hipLaunchKernelGGL(trace_scan_kernel, dim3(n_events), dim3(RO_THREADS), 0, s, tr, noise ? *noise : TraceNoiseDev{}, ro,
-                     seed, first_event, event_start, sc, kept, maps);
+                       uint32_t* kept, TraceMaps maps, const CommonDev* common) {
+  const TraceNoiseDev nz = noise ? *noise : TraceNoiseDev{};
+  if (common)
+    hipLaunchKernelGGL(trace_scan_kernel<true>, dim3(n_events), dim3(RO_THREADS), 0, s, tr, nz, ro, seed, first_event,
+                       event_start, sc, kept, maps, *common);
+  else
+    hipLaunchKernelGGL(trace_scan_kernel<false>, dim3(n_events), dim3(RO_THREADS), 0, s, tr, nz, ro, seed, first_event,
+                       event_start, sc, kept, maps, CommonDev{});
 }
 void launch_trace_noise_write(hipStream_t s, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                               uint64_t first_event, TraceMaps maps, const int64_t* kept_start, int32_t* pads,
-                              int16_t* samples, int64_t* out_labels, unsigned long long* sums) {
-  hipLaunchKernelGGL(trace_noise_write_kernel, dim3(n_events), dim3(RO_THREADS), 0, s, noise ? *noise : TraceNoiseDev{},
-                     seed, first_event, maps, kept_start, pads, samples, out_labels, sums);
+                              int16_t* samples, int64_t* out_labels, unsigned long long* sums, const CommonDev* common) {
+  const TraceNoiseDev nz = noise ? *noise : TraceNoiseDev{};
+  if (common)
+    hipLaunchKernelGGL(trace_noise_write_kernel<true>, dim3(n_events), dim3(RO_THREADS), 0, s, nz, seed, first_event, maps,
+                       kept_start, pads, samples, out_labels, sums, *common);
+  else
+    hipLaunchKernelGGL(trace_noise_write_kernel<false>, dim3(n_events), dim3(RO_THREADS), 0, s, nz, seed, first_event, maps,
+                       kept_start, pads, samples, out_labels, sums, CommonDev{});
+}
+
+// ---- common-mode noise: the values of every (event, group) of a launch ----
+constexpr int CMN_THREADS = 512;
+constexpr int CMN_WAVES = CMN_THREADS / 64;
+
+// One wave per (event, group): item i = e * n_groups + g, its 512 values drawn as a pad's noise is (noise_values with
+// the stage's table and domain, the group in the pad's place) and stored where the lanes of the trace kernels read them
+// (add_common): 1 KiB per item, one 16-byte store per lane.  The table sits in LDS as in the trace kernels.
+__global__ __launch_bounds__(CMN_THREADS) void common_mode_kernel(TraceNoiseDev table, uint64_t seed, uint64_t first_event,
+                                                                  uint32_t n_groups, uint64_t n_items,
+                                                                  int16_t* __restrict__ values) {
+  __shared__ uint32_t cdf[ATTPC_MAX_NOISE_LEVELS];
+  __shared__ uint16_t guide[256];
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  for (int i = t; i < ATTPC_MAX_NOISE_LEVELS; i += CMN_THREADS) cdf[i] = table.cdf[i];
+  if (t < 256) guide[t] = table.guide[t];
+  block_sync();
+  const uint64_t item = (uint64_t)blockIdx.x * CMN_WAVES + (uint64_t)wave;
+  if (item >= n_items) return;  // uniform per wave
+  const uint64_t e = item / n_groups;
+  const uint32_t g = (uint32_t)(item - e * n_groups);
+  int n[8];
+  noise_values(n, table, cdf, guide, seed, first_event + e, g, lane);
+  CommonLane c;
+  for (int s = 0; s < 8; ++s) c.v[s] = (int16_t)n[s];  // levels lie in -4095 .. 4606
+  *reinterpret_cast<CommonLane*>(values + item * ATTPC_NUM_TB + 8 * lane) = c;
+}
+
+void launch_common_mode(hipStream_t s, const TraceNoiseDev& table, uint64_t seed, uint32_t n_events, uint64_t first_event,
+                        uint32_t n_groups, int16_t* values) {
+  const uint64_t n_items = (uint64_t)n_events * n_groups;
+  hipLaunchKernelGGL(common_mode_kernel, dim3((uint32_t)((n_items + CMN_WAVES - 1) / CMN_WAVES)), dim3(CMN_THREADS), 0, s,
+                     table, seed, first_event, n_groups, n_items, values);
 }
 
 }  // namespace attpc

@@ -124,25 +124,39 @@ struct TraceMaps {
   uint32_t* kept;
   uint32_t* before;
 };
+// common-mode noise of the traces (attpc_trace_configure_common_mode): what the sample-producing kernels read
+struct CommonDev {
+  const int16_t* values;  // [events of the launch][n_groups][512], a group's 512 values in lane order: sample l + 64 s
+                          // at 8 l + s (common_mode_kernel writes them, add_common reads 16 B per lane)
+  const uint8_t* groups;  // [ATTPC_NUM_PADS] on the device: the pad's group, 255 = no common-mode term; nullptr = group 0
+  int32_t n_groups;       // 1 + the highest group of the map
+  int32_t top;            // largest pad-noise level + largest common-mode level: no sum n_p[j] + c_g[j] is above it
+};
+// values of events first_event .. first_event + n_events - 1, one wave per (event, group); `table`: the stage's own
+// noise table (cdf padded, guide, n_levels > 0, min_level, domain = DOMAIN_TRACE_COMMON | stream)
+void launch_common_mode(hipStream_t s, const TraceNoiseDev& table, uint64_t seed, uint32_t n_events, uint64_t first_event,
+                        uint32_t n_groups, int16_t* values);
 // kept[e]: kept pad rows of event e (the count pass works out every trace, keeps the ranks in scratch).
-// noise == nullptr: the noiseless kernels; ro == nullptr: hit-mode readout
+// noise == nullptr: the noiseless kernels; ro == nullptr: hit-mode readout; common == nullptr: no common-mode term
+// (with it the kernels with noise run, `noise` may then be a table-less, pedestal-less TraceNoiseDev or nullptr)
 void launch_trace_count(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
-                        TraceScratch sc, uint32_t* kept, const TraceReadoutDev* ro);
+                        TraceScratch sc, uint32_t* kept, const TraceReadoutDev* ro, const CommonDev* common = nullptr);
 // behind the count pass with ro: the noise-only verdicts of every event (empty ones included), kept[e] and the hit pads'
 // ranks over the union of kept pads, the maps of the noise write
 void launch_trace_scan(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, const TraceReadoutDev& ro,
                        uint64_t seed, uint32_t n_events, uint64_t first_event, const int64_t* event_start, TraceScratch sc,
-                       uint32_t* kept, TraceMaps maps);
+                       uint32_t* kept, TraceMaps maps, const CommonDev* common = nullptr);
 // the noise-only rows (label -1) at kept_start[e] + rank; the checksums as launch_trace_write
 void launch_trace_noise_write(hipStream_t s, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                               uint64_t first_event, TraceMaps maps, const int64_t* kept_start, int32_t* pads,
-                              int16_t* samples, int64_t* out_labels, unsigned long long* sums);
+                              int16_t* samples, int64_t* out_labels, unsigned long long* sums,
+                              const CommonDev* common = nullptr);
 // the kept rows at kept_start[e] + rank; sums[0] += sample checksum, sums[1] += pad checksum (event = first_event + e)
 void launch_trace_write(hipStream_t s, const TraceDev& tr, const TraceNoiseDev* noise, uint64_t seed, uint32_t n_events,
                         uint64_t first_event, const int64_t* event_start, const double* points, const int64_t* labels,
                         TraceScratch sc, const int64_t* kept_start, int32_t* pads, int16_t* samples, int64_t* out_labels,
-                        unsigned long long* sums);
+                        unsigned long long* sums, const CommonDev* common = nullptr);
 
 // micromegas gain of the traces (gain.hip; attpc_trace_configure_gain, the contract is in include/attpc_engine.h)
 struct GainDev {

@@ -13,7 +13,8 @@ _EXPORTS = {
     _traces: ("configure_traces", "simulate_batch_traces", "clouds_to_traces", "PeakSettings", "configure_trace_rows",
               "simulate_batch_trace_rows", "clouds_to_trace_rows", "BaselineSettings", "configure_baseline", "remove_baseline",
               "TriggerSettings", "configure_trigger", "traces_to_trigger", "TRIGGER_DTYPE",
-              "GainSettings", "configure_gain", "clouds_to_gain", "polya_rel_variance", "normal_quantile_table"),
+              "GainSettings", "configure_gain", "clouds_to_gain", "polya_rel_variance", "normal_quantile_table",
+              "CommonModeSettings", "configure_common_mode", "common_mode_values"),
     _summary: ("SummarySettings", "configure_summary", "simulate_batch_summary", "clouds_to_summary",
                "electrons_above_threshold"),
     _selection: ("Selection", "configure_selection", "simulate_batch_selected", "clouds_to_selection"),

@@ -163,14 +163,15 @@ def delivery_of(writer, config: Config):
     return "cloud", lambda points, labels, event: writer.write(points, labels, config, event)
 
 
-def plan_delivery(writer, config: Config, selection=None, trigger=None, gain=None, plain_clouds: bool = True):
+def plan_delivery(writer, config: Config, selection=None, trigger=None, gain=None, plain_clouds: bool = True,
+                  common_mode=None):
     """What run_simulation and run_fused may be asked for with ``writer`` -> (kind, emit, chain): ``delivery_of`` and,
     for a writer of traces or trace rows, the ``detector.traces.TraceChain`` to run (else None): ``writer.chain`` -- a
     writer without one: the TraceChain fields it has as attributes (``noise`` and ``readout`` as settings objects), the
     rest at their defaults -- on the run's ``config`` (it fills in a response or threshold the writer left unset), with
-    ``trigger``, gated for trace rows, and ``gain`` if given, else the writer's.  ValueError for a ``selection`` with a
-    trace writer and for a ``trigger`` or a ``gain`` with any other; AttributeError for plain clouds without a
-    selection unless ``plain_clouds``."""
+    ``trigger``, gated for trace rows, and ``gain`` and ``common_mode`` if given, else the writer's.  ValueError for a
+    ``selection`` with a trace writer and for a ``trigger``, a ``gain`` or a ``common_mode`` with any other;
+    AttributeError for plain clouds without a selection unless ``plain_clouds``."""
     kind, emit = delivery_of(writer, config)
     traces = kind in ("traces", "trace_rows")
     if selection is not None and traces:
@@ -179,15 +180,18 @@ def plan_delivery(writer, config: Config, selection=None, trigger=None, gain=Non
         raise ValueError("a trigger delivers traces or trace rows: writers of Spyral rows or clouds are not supported")
     if gain is not None and not traces:
         raise ValueError("a gain acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
+    if common_mode is not None and not traces:
+        raise ValueError("common-mode noise acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
     if kind == "cloud" and selection is None and not plain_clouds:
         raise AttributeError("run_fused needs a writer that offers write_rows or write_traces")
     if not traces:
         return kind, emit, None
-    names = ("response", "threshold", "offset", "noise", "readout", "gain", "peaks", "baseline")
+    names = ("response", "threshold", "offset", "noise", "readout", "gain", "peaks", "baseline", "common_mode")
     chain = getattr(writer, "chain", None) or TraceChain(config, **{n: getattr(writer, n) for n in names if hasattr(writer, n)})
     if trigger is not None and kind == "trace_rows":
         trigger = trigger.gated()
-    return kind, emit, chain.replace(config=config, trigger=trigger, gain=chain.gain if gain is None else gain)
+    return kind, emit, chain.replace(config=config, trigger=trigger, gain=chain.gain if gain is None else gain,
+                                     common_mode=chain.common_mode if common_mode is None else common_mode)
 
 
 def selected_events(res: dict, key: str):
@@ -225,7 +229,7 @@ def deliver_events(writer, n_events: int, batch_size: int, batch, emit) -> None:
 
 def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
                    indices: list[int] | None = None, batch_size: int = 16384,
-                   seed: int | None = None, selection=None, trigger=None, gain=None):
+                   seed: int | None = None, selection=None, trigger=None, gain=None, common_mode=None):
     """Apply the detector simulation to every event of a kinematics file (reference
     simulator.py:118-210): the writer is called once per event with a non-empty cloud, in event order, then
     closed.  A writer that offers ``write_rows`` (SpyralWriter) receives its rows ready to store: the response
@@ -242,7 +246,9 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     reach the writer, with their original event numbers -- a writer that receives traces or trace rows (for the latter
     the device skips the peak work of the others too); any other raises ValueError.  ``gain`` (a
     ``detector.traces.GainSettings``; default: the writer's own ``gain``, None = off): the micromegas gain of the traces
-    -- again a writer that receives traces or trace rows; any other raises ValueError."""
+    -- again a writer that receives traces or trace rows; any other raises ValueError.  ``common_mode`` (a
+    ``detector.traces.CommonModeSettings``; default: the writer's own, None = off): the common-mode noise of the traces,
+    under the same rule."""
     from ..io import KinematicsFileReader
 
     print("------- AT-TPC Simulation Engine (MI355X) -------")
@@ -255,7 +261,7 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     print(f"Output will be written to {writer.get_directory_name()}.")
     rng = default_rng(seed)
     run_seed = int(rng.integers(0, 1 << 63))
-    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain)
+    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, common_mode=common_mode)
 
     def batch(start, stop):
         vertices, momenta = reader.read(start, stop)

@@ -40,6 +40,11 @@ charge before the trace kernels read it -- a pure function of (seed, global even
 (include/attpc_engine.h; ``tests/gain_reference.py`` restates it).  ``clouds_to_gain`` is that stage alone on any host
 cloud.
 
+Common-mode noise is opt-in beside the pad noise (``CommonModeSettings``, ``common_mode=``): one further table-driven
+draw per (event, group, sample), added to every pad of the group before the clamp -- the coherent part of the GET
+noise, which lifts a whole chip or board over a threshold in the same sample.  The pad -> group map is the caller's
+(include/attpc_engine.h; ``tests/common_mode_reference.py`` restates it).  ``common_mode_values`` is that stage alone.
+
 Every stage is a settings class with its context slot (``slot``), its C call (``call``), ``token()`` -- its content,
 None when the stage changes nothing -- and ``desc()``, the call's descriptor; ``configure_stage`` applies any of them.
 ``TraceChain`` is one whole trace configuration, validated once: the entry points build it from their keywords, the
@@ -99,6 +104,31 @@ def configure_stage(ctx: _abi.Context, stage, settings) -> None:
     ctx.configure(stage.slot, token, stage.call, None if token is None else settings.desc())
 
 
+def _noise_table(what: str, sigma, table):
+    """(cdf u32, min_level, n_levels, sigma) of a noise table given as the Gaussian of ``sigma`` or as ``table`` =
+    (cdf, min_level), under the rules of ``NoiseSettings`` (``what`` names the table in the messages)."""
+    if table is not None and float(sigma) != 0.0:
+        raise ValueError(f"give the {what} sigma or its table, not both")
+    if table is None:
+        cdf, min_level = gaussian_noise_table(sigma)
+        sigma = float(sigma)
+    else:
+        cdf, min_level = table
+        sigma = math.nan
+    cdf = np.asarray(cdf)
+    if cdf.ndim != 1 or (cdf.size and (cdf.dtype.kind not in "iu" or cdf.min() < 0 or cdf.max() >= 1 << 32)):
+        raise ValueError(f"the {what} cdf must be a 1-D array of integers in [0, 2^32)")
+    if cdf.size + 1 > _abi.MAX_NOISE_LEVELS:
+        raise ValueError(f"a {what} table of {cdf.size + 1} levels: at most {_abi.MAX_NOISE_LEVELS}")
+    cdf = np.ascontiguousarray(cdf, dtype=np.uint32)
+    if np.any(np.diff(cdf.astype(np.int64)) < 0):
+        raise ValueError(f"the {what} cdf decreases")
+    if int(min_level) != min_level or not -4095 <= int(min_level) <= 4095:
+        raise ValueError(f"{what} min_level must be an integer in -4095 .. 4095, got {min_level}")
+    n_levels = cdf.size + 1 if (cdf.size or int(min_level)) else 0
+    return cdf, int(min_level), n_levels, (sigma if n_levels else 0.0)
+
+
 class NoiseSettings:
     """The validated noise of a trace configuration: cdf [n_levels - 1] u32, min_level, n_levels (0 = no noise draw),
     pedestals [ATTPC_NUM_PADS] i16 or None, stream, sigma (NaN for a custom table, 0 without noise)."""
@@ -106,28 +136,7 @@ class NoiseSettings:
     slot, call = "trace_noise", "attpc_trace_configure_noise"
 
     def __init__(self, noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0):
-        if noise_table is not None and float(noise_sigma) != 0.0:
-            raise ValueError("give noise_sigma or noise_table, not both")
-        if noise_table is None:
-            cdf, min_level = gaussian_noise_table(noise_sigma)
-            self.sigma = float(noise_sigma)
-        else:
-            cdf, min_level = noise_table
-            self.sigma = math.nan
-        cdf = np.asarray(cdf)
-        if cdf.ndim != 1 or (cdf.size and (cdf.dtype.kind not in "iu" or cdf.min() < 0 or cdf.max() >= 1 << 32)):
-            raise ValueError("the noise cdf must be a 1-D array of integers in [0, 2^32)")
-        if cdf.size + 1 > _abi.MAX_NOISE_LEVELS:
-            raise ValueError(f"a noise table of {cdf.size + 1} levels: at most {_abi.MAX_NOISE_LEVELS}")
-        self.cdf = np.ascontiguousarray(cdf, dtype=np.uint32)
-        if np.any(np.diff(self.cdf.astype(np.int64)) < 0):
-            raise ValueError("the noise cdf decreases")
-        if int(min_level) != min_level or not -4095 <= int(min_level) <= 4095:
-            raise ValueError(f"noise min_level must be an integer in -4095 .. 4095, got {min_level}")
-        self.min_level = int(min_level)
-        self.n_levels = self.cdf.size + 1 if (self.cdf.size or self.min_level) else 0
-        if self.n_levels == 0:
-            self.sigma = 0.0
+        self.cdf, self.min_level, self.n_levels, self.sigma = _noise_table("noise", noise_sigma, noise_table)
         if pedestals is not None:
             ped = np.broadcast_to(np.asarray(pedestals), (_abi.NUM_PADS,))
             if ped.dtype.kind not in "iu" or ped.min() < 0 or ped.max() > 4095:
@@ -158,6 +167,93 @@ class NoiseSettings:
 def configure_noise(ctx: _abi.Context, noise: NoiseSettings) -> None:
     """``attpc_trace_configure_noise`` unless this ctx already holds the same noise (decided on its content)."""
     configure_stage(ctx, NoiseSettings, noise)
+
+
+class CommonModeSettings:
+    """The validated common-mode noise of the traces (``attpc_trace_common_desc``, include/attpc_engine.h): the table of
+    its own as ``sigma`` (``gaussian_noise_table``) or ``table`` = (cdf, min_level) under the rules of the pad noise's,
+    ``groups`` ([ATTPC_NUM_PADS] uint8: below 255 the pad's group -- its chip or board; the map is the caller's --,
+    255 = the pad has no common-mode term; None = every pad in group 0) and ``stream`` in [0, 2^29) (another
+    realisation).  ``cdf``, ``min_level``, ``n_levels`` (0 = off) and ``n_groups`` (1 + the highest group) are the
+    results."""
+
+    slot, call = "trace_common", "attpc_trace_configure_common_mode"
+
+    def __init__(self, sigma: float = 0.0, table=None, groups=None, stream: int = 0):
+        self.cdf, self.min_level, self.n_levels, self.sigma = _noise_table("common-mode", sigma, table)
+        if groups is not None:
+            g = np.asarray(groups)
+            if g.shape != (_abi.NUM_PADS,) or g.dtype != np.uint8:
+                raise ValueError(f"common-mode groups must be {_abi.NUM_PADS} uint8, got {g.dtype} {g.shape}")
+            groups = np.ascontiguousarray(g)
+        self.groups = groups
+        if isinstance(stream, (bool, np.bool_)) or int(stream) != stream or not 0 <= int(stream) < 1 << 29:
+            raise ValueError(f"common-mode stream must be an integer in [0, 2^29), got {stream!r}")
+        self.stream = int(stream)
+
+    @property
+    def n_groups(self) -> int:
+        """1 + the highest group of the map (0: no pad has a group)."""
+        if self.groups is None:
+            return 1
+        used = self.groups[self.groups != 255]
+        return int(used.max()) + 1 if used.size else 0
+
+    @property
+    def on(self) -> bool:
+        """Anything added to a sample."""
+        return self.n_levels > 0 and self.n_groups > 0
+
+    def level_masses(self):
+        """(levels, their probabilities) of the table; the one level 0 when the stage is off."""
+        return _level_masses(self.cdf, self.min_level) if self.on else (np.zeros(1, dtype=np.int64), np.ones(1))
+
+    def token(self):
+        if not self.on:
+            return None
+        return (self.cdf.tobytes(), self.min_level, self.n_levels, None if self.groups is None else self.groups.tobytes(),
+                self.stream)
+
+    def desc(self) -> _abi.TraceCommonDesc:
+        """(the descriptor points into ``self.groups`` and ``self.cdf``: keep the settings alive over the call)"""
+        return _abi.TraceCommonDesc(_abi.iptr(self.groups, _abi.C.c_uint8), _abi.iptr(self.cdf, _abi.C.c_uint32),
+                                    self.n_levels, self.min_level, self.stream, 0)
+
+
+def _checked_common_mode(common_mode):
+    if common_mode is not None and not isinstance(common_mode, CommonModeSettings):
+        raise TypeError("common_mode must be a CommonModeSettings or None")
+    return common_mode
+
+
+def configure_common_mode(ctx: _abi.Context, common_mode: CommonModeSettings | None) -> None:
+    """``attpc_trace_configure_common_mode`` unless this ctx already holds the same setting (``None``, or one without
+    effect: off)."""
+    configure_stage(ctx, CommonModeSettings, _checked_common_mode(common_mode))
+
+
+def common_mode_values(n_events: int, common_mode: CommonModeSettings, seed: int = 0, first_event: int = 0,
+                       ctx: _abi.Context | None = None) -> np.ndarray:
+    """The common-mode stage alone (``attpc_common_mode_rows``; the kernel of the fused path, no other configuration
+    needed): c_g[j] of the global events ``first_event`` .. as [n_events, n_groups, 512] int16.  ``common_mode`` is
+    configured first; one that is off gives zeros."""
+    if not isinstance(common_mode, CommonModeSettings):
+        raise TypeError("common_mode must be a CommonModeSettings")
+    seed, first_event, n = _abi.check_id_range(seed, first_event, int(n_events))
+    ctx = ctx or _abi.default_context()
+    configure_common_mode(ctx, common_mode)
+    out = np.zeros((n, common_mode.n_groups, _abi.NUM_TB), dtype=np.int16)
+    if common_mode.on and n:
+        ctx.check(ctx.lib.attpc_common_mode_rows(ctx.handle, seed, first_event, n, _abi.iptr(out, _abi.C.c_int16)),
+                  "attpc_common_mode_rows")
+    return out
+
+
+def _level_masses(cdf, min_level: int):
+    """(levels [n], probabilities [n]) of a noise table: level min_level + i has 2^-32 (cdf[i] - cdf[i - 1]), with
+    cdf[-1] = 0 and cdf[n - 1] = 2^32."""
+    edges = np.concatenate(([0], np.asarray(cdf, dtype=np.int64), [1 << 32]))
+    return int(min_level) + np.arange(len(edges) - 1, dtype=np.int64), np.diff(edges) / 2.0 ** 32
 
 
 READOUT_MODES = {"hit": _abi.READOUT_HIT, "partial": _abi.READOUT_PARTIAL, "full": _abi.READOUT_FULL}
@@ -239,12 +335,15 @@ def readout_cutoff(cdf, min_level: int, threshold: float):
     return "draw", int(cdf[c - 1])
 
 
-def expected_noise_pads(noise_table, threshold: float, readout_pads=None, pedestals=None) -> float:
+def expected_noise_pads(noise_table, threshold: float, readout_pads=None, pedestals=None, common_mode=None) -> float:
     """The mean number of noise-only pads a partial readout keeps per event: sum over the pads p of the readout set of
     1 - (1 - q_p)^512, q_p the exact probability 2^-32 (2^32 - cut) that one draw reaches the cutoff of the decision
     rule, with its pedestal terms (a pad with 4095 - ped_p <= thr is never kept, one with -ped_p > thr always).
     ``noise_table``: (cdf, min_level), or None for no noise; ``readout_pads`` and ``pedestals`` as configure_traces
-    takes them."""
+    takes them.  ``common_mode`` (a ``CommonModeSettings``; None = off): for a pad with a group the per-sample probability
+    is P(n + c > thr), from the convolution of the two tables' level masses; the pad's probability is still
+    1 - (1 - q)^512, its 512 sums being independent, and the mean over the pads is still their sum.  The pads of a group
+    share their common-mode draws and are correlated, so the number of kept pads does not have the binomial variance."""
     cdf, min_level = (np.zeros(0, dtype=np.uint32), 0) if noise_table is None else noise_table
     noise = NoiseSettings(noise_table=(cdf, min_level), pedestals=pedestals)
     mask = readout_mask(readout_pads).astype(bool)
@@ -256,6 +355,14 @@ def expected_noise_pads(noise_table, threshold: float, readout_pads=None, pedest
         p_draw = -math.expm1(_abi.NUM_TB * math.log1p(-q)) if q < 1.0 else 1.0
     else:
         p_draw = 1.0 if kind == "always" else 0.0
+    p_draw = np.full(_abi.NUM_PADS, p_draw)
+    if _checked_common_mode(common_mode) is not None and common_mode.on:
+        levels, mass = _level_masses(noise.cdf, noise.min_level) if noise.n_levels else (np.zeros(1, dtype=np.int64), np.ones(1))
+        c_levels, c_mass = common_mode.level_masses()
+        over = (levels[:, None] + c_levels[None, :]) > thr
+        q = min(float((mass[:, None] * c_mass[None, :])[over].sum()), 1.0)
+        grouped = np.ones(_abi.NUM_PADS, dtype=bool) if common_mode.groups is None else common_mode.groups != 255
+        p_draw[grouped] = -math.expm1(_abi.NUM_TB * math.log1p(-q)) if q < 1.0 else 1.0
     p = np.where(4095 - ped > thr, np.where(-ped > thr, 1.0, p_draw), 0.0)
     return float(p[mask].sum())
 
@@ -268,14 +375,15 @@ class TraceChain:
     """One trace configuration, validated here, before any library call: ``config``, the ``response`` [512] f64,
     ``threshold`` and ``offset`` with their defaults filled in (``trace_settings``), the ``noise`` (a ``NoiseSettings``;
     None = off) and the ``readout`` (a ``ReadoutSettings``; None = hit pads), and the stages that are None when off:
-    ``gain``, ``peaks`` (trace rows; None = ``PeakSettings()``), ``baseline`` and ``trigger``."""
+    ``gain``, ``peaks`` (trace rows; None = ``PeakSettings()``), ``baseline``, ``trigger`` and ``common_mode``."""
 
     def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
-                 gain=None, peaks=None, baseline=None, trigger=None):
+                 gain=None, peaks=None, baseline=None, trigger=None, common_mode=None):
         self.config, self._given = config, (response, threshold)
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
         self.gain, self.peaks, self.baseline, self.trigger = _checked_gain(gain), peaks, baseline, trigger
+        self.common_mode = _checked_common_mode(common_mode)
 
     @classmethod
     def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
@@ -290,28 +398,31 @@ class TraceChain:
                    ReadoutSettings(get("readout", "hit"), get("readout_pads")))
 
     def replace(self, **fields) -> "TraceChain":
-        """The same chain with the given fields (config, gain, peaks, baseline, trigger; TypeError for any other)
-        replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger"}
+        """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode; TypeError for any
+        other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode"}
         if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline and trigger, not {sorted(unknown)}")
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger and common_mode, not {sorted(unknown)}")
         chain = copy.copy(self)
         vars(chain).update(fields)
         if "config" in fields:
             chain.response, chain.threshold, _ = trace_settings(chain.config, *self._given, self.offset)
         _checked_gain(chain.gain)
+        _checked_common_mode(chain.common_mode)
         return chain
 
     def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
         """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
-        trace, noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
+        trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
         baseline; trigger; gain.  A stage that is off is turned off, whatever an earlier use of the ctx left -- except
-        those of "trigger" and "gain" that ``keep`` names, which stay as the ctx holds them."""
+        those of "trigger", "gain" and "common_mode" that ``keep`` names, which stay as the ctx holds them."""
         from .simulator import configure_spyral
 
         ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
                       _abi.TraceDesc(_abi.dptr(self.response), self.threshold, self.offset, 0))
         configure_noise(ctx, self.noise)
+        if "common_mode" not in keep:
+            configure_common_mode(ctx, self.common_mode)
         configure_readout(ctx, self.readout)
         if rows:
             configure_spyral(self.config, ctx)
@@ -352,11 +463,11 @@ def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold
     0 .. 4095; ``noise_stream`` in [0, 2^31) draws another noise realisation.  ``readout``: "hit" (default: only pads
     with cloud rows), "partial" (noise-only pads of ``readout_pads`` that cross the threshold too) or "full" (every pad
     of ``readout_pads``); ``readout_pads``: None = every pad not in BEAM_PADS, a boolean mask [ATTPC_NUM_PADS] or
-    unique pad ids.  Everything is validated before the first call to the library; the trigger and the gain stay as
-    the ctx holds them."""
+    unique pad ids.  Everything is validated before the first call to the library; the trigger, the gain and the
+    common-mode noise stay as the ctx holds them."""
     chain = TraceChain(config, response, threshold, offset, NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream),
                        ReadoutSettings(readout, readout_pads))
-    chain.configure(ctx, keep=("trigger", "gain"))
+    chain.configure(ctx, keep=("trigger", "gain", "common_mode"))
 
 
 def validate_trace_kwargs(config: Config, trace_kwargs: dict, gain=None) -> None:
@@ -372,16 +483,17 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
                           response=None, threshold=None, offset: int = 0, capacity_per_event: int = 1024,
                           noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
                           readout: str = "hit", readout_pads=None, trigger: TriggerSettings | None = None,
-                          gain: GainSettings | None = None):
+                          gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None):
     """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``; the noise keyed on
     ``seed`` and the global event ids; ``readout`` / ``readout_pads`` as configure_traces) ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
     before the suppression, stats dict: the cloud's run statistics plus ``n_rows`` / ``sample_checksum`` /
     ``pad_checksum`` of the traces, and with ``trigger`` (a ``TriggerSettings``; None = off) its records [n] under
     ``"trigger"``).  ``gain`` (a ``GainSettings``; None = off): the micromegas gain of every cloud row's charge, keyed on
-    ``seed`` and the global event ids like the noise."""
+    ``seed`` and the global event ids like the noise.  ``common_mode`` (a ``CommonModeSettings``; None = off): the
+    common-mode noise of every pad with a group, keyed the same way."""
     chain = TraceChain(config, response, threshold, offset, NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream),
-                       ReadoutSettings(readout, readout_pads), gain, trigger=trigger)
+                       ReadoutSettings(readout, readout_pads), gain, trigger=trigger, common_mode=common_mode)
     return chain.run_batch(False, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event)
 
@@ -697,12 +809,14 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
 
 
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
-                         baseline: BaselineSettings | None = None, gain: GainSettings | None = None, **trace_kwargs) -> None:
+                         baseline: BaselineSettings | None = None, gain: GainSettings | None = None,
+                         common_mode: CommonModeSettings | None = None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
     the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
-    baseline (default None: off, the peaks stand on the configured pedestals) and the micromegas gain (default None:
-    off).  The trigger stays as the ctx holds it."""
-    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain)
+    baseline (default None: off, the peaks stand on the configured pedestals), the micromegas gain and the common-mode
+    noise (default None: off).  The trigger stays as the ctx holds it."""
+    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
+                                                                   common_mode=common_mode)
     chain.configure(ctx, rows=True, keep=("trigger",))
 
 
@@ -710,14 +824,17 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
                               peaks: PeakSettings | None = None, capacity_per_event: int = 2048,
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
-                              gain: GainSettings | None = None, **trace_kwargs):
+                              gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
+                              **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
     before any suppression, stats dict: the cloud's run statistics with ``n_points`` = the rows, plus ``n_rows`` /
     ``row_checksum``, and with ``trigger`` (a ``TriggerSettings``; None = off; its ``gate`` leaves the events that did
-    not fire without rows) its records [n] under ``"trigger"``).  ``gain`` as simulate_batch_traces takes it."""
-    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain)
+    not fire without rows) its records [n] under ``"trigger"``).  ``gain`` and ``common_mode`` as simulate_batch_traces
+    takes them."""
+    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
+                                                                   common_mode=common_mode)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event)
 

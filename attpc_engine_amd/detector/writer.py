@@ -152,7 +152,7 @@ class SpyralWriter(_RollingWriter):
 
     def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
                  first_run_number: int = 0, npz_fallback: bool = True, *, peaks=None, baseline=None,
-                 noise_seed: int = 0, gain=None, **trace_kwargs):
+                 noise_seed: int = 0, gain=None, common_mode=None, **trace_kwargs):
         """``peaks`` (keyword only; a ``detector.traces.PeakSettings``, default None = the reference's writer: one row
         per cloud point): the rows are the peaks of the event's digitised pad traces instead (EXTENSION, trace rows of
         include/attpc_engine.h), made on the device with the trace settings ``trace_kwargs`` (response, threshold,
@@ -161,15 +161,18 @@ class SpyralWriter(_RollingWriter):
         its own seed.  ``baseline`` (a ``detector.traces.BaselineSettings``, default None = the peaks stand on the
         configured pedestals): Spyral's Fourier baseline is removed from the traces first.  ``gain`` (a
         ``detector.traces.GainSettings``, default None = off): the micromegas gain of the traces, keyed like the noise.
-        The files have the same datasets either way."""
+        ``common_mode`` (a ``detector.traces.CommonModeSettings``, default None = off): the common-mode noise of the
+        traces, keyed the same way.  The files have the same datasets either way."""
         self.response = get_response(config).copy()
         self.peaks, self.baseline, self.gain, self.chain = peaks, baseline, gain, None
-        if peaks is None and (trace_kwargs or noise_seed or baseline is not None or gain is not None):
+        self.common_mode = common_mode
+        if peaks is None and (trace_kwargs or noise_seed or baseline is not None or gain is not None or common_mode is not None):
             given = (sorted(trace_kwargs) + (["noise_seed"] if noise_seed else []) + (["baseline"] if baseline is not None else [])
-                     + (["gain"] if gain is not None else []))
+                     + (["gain"] if gain is not None else []) + (["common_mode"] if common_mode is not None else []))
             raise TypeError(f"SpyralWriter takes trace settings only with peaks=: {given}")
         if peaks is not None:  # (the chain of a trace-row run; ``write`` uses it too)
-            self.chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain)
+            self.chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
+                                                                                common_mode=common_mode)
             self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
         self._trace_kwargs = dict(trace_kwargs)
         super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)
@@ -231,7 +234,10 @@ class TraceWriter(_RollingWriter):
     readout_pads (the pad ids of the readout set), in hit mode the files are those of a writer without them.
     ``gain`` (a ``detector.traces.GainSettings``, default None = off) is the micromegas gain of the traces, keyed like
     the noise; every file of a writer with a gain records the attributes gain_rel_variance and gain_stream, and the
-    dataset pad_gain when a gain map is given."""
+    dataset pad_gain when a gain map is given.  ``common_mode`` (a ``detector.traces.CommonModeSettings``, default None
+    = off) is the common-mode noise of the traces, keyed like the noise; every file of a writer with it records the
+    attributes common_mode_stream, common_mode_sigma (NaN for a custom table) and common_mode_min_level, the dataset
+    common_mode_cdf, and the dataset common_mode_groups when a map is given."""
 
     group = "trace"
 
@@ -239,12 +245,14 @@ class TraceWriter(_RollingWriter):
                  first_run_number: int = 0, npz_fallback: bool = True, response: np.ndarray | None = None,
                  threshold: float | None = None, offset: int = 0, noise_sigma: float = 0.0, noise_table=None,
                  pedestals=None, noise_stream: int = 0, noise_seed: int = 0, readout: str = "hit",
-                 readout_pads=None, gain=None):
+                 readout_pads=None, gain=None, common_mode=None):
         response, threshold, offset = trace_settings(config, response, threshold, offset)  # (this config's defaults in every run)
         noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
-        self.chain = chain = TraceChain(config, response.copy(), threshold, offset, noise, ReadoutSettings(readout, readout_pads), gain)
+        self.chain = chain = TraceChain(config, response.copy(), threshold, offset, noise, ReadoutSettings(readout, readout_pads), gain,
+                                        common_mode=common_mode)
         self.response, self.threshold, self.offset = chain.response, chain.threshold, chain.offset
         self.noise, self.readout, self.gain = chain.noise, chain.readout, chain.gain
+        self.common_mode = chain.common_mode
         self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
         super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)
 
@@ -265,6 +273,13 @@ class TraceWriter(_RollingWriter):
             f.set_attr("gain_stream", self.gain.stream)
             if self.gain.pad_gain is not None:
                 f.create_dataset("pad_gain", self.gain.pad_gain)
+        if self.common_mode is not None and self.common_mode.on:
+            f.set_attr("common_mode_stream", self.common_mode.stream)
+            f.set_attr("common_mode_sigma", self.common_mode.sigma)
+            f.set_attr("common_mode_min_level", self.common_mode.min_level)
+            f.create_dataset("common_mode_cdf", self.common_mode.cdf)
+            if self.common_mode.groups is not None:
+                f.create_dataset("common_mode_groups", self.common_mode.groups)
         return f
 
     def noise_kwargs(self) -> dict:

@@ -14,8 +14,9 @@ import numpy as np
 from . import _abi, nuclear_map
 from .detector.luts import build_det_desc, build_layout, species_for
 from .detector.simulator import default_indices, deliver_events, fired_events, plan_delivery, selected_events
-from .detector.traces import (BaselineSettings, GainSettings, PeakSettings, TriggerSettings, configure_baseline,
-                              configure_gain, configure_peaks, configure_traces, configure_trigger, trigger_result)
+from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings, PeakSettings, TriggerSettings,
+                              configure_baseline, configure_common_mode, configure_gain, configure_peaks, configure_traces,
+                              configure_trigger, trigger_result)
 from .outputs import RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -180,6 +181,16 @@ class Engine:
         off (the default).  The clouds of ``run`` and the rows of ``run_spyral`` never change."""
         configure_gain(self.ctx, _settings(GainSettings, gain, parameters))
 
+    # ---------------------------------------------------------------- common-mode noise of the pad traces
+    def configure_common_mode(self, common_mode=None, **parameters) -> None:
+        """The common-mode noise of the traces (include/attpc_engine.h): a ``detector.traces.CommonModeSettings`` or its
+        keywords (sigma or table, groups, stream) turn it on -- every pad with a group then gets its group's draw of
+        every sample on top of its own noise in ``run_traces``, ``run_trace_rows`` and ``run_trigger``, keyed on the
+        run's seed and the global event ids --, neither turns it off (the default).  It does not need
+        ``configure_traces`` to have set a pad noise.  The clouds of ``run`` and the rows of ``run_spyral`` never
+        change."""
+        configure_common_mode(self.ctx, _settings(CommonModeSettings, common_mode, parameters))
+
     # ---------------------------------------------------------------- multiplicity trigger on the pad traces
     def configure_trigger(self, trigger=None, **parameters) -> None:
         """The multiplicity trigger of the traces (include/attpc_engine.h): a ``detector.traces.TriggerSettings`` or its
@@ -328,7 +339,7 @@ def _settings(cls, given, parameters: dict, what: str = "keywords"):
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
               batch_size: int = 65536, context: _abi.Context | None = None, selection=None, trigger=None,
-              gain=None) -> None:
+              gain=None, common_mode=None) -> None:
     """run_kinematics_pipeline + run_simulation + SpyralWriter without the kinematics file and with
     the response / threshold / row conversion / z-sort done on the GPU: per event with a non-empty
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
@@ -338,12 +349,12 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     gets the peaks of the event's pad traces as its rows (``Engine.run_trace_rows``).  A writer that offers
     ``write_traces`` (TraceWriter) gets ``write_traces(pads, samples, labels, event_number)`` per such event instead,
     the traces made on the device (``Engine.run_traces``) with the writer's own trace settings.  ``selection``
-    (``Engine.run_selected``; rows or plain clouds), ``trigger`` and ``gain``: as ``run_simulation`` takes them, with
+    (``Engine.run_selected``; rows or plain clouds), ``trigger``, ``gain`` and ``common_mode``: as ``run_simulation`` takes them, with
     the same rules about the kinds of writer (``detector.simulator.plan_delivery``); event numbers stay the global
     ones, the file roll-over counts written events."""
     engine = Engine(pipeline, config, indices, context=context)
     seed = pipeline.seed if seed is None else int(seed)
-    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, plain_clouds=False)
+    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, plain_clouds=False, common_mode=common_mode)
     if selection is not None:
         engine.configure_selection(selection)
         if kind == "rows":

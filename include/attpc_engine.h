@@ -804,6 +804,70 @@ ATTPC_API int32_t attpc_trace_configure_gain(attpc_ctx* ctx, const attpc_trace_g
 ATTPC_API int32_t attpc_gain_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events,
                                   const int64_t* offsets, const double* points, double* gained);
 
+/* ---- common-mode noise of the traces (opt-in: off by default, and with it off every output of every entry point is
+ * bit for bit what it is without this section and no buffer of the stage is allocated) ----
+ * The noise above is independent from pad to pad.  On the GET electronics a share of the noise is coherent: every
+ * channel of a chip or board moves together.  The stage adds one further draw per (event, group, sample) to every pad of
+ * the group; the pad -> group map is the caller's (the project holds no hardware map).  The reference stops at point
+ * clouds and has no counterpart; tests/common_mode_reference.py restates the stage in numpy.
+ * Notation as in the noise contract (s_p, ped_p, n_p, thr, e, seed).
+ * Settings (attpc_trace_common_desc):
+ *   - groups [ATTPC_NUM_PADS] uint8: a value g < 255 is the pad's group, 255 means the pad has no common-mode term;
+ *     NULL puts every pad in group 0.  n_groups = 1 + max g over the pads with g < 255 (a map of 255 alone: the stage
+ *     is off).
+ *   - a noise table of its own -- cdf [n_levels - 1] u32, n_levels, min_level -- under the rules of
+ *     attpc_trace_noise_desc: at most ATTPC_MAX_NOISE_LEVELS levels, |min_level| <= 4095, a non-decreasing cdf;
+ *     n_levels = 0 turns the stage off.
+ *   - stream < 2^29 draws another realisation on the same physics.
+ * Draw of sample j of group g in event e:
+ *       out = Philox4x32-10(counter = (e[31:0], e[63:32], g * 128 + 2 * (j mod 64) + (j div 256), 0x20000000 | stream),
+ *                           key = (seed[31:0], seed[63:32])),   u = out[(j div 64) mod 4]
+ *       c_g[j] = min_level + #{k : cdf[k] <= u}
+ *     the pad noise's layout with g in place of p.  The domain 0x20000000 | stream is disjoint from every other draw's
+ *     (0, 1 + row, 0x200 + entry -- all below 2^19 --, the gain's 0x40000000 | stream, the noise's 0x80000000 | stream,
+ *     and the jitter generators).
+ * Sample of a pad with group g != 255:
+ *       trace_p[j] = min(max(s_p[j] + ped_p + n_p[j] + c_g[j], 0), 4095)
+ *     A pad of group 255 keeps the formula of the noise contract.  n_p = 0 and ped_p = 0 when no pad noise is configured:
+ *     the stage does not need attpc_trace_configure_noise.  A row is kept iff max_j (trace_p[j] - ped_p) > thr, as before,
+ *     in hit mode and for every candidate of ATTPC_READOUT_PARTIAL; ATTPC_READOUT_FULL keeps every pad of S.  Everything
+ *     is integer arithmetic, and c_g[j] is a pure function of (seed, global event id, group, sample): chunking, GPU count
+ *     and what shares a launch play no part.
+ * Unchanged: labels, row order, offsets, the definitions of sample_checksum and pad_checksum (over the samples with
+ *     the term), event_points, attpc_run_stats, every cloud output and the cloud-based Spyral rows.  The trace rows, the
+ *     Fourier baseline and the trigger see the stage through the traces.
+ * Decision rule for a noise-only pad of PARTIAL with group g != 255 (a consequence of the above, s_p = 0):
+ *   - 4095 - ped_p <= thr: the pad is never kept;
+ *   - -ped_p > thr: the pad is always kept (its samples never go below 0);
+ *   - otherwise the pad is kept iff some j has n_p[j] + c_g[j] > thr (the clamps cannot change the verdict then:
+ *     thr >= -ped_p and thr < 4095 - ped_p).
+ *   The one-compare cutoff of the readout contract holds for pads of group 255 only.  No noise-only pad at all is kept,
+ *   and the scan is skipped, iff thr >= 0, the pad table alone never crosses (c > n_levels - 1 there) and the largest
+ *   pad level plus the largest common-mode level is <= thr (0 for the pad level without a pad table).
+ * Device storage: 1 KiB per (event, group) of a chunk, int16 in the trace kernels' lane order (lane l of a wave holds
+ * samples l + 64 s, s = 0 .. 7, as 16 contiguous bytes), in a grow-only buffer of the chunk's assembly set, allocated
+ * only while the stage is on. */
+typedef struct attpc_trace_common_desc {
+  const uint8_t* groups;     /* [ATTPC_NUM_PADS], 255 = no common-mode term; NULL = every pad in group 0 */
+  const uint32_t* cdf;       /* [n_levels - 1] */
+  int32_t n_levels;          /* 0 = the stage off */
+  int32_t min_level;
+  uint32_t stream;           /* < 2^29 */
+  int32_t reserved;
+} attpc_trace_common_desc;
+
+/* desc == NULL turns the stage off (the default); so do n_levels == 0 and a map of 255 alone.  Independent of the other
+ * attpc_trace_configure_* calls: no call resets another.  ATTPC_E_INVALID for a decreasing cdf, more than
+ * ATTPC_MAX_NOISE_LEVELS levels, |min_level| > 4095, a table of several levels without a cdf, or stream >= 2^29.  With
+ * the stage on it acts wherever the pad noise does: attpc_sim_run_traces, attpc_det_run_traces, attpc_traces_at,
+ * attpc_traces and the trace-row entry points. */
+ATTPC_API int32_t attpc_trace_configure_common_mode(attpc_ctx* ctx, const attpc_trace_common_desc* desc);
+/* The stage alone, through the same kernel: out [n_events][n_groups][512] int16 in sample order, c_g[j] of the global
+ * events first_event .. first_event + n_events - 1.  ATTPC_E_NOTCONFIGURED with the stage off.  The id-range rules at
+ * the top apply. */
+ATTPC_API int32_t attpc_common_mode_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events,
+                                         int16_t* out);
+
 /* ---- event and track summaries of a device-resident run (opt-in: without a call of the entry points below every
  * output of every other entry point is what it is without this section) ----
  * A summary run is a device-resident run (attpc_sim_run with out == NULL: same chunks, no event-ordered copy of the

@@ -4,10 +4,12 @@ events/s and GB/s into page-locked host arrays (pads, 1 KiB of samples and the l
 one JSON line per workload with kept trace rows and bytes per event.  ``--noise-sigma S`` adds S ADC counts of
 Gaussian electronic noise, ``--pedestal P`` a pedestal of P counts on every pad (both off by default).
 ``--readout partial|full`` reads out the noise-only pads of every pad not in BEAM_PADS as well (default hit),
-``--threshold T`` sets the ADC threshold (default the workload's).
+``--threshold T`` sets the ADC threshold (default the workload's).  ``--common-sigma C`` adds C counts of common-mode
+noise (off by default) over ``--common-groups G`` groups of consecutive pads (default 40).
 
     python tools/trace_rate.py [--events N] [--deliver-events M] [--reps K] [--workloads o16aa,be10dp]
                                [--noise-sigma S] [--pedestal P] [--readout hit|partial|full] [--threshold T]
+                               [--common-sigma C] [--common-groups G]
 """
 from __future__ import annotations
 
@@ -31,7 +33,11 @@ def main() -> None:
     ap.add_argument("--pedestal", type=int, default=None, help="pedestal of every pad, ADC counts (default none)")
     ap.add_argument("--readout", default="hit", choices=["hit", "partial", "full"], help="readout of noise-only pads")
     ap.add_argument("--threshold", type=float, default=None, help="ADC threshold (default the workload's)")
+    ap.add_argument("--common-sigma", type=float, default=0.0, help="Gaussian common-mode noise, ADC counts (0 = off)")
+    ap.add_argument("--common-groups", type=int, default=40, help="groups of consecutive pads that share it (1 .. 255)")
     args = ap.parse_args()
+    if not 1 <= args.common_groups <= 255:
+        ap.error("--common-groups must lie in 1 .. 255")
 
     import numpy as np
 
@@ -48,6 +54,11 @@ def main() -> None:
         eng = Engine(pipeline, config, indices, context=ctx)
         eng.configure_traces(config, threshold=args.threshold, noise_sigma=args.noise_sigma, pedestals=args.pedestal,
                              readout=args.readout)
+        if args.common_sigma > 0.0:
+            from attpc_engine_amd.detector.traces import CommonModeSettings
+
+            groups = (np.arange(_abi.NUM_PADS) * args.common_groups // _abi.NUM_PADS).astype(np.uint8)
+            eng.configure_common_mode(CommonModeSettings(sigma=args.common_sigma, groups=groups))
         lib, seed = ctx.lib, 1
 
         def resident(first):
@@ -88,6 +99,7 @@ def main() -> None:
         print(json.dumps({
             "workload": name, "noise_sigma": args.noise_sigma, "pedestal": args.pedestal, "readout": args.readout,
             "threshold": float(config.elec_params.adc_threshold if args.threshold is None else args.threshold),
+            "common_sigma": args.common_sigma, "common_groups": args.common_groups if args.common_sigma > 0.0 else 0,
             "resident_events": args.events, "resident_events_per_s": args.events / t_res,
             "resident_s": times, "trace_rows_per_event": rows_per_event,
             "bytes_written_per_event": rows_per_event * row_bytes,
