@@ -91,14 +91,18 @@ __device__ __forceinline__ void rng_pair(uint64_t seed, uint64_t event, uint32_t
 __host__ __device__ __forceinline__ uint32_t jitter_key_word(uint32_t seed_lo, uint32_t seed_hi) {
   return seed_lo ^ ((seed_hi << 13) | (seed_hi >> 19)) ^ DOMAIN_JITTER;
 }
-// (`k` = jitter_key_word(seed): a per-launch constant the flush loop keeps in one scalar register)
+// (`k` = jitter_key_word(seed): a per-launch constant the flush loop keeps in one scalar register.  XOR3: the round's
+//  hi ^ k ^ c1 as one three-input v_bitop3_b32 where the compiler pairs two v_xor_b32 -- the scatter kernel's flush,
+//  which runs it once per cloud point; the same value bit for bit)
+template <bool XOR3 = false>
 __device__ __forceinline__ double jitter_uniform_k(uint32_t k, uint32_t ev_lo, uint32_t ev_hi, uint32_t key) {
   uint32_t c0 = ev_lo, c1 = (ev_hi << 24) | key;
 #pragma unroll
   for (int r = 0; r < 7; ++r) {
     uint32_t hi, lo;
     mul_hi_lo(c0, 0xD256D193u, hi, lo);
-    c0 = hi ^ k ^ c1;
+    if constexpr (XOR3) c0 = __builtin_amdgcn_bitop3_b32(hi, k, c1, 0x96);
+    else c0 = hi ^ k ^ c1;
     c1 = lo;
     k += 0x9E3779B9u;
   }

@@ -518,9 +518,25 @@ __device__ __forceinline__ bool stream_insert(ScatterShared& sh, const uint2* __
 // all instructions the kernel issued.  Here a trip is 40 vector + ~35 scalar instructions and 4 branches: `have` and
 // every condition are lane masks in scalar registers, the conditional LDS operations run under those masks, and the
 // per-lane probe count is replaced by a trip budget of the call (a table too full to take a run ends the window either
-// way).  Same table protocol as the C++ version: bucket read, ds_cmpst claim of the first free slot, ds_max label,
+// way).  The budget is counted only on the trips on which some lane meets a full bucket of other keys and moves on to
+// the next one -- the block most trips skip.  The loop still ends: on every other trip each lane with a run either
+// finishes it (at most the queue's items plus the 64 carried runs do) or loses a claim, and a claim is lost only to
+// another key that filled the slot between this trip's bucket read and its ds_cmpst.  Slots are never freed while
+// inserts run, so the fills are at most HASH_CAP per window, each lost claim belongs to a fill of its own trip's
+// interval, and after at most four of them at one bucket that bucket is full and the lane is on the counted path:
+// trips <= items + 64 + budget + HASH_CAP.  (The C++ version counts its per-lane probes on the same occasion only.)
+// Same table protocol as the C++ version: bucket read, ds_cmpst claim of the first free slot, ds_max label,
 // ds_add_u64 charge, a lost claim looks at the same bucket again.  Registers are named explicitly (the 128-bit bucket
 // and the {q, 0} pair of the 64-bit add need consecutive, even-aligned registers); the operands bind them.
+// (the u32 build reads a queue item {key | label, charge} with one 8-byte read into v[112:113]; the u64 build needs the
+//  charge as the low word of an even-aligned {q, 0} pair for its 64-bit add and keeps it in v[114:115])
+#if ATTPC_SC_WIDE_CHARGE
+#define SC_R_BA "v113"
+#define SC_R_Q "v114"
+#else
+#define SC_R_BA "v114"
+#define SC_R_Q "v113"
+#endif
 struct InsertCarry {
   uint32_t want, q, ba;     // per lane: key | label, charge, byte offset of the bucket inside keys[]
   uint32_t danger;          // per lane: OR of the old sums the adds returned (bit 31: see ADD_LIMIT)
@@ -569,21 +585,23 @@ __device__ __forceinline__ bool stream_insert(ScatterShared& sh, const uint2* __
       "s_or_b64 s[68:69], s[68:69], s[74:75]\n"
       "s_mov_b64 exec, s[74:75]\n"
       "v_lshl_add_u32 v120, v120, 3, v111\n"
+#if ATTPC_SC_WIDE_CHARGE
       "ds_read_b32 v112, v120\n"                // key | label
-      "ds_read_b32 v114, v120 offset:4\n"       // charge
+      "ds_read_b32 v114, v120 offset:4\n"       // charge (the low word of the {q, 0} pair)
       "s_waitcnt lgkmcnt(1)\n"
+#else
+      "ds_read_b64 v[112:113], v120\n"          // the 8-byte queue item in one read: key | label, charge
+      "s_waitcnt lgkmcnt(0)\n"
+#endif
       "v_and_b32 v121, 0xffffff, v112\n"
-      "v_mul_lo_u32 v113, v121, v127\n"
-      "v_mul_hi_u32 v113, v113, s96\n"          // bucket = (hash * buckets) >> 32
-      "v_lshlrev_b32 v113, 4, v113\n"           // * 16 bytes
-      "s_mov_b64 exec, s[70:71]\n"
-      "2:\n"
+      "v_mul_lo_u32 " SC_R_BA ", v121, v127\n"
+      "v_mul_hi_u32 " SC_R_BA ", " SC_R_BA ", s96\n"  // bucket = (hash * buckets) >> 32
+      "v_lshlrev_b32 " SC_R_BA ", 4, " SC_R_BA "\n"   // * 16 bytes
+      "2:\n"                                    // (exec is set below or at 9: nothing in between reads it)
       "s_cmp_eq_u64 s[68:69], 0\n"
       "s_cbranch_scc1 9f\n"
-      "s_sub_u32 s94, s94, 1\n"
-      "s_cbranch_scc1 8f\n"                     // out of trips: the table is too full for this window
       "s_mov_b64 exec, s[68:69]\n"
-      "ds_read_b128 v[116:119], v113 offset:%[keys]\n"
+      "ds_read_b128 v[116:119], " SC_R_BA " offset:%[keys]\n"
       "s_waitcnt lgkmcnt(0)\n"
       "v_and_b32 v120, 0xffffff, v116\n"
       "v_cmp_eq_u32 s[76:77], v120, v121\n"
@@ -610,7 +628,7 @@ __device__ __forceinline__ bool stream_insert(ScatterShared& sh, const uint2* __
       "s_or_b64 s[80:81], s[80:81], vcc\n"
       "s_or_b64 s[84:85], s[84:85], s[80:81]\n"      // any slot free
       "v_cndmask_b32 v122, v123, v122, s[82:83]\n"
-      "v_add_u32 v122, v113, v122\n"                 // byte offset of the slot inside keys[]
+      "v_add_u32 v122, " SC_R_BA ", v122\n"                 // byte offset of the slot inside keys[]
       "s_andn2_b64 s[74:75], s[84:85], s[82:83]\n"   // claim: key not there, a slot free
       "s_mov_b64 exec, s[74:75]\n"
       "ds_cmpst_rtn_b32 v125, v122, v126, v112 offset:%[keys]\n"
@@ -632,17 +650,20 @@ __device__ __forceinline__ bool stream_insert(ScatterShared& sh, const uint2* __
       "ds_add_u64 v120, v[114:115] offset:%[chg]\n"
 #else
       "v_or_b32 %[danger], %[danger], v124\n"       // (what these lanes' previous add returned: long since arrived)
-      "ds_add_rtn_u32 v124, v122, v114 offset:%[chg]\n"  // the slot's u32 sum; the old value comes back (ADD_LIMIT)
+      "ds_add_rtn_u32 v124, v122, " SC_R_Q " offset:%[chg]\n"  // the slot's u32 sum; the old value comes back (ADD_LIMIT)
 #endif
       "s_or_b64 s[76:77], s[82:83], s[84:85]\n"
       "s_andn2_b64 exec, s[68:69], s[76:77]\n"       // full bucket of other keys: on to the next one
+      "s_andn2_b64 s[68:69], s[68:69], s[90:91]\n"   // a lost claim looks at the same bucket again (the done lanes
+                                                     //  found or claimed a slot, so none of them is in exec here)
       "s_cbranch_execz 4f\n"                        // (rare at half load: most trips skip it)
-      "v_add_u32 v113, 16, v113\n"
-      "v_cmp_le_u32 vcc, %[nb16], v113\n"
-      "v_cndmask_b32 v113, v113, 0, vcc\n"          // ... around the end of the table
+      "s_sub_u32 s94, s94, 1\n"                     // the trip budget counts only the trips on which a lane moves on
+      "s_cbranch_scc1 8f\n"                         // out of them: the table is too full for this window
+      "v_add_u32 " SC_R_BA ", 16, " SC_R_BA "\n"
+      "v_cmp_le_u32 vcc, %[nb16], " SC_R_BA "\n"
+      "v_cndmask_b32 " SC_R_BA ", " SC_R_BA ", 0, vcc\n"  // ... around the end of the table
       "4:\n"
       "s_mov_b64 exec, s[70:71]\n"
-      "s_andn2_b64 s[68:69], s[68:69], s[90:91]\n"   // a lost claim looks at the same bucket again
       "s_branch 1b\n"
       "3:\n"                                         // the queue is used up
       "s_cmp_eq_u32 s98, 0\n"
@@ -657,7 +678,7 @@ __device__ __forceinline__ bool stream_insert(ScatterShared& sh, const uint2* __
 #if !ATTPC_SC_WIDE_CHARGE
       "v_or_b32 %[danger], %[danger], v124\n"       // what the last adds returned
 #endif
-      : "+{v112}"(c.want), "+{v113}"(c.ba), "+{v114}"(c.q), "+{s[68:69]}"(c.have), "+{s95}"(claimed), "={s99}"(fail), "={s94}"(budget_left),
+      : "+{v112}"(c.want), "+{" SC_R_BA "}"(c.ba), "+{" SC_R_Q "}"(c.q), "+{s[68:69]}"(c.have), "+{s95}"(claimed), "={s99}"(fail), "={s94}"(budget_left),
         [danger] "+v"(c.danger)
       : "{v111}"(qbase), "{s93}"(__builtin_amdgcn_readfirstlane(n_q)), "{s98}"((uint32_t)(drain ? 1u : 0u)),
         [nb] "n"(N_BUCKETS), [nb16] "n"(N_BUCKETS * 16),
@@ -665,7 +686,9 @@ __device__ __forceinline__ bool stream_insert(ScatterShared& sh, const uint2* __
       : "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "s70", "s71",
         "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87",
         "s88", "s89", "s90", "s91", "s92", "s96", "s97", "vcc", "scc", "memory");
-  trips += ((uint32_t)n_q >> 4) + 64u - (fail ? 0u : budget_left);  // diagnostic builds only (dead code otherwise)
+  // diagnostic builds only (dead code otherwise); with this loop the count is of the trips on which a lane moved on to
+  // the next bucket, the ones the budget counts -- all trips are counted by the ATTPC_SC_CXX_INSERT build
+  trips += ((uint32_t)n_q >> 4) + 64u - (fail ? 0u : budget_left);
   return fail == 0u;
 }
 #endif
@@ -835,6 +858,23 @@ __device__ __forceinline__ int fresh_tid() {
   asm volatile("" : "+v"(t));
   return t;
 }
+
+// pointers into global memory built from integers (through a plain pointer they would be generic and the stores flat)
+typedef __attribute__((address_space(1))) char global_char;
+typedef __attribute__((address_space(1))) double global_double;
+typedef __attribute__((address_space(1))) int64_t global_int64;
+
+// A member of the kernel's argument read from the kernel-argument segment where it is used (one s_load), for values
+// needed once per window: as ordinary uses of `a` they are loaded at the top of the kernel, held in scalar registers
+// across all of it and, beyond the 102 there are, spilled to vector lanes and read back one v_readlane each.  The
+// segment's address goes through an opaque asm, or the compiler merges this load with its own at the top.
+typedef __attribute__((address_space(4))) const char constant_char;
+__device__ __forceinline__ constant_char* kernarg_segment_here() {
+  constant_char* p = (constant_char*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+#define SCATTER_ARG_AT(segment, type, member) (*(__attribute__((address_space(4))) const type*)((segment) + offsetof(ScatterArgs, member)))
 
 // MC: the Monte-Carlo diffusion extension (its own instantiation, so that the default kernel keeps its
 // register budget).
@@ -1931,6 +1971,8 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
           sh.base = base;
           sh.n_keys = 0u;
           sh.ev_rows += n_rows;
+          // the event's share of the window's key checksum, once (mod 2^64 the same sum as row by row)
+          if constexpr (!MC) my_keys += (unsigned long long)n_rows * (event << 24);
           PHASE_MARK(17);  // segment written
         }
         if (tid < 64) {  // wave 0 chooses the next window; the barrier after the row stores publishes it
@@ -1950,36 +1992,97 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
         PHASE_MARK(6);
         if (tid == 0 && sh.wg_cursor != n_rows) atomicAdd(&a.out.ctrl[CTRL_MISMATCH], 1ull);  // self-check, never seen
         const unsigned long long base = sh.base;
-        // per-thread row pointers and the event id in VECTOR registers: as wave-uniform values they sat in
-        // scalar registers spilled to vector lanes, read back with one VALU instruction each per row
-        double* prow = a.out.points + (base + (unsigned long long)tid) * 3ull;
-        int64_t* plab = a.out.labels + (base + (unsigned long long)tid);
-        uint32_t ev_lo = (uint32_t)event, ev_hi = (uint32_t)(event >> 32);
-        asm volatile("" : "+v"(ev_lo), "+v"(ev_hi));
-        const uint32_t jitter_word =
-            (uint32_t)__builtin_amdgcn_readfirstlane((int)jitter_key_word((uint32_t)a.seed, (uint32_t)(a.seed >> 32)));
-        for (unsigned int r = tid; r < n_rows; r += SC_THREADS, prow += SC_THREADS * 3, plab += SC_THREADS) {
-          const uint32_t slot = reinterpret_cast<const unsigned short*>(&sh.queue[0][0])[r];
-          const uint32_t word = sh.keys[slot];
-          const unsigned long long q = sh.chg[slot];
-          sh.keys[slot] = EMPTY;
-          sh.chg[slot] = (charge_t)0;
-          const uint32_t key = word & KEY_MASK;
-          const int pad = (int)(key & 0x3fffu), tb = (int)(key >> 14);
-          my_charge += q;
-          my_keys += (((unsigned long long)ev_hi << 32 | ev_lo) << 24) + (unsigned long long)key;
-          if (base != ~0ull) {
-            // The key word goes through an opaque asm per row: the Philox round keys are then scalar adds inside the
-            // loop instead of scalar registers held (and, at the limit of 102, spilled to vector lanes and read back
-            // with a VALU instruction each) across the whole kernel
-            uint32_t jkey = jitter_word;
-            asm volatile("" : "+s"(jkey));
-            const double ua = jitter_uniform_k(jkey, ev_lo, ev_hi, key);  // simulator.py:108
-            prow[0] = (double)pad;
-            prow[1] = (double)tb + ua;
-            prow[2] = (double)q;
-            *plab = (int64_t)sh.label_of[word >> 24];  // from LDS: a global load here would
-                                                                    // make every store wait (one vmcnt)
+        if constexpr (MC) {
+          // (the Monte-Carlo instantiation keeps the loop as it was: with the one below its big and wide builds spill
+          //  more scalars than before -- 147 -> 152 and 106 -> 146 static spills -- and it is not where the time goes)
+          // per-thread row pointers and the event id in VECTOR registers: as wave-uniform values they sat in
+          // scalar registers spilled to vector lanes, read back with one VALU instruction each per row
+          double* prow = a.out.points + (base + (unsigned long long)tid) * 3ull;
+          int64_t* plab = a.out.labels + (base + (unsigned long long)tid);
+          uint32_t ev_lo = (uint32_t)event, ev_hi = (uint32_t)(event >> 32);
+          asm volatile("" : "+v"(ev_lo), "+v"(ev_hi));
+          const uint32_t jitter_word =
+              (uint32_t)__builtin_amdgcn_readfirstlane((int)jitter_key_word((uint32_t)a.seed, (uint32_t)(a.seed >> 32)));
+          for (unsigned int r = tid; r < n_rows; r += SC_THREADS, prow += SC_THREADS * 3, plab += SC_THREADS) {
+            const uint32_t slot = reinterpret_cast<const unsigned short*>(&sh.queue[0][0])[r];
+            const uint32_t word = sh.keys[slot];
+            const unsigned long long q = sh.chg[slot];
+            sh.keys[slot] = EMPTY;
+            sh.chg[slot] = (charge_t)0;
+            const uint32_t key = word & KEY_MASK;
+            const int pad = (int)(key & 0x3fffu), tb = (int)(key >> 14);
+            my_charge += q;
+            my_keys += (((unsigned long long)ev_hi << 32 | ev_lo) << 24) + (unsigned long long)key;
+            if (base != ~0ull) {
+              // The key word goes through an opaque asm per row: the Philox round keys are then scalar adds inside the
+              // loop instead of scalar registers held (and, at the limit of 102, spilled to vector lanes and read back
+              // with a VALU instruction each) across the whole kernel
+              uint32_t jkey = jitter_word;
+              asm volatile("" : "+s"(jkey));
+              const double ua = jitter_uniform_k<true>(jkey, ev_lo, ev_hi, key);  // simulator.py:108
+              prow[0] = (double)pad;
+              prow[1] = (double)tb + ua;
+              prow[2] = (double)q;
+              *plab = (int64_t)sh.label_of[word >> 24];  // from LDS: a global load here would
+                                                                      // make every store wait (one vmcnt)
+            }
+          }
+        } else {
+          // The rows of a window are addressed as a wave-uniform 64-bit base (scalar registers; a chunk's rows pass
+          // 4 GiB as a matter of course) plus a 32-bit byte offset per lane, which advances with one 32-bit add per
+          // stream; the event id stays in VECTOR registers (as wave-uniform values they sat in scalar registers
+          // spilled to vector lanes, read back with one VALU instruction each per row).  The loop adds only the key
+          // (24 bits) to the key checksum: the event's share, rows x (event << 24), was added by thread 0 above.
+          static_assert((unsigned long long)HASH_CAP * 3ull * sizeof(double) < (1ull << 31), "a window's rows within the 32-bit lane offset");
+          if (base != ~0ull) {  // workgroup uniform: decided once per window, not per row
+            constant_char* const args = kernarg_segment_here();
+            const unsigned long long seed = SCATTER_ARG_AT(args, unsigned long long, seed);
+            const unsigned long long pbytes = SCATTER_ARG_AT(args, unsigned long long, out.points) + base * 24ull;
+            const unsigned long long lbytes = SCATTER_ARG_AT(args, unsigned long long, out.labels) + base * 8ull;
+            global_char* const prow_base = (global_char*)(uintptr_t)(
+                (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pbytes) |
+                ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pbytes >> 32)) << 32));
+            global_char* const plab_base = (global_char*)(uintptr_t)(
+                (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lbytes) |
+                ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lbytes >> 32)) << 32));
+            uint32_t prow_off = (uint32_t)tid * 24u, plab_off = (uint32_t)tid * 8u;
+            uint32_t ev_lo = (uint32_t)event, ev_hi = (uint32_t)(event >> 32);
+            asm volatile("" : "+v"(ev_lo), "+v"(ev_hi));
+            const uint32_t jitter_word =
+                (uint32_t)__builtin_amdgcn_readfirstlane((int)jitter_key_word((uint32_t)seed, (uint32_t)(seed >> 32)));
+            for (unsigned int r = tid; r < n_rows; r += SC_THREADS, prow_off += SC_THREADS * 24u, plab_off += SC_THREADS * 8u) {
+              const uint32_t slot = reinterpret_cast<const unsigned short*>(&sh.queue[0][0])[r];
+              const uint32_t word = sh.keys[slot];
+              const unsigned long long q = sh.chg[slot];
+              sh.keys[slot] = EMPTY;
+              sh.chg[slot] = (charge_t)0;
+              const uint32_t key = word & KEY_MASK;
+              const int pad = (int)(key & 0x3fffu), tb = (int)(key >> 14);
+              my_charge += q;
+              my_keys += (unsigned long long)key;
+              // The key word goes through an opaque asm per row: the Philox round keys are then scalar adds inside the
+              // loop instead of scalar registers held (and, at the limit of 102, spilled to vector lanes and read back
+              // with a VALU instruction each) across the whole kernel
+              uint32_t jkey = jitter_word;
+              asm volatile("" : "+s"(jkey));
+              const double ua = jitter_uniform_k<true>(jkey, ev_lo, ev_hi, key);  // simulator.py:108
+              global_double* const prow = (global_double*)(prow_base + prow_off);
+              prow[0] = (double)pad;
+              prow[1] = (double)tb + ua;
+              prow[2] = (double)q;
+              // from LDS: a global load here would make every store wait (one vmcnt)
+              *(global_int64*)(plab_base + plab_off) = (int64_t)sh.label_of[word >> 24];
+            }
+          } else {  // out of capacity (the host repeats the launch): the table is reset and the checksums go on, no rows
+            for (unsigned int r = tid; r < n_rows; r += SC_THREADS) {
+              const uint32_t slot = reinterpret_cast<const unsigned short*>(&sh.queue[0][0])[r];
+              const uint32_t word = sh.keys[slot];
+              const unsigned long long q = sh.chg[slot];
+              sh.keys[slot] = EMPTY;
+              sh.chg[slot] = (charge_t)0;
+              my_charge += q;
+              my_keys += (unsigned long long)(word & KEY_MASK);
+            }
           }
         }
         // no barrier here: the next window was published before the row stores, and the first barrier of
