@@ -238,6 +238,27 @@ class TraceOut(C.Structure):
     ]
 
 
+class TracePackedOut(C.Structure):
+    _fields_ = [
+        ("capacity", C.c_int64),
+        ("offsets", C.POINTER(C.c_int64)),
+        ("pads", C.POINTER(C.c_int32)),
+        ("row_start", C.POINTER(C.c_int64)),
+        ("bytes", C.POINTER(C.c_uint8)),
+        ("byte_capacity", C.c_int64),
+        ("labels", C.POINTER(C.c_int64)),
+        ("event_points", C.POINTER(C.c_int64)),
+        ("n_rows", C.c_int64),
+        ("n_bytes", C.c_int64),
+        ("sample_checksum", C.c_uint64),
+        ("pad_checksum", C.c_uint64),
+    ]
+
+
+TRACE_PACK_FORMAT = "for64-bitplane-v1"  # ATTPC_TRACE_PACK_FORMAT
+TRACE_PACK_MAX_ROW_BYTES = 784
+
+
 class RunStats(C.Structure):
     _fields_ = [
         ("n_events", C.c_uint64), ("n_points", C.c_uint64), ("n_track_samples", C.c_uint64),
@@ -318,6 +339,8 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_trigger", "attpc_trigger_last", "attpc_trigger_rows",
     "attpc_trace_configure_gain", "attpc_gain_rows",
     "attpc_trace_configure_common_mode", "attpc_common_mode_rows",
+    "attpc_sim_run_traces_packed", "attpc_det_run_traces_packed", "attpc_traces_packed_at", "attpc_trace_pack",
+    "attpc_trace_pack_host", "attpc_trace_unpack",
     "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
     "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
 )
@@ -345,6 +368,10 @@ GAIN_SYMBOLS = ("attpc_trace_configure_gain", "attpc_gain_rows")
 
 # ... and the common-mode noise of the traces after the gain: the same rule.
 COMMON_SYMBOLS = ("attpc_trace_configure_common_mode", "attpc_common_mode_rows")
+
+# ... and the packed pad traces after the common-mode noise: the same rule.
+TRACE_PACK_SYMBOLS = ("attpc_sim_run_traces_packed", "attpc_det_run_traces_packed", "attpc_traces_packed_at",
+                      "attpc_trace_pack", "attpc_trace_pack_host", "attpc_trace_unpack")
 
 _lib = None
 
@@ -485,6 +512,19 @@ def load_library() -> C.CDLL:
     for name, argtypes in common.items():
         if not no_common:
             getattr(lib, name).argtypes = argtypes
+    i16p, i64p, u8p = C.POINTER(C.c_int16), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    trace_pack = {
+        "attpc_sim_run_traces_packed": lib.attpc_sim_run_traces.argtypes[:-2] + [C.POINTER(TracePackedOut), C.POINTER(RunStats)],
+        "attpc_det_run_traces_packed": lib.attpc_det_run_traces.argtypes[:-2] + [C.POINTER(TracePackedOut), C.POINTER(RunStats)],
+        "attpc_traces_packed_at": lib.attpc_traces_at.argtypes[:-1] + [C.POINTER(TracePackedOut)],
+        "attpc_trace_pack": [ctxp, C.c_int64, i16p, i64p, u8p, C.c_int64, i64p],
+        "attpc_trace_pack_host": [C.c_int64, i16p, i64p, u8p, C.c_int64, i64p],
+        "attpc_trace_unpack": [u8p, C.c_int64, i64p, C.c_int64, i16p, C.c_int32],
+    }
+    no_trace_pack = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in TRACE_PACK_SYMBOLS)
+    for name, argtypes in trace_pack.items():
+        if not no_trace_pack:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -508,7 +548,7 @@ def load_library() -> C.CDLL:
         if ((older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS)
                 or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)
                 or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)
-                or (no_common and name in COMMON_SYMBOLS)):
+                or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status

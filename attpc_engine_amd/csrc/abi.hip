@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "tracks_args.hpp"
+#include "trace_pack_host.hpp"
 #include "unpack_host.hpp"
 #include "spyral_integral.hpp"  // (behind the HIP runtime header)
 
@@ -93,6 +94,10 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf tg_records;           // trigger on (trigger.hip): the chunk's records, attpc_trigger_record [events]
   DevBuf tg_row_pass;          // ... with its gate, trace rows: fired of every kept trace row's event, uint8 [traces]
   Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
+  // packed traces (trace_pack.hip): the headers and record sizes of every kept trace row, their scanned byte offsets
+  // (tp_block_*: the scan's scratch) and the records; the chunk's bytes in pinned memory (the host waits on `counted`)
+  DevBuf tp_headers, tp_sizes, tp_row_start, tp_block_sums, tp_block_start, tp_bytes;
+  Pinned<int64_t> h_tp_total;  // [1]
   size_t row_cap = 0;  // rows the row-sized buffers of the set are kept at (grown with headroom: a launch's row
                        // capacity follows the observed rows per event and moves by fractions of a percent)
   Pinned<int64_t> h_start;     // CSR offsets of the chunk (n + 1 entries)
@@ -142,6 +147,7 @@ struct attpc_ctx {
   int opt_track_species_major = 1; // tracks handed out nucleus by nucleus, lightest species first (0: event by event)
   int opt_track_blocks_per_cu = 8; // track_kernel workgroups (256 threads) launched per CU at most
   int opt_serial_tracks = -1;      // -1 automatic (see pick_track_stream), 0 beside the scatter launches, 1 behind them
+  int opt_trace_pack_workgroups = 0;  // workgroups of the trace pack kernels at most; 0: 8 per CU
 
   bool kin_ready = false;
   attpc_kin_desc kin{};            // device pointers inside
@@ -791,6 +797,8 @@ struct RunOut {
   attpc_cloud_out* cloud = nullptr;  // cloud, spyral, trace_rows
   attpc_trace_out* trace = nullptr;  // traces
   int64_t rows = 0;                  // row cursor: rows of the chunks delivered so far
+  attpc_trace_packed_out* tpacked = nullptr;  // traces, packed: `trace` then holds its row arrays and no samples
+  int64_t bytes = 0;                 // ... and their byte cursor: packed bytes of the chunks so far
   bool over = false;                 // ... more than the caller's capacity
   attpc_summary_out* summary = nullptr;  // summary (a resident run: neither cloud nor trace)
   attpc_select_out* select = nullptr;    // a selected run: cloud and summary are views of it (mode cloud or spyral)
@@ -803,6 +811,7 @@ struct RunOut {
   bool bounded() const {
     if (select) return cloud->points && cloud->labels;  // (nothing of the rows is copied otherwise)
     if (mode == OutMode::trace_rows) return cloud->points || cloud->labels;
+    if (tpacked && (tpacked->row_start || tpacked->bytes)) return true;
     return cloud || (trace && (trace->pads || trace->samples || trace->labels));
   }
 };
@@ -1018,6 +1027,76 @@ int32_t copy_traces(attpc_ctx* ctx, AsmSet& as, int64_t total, int64_t base, con
   }
   HIP_TRY(ctx, hipEventRecord(as.copied, ctx->stream_c));
   return ATTPC_OK;
+}
+
+// Packed traces, first half: the size pass over `rows` (> 0) trace rows at `samples` on the device, the scan of the
+// record sizes into as.tp_row_start (relative to the chunk) and the copy of their total to as.h_tp_total, on S;
+// as.counted is recorded behind it.
+int32_t enqueue_trace_pack_size(attpc_ctx* ctx, AsmSet& as, int64_t rows, const int16_t* samples) {
+  int32_t rc;
+  const size_t cap = std::max(as.tr_cap, (size_t)rows);
+  const uint32_t blocks = peak_scan_blocks((uint32_t)rows);
+  if ((rc = ensure(ctx, as.tp_headers, cap * sizeof(uint4)))) return rc;
+  if ((rc = ensure(ctx, as.tp_sizes, cap * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, as.tp_row_start, (cap + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, as.tp_block_sums, (size_t)blocks * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, as.tp_block_start, ((size_t)blocks + 1) * sizeof(int64_t)))) return rc;
+  if ((rc = ensure_pinned(ctx, as.h_tp_total, 1))) return rc;
+  const uint32_t limit = ctx->opt_trace_pack_workgroups > 0 ? (uint32_t)ctx->opt_trace_pack_workgroups : (uint32_t)ctx->n_cus * 8u;
+  launch_trace_pack_size(ctx->stream, trace_pack_workgroups((uint32_t)rows, limit), (uint32_t)rows, samples,
+                         static_cast<uint4*>(as.tp_headers.p), static_cast<uint32_t*>(as.tp_sizes.p));
+  HIP_TRY(ctx, hipGetLastError());
+  launch_peak_scan(ctx->stream, static_cast<const uint32_t*>(as.tp_sizes.p), (uint32_t)rows, static_cast<int64_t*>(as.tp_row_start.p),
+                   static_cast<uint32_t*>(as.tp_block_sums.p), static_cast<int64_t*>(as.tp_block_start.p));
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(as.h_tp_total.p, static_cast<const int64_t*>(as.tp_row_start.p) + rows, sizeof(int64_t),
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipEventRecord(as.counted, ctx->stream));
+  return ATTPC_OK;
+}
+
+// ... second half, once the host knows the chunk's `total` bytes: the records into as.tp_bytes on S; as.tp_row_start
+// then holds the offsets + `base` (the bytes of the call's chunks before this one).
+int32_t enqueue_trace_pack_write(attpc_ctx* ctx, AsmSet& as, int64_t rows, const int16_t* samples, int64_t total, int64_t base) {
+  int32_t rc;
+  if ((size_t)total > as.tp_bytes.bytes && (rc = ensure(ctx, as.tp_bytes, (size_t)total + (size_t)total / 8))) return rc;
+  const uint32_t limit = ctx->opt_trace_pack_workgroups > 0 ? (uint32_t)ctx->opt_trace_pack_workgroups : (uint32_t)ctx->n_cus * 8u;
+  launch_trace_pack_write(ctx->stream, trace_pack_workgroups((uint32_t)rows, limit), (uint32_t)rows, samples,
+                          static_cast<const uint4*>(as.tp_headers.p), static_cast<int64_t*>(as.tp_row_start.p), base,
+                          static_cast<unsigned char*>(as.tp_bytes.p));
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// deliver() of packed traces: the chunk's `total` rows are written (as.traced is recorded behind them, and behind the
+// trigger).  Queue the size pass and the scan on S and wait for the chunk's bytes alone (an event of its own: the one
+// host round trip of the stage, as in deliver_trace_rows -- the bytes size the record buffer, rebase the next chunk's
+// row_start and answer the capacity); then the write pass, and on C the copies of row_start, bytes, pads and labels.
+int32_t deliver_packed_traces(attpc_ctx* ctx, RunOut& o, AsmSet& as, int64_t total, int64_t base, bool fits) {
+  attpc_trace_packed_out* out = o.tpacked;
+  const int16_t* samples = static_cast<const int16_t*>(as.tr_samples.p);
+  const int64_t byte_base = o.bytes;
+  int64_t chunk_bytes = 0;
+  int32_t rc;
+  if (total > 0) {
+    if ((rc = enqueue_trace_pack_size(ctx, as, total, samples))) return rc;
+    HIP_TRY(ctx, hipEventSynchronize(as.counted));
+    chunk_bytes = as.h_tp_total[0];
+    if ((rc = enqueue_trace_pack_write(ctx, as, total, samples, chunk_bytes, byte_base))) return rc;
+    HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
+  }
+  o.bytes = byte_base + chunk_bytes;
+  if (out->bytes && o.bytes > out->byte_capacity) fits = false;
+  if (!fits) o.over = true;
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
+  if (total > 0 && fits) {
+    if (out->row_start)  // (entry `base` is the chunk before's last, or the 0 the entry point wrote)
+      HIP_TRY(ctx, hipMemcpyAsync(out->row_start + base + 1, static_cast<const int64_t*>(as.tp_row_start.p) + 1,
+                                  (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream_c));
+    if (out->bytes)
+      HIP_TRY(ctx, hipMemcpyAsync(out->bytes + byte_base, as.tp_bytes.p, (size_t)chunk_bytes, hipMemcpyDeviceToHost, ctx->stream_c));
+  }
+  return copy_traces(ctx, as, total, base, o.trace, fits);  // pads and labels (no samples: NULL there)
 }
 
 // The flags pack_rows_kernel / launch_spyral_write leave behind the transfer records (of `record` bytes) of `as`.
@@ -1267,6 +1346,7 @@ int32_t deliver(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t firs
   int32_t rc;
   if ((rc = enqueue_trace_write(ctx, as, n, total, seed, first_global))) return rc;
   if (ctx->trigger_on && (rc = enqueue_trigger(ctx, as, n, total, first_local, false))) return rc;
+  if (o.tpacked) return deliver_packed_traces(ctx, o, as, total, base, fits);
   return copy_traces(ctx, as, total, base, o.trace, fits);
 }
 
@@ -1740,12 +1820,16 @@ int32_t read_trace_sums(attpc_ctx* ctx, const RunOut& o) {
   o.trace->n_rows = o.rows;
   o.trace->sample_checksum = sums[0];
   o.trace->pad_checksum = sums[1];
+  if (o.tpacked) o.tpacked->n_bytes = o.bytes;
   return ATTPC_OK;
 }
 
 // The end of a run: its statistics to the caller, then the verdicts on the capacity and on lost charge.
 int32_t run_status(attpc_ctx* ctx, const attpc_run_stats& st, attpc_run_stats* stats, const RunOut& o) {
   if (stats) *stats = st;
+  if (o.over && o.tpacked)
+    return fail(ctx, ATTPC_E_CAPACITY, "packed traces need %lld rows and %lld bytes, capacity %lld rows and %lld bytes",
+                (long long)o.rows, (long long)o.bytes, (long long)o.capacity(), (long long)o.tpacked->byte_capacity);
   if (o.over)
     return fail(ctx, ATTPC_E_CAPACITY, "%s %lld rows, capacity %lld",
                 o.mode == OutMode::traces ? "traces need" : o.mode == OutMode::trace_rows ? "trace rows need" : "cloud needs",
@@ -2049,6 +2133,9 @@ int32_t attpc_set_option(attpc_ctx* ctx, const char* name, int64_t value) {
   } else if (key == "scatter_merge") {
     if (value < -1 || value > 1) return fail(ctx, ATTPC_E_INVALID, "scatter_merge must be -1, 0 or 1");
     ctx->opt_merge = (int)value;
+  } else if (key == "trace_pack_workgroups") {
+    if (value < 0 || value > 65536) return fail(ctx, ATTPC_E_INVALID, "trace_pack_workgroups must be 0..65536");
+    ctx->opt_trace_pack_workgroups = (int)value;
   } else if (key == "chunk_events") {
     return attpc_set_chunk_events(ctx, (int32_t)value);
   } else {
@@ -2528,6 +2615,118 @@ int32_t attpc_traces_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
   if ((rc = host_cloud_run(ctx, seed, first_event, n_events, offsets, points, labels, o))) return rc;
   if ((rc = read_trace_sums(ctx, o))) return rc;
   return run_status(ctx, attpc_run_stats{}, nullptr, o);
+}
+
+// ---- packed pad traces (trace_pack.hip, trace_pack_host.cpp; the contract is in include/attpc_engine.h) ----
+namespace {
+// The row arrays of an attpc_trace_packed_out as the attpc_trace_out the run loop fills (no samples), and the way back.
+struct PackedView {
+  attpc_trace_out t{};
+  explicit PackedView(attpc_trace_packed_out* p) {
+    t.capacity = p->capacity;
+    t.offsets = p->offsets;
+    t.pads = p->pads;
+    t.labels = p->labels;
+    t.event_points = p->event_points;
+    p->n_rows = p->n_bytes = 0;
+    if (p->row_start) p->row_start[0] = 0;
+  }
+  RunOut run(attpc_trace_packed_out* p) {
+    RunOut o{OutMode::traces, nullptr, &t};
+    o.tpacked = p;
+    return o;
+  }
+  int32_t finish(attpc_trace_packed_out* p, int32_t rc) {
+    p->n_rows = t.n_rows;
+    p->sample_checksum = t.sample_checksum;
+    p->pad_checksum = t.pad_checksum;
+    return rc;
+  }
+};
+bool bad_packed_out(const attpc_trace_packed_out* out) { return !out || out->byte_capacity < 0; }
+}  // namespace
+
+int32_t attpc_sim_run_traces_packed(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                    const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
+                                    attpc_trace_packed_out* out, attpc_run_stats* stats) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (bad_packed_out(out)) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_trace_packed_out", __func__);
+  PackedView view(out);
+  return view.finish(out, run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{true},
+                                    RunSink{p4, vertex, kin_status}, view.run(out), stats));
+}
+
+int32_t attpc_det_run_traces_packed(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                    const attpc_event_layout* layout, const double* p4, const double* vertex,
+                                    attpc_trace_packed_out* out, attpc_run_stats* stats) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (bad_packed_out(out)) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_trace_packed_out", __func__);
+  PackedView view(out);
+  return view.finish(out, run_entry(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{},
+                                    view.run(out), stats));
+}
+
+int32_t attpc_traces_packed_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
+                               const double* points, const int64_t* labels, attpc_trace_packed_out* out) {
+  if (!ctx || bad_packed_out(out)) return ATTPC_E_INVALID;
+  PackedView view(out);
+  RunOut o = view.run(out);
+  int32_t rc;
+  if ((rc = host_cloud_run(ctx, seed, first_event, n_events, offsets, points, labels, o))) return rc;
+  if ((rc = read_trace_sums(ctx, o))) return rc;
+  return view.finish(out, run_status(ctx, attpc_run_stats{}, nullptr, o));
+}
+
+int32_t attpc_trace_pack(attpc_ctx* ctx, int64_t n_rows, const int16_t* samples, int64_t* row_start, uint8_t* bytes,
+                         int64_t byte_capacity, int64_t* n_bytes) {
+  if (!ctx || n_rows < 0 || byte_capacity < 0) return ATTPC_E_INVALID;
+  if (n_bytes) *n_bytes = 0;
+  if (row_start) row_start[0] = 0;
+  if (n_rows == 0) return ATTPC_OK;
+  if (!samples) return ATTPC_E_INVALID;
+  for (int64_t i = 0; i < n_rows * ATTPC_NUM_TB; ++i)
+    if (samples[i] < 0 || samples[i] > 4095)
+      return fail(ctx, ATTPC_E_INVALID, "sample %lld of row %lld is %d: 0 .. 4095", (long long)(i % ATTPC_NUM_TB),
+                  (long long)(i / ATTPC_NUM_TB), (int)samples[i]);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = drop_prefetch(ctx))) return rc;
+  if ((rc = sync_all(ctx))) return rc;
+  AsmSet& as = ctx->aset[0];
+  constexpr int64_t CHUNK = 16384;  // rows: 16 MiB of samples on the device
+  const size_t row_bytes = ATTPC_NUM_TB * sizeof(int16_t);
+  if ((rc = ensure(ctx, ctx->scratch[0], (size_t)std::min(n_rows, CHUNK) * row_bytes))) return rc;
+  const int16_t* d_samples = static_cast<const int16_t*>(ctx->scratch[0].p);
+  int64_t total = 0;
+  for (int64_t first = 0; first < n_rows; first += CHUNK) {
+    const int64_t n = std::min(CHUNK, n_rows - first);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, samples + first * ATTPC_NUM_TB, (size_t)n * row_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = enqueue_trace_pack_size(ctx, as, n, d_samples))) return rc;
+    HIP_TRY(ctx, hipEventSynchronize(as.counted));
+    const int64_t chunk_bytes = as.h_tp_total[0];
+    if ((rc = enqueue_trace_pack_write(ctx, as, n, d_samples, chunk_bytes, total))) return rc;
+    if (row_start)
+      HIP_TRY(ctx, hipMemcpyAsync(row_start + first + 1, static_cast<const int64_t*>(as.tp_row_start.p) + 1, (size_t)n * sizeof(int64_t),
+                                  hipMemcpyDeviceToHost, ctx->stream));
+    if (bytes && total + chunk_bytes <= byte_capacity)
+      HIP_TRY(ctx, hipMemcpyAsync(bytes + total, as.tp_bytes.p, (size_t)chunk_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    total += chunk_bytes;
+  }
+  if (n_bytes) *n_bytes = total;
+  if (bytes && total > byte_capacity)
+    return fail(ctx, ATTPC_E_CAPACITY, "packed rows need %lld bytes, capacity %lld", (long long)total, (long long)byte_capacity);
+  return ATTPC_OK;
+}
+
+int32_t attpc_trace_pack_host(int64_t n_rows, const int16_t* samples, int64_t* row_start, uint8_t* bytes, int64_t byte_capacity,
+                              int64_t* n_bytes) {
+  return trace_pack_host(n_rows, samples, row_start, bytes, byte_capacity, n_bytes);
+}
+
+int32_t attpc_trace_unpack(const uint8_t* bytes, int64_t n_bytes, const int64_t* row_start, int64_t n_rows, int16_t* samples,
+                           int32_t n_threads) {
+  return trace_unpack_host(bytes, n_bytes, row_start, n_rows, samples, n_threads);
 }
 
 // ---- micromegas gain of the traces (gain.hip; the contract is in include/attpc_engine.h) ----

@@ -225,6 +225,16 @@ struct TriggerArgs {
 // one workgroup per event, empty events included
 void launch_trigger(hipStream_t s, uint32_t n_events, const TriggerArgs& a);
 
+// packed pad traces (trace_pack.hip; the format "for64-bitplane-v1" is in include/attpc_engine.h).  samples
+// [n_rows][512] as the trace write pass left them, n_rows > 0; `workgroups` = trace_pack_workgroups(n_rows, limit).
+// size pass: headers [n_rows] (the eight u16 headers of every row) and sizes [n_rows] (bytes of its record)
+uint32_t trace_pack_workgroups(uint32_t n_rows, uint32_t limit);
+void launch_trace_pack_size(hipStream_t s, uint32_t workgroups, uint32_t n_rows, const int16_t* samples, uint4* headers,
+                            uint32_t* sizes);
+// write pass: row_start [n_rows + 1] = the exclusive scan of sizes on entry (relative to `bytes`), + base on return
+void launch_trace_pack_write(hipStream_t s, uint32_t workgroups, uint32_t n_rows, const int16_t* samples, const uint4* headers,
+                             int64_t* row_start, int64_t base, unsigned char* bytes);
+
 // event and track summaries of a scattered chunk (summary.hip; attpc_summary_configure, the contract is in
 // include/attpc_engine.h).  The rows are read in place through the launch's segment list.
 struct SummaryArgs {

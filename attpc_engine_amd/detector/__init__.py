@@ -14,11 +14,12 @@ _EXPORTS = {
               "simulate_batch_trace_rows", "clouds_to_trace_rows", "BaselineSettings", "configure_baseline", "remove_baseline",
               "TriggerSettings", "configure_trigger", "traces_to_trigger", "TRIGGER_DTYPE",
               "GainSettings", "configure_gain", "clouds_to_gain", "polya_rel_variance", "normal_quantile_table",
-              "CommonModeSettings", "configure_common_mode", "common_mode_values"),
+              "CommonModeSettings", "configure_common_mode", "common_mode_values",
+              "pack_traces", "pack_traces_host", "unpack_traces", "PackedRows", "TRACE_PACK_FORMAT"),
     _summary: ("SummarySettings", "configure_summary", "simulate_batch_summary", "clouds_to_summary",
                "electrons_above_threshold"),
     _selection: ("Selection", "configure_selection", "simulate_batch_selected", "clouds_to_selection"),
-    _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter"),
+    _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []
 for _module, _names in _EXPORTS.items():

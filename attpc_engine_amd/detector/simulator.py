@@ -16,7 +16,7 @@ from .. import _abi
 from ..outputs import RowArrays, call_with_capacity
 from .luts import build_det_desc, build_layout, species_for
 from .parameters import Config
-from .traces import TraceChain
+from .traces import PackedRows, TraceChain
 from .writer import SimulationWriter
 
 
@@ -155,12 +155,20 @@ def delivery_of(writer, config: Config):
     its rows are the peaks of the pad traces) or "cloud" with ``emit(points, labels, event)`` (the plain ``write`` of
     any SimulationWriter)."""
     if callable(getattr(writer, "write_traces", None)):
+        if writer_packed(writer):  # (pads, PackedRows, labels, event): the records as they crossed PCIe
+            return "traces", lambda pads, rows, labels, event: writer.write_packed_traces(pads, rows.row_start, rows.packed,
+                                                                                           labels, event)
         return "traces", writer.write_traces
     if callable(getattr(writer, "write_rows", None)):
         # (SpyralWriter(peaks=...): the rows are the peaks of the event's pad traces, made on the device)
         kind = "rows" if getattr(writer, "peaks", None) is None else "trace_rows"
         return kind, lambda rows, labels, event: writer.write_rows(rows, labels, event, presorted=True)
     return "cloud", lambda points, labels, event: writer.write(points, labels, config, event)
+
+
+def writer_packed(writer) -> bool:
+    """Does ``writer`` store packed pad traces (TraceWriter(packed=True))?  A run then takes the packed entry points."""
+    return bool(getattr(writer, "packed", False)) and callable(getattr(writer, "write_packed_traces", None))
 
 
 def plan_delivery(writer, config: Config, selection=None, trigger=None, gain=None, plain_clouds: bool = True,
@@ -273,8 +281,12 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
                                           response=getattr(writer, "response", None))
             return selected_events(res, "rows" if kind == "rows" else "points")
         if chain is not None:  # the pad traces, or their peaks as Spyral rows, are made on the device behind the scatter
+            packed = kind == "traces" and writer_packed(writer)
             offsets, *arrays, raw_points, stats = chain.run_batch(
-                kind == "trace_rows", momenta, vertices, proton_numbers, mass_numbers, run_seed, nuclei_to_sim, start)
+                kind == "trace_rows", momenta, vertices, proton_numbers, mass_numbers, run_seed, nuclei_to_sim, start,
+                packed=packed)
+            if packed:  # (pads, row_start, packed, labels) -> the records as one row-indexed array
+                arrays = [arrays[0], PackedRows(arrays[1], arrays[2]), arrays[3]]
             return fired_events(offsets, raw_points, stats.get("trigger"), *arrays)
         if kind == "rows":
             offsets, rows, labels, raw_points, _ = simulate_batch_spyral(

@@ -60,7 +60,7 @@ import statistics
 import numpy as np
 
 from .. import _abi
-from ..outputs import RowArrays, TraceArrays, call_with_capacity  # noqa: F401 (TraceArrays stays importable from here)
+from ..outputs import PackedTraceArrays, RowArrays, TraceArrays, call_with_capacity  # noqa: F401 (TraceArrays stays importable from here)
 from .parameters import Config
 
 
@@ -434,21 +434,29 @@ class TraceChain:
             configure_gain(ctx, self.gain)
 
     def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
-                  ctx: _abi.Context | None = None, capacity_per_event: int | None = None):
+                  ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False):
         """simulate() + this chain on the device for n events: what ``simulate_batch_trace_rows`` (``rows``) or
-        ``simulate_batch_traces`` returns (``capacity_per_event``: None = the default of that entry point)."""
+        ``simulate_batch_traces`` returns (``capacity_per_event``: None = the default of that entry point; ``packed``:
+        the traces as packed records, ``attpc_det_run_traces_packed``)."""
         from .simulator import run_batch
 
         ctx = ctx or _abi.default_context()
+        packed = _packed_flag(packed)
+        if packed and rows:
+            raise ValueError("packed applies to traces, not to trace rows")
 
         def configure(c):
             self.configure(c, rows)
             return 0 if rows else c._trace_readout_rows  # traces in full readout: |S| rows per event
 
-        arrays, stats = run_batch("attpc_det_run_trace_rows" if rows else "attpc_det_run_traces", momenta, vertices,
+        per_event = (2048 if rows else 1024) if capacity_per_event is None else capacity_per_event
+        how = dict(holder=RowArrays, width=8, slack=1024) if rows else {}
+        if packed:
+            how = dict(holder=PackedTraceArrays, byte_capacity=PACKED_BYTES_PER_ROW * max(1024, int(per_event) * len(momenta)))
+        arrays, stats = run_batch("attpc_det_run_trace_rows" if rows else "attpc_det_run_traces_packed" if packed
+                                  else "attpc_det_run_traces", momenta, vertices,
                                   proton_numbers, mass_numbers, self.config, seed, indices, first_event, ctx,
-                                  (2048 if rows else 1024) if capacity_per_event is None else capacity_per_event, configure,
-                                  **(dict(holder=RowArrays, width=8, slack=1024) if rows else {}))
+                                  per_event, configure, **how)
         extra = trigger_result(ctx, len(arrays.offsets) - 1)
         sums = ctx.trace_rows_last() if rows else arrays.sums()
         return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
@@ -483,7 +491,8 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
                           response=None, threshold=None, offset: int = 0, capacity_per_event: int = 1024,
                           noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
                           readout: str = "hit", readout_pads=None, trigger: TriggerSettings | None = None,
-                          gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None):
+                          gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
+                          packed: bool = False):
     """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``; the noise keyed on
     ``seed`` and the global event ids; ``readout`` / ``readout_pads`` as configure_traces) ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
@@ -491,11 +500,13 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     ``pad_checksum`` of the traces, and with ``trigger`` (a ``TriggerSettings``; None = off) its records [n] under
     ``"trigger"``).  ``gain`` (a ``GainSettings``; None = off): the micromegas gain of every cloud row's charge, keyed on
     ``seed`` and the global event ids like the noise.  ``common_mode`` (a ``CommonModeSettings``; None = off): the
-    common-mode noise of every pad with a group, keyed the same way."""
+    common-mode noise of every pad with a group, keyed the same way.  ``packed=True``
+    (``attpc_det_run_traces_packed``): (offsets, pads, row_start [R+1] i64, packed uint8, labels, event_points, stats
+    with ``n_bytes``) -- the rows as packed records, ``unpack_traces`` gives the samples back."""
     chain = TraceChain(config, response, threshold, offset, NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream),
                        ReadoutSettings(readout, readout_pads), gain, trigger=trigger, common_mode=common_mode)
     return chain.run_batch(False, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
-                           capacity_per_event)
+                           capacity_per_event, packed)
 
 
 def _host_cloud(offsets, points, labels, seed, first_event):
@@ -515,23 +526,140 @@ def _host_cloud(offsets, points, labels, seed, first_event):
 
 
 def clouds_to_traces(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,
-                     first_event: int = 0):
+                     first_event: int = 0, packed: bool = False):
     """Pad traces of any host cloud in CSR form (``attpc_traces_at``; ``ctx`` configured with ``configure_traces``):
     offsets [n+1], points [P,3] (pad, time bucket, electrons), labels [P] ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, {n_rows, sample_checksum, pad_checksum}; when
     the ctx holds a trigger (``configure_trigger``) its records [n] too, under ``"trigger"``).
     Event i of the call is the global event ``first_event + i``: its noise is keyed on (seed, first_event + i), and the
-    pad checksum counts events from ``first_event``."""
+    pad checksum counts events from ``first_event``.  ``packed=True`` (``attpc_traces_packed_at``): (offsets, pads,
+    row_start [R+1] i64, packed uint8, labels, sums with ``n_bytes``)."""
     offsets, points, labels, seed, first_event, n = _host_cloud(offsets, points, labels, seed, first_event)
+    packed = _packed_flag(packed)
+    name = "attpc_traces_packed_at" if packed else "attpc_traces_at"
 
     def call(out):
-        return ctx.lib.attpc_traces_at(ctx.handle, seed, first_event, n, _abi.iptr(offsets, _abi.C.c_int64),
-                                       _abi.dptr(points), _abi.iptr(labels, _abi.C.c_int64), out)
+        return getattr(ctx.lib, name)(ctx.handle, seed, first_event, n, _abi.iptr(offsets, _abi.C.c_int64),
+                                      _abi.dptr(points), _abi.iptr(labels, _abi.C.c_int64), out)
 
     rows = int(offsets[-1] - offsets[0]) if n else 0
-    rows = max(rows, ctx._trace_readout_rows * n)  # full readout: |S| rows per event
-    arrays = call_with_capacity(ctx, n, max(16, rows), call, "attpc_traces_at")
+    rows = max(16, rows, ctx._trace_readout_rows * n)  # full readout: |S| rows per event
+    how = dict(holder=PackedTraceArrays, byte_capacity=PACKED_BYTES_PER_ROW * rows) if packed else {}
+    arrays = call_with_capacity(ctx, n, rows, call, name, **how)
     return (*arrays.result(), {**arrays.sums(), **trigger_result(ctx, n)})
+
+
+# ---- packed pad traces (include/attpc_engine.h, "packed pad traces") ----
+TRACE_PACK_FORMAT = _abi.TRACE_PACK_FORMAT
+PACKED_BYTES_PER_ROW = 512  # the byte capacity a packed call first tries, per row of its row capacity (a row: 16 .. 784)
+
+
+def _packed_flag(packed) -> bool:
+    if not isinstance(packed, (bool, np.bool_)):
+        raise TypeError(f"packed must be a bool, got {packed!r}")
+    return bool(packed)
+
+
+class PackedRows:
+    """``row_start`` / ``packed`` of a packed call as one row-indexed sequence: ``rows[lo:hi]`` is the same for rows
+    lo .. hi - 1 (views, nothing is copied or decoded) -- what an event loop slices beside pads and labels."""
+
+    def __init__(self, row_start, packed):
+        self.row_start, self.packed = row_start, packed
+
+    def __len__(self) -> int:
+        return len(self.row_start) - 1
+
+    def __getitem__(self, rows: slice) -> "PackedRows":
+        lo, hi, step = rows.indices(len(self))
+        if step != 1:
+            raise IndexError("PackedRows takes slices of step 1")
+        return PackedRows(self.row_start[lo:max(hi, lo) + 1], self.packed)
+
+    def samples(self, n_threads: int = 0) -> np.ndarray:
+        return unpack_traces(self.row_start, self.packed, n_threads=n_threads)
+
+
+def _sample_rows(samples) -> np.ndarray:
+    samples = np.asarray(samples)
+    if samples.dtype.kind not in "iu":
+        raise TypeError(f"samples must be integers, got {samples.dtype}")
+    if samples.ndim != 2 or samples.shape[1] != _abi.NUM_TB:
+        raise ValueError(f"samples must be [R, {_abi.NUM_TB}], got {samples.shape}")
+    if samples.size and (samples.min() < 0 or samples.max() > 4095):
+        raise ValueError("samples must lie in 0 .. 4095")
+    return np.ascontiguousarray(samples, dtype=np.int16)
+
+
+def _pack(samples, call, check):
+    samples = _sample_rows(samples)
+    n = len(samples)
+    row_start = np.zeros(n + 1, dtype=np.int64)
+    n_bytes = _abi.C.c_int64()
+    i16, i64, u8 = _abi.C.c_int16, _abi.C.c_int64, _abi.C.c_uint8
+    packed = np.empty(max(8, n * _abi.TRACE_PACK_MAX_ROW_BYTES), dtype=np.uint8)  # (the most the rows can take: one call)
+    check(call(n, _abi.iptr(samples, i16), _abi.iptr(row_start, i64), _abi.iptr(packed, u8), len(packed), _abi.C.byref(n_bytes)))
+    return row_start, packed[:int(n_bytes.value)].copy()
+
+
+def pack_traces(samples, ctx: _abi.Context | None = None):
+    """The pack stage alone, on the device (``attpc_trace_pack``: the two kernels of the packed runs): samples [R,512]
+    integers in 0 .. 4095 (ValueError otherwise) -> (row_start [R+1] i64, packed uint8)."""
+    ctx = ctx or _abi.default_context()
+    return _pack(samples, lambda *a: ctx.lib.attpc_trace_pack(ctx.handle, *a), lambda status: ctx.check(status, "attpc_trace_pack"))
+
+
+def _check_host(what: str):
+    def check(status):
+        if status != _abi.OK:
+            raise ValueError(f"{what}: refused (status {status}): malformed records, offsets or samples")
+    return check
+
+
+def pack_traces_host(samples):
+    """The same encoder on the host (``attpc_trace_pack_host``: no context, no GPU) -> (row_start, packed)."""
+    return _pack(samples, _abi.load_library().attpc_trace_pack_host, _check_host("attpc_trace_pack_host"))
+
+
+def unpack_traces(row_start, packed, rows=None, n_threads: int = 0) -> np.ndarray:
+    """Packed records -> samples [R,512] int16, on the host (``attpc_trace_unpack``; ``n_threads`` 0 = automatic).
+    ``rows``: a slice (step 1) or an index array of the rows to decode -- one event of a run is
+    ``slice(offsets[e], offsets[e + 1])`` -- default all.  ValueError for records the decoder refuses."""
+    row_start = np.ascontiguousarray(row_start, dtype=np.int64)
+    packed = np.ascontiguousarray(packed, dtype=np.uint8)
+    if row_start.ndim != 1 or len(row_start) < 1:
+        raise ValueError("row_start needs R + 1 entries")
+    n_all = len(row_start) - 1
+    if rows is None:
+        rows = slice(0, n_all)
+    if isinstance(rows, slice):
+        lo, hi, step = rows.indices(n_all)
+        if step != 1:
+            rows = np.arange(lo, hi, step)
+        else:
+            starts = row_start[lo:max(hi, lo) + 1]
+    if not isinstance(rows, slice):
+        index = np.asarray(rows)
+        if index.dtype == bool:
+            index = np.flatnonzero(index)
+        index = np.where(index < 0, index + n_all, index).astype(np.int64).reshape(-1)
+        if index.size and (index.min() < 0 or index.max() >= n_all):
+            raise IndexError("rows out of range")
+        # the named records side by side in a byte array of their own
+        begin, size = row_start[index], row_start[index + 1] - row_start[index]
+        if (size < 0).any() or (begin < 0).any() or (index.size and (begin + size).max() > len(packed)):
+            raise ValueError("attpc_trace_unpack: offsets outside the packed bytes")
+        starts = np.zeros(len(index) + 1, dtype=np.int64)
+        np.cumsum(size, out=starts[1:])
+        gather = np.repeat(begin - starts[:-1], size) + np.arange(int(starts[-1]))
+        packed = np.ascontiguousarray(packed[gather])
+    starts = np.ascontiguousarray(starts)
+    out = np.empty((len(starts) - 1, _abi.NUM_TB), dtype=np.int16)
+    lib = _abi.load_library()
+    status = lib.attpc_trace_unpack(_abi.iptr(packed, _abi.C.c_uint8), len(packed), _abi.iptr(starts, _abi.C.c_int64), len(out),
+                                    _abi.iptr(out, _abi.C.c_int16), int(n_threads))
+    _check_host("attpc_trace_unpack")(status)
+    return out
 
 
 class PeakSettings:

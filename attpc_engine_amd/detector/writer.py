@@ -17,7 +17,8 @@ import numpy as np
 from .. import _abi
 from .parameters import Config
 from .response import get_response
-from .traces import NoiseSettings, ReadoutSettings, TraceChain, clouds_to_trace_rows, clouds_to_traces, trace_settings
+from .traces import (TRACE_PACK_FORMAT, NoiseSettings, ReadoutSettings, TraceChain, _packed_flag, clouds_to_trace_rows,
+                     clouds_to_traces, pack_traces_host, trace_settings, unpack_traces)
 
 
 class SimulationWriter(Protocol):
@@ -237,7 +238,12 @@ class TraceWriter(_RollingWriter):
     dataset pad_gain when a gain map is given.  ``common_mode`` (a ``detector.traces.CommonModeSettings``, default None
     = off) is the common-mode noise of the traces, keyed like the noise; every file of a writer with it records the
     attributes common_mode_stream, common_mode_sigma (NaN for a custom table) and common_mode_min_level, the dataset
-    common_mode_cdf, and the dataset common_mode_groups when a map is given."""
+    common_mode_cdf, and the dataset common_mode_groups when a map is given.
+    ``packed=True``: an event's samples are stored as losslessly packed records (include/attpc_engine.h, "packed pad
+    traces") -- ``trace_{event}_packed`` uint8 and ``trace_{event}_row_start`` [R+1] int64 (from 0) instead of
+    ``trace_{event}`` -- and the group carries the attribute trace_format; ``read_traces`` reads either layout.  A
+    run feeds such a writer from the packed entry points (``write_packed_traces``): the samples are never expanded
+    on the host.  Without ``packed`` the files are those of a writer that does not know the flag."""
 
     group = "trace"
 
@@ -245,7 +251,8 @@ class TraceWriter(_RollingWriter):
                  first_run_number: int = 0, npz_fallback: bool = True, response: np.ndarray | None = None,
                  threshold: float | None = None, offset: int = 0, noise_sigma: float = 0.0, noise_table=None,
                  pedestals=None, noise_stream: int = 0, noise_seed: int = 0, readout: str = "hit",
-                 readout_pads=None, gain=None, common_mode=None):
+                 readout_pads=None, gain=None, common_mode=None, packed: bool = False):
+        self.packed = _packed_flag(packed)
         response, threshold, offset = trace_settings(config, response, threshold, offset)  # (this config's defaults in every run)
         noise = NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream)
         self.chain = chain = TraceChain(config, response.copy(), threshold, offset, noise, ReadoutSettings(readout, readout_pads), gain,
@@ -258,6 +265,8 @@ class TraceWriter(_RollingWriter):
 
     def _open(self, run_number: int):
         f = super()._open(run_number)
+        if self.packed:
+            f.set_attr("trace_format", TRACE_PACK_FORMAT)
         if self.noise.n_levels:
             f.set_attr("noise_stream", self.noise.stream)
             f.set_attr("noise_sigma", self.noise.sigma)
@@ -297,16 +306,74 @@ class TraceWriter(_RollingWriter):
         ctx = _abi.default_context()
         self.chain.configure(ctx, keep=("trigger",))
         data = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3)
-        _, pads, samples, out_labels, _ = clouds_to_traces(np.array([0, len(data)], dtype=np.int64), data, labels, ctx,
-                                                           seed=self.noise_seed, first_event=event_number)
+        offsets = np.array([0, len(data)], dtype=np.int64)
+        if self.packed:
+            _, pads, row_start, packed, out_labels, _ = clouds_to_traces(offsets, data, labels, ctx, seed=self.noise_seed,
+                                                                         first_event=event_number, packed=True)
+            self.write_packed_traces(pads, row_start, packed, out_labels, event_number)
+            return
+        _, pads, samples, out_labels, _ = clouds_to_traces(offsets, data, labels, ctx, seed=self.noise_seed,
+                                                           first_event=event_number)
         self.write_traces(pads, samples, out_labels, event_number)
 
     def write_traces(self, pads: np.ndarray, samples: np.ndarray, labels: np.ndarray, event_number: int) -> None:
         """One event's kept pad rows, as the device makes them (``Engine.run_traces``, ``simulate_batch_traces``):
-        file roll-over, datasets and attributes."""
+        file roll-over, datasets and attributes.  A ``packed`` writer packs them with the host encoder."""
+        if self.packed:
+            row_start, packed = pack_traces_host(np.asarray(samples).reshape(-1, _abi.NUM_TB))
+            self.write_packed_traces(pads, row_start, packed, labels, event_number)
+            return
         self._begin_event(event_number)
         self.file.create_dataset(f"trace_{event_number}", np.asarray(samples, dtype=np.int16).reshape(-1, _abi.NUM_TB),
                                  {"orig_run": self.run_number, "orig_event": event_number})
         self.file.create_dataset(f"pads_{event_number}", np.asarray(pads, dtype=np.int32))
         self.file.create_dataset(f"labels_{event_number}", np.asarray(labels, dtype=np.int64))
         self._end_event(event_number)
+
+    def write_packed_traces(self, pads: np.ndarray, row_start: np.ndarray, packed: np.ndarray, labels: np.ndarray,
+                            event_number: int) -> None:
+        """One event's kept pad rows as packed records, as the packed entry points deliver them
+        (``Engine.run_traces(packed=True)``): ``row_start`` [R+1] any R + 1 consecutive offsets of a call (stored from
+        0), ``packed`` the bytes they point into.  Only a ``packed`` writer takes them."""
+        if not self.packed:
+            raise TypeError("write_packed_traces needs a TraceWriter(packed=True)")
+        row_start = np.asarray(row_start, dtype=np.int64)
+        records = np.asarray(packed, dtype=np.uint8)[int(row_start[0]):int(row_start[-1])]
+        self._begin_event(event_number)
+        self.file.create_dataset(f"trace_{event_number}_packed", records, {"orig_run": self.run_number, "orig_event": event_number})
+        self.file.create_dataset(f"trace_{event_number}_row_start", row_start - row_start[0])
+        self.file.create_dataset(f"pads_{event_number}", np.asarray(pads, dtype=np.int32))
+        self.file.create_dataset(f"labels_{event_number}", np.asarray(labels, dtype=np.int64))
+        self._end_event(event_number)
+
+
+def read_traces(path, event: int):
+    """One event of a TraceWriter file, ``.h5`` or ``.npz``, plain or packed -> (pads [R] i32, samples [R,512] i16,
+    labels [R] i64).  A packed event is decoded on the host (``unpack_traces``); a file whose trace_format this
+    package does not know is refused."""
+    path = Path(path)
+    if path.suffix == ".npz":
+        with np.load(path) as f:
+            names = set(f.files)
+            get = lambda name: f[f"trace/{name}"]  # noqa: E731
+            has = lambda name: f"trace/{name}" in names  # noqa: E731
+            fmt = str(f["trace@trace_format"]) if "trace@trace_format" in names else None
+            return _read_event(get, has, fmt, event)
+    import h5py
+
+    with h5py.File(path, "r") as f:
+        group = f["trace"]
+        fmt = group.attrs.get("trace_format")
+        fmt = fmt.decode() if isinstance(fmt, bytes) else (None if fmt is None else str(fmt))
+        return _read_event(lambda name: group[name][()], lambda name: name in group, fmt, event)
+
+
+def _read_event(get, has, fmt, event: int):
+    if fmt is not None and fmt != TRACE_PACK_FORMAT:
+        raise ValueError(f"unknown trace_format {fmt!r} (this package reads {TRACE_PACK_FORMAT!r})")
+    pads, labels = np.asarray(get(f"pads_{event}"), dtype=np.int32), np.asarray(get(f"labels_{event}"), dtype=np.int64)
+    if has(f"trace_{event}_packed"):
+        samples = unpack_traces(get(f"trace_{event}_row_start"), get(f"trace_{event}_packed"))
+    else:
+        samples = np.asarray(get(f"trace_{event}"), dtype=np.int16)
+    return pads, samples, labels

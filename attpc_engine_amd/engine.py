@@ -13,11 +13,11 @@ import numpy as np
 
 from . import _abi, nuclear_map
 from .detector.luts import build_det_desc, build_layout, species_for
-from .detector.simulator import default_indices, deliver_events, fired_events, plan_delivery, selected_events
-from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings, PeakSettings, TriggerSettings,
+from .detector.simulator import default_indices, deliver_events, fired_events, plan_delivery, selected_events, writer_packed
+from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings, PackedRows, PeakSettings, TriggerSettings,
                               configure_baseline, configure_common_mode, configure_gain, configure_peaks, configure_traces,
                               configure_trigger, trigger_result)
-from .outputs import RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
+from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
 class Engine:
@@ -146,18 +146,32 @@ class Engine:
             self._spyral_configured = self._peaks_configured = True
 
     def run_traces(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
-                   capacity_per_event: int = 1024) -> dict:
+                   capacity_per_event: int = 1024, packed: bool = False, packed_bytes_per_row: int = 512) -> dict:
         """Fused kinematics + detector + the digitised pad traces of every event, made on the device before anything
         crosses PCIe (``attpc_sim_run_traces``).  ``fetch=True``: offsets [n+1], pads [R] i32, samples [R,512] i16,
         labels [R] i64 (``pinned``: page-locked arrays), event_points [n] = cloud rows before the suppression, and the
         kinematics; ``fetch=False``: the traces stay on the device, only ``trace`` (n_rows and both checksums) and the
         cloud's ``stats`` come back.  Both: with a trigger configured (``configure_trigger``) its records [n] under
-        ``trigger``."""
+        ``trigger``.  ``packed=True`` (``attpc_sim_run_traces_packed``): the rows are packed losslessly on the device
+        and cross PCIe as records -- ``row_start`` [R+1] i64 and ``packed`` uint8 (``detector.traces.unpack_traces``
+        gives the samples back; format ``_abi.TRACE_PACK_FORMAT``) instead of ``samples``, and ``trace`` gains
+        ``n_bytes``, with ``fetch=False`` too; ``packed_bytes_per_row`` sizes the first try's byte array (a row takes
+        16 .. 784 bytes; too small costs one more run)."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
+        if not isinstance(packed, (bool, np.bool_)):
+            raise TypeError(f"packed must be a bool, got {packed!r}")
         if not self._traces_configured:
             self.configure_traces()
         ctx = self.ctx
         stats = _abi.RunStats()
+        if not fetch and packed:
+            out = _abi.TracePackedOut()
+            ctx.check(ctx.lib.attpc_sim_run_traces_packed(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
+                                                          None, None, None, out, stats), "attpc_sim_run_traces_packed")
+            return {"stats": stats.as_dict(), "trace": {"n_rows": int(out.n_rows), "n_bytes": int(out.n_bytes),
+                                                        "sample_checksum": int(out.sample_checksum),
+                                                        "pad_checksum": int(out.pad_checksum)},
+                    **trigger_result(ctx, n_events)}
         if not fetch:
             out = _abi.TraceOut()
             ctx.check(ctx.lib.attpc_sim_run_traces(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
@@ -167,6 +181,13 @@ class Engine:
                                                         "pad_checksum": int(out.pad_checksum)},
                     **trigger_result(ctx, n_events)}
         per_event = max(int(capacity_per_event), ctx._trace_readout_rows)  # full readout: |S|
+        if packed:
+            capacity = max(1024, per_event * n_events)
+            arrays, res = self._deliver("attpc_sim_run_traces_packed", n_events, seed, first_event, capacity, pinned,
+                                        holder=PackedTraceArrays, byte_capacity=capacity * max(16, int(packed_bytes_per_row)))
+            _, pads, row_start, bytes_, _ = arrays.result()
+            return {**res, "pads": pads, "row_start": row_start, "packed": bytes_, "trace": arrays.sums(),
+                    **trigger_result(ctx, n_events)}
         arrays, res = self._deliver("attpc_sim_run_traces", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned)
         _, pads, samples, _ = arrays.result()
@@ -372,9 +393,14 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
         engine._configure_chain(chain, rows=kind == "trace_rows")
     run = {"traces": engine.run_traces, "trace_rows": engine.run_trace_rows, "rows": engine.run_spyral}[kind]
 
+    packed = kind == "traces" and writer_packed(writer)
+
     def batch(start, stop):
-        res = run(stop - start, seed=seed, first_event=start)
-        arrays = (res["pads"], res["samples"]) if kind == "traces" else (res["rows"],)
+        res = run(stop - start, seed=seed, first_event=start, **({"packed": True} if packed else {}))
+        if packed:
+            arrays = (res["pads"], PackedRows(res["row_start"], res["packed"]))
+        else:
+            arrays = (res["pads"], res["samples"]) if kind == "traces" else (res["rows"],)
         return fired_events(res["offsets"], res["event_points"], res.get("trigger"), *arrays, res["labels"])
 
     deliver_events(writer, n_events, batch_size, batch, emit)

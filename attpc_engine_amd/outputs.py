@@ -2,7 +2,7 @@
 
 A run that delivers clouds, Spyral rows or pad traces writes into arrays the caller owns (``attpc_cloud_out`` /
 ``attpc_trace_out``, include/attpc_engine.h) and answers ATTPC_E_CAPACITY, with the rows it needs, when they are too
-small.  ``RowArrays`` and ``TraceArrays`` hold such arrays together with the struct that points at them (``SummaryArrays``: the
+small.  ``RowArrays``, ``TraceArrays`` and ``PackedTraceArrays`` (the rows as packed records, ``attpc_trace_packed_out``) hold such arrays together with the struct that points at them (``SummaryArrays``: the
 fixed-size records of a summary run, ``attpc_summary_out``, which have no capacity; ``SelectedArrays``: the rows of the
 events that pass a selection, ``passed`` and the records of all events, ``attpc_select_out``);
 ``call_with_capacity`` is the only place that allocates them, calls and allocates again.
@@ -68,6 +68,41 @@ class TraceArrays:
         return self.offsets, self.pads[:total], self.samples[:total], self.labels[:total]
 
 
+class PackedTraceArrays:
+    """Caller arrays of one packed trace call (``attpc_trace_packed_out``): TraceArrays with ``row_start`` [capacity + 1]
+    and ``packed`` [byte_capacity] uint8 in the place of the samples.  ``byte_capacity`` is the call's second capacity
+    (``needed_shape``)."""
+
+    def __init__(self, n_events: int, capacity: int, make=None, byte_capacity: int = 0):
+        make = make or _host_empty
+        byte_capacity = max(8, int(byte_capacity))
+        self.offsets = np.zeros(n_events + 1, dtype=np.int64)
+        self.pads = make((capacity,), np.int32)
+        self.row_start = make((capacity + 1,), np.int64)
+        self.packed = make((byte_capacity,), np.uint8)
+        self.labels = make((capacity,), np.int64)
+        self.event_points = np.zeros(n_events, dtype=np.int64)
+        i64 = _abi.C.c_int64
+        self.out = _abi.TracePackedOut(capacity, _abi.iptr(self.offsets, i64), _abi.iptr(self.pads, _abi.C.c_int32),
+                                       _abi.iptr(self.row_start, i64), _abi.iptr(self.packed, _abi.C.c_uint8), byte_capacity,
+                                       _abi.iptr(self.labels, i64), _abi.iptr(self.event_points, i64))
+
+    def needed(self, stats) -> int:
+        return int(self.out.n_rows)
+
+    def needed_shape(self, stats) -> dict:
+        """What the last call wanted of the capacities beside the rows."""
+        return {"byte_capacity": int(self.out.n_bytes)}
+
+    def sums(self) -> dict:
+        return {"n_rows": int(self.out.n_rows), "n_bytes": int(self.out.n_bytes),
+                "sample_checksum": int(self.out.sample_checksum), "pad_checksum": int(self.out.pad_checksum)}
+
+    def result(self):
+        total, n_bytes = int(self.out.n_rows), int(self.out.n_bytes)
+        return self.offsets, self.pads[:total], self.row_start[:total + 1], self.packed[:n_bytes], self.labels[:total]
+
+
 class SummaryArrays:
     """Caller arrays of one summary call -- ``events`` [n] and ``tracks`` [n, n_sim], structured
     (``_abi.EVENT_SUMMARY_DTYPE`` / ``_abi.TRACK_SUMMARY_DTYPE``) -- and the ``attpc_summary_out`` that points at them.
@@ -124,7 +159,9 @@ class SelectedArrays:
 def call_with_capacity(ctx: _abi.Context, n_events: int, capacity: int, call, what: str, stats=None,
                        holder=TraceArrays, slack: int = 0, pinned: bool = False, cache=None, reuse: bool = False, **shape):
     """Run ``call(out)`` with ``holder(n_events, capacity, **shape)`` arrays; on ATTPC_E_CAPACITY once more with the
-    rows the call reported (``holder.needed(stats)``, ``stats`` the RunStats that ``call`` fills) plus ``slack``.
+    rows the call reported (``holder.needed(stats)``, ``stats`` the RunStats that ``call`` fills) plus ``slack`` -- and,
+    for a holder with further capacities among ``shape`` (``needed_shape(stats)``: PackedTraceArrays' byte_capacity),
+    with those it reported.
     ``pinned``: the row arrays in page-locked memory (PCIe-rate copies).  ``cache``: an object whose ``_out_cache``
     attribute keeps the arrays, if ``reuse``, for its next call of the same shape -- the previous call's arrays are
     then overwritten -- and is emptied otherwise; assigning None to the attribute drops them.  Returns the holder of
@@ -141,8 +178,12 @@ def call_with_capacity(ctx: _abi.Context, n_events: int, capacity: int, call, wh
             if cache is not None:
                 cache._out_cache = (key, arrays) if reuse else None
         status = call(arrays.out)
-        if status == _abi.E_CAPACITY and arrays.needed(stats) > capacity:
-            capacity = arrays.needed(stats) + slack
+        more = {}
+        if status == _abi.E_CAPACITY and hasattr(arrays, "needed_shape"):
+            more = {name: need for name, need in arrays.needed_shape(stats).items() if need > shape.get(name, 0)}
+        if status == _abi.E_CAPACITY and (arrays.needed(stats) > capacity or more):
+            capacity = max(capacity, arrays.needed(stats) + slack if arrays.needed(stats) > capacity else 0)
+            shape.update(more)
             continue
         ctx.check(status, what)
         return arrays

@@ -23,7 +23,7 @@
  *   - seeds are any u64.  A call's event ids first_event .. first_event + n_events - 1 must all lie in
  *     [0, 2^64): a range that would wrap past 2^64 is ATTPC_E_INVALID (attpc_kin_run, attpc_det_run,
  *     attpc_sim_run, their _spyral, _traces, _trace_rows and _summary forms, attpc_det_tracks, attpc_det_scatter,
- *     attpc_sim_hint_next, attpc_traces_at, attpc_trace_rows_at).
+ *     attpc_sim_hint_next, attpc_traces_at, attpc_trace_rows_at, and the _traces_packed forms).
  *     Ids 2^40 apart share their jitter streams (the jitter counter holds event[39:0]) and nothing else.
  */
 #ifndef ATTPC_ENGINE_H
@@ -249,6 +249,8 @@ ATTPC_API int32_t attpc_sync(attpc_ctx* ctx);
  *                      up the pixel charges of consecutive track samples that fall on the same pad in the same time
  *                      bucket before the table sees them (same results; automatic = with the path-length dE/dx step,
  *                      attpc_det_desc.path_step > 0, where samples are far closer than a pad)
+ *   "trace_pack_workgroups"  workgroups (of four waves, one row a wave) the trace pack kernels are launched with at
+ *                      most; 0 (default) = 8 per compute unit.  Scheduling only: results do not depend on it
  *   "chunk_events"     as attpc_set_chunk_events */
 ATTPC_API int32_t attpc_set_option(attpc_ctx* ctx, const char* name, int64_t value);
 /* Page-locked host memory for output buffers (point clouds are PCIe bound on their way to the host:
@@ -703,7 +705,8 @@ ATTPC_API int32_t attpc_trace_baseline(attpc_ctx* ctx, int64_t n_rows, const int
  * that did not fire -- the peak passes skip its trace rows; offsets keep one entry per event (an unfired event is an
  * empty range), event_points and the cloud statistics keep their meaning, row_checksum and n_rows cover the rows
  * produced.  The trace entry points (attpc_*_run_traces, attpc_traces_at) deliver all rows whatever gate says:
- * compacting 1 KiB rows before the copy is deliberately out of scope. */
+ * dropping the rows of unfired events before the copy is out of scope (the packed entry points, "packed pad traces"
+ * below, make every row cheaper to copy instead; they too deliver all rows). */
 #define ATTPC_MAX_TRIGGER_GROUPS 16
 typedef struct attpc_trigger_desc {
   int32_t threshold;           /* 0..4095: discriminator level above the pedestal */
@@ -867,6 +870,85 @@ ATTPC_API int32_t attpc_trace_configure_common_mode(attpc_ctx* ctx, const attpc_
  * the top apply. */
 ATTPC_API int32_t attpc_common_mode_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events,
                                          int16_t* out);
+
+/* ---- packed pad traces (opt-in: without a call of the entry points below every output, kernel and instruction
+ * stream of every other entry point is what it is without this section) ----
+ * A kept pad row crosses PCIe as 512 int16 samples (1 KiB), most of them pedestal plus a few counts of noise.  The
+ * packed entry points deliver the same rows as losslessly packed records instead: a per-block frame-of-reference code
+ * with bit planes, made on the device from the samples the trace write pass left in HBM (csrc/trace_pack.hip), before
+ * anything crosses the link.  The encoding of a row is unique, so the device is tested byte for byte against the
+ * numpy restatement in tests/trace_pack_reference.py.  The reference has no counterpart (it stops at point clouds).
+ *
+ * Format ATTPC_TRACE_PACK_FORMAT = "for64-bitplane-v1".  A row is 512 samples s[j] in 0 .. 4095 (every trace
+ * configuration clamps to that range).  Block b (0 .. 7) holds samples 64 b .. 64 b + 63.  For each block
+ *     w_b = bit_length(maximum - minimum), in 0 .. 12,     base_b = min(the minimum of the block, 4096 - 2^w_b).
+ * The base is the block's minimum -- except where minimum + 2^w - 1 would pass 4095 (minimum 290, maximum 4095: w = 12),
+ * where it is the largest base whose w bits stay inside 0 .. 4095; s - base_b still needs exactly w_b bits.  So the
+ * header alone bounds every sample a record can hold, and a decoder checks nothing else to stay inside 12 bits.
+ * The record of a row is, in this order,
+ *   - 8 little-endian u16 headers h_b = base_b | w_b << 12 (16 bytes);
+ *   - then, for b ascending and k = 0 .. w_b - 1 ascending, one little-endian u64 plane word whose bit i is bit k of
+ *     s[64 b + i] - base_b.
+ * A row takes 16 + 8 sum_b w_b bytes: 16 (a constant row) to 784 (ATTPC_TRACE_PACK_MAX_ROW_BYTES), always a multiple
+ * of 8.  row_start is an int64 array [R + 1] of byte offsets into one byte array: record r is bytes row_start[r] ..
+ * row_start[r + 1]; row_start[0] = 0 and the offsets are absolute within a call, across its chunks.
+ * The encoders (device and host) emit exactly that base and the minimal width: the bytes are unique.  The decoder
+ * accepts any w <= 12 with base + 2^w - 1 <= 4095.
+ *
+ * Device cost: per chunk of a run two kernels behind the trace write pass (record sizes; records), a scan between
+ * them, and one host round trip for the chunk's bytes (they size the record buffer and the caller's row_start, and
+ * answer the capacity); 28 bytes of scratch per kept row and the records themselves beside the samples. */
+#define ATTPC_TRACE_PACK_FORMAT "for64-bitplane-v1"
+#define ATTPC_TRACE_PACK_MAX_ROW_BYTES 784
+
+/* attpc_trace_out with the samples replaced by their records; any array may be NULL (that output stays on the device;
+ * with all of them NULL the run still reports n_rows, n_bytes and the checksums: the packed size of a run at the
+ * device-resident rate). */
+typedef struct attpc_trace_packed_out {
+  int64_t capacity;          /* rows pads / labels hold; row_start holds capacity + 1 entries */
+  int64_t* offsets;          /* [n_events + 1] CSR offsets of the events' rows */
+  int32_t* pads;             /* [capacity] */
+  int64_t* row_start;        /* [capacity + 1] byte offsets of the rows' records in bytes */
+  uint8_t* bytes;            /* [byte_capacity] the records */
+  int64_t byte_capacity;
+  int64_t* labels;           /* [capacity] */
+  int64_t* event_points;     /* [n_events] */
+  int64_t n_rows;            /* written: kept rows of the call */
+  int64_t n_bytes;           /* written: bytes of their records */
+  uint64_t sample_checksum;  /* written: as in attpc_trace_out, taken over the samples */
+  uint64_t pad_checksum;     /* written: as in attpc_trace_out */
+} attpc_trace_packed_out;
+
+/* attpc_sim_run_traces, attpc_det_run_traces and attpc_traces_at with that out struct: the same events, rows, pads,
+ * labels, offsets, event_points, checksums, stats and trigger records (attpc_trigger_last), and the same id-range
+ * rules.  ATTPC_E_CAPACITY when the rows pass capacity (any row array wanted) or the bytes pass byte_capacity (bytes
+ * wanted): n_rows and n_bytes then hold what the whole call needs, and the row arrays are unspecified. */
+ATTPC_API int32_t attpc_sim_run_traces_packed(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                              const attpc_event_layout* layout, double* p4, double* vertex,
+                                              int32_t* kin_status, attpc_trace_packed_out* out, attpc_run_stats* stats);
+ATTPC_API int32_t attpc_det_run_traces_packed(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                              const attpc_event_layout* layout, const double* p4, const double* vertex,
+                                              attpc_trace_packed_out* out, attpc_run_stats* stats);
+ATTPC_API int32_t attpc_traces_packed_at(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events,
+                                         const int64_t* offsets, const double* points, const int64_t* labels,
+                                         attpc_trace_packed_out* out);
+/* The stage alone on any host rows, through the same two kernels: samples [n_rows][512] -> row_start [n_rows + 1]
+ * (may be NULL), bytes [byte_capacity] (may be NULL: sizes only) and *n_bytes (may be NULL) = the bytes all rows take.
+ * ATTPC_E_INVALID for a sample outside 0 .. 4095; ATTPC_E_CAPACITY (with *n_bytes and row_start written) when bytes
+ * is given and too small. */
+ATTPC_API int32_t attpc_trace_pack(attpc_ctx* ctx, int64_t n_rows, const int16_t* samples, int64_t* row_start,
+                                   uint8_t* bytes, int64_t byte_capacity, int64_t* n_bytes);
+/* The same encoder and the decoder on the host: no context, no GPU (csrc/trace_pack_host.cpp).  attpc_trace_pack_host
+ * takes and answers what attpc_trace_pack does.  attpc_trace_unpack: records row_start[r] .. row_start[r + 1] of bytes
+ * [n_bytes], r < n_rows (row_start[0] need not be 0: any run of consecutive rows of a call decodes alone) -> samples
+ * [n_rows][512], over n_threads host threads (the rule of attpc_unpack_rows; 0 = automatic).  ATTPC_E_INVALID, with no
+ * read or write outside what it was given, for: offsets that decrease or are no multiples of 8, a span past n_bytes
+ * or below 0, a width above 12, base + 2^w - 1 above 4095, a record whose header-implied size differs from its span
+ * (samples of a refused call are unspecified). */
+ATTPC_API int32_t attpc_trace_pack_host(int64_t n_rows, const int16_t* samples, int64_t* row_start, uint8_t* bytes,
+                                        int64_t byte_capacity, int64_t* n_bytes);
+ATTPC_API int32_t attpc_trace_unpack(const uint8_t* bytes, int64_t n_bytes, const int64_t* row_start, int64_t n_rows,
+                                     int16_t* samples, int32_t n_threads);
 
 /* ---- event and track summaries of a device-resident run (opt-in: without a call of the entry points below every
  * output of every other entry point is what it is without this section) ----
