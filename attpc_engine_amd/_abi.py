@@ -224,6 +224,16 @@ class SelectOut(C.Structure):
                 ("n_passed", C.c_int64), ("n_rows", C.c_int64)]
 
 
+class MapsDesc(C.Structure):
+    _fields_ = [("track_mask", C.c_uint32), ("selected", C.c_uint32)]
+
+
+class MapsOut(C.Structure):
+    _fields_ = [("pad_events", C.POINTER(C.c_uint64)), ("pad_charge", C.POINTER(C.c_int64)),
+                ("tb_events", C.POINTER(C.c_uint64)), ("tb_rows", C.POINTER(C.c_uint64)),
+                ("tb_charge", C.POINTER(C.c_int64)), ("n_events", C.c_uint64), ("n_hit", C.c_uint64)]
+
+
 class TraceOut(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64),
@@ -343,6 +353,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_pack_host", "attpc_trace_unpack",
     "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
     "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
+    "attpc_maps_configure", "attpc_sim_run_maps", "attpc_det_run_maps", "attpc_cloud_maps",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -372,6 +383,9 @@ COMMON_SYMBOLS = ("attpc_trace_configure_common_mode", "attpc_common_mode_rows")
 # ... and the packed pad traces after the common-mode noise: the same rule.
 TRACE_PACK_SYMBOLS = ("attpc_sim_run_traces_packed", "attpc_det_run_traces_packed", "attpc_traces_packed_at",
                       "attpc_trace_pack", "attpc_trace_pack_host", "attpc_trace_unpack")
+
+# ... and the run maps after the packed pad traces: the same rule.
+MAPS_SYMBOLS = ("attpc_maps_configure", "attpc_sim_run_maps", "attpc_det_run_maps", "attpc_cloud_maps")
 
 _lib = None
 
@@ -525,6 +539,19 @@ def load_library() -> C.CDLL:
     for name, argtypes in trace_pack.items():
         if not no_trace_pack:
             getattr(lib, name).argtypes = argtypes
+    maps = {
+        "attpc_maps_configure": [ctxp, C.POINTER(MapsDesc)],
+        "attpc_sim_run_maps": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
+                               C.POINTER(C.c_int32), C.POINTER(SummaryOut), u8p, C.POINTER(MapsOut), C.POINTER(RunStats)],
+        "attpc_det_run_maps": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
+                               C.POINTER(SummaryOut), u8p, C.POINTER(MapsOut), C.POINTER(RunStats)],
+        "attpc_cloud_maps": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(SummaryOut), u8p,
+                             C.POINTER(MapsOut)],
+    }
+    no_maps = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in MAPS_SYMBOLS)
+    for name, argtypes in maps.items():
+        if not no_maps:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -548,7 +575,8 @@ def load_library() -> C.CDLL:
         if ((older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS)
                 or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)
                 or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)
-                or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)):
+                or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)
+                or (no_maps and name in MAPS_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -558,7 +586,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select")
+                   "select", "maps")
 
 
 class Context:

@@ -239,6 +239,11 @@ struct attpc_ctx {
   // a call's events on the host (counted there, then copied to the caller's array if there is one)
   DevBuf sel_passed, sel_rows;
   std::vector<uint8_t> sel_host;
+  bool maps_on = false;            // attpc_maps_configure
+  attpc_maps_desc maps{};
+  // run maps (maps.hip): one map per control-word slot [MAX_SLOTS][MAPS_CELLS], the chunk in that slot's own, and the
+  // totals of the call in progress [MAPS_CELLS]
+  DevBuf mp_slots, mp_total;
   int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
   uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
@@ -802,6 +807,11 @@ struct RunOut {
   bool over = false;                 // ... more than the caller's capacity
   attpc_summary_out* summary = nullptr;  // summary (a resident run: neither cloud nor trace)
   attpc_select_out* select = nullptr;    // a selected run: cloud and summary are views of it (mode cloud or spyral)
+  attpc_maps_out* maps = nullptr;        // a maps run: the summary run that also accumulates the run maps (maps.hip)
+  uint8_t* maps_passed = nullptr;        // ... its caller's passed [n_events], or nullptr
+  bool maps_selected = false;            // ... only the events that pass the configured selection contribute
+  // the configured selection is evaluated on the records of every chunk (passed of the call in ctx->sel_host)
+  bool predicate() const { return select || maps_selected; }
   bool resident() const { return !cloud && !trace; }
   int64_t* offsets() const { return cloud ? cloud->offsets : trace ? trace->offsets : nullptr; }
   int64_t* event_points() const { return cloud ? cloud->event_points : trace ? trace->event_points : nullptr; }
@@ -1507,6 +1517,18 @@ attpc_event_summary empty_event_summary() {
   return r;
 }
 
+// 4 bits per label, 16 labels a word: the first position of layout->indices that holds the label, 15 = none
+void label_positions(const attpc_event_layout& lay, uint64_t nibbles[2]) {
+  nibbles[0] = nibbles[1] = ~0ull;
+  for (int label = 0; label < ATTPC_MAX_ROWS; ++label)
+    for (int s = 0; s < lay.n_sim; ++s)
+      if (lay.indices[s] == label) {
+        uint64_t& word = nibbles[label / 16];
+        word = (word & ~(15ull << (4 * (label % 16)))) | ((uint64_t)s << (4 * (label % 16)));
+        break;
+      }
+}
+
 // The records of `n` events of a batch (its events e0 ..), queued on S behind the launch that wrote the cloud
 // `chunk`.  trk == nullptr: no tracks, the empty track parts.
 int32_t enqueue_summary(attpc_ctx* ctx, const ChunkView& chunk, const attpc_event_layout& lay, const TrackBuffers* trk,
@@ -1528,14 +1550,7 @@ int32_t enqueue_summary(attpc_ctx* ctx, const ChunkView& chunk, const attpc_even
   a.seg_list = static_cast<uint32_t*>(ctx->sm_seg_list.p);
   if (trk) a.trk = *trk;
   a.n_sim = lay.n_sim;
-  a.slot_nibbles[0] = a.slot_nibbles[1] = ~0ull;  // 15 = no position
-  for (int label = 0; label < ATTPC_MAX_ROWS; ++label)
-    for (int s = 0; s < lay.n_sim; ++s)
-      if (lay.indices[s] == label) {  // the first position that holds the label
-        uint64_t& word = a.slot_nibbles[label / 16];
-        word = (word & ~(15ull << (4 * (label % 16)))) | ((uint64_t)s << (4 * (label % 16)));
-        break;
-      }
+  label_positions(lay, a.slot_nibbles);
   a.min_electrons = ctx->summary_min;
   a.pad_centers = ctx->summary_centers;
   a.events = static_cast<attpc_event_summary*>(ctx->sm_events.p);
@@ -1601,6 +1616,81 @@ int32_t validate_select_mask(attpc_ctx* ctx, const char* name, int n_sim) {
   return ATTPC_OK;
 }
 
+// ------------------------------------------------------------------ run maps (maps.hip) ----
+unsigned long long* slot_map(attpc_ctx* ctx, int slot) {
+  return static_cast<unsigned long long*>(ctx->mp_slots.p) + (size_t)slot * MAPS_CELLS;
+}
+
+// The map buffers, and the totals of the call that begins at zero (queued on S).
+int32_t begin_maps_call(attpc_ctx* ctx) {
+  int32_t rc;
+  if ((rc = ensure_idle(ctx, ctx->mp_slots, (size_t)MAX_SLOTS * MAPS_CELLS * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure_idle(ctx, ctx->mp_total, (size_t)MAPS_CELLS * sizeof(unsigned long long)))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->mp_total.p, 0, (size_t)MAPS_CELLS * sizeof(unsigned long long), ctx->stream));
+  return ATTPC_OK;
+}
+
+// The map of `n` events of a batch (its events e0 ..) into the map of `slot`, queued on S directly behind the chunk's
+// enqueue_summary (whose seg_start / seg_list it reads) and, with `selected`, its enqueue_select (passed).  The memset
+// in front makes a repeated chunk start from nothing.
+int32_t enqueue_maps(attpc_ctx* ctx, const ChunkView& chunk, int slot, const attpc_event_layout& lay, uint32_t e0, uint32_t n,
+                     bool selected) {
+  if (n == 0) return ATTPC_OK;
+  MapsArgs a{};
+  a.chunk = chunk;
+  a.n_events = n;
+  a.event0 = e0;
+  a.seg_start = static_cast<const int64_t*>(ctx->sm_seg_start.p);
+  a.seg_list = static_cast<const uint32_t*>(ctx->sm_seg_list.p);
+  a.passed = selected ? static_cast<const uint8_t*>(ctx->sel_passed.p) : nullptr;
+  a.n_sim = lay.n_sim;
+  a.track_mask = ctx->maps.track_mask;
+  label_positions(lay, a.slot_nibbles);
+  a.min_electrons = ctx->summary_min;
+  a.map = slot_map(ctx, slot);
+  HIP_TRY(ctx, hipMemsetAsync(a.map, 0, (size_t)MAPS_CELLS * sizeof(unsigned long long), ctx->stream));
+  if (!launch_maps_events(ctx->stream, a, (uint32_t)ctx->n_cus))
+    return fail(ctx, ATTPC_E_INVALID, "run maps: a chunk of %u events is too long for the %d workgroups' 32-bit cells", n, ctx->n_cus);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// The accepted chunk of `slot`: its map into the call's totals (queued on S).
+int32_t enqueue_maps_fold(attpc_ctx* ctx, int slot) {
+  launch_maps_fold(ctx->stream, slot_map(ctx, slot), static_cast<unsigned long long*>(ctx->mp_total.p));
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// The end of a maps call: the totals into the caller's attpc_maps_out.  `passed` [n_events] of the selection, or nullptr
+// (every event contributed).
+int32_t read_maps_total(attpc_ctx* ctx, attpc_maps_out* out, uint64_t n_events, const uint8_t* passed, uint8_t* passed_out) {
+  std::vector<unsigned long long> h(MAPS_CELLS);
+  HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->mp_total.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (out->pad_events) std::memcpy(out->pad_events, h.data() + MAPS_PAD_EVENTS, ATTPC_NUM_PADS * sizeof(uint64_t));
+  if (out->pad_charge) std::memcpy(out->pad_charge, h.data() + MAPS_PAD_CHARGE, ATTPC_NUM_PADS * sizeof(int64_t));
+  if (out->tb_events) std::memcpy(out->tb_events, h.data() + MAPS_TB_EVENTS, ATTPC_NUM_TB * sizeof(uint64_t));
+  if (out->tb_rows) std::memcpy(out->tb_rows, h.data() + MAPS_TB_ROWS, ATTPC_NUM_TB * sizeof(uint64_t));
+  if (out->tb_charge) std::memcpy(out->tb_charge, h.data() + MAPS_TB_CHARGE, ATTPC_NUM_TB * sizeof(int64_t));
+  out->n_hit = h[MAPS_N_HIT];
+  uint64_t n_in = n_events;
+  if (passed) {
+    n_in = 0;
+    for (uint64_t e = 0; e < n_events; ++e) n_in += passed[e];
+  }
+  out->n_events = n_in;
+  if (passed_out && n_events) {
+    if (passed) std::memcpy(passed_out, passed, (size_t)n_events);
+    else std::memset(passed_out, 1, (size_t)n_events);
+  }
+  return ATTPC_OK;
+}
+
+int32_t read_maps(attpc_ctx* ctx, const RunOut& o, uint64_t n_events) {
+  return read_maps_total(ctx, o.maps, n_events, o.maps_selected ? ctx->sel_host.data() : nullptr, o.maps_passed);
+}
+
 // ------------------------------------------------------------------ the run loop ----
 struct RunSource {   // where a batch's kinematics come from
   bool from_kernel = false;        // attpc_sim_run: kin_run_kernel on T
@@ -1658,7 +1748,7 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT && nb)  // their noise-only rows
       return trace_host_events(ctx, o, batch_first_local, nb, nullptr, nullptr, nullptr, seed, batch_first_global);
     if (o.summary && o.summary->events) std::fill(o.summary->events + batch_first_local, o.summary->events + batch_first_local + nb, empty_event_summary());
-    if (o.select && nb) {  // the predicate on the empty records (n_sim == 0: no position to cut on)
+    if (o.predicate() && nb) {  // the predicate on the empty records (n_sim == 0: no position to cut on)
       const uint8_t pass = select_passes(ctx->select, empty_event_summary(), nullptr, 0) ? 1 : 0;
       std::fill(ctx->sel_host.begin() + batch_first_local, ctx->sel_host.begin() + batch_first_local + nb, pass);
     }
@@ -1681,10 +1771,14 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
   // summary mode: the records of chunk c, queued directly behind its scatter (the next chunk overwrites the cloud)
   auto summarise = [&](const Chunk& c) -> int32_t {
     if (!o.summary) return ATTPC_OK;
-    return enqueue_summary(ctx, chunk_view(ctx, c.slot), lay, &trk, c.e0, c.n);
+    int32_t rc2;
+    if ((rc2 = enqueue_summary(ctx, chunk_view(ctx, c.slot), lay, &trk, c.e0, c.n)) || !o.maps) return rc2;
+    // a maps run: the chunk's map directly behind its records (the next chunk overwrites the segment lists as well)
+    if (o.maps_selected && (rc2 = enqueue_select(ctx, slot_words(ctx, c.slot), lay.n_sim, c.e0, c.n, nullptr))) return rc2;
+    return enqueue_maps(ctx, chunk_view(ctx, c.slot), c.slot, lay, c.e0, c.n, o.maps_selected);
   };
   if (o.summary && (rc = ensure_summary_records(ctx, nb, lay.n_sim))) return rc;
-  if (o.select && (rc = ensure_idle(ctx, ctx->sel_passed, std::max<size_t>(nb, 1)))) return rc;
+  if (o.predicate() && (rc = ensure_idle(ctx, ctx->sel_passed, std::max<size_t>(nb, 1)))) return rc;
   // The assembly of chunk c into `as`; a selected chunk first gets its records and the predicate on them, where its rows
   // lie, and only the rows of the events that pass are put in event order.
   auto assemble = [&](const Chunk& c, AsmSet& as) -> int32_t {
@@ -1715,7 +1809,9 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
     }
     if (r.overflow) return fail(ctx, ATTPC_E_HIP, "point cloud did not fit after repeated buffer growth");
     accumulate(st, r);
-    return ATTPC_OK;
+    // the chunk is accepted: only now does its map count (a repetition zeroed and filled it again); the fold runs on S
+    // before the slot's next chunk zeroes the map
+    return o.maps ? enqueue_maps_fold(ctx, c.slot) : ATTPC_OK;
   };
   if (o.resident()) {
     // device resident: queue up to MAX_SLOTS chunks back to back, read their control words once
@@ -1736,7 +1832,9 @@ int32_t run_batch_chunks(attpc_ctx* ctx, const attpc_event_layout& lay, const Tr
       for (const Chunk& c : group)
         if ((rc = settle(c, nullptr))) return rc;
     }
-    // every chunk of the batch has settled: its records are final
+    // every chunk of the batch has settled: its records (and passed) are final
+    if (o.maps_selected)
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->sel_host.data() + batch_first_local, ctx->sel_passed.p, nb, hipMemcpyDeviceToHost, ctx->stream));
     return o.summary ? copy_summary(ctx, o.summary, batch_first_local, nb, lay.n_sim) : ATTPC_OK;
   }
   // delivered clouds: chunk c+1 is scattered and assembled while chunk c crosses PCIe
@@ -1855,7 +1953,8 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   const uint64_t growths_before = ctx->n_growths;
   const int n_rows = lay.n_rows;
   if (int64_t* offsets = o.offsets()) offsets[0] = 0;
-  if (o.select) ctx->sel_host.assign((size_t)n_events, 0);
+  if (o.predicate()) ctx->sel_host.assign((size_t)n_events, 0);
+  if (o.maps && (rc = begin_maps_call(ctx))) return rc;
   // batches of up to MAX_SLOTS chunks (a small pilot batch while the arena need per track is unknown),
   // each integrated on T while the previous batch is scattered on S
   uint64_t b0 = 0;
@@ -1955,6 +2054,7 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
     o.select->n_passed = n_passed;
     o.select->n_rows = o.rows;
   } else if (o.mode == OutMode::spyral) st.n_points = (uint64_t)o.rows;  // rows that survive the threshold
+  if (o.maps && (rc = read_maps(ctx, o, n_events))) return rc;
   if (o.mode == OutMode::traces && (rc = read_trace_sums(ctx, o))) return rc;  // (the cloud's meaning stays in st)
   if (o.mode == OutMode::trace_rows) {
     st.n_points = (uint64_t)o.rows;  // the rows of the call, as in the Spyral mode
@@ -1996,7 +2096,9 @@ int32_t run_entry(const char* name, attpc_ctx* ctx, uint64_t seed, uint64_t firs
     if (!o.summary) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_summary_out", name);
     if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
   }
-  if (o.select) {
+  if (o.maps && !ctx->maps_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_maps_configure has not been called");
+  if (o.maps) o.maps_selected = ctx->maps.selected != 0;
+  if (o.predicate()) {
     if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
     if (!ctx->select_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_select_configure has not been called");
     if (n_events > (uint64_t)INT64_MAX) return fail(ctx, ATTPC_E_INVALID, "%s: too many events", name);
@@ -2004,7 +2106,7 @@ int32_t run_entry(const char* name, attpc_ctx* ctx, uint64_t seed, uint64_t firs
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc = validate_layout(ctx, layout, true);
   if (rc) return rc;
-  if (o.select && (rc = validate_select_mask(ctx, name, layout->n_sim))) return rc;
+  if (o.predicate() && (rc = validate_select_mask(ctx, name, layout->n_sim))) return rc;
   if (src.from_kernel && layout->n_rows != kin_rows(ctx))
     return fail(ctx, ATTPC_E_INVALID, "layout.n_rows=%d but the pipeline has %d rows", layout->n_rows, kin_rows(ctx));
   if ((makes_traces(o.mode) || o.mode == OutMode::summary || o.select) && (rc = drop_prefetch(ctx))) return rc;  // a trace, summary or selected call is never the announced one
@@ -2924,16 +3026,20 @@ int32_t attpc_det_run_summary(attpc_ctx* ctx, uint64_t seed, uint64_t first_even
 
 namespace {
 // attpc_cloud_summary, and with `passed` attpc_cloud_select: the records of a host cloud (to `out`, if given), then the
-// configured selection on them.
+// configured selection on them.  With `maps` attpc_cloud_maps: the selection only if the maps ask for it (`passed` is
+// then who contributed), and the cloud's maps behind it.
 int32_t host_cloud_records(const char* name, attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
-                           const int64_t* labels, const attpc_event_layout* layout, const attpc_summary_out* out, uint8_t* passed) {
+                           const int64_t* labels, const attpc_event_layout* layout, const attpc_summary_out* out, uint8_t* passed,
+                           attpc_maps_out* maps = nullptr) {
   if (n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
   if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes at most 2^31 - 1 events per call", name);
   if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
-  if (passed && !ctx->select_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_select_configure has not been called");
+  if (maps && !ctx->maps_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_maps_configure has not been called");
+  const bool predicate = maps ? ctx->maps.selected != 0 : passed != nullptr;
+  if (predicate && !ctx->select_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_select_configure has not been called");
   int32_t rc;
   if ((rc = validate_layout(ctx, layout, false))) return rc;
-  if (passed && (rc = validate_select_mask(ctx, name, layout->n_sim))) return rc;
+  if (predicate && (rc = validate_select_mask(ctx, name, layout->n_sim))) return rc;
   const uint32_t n = (uint32_t)n_events;
   const int64_t first = n ? offsets[0] : 0;
   if (first < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
@@ -2950,6 +3056,18 @@ int32_t host_cloud_records(const char* name, attpc_ctx* ctx, int64_t n_events, c
     if (!(tb >= 0.0 && tb < (double)ATTPC_NUM_TB))
       return fail(ctx, ATTPC_E_INVALID, "row %lld: time bucket %g outside [0, 512)", (long long)r, tb);
     if (!(q >= 0.0) || std::isinf(q)) return fail(ctx, ATTPC_E_INVALID, "row %lld: electrons %g", (long long)r, q);
+  }
+  if (maps) {
+    // (one workgroup may meet every row: the 32-bit cells of maps_event_kernel)
+    if (rows > (int64_t)UINT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes at most 2^32 - 1 rows per call", name);
+    maps->n_events = maps->n_hit = 0;
+    if (n == 0) {  // the maps of no event
+      if (maps->pad_events) std::fill(maps->pad_events, maps->pad_events + ATTPC_NUM_PADS, 0ull);
+      if (maps->pad_charge) std::fill(maps->pad_charge, maps->pad_charge + ATTPC_NUM_PADS, 0ll);
+      if (maps->tb_events) std::fill(maps->tb_events, maps->tb_events + ATTPC_NUM_TB, 0ull);
+      if (maps->tb_rows) std::fill(maps->tb_rows, maps->tb_rows + ATTPC_NUM_TB, 0ull);
+      if (maps->tb_charge) std::fill(maps->tb_charge, maps->tb_charge + ATTPC_NUM_TB, 0ll);
+    }
   }
   if (n == 0) return ATTPC_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2978,10 +3096,18 @@ int32_t host_cloud_records(const char* name, attpc_ctx* ctx, int64_t n_events, c
                         (int64_t)n, rows};
   if ((rc = enqueue_summary(ctx, chunk, *layout, nullptr, 0, n))) return rc;
   if (out && (rc = copy_summary(ctx, out, 0, n, layout->n_sim))) return rc;
-  if (passed) {
+  if (predicate) {
     if ((rc = ensure_idle(ctx, ctx->sel_passed, n))) return rc;
     if ((rc = enqueue_select(ctx, chunk.ctrl, layout->n_sim, 0, n, nullptr))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(passed, ctx->sel_passed.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (passed) HIP_TRY(ctx, hipMemcpyAsync(passed, ctx->sel_passed.p, n, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (maps) {  // the cloud as one accepted chunk of slot 0
+    std::vector<uint8_t> in(predicate ? n : 0);
+    if (predicate) HIP_TRY(ctx, hipMemcpyAsync(in.data(), ctx->sel_passed.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = begin_maps_call(ctx))) return rc;
+    if ((rc = enqueue_maps(ctx, chunk, 0, *layout, 0, n, predicate))) return rc;
+    if ((rc = enqueue_maps_fold(ctx, 0))) return rc;
+    return read_maps_total(ctx, maps, n, predicate ? in.data() : nullptr, passed);
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return ATTPC_OK;
@@ -3055,6 +3181,59 @@ int32_t attpc_cloud_select(attpc_ctx* ctx, int64_t n_events, const int64_t* offs
                            const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out, uint8_t* passed) {
   if (!ctx || !passed) return ATTPC_E_INVALID;
   return host_cloud_records(__func__, ctx, n_events, offsets, points, labels, layout, out, passed);
+}
+
+// ---- run maps (maps.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_maps_configure(attpc_ctx* ctx, const attpc_maps_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d) {
+    if (d->track_mask == 0u) return fail(ctx, ATTPC_E_INVALID, "run maps: empty track_mask");
+    if (d->track_mask >> (ATTPC_MAX_SIM + 1)) return fail(ctx, ATTPC_E_INVALID, "run maps: track_mask 0x%x has bits above %d", d->track_mask, ATTPC_MAX_SIM);
+    if (d->selected > 1u) return fail(ctx, ATTPC_E_INVALID, "run maps: selected %u", d->selected);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  ctx->maps_on = d != nullptr;
+  if (d) ctx->maps = *d;
+  return ATTPC_OK;
+}
+
+namespace {
+// The two maps entry points: the summary run with the maps on top.
+int32_t run_maps(const char* name, attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                 const attpc_event_layout* layout, const RunSource& src, const RunSink& sink, attpc_summary_out* records,
+                 uint8_t* passed, attpc_maps_out* maps, attpc_run_stats* stats) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (!maps) return fail(ctx, ATTPC_E_INVALID, "%s needs an attpc_maps_out", name);
+  maps->n_events = maps->n_hit = 0;
+  attpc_summary_out none{nullptr, nullptr};
+  RunOut o{OutMode::summary};
+  o.summary = records ? records : &none;
+  o.maps = maps;
+  o.maps_passed = passed;
+  return run_entry(name, ctx, seed, first_event, n_events, layout, src, sink, o, stats);
+}
+}  // namespace
+
+int32_t attpc_sim_run_maps(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                           const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
+                           attpc_summary_out* records, uint8_t* passed, attpc_maps_out* maps, attpc_run_stats* stats) {
+  return run_maps(__func__, ctx, seed, first_event, n_events, layout, RunSource{true}, RunSink{p4, vertex, kin_status}, records,
+                  passed, maps, stats);
+}
+
+int32_t attpc_det_run_maps(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                           const attpc_event_layout* layout, const double* p4, const double* vertex,
+                           attpc_summary_out* records, uint8_t* passed, attpc_maps_out* maps, attpc_run_stats* stats) {
+  return run_maps(__func__, ctx, seed, first_event, n_events, layout, RunSource{false, p4, vertex}, RunSink{}, records, passed,
+                  maps, stats);
+}
+
+int32_t attpc_cloud_maps(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                         const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* records,
+                         uint8_t* passed, attpc_maps_out* maps) {
+  if (!ctx || !maps) return ATTPC_E_INVALID;
+  return host_cloud_records(__func__, ctx, n_events, offsets, points, labels, layout, records, passed, maps);
 }
 
 // ---- trace rows (peaks.hip; the contract is in include/attpc_engine.h) ----

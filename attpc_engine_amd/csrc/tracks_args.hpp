@@ -311,6 +311,34 @@ struct SelectArgs {
 // passed and sel_rows of events event0 .. event0 + n_events - 1, one lane per event
 void launch_select(hipStream_t s, const SelectArgs& a);
 
+// run maps (maps.hip; attpc_maps_configure, the contract is in include/attpc_engine.h).  A map on the device is one
+// array of MAPS_CELLS u64 cells, the fields of attpc_maps_out one behind the other (the charges as two's complement):
+constexpr int MAPS_PAD_EVENTS = 0;
+constexpr int MAPS_PAD_CHARGE = MAPS_PAD_EVENTS + ATTPC_NUM_PADS;
+constexpr int MAPS_TB_EVENTS = MAPS_PAD_CHARGE + ATTPC_NUM_PADS;
+constexpr int MAPS_TB_ROWS = MAPS_TB_EVENTS + ATTPC_NUM_TB;
+constexpr int MAPS_TB_CHARGE = MAPS_TB_ROWS + ATTPC_NUM_TB;
+constexpr int MAPS_N_HIT = MAPS_TB_CHARGE + ATTPC_NUM_TB;
+constexpr int MAPS_CELLS = MAPS_N_HIT + 1;  // 22 017 cells, 172 KiB
+struct MapsArgs {
+  ChunkView chunk;                 // the chunk's cloud as the scatter left it
+  uint32_t n_events;               // events of the chunk
+  uint32_t event0;                 // first event of the chunk within the batch (passed)
+  const int64_t* seg_start;        // [n_events + 1] and
+  const uint32_t* seg_list;        // [seg_capacity]: the segments grouped by event, as the chunk's summary left them
+  const uint8_t* passed;           // [batch events] of the selection, or nullptr: every event contributes
+  int32_t n_sim;
+  uint32_t track_mask;             // bit s: rows of position s count; bit ATTPC_MAX_SIM: rows whose label has no position
+  uint64_t slot_nibbles[2];        // as SummaryArgs
+  double min_electrons;
+  unsigned long long* map;         // [MAPS_CELLS] the chunk's map, zero before the launch
+};
+// adds the chunk's events (n_events > 0) to a.map (global u64 atomics); max_workgroups: the compute units.  false:
+// nothing was launched, the chunk has too many events for the workgroups' u32 cells
+bool launch_maps_events(hipStream_t s, const MapsArgs& a, uint32_t max_workgroups);
+// total[i] += map[i]
+void launch_maps_fold(hipStream_t s, const unsigned long long* map, unsigned long long* total);
+
 // assembly of a scattered chunk and the small kernels of the host pipeline (assemble.hip)
 // out[i] = sum of in[0..i), i = 0 .. n.  ctrl (may be null): the scatter launch that produced the counts; all 0 if it overflowed
 void launch_exclusive_scan(hipStream_t s, const uint32_t* in, uint32_t n, int64_t* out, const unsigned long long* ctrl);

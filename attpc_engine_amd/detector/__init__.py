@@ -1,5 +1,6 @@
 """Detector effects: same public names as the reference package (reference
 ``detector/__init__.py:13-21``) plus the batch entry points, device backed."""
+from . import maps as _maps
 from . import parameters as _parameters
 from . import selection as _selection
 from . import simulator as _simulator
@@ -19,6 +20,7 @@ _EXPORTS = {
     _summary: ("SummarySettings", "configure_summary", "simulate_batch_summary", "clouds_to_summary",
                "electrons_above_threshold"),
     _selection: ("Selection", "configure_selection", "simulate_batch_selected", "clouds_to_selection"),
+    _maps: ("MapsSettings", "RunMaps", "configure_maps", "simulate_batch_maps", "clouds_to_maps"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

@@ -34,6 +34,7 @@ class Engine:
         self._out_cache = None  # (key, arrays) of the last run with reuse_buffers (call_with_capacity)
         self._spyral_configured = self._traces_configured = self._peaks_configured = self._summary_configured = False
         self._selection = None  # the Selection configure_selection uploaded
+        self._maps = None  # the MapsSettings configure_maps uploaded
         ctx = self.ctx
         kin, keep_k = pipeline.device_desc()
         ctx.check(ctx.lib.attpc_kin_configure(ctx.handle, kin), "attpc_kin_configure")
@@ -348,6 +349,50 @@ class Engine:
                                     holder=SelectedArrays, width=ROW_KINDS[rows], n_sim=len(self.indices), rows=fetch,
                                     slack=4096, cache=self, reuse=reuse_buffers)
         return {**res, **selected_result(arrays, rows, res["stats"]), "indices": list(self.indices)}
+
+    # ---------------------------------------------------------------- run maps
+    def configure_maps(self, maps=None, **parameters) -> None:
+        """The settings of ``run_maps``: a ``detector.maps.MapsSettings`` or its keywords (tracks: the positions of
+        ``indices`` whose rows contribute, default all; other_labels; selected: only the events that pass the configured
+        selection contribute; include/attpc_engine.h); neither: the defaults."""
+        from .detector.maps import MapsSettings, configure_maps
+
+        self._maps = configure_maps(self.ctx, _settings(MapsSettings, maps, parameters) or MapsSettings())
+
+    def run_maps(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
+        """``run_summary`` that also accumulates, on the device and behind every chunk's summary, the maps of the run
+        (``attpc_sim_run_maps``): ``maps`` (a ``detector.maps.RunMaps``: per pad the events that fired it and its charge,
+        per time bucket the events, rows and charge, over the kept rows of the configured track positions; ``n_events``
+        and ``n_hit``), ``passed`` [n] bool (the events that contributed: all without ``selected``), ``events`` [n] and
+        ``tracks`` [n, n_sim] (the records of ALL events, as ``run_summary``), ``indices``, the kinematics and the cloud's
+        ``stats``.  The maps of disjoint id ranges add (``RunMaps.__add__``): shards of a run combine that way.
+        Configures the summary and the maps with the defaults if they were not configured; raises if the maps are of the
+        selected events and no selection was configured."""
+        from .detector.maps import RunMaps
+
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
+        if self._maps is None:
+            self.configure_maps()
+        if self._maps.selected and self._selection is None:
+            raise RuntimeError("maps of the selected events need a selection: call configure_selection first")
+        if not self._summary_configured:
+            self.configure_summary()
+        # (the tokens of the context may have been replaced through another engine of the same context)
+        if self._maps.selected:
+            self.configure_selection(self._selection)
+        self.configure_maps(self._maps)
+        ctx, stats = self.ctx, _abi.RunStats()
+        p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
+        vertex = np.empty((n_events, 3), dtype=np.float64)
+        status = np.empty(n_events, dtype=np.int32)
+        arrays = SummaryArrays(n_events, n_sim=len(self.indices))
+        passed, maps = np.zeros(n_events, dtype=np.uint8), RunMaps()
+        out = maps.out()
+        ctx.check(ctx.lib.attpc_sim_run_maps(ctx.handle, seed, first_event, n_events, self.layout, _abi.dptr(p4),
+                                             _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32), arrays.out,
+                                             _abi.iptr(passed, _abi.C.c_uint8), out, stats), "attpc_sim_run_maps")
+        return {"maps": maps.absorb(out), "passed": passed.astype(bool), "events": arrays.events, "tracks": arrays.tracks,
+                "indices": list(self.indices), "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict()}
 
 
 def _settings(cls, given, parameters: dict, what: str = "keywords"):

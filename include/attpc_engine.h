@@ -1125,6 +1125,75 @@ ATTPC_API int32_t attpc_cloud_select(attpc_ctx* ctx, int64_t n_events, const int
                                      const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* out,
                                      uint8_t* passed);
 
+/* ---- run maps: pad and time-bucket hit maps summed over the events of a device-resident run (opt-in and additive
+ * under ABI version 3: without a call of the entry points below every output of every other entry point is what it is
+ * without this section) ----
+ * A maps run is the summary run of the section above that also reads every chunk's rows once more, in place and behind
+ * the chunk's summary kernels (and the selection on their records), into a few maps of the detector: how often every pad
+ * fires, how much charge it collects and where in the drift window the kept charge sits, over all events or over those
+ * an acceptance cut keeps.  The result is 172 KiB per call whatever its length.
+ * Settings (attpc_maps_desc):
+ *   - track_mask: bit s < ATTPC_MAX_SIM -- rows labelled layout->indices[s] contribute; bit ATTPC_MAX_SIM -- rows whose
+ *     label is in no position of layout->indices contribute.  The label -> position rule is the summary's: a label that
+ *     occurs twice in indices belongs to its first position (the bit of a later one names no row, nor does a bit at or
+ *     above layout->n_sim).  The full mask is (2 << ATTPC_MAX_SIM) - 1.
+ *   - selected: 0 -- every event contributes; 1 -- only the events that pass the configured selection
+ *     (attpc_select_configure: the predicate of "selected delivery", on the same records).
+ * min_electrons is that of attpc_summary_configure: KEPT means what it means there.
+ * For a call over the global ids [first, first + n): E = the events that contribute; a row COUNTS iff it belongs to an
+ * event of E, is kept (q >= min_electrons) and its position's bit is set; t = floor(tau).  Then
+ *   pad_events[p] = events of E with at least one counted row on pad p      pad_charge[p] = sum of q over those rows
+ *   tb_events[t]  = events of E with a counted row in time bucket t         tb_rows[t]    = counted rows in bucket t
+ *   tb_charge[t]  = sum of q over the counted rows in bucket t
+ *   n_events = |E| (an event with nothing to scatter is in E if it passes)  n_hit = events of E with a counted row
+ * Every term is an integer, so:
+ *   - maps(A u B) = maps(A) + maps(B), field by field, for disjoint id ranges A and B (what shards of a run add up);
+ *   - the maps do not depend on chunking, on the scatter build, on buffer growth (a chunk that is scattered again counts
+ *     once) or on the order in which workgroups run;
+ *   - with the full mask and selected = 0: sum(pad_events) = sum(events[].n_pads), sum(tb_rows) = sum(events[].n_kept);
+ *   - at min_electrons = 0 as well: sum(pad_charge) = sum(tb_charge) = sum(events[].charge).
+ * One call makes one plane: maps per position take one call per mask. */
+typedef struct attpc_maps_desc {
+  uint32_t track_mask; /* != 0, no bit above ATTPC_MAX_SIM */
+  uint32_t selected;   /* 0 / 1 */
+} attpc_maps_desc;
+
+/* Host output of a maps call.  Any array may be NULL; n_events and n_hit are filled whatever arrays are given. */
+typedef struct attpc_maps_out {
+  uint64_t* pad_events; /* [ATTPC_NUM_PADS] */
+  int64_t* pad_charge;  /* [ATTPC_NUM_PADS] */
+  uint64_t* tb_events;  /* [ATTPC_NUM_TB] */
+  uint64_t* tb_rows;    /* [ATTPC_NUM_TB] */
+  int64_t* tb_charge;   /* [ATTPC_NUM_TB] */
+  uint64_t n_events;    /* out */
+  uint64_t n_hit;       /* out */
+} attpc_maps_out;
+
+/* desc == NULL turns the mode off (the entry points below then answer ATTPC_E_NOTCONFIGURED).  Independent of every
+ * other *_configure: no call resets another.  ATTPC_E_INVALID for an empty mask, mask bits above ATTPC_MAX_SIM or
+ * selected > 1. */
+ATTPC_API int32_t attpc_maps_configure(attpc_ctx* ctx, const attpc_maps_desc* desc);
+/* attpc_sim_run_summary plus the maps.  records (may be NULL, as may its arrays): the records of ALL events, as
+ * attpc_sim_run_summary gives them; passed [n_events] (may be NULL): 1 = the event is in E (all ones with
+ * selected = 0).  Needs attpc_summary_configure and attpc_maps_configure, with selected attpc_select_configure as well
+ * (else ATTPC_E_NOTCONFIGURED; a selection mask bit at or above layout->n_sim is then ATTPC_E_INVALID).  A maps run is
+ * the resident run: attpc_run_stats keeps its cloud meaning, the id-range rules at the top apply, a pending
+ * attpc_sim_hint_next is dropped.  The sizes are known: there is no capacity. */
+ATTPC_API int32_t attpc_sim_run_maps(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                     const attpc_event_layout* layout, double* p4, double* vertex, int32_t* kin_status,
+                                     attpc_summary_out* records, uint8_t* passed, attpc_maps_out* maps,
+                                     attpc_run_stats* stats);
+/* The same with kinematics from host arrays p4 [n, n_rows, 4] / vertex [n, 3] (the file-driven flow). */
+ATTPC_API int32_t attpc_det_run_maps(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
+                                     const attpc_event_layout* layout, const double* p4, const double* vertex,
+                                     attpc_summary_out* records, uint8_t* passed, attpc_maps_out* maps,
+                                     attpc_run_stats* stats);
+/* The maps of any host cloud through the same kernel, one segment per event: the arguments and checks of
+ * attpc_cloud_select (records and passed may be NULL), at most 2^32 - 1 rows. */
+ATTPC_API int32_t attpc_cloud_maps(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
+                                   const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* records,
+                                   uint8_t* passed, attpc_maps_out* maps);
+
 #ifdef __cplusplus
 }
 #endif
