@@ -2448,6 +2448,9 @@ int32_t attpc_det_configure(attpc_ctx* ctx, const attpc_det_desc* d) {
   if ((size_t)d->n_species * ATTPC_DEDX_NODES * sizeof(double) > 150 * 1024)
     return fail(ctx, ATTPC_E_INVALID, "stopping-power tables of %d species do not fit LDS (max 13)", d->n_species);
   if (!d->pad_lut || d->lut_n < 1) return fail(ctx, ATTPC_E_INVALID, "missing pad look-up table");
+  // (the limit is also what scatter.hip's lut_offsets() rests on: it multiplies an index <= lut_n by the byte pitch
+  //  2 (lut_n + 1) as two 16-bit factors -- v_mad_u32_u16 -- which holds up to lut_n = 32 766; do not raise it past that)
+  static_assert(2 * (32000 + 1) < 65536, "the LUT's byte pitch is a 16-bit factor in scatter.hip");
   if (d->lut_n > 32000) return fail(ctx, ATTPC_E_INVALID, "pad look-up table larger than 32000 x 32000 (indices are staged as 16 bit)");
   if (d->windows_edge <= d->micromegas_edge) return fail(ctx, ATTPC_E_INVALID, "windows_edge <= micromegas_edge");
   if (!(d->length > 0.0) || !(d->w_value > 0.0)) return fail(ctx, ATTPC_E_INVALID, "length and w_value must be > 0");

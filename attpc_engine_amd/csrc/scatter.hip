@@ -108,6 +108,7 @@ constexpr int SC_THREADS = ATTPC_SC_THREADS;
 constexpr int N_WAVES = SC_THREADS / 64;
 constexpr int STAGE = ATTPC_SC_STAGE;            // entries staged per rows round
 constexpr int SORT_CAP = 2048;                   // events with at most this many entries are sorted by time bucket
+constexpr int PERM_ENTRY_BITS = 11;              // ... an entry number of theirs (the other five bits of a perm[] word: the nucleus)
 constexpr int LDS_BLOCKS = SORT_CAP / ARENA_BLK; // arena block ids per track kept in LDS: all a sorted event can use
 constexpr int MAX_CHUNKS = SORT_CAP / 4;         // chunks of an unsorted event with a time-bucket range of their own (the last
                                                  // one stands for all further chunks)
@@ -225,7 +226,8 @@ struct __align__(16) ScatterShared {
   short st_ix[STAGE][MESH];   // the lane's coordinate: LUT index of the y mesh line i, lut_n = off the pad plane
   short st_iy[STAGE][MESH];   // the stepped coordinate: LUT index of the x mesh line j
   int st_tb[STAGE];           // bits 0..9 time bucket, 24..26 position in `indices`, 30 point transport
-  unsigned short perm[SORT_CAP];    // entries (sample x slice) sorted by time bucket, events of <= SORT_CAP entries;
+  unsigned short perm[SORT_CAP];    // entries (sample x slice) sorted by time bucket, events of <= SORT_CAP entries
+                                    // (bits 0..10 entry number, 11..13 the sample's position in `indices`);
                                     // longer events: lowest / highest time bucket of every chunk of SC_THREADS entries
                                     // (two u32 per chunk: chunk_lo(), chunk_hi())
   // The merge variant keeps its sorted entry list in global memory and has no use for perm[]: its staging arrays
@@ -277,9 +279,22 @@ __device__ __forceinline__ MergeStage merge_stage(ScatterShared& sh) {
   return m;
 }
 
-// sample c of the event's concatenated tracks -> record pointer and position in `indices`.  `table` = the event's
-// rows of the block table in global memory: only events too long to be sorted (more than SORT_CAP entries) have
-// tracks with more than LDS_BLOCKS blocks, and only their code path passes it (nullptr: every block id is in LDS).
+// Record pointer of sample c of the event's concatenated tracks, for a sample whose position `isim` in `indices` is
+// known: the predecessor of a sample on its track, an entry of a sorted event at staging (perm[] carries the position
+// beside the entry number).  `table` = the event's rows of the block table in global memory: only events too long to be
+// sorted (more than SORT_CAP entries) have tracks with more than LDS_BLOCKS blocks, and only their code path passes it
+// (nullptr: every block id is in LDS).
+__device__ __forceinline__ const double* sample_ptr_of(const ScatterShared& sh, const double* arena, const int32_t* table, int c,
+                                                       int isim) {
+  const int s = c - sh.cnt[isim];
+  const int bi = s / ARENA_BLK;
+  int blk;
+  if (table != nullptr && bi >= LDS_BLOCKS) blk = table[isim * MAX_BLOCKS_PER_TRACK + bi];
+  else blk = sh.blocks[isim][bi];
+  return arena + ((size_t)blk * ARENA_BLK + (s & (ARENA_BLK - 1))) * 4;
+}
+// sample c -> record pointer and position in `indices`: the search for the position (seven LDS reads, compares and
+// selects, for a value of three bits), then sample_ptr_of()
 __device__ __forceinline__ const double* sample_ptr(const ScatterShared& sh, const double* arena, const int32_t* table, int c,
                                                     int& isim) {
   isim = 0;
@@ -288,6 +303,8 @@ __device__ __forceinline__ const double* sample_ptr(const ScatterShared& sh, con
 #pragma unroll
   for (int k = 1; k < ATTPC_MAX_SIM; ++k)
     if (c >= sh.cnt[k]) isim = k;
+  // (the tail of sample_ptr_of() written out: as a call of it -- the same operations -- the register allocation of the
+  //  whole kernel moves, and three instantiations spill more scalars than before)
   const int s = c - sh.cnt[isim];
   const int bi = s / ARENA_BLK;
   int blk;
@@ -714,13 +731,40 @@ __device__ __forceinline__ void mirror_electrons(const double (&w)[MESH / 2], do
   }
 }
 
+// LUT byte offsets of the ten gathers of a mesh line straight from the packed index pairs: iy[2k] and iy[2k + 1] are
+// the two 16-bit halves of pair[k], and v_mad_u32_u16 reads either half of a register (op_sel) -- ten multiply-adds
+// instead of five masks, five shifts and ten 24-bit multiply-adds.  Both factors are 16 bit: an index is at most lut_n,
+// the byte pitch 2 (lut_n + 1), and attpc_det_configure() refuses a table of more than 32 000 lines (abi.hip: a pitch of
+// 65 536 bytes, lut_n = 32 767, would be the first that does not fit).
+// MAD16 false: the same offsets by masks, shifts and the compiler's 24-bit multiply-adds (the merge variant, whose big
+// and wide builds spill more scalars with the asm form).
+template <bool MAD16 = true>
+__device__ __forceinline__ void lut_offsets(const uint32_t (&pair)[MESH / 2], unsigned int row_pitch, unsigned int col,
+                                            unsigned int (&off)[MESH]) {
+#pragma unroll
+  for (int k = 0; k < MESH / 2; ++k) {
+    if constexpr (MAD16) {
+      asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(off[2 * k]) : "v"(pair[k]), "s"(row_pitch), "v"(col));
+      asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(off[2 * k + 1]) : "v"(pair[k]), "s"(row_pitch), "v"(col));
+    } else {
+      off[2 * k] = __umul24(pair[k] & 0xffffu, row_pitch) + col;
+      off[2 * k + 1] = __umul24(pair[k] >> 16, row_pitch) + col;
+    }
+  }
+}
+// one index out of the packed pairs (the pixel-by-pixel path of a line, which is rare)
+__device__ __forceinline__ unsigned int packed_index(const uint32_t (&pair)[MESH / 2], int j) {
+  return (pair[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+}
+
 // Ten runs per lane at most -> the wave's queue: pixel j's run (key, electrons) goes to LDS address `at` + 8 x (lanes
 // below in mask[j]) on the lanes of mask[j]; `at` = scalar address of the queue's next free entry, advanced past the
 // pixels' runs in turn.  The masks go to exec as they are (an `if` on a mask that crossed a branch is rebuilt by the
 // compiler from a 0/1 vector value: two instructions a pixel), five writes between one save and one restore of exec.
-__device__ __forceinline__ void queue_put(uint32_t at, const unsigned long long (&mask)[MESH], uint32_t hi,
-                                          const int (&ended)[MESH], const uint32_t (&q)[MESH]) {
-  uint32_t addr[MESH];
+// The two halves of it are functions of their own: the address chain ends at `at` + 8 x (all runs of the 64 lines), so a
+// caller that needs the wave's run count reads it off the chain's end instead of adding the ten popcounts up a second
+// time (rows_round()), and writes only once it knows that the runs fit the queue.
+__device__ __forceinline__ uint32_t queue_addresses(uint32_t at, const unsigned long long (&mask)[MESH], uint32_t (&addr)[MESH]) {
 #pragma unroll
   for (int j = 0; j < MESH; ++j) {
     const unsigned long long mk = mask[j];
@@ -730,6 +774,10 @@ __device__ __forceinline__ void queue_put(uint32_t at, const unsigned long long 
     // also keeps `at` a scalar of its own: folded into the lane's count it costs a vector add
     asm("s_lshl3_add_u32 %0, %1, %0" : "+s"(at) : "s"((uint32_t)__popcll(mk)) : "scc");
   }
+  return at;
+}
+__device__ __forceinline__ void queue_write(const uint32_t (&addr)[MESH], const unsigned long long (&mask)[MESH], uint32_t hi,
+                                            const int (&ended)[MESH], const uint32_t (&q)[MESH]) {
   static_assert(MESH == 10, "two blocks of five writes");
 #pragma unroll
   for (int b = 0; b < MESH; b += 5) {
@@ -755,6 +803,12 @@ __device__ __forceinline__ void queue_put(uint32_t at, const unsigned long long 
           [q0] "v"(q[b]), [q1] "v"(q[b + 1]), [q2] "v"(q[b + 2]), [q3] "v"(q[b + 3]), [q4] "v"(q[b + 4])
         : "memory");
   }
+}
+__device__ __forceinline__ void queue_put(uint32_t at, const unsigned long long (&mask)[MESH], uint32_t hi,
+                                          const int (&ended)[MESH], const uint32_t (&q)[MESH]) {
+  uint32_t addr[MESH];
+  queue_addresses(at, mask, addr);
+  queue_write(addr, mask, hi, ended, q);
 }
 
 // Merge variant: what a lane carries along its sequence of entries -- ten accumulators (the pad under each of the
@@ -828,12 +882,19 @@ __device__ __forceinline__ void select_window(ScatterShared& sh, int from, int b
 #endif
   if ((unsigned int)sh.cum[ATTPC_NUM_TB - 1] - keys0 <= (unsigned int)budget + (unsigned int)budget * ATTPC_SC_TAIL_PCT / 100u)
     b0 = ATTPC_NUM_TB;
-  const unsigned int entries = (unsigned int)(sh.cum[b0 - 1] >> 32) - entries0;
-  const unsigned int passes = QUANTUM == SC_THREADS / MESH ? entries * MESH / SC_THREADS : entries / (unsigned int)QUANTUM;
-  if (passes >= 1u && (unsigned int)(sh.cum[ATTPC_NUM_TB - 1] >> 32) > entries0 + entries) {
-    const int b1 = wave_upper_bound<true>(sh.cum, a0, b0,
-                                          entries0 + (QUANTUM == SC_THREADS / MESH ? passes * SC_THREADS / MESH : passes * (unsigned int)QUANTUM), ln);
-    if (b1 > a0) b0 = b1;
+  // The cut-back to whole passes (ATTPC_SC_WHOLE_PASS 0: windows as the key budget cuts them; the A/B of
+  // profiles/r19_entry_paths.md).  The merge variant's quantum is a staging round and is cut back either way.
+#ifndef ATTPC_SC_WHOLE_PASS
+#define ATTPC_SC_WHOLE_PASS 1
+#endif
+  if (ATTPC_SC_WHOLE_PASS || QUANTUM != SC_THREADS / MESH) {
+    const unsigned int entries = (unsigned int)(sh.cum[b0 - 1] >> 32) - entries0;
+    const unsigned int passes = QUANTUM == SC_THREADS / MESH ? entries * MESH / SC_THREADS : entries / (unsigned int)QUANTUM;
+    if (passes >= 1u && (unsigned int)(sh.cum[ATTPC_NUM_TB - 1] >> 32) > entries0 + entries) {
+      const int b1 = wave_upper_bound<true>(sh.cum, a0, b0,
+                                            entries0 + (QUANTUM == SC_THREADS / MESH ? passes * SC_THREADS / MESH : passes * (unsigned int)QUANTUM), ln);
+      if (b1 > a0) b0 = b1;
+    }
   }
   if (ln == 0) {
     const unsigned long long last = sh.cum[b0 - 1];
@@ -989,7 +1050,22 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
       // t < 0 (sigma_t would be NaN: undefined in the reference) and tb >= 512 (removed by the
       // 0 <= tb < 512 mask of simulator.py:111-113) never reach the output
       const bool sorted = MERGE || total_s <= SORT_CAP;  // few enough entries: sort them by time bucket once
-      int my_tb[SORT_PER_THREAD];  // time bucket of this thread's entries tid, tid + SC_THREADS, ...
+      int my_tb[SORT_PER_THREAD];  // time bucket (bits 0..9) and nucleus (10..12) of this thread's entries tid, tid + SC_THREADS, ...
+      // entry number -> sample and slice; without the longitudinal extension (one slice, the usual case) the entry is the
+      // sample: no division, multiply or subtraction (the branch is wave uniform)
+      auto split_entry = [&](int cs, int& c, int& sl) {
+        if constexpr (MC) {
+          c = cs / n_slices;
+          sl = cs - c * n_slices;
+          return;
+        }
+        c = cs;
+        sl = 0;
+        if (n_slices != 1) {
+          c = cs / ATTPC_LONG_STEPS;
+          sl = cs - c * ATTPC_LONG_STEPS;
+        }
+      };
 #pragma unroll
       for (int k = 0; k < SORT_PER_THREAD; ++k) my_tb[k] = -1;
       if constexpr (MERGE) {
@@ -1012,8 +1088,7 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
               sl[u] = n_slices == 1 ? 0 : e / total;
               const int c = e - sl[u] * total;
               rec[u] = sample_ptr(sh, arena, ev_table, c, isim[u]);
-              int isim_prev;
-              if (c > sh.cnt[isim[u]]) prev[u] = sample_ptr(sh, arena, ev_table, c - 1, isim_prev);  // same track
+              if (c > sh.cnt[isim[u]]) prev[u] = sample_ptr_of(sh, arena, ev_table, c - 1, isim[u]);  // same track
             }
           }
 #pragma unroll
@@ -1048,21 +1123,21 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
         for (int k = 0; k < SORT_PER_THREAD; ++k) {
           const int cs = tid + k * SC_THREADS;
           if (cs < total_s) {
-            const int c = cs / n_slices;
-            int isim, isim_prev;
+            int c, sl;
+            split_entry(cs, c, sl);
+            int isim;
             const double* rec = sample_ptr(sh, arena, nullptr, c, isim);
             // (the predecessor on the same track: c - 1 unless c is the track's first sample)
-            const double* prev = c > sh.cnt[isim] ? sample_ptr(sh, arena, nullptr, c - 1, isim_prev) : nullptr;
+            const double* prev = c > sh.cnt[isim] ? sample_ptr_of(sh, arena, nullptr, c - 1, isim) : nullptr;
             const double t = rec[2];
             const double t_prev = prev != nullptr ? prev[2] : -1.0;
             if (t >= 0.0) {
-              const int sl = cs - c * n_slices;
               const double ts = slice_time(a.det, t, sl, n_slices);
               if (ts >= 0.0 && ts < (double)ATTPC_NUM_TB) {
-                my_tb[k] = (int)ts;
+                const int tb = (int)ts;
+                my_tb[k] = tb | (isim << 10);  // the nucleus rides along to perm[]
                 const double prev_ts = t_prev >= 0.0 ? slice_time(a.det, t_prev, sl, n_slices) : -1.0;
-                atomicAdd(&sh.cum[my_tb[k]],
-                          (1ull << 32) | (unsigned long long)key_estimate_on_track(rec, prev, t, my_tb[k], prev_ts, spread));
+                atomicAdd(&sh.cum[tb], (1ull << 32) | (unsigned long long)key_estimate_on_track(rec, prev, t, tb, prev_ts, spread));
               }
             }
           }
@@ -1152,9 +1227,12 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
 #pragma unroll
       for (int k = 0; k < SORT_PER_THREAD; ++k) {
         if (my_tb[k] >= 0) {  // counting sort: a window is then a contiguous range of perm[]
-          const unsigned int before = my_tb[k] > 0 ? (unsigned int)(sh.cum[my_tb[k] - 1] >> 32) : 0u;
-          sh.perm[before + atomicAdd(&reinterpret_cast<uint32_t*>(&sh.st_ix[0][0])[my_tb[k]], 1u)] =
-              (unsigned short)(tid + k * SC_THREADS);
+          const int tb = my_tb[k] & 0x3ff;
+          const unsigned int before = tb > 0 ? (unsigned int)(sh.cum[tb - 1] >> 32) : 0u;
+          // the entry number (11 bits) and, above it, the nucleus the histogram pass found: staging does not search again
+          static_assert(SORT_CAP <= (1 << PERM_ENTRY_BITS) && ATTPC_MAX_SIM <= (1 << (16 - PERM_ENTRY_BITS)), "perm[] holds entry | nucleus << 11");
+          sh.perm[before + atomicAdd(&reinterpret_cast<uint32_t*>(&sh.st_ix[0][0])[tb], 1u)] =
+              (unsigned short)((tid + k * SC_THREADS) | ((my_tb[k] >> 10) << PERM_ENTRY_BITS));
         }
       }
       if (tid < 64) select_window<WQ>(sh, 0, local_const(TK), lane);
@@ -1253,14 +1331,10 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
             // the row's 10 iy indices (5 dwords) and the first 5 of its weights (2 x 16 bytes + 8)
             const uint32_t* __restrict__ iy32 = reinterpret_cast<const uint32_t*>(&sh.st_iy[st][0]);
             const double* __restrict__ wrow = &sh.wtab[__umul24((unsigned int)i, (unsigned int)MESH)];
-            unsigned int iy[MESH];
+            uint32_t iy2[MESH / 2];  // iy[2k] | iy[2k + 1] << 16
             double w[MESH / 2];
 #pragma unroll
-            for (int j = 0; j < MESH; j += 2) {
-              const uint32_t pair = iy32[j >> 1];
-              iy[j] = pair & 0xffffu;
-              iy[j + 1] = pair >> 16;
-            }
+            for (int k = 0; k < MESH / 2; ++k) iy2[k] = iy32[k];
             mirror_weights(wrow, w);
             // per-pixel electrons int(pdf h^2 n) (transporter.py:240-246) as u32; the centre pixel is the
             // largest of the row, so one check bounds every run total of the row below 2^32
@@ -1276,27 +1350,34 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
               // asm takes all ten results: without it the compiler sinks each load into a branch on its
               // first use and waits there -- ten serial L2 round trips.
               const unsigned int col = 2u * (unsigned int)((have && !slow) ? ix : lut_n);
+              unsigned int off[MESH];
+              lut_offsets(iy2, row_pitch, col, off);
 #pragma unroll
-              for (int j = 0; j < MESH; ++j)
-                pad[j] = (int)*reinterpret_cast<const int16_t*>(lut_bytes + (__umul24(iy[j], row_pitch) + col));
+              for (int j = 0; j < MESH; ++j) pad[j] = (int)*reinterpret_cast<const int16_t*>(lut_bytes + off[j]);
+              // ... and the five pixel charges: they need nothing from the gathers, so their f64 multiplies and conversions
+              // belong in front of the wait for them, not behind it (where the compiler put them, after the slow block)
               asm volatile("" : "+v"(pad[0]), "+v"(pad[1]), "+v"(pad[2]), "+v"(pad[3]), "+v"(pad[4]), "+v"(pad[5]),
-                           "+v"(pad[6]), "+v"(pad[7]), "+v"(pad[8]), "+v"(pad[9]));
+                           "+v"(pad[6]), "+v"(pad[7]), "+v"(pad[8]), "+v"(pad[9]), "+v"(el[0]), "+v"(el[1]), "+v"(el[2]),
+                           "+v"(el[3]), "+v"(el[4]));
+#pragma unroll
+              for (int j = 0; j < MESH / 2; ++j) el[MESH - 1 - j] = el[j];
             }
 #ifdef ATTPC_PHASE_TIMERS
             PHASE_SYNC;
             PHASE_MARK(8);
 #endif
             bool slow_ok = true;
-            if (__any(slow)) {
-              if (slow) {
+            // (no __any(slow) around it: the `if` is an exec-mask branch that skips the block when no lane is slow, and
+            //  the vote on top of it cost five instructions per 64 lines -- a 0/1 vector value, its comparison, and three
+            //  scalar ones)
+            if (slow) {
 #pragma unroll 1
-                for (int j = 0; j < MESH && slow_ok; ++j) {
-                  if (point && (i != 0 || j != 0)) continue;
-                  const int p = (int)*reinterpret_cast<const int16_t*>(
-                      lut_bytes + (__umul24(iy[j], row_pitch) + 2u * (unsigned int)ix));
-                  const double q = (point ? 1.0 : sh.wtab[i * MESH + j]) * n_el;
-                  if (p >= 0) slow_ok = table_add(sh, word_hi | (uint32_t)p, (unsigned long long)q);
-                }
+              for (int j = 0; j < MESH && slow_ok; ++j) {
+                if (point && (i != 0 || j != 0)) continue;
+                const int p = (int)*reinterpret_cast<const int16_t*>(
+                    lut_bytes + (__umul24(packed_index(iy2, j), row_pitch) + 2u * (unsigned int)ix));
+                const double q = (point ? 1.0 : sh.wtab[i * MESH + j]) * n_el;
+                if (p >= 0) slow_ok = table_add(sh, word_hi | (uint32_t)p, (unsigned long long)q);
               }
             }
             // Merge runs of equal pads: a run's total sits with its last pixel, `ended[j]` = the pad of a run that ends at
@@ -1306,7 +1387,6 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
             uint32_t run_q[MESH];
             int ended[MESH];
             unsigned long long mask[MESH];
-            int wave_total = 0;
             {
               uint32_t acc = 0u;
 #pragma unroll
@@ -1321,18 +1401,22 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
                   ended[j] = pad[j];
                 }
                 mask[j] = __builtin_amdgcn_ballot_w64(ended[j] >= 0);
-                wave_total += (int)__popcll(mask[j]);
               }
             }
+            // queue positions pixel by pixel: the runs of the pixels before (scalar popcounts) + the lanes below in the
+            // pixel's own mask (mbcnt).  The chain of scalar addresses runs first, whether the runs fit the queue or not:
+            // it ends 8 bytes x the wave's runs behind the queue's start, which is where the run count comes from (one
+            // subtraction and a shift instead of nine additions of the same ten popcounts).
+            uint32_t q_addr[MESH];
+            const uint32_t q_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)qbase);
+            const int wave_total = (int)((queue_addresses(q_first, mask, q_addr) - q_first) >> 3);
 #ifdef ATTPC_PHASE_TIMERS
             asm volatile("" ::"v"(ended[0]), "v"(run_q[9]));
             PHASE_SYNC;
             PHASE_MARK(9);
 #endif
             if (wave_total <= WAVE_QUEUE) {
-              // queue positions pixel by pixel: the runs of the pixels before (scalar popcounts) + the lanes below in
-              // the pixel's own mask (mbcnt)
-              queue_put((uint32_t)__builtin_amdgcn_readfirstlane((int)qbase), mask, word_hi, ended, run_q);
+              queue_write(q_addr, mask, word_hi, ended, run_q);
 #ifdef ATTPC_PHASE_TIMERS
               PHASE_SYNC;
               PHASE_MARK(10);
@@ -1440,14 +1524,10 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
             const double n_el = have ? ms.n[st] : 0.0;
             const int ix = ms.ix[st][i];
             const uint32_t* __restrict__ iy32 = reinterpret_cast<const uint32_t*>(&ms.iy[st][0]);
-            unsigned int iy[MESH];
+            uint32_t iy2[MESH / 2];  // iy[2k] | iy[2k + 1] << 16
             double w[MESH / 2];
 #pragma unroll
-            for (int j = 0; j < MESH; j += 2) {
-              const uint32_t pair = iy32[j >> 1];
-              iy[j] = pair & 0xffffu;
-              iy[j + 1] = pair >> 16;
-            }
+            for (int k = 0; k < MESH / 2; ++k) iy2[k] = iy32[k];
             mirror_weights(&sh.wtab[i * MESH], w);
             uint32_t el[MESH];
             mirror_electrons(w, n_el, el);  // (transporter.py:240-246)
@@ -1457,14 +1537,15 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
             {
 #ifndef ATTPC_ABL_NOGATHER
               const unsigned int col = 2u * (unsigned int)((have && !slow) ? ix : lut_n);
+              unsigned int off[MESH];
+              lut_offsets<false>(iy2, row_pitch, col, off);
 #pragma unroll
-              for (int j = 0; j < MESH; ++j)
-                pad[j] = (int)*reinterpret_cast<const int16_t*>(lut_bytes + (__umul24(iy[j], row_pitch) + col));
+              for (int j = 0; j < MESH; ++j) pad[j] = (int)*reinterpret_cast<const int16_t*>(lut_bytes + off[j]);
               asm volatile("" : "+v"(pad[0]), "+v"(pad[1]), "+v"(pad[2]), "+v"(pad[3]), "+v"(pad[4]), "+v"(pad[5]),
                            "+v"(pad[6]), "+v"(pad[7]), "+v"(pad[8]), "+v"(pad[9]));
 #else  // (ablation builds only, wrong results: what do the gathers cost)
 #pragma unroll
-              for (int j = 0; j < MESH; ++j) pad[j] = (have && !slow) ? (int)(((iy[j] >> 2) * 64u + ((unsigned int)ix >> 2)) & 0x1fffu) : -1;
+              for (int j = 0; j < MESH; ++j) pad[j] = (have && !slow) ? (int)(((packed_index(iy2, j) >> 2) * 64u + ((unsigned int)ix >> 2)) & 0x1fffu) : -1;
 #endif
             }
 #ifdef ATTPC_PHASE_TIMERS
@@ -1472,13 +1553,13 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
             PHASE_MARK(8);
 #endif
             bool slow_ok = true;
-            if (__any(slow)) {
+            if (__any(slow)) {  // (kept here, unlike rows_round(): without it the small build spills one more scalar)
               if (slow) {
 #pragma unroll 1
                 for (int j = 0; j < MESH && slow_ok; ++j) {
                   if (point && (i != 0 || j != 0)) continue;
                   const int p = (int)*reinterpret_cast<const int16_t*>(
-                      lut_bytes + (__umul24(iy[j], row_pitch) + 2u * (unsigned int)ix));
+                      lut_bytes + (__umul24(packed_index(iy2, j), row_pitch) + 2u * (unsigned int)ix));
                   const double q = (point ? 1.0 : sh.wtab[i * MESH + j]) * n_el;
                   if (p >= 0) slow_ok = table_add(sh, word_hi | (uint32_t)p, (unsigned long long)q);
                 }
@@ -1714,12 +1795,12 @@ __global__ __launch_bounds__(SC_THREADS, (SC_THREADS * ATTPC_SC_WG_PER_CU + 255)
           for (int base = 0; base < n_win; base += STAGE) {
             const int n_stage = min(STAGE, n_win - base);
             if (tid < n_stage) {
-              const int cs = (int)sh.perm[r0 + base + tid];
-              const int c = cs / n_slices;
-              int isim;
-              const double* rec = sample_ptr(sh, arena, nullptr, c, isim);
-              stage_entry(tid, reinterpret_cast<const double2*>(rec)[0], reinterpret_cast<const double2*>(rec)[1], isim,
-                          cs - c * n_slices, cs);
+              const int word = (int)sh.perm[r0 + base + tid];
+              const int cs = word & ((1 << PERM_ENTRY_BITS) - 1), isim = word >> PERM_ENTRY_BITS;
+              int c, sl;
+              split_entry(cs, c, sl);
+              const double* rec = sample_ptr_of(sh, arena, nullptr, c, isim);
+              stage_entry(tid, reinterpret_cast<const double2*>(rec)[0], reinterpret_cast<const double2*>(rec)[1], isim, sl, cs);
             }
             block_sync();
             PHASE_MARK(3);
