@@ -159,6 +159,29 @@ assert all(TRIGGER_DTYPE.fields[name][1] == getattr(TriggerRecord, name).offset 
 MAX_TRIGGER_GROUPS = 16
 
 
+class EstimateDesc(C.Structure):
+    _fields_ = [("beam_region_radius", C.c_double), ("magnetic_field", C.c_double), ("min_points", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class TrackEstimate(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_used", C.c_int32), ("n_fit", C.c_int32), ("status", C.c_int32),
+                ("direction", C.c_int32), ("reserved", C.c_int32), ("charge", C.c_int64), ("arc", C.c_int64),
+                ("cx", C.c_double), ("cy", C.c_double), ("radius", C.c_double), ("vx", C.c_double), ("vy", C.c_double),
+                ("vz", C.c_double), ("slope", C.c_double), ("x_mean", C.c_double), ("y_mean", C.c_double),
+                ("dedx", C.c_double), ("brho", C.c_double)]
+
+
+# the track estimate as a numpy structured dtype: itemsize and field offsets are those of include/attpc_engine.h
+ESTIMATE_DTYPE = np.dtype([(name, {C.c_int32: "<i4", C.c_int64: "<i8", C.c_double: "<f8"}[ctype])
+                           for name, ctype in TrackEstimate._fields_], align=True)
+assert ESTIMATE_DTYPE.itemsize == C.sizeof(TrackEstimate) == 128
+assert all(ESTIMATE_DTYPE.fields[name][1] == getattr(TrackEstimate, name).offset for name, _ in TrackEstimate._fields_)
+# ATTPC_EST_*: the bits of TrackEstimate.status
+EST_EMPTY, EST_FEW, EST_RANGE, EST_CAPPED, EST_NO_CIRCLE, EST_ON_AXIS, EST_NO_SLOPE = 1, 2, 4, 8, 16, 32, 64
+EST_MAX_FIT = 2048
+
+
 class TraceGainDesc(C.Structure):
     _fields_ = [("rel_variance", C.c_double), ("pad_gain", _dp), ("quantiles", _dp), ("stream", C.c_uint32),
                 ("reserved", C.c_int32)]
@@ -354,6 +377,7 @@ EXPORTED_SYMBOLS = (
     "attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary",
     "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
     "attpc_maps_configure", "attpc_sim_run_maps", "attpc_det_run_maps", "attpc_cloud_maps",
+    "attpc_trace_configure_estimates", "attpc_estimates_last", "attpc_rows_estimate",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -386,6 +410,9 @@ TRACE_PACK_SYMBOLS = ("attpc_sim_run_traces_packed", "attpc_det_run_traces_packe
 
 # ... and the run maps after the packed pad traces: the same rule.
 MAPS_SYMBOLS = ("attpc_maps_configure", "attpc_sim_run_maps", "attpc_det_run_maps", "attpc_cloud_maps")
+
+# ... and the track estimates of the trace rows after the run maps: the same rule.
+ESTIMATE_SYMBOLS = ("attpc_trace_configure_estimates", "attpc_estimates_last", "attpc_rows_estimate")
 
 _lib = None
 
@@ -552,6 +579,16 @@ def load_library() -> C.CDLL:
     for name, argtypes in maps.items():
         if not no_maps:
             getattr(lib, name).argtypes = argtypes
+    estimates = {
+        "attpc_trace_configure_estimates": [ctxp, C.POINTER(EstimateDesc)],
+        "attpc_estimates_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(TrackEstimate)],
+        "attpc_rows_estimate": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
+                                C.POINTER(TrackEstimate)],
+    }
+    no_estimates = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in ESTIMATE_SYMBOLS)
+    for name, argtypes in estimates.items():
+        if not no_estimates:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -576,7 +613,7 @@ def load_library() -> C.CDLL:
                 or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)
                 or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)
                 or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)
-                or (no_maps and name in MAPS_SYMBOLS)):
+                or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -586,7 +623,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps")
+                   "select", "maps", "estimates")
 
 
 class Context:
@@ -649,6 +686,14 @@ class Context:
         (``attpc_trigger_last``); RuntimeError if no trigger was configured for it."""
         records = np.empty(int(n_events), dtype=TRIGGER_DTYPE)
         self.check(self.lib.attpc_trigger_last(self.handle, 0, len(records), iptr(records, TriggerRecord)), "attpc_trigger_last")
+        return records
+
+    def estimates_last(self, n_events: int, n_sim: int) -> np.ndarray:
+        """The track estimates [n_events, n_sim] (``ESTIMATE_DTYPE``) of this context's last trace-row call
+        (``attpc_estimates_last``); RuntimeError if the stage was off for it."""
+        records = np.empty((int(n_events), int(n_sim)), dtype=ESTIMATE_DTYPE)
+        self.check(self.lib.attpc_estimates_last(self.handle, 0, len(records), iptr(records, TrackEstimate)),
+                   "attpc_estimates_last")
         return records
 
     def set_option(self, name: str, value: int) -> None:

@@ -36,6 +36,7 @@
 #include "trace_pack_host.hpp"
 #include "unpack_host.hpp"
 #include "spyral_integral.hpp"  // (behind the HIP runtime header)
+#include "estimate_host.hpp"
 
 namespace {
 
@@ -93,6 +94,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf pk_y;                 // Fourier baseline on (baseline.hip): the y rows the peak kernels read, int16 [traces][512]
   DevBuf tg_records;           // trigger on (trigger.hip): the chunk's records, attpc_trigger_record [events]
   DevBuf tg_row_pass;          // ... with its gate, trace rows: fired of every kept trace row's event, uint8 [traces]
+  DevBuf est_records;          // track estimates on (estimate.hip): the chunk's records, attpc_track_estimate [events][n_sim]
   Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
   // packed traces (trace_pack.hip): the headers and record sizes of every kept trace row, their scanned byte offsets
   // (tp_block_*: the scan's scratch) and the records; the chunk's bytes in pinned memory (the host waits on `counted`)
@@ -227,6 +229,12 @@ struct attpc_ctx {
   DevBuf tg_op_groups;             // [ATTPC_NUM_PADS] the map of attpc_trigger_rows' last call
   Pinned<attpc_trigger_record> h_trigger;  // records of the last trace or trace-row call, in its event order
   int64_t trigger_call_events = -1;        // events of that call, -1: it had no trigger configured (or there was none)
+  bool estimates_on = false;       // attpc_trace_configure_estimates
+  attpc_estimate_desc estimates{};
+  int64_t est_slot_label[ATTPC_MAX_SIM] = {};  // the labels of the positions of the trace-row call in progress (EstimateArgs)
+  Pinned<attpc_track_estimate> h_estimates;    // records of the last trace-row call, [events][n_sim] in its event order
+  int64_t est_call_events = -1;    // events of that call, -1: it made no records (the stage was off, or there was no layout)
+  int32_t est_call_n_sim = 0;      // positions of its layout
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -997,6 +1005,61 @@ int32_t begin_trigger_call(attpc_ctx* ctx, uint64_t n) {
   return ATTPC_OK;
 }
 
+// The positions of `lay` as the estimate kernel takes them: the label of every position, -1 for a later position of a
+// label given twice (and for an index that is no label).
+void estimate_positions(const attpc_event_layout& lay, int64_t slot_label[ATTPC_MAX_SIM]) {
+  for (int s = 0; s < ATTPC_MAX_SIM; ++s) {
+    slot_label[s] = s < lay.n_sim && lay.indices[s] >= 0 ? (int64_t)lay.indices[s] : -1;
+    for (int t = 0; t < s && t < lay.n_sim; ++t)
+      if (lay.indices[t] == lay.indices[s]) slot_label[s] = -1;
+  }
+}
+
+// The kernel's settings from a checked desc.
+void estimate_settings(const attpc_estimate_desc& d, EstimateArgs* a) {
+  const int64_t rb = estimate_beam_units(d.beam_region_radius);
+  a->rb2 = rb * rb;
+  a->min_points = d.min_points;
+  a->magnetic_field = d.magnetic_field;
+}
+
+// The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none and makes no records):
+// room for its track estimates (attpc_estimates_last), if the stage is on.  Nothing of an earlier call is in flight.
+int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay) {
+  ctx->est_call_events = -1;
+  if (!ctx->estimates_on || !lay) return ATTPC_OK;
+  const int32_t rc = ensure_pinned(ctx, ctx->h_estimates, std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1));
+  if (rc) return rc;
+  estimate_positions(*lay, ctx->est_slot_label);
+  ctx->est_call_n_sim = lay->n_sim;
+  ctx->est_call_events = (int64_t)n;
+  return ATTPC_OK;
+}
+
+// The track estimates of the chunk in `as` (n events, rows written: directly behind launch_peak_rows) on S, as.traced
+// recorded again behind them, and the copy of the records to events first_local .. of the call's pinned array on C.
+int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first_local) {
+  const size_t n_sim = (size_t)ctx->est_call_n_sim;
+  if (!n || !n_sim) return ATTPC_OK;
+  int32_t rc;
+  if ((rc = ensure(ctx, as.est_records, (size_t)n * n_sim * sizeof(attpc_track_estimate)))) return rc;
+  EstimateArgs a{};
+  estimate_settings(ctx->estimates, &a);
+  a.ev_start = static_cast<const int64_t*>(as.pk_ev_start.p);
+  a.rows = static_cast<const double*>(as.sp_rows.p);  // (may be nullptr: then no event of the chunk has a row)
+  a.labels = static_cast<const int64_t*>(as.sp_labels.p);
+  a.records = static_cast<attpc_track_estimate*>(as.est_records.p);
+  std::memcpy(a.slot_label, ctx->est_slot_label, sizeof a.slot_label);
+  a.n_sim = (int32_t)n_sim;
+  launch_estimates(ctx->stream, n, a);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_estimates.p + first_local * n_sim, as.est_records.p,
+                              (size_t)n * n_sim * sizeof(attpc_track_estimate), hipMemcpyDeviceToHost, ctx->stream_c));
+  return ATTPC_OK;
+}
+
 // The trigger of the chunk in `as` (n events, `total` kept rows, written: directly behind enqueue_trace_write) on S --
 // with `gate` the pass byte of every kept row too --, as.traced recorded again behind it, and the copy of the records
 // to events first_local .. of the call's pinned array on C.
@@ -1451,6 +1514,7 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
       HIP_TRY(ctx, hipMemcpyAsync(o.cloud->labels + base, as.sp_labels.p, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost,
                                   ctx->stream_c));
   }
+  if (ctx->est_call_events >= 0 && (rc = enqueue_estimates(ctx, as, n, first_local))) return rc;
   HIP_TRY(ctx, hipEventRecord(as.copied, ctx->stream_c));
   return ATTPC_OK;
 }
@@ -1944,6 +2008,7 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
   if (makes_traces(o.mode) && (rc = reset_trace_sums(ctx, o.mode))) return rc;
   if (makes_traces(o.mode) && (rc = begin_trigger_call(ctx, n_events))) return rc;
+  if (o.mode == OutMode::trace_rows && (rc = begin_estimate_call(ctx, n_events, &lay))) return rc;
   // a readout run sizes its trace chunks for |S| rows per event until it has seen its own rate: the rate of an earlier
   // run says nothing once the threshold, the noise or the workload has changed (hit mode keeps the context's rate)
   if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT) ctx->trace_rows_per_event = 0.0;
@@ -2705,6 +2770,7 @@ int32_t host_cloud_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int6
   if ((rc = sync_all(ctx))) return rc;
   if ((rc = reset_trace_sums(ctx, o.mode))) return rc;
   if ((rc = begin_trigger_call(ctx, n))) return rc;
+  if (o.mode == OutMode::trace_rows && (rc = begin_estimate_call(ctx, n, nullptr))) return rc;  // (no layout: no records)
   const double keep = ctx->trace_rows_per_event;  // a host cloud says nothing about the configured workload
   rc = trace_host_events(ctx, o, 0, n, offsets, points, labels, seed, first_event);
   ctx->trace_rows_per_event = keep;
@@ -3441,6 +3507,86 @@ int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int64_t* offs
     launch_trigger(ctx->stream, (uint32_t)m, a);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out + e0, ctx->scratch[3].p, m * sizeof(attpc_trigger_record), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    e0 = e1;
+  }
+  return ATTPC_OK;
+}
+
+// ---- track estimates of the trace rows (estimate.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_estimates(attpc_ctx* ctx, const attpc_estimate_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = estimate_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  ctx->estimates_on = d != nullptr;
+  if (d) ctx->estimates = *d;
+  return ATTPC_OK;
+}
+
+int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_estimate* out) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->est_call_events < 0)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_estimates_last: the last trace-row call made no track estimates");
+  if (first < 0 || count < 0 || first > ctx->est_call_events || count > ctx->est_call_events - first)
+    return fail(ctx, ATTPC_E_INVALID, "attpc_estimates_last: records %lld .. + %lld of a call of %lld events", (long long)first,
+                (long long)count, (long long)ctx->est_call_events);
+  const size_t n_sim = (size_t)ctx->est_call_n_sim;
+  if (count == 0 || n_sim == 0) return ATTPC_OK;
+  if (!out) return ATTPC_E_INVALID;
+  std::memcpy(out, ctx->h_estimates.p + (size_t)first * n_sim, (size_t)count * n_sim * sizeof(attpc_track_estimate));
+  return ATTPC_OK;
+}
+
+int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                            const attpc_event_layout* layout, const attpc_estimate_desc* d, attpc_track_estimate* out) {
+  if (!ctx || n_events < 0 || !d || !layout) return ATTPC_E_INVALID;
+  if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
+    return fail(ctx, ATTPC_E_INVALID, "attpc_rows_estimate: n_sim %d outside 0 .. %d", layout->n_sim, ATTPC_MAX_SIM);
+  if (const char* bad = estimate_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
+  const size_t n_sim = (size_t)layout->n_sim;
+  if (n_events > 0 && (!offsets || (n_sim && !out))) return ATTPC_E_INVALID;
+  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_rows_estimate takes at most 2^31 - 1 events per call");
+  if (n_events > 0 && offsets[0] < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
+  for (int64_t e = 0; e < n_events; ++e) {
+    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %lld", (long long)e);
+    if (offsets[e + 1] - offsets[e] > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "event %lld has 2^31 rows or more", (long long)e);
+  }
+  if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !labels)) return ATTPC_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  if (n_events == 0 || n_sim == 0) return ATTPC_OK;
+  EstimateArgs a{};
+  estimate_settings(*d, &a);
+  estimate_positions(*layout, a.slot_label);
+  a.n_sim = (int32_t)n_sim;
+  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
+  std::vector<int64_t> start;
+  for (int64_t e0 = 0; e0 < n_events;) {
+    int64_t e1 = e0 + 1;
+    while (e1 < n_events && e1 - e0 < CHUNK_EVENTS && offsets[e1 + 1] - offsets[e0] <= CHUNK_ROWS) ++e1;
+    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
+    start.resize(m + 1);
+    for (size_t e = 0; e <= m; ++e) start[e] = offsets[e0 + (int64_t)e] - offsets[e0];
+    if ((rc = ensure(ctx, ctx->scratch[0], cap * 8 * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[1], cap * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[2], (m + 1) * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[3], m * n_sim * sizeof(attpc_track_estimate)))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, start.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (n_rows) {
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, rows + offsets[e0] * 8, n_rows * 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, labels + offsets[e0], n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    a.ev_start = static_cast<const int64_t*>(ctx->scratch[2].p);
+    a.rows = static_cast<const double*>(ctx->scratch[0].p);
+    a.labels = static_cast<const int64_t*>(ctx->scratch[1].p);
+    a.records = static_cast<attpc_track_estimate*>(ctx->scratch[3].p);
+    launch_estimates(ctx->stream, (uint32_t)m, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out + (size_t)e0 * n_sim, ctx->scratch[3].p, m * n_sim * sizeof(attpc_track_estimate), hipMemcpyDeviceToHost,
+                                ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     e0 = e1;
   }

@@ -225,6 +225,22 @@ struct TriggerArgs {
 // one workgroup per event, empty events included
 void launch_trigger(hipStream_t s, uint32_t n_events, const TriggerArgs& a);
 
+// track estimates of the trace rows (estimate.hip; attpc_trace_configure_estimates, the contract is in
+// include/attpc_engine.h)
+struct EstimateArgs {
+  const int64_t* ev_start;          // [n_events + 1] CSR offsets of the events' rows
+  const double* rows;               // [rows][8] Spyral rows, every event in its delivered order
+  const int64_t* labels;            // [rows]
+  attpc_track_estimate* records;    // [n_events][n_sim]
+  int64_t slot_label[ATTPC_MAX_SIM];  // the label of position s, -1: none (a later position of a label given twice)
+  int32_t n_sim;
+  int32_t min_points;
+  int64_t rb2;                      // Rb^2 in units^2
+  double magnetic_field;
+};
+// one workgroup per event, empty events included (n_events > 0, n_sim > 0)
+void launch_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a);
+
 // packed pad traces (trace_pack.hip; the format "for64-bitplane-v1" is in include/attpc_engine.h).  samples
 // [n_rows][512] as the trace write pass left them, n_rows > 0; `workgroups` = trace_pack_workgroups(n_rows, limit).
 // size pass: headers [n_rows] (the eight u16 headers of every row) and sizes [n_rows] (bytes of its record)

@@ -17,6 +17,7 @@ from .detector.simulator import default_indices, deliver_events, fired_events, p
 from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings, PackedRows, PeakSettings, TriggerSettings,
                               configure_baseline, configure_common_mode, configure_gain, configure_peaks, configure_traces,
                               configure_trigger, trigger_result)
+from .detector.estimate import EstimateSettings, configure_estimates, estimates_result
 from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -244,6 +245,15 @@ class Engine:
         parameters = {} if window_scale is None else {"window_scale": window_scale}
         configure_baseline(self.ctx, _settings(BaselineSettings, baseline, parameters, "window_scale"))
 
+    def _trace_rows_defaults(self) -> None:
+        """What a trace-row call needs and was not configured, with its defaults."""
+        if not self._traces_configured:
+            self.configure_traces()
+        if not self._spyral_configured:
+            self.configure_spyral()
+        if not self._peaks_configured:
+            self.configure_peaks()
+
     def run_trace_rows(self, n_events: int, seed: int = 0, first_event: int = 0, fetch: bool = True, pinned: bool = False,
                        capacity_per_event: int = 2048) -> dict:
         """Fused kinematics + detector + pad traces + the peaks of every kept trace as Spyral rows, all on the device
@@ -254,24 +264,52 @@ class Engine:
         ascending z), labels [P], event_points [n] and the kinematics; ``fetch=False``: the rows stay on the device.
         Both: ``trace_rows`` = {n_rows, row_checksum}, the cloud's ``stats`` (``n_points`` = the rows) and, with a
         trigger configured (``configure_trigger``), its records [n] under ``trigger`` (with its ``gate`` an event that
-        did not fire is an empty range of the offsets)."""
+        did not fire is an empty range of the offsets); with the track estimates configured (``configure_estimates``)
+        their records [n, n_sim] under ``estimates``."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
-        if not self._traces_configured:
-            self.configure_traces()
-        if not self._spyral_configured:
-            self.configure_spyral()
-        if not self._peaks_configured:
-            self.configure_peaks()
+        self._trace_rows_defaults()
         ctx = self.ctx
         if not fetch:
             stats, out = _abi.RunStats(), _abi.CloudOut()
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
-            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events)}
+            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
+                    **estimates_result(ctx, n_events, len(self.indices))}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
-        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events)}
+        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
+                **estimates_result(ctx, n_events, len(self.indices))}
+
+    # ---------------------------------------------------------------- track estimates of the trace rows
+    def configure_estimates(self, estimates=None, **parameters) -> None:
+        """The track estimates of the trace rows (include/attpc_engine.h): a ``detector.estimate.EstimateSettings`` or
+        its keywords (beam_region_radius, min_points) turn them on -- ``run_trace_rows`` and ``run_estimates`` then
+        return one record per (event, position of ``indices``) under ``estimates``: circle, B rho, slope of z against
+        the path, vertex and dE/dx of every simulated nucleus, made on the device from its trace rows; the field is the
+        config's --, neither turns them off (the default).  The writers do not store the records."""
+        configure_estimates(self.ctx, _settings(EstimateSettings, estimates, parameters), self.config)
+
+    def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
+        """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
+        128 bytes per track cross PCIe (``estimates`` [n, n_sim], ``detector.estimate.ESTIMATE_DTYPE``), beside the
+        kinematics they estimate (``p4``, ``vertex``, ``status``; ``detector.estimate.truth_tracks``) and ``indices``,
+        as ``run_summary`` returns them; ``trace_rows`` and ``stats`` as ``run_trace_rows``.  Raises if the estimates
+        are not configured."""
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
+        if self.ctx._tokens["estimates"] is None:
+            raise RuntimeError("run_estimates needs the estimates: call configure_estimates first")
+        self._trace_rows_defaults()
+        ctx, stats, out = self.ctx, _abi.RunStats(), _abi.CloudOut()
+        p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
+        vertex = np.empty((n_events, 3), dtype=np.float64)
+        status = np.empty(n_events, dtype=np.int32)
+        ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
+                                                   _abi.dptr(p4), _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32),
+                                                   out, stats), "attpc_sim_run_trace_rows")
+        return {"estimates": ctx.estimates_last(n_events, len(self.indices)), "indices": list(self.indices),
+                "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
+                "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

@@ -589,7 +589,8 @@ ATTPC_API int32_t attpc_trace_configure_readout(attpc_ctx* ctx, const attpc_trac
  * the arrival's z; with offset = 0 every point sits argmax(R) buckets late.
  * By default the baseline is not fitted: the analysis is handed every pad's true pedestal.  Spyral has to estimate
  * it, with a Fourier low-pass filter that takes part of a wide pulse for baseline; attpc_trace_configure_baseline
- * (below) runs that estimate in place of step 1.  Spyral's later phases (clustering, fitting) are not part of this.
+ * (below) runs that estimate in place of step 1.  Spyral's later phases (clustering, fitting) are not part of this;
+ * its estimation phase on the labelled rows is "track estimates of the trace rows" at the end of this file.
  * Results of a call: rows of EIGHT doubles in out->points (capacity counts rows), out->labels, out->offsets,
  * out->event_points; any of them may be NULL, and with points and labels both NULL the capacity does not bind: the
  * rows stay on the device.  stats->n_points is the number of rows of the call (as attpc_sim_run_spyral reports its
@@ -1193,6 +1194,122 @@ ATTPC_API int32_t attpc_det_run_maps(attpc_ctx* ctx, uint64_t seed, uint64_t fir
 ATTPC_API int32_t attpc_cloud_maps(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
                                    const int64_t* labels, const attpc_event_layout* layout, attpc_summary_out* records,
                                    uint8_t* passed, attpc_maps_out* maps);
+
+/* ---- track estimates of the trace rows (opt-in: off by default, and with it off every output, kernel and buffer of
+ * every entry point is what it is without this section; the entry points are additions under ABI version 3) ----
+ * What Spyral's estimation phase computes for every cluster, made on the device for every simulated nucleus of every
+ * event from the event's trace rows, right behind the kernel that writes them: a circle in the pad plane (radius ->
+ * B rho), the polar angle from z against the path in the pad plane, the vertex and dE/dx.  Clustering is not needed:
+ * a trace row carries the label of the nucleus that made it.  One 128-byte record (attpc_track_estimate) per event and
+ * position of layout->indices crosses PCIe, beside the p4 / vertex of the same call, which are the truth.
+ * The formulae follow Spyral's estimate_physics in STRUCTURE -- the start at the beam axis, a circle on the first part
+ * of the trajectory, the polar angle from z against the cumulated pad-plane distance of consecutive points (zig-zag
+ * included), B rho = B R / sin(theta), dE/dx = charge over that length -- but THIS CONTRACT, not Spyral's source, is
+ * what the device is tested against (tests/estimate_reference.py restates it in numpy), and the circle is the
+ * algebraic (Kasa) least-squares fit in closed form, not Spyral's iterative one.
+ * A "unit" is the quantisation step of the coordinates, 1/16 mm.
+ * Settings (attpc_estimate_desc): beam_region_radius in mm, finite and >= 0; min_points >= 3; magnetic_field in T, not
+ * NaN; reserved = 0.
+ * For event e and position s of layout->indices take the event's trace rows in their delivered order (ascending z)
+ * whose label equals indices[s].  A label that occurs twice in indices goes to its FIRST position, as in the summaries;
+ * a later position gets the empty record.  Rows of label -1 and of any other label take no part.
+ *   1. Quantise.  X = rint(16 x), Y = rint(16 y), Z = rint(16 z) (columns 0, 1, 2 of the row; the product is exact,
+ *      rint rounds half to even), I = rint(integral) (column 4): integers.  A row is OUT OF RANGE if any of x, y, z,
+ *      integral is not finite, or |x| > 320 mm, |y| > 320 mm, |z| > 8192 mm or |integral| >= 2^31; such a row is not
+ *      used and sets the status bit RANGE.  A row is USED iff it is in range and X^2 + Y^2 >= Rb^2 with
+ *      Rb = rint(16 beam_region_radius) -- an integer comparison (Rb^2 as a 64-bit integer, Rb clamped to 2^31 - 1).
+ *      n_rows = rows of the label, n_used = used rows.
+ *   2. Few points.  n_used < min_points: status FEW (EMPTY instead if n_rows == 0), plus RANGE if it was set;
+ *      n_fit = 0, direction = 0, charge = 0, arc = 0 and every f64 field NaN.  Nothing else is computed.
+ *   3. Direction.  direction = +1 if X^2 + Y^2 of the first used row <= that of the last used row (a tie is +1);
+ *      otherwise direction = -1 and the used rows are taken in reverse order.  The end nearer the beam axis is the start.
+ *   4. Fit segment: the first m = min(max((n_used + 1) div 2, min_points), 2048) used rows in that order; n_fit = m.
+ *      A cut at 2048 sets the status bit CAPPED.
+ *   5. Moment sums.  Row 0 of the segment gives (X0, Y0, Z0).  For segment rows i = 0 .. m - 1: u = X - X0,
+ *      v = Y - Y0, w = Z - Z0; d_0 = 0 and d_i = rint(sqrt((double)(dX^2 + dY^2))) with (dX, dY) the step from segment
+ *      row i - 1 (the radicand is an exact integer below 2^53, the square root correctly rounded, the result an
+ *      integer again); S_i = S_(i-1) + d_i.  The 64-bit integer sums over the segment:
+ *        Su, Sv, Suu, Suv, Svv, Suuu, Suvv, Svvv, Svuu (of u, v, u u, u v, ..., v u u), SS, Sw, SSS, SSw (of S, w,
+ *        S S, S w) and SI (of I).
+ *      Bounds: |X|, |Y| <= 5120, so |u|, |v| <= 10240 and d <= 14482; |Z| <= 131072, so |w| <= 262144;
+ *      S <= 2047 * 14482 < 3e7.  With m <= 2048: |Suuu| <= 2048 * 10240^3 < 2.2e15, SSS <= 2048 * 9e14 < 1.8e18,
+ *      |SSw| <= 2048 * 3e7 * 262144 < 1.7e16, |SI| <= 2^42 -- all inside 2^63 = 9.2e18.  No sum can overflow, so the
+ *      sums are exact and independent of any order of summation.
+ *   6. Closed form, in f64: the sums and m, X0, Y0, Z0 converted to double (one rounding each), then exactly the
+ *      operations below, each rounded once, left to right as C evaluates the expression, no fused multiply-add
+ *      (#pragma clang fp contract(off)); only + - * / and sqrt.  Trigonometric functions stay on the host.
+ *        A = m Suu - Su Su;  B = m Suv - Su Sv;  C = m Svv - Sv Sv
+ *        D = (m (Suvv + Suuu) - Su (Suu + Svv)) / 2;  E = (m (Svuu + Svvv) - Sv (Suu + Svv)) / 2
+ *        den = A C - B B;  uc = (D C - B E) / den;  vc = (A E - B D) / den
+ *        r2 = (Suu + Svv - 2 uc Su - 2 vc Sv) / m + uc uc + vc vc
+ *      den == 0 or not r2 > 0: status NO_CIRCLE; cx, cy, radius, vx, vy, vz and brho are NaN.  Otherwise
+ *        cx = (X0 + uc) / 16;  cy = (Y0 + vc) / 16;  radius = sqrt(r2) / 16                       (mm)
+ *      Vertex in the plane, the circle's point nearest the z axis: c = sqrt(cx cx + cy cy);
+ *        vx = cx (1 - radius / c);  vy = cy (1 - radius / c)
+ *      c == 0: status ON_AXIS; vx, vy, vz are NaN.
+ *      Slope of z against the path: sden = m SSS - SS SS; sden == 0: status NO_SLOPE; slope, vz and brho are NaN.  Else
+ *        slope = b = (m SSw - SS Sw) / sden     (signed along the direction of travel: a backward track has b < 0)
+ *      Vertex z, the regression's value at S = 0 carried back by the chord from segment row 0 to the vertex:
+ *        a0 = (Sw - b SS) / m;  gx = X0 - 16 vx;  gy = Y0 - 16 vy;  chord0 = sqrt(gx gx + gy gy)
+ *        vz = (Z0 + a0 - b chord0) / 16
+ *      x_mean = (X0 + Su / m) / 16, y_mean = (Y0 + Sv / m) / 16 (the host takes the azimuth from the chord vertex ->
+ *      segment mean); arc = S_(m-1) (int64, units); charge = SI (int64);
+ *        dedx = charge / (arc / 16), NaN at arc == 0
+ *        brho = magnetic_field radius 1e-3 sqrt(1 + b b)  (T m: B R / sin(theta) with cot(theta) = b)
+ * An event that a trigger gate left without rows has EMPTY records.  Every field is a pure function of the event's
+ * rows, hence of (seed, global event id): independent of chunking, shards and scatter build. */
+#define ATTPC_EST_EMPTY 1      /* no row of the label (or a later position of a label given twice) */
+#define ATTPC_EST_FEW 2        /* n_used < min_points */
+#define ATTPC_EST_RANGE 4      /* a row of the label was out of range and not used */
+#define ATTPC_EST_CAPPED 8     /* the fit segment was cut at 2048 rows */
+#define ATTPC_EST_NO_CIRCLE 16
+#define ATTPC_EST_ON_AXIS 32
+#define ATTPC_EST_NO_SLOPE 64
+#define ATTPC_EST_MAX_FIT 2048
+
+typedef struct attpc_estimate_desc {
+  double beam_region_radius;  /* mm, finite and >= 0; Spyral's default is 25 */
+  double magnetic_field;      /* T */
+  int32_t min_points;         /* >= 3; Spyral's default is 30 */
+  int32_t reserved;           /* 0 */
+} attpc_estimate_desc;
+
+typedef struct attpc_track_estimate {
+  int32_t n_rows;
+  int32_t n_used;
+  int32_t n_fit;
+  int32_t status;     /* ATTPC_EST_* bits */
+  int32_t direction;  /* +1, -1, or 0 without a fit */
+  int32_t reserved;   /* 0 */
+  int64_t charge;
+  int64_t arc;
+  double cx, cy, radius;
+  double vx, vy, vz;
+  double slope;
+  double x_mean, y_mean;
+  double dedx;
+  double brho;
+} attpc_track_estimate;  /* 128 bytes */
+
+/* desc == NULL turns the stage off (the default).  Independent of every other configure call: no call resets another.
+ * ATTPC_E_INVALID outside the ranges above, NaN included.  Takes effect in attpc_sim_run_trace_rows and
+ * attpc_det_run_trace_rows: every chunk's records are made right behind the kernel that writes its rows, on the same
+ * stream, and copied to pinned host memory in the call's event order -- also when the rows stay on the device (points
+ * and labels NULL).  attpc_trace_rows_at takes no layout, so it makes no records (attpc_estimates_last then answers
+ * ATTPC_E_NOTCONFIGURED); attpc_rows_estimate on its rows gives them. */
+ATTPC_API int32_t attpc_trace_configure_estimates(attpc_ctx* ctx, const attpc_estimate_desc* desc);
+/* Records [count][layout->n_sim] of events first .. first + count - 1 of the context's last trace-row call, in the
+ * call's event order (a call repeated after ATTPC_E_CAPACITY overwrites them).  ATTPC_E_NOTCONFIGURED if the stage was
+ * off for that call, ATTPC_E_INVALID for a range outside it. */
+ATTPC_API int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_estimate* out);
+/* The stage alone on any host rows in CSR form, through the same kernel (what attpc_trigger_rows is to the trigger):
+ * offsets [n_events + 1], rows [R][8] as the trace-row and Spyral-row entry points deliver them, labels [R] -> out
+ * [n_events][layout->n_sim]; of the layout only n_sim and indices are read.  Needs no other configure call and leaves
+ * the configured stage as it is.  ATTPC_E_INVALID for decreasing offsets, n_sim outside 0 .. ATTPC_MAX_SIM or a desc
+ * out of range. */
+ATTPC_API int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                      const int64_t* labels, const attpc_event_layout* layout,
+                                      const attpc_estimate_desc* desc, attpc_track_estimate* out);
 
 #ifdef __cplusplus
 }

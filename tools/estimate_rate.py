@@ -1,0 +1,159 @@
+"""Cost and yield of the track estimates of the trace rows (attpc_trace_configure_estimates): one GPU,
+o16aa and be10dp, two trace modes -- hit mode without noise, partial readout with sigma = 5, pedestals and
+threshold 20.
+
+Rates: per (workload, mode) one engine in this process; ``run_trace_rows(fetch=False)`` of ``--events`` events with
+the stage off and on, alternating, ``--reps`` timed calls each behind one warm-up call of each kind (buffers settle).
+A leg's figure is the median of its timed calls, its spread their minimum and maximum; the stage's cost per event is
+1 / rate(on) - 1 / rate(off).
+Yield: ``--stats-events`` events through ``run_estimates`` in calls of ``--events``: the share of tracks per status
+bit, and for the tracks with B rho and slope the median and the 16 .. 84 % half-width of brho / brho_true - 1 and of
+polar - polar_true against ``truth_tracks`` of the same call -- and, to tell the two factors of B rho apart, of
+radius / radius_true - 1 and of the cumulated distance over twice the chord vertex -> segment mean (1 for a thin
+straight segment; the zig-zag of neighbouring pads raises it).  Reported values for the settings used, no limits.
+``--profile WORKLOAD`` runs two ``run_estimates`` calls in partial readout and nothing else, for
+``rocprofv3 --kernel-trace --stats -- python tools/estimate_rate.py --profile o16aa`` (a run of its own).
+
+    python tools/estimate_rate.py [--events N] [--reps K] [--stats-events M] [--workloads o16aa,be10dp] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+MODES = {
+    "hit": {},
+    "partial": {"noise_sigma": 5.0, "pedestals": 300, "threshold": 20.0, "readout": "partial"},
+}
+
+
+def _engine(name: str, mode: str):
+    import numpy as np
+
+    from attpc_engine_amd import _abi, workloads
+    from attpc_engine_amd.detector.response import get_response
+    from attpc_engine_amd.engine import Engine
+
+    pipeline, config, indices = workloads.WORKLOADS[name]()
+    eng = Engine(pipeline, config, indices, context=_abi.Context(0))
+    eng.configure_traces(config, offset=int(np.argmax(get_response(config))), **MODES[mode])
+    return eng
+
+
+def _median(values):
+    v = sorted(values)
+    return v[len(v) // 2]
+
+
+def rates(eng, events: int, reps: int) -> dict:
+    from attpc_engine_amd.detector.estimate import EstimateSettings
+
+    legs = {"off": [], "on": []}
+
+    def call(on: bool):
+        eng.configure_estimates(EstimateSettings() if on else None)
+        t0 = time.perf_counter()
+        res = eng.run_trace_rows(events, seed=1, fetch=False)
+        return events / (time.perf_counter() - t0), res
+
+    call(False), call(True)
+    rows = 0
+    for _ in range(reps):
+        for on in (False, True):
+            rate, res = call(on)
+            legs["on" if on else "off"].append(rate)
+            rows = res["trace_rows"]["n_rows"]
+    eng.configure_estimates()
+    return {"rows_per_event": rows / events, **{k: [_median(v), min(v), max(v)] for k, v in legs.items()}}
+
+
+def yield_(eng, events: int, total: int) -> dict:
+    import numpy as np
+
+    from attpc_engine_amd.detector.estimate import STATUS_BITS, EstimateSettings, polar, truth_tracks
+
+    eng.configure_estimates(EstimateSettings())
+    est, truth = [], []
+    for first in range(0, total, events):
+        res = eng.run_estimates(min(events, total - first), seed=1, first_event=first)
+        est.append(res["estimates"])
+        truth.append(truth_tracks(res["p4"], res["indices"], eng.z))
+    eng.configure_estimates()
+    est = np.concatenate(est)
+    field = float(eng.config.det_params.bfield)
+    truth = {k: np.concatenate([t[k] for t in truth]) for k in truth[0]}
+    out = {"tracks": int(est.size), "indices": list(eng.indices), "positions": []}
+    for s in range(est.shape[1]):
+        e = est[:, s]
+        pos = {"status": {name: float((e["status"] & bit != 0).mean()) for name, bit in STATUS_BITS.items()},
+               "clean": float((e["status"] == 0).mean())}
+        good = np.isfinite(e["brho"]) & np.isfinite(e["slope"]) & np.isfinite(truth["brho"][:, s])
+        pos["estimated"] = float(good.mean())
+        if good.sum() >= 10:
+            # the two factors of brho apart: the circle against R = B rho sin(theta) / B of the truth, and the
+            # cumulated pad-plane distance against the straight chord of the same segment (zig-zag: above 1)
+            radius_true = truth["brho"][good, s] * np.sin(truth["polar"][good, s]) / field * 1.0e3
+            chord = 16.0 * np.hypot(e["x_mean"][good] - e["vx"][good], e["y_mean"][good] - e["vy"][good])
+            for name, delta in (("brho_rel", e["brho"][good] / truth["brho"][good, s] - 1.0),
+                                ("polar", polar(e)[good] - truth["polar"][good, s]),
+                                ("radius_rel", e["radius"][good] / radius_true - 1.0),
+                                ("arc_over_2chord_to_mean", e["arc"][good] / (2.0 * chord))):
+                lo, mid, hi = np.percentile(delta, [16.0, 50.0, 84.0])
+                pos[name] = {"median": float(mid), "half_width_16_84": float((hi - lo) / 2.0)}
+        out["positions"].append(pos)
+    return out
+
+
+def profile(name: str, events: int) -> None:
+    from attpc_engine_amd.detector.estimate import EstimateSettings
+
+    eng = _engine(name, "partial")
+    eng.configure_estimates(EstimateSettings())
+    eng.run_estimates(events, seed=1)
+    eng.run_estimates(events, seed=1)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--profile")
+    ap.add_argument("--events", type=int, default=16384)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--stats-events", type=int, default=100000)
+    ap.add_argument("--workloads", default="o16aa,be10dp")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    if args.profile:
+        return profile(args.profile, args.events)
+    for name in args.workloads.split(","):
+        for mode in MODES:
+            eng = _engine(name, mode)
+            line = {"workload": name, "mode": mode, "events": args.events, "rates": rates(eng, args.events, args.reps)}
+            if args.stats_events > 0:
+                line["yield"] = yield_(eng, args.events, args.stats_events)
+            eng.ctx.close()
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+            r = line["rates"]
+            cost = 1.0 / r["on"][0] - 1.0 / r["off"][0]
+            print(f"## {name} / {mode}: {r['rows_per_event']:.1f} trace rows per event", flush=True)
+            for leg in ("off", "on"):
+                print(f"  run_trace_rows(fetch=False), estimates {leg:3s} {r[leg][0]:12.0f} events/s  ({r[leg][1]:.0f} .. {r[leg][2]:.0f})")
+            print(f"  cost of the stage: {cost * 1e6:.3f} us per event, {100.0 * (1.0 - r['on'][0] / r['off'][0]):.1f} % of the stage-off rate")
+            for s, pos in enumerate(line.get("yield", {}).get("positions", [])):
+                shares = ", ".join(f"{k} {100 * v:.1f} %" for k, v in pos["status"].items())
+                print(f"  position {s} (nucleus {line['yield']['indices'][s]}): clean {100 * pos['clean']:.1f} %, estimated"
+                      f" {100 * pos['estimated']:.1f} %; {shares}")
+                for key in ("brho_rel", "polar", "radius_rel", "arc_over_2chord_to_mean"):
+                    if key in pos:
+                        print(f"    {key}: median {pos[key]['median']:+.4f}, 16 .. 84 % half-width {pos[key]['half_width_16_84']:.4f}")
+
+
+if __name__ == "__main__":
+    main()
