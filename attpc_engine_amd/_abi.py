@@ -182,6 +182,20 @@ EST_EMPTY, EST_FEW, EST_RANGE, EST_CAPPED, EST_NO_CIRCLE, EST_ON_AXIS, EST_NO_SL
 EST_MAX_FIT = 2048
 
 
+class ThinDesc(C.Structure):
+    _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
+
+
+class ThinInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_points", C.c_int32), ("n_dropped", C.c_int32), ("n_split", C.c_int32)]
+
+
+# attpc_thin_info as a numpy structured dtype
+THIN_INFO_DTYPE = np.dtype([(name, "<i4") for name, _ in ThinInfo._fields_], align=True)
+assert THIN_INFO_DTYPE.itemsize == C.sizeof(ThinInfo) == 16
+THIN_MAX_RUN = 4096
+
+
 class TraceGainDesc(C.Structure):
     _fields_ = [("rel_variance", C.c_double), ("pad_gain", _dp), ("quantiles", _dp), ("stream", C.c_uint32),
                 ("reserved", C.c_int32)]
@@ -378,6 +392,7 @@ EXPORTED_SYMBOLS = (
     "attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select",
     "attpc_maps_configure", "attpc_sim_run_maps", "attpc_det_run_maps", "attpc_cloud_maps",
     "attpc_trace_configure_estimates", "attpc_estimates_last", "attpc_rows_estimate",
+    "attpc_trace_configure_thinning", "attpc_rows_thin",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -413,6 +428,9 @@ MAPS_SYMBOLS = ("attpc_maps_configure", "attpc_sim_run_maps", "attpc_det_run_map
 
 # ... and the track estimates of the trace rows after the run maps: the same rule.
 ESTIMATE_SYMBOLS = ("attpc_trace_configure_estimates", "attpc_estimates_last", "attpc_rows_estimate")
+
+# ... and the thinned track points after the track estimates: the same rule.
+THIN_SYMBOLS = ("attpc_trace_configure_thinning", "attpc_rows_thin")
 
 _lib = None
 
@@ -589,6 +607,15 @@ def load_library() -> C.CDLL:
     for name, argtypes in estimates.items():
         if not no_estimates:
             getattr(lib, name).argtypes = argtypes
+    thinning = {
+        "attpc_trace_configure_thinning": [ctxp, C.POINTER(ThinDesc)],
+        "attpc_rows_thin": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(ThinDesc), C.c_int64, i64p, _dp,
+                            i64p, C.POINTER(ThinInfo), i64p],
+    }
+    no_thinning = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in THIN_SYMBOLS)
+    for name, argtypes in thinning.items():
+        if not no_thinning:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -613,7 +640,8 @@ def load_library() -> C.CDLL:
                 or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)
                 or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)
                 or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)
-                or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)):
+                or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)
+                or (no_thinning and name in THIN_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -623,7 +651,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates")
+                   "select", "maps", "estimates", "thinning")
 
 
 class Context:

@@ -37,6 +37,7 @@
 #include "unpack_host.hpp"
 #include "spyral_integral.hpp"  // (behind the HIP runtime header)
 #include "estimate_host.hpp"
+#include "thin_host.hpp"
 
 namespace {
 
@@ -95,6 +96,8 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf tg_records;           // trigger on (trigger.hip): the chunk's records, attpc_trigger_record [events]
   DevBuf tg_row_pass;          // ... with its gate, trace rows: fired of every kept trace row's event, uint8 [traces]
   DevBuf est_records;          // track estimates on (estimate.hip): the chunk's records, attpc_track_estimate [events][n_sim]
+  DevBuf thin_points;          // ... of thinned points (thin.hip): one ThinPoint per trace row (pk_cap)
+  DevBuf thin_info;            // ... and the attpc_thin_info of every (event, position)
   Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
   // packed traces (trace_pack.hip): the headers and record sizes of every kept trace row, their scanned byte offsets
   // (tp_block_*: the scan's scratch) and the records; the chunk's bytes in pinned memory (the host waits on `counted`)
@@ -235,6 +238,8 @@ struct attpc_ctx {
   Pinned<attpc_track_estimate> h_estimates;    // records of the last trace-row call, [events][n_sim] in its event order
   int64_t est_call_events = -1;    // events of that call, -1: it made no records (the stage was off, or there was no layout)
   int32_t est_call_n_sim = 0;      // positions of its layout
+  bool thinning_on = false;        // attpc_trace_configure_thinning (inert while the estimates are off)
+  attpc_thin_desc thinning{};
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -1038,11 +1043,16 @@ int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout
 
 // The track estimates of the chunk in `as` (n events, rows written: directly behind launch_peak_rows) on S, as.traced
 // recorded again behind them, and the copy of the records to events first_local .. of the call's pinned array on C.
+// With thinning on the rows are thinned first (thin.hip) and the estimates are those of the points.
 int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first_local) {
   const size_t n_sim = (size_t)ctx->est_call_n_sim;
   if (!n || !n_sim) return ATTPC_OK;
   int32_t rc;
   if ((rc = ensure(ctx, as.est_records, (size_t)n * n_sim * sizeof(attpc_track_estimate)))) return rc;
+  if (ctx->thinning_on) {  // (a point per trace row is room enough: pk_cap is what sp_rows holds)
+    if ((rc = ensure(ctx, as.thin_points, std::max<size_t>(as.pk_cap, 1) * sizeof(ThinPoint)))) return rc;
+    if ((rc = ensure(ctx, as.thin_info, (size_t)n * n_sim * sizeof(attpc_thin_info)))) return rc;
+  }
   EstimateArgs a{};
   estimate_settings(ctx->estimates, &a);
   a.ev_start = static_cast<const int64_t*>(as.pk_ev_start.p);
@@ -1051,7 +1061,24 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   a.records = static_cast<attpc_track_estimate*>(as.est_records.p);
   std::memcpy(a.slot_label, ctx->est_slot_label, sizeof a.slot_label);
   a.n_sim = (int32_t)n_sim;
-  launch_estimates(ctx->stream, n, a);
+  if (ctx->thinning_on) {
+    ThinArgs t{};
+    t.ev_start = a.ev_start;
+    t.rows = a.rows;
+    t.labels = a.labels;
+    t.points = static_cast<ThinPoint*>(as.thin_points.p);
+    t.info = static_cast<attpc_thin_info*>(as.thin_info.p);
+    std::memcpy(t.slot_label, a.slot_label, sizeof t.slot_label);
+    t.n_sim = a.n_sim;
+    t.step = thin_step_units(ctx->thinning.z_step);
+    launch_thin(ctx->stream, n, t);
+    HIP_TRY(ctx, hipGetLastError());
+    a.points = t.points;
+    a.thin_info = t.info;
+    launch_point_estimates(ctx->stream, n, a);
+  } else {
+    launch_estimates(ctx->stream, n, a);
+  }
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
@@ -3590,6 +3617,113 @@ int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* off
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     e0 = e1;
   }
+  return ATTPC_OK;
+}
+
+// ---- thinned track points (thin.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_thinning(attpc_ctx* ctx, const attpc_thin_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = thin_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "thinning: %s", bad);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  ctx->thinning_on = d != nullptr;
+  if (d) ctx->thinning = *d;
+  return ATTPC_OK;
+}
+
+int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                        const attpc_event_layout* layout, const attpc_thin_desc* d, int64_t capacity, int64_t* point_offsets,
+                        double* points, int64_t* point_labels, attpc_thin_info* info, int64_t* needed) {
+  if (!ctx || n_events < 0 || !d || !layout || capacity < 0 || !needed) return ATTPC_E_INVALID;
+  if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
+    return fail(ctx, ATTPC_E_INVALID, "attpc_rows_thin: n_sim %d outside 0 .. %d", layout->n_sim, ATTPC_MAX_SIM);
+  if (const char* bad = thin_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "thinning: %s", bad);
+  const size_t n_sim = (size_t)layout->n_sim;
+  if (!point_offsets || (n_events > 0 && (!offsets || (n_sim && !info)))) return ATTPC_E_INVALID;
+  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_rows_thin takes at most 2^31 - 1 events per call");
+  if (n_events > 0 && offsets[0] < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
+  for (int64_t e = 0; e < n_events; ++e) {
+    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %lld", (long long)e);
+    if (offsets[e + 1] - offsets[e] > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "event %lld has 2^31 rows or more", (long long)e);
+  }
+  if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !labels)) return ATTPC_E_INVALID;
+  if (capacity > 0 && (!points || !point_labels)) return ATTPC_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  *needed = 0;
+  point_offsets[0] = 0;
+  if (n_events == 0) return ATTPC_OK;
+  if (n_sim == 0) {
+    std::fill(point_offsets, point_offsets + n_events + 1, (int64_t)0);
+    return ATTPC_OK;
+  }
+  ThinArgs a{};
+  estimate_positions(*layout, a.slot_label);
+  a.n_sim = (int32_t)n_sim;
+  a.step = thin_step_units(d->z_step);
+  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
+  std::vector<int64_t> start;
+  std::vector<ThinPoint> sparse;  // the chunk's point buffer: the regions of its (event, position)s
+  int64_t total = 0;              // points so far
+  for (int64_t e0 = 0; e0 < n_events;) {
+    int64_t e1 = e0 + 1;
+    while (e1 < n_events && e1 - e0 < CHUNK_EVENTS && offsets[e1 + 1] - offsets[e0] <= CHUNK_ROWS) ++e1;
+    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
+    start.resize(m + 1);
+    for (size_t e = 0; e <= m; ++e) start[e] = offsets[e0 + (int64_t)e] - offsets[e0];
+    if ((rc = ensure(ctx, ctx->scratch[0], cap * 8 * sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[1], cap * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[2], (m + 1) * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[3], cap * sizeof(ThinPoint)))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch[4], m * n_sim * sizeof(attpc_thin_info)))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, start.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (n_rows) {
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, rows + offsets[e0] * 8, n_rows * 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, labels + offsets[e0], n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    a.ev_start = static_cast<const int64_t*>(ctx->scratch[2].p);
+    a.rows = static_cast<const double*>(ctx->scratch[0].p);
+    a.labels = static_cast<const int64_t*>(ctx->scratch[1].p);
+    a.points = static_cast<ThinPoint*>(ctx->scratch[3].p);
+    a.info = static_cast<attpc_thin_info*>(ctx->scratch[4].p);
+    launch_thin(ctx->stream, (uint32_t)m, a);
+    HIP_TRY(ctx, hipGetLastError());
+    sparse.resize(cap);
+    attpc_thin_info* chunk_info = info + (size_t)e0 * n_sim;
+    HIP_TRY(ctx, hipMemcpyAsync(chunk_info, ctx->scratch[4].p, m * n_sim * sizeof(attpc_thin_info), hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rows)
+      HIP_TRY(ctx, hipMemcpyAsync(sparse.data(), ctx->scratch[3].p, n_rows * sizeof(ThinPoint), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // the regions -> CSR, position-major per event
+    for (size_t e = 0; e < m; ++e) {
+      int64_t region = start[e];
+      for (size_t s = 0; s < n_sim; ++s) {
+        const attpc_thin_info& i = chunk_info[e * n_sim + s];
+        for (int32_t k = 0; k < i.n_points; ++k, ++total) {
+          if (total >= capacity) continue;
+          const ThinPoint& p = sparse[(size_t)region + (size_t)k];
+          double* row = points + total * 8;
+          row[0] = (double)p.X / 16.0;
+          row[1] = (double)p.Y / 16.0;
+          row[2] = (double)p.Z / 16.0;
+          row[3] = p.amplitude;
+          row[4] = (double)p.si;
+          row[5] = (double)p.n;
+          row[6] = (double)p.bin;
+          row[7] = (double)p.split;
+          point_labels[total] = layout->indices[s];
+        }
+        region += i.n_rows;
+      }
+      point_offsets[e0 + (int64_t)e + 1] = total;
+    }
+    e0 = e1;
+  }
+  *needed = total;
+  if (total > capacity)
+    return fail(ctx, ATTPC_E_CAPACITY, "attpc_rows_thin: %lld points, capacity %lld", (long long)total, (long long)capacity);
   return ATTPC_OK;
 }
 

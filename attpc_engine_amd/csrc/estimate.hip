@@ -14,6 +14,10 @@
 //   fourteen sums of its own rows in registers; they are reduced over the wave once, with integer adds.
 // The second pass reads the rows of the first again (72 B per row of the label, out of L2).  All lanes evaluate the
 // closed form (it is wave-uniform); lane 0 stores the record.
+//
+// estimate_kernel<true> is the same body on thinned points (thin.hip, "thinned track points" in the header): the rows
+// of position s are the points of its region of the chunk's point buffer -- every one of them matches --, a point is
+// out of range at |SI| >= 2^31, and RANGE is set from the start if thinning dropped a row of the label.
 #include "tracks_args.hpp"
 
 #include "estimate_host.hpp"
@@ -31,9 +35,26 @@ struct EstRow {
   bool match, used, out_of_range;
 };
 
-// row r of the chunk for the label `target` (valid: r is a row of the event)
+// row r of the chunk for the label `target` (valid: r is a row of the event); POINTS: point r of the point buffer
+// (valid: r is a point of the position's region)
+template <bool POINTS>
 __device__ __forceinline__ EstRow est_row(const EstimateArgs& a, int64_t r, bool valid, int64_t target) {
   EstRow row{0, 0, 0, 0, false, false, false};
+  if constexpr (POINTS) {
+    row.match = valid;
+    if (valid) {
+      const ThinPoint p = a.points[r];
+      // (estimate_quantise of the point row: the coordinates are in range by construction, SI is an integer)
+      const bool ok = p.si > -2147483648ll && p.si < 2147483648ll;
+      row.X = ok ? p.X : 0;
+      row.Y = ok ? p.Y : 0;
+      row.Z = ok ? p.Z : 0;
+      row.I = ok ? p.si : 0;
+      row.out_of_range = !ok;
+      row.used = ok && (int64_t)row.X * row.X + (int64_t)row.Y * row.Y >= a.rb2;
+    }
+    return row;
+  }
   row.match = valid && a.labels[r] == target;
   if (row.match) {
     const double* p = a.rows + r * 8;
@@ -42,6 +63,23 @@ __device__ __forceinline__ EstRow est_row(const EstimateArgs& a, int64_t r, bool
     row.used = ok && (int64_t)row.X * row.X + (int64_t)row.Y * row.Y >= a.rb2;
   }
   return row;
+}
+
+struct EstSpan {
+  int64_t lo, hi;  // the rows to walk
+  bool range;      // RANGE is set before any of them is read
+};
+
+// the event's rows; POINTS: the region of position s, behind the rows of the labels of the positions below it
+template <bool POINTS>
+__device__ __forceinline__ EstSpan est_span(const EstimateArgs& a, uint32_t e, int s, int64_t ev_lo, int64_t ev_hi) {
+  if constexpr (POINTS) {
+    const attpc_thin_info* info = a.thin_info + (size_t)e * (size_t)a.n_sim;
+    int64_t lo = ev_lo;
+    for (int t = 0; t < s; ++t) lo += info[t].n_rows;
+    return EstSpan{lo, lo + info[s].n_points, info[s].n_dropped != 0};
+  }
+  return EstSpan{ev_lo, ev_hi, false};
 }
 
 __device__ __forceinline__ int64_t est_wave_add(int64_t v) {
@@ -60,10 +98,11 @@ __device__ __forceinline__ int32_t est_wave_inclusive(int32_t v, int lane) {
 
 }  // namespace
 
+template <bool POINTS>
 __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
   const uint32_t e = blockIdx.x;
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  const int64_t lo = a.ev_start[e], hi = a.ev_start[e + 1];
+  const int64_t ev_lo = a.ev_start[e], ev_hi = a.ev_start[e + 1];
   const uint64_t below = (1ull << lane) - 1ull;  // the lanes below this one
   for (int s = wave; s < a.n_sim; s += EST_WAVES) {
     attpc_track_estimate rec;
@@ -71,12 +110,14 @@ __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
     const int64_t target = a.slot_label[s];
     // ---- pass A: counts, the first and last used row ----
     int32_t n_rows = 0, n_used = 0;
-    bool range = false;
+    const EstSpan span = est_span<POINTS>(a, e, s, ev_lo, ev_hi);
+    const int64_t lo = span.lo, hi = span.hi;
+    bool range = span.range;
     int64_t first = -1, last = -1;
     int32_t rho_first = 0, rho_last = 0;  // X^2 + Y^2 <= 2 * 5120^2
     if (target >= 0) {
       for (int64_t base = lo; base < hi; base += 64) {
-        const EstRow row = est_row(a, base + lane, base + lane < hi, target);
+        const EstRow row = est_row<POINTS>(a, base + lane, base + lane < hi, target);
         const uint64_t bm = __ballot(row.match), bu = __ballot(row.used);
         if (bm == 0ull) continue;
         n_rows += __popcll(bm);
@@ -105,14 +146,14 @@ __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
     // ---- pass B: the segment's sums ----
     const int64_t n = hi - lo;
     const int64_t q0 = direction > 0 ? first - lo : hi - 1 - last;  // the start row: rank 0, lane 0 of the first tile
-    const EstRow origin = est_row(a, direction > 0 ? first : last, true, target);
+    const EstRow origin = est_row<POINTS>(a, direction > 0 ? first : last, true, target);
     int64_t su = 0, sv = 0, suu = 0, suv = 0, svv = 0, suuu = 0, suvv = 0, svvv = 0, svuu = 0;
     int64_t ss = 0, sw = 0, sss = 0, ssw = 0, si = 0;
     int32_t count = 0, arc = 0;                  // segment rows so far, S of the last of them
     int32_t prev_x = origin.X, prev_y = origin.Y;  // (X, Y) of the last of them
     for (int64_t qb = q0; qb < n && count < m; qb += 64) {
       const int64_t q = qb + lane;
-      const EstRow row = est_row(a, direction > 0 ? lo + q : hi - 1 - q, q < n, target);
+      const EstRow row = est_row<POINTS>(a, direction > 0 ? lo + q : hi - 1 - q, q < n, target);
       const uint64_t bu = __ballot(row.used);
       if (bu == 0ull) continue;
       const bool seg = row.used && count + __popcll(bu & below) < m;
@@ -178,7 +219,11 @@ __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
 }
 
 void launch_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a) {
-  hipLaunchKernelGGL(estimate_kernel, dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  hipLaunchKernelGGL(estimate_kernel<false>, dim3(n_events), dim3(EST_THREADS), 0, s, a);
+}
+
+void launch_point_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a) {
+  hipLaunchKernelGGL(estimate_kernel<true>, dim3(n_events), dim3(EST_THREADS), 0, s, a);
 }
 
 }  // namespace attpc

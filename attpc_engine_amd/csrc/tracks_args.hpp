@@ -225,6 +225,16 @@ struct TriggerArgs {
 // one workgroup per event, empty events included
 void launch_trigger(hipStream_t s, uint32_t n_events, const TriggerArgs& a);
 
+// one thinned track point (thin.hip writes them, estimate.hip reads them)
+struct ThinPoint {  // what the estimator reads first, then what attpc_rows_thin delivers
+  int32_t X, Y, Z;   // C(Sx), C(Sy), C(Sz) in units
+  int32_t n;
+  int64_t si;
+  double amplitude;
+  int32_t bin;
+  int32_t split;
+};  // 40 bytes
+
 // track estimates of the trace rows (estimate.hip; attpc_trace_configure_estimates, the contract is in
 // include/attpc_engine.h)
 struct EstimateArgs {
@@ -237,9 +247,29 @@ struct EstimateArgs {
   int32_t min_points;
   int64_t rb2;                      // Rb^2 in units^2
   double magnetic_field;
+  // the estimates of thinned points (launch_point_estimates) read these in the place of rows and labels
+  const ThinPoint* points;            // [rows] the regions thin_kernel filled
+  const attpc_thin_info* thin_info;   // [n_events][n_sim]
 };
 // one workgroup per event, empty events included (n_events > 0, n_sim > 0)
 void launch_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a);
+// the same on the thinned points of every (event, position): a.points and a.thin_info as launch_thin left them
+void launch_point_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a);
+
+// thinned track points (thin.hip; attpc_trace_configure_thinning, the contract is in include/attpc_engine.h)
+struct ThinArgs {
+  const int64_t* ev_start;          // [n_events + 1] CSR offsets of the events' rows
+  const double* rows;               // [rows][8]
+  const int64_t* labels;            // [rows]
+  ThinPoint* points;                // [rows]: the region of (e, s) starts at ev_start[e] + the rows of the labels of the
+                                    // positions below s and holds info[e][s].n_points points
+  attpc_thin_info* info;            // [n_events][n_sim]
+  int64_t slot_label[ATTPC_MAX_SIM];  // as EstimateArgs
+  int32_t n_sim;
+  int32_t step;                     // H in units
+};
+// one workgroup per event, empty events included (n_events > 0, n_sim > 0)
+void launch_thin(hipStream_t s, uint32_t n_events, const ThinArgs& a);
 
 // packed pad traces (trace_pack.hip; the format "for64-bitplane-v1" is in include/attpc_engine.h).  samples
 // [n_rows][512] as the trace write pass left them, n_rows > 0; `workgroups` = trace_pack_workgroups(n_rows, limit).

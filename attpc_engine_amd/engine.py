@@ -18,6 +18,7 @@ from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings
                               configure_baseline, configure_common_mode, configure_gain, configure_peaks, configure_traces,
                               configure_trigger, trigger_result)
 from .detector.estimate import EstimateSettings, configure_estimates, estimates_result
+from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -265,7 +266,8 @@ class Engine:
         Both: ``trace_rows`` = {n_rows, row_checksum}, the cloud's ``stats`` (``n_points`` = the rows) and, with a
         trigger configured (``configure_trigger``), its records [n] under ``trigger`` (with its ``gate`` an event that
         did not fire is an empty range of the offsets); with the track estimates configured (``configure_estimates``)
-        their records [n, n_sim] under ``estimates``."""
+        their records [n, n_sim] under ``estimates`` -- with the thinning configured too (``configure_thinning``) those
+        of the thinned points, and its z step under ``thinning``."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         self._trace_rows_defaults()
         ctx = self.ctx
@@ -274,12 +276,12 @@ class Engine:
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
-                    **estimates_result(ctx, n_events, len(self.indices))}
+                    **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
-                **estimates_result(ctx, n_events, len(self.indices))}
+                **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx)}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -289,6 +291,14 @@ class Engine:
         the path, vertex and dE/dx of every simulated nucleus, made on the device from its trace rows; the field is the
         config's --, neither turns them off (the default).  The writers do not store the records."""
         configure_estimates(self.ctx, _settings(EstimateSettings, estimates, parameters), self.config)
+
+    def configure_thinning(self, thinning=None, **parameters) -> None:
+        """Thinning in front of the track estimates (include/attpc_engine.h, "thinned track points"): a
+        ``detector.thinning.ThinSettings`` or its keyword (z_step in mm, default 5) turns it on -- the estimates of
+        ``run_trace_rows`` / ``run_estimates`` are then made of one charge-weighted centroid per z bin of every track,
+        not of its raw rows, and ``min_points`` counts those points --, neither turns it off (the default).  Without
+        the estimates it does nothing."""
+        configure_thinning(self.ctx, _settings(ThinSettings, thinning, parameters))
 
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
@@ -309,7 +319,7 @@ class Engine:
                                                    out, stats), "attpc_sim_run_trace_rows")
         return {"estimates": ctx.estimates_last(n_events, len(self.indices)), "indices": list(self.indices),
                 "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
-                "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events)}
+                "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

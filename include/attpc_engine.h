@@ -1311,6 +1311,70 @@ ATTPC_API int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const in
                                       const int64_t* labels, const attpc_event_layout* layout,
                                       const attpc_estimate_desc* desc, attpc_track_estimate* out);
 
+/* ---- thinned track points (opt-in: off by default, and with it off every output, kernel and buffer of every entry
+ * point is what it is without this section; the entry points are additions under ABI version 3) ----
+ * A track lights several neighbouring pads at every z, so its labelled trace rows form a band, not a line: the
+ * cumulated pad-plane distance of the estimates zig-zags across it and their unweighted circle shrinks.  Thinning
+ * reduces every track's rows to ONE charge-weighted centroid per z bin, on the device and in exact integer arithmetic,
+ * in front of the estimates.  tests/thin_reference.py restates this contract in numpy.  A "unit" is 1/16 mm, as above.
+ * Settings (attpc_thin_desc): z_step in mm, finite, 1/16 <= z_step <= 512; reserved = pad = 0.
+ * H = rint(16 z_step), an integer in 1 .. 8192.
+ * For event e and position s of layout->indices the event's rows in their delivered order whose label equals
+ * indices[s] take part.  A label given twice goes to its FIRST position only; label -1 and labels that are not in
+ * indices take no part.
+ *   1. Quantise exactly as step 1 of the estimates (the same code): X, Y, Z, I.  A row that is out of range there is
+ *      DROPPED and counted in n_dropped.
+ *   2. bin = floor(Z / H) (floor also for negative Z: -1 / H is bin -1), weight w = max(I, 1).
+ *   3. A POINT is a maximal run of consecutive participating rows (the dropped ones taken out) of equal bin.  Delivered
+ *      rows are in ascending z, so a bin's rows are one run; the rule is on consecutive rows and assumes no order:
+ *      unsorted rows simply make more points.  A run is cut after 4096 rows: if the next participating row has the same
+ *      bin it starts a new point (a SPLIT), the point in front of it has column 7 = 1, and every point that ends or
+ *      begins at a split counts once in n_split (a bin of 4097 rows: 2, of 8193 rows: 3).  A run of exactly 4096 rows
+ *      that a change of bin ends is no split.
+ *   4. Sums of a point, 64-bit integers: W = sum w, Sx = sum w X, Sy = sum w Y, Sz = sum w Z, SI = sum I, n = rows;
+ *      amplitude = fmax over column 3 of its rows, NaN ignored (NaN if every one is).
+ *   5. Bounds: w < 2^31, |X|, |Y| <= 5120, |Z| <= 2^17 and n <= 4096, so |Sz| < 2^31 2^17 2^12 = 2^60 (|Sx|, |Sy| less),
+ *      |2 Sz + W| < 2^62 and 0 < W < 2^43, |SI| < 2^43.  Nothing can overflow: the sums are exact and independent of the
+ *      order of summation.
+ *   6. Centroid, integers only: C(S) = floor_div(2 S + W, 2 W) -- S / W to the nearest integer, a tie upwards, floor
+ *      semantics for a negative numerator.  The point is (C(Sx), C(Sy), C(Sz), SI); |C(Sx)| <= 5120, |C(Sz)| <= 2^17.
+ * Point row [8]: x = C(Sx) / 16, y = C(Sy) / 16, z = C(Sz) / 16 (exact), amplitude, SI, n, bin, 1 if a split closed it
+ * else 0.  Such rows are valid input of attpc_rows_estimate as they are (quantising them gives C(Sx), C(Sy), C(Sz) and
+ * SI back; a point with |SI| >= 2^31 is out of range by the rule there), and the fused stage is DEFINED by that:
+ * with thinning and the estimates both on, the records of attpc_estimates_last are exactly the records the estimate
+ * contract gives on the event's point rows with their labels -- n_rows counts the label's points, n_used the used
+ * points, min_points counts points -- with ATTPC_EST_RANGE OR-ed in if thinning dropped a row of the label. */
+typedef struct attpc_thin_desc {
+  double z_step;     /* mm, 1/16 .. 512 */
+  int32_t reserved;  /* 0 */
+  int32_t pad;       /* 0 */
+} attpc_thin_desc;
+
+typedef struct attpc_thin_info {
+  int32_t n_rows;     /* rows of the label, dropped ones included */
+  int32_t n_points;
+  int32_t n_dropped;
+  int32_t n_split;
+} attpc_thin_info;  /* 16 bytes */
+
+#define ATTPC_THIN_MAX_RUN 4096
+
+/* desc == NULL turns the stage off (the default).  Independent of every other configure call.  ATTPC_E_INVALID outside
+ * the ranges above, NaN included.  Takes effect only in the trace-row calls in which the estimates are on: every chunk's
+ * rows are then thinned right behind the kernel that writes them and the estimates are made of the points.  Alone it is
+ * inert: no kernel, no buffer.  The trace rows, labels, offsets and checksums of the call do not change. */
+ATTPC_API int32_t attpc_trace_configure_thinning(attpc_ctx* ctx, const attpc_thin_desc* desc);
+/* The stage alone on any host rows in CSR form, through the same kernel: offsets [n_events + 1], rows [R][8], labels
+ * [R] -> point_offsets [n_events + 1], points [P][8], point_labels [P] (= indices[s]) and info [n_events][n_sim].  Per
+ * event the points come position-major (s ascending) and in run order inside a position.  P <= R always, so capacity
+ * = R cannot fail; capacity < P gives ATTPC_E_CAPACITY with *needed = P (point_offsets and info are complete then, the
+ * points are not).  Needs no other configure call and leaves the configured stage as it is.  ATTPC_E_INVALID as
+ * attpc_rows_estimate. */
+ATTPC_API int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                  const int64_t* labels, const attpc_event_layout* layout, const attpc_thin_desc* desc,
+                                  int64_t capacity, int64_t* point_offsets, double* points, int64_t* point_labels,
+                                  attpc_thin_info* info, int64_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

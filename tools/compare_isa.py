@@ -1,9 +1,10 @@
 """Kernel-by-kernel comparison of the gfx950 code of two library builds (no GPU needed):
-    python tools/compare_isa.py before.so after.so
+    python tools/compare_isa.py before.so after.so [old=new ...]
 Per kernel: are the instruction texts (addresses stripped) identical, or at least the mnemonic sequences, and the
 resources of the code-object notes (VGPRs, SGPRs, LDS bytes, private_segment_fixed_size); for every kernel, whether each
 barrier waits for the wave's LDS operations (tests/isa_tools.py).  Kernels are matched by name without namespace and
-argument list.  Prints a markdown table."""
+argument list; ``old=new`` (e.g. ``'estimate_kernel=estimate_kernel<0>'``) compares the kernel ``old`` of before.so with
+``new`` of after.so, for a kernel that became an instantiation of a template.  Prints a markdown table."""
 import re
 import subprocess
 import sys
@@ -56,6 +57,8 @@ def text_of(insns: list) -> list:
 
 def main() -> None:
     before, after = kernels_of(Path(sys.argv[1])), kernels_of(Path(sys.argv[2]))
+    for old, new in (arg.split("=", 1) for arg in sys.argv[3:]):
+        before[new] = before.pop(old)
     print("| kernel | text | mnemonics | instructions | VGPR | SGPR | LDS | scratch | bare barriers |")
     print("|---|---|---|---|---|---|---|---|---|")
     for name in sorted(set(before) | set(after)):

@@ -11,10 +11,16 @@ bit, and for the tracks with B rho and slope the median and the 16 .. 84 % half-
 polar - polar_true against ``truth_tracks`` of the same call -- and, to tell the two factors of B rho apart, of
 radius / radius_true - 1 and of the cumulated distance over twice the chord vertex -> segment mean (1 for a thin
 straight segment; the zig-zag of neighbouring pads raises it).  Reported values for the settings used, no limits.
+Thinning (attpc_trace_configure_thinning): ``--thinning Z`` times the estimates without and with
+thinning at a z step of Z mm in the place of stage off / on (both legs have the estimates on, ``--min-points`` points),
+and ``--thin-steps 2,5,10`` repeats the yield at these steps beside the unthinned one.  ``--estimates-only`` times the
+estimates leg alone: what a library without the thinning entry points (``ATTPC_HIP_LIBRARY``, a build of the parent
+commit by tools/build_variant.sh) can run, to set beside the same leg of this build in the same session.
 ``--profile WORKLOAD`` runs two ``run_estimates`` calls in partial readout and nothing else, for
 ``rocprofv3 --kernel-trace --stats -- python tools/estimate_rate.py --profile o16aa`` (a run of its own).
 
     python tools/estimate_rate.py [--events N] [--reps K] [--stats-events M] [--workloads o16aa,be10dp] [--out FILE]
+                                  [--thinning Z | --estimates-only] [--thin-steps 2,5,10] [--min-points P]
 """
 from __future__ import annotations
 
@@ -73,22 +79,55 @@ def rates(eng, events: int, reps: int) -> dict:
     return {"rows_per_event": rows / events, **{k: [_median(v), min(v), max(v)] for k, v in legs.items()}}
 
 
-def yield_(eng, events: int, total: int) -> dict:
+def thinning_rates(eng, events: int, reps: int, z_step, min_points: int) -> dict:
+    """The estimates alone against the estimates of thinned points (``z_step`` None: the first leg only)."""
+    from attpc_engine_amd.detector.estimate import EstimateSettings
+
+    kinds = ("estimates",) if z_step is None else ("estimates", "thinned")
+    legs = {kind: [] for kind in kinds}
+    eng.configure_estimates(EstimateSettings(min_points=min_points))
+
+    def call(kind: str):
+        if z_step is not None:
+            eng.configure_thinning(**({"z_step": z_step} if kind == "thinned" else {}))
+        t0 = time.perf_counter()
+        res = eng.run_trace_rows(events, seed=1, fetch=False)
+        return events / (time.perf_counter() - t0), res
+
+    for kind in kinds:
+        call(kind)
+    rows = 0
+    for _ in range(reps):
+        for kind in kinds:
+            rate, res = call(kind)
+            legs[kind].append(rate)
+            rows = res["trace_rows"]["n_rows"]
+    eng.configure_estimates()
+    if z_step is not None:
+        eng.configure_thinning()
+    return {"rows_per_event": rows / events, **{k: [_median(v), min(v), max(v)] for k, v in legs.items()}}
+
+
+def yield_(eng, events: int, total: int, z_step=None, min_points: int = 30) -> dict:
     import numpy as np
 
     from attpc_engine_amd.detector.estimate import STATUS_BITS, EstimateSettings, polar, truth_tracks
 
-    eng.configure_estimates(EstimateSettings())
+    eng.configure_estimates(EstimateSettings(min_points=min_points))
+    if z_step is not None:
+        eng.configure_thinning(z_step=z_step)
     est, truth = [], []
     for first in range(0, total, events):
         res = eng.run_estimates(min(events, total - first), seed=1, first_event=first)
         est.append(res["estimates"])
         truth.append(truth_tracks(res["p4"], res["indices"], eng.z))
     eng.configure_estimates()
+    if z_step is not None:
+        eng.configure_thinning()
     est = np.concatenate(est)
     field = float(eng.config.det_params.bfield)
     truth = {k: np.concatenate([t[k] for t in truth]) for k in truth[0]}
-    out = {"tracks": int(est.size), "indices": list(eng.indices), "positions": []}
+    out = {"tracks": int(est.size), "indices": list(eng.indices), "z_step": z_step, "min_points": min_points, "positions": []}
     for s in range(est.shape[1]):
         e = est[:, s]
         pos = {"status": {name: float((e["status"] & bit != 0).mean()) for name, bit in STATUS_BITS.items()},
@@ -110,11 +149,51 @@ def yield_(eng, events: int, total: int) -> dict:
     return out
 
 
-def profile(name: str, events: int) -> None:
+def _print_yield(y: dict) -> None:
+    for s, pos in enumerate(y["positions"]):
+        shares = ", ".join(f"{k} {100 * v:.1f} %" for k, v in pos["status"].items())
+        print(f"  position {s} (nucleus {y['indices'][s]}): clean {100 * pos['clean']:.1f} %, estimated"
+              f" {100 * pos['estimated']:.1f} %; {shares}")
+        for key in ("brho_rel", "polar", "radius_rel", "arc_over_2chord_to_mean"):
+            if key in pos:
+                print(f"    {key}: median {pos[key]['median']:+.4f}, 16 .. 84 % half-width {pos[key]['half_width_16_84']:.4f}")
+
+
+def thinning_main(args) -> None:
+    steps = [float(z) for z in args.thin_steps.split(",") if z]
+    for name in args.workloads.split(","):
+        for mode in MODES:
+            eng = _engine(name, mode)
+            line = {"workload": name, "mode": mode, "events": args.events, "min_points": args.min_points}
+            if args.reps > 0:
+                r = line["rates"] = thinning_rates(eng, args.events, args.reps, args.thinning, args.min_points)
+                print(f"## {name} / {mode}: {r['rows_per_event']:.1f} trace rows per event, min_points {args.min_points}", flush=True)
+                for leg in ("estimates", "thinned"):
+                    if leg in r:
+                        print(f"  run_trace_rows(fetch=False), {leg:9s} {r[leg][0]:12.0f} events/s  ({r[leg][1]:.0f} .. {r[leg][2]:.0f})")
+                if "thinned" in r:
+                    cost = 1.0 / r["thinned"][0] - 1.0 / r["estimates"][0]
+                    print(f"  cost of thinning at {args.thinning} mm: {cost * 1e9:.0f} ns per event, "
+                          f"{100.0 * (1.0 - r['thinned'][0] / r['estimates'][0]):.2f} % of the rate without it")
+            line["yield"] = []
+            for z_step in ([None] + steps if steps and args.stats_events > 0 else []):
+                y = yield_(eng, args.events, args.stats_events, z_step, args.min_points)
+                line["yield"].append(y)
+                print(f"## {name} / {mode}: records of {args.stats_events} events, " + ("raw rows" if z_step is None else f"z step {z_step} mm"), flush=True)
+                _print_yield(y)
+            eng.ctx.close()
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+
+
+def profile(name: str, events: int, z_step=None, min_points: int = 30) -> None:
     from attpc_engine_amd.detector.estimate import EstimateSettings
 
     eng = _engine(name, "partial")
-    eng.configure_estimates(EstimateSettings())
+    eng.configure_estimates(EstimateSettings(min_points=min_points))
+    if z_step is not None:
+        eng.configure_thinning(z_step=z_step)
     eng.run_estimates(events, seed=1)
     eng.run_estimates(events, seed=1)
 
@@ -127,9 +206,15 @@ def main() -> None:
     ap.add_argument("--stats-events", type=int, default=100000)
     ap.add_argument("--workloads", default="o16aa,be10dp")
     ap.add_argument("--out")
+    ap.add_argument("--thinning", type=float)
+    ap.add_argument("--estimates-only", action="store_true")
+    ap.add_argument("--thin-steps", default="")
+    ap.add_argument("--min-points", type=int, default=30)
     args = ap.parse_args()
     if args.profile:
-        return profile(args.profile, args.events)
+        return profile(args.profile, args.events, args.thinning, args.min_points)
+    if args.thinning is not None or args.estimates_only or args.thin_steps:
+        return thinning_main(args)
     for name in args.workloads.split(","):
         for mode in MODES:
             eng = _engine(name, mode)
@@ -146,13 +231,8 @@ def main() -> None:
             for leg in ("off", "on"):
                 print(f"  run_trace_rows(fetch=False), estimates {leg:3s} {r[leg][0]:12.0f} events/s  ({r[leg][1]:.0f} .. {r[leg][2]:.0f})")
             print(f"  cost of the stage: {cost * 1e6:.3f} us per event, {100.0 * (1.0 - r['on'][0] / r['off'][0]):.1f} % of the stage-off rate")
-            for s, pos in enumerate(line.get("yield", {}).get("positions", [])):
-                shares = ", ".join(f"{k} {100 * v:.1f} %" for k, v in pos["status"].items())
-                print(f"  position {s} (nucleus {line['yield']['indices'][s]}): clean {100 * pos['clean']:.1f} %, estimated"
-                      f" {100 * pos['estimated']:.1f} %; {shares}")
-                for key in ("brho_rel", "polar", "radius_rel", "arc_over_2chord_to_mean"):
-                    if key in pos:
-                        print(f"    {key}: median {pos[key]['median']:+.4f}, 16 .. 84 % half-width {pos[key]['half_width_16_84']:.4f}")
+            if "yield" in line:
+                _print_yield(line["yield"])
 
 
 if __name__ == "__main__":
