@@ -153,6 +153,7 @@ struct attpc_ctx {
   int opt_track_blocks_per_cu = 8; // track_kernel workgroups (256 threads) launched per CU at most
   int opt_serial_tracks = -1;      // -1 automatic (see pick_track_stream), 0 beside the scatter launches, 1 behind them
   int opt_trace_pack_workgroups = 0;  // workgroups of the trace pack kernels at most; 0: 8 per CU
+  int opt_track_workgroups = 0;    // > 0: track_kernel workgroups at most (test hook: few waves, many tracks per lane)
 
   bool kin_ready = false;
   attpc_kin_desc kin{};            // device pointers inside
@@ -492,7 +493,8 @@ int32_t launch_tracks(attpc_ctx* ctx, TrackSet& ts, const TrackLaunch& tl) {
     if ((rc = ensure(ctx, ts.n_steps, alloc_tracks * sizeof(int32_t)))) return rc;
     const size_t lds = (size_t)ctx->det.n_species * ATTPC_DEDX_NODES * sizeof(double);
     const uint32_t waves_needed = (n_tracks + 63) / 64;
-    const uint32_t blocks = std::min<uint32_t>((waves_needed + 3) / 4, (uint32_t)ctx->n_cus * (uint32_t)ctx->opt_track_blocks_per_cu);
+    uint32_t blocks = std::min<uint32_t>((waves_needed + 3) / 4, (uint32_t)ctx->n_cus * (uint32_t)ctx->opt_track_blocks_per_cu);
+    if (ctx->opt_track_workgroups > 0) blocks = std::min<uint32_t>(blocks, (uint32_t)ctx->opt_track_workgroups);
     // every wave reserves arena blocks 64 at a time: that slack comes on top of what the samples need
     // keep the arena while it covers the observed need with 3 % to spare, grow it by 25 % when it does not:
     // the need per track moves by fractions of a percent from batch to batch, and re-allocating tens of GB
@@ -2330,6 +2332,9 @@ int32_t attpc_set_option(attpc_ctx* ctx, const char* name, int64_t value) {
   } else if (key == "trace_pack_workgroups") {
     if (value < 0 || value > 65536) return fail(ctx, ATTPC_E_INVALID, "trace_pack_workgroups must be 0..65536");
     ctx->opt_trace_pack_workgroups = (int)value;
+  } else if (key == "track_workgroups") {
+    if (value < 0 || value > 65536) return fail(ctx, ATTPC_E_INVALID, "track_workgroups must be 0..65536");
+    ctx->opt_track_workgroups = (int)value;
   } else if (key == "chunk_events") {
     return attpc_set_chunk_events(ctx, (int32_t)value);
   } else {
@@ -3839,10 +3844,16 @@ int32_t attpc_det_tracks(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, ui
     // TRK_NEXT_BLOCK counts reserved blocks (waves reserve pools), all below arena_blocks after a good run
     std::vector<double> arena(std::min<size_t>(ts.h_ctrl[TRK_NEXT_BLOCK], ts.arena_blocks) * ARENA_BLK * 4);
     if (!arena.empty()) HIP_TRY(ctx, hipMemcpy(arena.data(), ts.arena.p, arena.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t n_blocks = arena.size() / ((size_t)ARENA_BLK * 4);
     for (uint32_t t = 0; t < n_tracks; ++t) {
+      // a track the kernel never ran leaves whatever its count and block entries held: an error, not a read past the copy
+      if (counts[t] < 0 || counts[t] > MAX_BLOCKS_PER_TRACK * ARENA_BLK)
+        return fail(ctx, ATTPC_E_DATALOSS, "attpc_det_tracks: track %u has %d samples (0..%d)", t, counts[t], MAX_BLOCKS_PER_TRACK * ARENA_BLK);
       const int64_t c = std::min<int64_t>(counts[t], max_samples_per_track);
       for (int64_t s = 0; s < c; ++s) {
         const int32_t blk = table[(size_t)t * MAX_BLOCKS_PER_TRACK + s / ARENA_BLK];
+        if (blk < 0 || (size_t)blk >= n_blocks)
+          return fail(ctx, ATTPC_E_DATALOSS, "attpc_det_tracks: track %u names arena block %d of %zu", t, blk, n_blocks);
         std::memcpy(samples + ((size_t)t * max_samples_per_track + s) * 4,
                     arena.data() + ((size_t)blk * ARENA_BLK + (s % ARENA_BLK)) * 4, 4 * sizeof(double));
       }

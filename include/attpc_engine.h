@@ -251,6 +251,10 @@ ATTPC_API int32_t attpc_sync(attpc_ctx* ctx);
  *                      attpc_det_desc.path_step > 0, where samples are far closer than a pad)
  *   "trace_pack_workgroups"  workgroups (of four waves, one row a wave) the trace pack kernels are launched with at
  *                      most; 0 (default) = 8 per compute unit.  Scheduling only: results do not depend on it
+ *   "track_workgroups"  0..65536, workgroups (of four waves) the track kernel is launched with at most; 0 (default) =
+ *                      as many as the tracks need, up to "track_blocks_per_cu" per compute unit.  A test hook: with one
+ *                      workgroup a few hundred tracks make every lane take several tracks, and every wave several
+ *                      batches of track ids and pools of arena blocks.  Scheduling only: results do not depend on it
  *   "chunk_events"     as attpc_set_chunk_events */
 ATTPC_API int32_t attpc_set_option(attpc_ctx* ctx, const char* name, int64_t value);
 /* Page-locked host memory for output buffers (point clouds are PCIe bound on their way to the host:
@@ -343,7 +347,8 @@ ATTPC_API int32_t attpc_sim_hint_next(attpc_ctx* ctx, uint64_t seed, uint64_t fi
 /* Diagnostics used by the parity tests: one track per (event, simulated nucleus) of a
  * det_run-style input.  samples [n_tracks, ATTPC_TIME_SAMPLES, 4] rows (x m, y m,
  * time bucket, electrons*gain) of the samples with >= 1 electron; counts [n_tracks];
- * n_steps [n_tracks] = number of recorded ODE samples (rows of the reference's track). */
+ * n_steps [n_tracks] = number of recorded ODE samples (rows of the reference's track).  A track whose count or
+ * arena block lies outside the track buffers (a track the kernel never ran) is ATTPC_E_DATALOSS, not a copy. */
 ATTPC_API int32_t attpc_det_tracks(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                          const attpc_event_layout* layout, const double* p4,
                          const double* vertex, int64_t max_samples_per_track, double* samples,
