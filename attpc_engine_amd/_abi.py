@@ -302,6 +302,11 @@ class TracePackedOut(C.Structure):
     ]
 
 
+class StraggleDesc(C.Structure):  # attpc_straggle_desc
+    _fields_ = [("angular_scale", C.c_double), ("energy_scale", C.c_double), ("radiation_length", C.c_double),
+                ("electron_density", C.c_double), ("stream", C.c_uint32)]
+
+
 TRACE_PACK_FORMAT = "for64-bitplane-v1"  # ATTPC_TRACE_PACK_FORMAT
 TRACE_PACK_MAX_ROW_BYTES = 784
 
@@ -393,6 +398,7 @@ EXPORTED_SYMBOLS = (
     "attpc_maps_configure", "attpc_sim_run_maps", "attpc_det_run_maps", "attpc_cloud_maps",
     "attpc_trace_configure_estimates", "attpc_estimates_last", "attpc_rows_estimate",
     "attpc_trace_configure_thinning", "attpc_rows_thin",
+    "attpc_det_configure_straggling",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -431,6 +437,9 @@ ESTIMATE_SYMBOLS = ("attpc_trace_configure_estimates", "attpc_estimates_last", "
 
 # ... and the thinned track points after the track estimates: the same rule.
 THIN_SYMBOLS = ("attpc_trace_configure_thinning", "attpc_rows_thin")
+
+# ... and the track straggling after the thinned track points: the same rule.
+STRAGGLE_SYMBOLS = ("attpc_det_configure_straggling",)
 
 _lib = None
 
@@ -616,6 +625,9 @@ def load_library() -> C.CDLL:
     for name, argtypes in thinning.items():
         if not no_thinning:
             getattr(lib, name).argtypes = argtypes
+    no_straggling = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in STRAGGLE_SYMBOLS)
+    if not no_straggling:
+        lib.attpc_det_configure_straggling.argtypes = [ctxp, C.POINTER(StraggleDesc)]
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -641,7 +653,7 @@ def load_library() -> C.CDLL:
                 or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)
                 or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)
                 or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)
-                or (no_thinning and name in THIN_SYMBOLS)):
+                or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -651,7 +663,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning")
+                   "select", "maps", "estimates", "thinning", "straggling")
 
 
 class Context:

@@ -38,6 +38,7 @@
 #include "spyral_integral.hpp"  // (behind the HIP runtime header)
 #include "estimate_host.hpp"
 #include "thin_host.hpp"
+#include "straggle_host.hpp"
 
 namespace {
 
@@ -162,6 +163,8 @@ struct attpc_ctx {
   bool det_ready = false;
   DetDev det{};
   std::vector<void*> det_allocs;
+  bool straggle_on = false;        // attpc_det_configure_straggling (kept over attpc_det_configure)
+  attpc_straggle_desc straggle{};
 
   TrackSet tset[2];
   // cloud of one chunk
@@ -532,7 +535,7 @@ int32_t launch_tracks(attpc_ctx* ctx, TrackSet& ts, const TrackLaunch& tl) {
       if (!ctx->opt_track_species_major || n_sim <= 1) ta.sim_order[0] = 0xffu;
     }
     HIP_TRY(ctx, hipEventRecord(ts.t0, ctx->stream_t));
-    launch_track_kernel(blocks, lds, ctx->stream_t, ta);
+    launch_track_kernel(blocks, lds, ctx->stream_t, ta, ctx->straggle_on ? &ctx->straggle : nullptr);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ts.t1, ctx->stream_t));
   }
@@ -2605,6 +2608,21 @@ int32_t attpc_det_configure(attpc_ctx* ctx, const attpc_det_desc* d) {
   ctx->det_ready = true;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_t_own));  // (sync_all above covered stream_t, whichever it was)
   pick_track_stream(ctx);
+  return ATTPC_OK;
+}
+
+// ---- track straggling (tracks.hip, straggle_host.hpp; the contract is in include/attpc_engine.h) ----
+int32_t attpc_det_configure_straggling(attpc_ctx* ctx, const attpc_straggle_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d) {
+    const char* wrong = straggle_desc_error(*d);
+    if (wrong) return fail(ctx, ATTPC_E_INVALID, "attpc_det_configure_straggling: %s", wrong);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // (a track batch queued ahead of the next call was integrated under the old settings)
+  { int32_t rc0 = drop_prefetch(ctx); if (rc0) return rc0; }
+  ctx->straggle_on = d != nullptr;
+  ctx->straggle = d ? *d : attpc_straggle_desc{};
   return ATTPC_OK;
 }
 

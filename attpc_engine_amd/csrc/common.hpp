@@ -32,6 +32,13 @@ constexpr uint32_t DOMAIN_TRACE_COMMON = 0x20000000u; // | common-mode stream (<
 //  key words of Philox2x32)
 static_assert(0x200ull + (unsigned long long)ATTPC_MAX_SIM * ATTPC_TIME_SAMPLES * ATTPC_LONG_STEPS < DOMAIN_TRACE_COMMON,
               "DOMAIN_MC + entry stays below the trace domains");
+// track straggling (tracks.hip): + stream * 32 + row of the nucleus (stream < 2^16, row < 32); index = 2 * sample (the
+// direction's pair) and 2 * sample + 1 (the energy's).  Above everything DOMAIN_MC reaches, below the trace domains.
+constexpr uint32_t DOMAIN_STRAGGLE = 0x10000000u;
+static_assert(ATTPC_MAX_ROWS <= 32, "the row of a nucleus takes 5 bits of the straggling domain");
+static_assert(0x200ull + (unsigned long long)ATTPC_MAX_SIM * ATTPC_TIME_SAMPLES * ATTPC_LONG_STEPS <= DOMAIN_STRAGGLE &&
+                  DOMAIN_STRAGGLE + 65536ull * 32ull <= DOMAIN_TRACE_COMMON,
+              "the straggling domains lie between DOMAIN_MC + entry and the trace domains");
 constexpr uint32_t KIN_SLOTS = 64u;
 
 // Philox4x32-10 (Salmon et al. SC'11), the algorithm of rocRAND's default generator, written

@@ -17,7 +17,10 @@
 //
 // Bound: f64 VALU (about 2 rsqrt + 45 fma-class ops per right-hand side, 4 per step) plus one
 // Philox + Box-Muller per two ionising samples; HBM traffic is 32 B per kept sample.
+#include <type_traits>
+
 #include "tracks_args.hpp"
+#include "straggle_host.hpp"  // (behind the HIP runtime header)
 
 namespace attpc {
 
@@ -75,8 +78,22 @@ __device__ __forceinline__ void rhs(const double s[6], const Decomp& d, const Sp
 #ifndef ATTPC_TRACK_MIN_WAVES
 #define ATTPC_TRACK_MIN_WAVES 1  // waves per SIMD the register allocation must leave room for (experiments)
 #endif
-template <bool PATH>
-__global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_kernel(TrackArgs a) {
+//
+// STRAGGLE: the track straggling (include/attpc_engine.h, "track straggling"; the kick itself is straggle_host.hpp) --
+// again its own instantiations, with an argument block of their own, so that the two kernels of the stage off keep
+// their code, their registers and their kernel arguments.
+struct StraggleDev {
+  StraggleParams p;
+  uint32_t domain;  // DOMAIN_STRAGGLE + stream * 32
+};
+struct TrackArgsStraggle : TrackArgs {
+  StraggleDev sg;
+};
+template <bool STRAGGLE>
+using TrackKernelArgs = std::conditional_t<STRAGGLE, TrackArgsStraggle, TrackArgs>;
+
+template <bool PATH, bool STRAGGLE>
+__global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_kernel(TrackKernelArgs<STRAGGLE> a) {
   extern __shared__ double lds_tab[];  // [n_species][ATTPC_DEDX_NODES]
   const int n_tab = a.det.n_species * ATTPC_DEDX_NODES;
   for (int i = threadIdx.x; i < n_tab; i += TRACK_THREADS) lds_tab[i] = a.det.dedx[i];
@@ -99,6 +116,8 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
   double s[6] = {0, 0, 0, 0, 0, 0};
   Decomp dc = {0, 0, 0, 0};
   double g_ke = 0, g_zf = 0, g_zb = 0, g_rho = 0, ke_prev = 0;
+  double z_charge = 0.0;  // STRAGGLE: the charge number of the lane's nucleus ...
+  double ds_step = 0.0;   // ... and the length of the step to the sample in progress
   SpeciesConst sc = {0, 0, 0, 0};
   const double* tab = lds_tab;
   double z_cache_cos = 0.0, z_cache_sin = 0.0;  // the two Box-Muller normals of the cached Philox pair ...
@@ -173,6 +192,7 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
             sc.qm_e = q_m * (-a.det.efield) / C_LIGHT;
             sc.drag = MEV_2_JOULE * a.det.density * 100.0 / mass_kg / C_LIGHT;
             tab = lds_tab + sp * ATTPC_DEDX_NODES;
+            if constexpr (STRAGGLE) z_charge = (double)a.det.Z[sp];
             dc = decompose(s[3], s[4], s[5], mass);
             g_ke = dc.ke - KE_LIMIT;
             g_zf = s[2] - 1.0;
@@ -209,7 +229,10 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
           }
           t_now += h_sample;
           h = h_sample / (double)nsub;
+          if constexpr (STRAGGLE) ds_step = v * h_sample;  // (= straggle_step_length(gv2, h_sample))
         }
+      } else if constexpr (STRAGGLE) {
+        if (active) ds_step = straggle_step_length(s[3] * s[3] + s[4] * s[4] + s[5] * s[5], 1.0e-10);
       }
       if (active) {
         for (int sub = 0; sub < nsub && !stop; ++sub) {
@@ -241,6 +264,29 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
         }
         if (!stop) {
           k++;
+          if constexpr (STRAGGLE) {
+            // the kick of sample k, inside the lane's own active && !stop region: the draws are the lane's alone (no
+            // ballot, no shuffle), a part whose scale is 0 draws nothing (the scales are kernel arguments: uniform)
+            double n1 = 0.0, n2 = 0.0, n3 = 0.0, ua, ub;
+            const uint32_t domain = a.sg.domain + (fano_domain - DOMAIN_FANO0);  // + row
+            if (a.sg.p.angular_scale > 0.0) {
+              rng_pair(a.seed, event, 2u * (uint32_t)k, domain, ua, ub);
+              const double rad = sqrt(-2.0 * log(1.0 - ua));
+              double sn, cs;
+              sincos(TWO_PI * ub, &sn, &cs);
+              n1 = rad * cs;
+              n2 = rad * sn;
+            }
+            if (a.sg.p.energy_scale > 0.0) {
+              rng_pair(a.seed, event, 2u * (uint32_t)k + 1u, domain, ua, ub);
+              n3 = normal_from(ua, ub);
+            }
+            double g[3] = {s[3], s[4], s[5]};
+            const bool clamped = straggle_kick(g, sc.mass, z_charge, ds_step, n1, n2, n3, a.sg.p);
+            s[3] = g[0]; s[4] = g[1]; s[5] = g[2];
+            dc = decompose(s[3], s[4], s[5], sc.mass);
+            g_ke = clamped ? 0.0 : dc.ke - KE_LIMIT;  // (the other three event functions do not depend on g)
+          }
           // generate_electrons, solver.py:338-346: mu = |dKE| 1e6 / W, n = trunc(N(mu, sqrt(F mu)))
           const double mu = fabs(dc.ke - ke_prev) * e_scale;
           ke_prev = dc.ke;
@@ -337,11 +383,24 @@ __global__ __launch_bounds__(TRACK_THREADS, ATTPC_TRACK_MIN_WAVES) void track_ke
   }
 }
 
-void launch_track_kernel(uint32_t blocks, size_t lds_bytes, hipStream_t s, const TrackArgs& a) {
+void launch_track_kernel(uint32_t blocks, size_t lds_bytes, hipStream_t s, const TrackArgs& a,
+                         const attpc_straggle_desc* straggle) {
+  if (straggle != nullptr && (straggle->angular_scale > 0.0 || straggle->energy_scale > 0.0)) {
+    TrackArgsStraggle b;
+    static_cast<TrackArgs&>(b) = a;
+    b.sg.p = StraggleParams{straggle->angular_scale, straggle->energy_scale, straggle->radiation_length,
+                            straggle->electron_density};
+    b.sg.domain = DOMAIN_STRAGGLE + straggle->stream * 32u;
+    if (a.det.path_step > 0.0)
+      hipLaunchKernelGGL((track_kernel<true, true>), dim3(blocks), dim3(TRACK_THREADS), lds_bytes, s, b);
+    else
+      hipLaunchKernelGGL((track_kernel<false, true>), dim3(blocks), dim3(TRACK_THREADS), lds_bytes, s, b);
+    return;
+  }
   if (a.det.path_step > 0.0)
-    hipLaunchKernelGGL(track_kernel<true>, dim3(blocks), dim3(TRACK_THREADS), lds_bytes, s, a);
+    hipLaunchKernelGGL((track_kernel<true, false>), dim3(blocks), dim3(TRACK_THREADS), lds_bytes, s, a);
   else
-    hipLaunchKernelGGL(track_kernel<false>, dim3(blocks), dim3(TRACK_THREADS), lds_bytes, s, a);
+    hipLaunchKernelGGL((track_kernel<false, false>), dim3(blocks), dim3(TRACK_THREADS), lds_bytes, s, a);
 }
 
 }  // namespace attpc

@@ -46,7 +46,10 @@ void launch_kin_calculate(hipStream_t s, const attpc_kin_desc& d, uint32_t n, co
                           const double* th, const double* ph, double* p4, int32_t* status);
 void launch_decay_calculate(hipStream_t s, uint32_t n, const double* parent, double m1, double m2, const double* ex,
                             const double* th, const double* ph, double* out, int32_t* status);
-void launch_track_kernel(uint32_t blocks, size_t lds_bytes, hipStream_t s, const TrackArgs& a);
+// straggle (attpc_det_configure_straggling; nullptr or both scales 0: the kernels of the stage off): the track
+// straggling, track_kernel<*, true> with an argument block of its own (tracks.hip)
+void launch_track_kernel(uint32_t blocks, size_t lds_bytes, hipStream_t s, const TrackArgs& a,
+                         const attpc_straggle_desc* straggle = nullptr);
 // scatter.hip compiled as it is / through scatter_small.hip (workgroups per CU: 1 / 2)
 void launch_scatter_kernel_big(uint32_t n_workgroups, hipStream_t s, const ScatterArgs& a);
 void launch_scatter_kernel_small(uint32_t n_workgroups, hipStream_t s, const ScatterArgs& a);

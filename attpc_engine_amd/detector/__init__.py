@@ -4,6 +4,7 @@ from . import maps as _maps
 from . import parameters as _parameters
 from . import selection as _selection
 from . import simulator as _simulator
+from . import straggling as _straggling
 from . import summary as _summary
 from . import traces as _traces
 from . import writer as _writer
@@ -21,6 +22,7 @@ _EXPORTS = {
                "electrons_above_threshold"),
     _selection: ("Selection", "configure_selection", "simulate_batch_selected", "clouds_to_selection"),
     _maps: ("MapsSettings", "RunMaps", "configure_maps", "simulate_batch_maps", "clouds_to_maps"),
+    _straggling: ("StragglingSettings", "configure_straggling", "radiation_length", "electron_density"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

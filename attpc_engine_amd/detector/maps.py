@@ -128,14 +128,16 @@ def configure_maps(ctx: _abi.Context, maps: MapsSettings | None = None, **parame
 
 def simulate_batch_maps(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config, seed: int,
                         indices: list[int], maps: MapsSettings | None = None, selection=None, first_event: int = 0,
-                        ctx: _abi.Context | None = None, min_electrons: int | None = None) -> dict:
+                        ctx: _abi.Context | None = None, min_electrons: int | None = None, straggling=None) -> dict:
     """simulate() for n events with the clouds left on the device and accumulated there (``attpc_det_run_maps``; ``maps``
     default ``MapsSettings()``, with ``maps.selected`` the ``selection``) -> a dict: maps (``RunMaps``), events [n] and
     tracks [n, n_sim] (the records of all events, as ``simulate_batch_summary``), passed [n] bool (the events that
-    contributed), stats."""
+    contributed), stats.  ``straggling`` (a ``detector.straggling.StragglingSettings``; None = off): the track
+    straggling."""
     from .luts import build_layout, species_for
     from .selection import Selection, configure_selection
     from .simulator import configure_detector
+    from .straggling import configure_straggling
     from .summary import SummarySettings, configure_summary
 
     maps = MapsSettings() if maps is None else maps
@@ -153,6 +155,7 @@ def simulate_batch_maps(momenta: np.ndarray, vertices: np.ndarray, proton_number
     indices = list(indices)
     keys = species_for(proton_numbers, mass_numbers, indices)
     configure_detector(config, keys, ctx)
+    configure_straggling(ctx, straggling, config)
     configure_summary(config, ctx, min_electrons)
     if maps.selected:
         configure_selection(ctx, selection)

@@ -459,10 +459,12 @@ class TraceChain:
             configure_thinning(ctx, self.thinning)
 
     def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
-                  ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False):
+                  ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False,
+                  straggling=None):
         """simulate() + this chain on the device for n events: what ``simulate_batch_trace_rows`` (``rows``) or
         ``simulate_batch_traces`` returns (``capacity_per_event``: None = the default of that entry point; ``packed``:
-        the traces as packed records, ``attpc_det_run_traces_packed``)."""
+        the traces as packed records, ``attpc_det_run_traces_packed``; ``straggling``: the track straggling, a
+        ``detector.straggling.StragglingSettings`` or None = off)."""
         from .simulator import run_batch
 
         ctx = ctx or _abi.default_context()
@@ -481,7 +483,7 @@ class TraceChain:
         arrays, stats = run_batch("attpc_det_run_trace_rows" if rows else "attpc_det_run_traces_packed" if packed
                                   else "attpc_det_run_traces", momenta, vertices,
                                   proton_numbers, mass_numbers, self.config, seed, indices, first_event, ctx,
-                                  per_event, configure, **how)
+                                  per_event, configure, straggling=straggling, **how)
         extra = trigger_result(ctx, len(arrays.offsets) - 1)
         if rows:
             from .estimate import estimates_result
@@ -523,7 +525,7 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
                           noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
                           readout: str = "hit", readout_pads=None, trigger: TriggerSettings | None = None,
                           gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
-                          packed: bool = False):
+                          packed: bool = False, straggling=None):
     """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``; the noise keyed on
     ``seed`` and the global event ids; ``readout`` / ``readout_pads`` as configure_traces) ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
@@ -533,11 +535,12 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     ``seed`` and the global event ids like the noise.  ``common_mode`` (a ``CommonModeSettings``; None = off): the
     common-mode noise of every pad with a group, keyed the same way.  ``packed=True``
     (``attpc_det_run_traces_packed``): (offsets, pads, row_start [R+1] i64, packed uint8, labels, event_points, stats
-    with ``n_bytes``) -- the rows as packed records, ``unpack_traces`` gives the samples back."""
+    with ``n_bytes``) -- the rows as packed records, ``unpack_traces`` gives the samples back.  ``straggling`` (a
+    ``detector.straggling.StragglingSettings``; None = off): multiple scattering and energy-loss straggling of the tracks."""
     chain = TraceChain(config, response, threshold, offset, NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream),
                        ReadoutSettings(readout, readout_pads), gain, trigger=trigger, common_mode=common_mode)
     return chain.run_batch(False, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
-                           capacity_per_event, packed)
+                           capacity_per_event, packed, straggling=straggling)
 
 
 def _host_cloud(offsets, points, labels, seed, first_event):
@@ -989,7 +992,7 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               peaks: PeakSettings | None = None, capacity_per_event: int = 2048,
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
-                              estimates=None, thinning=None, **trace_kwargs):
+                              estimates=None, thinning=None, straggling=None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -999,12 +1002,12 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     ``detector.estimate.EstimateSettings``; None = off) the track estimates [n, len(indices)] under ``"estimates"`` --
     with ``thinning`` (a ``detector.thinning.ThinSettings``; None = off) those of the thinned points, and its z step
     under ``"thinning"``).
-    ``gain`` and ``common_mode`` as simulate_batch_traces takes them."""
+    ``gain``, ``common_mode`` and ``straggling`` as simulate_batch_traces takes them."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
                                                                    thinning=thinning)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
-                           capacity_per_event)
+                           capacity_per_event, straggling=straggling)
 
 
 def clouds_to_trace_rows(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,

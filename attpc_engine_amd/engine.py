@@ -19,6 +19,7 @@ from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings
                               configure_trigger, trigger_result)
 from .detector.estimate import EstimateSettings, configure_estimates, estimates_result
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
+from .detector.straggling import StragglingSettings, configure_straggling
 from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -46,6 +47,7 @@ class Engine:
         det, keep_d = build_det_desc(config, nuclei, ode_substeps=ode_substeps)
         ctx.check(ctx.lib.attpc_det_configure(ctx.handle, det), "attpc_det_configure")
         ctx.forget("det")  # (what configure_detector last uploaded is no longer what the device holds)
+        configure_straggling(ctx, None)  # a new engine starts without the track straggling an earlier one configured
         self.layout = build_layout(self.z, self.a, self.indices, self.species)
         if chunk_events:
             ctx.check(ctx.lib.attpc_set_chunk_events(ctx.handle, int(chunk_events)), "attpc_set_chunk_events")
@@ -100,6 +102,16 @@ class Engine:
                                     max(4096, int(capacity_per_event) * n_events), pinned, holder=RowArrays, width=3,
                                     slack=4096, cache=self, reuse=reuse_buffers)
         return {**res, "points": arrays.result()[1]}
+
+    # ---------------------------------------------------------------- track straggling
+    def configure_straggling(self, settings=None, **parameters) -> None:
+        """Multiple scattering and energy-loss straggling of the tracks (include/attpc_engine.h, "track straggling"):
+        a ``detector.straggling.StragglingSettings`` or its keywords (angular_scale, energy_scale, radiation_length,
+        electron_density, stream) turn the stage on for every run function of this engine -- every recorded sample of
+        every track gets a Gaussian kick of its direction and of its kinetic energy, a pure function of the run's seed,
+        the global event id, the nucleus and the stream; a radiation length or an electron density left open is that
+        of the config's gas target --, neither turns it off (the default)."""
+        configure_straggling(self.ctx, _settings(StragglingSettings, settings, parameters), self.config)
 
     # ---------------------------------------------------------------- Spyral rows on the device
     def configure_spyral(self, config=None, response=None) -> None:
@@ -453,7 +465,7 @@ def _settings(cls, given, parameters: dict, what: str = "keywords"):
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
               batch_size: int = 65536, context: _abi.Context | None = None, selection=None, trigger=None,
-              gain=None, common_mode=None) -> None:
+              gain=None, common_mode=None, straggling=None) -> None:
     """run_kinematics_pipeline + run_simulation + SpyralWriter without the kinematics file and with
     the response / threshold / row conversion / z-sort done on the GPU: per event with a non-empty
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
@@ -465,8 +477,10 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     the traces made on the device (``Engine.run_traces``) with the writer's own trace settings.  ``selection``
     (``Engine.run_selected``; rows or plain clouds), ``trigger``, ``gain`` and ``common_mode``: as ``run_simulation`` takes them, with
     the same rules about the kinds of writer (``detector.simulator.plan_delivery``); event numbers stay the global
-    ones, the file roll-over counts written events."""
+    ones, the file roll-over counts written events.  ``straggling`` (a ``detector.straggling.StragglingSettings``; None =
+    off): the track straggling (``Engine.configure_straggling``), with any writer."""
     engine = Engine(pipeline, config, indices, context=context)
+    engine.configure_straggling(straggling)
     seed = pipeline.seed if seed is None else int(seed)
     kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, plain_clouds=False, common_mode=common_mode)
     if selection is not None:

@@ -1380,6 +1380,56 @@ ATTPC_API int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_
                                   int64_t capacity, int64_t* point_offsets, double* points, int64_t* point_labels,
                                   attpc_thin_info* info, int64_t* needed);
 
+/* ---- track straggling (opt-in: off by default, and with it off every output, kernel and buffer of every entry point
+ * is what it is without this section; the entry point is an addition under ABI version 3) ----
+ * The track integrator solves a deterministic equation of motion, so two particles of one momentum follow one path.
+ * This stage adds multiple Coulomb scattering and energy-loss straggling to every recorded sample of every track.
+ * tests/straggle_reference.py restates this contract in numpy; csrc/straggle_host.hpp is its arithmetic, shared by
+ * the kernel and the host, + - * / and sqrt only with every operation rounded (no fused multiply-add).
+ *
+ * The model, and what it is not: first order, Gaussian per step.  No single-scattering tail, no Landau tail; Bohr's
+ * variance is too large at low velocity.  The two scales exist so that a user can fit the lateral and the range
+ * straggling of their own SRIM or LISE tables.
+ *
+ * Where: after the RK4 sub-steps of recorded sample k (1 .. 10 000) have been accepted and before the electrons of
+ * that sample are made.  g = gamma beta after the step, m and Z the species' mass [MeV] and charge number.
+ * Step length: ds = c * sqrt(gv2 / (1 + gv2)) * h_sample, gv2 = |gamma beta|^2 of the state at the PREVIOUS recorded
+ * sample (after that sample's own kick), h_sample = 1e-10 s on the time grid and the path-length mode's own step
+ * otherwise.
+ * Angular kick (Rossi-Greisen, without Highland's logarithm: the variances of consecutive steps add and the result
+ * does not depend on the step length), skipped if angular_scale == 0:
+ *   theta0 = angular_scale * (13.6 MeV * |Z| / (beta p)) * sqrt(ds / X0), p = m |g|, beta = |g| / sqrt(1 + |g|^2)
+ *   u = g / |g|;  sign = copysign(1, u_z), a = -1 / (sign + u_z), b = u_x u_y a (Duff et al., JCGT 6(1), 2017)
+ *   e1 = (1 + sign u_x^2 a, sign b, -sign u_x),  e2 = (b, sign + u_y^2 a, -u_y)
+ *   d = u + theta0 n1 e1 + theta0 n2 e2;  the new direction is d / |d|  (else: u)
+ * Energy fluctuation (Bohr, Gaussian), skipped if energy_scale == 0:
+ *   KE = m |g|^2 / (gamma + 1)   (= m (gamma - 1)),  gamma^2 = 1 + |g|^2
+ *   Omega^2 = energy_scale^2 * K * Z^2 * n_e * ds * gamma^2 * (1 - beta^2 / 2),  K = 4 pi (r_e m_e c^2)^2 =
+ *             2.605634303273153e-29 MeV^2 m^2 (CODATA)
+ *   KE' = max(KE - Omega n3, KE_LIMIT);  |g'|^2 = (KE' / m) (KE' / m + 2)   (else: |g'| = |g|)
+ *   Unclamped on the high side on purpose: a step may "lose" a negative amount, the mean loss stays the table's.
+ * g' = |g'| * direction.  A skipped part uses no draw and keeps the direction u / the magnitude |g| bit for bit; with
+ * both scales 0 the stage is off.  Then the event functions and the sample's electrons are those of g' (the electrons
+ * come from |KE(g') - KE(previous sample)| as always).  A sample whose energy was clamped sits AT the limit: its "ke"
+ * event function is exactly 0, and the next step ends the track through the ordinary "ke" event.
+ * Random numbers: (n1, n2) are the Box-Muller (cos, sin) normals of the Philox pair (seed, event, 2 k, D), n3 the cos
+ * normal of the pair (seed, event, 2 k + 1, D), D = 0x10000000 + stream * 32 + row of the nucleus (row < 32).  A track
+ * is a pure function of (seed, global event id, row, stream): chunking, lanes and the number of GPUs do not enter. */
+typedef struct {
+  double angular_scale;     /* >= 0; 0 = no angular kick */
+  double energy_scale;      /* >= 0; 0 = no energy fluctuation */
+  double radiation_length;  /* X0 of the gas at its density, m, > 0 */
+  double electron_density;  /* electrons per m^3, > 0 */
+  uint32_t stream;          /* < 2^16 */
+} attpc_straggle_desc;
+
+/* desc == NULL turns the stage off (the default).  ATTPC_E_INVALID for a value that is not finite, a negative scale,
+ * X0 or n_e <= 0 or stream >= 2^16.  The descriptor is kept on the context, independent of every other configure call
+ * (attpc_det_configure does not drop it), and every entry point that integrates tracks uses it: attpc_det_tracks,
+ * attpc_det_run* and attpc_sim_run* in all their forms, and the batch attpc_sim_hint_next starts early.  With both
+ * scales 0 the kernels that run are those of the stage off. */
+ATTPC_API int32_t attpc_det_configure_straggling(attpc_ctx* ctx, const attpc_straggle_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif
