@@ -39,6 +39,7 @@
 #include "estimate_host.hpp"
 #include "thin_host.hpp"
 #include "straggle_host.hpp"
+#include "host_args.hpp"
 
 namespace {
 
@@ -70,6 +71,15 @@ struct Pinned {  // page-locked host array of the library, grow-only (ensure_pin
   Pinned& operator=(const Pinned&) = delete;
   ~Pinned() { if (p) (void)hipHostFree(p); }
   T& operator[](size_t i) const { return p[i]; }
+};
+
+struct DevAllocs {  // the device allocations of one configure call (upload()): freed on clear() and with their owner
+  std::vector<void*> ptrs;
+  DevAllocs() = default;
+  DevAllocs(const DevAllocs&) = delete;
+  DevAllocs& operator=(const DevAllocs&) = delete;
+  ~DevAllocs() { clear(); }
+  void clear() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
 };
 
 struct TrackSet {  // kinematics + tracks of one track batch
@@ -158,11 +168,11 @@ struct attpc_ctx {
 
   bool kin_ready = false;
   attpc_kin_desc kin{};            // device pointers inside
-  std::vector<void*> kin_allocs;
+  DevAllocs kin_allocs;
 
   bool det_ready = false;
   DetDev det{};
-  std::vector<void*> det_allocs;
+  DevAllocs det_allocs;
   bool straggle_on = false;        // attpc_det_configure_straggling (kept over attpc_det_configure)
   attpc_straggle_desc straggle{};
 
@@ -203,23 +213,23 @@ struct attpc_ctx {
   SpyralDev spyral{};
   bool trace_ready = false;
   TraceDev trace{};
-  std::vector<void*> trace_allocs;
+  DevAllocs trace_allocs;
   bool noise_on = false;           // attpc_trace_configure_noise: noise and / or pedestals on (the NOISE kernels)
   TraceNoiseDev noise{};
-  std::vector<void*> noise_allocs;
+  DevAllocs noise_allocs;
   std::vector<uint32_t> noise_cdf;  // host copy of the noise cdf [n_levels - 1] (the readout's cutoff)
   bool gain_on = false;            // attpc_trace_configure_gain
   GainDev gain{};
-  std::vector<void*> gain_allocs;
+  DevAllocs gain_allocs;
   bool common_on = false;          // attpc_trace_configure_common_mode
   TraceNoiseDev common_table{};    // the stage's own noise table (no pedestals), domain DOMAIN_TRACE_COMMON | stream
   const uint8_t* common_groups = nullptr;  // [ATTPC_NUM_PADS] on the device, or nullptr = every pad in group 0
   int32_t common_n_groups = 0;     // 1 + the highest group of the map
-  std::vector<void*> common_allocs;
+  DevAllocs common_allocs;
   int32_t readout_mode = ATTPC_READOUT_HIT;  // attpc_trace_configure_readout
   int64_t readout_pads = 0;        // |S|
   const uint32_t* readout_channels = nullptr;  // [TR_MAP_WORDS] bitmap of S on the device
-  std::vector<void*> readout_allocs;
+  DevAllocs readout_allocs;
   DevBuf trace_sums;               // [2] sample / pad checksums of the trace run in progress
   bool peaks_on = false;           // attpc_trace_configure_peaks
   PeakDev peaks{};
@@ -247,7 +257,7 @@ struct attpc_ctx {
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
-  std::vector<void*> summary_allocs;
+  DevAllocs summary_allocs;
   // summaries of a batch (summary.hip): the records, and per chunk the segments grouped by event
   DevBuf sm_events, sm_tracks, sm_seg_count, sm_seg_rank, sm_seg_start, sm_seg_list, sm_host_segs, sm_host_ctrl;
   bool select_on = false;          // attpc_select_configure
@@ -264,7 +274,7 @@ struct attpc_ctx {
   int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
   uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
-  std::vector<void*> spyral_allocs;
+  DevAllocs spyral_allocs;
   std::vector<double> h_pad_centers, h_pad_sizes;  // host copies: the expansion of compact Spyral records needs them
   DevBuf scratch[8];
   std::vector<void*> host_allocs;  // attpc_host_alloc
@@ -279,9 +289,7 @@ struct attpc_ctx {
   uint64_t unpack_submitted = 0, unpack_done = 0;
   bool unpack_stop = false, unpack_failed = false;
 
-  ~attpc_ctx() {  // (attpc_ctx_destroy has stopped everything first; the DevBuf / Pinned members free themselves)
-    for (std::vector<void*>* v : {&kin_allocs, &det_allocs, &spyral_allocs, &trace_allocs, &noise_allocs, &gain_allocs, &common_allocs, &readout_allocs, &summary_allocs})
-      for (void* p : *v) (void)hipFree(p);
+  ~attpc_ctx() {  // (attpc_ctx_destroy has stopped everything first; the DevBuf / Pinned / DevAllocs members free themselves)
     for (void* p : host_allocs) (void)hipHostFree(p);
   }
 };
@@ -324,6 +332,34 @@ int32_t ensure(attpc_ctx* ctx, DevBuf& b, size_t bytes) {
   return ATTPC_OK;
 }
 
+// Staging of an operator on host arrays: scratch slot `k` as `n` elements of T, grow-only like ensure() -- the byte count
+// is formed here and nowhere else.  `rc` is the operator's status: a call does nothing once it is set and sets it when it
+// fails, so an operator names its buffers one after the other and looks at rc once before the launch.
+template <typename T>
+T* stage(attpc_ctx* ctx, int k, size_t n, int32_t& rc) {
+  if (!rc) rc = ensure(ctx, ctx->scratch[k], n * sizeof(T));
+  return rc ? nullptr : static_cast<T*>(ctx->scratch[k].p);
+}
+
+// ... filled with host[0 .. n) by a copy on S (`room` > n: the elements the slot holds at least, also for a chunk without rows)
+template <typename T>
+const T* stage_in(attpc_ctx* ctx, int k, const T* host, size_t n, int32_t& rc, size_t room = 0) {
+  T* dev = stage<T>(ctx, k, std::max(n, room), rc);
+  if (!rc && n)
+    rc = [&]() -> int32_t {
+      HIP_TRY(ctx, hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+      return ATTPC_OK;
+    }();
+  return dev;
+}
+
+// n elements of a staged result back to the host, by a copy on S
+template <typename T>
+int32_t stage_out(attpc_ctx* ctx, T* host, const T* dev, size_t n) {
+  HIP_TRY(ctx, hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+  return ATTPC_OK;
+}
+
 // grow-only pinned host array: at least `n` elements, re-allocated at `alloc` (with headroom, if larger) when it grows;
 // the caller makes sure no copy in flight uses it then
 template <typename T>
@@ -339,18 +375,13 @@ int32_t ensure_pinned(attpc_ctx* ctx, Pinned<T>& b, size_t n, size_t alloc = 0) 
 }
 
 template <typename T>
-int32_t upload(attpc_ctx* ctx, std::vector<void*>& owner, const T* host, size_t n, const T** dev) {
+int32_t upload(attpc_ctx* ctx, DevAllocs& owner, const T* host, size_t n, const T** dev) {
   void* p = nullptr;
   HIP_TRY(ctx, hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-  owner.push_back(p);
+  owner.ptrs.push_back(p);
   if (n) HIP_TRY(ctx, hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
   *dev = static_cast<const T*>(p);
   return ATTPC_OK;
-}
-
-void free_all(std::vector<void*>& v) {
-  for (void* p : v) (void)hipFree(p);
-  v.clear();
 }
 
 // The tables of baseline.hip.  filter: F[k] = sinc(w_k / scale), w_k = k below 256 and k - 512 from there on, divided by
@@ -390,6 +421,17 @@ int32_t sync_all(attpc_ctx* ctx) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_c));
   return ATTPC_OK;
+}
+
+// how a configure call opens: its device selected and nothing in flight on any stream
+int32_t begin_configure(attpc_ctx* ctx) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return sync_all(ctx);
+}
+
+// ATTPC_E_INVALID for what a check of host_args.hpp found (a refusal without a text leaves the last error as it was)
+int32_t refuse(attpc_ctx* ctx, const ArgError& bad) {
+  return bad.text.empty() ? ATTPC_E_INVALID : fail(ctx, ATTPC_E_INVALID, "%s", bad.text.c_str());
 }
 
 // A first track batch queued ahead for a call that does not come (another entry point, other events, a new
@@ -1573,8 +1615,7 @@ int32_t trace_host_events(attpc_ctx* ctx, RunOut& o, uint64_t first_local, uint3
     int32_t rc;
     if ((rc = ensure_asm_cloud(ctx, as, m, cap))) return rc;
     std::vector<int64_t> start((size_t)m + 1, 0);
-    if (offsets)
-      for (uint32_t e = 0; e <= m; ++e) start[e] = offsets[e0 + e] - lo;
+    if (offsets) chunk_starts(offsets, e0, e0 + m, &start);
     HIP_TRY(ctx, hipMemcpyAsync(as.ev_start.p, start.data(), start.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     if (rows > 0) {
       HIP_TRY(ctx, hipMemcpyAsync(as.points.p, points + 3 * lo, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -2407,12 +2448,11 @@ int32_t attpc_sync(attpc_ctx* ctx) {
 
 int32_t attpc_kin_configure(attpc_ctx* ctx, const attpc_kin_desc* d) {
   if (!ctx || !d) return ATTPC_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (d->n_steps < 1 || d->n_steps > ATTPC_MAX_STEPS) return fail(ctx, ATTPC_E_INVALID, "n_steps=%d", d->n_steps);
   if (d->sample_limit < 1) return fail(ctx, ATTPC_E_INVALID, "sample_limit=%d", d->sample_limit);
-  { int32_t rc0 = drop_prefetch(ctx); if (rc0) return rc0; }
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->kin_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = drop_prefetch(ctx); if (rc0) return rc0; }  // (nothing is in flight: it only forgets the batch)
+  ctx->kin_allocs.clear();
   ctx->kin_ready = false;
   ctx->rows_per_event = ctx->segs_per_event = ctx->blocks_per_track = 0.0;  // another workload: size estimates start over
   attpc_kin_desc k = *d;
@@ -2465,22 +2505,19 @@ int32_t attpc_kin_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint6
   if (rc) return rc;
   const uint64_t chunk = (uint64_t)std::max(1, ctx->chunk_events) * 4;
   const size_t cap = (size_t)std::min<uint64_t>(chunk, std::max<uint64_t>(n_events, 1));
-  if ((rc = ensure(ctx, ctx->scratch[4], cap * n_rows * 4 * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[5], cap * 3 * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[6], cap * sizeof(int32_t)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[7], cap * sizeof(uint32_t)))) return rc;
-  double* d_p4 = static_cast<double*>(ctx->scratch[4].p);
-  double* d_vertex = static_cast<double*>(ctx->scratch[5].p);
-  int32_t* d_status = static_cast<int32_t*>(ctx->scratch[6].p);
-  uint32_t* d_attempts = static_cast<uint32_t*>(ctx->scratch[7].p);
+  double* d_p4 = stage<double>(ctx, 4, cap * n_rows * 4, rc);
+  double* d_vertex = stage<double>(ctx, 5, cap * 3, rc);
+  int32_t* d_status = stage<int32_t>(ctx, 6, cap, rc);
+  uint32_t* d_attempts = stage<uint32_t>(ctx, 7, cap, rc);
+  if (rc) return rc;
   for (uint64_t done = 0; done < n_events; done += chunk) {
     const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, n_events - done);
     launch_kin_run(ctx->stream, ctx->kin, seed, first_event + done, n, d_p4, d_vertex, d_status, d_attempts);
     HIP_TRY(ctx, hipGetLastError());
-    if (p4) HIP_TRY(ctx, hipMemcpyAsync(p4 + done * n_rows * 4, d_p4, (size_t)n * n_rows * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (vertex) HIP_TRY(ctx, hipMemcpyAsync(vertex + done * 3, d_vertex, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIP_TRY(ctx, hipMemcpyAsync(status + done, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (attempts) HIP_TRY(ctx, hipMemcpyAsync(attempts + done, d_attempts, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (p4 && (rc = stage_out(ctx, p4 + done * n_rows * 4, d_p4, (size_t)n * n_rows * 4))) return rc;
+    if (vertex && (rc = stage_out(ctx, vertex + done * 3, d_vertex, (size_t)n * 3))) return rc;
+    if (status && (rc = stage_out(ctx, status + done, d_status, (size_t)n))) return rc;
+    if (attempts && (rc = stage_out(ctx, attempts + done, d_attempts, (size_t)n))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return ATTPC_OK;
@@ -2493,23 +2530,18 @@ int32_t attpc_kin_calculate(attpc_ctx* ctx, uint64_t n, const double* beam_energ
   if (n == 0) return ATTPC_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int ns = ctx->kin.n_steps, n_rows = kin_rows(ctx);
-  int32_t rc;
-  if ((rc = ensure(ctx, ctx->scratch[0], n * sizeof(double)))) return rc;
-  for (int i = 1; i <= 3; ++i)
-    if ((rc = ensure(ctx, ctx->scratch[i], n * ns * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[4], n * n_rows * 4 * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[5], n * sizeof(int32_t)))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, beam_energy, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, ex, n * ns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, polar, n * ns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[3].p, azim, n * ns * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  launch_kin_calculate(ctx->stream, ctx->kin, (uint32_t)n, static_cast<const double*>(ctx->scratch[0].p),
-                     static_cast<const double*>(ctx->scratch[1].p), static_cast<const double*>(ctx->scratch[2].p),
-                     static_cast<const double*>(ctx->scratch[3].p), static_cast<double*>(ctx->scratch[4].p),
-                     static_cast<int32_t*>(ctx->scratch[5].p));
+  int32_t rc = ATTPC_OK;
+  const double* d_beam = stage_in(ctx, 0, beam_energy, n, rc);
+  const double* d_ex = stage_in(ctx, 1, ex, n * ns, rc);
+  const double* d_polar = stage_in(ctx, 2, polar, n * ns, rc);
+  const double* d_azim = stage_in(ctx, 3, azim, n * ns, rc);
+  double* d_p4 = stage<double>(ctx, 4, n * n_rows * 4, rc);
+  int32_t* d_status = stage<int32_t>(ctx, 5, n, rc);
+  if (rc) return rc;
+  launch_kin_calculate(ctx->stream, ctx->kin, (uint32_t)n, d_beam, d_ex, d_polar, d_azim, d_p4, d_status);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(p4, ctx->scratch[4].p, n * n_rows * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(status, ctx->scratch[5].p, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = stage_out(ctx, p4, d_p4, n * n_rows * 4))) return rc;
+  if ((rc = stage_out(ctx, status, d_status, n))) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return ATTPC_OK;
 }
@@ -2520,30 +2552,24 @@ int32_t attpc_decay_calculate(attpc_ctx* ctx, uint64_t n, const double* parent, 
   if (!ctx || !parent || !ex || !polar || !azim || !out || !status) return ATTPC_E_INVALID;
   if (n == 0) return ATTPC_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int32_t rc;
-  if ((rc = ensure(ctx, ctx->scratch[0], n * 4 * sizeof(double)))) return rc;
-  for (int i = 1; i <= 3; ++i)
-    if ((rc = ensure(ctx, ctx->scratch[i], n * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[4], n * 8 * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[5], n * sizeof(int32_t)))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, parent, n * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, ex, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, polar, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[3].p, azim, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  launch_decay_calculate(ctx->stream, (uint32_t)n, static_cast<const double*>(ctx->scratch[0].p), mass_1, mass_2,
-                     static_cast<const double*>(ctx->scratch[1].p), static_cast<const double*>(ctx->scratch[2].p),
-                     static_cast<const double*>(ctx->scratch[3].p), static_cast<double*>(ctx->scratch[4].p),
-                     static_cast<int32_t*>(ctx->scratch[5].p));
+  int32_t rc = ATTPC_OK;
+  const double* d_parent = stage_in(ctx, 0, parent, n * 4, rc);
+  const double* d_ex = stage_in(ctx, 1, ex, n, rc);
+  const double* d_polar = stage_in(ctx, 2, polar, n, rc);
+  const double* d_azim = stage_in(ctx, 3, azim, n, rc);
+  double* d_out = stage<double>(ctx, 4, n * 8, rc);
+  int32_t* d_status = stage<int32_t>(ctx, 5, n, rc);
+  if (rc) return rc;
+  launch_decay_calculate(ctx->stream, (uint32_t)n, d_parent, mass_1, mass_2, d_ex, d_polar, d_azim, d_out, d_status);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch[4].p, n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(status, ctx->scratch[5].p, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = stage_out(ctx, out, d_out, n * 8))) return rc;
+  if ((rc = stage_out(ctx, status, d_status, n))) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return ATTPC_OK;
 }
 
 int32_t attpc_det_configure(attpc_ctx* ctx, const attpc_det_desc* d) {
   if (!ctx || !d) return ATTPC_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (d->n_species < 1 || d->n_species > ATTPC_MAX_SPECIES) return fail(ctx, ATTPC_E_INVALID, "n_species=%d", d->n_species);
   if ((size_t)d->n_species * ATTPC_DEDX_NODES * sizeof(double) > 150 * 1024)
     return fail(ctx, ATTPC_E_INVALID, "stopping-power tables of %d species do not fit LDS (max 13)", d->n_species);
@@ -2561,9 +2587,9 @@ int32_t attpc_det_configure(attpc_ctx* ctx, const attpc_det_desc* d) {
       if (d->pad_lut[i] < -1 || d->pad_lut[i] >= LONE_PADS)
         return fail(ctx, ATTPC_E_INVALID, "pad look-up table holds pad id %d at cell %zu: ids must be in [-1, %d]", (int)d->pad_lut[i], i, LONE_PADS - 1);
   }
-  { int32_t rc0 = drop_prefetch(ctx); if (rc0) return rc0; }
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->det_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = drop_prefetch(ctx); if (rc0) return rc0; }  // (nothing is in flight: it only forgets the batch)
+  ctx->det_allocs.clear();
   ctx->det_ready = false;
   ctx->rows_per_event = ctx->segs_per_event = ctx->blocks_per_track = 0.0;  // size estimates start over
   ctx->prefer_big = false;
@@ -2663,9 +2689,8 @@ int32_t attpc_trace_configure(attpc_ctx* ctx, const attpc_trace_desc* d) {
   for (int j = 0; j < ATTPC_NUM_TB; ++j)
     if (!(d->response[j] >= 0.0) || std::isinf(d->response[j]))
       return fail(ctx, ATTPC_E_INVALID, "response[%d] = %g: the trace response must be finite and >= 0", j, d->response[j]);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->trace_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->trace_allocs.clear();
   ctx->trace_ready = false;
   TraceDev tr{};
   int32_t rc;
@@ -2693,28 +2718,18 @@ int32_t attpc_trace_configure_noise(attpc_ctx* ctx, const attpc_trace_noise_desc
           return fail(ctx, ATTPC_E_INVALID, "pedestal of pad %d is %d, outside 0 .. 4095", p, (int)d->pedestals[p]);
     if (d->stream >= 0x80000000u) return fail(ctx, ATTPC_E_INVALID, "noise stream %u >= 2^31", d->stream);
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->noise_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->noise_allocs.clear();
   ctx->noise_on = false;
   ctx->noise = TraceNoiseDev{};
   ctx->noise_cdf.clear();
   if (!d || (d->n_levels == 0 && !d->pedestals)) return ATTPC_OK;  // the noiseless contract
-  // the cdf padded to the full table (the kernels copy all of it to LDS) and the guide: the search for u starts at
-  // #{k : cdf[k] <= (u >> 24) << 24}
-  const int n_cdf = std::max(d->n_levels - 1, 0);
-  std::vector<uint32_t> cdf(ATTPC_MAX_NOISE_LEVELS, 0xFFFFFFFFu);
-  for (int k = 0; k < n_cdf; ++k) cdf[k] = d->cdf[k];
-  ctx->noise_cdf.assign(cdf.begin(), cdf.begin() + n_cdf);
-  std::vector<uint16_t> guide(256);
-  for (int b = 0, k = 0; b < 256; ++b) {
-    while (k < n_cdf && cdf[k] <= (uint32_t)b << 24) ++k;
-    guide[b] = (uint16_t)k;
-  }
+  const NoiseTable table = noise_table(d->n_levels, d->cdf);
+  ctx->noise_cdf.assign(table.cdf.begin(), table.cdf.begin() + std::max(d->n_levels - 1, 0));
   TraceNoiseDev nz{};
   int32_t rc;
-  if ((rc = upload(ctx, ctx->noise_allocs, cdf.data(), cdf.size(), &nz.cdf))) return rc;
-  if ((rc = upload(ctx, ctx->noise_allocs, guide.data(), guide.size(), &nz.guide))) return rc;
+  if ((rc = upload(ctx, ctx->noise_allocs, table.cdf.data(), table.cdf.size(), &nz.cdf))) return rc;
+  if ((rc = upload(ctx, ctx->noise_allocs, table.guide.data(), table.guide.size(), &nz.guide))) return rc;
   if (d->pedestals && (rc = upload(ctx, ctx->noise_allocs, d->pedestals, (size_t)ATTPC_NUM_PADS, &nz.pedestals))) return rc;
   nz.n_levels = d->n_levels;
   nz.min_level = d->min_level;
@@ -2728,9 +2743,8 @@ int32_t attpc_trace_configure_readout(attpc_ctx* ctx, const attpc_trace_readout_
   if (!ctx) return ATTPC_E_INVALID;
   if (d && d->mode != ATTPC_READOUT_HIT && d->mode != ATTPC_READOUT_PARTIAL && d->mode != ATTPC_READOUT_FULL)
     return fail(ctx, ATTPC_E_INVALID, "trace readout mode %d: 0 (hit), 1 (partial) or 2 (full)", d->mode);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->readout_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->readout_allocs.clear();
   ctx->readout_mode = ATTPC_READOUT_HIT;
   ctx->readout_pads = 0;
   ctx->readout_channels = nullptr;
@@ -2775,32 +2789,11 @@ namespace {
 // (pad, t) of their own within the event.
 int32_t check_host_cloud(attpc_ctx* ctx, const char* what, int64_t n_events, const int64_t* offsets, const double* points,
                          bool has_labels) {
-  if (n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
-  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes at most 2^31 - 1 events per call", what);
-  const uint32_t n = (uint32_t)n_events;
-  const int64_t first = n ? offsets[0] : 0;
-  for (uint32_t e = 0; e < n; ++e)
-    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %u", e);
-  if (first < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
-  const int64_t rows = n ? offsets[n] - first : 0;
+  if (const ArgError bad = csr_error(what, n_events, offsets, CSR_CLOUD)) return refuse(ctx, bad);
+  const int64_t rows = n_events ? offsets[n_events] - offsets[0] : 0;
   if (rows > 0 && (!points || !has_labels)) return ATTPC_E_INVALID;
   if (rows > (int64_t)UINT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes fewer than 2^32 rows per call", what);
-  std::vector<uint32_t> keys;
-  for (uint32_t e = 0; e < n; ++e) {
-    keys.clear();
-    for (int64_t r = offsets[e]; r < offsets[e + 1]; ++r) {
-      const double padf = points[3 * r], tb = points[3 * r + 1], q = points[3 * r + 2];
-      if (!(padf >= 0.0 && padf < (double)ATTPC_NUM_PADS) || padf != std::floor(padf))
-        return fail(ctx, ATTPC_E_INVALID, "row %lld: pad %g is not an integer in [0, %d)", (long long)r, padf, ATTPC_NUM_PADS);
-      if (!(tb >= 0.0 && tb < (double)ATTPC_NUM_TB))
-        return fail(ctx, ATTPC_E_INVALID, "row %lld: time bucket %g outside [0, 512)", (long long)r, tb);
-      if (!(q >= 0.0) || std::isinf(q)) return fail(ctx, ATTPC_E_INVALID, "row %lld: electrons %g", (long long)r, q);
-      keys.push_back((uint32_t)padf * ATTPC_NUM_TB + (uint32_t)std::floor(tb));
-    }
-    std::sort(keys.begin(), keys.end());
-    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
-      return fail(ctx, ATTPC_E_INVALID, "event %u has two rows on one pad and time bucket", e);
-  }
+  if (const ArgError bad = cloud_rows_error(n_events, offsets, points, true)) return refuse(ctx, bad);
   return ATTPC_OK;
 }
 
@@ -2808,8 +2801,7 @@ int32_t check_host_cloud(attpc_ctx* ctx, const char* what, int64_t n_events, con
 // into `o`.
 int32_t host_cloud_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int64_t n_events, const int64_t* offsets,
                        const double* points, const int64_t* labels, RunOut& o) {
-  if (n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
-  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_traces takes at most 2^31 - 1 events per call");
+  if (const ArgError bad = csr_count_error("attpc_traces", n_events, offsets)) return refuse(ctx, bad);
   if (validate_id_range(ctx, first_event, (uint64_t)n_events)) return ATTPC_E_INVALID;
   if (!ctx->trace_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trace_configure has not been called");
   const uint32_t n = (uint32_t)n_events;
@@ -2905,23 +2897,18 @@ int32_t attpc_trace_pack(attpc_ctx* ctx, int64_t n_rows, const int16_t* samples,
   if (row_start) row_start[0] = 0;
   if (n_rows == 0) return ATTPC_OK;
   if (!samples) return ATTPC_E_INVALID;
-  for (int64_t i = 0; i < n_rows * ATTPC_NUM_TB; ++i)
-    if (samples[i] < 0 || samples[i] > 4095)
-      return fail(ctx, ATTPC_E_INVALID, "sample %lld of row %lld is %d: 0 .. 4095", (long long)(i % ATTPC_NUM_TB),
-                  (long long)(i / ATTPC_NUM_TB), (int)samples[i]);
+  if (const ArgError bad = sample_error(samples, 0, n_rows)) return refuse(ctx, bad);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc;
   if ((rc = drop_prefetch(ctx))) return rc;
   if ((rc = sync_all(ctx))) return rc;
   AsmSet& as = ctx->aset[0];
   constexpr int64_t CHUNK = 16384;  // rows: 16 MiB of samples on the device
-  const size_t row_bytes = ATTPC_NUM_TB * sizeof(int16_t);
-  if ((rc = ensure(ctx, ctx->scratch[0], (size_t)std::min(n_rows, CHUNK) * row_bytes))) return rc;
-  const int16_t* d_samples = static_cast<const int16_t*>(ctx->scratch[0].p);
   int64_t total = 0;
   for (int64_t first = 0; first < n_rows; first += CHUNK) {
-    const int64_t n = std::min(CHUNK, n_rows - first);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, samples + first * ATTPC_NUM_TB, (size_t)n * row_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int64_t n = std::min(CHUNK, n_rows - first);  // (the first chunk is the largest: the slot grows once)
+    const int16_t* d_samples = stage_in(ctx, 0, samples + first * ATTPC_NUM_TB, (size_t)n * ATTPC_NUM_TB, rc);
+    if (rc) return rc;
     if ((rc = enqueue_trace_pack_size(ctx, as, n, d_samples))) return rc;
     HIP_TRY(ctx, hipEventSynchronize(as.counted));
     const int64_t chunk_bytes = as.h_tp_total[0];
@@ -2969,9 +2956,8 @@ int32_t attpc_trace_configure_gain(attpc_ctx* ctx, const attpc_trace_gain_desc* 
     }
     if (d->stream >= 0x40000000u) return fail(ctx, ATTPC_E_INVALID, "gain stream %u >= 2^30", d->stream);
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->gain_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->gain_allocs.clear();
   ctx->gain_on = false;
   ctx->gain = GainDev{};
   if (!d || (d->rel_variance == 0.0 && !d->pad_gain)) return ATTPC_OK;  // q'' = q: the contract without the stage
@@ -3000,25 +2986,20 @@ int32_t attpc_gain_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int
   // chunks of whole events: about 4 Mi rows (96 MiB of points) and at most 1 Mi events, one event at the least
   constexpr int64_t CHUNK_ROWS = 4ll << 20, CHUNK_EVENTS = 1ll << 20;
   std::vector<int64_t> start;
-  for (int64_t e0 = 0; e0 < n_events;) {
-    int64_t e1 = e0 + 1;
-    while (e1 < n_events && e1 - e0 < CHUNK_EVENTS && offsets[e1 + 1] - offsets[e0] <= CHUNK_ROWS) ++e1;
+  for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
+    e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
     const int64_t lo = offsets[e0], rows = offsets[e1] - lo, m = e1 - e0;
     if (rows > 0) {
-      start.resize((size_t)m + 1);
-      for (int64_t e = 0; e <= m; ++e) start[(size_t)e] = offsets[e0 + e] - lo;
-      if ((rc = ensure(ctx, ctx->scratch[0], start.size() * sizeof(int64_t)))) return rc;
-      if ((rc = ensure(ctx, ctx->scratch[1], (size_t)rows * 3 * sizeof(double)))) return rc;
-      if ((rc = ensure(ctx, ctx->scratch[2], (size_t)rows * sizeof(double)))) return rc;
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, start.data(), start.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, points + 3 * lo, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      launch_gain(ctx->stream, ctx->gain, seed, (uint32_t)m, first_event + (uint64_t)e0, static_cast<const int64_t*>(ctx->scratch[0].p),
-                  static_cast<const double*>(ctx->scratch[1].p), static_cast<double*>(ctx->scratch[2].p));
+      chunk_starts(offsets, e0, e1, &start);
+      const int64_t* d_start = stage_in(ctx, 0, start.data(), start.size(), rc);
+      const double* d_points = stage_in(ctx, 1, points + 3 * lo, (size_t)rows * 3, rc);
+      double* d_gained = stage<double>(ctx, 2, (size_t)rows, rc);
+      if (rc) return rc;
+      launch_gain(ctx->stream, ctx->gain, seed, (uint32_t)m, first_event + (uint64_t)e0, d_start, d_points, d_gained);
       HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipMemcpyAsync(gained + lo, ctx->scratch[2].p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      if ((rc = stage_out(ctx, gained + lo, d_gained, (size_t)rows))) return rc;
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    e0 = e1;
   }
   return ATTPC_OK;
 }
@@ -3041,28 +3022,19 @@ int32_t attpc_trace_configure_common_mode(attpc_ctx* ctx, const attpc_trace_comm
       for (int p = 0; p < ATTPC_NUM_PADS; ++p)
         if (d->groups[p] != 255) n_groups = std::max(n_groups, (int)d->groups[p] + 1);
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->common_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->common_allocs.clear();
   ctx->common_on = false;
   ctx->common_table = TraceNoiseDev{};
   ctx->common_groups = nullptr;
   ctx->common_n_groups = 0;
   if (!d || d->n_levels == 0 || n_groups == 0) return ATTPC_OK;  // the contract without the stage
-  // the table as attpc_trace_configure_noise lays it out: the cdf padded to the full table, and the guide
-  const int n_cdf = d->n_levels - 1;
-  std::vector<uint32_t> cdf(ATTPC_MAX_NOISE_LEVELS, 0xFFFFFFFFu);
-  for (int k = 0; k < n_cdf; ++k) cdf[k] = d->cdf[k];
-  std::vector<uint16_t> guide(256);
-  for (int b = 0, k = 0; b < 256; ++b) {
-    while (k < n_cdf && cdf[k] <= (uint32_t)b << 24) ++k;
-    guide[b] = (uint16_t)k;
-  }
+  const NoiseTable table = noise_table(d->n_levels, d->cdf);
   TraceNoiseDev t{};
   const uint8_t* groups = nullptr;
   int32_t rc;
-  if ((rc = upload(ctx, ctx->common_allocs, cdf.data(), cdf.size(), &t.cdf))) return rc;
-  if ((rc = upload(ctx, ctx->common_allocs, guide.data(), guide.size(), &t.guide))) return rc;
+  if ((rc = upload(ctx, ctx->common_allocs, table.cdf.data(), table.cdf.size(), &t.cdf))) return rc;
+  if ((rc = upload(ctx, ctx->common_allocs, table.guide.data(), table.guide.size(), &t.guide))) return rc;
   if (d->groups && (rc = upload(ctx, ctx->common_allocs, d->groups, (size_t)ATTPC_NUM_PADS, &groups))) return rc;
   t.n_levels = d->n_levels;
   t.min_level = d->min_level;
@@ -3090,12 +3062,13 @@ int32_t attpc_common_mode_rows(attpc_ctx* ctx, uint64_t seed, uint64_t first_eve
   for (int64_t e0 = 0; e0 < n_events; e0 += step) {
     const int64_t m = std::min(step, n_events - e0);
     const size_t count = (size_t)m * per_event;
-    if ((rc = ensure(ctx, ctx->scratch[0], count * sizeof(int16_t)))) return rc;
+    int16_t* d_lanes = stage<int16_t>(ctx, 0, count, rc);
+    if (rc) return rc;
     launch_common_mode(ctx->stream, ctx->common_table, seed, (uint32_t)m, first_event + (uint64_t)e0,
-                       (uint32_t)ctx->common_n_groups, static_cast<int16_t*>(ctx->scratch[0].p));
+                       (uint32_t)ctx->common_n_groups, d_lanes);
     HIP_TRY(ctx, hipGetLastError());
     lanes.resize(count);
-    HIP_TRY(ctx, hipMemcpyAsync(lanes.data(), ctx->scratch[0].p, count * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = stage_out(ctx, lanes.data(), d_lanes, count))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // the device keeps a group's values in lane order (sample l + 64 s at 8 l + s): sample order for the caller
     int16_t* dst = out + (size_t)e0 * per_event;
@@ -3114,9 +3087,8 @@ int32_t attpc_summary_configure(attpc_ctx* ctx, const attpc_summary_desc* d) {
     if (d->n_pads < ATTPC_NUM_PADS) return fail(ctx, ATTPC_E_INVALID, "summary geometry of %d pads, the clouds name pads up to %d", d->n_pads, ATTPC_NUM_PADS - 1);
     if (!d->pad_centers) return fail(ctx, ATTPC_E_INVALID, "summary geometry without pad centres");
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->summary_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->summary_allocs.clear();
   ctx->summary_on = false;
   ctx->summary_centers = nullptr;
   if (!d) return ATTPC_OK;
@@ -3150,8 +3122,7 @@ namespace {
 int32_t host_cloud_records(const char* name, attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* points,
                            const int64_t* labels, const attpc_event_layout* layout, const attpc_summary_out* out, uint8_t* passed,
                            attpc_maps_out* maps = nullptr) {
-  if (n_events < 0 || (n_events > 0 && !offsets)) return ATTPC_E_INVALID;
-  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes at most 2^31 - 1 events per call", name);
+  if (const ArgError bad = csr_count_error(name, n_events, offsets)) return refuse(ctx, bad);
   if (!ctx->summary_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_summary_configure has not been called");
   if (maps && !ctx->maps_on) return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_maps_configure has not been called");
   const bool predicate = maps ? ctx->maps.selected != 0 : passed != nullptr;
@@ -3160,22 +3131,11 @@ int32_t host_cloud_records(const char* name, attpc_ctx* ctx, int64_t n_events, c
   if ((rc = validate_layout(ctx, layout, false))) return rc;
   if (predicate && (rc = validate_select_mask(ctx, name, layout->n_sim))) return rc;
   const uint32_t n = (uint32_t)n_events;
+  if (const ArgError bad = csr_error(name, n_events, offsets)) return refuse(ctx, bad);
   const int64_t first = n ? offsets[0] : 0;
-  if (first < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
-  for (uint32_t e = 0; e < n; ++e) {
-    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %u", e);
-    if (offsets[e + 1] - offsets[e] > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "event %u has 2^31 rows or more", e);
-  }
   const int64_t rows = n ? offsets[n] - first : 0;
   if (rows > 0 && (!points || !labels)) return ATTPC_E_INVALID;
-  for (int64_t r = first; r < first + rows; ++r) {  // the contract's rows
-    const double padf = points[3 * r], tb = points[3 * r + 1], q = points[3 * r + 2];
-    if (!(padf >= 0.0 && padf < (double)ATTPC_NUM_PADS) || padf != std::floor(padf))
-      return fail(ctx, ATTPC_E_INVALID, "row %lld: pad %g is not an integer in [0, %d)", (long long)r, padf, ATTPC_NUM_PADS);
-    if (!(tb >= 0.0 && tb < (double)ATTPC_NUM_TB))
-      return fail(ctx, ATTPC_E_INVALID, "row %lld: time bucket %g outside [0, 512)", (long long)r, tb);
-    if (!(q >= 0.0) || std::isinf(q)) return fail(ctx, ATTPC_E_INVALID, "row %lld: electrons %g", (long long)r, q);
-  }
+  if (const ArgError bad = cloud_rows_error(n_events, offsets, points, false)) return refuse(ctx, bad);  // the contract's rows
   if (maps) {
     // (one workgroup may meet every row: the 32-bit cells of maps_event_kernel)
     if (rows > (int64_t)UINT32_MAX) return fail(ctx, ATTPC_E_INVALID, "%s takes at most 2^32 - 1 rows per call", name);
@@ -3259,8 +3219,7 @@ int32_t attpc_select_configure(attpc_ctx* ctx, const attpc_select_desc* d) {
     if (d->min_tracks > (uint32_t)__builtin_popcount(d->track_mask))
       return fail(ctx, ATTPC_E_INVALID, "selection: min_tracks %u above the %d masked positions", d->min_tracks, __builtin_popcount(d->track_mask));
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
   ctx->select_on = d != nullptr;
   if (d) ctx->select = *d;
   return ATTPC_OK;
@@ -3310,8 +3269,7 @@ int32_t attpc_maps_configure(attpc_ctx* ctx, const attpc_maps_desc* d) {
     if (d->track_mask >> (ATTPC_MAX_SIM + 1)) return fail(ctx, ATTPC_E_INVALID, "run maps: track_mask 0x%x has bits above %d", d->track_mask, ATTPC_MAX_SIM);
     if (d->selected > 1u) return fail(ctx, ATTPC_E_INVALID, "run maps: selected %u", d->selected);
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
   ctx->maps_on = d != nullptr;
   if (d) ctx->maps = *d;
   return ATTPC_OK;
@@ -3366,8 +3324,7 @@ int32_t attpc_trace_configure_peaks(attpc_ctx* ctx, const attpc_peak_desc* d) {
     if (!(d->rel_height > 0.0 && d->rel_height <= 1.0)) return fail(ctx, ATTPC_E_INVALID, "peak rel_height %g: in (0, 1]", d->rel_height);
     if (std::isnan(d->threshold)) return fail(ctx, ATTPC_E_INVALID, "peak threshold is NaN");
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
   ctx->peaks_on = false;
   if (!d) return ATTPC_OK;
   PeakDev pk{};
@@ -3387,8 +3344,7 @@ int32_t attpc_trace_configure_baseline(attpc_ctx* ctx, const attpc_baseline_desc
   if (!ctx) return ATTPC_E_INVALID;
   if (d && !(std::isfinite(d->window_scale) && d->window_scale > 0.0))
     return fail(ctx, ATTPC_E_INVALID, "baseline window_scale %g: finite and > 0", d->window_scale);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
   ctx->baseline_on = false;
   if (!d) return ATTPC_OK;
   int32_t rc;
@@ -3404,10 +3360,7 @@ int32_t attpc_trace_baseline(attpc_ctx* ctx, int64_t n_rows, const int16_t* samp
     return fail(ctx, ATTPC_E_INVALID, "baseline window_scale %g: finite and > 0", window_scale);
   if (n_rows == 0) return ATTPC_OK;
   if (!samples || !y) return ATTPC_E_INVALID;
-  for (int64_t i = 0; i < n_rows * ATTPC_NUM_TB; ++i)
-    if (samples[i] < 0 || samples[i] > 4095)
-      return fail(ctx, ATTPC_E_INVALID, "sample %lld of row %lld is %d: 0 .. 4095", (long long)(i % ATTPC_NUM_TB),
-                  (long long)(i / ATTPC_NUM_TB), (int)samples[i]);
+  if (const ArgError bad = sample_error(samples, 0, n_rows)) return refuse(ctx, bad);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc;
   if ((rc = sync_all(ctx))) return rc;
@@ -3417,21 +3370,17 @@ int32_t attpc_trace_baseline(attpc_ctx* ctx, int64_t n_rows, const int16_t* samp
     ctx->bl_op_scale = window_scale;
   }
   constexpr int64_t CHUNK = 16384;  // rows: 16 MiB of samples, 16 MiB of y and 64 MiB of baseline on the device
-  const size_t rows = (size_t)std::min(n_rows, CHUNK), row_bytes = ATTPC_NUM_TB * sizeof(int16_t);
-  if ((rc = ensure(ctx, ctx->scratch[0], rows * row_bytes))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[1], rows * row_bytes))) return rc;
-  if (baseline && (rc = ensure(ctx, ctx->scratch[2], rows * ATTPC_NUM_TB * sizeof(double)))) return rc;
   for (int64_t first = 0; first < n_rows; first += CHUNK) {
-    const size_t n = (size_t)std::min(CHUNK, n_rows - first);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, samples + first * ATTPC_NUM_TB, n * row_bytes, hipMemcpyHostToDevice, ctx->stream));
-    launch_baseline(ctx->stream, (uint32_t)n, static_cast<const int16_t*>(ctx->scratch[0].p),
-                    static_cast<const double2*>(ctx->bl_twiddle.p), static_cast<const double*>(ctx->bl_op_filter.p),
-                    static_cast<int16_t*>(ctx->scratch[1].p), baseline ? static_cast<double*>(ctx->scratch[2].p) : nullptr);
+    const size_t n = (size_t)std::min(CHUNK, n_rows - first) * ATTPC_NUM_TB;  // samples (the first chunk is the largest)
+    const int16_t* d_samples = stage_in(ctx, 0, samples + first * ATTPC_NUM_TB, n, rc);
+    int16_t* d_y = stage<int16_t>(ctx, 1, n, rc);
+    double* d_baseline = baseline ? stage<double>(ctx, 2, n, rc) : nullptr;
+    if (rc) return rc;
+    launch_baseline(ctx->stream, (uint32_t)(n / ATTPC_NUM_TB), d_samples, static_cast<const double2*>(ctx->bl_twiddle.p),
+                    static_cast<const double*>(ctx->bl_op_filter.p), d_y, d_baseline);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(y + first * ATTPC_NUM_TB, ctx->scratch[1].p, n * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (baseline)
-      HIP_TRY(ctx, hipMemcpyAsync(baseline + first * ATTPC_NUM_TB, ctx->scratch[2].p, n * ATTPC_NUM_TB * sizeof(double),
-                                  hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = stage_out(ctx, y + first * ATTPC_NUM_TB, d_y, n))) return rc;
+    if (baseline && (rc = stage_out(ctx, baseline + first * ATTPC_NUM_TB, d_baseline, n))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return ATTPC_OK;
@@ -3456,9 +3405,8 @@ int32_t upload_trigger(attpc_ctx* ctx, const attpc_trigger_desc* d, DevBuf& buf,
         return fail(ctx, ATTPC_E_INVALID, "trigger group %d of pad %d: below %d, or 255", g, p, ATTPC_MAX_TRIGGER_GROUPS);
       if (g != 255) n_groups = std::max(n_groups, g + 1);
     }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int32_t rc;
-  if ((rc = sync_all(ctx))) return rc;
+  int32_t rc = begin_configure(ctx);
+  if (rc) return rc;
   if (d->groups) {
     if ((rc = ensure(ctx, buf, ATTPC_NUM_PADS))) return rc;
     HIP_TRY(ctx, hipMemcpy(buf.p, d->groups, ATTPC_NUM_PADS, hipMemcpyHostToDevice));
@@ -3472,8 +3420,7 @@ int32_t upload_trigger(attpc_ctx* ctx, const attpc_trigger_desc* d, DevBuf& buf,
 int32_t attpc_trace_configure_trigger(attpc_ctx* ctx, const attpc_trigger_desc* d) {
   if (!ctx) return ATTPC_E_INVALID;
   if (!d) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+    { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
     ctx->trigger_on = false;
     return ATTPC_OK;
   }
@@ -3490,9 +3437,7 @@ int32_t attpc_trigger_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_t
   if (!ctx) return ATTPC_E_INVALID;
   if (ctx->trigger_call_events < 0)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trigger_last: no trigger was configured for the last trace call");
-  if (first < 0 || count < 0 || first > ctx->trigger_call_events || count > ctx->trigger_call_events - first)
-    return fail(ctx, ATTPC_E_INVALID, "attpc_trigger_last: records %lld .. + %lld of a call of %lld events", (long long)first,
-                (long long)count, (long long)ctx->trigger_call_events);
+  if (const ArgError bad = records_range_error(__func__, first, count, ctx->trigger_call_events)) return refuse(ctx, bad);
   if (count == 0) return ATTPC_OK;
   if (!out) return ATTPC_E_INVALID;
   std::memcpy(out, ctx->h_trigger.p + first, (size_t)count * sizeof(attpc_trigger_record));
@@ -3502,22 +3447,14 @@ int32_t attpc_trigger_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_t
 int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const int32_t* pads, const int16_t* samples,
                            const int16_t* pedestals, const attpc_trigger_desc* d, attpc_trigger_record* out) {
   if (!ctx || n_events < 0 || !d) return ATTPC_E_INVALID;
-  if (n_events > 0 && (!offsets || !out)) return ATTPC_E_INVALID;
-  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_trigger_rows takes at most 2^31 - 1 events per call");
-  if (n_events > 0 && offsets[0] < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
-  for (int64_t e = 0; e < n_events; ++e) {
-    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %lld", (long long)e);
-    if (offsets[e + 1] - offsets[e] > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "event %lld has 2^31 rows or more", (long long)e);
-  }
+  if (n_events > 0 && !out) return ATTPC_E_INVALID;
+  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
   const int64_t r0 = n_events ? offsets[0] : 0, r1 = n_events ? offsets[n_events] : 0;
   if (r1 > r0 && (!pads || !samples)) return ATTPC_E_INVALID;
   for (int64_t r = r0; r < r1; ++r)
     if (pads[r] < 0 || pads[r] >= ATTPC_NUM_PADS)
       return fail(ctx, ATTPC_E_INVALID, "row %lld: pad %d outside 0 .. %d", (long long)r, pads[r], ATTPC_NUM_PADS - 1);
-  for (int64_t i = r0 * ATTPC_NUM_TB; i < r1 * ATTPC_NUM_TB; ++i)
-    if (samples[i] < 0 || samples[i] > 4095)
-      return fail(ctx, ATTPC_E_INVALID, "sample %lld of row %lld is %d: 0 .. 4095", (long long)(i % ATTPC_NUM_TB),
-                  (long long)(i / ATTPC_NUM_TB), (int)samples[i]);
+  if (const ArgError bad = sample_error(samples, r0, r1)) return refuse(ctx, bad);
   if (pedestals)
     for (int p = 0; p < ATTPC_NUM_PADS; ++p)
       if (pedestals[p] < 0 || pedestals[p] > 4095)
@@ -3526,39 +3463,28 @@ int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int64_t* offs
   int32_t rc;
   if ((rc = upload_trigger(ctx, d, ctx->tg_op_groups, &a.tg))) return rc;  // (checks, device, sync_all)
   if (n_events == 0) return ATTPC_OK;
-  if (pedestals) {
-    if ((rc = ensure(ctx, ctx->scratch[4], ATTPC_NUM_PADS * sizeof(int16_t)))) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->scratch[4].p, pedestals, ATTPC_NUM_PADS * sizeof(int16_t), hipMemcpyHostToDevice));
-    a.pedestals = static_cast<const int16_t*>(ctx->scratch[4].p);
+  if (pedestals) {  // (a blocking copy, as it has always been: the slot is not one of the chunks')
+    int16_t* d_pedestals = stage<int16_t>(ctx, 4, ATTPC_NUM_PADS, rc);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(d_pedestals, pedestals, ATTPC_NUM_PADS * sizeof(int16_t), hipMemcpyHostToDevice));
+    a.pedestals = d_pedestals;
   }
   constexpr int64_t CHUNK_ROWS = 16384, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> start;
-  for (int64_t e0 = 0; e0 < n_events;) {
-    int64_t e1 = e0 + 1;
-    while (e1 < n_events && e1 - e0 < CHUNK_EVENTS && offsets[e1 + 1] - offsets[e0] <= CHUNK_ROWS) ++e1;
-    const size_t m = (size_t)(e1 - e0), rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(rows, 1);
-    start.resize(m + 1);
-    for (size_t e = 0; e <= m; ++e) start[e] = offsets[e0 + (int64_t)e] - offsets[e0];
-    if ((rc = ensure(ctx, ctx->scratch[0], cap * ATTPC_NUM_TB * sizeof(int16_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[1], cap * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[2], (m + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[3], m * sizeof(attpc_trigger_record)))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, start.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (rows) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, samples + offsets[e0] * ATTPC_NUM_TB, rows * ATTPC_NUM_TB * sizeof(int16_t),
-                                  hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, pads + offsets[e0], rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    a.kept_start = static_cast<const int64_t*>(ctx->scratch[2].p);
-    a.pads = static_cast<const int32_t*>(ctx->scratch[1].p);
-    a.samples = static_cast<const int16_t*>(ctx->scratch[0].p);
-    a.records = static_cast<attpc_trigger_record*>(ctx->scratch[3].p);
+  for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
+    e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
+    const size_t m = (size_t)(e1 - e0), rows = (size_t)(offsets[e1] - offsets[e0]);
+    chunk_starts(offsets, e0, e1, &start);
+    a.kept_start = stage_in(ctx, 2, start.data(), m + 1, rc);
+    a.samples = stage_in(ctx, 0, rows ? samples + offsets[e0] * ATTPC_NUM_TB : nullptr, rows * ATTPC_NUM_TB, rc, ATTPC_NUM_TB);
+    a.pads = stage_in(ctx, 1, rows ? pads + offsets[e0] : nullptr, rows, rc, 1);
+    a.records = stage<attpc_trigger_record>(ctx, 3, m, rc);
+    if (rc) return rc;
     a.row_pass = nullptr;
     launch_trigger(ctx->stream, (uint32_t)m, a);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(out + e0, ctx->scratch[3].p, m * sizeof(attpc_trigger_record), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = stage_out(ctx, out + e0, a.records, m))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    e0 = e1;
   }
   return ATTPC_OK;
 }
@@ -3568,8 +3494,7 @@ int32_t attpc_trace_configure_estimates(attpc_ctx* ctx, const attpc_estimate_des
   if (!ctx) return ATTPC_E_INVALID;
   if (d)
     if (const char* bad = estimate_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
   ctx->estimates_on = d != nullptr;
   if (d) ctx->estimates = *d;
   return ATTPC_OK;
@@ -3579,9 +3504,7 @@ int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc
   if (!ctx) return ATTPC_E_INVALID;
   if (ctx->est_call_events < 0)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_estimates_last: the last trace-row call made no track estimates");
-  if (first < 0 || count < 0 || first > ctx->est_call_events || count > ctx->est_call_events - first)
-    return fail(ctx, ATTPC_E_INVALID, "attpc_estimates_last: records %lld .. + %lld of a call of %lld events", (long long)first,
-                (long long)count, (long long)ctx->est_call_events);
+  if (const ArgError bad = records_range_error(__func__, first, count, ctx->est_call_events)) return refuse(ctx, bad);
   const size_t n_sim = (size_t)ctx->est_call_n_sim;
   if (count == 0 || n_sim == 0) return ATTPC_OK;
   if (!out) return ATTPC_E_INVALID;
@@ -3596,13 +3519,8 @@ int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* off
     return fail(ctx, ATTPC_E_INVALID, "attpc_rows_estimate: n_sim %d outside 0 .. %d", layout->n_sim, ATTPC_MAX_SIM);
   if (const char* bad = estimate_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
   const size_t n_sim = (size_t)layout->n_sim;
-  if (n_events > 0 && (!offsets || (n_sim && !out))) return ATTPC_E_INVALID;
-  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_rows_estimate takes at most 2^31 - 1 events per call");
-  if (n_events > 0 && offsets[0] < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
-  for (int64_t e = 0; e < n_events; ++e) {
-    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %lld", (long long)e);
-    if (offsets[e + 1] - offsets[e] > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "event %lld has 2^31 rows or more", (long long)e);
-  }
+  if (n_events > 0 && n_sim && !out) return ATTPC_E_INVALID;
+  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
   if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !labels)) return ATTPC_E_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc;
@@ -3614,31 +3532,19 @@ int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* off
   a.n_sim = (int32_t)n_sim;
   constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> start;
-  for (int64_t e0 = 0; e0 < n_events;) {
-    int64_t e1 = e0 + 1;
-    while (e1 < n_events && e1 - e0 < CHUNK_EVENTS && offsets[e1 + 1] - offsets[e0] <= CHUNK_ROWS) ++e1;
-    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
-    start.resize(m + 1);
-    for (size_t e = 0; e <= m; ++e) start[e] = offsets[e0 + (int64_t)e] - offsets[e0];
-    if ((rc = ensure(ctx, ctx->scratch[0], cap * 8 * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[1], cap * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[2], (m + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[3], m * n_sim * sizeof(attpc_track_estimate)))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, start.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (n_rows) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, rows + offsets[e0] * 8, n_rows * 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, labels + offsets[e0], n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    a.ev_start = static_cast<const int64_t*>(ctx->scratch[2].p);
-    a.rows = static_cast<const double*>(ctx->scratch[0].p);
-    a.labels = static_cast<const int64_t*>(ctx->scratch[1].p);
-    a.records = static_cast<attpc_track_estimate*>(ctx->scratch[3].p);
+  for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
+    e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
+    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]);
+    chunk_starts(offsets, e0, e1, &start);
+    a.ev_start = stage_in(ctx, 2, start.data(), m + 1, rc);
+    a.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
+    a.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
+    a.records = stage<attpc_track_estimate>(ctx, 3, m * n_sim, rc);
+    if (rc) return rc;
     launch_estimates(ctx->stream, (uint32_t)m, a);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(out + (size_t)e0 * n_sim, ctx->scratch[3].p, m * n_sim * sizeof(attpc_track_estimate), hipMemcpyDeviceToHost,
-                                ctx->stream));
+    if ((rc = stage_out(ctx, out + (size_t)e0 * n_sim, a.records, m * n_sim))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    e0 = e1;
   }
   return ATTPC_OK;
 }
@@ -3648,8 +3554,7 @@ int32_t attpc_trace_configure_thinning(attpc_ctx* ctx, const attpc_thin_desc* d)
   if (!ctx) return ATTPC_E_INVALID;
   if (d)
     if (const char* bad = thin_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "thinning: %s", bad);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
   ctx->thinning_on = d != nullptr;
   if (d) ctx->thinning = *d;
   return ATTPC_OK;
@@ -3663,13 +3568,8 @@ int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets
     return fail(ctx, ATTPC_E_INVALID, "attpc_rows_thin: n_sim %d outside 0 .. %d", layout->n_sim, ATTPC_MAX_SIM);
   if (const char* bad = thin_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "thinning: %s", bad);
   const size_t n_sim = (size_t)layout->n_sim;
-  if (!point_offsets || (n_events > 0 && (!offsets || (n_sim && !info)))) return ATTPC_E_INVALID;
-  if (n_events > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "attpc_rows_thin takes at most 2^31 - 1 events per call");
-  if (n_events > 0 && offsets[0] < 0) return fail(ctx, ATTPC_E_INVALID, "offsets[0] < 0");
-  for (int64_t e = 0; e < n_events; ++e) {
-    if (offsets[e + 1] < offsets[e]) return fail(ctx, ATTPC_E_INVALID, "offsets decrease at event %lld", (long long)e);
-    if (offsets[e + 1] - offsets[e] > (int64_t)INT32_MAX) return fail(ctx, ATTPC_E_INVALID, "event %lld has 2^31 rows or more", (long long)e);
-  }
+  if (!point_offsets || (n_events > 0 && n_sim && !info)) return ATTPC_E_INVALID;
+  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
   if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !labels)) return ATTPC_E_INVALID;
   if (capacity > 0 && (!points || !point_labels)) return ATTPC_E_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3690,34 +3590,22 @@ int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets
   std::vector<int64_t> start;
   std::vector<ThinPoint> sparse;  // the chunk's point buffer: the regions of its (event, position)s
   int64_t total = 0;              // points so far
-  for (int64_t e0 = 0; e0 < n_events;) {
-    int64_t e1 = e0 + 1;
-    while (e1 < n_events && e1 - e0 < CHUNK_EVENTS && offsets[e1 + 1] - offsets[e0] <= CHUNK_ROWS) ++e1;
+  for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
+    e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
     const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
-    start.resize(m + 1);
-    for (size_t e = 0; e <= m; ++e) start[e] = offsets[e0 + (int64_t)e] - offsets[e0];
-    if ((rc = ensure(ctx, ctx->scratch[0], cap * 8 * sizeof(double)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[1], cap * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[2], (m + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[3], cap * sizeof(ThinPoint)))) return rc;
-    if ((rc = ensure(ctx, ctx->scratch[4], m * n_sim * sizeof(attpc_thin_info)))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, start.data(), (m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (n_rows) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, rows + offsets[e0] * 8, n_rows * 8 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, labels + offsets[e0], n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    a.ev_start = static_cast<const int64_t*>(ctx->scratch[2].p);
-    a.rows = static_cast<const double*>(ctx->scratch[0].p);
-    a.labels = static_cast<const int64_t*>(ctx->scratch[1].p);
-    a.points = static_cast<ThinPoint*>(ctx->scratch[3].p);
-    a.info = static_cast<attpc_thin_info*>(ctx->scratch[4].p);
+    chunk_starts(offsets, e0, e1, &start);
+    a.ev_start = stage_in(ctx, 2, start.data(), m + 1, rc);
+    a.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
+    a.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
+    a.points = stage<ThinPoint>(ctx, 3, cap, rc);
+    a.info = stage<attpc_thin_info>(ctx, 4, m * n_sim, rc);
+    if (rc) return rc;
     launch_thin(ctx->stream, (uint32_t)m, a);
     HIP_TRY(ctx, hipGetLastError());
     sparse.resize(cap);
     attpc_thin_info* chunk_info = info + (size_t)e0 * n_sim;
-    HIP_TRY(ctx, hipMemcpyAsync(chunk_info, ctx->scratch[4].p, m * n_sim * sizeof(attpc_thin_info), hipMemcpyDeviceToHost, ctx->stream));
-    if (n_rows)
-      HIP_TRY(ctx, hipMemcpyAsync(sparse.data(), ctx->scratch[3].p, n_rows * sizeof(ThinPoint), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = stage_out(ctx, chunk_info, a.info, m * n_sim))) return rc;
+    if (n_rows && (rc = stage_out(ctx, sparse.data(), a.points, n_rows))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // the regions -> CSR, position-major per event
     for (size_t e = 0; e < m; ++e) {
@@ -3742,7 +3630,6 @@ int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets
       }
       point_offsets[e0 + (int64_t)e + 1] = total;
     }
-    e0 = e1;
   }
   *needed = total;
   if (total > capacity)
@@ -3804,9 +3691,8 @@ int32_t attpc_sim_hint_next(attpc_ctx* ctx, uint64_t seed, uint64_t first_event,
 int32_t attpc_spyral_configure(attpc_ctx* ctx, const attpc_spyral_desc* d) {
   if (!ctx || !d || !d->response || !d->pad_centers || !d->pad_sizes || d->n_pads < 1) return ATTPC_E_INVALID;
   if (d->windows_edge <= d->micromegas_edge) return fail(ctx, ATTPC_E_INVALID, "windows_edge <= micromegas_edge");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  { int32_t rc0 = sync_all(ctx); if (rc0) return rc0; }
-  free_all(ctx->spyral_allocs);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->spyral_allocs.clear();
   ctx->spyral_ready = false;
   SpyralDev sp{};
   static_assert(SPYRAL_SAMPLES == ATTPC_NUM_TB, "spyral_integral.hpp: one table entry per response sample");
@@ -3948,22 +3834,18 @@ extern "C" int32_t attpc_spyral_rows(attpc_ctx* ctx, int64_t n_points, const dou
   if (!ctx || !points || !response || !pad_centers || !pad_sizes || !rows || n_pads < 1) return ATTPC_E_INVALID;
   if (n_points <= 0) return ATTPC_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int32_t rc;
+  int32_t rc = ATTPC_OK;
   const size_t n = (size_t)n_points;
-  if ((rc = ensure(ctx, ctx->scratch[0], n * 3 * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[1], ATTPC_NUM_TB * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[2], (size_t)n_pads * 2 * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[3], (size_t)n_pads * sizeof(double)))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch[4], n * 8 * sizeof(double)))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[0].p, points, n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[1].p, response, ATTPC_NUM_TB * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[2].p, pad_centers, (size_t)n_pads * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[3].p, pad_sizes, (size_t)n_pads * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  attpc::launch_spyral_rows_kernel(ctx->stream, n_points, static_cast<const double*>(ctx->scratch[0].p), static_cast<const double*>(ctx->scratch[1].p),
-                                   static_cast<const double*>(ctx->scratch[2].p), static_cast<const double*>(ctx->scratch[3].p), n_pads,
-                                   (double)windows_edge, (double)micromegas_edge, length, static_cast<double*>(ctx->scratch[4].p));
+  const double* d_points = stage_in(ctx, 0, points, n * 3, rc);
+  const double* d_response = stage_in(ctx, 1, response, (size_t)ATTPC_NUM_TB, rc);
+  const double* d_centers = stage_in(ctx, 2, pad_centers, (size_t)n_pads * 2, rc);
+  const double* d_sizes = stage_in(ctx, 3, pad_sizes, (size_t)n_pads, rc);
+  double* d_rows = stage<double>(ctx, 4, n * 8, rc);
+  if (rc) return rc;
+  attpc::launch_spyral_rows_kernel(ctx->stream, n_points, d_points, d_response, d_centers, d_sizes, n_pads, (double)windows_edge,
+                                   (double)micromegas_edge, length, d_rows);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(rows, ctx->scratch[4].p, n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = stage_out(ctx, rows, d_rows, n * 8))) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return ATTPC_OK;
 }
