@@ -43,7 +43,11 @@ __device__ __forceinline__ void two_body(const P4& parent, double m_out, double 
   const double ecm = pcm.t;
   const double mo = m_other + ex;
   const double e_a = (m_out * m_out - mo * mo + ecm * ecm) / (2.0 * ecm);
-  const double p_a = sqrt(e_a * e_a - m_out * m_out);
+  // "allowed" is decided on inv_mass(parent), ecm comes out of the boost: they differ in the last bits, and an allowed
+  // step a hair above its threshold could land on d < 0 and hand NaN momenta on with status 0.  p* = 0 there (DESIGN
+  // section 6, deviation (vi)); not fmax: a NaN input stays a NaN
+  const double d = e_a * e_a - m_out * m_out;
+  const double p_a = sqrt(d < 0.0 ? 0.0 : d);
   double sp, cp, sa, ca;
   sincos(polar, &sp, &cp);
   sincos(azim, &sa, &ca);

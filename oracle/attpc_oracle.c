@@ -145,7 +145,10 @@ static void two_body(const double parent[4], double m_out, double m_other, doubl
   double ecm = parent_cm[3];
   double mo = m_other + ex;
   double e_a = (m_out * m_out - mo * mo + ecm * ecm) / (2.0 * ecm);
-  double p_a = sqrt(e_a * e_a - m_out * m_out);
+  /* an allowed step whose ecm lands a last bit under the threshold: p* = 0, not NaN (deviation
+   * (vi)); a NaN input stays a NaN, which fmax would swallow */
+  double d = e_a * e_a - m_out * m_out;
+  double p_a = sqrt(d < 0.0 ? 0.0 : d);
   double cm[4] = {p_a * sin(polar) * cos(azim), p_a * sin(polar) * sin(azim), p_a * cos(polar), e_a};
   boost_p4(cm, parent, out_a);
   for (int i = 0; i < 4; ++i) out_b[i] = parent[i] - out_a[i];
