@@ -182,6 +182,16 @@ EST_EMPTY, EST_FEW, EST_RANGE, EST_CAPPED, EST_NO_CIRCLE, EST_ON_AXIS, EST_NO_SL
 EST_MAX_FIT = 2048
 
 
+class CircleDesc(C.Structure):
+    _fields_ = [("tolerance", C.c_double), ("max_evaluations", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the geometric circle fit behind the estimates: its status bit, the range of max_evaluations and the defaults
+EST_NOT_CONVERGED = 128
+CIRCLE_MIN_EVALUATIONS, CIRCLE_MAX_EVALUATIONS = 2, 64
+CIRCLE_DEFAULT_EVALUATIONS, CIRCLE_DEFAULT_TOLERANCE = 32, 1.0 / 128.0
+
+
 class ThinDesc(C.Structure):
     _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
 
@@ -399,6 +409,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_estimates", "attpc_estimates_last", "attpc_rows_estimate",
     "attpc_trace_configure_thinning", "attpc_rows_thin",
     "attpc_det_configure_straggling",
+    "attpc_trace_configure_circle", "attpc_rows_estimate_circle",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -440,6 +451,9 @@ THIN_SYMBOLS = ("attpc_trace_configure_thinning", "attpc_rows_thin")
 
 # ... and the track straggling after the thinned track points: the same rule.
 STRAGGLE_SYMBOLS = ("attpc_det_configure_straggling",)
+
+# ... and the geometric circle fit after the track straggling: the same rule.
+CIRCLE_SYMBOLS = ("attpc_trace_configure_circle", "attpc_rows_estimate_circle")
 
 _lib = None
 
@@ -628,6 +642,15 @@ def load_library() -> C.CDLL:
     no_straggling = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in STRAGGLE_SYMBOLS)
     if not no_straggling:
         lib.attpc_det_configure_straggling.argtypes = [ctxp, C.POINTER(StraggleDesc)]
+    circle = {
+        "attpc_trace_configure_circle": [ctxp, C.POINTER(CircleDesc)],
+        "attpc_rows_estimate_circle": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
+                                       C.POINTER(CircleDesc), C.POINTER(TrackEstimate)],
+    }
+    no_circle = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in CIRCLE_SYMBOLS)
+    for name, argtypes in circle.items():
+        if not no_circle:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -653,7 +676,8 @@ def load_library() -> C.CDLL:
                 or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)
                 or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)
                 or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)
-                or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)):
+                or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)
+                or (no_circle and name in CIRCLE_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -663,7 +687,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle")
 
 
 class Context:

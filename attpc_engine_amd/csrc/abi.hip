@@ -36,6 +36,7 @@
 #include "trace_pack_host.hpp"
 #include "unpack_host.hpp"
 #include "spyral_integral.hpp"  // (behind the HIP runtime header)
+#include "circle_host.hpp"
 #include "estimate_host.hpp"
 #include "thin_host.hpp"
 #include "straggle_host.hpp"
@@ -254,6 +255,8 @@ struct attpc_ctx {
   int32_t est_call_n_sim = 0;      // positions of its layout
   bool thinning_on = false;        // attpc_trace_configure_thinning (inert while the estimates are off)
   attpc_thin_desc thinning{};
+  bool circle_on = false;          // attpc_trace_configure_circle (inert while the estimates are off)
+  attpc_circle_desc circle{};
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -1075,6 +1078,12 @@ void estimate_settings(const attpc_estimate_desc& d, EstimateArgs* a) {
   a->magnetic_field = d.magnetic_field;
 }
 
+// The refining kernel's settings from a checked desc.
+void circle_settings(const attpc_circle_desc& d, EstimateArgs* a) {
+  a->circle_tolerance = d.tolerance;
+  a->circle_max_evaluations = d.max_evaluations;
+}
+
 // The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none and makes no records):
 // room for its track estimates (attpc_estimates_last), if the stage is on.  Nothing of an earlier call is in flight.
 int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay) {
@@ -1090,7 +1099,8 @@ int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout
 
 // The track estimates of the chunk in `as` (n events, rows written: directly behind launch_peak_rows) on S, as.traced
 // recorded again behind them, and the copy of the records to events first_local .. of the call's pinned array on C.
-// With thinning on the rows are thinned first (thin.hip) and the estimates are those of the points.
+// With thinning on the rows are thinned first (thin.hip) and the estimates are those of the points; with the geometric
+// circle fit on the estimate kernel is its refining instantiation.
 int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first_local) {
   const size_t n_sim = (size_t)ctx->est_call_n_sim;
   if (!n || !n_sim) return ATTPC_OK;
@@ -1122,10 +1132,14 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
     HIP_TRY(ctx, hipGetLastError());
     a.points = t.points;
     a.thin_info = t.info;
-    launch_point_estimates(ctx->stream, n, a);
-  } else {
-    launch_estimates(ctx->stream, n, a);
   }
+  if (ctx->circle_on) {
+    circle_settings(ctx->circle, &a);
+    launch_circle_estimates(ctx->stream, n, a, ctx->thinning_on);
+  } else if (ctx->thinning_on)
+    launch_point_estimates(ctx->stream, n, a);
+  else
+    launch_estimates(ctx->stream, n, a);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
@@ -3512,15 +3526,20 @@ int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc
   return ATTPC_OK;
 }
 
-int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
-                            const attpc_event_layout* layout, const attpc_estimate_desc* d, attpc_track_estimate* out) {
+namespace {
+// attpc_rows_estimate (circle == nullptr) and attpc_rows_estimate_circle under the name `func`
+int32_t rows_estimate(attpc_ctx* ctx, const char* func, int64_t n_events, const int64_t* offsets, const double* rows,
+                      const int64_t* labels, const attpc_event_layout* layout, const attpc_estimate_desc* d,
+                      const attpc_circle_desc* circle, attpc_track_estimate* out) {
   if (!ctx || n_events < 0 || !d || !layout) return ATTPC_E_INVALID;
   if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
-    return fail(ctx, ATTPC_E_INVALID, "attpc_rows_estimate: n_sim %d outside 0 .. %d", layout->n_sim, ATTPC_MAX_SIM);
+    return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", func, layout->n_sim, ATTPC_MAX_SIM);
   if (const char* bad = estimate_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
+  if (circle)
+    if (const char* bad = circle_desc_error(*circle)) return fail(ctx, ATTPC_E_INVALID, "circle: %s", bad);
   const size_t n_sim = (size_t)layout->n_sim;
   if (n_events > 0 && n_sim && !out) return ATTPC_E_INVALID;
-  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
+  if (const ArgError bad = csr_error(func, n_events, offsets)) return refuse(ctx, bad);
   if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !labels)) return ATTPC_E_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc;
@@ -3530,6 +3549,7 @@ int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* off
   estimate_settings(*d, &a);
   estimate_positions(*layout, a.slot_label);
   a.n_sim = (int32_t)n_sim;
+  if (circle) circle_settings(*circle, &a);
   constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> start;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
@@ -3541,12 +3561,39 @@ int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* off
     a.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
     a.records = stage<attpc_track_estimate>(ctx, 3, m * n_sim, rc);
     if (rc) return rc;
-    launch_estimates(ctx->stream, (uint32_t)m, a);
+    if (circle)
+      launch_circle_estimates(ctx->stream, (uint32_t)m, a, false);
+    else
+      launch_estimates(ctx->stream, (uint32_t)m, a);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = stage_out(ctx, out + (size_t)e0 * n_sim, a.records, m * n_sim))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return ATTPC_OK;
+}
+}  // namespace
+
+int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                            const attpc_event_layout* layout, const attpc_estimate_desc* d, attpc_track_estimate* out) {
+  return rows_estimate(ctx, __func__, n_events, offsets, rows, labels, layout, d, nullptr, out);
+}
+
+// ---- geometric circle fit (estimate.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_circle(attpc_ctx* ctx, const attpc_circle_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = circle_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "circle: %s", bad);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->circle_on = d != nullptr;
+  if (d) ctx->circle = *d;
+  return ATTPC_OK;
+}
+
+int32_t attpc_rows_estimate_circle(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                   const int64_t* labels, const attpc_event_layout* layout, const attpc_estimate_desc* d,
+                                   const attpc_circle_desc* circle, attpc_track_estimate* out) {
+  if (!circle) return ATTPC_E_INVALID;
+  return rows_estimate(ctx, __func__, n_events, offsets, rows, labels, layout, d, circle, out);
 }
 
 // ---- thinned track points (thin.hip; the contract is in include/attpc_engine.h) ----

@@ -15,11 +15,21 @@
 // The second pass reads the rows of the first again (72 B per row of the label, out of L2).  All lanes evaluate the
 // closed form (it is wave-uniform); lane 0 stores the record.
 //
-// estimate_kernel<true> is the same body on thinned points (thin.hip, "thinned track points" in the header): the rows
-// of position s are the points of its region of the chunk's point buffer -- every one of them matches --, a point is
-// out of range at |SI| >= 2^31, and RANGE is set from the start if thinning dropped a row of the label.
+// estimate_kernel<true, *> is the same body on thinned points (thin.hip, "thinned track points" in the header): the
+// rows of position s are the points of its region of the chunk's point buffer -- every one of them matches --, a point
+// is out of range at |SI| >= 2^31, and RANGE is set from the start if thinning dropped a row of the label.
+//
+// estimate_kernel<*, true> is the same body again with the geometric circle fit behind the Kasa circle ("geometric
+// circle fit" in the header; its arithmetic is circle_host.hpp, shared with the host).  Pass B knows every segment
+// row's rank, so it parks the row's (u, v) there as one packed word (|u|, |v| <= 10 240 fit int16) in the wave's own
+// 8 KiB of LDS: 2 048 points x 4 B x 4 waves = 32 KiB static, in these two instantiations only (with CIRCLE false
+// nothing of it is instantiated: those two kernels are instruction for instruction what they were without it).  An
+// evaluation is then a lane-strided walk over the parked points (rank i in lane i mod 64, ascending) and nine xor-tree
+// reductions; the iteration is wave-uniform, since every lane holds the same sums.  No barrier: a wave reads only what
+// it wrote, and the LDS operations of one wave complete in order.
 #include "tracks_args.hpp"
 
+#include "circle_host.hpp"
 #include "estimate_host.hpp"
 
 namespace attpc {
@@ -96,14 +106,43 @@ __device__ __forceinline__ int32_t est_wave_inclusive(int32_t v, int lane) {
   return v;
 }
 
+__device__ __forceinline__ double est_wave_add(double v) {
+#pragma clang fp contract(off)
+  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
+  return v;
+}
+
+// one evaluation of the circle fit on the wave's m parked points
+__device__ __forceinline__ CircleSums est_circle_evaluate(const uint32_t* parked, int32_t m, int lane, double a, double b,
+                                                          double R) {
+  CircleSums k = circle_zero();
+  for (int32_t i = lane; i < m; i += 64) {
+    const uint32_t word = parked[i];
+    circle_point((int16_t)(word & 0xffffu), (int16_t)(word >> 16), a, b, R, &k);
+  }
+  return CircleSums{est_wave_add(k.f),  est_wave_add(k.uu), est_wave_add(k.uv), est_wave_add(k.vv), est_wave_add(k.u),
+                    est_wave_add(k.v),  est_wave_add(k.gu), est_wave_add(k.gv), est_wave_add(k.g)};
+}
+
+// CIRCLE: the wave's ATTPC_EST_MAX_FIT words of LDS (static, in the instantiations that ask for them only)
+template <bool CIRCLE>
+__device__ __forceinline__ uint32_t* est_parked(int wave) {
+  if constexpr (CIRCLE) {
+    __shared__ uint32_t parked[EST_WAVES][ATTPC_EST_MAX_FIT];
+    return parked[wave];
+  }
+  return nullptr;
+}
+
 }  // namespace
 
-template <bool POINTS>
+template <bool POINTS, bool CIRCLE>
 __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
   const uint32_t e = blockIdx.x;
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int64_t ev_lo = a.ev_start[e], ev_hi = a.ev_start[e + 1];
   const uint64_t below = (1ull << lane) - 1ull;  // the lanes below this one
+  [[maybe_unused]] uint32_t* const parked = est_parked<CIRCLE>(wave);
   for (int s = wave; s < a.n_sim; s += EST_WAVES) {
     attpc_track_estimate rec;
     attpc_track_estimate* out = a.records + (size_t)e * (size_t)a.n_sim + (size_t)s;
@@ -166,6 +205,8 @@ __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
       const int32_t incl = est_wave_inclusive(d, lane);
       if (seg) {
         const int64_t u = row.X - origin.X, v = row.Y - origin.Y, w = row.Z - origin.Z, S = arc + incl;
+        if constexpr (CIRCLE)  // (the rank is < m <= ATTPC_EST_MAX_FIT)
+          parked[count + __popcll(bu & below)] = ((uint32_t)u & 0xffffu) | ((uint32_t)v << 16);
         su += u;
         sv += v;
         suu += u * u;
@@ -213,17 +254,32 @@ __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
     rec.status = (range ? ATTPC_EST_RANGE : 0) | (capped ? ATTPC_EST_CAPPED : 0);
     rec.direction = direction;
     rec.reserved = 0;
-    estimate_closed_form(k, a.magnetic_field, &rec);
+    if constexpr (CIRCLE) {
+      // (the iteration is uniform over the wave: every lane holds the same sums)
+      estimate_closed_form_circle(k, a.magnetic_field, a.circle_tolerance, a.circle_max_evaluations,
+                                  [&](double ta, double tb, double tr) { return est_circle_evaluate(parked, m, lane, ta, tb, tr); },
+                                  &rec);
+    } else {
+      estimate_closed_form(k, a.magnetic_field, &rec);
+    }
     if (lane == 0) *out = rec;
   }
 }
 
+// (the refining instantiations first: the two others then lie in the code object as they did without them)
+void launch_circle_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a, bool points) {
+  if (points)
+    hipLaunchKernelGGL((estimate_kernel<true, true>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  else
+    hipLaunchKernelGGL((estimate_kernel<false, true>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+}
+
 void launch_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a) {
-  hipLaunchKernelGGL(estimate_kernel<false>, dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  hipLaunchKernelGGL((estimate_kernel<false, false>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
 }
 
 void launch_point_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a) {
-  hipLaunchKernelGGL(estimate_kernel<true>, dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  hipLaunchKernelGGL((estimate_kernel<true, false>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
 }
 
 }  // namespace attpc

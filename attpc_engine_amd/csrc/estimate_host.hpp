@@ -55,6 +55,89 @@ struct EstimateSums {  // step 5
   int64_t arc;
 };
 
+// estimate_kasa and estimate_from_circle are step 6 in two halves, for the geometric circle fit between them
+// (circle_host.hpp).  estimate_closed_form below stays the one piece it was: the kernels of the stage off are then
+// instruction for instruction what they were; tests/test_circle_cpu.py holds the halves to it bit for bit.
+// step 6, the Kasa circle of the sums: (uc, vc, r2) in units relative to (X0, Y0); false = there is none (NO_CIRCLE)
+ATTPC_EST_HD bool estimate_kasa(const EstimateSums& k, double* uc_out, double* vc_out, double* r2_out) {
+#pragma clang fp contract(off)
+  const double m = (double)k.m;
+  const double Su = (double)k.su, Sv = (double)k.sv, Suu = (double)k.suu, Suv = (double)k.suv, Svv = (double)k.svv;
+  const double Suuu = (double)k.suuu, Suvv = (double)k.suvv, Svvv = (double)k.svvv, Svuu = (double)k.svuu;
+  const double A = m * Suu - Su * Su;
+  const double B = m * Suv - Su * Sv;
+  const double C = m * Svv - Sv * Sv;
+  const double D = (m * (Suvv + Suuu) - Su * (Suu + Svv)) / 2.0;
+  const double E = (m * (Svuu + Svvv) - Sv * (Suu + Svv)) / 2.0;
+  const double den = A * C - B * B;
+  if (den == 0.0) return false;
+  const double uc = (D * C - B * E) / den;
+  const double vc = (A * E - B * D) / den;
+  const double r2 = (Suu + Svv - 2.0 * uc * Su - 2.0 * vc * Sv) / m + uc * uc + vc * vc;
+  *uc_out = uc;
+  *vc_out = vc;
+  *r2_out = r2;
+  return r2 > 0.0;
+}
+
+// step 6 behind the circle (a, b, R) in units relative to (X0, Y0) -- `circle`: there is one --: the f64 fields, charge
+// and arc of *r, and the status bits it adds
+ATTPC_EST_HD void estimate_from_circle(const EstimateSums& k, double magnetic_field, bool circle, double a, double b_units,
+                                       double R, attpc_track_estimate* r) {
+#pragma clang fp contract(off)
+  const double nan = __builtin_nan("");
+  const double m = (double)k.m, X0 = (double)k.x0, Y0 = (double)k.y0, Z0 = (double)k.z0;
+  const double Su = (double)k.su, Sv = (double)k.sv;
+  const double SS = (double)k.ss, Sw = (double)k.sw, SSS = (double)k.sss, SSw = (double)k.ssw;
+  int32_t status = 0;
+  double cx = nan, cy = nan, radius = nan, vx = nan, vy = nan;
+  if (circle) {
+    cx = (X0 + a) / 16.0;
+    cy = (Y0 + b_units) / 16.0;
+    radius = R / 16.0;
+  }
+  bool vertex = circle;
+  if (!circle) status |= ATTPC_EST_NO_CIRCLE;
+  if (circle) {
+    const double c = sqrt(cx * cx + cy * cy);
+    if (c == 0.0) {
+      status |= ATTPC_EST_ON_AXIS;
+      vertex = false;
+    } else {
+      vx = cx * (1.0 - radius / c);
+      vy = cy * (1.0 - radius / c);
+    }
+  }
+  const double sden = m * SSS - SS * SS;
+  double b = nan, vz = nan, brho = nan;
+  if (sden == 0.0) {
+    status |= ATTPC_EST_NO_SLOPE;
+  } else {
+    b = (m * SSw - SS * Sw) / sden;
+    if (vertex) {
+      const double a0 = (Sw - b * SS) / m;
+      const double gx = X0 - 16.0 * vx, gy = Y0 - 16.0 * vy;
+      const double chord0 = sqrt(gx * gx + gy * gy);
+      vz = (Z0 + a0 - b * chord0) / 16.0;
+    }
+    if (circle) brho = magnetic_field * radius * 1.0e-3 * sqrt(1.0 + b * b);
+  }
+  r->status |= status;
+  r->charge = k.si;
+  r->arc = k.arc;
+  r->cx = cx;
+  r->cy = cy;
+  r->radius = radius;
+  r->vx = vx;
+  r->vy = vy;
+  r->vz = vz;
+  r->slope = b;
+  r->x_mean = (X0 + Su / m) / 16.0;
+  r->y_mean = (Y0 + Sv / m) / 16.0;
+  r->dedx = k.arc == 0 ? nan : (double)k.si / ((double)k.arc / 16.0);
+  r->brho = brho;
+}
+
 // step 6: the f64 fields, charge and arc of *r, and the status bits it adds
 ATTPC_EST_HD void estimate_closed_form(const EstimateSums& k, double magnetic_field, attpc_track_estimate* r) {
 #pragma clang fp contract(off)

@@ -253,11 +253,17 @@ struct EstimateArgs {
   // the estimates of thinned points (launch_point_estimates) read these in the place of rows and labels
   const ThinPoint* points;            // [rows] the regions thin_kernel filled
   const attpc_thin_info* thin_info;   // [n_events][n_sim]
+  // the geometric circle fit (launch_circle_estimates) reads these
+  double circle_tolerance;            // units
+  int32_t circle_max_evaluations;     // 2 .. 64
 };
 // one workgroup per event, empty events included (n_events > 0, n_sim > 0)
 void launch_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a);
 // the same on the thinned points of every (event, position): a.points and a.thin_info as launch_thin left them
 void launch_point_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a);
+// launch_estimates (points = false) or launch_point_estimates (points = true) with the geometric circle fit behind the
+// Kasa circle (attpc_trace_configure_circle, "geometric circle fit" in the header): a.circle_* are set
+void launch_circle_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a, bool points);
 
 // thinned track points (thin.hip; attpc_trace_configure_thinning, the contract is in include/attpc_engine.h)
 struct ThinArgs {

@@ -15,12 +15,12 @@ import math
 import numpy as np
 
 from .. import _abi
-from .._abi import (ESTIMATE_DTYPE, EST_CAPPED, EST_EMPTY, EST_FEW, EST_MAX_FIT, EST_NO_CIRCLE, EST_NO_SLOPE,  # noqa: F401
-                    EST_ON_AXIS, EST_RANGE)
+from .._abi import (ESTIMATE_DTYPE, EST_CAPPED, EST_EMPTY, EST_FEW, EST_MAX_FIT, EST_NOT_CONVERGED, EST_NO_CIRCLE,  # noqa: F401
+                    EST_NO_SLOPE, EST_ON_AXIS, EST_RANGE)
 from .traces import configure_stage
 
 STATUS_BITS = {"EMPTY": EST_EMPTY, "FEW": EST_FEW, "RANGE": EST_RANGE, "CAPPED": EST_CAPPED, "NO_CIRCLE": EST_NO_CIRCLE,
-               "ON_AXIS": EST_ON_AXIS, "NO_SLOPE": EST_NO_SLOPE}
+               "ON_AXIS": EST_ON_AXIS, "NO_SLOPE": EST_NO_SLOPE, "NOT_CONVERGED": EST_NOT_CONVERGED}
 C_MEV_PER_TM = 299.792458  # p [MeV/c] = 299.792458 Z B rho [T m]
 
 
@@ -93,13 +93,17 @@ def _layout(indices) -> _abi.EventLayout:
 
 
 def rows_to_estimates(offsets, rows, labels, indices, settings: EstimateSettings, ctx: _abi.Context | None = None,
-                      config=None) -> np.ndarray:
+                      config=None, circle=None) -> np.ndarray:
     """The estimate stage alone on any host rows in CSR form (``attpc_rows_estimate``; the kernel of the fused path, no
     other configuration needed): offsets [n+1], rows [R,8] as ``run_trace_rows`` / ``run_spyral`` deliver them, labels
     [R], ``indices`` (the nucleus of every track position) -> records [n, len(indices)] (``ESTIMATE_DTYPE``).  The field
-    is the settings' own, else ``config.det_params.bfield``."""
+    is the settings' own, else ``config.det_params.bfield``.  ``circle`` (a ``detector.circle.CircleFitSettings``; None =
+    off): the geometric circle fit behind the Kasa circle (``attpc_rows_estimate_circle``)."""
+    from .circle import _checked as _checked_circle
+
     if not isinstance(settings, EstimateSettings):
         raise TypeError("settings must be an EstimateSettings")
+    _checked_circle(circle)
     if config is not None:
         settings = settings.for_field(config.det_params.bfield)
     desc = settings.desc()
@@ -114,6 +118,11 @@ def rows_to_estimates(offsets, rows, labels, indices, settings: EstimateSettings
     n = len(offsets) - 1
     records = np.empty((n, layout.n_sim), dtype=ESTIMATE_DTYPE)
     ctx = ctx or _abi.default_context()
+    if circle is not None:
+        ctx.check(ctx.lib.attpc_rows_estimate_circle(ctx.handle, n, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(rows),
+                                                     _abi.iptr(labels, _abi.C.c_int64), layout, desc, circle.desc(),
+                                                     _abi.iptr(records, _abi.TrackEstimate)), "attpc_rows_estimate_circle")
+        return records
     ctx.check(ctx.lib.attpc_rows_estimate(ctx.handle, n, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(rows),
                                           _abi.iptr(labels, _abi.C.c_int64), layout, desc,
                                           _abi.iptr(records, _abi.TrackEstimate)), "attpc_rows_estimate")

@@ -232,6 +232,12 @@ def _checked_thinning(thinning):
     return _checked(thinning)
 
 
+def _checked_circle(circle):
+    from .circle import _checked
+
+    return _checked(circle)
+
+
 def _checked_common_mode(common_mode):
     if common_mode is not None and not isinstance(common_mode, CommonModeSettings):
         raise TypeError("common_mode must be a CommonModeSettings or None")
@@ -388,18 +394,20 @@ class TraceChain:
     ``threshold`` and ``offset`` with their defaults filled in (``trace_settings``), the ``noise`` (a ``NoiseSettings``;
     None = off) and the ``readout`` (a ``ReadoutSettings``; None = hit pads), and the stages that are None when off:
     ``gain``, ``peaks`` (trace rows; None = ``PeakSettings()``), ``baseline``, ``trigger``, ``common_mode``,
-    ``estimates`` (trace rows: a ``detector.estimate.EstimateSettings``) and ``thinning`` (the rows in front of the
-    estimates: a ``detector.thinning.ThinSettings``)."""
+    ``estimates`` (trace rows: a ``detector.estimate.EstimateSettings``), ``thinning`` (the rows in front of the
+    estimates: a ``detector.thinning.ThinSettings``) and ``circle`` (the geometric circle fit behind them: a
+    ``detector.circle.CircleFitSettings``)."""
 
     def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
                  gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
-                 thinning=None):
+                 thinning=None, circle=None):
         self.config, self._given = config, (response, threshold)
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
         self.gain, self.peaks, self.baseline, self.trigger = _checked_gain(gain), peaks, baseline, trigger
         self.common_mode = _checked_common_mode(common_mode)
         self.estimates, self.thinning = _checked_estimates(estimates), _checked_thinning(thinning)
+        self.circle = _checked_circle(circle)
 
     @classmethod
     def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
@@ -414,11 +422,11 @@ class TraceChain:
                    ReadoutSettings(get("readout", "hit"), get("readout_pads")))
 
     def replace(self, **fields) -> "TraceChain":
-        """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning;
-        TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning"}
+        """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning,
+        circle; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle"}
         if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates and thinning, not {sorted(unknown)}")
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning and circle, not {sorted(unknown)}")
         chain = copy.copy(self)
         vars(chain).update(fields)
         if "config" in fields:
@@ -427,14 +435,15 @@ class TraceChain:
         _checked_common_mode(chain.common_mode)
         _checked_estimates(chain.estimates)
         _checked_thinning(chain.thinning)
+        _checked_circle(chain.circle)
         return chain
 
     def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
         """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
         trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
-        baseline; trigger; gain; with ``rows`` the track estimates and the thinning in front of them.  A stage that is
+        baseline; trigger; gain; with ``rows`` the track estimates, the thinning in front of them and the circle fit behind them.  A stage that is
         off is turned off, whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode"
-        and "estimates" (the thinning with them) that ``keep`` names, which stay as the ctx holds them."""
+        and "estimates" (the thinning and the circle fit with them) that ``keep`` names, which stay as the ctx holds them."""
         from .simulator import configure_spyral
 
         ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
@@ -452,11 +461,13 @@ class TraceChain:
         if "gain" not in keep:
             configure_gain(ctx, self.gain)
         if rows and "estimates" not in keep:
+            from .circle import configure_circle
             from .estimate import configure_estimates
             from .thinning import configure_thinning
 
             configure_estimates(ctx, self.estimates, self.config)
             configure_thinning(ctx, self.thinning)
+            configure_circle(ctx, self.circle)
 
     def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
                   ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False,
@@ -486,11 +497,13 @@ class TraceChain:
                                   per_event, configure, straggling=straggling, **how)
         extra = trigger_result(ctx, len(arrays.offsets) - 1)
         if rows:
+            from .circle import circle_result
             from .estimate import estimates_result
             from .thinning import thinning_result
 
             extra.update(estimates_result(ctx, len(arrays.offsets) - 1, len(indices)))
             extra.update(thinning_result(ctx))
+            extra.update(circle_result(ctx))
         sums = ctx.trace_rows_last() if rows else arrays.sums()
         return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
 
@@ -972,19 +985,24 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
 
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
                          baseline: BaselineSettings | None = None, gain: GainSettings | None = None,
-                         common_mode: CommonModeSettings | None = None, thinning=None, **trace_kwargs) -> None:
+                         common_mode: CommonModeSettings | None = None, thinning=None, circle=None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
     the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
     baseline (default None: off, the peaks stand on the configured pedestals), the micromegas gain and the common-mode
-    noise (default None: off).  The trigger, the track estimates and the thinning stay as the ctx holds them; a
-    ``thinning`` (a ``detector.thinning.ThinSettings``) is configured, None leaves what the ctx holds."""
+    noise (default None: off).  The trigger, the track estimates, the thinning and the circle fit stay as the ctx holds
+    them; a ``thinning`` (a ``detector.thinning.ThinSettings``) or a ``circle`` (a ``detector.circle.CircleFitSettings``)
+    is configured, None leaves what the ctx holds."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
-                                                                   common_mode=common_mode, thinning=thinning)
+                                                                   common_mode=common_mode, thinning=thinning, circle=circle)
     chain.configure(ctx, rows=True, keep=("trigger", "estimates"))
     if thinning is not None:
         from .thinning import configure_thinning
 
         configure_thinning(ctx, chain.thinning)
+    if circle is not None:
+        from .circle import configure_circle
+
+        configure_circle(ctx, chain.circle)
 
 
 def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
@@ -992,7 +1010,7 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               peaks: PeakSettings | None = None, capacity_per_event: int = 2048,
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
-                              estimates=None, thinning=None, straggling=None, **trace_kwargs):
+                              estimates=None, thinning=None, straggling=None, circle=None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -1001,11 +1019,12 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     not fire without rows) its records [n] under ``"trigger"``, and with ``estimates`` (a
     ``detector.estimate.EstimateSettings``; None = off) the track estimates [n, len(indices)] under ``"estimates"`` --
     with ``thinning`` (a ``detector.thinning.ThinSettings``; None = off) those of the thinned points, and its z step
-    under ``"thinning"``).
+    under ``"thinning"``; with ``circle`` (a ``detector.circle.CircleFitSettings``; None = off) their circles refined by
+    the geometric fit, and ``"circle": "geometric"``).
     ``gain``, ``common_mode`` and ``straggling`` as simulate_batch_traces takes them."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
-                                                                   thinning=thinning)
+                                                                   thinning=thinning, circle=circle)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event, straggling=straggling)
 

@@ -18,6 +18,7 @@ from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings
                               configure_baseline, configure_common_mode, configure_gain, configure_peaks, configure_traces,
                               configure_trigger, trigger_result)
 from .detector.estimate import EstimateSettings, configure_estimates, estimates_result
+from .detector.circle import CircleFitSettings, circle_result, configure_circle
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .detector.straggling import StragglingSettings, configure_straggling
 from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
@@ -279,7 +280,8 @@ class Engine:
         trigger configured (``configure_trigger``), its records [n] under ``trigger`` (with its ``gate`` an event that
         did not fire is an empty range of the offsets); with the track estimates configured (``configure_estimates``)
         their records [n, n_sim] under ``estimates`` -- with the thinning configured too (``configure_thinning``) those
-        of the thinned points, and its z step under ``thinning``."""
+        of the thinned points, and its z step under ``thinning``; with the geometric circle fit configured as well
+        (``configure_circle_fit``) their circles are the refined ones, and ``circle`` is "geometric"."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         self._trace_rows_defaults()
         ctx = self.ctx
@@ -288,12 +290,12 @@ class Engine:
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
-                    **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx)}
+                    **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
-                **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx)}
+                **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx)}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -311,6 +313,14 @@ class Engine:
         not of its raw rows, and ``min_points`` counts those points --, neither turns it off (the default).  Without
         the estimates it does nothing."""
         configure_thinning(self.ctx, _settings(ThinSettings, thinning, parameters))
+
+    def configure_circle_fit(self, circle=None, **parameters) -> None:
+        """The geometric circle fit behind the track estimates (include/attpc_engine.h, "geometric circle fit"): a
+        ``detector.circle.CircleFitSettings`` or its keywords (max_evaluations, tolerance in units of 1/16 mm) turn it
+        on -- centre, radius, vertex and B rho of the estimates of ``run_trace_rows`` / ``run_estimates`` then come from
+        the Kasa circle refined by a least-squares fit of the geometric distances, ``reserved`` carries the evaluations
+        made --, neither turns it off (the default).  Without the estimates it does nothing."""
+        configure_circle(self.ctx, _settings(CircleFitSettings, circle, parameters))
 
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
@@ -331,7 +341,8 @@ class Engine:
                                                    out, stats), "attpc_sim_run_trace_rows")
         return {"estimates": ctx.estimates_last(n_events, len(self.indices)), "indices": list(self.indices),
                 "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
-                "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx)}
+                "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx),
+                **circle_result(ctx)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

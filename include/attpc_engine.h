@@ -1211,7 +1211,8 @@ ATTPC_API int32_t attpc_cloud_maps(attpc_ctx* ctx, int64_t n_events, const int64
  * of the trajectory, the polar angle from z against the cumulated pad-plane distance of consecutive points (zig-zag
  * included), B rho = B R / sin(theta), dE/dx = charge over that length -- but THIS CONTRACT, not Spyral's source, is
  * what the device is tested against (tests/estimate_reference.py restates it in numpy), and the circle is the
- * algebraic (Kasa) least-squares fit in closed form, not Spyral's iterative one.
+ * algebraic (Kasa) least-squares fit in closed form, not Spyral's iterative one ("geometric circle fit" below refines
+ * it by an iterative least-squares fit of the geometric distances, opt-in).
  * A "unit" is the quantisation step of the coordinates, 1/16 mm.
  * Settings (attpc_estimate_desc): beam_region_radius in mm, finite and >= 0; min_points >= 3; magnetic_field in T, not
  * NaN; reserved = 0.
@@ -1285,7 +1286,7 @@ typedef struct attpc_track_estimate {
   int32_t n_fit;
   int32_t status;     /* ATTPC_EST_* bits */
   int32_t direction;  /* +1, -1, or 0 without a fit */
-  int32_t reserved;   /* 0 */
+  int32_t reserved;   /* 0; with the geometric circle fit on: its evaluations */
   int64_t charge;
   int64_t arc;
   double cx, cy, radius;
@@ -1379,6 +1380,73 @@ ATTPC_API int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_
                                   const int64_t* labels, const attpc_event_layout* layout, const attpc_thin_desc* desc,
                                   int64_t capacity, int64_t* point_offsets, double* points, int64_t* point_labels,
                                   attpc_thin_info* info, int64_t* needed);
+
+/* ---- geometric circle fit (opt-in: off by default, and with it off every output, kernel and buffer of every entry
+ * point is what it is without this section; the entry points are additions under ABI version 3) ----
+ * The Kasa circle of step 6 of the estimates minimises an algebraic distance, which pulls the radius low on a short
+ * noisy arc.  With this stage on, the (cx, cy, radius) of step 6 are refined by a least-squares fit of the GEOMETRIC
+ * distances of the fit segment's points to the circle (Levenberg-Marquardt, started from the Kasa circle), and all that
+ * step 6 derives from the circle (vx, vy, vz, brho) is made from the refined circle by the same formulae.  Unweighted;
+ * Spyral's ODE fit it is not.  tests/circle_reference.py restates this contract in numpy; csrc/circle_host.hpp is its
+ * arithmetic, shared by the kernel and the host.  A "unit" is 1/16 mm, as above.
+ * Settings (attpc_circle_desc): tolerance in units, finite and > 0 (default 2^-7); max_evaluations in 2 .. 64 (default
+ * 32); reserved = 0.
+ * When: only if step 6 found a Kasa circle (den != 0 and r2 > 0).  NO_CIRCLE stays NO_CIRCLE, nothing is refined and
+ * reserved stays 0.  The start is p = (a, b, R) = (uc, vc, sqrt(r2)) of step 6: units, relative to (X0, Y0).
+ * All arithmetic is f64, one rounding per operation, no fused multiply-add, only + - * / and sqrt, as step 6.
+ *   One EVALUATION at p = (a, b, R).  For segment rank i = 0 .. m - 1 with the integers u_i, v_i of step 5:
+ *       dx = u - a;  dy = v - b;  r = sqrt(dx dx + dy dy);  U = dx / r;  V = dy / r  (r == 0: U = V = 0);  g = r - R
+ *     and the nine sums F = sum g g, SUU = sum U U, SUV = sum U V, SVV = sum V V, SU = sum U, SV = sum V,
+ *     SgU = sum g U, SgV = sum g V, Sg = sum g.
+ *     The ORDER OF SUMMATION is part of the contract (these sums are not integers): rank i belongs to lane i mod 64; a
+ *     lane adds its terms in ascending i onto +0.0 (a lane without a term holds +0.0); the 64 lane values are then
+ *     combined by s[lane] <- s[lane] + s[lane xor off] for off = 32, 16, 8, 4, 2, 1, all lanes at once.  Addition is
+ *     commutative, so every lane ends with the same bits: that value is the sum.
+ *   The STEP at p with the sums of p and the damping lambda, by this one elimination (M = double(m)):
+ *       m00 = SUU + lambda SUU;  m11 = SVV + lambda SVV;  m22 = M + lambda M
+ *       l10 = SUV / m00;  l20 = SU / m00
+ *       a11 = m11 - l10 SUV;  a12 = SV - l10 SU;  b1 = SgV - l10 SgU
+ *       a22 = m22 - l20 SU;   b2 = Sg - l20 SgU
+ *       l21 = a12 / a11;  c22 = a22 - l21 a12;  c2 = b2 - l21 b1
+ *       d2 = c2 / c22;  d1 = (b1 - a12 d2) / a11;  d0 = (SgU - SUV d1 - SU d2) / m00
+ *     -- (N + lambda diag N) d = (SgU, SgV, Sg) with N = [[SUU, SUV, SU], [SUV, SVV, SV], [SU, SV, M]], no pivoting.
+ *   ITERATION.  lambda = 2^-10; evaluate at the start (evaluation 1).  Then repeat:
+ *       if the evaluations made == max_evaluations: stop with the status bit NOT_CONVERGED
+ *       d = the step at p;  p' = (a + d0, b + d1, R + d2);  evaluate at p'
+ *       accepted = F' <= F and R' > 0   (a NaN anywhere fails one of the two comparisons: rejected)
+ *       accepted: p = p' with its sums, lambda = 0.04 lambda, and if max(|d0|, |d1|, |d2|) <= tolerance stop, converged
+ *       rejected: lambda = 10 lambda
+ *     So a converged fit has made 2 .. max_evaluations evaluations, and the p of the record is the last accepted one
+ *     (the start if none was).
+ * Record: reserved = the evaluations made (>= 1 where the refinement ran, 0 everywhere else -- also in every record
+ * made with the stage off); status gets ATTPC_EST_NOT_CONVERGED where the iteration stopped unconverged;
+ *   cx = (X0 + a) / 16;  cy = (Y0 + b) / 16;  radius = R / 16
+ * and c, vx, vy, ON_AXIS, chord0, vz and brho follow from these as in step 6.  slope, x_mean, y_mean, dedx, charge, arc
+ * and the counts do not depend on the circle.  (A fit that makes no accepted step leaves exactly the Kasa record, plus
+ * reserved and the bit.)
+ * A record stays a pure function of the event's rows; with thinning on, the fused records are still DEFINED as this
+ * contract on the event's point rows. */
+#define ATTPC_EST_NOT_CONVERGED 128  /* the geometric circle fit spent max_evaluations evaluations */
+#define ATTPC_CIRCLE_MIN_EVALUATIONS 2
+#define ATTPC_CIRCLE_MAX_EVALUATIONS 64
+
+typedef struct attpc_circle_desc {
+  double tolerance;         /* units (1/16 mm), finite and > 0; default 2^-7 = 0.0078125 */
+  int32_t max_evaluations;  /* 2 .. 64; default 32 */
+  int32_t reserved;         /* 0 */
+} attpc_circle_desc;
+
+/* desc == NULL turns the stage off (the default).  Independent of every other configure call.  ATTPC_E_INVALID outside
+ * the ranges above, NaN included.  Takes effect only in the trace-row calls in which the estimates are on, with or
+ * without thinning: the estimate kernel that runs is then its refining instantiation.  Alone it is inert: no kernel, no
+ * buffer.  The trace rows, labels, offsets and checksums of the call do not change. */
+ATTPC_API int32_t attpc_trace_configure_circle(attpc_ctx* ctx, const attpc_circle_desc* desc);
+/* attpc_rows_estimate with the geometric circle fit of `circle` (not NULL), through the refining kernel.  Errors as
+ * attpc_rows_estimate, and ATTPC_E_INVALID for a circle desc out of range. */
+ATTPC_API int32_t attpc_rows_estimate_circle(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                             const int64_t* labels, const attpc_event_layout* layout,
+                                             const attpc_estimate_desc* desc, const attpc_circle_desc* circle,
+                                             attpc_track_estimate* out);
 
 /* ---- track straggling (opt-in: off by default, and with it off every output, kernel and buffer of every entry point
  * is what it is without this section; the entry point is an addition under ABI version 3) ----

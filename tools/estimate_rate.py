@@ -16,11 +16,15 @@ thinning at a z step of Z mm in the place of stage off / on (both legs have the 
 and ``--thin-steps 2,5,10`` repeats the yield at these steps beside the unthinned one.  ``--estimates-only`` times the
 estimates leg alone: what a library without the thinning entry points (``ATTPC_HIP_LIBRARY``, a build of the parent
 commit by tools/build_variant.sh) can run, to set beside the same leg of this build in the same session.
+Geometric circle fit (attpc_trace_configure_circle): ``--circle`` times the estimates with the Kasa circle
+against the estimates with the geometric fit behind it, alternating (both legs on raw rows, or with ``--thinning Z`` on
+the points of that z step), and repeats the yield with the Kasa circle and with the geometric fit -- on the raw rows, or
+at every step of ``--thin-steps`` if given -- with the distribution of the evaluations made (``reserved``) beside it.
 ``--profile WORKLOAD`` runs two ``run_estimates`` calls in partial readout and nothing else, for
 ``rocprofv3 --kernel-trace --stats -- python tools/estimate_rate.py --profile o16aa`` (a run of its own).
 
     python tools/estimate_rate.py [--events N] [--reps K] [--stats-events M] [--workloads o16aa,be10dp] [--out FILE]
-                                  [--thinning Z | --estimates-only] [--thin-steps 2,5,10] [--min-points P]
+                                  [--thinning Z | --estimates-only] [--thin-steps 2,5,10] [--min-points P] [--circle]
 """
 from __future__ import annotations
 
@@ -108,14 +112,48 @@ def thinning_rates(eng, events: int, reps: int, z_step, min_points: int) -> dict
     return {"rows_per_event": rows / events, **{k: [_median(v), min(v), max(v)] for k, v in legs.items()}}
 
 
-def yield_(eng, events: int, total: int, z_step=None, min_points: int = 30) -> dict:
+def circle_rates(eng, events: int, reps: int, z_step, min_points: int) -> dict:
+    """The estimates with the Kasa circle against the estimates with the geometric fit behind it (``z_step``: both on
+    the thinned points of that step, None: on the raw rows)."""
+    from attpc_engine_amd.detector.circle import CircleFitSettings
+    from attpc_engine_amd.detector.estimate import EstimateSettings
+
+    kinds = ("kasa", "geometric")
+    legs = {kind: [] for kind in kinds}
+    eng.configure_estimates(EstimateSettings(min_points=min_points))
+    if z_step is not None:
+        eng.configure_thinning(z_step=z_step)
+
+    def call(kind: str):
+        eng.configure_circle_fit(CircleFitSettings() if kind == "geometric" else None)
+        t0 = time.perf_counter()
+        res = eng.run_trace_rows(events, seed=1, fetch=False)
+        return events / (time.perf_counter() - t0), res
+
+    for kind in kinds:
+        call(kind)
+    rows = 0
+    for _ in range(reps):
+        for kind in kinds:
+            rate, res = call(kind)
+            legs[kind].append(rate)
+            rows = res["trace_rows"]["n_rows"]
+    eng.configure_estimates()
+    eng.configure_thinning()
+    eng.configure_circle_fit()
+    return {"rows_per_event": rows / events, "z_step": z_step, **{k: [_median(v), min(v), max(v)] for k, v in legs.items()}}
+
+
+def yield_(eng, events: int, total: int, z_step=None, min_points: int = 30, circle: bool = False) -> dict:
     import numpy as np
 
+    from attpc_engine_amd.detector.circle import CircleFitSettings
     from attpc_engine_amd.detector.estimate import STATUS_BITS, EstimateSettings, polar, truth_tracks
 
     eng.configure_estimates(EstimateSettings(min_points=min_points))
     if z_step is not None:
         eng.configure_thinning(z_step=z_step)
+    eng.configure_circle_fit(CircleFitSettings() if circle else None)
     est, truth = [], []
     for first in range(0, total, events):
         res = eng.run_estimates(min(events, total - first), seed=1, first_event=first)
@@ -124,16 +162,23 @@ def yield_(eng, events: int, total: int, z_step=None, min_points: int = 30) -> d
     eng.configure_estimates()
     if z_step is not None:
         eng.configure_thinning()
+    eng.configure_circle_fit()
     est = np.concatenate(est)
     field = float(eng.config.det_params.bfield)
     truth = {k: np.concatenate([t[k] for t in truth]) for k in truth[0]}
-    out = {"tracks": int(est.size), "indices": list(eng.indices), "z_step": z_step, "min_points": min_points, "positions": []}
+    out = {"tracks": int(est.size), "indices": list(eng.indices), "z_step": z_step, "min_points": min_points,
+           "circle": "geometric" if circle else "kasa", "positions": []}
     for s in range(est.shape[1]):
         e = est[:, s]
         pos = {"status": {name: float((e["status"] & bit != 0).mean()) for name, bit in STATUS_BITS.items()},
                "clean": float((e["status"] == 0).mean())}
         good = np.isfinite(e["brho"]) & np.isfinite(e["slope"]) & np.isfinite(truth["brho"][:, s])
         pos["estimated"] = float(good.mean())
+        ran = e["reserved"] > 0
+        if ran.any():  # the geometric circle fit: the evaluations of the records it ran on
+            pos["evaluations"] = {"share": float(ran.mean()), "median": float(np.median(e["reserved"][ran])),
+                                  "p90": float(np.percentile(e["reserved"][ran], 90.0)), "max": int(e["reserved"][ran].max()),
+                                  "histogram": np.bincount(e["reserved"][ran], minlength=65).tolist()}
         if good.sum() >= 10:
             # the two factors of brho apart: the circle against R = B rho sin(theta) / B of the truth, and the
             # cumulated pad-plane distance against the straight chord of the same segment (zig-zag: above 1)
@@ -157,6 +202,9 @@ def _print_yield(y: dict) -> None:
         for key in ("brho_rel", "polar", "radius_rel", "arc_over_2chord_to_mean"):
             if key in pos:
                 print(f"    {key}: median {pos[key]['median']:+.4f}, 16 .. 84 % half-width {pos[key]['half_width_16_84']:.4f}")
+        if "evaluations" in pos:
+            ev = pos["evaluations"]
+            print(f"    evaluations (fit ran on {100 * ev['share']:.1f} %): median {ev['median']:.0f}, 90 % {ev['p90']:.0f}, max {ev['max']}")
 
 
 def thinning_main(args) -> None:
@@ -187,13 +235,44 @@ def thinning_main(args) -> None:
                     f.write(json.dumps(line) + "\n")
 
 
-def profile(name: str, events: int, z_step=None, min_points: int = 30) -> None:
+def circle_main(args) -> None:
+    steps = [float(z) for z in args.thin_steps.split(",") if z] or [None]
+    for name in args.workloads.split(","):
+        for mode in MODES:
+            eng = _engine(name, mode)
+            line = {"workload": name, "mode": mode, "events": args.events, "min_points": args.min_points}
+            if args.reps > 0:
+                r = line["rates"] = circle_rates(eng, args.events, args.reps, args.thinning, args.min_points)
+                where = "raw rows" if args.thinning is None else f"points of {args.thinning} mm"
+                print(f"## {name} / {mode}: {r['rows_per_event']:.1f} trace rows per event, min_points {args.min_points}, {where}", flush=True)
+                for leg in ("kasa", "geometric"):
+                    print(f"  run_trace_rows(fetch=False), {leg:9s} {r[leg][0]:12.0f} events/s  ({r[leg][1]:.0f} .. {r[leg][2]:.0f})")
+                cost = 1.0 / r["geometric"][0] - 1.0 / r["kasa"][0]
+                print(f"  cost of the geometric fit: {cost * 1e9:.0f} ns per event, "
+                      f"{100.0 * (1.0 - r['geometric'][0] / r['kasa'][0]):.2f} % of the rate without it")
+            line["yield"] = []
+            for z_step in (steps if args.stats_events > 0 else []):
+                for circle in (False, True):
+                    y = yield_(eng, args.events, args.stats_events, z_step, args.min_points, circle)
+                    line["yield"].append(y)
+                    print(f"## {name} / {mode}: records of {args.stats_events} events, " + ("raw rows" if z_step is None else f"z step {z_step} mm")
+                          + f", {y['circle']} circle", flush=True)
+                    _print_yield(y)
+            eng.ctx.close()
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+
+
+def profile(name: str, events: int, z_step=None, min_points: int = 30, circle: bool = False) -> None:
     from attpc_engine_amd.detector.estimate import EstimateSettings
 
     eng = _engine(name, "partial")
     eng.configure_estimates(EstimateSettings(min_points=min_points))
     if z_step is not None:
         eng.configure_thinning(z_step=z_step)
+    if circle:
+        eng.configure_circle_fit(max_evaluations=32)
     eng.run_estimates(events, seed=1)
     eng.run_estimates(events, seed=1)
 
@@ -210,9 +289,12 @@ def main() -> None:
     ap.add_argument("--estimates-only", action="store_true")
     ap.add_argument("--thin-steps", default="")
     ap.add_argument("--min-points", type=int, default=30)
+    ap.add_argument("--circle", action="store_true")
     args = ap.parse_args()
     if args.profile:
-        return profile(args.profile, args.events, args.thinning, args.min_points)
+        return profile(args.profile, args.events, args.thinning, args.min_points, args.circle)
+    if args.circle:
+        return circle_main(args)
     if args.thinning is not None or args.estimates_only or args.thin_steps:
         return thinning_main(args)
     for name in args.workloads.split(","):
