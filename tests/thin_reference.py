@@ -125,13 +125,19 @@ def band_slope(n_z, turn, dz):
     return dz * (n_z - 1) / (BAND_RADIUS * turn)
 
 
-def fused_records(offsets, rows, labels, indices, z_step, params):
+def fused_records(offsets, rows, labels, indices, z_step, params, circle=None):
     """The records of a trace-row call with the estimates and thinning both on: the estimate contract on the event's
-    point rows, ATTPC_EST_RANGE OR-ed in where thinning dropped a row of the label."""
+    point rows, ATTPC_EST_RANGE OR-ed in where thinning dropped a row of the label.  ``circle`` (a
+    ``circle_reference.Settings``): with the geometric circle fit on as well."""
     from attpc_engine_amd._abi import EST_RANGE
     from tests import estimate_reference as est
 
     point_offsets, points, point_labels, info = thin(offsets, rows, labels, indices, z_step)
-    records = est.records(point_offsets, points, point_labels, indices, params)
+    if circle is not None:
+        from tests import circle_reference
+
+        records = circle_reference.records(point_offsets, points, point_labels, indices, params, circle)
+    else:
+        records = est.records(point_offsets, points, point_labels, indices, params)
     records["status"] |= np.where(info["n_dropped"] > 0, EST_RANGE, 0).astype(np.int32)
     return records
