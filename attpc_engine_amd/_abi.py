@@ -192,6 +192,15 @@ CIRCLE_MIN_EVALUATIONS, CIRCLE_MAX_EVALUATIONS = 2, 64
 CIRCLE_DEFAULT_EVALUATIONS, CIRCLE_DEFAULT_TOLERANCE = 32, 1.0 / 128.0
 
 
+class HelixDesc(C.Structure):
+    _fields_ = [("regressor", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the helix slope behind the circle of the estimates: its status bit and the regressors
+EST_NO_HELIX = 256
+HELIX_AUTO, HELIX_Z_ON_PATH, HELIX_PATH_ON_Z = 0, 1, 2
+
+
 class ThinDesc(C.Structure):
     _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
 
@@ -410,6 +419,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_thinning", "attpc_rows_thin",
     "attpc_det_configure_straggling",
     "attpc_trace_configure_circle", "attpc_rows_estimate_circle",
+    "attpc_trace_configure_helix", "attpc_rows_estimate_helix",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -454,6 +464,9 @@ STRAGGLE_SYMBOLS = ("attpc_det_configure_straggling",)
 
 # ... and the geometric circle fit after the track straggling: the same rule.
 CIRCLE_SYMBOLS = ("attpc_trace_configure_circle", "attpc_rows_estimate_circle")
+
+# ... and the helix slope after the geometric circle fit: the same rule.
+HELIX_SYMBOLS = ("attpc_trace_configure_helix", "attpc_rows_estimate_helix")
 
 _lib = None
 
@@ -651,6 +664,15 @@ def load_library() -> C.CDLL:
     for name, argtypes in circle.items():
         if not no_circle:
             getattr(lib, name).argtypes = argtypes
+    helix = {
+        "attpc_trace_configure_helix": [ctxp, C.POINTER(HelixDesc)],
+        "attpc_rows_estimate_helix": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
+                                      C.POINTER(CircleDesc), C.POINTER(HelixDesc), C.POINTER(TrackEstimate)],
+    }
+    no_helix = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in HELIX_SYMBOLS)
+    for name, argtypes in helix.items():
+        if not no_helix:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -677,7 +699,7 @@ def load_library() -> C.CDLL:
                 or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)
                 or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)
                 or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)
-                or (no_circle and name in CIRCLE_SYMBOLS)):
+                or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -687,7 +709,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling", "circle")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix")
 
 
 class Context:

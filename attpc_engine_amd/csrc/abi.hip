@@ -37,6 +37,7 @@
 #include "unpack_host.hpp"
 #include "spyral_integral.hpp"  // (behind the HIP runtime header)
 #include "circle_host.hpp"
+#include "helix_host.hpp"
 #include "estimate_host.hpp"
 #include "thin_host.hpp"
 #include "straggle_host.hpp"
@@ -257,6 +258,8 @@ struct attpc_ctx {
   attpc_thin_desc thinning{};
   bool circle_on = false;          // attpc_trace_configure_circle (inert while the estimates are off)
   attpc_circle_desc circle{};
+  bool helix_on = false;           // attpc_trace_configure_helix (inert while the estimates are off)
+  attpc_helix_desc helix{};
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -1100,7 +1103,7 @@ int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout
 // The track estimates of the chunk in `as` (n events, rows written: directly behind launch_peak_rows) on S, as.traced
 // recorded again behind them, and the copy of the records to events first_local .. of the call's pinned array on C.
 // With thinning on the rows are thinned first (thin.hip) and the estimates are those of the points; with the geometric
-// circle fit on the estimate kernel is its refining instantiation.
+// circle fit on the estimate kernel is its refining instantiation, with the helix slope on the one with its third pass.
 int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first_local) {
   const size_t n_sim = (size_t)ctx->est_call_n_sim;
   if (!n || !n_sim) return ATTPC_OK;
@@ -1133,10 +1136,13 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
     a.points = t.points;
     a.thin_info = t.info;
   }
-  if (ctx->circle_on) {
-    circle_settings(ctx->circle, &a);
+  if (ctx->circle_on) circle_settings(ctx->circle, &a);
+  if (ctx->helix_on) {
+    a.helix_regressor = ctx->helix.regressor;
+    launch_helix_estimates(ctx->stream, n, a, ctx->thinning_on, ctx->circle_on);
+  } else if (ctx->circle_on)
     launch_circle_estimates(ctx->stream, n, a, ctx->thinning_on);
-  } else if (ctx->thinning_on)
+  else if (ctx->thinning_on)
     launch_point_estimates(ctx->stream, n, a);
   else
     launch_estimates(ctx->stream, n, a);
@@ -3527,16 +3533,19 @@ int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc
 }
 
 namespace {
-// attpc_rows_estimate (circle == nullptr) and attpc_rows_estimate_circle under the name `func`
+// attpc_rows_estimate (circle == nullptr), attpc_rows_estimate_circle and attpc_rows_estimate_helix (helix != nullptr)
+// under the name `func`
 int32_t rows_estimate(attpc_ctx* ctx, const char* func, int64_t n_events, const int64_t* offsets, const double* rows,
                       const int64_t* labels, const attpc_event_layout* layout, const attpc_estimate_desc* d,
-                      const attpc_circle_desc* circle, attpc_track_estimate* out) {
+                      const attpc_circle_desc* circle, attpc_track_estimate* out, const attpc_helix_desc* helix = nullptr) {
   if (!ctx || n_events < 0 || !d || !layout) return ATTPC_E_INVALID;
   if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
     return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", func, layout->n_sim, ATTPC_MAX_SIM);
   if (const char* bad = estimate_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
   if (circle)
     if (const char* bad = circle_desc_error(*circle)) return fail(ctx, ATTPC_E_INVALID, "circle: %s", bad);
+  if (helix)
+    if (const char* bad = helix_desc_error(*helix)) return fail(ctx, ATTPC_E_INVALID, "helix: %s", bad);
   const size_t n_sim = (size_t)layout->n_sim;
   if (n_events > 0 && n_sim && !out) return ATTPC_E_INVALID;
   if (const ArgError bad = csr_error(func, n_events, offsets)) return refuse(ctx, bad);
@@ -3550,6 +3559,7 @@ int32_t rows_estimate(attpc_ctx* ctx, const char* func, int64_t n_events, const 
   estimate_positions(*layout, a.slot_label);
   a.n_sim = (int32_t)n_sim;
   if (circle) circle_settings(*circle, &a);
+  if (helix) a.helix_regressor = helix->regressor;
   constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> start;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
@@ -3561,7 +3571,9 @@ int32_t rows_estimate(attpc_ctx* ctx, const char* func, int64_t n_events, const 
     a.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
     a.records = stage<attpc_track_estimate>(ctx, 3, m * n_sim, rc);
     if (rc) return rc;
-    if (circle)
+    if (helix)
+      launch_helix_estimates(ctx->stream, (uint32_t)m, a, false, circle != nullptr);
+    else if (circle)
       launch_circle_estimates(ctx->stream, (uint32_t)m, a, false);
     else
       launch_estimates(ctx->stream, (uint32_t)m, a);
@@ -3594,6 +3606,24 @@ int32_t attpc_rows_estimate_circle(attpc_ctx* ctx, int64_t n_events, const int64
                                    const attpc_circle_desc* circle, attpc_track_estimate* out) {
   if (!circle) return ATTPC_E_INVALID;
   return rows_estimate(ctx, __func__, n_events, offsets, rows, labels, layout, d, circle, out);
+}
+
+// ---- helix slope (estimate.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_helix(attpc_ctx* ctx, const attpc_helix_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = helix_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "helix: %s", bad);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->helix_on = d != nullptr;
+  if (d) ctx->helix = *d;
+  return ATTPC_OK;
+}
+
+int32_t attpc_rows_estimate_helix(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                  const int64_t* labels, const attpc_event_layout* layout, const attpc_estimate_desc* d,
+                                  const attpc_circle_desc* circle, const attpc_helix_desc* helix, attpc_track_estimate* out) {
+  if (!helix) return ATTPC_E_INVALID;
+  return rows_estimate(ctx, __func__, n_events, offsets, rows, labels, layout, d, circle, out, helix);
 }
 
 // ---- thinned track points (thin.hip; the contract is in include/attpc_engine.h) ----

@@ -27,10 +27,19 @@
 // evaluation is then a lane-strided walk over the parked points (rank i in lane i mod 64, ascending) and nine xor-tree
 // reductions; the iteration is wave-uniform, since every lane holds the same sums.  No barrier: a wave reads only what
 // it wrote, and the LDS operations of one wave complete in order.
+//
+// estimate_kernel<*, *, true> is the same body once more with the helix slope behind the circle ("helix slope" in the
+// header; its arithmetic is helix_host.hpp, shared with the host).  Once the circle (a, b, R) is in every lane, pass C
+// walks the rows as pass B does: a segment lane computes its quantised turning angle about the centre (written
+// arctangent: selects, two divisions, no libm), takes the previous segment row's angle as pass B takes (X, Y), gets the
+// wrap j, the turn count K by the integer wave prefix plus the carry, and the unwrapped angle; a ballot covers the cap;
+// four integer sums, reduced once.  No f64 sum, nothing parked: the rows are read a third time out of L2.  With HELIX
+// false nothing of it is instantiated: those four kernels are instruction for instruction what they were.
 #include "tracks_args.hpp"
 
 #include "circle_host.hpp"
 #include "estimate_host.hpp"
+#include "helix_host.hpp"
 
 namespace attpc {
 
@@ -136,7 +145,7 @@ __device__ __forceinline__ uint32_t* est_parked(int wave) {
 
 }  // namespace
 
-template <bool POINTS, bool CIRCLE>
+template <bool POINTS, bool CIRCLE, bool HELIX>
 __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
   const uint32_t e = blockIdx.x;
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -254,7 +263,57 @@ __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
     rec.status = (range ? ATTPC_EST_RANGE : 0) | (capped ? ATTPC_EST_CAPPED : 0);
     rec.direction = direction;
     rec.reserved = 0;
-    if constexpr (CIRCLE) {
+    if constexpr (HELIX) {
+      // step 6 up to the circle, which stays in registers: (a, b, R) in every lane
+      double ca, cb, cR;
+      bool circle;
+      if constexpr (CIRCLE)
+        circle = helix_step6(k, a.magnetic_field, true, a.circle_tolerance, a.circle_max_evaluations,
+                             [&](double ta, double tb, double tr) { return est_circle_evaluate(parked, m, lane, ta, tb, tr); },
+                             &rec, &ca, &cb, &cR);
+      else
+        circle = helix_step6(k, a.magnetic_field, false, 0.0, 0, [](double, double, double) { return circle_zero(); }, &rec,
+                             &ca, &cb, &cR);
+      if (!circle) {
+        rec.status |= ATTPC_EST_NO_HELIX;
+      } else {
+        // ---- pass C: the segment's turning angles about the centre, walked as pass B walks ----
+        const double p0x = -ca, p0y = -cb;
+        int64_t sp = 0, spp = 0, spw = 0, sww = 0;
+        int32_t done = 0, turns = 0, prev_phi = 0;  // segment rows so far, K and phi_q of the last of them
+        bool no_helix = false;
+        for (int64_t qb = q0; qb < n && done < m; qb += 64) {
+          const int64_t q = qb + lane;
+          const EstRow row = est_row<POINTS>(a, direction > 0 ? lo + q : hi - 1 - q, q < n, target);
+          const uint64_t bu = __ballot(row.used);
+          if (bu == 0ull) continue;
+          const bool seg = row.used && done + __popcll(bu & below) < m;
+          const uint64_t bs = __ballot(seg);
+          const uint64_t before = bs & below;
+          const int src = before ? 63 - __clzll((long long)before) : lane;
+          bool bad;
+          const int32_t phi = helix_phi(p0x, p0y, (double)(row.X - origin.X) - ca, (double)(row.Y - origin.Y) - cb, &bad);
+          const int32_t from_phi = __shfl(phi, src);
+          const int32_t j = seg ? helix_wrap(before ? from_phi : prev_phi, phi) : 0;  // (rank 0: phi = 0 against 0)
+          const int32_t K = turns + est_wave_inclusive(j, lane);
+          const int32_t unwrapped = phi + HELIX_TURN * K;  // (|K| <= 2047: below 2^30)
+          const bool over = seg && (bad || unwrapped >= HELIX_CAP || unwrapped <= -HELIX_CAP);
+          no_helix = no_helix || __ballot(over) != 0ull;
+          if (seg) {
+            const int64_t P = over ? 0 : unwrapped, w = row.Z - origin.Z;
+            sp += P;
+            spp += P * P;
+            spw += P * w;
+            sww += w * w;
+          }
+          turns = __shfl(K, 63);
+          prev_phi = __shfl(phi, 63 - __clzll((long long)bs));
+          done += __popcll(bs);
+        }
+        const HelixSums h{est_wave_add(sp), est_wave_add(spp), est_wave_add(spw), est_wave_add(sww), no_helix};
+        helix_closed_form(k, h, a.helix_regressor, a.magnetic_field, ca, cb, cR, &rec);
+      }
+    } else if constexpr (CIRCLE) {
       // (the iteration is uniform over the wave: every lane holds the same sums)
       estimate_closed_form_circle(k, a.magnetic_field, a.circle_tolerance, a.circle_max_evaluations,
                                   [&](double ta, double tb, double tr) { return est_circle_evaluate(parked, m, lane, ta, tb, tr); },
@@ -266,20 +325,32 @@ __global__ __launch_bounds__(EST_THREADS) void estimate_kernel(EstimateArgs a) {
   }
 }
 
-// (the refining instantiations first: the two others then lie in the code object as they did without them)
+// (the instantiations of the helix slope first, then the refining ones: the two others then lie in the code object as
+//  they did without them)
+void launch_helix_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a, bool points, bool circle) {
+  if (points && circle)
+    hipLaunchKernelGGL((estimate_kernel<true, true, true>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  else if (circle)
+    hipLaunchKernelGGL((estimate_kernel<false, true, true>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  else if (points)
+    hipLaunchKernelGGL((estimate_kernel<true, false, true>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  else
+    hipLaunchKernelGGL((estimate_kernel<false, false, true>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+}
+
 void launch_circle_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a, bool points) {
   if (points)
-    hipLaunchKernelGGL((estimate_kernel<true, true>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+    hipLaunchKernelGGL((estimate_kernel<true, true, false>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
   else
-    hipLaunchKernelGGL((estimate_kernel<false, true>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+    hipLaunchKernelGGL((estimate_kernel<false, true, false>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
 }
 
 void launch_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a) {
-  hipLaunchKernelGGL((estimate_kernel<false, false>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  hipLaunchKernelGGL((estimate_kernel<false, false, false>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
 }
 
 void launch_point_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a) {
-  hipLaunchKernelGGL((estimate_kernel<true, false>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
+  hipLaunchKernelGGL((estimate_kernel<true, false, false>), dim3(n_events), dim3(EST_THREADS), 0, s, a);
 }
 
 }  // namespace attpc

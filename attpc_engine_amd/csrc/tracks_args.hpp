@@ -256,6 +256,8 @@ struct EstimateArgs {
   // the geometric circle fit (launch_circle_estimates) reads these
   double circle_tolerance;            // units
   int32_t circle_max_evaluations;     // 2 .. 64
+  // the helix slope (launch_helix_estimates) reads this
+  int32_t helix_regressor;            // 0 .. 2
 };
 // one workgroup per event, empty events included (n_events > 0, n_sim > 0)
 void launch_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a);
@@ -264,6 +266,9 @@ void launch_point_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs
 // launch_estimates (points = false) or launch_point_estimates (points = true) with the geometric circle fit behind the
 // Kasa circle (attpc_trace_configure_circle, "geometric circle fit" in the header): a.circle_* are set
 void launch_circle_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a, bool points);
+// any of the four with the helix slope behind the circle (attpc_trace_configure_helix, "helix slope" in the header):
+// a.helix_regressor is set, and with `circle` a.circle_* are
+void launch_helix_estimates(hipStream_t s, uint32_t n_events, const EstimateArgs& a, bool points, bool circle);
 
 // thinned track points (thin.hip; attpc_trace_configure_thinning, the contract is in include/attpc_engine.h)
 struct ThinArgs {

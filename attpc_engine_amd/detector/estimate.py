@@ -16,11 +16,12 @@ import numpy as np
 
 from .. import _abi
 from .._abi import (ESTIMATE_DTYPE, EST_CAPPED, EST_EMPTY, EST_FEW, EST_MAX_FIT, EST_NOT_CONVERGED, EST_NO_CIRCLE,  # noqa: F401
-                    EST_NO_SLOPE, EST_ON_AXIS, EST_RANGE)
+                    EST_NO_HELIX, EST_NO_SLOPE, EST_ON_AXIS, EST_RANGE)
 from .traces import configure_stage
 
 STATUS_BITS = {"EMPTY": EST_EMPTY, "FEW": EST_FEW, "RANGE": EST_RANGE, "CAPPED": EST_CAPPED, "NO_CIRCLE": EST_NO_CIRCLE,
                "ON_AXIS": EST_ON_AXIS, "NO_SLOPE": EST_NO_SLOPE, "NOT_CONVERGED": EST_NOT_CONVERGED}
+# (the eight bits of the estimates and the circle fit; ``detector.helix.STATUS_BITS`` adds the helix slope's NO_HELIX)
 C_MEV_PER_TM = 299.792458  # p [MeV/c] = 299.792458 Z B rho [T m]
 
 
@@ -93,17 +94,21 @@ def _layout(indices) -> _abi.EventLayout:
 
 
 def rows_to_estimates(offsets, rows, labels, indices, settings: EstimateSettings, ctx: _abi.Context | None = None,
-                      config=None, circle=None) -> np.ndarray:
+                      config=None, circle=None, helix=None) -> np.ndarray:
     """The estimate stage alone on any host rows in CSR form (``attpc_rows_estimate``; the kernel of the fused path, no
     other configuration needed): offsets [n+1], rows [R,8] as ``run_trace_rows`` / ``run_spyral`` deliver them, labels
     [R], ``indices`` (the nucleus of every track position) -> records [n, len(indices)] (``ESTIMATE_DTYPE``).  The field
     is the settings' own, else ``config.det_params.bfield``.  ``circle`` (a ``detector.circle.CircleFitSettings``; None =
-    off): the geometric circle fit behind the Kasa circle (``attpc_rows_estimate_circle``)."""
+    off): the geometric circle fit behind the Kasa circle (``attpc_rows_estimate_circle``).  ``helix`` (a
+    ``detector.helix.HelixSlopeSettings``; None = off): the helix slope behind the circle, with or without ``circle``
+    (``attpc_rows_estimate_helix``)."""
     from .circle import _checked as _checked_circle
+    from .helix import _checked as _checked_helix
 
     if not isinstance(settings, EstimateSettings):
         raise TypeError("settings must be an EstimateSettings")
     _checked_circle(circle)
+    _checked_helix(helix)
     if config is not None:
         settings = settings.for_field(config.det_params.bfield)
     desc = settings.desc()
@@ -118,6 +123,12 @@ def rows_to_estimates(offsets, rows, labels, indices, settings: EstimateSettings
     n = len(offsets) - 1
     records = np.empty((n, layout.n_sim), dtype=ESTIMATE_DTYPE)
     ctx = ctx or _abi.default_context()
+    if helix is not None:
+        ctx.check(ctx.lib.attpc_rows_estimate_helix(ctx.handle, n, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(rows),
+                                                    _abi.iptr(labels, _abi.C.c_int64), layout, desc,
+                                                    None if circle is None else circle.desc(), helix.desc(),
+                                                    _abi.iptr(records, _abi.TrackEstimate)), "attpc_rows_estimate_helix")
+        return records
     if circle is not None:
         ctx.check(ctx.lib.attpc_rows_estimate_circle(ctx.handle, n, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(rows),
                                                      _abi.iptr(labels, _abi.C.c_int64), layout, desc, circle.desc(),

@@ -238,6 +238,12 @@ def _checked_circle(circle):
     return _checked(circle)
 
 
+def _checked_helix(helix):
+    from .helix import _checked
+
+    return _checked(helix)
+
+
 def _checked_common_mode(common_mode):
     if common_mode is not None and not isinstance(common_mode, CommonModeSettings):
         raise TypeError("common_mode must be a CommonModeSettings or None")
@@ -395,12 +401,13 @@ class TraceChain:
     None = off) and the ``readout`` (a ``ReadoutSettings``; None = hit pads), and the stages that are None when off:
     ``gain``, ``peaks`` (trace rows; None = ``PeakSettings()``), ``baseline``, ``trigger``, ``common_mode``,
     ``estimates`` (trace rows: a ``detector.estimate.EstimateSettings``), ``thinning`` (the rows in front of the
-    estimates: a ``detector.thinning.ThinSettings``) and ``circle`` (the geometric circle fit behind them: a
-    ``detector.circle.CircleFitSettings``)."""
+    estimates: a ``detector.thinning.ThinSettings``), ``circle`` (the geometric circle fit behind them: a
+    ``detector.circle.CircleFitSettings``) and ``helix`` (the helix slope behind the circle: a
+    ``detector.helix.HelixSlopeSettings``)."""
 
     def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
                  gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
-                 thinning=None, circle=None):
+                 thinning=None, circle=None, helix=None):
         self.config, self._given = config, (response, threshold)
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
@@ -408,6 +415,7 @@ class TraceChain:
         self.common_mode = _checked_common_mode(common_mode)
         self.estimates, self.thinning = _checked_estimates(estimates), _checked_thinning(thinning)
         self.circle = _checked_circle(circle)
+        self.helix = _checked_helix(helix)
 
     @classmethod
     def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
@@ -423,10 +431,10 @@ class TraceChain:
 
     def replace(self, **fields) -> "TraceChain":
         """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning,
-        circle; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle"}
+        circle, helix; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix"}
         if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning and circle, not {sorted(unknown)}")
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle and helix, not {sorted(unknown)}")
         chain = copy.copy(self)
         vars(chain).update(fields)
         if "config" in fields:
@@ -436,14 +444,15 @@ class TraceChain:
         _checked_estimates(chain.estimates)
         _checked_thinning(chain.thinning)
         _checked_circle(chain.circle)
+        _checked_helix(chain.helix)
         return chain
 
     def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
         """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
         trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
-        baseline; trigger; gain; with ``rows`` the track estimates, the thinning in front of them and the circle fit behind them.  A stage that is
+        baseline; trigger; gain; with ``rows`` the track estimates, the thinning in front of them, the circle fit behind them and the helix slope behind that.  A stage that is
         off is turned off, whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode"
-        and "estimates" (the thinning and the circle fit with them) that ``keep`` names, which stay as the ctx holds them."""
+        and "estimates" (the thinning, the circle fit and the helix slope with them) that ``keep`` names, which stay as the ctx holds them."""
         from .simulator import configure_spyral
 
         ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
@@ -463,11 +472,13 @@ class TraceChain:
         if rows and "estimates" not in keep:
             from .circle import configure_circle
             from .estimate import configure_estimates
+            from .helix import configure_helix
             from .thinning import configure_thinning
 
             configure_estimates(ctx, self.estimates, self.config)
             configure_thinning(ctx, self.thinning)
             configure_circle(ctx, self.circle)
+            configure_helix(ctx, self.helix)
 
     def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
                   ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False,
@@ -499,11 +510,13 @@ class TraceChain:
         if rows:
             from .circle import circle_result
             from .estimate import estimates_result
+            from .helix import helix_result
             from .thinning import thinning_result
 
             extra.update(estimates_result(ctx, len(arrays.offsets) - 1, len(indices)))
             extra.update(thinning_result(ctx))
             extra.update(circle_result(ctx))
+            extra.update(helix_result(ctx))
         sums = ctx.trace_rows_last() if rows else arrays.sums()
         return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
 
@@ -985,15 +998,18 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
 
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
                          baseline: BaselineSettings | None = None, gain: GainSettings | None = None,
-                         common_mode: CommonModeSettings | None = None, thinning=None, circle=None, **trace_kwargs) -> None:
+                         common_mode: CommonModeSettings | None = None, thinning=None, circle=None, helix=None,
+                         **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
     the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
     baseline (default None: off, the peaks stand on the configured pedestals), the micromegas gain and the common-mode
-    noise (default None: off).  The trigger, the track estimates, the thinning and the circle fit stay as the ctx holds
-    them; a ``thinning`` (a ``detector.thinning.ThinSettings``) or a ``circle`` (a ``detector.circle.CircleFitSettings``)
-    is configured, None leaves what the ctx holds."""
+    noise (default None: off).  The trigger, the track estimates, the thinning, the circle fit and the helix slope stay
+    as the ctx holds them; a ``thinning`` (a ``detector.thinning.ThinSettings``), a ``circle`` (a
+    ``detector.circle.CircleFitSettings``) or a ``helix`` (a ``detector.helix.HelixSlopeSettings``) is configured, None
+    leaves what the ctx holds."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
-                                                                   common_mode=common_mode, thinning=thinning, circle=circle)
+                                                                   common_mode=common_mode, thinning=thinning, circle=circle,
+                                                                   helix=helix)
     chain.configure(ctx, rows=True, keep=("trigger", "estimates"))
     if thinning is not None:
         from .thinning import configure_thinning
@@ -1003,6 +1019,10 @@ def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings 
         from .circle import configure_circle
 
         configure_circle(ctx, chain.circle)
+    if helix is not None:
+        from .helix import configure_helix
+
+        configure_helix(ctx, chain.helix)
 
 
 def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
@@ -1010,7 +1030,8 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               peaks: PeakSettings | None = None, capacity_per_event: int = 2048,
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
-                              estimates=None, thinning=None, straggling=None, circle=None, **trace_kwargs):
+                              estimates=None, thinning=None, straggling=None, circle=None, helix=None,
+                              **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -1020,11 +1041,12 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     ``detector.estimate.EstimateSettings``; None = off) the track estimates [n, len(indices)] under ``"estimates"`` --
     with ``thinning`` (a ``detector.thinning.ThinSettings``; None = off) those of the thinned points, and its z step
     under ``"thinning"``; with ``circle`` (a ``detector.circle.CircleFitSettings``; None = off) their circles refined by
-    the geometric fit, and ``"circle": "geometric"``).
+    the geometric fit, and ``"circle": "geometric"``; with ``helix`` (a ``detector.helix.HelixSlopeSettings``; None =
+    off) their slope, vz and B rho from the helix, and ``"slope": "helix"``).
     ``gain``, ``common_mode`` and ``straggling`` as simulate_batch_traces takes them."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
-                                                                   thinning=thinning, circle=circle)
+                                                                   thinning=thinning, circle=circle, helix=helix)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event, straggling=straggling)
 

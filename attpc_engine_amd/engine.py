@@ -19,6 +19,7 @@ from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings
                               configure_trigger, trigger_result)
 from .detector.estimate import EstimateSettings, configure_estimates, estimates_result
 from .detector.circle import CircleFitSettings, circle_result, configure_circle
+from .detector.helix import HelixSlopeSettings, configure_helix, helix_result
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .detector.straggling import StragglingSettings, configure_straggling
 from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
@@ -281,7 +282,9 @@ class Engine:
         did not fire is an empty range of the offsets); with the track estimates configured (``configure_estimates``)
         their records [n, n_sim] under ``estimates`` -- with the thinning configured too (``configure_thinning``) those
         of the thinned points, and its z step under ``thinning``; with the geometric circle fit configured as well
-        (``configure_circle_fit``) their circles are the refined ones, and ``circle`` is "geometric"."""
+        (``configure_circle_fit``) their circles are the refined ones, and ``circle`` is "geometric"; with the helix
+        slope configured (``configure_helix_slope``) their slope, vz and B rho come from the turning angle about the
+        circle's centre, and ``slope`` is "helix"."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         self._trace_rows_defaults()
         ctx = self.ctx
@@ -290,12 +293,14 @@ class Engine:
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
-                    **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx)}
+                    **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
+                    **helix_result(ctx)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
-                **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx)}
+                **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
+                    **helix_result(ctx)}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -322,6 +327,15 @@ class Engine:
         made --, neither turns it off (the default).  Without the estimates it does nothing."""
         configure_circle(self.ctx, _settings(CircleFitSettings, circle, parameters))
 
+    def configure_helix_slope(self, settings=None, **parameters) -> None:
+        """The helix slope behind the circle of the track estimates (include/attpc_engine.h, "helix slope"): a
+        ``detector.helix.HelixSlopeSettings`` or its keyword (regressor) turns it on -- slope, vz and B rho of the
+        estimates of ``run_trace_rows`` / ``run_estimates`` then come from the regression of z against the turning
+        angle of the segment's points about the centre of the record's circle, and ``detector.helix.STATUS_BITS["NO_HELIX"]`` marks
+        a record in which it could not run --, neither turns it off (the default).  Without the estimates it does
+        nothing."""
+        configure_helix(self.ctx, _settings(HelixSlopeSettings, settings, parameters))
+
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
         128 bytes per track cross PCIe (``estimates`` [n, n_sim], ``detector.estimate.ESTIMATE_DTYPE``), beside the
@@ -342,7 +356,7 @@ class Engine:
         return {"estimates": ctx.estimates_last(n_events, len(self.indices)), "indices": list(self.indices),
                 "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
                 "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx),
-                **circle_result(ctx)}
+                **circle_result(ctx), **helix_result(ctx)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

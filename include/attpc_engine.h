@@ -1448,6 +1448,77 @@ ATTPC_API int32_t attpc_rows_estimate_circle(attpc_ctx* ctx, int64_t n_events, c
                                              const attpc_estimate_desc* desc, const attpc_circle_desc* circle,
                                              attpc_track_estimate* out);
 
+/* ---- helix slope (opt-in: off by default, and with it off every output, kernel and buffer of every entry point is what
+ * it is without this section; the entry points are additions under ABI version 3) ----
+ * The slope of step 6 is the regression of z against the cumulated pad-plane distance between consecutive points.
+ * Every bit of lateral scatter lengthens that zig-zag path, so cot(theta) comes out low and the polar angle is pulled
+ * towards pi/2, most for stiff forward tracks.  With this stage on, a point's progress is its TURNING ANGLE about the
+ * centre of the record's circle instead -- the radial scatter drops out of the path -- and slope, vz and brho are made
+ * from the regression of z against that angle.  tests/helix_reference.py restates this contract in numpy;
+ * csrc/helix_host.hpp is its arithmetic, shared by the kernel and the host.  A "unit" is 1/16 mm, as above.
+ * Settings (attpc_helix_desc): regressor 0 = auto, 1 = z against the path, 2 = the path against z; reserved = 0.
+ * When: only in a record that has a circle (no NO_CIRCLE; Kasa or refined, an unconverged refined one included), on the
+ * circle the record carries: centre (a, b) and radius R in units relative to (X0, Y0).  A NO_CIRCLE record gets
+ * NO_HELIX too and is otherwise unchanged; EMPTY and FEW records are untouched and get no NO_HELIX.
+ *   1. Turning angle.  For segment rank i = 0 .. m - 1 with the integers u_i, v_i, w_i of step 5, in f64:
+ *        px = u - a;  py = v - b;  p0 = (-a, -b), rank 0's;  cr = p0x py - p0y px;  dt = p0x px + p0y py
+ *        phi_q = (int) rint(65536 atan2w(cr, dt)), an integer in -205887 .. 205887
+ *      atan2w(y, x) is WRITTEN arithmetic: + - * / only, one rounding per operation, no fused multiply-add:
+ *        ax = |x|;  ay = |y|;  hi = the larger, lo = the smaller;  hi == 0: the result is 0;  t = lo / hi
+ *        t > 0.41421356237309503: r = (t - 1) / (t + 1), base = pi/4;  otherwise r = t, base = 0;  z = r r
+ *        p = c_19;  p = p z + c_k for k = 18 .. 0, c_k = (-1)^k / (2 k + 1) as f64 (the 20 Taylor coefficients)
+ *        at = base + r p;  if ay > ax: at = pi/2 - at;  then if x < 0: at = pi - at;  then if y < 0: at = -at
+ *      with pi = 3.141592653589793, pi/2 = 1.5707963267948966, pi/4 = 0.7853981633974483 and plain comparisons (-0.0 is
+ *      not negative).  |r| < 0.4143, so the truncation is below 5e-18; against the C library the result differs by at
+ *      most 4.44e-16 (2 ulp of pi, observed on 3e6 inputs) and rint(65536 .) of the two never.  An angle that is not a
+ *      number (a circle so large that the products overflow) gives NO_HELIX.
+ *   2. Unwrap, integers only.  K_0 = 0; for i >= 1 with D = phi_q_i - phi_q_(i-1): j_i = -1 if D > 205887, +1 if
+ *      D < -205887, else 0; K_i = K_(i-1) + j_i; PHI_i = phi_q_i + 411775 K_i  (411775 = rint(2 pi 65536),
+ *      205887 = rint(pi 65536)).  Any |PHI_i| >= 2^24 (about 40 turns): NO_HELIX.
+ *   3. Sums, 64-bit integers: SP = sum PHI, SPP = sum PHI PHI, SPw = sum PHI w, Sww = sum w w; Sw and m are step 5's.
+ *      Bounds: |PHI| < 2^24, |w| <= 2^18 and m <= 2^11, so SPP < 2^11 2^48 = 2^59, |SPw| < 2^11 2^24 2^18 = 2^53 and
+ *      Sww <= 2^11 2^36 = 2^47 -- inside 2^63 (in a record past the cap the sums are not used; an implementation lets
+ *      such an angle add nothing).  Nothing can overflow: the sums are exact and independent of any order of summation.
+ *   4. Closed form, f64: the sums converted once each, then exactly these operations, left to right, no fused
+ *      multiply-add, + - * / and sqrt only.  M = (double) m.
+ *        vp = M SPP - SP SP;  vw = M Sww - Sw Sw;  cv = M SPw - SP Sw
+ *      vp == 0 (no angular spread; a first point at the centre ends here): NO_HELIX.
+ *      B ("the path against z") holds with regressor 2; with regressor 0 iff vw 4294967296.0 >= vp R R and cv != 0 (the
+ *      regressor is the coordinate with the larger spread); not with regressor 1.
+ *        q = vw / cv with B (cv == 0: NO_HELIX), else q = cv / vp;  q not finite: NO_HELIX
+ *        sg = +1 if SP >= 0 else -1;  slope = b = (sg 65536.0 q) / R   (dz/ds along the direction of travel: a backward
+ *                                                                        track has b < 0, as in step 6)
+ *        a0 = (Sw - q SP) / M;  pv = (-(X0 + a), -(Y0 + b_centre))
+ *        Pv = rint(65536 atan2w(p0x pvy - p0y pvx, p0x pvx + p0y pvy))  (a double, not unwrapped)
+ *        vz = (Z0 + a0 + q Pv) / 16   (NaN with ON_AXIS, as in step 6)
+ *        brho = magnetic_field radius 1e-3 sqrt(1 + b b)
+ * With NO_HELIX the record is exactly the one the stage-off contract gives, plus the bit.  Otherwise only slope, vz,
+ * brho and the status change: a NO_SLOPE bit of step 6 is cleared.  The counts, arc, charge, dedx, the circle, vx, vy,
+ * x_mean, y_mean and reserved do not change.  A record stays a pure function of the event's rows; with thinning on, the
+ * fused records are still DEFINED as this contract on the event's point rows. */
+#define ATTPC_EST_NO_HELIX 256   /* the stage was on and could not run; the record is step 6's */
+#define ATTPC_HELIX_AUTO 0
+#define ATTPC_HELIX_Z_ON_PATH 1
+#define ATTPC_HELIX_PATH_ON_Z 2
+
+typedef struct attpc_helix_desc {
+  int32_t regressor;  /* 0 = auto, 1 = z against the path, 2 = the path against z */
+  int32_t reserved;   /* 0 */
+} attpc_helix_desc;
+
+/* desc == NULL turns the stage off (the default).  Independent of every other configure call.  ATTPC_E_INVALID for a
+ * regressor outside 0 .. 2 or a non-zero reserved.  Takes effect only in the trace-row calls in which the estimates are
+ * on, on raw rows and on thinned points, behind the Kasa circle and behind the geometric circle fit: the estimate kernel
+ * that runs is then its instantiation with one more pass.  Alone it is inert: no kernel, no buffer.  The trace rows,
+ * labels, offsets and checksums of the call do not change. */
+ATTPC_API int32_t attpc_trace_configure_helix(attpc_ctx* ctx, const attpc_helix_desc* desc);
+/* attpc_rows_estimate_circle with the helix slope of `helix` (not NULL) behind the circle; `circle` may be NULL: the
+ * Kasa circle then.  Errors as attpc_rows_estimate_circle, and ATTPC_E_INVALID for a helix desc out of range. */
+ATTPC_API int32_t attpc_rows_estimate_helix(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                            const int64_t* labels, const attpc_event_layout* layout,
+                                            const attpc_estimate_desc* desc, const attpc_circle_desc* circle,
+                                            const attpc_helix_desc* helix, attpc_track_estimate* out);
+
 /* ---- track straggling (opt-in: off by default, and with it off every output, kernel and buffer of every entry point
  * is what it is without this section; the entry point is an addition under ABI version 3) ----
  * The track integrator solves a deterministic equation of motion, so two particles of one momentum follow one path.

@@ -20,11 +20,18 @@ Geometric circle fit (attpc_trace_configure_circle): ``--circle``
 against the estimates with the geometric fit behind it, alternating (both legs on raw rows, or with ``--thinning Z`` on
 the points of that z step), and repeats the yield with the Kasa circle and with the geometric fit -- on the raw rows, or
 at every step of ``--thin-steps`` if given -- with the distribution of the evaluations made (``reserved``) beside it.
+Helix slope (attpc_trace_configure_helix): ``--helix`` times the estimates with the zig-zag slope against
+the estimates with the helix slope, alternating (both legs with ``--thinning Z`` and ``--circle`` as given), and repeats
+the yield with the stage off and on at every step of ``--thin-steps`` -- with the share of NO_HELIX and the share of
+tracks for which regressor "auto" took the path against z (the records of three runs, one per regressor, compared)
+beside it.  ``--helix-off-only`` times the stage-off leg alone: what a library without the helix entry points
+(``ATTPC_HIP_LIBRARY``, a build of the parent commit) can run, to set beside the same leg of this build.
 ``--profile WORKLOAD`` runs two ``run_estimates`` calls in partial readout and nothing else, for
 ``rocprofv3 --kernel-trace --stats -- python tools/estimate_rate.py --profile o16aa`` (a run of its own).
 
     python tools/estimate_rate.py [--events N] [--reps K] [--stats-events M] [--workloads o16aa,be10dp] [--out FILE]
                                   [--thinning Z | --estimates-only] [--thin-steps 2,5,10] [--min-points P] [--circle]
+                                  [--helix | --helix-off-only]
 """
 from __future__ import annotations
 
@@ -144,36 +151,93 @@ def circle_rates(eng, events: int, reps: int, z_step, min_points: int) -> dict:
     return {"rows_per_event": rows / events, "z_step": z_step, **{k: [_median(v), min(v), max(v)] for k, v in legs.items()}}
 
 
-def yield_(eng, events: int, total: int, z_step=None, min_points: int = 30, circle: bool = False) -> dict:
+def helix_rates(eng, events: int, reps: int, z_step, min_points: int, circle: bool, off_only: bool = False) -> dict:
+    """The estimates with the zig-zag slope against the estimates with the helix slope (``z_step``: both on the thinned
+    points of that step; ``circle``: both behind the geometric circle fit; ``off_only``: the first leg alone)."""
+    from attpc_engine_amd.detector.circle import CircleFitSettings
+    from attpc_engine_amd.detector.estimate import EstimateSettings
+
+    kinds = ("zigzag",) if off_only else ("zigzag", "helix")
+    legs = {kind: [] for kind in kinds}
+    eng.configure_estimates(EstimateSettings(min_points=min_points))
+    if z_step is not None:
+        eng.configure_thinning(z_step=z_step)
+    if circle:
+        eng.configure_circle_fit(CircleFitSettings())
+
+    def call(kind: str):
+        if not off_only:
+            eng.configure_helix_slope(**({"regressor": "auto"} if kind == "helix" else {}))
+        t0 = time.perf_counter()
+        res = eng.run_trace_rows(events, seed=1, fetch=False)
+        return events / (time.perf_counter() - t0), res
+
+    for kind in kinds:
+        call(kind)
+    rows = 0
+    for _ in range(reps):
+        for kind in kinds:
+            rate, res = call(kind)
+            legs[kind].append(rate)
+            rows = res["trace_rows"]["n_rows"]
+    eng.configure_estimates()
+    eng.configure_thinning()
+    eng.configure_circle_fit()
+    if not off_only:
+        eng.configure_helix_slope()
+    return {"rows_per_event": rows / events, "z_step": z_step, "circle": circle, **{k: [_median(v), min(v), max(v)] for k, v in legs.items()}}
+
+
+def yield_(eng, events: int, total: int, z_step=None, min_points: int = 30, circle: bool = False, helix: bool = False) -> dict:
     import numpy as np
 
     from attpc_engine_amd.detector.circle import CircleFitSettings
-    from attpc_engine_amd.detector.estimate import STATUS_BITS, EstimateSettings, polar, truth_tracks
+    from attpc_engine_amd.detector.estimate import EstimateSettings, polar, truth_tracks
+    from attpc_engine_amd.detector.helix import STATUS_BITS
 
     eng.configure_estimates(EstimateSettings(min_points=min_points))
     if z_step is not None:
         eng.configure_thinning(z_step=z_step)
     eng.configure_circle_fit(CircleFitSettings() if circle else None)
-    est, truth = [], []
-    for first in range(0, total, events):
-        res = eng.run_estimates(min(events, total - first), seed=1, first_event=first)
-        est.append(res["estimates"])
-        truth.append(truth_tracks(res["p4"], res["indices"], eng.z))
+    est, truth, fixed = [], [], {"z_on_path": [], "path_on_z": []}
+    for regressor in (("auto", "z_on_path", "path_on_z") if helix else (None,)):
+        if helix:
+            eng.configure_helix_slope(regressor=regressor)
+        for first in range(0, total, events):
+            res = eng.run_estimates(min(events, total - first), seed=1, first_event=first)
+            if regressor in fixed:
+                fixed[regressor].append(res["estimates"])
+                continue
+            est.append(res["estimates"])
+            truth.append(truth_tracks(res["p4"], res["indices"], eng.z))
     eng.configure_estimates()
     if z_step is not None:
         eng.configure_thinning()
     eng.configure_circle_fit()
+    if helix:
+        eng.configure_helix_slope()
     est = np.concatenate(est)
     field = float(eng.config.det_params.bfield)
     truth = {k: np.concatenate([t[k] for t in truth]) for k in truth[0]}
     out = {"tracks": int(est.size), "indices": list(eng.indices), "z_step": z_step, "min_points": min_points,
-           "circle": "geometric" if circle else "kasa", "positions": []}
+           "circle": "geometric" if circle else "kasa", "slope": "helix" if helix else "zigzag", "positions": []}
+    if helix:
+        fixed = {k: np.concatenate(v) for k, v in fixed.items()}
     for s in range(est.shape[1]):
         e = est[:, s]
         pos = {"status": {name: float((e["status"] & bit != 0).mean()) for name, bit in STATUS_BITS.items()},
                "clean": float((e["status"] == 0).mean())}
         good = np.isfinite(e["brho"]) & np.isfinite(e["slope"]) & np.isfinite(truth["brho"][:, s])
         pos["estimated"] = float(good.mean())
+        if helix:  # which regressor "auto" took: its slope is bit for bit the one of that regressor's run
+            ran_helix = np.isfinite(e["slope"]) & (e["status"] & STATUS_BITS["NO_HELIX"] == 0) & (e["n_fit"] > 0)
+            same = {k: e["slope"].view(np.int64) == v[:, s]["slope"].view(np.int64) for k, v in fixed.items()}
+            if ran_helix.any():
+                pos["auto"] = {"path_on_z": float((same["path_on_z"] & ~same["z_on_path"])[ran_helix].mean()),
+                               "z_on_path": float((same["z_on_path"] & ~same["path_on_z"])[ran_helix].mean()),
+                               "either": float((same["z_on_path"] & same["path_on_z"])[ran_helix].mean())}
+            fitted = e["n_fit"] > 0
+            pos["no_helix_of_fitted"] = float((e["status"][fitted] & STATUS_BITS["NO_HELIX"] != 0).mean()) if fitted.any() else 0.0
         ran = e["reserved"] > 0
         if ran.any():  # the geometric circle fit: the evaluations of the records it ran on
             pos["evaluations"] = {"share": float(ran.mean()), "median": float(np.median(e["reserved"][ran])),
@@ -202,6 +266,9 @@ def _print_yield(y: dict) -> None:
         for key in ("brho_rel", "polar", "radius_rel", "arc_over_2chord_to_mean"):
             if key in pos:
                 print(f"    {key}: median {pos[key]['median']:+.4f}, 16 .. 84 % half-width {pos[key]['half_width_16_84']:.4f}")
+        if "auto" in pos:
+            print(f"    NO_HELIX {100 * pos['no_helix_of_fitted']:.2f} % of the fitted tracks; auto took the path against z for "
+                  f"{100 * pos['auto']['path_on_z']:.1f} %, z against the path for {100 * pos['auto']['z_on_path']:.1f} %")
         if "evaluations" in pos:
             ev = pos["evaluations"]
             print(f"    evaluations (fit ran on {100 * ev['share']:.1f} %): median {ev['median']:.0f}, 90 % {ev['p90']:.0f}, max {ev['max']}")
@@ -264,7 +331,39 @@ def circle_main(args) -> None:
                     f.write(json.dumps(line) + "\n")
 
 
-def profile(name: str, events: int, z_step=None, min_points: int = 30, circle: bool = False) -> None:
+def helix_main(args) -> None:
+    steps = [float(z) for z in args.thin_steps.split(",") if z] or [None]
+    for name in args.workloads.split(","):
+        for mode in MODES:
+            eng = _engine(name, mode)
+            line = {"workload": name, "mode": mode, "events": args.events, "min_points": args.min_points}
+            if args.reps > 0:
+                r = line["rates"] = helix_rates(eng, args.events, args.reps, args.thinning, args.min_points, args.circle, args.helix_off_only)
+                where = "raw rows" if args.thinning is None else f"points of {args.thinning} mm"
+                print(f"## {name} / {mode}: {r['rows_per_event']:.1f} trace rows per event, min_points {args.min_points}, {where}, "
+                      f"{'geometric' if args.circle else 'kasa'} circle", flush=True)
+                for leg in ("zigzag", "helix"):
+                    if leg in r:
+                        print(f"  run_trace_rows(fetch=False), {leg:9s} {r[leg][0]:12.0f} events/s  ({r[leg][1]:.0f} .. {r[leg][2]:.0f})")
+                if "helix" in r:
+                    cost = 1.0 / r["helix"][0] - 1.0 / r["zigzag"][0]
+                    print(f"  cost of the helix slope: {cost * 1e9:.0f} ns per event, "
+                          f"{100.0 * (1.0 - r['helix'][0] / r['zigzag'][0]):.2f} % of the rate without it")
+            line["yield"] = []
+            for z_step in (steps if args.stats_events > 0 and not args.helix_off_only else []):
+                for helix in (False, True):
+                    y = yield_(eng, args.events, args.stats_events, z_step, args.min_points, args.circle, helix)
+                    line["yield"].append(y)
+                    print(f"## {name} / {mode}: records of {args.stats_events} events, " + ("raw rows" if z_step is None else f"z step {z_step} mm")
+                          + f", {y['circle']} circle, {y['slope']} slope", flush=True)
+                    _print_yield(y)
+            eng.ctx.close()
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+
+
+def profile(name: str, events: int, z_step=None, min_points: int = 30, circle: bool = False, helix: bool = False) -> None:
     from attpc_engine_amd.detector.estimate import EstimateSettings
 
     eng = _engine(name, "partial")
@@ -273,6 +372,8 @@ def profile(name: str, events: int, z_step=None, min_points: int = 30, circle: b
         eng.configure_thinning(z_step=z_step)
     if circle:
         eng.configure_circle_fit(max_evaluations=32)
+    if helix:
+        eng.configure_helix_slope(regressor="auto")
     eng.run_estimates(events, seed=1)
     eng.run_estimates(events, seed=1)
 
@@ -290,9 +391,13 @@ def main() -> None:
     ap.add_argument("--thin-steps", default="")
     ap.add_argument("--min-points", type=int, default=30)
     ap.add_argument("--circle", action="store_true")
+    ap.add_argument("--helix", action="store_true")
+    ap.add_argument("--helix-off-only", action="store_true")
     args = ap.parse_args()
     if args.profile:
-        return profile(args.profile, args.events, args.thinning, args.min_points, args.circle)
+        return profile(args.profile, args.events, args.thinning, args.min_points, args.circle, args.helix)
+    if args.helix or args.helix_off_only:
+        return helix_main(args)
     if args.circle:
         return circle_main(args)
     if args.thinning is not None or args.estimates_only or args.thin_steps:
