@@ -326,6 +326,12 @@ class StraggleDesc(C.Structure):  # attpc_straggle_desc
                 ("electron_density", C.c_double), ("stream", C.c_uint32)]
 
 
+class DistortDesc(C.Structure):  # attpc_distort_desc
+    _fields_ = [("rho_step", C.c_double), ("tau_step", C.c_double), ("tb_origin", C.c_double),
+                ("n_rho", C.c_int32), ("n_tau", C.c_int32),
+                ("radial", _dp), ("azimuthal", _dp), ("time", _dp)]
+
+
 TRACE_PACK_FORMAT = "for64-bitplane-v1"  # ATTPC_TRACE_PACK_FORMAT
 TRACE_PACK_MAX_ROW_BYTES = 784
 
@@ -420,6 +426,7 @@ EXPORTED_SYMBOLS = (
     "attpc_det_configure_straggling",
     "attpc_trace_configure_circle", "attpc_rows_estimate_circle",
     "attpc_trace_configure_helix", "attpc_rows_estimate_helix",
+    "attpc_det_configure_distortion", "attpc_samples_distort",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -467,6 +474,9 @@ CIRCLE_SYMBOLS = ("attpc_trace_configure_circle", "attpc_rows_estimate_circle")
 
 # ... and the helix slope after the geometric circle fit: the same rule.
 HELIX_SYMBOLS = ("attpc_trace_configure_helix", "attpc_rows_estimate_helix")
+
+# ... and the drift distortion after the helix slope: the same rule.
+DISTORT_SYMBOLS = ("attpc_det_configure_distortion", "attpc_samples_distort")
 
 _lib = None
 
@@ -673,6 +683,14 @@ def load_library() -> C.CDLL:
     for name, argtypes in helix.items():
         if not no_helix:
             getattr(lib, name).argtypes = argtypes
+    distortion = {
+        "attpc_det_configure_distortion": [ctxp, C.POINTER(DistortDesc)],
+        "attpc_samples_distort": [ctxp, C.c_int64, _dp, C.POINTER(DistortDesc), _dp],
+    }
+    no_distortion = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in DISTORT_SYMBOLS)
+    for name, argtypes in distortion.items():
+        if not no_distortion:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -699,7 +717,8 @@ def load_library() -> C.CDLL:
                 or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)
                 or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)
                 or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)
-                or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)):
+                or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)
+                or (no_distortion and name in DISTORT_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -709,7 +728,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion")
 
 
 class Context:

@@ -177,6 +177,9 @@ struct attpc_ctx {
   DevAllocs det_allocs;
   bool straggle_on = false;        // attpc_det_configure_straggling (kept over attpc_det_configure)
   attpc_straggle_desc straggle{};
+  bool distort_on = false;         // attpc_det_configure_distortion (kept over attpc_det_configure)
+  DistortMap distort{};            // the tables on the device
+  DevAllocs distort_allocs;
 
   TrackSet tset[2];
   // cloud of one chunk
@@ -585,6 +588,14 @@ int32_t launch_tracks(attpc_ctx* ctx, TrackSet& ts, const TrackLaunch& tl) {
     HIP_TRY(ctx, hipEventRecord(ts.t0, ctx->stream_t));
     launch_track_kernel(blocks, lds, ctx->stream_t, ta, ctx->straggle_on ? &ctx->straggle : nullptr);
     HIP_TRY(ctx, hipGetLastError());
+    if (ctx->distort_on) {
+      // the drift distortion of the batch's records, in place and here only: once per run of the track kernel,
+      // however often the batch is scattered; a batch run again for a larger arena passes here again
+      uint32_t limit = (uint32_t)ctx->n_cus * (uint32_t)ctx->opt_track_blocks_per_cu;
+      if (ctx->opt_track_workgroups > 0) limit = std::min<uint32_t>(limit, (uint32_t)ctx->opt_track_workgroups);
+      launch_distort(distort_workgroups(n_tracks, limit), ctx->stream_t, DistortArgs{ctx->distort, ta.buf, n_tracks});
+      HIP_TRY(ctx, hipGetLastError());
+    }
     HIP_TRY(ctx, hipEventRecord(ts.t1, ctx->stream_t));
   }
   if (tl.use_status && tl.n) {  // events that hit event_sample_limit
@@ -2669,6 +2680,81 @@ int32_t attpc_det_configure_straggling(attpc_ctx* ctx, const attpc_straggle_desc
   { int32_t rc0 = drop_prefetch(ctx); if (rc0) return rc0; }
   ctx->straggle_on = d != nullptr;
   ctx->straggle = d ? *d : attpc_straggle_desc{};
+  return ATTPC_OK;
+}
+
+// ---- drift distortion (distort.hip, distort_host.hpp; the contract is in include/attpc_engine.h) ----
+// the tables of a checked desc on the device, owned by `owner` (a NULL table stays NULL: zeros)
+static int32_t upload_distort_map(attpc_ctx* ctx, DevAllocs& owner, const attpc_distort_desc& d, DistortMap* map) {
+  const size_t nodes = (size_t)d.n_rho * (size_t)d.n_tau;
+  DistortMap m{d.rho_step, d.tau_step, d.tb_origin, d.n_rho, d.n_tau, nullptr, nullptr, nullptr};
+  int32_t rc;
+  if (d.radial && (rc = upload(ctx, owner, d.radial, nodes, &m.radial))) return rc;
+  if (d.azimuthal && (rc = upload(ctx, owner, d.azimuthal, nodes, &m.azimuthal))) return rc;
+  if (d.time && (rc = upload(ctx, owner, d.time, nodes, &m.time))) return rc;
+  *map = m;
+  return ATTPC_OK;
+}
+
+int32_t attpc_det_configure_distortion(attpc_ctx* ctx, const attpc_distort_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d) {
+    const char* wrong = distort_desc_error(*d);
+    if (wrong) return fail(ctx, ATTPC_E_INVALID, "attpc_det_configure_distortion: %s", wrong);
+  }
+  // nothing in flight may read the old tables (and a track batch queued ahead was made under the old map)
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  { int32_t rc0 = drop_prefetch(ctx); if (rc0) return rc0; }
+  ctx->distort_on = false;
+  ctx->distort = DistortMap{};
+  ctx->distort_allocs.clear();
+  if (!d || distort_desc_is_off(*d)) return ATTPC_OK;
+  int32_t rc = upload_distort_map(ctx, ctx->distort_allocs, *d, &ctx->distort);
+  if (rc) {
+    ctx->distort_allocs.clear();
+    return rc;
+  }
+  ctx->distort_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_samples_distort(attpc_ctx* ctx, int64_t n, const double* samples, const attpc_distort_desc* d, double* out) {
+  if (!ctx || !d || n < 0 || n > ((int64_t)1 << 36) || (n > 0 && (!samples || !out))) return ATTPC_E_INVALID;
+  const char* wrong = distort_desc_error(*d);
+  if (wrong) return fail(ctx, ATTPC_E_INVALID, "attpc_samples_distort: %s", wrong);
+  if (n == 0) return ATTPC_OK;
+  if (distort_desc_is_off(*d)) {
+    if (out != samples) std::memcpy(out, samples, (size_t)n * 4 * sizeof(double));
+    return ATTPC_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the array as chains of consecutive arena blocks: "tracks" of MAX_BLOCKS_PER_TRACK blocks, the last one shorter
+  constexpr int64_t CHAIN = (int64_t)MAX_BLOCKS_PER_TRACK * ARENA_BLK;
+  const size_t n_blocks = (size_t)((n + ARENA_BLK - 1) / ARENA_BLK);
+  const uint32_t n_tracks = (uint32_t)((n + CHAIN - 1) / CHAIN);
+  std::vector<int32_t> table((size_t)n_tracks * MAX_BLOCKS_PER_TRACK, -1), counts(n_tracks);
+  for (size_t b = 0; b < n_blocks; ++b) table[b] = (int32_t)b;
+  for (uint32_t t = 0; t < n_tracks; ++t) counts[t] = (int32_t)std::min<int64_t>(CHAIN, n - (int64_t)t * CHAIN);
+  DevAllocs tables;  // this call's own copy of the map, freed when it returns
+  DistortArgs a{};
+  int32_t rc = upload_distort_map(ctx, tables, *d, &a.map);
+  // (the arena's tail past record n is read by the kernel's whole-block loads and never stored)
+  double* d_arena = stage<double>(ctx, 0, n_blocks * ARENA_BLK * 4, rc);
+  const int32_t* d_table = stage_in(ctx, 1, table.data(), table.size(), rc);
+  const int32_t* d_counts = stage_in(ctx, 2, counts.data(), counts.size(), rc);
+  uint32_t* d_ctrl = stage<uint32_t>(ctx, 3, TRK_WORDS, rc);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(d_arena, samples, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(d_ctrl, 0, TRK_WORDS * sizeof(uint32_t), ctx->stream));
+  a.buf = TrackBuffers{d_arena, const_cast<int32_t*>(d_table), const_cast<int32_t*>(d_counts), nullptr, d_ctrl,
+                       (uint32_t)std::min<size_t>(n_blocks, 0xFFFFFFFFu)};
+  a.n_tracks = n_tracks;
+  uint32_t limit = (uint32_t)ctx->n_cus * (uint32_t)ctx->opt_track_blocks_per_cu;
+  if (ctx->opt_track_workgroups > 0) limit = std::min<uint32_t>(limit, (uint32_t)ctx->opt_track_workgroups);
+  launch_distort(distort_workgroups(n_tracks, limit), ctx->stream, a);
+  HIP_TRY(ctx, hipGetLastError());
+  if ((rc = stage_out(ctx, out, d_arena, (size_t)n * 4))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (before `tables` and the host vectors go)
   return ATTPC_OK;
 }
 

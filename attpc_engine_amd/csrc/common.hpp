@@ -199,9 +199,10 @@ enum TrackWord : int {
   TRK_OVERFLOW = 2,     // != 0: the arena ran out, the host repeats the batch with a larger one
   TRK_AT_LIMIT = 3,     // events at the sample limit (count_status_kernel)
   TRK_CAPPED = 4,       // tracks ended by the sample cap (path-length step)
+  TRK_NEXT_DISTORT = 5, // next unassigned track of the drift distortion pass behind the track kernel (distort.hip)
   TRK_WORDS = 16
 };
-static_assert(TRK_CAPPED < TRK_WORDS, "track control words");
+static_assert(TRK_NEXT_DISTORT < TRK_WORDS, "track control words");
 
 struct TrackBuffers {
   double* arena;          // [arena_blocks][ARENA_BLK][4]

@@ -1,6 +1,7 @@
 // tracks_args.hpp -- kernel argument blocks and host launch wrappers (one per kernel file).
 #pragma once
 #include "common.hpp"
+#include "distort_host.hpp"
 #include "unpack_host.hpp"
 
 namespace attpc {
@@ -50,6 +51,20 @@ void launch_decay_calculate(hipStream_t s, uint32_t n, const double* parent, dou
 // straggling, track_kernel<*, true> with an argument block of its own (tracks.hip)
 void launch_track_kernel(uint32_t blocks, size_t lds_bytes, hipStream_t s, const TrackArgs& a,
                          const attpc_straggle_desc* straggle = nullptr);
+// drift distortion of a track batch's records (distort.hip; attpc_det_configure_distortion, the contract is in
+// include/attpc_engine.h): every record below counts[t] of tracks 0 .. n_tracks - 1 is shifted in place by `map`
+struct DistortArgs {
+  DistortMap map;       // the tables on the device
+  TrackBuffers buf;     // ctrl[TRK_NEXT_DISTORT] zero before the launch; ctrl[TRK_OVERFLOW] != 0: nothing is touched
+  uint32_t n_tracks;
+};
+// persistent waves, four per workgroup, each taking four tracks at a time: `workgroups` = distort_workgroups(n_tracks,
+// limit) > 0
+inline uint32_t distort_workgroups(uint32_t n_tracks, uint32_t limit) {
+  const uint32_t want = (n_tracks + 15u) / 16u;
+  return want < limit ? (want ? want : 1u) : (limit ? limit : 1u);
+}
+void launch_distort(uint32_t workgroups, hipStream_t s, const DistortArgs& a);
 // scatter.hip compiled as it is / through scatter_small.hip (workgroups per CU: 1 / 2)
 void launch_scatter_kernel_big(uint32_t n_workgroups, hipStream_t s, const ScatterArgs& a);
 void launch_scatter_kernel_small(uint32_t n_workgroups, hipStream_t s, const ScatterArgs& a);

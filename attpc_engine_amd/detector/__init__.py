@@ -1,5 +1,6 @@
 """Detector effects: same public names as the reference package (reference
 ``detector/__init__.py:13-21``) plus the batch entry points, device backed."""
+from . import distortion as _distortion
 from . import maps as _maps
 from . import parameters as _parameters
 from . import selection as _selection
@@ -23,6 +24,7 @@ _EXPORTS = {
     _selection: ("Selection", "configure_selection", "simulate_batch_selected", "clouds_to_selection"),
     _maps: ("MapsSettings", "RunMaps", "configure_maps", "simulate_batch_maps", "clouds_to_maps"),
     _straggling: ("StragglingSettings", "configure_straggling", "radiation_length", "electron_density"),
+    _distortion: ("DistortionMap", "configure_distortion", "samples_to_distortion"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

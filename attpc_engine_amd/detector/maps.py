@@ -128,12 +128,14 @@ def configure_maps(ctx: _abi.Context, maps: MapsSettings | None = None, **parame
 
 def simulate_batch_maps(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config, seed: int,
                         indices: list[int], maps: MapsSettings | None = None, selection=None, first_event: int = 0,
-                        ctx: _abi.Context | None = None, min_electrons: int | None = None, straggling=None) -> dict:
+                        ctx: _abi.Context | None = None, min_electrons: int | None = None, straggling=None,
+                        distortion=None) -> dict:
     """simulate() for n events with the clouds left on the device and accumulated there (``attpc_det_run_maps``; ``maps``
     default ``MapsSettings()``, with ``maps.selected`` the ``selection``) -> a dict: maps (``RunMaps``), events [n] and
     tracks [n, n_sim] (the records of all events, as ``simulate_batch_summary``), passed [n] bool (the events that
     contributed), stats.  ``straggling`` (a ``detector.straggling.StragglingSettings``; None = off): the track
-    straggling."""
+    straggling.  ``distortion`` (a ``detector.distortion.DistortionMap``; None = off): the drift distortion."""
+    from .distortion import configure_distortion
     from .luts import build_layout, species_for
     from .selection import Selection, configure_selection
     from .simulator import configure_detector
@@ -156,6 +158,7 @@ def simulate_batch_maps(momenta: np.ndarray, vertices: np.ndarray, proton_number
     keys = species_for(proton_numbers, mass_numbers, indices)
     configure_detector(config, keys, ctx)
     configure_straggling(ctx, straggling, config)
+    configure_distortion(ctx, distortion, config)
     configure_summary(config, ctx, min_electrons)
     if maps.selected:
         configure_selection(ctx, selection)

@@ -166,13 +166,15 @@ def simulate_batch_selected(momenta: np.ndarray, vertices: np.ndarray, proton_nu
                             seed: int, indices: list[int], selection: Selection, kind: str = "cloud",
                             first_event: int = 0, ctx: _abi.Context | None = None, min_electrons: int | None = None,
                             response: np.ndarray | None = None, capacity_per_event: int | None = None,
-                            straggling=None) -> dict:
+                            straggling=None, distortion=None) -> dict:
     """simulate() for n events, delivering only the events that pass ``selection`` (``attpc_det_run_selected``):
     ``kind`` "cloud" -> points [P,3] as ``simulate_batch``, "spyral" -> rows [P',8] as ``simulate_batch_spyral``.
     Returns a dict: passed [n] bool, n_passed, n_rows, offsets [n+1] (a rejected event is an empty range), points or
     rows, labels, event_points [n] (cloud rows of every event before selection and threshold), events [n] and tracks
     [n, n_sim] (the records of all events, as ``simulate_batch_summary`` with ``min_electrons``), stats.  ``straggling``
-    (a ``detector.straggling.StragglingSettings``; None = off): the track straggling."""
+    (a ``detector.straggling.StragglingSettings``; None = off): the track straggling.  ``distortion`` (a
+    ``detector.distortion.DistortionMap``; None = off): the drift distortion; a cut on a track's end point sees the
+    shifted, apparent one."""
     from .simulator import configure_spyral, run_batch
     from .summary import SummarySettings, configure_summary
 
@@ -191,6 +193,7 @@ def simulate_batch_selected(momenta: np.ndarray, vertices: np.ndarray, proton_nu
     per_event = capacity_per_event if capacity_per_event is not None else (16384 if kind == "cloud" else 8192)
     arrays, stats = run_batch("attpc_det_run_selected", momenta, vertices, proton_numbers, mass_numbers, config, seed,
                               list(indices), first_event, ctx, per_event, configure=configure, straggling=straggling,
+                              distortion=distortion,
                               holder=SelectedArrays,
                               width=ROW_KINDS[kind], n_sim=len(indices), slack=1024)
     return selected_result(arrays, kind, stats.as_dict())

@@ -85,12 +85,15 @@ def configure_spyral(config: Config, ctx: _abi.Context, response: np.ndarray | N
 
 
 def run_batch(call: str, momenta, vertices, proton_numbers, mass_numbers, config: Config, seed, indices, first_event,
-              ctx: _abi.Context | None, capacity_per_event: int, configure=None, straggling=None, **how):
+              ctx: _abi.Context | None, capacity_per_event: int, configure=None, straggling=None, distortion=None, **how):
     """What simulate_batch, simulate_batch_spyral and simulate_batch_traces share: the inputs as the C ABI takes them,
     the detector on ``ctx`` (``configure_detector``), then the mode's own settings (``configure(ctx)``, which may return
     the rows per event the mode is known to need), the layout and ``lib.<call>`` under ``call_with_capacity(**how)``
     -> (the output holder, the run's RunStats).  ``straggling`` (a ``detector.straggling.StragglingSettings``; None =
-    off): the track straggling of the call's tracks, on the gas of ``config``."""
+    off): the track straggling of the call's tracks, on the gas of ``config``.  ``distortion`` (a
+    ``detector.distortion.DistortionMap``; None = off): the drift distortion of the call's track samples, in the drift of
+    ``config``."""
+    from .distortion import configure_distortion
     from .straggling import configure_straggling
 
     ctx = ctx or _abi.default_context()
@@ -100,6 +103,7 @@ def run_batch(call: str, momenta, vertices, proton_numbers, mass_numbers, config
     keys = species_for(proton_numbers, mass_numbers, indices)
     configure_detector(config, keys, ctx)
     configure_straggling(ctx, straggling, config)
+    configure_distortion(ctx, distortion, config)
     known = configure(ctx) if configure else None
     per_event = max(int(capacity_per_event), known or 0)
     layout = build_layout(proton_numbers, mass_numbers, indices, keys)
@@ -114,43 +118,46 @@ def run_batch(call: str, momenta, vertices, proton_numbers, mass_numbers, config
 
 def simulate_batch(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers,
                    config: Config, seed: int, indices: list[int], first_event: int = 0,
-                   ctx: _abi.Context | None = None, capacity_per_event: int = 16384, straggling=None):
+                   ctx: _abi.Context | None = None, capacity_per_event: int = 16384, straggling=None,
+                   distortion=None):
     """simulate() for n events: momenta [n,N,4], vertices [n,3] ->
-    (offsets [n+1], points [P,3], labels [P], stats dict).  ``straggling``: as ``run_batch`` takes it."""
+    (offsets [n+1], points [P,3], labels [P], stats dict).  ``straggling`` and ``distortion``: as ``run_batch`` takes
+    them."""
     arrays, stats = run_batch("attpc_det_run", momenta, vertices, proton_numbers, mass_numbers, config, seed, indices,
-                              first_event, ctx, capacity_per_event, straggling=straggling, holder=RowArrays, width=3,
-                              event_points=False, slack=1024)
+                              first_event, ctx, capacity_per_event, straggling=straggling, distortion=distortion,
+                              holder=RowArrays, width=3, event_points=False, slack=1024)
     return (*arrays.result(), stats.as_dict())
 
 
 def simulate_batch_spyral(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers,
                           config: Config, seed: int, indices: list[int], first_event: int = 0,
                           ctx: _abi.Context | None = None, response: np.ndarray | None = None,
-                          capacity_per_event: int = 8192, straggling=None):
+                          capacity_per_event: int = 8192, straggling=None, distortion=None):
     """simulate() + what SpyralWriter.write does per event (convert_to_spyral, ADC threshold, z-sort; reference
     writer.py:194-238) for n events in one launch sequence, all on the device (``attpc_det_run_spyral``) ->
     (offsets [n+1], rows [P',8], labels [P'], event_points [n] = cloud rows of every event BEFORE the threshold,
-    stats dict).  ``straggling``: as ``run_batch`` takes it."""
+    stats dict).  ``straggling`` and ``distortion``: as ``run_batch`` takes them."""
     arrays, stats = run_batch("attpc_det_run_spyral", momenta, vertices, proton_numbers, mass_numbers, config, seed,
-                              indices, first_event, ctx, capacity_per_event, straggling=straggling,
+                              indices, first_event, ctx, capacity_per_event, straggling=straggling, distortion=distortion,
                               configure=lambda ctx: configure_spyral(config, ctx, response), holder=RowArrays, width=8,
                               slack=1024)
     return (*arrays.result(), arrays.event_points, stats.as_dict())
 
 
 def simulate(momenta: np.ndarray, vertex: np.ndarray, proton_numbers: np.ndarray,
-             mass_numbers: np.ndarray, config: Config, rng: Generator, indices: list[int], straggling=None):
+             mass_numbers: np.ndarray, config: Config, rng: Generator, indices: list[int], straggling=None,
+             distortion=None):
     """One kinematics event -> (points [P,3] = pad, time bucket, electrons; labels [P])
     (reference simulator.py:52-115).  ``rng`` seeds the device Philox streams (one draw).
     Row order is unspecified (the reference's is dict-insertion order); use
     ``np.lexsort((points[:,1], points[:,0]))`` for a canonical order.  ``straggling`` (a
     ``detector.straggling.StragglingSettings``; None = off): multiple scattering and energy-loss straggling of the
-    tracks."""
+    tracks.  ``distortion`` (a ``detector.distortion.DistortionMap``; None = off): the drift distortion."""
     seed = int(rng.integers(0, 1 << 63))
     momenta = np.ascontiguousarray(momenta, dtype=np.float64)[None]
     vertex = np.ascontiguousarray(vertex, dtype=np.float64)[None]
     _, points, labels, _ = simulate_batch(momenta, vertex, proton_numbers, mass_numbers, config,
-                                          seed, list(indices), straggling=straggling)
+                                          seed, list(indices), straggling=straggling, distortion=distortion)
     return points, labels
 
 
@@ -244,7 +251,7 @@ def deliver_events(writer, n_events: int, batch_size: int, batch, emit) -> None:
 def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
                    indices: list[int] | None = None, batch_size: int = 16384,
                    seed: int | None = None, selection=None, trigger=None, gain=None, common_mode=None,
-                   straggling=None):
+                   straggling=None, distortion=None):
     """Apply the detector simulation to every event of a kinematics file (reference
     simulator.py:118-210): the writer is called once per event with a non-empty cloud, in event order, then
     closed.  A writer that offers ``write_rows`` (SpyralWriter) receives its rows ready to store: the response
@@ -264,7 +271,8 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     -- again a writer that receives traces or trace rows; any other raises ValueError.  ``common_mode`` (a
     ``detector.traces.CommonModeSettings``; default: the writer's own, None = off): the common-mode noise of the traces,
     under the same rule.  ``straggling`` (a ``detector.straggling.StragglingSettings``; None = off): multiple scattering
-    and energy-loss straggling of every track, with any writer."""
+    and energy-loss straggling of every track, with any writer.  ``distortion`` (a
+    ``detector.distortion.DistortionMap``; None = off): the drift distortion of every track sample, with any writer."""
     from ..io import KinematicsFileReader
 
     print("------- AT-TPC Simulation Engine (MI355X) -------")
@@ -286,21 +294,23 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
             from .selection import simulate_batch_selected
 
             res = simulate_batch_selected(*args, selection, kind="spyral" if kind == "rows" else "cloud", first_event=start,
-                                          response=getattr(writer, "response", None), straggling=straggling)
+                                          response=getattr(writer, "response", None), straggling=straggling,
+                                          distortion=distortion)
             return selected_events(res, "rows" if kind == "rows" else "points")
         if chain is not None:  # the pad traces, or their peaks as Spyral rows, are made on the device behind the scatter
             packed = kind == "traces" and writer_packed(writer)
             offsets, *arrays, raw_points, stats = chain.run_batch(
                 kind == "trace_rows", momenta, vertices, proton_numbers, mass_numbers, run_seed, nuclei_to_sim, start,
-                packed=packed, straggling=straggling)
+                packed=packed, straggling=straggling, distortion=distortion)
             if packed:  # (pads, row_start, packed, labels) -> the records as one row-indexed array
                 arrays = [arrays[0], PackedRows(arrays[1], arrays[2]), arrays[3]]
             return fired_events(offsets, raw_points, stats.get("trigger"), *arrays)
         if kind == "rows":
             offsets, rows, labels, raw_points, _ = simulate_batch_spyral(
-                *args, first_event=start, response=getattr(writer, "response", None), straggling=straggling)
+                *args, first_event=start, response=getattr(writer, "response", None), straggling=straggling,
+                distortion=distortion)
             return offsets, raw_points, rows, labels
-        offsets, points, labels, _ = simulate_batch(*args, first_event=start, straggling=straggling)
+        offsets, points, labels, _ = simulate_batch(*args, first_event=start, straggling=straggling, distortion=distortion)
         return offsets, None, points, labels
 
     deliver_events(writer, n_events, batch_size, batch, emit)

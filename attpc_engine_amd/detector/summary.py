@@ -84,17 +84,19 @@ def configure_summary(config: Config, ctx: _abi.Context, min_electrons: int | No
 
 def simulate_batch_summary(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
                            seed: int, indices: list[int], first_event: int = 0, ctx: _abi.Context | None = None,
-                           min_electrons: int | None = None, straggling=None):
+                           min_electrons: int | None = None, straggling=None, distortion=None):
     """simulate() for n events with the clouds left on the device and reduced there (``attpc_det_run_summary``) ->
     (events [n] structured, tracks [n, n_sim] structured, stats dict: the cloud's run statistics).  ``straggling`` (a
-    ``detector.straggling.StragglingSettings``; None = off): the track straggling."""
+    ``detector.straggling.StragglingSettings``; None = off): the track straggling.  ``distortion`` (a
+    ``detector.distortion.DistortionMap``; None = off): the drift distortion -- the tracks' end points are then the
+    shifted, apparent ones."""
     from .simulator import run_batch
 
     SummarySettings(min_electrons, config)  # (validated before the first library call)
     arrays, stats = run_batch("attpc_det_run_summary", momenta, vertices, proton_numbers, mass_numbers, config, seed,
                               list(indices), first_event, ctx, 0,
                               configure=lambda c: configure_summary(config, c, min_electrons) and None,
-                              straggling=straggling, holder=SummaryArrays, n_sim=len(indices))
+                              straggling=straggling, distortion=distortion, holder=SummaryArrays, n_sim=len(indices))
     return (*arrays.result(), stats.as_dict())
 
 

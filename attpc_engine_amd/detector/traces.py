@@ -482,11 +482,12 @@ class TraceChain:
 
     def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
                   ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False,
-                  straggling=None):
+                  straggling=None, distortion=None):
         """simulate() + this chain on the device for n events: what ``simulate_batch_trace_rows`` (``rows``) or
         ``simulate_batch_traces`` returns (``capacity_per_event``: None = the default of that entry point; ``packed``:
         the traces as packed records, ``attpc_det_run_traces_packed``; ``straggling``: the track straggling, a
-        ``detector.straggling.StragglingSettings`` or None = off)."""
+        ``detector.straggling.StragglingSettings`` or None = off; ``distortion``: the drift distortion, a
+        ``detector.distortion.DistortionMap`` or None = off)."""
         from .simulator import run_batch
 
         ctx = ctx or _abi.default_context()
@@ -505,7 +506,7 @@ class TraceChain:
         arrays, stats = run_batch("attpc_det_run_trace_rows" if rows else "attpc_det_run_traces_packed" if packed
                                   else "attpc_det_run_traces", momenta, vertices,
                                   proton_numbers, mass_numbers, self.config, seed, indices, first_event, ctx,
-                                  per_event, configure, straggling=straggling, **how)
+                                  per_event, configure, straggling=straggling, distortion=distortion, **how)
         extra = trigger_result(ctx, len(arrays.offsets) - 1)
         if rows:
             from .circle import circle_result
@@ -551,7 +552,7 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
                           noise_sigma: float = 0.0, noise_table=None, pedestals=None, noise_stream: int = 0,
                           readout: str = "hit", readout_pads=None, trigger: TriggerSettings | None = None,
                           gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
-                          packed: bool = False, straggling=None):
+                          packed: bool = False, straggling=None, distortion=None):
     """simulate() + the pad traces of every event, on the device (``attpc_det_run_traces``; the noise keyed on
     ``seed`` and the global event ids; ``readout`` / ``readout_pads`` as configure_traces) ->
     (offsets [n+1], pads [R] i32, samples [R,512] i16, labels [R] i64, event_points [n] = cloud rows of every event
@@ -562,11 +563,12 @@ def simulate_batch_traces(momenta: np.ndarray, vertices: np.ndarray, proton_numb
     common-mode noise of every pad with a group, keyed the same way.  ``packed=True``
     (``attpc_det_run_traces_packed``): (offsets, pads, row_start [R+1] i64, packed uint8, labels, event_points, stats
     with ``n_bytes``) -- the rows as packed records, ``unpack_traces`` gives the samples back.  ``straggling`` (a
-    ``detector.straggling.StragglingSettings``; None = off): multiple scattering and energy-loss straggling of the tracks."""
+    ``detector.straggling.StragglingSettings``; None = off): multiple scattering and energy-loss straggling of the tracks.
+    ``distortion`` (a ``detector.distortion.DistortionMap``; None = off): the drift distortion of the track samples."""
     chain = TraceChain(config, response, threshold, offset, NoiseSettings(noise_sigma, noise_table, pedestals, noise_stream),
                        ReadoutSettings(readout, readout_pads), gain, trigger=trigger, common_mode=common_mode)
     return chain.run_batch(False, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
-                           capacity_per_event, packed, straggling=straggling)
+                           capacity_per_event, packed, straggling=straggling, distortion=distortion)
 
 
 def _host_cloud(offsets, points, labels, seed, first_event):
@@ -1031,7 +1033,7 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
                               estimates=None, thinning=None, straggling=None, circle=None, helix=None,
-                              **trace_kwargs):
+                              distortion=None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -1043,12 +1045,12 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     under ``"thinning"``; with ``circle`` (a ``detector.circle.CircleFitSettings``; None = off) their circles refined by
     the geometric fit, and ``"circle": "geometric"``; with ``helix`` (a ``detector.helix.HelixSlopeSettings``; None =
     off) their slope, vz and B rho from the helix, and ``"slope": "helix"``).
-    ``gain``, ``common_mode`` and ``straggling`` as simulate_batch_traces takes them."""
+    ``gain``, ``common_mode``, ``straggling`` and ``distortion`` as simulate_batch_traces takes them."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
                                                                    thinning=thinning, circle=circle, helix=helix)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
-                           capacity_per_event, straggling=straggling)
+                           capacity_per_event, straggling=straggling, distortion=distortion)
 
 
 def clouds_to_trace_rows(offsets: np.ndarray, points: np.ndarray, labels: np.ndarray, ctx: _abi.Context, seed: int = 0,

@@ -22,6 +22,7 @@ from .detector.circle import CircleFitSettings, circle_result, configure_circle
 from .detector.helix import HelixSlopeSettings, configure_helix, helix_result
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .detector.straggling import StragglingSettings, configure_straggling
+from .detector.distortion import DistortionMap, configure_distortion
 from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -50,6 +51,7 @@ class Engine:
         ctx.check(ctx.lib.attpc_det_configure(ctx.handle, det), "attpc_det_configure")
         ctx.forget("det")  # (what configure_detector last uploaded is no longer what the device holds)
         configure_straggling(ctx, None)  # a new engine starts without the track straggling an earlier one configured
+        configure_distortion(ctx, None)  # ... and without its drift distortion
         self.layout = build_layout(self.z, self.a, self.indices, self.species)
         if chunk_events:
             ctx.check(ctx.lib.attpc_set_chunk_events(ctx.handle, int(chunk_events)), "attpc_set_chunk_events")
@@ -114,6 +116,15 @@ class Engine:
         the global event id, the nucleus and the stream; a radiation length or an electron density left open is that
         of the config's gas target --, neither turns it off (the default)."""
         configure_straggling(self.ctx, _settings(StragglingSettings, settings, parameters), self.config)
+
+    # ---------------------------------------------------------------- drift distortion
+    def configure_distortion(self, distortion=None, **parameters) -> None:
+        """The drift distortion of the track samples (include/attpc_engine.h, "drift distortion"): a
+        ``detector.distortion.DistortionMap`` or its keywords (radial, azimuthal, time, rho_max, length) turn the stage
+        on for every run function of this engine -- every kept sample of every track is moved radially, azimuthally and
+        in time by the map before anything reads it, a pure function of the sample and the map; the map's drift-distance
+        nodes are placed by the config's time-bucket edges --, neither turns it off (the default)."""
+        configure_distortion(self.ctx, _settings(DistortionMap, distortion, parameters), self.config)
 
     # ---------------------------------------------------------------- Spyral rows on the device
     def configure_spyral(self, config=None, response=None) -> None:
@@ -490,7 +501,7 @@ def _settings(cls, given, parameters: dict, what: str = "keywords"):
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
               batch_size: int = 65536, context: _abi.Context | None = None, selection=None, trigger=None,
-              gain=None, common_mode=None, straggling=None) -> None:
+              gain=None, common_mode=None, straggling=None, distortion=None) -> None:
     """run_kinematics_pipeline + run_simulation + SpyralWriter without the kinematics file and with
     the response / threshold / row conversion / z-sort done on the GPU: per event with a non-empty
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
@@ -503,9 +514,12 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     (``Engine.run_selected``; rows or plain clouds), ``trigger``, ``gain`` and ``common_mode``: as ``run_simulation`` takes them, with
     the same rules about the kinds of writer (``detector.simulator.plan_delivery``); event numbers stay the global
     ones, the file roll-over counts written events.  ``straggling`` (a ``detector.straggling.StragglingSettings``; None =
-    off): the track straggling (``Engine.configure_straggling``), with any writer."""
+    off): the track straggling (``Engine.configure_straggling``), with any writer.  ``distortion`` (a
+    ``detector.distortion.DistortionMap``; None = off): the drift distortion (``Engine.configure_distortion``), with any
+    writer."""
     engine = Engine(pipeline, config, indices, context=context)
     engine.configure_straggling(straggling)
+    engine.configure_distortion(distortion)
     seed = pipeline.seed if seed is None else int(seed)
     kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, plain_clouds=False, common_mode=common_mode)
     if selection is not None:

@@ -1569,6 +1569,62 @@ typedef struct {
  * scales 0 the kernels that run are those of the stage off. */
 ATTPC_API int32_t attpc_det_configure_straggling(attpc_ctx* ctx, const attpc_straggle_desc* desc);
 
+/* ---- drift distortion (opt-in: off by default, and with it off every output, kernel and buffer of every entry point
+ * is what it is without this section; the entry points are additions under ABI version 3) ----
+ * The engine's drift field is ideal: an electron made at (x, y, z) lands at (x, y) on the pad plane at time bucket
+ * (length - z) / dv + micromegas_edge.  A real field cage and space charge give E a radial component; with B parallel
+ * to E the drifting electrons are pushed radially and, through E x B, azimuthally, and they arrive at a shifted time.
+ * This stage moves every kept track record (x m, y m, time bucket, electrons x gain) by a map of those three shifts
+ * over (creation radius, ideal drift time), before anything reads the records.  tests/distortion_reference.py restates
+ * this contract in numpy; csrc/distort_host.hpp is its arithmetic, shared by the kernel and the host.
+ *
+ * The map.  Node (i, j) stands for creation radius rho = i * rho_step and ideal drift tau = tb - tb_origin =
+ * j * tau_step.  Every table value is finite, |radial| and |azimuthal| <= 1 m, |time| <= 1024 time buckets: the caps
+ * keep a shifted record inside what the scatter is built to take.
+ *
+ * One record (x, y, tb, q), in f64, every operation rounded once in the written order (no fused multiply-add), + - * /
+ * and sqrt only:
+ *  1. rho = sqrt(x * x + y * y), tau = tb - tb_origin.  A record whose x, y or tb is not finite keeps its bits.
+ *  2. a = rho / rho_step clamped to [0, n_rho - 1] by plain comparisons; i = min((int) floor(a), n_rho - 2),
+ *     fr = a - i.  b = tau / tau_step, clamped to [0, n_tau - 1], gives j and fs the same way.  Outside the grid the
+ *     edge value holds.
+ *  3. for each table T: lo = T[i][j] + fs * (T[i][j+1] - T[i][j]), hi = T[i+1][j] + fs * (T[i+1][j+1] - T[i+1][j]),
+ *     v = lo + fr * (hi - lo): dr, da, dt (a NULL table gives 0).
+ *  4. ux = x / rho, uy = y / rho (rho == 0: both 0 -- no direction, no shift in the plane);
+ *     x' = (x + dr * ux) - da * uy,  y' = (y + dr * uy) + da * ux,  tb' = tb + dt,  q' = q bit for bit.
+ * A record is a pure function of itself and the map: no random draw, no dependence on event id, chunking or shard.
+ *
+ * Who sees it.  Every entry point that integrates tracks: attpc_sim_run* and attpc_det_run* in all their forms (the
+ * batch attpc_sim_hint_next starts early included) and attpc_det_tracks, which returns the shifted records.
+ * attpc_det_scatter takes records as given and does not apply it.  The shift is applied exactly once per track batch,
+ * however often the batch is scattered (chunks, a launch repeated with larger buffers, a call repeated after
+ * ATTPC_E_CAPACITY).  The diffusion widths of a record are those of its shifted arrival time, as for any record, and a
+ * record shifted out of the time buckets 0 .. 511 is dropped by the scatter like any other.  The end point of a track
+ * summary (end_x, end_y, end_tb) and a selection on it are those of the shifted, apparent record; counts, n_steps,
+ * n_track_samples and whether the arena overflowed do not change. */
+typedef struct attpc_distort_desc {
+  double rho_step;          /* m, finite, > 0 */
+  double tau_step;          /* time buckets, finite, > 0 */
+  double tb_origin;         /* the time bucket of drift distance 0 (the config's micromegas_edge), finite */
+  int32_t n_rho, n_tau;     /* 2 .. 256 each */
+  const double* radial;     /* [n_rho][n_tau] m, + = outward;                 NULL = zeros */
+  const double* azimuthal;  /* [n_rho][n_tau] m of arc, + = counter-clockwise; NULL = zeros */
+  const double* time;       /* [n_rho][n_tau] time buckets, + = later;        NULL = zeros */
+} attpc_distort_desc;
+
+/* desc == NULL turns the stage off (the default), and so does a desc whose three tables are all NULL or all zero: no
+ * kernel is launched then.  ATTPC_E_INVALID for anything the section above rules out, a NaN in any field included.
+ * The library copies the tables to the device and owns the copies.  The map is kept on the context, independent of
+ * every other configure call (attpc_det_configure does not drop it); the call drops a track batch queued ahead. */
+ATTPC_API int32_t attpc_det_configure_distortion(attpc_ctx* ctx, const attpc_distort_desc* desc);
+
+/* The stage alone: out[k] = the shifted record of samples[k] ([n][4] each: x, y, tb, q), by the same kernel on the
+ * array presented as chains of arena blocks.  Any n >= 0 (n == 0: nothing is read or written); desc as above and not
+ * NULL (an all-zero map copies the records).  Needs no other configure call and leaves the configured stage as it is.
+ * out may be samples. */
+ATTPC_API int32_t attpc_samples_distort(attpc_ctx* ctx, int64_t n, const double* samples, const attpc_distort_desc* desc,
+                                        double* out);
+
 #ifdef __cplusplus
 }
 #endif
