@@ -332,6 +332,20 @@ class DistortDesc(C.Structure):  # attpc_distort_desc
                 ("radial", _dp), ("azimuthal", _dp), ("time", _dp)]
 
 
+class UndistortDesc(C.Structure):  # attpc_undistort_desc
+    _fields_ = [("map", DistortDesc), ("windows_edge", C.c_int32), ("micromegas_edge", C.c_int32), ("length", C.c_double),
+                ("iterations", C.c_int32), ("tolerance_xy", C.c_double), ("tolerance_tb", C.c_double)]
+
+
+class UndistortInfo(C.Structure):  # attpc_undistort_info
+    _fields_ = [("n_rows", C.c_int64), ("n_skipped", C.c_int64), ("n_unconverged", C.c_int64), ("n_moved", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+assert C.sizeof(UndistortDesc) == 96 and C.sizeof(UndistortInfo) == 32
+
 TRACE_PACK_FORMAT = "for64-bitplane-v1"  # ATTPC_TRACE_PACK_FORMAT
 TRACE_PACK_MAX_ROW_BYTES = 784
 
@@ -427,6 +441,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_circle", "attpc_rows_estimate_circle",
     "attpc_trace_configure_helix", "attpc_rows_estimate_helix",
     "attpc_det_configure_distortion", "attpc_samples_distort",
+    "attpc_trace_configure_correction", "attpc_correction_last", "attpc_rows_undistort",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -477,6 +492,9 @@ HELIX_SYMBOLS = ("attpc_trace_configure_helix", "attpc_rows_estimate_helix")
 
 # ... and the drift distortion after the helix slope: the same rule.
 DISTORT_SYMBOLS = ("attpc_det_configure_distortion", "attpc_samples_distort")
+
+# ... and the drift correction of the trace rows after the drift distortion: the same rule.
+UNDISTORT_SYMBOLS = ("attpc_trace_configure_correction", "attpc_correction_last", "attpc_rows_undistort")
 
 _lib = None
 
@@ -691,6 +709,16 @@ def load_library() -> C.CDLL:
     for name, argtypes in distortion.items():
         if not no_distortion:
             getattr(lib, name).argtypes = argtypes
+    correction = {
+        "attpc_trace_configure_correction": [ctxp, C.POINTER(UndistortDesc)],
+        "attpc_correction_last": [ctxp, C.POINTER(UndistortInfo)],
+        "attpc_rows_undistort": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(UndistortDesc), _dp, i64p, i64p,
+                                 C.POINTER(UndistortInfo)],
+    }
+    no_correction = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in UNDISTORT_SYMBOLS)
+    for name, argtypes in correction.items():
+        if not no_correction:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -718,7 +746,7 @@ def load_library() -> C.CDLL:
                 or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)
                 or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)
                 or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)
-                or (no_distortion and name in DISTORT_SYMBOLS)):
+                or (no_distortion and name in DISTORT_SYMBOLS) or (no_correction and name in UNDISTORT_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -728,7 +756,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction")
 
 
 class Context:
@@ -785,6 +813,13 @@ class Context:
         n_rows, checksum = C.c_int64(), C.c_uint64()
         self.check(self.lib.attpc_trace_rows_last(self.handle, C.byref(n_rows), C.byref(checksum)), "attpc_trace_rows_last")
         return {"n_rows": int(n_rows.value), "row_checksum": int(checksum.value)}
+
+    def correction_last(self) -> dict:
+        """The counts of the drift correction in this context's last trace-row call (``attpc_correction_last``);
+        RuntimeError if the stage was off for it."""
+        info = UndistortInfo()
+        self.check(self.lib.attpc_correction_last(self.handle, C.byref(info)), "attpc_correction_last")
+        return info.as_dict()
 
     def trigger_last(self, n_events: int) -> np.ndarray:
         """The trigger records [n_events] (``TRIGGER_DTYPE``) of this context's last trace or trace-row call

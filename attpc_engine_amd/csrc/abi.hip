@@ -111,6 +111,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf est_records;          // track estimates on (estimate.hip): the chunk's records, attpc_track_estimate [events][n_sim]
   DevBuf thin_points;          // ... of thinned points (thin.hip): one ThinPoint per trace row (pk_cap)
   DevBuf thin_info;            // ... and the attpc_thin_info of every (event, position)
+  DevBuf uc_rows, uc_labels;   // drift correction on (undistort.hip): the chunk's corrected, re-sorted rows and labels (pk_cap)
   Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
   // packed traces (trace_pack.hip): the headers and record sizes of every kept trace row, their scanned byte offsets
   // (tp_block_*: the scan's scratch) and the records; the chunk's bytes in pinned memory (the host waits on `counted`)
@@ -280,6 +281,13 @@ struct attpc_ctx {
   // run maps (maps.hip): one map per control-word slot [MAX_SLOTS][MAPS_CELLS], the chunk in that slot's own, and the
   // totals of the call in progress [MAPS_CELLS]
   DevBuf mp_slots, mp_total;
+  bool correction_on = false;      // attpc_trace_configure_correction
+  UndistortSettings correction{};  // the map's tables on the device
+  DevAllocs correction_allocs;
+  DevBuf uc_xyt;                   // [rows][3] the corrected points of the chunk being corrected (undistort.hip's scratch)
+  DevBuf uc_sums;                  // [4] the counts of the trace-row run in progress
+  bool correction_call = false;    // attpc_correction_last: the stage was on for the last trace-row call, and its counts
+  attpc_undistort_info last_correction{};
   int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
   uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
@@ -1127,8 +1135,9 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   EstimateArgs a{};
   estimate_settings(ctx->estimates, &a);
   a.ev_start = static_cast<const int64_t*>(as.pk_ev_start.p);
-  a.rows = static_cast<const double*>(as.sp_rows.p);  // (may be nullptr: then no event of the chunk has a row)
-  a.labels = static_cast<const int64_t*>(as.sp_labels.p);
+  // (may be nullptr: then no event of the chunk has a row; with the drift correction on its rows and labels)
+  a.rows = static_cast<const double*>(ctx->correction_on ? as.uc_rows.p : as.sp_rows.p);
+  a.labels = static_cast<const int64_t*>(ctx->correction_on ? as.uc_labels.p : as.sp_labels.p);
   a.records = static_cast<attpc_track_estimate*>(as.est_records.p);
   std::memcpy(a.slot_label, ctx->est_slot_label, sizeof a.slot_label);
   a.n_sim = (int32_t)n_sim;
@@ -1162,6 +1171,31 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_estimates.p + first_local * n_sim, as.est_records.p,
                               (size_t)n * n_sim * sizeof(attpc_track_estimate), hipMemcpyDeviceToHost, ctx->stream_c));
+  return ATTPC_OK;
+}
+
+// The drift correction of the chunk in `as` (n events, rows written: directly behind launch_peak_rows, which is done
+// with the sort scratch on the same stream) on S: as.sp_rows / as.sp_labels -> as.uc_rows / as.uc_labels, the rows and
+// labels every later stage and the delivery read.  The counts go to ctx->uc_sums; a chunk is delivered once, so every
+// event counts once.
+int32_t enqueue_correction(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
+  int32_t rc;
+  if ((rc = ensure(ctx, as.uc_rows, as.pk_cap * 8 * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, as.uc_labels, as.pk_cap * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, ctx->uc_xyt, as.pk_cap * 3 * sizeof(double)))) return rc;
+  UndistortArgs a{};
+  a.s = ctx->correction;
+  a.ev_start = static_cast<const int64_t*>(as.pk_ev_start.p);
+  a.rows = static_cast<const double*>(as.sp_rows.p);
+  a.labels = static_cast<const int64_t*>(as.sp_labels.p);
+  a.xyt = static_cast<double*>(ctx->uc_xyt.p);
+  a.sort_idx = static_cast<uint32_t*>(ctx->sort_idx.p);
+  a.sort_key = static_cast<double*>(ctx->sort_key.p);
+  a.out_rows = static_cast<double*>(as.uc_rows.p);
+  a.out_labels = static_cast<int64_t*>(as.uc_labels.p);
+  a.counts = static_cast<unsigned long long*>(ctx->uc_sums.p);
+  launch_undistort(ctx->stream, n, a);
+  HIP_TRY(ctx, hipGetLastError());
   return ATTPC_OK;
 }
 
@@ -1608,15 +1642,18 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
                      static_cast<double*>(ctx->sort_key.p), static_cast<double*>(as.sp_rows.p),
                      static_cast<int64_t*>(as.sp_labels.p), static_cast<unsigned long long*>(ctx->peak_sums.p));
     HIP_TRY(ctx, hipGetLastError());
+    if (ctx->correction_on && (rc = enqueue_correction(ctx, as, n))) return rc;
   }
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
   if (total > 0 && fits) {
+    const void* d_rows = ctx->correction_on ? as.uc_rows.p : as.sp_rows.p;
+    const void* d_labels = ctx->correction_on ? as.uc_labels.p : as.sp_labels.p;
     if (o.cloud->points)
-      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->points + base * 8, as.sp_rows.p, (size_t)total * 8 * sizeof(double), hipMemcpyDeviceToHost,
+      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->points + base * 8, d_rows, (size_t)total * 8 * sizeof(double), hipMemcpyDeviceToHost,
                                   ctx->stream_c));
     if (o.cloud->labels)
-      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->labels + base, as.sp_labels.p, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost,
+      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->labels + base, d_labels, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost,
                                   ctx->stream_c));
   }
   if (ctx->est_call_events >= 0 && (rc = enqueue_estimates(ctx, as, n, first_local))) return rc;
@@ -2065,6 +2102,10 @@ int32_t reset_trace_sums(attpc_ctx* ctx, OutMode mode) {
   if (mode != OutMode::trace_rows) return ATTPC_OK;
   if ((rc = ensure(ctx, ctx->peak_sums, sizeof(unsigned long long)))) return rc;
   HIP_TRY(ctx, hipMemsetAsync(ctx->peak_sums.p, 0, sizeof(unsigned long long), ctx->stream));
+  ctx->correction_call = false;
+  if (!ctx->correction_on) return ATTPC_OK;
+  if ((rc = ensure(ctx, ctx->uc_sums, 4 * sizeof(unsigned long long)))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->uc_sums.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
   return ATTPC_OK;
 }
 
@@ -2075,6 +2116,13 @@ int32_t read_peak_sums(attpc_ctx* ctx, const RunOut& o) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->last_rows = o.rows;
   ctx->last_row_checksum = sum;
+  if (ctx->correction_on) {  // the counts of the drift correction, read like the checksum: once, when the call has ended
+    unsigned long long counts[4] = {0ull, 0ull, 0ull, 0ull};
+    HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->uc_sums.p, sizeof counts, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->last_correction = attpc_undistort_info{(int64_t)counts[0], (int64_t)counts[1], (int64_t)counts[2], (int64_t)counts[3]};
+    ctx->correction_call = true;
+  }
   return ATTPC_OK;
 }
 
@@ -2758,6 +2806,91 @@ int32_t attpc_samples_distort(attpc_ctx* ctx, int64_t n, const double* samples, 
   return ATTPC_OK;
 }
 
+// ---- drift correction (undistort.hip, undistort_host.hpp; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_correction(attpc_ctx* ctx, const attpc_undistort_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* wrong = undistort_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "attpc_trace_configure_correction: %s", wrong);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }  // nothing in flight may read the old tables
+  ctx->correction_on = false;
+  ctx->correction = UndistortSettings{};
+  ctx->correction_allocs.clear();
+  if (!d || distort_desc_is_off(d->map)) return ATTPC_OK;
+  DistortMap map{};
+  const int32_t rc = upload_distort_map(ctx, ctx->correction_allocs, d->map, &map);
+  if (rc) {
+    ctx->correction_allocs.clear();
+    return rc;
+  }
+  ctx->correction = undistort_settings(*d, map);
+  ctx->correction_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_correction_last(attpc_ctx* ctx, attpc_undistort_info* info) {
+  if (!ctx || !info) return ATTPC_E_INVALID;
+  if (!ctx->correction_call)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_correction_last: the drift correction was off for the last trace-row call");
+  *info = ctx->last_correction;
+  return ATTPC_OK;
+}
+
+int32_t attpc_rows_undistort(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                             const attpc_undistort_desc* d, double* out_rows, int64_t* out_labels, int64_t* order,
+                             attpc_undistort_info* info) {
+  if (!ctx || !d || !info || n_events < 0) return ATTPC_E_INVALID;
+  if (const char* wrong = undistort_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "attpc_rows_undistort: %s", wrong);
+  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
+  if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !out_rows)) return ATTPC_E_INVALID;
+  if ((labels == nullptr) != (out_labels == nullptr)) return ATTPC_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  *info = attpc_undistort_info{};
+  if (n_events == 0) return ATTPC_OK;
+  DevAllocs tables;  // this call's own copy of the map, freed when it returns
+  DistortMap map{};
+  if ((rc = upload_distort_map(ctx, tables, d->map, &map))) return rc;
+  UndistortArgs a{};
+  a.s = undistort_settings(*d, map);
+  unsigned long long* d_counts = stage<unsigned long long>(ctx, 6, 4, rc);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  a.counts = d_counts;
+  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
+  std::vector<int64_t> start;
+  for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
+    e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
+    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
+    if (!n_rows) continue;  // (empty events: nothing to count)
+    chunk_starts(offsets, e0, e1, &start);
+    a.ev_start = stage_in(ctx, 2, start.data(), m + 1, rc);
+    a.rows = stage_in(ctx, 0, rows + offsets[e0] * 8, n_rows * 8, rc);
+    a.labels = labels ? stage_in(ctx, 1, labels + offsets[e0], n_rows, rc) : nullptr;
+    a.out_rows = stage<double>(ctx, 3, cap * 8, rc);
+    a.out_labels = labels ? stage<int64_t>(ctx, 4, cap, rc) : nullptr;
+    a.order = order ? stage<int64_t>(ctx, 5, cap, rc) : nullptr;
+    a.order_base = offsets[e0];
+    if (!rc) rc = ensure(ctx, ctx->uc_xyt, cap * 3 * sizeof(double));
+    if (!rc) rc = ensure(ctx, ctx->sort_idx, cap * sizeof(uint32_t));
+    if (!rc) rc = ensure(ctx, ctx->sort_key, cap * sizeof(double));
+    if (rc) return rc;
+    a.xyt = static_cast<double*>(ctx->uc_xyt.p);
+    a.sort_idx = static_cast<uint32_t*>(ctx->sort_idx.p);
+    a.sort_key = static_cast<double*>(ctx->sort_key.p);
+    launch_undistort(ctx->stream, (uint32_t)m, a);
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = stage_out(ctx, out_rows + offsets[e0] * 8, a.out_rows, n_rows * 8))) return rc;
+    if (labels && (rc = stage_out(ctx, out_labels + offsets[e0], a.out_labels, n_rows))) return rc;
+    if (order && (rc = stage_out(ctx, order + offsets[e0], a.order, n_rows))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (before the staging is filled again)
+  }
+  unsigned long long counts[4] = {0ull, 0ull, 0ull, 0ull};
+  HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (before `tables` and the host vector go)
+  *info = attpc_undistort_info{(int64_t)counts[0], (int64_t)counts[1], (int64_t)counts[2], (int64_t)counts[3]};
+  return ATTPC_OK;
+}
 
 int32_t attpc_det_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t n_events,
                       const attpc_event_layout* layout, const double* p4, const double* vertex,

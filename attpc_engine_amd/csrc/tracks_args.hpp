@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "distort_host.hpp"
+#include "undistort_host.hpp"
 #include "unpack_host.hpp"
 
 namespace attpc {
@@ -299,6 +300,25 @@ struct ThinArgs {
 };
 // one workgroup per event, empty events included (n_events > 0, n_sim > 0)
 void launch_thin(hipStream_t s, uint32_t n_events, const ThinArgs& a);
+
+// drift correction of trace rows (undistort.hip; attpc_trace_configure_correction, the contract is in
+// include/attpc_engine.h)
+struct UndistortArgs {
+  UndistortSettings s;              // the map's tables on the device
+  const int64_t* ev_start;          // [n_events + 1] CSR offsets of the events' rows
+  const double* rows;               // [rows][8]
+  const int64_t* labels;            // [rows] or nullptr
+  double* xyt;                      // [rows][3] scratch: the corrected x, y (m) and t of every row (t NaN: skipped)
+  uint32_t* sort_idx;               // [rows] and
+  double* sort_key;                 // [rows]: the sort's scratch
+  double* out_rows;                 // [rows][8]
+  int64_t* out_labels;              // [rows] or nullptr
+  int64_t* order;                   // [rows] or nullptr: order_base + the input row of every output row
+  int64_t order_base;
+  unsigned long long* counts;       // [4] += n_rows, n_skipped, n_unconverged, n_moved
+};
+// one workgroup per event, empty events included (n_events > 0)
+void launch_undistort(hipStream_t s, uint32_t n_events, const UndistortArgs& a);
 
 // packed pad traces (trace_pack.hip; the format "for64-bitplane-v1" is in include/attpc_engine.h).  samples
 // [n_rows][512] as the trace write pass left them, n_rows > 0; `workgroups` = trace_pack_workgroups(n_rows, limit).

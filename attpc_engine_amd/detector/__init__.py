@@ -1,5 +1,6 @@
 """Detector effects: same public names as the reference package (reference
 ``detector/__init__.py:13-21``) plus the batch entry points, device backed."""
+from . import correction as _correction
 from . import distortion as _distortion
 from . import maps as _maps
 from . import parameters as _parameters
@@ -25,6 +26,7 @@ _EXPORTS = {
     _maps: ("MapsSettings", "RunMaps", "configure_maps", "simulate_batch_maps", "clouds_to_maps"),
     _straggling: ("StragglingSettings", "configure_straggling", "radiation_length", "electron_density"),
     _distortion: ("DistortionMap", "configure_distortion", "samples_to_distortion"),
+    _correction: ("CorrectionSettings", "configure_correction", "rows_to_correction"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

@@ -185,14 +185,15 @@ def writer_packed(writer) -> bool:
 
 
 def plan_delivery(writer, config: Config, selection=None, trigger=None, gain=None, plain_clouds: bool = True,
-                  common_mode=None):
+                  common_mode=None, correction=None):
     """What run_simulation and run_fused may be asked for with ``writer`` -> (kind, emit, chain): ``delivery_of`` and,
     for a writer of traces or trace rows, the ``detector.traces.TraceChain`` to run (else None): ``writer.chain`` -- a
     writer without one: the TraceChain fields it has as attributes (``noise`` and ``readout`` as settings objects), the
     rest at their defaults -- on the run's ``config`` (it fills in a response or threshold the writer left unset), with
     ``trigger``, gated for trace rows, and ``gain`` and ``common_mode`` if given, else the writer's.  ValueError for a
     ``selection`` with a trace writer and for a ``trigger``, a ``gain`` or a ``common_mode`` with any other;
-    AttributeError for plain clouds without a selection unless ``plain_clouds``."""
+    ``correction`` (the drift correction, a ``detector.correction.CorrectionSettings``; else the writer's) goes with
+    trace rows only, ValueError with any other writer.  AttributeError for plain clouds without a selection unless ``plain_clouds``."""
     kind, emit = delivery_of(writer, config)
     traces = kind in ("traces", "trace_rows")
     if selection is not None and traces:
@@ -203,16 +204,19 @@ def plan_delivery(writer, config: Config, selection=None, trigger=None, gain=Non
         raise ValueError("a gain acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
     if common_mode is not None and not traces:
         raise ValueError("common-mode noise acts on traces or trace rows: writers of Spyral rows or clouds are not supported")
+    if correction is not None and kind != "trace_rows":
+        raise ValueError("the drift correction acts on trace rows: only a SpyralWriter with peaks= is supported")
     if kind == "cloud" and selection is None and not plain_clouds:
         raise AttributeError("run_fused needs a writer that offers write_rows or write_traces")
     if not traces:
         return kind, emit, None
-    names = ("response", "threshold", "offset", "noise", "readout", "gain", "peaks", "baseline", "common_mode")
+    names = ("response", "threshold", "offset", "noise", "readout", "gain", "peaks", "baseline", "common_mode", "correction")
     chain = getattr(writer, "chain", None) or TraceChain(config, **{n: getattr(writer, n) for n in names if hasattr(writer, n)})
     if trigger is not None and kind == "trace_rows":
         trigger = trigger.gated()
     return kind, emit, chain.replace(config=config, trigger=trigger, gain=chain.gain if gain is None else gain,
-                                     common_mode=chain.common_mode if common_mode is None else common_mode)
+                                     common_mode=chain.common_mode if common_mode is None else common_mode,
+                                     correction=chain.correction if correction is None else correction)
 
 
 def selected_events(res: dict, key: str):
@@ -251,7 +255,7 @@ def deliver_events(writer, n_events: int, batch_size: int, batch, emit) -> None:
 def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
                    indices: list[int] | None = None, batch_size: int = 16384,
                    seed: int | None = None, selection=None, trigger=None, gain=None, common_mode=None,
-                   straggling=None, distortion=None):
+                   straggling=None, distortion=None, correction=None):
     """Apply the detector simulation to every event of a kinematics file (reference
     simulator.py:118-210): the writer is called once per event with a non-empty cloud, in event order, then
     closed.  A writer that offers ``write_rows`` (SpyralWriter) receives its rows ready to store: the response
@@ -272,7 +276,9 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     ``detector.traces.CommonModeSettings``; default: the writer's own, None = off): the common-mode noise of the traces,
     under the same rule.  ``straggling`` (a ``detector.straggling.StragglingSettings``; None = off): multiple scattering
     and energy-loss straggling of every track, with any writer.  ``distortion`` (a
-    ``detector.distortion.DistortionMap``; None = off): the drift distortion of every track sample, with any writer."""
+    ``detector.distortion.DistortionMap``; None = off): the drift distortion of every track sample, with any writer.
+    ``correction`` (a ``detector.correction.CorrectionSettings``; default: the writer's own, None = off): the drift
+    correction of the trace rows -- a SpyralWriter with ``peaks``; any other raises ValueError."""
     from ..io import KinematicsFileReader
 
     print("------- AT-TPC Simulation Engine (MI355X) -------")
@@ -285,7 +291,7 @@ def run_simulation(config: Config, input_path: Path, writer: SimulationWriter,
     print(f"Output will be written to {writer.get_directory_name()}.")
     rng = default_rng(seed)
     run_seed = int(rng.integers(0, 1 << 63))
-    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, common_mode=common_mode)
+    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, common_mode=common_mode, correction=correction)
 
     def batch(start, stop):
         vertices, momenta = reader.read(start, stop)

@@ -244,6 +244,12 @@ def _checked_helix(helix):
     return _checked(helix)
 
 
+def _checked_correction(correction):
+    from .correction import _checked
+
+    return _checked(correction)
+
+
 def _checked_common_mode(common_mode):
     if common_mode is not None and not isinstance(common_mode, CommonModeSettings):
         raise TypeError("common_mode must be a CommonModeSettings or None")
@@ -402,12 +408,13 @@ class TraceChain:
     ``gain``, ``peaks`` (trace rows; None = ``PeakSettings()``), ``baseline``, ``trigger``, ``common_mode``,
     ``estimates`` (trace rows: a ``detector.estimate.EstimateSettings``), ``thinning`` (the rows in front of the
     estimates: a ``detector.thinning.ThinSettings``), ``circle`` (the geometric circle fit behind them: a
-    ``detector.circle.CircleFitSettings``) and ``helix`` (the helix slope behind the circle: a
-    ``detector.helix.HelixSlopeSettings``)."""
+    ``detector.circle.CircleFitSettings``), ``helix`` (the helix slope behind the circle: a
+    ``detector.helix.HelixSlopeSettings``) and ``correction`` (trace rows: the drift correction of the rows, in front
+    of the thinning, the estimates and the delivery: a ``detector.correction.CorrectionSettings``)."""
 
     def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
                  gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
-                 thinning=None, circle=None, helix=None):
+                 thinning=None, circle=None, helix=None, correction=None):
         self.config, self._given = config, (response, threshold)
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
@@ -416,6 +423,7 @@ class TraceChain:
         self.estimates, self.thinning = _checked_estimates(estimates), _checked_thinning(thinning)
         self.circle = _checked_circle(circle)
         self.helix = _checked_helix(helix)
+        self.correction = _checked_correction(correction)
 
     @classmethod
     def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
@@ -431,10 +439,10 @@ class TraceChain:
 
     def replace(self, **fields) -> "TraceChain":
         """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning,
-        circle, helix; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix"}
+        circle, helix, correction; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction"}
         if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle and helix, not {sorted(unknown)}")
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix and correction, not {sorted(unknown)}")
         chain = copy.copy(self)
         vars(chain).update(fields)
         if "config" in fields:
@@ -445,14 +453,15 @@ class TraceChain:
         _checked_thinning(chain.thinning)
         _checked_circle(chain.circle)
         _checked_helix(chain.helix)
+        _checked_correction(chain.correction)
         return chain
 
     def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
         """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
         trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
-        baseline; trigger; gain; with ``rows`` the track estimates, the thinning in front of them, the circle fit behind them and the helix slope behind that.  A stage that is
+        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them and the helix slope behind that.  A stage that is
         off is turned off, whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode"
-        and "estimates" (the thinning, the circle fit and the helix slope with them) that ``keep`` names, which stay as the ctx holds them."""
+        "estimates" (the thinning, the circle fit and the helix slope with them) and "correction" that ``keep`` names, which stay as the ctx holds them."""
         from .simulator import configure_spyral
 
         ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
@@ -469,6 +478,10 @@ class TraceChain:
             configure_trigger(ctx, self.trigger)
         if "gain" not in keep:
             configure_gain(ctx, self.gain)
+        if rows and "correction" not in keep:
+            from .correction import configure_correction
+
+            configure_correction(ctx, self.correction, self.config)
         if rows and "estimates" not in keep:
             from .circle import configure_circle
             from .estimate import configure_estimates
@@ -518,6 +531,9 @@ class TraceChain:
             extra.update(thinning_result(ctx))
             extra.update(circle_result(ctx))
             extra.update(helix_result(ctx))
+            from .correction import correction_result
+
+            extra.update(correction_result(ctx))
         sums = ctx.trace_rows_last() if rows else arrays.sums()
         return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
 
@@ -1001,18 +1017,23 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
                          baseline: BaselineSettings | None = None, gain: GainSettings | None = None,
                          common_mode: CommonModeSettings | None = None, thinning=None, circle=None, helix=None,
-                         **trace_kwargs) -> None:
+                         correction=None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
     the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
     baseline (default None: off, the peaks stand on the configured pedestals), the micromegas gain and the common-mode
     noise (default None: off).  The trigger, the track estimates, the thinning, the circle fit and the helix slope stay
     as the ctx holds them; a ``thinning`` (a ``detector.thinning.ThinSettings``), a ``circle`` (a
     ``detector.circle.CircleFitSettings``) or a ``helix`` (a ``detector.helix.HelixSlopeSettings``) is configured, None
-    leaves what the ctx holds."""
+    leaves what the ctx holds; so does ``correction`` (the drift correction of the rows, a
+    ``detector.correction.CorrectionSettings``)."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
                                                                    common_mode=common_mode, thinning=thinning, circle=circle,
-                                                                   helix=helix)
-    chain.configure(ctx, rows=True, keep=("trigger", "estimates"))
+                                                                   helix=helix, correction=correction)
+    chain.configure(ctx, rows=True, keep=("trigger", "estimates", "correction"))
+    if correction is not None:
+        from .correction import configure_correction
+
+        configure_correction(ctx, chain.correction, config)
     if thinning is not None:
         from .thinning import configure_thinning
 
@@ -1033,7 +1054,7 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
                               estimates=None, thinning=None, straggling=None, circle=None, helix=None,
-                              distortion=None, **trace_kwargs):
+                              distortion=None, correction=None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -1045,10 +1066,14 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     under ``"thinning"``; with ``circle`` (a ``detector.circle.CircleFitSettings``; None = off) their circles refined by
     the geometric fit, and ``"circle": "geometric"``; with ``helix`` (a ``detector.helix.HelixSlopeSettings``; None =
     off) their slope, vz and B rho from the helix, and ``"slope": "helix"``).
-    ``gain``, ``common_mode``, ``straggling`` and ``distortion`` as simulate_batch_traces takes them."""
+    ``gain``, ``common_mode``, ``straggling`` and ``distortion`` as simulate_batch_traces takes them.  With
+    ``correction`` (a ``detector.correction.CorrectionSettings``; None = off) the rows and labels are the drift-corrected
+    ones, per event in ascending corrected z, the estimates are made of them, and the stage's counts come under
+    ``"correction"``."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
-                                                                   thinning=thinning, circle=circle, helix=helix)
+                                                                   thinning=thinning, circle=circle, helix=helix,
+                                                                   correction=correction)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event, straggling=straggling, distortion=distortion)
 

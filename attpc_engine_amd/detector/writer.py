@@ -153,7 +153,7 @@ class SpyralWriter(_RollingWriter):
 
     def __init__(self, directory_path: Path, config: Config, max_events_per_file: int = 5_000,
                  first_run_number: int = 0, npz_fallback: bool = True, *, peaks=None, baseline=None,
-                 noise_seed: int = 0, gain=None, common_mode=None, **trace_kwargs):
+                 noise_seed: int = 0, gain=None, common_mode=None, correction=None, **trace_kwargs):
         """``peaks`` (keyword only; a ``detector.traces.PeakSettings``, default None = the reference's writer: one row
         per cloud point): the rows are the peaks of the event's digitised pad traces instead (EXTENSION, trace rows of
         include/attpc_engine.h), made on the device with the trace settings ``trace_kwargs`` (response, threshold,
@@ -163,17 +163,21 @@ class SpyralWriter(_RollingWriter):
         configured pedestals): Spyral's Fourier baseline is removed from the traces first.  ``gain`` (a
         ``detector.traces.GainSettings``, default None = off): the micromegas gain of the traces, keyed like the noise.
         ``common_mode`` (a ``detector.traces.CommonModeSettings``, default None = off): the common-mode noise of the
-        traces, keyed the same way.  The files have the same datasets either way."""
+        traces, keyed the same way.  ``correction`` (a ``detector.correction.CorrectionSettings``, default None = off):
+        the drift correction of the rows, which are then stored corrected and in ascending corrected z.  The files have
+        the same datasets either way."""
         self.response = get_response(config).copy()
         self.peaks, self.baseline, self.gain, self.chain = peaks, baseline, gain, None
-        self.common_mode = common_mode
-        if peaks is None and (trace_kwargs or noise_seed or baseline is not None or gain is not None or common_mode is not None):
+        self.common_mode, self.correction = common_mode, correction
+        if peaks is None and (trace_kwargs or noise_seed or baseline is not None or gain is not None or common_mode is not None
+                              or correction is not None):
             given = (sorted(trace_kwargs) + (["noise_seed"] if noise_seed else []) + (["baseline"] if baseline is not None else [])
-                     + (["gain"] if gain is not None else []) + (["common_mode"] if common_mode is not None else []))
+                     + (["gain"] if gain is not None else []) + (["common_mode"] if common_mode is not None else [])
+                     + (["correction"] if correction is not None else []))
             raise TypeError(f"SpyralWriter takes trace settings only with peaks=: {given}")
         if peaks is not None:  # (the chain of a trace-row run; ``write`` uses it too)
             self.chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
-                                                                                common_mode=common_mode)
+                                                                                common_mode=common_mode, correction=correction)
             self.noise_seed = _abi.check_id_range(noise_seed, 0, 0)[0]
         self._trace_kwargs = dict(trace_kwargs)
         super().__init__(directory_path, max_events_per_file, first_run_number, npz_fallback)

@@ -23,6 +23,7 @@ from .detector.helix import HelixSlopeSettings, configure_helix, helix_result
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .detector.straggling import StragglingSettings, configure_straggling
 from .detector.distortion import DistortionMap, configure_distortion
+from .detector.correction import CorrectionSettings, configure_correction, correction_result
 from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -125,6 +126,16 @@ class Engine:
         in time by the map before anything reads it, a pure function of the sample and the map; the map's drift-distance
         nodes are placed by the config's time-bucket edges --, neither turns it off (the default)."""
         configure_distortion(self.ctx, _settings(DistortionMap, distortion, parameters), self.config)
+
+    # ---------------------------------------------------------------- drift correction of the trace rows
+    def configure_correction(self, correction=None, **parameters) -> None:
+        """The drift correction of the trace rows (include/attpc_engine.h, "drift correction"): a
+        ``detector.correction.CorrectionSettings`` or its keywords (map, iterations, tolerance_xy, tolerance_tb) turn
+        the stage on -- every row of ``run_trace_rows`` / ``run_estimates`` is taken back through the map on the device
+        and every event's rows are sorted again by their corrected time, before the thinning, the estimates and the
+        delivery read them; the counts come back under ``correction`` --, neither turns it off (the default).  The map
+        need not be the one of ``configure_distortion``."""
+        configure_correction(self.ctx, _settings(CorrectionSettings, correction, parameters), self.config)
 
     # ---------------------------------------------------------------- Spyral rows on the device
     def configure_spyral(self, config=None, response=None) -> None:
@@ -295,7 +306,9 @@ class Engine:
         of the thinned points, and its z step under ``thinning``; with the geometric circle fit configured as well
         (``configure_circle_fit``) their circles are the refined ones, and ``circle`` is "geometric"; with the helix
         slope configured (``configure_helix_slope``) their slope, vz and B rho come from the turning angle about the
-        circle's centre, and ``slope`` is "helix"."""
+        circle's centre, and ``slope`` is "helix"; with the drift correction configured (``configure_correction``) the
+        rows, labels and estimates are those of the corrected rows, and ``correction`` holds its counts (n_rows,
+        n_skipped, n_unconverged, n_moved)."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         self._trace_rows_defaults()
         ctx = self.ctx
@@ -305,13 +318,13 @@ class Engine:
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                     **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
-                    **helix_result(ctx)}
+                    **helix_result(ctx), **correction_result(ctx)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                 **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
-                    **helix_result(ctx)}
+                    **helix_result(ctx), **correction_result(ctx)}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -367,7 +380,7 @@ class Engine:
         return {"estimates": ctx.estimates_last(n_events, len(self.indices)), "indices": list(self.indices),
                 "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
                 "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx),
-                **circle_result(ctx), **helix_result(ctx)}
+                **circle_result(ctx), **helix_result(ctx), **correction_result(ctx)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run
@@ -501,7 +514,7 @@ def _settings(cls, given, parameters: dict, what: str = "keywords"):
 
 def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None = None, seed: int | None = None,
               batch_size: int = 65536, context: _abi.Context | None = None, selection=None, trigger=None,
-              gain=None, common_mode=None, straggling=None, distortion=None) -> None:
+              gain=None, common_mode=None, straggling=None, distortion=None, correction=None) -> None:
     """run_kinematics_pipeline + run_simulation + SpyralWriter without the kinematics file and with
     the response / threshold / row conversion / z-sort done on the GPU: per event with a non-empty
     cloud (before the threshold, as simulator.py:204-205 decides it -- an event whose rows all fall
@@ -516,12 +529,14 @@ def run_fused(pipeline, config, writer, n_events: int, indices: list[int] | None
     ones, the file roll-over counts written events.  ``straggling`` (a ``detector.straggling.StragglingSettings``; None =
     off): the track straggling (``Engine.configure_straggling``), with any writer.  ``distortion`` (a
     ``detector.distortion.DistortionMap``; None = off): the drift distortion (``Engine.configure_distortion``), with any
-    writer."""
+    writer.  ``correction`` (a ``detector.correction.CorrectionSettings``; default: the writer's own, None = off): the
+    drift correction of the trace rows, with a SpyralWriter with ``peaks``."""
     engine = Engine(pipeline, config, indices, context=context)
     engine.configure_straggling(straggling)
     engine.configure_distortion(distortion)
     seed = pipeline.seed if seed is None else int(seed)
-    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, plain_clouds=False, common_mode=common_mode)
+    kind, emit, chain = plan_delivery(writer, config, selection, trigger, gain, plain_clouds=False, common_mode=common_mode,
+                                      correction=correction)
     if selection is not None:
         engine.configure_selection(selection)
         if kind == "rows":

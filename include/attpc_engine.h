@@ -1625,6 +1625,75 @@ ATTPC_API int32_t attpc_det_configure_distortion(attpc_ctx* ctx, const attpc_dis
 ATTPC_API int32_t attpc_samples_distort(attpc_ctx* ctx, int64_t n, const double* samples, const attpc_distort_desc* desc,
                                         double* out);
 
+/* ---- drift correction (opt-in: off by default, and with it off every output, kernel and buffer of every entry point
+ * is what it is without this section; the entry points are additions under ABI version 3) ----
+ * The way back from the drift distortion, on the trace rows: every row of a chunk is taken from its apparent place
+ * (x, y, time) to where its electrons were made, by fixed-point iteration on the forward map of the section above, and
+ * the rows of every event are sorted again, because a map with a time table changes z and with it the order that the
+ * thinning and the estimates rely on.  The stage sits between the kernel that writes a chunk's trace rows and everything
+ * that reads them: thinning, estimates, delivery.  tests/undistort_reference.py restates this contract in numpy;
+ * csrc/undistort_host.hpp is the arithmetic of one row, shared by the kernel and the host.
+ *
+ * Settings (attpc_undistort_desc): map, an attpc_distort_desc under the rules of attpc_det_configure_distortion -- the
+ * caller's correction map, which need not be the map the tracks were distorted with; windows_edge > micromegas_edge;
+ * length in m, finite and > 0; iterations in 1 .. 64; tolerance_xy in m and tolerance_tb in time buckets, each finite
+ * and >= 0.
+ *
+ * One row (8 doubles), in f64, every operation rounded once in the written order (no fused multiply-add), + - * / and
+ * sqrt only:
+ *  1. Observed point: sx = row[0] / 1000.0, sy = row[1] / 1000.0, st = row[6] (the centroid in time buckets, which is
+ *     exact; the time is not taken back from z).
+ *  2. A row whose row[0], row[1] or row[6] is not finite keeps all its bits and is SKIPPED (n_skipped).
+ *  3. Estimate (x, y, t) = (sx, sy, st).  `iterations` times: (fx, fy, ft) = the shifted record of (x, y, t) by the map
+ *     (steps 1 .. 4 of "drift distortion"); dx = fx - sx, dy = fy - sy, dt = ft - st; x = x - dx, y = y - dy,
+ *     t = t - dt.
+ *  4. The row is UNCONVERGED iff on the last repetition |dx| > tolerance_xy or |dy| > tolerance_xy or
+ *     |dt| > tolerance_tb.  (The estimate cannot run away: x - dx is sx minus a shift, and a shift is at most 1 m.)
+ *  5. Output row: [0] = x * 1000.0, [1] = y * 1000.0, [2] = ((windows_edge - t) / (windows_edge - micromegas_edge))
+ *     * length * 1000.0 with the division correctly rounded -- the expression of the trace rows' own z, so that a map
+ *     that shifts nothing gives z back bit for bit.  Columns 3 .. 7 keep their bits; column 6 stays the observed time.
+ *  6. Order: within an event the output rows stand in descending corrected t (ascending corrected z), equal t in input
+ *     order (stable), the skipped rows behind every corrected row in input order.  Labels move with their rows, the
+ *     offsets do not change.  n_moved counts the rows whose position changed.
+ * Rows and counts are pure functions of the input rows and the settings: no random draw, no dependence on event id,
+ * chunking or shard. */
+typedef struct attpc_undistort_desc {
+  attpc_distort_desc map;
+  int32_t windows_edge;
+  int32_t micromegas_edge;  /* < windows_edge */
+  double length;            /* m, finite, > 0 */
+  int32_t iterations;       /* 1 .. 64 (four bytes of padding follow) */
+  double tolerance_xy;      /* m, finite, >= 0 */
+  double tolerance_tb;      /* time buckets, finite, >= 0 */
+} attpc_undistort_desc;
+
+typedef struct attpc_undistort_info {
+  int64_t n_rows;         /* rows seen, skipped ones included */
+  int64_t n_skipped;
+  int64_t n_unconverged;
+  int64_t n_moved;
+} attpc_undistort_info;  /* 32 bytes */
+
+/* desc == NULL turns the stage off (the default), and so does a desc whose map shifts nothing: no kernel is launched
+ * and no buffer is held then.  ATTPC_E_INVALID for anything the section above rules out, a NaN in any field included.
+ * The library copies the tables to the device and owns the copies.  Independent of every other configure call.  With
+ * the stage on attpc_sim_run_trace_rows, attpc_det_run_trace_rows and attpc_trace_rows_at deliver the corrected,
+ * re-sorted rows and labels, and the thinning and the estimates read them; offsets, event_points and the row checksum
+ * (whose terms are event, pad and sample) do not change.  It costs a second row and label buffer per chunk set, 72
+ * bytes of device memory per row. */
+ATTPC_API int32_t attpc_trace_configure_correction(attpc_ctx* ctx, const attpc_undistort_desc* desc);
+/* The counts of the context's last trace-row call, every event counted exactly once however the call was chunked;
+ * ATTPC_E_NOTCONFIGURED if the stage was off for it (or there was none). */
+ATTPC_API int32_t attpc_correction_last(attpc_ctx* ctx, attpc_undistort_info* info);
+/* The stage alone on any host rows in CSR form, through the same kernel: offsets [n_events + 1], rows [R][8], labels
+ * [R] or NULL -> out_rows [R][8], out_labels [R] (NULL with labels NULL), order [R] or NULL (order[k] = the input row
+ * of output row k; all five arrays are indexed by the row numbers of offsets) and *info.  desc not NULL; a map that shifts nothing runs like any other
+ * (the rows come back bit for bit, sorted by column 6).  Needs no other configure call and leaves the configured stage
+ * as it is.  Rows of attpc_*_run_spyral are valid input as well.  An event holds fewer than 2^31 rows. */
+ATTPC_API int32_t attpc_rows_undistort(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                       const int64_t* labels, const attpc_undistort_desc* desc, double* out_rows,
+                                       int64_t* out_labels, int64_t* order, attpc_undistort_info* info);
+
 #ifdef __cplusplus
 }
 #endif
