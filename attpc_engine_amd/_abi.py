@@ -201,6 +201,31 @@ EST_NO_HELIX = 256
 HELIX_AUTO, HELIX_Z_ON_PATH, HELIX_PATH_ON_Z = 0, 1, 2
 
 
+class FitDesc(C.Structure):
+    _fields_ = [("time_step", C.c_double), ("tolerance_momentum", C.c_double), ("tolerance_position", C.c_double),
+                ("max_steps", C.c_int32), ("max_evaluations", C.c_int32)]
+
+
+class TrackFit(C.Structure):
+    _fields_ = [("status", C.c_int32), ("evaluations", C.c_int32), ("n_points", C.c_int32), ("n_inside", C.c_int32),
+                ("steps", C.c_int32), ("end", C.c_int32), ("f", C.c_double), ("lambda_", C.c_double), ("g", C.c_double * 3),
+                ("vertex", C.c_double * 3), ("ke", C.c_double), ("brho", C.c_double), ("path", C.c_double),
+                ("reserved", C.c_double * 2)]
+
+
+# the track fit as a numpy structured dtype: itemsize and field offsets are those of include/attpc_engine.h
+FIT_DTYPE = np.dtype([("status", "<i4"), ("evaluations", "<i4"), ("n_points", "<i4"), ("n_inside", "<i4"), ("steps", "<i4"),
+                      ("end", "<i4"), ("f", "<f8"), ("lambda", "<f8"), ("g", "<f8", (3,)), ("vertex", "<f8", (3,)),
+                      ("ke", "<f8"), ("brho", "<f8"), ("path", "<f8"), ("reserved", "<f8", (2,))], align=True)
+assert FIT_DTYPE.itemsize == C.sizeof(TrackFit) == 128 and C.sizeof(FitDesc) == 32
+assert all(FIT_DTYPE.fields[name.rstrip("_")][1] == getattr(TrackFit, name).offset for name, _ in TrackFit._fields_)
+# ATTPC_FIT_*: the bits of TrackFit.status, the ends of a trial, the limits and the defaults
+FIT_EMPTY, FIT_FEW, FIT_CAPPED, FIT_NO_START, FIT_SINGULAR, FIT_STEP_CAP, FIT_NOT_CONVERGED = 1, 2, 8, 16, 32, 64, 128
+FIT_END_STOPPED, FIT_END_LEFT, FIT_END_STEP_CAP, FIT_END_NOT_FINITE = 1, 2, 3, 4
+FIT_MAX_POINTS, FIT_MAX_STEPS, FIT_MIN_EVALUATIONS, FIT_MAX_EVALUATIONS = 2048, 10000, 2, 32
+FIT_DEFAULT_TIME_STEP, FIT_DEFAULT_EVALUATIONS = 1.0e-10, 12
+
+
 class ThinDesc(C.Structure):
     _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
 
@@ -442,6 +467,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_helix", "attpc_rows_estimate_helix",
     "attpc_det_configure_distortion", "attpc_samples_distort",
     "attpc_trace_configure_correction", "attpc_correction_last", "attpc_rows_undistort",
+    "attpc_trace_configure_fit", "attpc_fits_last", "attpc_rows_fit",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -495,6 +521,9 @@ DISTORT_SYMBOLS = ("attpc_det_configure_distortion", "attpc_samples_distort")
 
 # ... and the drift correction of the trace rows after the drift distortion: the same rule.
 UNDISTORT_SYMBOLS = ("attpc_trace_configure_correction", "attpc_correction_last", "attpc_rows_undistort")
+
+# ... and the track fit after the drift correction: the same rule.
+FIT_SYMBOLS = ("attpc_trace_configure_fit", "attpc_fits_last", "attpc_rows_fit")
 
 _lib = None
 
@@ -719,6 +748,16 @@ def load_library() -> C.CDLL:
     for name, argtypes in correction.items():
         if not no_correction:
             getattr(lib, name).argtypes = argtypes
+    fit = {
+        "attpc_trace_configure_fit": [ctxp, C.POINTER(FitDesc)],
+        "attpc_fits_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(TrackFit)],
+        "attpc_rows_fit": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
+                           C.POINTER(TrackEstimate), _dp, C.POINTER(FitDesc), C.POINTER(TrackFit)],
+    }
+    no_fit = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in FIT_SYMBOLS)
+    for name, argtypes in fit.items():
+        if not no_fit:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -746,7 +785,8 @@ def load_library() -> C.CDLL:
                 or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)
                 or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)
                 or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)
-                or (no_distortion and name in DISTORT_SYMBOLS) or (no_correction and name in UNDISTORT_SYMBOLS)):
+                or (no_distortion and name in DISTORT_SYMBOLS) or (no_correction and name in UNDISTORT_SYMBOLS)
+                or (no_fit and name in FIT_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -756,7 +796,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit")
 
 
 class Context:

@@ -37,6 +37,7 @@
 #include "unpack_host.hpp"
 #include "spyral_integral.hpp"  // (behind the HIP runtime header)
 #include "circle_host.hpp"
+#include "fit_host.hpp"
 #include "helix_host.hpp"
 #include "estimate_host.hpp"
 #include "thin_host.hpp"
@@ -108,6 +109,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf pk_y;                 // Fourier baseline on (baseline.hip): the y rows the peak kernels read, int16 [traces][512]
   DevBuf tg_records;           // trigger on (trigger.hip): the chunk's records, attpc_trigger_record [events]
   DevBuf tg_row_pass;          // ... with its gate, trace rows: fired of every kept trace row's event, uint8 [traces]
+  DevBuf fit_records;          // track fit on (fit.hip): the chunk's records, attpc_track_fit [events][n_sim]
   DevBuf est_records;          // track estimates on (estimate.hip): the chunk's records, attpc_track_estimate [events][n_sim]
   DevBuf thin_points;          // ... of thinned points (thin.hip): one ThinPoint per trace row (pk_cap)
   DevBuf thin_info;            // ... and the attpc_thin_info of every (event, position)
@@ -264,6 +266,12 @@ struct attpc_ctx {
   attpc_circle_desc circle{};
   bool helix_on = false;           // attpc_trace_configure_helix (inert while the estimates are off)
   attpc_helix_desc helix{};
+  bool fit_on = false;             // attpc_trace_configure_fit (inert while the estimates are off)
+  attpc_fit_desc fit{};
+  FitPosition fit_position[ATTPC_MAX_SIM] = {};  // the nuclei of the positions of the trace-row call in progress
+  Pinned<attpc_track_fit> h_fits;  // records of the last trace-row call, as h_estimates
+  bool fit_call = false;           // that call made them
+  DevBuf fit_scratch;              // the trials' residuals (FitArgs::scratch), shared by the chunks: they run in stream order
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -1106,16 +1114,66 @@ void circle_settings(const attpc_circle_desc& d, EstimateArgs* a) {
   a->circle_max_evaluations = d.max_evaluations;
 }
 
+// The nuclei of the layout's positions for the track fit, from the configured detector.
+void fit_positions(const DetDev& det, const attpc_event_layout& lay, FitPosition position[ATTPC_MAX_SIM]) {
+  for (int s = 0; s < ATTPC_MAX_SIM; ++s) {
+    FitPosition& p = position[s];
+    p = FitPosition{0.0, 0.0, 0.0, 0.0, 0.0, -1, 0};
+    if (s >= lay.n_sim || lay.indices[s] < 0 || lay.indices[s] >= lay.n_rows) continue;
+    const int sp = lay.species_of_row[lay.indices[s]];
+    if (sp < 0 || sp >= det.n_species || det.Z[sp] <= 0 || !(det.mass[sp] > 0.0)) continue;
+    const FitSpecies f = fit_species(det.mass[sp], det.Z[sp], det.bfield, det.efield, det.density);
+    p = FitPosition{f.mass, f.charge, f.qm_b, f.qm_e, f.drag, sp, 0};
+  }
+}
+
+// The track fit of `n` events behind their estimates on S: the arguments the estimates had, their records, and room
+// for the trials.
+int32_t enqueue_fit(attpc_ctx* ctx, const EstimateArgs& e, uint32_t n, const attpc_fit_desc& d, const FitPosition* position,
+                    const double* start, attpc_track_fit* records) {
+  const uint32_t workgroups = fit_workgroups(n, e.n_sim);
+  const int32_t rc = ensure(ctx, ctx->fit_scratch, (size_t)workgroups * FIT_SCRATCH_PER_WORKGROUP);
+  if (rc) return rc;
+  FitArgs a{};
+  a.ev_start = e.ev_start;
+  a.rows = e.rows;
+  a.labels = e.labels;
+  a.points = e.points;
+  a.thin_info = e.thin_info;
+  a.estimates = e.records;
+  a.start = start;
+  a.records = records;
+  a.scratch = static_cast<double*>(ctx->fit_scratch.p);
+  a.dedx = ctx->det.dedx;
+  std::memcpy(a.slot_label, e.slot_label, sizeof a.slot_label);
+  std::memcpy(a.position, position, sizeof a.position);
+  a.d = d;
+  a.length = ctx->det.length;
+  a.rb2 = e.rb2;
+  a.n_events = n;
+  a.n_sim = e.n_sim;
+  launch_fit(ctx->stream, a);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
 // The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none and makes no records):
 // room for its track estimates (attpc_estimates_last), if the stage is on.  Nothing of an earlier call is in flight.
 int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay) {
   ctx->est_call_events = -1;
+  ctx->fit_call = false;
   if (!ctx->estimates_on || !lay) return ATTPC_OK;
   const int32_t rc = ensure_pinned(ctx, ctx->h_estimates, std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1));
   if (rc) return rc;
   estimate_positions(*lay, ctx->est_slot_label);
   ctx->est_call_n_sim = lay->n_sim;
   ctx->est_call_events = (int64_t)n;
+  if (ctx->fit_on) {
+    const int32_t rc2 = ensure_pinned(ctx, ctx->h_fits, std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1));
+    if (rc2) return rc2;
+    fit_positions(ctx->det, *lay, ctx->fit_position);
+    ctx->fit_call = true;
+  }
   return ATTPC_OK;
 }
 
@@ -1167,8 +1225,16 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   else
     launch_estimates(ctx->stream, n, a);
   HIP_TRY(ctx, hipGetLastError());
+  if (ctx->fit_call) {
+    if ((rc = ensure(ctx, as.fit_records, (size_t)n * n_sim * sizeof(attpc_track_fit)))) return rc;
+    if ((rc = enqueue_fit(ctx, a, n, ctx->fit, ctx->fit_position, nullptr, static_cast<attpc_track_fit*>(as.fit_records.p))))
+      return rc;
+  }
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
+  if (ctx->fit_call)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fits.p + first_local * n_sim, as.fit_records.p, (size_t)n * n_sim * sizeof(attpc_track_fit),
+                                hipMemcpyDeviceToHost, ctx->stream_c));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_estimates.p + first_local * n_sim, as.est_records.p,
                               (size_t)n * n_sim * sizeof(attpc_track_estimate), hipMemcpyDeviceToHost, ctx->stream_c));
   return ATTPC_OK;
@@ -3843,6 +3909,74 @@ int32_t attpc_rows_estimate_helix(attpc_ctx* ctx, int64_t n_events, const int64_
                                   const attpc_circle_desc* circle, const attpc_helix_desc* helix, attpc_track_estimate* out) {
   if (!helix) return ATTPC_E_INVALID;
   return rows_estimate(ctx, __func__, n_events, offsets, rows, labels, layout, d, circle, out, helix);
+}
+
+// ---- track fit (fit.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_fit(attpc_ctx* ctx, const attpc_fit_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = fit_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "fit: %s", bad);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->fit_on = d != nullptr;
+  if (d) ctx->fit = *d;
+  return ATTPC_OK;
+}
+
+int32_t attpc_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_fit* out) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->est_call_events < 0 || !ctx->fit_call)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_fits_last: the last trace-row call made no track fits");
+  if (const ArgError bad = records_range_error(__func__, first, count, ctx->est_call_events)) return refuse(ctx, bad);
+  const size_t n_sim = (size_t)ctx->est_call_n_sim;
+  if (count == 0 || n_sim == 0) return ATTPC_OK;
+  if (!out) return ATTPC_E_INVALID;
+  std::memcpy(out, ctx->h_fits.p + (size_t)first * n_sim, (size_t)count * n_sim * sizeof(attpc_track_fit));
+  return ATTPC_OK;
+}
+
+int32_t attpc_rows_fit(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                       const attpc_event_layout* layout, const attpc_estimate_desc* ed, const attpc_track_estimate* estimates_in,
+                       const double* start, const attpc_fit_desc* fd, attpc_track_fit* out) {
+  if (!ctx || n_events < 0 || !ed || !fd || !layout) return ATTPC_E_INVALID;
+  if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
+    return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", __func__, layout->n_sim, ATTPC_MAX_SIM);
+  if (layout->n_rows < 0 || layout->n_rows > ATTPC_MAX_ROWS)
+    return fail(ctx, ATTPC_E_INVALID, "%s: n_rows %d outside 0 .. %d", __func__, layout->n_rows, ATTPC_MAX_ROWS);
+  if (const char* bad = estimate_desc_error(*ed)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
+  if (const char* bad = fit_desc_error(*fd)) return fail(ctx, ATTPC_E_INVALID, "fit: %s", bad);
+  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "%s: no detector is configured", __func__);
+  const size_t n_sim = (size_t)layout->n_sim;
+  if (n_events > 0 && n_sim && (!out || !estimates_in)) return ATTPC_E_INVALID;
+  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
+  if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !labels)) return ATTPC_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  if (n_events == 0 || n_sim == 0) return ATTPC_OK;
+  EstimateArgs a{};
+  estimate_settings(*ed, &a);
+  estimate_positions(*layout, a.slot_label);
+  a.n_sim = (int32_t)n_sim;
+  FitPosition position[ATTPC_MAX_SIM];
+  fit_positions(ctx->det, *layout, position);
+  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
+  std::vector<int64_t> first;
+  for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
+    e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
+    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]);
+    chunk_starts(offsets, e0, e1, &first);
+    a.ev_start = stage_in(ctx, 2, first.data(), m + 1, rc);
+    a.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
+    a.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
+    a.records = const_cast<attpc_track_estimate*>(stage_in(ctx, 3, estimates_in + (size_t)e0 * n_sim, m * n_sim, rc));
+    const double* d_start = start ? stage_in(ctx, 4, start + (size_t)e0 * n_sim * 6, m * n_sim * 6, rc) : nullptr;
+    attpc_track_fit* d_out = stage<attpc_track_fit>(ctx, 5, m * n_sim, rc);
+    if (rc) return rc;
+    if ((rc = enqueue_fit(ctx, a, (uint32_t)m, *fd, position, d_start, d_out))) return rc;
+    if ((rc = stage_out(ctx, out + (size_t)e0 * n_sim, d_out, m * n_sim))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return ATTPC_OK;
 }
 
 // ---- thinned track points (thin.hip; the contract is in include/attpc_engine.h) ----

@@ -301,6 +301,37 @@ struct ThinArgs {
 // one workgroup per event, empty events included (n_events > 0, n_sim > 0)
 void launch_thin(hipStream_t s, uint32_t n_events, const ThinArgs& a);
 
+// track fit (fit.hip; attpc_trace_configure_fit, the contract is in include/attpc_engine.h)
+struct FitPosition {                // the nucleus of position s (FitSpecies of fit_host.hpp)
+  double mass, charge, qm_b, qm_e, drag;
+  int32_t table;                    // its table in dedx, -1: the position has no species
+  int32_t pad;
+};
+struct FitArgs {
+  const int64_t* ev_start;          // as EstimateArgs: the rows ...
+  const double* rows;
+  const int64_t* labels;
+  const ThinPoint* points;          // ... or, if not nullptr, the thinned points
+  const attpc_thin_info* thin_info;
+  const attpc_track_estimate* estimates;  // [n_events][n_sim]
+  const double* start;              // [n_events][n_sim][6] or nullptr
+  attpc_track_fit* records;         // [n_events][n_sim]
+  double* scratch;                  // [workgroups][8 tracks][8][ATTPC_FIT_MAX_POINTS][3]
+  const double* dedx;               // [n_species][ATTPC_DEDX_NODES]
+  int64_t slot_label[ATTPC_MAX_SIM];
+  FitPosition position[ATTPC_MAX_SIM];
+  attpc_fit_desc d;
+  double length;                    // m
+  int64_t rb2;
+  uint32_t n_events;
+  int32_t n_sim;
+};
+constexpr uint32_t FIT_MAX_WORKGROUPS = 1024;
+constexpr size_t FIT_SCRATCH_PER_WORKGROUP = (size_t)8 * 8 * ATTPC_FIT_MAX_POINTS * 3 * sizeof(double);
+// the workgroups (one wave of eight tracks each) for n_events * n_sim tracks; a.scratch holds that many regions
+uint32_t fit_workgroups(uint32_t n_events, int32_t n_sim);
+void launch_fit(hipStream_t s, const FitArgs& a);
+
 // drift correction of trace rows (undistort.hip; attpc_trace_configure_correction, the contract is in
 // include/attpc_engine.h)
 struct UndistortArgs {

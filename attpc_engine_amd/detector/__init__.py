@@ -2,6 +2,7 @@
 ``detector/__init__.py:13-21``) plus the batch entry points, device backed."""
 from . import correction as _correction
 from . import distortion as _distortion
+from . import fit as _fit
 from . import maps as _maps
 from . import parameters as _parameters
 from . import selection as _selection
@@ -27,6 +28,7 @@ _EXPORTS = {
     _straggling: ("StragglingSettings", "configure_straggling", "radiation_length", "electron_density"),
     _distortion: ("DistortionMap", "configure_distortion", "samples_to_distortion"),
     _correction: ("CorrectionSettings", "configure_correction", "rows_to_correction"),
+    _fit: ("TrackFitSettings", "configure_track_fit", "rows_to_fit"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

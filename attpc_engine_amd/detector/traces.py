@@ -238,6 +238,12 @@ def _checked_circle(circle):
     return _checked(circle)
 
 
+def _checked_fit(fit):
+    from .fit import _checked
+
+    return _checked(fit)
+
+
 def _checked_helix(helix):
     from .helix import _checked
 
@@ -410,11 +416,12 @@ class TraceChain:
     estimates: a ``detector.thinning.ThinSettings``), ``circle`` (the geometric circle fit behind them: a
     ``detector.circle.CircleFitSettings``), ``helix`` (the helix slope behind the circle: a
     ``detector.helix.HelixSlopeSettings``) and ``correction`` (trace rows: the drift correction of the rows, in front
-    of the thinning, the estimates and the delivery: a ``detector.correction.CorrectionSettings``)."""
+    of the thinning, the estimates and the delivery: a ``detector.correction.CorrectionSettings``) and ``fit`` (the
+    track fit behind the estimates: a ``detector.fit.TrackFitSettings``)."""
 
     def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
                  gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
-                 thinning=None, circle=None, helix=None, correction=None):
+                 thinning=None, circle=None, helix=None, correction=None, fit=None):
         self.config, self._given = config, (response, threshold)
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
@@ -424,6 +431,7 @@ class TraceChain:
         self.circle = _checked_circle(circle)
         self.helix = _checked_helix(helix)
         self.correction = _checked_correction(correction)
+        self.fit = _checked_fit(fit)
 
     @classmethod
     def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
@@ -439,10 +447,10 @@ class TraceChain:
 
     def replace(self, **fields) -> "TraceChain":
         """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning,
-        circle, helix, correction; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction"}
+        circle, helix, correction, fit; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction", "fit"}
         if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix and correction, not {sorted(unknown)}")
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix, correction and fit, not {sorted(unknown)}")
         chain = copy.copy(self)
         vars(chain).update(fields)
         if "config" in fields:
@@ -454,14 +462,15 @@ class TraceChain:
         _checked_circle(chain.circle)
         _checked_helix(chain.helix)
         _checked_correction(chain.correction)
+        _checked_fit(chain.fit)
         return chain
 
     def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
         """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
         trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
-        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them and the helix slope behind that.  A stage that is
+        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them, the helix slope behind that and the track fit behind the estimates.  A stage that is
         off is turned off, whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode"
-        "estimates" (the thinning, the circle fit and the helix slope with them) and "correction" that ``keep`` names, which stay as the ctx holds them."""
+        "estimates" (the thinning, the circle fit, the helix slope and the track fit with them) and "correction" that ``keep`` names, which stay as the ctx holds them."""
         from .simulator import configure_spyral
 
         ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
@@ -485,6 +494,7 @@ class TraceChain:
         if rows and "estimates" not in keep:
             from .circle import configure_circle
             from .estimate import configure_estimates
+            from .fit import configure_track_fit
             from .helix import configure_helix
             from .thinning import configure_thinning
 
@@ -492,6 +502,7 @@ class TraceChain:
             configure_thinning(ctx, self.thinning)
             configure_circle(ctx, self.circle)
             configure_helix(ctx, self.helix)
+            configure_track_fit(ctx, self.fit)
 
     def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
                   ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False,
@@ -534,6 +545,9 @@ class TraceChain:
             from .correction import correction_result
 
             extra.update(correction_result(ctx))
+            from .fit import fit_result
+
+            extra.update(fit_result(ctx, len(arrays.offsets) - 1, len(indices)))
         sums = ctx.trace_rows_last() if rows else arrays.sums()
         return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
 
@@ -1054,7 +1068,7 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
                               estimates=None, thinning=None, straggling=None, circle=None, helix=None,
-                              distortion=None, correction=None, **trace_kwargs):
+                              distortion=None, correction=None, fit=None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -1069,11 +1083,12 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     ``gain``, ``common_mode``, ``straggling`` and ``distortion`` as simulate_batch_traces takes them.  With
     ``correction`` (a ``detector.correction.CorrectionSettings``; None = off) the rows and labels are the drift-corrected
     ones, per event in ascending corrected z, the estimates are made of them, and the stage's counts come under
-    ``"correction"``."""
+    ``"correction"``.  With ``fit`` (a ``detector.fit.TrackFitSettings``; None = off) and ``estimates`` the track fits
+    [n, len(indices)] come under ``"fits"``."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
                                                                    thinning=thinning, circle=circle, helix=helix,
-                                                                   correction=correction)
+                                                                   correction=correction, fit=fit)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event, straggling=straggling, distortion=distortion)
 

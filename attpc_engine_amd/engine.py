@@ -19,6 +19,7 @@ from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings
                               configure_trigger, trigger_result)
 from .detector.estimate import EstimateSettings, configure_estimates, estimates_result
 from .detector.circle import CircleFitSettings, circle_result, configure_circle
+from .detector.fit import TrackFitSettings, configure_track_fit, fit_result
 from .detector.helix import HelixSlopeSettings, configure_helix, helix_result
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .detector.straggling import StragglingSettings, configure_straggling
@@ -302,7 +303,8 @@ class Engine:
         Both: ``trace_rows`` = {n_rows, row_checksum}, the cloud's ``stats`` (``n_points`` = the rows) and, with a
         trigger configured (``configure_trigger``), its records [n] under ``trigger`` (with its ``gate`` an event that
         did not fire is an empty range of the offsets); with the track estimates configured (``configure_estimates``)
-        their records [n, n_sim] under ``estimates`` -- with the thinning configured too (``configure_thinning``) those
+        their records [n, n_sim] under ``estimates`` (and with the track fit
+        configured, ``configure_track_fit``, its records under ``fits``) -- with the thinning configured too (``configure_thinning``) those
         of the thinned points, and its z step under ``thinning``; with the geometric circle fit configured as well
         (``configure_circle_fit``) their circles are the refined ones, and ``circle`` is "geometric"; with the helix
         slope configured (``configure_helix_slope``) their slope, vz and B rho come from the turning angle about the
@@ -318,13 +320,13 @@ class Engine:
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                     **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
-                    **helix_result(ctx), **correction_result(ctx)}
+                    **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices))}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                 **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
-                    **helix_result(ctx), **correction_result(ctx)}
+                    **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices))}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -360,6 +362,15 @@ class Engine:
         nothing."""
         configure_helix(self.ctx, _settings(HelixSlopeSettings, settings, parameters))
 
+    def configure_track_fit(self, settings=None, **parameters) -> None:
+        """The track fit behind the track estimates (include/attpc_engine.h, "track fit"): a
+        ``detector.fit.TrackFitSettings`` or its keywords (time_step, max_steps, max_evaluations, tolerance_momentum,
+        tolerance_position) turn it on -- ``run_trace_rows`` and ``run_estimates`` then return one record per (event,
+        position) under ``fits`` (``detector.fit.FIT_DTYPE``): momentum over mass and vertex of the trial track through
+        the gas that fits the track's points best, started from its estimate record --, neither turns it off (the
+        default).  Without the estimates it does nothing.  The writers do not store the records."""
+        configure_track_fit(self.ctx, _settings(TrackFitSettings, settings, parameters))
+
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
         128 bytes per track cross PCIe (``estimates`` [n, n_sim], ``detector.estimate.ESTIMATE_DTYPE``), beside the
@@ -380,7 +391,8 @@ class Engine:
         return {"estimates": ctx.estimates_last(n_events, len(self.indices)), "indices": list(self.indices),
                 "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
                 "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx),
-                **circle_result(ctx), **helix_result(ctx), **correction_result(ctx)}
+                **circle_result(ctx), **helix_result(ctx), **correction_result(ctx),
+                **fit_result(ctx, n_events, len(self.indices))}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

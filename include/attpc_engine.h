@@ -1694,6 +1694,141 @@ ATTPC_API int32_t attpc_rows_undistort(attpc_ctx* ctx, int64_t n_events, const i
                                        const int64_t* labels, const attpc_undistort_desc* desc, double* out_rows,
                                        int64_t* out_labels, int64_t* order, attpc_undistort_info* info);
 
+/* ---- track fit (opt-in: off by default, and with it off every output, kernel and buffer of every entry point is what
+ * it is without this section; inert while the track estimates are off; the entry points are additions under ABI
+ * version 3) ----
+ * Every stage above fits a circle and a straight line, a model in which the particle loses no energy.  The track fit
+ * is Spyral's solver phase on the device: for every (event, position) it takes the estimate record as a start and fits
+ * the momentum and the vertex of a trial track, integrated through the gas with the species' stopping-power table, to
+ * the label's points.  One 128-byte record (attpc_track_fit) per event and position, beside the estimate record.
+ * THIS CONTRACT is what the device is tested against; tests/fit_reference.py restates it in numpy, and
+ * csrc/fit_host.hpp is its arithmetic, the same code on the device and on the host.  Everything is f64, each operation
+ * rounded once, left to right as C evaluates the expression, no fused multiply-add; only + - * / and sqrt.
+ *
+ * Settings (attpc_fit_desc): time_step in s, tolerance_momentum (relative), tolerance_position in m, all finite and
+ * > 0; max_steps 1 .. 10000; max_evaluations 2 .. 32.
+ *
+ * Parameters.  q = (gx, gy, gz, x0, y0, z0): g = gamma beta at the vertex, the vertex in metres.
+ *
+ * Species.  The position's nucleus is species_of_row[indices[s]] of the layout, with the context's mass m (MeV), charge
+ * number Z, stopping-power table and the fields, density and length of its detector:
+ *   mkg = m * 1.7826619216278976e-30;  qm = Z * 1.602176634e-19 / mkg;  c = 299792458
+ *   qb = qm * (-B) / c;  qe = qm * (-E) / c;  drag = 1.6021766339999998e-13 * density * 100 / mkg / c
+ * Right-hand side of the state s = (x, y, z, gx, gy, gz), that of the track kernel with sqrt and / for rsqrt:
+ *   gv2 = gx gx + gy gy + gz gz;  gv = sqrt(gv2);  gamma = sqrt(1 + gv2);  ke = m (gamma - 1);  vs = c / gamma
+ *   v = (gx vs, gy vs, gz vs);  dec = dedx(ke) * drag / gv
+ *   ds = (vx, vy, vz, qb vy - dec gx, (-qb) vx - dec gy, qe - dec gz)
+ * dedx(ke) reads the table as the track kernel does (exponent -> binade, top five mantissa bits -> node i, the low 47
+ * bits / 2^47 -> t; lo + t * (hi - lo); table[0] below 2^-30 MeV or for a NaN, the last node from 2^14 MeV).
+ * Step of length h = time_step, classical RK4: k1 = f(s), k2 = f(s + (0.5 h) k1), k3 = f(s + (0.5 h) k2),
+ * k4 = f(s + h k3), s' = s + (h / 6) * (((k1 + 2 k2) + 2 k3) + k4), component by component.
+ *
+ * End of a trial.  Sample 0 is the vertex, sample n the state after n steps.  The trial ends at the first sample for
+ * which, tested in this order: a component of s is not finite (end = 4); ke <= 1e-6 MeV (end = 1, stopped);
+ * z < 0, z > length or x x + y y >= 0.292 * 0.292 (end = 2, left); n >= max_steps (end = 3, step cap).
+ *
+ * Data.  The USED rows of the label (step 1 of the track estimates, the same code; with thinning on the label's
+ * thinned points), all of them, in delivered order: n_used.  n_points = min(n_used, 2048); data point j is used row
+ * j for n_used <= 2048 and used row floor(j n_used / 2048) otherwise, which sets CAPPED.  Metres: x = (double)X /
+ * 16000.0, and so y and z.
+ *
+ * Residuals of a trial.  sg = +1 for gz >= 0 at the vertex, else -1; the cursor c = 0, 1, .. stands for data point c
+ * (sg = +1) or n_points - 1 - c (sg = -1).  (i) While sg z_c < sg z_vertex: r_c = vertex - point (three components),
+ * next c.  (ii) After every step from sample p to sample s, with d = s - p: while sg z_c <= sg z_s:
+ * w = 0 if dz == 0, else (z_c - z_p) / dz; r_c = ((x_p + w dx) - x_c, (y_p + w dy) - y_c, 0), the point counts as
+ * inside, next c.  A tie in z therefore goes to the first bracket that reaches it, and an empty bracket (dz == 0) gives
+ * sample p.  The end test follows (ii).  (iii) Every point left when the trial has ended: r_c = last sample - point
+ * (three components).  path = the sum over the steps of sqrt((dx dx + dy dy) + dz dz), in step order.
+ *
+ * Evaluation at q: seven trials, trial 0 at q and trial k at q + delta_(k-1) e_(k-1), with delta = 2^-16 |g_start| for
+ * the momentum components and 2^-16 m for the vertex, fixed for the whole fit (|v| = sqrt((v0 v0 + v1 v1) + v2 v2)).
+ * Per point J_k = (r^(k+1) - r^(0)) / delta_k component by component, dot(a, b) = (a0 b0 + a1 b1) + a2 b2, and the 28
+ * sums f = sum dot(r0, r0), (J^T r)_k = sum dot(J_k, r0), N_kl = sum dot(J_k, J_l) for k <= l.
+ * ORDER OF SUMMATION: eight accumulators starting at 0, point i to accumulator i mod 8 in ascending i; then
+ * a_l <- a_l + a_(l xor 4), a_l <- a_l + a_(l xor 2), a_l <- a_l + a_(l xor 1) on all eight at once; the sum is a_0.
+ *
+ * Step: A = N (symmetric), A_kk = N_kk + lambda N_kk, b = -(J^T r).  For p = 0 .. 5: a pivot A_pp that is not > 0 ->
+ * SINGULAR; for r > p: l = A_rp / A_pp, A_rc = A_rc - l A_pc for c = p .. 5, b_r = b_r - l b_p.  Back substitution for
+ * p = 5 .. 0: v = b_p; v = v - A_pc d_c for c = p + 1 .. 5 ascending; d_p = v / A_pp.
+ *
+ * Iteration (Levenberg-Marquardt with the constants of the geometric circle fit): lambda = 2^-10; evaluate the start;
+ * while evaluations < max_evaluations: solve the step (SINGULAR ends the fit with the kept q), evaluate q + d; the
+ * trial is ACCEPTED iff f(q + d) <= f(q) and every component of q + d is finite: q <- q + d with its sums,
+ * lambda <- 0.04 lambda, and the fit has converged if |d_g| <= tolerance_momentum |g| (the new g) and
+ * |d_x| <= tolerance_position; otherwise lambda <- 10 lambda and the step is solved again from the kept sums.
+ * Neither converged nor singular: NOT_CONVERGED.
+ *
+ * Start from the estimate record e (rows of Z mass units as above):
+ *   |g| = 299.792458 * Z * e.brho / m;  b = e.slope;  w = sqrt(1 + b b);  st = 1 / w;  ct = b / w
+ *   n = ((e.vx - e.cx) / e.radius, (e.vy - e.cy) / e.radius);  t = (-ny, nx), negated if
+ *   tx (e.x_mean - e.vx) + ty (e.y_mean - e.vy) < 0;  q = (|g| st tx, |g| st ty, |g| ct, e.vx / 1000, e.vy / 1000,
+ *   e.vz / 1000).
+ * e.status with EMPTY or FEW -> the same bit here; a start value that is not finite, or a position without a species
+ * (Z = 0) -> NO_START.  In all three cases n_points = min(e.n_used, 2048), evaluations, n_inside, steps and end are 0 and
+ * every f64 field is NaN (the reserved ones are 0).
+ *
+ * Record: f, lambda, g, the vertex in mm (x0 * 1000.0), n_inside, steps, end and path of trial 0 of the kept q,
+ * ke = m (sqrt(1 + |g| |g|) - 1) in MeV, brho = |g| m / (299.792458 * Z) in T m; STEP_CAP iff end == 3.
+ * A label given twice goes to its first position (the later one is EMPTY through its estimate).  A record is a pure
+ * function of the event's rows, the estimate record, the species' table and the settings. */
+#define ATTPC_FIT_EMPTY 1
+#define ATTPC_FIT_FEW 2
+#define ATTPC_FIT_CAPPED 8          /* more than 2048 used rows: every floor(j n_used / 2048)-th was taken */
+#define ATTPC_FIT_NO_START 16
+#define ATTPC_FIT_SINGULAR 32
+#define ATTPC_FIT_STEP_CAP 64       /* the final trial ended at sample max_steps */
+#define ATTPC_FIT_NOT_CONVERGED 128
+#define ATTPC_FIT_MAX_POINTS 2048
+#define ATTPC_FIT_MAX_STEPS 10000
+#define ATTPC_FIT_MIN_EVALUATIONS 2
+#define ATTPC_FIT_MAX_EVALUATIONS 32
+#define ATTPC_FIT_END_STOPPED 1
+#define ATTPC_FIT_END_LEFT 2
+#define ATTPC_FIT_END_STEP_CAP 3
+#define ATTPC_FIT_END_NOT_FINITE 4
+
+typedef struct attpc_fit_desc {
+  double time_step;           /* s; 1e-10 is the grid of the track kernel */
+  double tolerance_momentum;  /* relative to |g| */
+  double tolerance_position;  /* m */
+  int32_t max_steps;          /* 1 .. 10000 */
+  int32_t max_evaluations;    /* 2 .. 32 */
+} attpc_fit_desc;  /* 32 bytes */
+
+typedef struct attpc_track_fit {
+  int32_t status;       /* ATTPC_FIT_* bits */
+  int32_t evaluations;
+  int32_t n_points;
+  int32_t n_inside;
+  int32_t steps;
+  int32_t end;          /* ATTPC_FIT_END_* of the final trial */
+  double f;             /* m^2 */
+  double lambda;
+  double g[3];
+  double vertex[3];     /* mm */
+  double ke;            /* MeV */
+  double brho;          /* T m */
+  double path;          /* m; the range of a stopped track */
+  double reserved[2];   /* 0 */
+} attpc_track_fit;  /* 128 bytes */
+
+/* desc == NULL turns the stage off (the default).  ATTPC_E_INVALID outside the ranges above, NaN included.
+ * Independent of every other configure call.  With the track estimates on, attpc_sim_run_trace_rows and
+ * attpc_det_run_trace_rows launch the fit behind every chunk's estimate kernel on the same stream, on what the
+ * estimates read (corrected rows, thinned points or raw rows), also when the rows stay on the device.  It holds 3 MiB
+ * of device memory per resident wave for the trials' residuals, 1024 waves at the most. */
+ATTPC_API int32_t attpc_trace_configure_fit(attpc_ctx* ctx, const attpc_fit_desc* desc);
+/* Records [count][layout->n_sim] of the context's last trace-row call, as attpc_estimates_last. */
+ATTPC_API int32_t attpc_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_fit* out);
+/* The stage alone on any host rows in CSR form, through the same kernel: estimates_in [n_events][n_sim] are the
+ * records of attpc_rows_estimate* on the same rows with estimate_desc; start [n_events][n_sim][6] or NULL replaces
+ * the start from the estimates (EMPTY and FEW still come from them).  The context needs a configured detector
+ * (ATTPC_E_NOTCONFIGURED without one); indices and species_of_row of the layout are read. */
+ATTPC_API int32_t attpc_rows_fit(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                 const int64_t* labels, const attpc_event_layout* layout,
+                                 const attpc_estimate_desc* estimate_desc, const attpc_track_estimate* estimates_in,
+                                 const double* start, const attpc_fit_desc* fit_desc, attpc_track_fit* out);
+
 #ifdef __cplusplus
 }
 #endif
