@@ -1,33 +1,40 @@
 """The restatements of the single trace stages (tests/*_reference.py) composed in the order of the contract
 (include/attpc_engine.h): gain -> traces (noise, pedestals, common mode, readout) -> trigger -> gate -> baseline or
-pedestal subtraction -> peaks -> thinning -> estimates / circle fit.  ``chain`` takes the stage settings of one case
-(``tests.chain_cases.settings``) and one run's cloud and returns what every downstream output must be.  No arithmetic
-of its own: every stage is a call of its restatement, a stage that is off is passed by, and the steps are functions of
-their own so that tests/test_chain_cpu.py can put them together wrongly on purpose."""
+pedestal subtraction -> peaks -> drift correction -> thinning -> estimates / circle fit / helix slope -> track fit.
+``chain`` takes the stage settings of one case (``tests.chain_cases.settings``) and one run's cloud and returns what
+every downstream output must be.  Straggling and the drift distortion act in front of the cloud: they shape it, and the
+chain of a given cloud does not know of them.  No arithmetic of its own: every stage is a call of its restatement, a
+stage that is off is passed by, and the steps are functions of their own so that tests/test_chain_cpu.py can put them
+together wrongly on purpose."""
 from __future__ import annotations
 
 from typing import NamedTuple
 
 import numpy as np
 
+from attpc_engine_amd._abi import EST_NO_HELIX, EST_RANGE, FIT_EMPTY
 from attpc_engine_amd.detector.response import get_response
 from attpc_engine_amd.detector.traces import gaussian_noise_table, normal_quantile_table, readout_mask
 from tests import baseline_reference, circle_reference, common_mode_reference, estimate_reference, gain_reference
-from tests import peaks_reference, readout_reference, thin_reference, trace_noise_reference, trace_reference
-from tests import trigger_reference
+from tests import distortion_cases, fit_reference, helix_reference, peaks_reference, readout_reference, thin_reference
+from tests import trace_noise_reference, trace_reference, trigger_reference, undistort_reference
 
 
 class Chain(NamedTuple):
     """Every output of one case.  ``traces`` = (offsets, pads, samples, labels, sums) as ``run_traces`` delivers them;
     ``trigger`` the records [n] or None; ``fired`` bool [n] (all True without a gate); ``rows`` = (offsets, rows,
-    labels, sums) as ``run_trace_rows`` delivers them; ``points`` = what ``rows_to_points`` makes of the rows, or None;
-    ``records`` the estimates [n, n_sim] or None."""
+    labels, sums) as ``run_trace_rows`` delivers them (with the drift correction on: the corrected rows); ``points`` =
+    what ``rows_to_points`` makes of the rows, or None; ``records`` the estimates [n, n_sim] or None; ``correction``
+    the counts of the drift correction or None; ``fits`` the track-fit records [n, n_sim] or None."""
     traces: tuple
     trigger: np.ndarray | None
     fired: np.ndarray
     rows: tuple
     points: tuple | None
     records: np.ndarray | None
+    correction: dict | None = None
+    fits: np.ndarray | None = None
+    uncorrected: tuple | None = None  # the rows in front of the drift correction (None without it); not an output
 
 
 # ---------------------------------------------------------------- the settings, restated ----
@@ -74,6 +81,27 @@ def params_of(s: dict, config):
 def circle_of(s: dict):
     c = s["circle"]
     return None if c is None else circle_reference.Settings(c.max_evaluations, c.tolerance)
+
+
+def correction_of(s: dict, config):
+    """The drift correction's descriptor: the map's three derived numbers as tests/distortion_cases.py writes them out,
+    the drift of the config."""
+    c = s["correction"]
+    if c is None:
+        return None
+    return undistort_reference.Settings(distortion_cases.reference_map(c.map, config), int(config.elec_params.windows_edge),
+                                        int(config.elec_params.micromegas_edge), float(config.det_params.length),
+                                        c.iterations, c.tolerance_xy, c.tolerance_tb)
+
+
+def helix_of(s: dict):
+    return None if s["helix"] is None else helix_reference.Settings(s["helix"].regressor)
+
+
+def fit_of(s: dict):
+    f = s["fit"]
+    return None if f is None else fit_reference.Settings(f.time_step, f.max_steps, f.max_evaluations, f.tolerance_momentum,
+                                                         f.tolerance_position)
 
 
 # ---------------------------------------------------------------- the steps ----
@@ -159,6 +187,17 @@ def rows_of(s: dict, config, offsets, pads, y, labels, pedestals, seed: int, fir
     return peaks_reference.trace_rows(offsets, pads, y, labels, pk, peaks_reference.Geometry.of(config), seed, first, pedestals)
 
 
+def corrected_of(s: dict, config, rows, mutant=None):
+    """Step 6b -> (the rows every later step and the delivery see, the correction's counts or None): every gated row
+    taken back through the map and every event's rows sorted again.  Offsets, n_rows and the row checksum (terms of
+    event, pad and sample) stay."""
+    settings = correction_of(s, config)
+    if settings is None:
+        return rows, None
+    new_rows, new_labels, _, info = undistort_reference.undistort(settings, rows[0], rows[1], rows[2], mutant)
+    return (rows[0], new_rows, new_labels, rows[3]), info
+
+
 def points_of(s: dict, rows, indices):
     """Step 7 (None: no thinning)."""
     if s["estimates"] is None or s["thinning"] is None:
@@ -170,7 +209,14 @@ def records_of(s: dict, config, rows, indices):
     """Step 8 (None: no estimates)."""
     if s["estimates"] is None:
         return None
-    params, circle = params_of(s, config), circle_of(s)
+    params, circle, helix = params_of(s, config), circle_of(s), helix_of(s)
+    if helix is not None:  # (as tests/test_gpu_helix.py composes it)
+        if s["thinning"] is None:
+            return helix_reference.records(rows[0], rows[1], rows[2], indices, params, helix, circle)
+        point_offsets, points, point_labels, info = thin_reference.thin(rows[0], rows[1], rows[2], indices, s["thinning"].z_step)
+        records = helix_reference.records(point_offsets, points, point_labels, indices, params, helix, circle)
+        records["status"] |= np.where(info["n_dropped"] > 0, EST_RANGE, 0).astype(np.int32)
+        return records
     if s["thinning"] is not None:
         return thin_reference.fused_records(rows[0], rows[1], rows[2], indices, s["thinning"].z_step, params, circle)
     if circle is not None:
@@ -178,17 +224,35 @@ def records_of(s: dict, config, rows, indices):
     return estimate_reference.records(rows[0], rows[1], rows[2], indices, params)
 
 
+def fits_of(s: dict, inp, rows, records):
+    """Step 9 (None: no track fit, or no estimates to start it from): the fit on what the estimates read -- the
+    corrected rows, thinned if the thinning is on -- started from the restatement's own estimate records.  ``inp``: the
+    workload's descriptors (``tests.helpers.Inputs``), whose detector and layout are the model."""
+    if s["fit"] is None or s["estimates"] is None:
+        return None
+    assert inp is not None, "the track fit needs the workload's descriptors: chain(..., inp=)"
+    seen = rows[:3]
+    if s["thinning"] is not None:
+        seen = thin_reference.thin(rows[0], rows[1], rows[2], inp.indices, s["thinning"].z_step)[:3]
+    return fit_reference.records(*seen, inp.indices, fit_reference.Model(inp.det, inp.layout), records, fit_of(s),
+                                 s["estimates"].beam_region_radius)
+
+
 # ---------------------------------------------------------------- the composition ----
-def chain(s: dict, config, indices, cloud, seed: int, first: int, baseline=numpy_baseline, traces=None) -> Chain:
+def chain(s: dict, config, indices, cloud, seed: int, first: int, baseline=numpy_baseline, traces=None, inp=None) -> Chain:
     """The steps in contract order.  ``baseline``: the operator of step 5 (the device tests pass the device's own,
-    which they hold to ``baseline_reference`` under its ambiguity rule); ``traces``: step 1 and 2 if already made."""
+    which they hold to ``baseline_reference`` under its ambiguity rule); ``traces``: step 1 and 2 if already made;
+    ``inp``: the workload's descriptors, which the track fit needs."""
     tr = traces_of(s, config, cloud, seed, first) if traces is None else traces
     trigger = trigger_of(s, tr)
     fired = fired_of(s, trigger, len(tr[0]) - 1)
     offsets, pads, samples, labels = gated(tr[:4], fired)
     y, pedestals = y_of(s, samples, baseline)
-    rows = rows_of(s, config, offsets, pads, y, labels, pedestals, seed, first)
-    return Chain(tr, trigger, fired, rows, points_of(s, rows, indices), records_of(s, config, rows, indices))
+    plain = rows_of(s, config, offsets, pads, y, labels, pedestals, seed, first)
+    rows, correction = corrected_of(s, config, plain)
+    records = records_of(s, config, rows, indices)
+    return Chain(tr, trigger, fired, rows, points_of(s, rows, indices), records, correction, fits_of(s, inp, rows, records),
+                 None if correction is None else plain)
 
 
 def assert_same(got: Chain, want: Chain) -> None:
@@ -208,6 +272,10 @@ def assert_same(got: Chain, want: Chain) -> None:
         thin_reference.assert_same_points(got.points, want.points)
     if want.records is not None:
         estimate_reference.assert_same_records(got.records, want.records)
+    assert got.correction == want.correction, (got.correction, want.correction)
+    assert (got.fits is None) == (want.fits is None)
+    if want.fits is not None:
+        fit_reference.assert_same_records(got.fits, want.fits)
 
 
 # ---------------------------------------------------------------- what makes a case worth running ----
@@ -252,6 +320,22 @@ def counts(s: dict, config, indices, cloud, seed: int, first: int, got: Chain, b
         out["status_not_0"] = int((got.records["status"] != 0).sum())
         if s["circle"] is not None:
             out["circle_fits"] = int((got.records["reserved"] > 0).sum())
+    if got.correction is not None:  # rows the re-sort moved, and events whose corrected rows would not be in ascending z
+        out["rows_moved"] = got.correction["n_moved"]
+        unsorted = undistort_reference.undistort(correction_of(s, config), *got.uncorrected[:3], "no_resort")[0]
+        out["events_out_of_order"] = sum(bool((np.diff(unsorted[lo:hi, 2]) < 0.0).any())
+                                         for lo, hi in zip(got.rows[0][:-1], got.rows[0][1:]))
+    if got.records is not None and s["helix"] is not None:  # records the helix ran in, and those whose slope it moved
+        ran = (got.records["n_fit"] > 0) & (got.records["status"] & EST_NO_HELIX == 0)
+        without = records_of({**s, "helix": None}, config, got.rows, indices)
+        out["helix_ran"] = int(ran.sum())
+        out["helix_slopes_moved"] = int((got.records["slope"][ran] != without["slope"][ran]).sum())
+    if got.fits is not None:
+        ran = got.fits["evaluations"] >= 2
+        out["fits_ran"] = int(ran.sum())
+        if "fired" in out:  # behind a gate: fits that ran in events that fired, records of events that did not
+            out["fits_ran_fired"] = int(ran[got.fired].sum())
+            out["fits_not_fired"] = int((got.fits["status"][~got.fired] == FIT_EMPTY).sum())
     return out
 
 
@@ -267,3 +351,7 @@ def assert_not_vacuous(c: dict, n_events: int) -> None:
     assert c.get("thinned_tracks", 1) >= 1, c
     assert c.get("status_0", 4) >= 4 and c.get("status_not_0", 1) >= 1, c
     assert c.get("circle_fits", 1) >= 1, c
+    assert c.get("rows_moved", 1) >= 1 and c.get("events_out_of_order", 1) >= 1, c
+    assert c.get("helix_ran", 2) >= 2 and c.get("helix_slopes_moved", 1) >= 1, c
+    assert c.get("fits_ran", 2) >= 2, c
+    assert c.get("fits_ran_fired", 1) >= 1 and c.get("fits_not_fired", 1) >= 1, c

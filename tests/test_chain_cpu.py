@@ -1,25 +1,29 @@
 """The table of stage combinations (tests/chain_cases.py) and the composed restatement (tests/chain_reference.py),
-without a device: the committed table covers every valid pair of levels; with every stage off, and with each stage on
-alone, the composition is what the stage's own restatement gives on the same oracle cloud; the settings can meet the
-non-vacuity conditions of every row (on the oracle's cloud, without straggling: tests/test_gpu_chain.py asserts them
-again on the device's); and a composition that is wrong in one of four ways fails the comparison on the all-on row."""
+without a device: the committed table covers every valid pair of levels of its 16 factors in at most 14 rows, and its
+first generation of 12 factors stands in it unchanged; with every stage off, and with each stage on alone, the
+composition is what the stage's own restatement gives on the same oracle cloud; the settings can meet the non-vacuity
+conditions of every row (on the oracle's cloud, without straggling and distortion: tests/test_gpu_chain.py asserts them
+again on the device's); and a composition that is wrong in one of eight ways fails the comparison on the all-on row."""
 import itertools
 
 import numpy as np
 import pytest
 
+from attpc_engine_amd import _abi
 from attpc_engine_amd.detector.response import get_response
 from attpc_engine_amd.detector.traces import normal_quantile_table
 from tests import chain_cases as cc
 from tests import chain_reference as cr
-from tests import (circle_reference, common_mode_reference, estimate_reference, gain_reference, peaks_reference,
-                   thin_reference, trace_noise_reference, trace_reference, trigger_reference)
+from tests import (circle_reference, common_mode_reference, distortion_cases, estimate_reference, fit_reference,
+                   gain_reference, helix_reference, peaks_reference, thin_reference, trace_noise_reference, trace_reference,
+                   trigger_reference, undistort_reference)
 from tests.helpers import Inputs
 
 
 # ---------------------------------------------------------------- 1. the table ----
 def test_table_covers_every_valid_pair():
-    assert 9 <= len(cc.TABLE) <= 12 and len({c.name for c in cc.TABLE}) == len(cc.TABLE)
+    assert len(cc.NAMES) == 16 and cc.NAMES[12:] == ("distortion", "correction", "helix", "fit")
+    assert 9 <= len(cc.TABLE) <= 14 and len({c.name for c in cc.TABLE}) == len(cc.TABLE)
     for c in cc.TABLE:
         assert cc.valid(c.levels()), c
         for name, level in zip(cc.NAMES, c.levels()):
@@ -29,20 +33,44 @@ def test_table_covers_every_valid_pair():
     for c in cc.TABLE:
         covered |= set(itertools.combinations(zip(cc.NAMES, c.levels()), 2))
     every = {((f, a), (g, b)) for f, g in itertools.combinations(cc.NAMES, 2) for a in cc.FACTORS[f] for b in cc.FACTORS[g]}
-    assert covered <= every
-    assert every - covered == {(("estimates", "off"), ("circle", True))}
-    # ... and that pair is invalid by the stated rule, as is a partial readout without a noise source -- and nothing else
+    assert covered <= every and len(every) == 541
+    assert every - covered == {(("estimates", "off"), (stage, True)) for stage in ("circle", "helix", "fit")}
+    assert covered == cc.valid_pairs()
+    # ... and those pairs are invalid by the stated rule, as is a partial readout without a noise source -- and nothing else
     invalid = [levels for levels in itertools.product(*cc.FACTORS.values()) if not cc.valid(levels)]
     for levels in invalid:
         a = dict(zip(cc.NAMES, levels))
-        assert (a["circle"] and a["estimates"] == "off") or (a["readout"] == "partial" and not a["noise"] and not a["common"])
+        assert ((a["circle"] or a["helix"] or a["fit"]) and a["estimates"] == "off") \
+            or (a["readout"] == "partial" and not a["noise"] and not a["common"])
     n_all = int(np.prod([len(v) for v in cc.FACTORS.values()]))
-    circle_rule, readout_rule = n_all // 6, n_all // 8  # (one of 2 x 3 circle/estimates cells; one of 8 readout/noise/common)
-    assert len(invalid) == circle_rule + readout_rule - n_all // 48
+    # (7 of 8 circle/helix/fit cells in one of 3 estimates cells; one of 8 readout/noise/common cells)
+    estimates_rule, readout_rule = 7 * n_all // 24, n_all // 8
+    assert len(invalid) == estimates_rule + readout_rule - 7 * n_all // 192
     levels = [c.levels() for c in cc.TABLE]
     assert cc.ALL_ON in levels and cc.ALL_OFF in levels
     assert cc.case("all_on").levels() == cc.ALL_ON and cc.case("all_off").levels() == cc.ALL_OFF
     assert levels == cc.generate()  # (the table is what the generator in the module gives)
+    # the table's first generation runs on as it was: its eleven rows and their twelve columns, by name and in order
+    assert [c.levels()[:cc.N_BASE] for c in cc.TABLE[:11]] == cc.generate_base() == FIRST_GENERATION
+    assert [c.name for c in cc.TABLE[:11]] == FIRST_GENERATION_NAMES
+
+
+FIRST_GENERATION_NAMES = ["all_on", "all_off", "noise_partial_trigger_rows", "gain_common_gate_circle", "common_baseline_thinned_circle",
+                          "gain_common_partial_baseline", "noise_hit_thinned_circle", "noise_partial_baseline_gate",
+                          "gain_common_trigger", "straggle_gain_baseline_rows", "noise_trigger_thinned"]
+FIRST_GENERATION = [
+    (True, True, True, True, "partial", True, "gate", "thinned", True, 3, "straddle", "fetch"),
+    (False, False, False, False, "hit", False, "off", "off", False, 1, "zero", "resident"),
+    (True, False, True, False, "partial", False, "on", "rows", False, 1, "straddle", "fetch"),
+    (False, True, False, True, "hit", False, "gate", "rows", True, 3, "zero", "resident"),
+    (False, False, False, True, "hit", True, "on", "thinned", True, 1, "straddle", "resident"),
+    (True, True, False, True, "partial", True, "off", "off", False, 3, "zero", "resident"),
+    (True, False, True, False, "hit", False, "off", "thinned", True, 3, "zero", "fetch"),
+    (False, False, True, False, "partial", True, "gate", "off", False, 1, "straddle", "resident"),
+    (False, True, False, True, "hit", False, "on", "off", False, 1, "zero", "fetch"),
+    (True, True, False, False, "hit", True, "off", "rows", False, 3, "straddle", "resident"),
+    (True, False, True, False, "hit", False, "on", "thinned", False, 3, "zero", "resident"),
+]
 
 
 def test_chunks_of_the_workload():
@@ -81,7 +109,7 @@ def _head(cloud, n):
 
 def _chain(inp, c, cloud, **kw):
     s = cc.settings(c, inp.config)
-    return s, cr.chain(s, inp.config, inp.indices, _head(cloud, c.n_events), cc.SEED, cc.first_event(c), **kw)
+    return s, cr.chain(s, inp.config, inp.indices, _head(cloud, c.n_events), cc.SEED, cc.first_event(c), inp=inp, **kw)
 
 
 # ---------------------------------------------------------------- 2. off, and one stage at a time ----
@@ -120,6 +148,9 @@ def test_every_stage_off_is_traces_then_peaks(inp, clouds):
 
 
 def test_one_stage_on_is_that_stage_alone(inp, clouds):
+    """Straggling and the drift distortion only shape the cloud: on a given cloud the chain with either on is the chain
+    with it off (what they do to the cloud is held to their restatements in tests/test_gpu_straggling.py and
+    tests/test_gpu_distortion.py).  Every other stage on alone gives what its own restatement gives."""
     cloud = _head(clouds[0], FEW)
     offsets, points, labels = cloud
     resp = get_response(inp.config)
@@ -186,6 +217,37 @@ def test_one_stage_on_is_that_stage_alone(inp, clouds):
     s, got = _chain(inp, OFF._replace(estimates="thinned"), clouds[0])
     thin_reference.assert_same_points(got.points, thin_reference.thin(*plain_rows[:3], inp.indices, cc.THIN_STEP))
     estimate_reference.assert_same_records(got.records, thin_reference.fused_records(*plain_rows[:3], inp.indices, cc.THIN_STEP, params))
+    # straggling, the drift distortion: nothing of the chain of this cloud moves
+    _, off = _chain(inp, OFF, clouds[0])
+    for shaped in (OFF._replace(straggling=True), OFF._replace(distortion=True)):
+        s, got = _chain(inp, shaped, clouds[0])
+        assert s["straggling"] is not None or s["distortion"] is not None
+        cr.assert_same(got, off)
+    # the drift correction: the restatement on the plain rows; offsets, the number of rows and the checksum stay
+    s, got = _chain(inp, OFF._replace(correction=True), clouds[0])
+    drift = inp.config.elec_params
+    settings = undistort_reference.Settings(distortion_cases.reference_map(distortion_cases.named_map(), inp.config),
+                                            int(drift.windows_edge), int(drift.micromegas_edge), float(inp.config.det_params.length))
+    fixed = undistort_reference.undistort(settings, *plain_rows[:3])
+    _assert_traces_and_rows(got, plain_traces, (plain_rows[0], fixed[0], fixed[1], plain_rows[3]))
+    # (rows that change places need more events: a condition of every table row with the stage, not of these six)
+    assert got.correction == fixed[3] and fixed[3]["n_rows"] == len(plain_rows[1]) and not np.array_equal(fixed[0], plain_rows[1])
+    assert got.records is None and got.fits is None and off.correction is None
+    # the helix slope and the track fit, each alone behind the estimates of the raw rows
+    params = estimate_reference.Params(*cc.ESTIMATES["rows"], inp.config.det_params.bfield)
+    plain_records = estimate_reference.records(*plain_rows[:3], inp.indices, params)
+    s, got = _chain(inp, OFF._replace(estimates="rows", helix=True), clouds[0])
+    _assert_traces_and_rows(got, plain_traces, plain_rows)
+    estimate_reference.assert_same_records(got.records, helix_reference.records(*plain_rows[:3], inp.indices, params,
+                                                                                helix_reference.Settings()))
+    assert (got.records["slope"] != plain_records["slope"]).any() and got.fits is None
+    s, got = _chain(inp, OFF._replace(estimates="rows", fit=True), clouds[0])
+    _assert_traces_and_rows(got, plain_traces, plain_rows)
+    estimate_reference.assert_same_records(got.records, plain_records)
+    fits = fit_reference.records(*plain_rows[:3], inp.indices, fit_reference.Model(inp.det, inp.layout), plain_records,
+                                 fit_reference.Settings(**cc.FIT), cc.ESTIMATES["rows"][0])
+    fit_reference.assert_same_records(got.fits, fits)
+    assert (fits["evaluations"] >= 2).any()
 
 
 # ---------------------------------------------------------------- 3. every row has something to show ----
@@ -237,15 +299,47 @@ def _wrong(inp, clouds, all_on, fault):
     rows = cr.rows_of(s, config, offsets, pads, y, labels, pedestals, seed, first)
     if not early:  # the rows of the events that did not fire dropped now: the sums are those of every event
         rows = cr.gated(rows[:3], fired) + (rows[3],)
+    rows, correction = cr.corrected_of(s, config, rows)
     seen = rows
     if fault == "thinning of the ungated rows":
         ungated = cr.y_of(s, tr[2])
-        seen = cr.rows_of(s, config, tr[0], tr[1], ungated[0], tr[3], ungated[1], seed, first)
-    return cr.Chain(tr, trigger, fired, rows, cr.points_of(s, seen, indices), cr.records_of(s, config, seen, indices))
+        seen = cr.corrected_of(s, config, cr.rows_of(s, config, tr[0], tr[1], ungated[0], tr[3], ungated[1], seed, first))[0]
+    records = cr.records_of(s, config, seen, indices)
+    return cr.Chain(tr, trigger, fired, rows, cr.points_of(s, seen, indices), records, correction, cr.fits_of(s, inp, seen, records))
+
+
+def _wrong_behind_the_rows(inp, all_on, fault):
+    """The all-on chain with one of the steps behind the trace rows out of place (the rows are the right chain's)."""
+    c, s, right = all_on
+    config, indices = inp.config, inp.indices
+    if fault == "the correction after the thinning":
+        # the uncorrected rows thinned, the points taken back through the map and sorted, then estimated and fitted
+        point_offsets, points, point_labels, info = cr.points_of(s, right.uncorrected, indices)
+        points, point_labels = cr.corrected_of(s, config, (point_offsets, points, point_labels, None))[0][1:3]
+        unthinned = {**s, "thinning": None}
+        records = cr.records_of(unthinned, config, (point_offsets, points, point_labels), indices)
+        records["status"] |= np.where(info["n_dropped"] > 0, _abi.EST_RANGE, 0).astype(np.int32)
+        fits = cr.fits_of(unthinned, inp, (point_offsets, points, point_labels), records)
+        return right._replace(points=(point_offsets, points, point_labels, info), records=records, fits=fits)
+    if fault == "the fit on the uncorrected rows":
+        return right._replace(fits=cr.fits_of(s, inp, right.uncorrected, right.records))
+    if fault == "the fit on the raw rows although thinning is on":
+        return right._replace(fits=cr.fits_of({**s, "thinning": None}, inp, right.rows, right.records))
+    assert fault == "the fit started from estimates without the helix slope"
+    return right._replace(fits=cr.fits_of(s, inp, right.rows, cr.records_of({**s, "helix": None}, config, right.rows, indices)))
 
 
 def test_the_steps_in_order_are_the_chain(inp, clouds, all_on):
     cr.assert_same(_wrong(inp, clouds, all_on, None), all_on[2])
+
+
+@pytest.mark.parametrize("fault", ["the correction after the thinning", "the fit on the uncorrected rows",
+                                   "the fit on the raw rows although thinning is on",
+                                   "the fit started from estimates without the helix slope"])
+def test_a_wrong_composition_behind_the_rows_is_caught(inp, all_on, fault):
+    wrong = _wrong_behind_the_rows(inp, all_on, fault)
+    with pytest.raises(AssertionError):
+        cr.assert_same(wrong, all_on[2])
 
 
 @pytest.mark.parametrize("fault", ["the pedestal as well as the baseline", "the gate after the peaks", "gain after the noise",

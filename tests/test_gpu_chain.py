@@ -1,18 +1,23 @@
-"""Every pair of opt-in trace stages together on the device: one test per row of the table of tests/chain_cases.py, the
-device against the composition of the stages' numpy restatements (tests/chain_reference.py) on the device's own cloud
--- traces, trigger records, trace rows, thinned points and estimates equal, every comparison an equality; the one
-exception is the Fourier baseline's operator, held to its restatement under the rule and the constants of
+"""Every pair of opt-in stages together on the device -- the trace stages, and straggling, drift distortion, drift
+correction, helix slope and track fit around them: one test per row of the table of tests/chain_cases.py (16 factors),
+the device against the composition of the stages' numpy restatements (tests/chain_reference.py) on the device's own
+cloud -- traces, trigger records, trace rows (the corrected ones with the drift correction on, and its counts), thinned
+points, estimates and track fits equal, every comparison an equality (integer fields equal, f64 fields bit for bit);
+the one exception is the Fourier baseline's operator, held to its restatement under the rule and the constants of
 tests/test_gpu_baseline.py, the rows then exact given its y.  Each row states on the restatement's own figures that it
-is not vacuous.  Then every run kind in turn on one context against fresh contexts, and the file-driven forms against
-the ``Engine``.  Needs a real MI355X: ``-m gpu``.
+is not vacuous.  Then every run kind in turn on one context against fresh contexts, with every stage of the all-on row
+configured, and the file-driven forms against the ``Engine``.  Needs a real MI355X: ``-m gpu``.
 
 The cloud behind every later call is held to the first one's by the run statistics: both checksums and the number of
 track samples everywhere, ``n_points`` for the trace calls -- a trace-row call reports its rows there (the contract of
-``run_trace_rows``), which are held to the restatement's count instead.
+``run_trace_rows``), which are held to the restatement's count instead.  Straggling and the drift distortion shape
+that cloud and nothing behind it: with either on, every run kind still reports the first call's sums.
 
-Measured on an MI355X, wall time per row with its restatement: 4.6 s for the all-on row (36 729 traces; 0.9 s at the
-other chunking, the restatement made once), 0.3 .. 2.2 s for the others; no row found a difference.  The figures of the
-non-vacuity conditions of every row are in DESIGN.md §6; each test prints its own."""
+Measured on an MI355X, wall time per row with its restatement: 5.5 s for the all-on row (36 735 traces, 4 track fits;
+1.0 s at the other chunking and 1.5 s with every event a chunk of its own, the restatement made once), 0.3 .. 2.9 s
+for the others (the rows with the track fit: 1.2 .. 2.9 s); the same file with the table of 12 factors, on the same
+machine: 4.4 s, 1.0 s and 0.3 .. 2.2 s.  No row found a difference.  The figures of the non-vacuity conditions of every
+row are in DESIGN.md §6; each test prints its own."""
 import sys
 import time
 import warnings
@@ -26,7 +31,7 @@ from attpc_engine_amd.detector.traces import remove_baseline, simulate_batch_tra
 from tests import chain_cases as cc
 from tests import chain_reference as cr
 from tests import estimate_reference as est
-from tests import thin_reference, trace_pack_reference, trigger_reference
+from tests import fit_reference, thin_reference, trace_pack_reference, trigger_reference
 from tests.helpers import Inputs
 from tests.maps_reference import assert_same_maps
 from tests.test_gpu_baseline import _assert_operator_equals_restatement, _read_spyral_files
@@ -50,6 +55,7 @@ def inp():
 def _configure(eng, s) -> None:
     """Every stage of the chain as the settings have it, on or off."""
     eng.configure_straggling(s["straggling"])
+    eng.configure_distortion(s["distortion"])
     eng.configure_traces(eng.config, **s["traces"])
     eng.configure_spyral(eng.config)
     eng.configure_gain(s["gain"])
@@ -60,12 +66,16 @@ def _configure(eng, s) -> None:
     eng.configure_estimates(s["estimates"])
     eng.configure_thinning(s["thinning"])
     eng.configure_circle_fit(s["circle"])
+    eng.configure_helix_slope(s["helix"])
+    eng.configure_track_fit(s["fit"])
+    eng.configure_correction(s["correction"])
 
 
 def _engine(inp, ctx, s, chunks: int = 1):
     from attpc_engine_amd.engine import Engine
 
-    eng = Engine(inp.pipeline, inp.config, inp.indices, context=ctx, chunk_events=cc.CHUNK_EVENTS if chunks == 3 else None)
+    chunk_events = {1: None, 3: cc.CHUNK_EVENTS, "one event each": 1}[chunks]
+    eng = Engine(inp.pipeline, inp.config, inp.indices, context=ctx, chunk_events=chunk_events)
     _configure(eng, s)
     return eng
 
@@ -111,11 +121,11 @@ def _reference(inp, ctx, c, s, cloud):
     first = cc.first_event(c)
     csr = (cloud["offsets"], cloud["points"], cloud["labels"])
     operator = _device_baseline(ctx, c.name)
-    want = cr.chain(s, inp.config, inp.indices, csr, cc.SEED, first, baseline=operator)
+    want = cr.chain(s, inp.config, inp.indices, csr, cc.SEED, first, baseline=operator, inp=inp)
     ungated = None
     if c.trigger == "gate":
         ungated = cr.chain({**s, "trigger": s["trigger"].gated(False)}, inp.config, inp.indices, csr, cc.SEED, first,
-                           baseline=operator, traces=want.traces)
+                           baseline=operator, traces=want.traces, inp=inp)
     figures = cr.counts(s, inp.config, inp.indices, csr, cc.SEED, first, want)
     print(f"{c.name}: {figures}")
     cr.assert_not_vacuous(figures, c.n_events)
@@ -177,8 +187,8 @@ def _check_case(inp, ctx, c, chunks):
         assert kept["trace_rows"] == want.rows[3], (kept["trace_rows"], want.rows[3])
         _assert_run(kept, cloud, "run_trace_rows, resident", n_points=want.rows[3]["n_rows"])
         triggers.append(kept.get("trigger"))
-        records = [kept.get("estimates")]
-        rows = want.rows
+        records, fits, corrections = [kept.get("estimates")], [kept.get("fits")], [kept.get("correction")]
+        rows = want.rows  # (with the drift correction on: the corrected rows and the labels that moved with them)
         if fetch:
             res = eng.run_trace_rows(n, **run)
             for k, key in enumerate(("offsets", "rows", "labels")):
@@ -188,6 +198,8 @@ def _check_case(inp, ctx, c, chunks):
             np.testing.assert_array_equal(res["event_points"], np.diff(cloud["offsets"]))
             triggers.append(res.get("trigger"))
             records.append(res.get("estimates"))
+            fits.append(res.get("fits"))
+            corrections.append(res.get("correction"))
             rows = (res["offsets"], res["rows"], res["labels"])
         # ---- trigger: one set of records, whichever call made them
         if s["trigger"] is None:
@@ -200,15 +212,29 @@ def _check_case(inp, ctx, c, chunks):
         if s["thinning"] is not None:
             thin_reference.assert_same_points(rows_to_points(*rows[:3], inp.indices, s["thinning"], ctx), want.points)
         if s["estimates"] is None:
-            assert records == [None] * len(records)
+            assert records == [None] * len(records) and "slope" not in kept
         else:
             only = eng.run_estimates(n, **run)
             assert only["trace_rows"] == want.rows[3]
             records.append(only["estimates"])
+            fits.append(only.get("fits"))
+            corrections.append(only.get("correction"))
             for got in records:
                 est.assert_same_records(got, want.records)
             assert kept.get("thinning") == (cc.THIN_STEP if c.estimates == "thinned" else None)
             assert kept.get("circle") == ("geometric" if c.circle else None)
+            assert kept.get("slope") == only.get("slope") == ("helix" if c.helix else None)
+        # ---- the drift correction's counts and the track fits: one set, whichever call made them; absent when off
+        if s["correction"] is None:
+            assert corrections == [None] * len(corrections) and want.correction is None
+        else:
+            assert corrections == [want.correction] * len(corrections), (corrections, want.correction)
+        if s["fit"] is None:
+            assert fits == [None] * len(fits) and want.fits is None
+        else:
+            assert len(fits) >= 2
+            for got in fits:
+                fit_reference.assert_same_records(got, want.fits)
         # ---- gate
         if c.trigger == "gate":
             fired = want.fired
@@ -225,6 +251,14 @@ def _check_case(inp, ctx, c, chunks):
                 empty = records[0][~fired]
                 assert (empty["status"] == _abi.EST_EMPTY).all() and (empty["n_rows"] == 0).all() and (empty["reserved"] == 0).all()
                 est.assert_same_records(records[0][fired], ungated.records[fired])
+            if s["fit"] is not None:
+                empty = fits[0][~fired]
+                assert (empty["status"] == _abi.FIT_EMPTY).all() and not empty["reserved"].any()
+                for field in ("evaluations", "n_points", "n_inside", "steps", "end"):
+                    assert not empty[field].any(), field
+                for field in ("f", "lambda", "g", "vertex", "ke", "brho", "path"):  # (every f64 field but the reserved ones)
+                    assert np.isnan(empty[field]).all(), field
+                fit_reference.assert_same_records(fits[0][fired], ungated.fits[fired])
     finally:
         _reset(inp, ctx)
     print(f"{c.name}, {chunks} chunk(s): {time.perf_counter() - started:.1f} s")
@@ -242,6 +276,13 @@ def test_all_on_does_not_depend_on_the_chunks(ctx, inp):
     _check_case(inp, ctx, c, 1 if c.chunks == 3 else 3)
 
 
+def test_all_on_in_chunks_of_one_event(ctx, inp):
+    """The all-on row once more, every event a chunk of its own: the chunk of an event that did not fire holds no row,
+    so the drift correction is not run on it while the thinning, the estimates and the track fit behind it still are;
+    and the chunk of one that fired uses the sort keys and the fit's scratch its neighbours left."""
+    _check_case(inp, ctx, cc.case("all_on"), "one event each")
+
+
 # ---------------------------------------------------------------- one context, every run kind ----
 def _same_result(got, want, what, unordered=None):
     assert set(got) == set(want), (what, sorted(got), sorted(want))
@@ -253,6 +294,10 @@ def _same_result(got, want, what, unordered=None):
             assert_same_maps(g, w, what)
         elif key == "estimates":
             est.assert_same_records(g, w)
+        elif key == "fits":
+            fit_reference.assert_same_records(g, w)
+        elif key == "correction":
+            assert g == w and set(w) == {"n_rows", "n_skipped", "n_unconverged", "n_moved"}, (what, g, w)
         elif key in (unordered, "labels") and unordered:
             pass  # (below, in canonical order)
         elif isinstance(w, np.ndarray) and w.dtype.names:
@@ -283,9 +328,10 @@ SEQUENCE = RUN_KINDS + RUN_KINDS[:3]
 
 
 def test_every_run_kind_in_turn_on_one_context(inp):
-    """The kinds share device buffers (the sort keys, the assembly sets, the per-chunk buffers that only grow): each
-    call on the one context gives what the same call gives on a context that never ran anything else -- at two event
-    counts, the smaller one second, so that the buffers both grow and are used again at a smaller size."""
+    """The kinds share device buffers (the sort keys, which the drift correction borrows, the assembly sets, the
+    uncorrected rows, the track fit's scratch, the per-chunk buffers that only grow): each call on the one context, with
+    every stage of the all-on row configured, gives what the same call gives on a context that never ran anything else
+    -- at two event counts, the smaller one second, so that the buffers both grow and are used again at a smaller size."""
     c = cc.case("all_on")
     s = cc.settings(c, inp.config)
     kw = dict(seed=cc.SEED, first_event=cc.first_event(c))
@@ -309,6 +355,8 @@ def test_every_run_kind_in_turn_on_one_context(inp):
                 finally:
                     fresh.close()
                 _same_result(got, want, f"{name}, {n} events", unordered)
+                if n == c.n_events and name in ("run_trace_rows", "run_estimates"):  # (the sort and the fit had work to do)
+                    assert want["correction"]["n_moved"] > 0 and (want["fits"]["evaluations"] >= 2).any(), name
                 if name.startswith("run_selected"):
                     passed = want["passed"]
             assert 0 < passed.sum() < n  # (the selection takes some of the events and leaves some)
@@ -333,7 +381,8 @@ def test_file_driven_forms_give_the_rows_and_records_of_the_engine(ctx, inp, tmp
                 off, rows, labels, event_points, stats = simulate_batch_trace_rows(
                     res["p4"], res["vertex"], inp.z, inp.a, inp.config, seed, inp.indices, first_event=first, ctx=ctx,
                     trigger=s["trigger"], estimates=s["estimates"], thinning=s["thinning"], circle=s["circle"],
-                    straggling=s["straggling"], **stages, **s["traces"])
+                    straggling=s["straggling"], distortion=s["distortion"], correction=s["correction"], helix=s["helix"],
+                    fit=s["fit"], **stages, **s["traces"])
                 np.testing.assert_array_equal(off, res["offsets"])
                 np.testing.assert_array_equal(rows, res["rows"])
                 np.testing.assert_array_equal(labels, res["labels"])
@@ -341,14 +390,17 @@ def test_file_driven_forms_give_the_rows_and_records_of_the_engine(ctx, inp, tmp
                 assert {k: stats[k] for k in ("n_rows", "row_checksum")} == res["trace_rows"]
                 est.assert_same_records(stats["estimates"], res["estimates"])
                 _assert_trigger(stats["trigger"], res["trigger"], "simulate_batch_trace_rows")
-                assert stats["thinning"] == cc.THIN_STEP and stats["circle"] == "geometric"
+                assert stats["thinning"] == cc.THIN_STEP and stats["circle"] == "geometric" and stats["slope"] == "helix"
+                fit_reference.assert_same_records(stats["fits"], res["fits"])
+                assert stats["correction"] == res["correction"] and res["correction"]["n_moved"] > 0
+                assert (res["fits"]["evaluations"] >= 2).any()
                 continue
             # SpyralWriter(peaks=...) through run_fused: events 0 .. n - 1, those that fired and are not empty
             monkeypatch.setitem(sys.modules, "h5py", None)
             warnings.simplefilter("ignore", RuntimeWarning)
-            writer = SpyralWriter(tmp_path, inp.config, max_events_per_file=5, **stages, **s["traces"])
+            writer = SpyralWriter(tmp_path, inp.config, max_events_per_file=5, correction=s["correction"], **stages, **s["traces"])
             run_fused(inp.pipeline, inp.config, writer, n, inp.indices, seed=seed, batch_size=cc.CHUNK_EVENTS, context=ctx,
-                      trigger=s["trigger"], straggling=s["straggling"])
+                      trigger=s["trigger"], straggling=s["straggling"], distortion=s["distortion"], correction=s["correction"])
             got = _read_spyral_files(tmp_path)
             written = [e for e in range(n) if res["event_points"][e] > 0 and res["trigger"]["fired"][e]]
             assert sorted(got) == written and written

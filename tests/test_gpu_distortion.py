@@ -160,6 +160,40 @@ def test_records_equal_the_restatement(ctx, orc, name, n, options):
         assert not on[0][t, c:].any()
 
 
+def test_records_equal_the_restatement_behind_the_straggling(ctx, orc):
+    """Straggling and the distortion both act on the track samples in front of the scatter, the distortion last: with
+    both on, the records are the restatement's shift of the device's own straggled records, bit for bit."""
+    from attpc_engine_amd.detector.straggling import StragglingSettings, configure_straggling
+    inp = Inputs("be10dp")
+    seed, first, n = 13, 5, 8
+    vertex, p4, _, _ = orc.kin_batch(inp.kin, seed, first, n, threads=8)
+    m = dc.reference_map()
+    try:
+        _distortion(ctx, None)
+        plain = _device_tracks(ctx, inp, p4, vertex, seed, first)
+        configure_straggling(ctx, StragglingSettings(stream=3), inp.config)
+        straggled = _device_tracks(ctx, inp, p4, vertex, seed, first)
+        _distortion(ctx, m)
+        both = _device_tracks(ctx, inp, p4, vertex, seed, first)
+    finally:
+        configure_straggling(ctx, None)
+        _distortion(ctx, None)
+    counts = straggled[1]
+    print("tracks", len(counts), "records", int(counts.sum()), "unstraggled", int(plain[1].sum()))
+    assert np.array_equal(both[1], counts) and np.array_equal(both[2], straggled[2]) and counts.sum() > 1000
+    # the straggling is there: other records than without it
+    assert not np.array_equal(counts, plain[1]) or not dref.same_bits(_kept(straggled[0], counts), _kept(plain[0], plain[1]))
+    want = dref.shift_records(m, _kept(straggled[0], counts))
+    got = _kept(both[0], counts)
+    differ = np.flatnonzero((got.view(np.uint64) != want.view(np.uint64)).any(axis=1))
+    assert differ.size == 0, (differ[:10], got[differ[:3]], want[differ[:3]])
+    assert (got[:, :3] != _kept(straggled[0], counts)[:, :3]).any(axis=1).mean() > 0.5
+    for t, c in enumerate(counts):
+        assert not both[0][t, c:].any()
+    # ... and with the stages off again the records are the first ones
+    _same(plain, _device_tracks(ctx, inp, p4, vertex, seed, first))
+
+
 # 3 ------------------------------------------------------------------------------------------ the stage alone ----
 def test_stage_alone(ctx):
     named, m, config = dc.named_map(), dc.reference_map(), dc.drift()
