@@ -226,6 +226,37 @@ FIT_MAX_POINTS, FIT_MAX_STEPS, FIT_MIN_EVALUATIONS, FIT_MAX_EVALUATIONS = 2048, 
 FIT_DEFAULT_TIME_STEP, FIT_DEFAULT_EVALUATIONS = 1.0e-10, 12
 
 
+class ClusterDesc(C.Structure):  # attpc_cluster_desc
+    _fields_ = [("eps_xy", C.c_double), ("eps_z", C.c_double), ("min_samples", C.c_int32), ("min_cluster_size", C.c_int32),
+                ("max_rows", C.c_int32), ("match", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class ClusterEvent(C.Structure):  # attpc_cluster_event
+    _fields_ = [("n_rows", C.c_int32), ("n_range", C.c_int32), ("n_core", C.c_int32), ("n_border", C.c_int32),
+                ("n_noise", C.c_int32), ("n_clusters", C.c_int32), ("n_small", C.c_int32), ("n_split", C.c_int32),
+                ("n_fake", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32 * 2), ("truth_rows", C.c_uint16 * MAX_SIM)]
+
+
+class ClusterRecord(C.Structure):  # attpc_cluster_record
+    _fields_ = [("rows", C.c_int32), ("core_rows", C.c_int32), ("first_row", C.c_int32), ("majority", C.c_int32),
+                ("majority_rows", C.c_int32), ("label", C.c_int32), ("z_min", C.c_int32), ("z_max", C.c_int32)]
+
+
+# the cluster records as numpy structured dtypes: itemsize and field offsets are those of include/attpc_engine.h
+CLUSTER_EVENT_DTYPE = np.dtype([("n_rows", "<i4"), ("n_range", "<i4"), ("n_core", "<i4"), ("n_border", "<i4"), ("n_noise", "<i4"),
+                                ("n_clusters", "<i4"), ("n_small", "<i4"), ("n_split", "<i4"), ("n_fake", "<i4"), ("status", "<i4"),
+                                ("reserved", "<i4", (2,)), ("truth_rows", "<u2", (MAX_SIM,))], align=True)
+CLUSTER_DTYPE = np.dtype([("rows", "<i4"), ("core_rows", "<i4"), ("first_row", "<i4"), ("majority", "<i4"),
+                          ("majority_rows", "<i4"), ("label", "<i4"), ("z_min", "<i4"), ("z_max", "<i4")], align=True)
+assert C.sizeof(ClusterDesc) == 40 and CLUSTER_EVENT_DTYPE.itemsize == C.sizeof(ClusterEvent) == 64
+assert CLUSTER_DTYPE.itemsize == C.sizeof(ClusterRecord) == 32
+assert all(CLUSTER_EVENT_DTYPE.fields[name][1] == getattr(ClusterEvent, name).offset for name, _ in ClusterEvent._fields_)
+# ATTPC_CLUSTER_*: the match modes, the bits of ClusterEvent.status, the limits and the default
+CLUSTER_MATCH_TRUTH, CLUSTER_MATCH_RANK = 0, 1
+CLUSTER_CAPPED, CLUSTER_INTERNAL = 1, 2
+CLUSTER_DEFAULT_MAX_ROWS, CLUSTER_MAX_ROWS_LIMIT = 16384, 65535
+
+
 class ThinDesc(C.Structure):
     _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
 
@@ -468,6 +499,7 @@ EXPORTED_SYMBOLS = (
     "attpc_det_configure_distortion", "attpc_samples_distort",
     "attpc_trace_configure_correction", "attpc_correction_last", "attpc_rows_undistort",
     "attpc_trace_configure_fit", "attpc_fits_last", "attpc_rows_fit",
+    "attpc_trace_configure_clustering", "attpc_clusters_last", "attpc_cluster_labels_last", "attpc_rows_cluster",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -524,6 +556,9 @@ UNDISTORT_SYMBOLS = ("attpc_trace_configure_correction", "attpc_correction_last"
 
 # ... and the track fit after the drift correction: the same rule.
 FIT_SYMBOLS = ("attpc_trace_configure_fit", "attpc_fits_last", "attpc_rows_fit")
+
+# ... and the clustering after the track fit: the same rule.
+CLUSTER_SYMBOLS = ("attpc_trace_configure_clustering", "attpc_clusters_last", "attpc_cluster_labels_last", "attpc_rows_cluster")
 
 _lib = None
 
@@ -758,6 +793,17 @@ def load_library() -> C.CDLL:
     for name, argtypes in fit.items():
         if not no_fit:
             getattr(lib, name).argtypes = argtypes
+    clustering = {
+        "attpc_trace_configure_clustering": [ctxp, C.POINTER(ClusterDesc)],
+        "attpc_clusters_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(ClusterEvent), C.POINTER(ClusterRecord)],
+        "attpc_cluster_labels_last": [ctxp, C.c_int64, C.c_int64, i64p],
+        "attpc_rows_cluster": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(ClusterDesc), i64p,
+                               C.POINTER(ClusterEvent), C.POINTER(ClusterRecord)],
+    }
+    no_clustering = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in CLUSTER_SYMBOLS)
+    for name, argtypes in clustering.items():
+        if not no_clustering:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -786,7 +832,7 @@ def load_library() -> C.CDLL:
                 or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)
                 or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)
                 or (no_distortion and name in DISTORT_SYMBOLS) or (no_correction and name in UNDISTORT_SYMBOLS)
-                or (no_fit and name in FIT_SYMBOLS)):
+                or (no_fit and name in FIT_SYMBOLS) or (no_clustering and name in CLUSTER_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -796,7 +842,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit", "clustering")
 
 
 class Context:

@@ -114,6 +114,8 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf thin_points;          // ... of thinned points (thin.hip): one ThinPoint per trace row (pk_cap)
   DevBuf thin_info;            // ... and the attpc_thin_info of every (event, position)
   DevBuf uc_rows, uc_labels;   // drift correction on (undistort.hip): the chunk's corrected, re-sorted rows and labels (pk_cap)
+  DevBuf cl_labels;            // clustering on (cluster.hip): the chunk's cluster labels (pk_cap),
+  DevBuf cl_events, cl_records;  // ... its attpc_cluster_event [events] and attpc_cluster_record [events][ATTPC_MAX_SIM]
   Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
   // packed traces (trace_pack.hip): the headers and record sizes of every kept trace row, their scanned byte offsets
   // (tp_block_*: the scan's scratch) and the records; the chunk's bytes in pinned memory (the host waits on `counted`)
@@ -296,6 +298,15 @@ struct attpc_ctx {
   DevBuf uc_sums;                  // [4] the counts of the trace-row run in progress
   bool correction_call = false;    // attpc_correction_last: the stage was on for the last trace-row call, and its counts
   attpc_undistort_info last_correction{};
+  bool cluster_on = false;         // attpc_trace_configure_clustering
+  attpc_cluster_desc cluster{};
+  DevBuf cl_scratch;               // [rows][CLUSTER_SCRATCH_WORDS] the per-row state of the chunk being clustered (cluster.hip)
+  int64_t cluster_call_events = -1;  // attpc_clusters_last: events of the last trace-row call, -1: the stage was off for it
+  ClusterSettings cluster_call{};  // ... its settings with the call's layout
+  Pinned<attpc_cluster_event> h_cl_events;    // ... and its records, as h_estimates
+  Pinned<attpc_cluster_record> h_cl_records;
+  Pinned<int64_t> h_cl_labels;     // attpc_cluster_labels_last: the cluster labels of the call's delivered rows,
+  int64_t cluster_call_rows = -1;  // ... how many (-1: the call did not fetch its rows)
   int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
   uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
@@ -1196,6 +1207,7 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   // (may be nullptr: then no event of the chunk has a row; with the drift correction on its rows and labels)
   a.rows = static_cast<const double*>(ctx->correction_on ? as.uc_rows.p : as.sp_rows.p);
   a.labels = static_cast<const int64_t*>(ctx->correction_on ? as.uc_labels.p : as.sp_labels.p);
+  if (ctx->cluster_call_events >= 0) a.labels = static_cast<const int64_t*>(as.cl_labels.p);  // (clustering on: its labels)
   a.records = static_cast<attpc_track_estimate*>(as.est_records.p);
   std::memcpy(a.slot_label, ctx->est_slot_label, sizeof a.slot_label);
   a.n_sim = (int32_t)n_sim;
@@ -1261,6 +1273,50 @@ int32_t enqueue_correction(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
   a.out_labels = static_cast<int64_t*>(as.uc_labels.p);
   a.counts = static_cast<unsigned long long*>(ctx->uc_sums.p);
   launch_undistort(ctx->stream, n, a);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none and is not clustered):
+// room for its cluster records and, if the call fetches its rows (`row_capacity` of them, -1: it does not), for their
+// cluster labels.  Nothing of an earlier call is in flight.
+int32_t begin_cluster_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay, int64_t row_capacity) {
+  ctx->cluster_call_events = -1;
+  ctx->cluster_call_rows = -1;
+  if (!ctx->cluster_on || !lay) return ATTPC_OK;
+  int32_t rc;
+  if ((rc = ensure_pinned(ctx, ctx->h_cl_events, std::max<size_t>((size_t)n, 1)))) return rc;
+  if ((rc = ensure_pinned(ctx, ctx->h_cl_records, std::max<size_t>((size_t)n * ATTPC_MAX_SIM, 1)))) return rc;
+  if (row_capacity >= 0) {
+    if ((rc = ensure_pinned(ctx, ctx->h_cl_labels, std::max<size_t>((size_t)row_capacity, 1)))) return rc;
+    ctx->cluster_call_rows = 0;
+  }
+  ctx->cluster_call = cluster_settings(ctx->cluster, *lay);
+  ctx->cluster_call_events = (int64_t)n;
+  return ATTPC_OK;
+}
+
+// The clustering of the chunk in `as` (n events; rows written, and corrected if the drift correction is on) on S: the
+// rows and truth labels every later stage would read -> as.cl_labels, the labels the thinning, the estimates and the
+// fit read instead, and the chunk's records.
+int32_t enqueue_clustering(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
+  if (!n) return ATTPC_OK;
+  const size_t cap = std::max<size_t>(as.pk_cap, 1);
+  int32_t rc;
+  if ((rc = ensure(ctx, as.cl_labels, cap * sizeof(int64_t)))) return rc;
+  if ((rc = ensure(ctx, as.cl_events, (size_t)n * sizeof(attpc_cluster_event)))) return rc;
+  if ((rc = ensure(ctx, as.cl_records, (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_cluster_record)))) return rc;
+  if ((rc = ensure(ctx, ctx->cl_scratch, cap * CLUSTER_SCRATCH_WORDS * sizeof(int32_t)))) return rc;
+  ClusterArgs a{};
+  a.s = ctx->cluster_call;
+  a.ev_start = static_cast<const int64_t*>(as.pk_ev_start.p);
+  a.rows = static_cast<const double*>(ctx->correction_on ? as.uc_rows.p : as.sp_rows.p);  // (nullptr: no event has a row)
+  a.labels = static_cast<const int64_t*>(ctx->correction_on ? as.uc_labels.p : as.sp_labels.p);
+  a.scratch = static_cast<int32_t*>(ctx->cl_scratch.p);
+  a.out_labels = static_cast<int64_t*>(as.cl_labels.p);
+  a.events = static_cast<attpc_cluster_event*>(as.cl_events.p);
+  a.records = static_cast<attpc_cluster_record*>(as.cl_records.p);
+  launch_cluster(ctx->stream, n, a);
   HIP_TRY(ctx, hipGetLastError());
   return ATTPC_OK;
 }
@@ -1710,8 +1766,22 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->correction_on && (rc = enqueue_correction(ctx, as, n))) return rc;
   }
+  const bool clustered = ctx->cluster_call_events >= 0 && n > 0;
+  if (clustered && (rc = enqueue_clustering(ctx, as, n))) return rc;  // (an event without rows has a record too)
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
+  if (clustered) {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_events.p + first_local, as.cl_events.p, (size_t)n * sizeof(attpc_cluster_event),
+                                hipMemcpyDeviceToHost, ctx->stream_c));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_records.p + first_local * ATTPC_MAX_SIM, as.cl_records.p,
+                                (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_cluster_record), hipMemcpyDeviceToHost, ctx->stream_c));
+    if (ctx->cluster_call_rows >= 0 && fits && o.cloud->points) {
+      if (total > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_labels.p + base, as.cl_labels.p, (size_t)total * sizeof(int64_t),
+                                    hipMemcpyDeviceToHost, ctx->stream_c));
+      ctx->cluster_call_rows = base + total;
+    }
+  }
   if (total > 0 && fits) {
     const void* d_rows = ctx->correction_on ? as.uc_rows.p : as.sp_rows.p;
     const void* d_labels = ctx->correction_on ? as.uc_labels.p : as.sp_labels.p;
@@ -2227,6 +2297,9 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   if (makes_traces(o.mode) && (rc = reset_trace_sums(ctx, o.mode))) return rc;
   if (makes_traces(o.mode) && (rc = begin_trigger_call(ctx, n_events))) return rc;
   if (o.mode == OutMode::trace_rows && (rc = begin_estimate_call(ctx, n_events, &lay))) return rc;
+  if (o.mode == OutMode::trace_rows &&
+      (rc = begin_cluster_call(ctx, n_events, &lay, o.cloud && o.cloud->points ? o.cloud->capacity : -1)))
+    return rc;
   // a readout run sizes its trace chunks for |S| rows per event until it has seen its own rate: the rate of an earlier
   // run says nothing once the threshold, the noise or the workload has changed (hit mode keeps the context's rate)
   if (makes_traces(o.mode) && ctx->readout_mode != ATTPC_READOUT_HIT) ctx->trace_rows_per_event = 0.0;
@@ -3118,6 +3191,7 @@ int32_t host_cloud_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int6
   if ((rc = reset_trace_sums(ctx, o.mode))) return rc;
   if ((rc = begin_trigger_call(ctx, n))) return rc;
   if (o.mode == OutMode::trace_rows && (rc = begin_estimate_call(ctx, n, nullptr))) return rc;  // (no layout: no records)
+  if (o.mode == OutMode::trace_rows && (rc = begin_cluster_call(ctx, n, nullptr, -1))) return rc;  // (... and no clusters)
   const double keep = ctx->trace_rows_per_event;  // a host cloud says nothing about the configured workload
   rc = trace_host_events(ctx, o, 0, n, offsets, points, labels, seed, first_event);
   ctx->trace_rows_per_event = keep;
@@ -3909,6 +3983,85 @@ int32_t attpc_rows_estimate_helix(attpc_ctx* ctx, int64_t n_events, const int64_
                                   const attpc_circle_desc* circle, const attpc_helix_desc* helix, attpc_track_estimate* out) {
   if (!helix) return ATTPC_E_INVALID;
   return rows_estimate(ctx, __func__, n_events, offsets, rows, labels, layout, d, circle, out, helix);
+}
+
+// ---- clustering (cluster.hip, cluster_host.hpp; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_clustering(attpc_ctx* ctx, const attpc_cluster_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = cluster_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "clustering: %s", bad);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->cluster_on = d != nullptr;
+  if (d) ctx->cluster = *d;
+  return ATTPC_OK;
+}
+
+int32_t attpc_clusters_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_cluster_event* events,
+                            attpc_cluster_record* records) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->cluster_call_events < 0)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_clusters_last: the clustering was off for the last trace-row call");
+  if (const ArgError bad = records_range_error(__func__, first, count, ctx->cluster_call_events)) return refuse(ctx, bad);
+  if (count == 0) return ATTPC_OK;
+  if (events) std::memcpy(events, ctx->h_cl_events.p + (size_t)first, (size_t)count * sizeof(attpc_cluster_event));
+  if (records)
+    std::memcpy(records, ctx->h_cl_records.p + (size_t)first * ATTPC_MAX_SIM, (size_t)count * ATTPC_MAX_SIM * sizeof(attpc_cluster_record));
+  return ATTPC_OK;
+}
+
+int32_t attpc_cluster_labels_last(attpc_ctx* ctx, int64_t first_row, int64_t count, int64_t* out) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->cluster_call_events < 0 || ctx->cluster_call_rows < 0)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_cluster_labels_last: the last trace-row call made no cluster labels or did not fetch its rows");
+  if (first_row < 0 || count < 0 || first_row > ctx->cluster_call_rows || count > ctx->cluster_call_rows - first_row)
+    return fail(ctx, ATTPC_E_INVALID, "attpc_cluster_labels_last: rows %lld .. + %lld of %lld", (long long)first_row, (long long)count,
+                (long long)ctx->cluster_call_rows);
+  if (count == 0) return ATTPC_OK;
+  if (!out) return ATTPC_E_INVALID;
+  std::memcpy(out, ctx->h_cl_labels.p + (size_t)first_row, (size_t)count * sizeof(int64_t));
+  return ATTPC_OK;
+}
+
+int32_t attpc_rows_cluster(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                           const attpc_event_layout* layout, const attpc_cluster_desc* d, int64_t* out_labels,
+                           attpc_cluster_event* events, attpc_cluster_record* records) {
+  if (!ctx || n_events < 0 || !d || !layout) return ATTPC_E_INVALID;
+  if (const char* bad = cluster_layout_error(*layout)) return fail(ctx, ATTPC_E_INVALID, "%s: %s", __func__, bad);
+  if (const char* bad = cluster_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "clustering: %s", bad);
+  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
+  if (n_events > 0 && offsets[n_events] > offsets[0] && !rows) return ATTPC_E_INVALID;
+  for (int64_t e = 0; e < n_events; ++e)
+    if (offsets[e + 1] > offsets[e] && !cluster_rows_sorted(offsets[e + 1] - offsets[e], rows + offsets[e] * 8))
+      return fail(ctx, ATTPC_E_INVALID, "%s: the in-range rows of event %lld are not in nondecreasing z", __func__, (long long)e);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  if (n_events == 0) return ATTPC_OK;
+  ClusterArgs a{};
+  a.s = cluster_settings(*d, *layout);
+  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
+  std::vector<int64_t> start;
+  for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
+    e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
+    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
+    chunk_starts(offsets, e0, e1, &start);
+    a.ev_start = stage_in(ctx, 2, start.data(), m + 1, rc);
+    a.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
+    a.labels = labels ? stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1) : nullptr;
+    a.out_labels = stage<int64_t>(ctx, 3, cap, rc);
+    a.events = stage<attpc_cluster_event>(ctx, 4, m, rc);
+    a.records = stage<attpc_cluster_record>(ctx, 5, m * ATTPC_MAX_SIM, rc);
+    if (!rc) rc = ensure(ctx, ctx->cl_scratch, cap * CLUSTER_SCRATCH_WORDS * sizeof(int32_t));
+    if (rc) return rc;
+    a.scratch = static_cast<int32_t*>(ctx->cl_scratch.p);
+    launch_cluster(ctx->stream, (uint32_t)m, a);
+    HIP_TRY(ctx, hipGetLastError());
+    if (out_labels && n_rows && (rc = stage_out(ctx, out_labels + offsets[e0], a.out_labels, n_rows))) return rc;
+    if (events && (rc = stage_out(ctx, events + e0, a.events, m))) return rc;
+    if (records && (rc = stage_out(ctx, records + (size_t)e0 * ATTPC_MAX_SIM, a.records, m * ATTPC_MAX_SIM))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (before the staging is filled again)
+  }
+  return ATTPC_OK;
 }
 
 // ---- track fit (fit.hip; the contract is in include/attpc_engine.h) ----

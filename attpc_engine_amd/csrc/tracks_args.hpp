@@ -1,6 +1,7 @@
 // tracks_args.hpp -- kernel argument blocks and host launch wrappers (one per kernel file).
 #pragma once
 #include "common.hpp"
+#include "cluster_host.hpp"  // (behind the HIP runtime header)
 #include "distort_host.hpp"
 #include "undistort_host.hpp"
 #include "unpack_host.hpp"
@@ -350,6 +351,21 @@ struct UndistortArgs {
 };
 // one workgroup per event, empty events included (n_events > 0)
 void launch_undistort(hipStream_t s, uint32_t n_events, const UndistortArgs& a);
+
+// clustering of trace rows (cluster.hip; attpc_trace_configure_clustering, the contract is in include/attpc_engine.h)
+constexpr size_t CLUSTER_SCRATCH_WORDS = 25;  // 32-bit words of scratch per row (cluster.hip lists them)
+struct ClusterArgs {
+  ClusterSettings s;
+  const int64_t* ev_start;          // [n_events + 1] CSR offsets of the events' rows
+  const double* rows;               // [rows][8]
+  const int64_t* labels;            // [rows] the truth labels, or nullptr: nobody votes
+  int32_t* scratch;                 // [rows][CLUSTER_SCRATCH_WORDS]
+  int64_t* out_labels;              // [rows] the cluster labels
+  attpc_cluster_event* events;      // [n_events] or nullptr
+  attpc_cluster_record* records;    // [n_events][ATTPC_MAX_SIM] or nullptr
+};
+// one workgroup per event, empty events included (n_events > 0)
+void launch_cluster(hipStream_t s, uint32_t n_events, const ClusterArgs& a);
 
 // packed pad traces (trace_pack.hip; the format "for64-bitplane-v1" is in include/attpc_engine.h).  samples
 // [n_rows][512] as the trace write pass left them, n_rows > 0; `workgroups` = trace_pack_workgroups(n_rows, limit).

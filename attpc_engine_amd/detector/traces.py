@@ -244,6 +244,12 @@ def _checked_fit(fit):
     return _checked(fit)
 
 
+def _checked_clustering(clustering):
+    from .clustering import _checked
+
+    return _checked(clustering)
+
+
 def _checked_helix(helix):
     from .helix import _checked
 
@@ -416,12 +422,14 @@ class TraceChain:
     estimates: a ``detector.thinning.ThinSettings``), ``circle`` (the geometric circle fit behind them: a
     ``detector.circle.CircleFitSettings``), ``helix`` (the helix slope behind the circle: a
     ``detector.helix.HelixSlopeSettings``) and ``correction`` (trace rows: the drift correction of the rows, in front
-    of the thinning, the estimates and the delivery: a ``detector.correction.CorrectionSettings``) and ``fit`` (the
-    track fit behind the estimates: a ``detector.fit.TrackFitSettings``)."""
+    of the thinning, the estimates and the delivery: a ``detector.correction.CorrectionSettings``), ``fit`` (the
+    track fit behind the estimates: a ``detector.fit.TrackFitSettings``) and ``clustering`` (trace rows: the cluster
+    labels the thinning, the estimates and the fit match in place of the truth labels: a
+    ``detector.clustering.ClusterSettings``)."""
 
     def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
                  gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
-                 thinning=None, circle=None, helix=None, correction=None, fit=None):
+                 thinning=None, circle=None, helix=None, correction=None, fit=None, clustering=None):
         self.config, self._given = config, (response, threshold)
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
@@ -432,6 +440,7 @@ class TraceChain:
         self.helix = _checked_helix(helix)
         self.correction = _checked_correction(correction)
         self.fit = _checked_fit(fit)
+        self.clustering = _checked_clustering(clustering)
 
     @classmethod
     def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
@@ -447,10 +456,10 @@ class TraceChain:
 
     def replace(self, **fields) -> "TraceChain":
         """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning,
-        circle, helix, correction, fit; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction", "fit"}
+        circle, helix, correction, fit, clustering; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction", "fit", "clustering"}
         if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix, correction and fit, not {sorted(unknown)}")
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix, correction, fit and clustering, not {sorted(unknown)}")
         chain = copy.copy(self)
         vars(chain).update(fields)
         if "config" in fields:
@@ -463,14 +472,15 @@ class TraceChain:
         _checked_helix(chain.helix)
         _checked_correction(chain.correction)
         _checked_fit(chain.fit)
+        _checked_clustering(chain.clustering)
         return chain
 
     def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
         """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
         trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
-        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them, the helix slope behind that and the track fit behind the estimates.  A stage that is
+        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them, the helix slope behind that and the track fit behind the estimates, and the clustering in front of them all.  A stage that is
         off is turned off, whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode"
-        "estimates" (the thinning, the circle fit, the helix slope and the track fit with them) and "correction" that ``keep`` names, which stay as the ctx holds them."""
+        "estimates" (the thinning, the circle fit, the helix slope and the track fit with them) "correction" and "clustering" that ``keep`` names, which stay as the ctx holds them."""
         from .simulator import configure_spyral
 
         ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
@@ -491,6 +501,10 @@ class TraceChain:
             from .correction import configure_correction
 
             configure_correction(ctx, self.correction, self.config)
+        if rows and "clustering" not in keep:
+            from .clustering import configure_clustering
+
+            configure_clustering(ctx, self.clustering)
         if rows and "estimates" not in keep:
             from .circle import configure_circle
             from .estimate import configure_estimates
@@ -548,6 +562,9 @@ class TraceChain:
             from .fit import fit_result
 
             extra.update(fit_result(ctx, len(arrays.offsets) - 1, len(indices)))
+            from .clustering import clustering_result
+
+            extra.update(clustering_result(ctx, len(arrays.offsets) - 1, int(arrays.offsets[-1])))
         sums = ctx.trace_rows_last() if rows else arrays.sums()
         return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
 
@@ -1031,19 +1048,24 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
                          baseline: BaselineSettings | None = None, gain: GainSettings | None = None,
                          common_mode: CommonModeSettings | None = None, thinning=None, circle=None, helix=None,
-                         correction=None, **trace_kwargs) -> None:
+                         correction=None, clustering=None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
     the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
     baseline (default None: off, the peaks stand on the configured pedestals), the micromegas gain and the common-mode
     noise (default None: off).  The trigger, the track estimates, the thinning, the circle fit and the helix slope stay
     as the ctx holds them; a ``thinning`` (a ``detector.thinning.ThinSettings``), a ``circle`` (a
     ``detector.circle.CircleFitSettings``) or a ``helix`` (a ``detector.helix.HelixSlopeSettings``) is configured, None
-    leaves what the ctx holds; so does ``correction`` (the drift correction of the rows, a
-    ``detector.correction.CorrectionSettings``)."""
+    leaves what the ctx holds; so do ``correction`` (the drift correction of the rows, a
+    ``detector.correction.CorrectionSettings``) and ``clustering`` (the cluster labels in place of the truth labels, a
+    ``detector.clustering.ClusterSettings``)."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
                                                                    common_mode=common_mode, thinning=thinning, circle=circle,
-                                                                   helix=helix, correction=correction)
-    chain.configure(ctx, rows=True, keep=("trigger", "estimates", "correction"))
+                                                                   helix=helix, correction=correction, clustering=clustering)
+    chain.configure(ctx, rows=True, keep=("trigger", "estimates", "correction", "clustering"))
+    if clustering is not None:
+        from .clustering import configure_clustering
+
+        configure_clustering(ctx, chain.clustering)
     if correction is not None:
         from .correction import configure_correction
 
@@ -1068,7 +1090,7 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
                               estimates=None, thinning=None, straggling=None, circle=None, helix=None,
-                              distortion=None, correction=None, fit=None, **trace_kwargs):
+                              distortion=None, correction=None, fit=None, clustering=None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -1084,11 +1106,14 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     ``correction`` (a ``detector.correction.CorrectionSettings``; None = off) the rows and labels are the drift-corrected
     ones, per event in ascending corrected z, the estimates are made of them, and the stage's counts come under
     ``"correction"``.  With ``fit`` (a ``detector.fit.TrackFitSettings``; None = off) and ``estimates`` the track fits
-    [n, len(indices)] come under ``"fits"``."""
+    [n, len(indices)] come under ``"fits"``.  With ``clustering`` (a ``detector.clustering.ClusterSettings``; None = off)
+    the thinning, the estimates and the fit match the cluster labels in place of the truth labels; the labels returned
+    stay the truth labels, the cluster labels [P] come under ``"cluster_labels"`` and the event and cluster records
+    under ``"clusters"``."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
                                                                    thinning=thinning, circle=circle, helix=helix,
-                                                                   correction=correction, fit=fit)
+                                                                   correction=correction, fit=fit, clustering=clustering)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event, straggling=straggling, distortion=distortion)
 

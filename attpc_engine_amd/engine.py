@@ -20,6 +20,7 @@ from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings
 from .detector.estimate import EstimateSettings, configure_estimates, estimates_result
 from .detector.circle import CircleFitSettings, circle_result, configure_circle
 from .detector.fit import TrackFitSettings, configure_track_fit, fit_result
+from .detector.clustering import ClusterSettings, clustering_result, configure_clustering
 from .detector.helix import HelixSlopeSettings, configure_helix, helix_result
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .detector.straggling import StragglingSettings, configure_straggling
@@ -320,13 +321,15 @@ class Engine:
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                     **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
-                    **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices))}
+                    **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices)),
+                    **clustering_result(ctx, n_events)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                 **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
-                    **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices))}
+                    **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices)),
+                    **clustering_result(ctx, n_events, int(arrays.offsets[-1]))}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -371,6 +374,17 @@ class Engine:
         default).  Without the estimates it does nothing.  The writers do not store the records."""
         configure_track_fit(self.ctx, _settings(TrackFitSettings, settings, parameters))
 
+    def configure_clustering(self, settings=None, **parameters) -> None:
+        """The clustering of the trace rows (include/attpc_engine.h, "clustering"): a
+        ``detector.clustering.ClusterSettings`` or its keywords (eps_xy, eps_z, min_samples, min_cluster_size, max_rows,
+        match) turn it on -- every chunk of ``run_trace_rows`` / ``run_estimates`` is clustered on the device behind the
+        drift correction, and the thinning, the estimates and the track fit match the cluster labels in place of the
+        truth labels; the results carry ``clusters`` = (events [n] ``CLUSTER_EVENT_DTYPE``, records [n, 8]
+        ``CLUSTER_DTYPE``) and, where the rows are fetched, ``cluster_labels``; ``labels`` stay the truth labels --,
+        neither turns it off (the default).  DBSCAN with definite ties, not Spyral's HDBSCAN sequence.  The writers do not
+        store the records."""
+        configure_clustering(self.ctx, _settings(ClusterSettings, settings, parameters))
+
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
         128 bytes per track cross PCIe (``estimates`` [n, n_sim], ``detector.estimate.ESTIMATE_DTYPE``), beside the
@@ -392,7 +406,7 @@ class Engine:
                 "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
                 "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx),
                 **circle_result(ctx), **helix_result(ctx), **correction_result(ctx),
-                **fit_result(ctx, n_events, len(self.indices))}
+                **fit_result(ctx, n_events, len(self.indices)), **clustering_result(ctx, n_events)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

@@ -1829,6 +1829,133 @@ ATTPC_API int32_t attpc_rows_fit(attpc_ctx* ctx, int64_t n_events, const int64_t
                                  const attpc_estimate_desc* estimate_desc, const attpc_track_estimate* estimates_in,
                                  const double* start, const attpc_fit_desc* fit_desc, attpc_track_fit* out);
 
+/* ---- clustering (opt-in: off by default, and with it off every output, kernel and buffer of every entry point is
+ * what it is without this section; the entry points are additions under ABI version 3) ----
+ * Every stage above selects "the rows of a track" by the truth label the simulation gave the row.  This stage splits an
+ * event's rows into tracks without it: it sits behind the drift correction (when that is on) and in front of the
+ * thinning, the estimates, the circle fit, the helix slope and the track fit, reads a chunk's rows where they lie and
+ * writes one CLUSTER LABEL per row, which those stages then read in place of the truth label.  The delivered labels
+ * stay the truth labels; the cluster labels and the records below are additional outputs.
+ *
+ * The algorithm is DBSCAN with every tie made definite.  It is NOT Spyral's sequence of HDBSCAN, cluster joining by
+ * circle overlap and outlier-factor cleanup, and nothing here has been compared against Spyral.  The arithmetic is
+ * integer throughout, so a result is a pure function of the event's rows and the settings: no dependence on event id,
+ * chunking, shard or the order in which the device happens to work.  tests/cluster_reference.py restates this contract
+ * in numpy by brute force; csrc/cluster_host.hpp holds the metric and a plain sequential form, shared with the host.
+ *
+ * Settings (attpc_cluster_desc): eps_xy and eps_z, the linking lengths in mm, each finite and in 1/16 .. 64, as
+ * Exy = rint(16 eps_xy) and Ez = rint(16 eps_z), integers in 1 .. 1024; min_samples >= 1, the neighbours a core row
+ * needs, itself included; min_cluster_size >= 1, the rows a cluster needs to survive; max_rows in 1 .. 65535, the rows
+ * of an event above which it is not clustered; match, ATTPC_CLUSTER_MATCH_TRUTH or ATTPC_CLUSTER_MATCH_RANK; the
+ * reserved words 0.
+ *
+ * One event, on its n rows in delivered order, row index i = 0 .. n-1 (rows [n][8] in ascending z, truth labels [n]):
+ *  1. Quantise: estimate_quantise of "track estimates" on columns 0, 1, 2 and 4 -- the same code -- gives X, Y, Z in
+ *     units of 1/16 mm.  A row out of its range (a NaN, or the skipped rows the drift correction leaves behind the
+ *     others) is noise and counts in n_range.  The in-range rows stand in nondecreasing Z.
+ *  2. Metric: d(i, j) = (dX^2 + dY^2) Ez^2 + dZ^2 Exy^2 in int64.  j is a NEIGHBOUR of i iff |dZ| <= Ez and
+ *     d <= Exy^2 Ez^2 (an ellipsoid with the half axes eps_xy, eps_xy, eps_z, its surface included); i is its own
+ *     neighbour.  Bounds: |dX|, |dY| <= 10 240 and Ez^2 <= 2^20 give (dX^2 + dY^2) Ez^2 < 2^48, |dZ| <= Ez gives
+ *     dZ^2 Exy^2 <= 2^40, so d < 2^49 and the threshold is <= 2^40: nothing overflows 64 bits.
+ *  3. Core: row i is CORE iff it has at least min_samples neighbours.
+ *  4. Cluster: a connected component of the core rows under "is a neighbour of"; its id is the lowest row index among
+ *     its core rows.
+ *  5. Border: an in-range row that is not core and has a core neighbour joins the cluster of the core neighbour with
+ *     the smallest d, ties to the lowest row index.  Every other row is noise.
+ *  6. Size cut: a cluster of fewer than min_cluster_size rows (core and border) is dissolved into noise (n_small).
+ *  7. Rank: the surviving clusters by rows descending, ties by id ascending.
+ *  8. Labels, values of layout->indices or -1 (what thinning, estimates and fit then match against):
+ *     MATCH_RANK: the cluster of rank k < n_sim gets indices[k], every other -1.  This is the label-free mode; with
+ *       the track fit on, a slot's species is then the position's, not the particle's.  n_split = n_fake = 0.
+ *     MATCH_TRUTH: a row VOTES for the lowest position s < n_sim with indices[s] == its truth label (a row whose label
+ *       is negative or not among indices votes for nobody).  A cluster's MAJORITY is the position with the most votes,
+ *       ties to the lower s; without a vote it has none (-1).  For every position the best-ranked cluster with that
+ *       majority gets indices[s]; every other cluster gets -1 and counts in n_split if it had a majority, in n_fake
+ *       (made of noise) if it had none.  This stands in for the particle-identification gate an analysis applies, and
+ *       it makes estimates[e, s] and fits[e, s] directly comparable with those of the truth-labelled run.
+ *     The majority is formed in both modes (the records carry it).
+ *  9. Cap: an event of more than max_rows rows is not clustered: every row gets -1 and status carries CAPPED.
+ * An event whose components the device could not settle within the bound every one of its loops has (a defect, never
+ * seen) is labelled -1 throughout with INTERNAL in status.  In both cases the record holds n_rows, n_noise = n_rows,
+ * truth_rows and status, every other field 0, and the event has no cluster records.
+ *
+ * attpc_cluster_event: n_rows; n_range (step 1); n_core and n_border, the core and border rows of the surviving
+ * clusters; n_noise = n_rows - n_core - n_border; n_clusters, the surviving clusters; n_small (step 6); n_split and
+ * n_fake (step 8); status; truth_rows[s], the event's rows that vote for position s (all rows, in range or not),
+ * saturating at 65535 -- which only a CAPPED event can reach.
+ * attpc_cluster_record [n_events][ATTPC_MAX_SIM], the clusters of rank 0 .. 7: rows; core_rows; first_row, the id;
+ * majority, the position or -1; majority_rows, its votes (0 without one); label, what step 8 gave (or -1); z_min and
+ * z_max of its rows in units.  An unused slot is zero with first_row = -1.  Every field is a count, a minimum or a
+ * maximum: nothing depends on an order of accumulation. */
+#define ATTPC_CLUSTER_MATCH_TRUTH 0
+#define ATTPC_CLUSTER_MATCH_RANK 1
+#define ATTPC_CLUSTER_CAPPED 1    /* status: more than max_rows rows */
+#define ATTPC_CLUSTER_INTERNAL 2  /* status: a loop of the kernel met its bound */
+#define ATTPC_CLUSTER_DEFAULT_MAX_ROWS 16384
+
+typedef struct attpc_cluster_desc {
+  double eps_xy;             /* mm, 1/16 .. 64 */
+  double eps_z;              /* mm, 1/16 .. 64 */
+  int32_t min_samples;       /* >= 1 */
+  int32_t min_cluster_size;  /* >= 1 */
+  int32_t max_rows;          /* 1 .. 65535 */
+  int32_t match;             /* ATTPC_CLUSTER_MATCH_* */
+  int32_t reserved[2];       /* 0 */
+} attpc_cluster_desc;  /* 40 bytes */
+
+typedef struct attpc_cluster_event {
+  int32_t n_rows;
+  int32_t n_range;
+  int32_t n_core;
+  int32_t n_border;
+  int32_t n_noise;
+  int32_t n_clusters;
+  int32_t n_small;
+  int32_t n_split;
+  int32_t n_fake;
+  int32_t status;       /* ATTPC_CLUSTER_CAPPED, ATTPC_CLUSTER_INTERNAL */
+  int32_t reserved[2];  /* 0 */
+  uint16_t truth_rows[ATTPC_MAX_SIM];
+} attpc_cluster_event;  /* 64 bytes */
+
+typedef struct attpc_cluster_record {
+  int32_t rows;
+  int32_t core_rows;
+  int32_t first_row;      /* the id; -1: the slot is unused */
+  int32_t majority;       /* position, -1: none */
+  int32_t majority_rows;
+  int32_t label;          /* a value of layout->indices, or -1 */
+  int32_t z_min;          /* units of 1/16 mm */
+  int32_t z_max;
+} attpc_cluster_record;  /* 32 bytes */
+
+/* desc == NULL turns the stage off (the default): no kernel is launched and no buffer is held then.  ATTPC_E_INVALID
+ * for anything the section above rules out, a NaN included.  Independent of every other configure call.  With the
+ * stage on attpc_sim_run_trace_rows and attpc_det_run_trace_rows cluster every chunk behind the drift correction, also
+ * when the rows stay on the device, and the thinning, the estimates and the fit match the cluster labels; rows, truth
+ * labels, offsets and checksums are delivered as without it.  The stage needs a layout, so attpc_trace_rows_at does not
+ * run it.  Behind a trigger gate an event that did not fire has no rows and a record of zeros.  It holds 108 bytes of
+ * device memory per row of a chunk. */
+ATTPC_API int32_t attpc_trace_configure_clustering(attpc_ctx* ctx, const attpc_cluster_desc* desc);
+/* The records of events first .. first + count - 1 of the context's last trace-row call: events [count] and records
+ * [count][ATTPC_MAX_SIM], either may be NULL.  ATTPC_E_NOTCONFIGURED if the stage was off for that call (or it had no
+ * layout), ATTPC_E_INVALID for a range outside it. */
+ATTPC_API int32_t attpc_clusters_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_cluster_event* events,
+                                      attpc_cluster_record* records);
+/* The cluster labels of rows first_row .. first_row + count - 1 of that call, indexed as its delivered rows are, from a
+ * buffer the context owns.  It is filled only when the call fetched the rows themselves: ATTPC_E_NOTCONFIGURED
+ * otherwise, ATTPC_E_INVALID for a range outside the delivered rows. */
+ATTPC_API int32_t attpc_cluster_labels_last(attpc_ctx* ctx, int64_t first_row, int64_t count, int64_t* out);
+/* The stage alone on any host rows in CSR form, through the same kernel: offsets [n_events + 1], rows [R][8], labels
+ * [R] the truth labels or NULL (then nobody votes) -> out_labels [R], events [n_events] and records
+ * [n_events][ATTPC_MAX_SIM] (each of the three may be NULL).  n_sim and indices of the layout are read.  The in-range
+ * rows of every event must stand in nondecreasing Z, which is checked on the host: ATTPC_E_INVALID otherwise.  Needs no
+ * other configure call and leaves the configured stage as it is.  An event holds fewer than 2^31 rows. */
+ATTPC_API int32_t attpc_rows_cluster(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                     const int64_t* labels, const attpc_event_layout* layout,
+                                     const attpc_cluster_desc* desc, int64_t* out_labels, attpc_cluster_event* events,
+                                     attpc_cluster_record* records);
+
 #ifdef __cplusplus
 }
 #endif
