@@ -257,6 +257,32 @@ CLUSTER_CAPPED, CLUSTER_INTERNAL = 1, 2
 CLUSTER_DEFAULT_MAX_ROWS, CLUSTER_MAX_ROWS_LIMIT = 16384, 65535
 
 
+class JoinDesc(C.Structure):  # attpc_join_desc
+    _fields_ = [("overlap_ratio", C.c_double), ("min_radius", C.c_double), ("radius_ratio", C.c_double),
+                ("max_clusters", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class JoinEvent(C.Structure):  # attpc_join_event
+    _fields_ = [("n_candidates", C.c_int32), ("n_circles", C.c_int32), ("n_taking_part", C.c_int32), ("n_pairs", C.c_int32),
+                ("n_joined", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class JoinRecord(C.Structure):  # attpc_join_record
+    _fields_ = [("parts", C.c_int32), ("first_row", C.c_int32), ("a", C.c_double), ("b", C.c_double), ("radius", C.c_double)]
+
+
+# the join records as numpy structured dtypes: itemsize and field offsets are those of include/attpc_engine.h
+JOIN_EVENT_DTYPE = np.dtype([("n_candidates", "<i4"), ("n_circles", "<i4"), ("n_taking_part", "<i4"), ("n_pairs", "<i4"),
+                             ("n_joined", "<i4"), ("status", "<i4"), ("reserved", "<i4", (2,))], align=True)
+JOIN_DTYPE = np.dtype([("parts", "<i4"), ("first_row", "<i4"), ("a", "<f8"), ("b", "<f8"), ("radius", "<f8")], align=True)
+assert C.sizeof(JoinDesc) == 40 and JOIN_EVENT_DTYPE.itemsize == C.sizeof(JoinEvent) == 32
+assert JOIN_DTYPE.itemsize == C.sizeof(JoinRecord) == 32
+assert all(JOIN_DTYPE.fields[name][1] == getattr(JoinRecord, name).offset for name, _ in JoinRecord._fields_)
+# ATTPC_JOIN_*: the bits of JoinEvent.status and the limit of max_clusters
+JOIN_CAPPED, JOIN_NOT_CLUSTERED = 1, 2
+JOIN_MAX_CLUSTERS = 64
+
+
 class ThinDesc(C.Structure):
     _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
 
@@ -500,6 +526,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_correction", "attpc_correction_last", "attpc_rows_undistort",
     "attpc_trace_configure_fit", "attpc_fits_last", "attpc_rows_fit",
     "attpc_trace_configure_clustering", "attpc_clusters_last", "attpc_cluster_labels_last", "attpc_rows_cluster",
+    "attpc_trace_configure_cluster_join", "attpc_joins_last", "attpc_rows_cluster_join",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -559,6 +586,9 @@ FIT_SYMBOLS = ("attpc_trace_configure_fit", "attpc_fits_last", "attpc_rows_fit")
 
 # ... and the clustering after the track fit: the same rule.
 CLUSTER_SYMBOLS = ("attpc_trace_configure_clustering", "attpc_clusters_last", "attpc_cluster_labels_last", "attpc_rows_cluster")
+
+# ... and the cluster joining after the clustering: the same rule.
+JOIN_SYMBOLS = ("attpc_trace_configure_cluster_join", "attpc_joins_last", "attpc_rows_cluster_join")
 
 _lib = None
 
@@ -804,6 +834,17 @@ def load_library() -> C.CDLL:
     for name, argtypes in clustering.items():
         if not no_clustering:
             getattr(lib, name).argtypes = argtypes
+    joining = {
+        "attpc_trace_configure_cluster_join": [ctxp, C.POINTER(JoinDesc)],
+        "attpc_joins_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(JoinEvent), C.POINTER(JoinRecord)],
+        "attpc_rows_cluster_join": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(ClusterDesc),
+                                    C.POINTER(JoinDesc), i64p, C.POINTER(ClusterEvent), C.POINTER(ClusterRecord),
+                                    C.POINTER(JoinEvent), C.POINTER(JoinRecord)],
+    }
+    no_joining = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in JOIN_SYMBOLS)
+    for name, argtypes in joining.items():
+        if not no_joining:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -832,7 +873,8 @@ def load_library() -> C.CDLL:
                 or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)
                 or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)
                 or (no_distortion and name in DISTORT_SYMBOLS) or (no_correction and name in UNDISTORT_SYMBOLS)
-                or (no_fit and name in FIT_SYMBOLS) or (no_clustering and name in CLUSTER_SYMBOLS)):
+                or (no_fit and name in FIT_SYMBOLS) or (no_clustering and name in CLUSTER_SYMBOLS)
+                or (no_joining and name in JOIN_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -842,7 +884,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit", "clustering")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit", "clustering", "cluster_join")
 
 
 class Context:

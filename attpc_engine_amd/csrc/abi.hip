@@ -116,6 +116,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf uc_rows, uc_labels;   // drift correction on (undistort.hip): the chunk's corrected, re-sorted rows and labels (pk_cap)
   DevBuf cl_labels;            // clustering on (cluster.hip): the chunk's cluster labels (pk_cap),
   DevBuf cl_events, cl_records;  // ... its attpc_cluster_event [events] and attpc_cluster_record [events][ATTPC_MAX_SIM]
+  DevBuf jn_events, jn_records;  // cluster joining on (cluster_join.hip): attpc_join_event [events], attpc_join_record [events][ATTPC_MAX_SIM]
   Pinned<int64_t> h_pk_start;  // CSR offsets of the chunk's points by event (n + 1 entries)
   // packed traces (trace_pack.hip): the headers and record sizes of every kept trace row, their scanned byte offsets
   // (tp_block_*: the scan's scratch) and the records; the chunk's bytes in pinned memory (the host waits on `counted`)
@@ -307,6 +308,12 @@ struct attpc_ctx {
   Pinned<attpc_cluster_record> h_cl_records;
   Pinned<int64_t> h_cl_labels;     // attpc_cluster_labels_last: the cluster labels of the call's delivered rows,
   int64_t cluster_call_rows = -1;  // ... how many (-1: the call did not fetch its rows)
+  bool join_on = false;            // attpc_trace_configure_cluster_join
+  attpc_join_desc join{};
+  bool join_call = false;          // attpc_joins_last: the last trace-row call joined its clusters (cluster_call_events of them)
+  JoinSettings join_call_settings{};  // ... with these settings
+  Pinned<attpc_join_event> h_jn_events;    // ... and its join records, as h_cl_events
+  Pinned<attpc_join_record> h_jn_records;
   int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
   uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
@@ -1283,8 +1290,15 @@ int32_t enqueue_correction(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
 int32_t begin_cluster_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay, int64_t row_capacity) {
   ctx->cluster_call_events = -1;
   ctx->cluster_call_rows = -1;
+  ctx->join_call = false;
   if (!ctx->cluster_on || !lay) return ATTPC_OK;
   int32_t rc;
+  if (ctx->join_on) {  // (the joining does nothing without the clustering)
+    if ((rc = ensure_pinned(ctx, ctx->h_jn_events, std::max<size_t>((size_t)n, 1)))) return rc;
+    if ((rc = ensure_pinned(ctx, ctx->h_jn_records, std::max<size_t>((size_t)n * ATTPC_MAX_SIM, 1)))) return rc;
+    ctx->join_call_settings = join_settings(ctx->join);
+    ctx->join_call = true;
+  }
   if ((rc = ensure_pinned(ctx, ctx->h_cl_events, std::max<size_t>((size_t)n, 1)))) return rc;
   if ((rc = ensure_pinned(ctx, ctx->h_cl_records, std::max<size_t>((size_t)n * ATTPC_MAX_SIM, 1)))) return rc;
   if (row_capacity >= 0) {
@@ -1318,6 +1332,17 @@ int32_t enqueue_clustering(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
   a.records = static_cast<attpc_cluster_record*>(as.cl_records.p);
   launch_cluster(ctx->stream, n, a);
   HIP_TRY(ctx, hipGetLastError());
+  if (ctx->join_call) {  // right behind the clustering on S: it reads the scratch that kernel left
+    if ((rc = ensure(ctx, as.jn_events, (size_t)n * sizeof(attpc_join_event)))) return rc;
+    if ((rc = ensure(ctx, as.jn_records, (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_join_record)))) return rc;
+    ClusterJoinArgs j{};
+    j.c = a;
+    j.j = ctx->join_call_settings;
+    j.join_events = static_cast<attpc_join_event*>(as.jn_events.p);
+    j.join_records = static_cast<attpc_join_record*>(as.jn_records.p);
+    launch_cluster_join(ctx->stream, n, j);
+    HIP_TRY(ctx, hipGetLastError());
+  }
   return ATTPC_OK;
 }
 
@@ -1775,6 +1800,12 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
                                 hipMemcpyDeviceToHost, ctx->stream_c));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_records.p + first_local * ATTPC_MAX_SIM, as.cl_records.p,
                                 (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_cluster_record), hipMemcpyDeviceToHost, ctx->stream_c));
+    if (ctx->join_call) {
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_jn_events.p + first_local, as.jn_events.p, (size_t)n * sizeof(attpc_join_event),
+                                  hipMemcpyDeviceToHost, ctx->stream_c));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_jn_records.p + first_local * ATTPC_MAX_SIM, as.jn_records.p,
+                                  (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_join_record), hipMemcpyDeviceToHost, ctx->stream_c));
+    }
     if (ctx->cluster_call_rows >= 0 && fits && o.cloud->points) {
       if (total > 0)
         HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_labels.p + base, as.cl_labels.p, (size_t)total * sizeof(int64_t),
@@ -4022,17 +4053,23 @@ int32_t attpc_cluster_labels_last(attpc_ctx* ctx, int64_t first_row, int64_t cou
   return ATTPC_OK;
 }
 
-int32_t attpc_rows_cluster(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
-                           const attpc_event_layout* layout, const attpc_cluster_desc* d, int64_t* out_labels,
-                           attpc_cluster_event* events, attpc_cluster_record* records) {
+namespace {
+
+// attpc_rows_cluster (jd == nullptr) and attpc_rows_cluster_join
+int32_t rows_cluster(attpc_ctx* ctx, const char* func, int64_t n_events, const int64_t* offsets, const double* rows,
+                     const int64_t* labels, const attpc_event_layout* layout, const attpc_cluster_desc* d,
+                     const attpc_join_desc* jd, int64_t* out_labels, attpc_cluster_event* events, attpc_cluster_record* records,
+                     attpc_join_event* join_events, attpc_join_record* join_records) {
   if (!ctx || n_events < 0 || !d || !layout) return ATTPC_E_INVALID;
-  if (const char* bad = cluster_layout_error(*layout)) return fail(ctx, ATTPC_E_INVALID, "%s: %s", __func__, bad);
+  if (const char* bad = cluster_layout_error(*layout)) return fail(ctx, ATTPC_E_INVALID, "%s: %s", func, bad);
   if (const char* bad = cluster_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "clustering: %s", bad);
-  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
+  if (jd)
+    if (const char* bad = join_desc_error(*jd)) return fail(ctx, ATTPC_E_INVALID, "cluster joining: %s", bad);
+  if (const ArgError bad = csr_error(func, n_events, offsets)) return refuse(ctx, bad);
   if (n_events > 0 && offsets[n_events] > offsets[0] && !rows) return ATTPC_E_INVALID;
   for (int64_t e = 0; e < n_events; ++e)
     if (offsets[e + 1] > offsets[e] && !cluster_rows_sorted(offsets[e + 1] - offsets[e], rows + offsets[e] * 8))
-      return fail(ctx, ATTPC_E_INVALID, "%s: the in-range rows of event %lld are not in nondecreasing z", __func__, (long long)e);
+      return fail(ctx, ATTPC_E_INVALID, "%s: the in-range rows of event %lld are not in nondecreasing z", func, (long long)e);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc;
   if ((rc = sync_all(ctx))) return rc;
@@ -4056,12 +4093,64 @@ int32_t attpc_rows_cluster(attpc_ctx* ctx, int64_t n_events, const int64_t* offs
     a.scratch = static_cast<int32_t*>(ctx->cl_scratch.p);
     launch_cluster(ctx->stream, (uint32_t)m, a);
     HIP_TRY(ctx, hipGetLastError());
+    if (jd) {
+      ClusterJoinArgs j{};
+      j.c = a;
+      j.j = join_settings(*jd);
+      j.join_events = stage<attpc_join_event>(ctx, 6, m, rc);
+      j.join_records = stage<attpc_join_record>(ctx, 7, m * ATTPC_MAX_SIM, rc);
+      if (rc) return rc;
+      launch_cluster_join(ctx->stream, (uint32_t)m, j);
+      HIP_TRY(ctx, hipGetLastError());
+      if (join_events && (rc = stage_out(ctx, join_events + e0, j.join_events, m))) return rc;
+      if (join_records && (rc = stage_out(ctx, join_records + (size_t)e0 * ATTPC_MAX_SIM, j.join_records, m * ATTPC_MAX_SIM))) return rc;
+    }
     if (out_labels && n_rows && (rc = stage_out(ctx, out_labels + offsets[e0], a.out_labels, n_rows))) return rc;
     if (events && (rc = stage_out(ctx, events + e0, a.events, m))) return rc;
     if (records && (rc = stage_out(ctx, records + (size_t)e0 * ATTPC_MAX_SIM, a.records, m * ATTPC_MAX_SIM))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (before the staging is filled again)
   }
   return ATTPC_OK;
+}
+
+}  // namespace
+
+int32_t attpc_rows_cluster(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                           const attpc_event_layout* layout, const attpc_cluster_desc* d, int64_t* out_labels,
+                           attpc_cluster_event* events, attpc_cluster_record* records) {
+  return rows_cluster(ctx, __func__, n_events, offsets, rows, labels, layout, d, nullptr, out_labels, events, records, nullptr, nullptr);
+}
+
+// ---- cluster joining (cluster_join.hip, join_host.hpp; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_cluster_join(attpc_ctx* ctx, const attpc_join_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = join_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "cluster joining: %s", bad);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->join_on = d != nullptr;
+  if (d) ctx->join = *d;
+  return ATTPC_OK;
+}
+
+int32_t attpc_joins_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_join_event* events, attpc_join_record* records) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->cluster_call_events < 0 || !ctx->join_call)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_joins_last: the cluster joining or the clustering was off for the last trace-row call");
+  if (const ArgError bad = records_range_error(__func__, first, count, ctx->cluster_call_events)) return refuse(ctx, bad);
+  if (count == 0) return ATTPC_OK;
+  if (events) std::memcpy(events, ctx->h_jn_events.p + (size_t)first, (size_t)count * sizeof(attpc_join_event));
+  if (records)
+    std::memcpy(records, ctx->h_jn_records.p + (size_t)first * ATTPC_MAX_SIM, (size_t)count * ATTPC_MAX_SIM * sizeof(attpc_join_record));
+  return ATTPC_OK;
+}
+
+int32_t attpc_rows_cluster_join(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                                const attpc_event_layout* layout, const attpc_cluster_desc* d, const attpc_join_desc* jd,
+                                int64_t* out_labels, attpc_cluster_event* events, attpc_cluster_record* records,
+                                attpc_join_event* join_events, attpc_join_record* join_records) {
+  if (!jd) return ATTPC_E_INVALID;
+  return rows_cluster(ctx, __func__, n_events, offsets, rows, labels, layout, d, jd, out_labels, events, records, join_events,
+                      join_records);
 }
 
 // ---- track fit (fit.hip; the contract is in include/attpc_engine.h) ----

@@ -146,10 +146,23 @@ inline bool cluster_rows_sorted(int64_t n, const double* rows) {
   return true;
 }
 
+// a cluster of the sequential form: the id is a row index
+struct HostCluster { uint32_t id, rows, core_rows, votes[ATTPC_MAX_SIM], majority_rows; int32_t majority, label, z_min, z_max; };
+
+// What may stand between step 6 and step 7 of the sequential form (join_host.hpp, "cluster joining"): it sees the
+// surviving clusters, the rows in units and the cluster id of every row (CLUSTER_NONE: none), and may replace the
+// clusters and move rows from one id to another.
+struct ClusterHostHook {
+  virtual void between_6_and_7(std::vector<HostCluster>& kept, int64_t n, const int32_t* X, const int32_t* Y,
+                               std::vector<uint32_t>& cluster_of_row) = 0;
+  virtual ~ClusterHostHook() {}
+};
+
 // Steps 1 to 9 of one event, one row after the other: rows [n][8], labels [n] or nullptr -> out_labels [n], *ev and
-// rec[ATTPC_MAX_SIM].  n < 2^31.
+// rec[ATTPC_MAX_SIM].  n < 2^31.  `hook`: see ClusterHostHook; nullptr is the clustering alone.
 inline void cluster_event_host(const ClusterSettings& s, int64_t n, const double* rows, const int64_t* labels,
-                               int64_t* out_labels, attpc_cluster_event* ev, attpc_cluster_record* rec) {
+                               int64_t* out_labels, attpc_cluster_event* ev, attpc_cluster_record* rec,
+                               ClusterHostHook* hook = nullptr) {
   *ev = attpc_cluster_event{};
   for (int k = 0; k < ATTPC_MAX_SIM; ++k) rec[k] = cluster_record_unused();
   for (int64_t i = 0; i < n; ++i) {
@@ -210,7 +223,7 @@ inline void cluster_event_host(const ClusterSettings& s, int64_t n, const double
     if (best >= 0) r[i].cluster = r[best].cluster;
   }
   // steps 6 and 7: the clusters by id, their sizes, votes and extent
-  struct Cluster { uint32_t id, rows, core_rows, votes[ATTPC_MAX_SIM], majority_rows; int32_t majority, label, z_min, z_max; };
+  typedef HostCluster Cluster;
   std::vector<Cluster> clusters;
   std::vector<int64_t> slot((size_t)n, -1);
   for (int64_t i = 0; i < n; ++i) {
@@ -235,6 +248,17 @@ inline void cluster_event_host(const ClusterSettings& s, int64_t n, const double
       n_small += 1;
     else
       kept.push_back(k);
+  }
+  if (hook) {
+    std::vector<int32_t> X((size_t)n), Y((size_t)n);
+    std::vector<uint32_t> of((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      X[i] = r[i].X;
+      Y[i] = r[i].Y;
+      of[i] = r[i].cluster;
+    }
+    hook->between_6_and_7(kept, n, X.data(), Y.data(), of);
+    for (int64_t i = 0; i < n; ++i) r[i].cluster = of[i];
   }
   for (size_t a = 1; a < kept.size(); ++a)  // (insertion sort by the key, descending)
     for (size_t b = a; b > 0 && cluster_key(kept[b].rows, kept[b].id) > cluster_key(kept[b - 1].rows, kept[b - 1].id); --b)

@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "cluster_host.hpp"  // (behind the HIP runtime header)
 #include "distort_host.hpp"
+#include "join_host.hpp"
 #include "undistort_host.hpp"
 #include "unpack_host.hpp"
 
@@ -353,6 +354,9 @@ struct UndistortArgs {
 void launch_undistort(hipStream_t s, uint32_t n_events, const UndistortArgs& a);
 
 // clustering of trace rows (cluster.hip; attpc_trace_configure_clustering, the contract is in include/attpc_engine.h)
+// cluster_join_kernel (cluster_join.hip) reads this scratch as cluster_kernel left it -- cx, cy, cz, orig, core, comp
+// and the per-root counts, votes and extent -- and reuses w_lo: it must be launched right behind cluster_kernel on the
+// same stream with nothing else in between that touches the scratch, which is what keeps it alive.
 constexpr size_t CLUSTER_SCRATCH_WORDS = 25;  // 32-bit words of scratch per row (cluster.hip lists them)
 struct ClusterArgs {
   ClusterSettings s;
@@ -366,6 +370,16 @@ struct ClusterArgs {
 };
 // one workgroup per event, empty events included (n_events > 0)
 void launch_cluster(hipStream_t s, uint32_t n_events, const ClusterArgs& a);
+
+// cluster joining (cluster_join.hip; attpc_trace_configure_cluster_join, the contract is in include/attpc_engine.h)
+struct ClusterJoinArgs {
+  ClusterArgs c;                    // what cluster_kernel was launched with just before; c.events is not nullptr
+  JoinSettings j;
+  attpc_join_event* join_events;    // [n_events] or nullptr
+  attpc_join_record* join_records;  // [n_events][ATTPC_MAX_SIM] or nullptr
+};
+// one workgroup per event, right behind launch_cluster on the same stream (n_events > 0)
+void launch_cluster_join(hipStream_t s, uint32_t n_events, const ClusterJoinArgs& a);
 
 // packed pad traces (trace_pack.hip; the format "for64-bitplane-v1" is in include/attpc_engine.h).  samples
 // [n_rows][512] as the trace write pass left them, n_rows > 0; `workgroups` = trace_pack_workgroups(n_rows, limit).

@@ -1,6 +1,7 @@
 """Detector effects: same public names as the reference package (reference
 ``detector/__init__.py:13-21``) plus the batch entry points, device backed."""
 from . import clustering as _clustering
+from . import joining as _joining
 from . import correction as _correction
 from . import distortion as _distortion
 from . import fit as _fit
@@ -31,6 +32,7 @@ _EXPORTS = {
     _correction: ("CorrectionSettings", "configure_correction", "rows_to_correction"),
     _fit: ("TrackFitSettings", "configure_track_fit", "rows_to_fit"),
     _clustering: ("ClusterSettings", "configure_clustering", "rows_to_clusters", "cluster_scores"),
+    _joining: ("JoinSettings", "configure_cluster_join", "joins_last", "rows_to_joined_clusters"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

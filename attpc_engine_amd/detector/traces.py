@@ -250,6 +250,12 @@ def _checked_clustering(clustering):
     return _checked(clustering)
 
 
+def _checked_join(join):
+    from .joining import _checked
+
+    return _checked(join)
+
+
 def _checked_helix(helix):
     from .helix import _checked
 
@@ -425,11 +431,12 @@ class TraceChain:
     of the thinning, the estimates and the delivery: a ``detector.correction.CorrectionSettings``), ``fit`` (the
     track fit behind the estimates: a ``detector.fit.TrackFitSettings``) and ``clustering`` (trace rows: the cluster
     labels the thinning, the estimates and the fit match in place of the truth labels: a
-    ``detector.clustering.ClusterSettings``)."""
+    ``detector.clustering.ClusterSettings``) with ``join`` (the cluster joining between the clustering's size cut and
+    its ranking: a ``detector.joining.JoinSettings``; it does nothing without the clustering)."""
 
     def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
                  gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
-                 thinning=None, circle=None, helix=None, correction=None, fit=None, clustering=None):
+                 thinning=None, circle=None, helix=None, correction=None, fit=None, clustering=None, join=None):
         self.config, self._given = config, (response, threshold)
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
@@ -441,6 +448,7 @@ class TraceChain:
         self.correction = _checked_correction(correction)
         self.fit = _checked_fit(fit)
         self.clustering = _checked_clustering(clustering)
+        self.join = _checked_join(join)
 
     @classmethod
     def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
@@ -456,10 +464,10 @@ class TraceChain:
 
     def replace(self, **fields) -> "TraceChain":
         """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning,
-        circle, helix, correction, fit, clustering; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction", "fit", "clustering"}
+        circle, helix, correction, fit, clustering, join; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction", "fit", "clustering", "join"}
         if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix, correction, fit and clustering, not {sorted(unknown)}")
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix, correction, fit, clustering and join, not {sorted(unknown)}")
         chain = copy.copy(self)
         vars(chain).update(fields)
         if "config" in fields:
@@ -473,14 +481,15 @@ class TraceChain:
         _checked_correction(chain.correction)
         _checked_fit(chain.fit)
         _checked_clustering(chain.clustering)
+        _checked_join(chain.join)
         return chain
 
     def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
         """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
         trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
-        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them, the helix slope behind that and the track fit behind the estimates, and the clustering in front of them all.  A stage that is
+        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them, the helix slope behind that and the track fit behind the estimates, and the clustering in front of them all, the cluster joining with it.  A stage that is
         off is turned off, whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode"
-        "estimates" (the thinning, the circle fit, the helix slope and the track fit with them) "correction" and "clustering" that ``keep`` names, which stay as the ctx holds them."""
+        "estimates" (the thinning, the circle fit, the helix slope and the track fit with them) "correction" and "clustering" (the cluster joining with it) that ``keep`` names, which stay as the ctx holds them."""
         from .simulator import configure_spyral
 
         ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
@@ -505,6 +514,9 @@ class TraceChain:
             from .clustering import configure_clustering
 
             configure_clustering(ctx, self.clustering)
+            from .joining import configure_cluster_join
+
+            configure_cluster_join(ctx, self.join)
         if rows and "estimates" not in keep:
             from .circle import configure_circle
             from .estimate import configure_estimates
@@ -565,6 +577,9 @@ class TraceChain:
             from .clustering import clustering_result
 
             extra.update(clustering_result(ctx, len(arrays.offsets) - 1, int(arrays.offsets[-1])))
+            from .joining import join_result
+
+            extra.update(join_result(ctx, len(arrays.offsets) - 1))
         sums = ctx.trace_rows_last() if rows else arrays.sums()
         return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
 
@@ -1048,7 +1063,7 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
                          baseline: BaselineSettings | None = None, gain: GainSettings | None = None,
                          common_mode: CommonModeSettings | None = None, thinning=None, circle=None, helix=None,
-                         correction=None, clustering=None, **trace_kwargs) -> None:
+                         correction=None, clustering=None, join=None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
     the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
     baseline (default None: off, the peaks stand on the configured pedestals), the micromegas gain and the common-mode
@@ -1057,15 +1072,21 @@ def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings 
     ``detector.circle.CircleFitSettings``) or a ``helix`` (a ``detector.helix.HelixSlopeSettings``) is configured, None
     leaves what the ctx holds; so do ``correction`` (the drift correction of the rows, a
     ``detector.correction.CorrectionSettings``) and ``clustering`` (the cluster labels in place of the truth labels, a
-    ``detector.clustering.ClusterSettings``)."""
+    ``detector.clustering.ClusterSettings``) and ``join`` (the cluster joining behind it, a
+    ``detector.joining.JoinSettings``)."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
                                                                    common_mode=common_mode, thinning=thinning, circle=circle,
-                                                                   helix=helix, correction=correction, clustering=clustering)
+                                                                   helix=helix, correction=correction, clustering=clustering,
+                                                                   join=join)
     chain.configure(ctx, rows=True, keep=("trigger", "estimates", "correction", "clustering"))
     if clustering is not None:
         from .clustering import configure_clustering
 
         configure_clustering(ctx, chain.clustering)
+    if join is not None:
+        from .joining import configure_cluster_join
+
+        configure_cluster_join(ctx, chain.join)
     if correction is not None:
         from .correction import configure_correction
 
@@ -1090,7 +1111,7 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
                               estimates=None, thinning=None, straggling=None, circle=None, helix=None,
-                              distortion=None, correction=None, fit=None, clustering=None, **trace_kwargs):
+                              distortion=None, correction=None, fit=None, clustering=None, join=None, **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -1109,11 +1130,14 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     [n, len(indices)] come under ``"fits"``.  With ``clustering`` (a ``detector.clustering.ClusterSettings``; None = off)
     the thinning, the estimates and the fit match the cluster labels in place of the truth labels; the labels returned
     stay the truth labels, the cluster labels [P] come under ``"cluster_labels"`` and the event and cluster records
-    under ``"clusters"``."""
+    under ``"clusters"``.  With ``join`` (a ``detector.joining.JoinSettings``; None = off) beside it, clusters whose
+    circles overlap are joined before they are ranked and labelled, and the join events and records come under
+    ``"joins"``."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
                                                                    thinning=thinning, circle=circle, helix=helix,
-                                                                   correction=correction, fit=fit, clustering=clustering)
+                                                                   correction=correction, fit=fit, clustering=clustering,
+                                                                   join=join)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event, straggling=straggling, distortion=distortion)
 

@@ -21,6 +21,7 @@ from .detector.estimate import EstimateSettings, configure_estimates, estimates_
 from .detector.circle import CircleFitSettings, circle_result, configure_circle
 from .detector.fit import TrackFitSettings, configure_track_fit, fit_result
 from .detector.clustering import ClusterSettings, clustering_result, configure_clustering
+from .detector.joining import JoinSettings, configure_cluster_join, join_result
 from .detector.helix import HelixSlopeSettings, configure_helix, helix_result
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .detector.straggling import StragglingSettings, configure_straggling
@@ -322,14 +323,14 @@ class Engine:
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                     **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
                     **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices)),
-                    **clustering_result(ctx, n_events)}
+                    **clustering_result(ctx, n_events), **join_result(ctx, n_events)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                 **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
                     **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices)),
-                    **clustering_result(ctx, n_events, int(arrays.offsets[-1]))}
+                    **clustering_result(ctx, n_events, int(arrays.offsets[-1])), **join_result(ctx, n_events)}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -385,6 +386,17 @@ class Engine:
         store the records."""
         configure_clustering(self.ctx, _settings(ClusterSettings, settings, parameters))
 
+    def configure_cluster_join(self, settings=None, **parameters) -> None:
+        """The cluster joining behind the clustering (include/attpc_engine.h, "cluster joining"): a
+        ``detector.joining.JoinSettings`` or its keywords (overlap_ratio, min_radius, radius_ratio, max_clusters) turn it
+        on -- with the clustering configured too, the clusters of an event whose circles in the pad plane overlap are
+        joined before they are ranked and labelled, so the pieces of a broken track carry one label into the thinning,
+        the estimates and the track fit; the results of ``run_trace_rows`` / ``run_estimates`` carry ``joins`` = (events
+        [n] ``JOIN_EVENT_DTYPE``, records [n, 8] ``JOIN_DTYPE``), and ``clusters`` describe the joined clusters --,
+        neither turns it off (the default).  Without the clustering it does nothing.  Spyral's joining in structure, with
+        definite ties and one round only; not compared against Spyral.  The writers do not store the records."""
+        configure_cluster_join(self.ctx, _settings(JoinSettings, settings, parameters))
+
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
         128 bytes per track cross PCIe (``estimates`` [n, n_sim], ``detector.estimate.ESTIMATE_DTYPE``), beside the
@@ -406,7 +418,8 @@ class Engine:
                 "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
                 "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx),
                 **circle_result(ctx), **helix_result(ctx), **correction_result(ctx),
-                **fit_result(ctx, n_events, len(self.indices)), **clustering_result(ctx, n_events)}
+                **fit_result(ctx, n_events, len(self.indices)), **clustering_result(ctx, n_events),
+                **join_result(ctx, n_events)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

@@ -1956,6 +1956,108 @@ ATTPC_API int32_t attpc_rows_cluster(attpc_ctx* ctx, int64_t n_events, const int
                                      const attpc_cluster_desc* desc, int64_t* out_labels, attpc_cluster_event* events,
                                      attpc_cluster_record* records);
 
+/* ---- cluster joining (opt-in: off by default, and with it off every output, kernel and buffer of every entry point is
+ * what it is without this section; the entry points are additions under ABI version 3) ----
+ * The clustering above breaks a track into pieces where its rows lie farther apart than the linking lengths (n_split).
+ * This stage joins clusters whose circles in the pad plane overlap, which is what Spyral does between its clustering and
+ * its estimation.  It does nothing unless the clustering is on; it sits between step 6 (size cut) and step 7 (rank) of
+ * the clustering contract, so with it on steps 7 to 9 run on the JOINED clusters and every stage behind the clustering
+ * (thinning, estimates, circle fit, helix slope, track fit) reads the joined labels.
+ *
+ * The contract is Spyral's in structure, with every tie made definite.  It is NOT Spyral's code, Spyral ITERATES the
+ * joining with refitted circles and this stage does NOT (one round: a joined cluster's circle is not fitted again), and
+ * nothing here has been compared against Spyral.  tests/join_reference.py restates this contract in numpy;
+ * csrc/join_host.hpp holds the circle, the overlap predicate, the merge and a plain sequential form, shared with the
+ * host.
+ *
+ * Settings (attpc_join_desc): overlap_ratio, f64 in (0, 1]; min_radius in mm, 1/16 .. 5000; radius_ratio, 0 (no
+ * condition) or >= 1; max_clusters in 2 .. 64; the reserved words 0.  A NaN is refused.  The defaults (0.5, 10 mm, 0,
+ * 32) are a starting point, not a tuning.
+ *
+ * One event, behind step 6:
+ *  6a. Candidates: the surviving clusters of step 6 in ascending id, K of them.  An event of more than max_clusters
+ *      candidates is not joined: its labels, cluster event and cluster records are exactly those of the stage off, its
+ *      join event holds n_candidates and JOIN_CAPPED with every other field 0, and its join records are unused.  An
+ *      event the clustering did not cluster (CAPPED, INTERNAL, or no rows at all) is not joined either: its join event
+ *      is zeros plus JOIN_NOT_CLUSTERED, its join records are unused.
+ *  6b. Circle of a candidate: over all its rows, core and border, u = X - X_id and v = Y - Y_id in units of 1/16 mm,
+ *      (X_id, Y_id) the cluster's id row, so |u|, |v| <= 10 240.  The sums of u, v, u^2, v^2, uv, u (u^2 + v^2) and
+ *      v (u^2 + v^2) are exact in int64: a cluster has at most 65 535 rows, and 65 535 * 10 240 * 2 * 10 240^2 < 2^57.
+ *      The Kasa circle follows from them in f64 by estimate_kasa of "track estimates" -- the same code, its two cubic
+ *      sums of each axis given as one -- and is moved to absolute mm: a = (X_id + uc) / 16, b = (Y_id + vc) / 16,
+ *      R = sqrt(r2) / 16.  A candidate has NO CIRCLE and takes no part if it has fewer than 3 rows, a zero determinant,
+ *      r2 <= 0 or a non-finite a, b or R (which covers a determinant that is not finite).  A candidate with
+ *      R < min_radius has a circle but takes no part.
+ *  6c. Overlap of two candidates that take part, Rs <= Rl their radii (on a tie the lower id is "s"),
+ *      d = sqrt(da^2 + db^2) the distance of their centres:
+ *        d >= Rs + Rl:  A = 0;      d <= Rl - Rs:  A = pi Rs^2;     otherwise
+ *        A = Rs^2 acos(cs) + Rl^2 acos(cl) - sqrt(k) / 2,  cs = (d^2 + Rs^2 - Rl^2) / (2 d Rs),
+ *        cl = (d^2 + Rl^2 - Rs^2) / (2 d Rl),  k = (-d + Rs + Rl)(d + Rs - Rl)(d - Rs + Rl)(d + Rs + Rl) clamped at 0,
+ *        acos(c) = atan2w(sqrt(max(0, 1 - c^2)), c) with the written arctangent of "helix slope", the same code, and
+ *        pi its f64 constant 3.141592653589793.
+ *      The pair is JOINED iff A >= overlap_ratio * (pi * Rs^2) and (radius_ratio == 0 or Rl <= radius_ratio * Rs).
+ *      Every operation is one f64 rounding in the written order (no contraction).
+ *  6d. Join: the joined clusters are the connected components of the candidates under "is joined with" (transitive, one
+ *      round).  A component's id is its lowest member id; its rows, core rows and votes are the members' sums, its z
+ *      extent their minimum and maximum.  A candidate that takes no part is a component of its own.
+ *  7 to 9 run on the components: rank by (rows descending, id ascending), the majority from the summed votes,
+ *      MATCH_TRUTH and MATCH_RANK as before.  n_clusters counts components, n_split and n_fake are counted on
+ *      components; n_core, n_border, n_noise, n_small and n_range do not change.  The cluster records describe
+ *      components.  attpc_cluster_event and attpc_cluster_record keep their layouts and their reserved words (0).
+ *
+ * attpc_join_event, one per event: n_candidates (K); n_circles, the candidates with a circle; n_taking_part; n_pairs,
+ * the pairs joined in 6c; n_joined = candidates - components; status.
+ * attpc_join_record [n_events][ATTPC_MAX_SIM], one per ranked component, beside its cluster record: parts, the members
+ * it has; first_row, its id; a, b, radius in mm, the circle of its lowest-id member that has one, NaN if none has.  An
+ * unused slot is zero with first_row = -1. */
+#define ATTPC_JOIN_CAPPED 1         /* status: more than max_clusters candidates, not joined */
+#define ATTPC_JOIN_NOT_CLUSTERED 2  /* status: the clustering did not cluster the event */
+#define ATTPC_JOIN_MAX_CLUSTERS 64
+
+typedef struct attpc_join_desc {
+  double overlap_ratio;   /* (0, 1] */
+  double min_radius;      /* mm, 1/16 .. 5000 */
+  double radius_ratio;    /* 0: no condition, or >= 1 */
+  int32_t max_clusters;   /* 2 .. 64 */
+  int32_t reserved[3];    /* 0 */
+} attpc_join_desc;  /* 40 bytes */
+
+typedef struct attpc_join_event {
+  int32_t n_candidates;
+  int32_t n_circles;
+  int32_t n_taking_part;
+  int32_t n_pairs;
+  int32_t n_joined;
+  int32_t status;       /* ATTPC_JOIN_CAPPED, ATTPC_JOIN_NOT_CLUSTERED */
+  int32_t reserved[2];  /* 0 */
+} attpc_join_event;  /* 32 bytes */
+
+typedef struct attpc_join_record {
+  int32_t parts;        /* the members of the component */
+  int32_t first_row;    /* the id; -1: the slot is unused */
+  double a, b, radius;  /* mm; NaN: no member has a circle */
+} attpc_join_record;  /* 32 bytes */
+
+/* desc == NULL turns the stage off (the default): no kernel is launched and no buffer is held then.  ATTPC_E_INVALID
+ * for anything the section above rules out, a NaN included; refused for nothing else: it is independent of every other
+ * configure call, and without the clustering it does nothing.  With both on, every chunk of
+ * attpc_sim_run_trace_rows and attpc_det_run_trace_rows is joined right behind its clustering, also when the rows stay
+ * on the device.  Behind a trigger gate an event that did not fire has no rows: a join event of zeros plus
+ * JOIN_NOT_CLUSTERED and unused join records. */
+ATTPC_API int32_t attpc_trace_configure_cluster_join(attpc_ctx* ctx, const attpc_join_desc* desc);
+/* The join records of events first .. first + count - 1 of the context's last trace-row call: events [count] and
+ * records [count][ATTPC_MAX_SIM], either may be NULL.  ATTPC_E_NOTCONFIGURED if this stage or the clustering was off
+ * for that call (or it had no layout), ATTPC_E_INVALID for a range outside it. */
+ATTPC_API int32_t attpc_joins_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_join_event* events,
+                                   attpc_join_record* records);
+/* attpc_rows_cluster with the joining behind it, through the same kernels: join_desc must not be NULL; join_events
+ * [n_events] and join_records [n_events][ATTPC_MAX_SIM] may be NULL like the other outputs. */
+ATTPC_API int32_t attpc_rows_cluster_join(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                          const int64_t* labels, const attpc_event_layout* layout,
+                                          const attpc_cluster_desc* desc, const attpc_join_desc* join_desc,
+                                          int64_t* out_labels, attpc_cluster_event* events, attpc_cluster_record* records,
+                                          attpc_join_event* join_events, attpc_join_record* join_records);
+
 #ifdef __cplusplus
 }
 #endif

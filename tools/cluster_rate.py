@@ -13,9 +13,14 @@ cluster, the share with completeness >= 0.9 and purity >= 0.9, and the median an
 brho(estimate) / brho(truth) - 1, truth-labelled and clustered side by side, on the tracks both legs estimate and on all
 that each leg estimates; per workload the share of events with n_split, n_fake, n_small > 0 and the rows rejected.
 Reported values for the settings used, no limits.
+``--join`` is the leg of the cluster joining (attpc_trace_configure_cluster_join): in (a) both legs cluster
+and "on" also joins, so the cost is the joining's against the clustering alone; in (b) the clustered leg joins too, and
+the line carries the join counts (events joined, clusters joined away, events capped).  ``--overlap-ratio``,
+``--min-radius``, ``--radius-ratio`` (0 = no condition) and ``--max-clusters`` are its settings.
 
     python tools/cluster_rate.py [--events N] [--reps K] [--stats-events M] [--workloads o16aa,be10dp]
                                  [--eps-xy MM] [--eps-z MM] [--min-samples N] [--min-cluster-size N] [--out FILE]
+                                 [--join [--overlap-ratio R] [--min-radius MM] [--radius-ratio Q] [--max-clusters K]]
 """
 from __future__ import annotations
 
@@ -30,7 +35,7 @@ sys.path.insert(0, str(ROOT))
 
 PARTIAL = {"noise_sigma": 5.0, "pedestals": 300, "threshold": 20.0, "readout": "partial"}
 SETTINGS = ("events", "min_points", "thinning", "eps_xy", "eps_z", "min_samples", "min_cluster_size", "peak_threshold",
-            "peak_prominence")
+            "peak_prominence", "join", "overlap_ratio", "min_radius", "radius_ratio", "max_clusters")
 
 
 def _engine(name: str, args):
@@ -58,6 +63,12 @@ def _clustering(args):
     return ClusterSettings(args.eps_xy, args.eps_z, args.min_samples, args.min_cluster_size)
 
 
+def _join(args):
+    from attpc_engine_amd.detector.joining import JoinSettings
+
+    return JoinSettings(args.overlap_ratio, args.min_radius, args.radius_ratio or None, args.max_clusters) if args.join else None
+
+
 def _median(values):
     v = sorted(values)
     return v[len(v) // 2]
@@ -67,7 +78,10 @@ def rates(eng, args) -> dict:
     legs = {"off": [], "on": []}
 
     def call(on: bool):
-        if not args.off_only:
+        if args.join:  # both legs cluster; "on" joins
+            eng.configure_clustering(_clustering(args))
+            eng.configure_cluster_join(_join(args) if on else None)
+        elif not args.off_only:
             eng.configure_clustering(_clustering(args) if on else None)
         t0 = time.perf_counter()
         eng.run_estimates(args.events, seed=1)
@@ -84,6 +98,8 @@ def rates(eng, args) -> dict:
     if args.off_only:
         return out
     eng.configure_clustering()
+    if args.join:
+        eng.configure_cluster_join()
     out["cost_share"] = 1.0 - out["on"][0] / out["off"][0]
     out["seconds_per_event"] = 1.0 / out["on"][0] - 1.0 / out["off"][0]
     return out
@@ -107,18 +123,22 @@ def quality(eng, pipeline, indices, args) -> dict:
 
     z = pipeline.get_proton_numbers()
     est = {"truth": [], "clustered": []}
-    events, records, truth = [], [], []
+    events, records, truth, joins = [], [], [], []
     t0, done = time.perf_counter(), 0
     while done < args.stats_events:
         for leg in ("truth", "clustered"):
             eng.configure_clustering(_clustering(args) if leg == "clustered" else None)
+            eng.configure_cluster_join(_join(args) if leg == "clustered" else None)
             res = eng.run_estimates(args.events, seed=2, first_event=done)
             est[leg].append(res["estimates"])
+        if args.join:
+            joins.append(res["joins"][0])
         events.append(res["clusters"][0])
         records.append(res["clusters"][1])
         truth.append(estimate.truth_tracks(res["p4"], indices, z)["brho"])
         done += args.events
     eng.configure_clustering()
+    eng.configure_cluster_join()
     est = {k: np.concatenate(v) for k, v in est.items()}
     events, records, truth = np.concatenate(events), np.concatenate(records), np.concatenate(truth)
     completeness, purity = cluster_scores(events, records)
@@ -127,6 +147,12 @@ def quality(eng, pipeline, indices, args) -> dict:
     out["event_share"]["status"] = float((events["status"] != 0).mean())
     out["rows"] = {name: int(events[name].sum()) for name in ("n_rows", "n_range", "n_core", "n_border", "n_noise")}
     out["clusters_per_event"] = np.bincount(np.minimum(events["n_clusters"], 9), minlength=10).tolist()
+    if joins:
+        joins = np.concatenate(joins)
+        out["joins"] = {"events_joined": float((joins["n_joined"] > 0).mean()), "n_joined": int(joins["n_joined"].sum()),
+                        "n_pairs": int(joins["n_pairs"].sum()), "n_candidates": int(joins["n_candidates"].sum()),
+                        "n_circles": int(joins["n_circles"].sum()), "n_taking_part": int(joins["n_taking_part"].sum()),
+                        "events_capped": int((joins["status"] == 1).sum()), "events_not_clustered": int((joins["status"] == 2).sum())}
     for s in range(len(indices)):
         has_rows = events["truth_rows"][:, s] > 0
         found = has_rows & np.isfinite(completeness[:, s])
@@ -162,6 +188,11 @@ def main() -> int:
     ap.add_argument("--peak-threshold", type=float, default=None)
     ap.add_argument("--peak-prominence", type=float, default=None)
     ap.add_argument("--off-only", action="store_true")
+    ap.add_argument("--join", action="store_true")
+    ap.add_argument("--overlap-ratio", type=float, default=0.5)
+    ap.add_argument("--min-radius", type=float, default=10.0)
+    ap.add_argument("--radius-ratio", type=float, default=0.0)
+    ap.add_argument("--max-clusters", type=int, default=32)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     lines = []
@@ -169,7 +200,7 @@ def main() -> int:
         eng, pipeline, indices = _engine(name, args)
         settings = {k: getattr(args, k) for k in SETTINGS}
         if args.reps > 0:
-            lines.append({"workload": name, "kind": "rates_off_only" if args.off_only else "rates", **settings, **rates(eng, args)})
+            lines.append({"workload": name, "kind": "rates_off_only" if args.off_only else "rates_join" if args.join else "rates", **settings, **rates(eng, args)})
             print(json.dumps(lines[-1]), flush=True)
         if args.stats_events > 0 and not args.off_only:
             lines.append({"workload": name, "kind": "quality", **settings, **quality(eng, pipeline, indices, args)})
