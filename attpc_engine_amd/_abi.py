@@ -282,6 +282,27 @@ assert all(JOIN_DTYPE.fields[name][1] == getattr(JoinRecord, name).offset for na
 JOIN_CAPPED, JOIN_NOT_CLUSTERED = 1, 2
 JOIN_MAX_CLUSTERS = 64
 
+# ATTPC_PID_*: the modes, the limit of a gate's vertices and the bits of PidRecord.status; ATTPC_FIT_NO_PID
+PID_ANY, PID_OWN = 0, 1
+PID_MAX_VERTICES = 32
+PID_NO_ESTIMATE, PID_NONE, PID_TAKEN, PID_AMBIGUOUS = 1, 2, 4, 8
+FIT_NO_PID = 256
+
+
+class PidDesc(C.Structure):  # attpc_pid_desc
+    _fields_ = [("n_vertices", C.c_int32 * MAX_SIM), ("mode", C.c_int32), ("reserved", C.c_int32),
+                ("vertices", C.c_double * 2 * PID_MAX_VERTICES * MAX_SIM)]
+
+
+class PidRecord(C.Structure):  # attpc_pid_record
+    _fields_ = [("position", C.c_int32), ("species", C.c_int32), ("held", C.c_int32), ("status", C.c_int32)]
+
+
+# the pid records as a numpy structured dtype: itemsize and field offsets are those of include/attpc_engine.h
+PID_DTYPE = np.dtype([("position", "<i4"), ("species", "<i4"), ("held", "<i4"), ("status", "<i4")], align=True)
+assert C.sizeof(PidDesc) == 4136 and PID_DTYPE.itemsize == C.sizeof(PidRecord) == 16
+assert all(PID_DTYPE.fields[name][1] == getattr(PidRecord, name).offset for name, _ in PidRecord._fields_)
+
 
 class ThinDesc(C.Structure):
     _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
@@ -527,6 +548,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_fit", "attpc_fits_last", "attpc_rows_fit",
     "attpc_trace_configure_clustering", "attpc_clusters_last", "attpc_cluster_labels_last", "attpc_rows_cluster",
     "attpc_trace_configure_cluster_join", "attpc_joins_last", "attpc_rows_cluster_join",
+    "attpc_trace_configure_pid", "attpc_pid_last", "attpc_estimates_pid", "attpc_rows_fit_pid",
 )
 
 # The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
@@ -589,6 +611,9 @@ CLUSTER_SYMBOLS = ("attpc_trace_configure_clustering", "attpc_clusters_last", "a
 
 # ... and the cluster joining after the clustering: the same rule.
 JOIN_SYMBOLS = ("attpc_trace_configure_cluster_join", "attpc_joins_last", "attpc_rows_cluster_join")
+
+# ... and the particle identification after the cluster joining: the same rule.
+PID_SYMBOLS = ("attpc_trace_configure_pid", "attpc_pid_last", "attpc_estimates_pid", "attpc_rows_fit_pid")
 
 _lib = None
 
@@ -845,6 +870,18 @@ def load_library() -> C.CDLL:
     for name, argtypes in joining.items():
         if not no_joining:
             getattr(lib, name).argtypes = argtypes
+    pid = {
+        "attpc_trace_configure_pid": [ctxp, C.POINTER(PidDesc)],
+        "attpc_pid_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(PidRecord)],
+        "attpc_estimates_pid": [ctxp, C.c_int64, C.c_int32, C.POINTER(TrackEstimate), C.POINTER(PidDesc),
+                                C.POINTER(PidRecord)],
+        "attpc_rows_fit_pid": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
+                               C.POINTER(TrackEstimate), _dp, C.POINTER(FitDesc), C.POINTER(PidRecord), C.POINTER(TrackFit)],
+    }
+    no_pid = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in PID_SYMBOLS)
+    for name, argtypes in pid.items():
+        if not no_pid:
+            getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
         _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -874,7 +911,7 @@ def load_library() -> C.CDLL:
                 or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)
                 or (no_distortion and name in DISTORT_SYMBOLS) or (no_correction and name in UNDISTORT_SYMBOLS)
                 or (no_fit and name in FIT_SYMBOLS) or (no_clustering and name in CLUSTER_SYMBOLS)
-                or (no_joining and name in JOIN_SYMBOLS)):
+                or (no_joining and name in JOIN_SYMBOLS) or (no_pid and name in PID_SYMBOLS)):
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status
@@ -884,7 +921,7 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit", "clustering", "cluster_join")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit", "clustering", "cluster_join", "pid")
 
 
 class Context:

@@ -38,6 +38,7 @@
 #include "spyral_integral.hpp"  // (behind the HIP runtime header)
 #include "circle_host.hpp"
 #include "fit_host.hpp"
+#include "pid_host.hpp"
 #include "helix_host.hpp"
 #include "estimate_host.hpp"
 #include "thin_host.hpp"
@@ -110,6 +111,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf tg_records;           // trigger on (trigger.hip): the chunk's records, attpc_trigger_record [events]
   DevBuf tg_row_pass;          // ... with its gate, trace rows: fired of every kept trace row's event, uint8 [traces]
   DevBuf fit_records;          // track fit on (fit.hip): the chunk's records, attpc_track_fit [events][n_sim]
+  DevBuf pid_records;          // particle identification on (pid.hip): the chunk's records, attpc_pid_record [events][n_sim]
   DevBuf est_records;          // track estimates on (estimate.hip): the chunk's records, attpc_track_estimate [events][n_sim]
   DevBuf thin_points;          // ... of thinned points (thin.hip): one ThinPoint per trace row (pk_cap)
   DevBuf thin_info;            // ... and the attpc_thin_info of every (event, position)
@@ -275,6 +277,12 @@ struct attpc_ctx {
   Pinned<attpc_track_fit> h_fits;  // records of the last trace-row call, as h_estimates
   bool fit_call = false;           // that call made them
   DevBuf fit_scratch;              // the trials' residuals (FitArgs::scratch), shared by the chunks: they run in stream order
+  bool pid_on = false;             // attpc_trace_configure_pid (inert while the estimates are off)
+  attpc_pid_desc pid{};
+  DevBuf pid_gates;                // the gates on the device (PidGates), filled by the configure call
+  int32_t pid_species[ATTPC_MAX_SIM] = {};  // the species of the positions of the trace-row call in progress
+  Pinned<attpc_pid_record> h_pid;  // records of the last trace-row call, as h_estimates
+  bool pid_call = false;           // that call made them
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -1148,7 +1156,7 @@ void fit_positions(const DetDev& det, const attpc_event_layout& lay, FitPosition
 // The track fit of `n` events behind their estimates on S: the arguments the estimates had, their records, and room
 // for the trials.
 int32_t enqueue_fit(attpc_ctx* ctx, const EstimateArgs& e, uint32_t n, const attpc_fit_desc& d, const FitPosition* position,
-                    const double* start, attpc_track_fit* records) {
+                    const double* start, const attpc_pid_record* pid, attpc_track_fit* records) {
   const uint32_t workgroups = fit_workgroups(n, e.n_sim);
   const int32_t rc = ensure(ctx, ctx->fit_scratch, (size_t)workgroups * FIT_SCRATCH_PER_WORKGROUP);
   if (rc) return rc;
@@ -1170,7 +1178,35 @@ int32_t enqueue_fit(attpc_ctx* ctx, const EstimateArgs& e, uint32_t n, const att
   a.rb2 = e.rb2;
   a.n_events = n;
   a.n_sim = e.n_sim;
-  launch_fit(ctx->stream, a);
+  launch_fit(ctx->stream, a, pid);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// The gates of a checked desc on the device, in `buf`.
+int32_t upload_pid_gates(attpc_ctx* ctx, DevBuf& buf, const attpc_pid_desc& d) {
+  PidGates g{};
+  std::memcpy(g.vertices, d.vertices, sizeof g.vertices);
+  std::memcpy(g.n_vertices, d.n_vertices, sizeof g.n_vertices);
+  const int32_t rc = ensure(ctx, buf, sizeof g);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpy(buf.p, &g, sizeof g, hipMemcpyHostToDevice));
+  return ATTPC_OK;
+}
+
+// The particle identification of `n` > 0 events of n_sim > 0 positions on S: their estimate records against the gates
+// in `gates` (upload_pid_gates).
+int32_t enqueue_pid(attpc_ctx* ctx, const attpc_track_estimate* estimates, uint32_t n, int32_t n_sim, const DevBuf& gates,
+                    int32_t mode, const int32_t* species, attpc_pid_record* records) {
+  PidArgs a{};
+  a.estimates = estimates;
+  a.gates = static_cast<const PidGates*>(gates.p);
+  a.records = records;
+  for (int s = 0; s < ATTPC_MAX_SIM; ++s) a.species[s] = species ? species[s] : -1;
+  a.n_events = n;
+  a.n_sim = n_sim;
+  a.mode = mode;
+  launch_pid(ctx->stream, a);
   HIP_TRY(ctx, hipGetLastError());
   return ATTPC_OK;
 }
@@ -1180,6 +1216,7 @@ int32_t enqueue_fit(attpc_ctx* ctx, const EstimateArgs& e, uint32_t n, const att
 int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay) {
   ctx->est_call_events = -1;
   ctx->fit_call = false;
+  ctx->pid_call = false;
   if (!ctx->estimates_on || !lay) return ATTPC_OK;
   const int32_t rc = ensure_pinned(ctx, ctx->h_estimates, std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1));
   if (rc) return rc;
@@ -1191,6 +1228,13 @@ int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout
     if (rc2) return rc2;
     fit_positions(ctx->det, *lay, ctx->fit_position);
     ctx->fit_call = true;
+  }
+  if (ctx->pid_on) {  // (the identification does nothing without the estimates)
+    const int32_t rc2 = ensure_pinned(ctx, ctx->h_pid, std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1));
+    if (rc2) return rc2;
+    if (!ctx->fit_on) fit_positions(ctx->det, *lay, ctx->fit_position);
+    for (int s = 0; s < ATTPC_MAX_SIM; ++s) ctx->pid_species[s] = ctx->fit_position[s].table;
+    ctx->pid_call = true;
   }
   return ATTPC_OK;
 }
@@ -1244,15 +1288,26 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   else
     launch_estimates(ctx->stream, n, a);
   HIP_TRY(ctx, hipGetLastError());
+  const attpc_pid_record* pid = nullptr;
+  if (ctx->pid_call) {
+    if ((rc = ensure(ctx, as.pid_records, (size_t)n * n_sim * sizeof(attpc_pid_record)))) return rc;
+    if ((rc = enqueue_pid(ctx, a.records, n, a.n_sim, ctx->pid_gates, ctx->pid.mode, ctx->pid_species,
+                          static_cast<attpc_pid_record*>(as.pid_records.p))))
+      return rc;
+    pid = static_cast<const attpc_pid_record*>(as.pid_records.p);
+  }
   if (ctx->fit_call) {
     if ((rc = ensure(ctx, as.fit_records, (size_t)n * n_sim * sizeof(attpc_track_fit)))) return rc;
-    if ((rc = enqueue_fit(ctx, a, n, ctx->fit, ctx->fit_position, nullptr, static_cast<attpc_track_fit*>(as.fit_records.p))))
+    if ((rc = enqueue_fit(ctx, a, n, ctx->fit, ctx->fit_position, nullptr, pid, static_cast<attpc_track_fit*>(as.fit_records.p))))
       return rc;
   }
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
   if (ctx->fit_call)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fits.p + first_local * n_sim, as.fit_records.p, (size_t)n * n_sim * sizeof(attpc_track_fit),
+                                hipMemcpyDeviceToHost, ctx->stream_c));
+  if (ctx->pid_call)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pid.p + first_local * n_sim, as.pid_records.p, (size_t)n * n_sim * sizeof(attpc_pid_record),
                                 hipMemcpyDeviceToHost, ctx->stream_c));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_estimates.p + first_local * n_sim, as.est_records.p,
                               (size_t)n * n_sim * sizeof(attpc_track_estimate), hipMemcpyDeviceToHost, ctx->stream_c));
@@ -4176,21 +4231,29 @@ int32_t attpc_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_trac
   return ATTPC_OK;
 }
 
-int32_t attpc_rows_fit(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
-                       const attpc_event_layout* layout, const attpc_estimate_desc* ed, const attpc_track_estimate* estimates_in,
-                       const double* start, const attpc_fit_desc* fd, attpc_track_fit* out) {
+namespace {
+
+// attpc_rows_fit (pid == nullptr) and attpc_rows_fit_pid
+int32_t rows_fit(attpc_ctx* ctx, const char* func, int64_t n_events, const int64_t* offsets, const double* rows,
+                 const int64_t* labels, const attpc_event_layout* layout, const attpc_estimate_desc* ed,
+                 const attpc_track_estimate* estimates_in, const double* start, const attpc_fit_desc* fd,
+                 const attpc_pid_record* pid, bool with_pid, attpc_track_fit* out) {
   if (!ctx || n_events < 0 || !ed || !fd || !layout) return ATTPC_E_INVALID;
   if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
-    return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", __func__, layout->n_sim, ATTPC_MAX_SIM);
+    return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", func, layout->n_sim, ATTPC_MAX_SIM);
   if (layout->n_rows < 0 || layout->n_rows > ATTPC_MAX_ROWS)
-    return fail(ctx, ATTPC_E_INVALID, "%s: n_rows %d outside 0 .. %d", __func__, layout->n_rows, ATTPC_MAX_ROWS);
+    return fail(ctx, ATTPC_E_INVALID, "%s: n_rows %d outside 0 .. %d", func, layout->n_rows, ATTPC_MAX_ROWS);
   if (const char* bad = estimate_desc_error(*ed)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
   if (const char* bad = fit_desc_error(*fd)) return fail(ctx, ATTPC_E_INVALID, "fit: %s", bad);
-  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "%s: no detector is configured", __func__);
+  if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "%s: no detector is configured", func);
   const size_t n_sim = (size_t)layout->n_sim;
-  if (n_events > 0 && n_sim && (!out || !estimates_in)) return ATTPC_E_INVALID;
-  if (const ArgError bad = csr_error(__func__, n_events, offsets)) return refuse(ctx, bad);
+  if (n_events > 0 && n_sim && (!out || !estimates_in || (with_pid && !pid))) return ATTPC_E_INVALID;
+  if (const ArgError bad = csr_error(func, n_events, offsets)) return refuse(ctx, bad);
   if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !labels)) return ATTPC_E_INVALID;
+  if (with_pid)
+    for (size_t i = 0; i < (size_t)n_events * n_sim; ++i)
+      if (pid[i].position < -1 || pid[i].position >= layout->n_sim)
+        return fail(ctx, ATTPC_E_INVALID, "%s: pid[%zu].position %d outside -1 .. %d", func, i, pid[i].position, layout->n_sim - 1);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc;
   if ((rc = sync_all(ctx))) return rc;
@@ -4213,9 +4276,83 @@ int32_t attpc_rows_fit(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets,
     a.records = const_cast<attpc_track_estimate*>(stage_in(ctx, 3, estimates_in + (size_t)e0 * n_sim, m * n_sim, rc));
     const double* d_start = start ? stage_in(ctx, 4, start + (size_t)e0 * n_sim * 6, m * n_sim * 6, rc) : nullptr;
     attpc_track_fit* d_out = stage<attpc_track_fit>(ctx, 5, m * n_sim, rc);
+    const attpc_pid_record* d_pid = with_pid ? stage_in(ctx, 6, pid + (size_t)e0 * n_sim, m * n_sim, rc) : nullptr;
     if (rc) return rc;
-    if ((rc = enqueue_fit(ctx, a, (uint32_t)m, *fd, position, d_start, d_out))) return rc;
+    if ((rc = enqueue_fit(ctx, a, (uint32_t)m, *fd, position, d_start, d_pid, d_out))) return rc;
     if ((rc = stage_out(ctx, out + (size_t)e0 * n_sim, d_out, m * n_sim))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return ATTPC_OK;
+}
+
+}  // namespace
+
+int32_t attpc_rows_fit(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                       const attpc_event_layout* layout, const attpc_estimate_desc* ed, const attpc_track_estimate* estimates_in,
+                       const double* start, const attpc_fit_desc* fd, attpc_track_fit* out) {
+  return rows_fit(ctx, __func__, n_events, offsets, rows, labels, layout, ed, estimates_in, start, fd, nullptr, false, out);
+}
+
+// ---- particle identification (pid.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_rows_fit_pid(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
+                           const attpc_event_layout* layout, const attpc_estimate_desc* ed,
+                           const attpc_track_estimate* estimates_in, const double* start, const attpc_fit_desc* fd,
+                           const attpc_pid_record* pid, attpc_track_fit* out) {
+  return rows_fit(ctx, __func__, n_events, offsets, rows, labels, layout, ed, estimates_in, start, fd, pid, true, out);
+}
+
+int32_t attpc_trace_configure_pid(attpc_ctx* ctx, const attpc_pid_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = pid_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "pid: %s", bad);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->pid_on = false;
+  if (!d) {  // (off: the gates' buffer goes too)
+    if (ctx->pid_gates.p) {
+      ctx->device_bytes -= ctx->pid_gates.bytes;
+      ctx->pid_gates = DevBuf{};
+    }
+    return ATTPC_OK;
+  }
+  const int32_t rc = upload_pid_gates(ctx, ctx->pid_gates, *d);
+  if (rc) return rc;
+  ctx->pid = *d;
+  ctx->pid_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_pid_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_pid_record* out) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->est_call_events < 0 || !ctx->pid_call)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_pid_last: the last trace-row call made no particle identification");
+  if (const ArgError bad = records_range_error(__func__, first, count, ctx->est_call_events)) return refuse(ctx, bad);
+  const size_t n_sim = (size_t)ctx->est_call_n_sim;
+  if (count == 0 || n_sim == 0) return ATTPC_OK;
+  if (!out) return ATTPC_E_INVALID;
+  std::memcpy(out, ctx->h_pid.p + (size_t)first * n_sim, (size_t)count * n_sim * sizeof(attpc_pid_record));
+  return ATTPC_OK;
+}
+
+int32_t attpc_estimates_pid(attpc_ctx* ctx, int64_t n_events, int32_t n_sim, const attpc_track_estimate* estimates,
+                            const attpc_pid_desc* d, attpc_pid_record* out) {
+  if (!ctx || n_events < 0 || !d) return ATTPC_E_INVALID;
+  if (n_sim < 0 || n_sim > ATTPC_MAX_SIM)
+    return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", __func__, n_sim, ATTPC_MAX_SIM);
+  if (const char* bad = pid_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "pid: %s", bad);
+  if (n_events > 0 && n_sim && (!estimates || !out)) return ATTPC_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  if (n_events == 0 || n_sim == 0) return ATTPC_OK;
+  if ((rc = upload_pid_gates(ctx, ctx->scratch[2], *d))) return rc;
+  constexpr int64_t CHUNK_EVENTS = 1 << 20;
+  for (int64_t e0 = 0; e0 < n_events; e0 += CHUNK_EVENTS) {
+    const size_t m = (size_t)std::min<int64_t>(CHUNK_EVENTS, n_events - e0);
+    const attpc_track_estimate* d_est = stage_in(ctx, 0, estimates + (size_t)e0 * (size_t)n_sim, m * (size_t)n_sim, rc);
+    attpc_pid_record* d_out = stage<attpc_pid_record>(ctx, 1, m * (size_t)n_sim, rc);
+    if (rc) return rc;
+    if ((rc = enqueue_pid(ctx, d_est, (uint32_t)m, n_sim, ctx->scratch[2], d->mode, nullptr, d_out))) return rc;
+    if ((rc = stage_out(ctx, out + (size_t)e0 * (size_t)n_sim, d_out, m * (size_t)n_sim))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return ATTPC_OK;

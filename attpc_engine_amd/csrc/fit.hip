@@ -23,6 +23,8 @@
 // eight tables in LDS (90 KiB) would hold a CU to one workgroup.
 #include "tracks_args.hpp"
 
+#include <type_traits>
+
 #include "estimate_host.hpp"
 #include "fit_host.hpp"
 
@@ -66,7 +68,11 @@ __device__ __forceinline__ double fit_group_add(double v) {
 
 }  // namespace
 
-__global__ __launch_bounds__(64) void fit_kernel(FitArgs a) {
+// fit_kernel<false> is the fit of "track fit"; fit_kernel<true> is the same body behind the particle identification
+// ("particle identification" in the header): the nucleus of slot s is that of the position its pid record names, and a
+// slot without one gets the record without a fit, NO_PID.
+template <bool PID>
+__global__ __launch_bounds__(64) void fit_kernel(std::conditional_t<PID, FitPidArgs, FitArgs> a) {
   const int lane = (int)threadIdx.x, k = lane & 7, group = lane & ~7;
   const uint32_t below = (1u << k) - 1u;
   const uint64_t n_tracks = (uint64_t)a.n_events * (uint64_t)a.n_sim;
@@ -77,7 +83,17 @@ __global__ __launch_bounds__(64) void fit_kernel(FitArgs a) {
     const int s = (int)(track - (uint64_t)e * (uint64_t)a.n_sim);
     attpc_track_fit* out = a.records + track;
     const attpc_track_estimate est = a.estimates[track];
-    const FitPosition pos = a.position[s];
+    int at = s;  // the position whose nucleus the track is taken for
+    if constexpr (PID) {
+      at = a.pid[track].position;
+      if (at < 0 || at >= a.n_sim) {
+        attpc_track_fit none;
+        fit_no_fit(ATTPC_FIT_NO_PID, est.n_used < ATTPC_FIT_MAX_POINTS ? est.n_used : ATTPC_FIT_MAX_POINTS, &none);
+        if (k == 0) *out = none;
+        continue;
+      }
+    }
+    const FitPosition pos = a.position[at];
     attpc_track_fit rec;
     const int32_t est_points = est.n_used < ATTPC_FIT_MAX_POINTS ? est.n_used : ATTPC_FIT_MAX_POINTS;
     double start[6];
@@ -150,8 +166,14 @@ uint32_t fit_workgroups(uint32_t n_events, int32_t n_sim) {
   return (uint32_t)(groups < FIT_MAX_WORKGROUPS ? groups : FIT_MAX_WORKGROUPS);
 }
 
-void launch_fit(hipStream_t s, const FitArgs& a) {
-  hipLaunchKernelGGL(fit_kernel, dim3(fit_workgroups(a.n_events, a.n_sim)), dim3(64), 0, s, a);
+void launch_fit(hipStream_t s, const FitArgs& a, const attpc_pid_record* pid) {
+  if (pid) {
+    FitPidArgs with;
+    static_cast<FitArgs&>(with) = a;
+    with.pid = pid;
+    hipLaunchKernelGGL(fit_kernel<true>, dim3(fit_workgroups(a.n_events, a.n_sim)), dim3(64), 0, s, with);
+  } else
+    hipLaunchKernelGGL(fit_kernel<false>, dim3(fit_workgroups(a.n_events, a.n_sim)), dim3(64), 0, s, a);
 }
 
 }  // namespace attpc

@@ -328,11 +328,34 @@ struct FitArgs {
   uint32_t n_events;
   int32_t n_sim;
 };
+struct FitPidArgs : FitArgs {       // fit_kernel<true>: behind the particle identification (pid.hip), the nucleus of
+  const attpc_pid_record* pid;      // slot s is that of position pid[e][s].position; [n_events][n_sim]
+};
 constexpr uint32_t FIT_MAX_WORKGROUPS = 1024;
 constexpr size_t FIT_SCRATCH_PER_WORKGROUP = (size_t)8 * 8 * ATTPC_FIT_MAX_POINTS * 3 * sizeof(double);
 // the workgroups (one wave of eight tracks each) for n_events * n_sim tracks; a.scratch holds that many regions
 uint32_t fit_workgroups(uint32_t n_events, int32_t n_sim);
-void launch_fit(hipStream_t s, const FitArgs& a);
+// fit_kernel<false>, or with `pid` fit_kernel<true> (FitPidArgs)
+void launch_fit(hipStream_t s, const FitArgs& a, const attpc_pid_record* pid = nullptr);
+
+// particle identification (pid.hip; attpc_trace_configure_pid, the contract is in include/attpc_engine.h)
+struct PidGates {                   // the gates of an attpc_pid_desc as the device holds them
+  double vertices[ATTPC_MAX_SIM * ATTPC_PID_MAX_VERTICES * 2];
+  int32_t n_vertices[ATTPC_MAX_SIM];
+};
+struct PidArgs {
+  const attpc_track_estimate* estimates;  // [n_events][n_sim]
+  const PidGates* gates;
+  attpc_pid_record* records;        // [n_events][n_sim]
+  int32_t species[ATTPC_MAX_SIM];   // the detector species of every position, -1: none
+  uint32_t n_events;                // > 0
+  int32_t n_sim;                    // 1 .. ATTPC_MAX_SIM
+  int32_t mode;                     // ATTPC_PID_ANY, ATTPC_PID_OWN
+};
+constexpr uint32_t PID_MAX_WORKGROUPS = 2048;
+// the workgroups (one wave each) for n_events events
+uint32_t pid_workgroups(uint32_t n_events);
+void launch_pid(hipStream_t s, const PidArgs& a);
 
 // drift correction of trace rows (undistort.hip; attpc_trace_configure_correction, the contract is in
 // include/attpc_engine.h)

@@ -7,6 +7,7 @@ from . import distortion as _distortion
 from . import fit as _fit
 from . import maps as _maps
 from . import parameters as _parameters
+from . import pid as _pid
 from . import selection as _selection
 from . import simulator as _simulator
 from . import straggling as _straggling
@@ -33,6 +34,7 @@ _EXPORTS = {
     _fit: ("TrackFitSettings", "configure_track_fit", "rows_to_fit"),
     _clustering: ("ClusterSettings", "configure_clustering", "rows_to_clusters", "cluster_scores"),
     _joining: ("JoinSettings", "configure_cluster_join", "joins_last", "rows_to_joined_clusters"),
+    _pid: ("Gate", "PidSettings", "configure_pid", "pid_last", "estimates_to_pid", "by_position", "PID_DTYPE"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

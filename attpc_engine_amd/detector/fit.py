@@ -103,13 +103,16 @@ def _layout(indices, species_of_row) -> _abi.EventLayout:
 
 
 def rows_to_fit(offsets, rows, labels, indices, estimates, ctx: _abi.Context, settings: TrackFitSettings, start=None, *,
-                estimate_settings=None, species_of_row=None) -> np.ndarray:
+                estimate_settings=None, species_of_row=None, pid=None) -> np.ndarray:
     """The stage alone on any host rows in CSR form (``attpc_rows_fit``; the kernel of the fused path): offsets [n+1],
     rows [R,8], labels [R], ``indices`` (an ``_abi.EventLayout`` such as ``Engine.layout``, or the nucleus of every
     position with ``species_of_row``), ``estimates`` [n, n_sim] (``ESTIMATE_DTYPE``, of ``rows_to_estimates`` on the
     same rows with ``estimate_settings``) -> records [n, n_sim] (``FIT_DTYPE``).  ``start`` [n, n_sim, 6] = (gamma beta
     x, y, z, vertex x, y, z in metres) replaces the start from the estimates.  ``ctx`` must hold a configured detector:
-    its species tables, masses, charges, fields and length are the model."""
+    its species tables, masses, charges, fields and length are the model.  ``pid`` [n, n_sim] (``PID_DTYPE``, of
+    ``detector.pid.estimates_to_pid`` on the same estimates): the fit behind the particle identification
+    (``attpc_rows_fit_pid``) -- slot k is fitted as the nucleus of position ``pid["position"][e, k]``, and a slot without
+    a position gets the record without a fit, ``FIT_NO_PID``."""
     from .estimate import EstimateSettings
 
     if not isinstance(settings, TrackFitSettings):
@@ -136,6 +139,17 @@ def rows_to_fit(offsets, rows, labels, indices, estimates, ctx: _abi.Context, se
         if start.shape != (n, layout.n_sim, 6):
             raise ValueError(f"start must be [{n}, {layout.n_sim}, 6], got {start.shape}")
     records = np.empty((n, layout.n_sim), dtype=FIT_DTYPE)
+    if pid is not None:
+        pid = np.ascontiguousarray(pid, dtype=_abi.PID_DTYPE)
+        if pid.shape != (n, layout.n_sim):
+            raise ValueError(f"pid must be [{n}, {layout.n_sim}], got {pid.shape}")
+        ctx.check(ctx.lib.attpc_rows_fit_pid(ctx.handle, n, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(rows),
+                                             _abi.iptr(labels, _abi.C.c_int64), layout, estimate_settings.desc(),
+                                             _abi.iptr(estimates, _abi.TrackEstimate),
+                                             None if start is None else _abi.dptr(start), settings.desc(),
+                                             _abi.iptr(pid, _abi.PidRecord), _abi.iptr(records, _abi.TrackFit)),
+                  "attpc_rows_fit_pid")
+        return records
     ctx.check(ctx.lib.attpc_rows_fit(ctx.handle, n, _abi.iptr(offsets, _abi.C.c_int64), _abi.dptr(rows),
                                      _abi.iptr(labels, _abi.C.c_int64), layout, estimate_settings.desc(),
                                      _abi.iptr(estimates, _abi.TrackEstimate), None if start is None else _abi.dptr(start),

@@ -256,6 +256,12 @@ def _checked_join(join):
     return _checked(join)
 
 
+def _checked_pid(pid):
+    from .pid import _checked
+
+    return _checked(pid)
+
+
 def _checked_helix(helix):
     from .helix import _checked
 
@@ -432,11 +438,14 @@ class TraceChain:
     track fit behind the estimates: a ``detector.fit.TrackFitSettings``) and ``clustering`` (trace rows: the cluster
     labels the thinning, the estimates and the fit match in place of the truth labels: a
     ``detector.clustering.ClusterSettings``) with ``join`` (the cluster joining between the clustering's size cut and
-    its ranking: a ``detector.joining.JoinSettings``; it does nothing without the clustering)."""
+    its ranking: a ``detector.joining.JoinSettings``; it does nothing without the clustering) and ``pid`` (the particle
+    identification between the estimates and the track fit: a ``detector.pid.PidSettings``; it does nothing without
+    the estimates)."""
 
     def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
                  gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
-                 thinning=None, circle=None, helix=None, correction=None, fit=None, clustering=None, join=None):
+                 thinning=None, circle=None, helix=None, correction=None, fit=None, clustering=None, join=None,
+                 pid=None):
         self.config, self._given = config, (response, threshold)
         self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
         self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
@@ -449,6 +458,7 @@ class TraceChain:
         self.fit = _checked_fit(fit)
         self.clustering = _checked_clustering(clustering)
         self.join = _checked_join(join)
+        self.pid = _checked_pid(pid)
 
     @classmethod
     def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
@@ -464,10 +474,10 @@ class TraceChain:
 
     def replace(self, **fields) -> "TraceChain":
         """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning,
-        circle, helix, correction, fit, clustering, join; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction", "fit", "clustering", "join"}
+        circle, helix, correction, fit, clustering, join, pid; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
+        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction", "fit", "clustering", "join", "pid"}
         if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix, correction, fit, clustering and join, not {sorted(unknown)}")
+            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix, correction, fit, clustering, join and pid, not {sorted(unknown)}")
         chain = copy.copy(self)
         vars(chain).update(fields)
         if "config" in fields:
@@ -482,14 +492,15 @@ class TraceChain:
         _checked_fit(chain.fit)
         _checked_clustering(chain.clustering)
         _checked_join(chain.join)
+        _checked_pid(chain.pid)
         return chain
 
     def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
         """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
         trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
-        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them, the helix slope behind that and the track fit behind the estimates, and the clustering in front of them all, the cluster joining with it.  A stage that is
+        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them, the helix slope behind that, the particle identification and the track fit behind the estimates, and the clustering in front of them all, the cluster joining with it.  A stage that is
         off is turned off, whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode"
-        "estimates" (the thinning, the circle fit, the helix slope and the track fit with them) "correction" and "clustering" (the cluster joining with it) that ``keep`` names, which stay as the ctx holds them."""
+        "estimates" (the thinning, the circle fit, the helix slope, the particle identification and the track fit with them) "correction" and "clustering" (the cluster joining with it) that ``keep`` names, which stay as the ctx holds them."""
         from .simulator import configure_spyral
 
         ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
@@ -522,6 +533,7 @@ class TraceChain:
             from .estimate import configure_estimates
             from .fit import configure_track_fit
             from .helix import configure_helix
+            from .pid import configure_pid
             from .thinning import configure_thinning
 
             configure_estimates(ctx, self.estimates, self.config)
@@ -529,6 +541,7 @@ class TraceChain:
             configure_circle(ctx, self.circle)
             configure_helix(ctx, self.helix)
             configure_track_fit(ctx, self.fit)
+            configure_pid(ctx, self.pid)
 
     def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
                   ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False,
@@ -580,6 +593,9 @@ class TraceChain:
             from .joining import join_result
 
             extra.update(join_result(ctx, len(arrays.offsets) - 1))
+            from .pid import pid_result
+
+            extra.update(pid_result(ctx, len(arrays.offsets) - 1, len(indices)))
         sums = ctx.trace_rows_last() if rows else arrays.sums()
         return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
 
@@ -1063,7 +1079,7 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
                          baseline: BaselineSettings | None = None, gain: GainSettings | None = None,
                          common_mode: CommonModeSettings | None = None, thinning=None, circle=None, helix=None,
-                         correction=None, clustering=None, join=None, **trace_kwargs) -> None:
+                         correction=None, clustering=None, join=None, pid=None, **trace_kwargs) -> None:
     """Everything a trace-row call needs beside the detector: the trace settings (``configure_traces(**trace_kwargs)``),
     the geometry of the rows (``configure_spyral``), the peak parameters (default ``PeakSettings()``), the Fourier
     baseline (default None: off, the peaks stand on the configured pedestals), the micromegas gain and the common-mode
@@ -1073,12 +1089,17 @@ def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings 
     leaves what the ctx holds; so do ``correction`` (the drift correction of the rows, a
     ``detector.correction.CorrectionSettings``) and ``clustering`` (the cluster labels in place of the truth labels, a
     ``detector.clustering.ClusterSettings``) and ``join`` (the cluster joining behind it, a
-    ``detector.joining.JoinSettings``)."""
+    ``detector.joining.JoinSettings``) and ``pid`` (the particle identification behind the estimates, a
+    ``detector.pid.PidSettings``)."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
                                                                    common_mode=common_mode, thinning=thinning, circle=circle,
                                                                    helix=helix, correction=correction, clustering=clustering,
-                                                                   join=join)
+                                                                   join=join, pid=pid)
     chain.configure(ctx, rows=True, keep=("trigger", "estimates", "correction", "clustering"))
+    if pid is not None:
+        from .pid import configure_pid
+
+        configure_pid(ctx, chain.pid)
     if clustering is not None:
         from .clustering import configure_clustering
 
@@ -1111,7 +1132,8 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
                               baseline: BaselineSettings | None = None, trigger: TriggerSettings | None = None,
                               gain: GainSettings | None = None, common_mode: CommonModeSettings | None = None,
                               estimates=None, thinning=None, straggling=None, circle=None, helix=None,
-                              distortion=None, correction=None, fit=None, clustering=None, join=None, **trace_kwargs):
+                              distortion=None, correction=None, fit=None, clustering=None, join=None, pid=None,
+                              **trace_kwargs):
     """simulate() + the pad traces of every event + their peaks as Spyral rows, all on the device
     (``attpc_det_run_trace_rows``; ``trace_kwargs`` as configure_traces takes them, ``baseline`` as configure_trace_rows) ->
     (offsets [n+1], rows [P,8] in ascending z per event, labels [P], event_points [n] = cloud rows of every event
@@ -1132,12 +1154,14 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     stay the truth labels, the cluster labels [P] come under ``"cluster_labels"`` and the event and cluster records
     under ``"clusters"``.  With ``join`` (a ``detector.joining.JoinSettings``; None = off) beside it, clusters whose
     circles overlap are joined before they are ranked and labelled, and the join events and records come under
-    ``"joins"``."""
+    ``"joins"``.  With ``pid`` (a ``detector.pid.PidSettings``; None = off) beside the estimates, every (event, slot)
+    is assigned a position by the gates on its estimate record's dE/dx against B rho, the fit uses that position's
+    species, and the records [n, len(indices)] come under ``"pid"``."""
     chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
                                                                    common_mode=common_mode, estimates=estimates,
                                                                    thinning=thinning, circle=circle, helix=helix,
                                                                    correction=correction, fit=fit, clustering=clustering,
-                                                                   join=join)
+                                                                   join=join, pid=pid)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event, straggling=straggling, distortion=distortion)
 

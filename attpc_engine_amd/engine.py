@@ -22,6 +22,7 @@ from .detector.circle import CircleFitSettings, circle_result, configure_circle
 from .detector.fit import TrackFitSettings, configure_track_fit, fit_result
 from .detector.clustering import ClusterSettings, clustering_result, configure_clustering
 from .detector.joining import JoinSettings, configure_cluster_join, join_result
+from .detector.pid import PidSettings, configure_pid, pid_result
 from .detector.helix import HelixSlopeSettings, configure_helix, helix_result
 from .detector.thinning import ThinSettings, configure_thinning, thinning_result
 from .detector.straggling import StragglingSettings, configure_straggling
@@ -323,14 +324,16 @@ class Engine:
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                     **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
                     **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices)),
-                    **clustering_result(ctx, n_events), **join_result(ctx, n_events)}
+                    **clustering_result(ctx, n_events), **join_result(ctx, n_events),
+                **pid_result(ctx, n_events, len(self.indices))}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
                 **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
                     **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices)),
-                    **clustering_result(ctx, n_events, int(arrays.offsets[-1])), **join_result(ctx, n_events)}
+                    **clustering_result(ctx, n_events, int(arrays.offsets[-1])), **join_result(ctx, n_events),
+                **pid_result(ctx, n_events, len(self.indices))}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -397,6 +400,19 @@ class Engine:
         definite ties and one round only; not compared against Spyral.  The writers do not store the records."""
         configure_cluster_join(self.ctx, _settings(JoinSettings, settings, parameters))
 
+    def configure_pid(self, gates=None, mode: str = "any") -> None:
+        """The particle identification between the track estimates and the track fit (include/attpc_engine.h, "particle
+        identification"): a ``detector.pid.PidSettings``, or ``gates`` (a sequence or a dict by position of
+        ``detector.pid.Gate``, None = no gate) with ``mode`` ("any" or "own"), turns it on -- every (event, slot) of
+        ``run_trace_rows`` / ``run_estimates`` is then assigned the lowest free position whose polygon gate holds its
+        estimate record's (B rho, dE/dx), the track fit uses that position's species and skips the slots without one
+        (``detector.pid.FIT_NO_PID``), and the results carry ``pid`` [n, n_sim] (``detector.pid.PID_DTYPE``) --, None
+        turns it off (the default).  Without the estimates it does nothing.  ``detector.pid.Gate.from_band`` makes gates
+        from a calibration run.  The writers, ``run_simulation`` and ``run_fused`` do not take it and do not store the
+        records."""
+        settings = gates if gates is None or isinstance(gates, PidSettings) else PidSettings(gates, mode)
+        configure_pid(self.ctx, settings)
+
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
         128 bytes per track cross PCIe (``estimates`` [n, n_sim], ``detector.estimate.ESTIMATE_DTYPE``), beside the
@@ -419,7 +435,8 @@ class Engine:
                 "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx),
                 **circle_result(ctx), **helix_result(ctx), **correction_result(ctx),
                 **fit_result(ctx, n_events, len(self.indices)), **clustering_result(ctx, n_events),
-                **join_result(ctx, n_events)}
+                **join_result(ctx, n_events),
+                **pid_result(ctx, n_events, len(self.indices))}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

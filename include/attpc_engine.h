@@ -2058,6 +2058,99 @@ ATTPC_API int32_t attpc_rows_cluster_join(attpc_ctx* ctx, int64_t n_events, cons
                                           int64_t* out_labels, attpc_cluster_event* events, attpc_cluster_record* records,
                                           attpc_join_event* join_events, attpc_join_record* join_records);
 
+/* ---- particle identification (opt-in: off by default, and with it off every output, kernel and buffer of every entry
+ * point is what it is without this section; inert while the track estimates are off; the entry points are additions
+ * under ABI version 3) ----
+ * With the clustering in MATCH_RANK, slot k of an event is its k-th largest cluster and the track fit integrates its
+ * trials with the stopping-power table of POSITION k, whatever the particle.  This stage decides per (event, slot)
+ * which position's species the track is, or none: a polygon gate per position in the plane of the estimate record's
+ * dE/dx against B rho, which is the one tool an analysis of data has (Spyral's particle ID is such a gate).  It sits
+ * behind the estimate kernel and in front of the track fit; the fit of a slot then uses the species of the position the
+ * slot was assigned and skips the slots no gate holds.  The estimates' dedx and brho are strongly biased; a gate is
+ * drawn on the biased quantities themselves.  tests/pid_reference.py restates this contract in numpy;
+ * csrc/pid_host.hpp holds the desc check, the edge rule, the inside test, the assignment walk and a plain sequential
+ * form, shared with the host.  Gates are not read from Spyral's files, and nothing here has been compared against
+ * Spyral.
+ *
+ * Gates (attpc_pid_desc): one per layout position p < ATTPC_MAX_SIM.  n_vertices[p] is 0 (no gate: the position is
+ * never assigned) or 3 .. ATTPC_PID_MAX_VERTICES; vertices[p][v] = (x, y) in f64, finite: x is B rho in T m, y is
+ * dE/dx in the units of attpc_track_estimate.dedx; the vertices behind n_vertices[p] are not read.  mode is
+ * ATTPC_PID_ANY or ATTPC_PID_OWN; reserved is 0.  Anything else, a NaN vertex included, is ATTPC_E_INVALID.
+ *
+ * Inside.  A record's point is (x, y) = (brho, dedx).  It is tested only if both are finite and > 0; otherwise the
+ * slot's status is NO_ESTIMATE (position and species -1, held 0).  The test is the crossing number with one written
+ * rule per edge from (x0, y0) = vertex v to (x1, y1) = vertex v + 1, the closing edge from the last vertex to the first
+ * included: the edge COUNTS iff
+ *   (y0 > y) != (y1 > y)   and   d != 0   and   (d > 0) == (y1 > y0),
+ *   d = (x1 - x0) * (y - y0) - (x - x0) * (y1 - y0),
+ * every difference and product rounded once in f64, nothing contracted into a fused multiply-add.  The point is inside
+ * iff the count is odd.  A horizontal edge never counts; a point on an edge (d == 0) does not count that edge, so a
+ * point on an edge or a vertex has a definite answer (tests/pid_cases.py pins which).  No division, no transcendental.
+ *
+ * Assignment per event.  held[k] is the bit mask of the positions p < n_sim whose gate holds slot k's point; in mode
+ * OWN only bit k is tested.  The slots are walked in ascending k (with the clustering on this is rank order, the
+ * largest cluster first): slot k takes the LOWEST position in held[k] that no earlier slot took.
+ *
+ * attpc_pid_record per (event, slot): position (-1: none); species, the detector species of that position
+ * (species_of_row[indices[position]] of the call's layout where the context's detector has it with Z > 0 and a mass,
+ * the index of the table the fit then reads; -1 if there is none, and always -1 from attpc_estimates_pid, which has no
+ * layout); held; status, the bits
+ *   NO_ESTIMATE  the point was not tested;
+ *   NONE         no gate holds it (held == 0);
+ *   TAKEN        gates hold it, but all their positions are taken (position -1);
+ *   AMBIGUOUS    more than one gate holds it (set beside an assignment, which is still made, or beside TAKEN).
+ * A record is a pure function of the event's estimate records and the gates, whatever the chunking.
+ *
+ * Fit.  With this stage on, the fit of slot k uses the nucleus of position pid.position in every place where "track
+ * fit" says "the position's nucleus"; everything else it reads (rows, cluster labels, thinned points, the estimate
+ * record as the start) stays slot k's.  A slot with position < 0 is not fitted: its record is the record without a fit
+ * of "track fit" (n_points = min(n_used, 2048), the integers 0, every f64 NaN) with status ATTPC_FIT_NO_PID alone. */
+#define ATTPC_PID_ANY 0
+#define ATTPC_PID_OWN 1
+#define ATTPC_PID_MAX_VERTICES 32
+#define ATTPC_PID_NO_ESTIMATE 1
+#define ATTPC_PID_NONE 2
+#define ATTPC_PID_TAKEN 4
+#define ATTPC_PID_AMBIGUOUS 8
+#define ATTPC_FIT_NO_PID 256        /* attpc_track_fit.status: the particle identification gave the slot no position */
+
+typedef struct attpc_pid_desc {
+  int32_t n_vertices[ATTPC_MAX_SIM];  /* 0, or 3 .. 32 */
+  int32_t mode;                       /* ATTPC_PID_ANY, ATTPC_PID_OWN */
+  int32_t reserved;                   /* 0 */
+  double vertices[ATTPC_MAX_SIM][ATTPC_PID_MAX_VERTICES][2];  /* (B rho in T m, dE/dx) */
+} attpc_pid_desc;  /* 4136 bytes */
+
+typedef struct attpc_pid_record {
+  int32_t position;  /* -1: none */
+  int32_t species;   /* -1: none */
+  int32_t held;      /* bit p: the gate of position p holds the point */
+  int32_t status;    /* ATTPC_PID_* bits */
+} attpc_pid_record;  /* 16 bytes */
+
+/* desc == NULL turns the stage off (the default): no kernel is launched and no buffer is held then.  ATTPC_E_INVALID
+ * for anything the section above rules out; refused for nothing else: it is independent of every other configure call,
+ * and without the track estimates it does nothing.  With both on, attpc_sim_run_trace_rows and attpc_det_run_trace_rows
+ * launch the stage behind every chunk's estimate kernel and in front of its track fit on the same stream, also when the
+ * rows stay on the device, with the fit off as well.  It holds 4 KiB of device memory for the gates. */
+ATTPC_API int32_t attpc_trace_configure_pid(attpc_ctx* ctx, const attpc_pid_desc* desc);
+/* Records [count][layout->n_sim] of the context's last trace-row call, as attpc_estimates_last.
+ * ATTPC_E_NOTCONFIGURED if this stage or the estimates were off for that call. */
+ATTPC_API int32_t attpc_pid_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_pid_record* out);
+/* The stage alone on any host estimate records [n_events][n_sim], through the same kernel: n_sim in
+ * 0 .. ATTPC_MAX_SIM, desc not NULL, out [n_events][n_sim]; only brho and dedx of a record are read.  Needs no other
+ * configure call and leaves the configured stage as it is. */
+ATTPC_API int32_t attpc_estimates_pid(attpc_ctx* ctx, int64_t n_events, int32_t n_sim,
+                                      const attpc_track_estimate* estimates, const attpc_pid_desc* desc,
+                                      attpc_pid_record* out);
+/* attpc_rows_fit with the records of this stage, through the same instantiation of the fit kernel as the fused path:
+ * pid [n_events][n_sim], of which position is read (ATTPC_E_INVALID outside -1 .. n_sim - 1). */
+ATTPC_API int32_t attpc_rows_fit_pid(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                     const int64_t* labels, const attpc_event_layout* layout,
+                                     const attpc_estimate_desc* estimate_desc, const attpc_track_estimate* estimates_in,
+                                     const double* start, const attpc_fit_desc* fit_desc, const attpc_pid_record* pid,
+                                     attpc_track_fit* out);
+
 #ifdef __cplusplus
 }
 #endif
