@@ -551,69 +551,135 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_pid", "attpc_pid_last", "attpc_estimates_pid", "attpc_rows_fit_pid",
 )
 
-# The trace-row entry points were added under ABI version 3 (additive).  Another build of that version named by
-# ATTPC_HIP_LIBRARY -- the yardstick of tools/trace_rows_rate.py -- may lack them: it loads, and a call of a missing
-# entry point is the AttributeError ctypes raises.  The package's own library must have every symbol.
-TRACE_ROW_SYMBOLS = ("attpc_trace_configure_peaks", "attpc_sim_run_trace_rows", "attpc_det_run_trace_rows",
-                     "attpc_trace_rows_at", "attpc_trace_rows_last")
+# The entry points added under ABI version 3 (additive), group by group in the order they were added:
+# group -> {symbol: argtypes}.  Another build of that version named by ATTPC_HIP_LIBRARY -- the yardstick of
+# tools/trace_rows_rate.py -- may lack whole groups: it loads, and a call of a missing entry point is the AttributeError
+# ctypes raises.  The package's own library must have every symbol.
+_ctxp, _i16p, _i32p, _i64p, _u8p = C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+_ids = [_ctxp, C.c_uint64, C.c_uint64, C.c_uint64]  # (seed, first event, events)
+_rows_in = [_ctxp, C.c_int64, _i64p, _dp, _i64p]  # (events, offsets, rows, labels of host rows in CSR form)
+_sim_head = _ids + [C.POINTER(EventLayout), _dp, _dp, _i32p]  # ... then the output struct and the statistics
+_det_head = _ids + [C.POINTER(EventLayout), _dp, _dp]
+_at_head = [_ctxp, C.c_uint64, C.c_uint64, C.c_int64, _i64p, _dp, _i64p]
 
-# The summary entry points were added under ABI version 3 as well, after the trace rows: the same rule.
-SUMMARY_SYMBOLS = ("attpc_summary_configure", "attpc_sim_run_summary", "attpc_det_run_summary", "attpc_cloud_summary")
 
-# ... and the selected delivery after the summaries: the same rule.
-SELECT_SYMBOLS = ("attpc_select_configure", "attpc_sim_run_selected", "attpc_det_run_selected", "attpc_cloud_select")
+def _run(head, out):
+    return head + [C.POINTER(out), C.POINTER(RunStats)]
 
-# ... and the Fourier baseline of the trace rows after the selected delivery: the same rule.
-BASELINE_SYMBOLS = ("attpc_trace_configure_baseline", "attpc_trace_baseline")
 
-# ... and the multiplicity trigger of the traces after the Fourier baseline: the same rule.
-TRIGGER_SYMBOLS = ("attpc_trace_configure_trigger", "attpc_trigger_last", "attpc_trigger_rows")
-
-# ... and the micromegas gain of the traces after the trigger: the same rule.
-GAIN_SYMBOLS = ("attpc_trace_configure_gain", "attpc_gain_rows")
-
-# ... and the common-mode noise of the traces after the gain: the same rule.
-COMMON_SYMBOLS = ("attpc_trace_configure_common_mode", "attpc_common_mode_rows")
-
-# ... and the packed pad traces after the common-mode noise: the same rule.
-TRACE_PACK_SYMBOLS = ("attpc_sim_run_traces_packed", "attpc_det_run_traces_packed", "attpc_traces_packed_at",
-                      "attpc_trace_pack", "attpc_trace_pack_host", "attpc_trace_unpack")
-
-# ... and the run maps after the packed pad traces: the same rule.
-MAPS_SYMBOLS = ("attpc_maps_configure", "attpc_sim_run_maps", "attpc_det_run_maps", "attpc_cloud_maps")
-
-# ... and the track estimates of the trace rows after the run maps: the same rule.
-ESTIMATE_SYMBOLS = ("attpc_trace_configure_estimates", "attpc_estimates_last", "attpc_rows_estimate")
-
-# ... and the thinned track points after the track estimates: the same rule.
-THIN_SYMBOLS = ("attpc_trace_configure_thinning", "attpc_rows_thin")
-
-# ... and the track straggling after the thinned track points: the same rule.
-STRAGGLE_SYMBOLS = ("attpc_det_configure_straggling",)
-
-# ... and the geometric circle fit after the track straggling: the same rule.
-CIRCLE_SYMBOLS = ("attpc_trace_configure_circle", "attpc_rows_estimate_circle")
-
-# ... and the helix slope after the geometric circle fit: the same rule.
-HELIX_SYMBOLS = ("attpc_trace_configure_helix", "attpc_rows_estimate_helix")
-
-# ... and the drift distortion after the helix slope: the same rule.
-DISTORT_SYMBOLS = ("attpc_det_configure_distortion", "attpc_samples_distort")
-
-# ... and the drift correction of the trace rows after the drift distortion: the same rule.
-UNDISTORT_SYMBOLS = ("attpc_trace_configure_correction", "attpc_correction_last", "attpc_rows_undistort")
-
-# ... and the track fit after the drift correction: the same rule.
-FIT_SYMBOLS = ("attpc_trace_configure_fit", "attpc_fits_last", "attpc_rows_fit")
-
-# ... and the clustering after the track fit: the same rule.
-CLUSTER_SYMBOLS = ("attpc_trace_configure_clustering", "attpc_clusters_last", "attpc_cluster_labels_last", "attpc_rows_cluster")
-
-# ... and the cluster joining after the clustering: the same rule.
-JOIN_SYMBOLS = ("attpc_trace_configure_cluster_join", "attpc_joins_last", "attpc_rows_cluster_join")
-
-# ... and the particle identification after the cluster joining: the same rule.
-PID_SYMBOLS = ("attpc_trace_configure_pid", "attpc_pid_last", "attpc_estimates_pid", "attpc_rows_fit_pid")
+SYMBOL_GROUPS = {
+    "trace_rows": {
+        "attpc_trace_configure_peaks": [_ctxp, C.POINTER(PeakDesc)],
+        "attpc_sim_run_trace_rows": _run(_sim_head, CloudOut),
+        "attpc_det_run_trace_rows": _run(_det_head, CloudOut),
+        "attpc_trace_rows_at": _at_head + [C.POINTER(CloudOut)],
+        "attpc_trace_rows_last": [_ctxp, _i64p, C.POINTER(C.c_uint64)],
+    },
+    "summary": {
+        "attpc_summary_configure": [_ctxp, C.POINTER(SummaryDesc)],
+        "attpc_sim_run_summary": _run(_sim_head, SummaryOut),
+        "attpc_det_run_summary": _run(_det_head, SummaryOut),
+        "attpc_cloud_summary": _rows_in + [C.POINTER(EventLayout), C.POINTER(SummaryOut)],
+    },
+    "select": {
+        "attpc_select_configure": [_ctxp, C.POINTER(SelectDesc)],
+        "attpc_sim_run_selected": _run(_sim_head, SelectOut),
+        "attpc_det_run_selected": _run(_det_head, SelectOut),
+        "attpc_cloud_select": _rows_in + [C.POINTER(EventLayout), C.POINTER(SummaryOut), _u8p],
+    },
+    "baseline": {
+        "attpc_trace_configure_baseline": [_ctxp, C.POINTER(BaselineDesc)],
+        "attpc_trace_baseline": [_ctxp, C.c_int64, _i16p, C.c_double, _i16p, _dp],
+    },
+    "trigger": {
+        "attpc_trace_configure_trigger": [_ctxp, C.POINTER(TriggerDesc)],
+        "attpc_trigger_last": [_ctxp, C.c_int64, C.c_int64, C.POINTER(TriggerRecord)],
+        "attpc_trigger_rows": [_ctxp, C.c_int64, _i64p, _i32p, _i16p, _i16p, C.POINTER(TriggerDesc), C.POINTER(TriggerRecord)],
+    },
+    "gain": {
+        "attpc_trace_configure_gain": [_ctxp, C.POINTER(TraceGainDesc)],
+        "attpc_gain_rows": [_ctxp, C.c_uint64, C.c_uint64, C.c_int64, _i64p, _dp, _dp],
+    },
+    "common_mode": {
+        "attpc_trace_configure_common_mode": [_ctxp, C.POINTER(TraceCommonDesc)],
+        "attpc_common_mode_rows": [_ctxp, C.c_uint64, C.c_uint64, C.c_int64, _i16p],
+    },
+    "trace_pack": {
+        "attpc_sim_run_traces_packed": _run(_sim_head, TracePackedOut),
+        "attpc_det_run_traces_packed": _run(_det_head, TracePackedOut),
+        "attpc_traces_packed_at": _at_head + [C.POINTER(TracePackedOut)],
+        "attpc_trace_pack": [_ctxp, C.c_int64, _i16p, _i64p, _u8p, C.c_int64, _i64p],
+        "attpc_trace_pack_host": [C.c_int64, _i16p, _i64p, _u8p, C.c_int64, _i64p],
+        "attpc_trace_unpack": [_u8p, C.c_int64, _i64p, C.c_int64, _i16p, C.c_int32],
+    },
+    "maps": {
+        "attpc_maps_configure": [_ctxp, C.POINTER(MapsDesc)],
+        "attpc_sim_run_maps": _sim_head + [C.POINTER(SummaryOut), _u8p, C.POINTER(MapsOut), C.POINTER(RunStats)],
+        "attpc_det_run_maps": _det_head + [C.POINTER(SummaryOut), _u8p, C.POINTER(MapsOut), C.POINTER(RunStats)],
+        "attpc_cloud_maps": _rows_in + [C.POINTER(EventLayout), C.POINTER(SummaryOut), _u8p, C.POINTER(MapsOut)],
+    },
+    "estimates": {
+        "attpc_trace_configure_estimates": [_ctxp, C.POINTER(EstimateDesc)],
+        "attpc_estimates_last": [_ctxp, C.c_int64, C.c_int64, C.POINTER(TrackEstimate)],
+        "attpc_rows_estimate": _rows_in + [C.POINTER(EventLayout), C.POINTER(EstimateDesc), C.POINTER(TrackEstimate)],
+    },
+    "thinning": {
+        "attpc_trace_configure_thinning": [_ctxp, C.POINTER(ThinDesc)],
+        "attpc_rows_thin": _rows_in + [C.POINTER(EventLayout), C.POINTER(ThinDesc), C.c_int64, _i64p, _dp, _i64p,
+                                       C.POINTER(ThinInfo), _i64p],
+    },
+    "straggling": {"attpc_det_configure_straggling": [_ctxp, C.POINTER(StraggleDesc)]},
+    "circle": {
+        "attpc_trace_configure_circle": [_ctxp, C.POINTER(CircleDesc)],
+        "attpc_rows_estimate_circle": _rows_in + [C.POINTER(EventLayout), C.POINTER(EstimateDesc), C.POINTER(CircleDesc),
+                                                  C.POINTER(TrackEstimate)],
+    },
+    "helix": {
+        "attpc_trace_configure_helix": [_ctxp, C.POINTER(HelixDesc)],
+        "attpc_rows_estimate_helix": _rows_in + [C.POINTER(EventLayout), C.POINTER(EstimateDesc), C.POINTER(CircleDesc),
+                                                 C.POINTER(HelixDesc), C.POINTER(TrackEstimate)],
+    },
+    "distortion": {
+        "attpc_det_configure_distortion": [_ctxp, C.POINTER(DistortDesc)],
+        "attpc_samples_distort": [_ctxp, C.c_int64, _dp, C.POINTER(DistortDesc), _dp],
+    },
+    "correction": {
+        "attpc_trace_configure_correction": [_ctxp, C.POINTER(UndistortDesc)],
+        "attpc_correction_last": [_ctxp, C.POINTER(UndistortInfo)],
+        "attpc_rows_undistort": _rows_in + [C.POINTER(UndistortDesc), _dp, _i64p, _i64p, C.POINTER(UndistortInfo)],
+    },
+    "fit": {
+        "attpc_trace_configure_fit": [_ctxp, C.POINTER(FitDesc)],
+        "attpc_fits_last": [_ctxp, C.c_int64, C.c_int64, C.POINTER(TrackFit)],
+        "attpc_rows_fit": _rows_in + [C.POINTER(EventLayout), C.POINTER(EstimateDesc), C.POINTER(TrackEstimate), _dp,
+                                      C.POINTER(FitDesc), C.POINTER(TrackFit)],
+    },
+    "clustering": {
+        "attpc_trace_configure_clustering": [_ctxp, C.POINTER(ClusterDesc)],
+        "attpc_clusters_last": [_ctxp, C.c_int64, C.c_int64, C.POINTER(ClusterEvent), C.POINTER(ClusterRecord)],
+        "attpc_cluster_labels_last": [_ctxp, C.c_int64, C.c_int64, _i64p],
+        "attpc_rows_cluster": _rows_in + [C.POINTER(EventLayout), C.POINTER(ClusterDesc), _i64p, C.POINTER(ClusterEvent),
+                                          C.POINTER(ClusterRecord)],
+    },
+    "cluster_join": {
+        "attpc_trace_configure_cluster_join": [_ctxp, C.POINTER(JoinDesc)],
+        "attpc_joins_last": [_ctxp, C.c_int64, C.c_int64, C.POINTER(JoinEvent), C.POINTER(JoinRecord)],
+        "attpc_rows_cluster_join": _rows_in + [C.POINTER(EventLayout), C.POINTER(ClusterDesc), C.POINTER(JoinDesc), _i64p,
+                                               C.POINTER(ClusterEvent), C.POINTER(ClusterRecord), C.POINTER(JoinEvent),
+                                               C.POINTER(JoinRecord)],
+    },
+    "pid": {
+        "attpc_trace_configure_pid": [_ctxp, C.POINTER(PidDesc)],
+        "attpc_pid_last": [_ctxp, C.c_int64, C.c_int64, C.POINTER(PidRecord)],
+        "attpc_estimates_pid": [_ctxp, C.c_int64, C.c_int32, C.POINTER(TrackEstimate), C.POINTER(PidDesc), C.POINTER(PidRecord)],
+        "attpc_rows_fit_pid": _rows_in + [C.POINTER(EventLayout), C.POINTER(EstimateDesc), C.POINTER(TrackEstimate), _dp,
+                                          C.POINTER(FitDesc), C.POINTER(PidRecord), C.POINTER(TrackFit)],
+    },
+}
+(TRACE_ROW_SYMBOLS, SUMMARY_SYMBOLS, SELECT_SYMBOLS, BASELINE_SYMBOLS, TRIGGER_SYMBOLS, GAIN_SYMBOLS, COMMON_SYMBOLS,
+ TRACE_PACK_SYMBOLS, MAPS_SYMBOLS, ESTIMATE_SYMBOLS, THIN_SYMBOLS, STRAGGLE_SYMBOLS, CIRCLE_SYMBOLS, HELIX_SYMBOLS,
+ DISTORT_SYMBOLS, UNDISTORT_SYMBOLS, FIT_SYMBOLS, CLUSTER_SYMBOLS, JOIN_SYMBOLS, PID_SYMBOLS) = (
+     tuple(group) for group in SYMBOL_GROUPS.values())
 
 _lib = None
 
@@ -656,231 +722,25 @@ def load_library() -> C.CDLL:
         ctxp, C.c_uint64, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32),
     ]
     lib.attpc_det_configure.argtypes = [ctxp, C.POINTER(DetDesc)]
-    lib.attpc_det_run.argtypes = [
-        ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-        C.POINTER(CloudOut), C.POINTER(RunStats),
-    ]
-    lib.attpc_sim_run.argtypes = [
-        ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-        C.POINTER(C.c_int32), C.POINTER(CloudOut), C.POINTER(RunStats),
-    ]
+    lib.attpc_det_run.argtypes = _run(_det_head, CloudOut)
+    lib.attpc_sim_run.argtypes = _run(_sim_head, CloudOut)
     lib.attpc_sim_run_spyral.argtypes = lib.attpc_sim_run.argtypes
     lib.attpc_det_run_spyral.argtypes = lib.attpc_det_run.argtypes
     lib.attpc_sim_hint_next.argtypes = [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout)]
     lib.attpc_spyral_configure.argtypes = [ctxp, C.POINTER(SpyralDesc)]
     lib.attpc_trace_configure.argtypes = [ctxp, C.POINTER(TraceDesc)]
-    lib.attpc_sim_run_traces.argtypes = [
-        ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-        C.POINTER(C.c_int32), C.POINTER(TraceOut), C.POINTER(RunStats),
-    ]
-    lib.attpc_det_run_traces.argtypes = [
-        ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-        C.POINTER(TraceOut), C.POINTER(RunStats),
-    ]
+    lib.attpc_sim_run_traces.argtypes = _run(_sim_head, TraceOut)
+    lib.attpc_det_run_traces.argtypes = _run(_det_head, TraceOut)
     lib.attpc_traces.argtypes = [ctxp, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(TraceOut)]
     lib.attpc_trace_configure_noise.argtypes = [ctxp, C.POINTER(TraceNoiseDesc)]
-    lib.attpc_traces_at.argtypes = [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64), _dp,
-                                    C.POINTER(C.c_int64), C.POINTER(TraceOut)]
+    lib.attpc_traces_at.argtypes = _at_head + [C.POINTER(TraceOut)]
     lib.attpc_trace_configure_readout.argtypes = [ctxp, C.POINTER(TraceReadoutDesc)]
-    trace_rows = {
-        "attpc_trace_configure_peaks": [ctxp, C.POINTER(PeakDesc)],
-        "attpc_sim_run_trace_rows": lib.attpc_sim_run.argtypes,
-        "attpc_det_run_trace_rows": lib.attpc_det_run.argtypes,
-        "attpc_trace_rows_at": [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64),
-                                C.POINTER(CloudOut)],
-        "attpc_trace_rows_last": [ctxp, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)],
-    }
-    older = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in TRACE_ROW_SYMBOLS)
-    for name, argtypes in trace_rows.items():
-        if not older:
-            getattr(lib, name).argtypes = argtypes
-    summary = {
-        "attpc_summary_configure": [ctxp, C.POINTER(SummaryDesc)],
-        "attpc_sim_run_summary": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-                                  C.POINTER(C.c_int32), C.POINTER(SummaryOut), C.POINTER(RunStats)],
-        "attpc_det_run_summary": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-                                  C.POINTER(SummaryOut), C.POINTER(RunStats)],
-        "attpc_cloud_summary": [ctxp, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(EventLayout),
-                                C.POINTER(SummaryOut)],
-    }
-    no_summary = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in SUMMARY_SYMBOLS)
-    for name, argtypes in summary.items():
-        if not no_summary:
-            getattr(lib, name).argtypes = argtypes
-    select = {
-        "attpc_select_configure": [ctxp, C.POINTER(SelectDesc)],
-        "attpc_sim_run_selected": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-                                   C.POINTER(C.c_int32), C.POINTER(SelectOut), C.POINTER(RunStats)],
-        "attpc_det_run_selected": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-                                   C.POINTER(SelectOut), C.POINTER(RunStats)],
-        "attpc_cloud_select": [ctxp, C.c_int64, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), C.POINTER(EventLayout),
-                               C.POINTER(SummaryOut), C.POINTER(C.c_uint8)],
-    }
-    no_select = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in SELECT_SYMBOLS)
-    for name, argtypes in select.items():
-        if not no_select:
-            getattr(lib, name).argtypes = argtypes
-    baseline = {
-        "attpc_trace_configure_baseline": [ctxp, C.POINTER(BaselineDesc)],
-        "attpc_trace_baseline": [ctxp, C.c_int64, C.POINTER(C.c_int16), C.c_double, C.POINTER(C.c_int16), _dp],
-    }
-    no_baseline = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in BASELINE_SYMBOLS)
-    for name, argtypes in baseline.items():
-        if not no_baseline:
-            getattr(lib, name).argtypes = argtypes
-    trigger = {
-        "attpc_trace_configure_trigger": [ctxp, C.POINTER(TriggerDesc)],
-        "attpc_trigger_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(TriggerRecord)],
-        "attpc_trigger_rows": [ctxp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int16),
-                               C.POINTER(C.c_int16), C.POINTER(TriggerDesc), C.POINTER(TriggerRecord)],
-    }
-    no_trigger = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in TRIGGER_SYMBOLS)
-    for name, argtypes in trigger.items():
-        if not no_trigger:
-            getattr(lib, name).argtypes = argtypes
-    gain = {
-        "attpc_trace_configure_gain": [ctxp, C.POINTER(TraceGainDesc)],
-        "attpc_gain_rows": [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int64), _dp, _dp],
-    }
-    no_gain = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in GAIN_SYMBOLS)
-    for name, argtypes in gain.items():
-        if not no_gain:
-            getattr(lib, name).argtypes = argtypes
-    common = {
-        "attpc_trace_configure_common_mode": [ctxp, C.POINTER(TraceCommonDesc)],
-        "attpc_common_mode_rows": [ctxp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(C.c_int16)],
-    }
-    no_common = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in COMMON_SYMBOLS)
-    for name, argtypes in common.items():
-        if not no_common:
-            getattr(lib, name).argtypes = argtypes
-    i16p, i64p, u8p = C.POINTER(C.c_int16), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
-    trace_pack = {
-        "attpc_sim_run_traces_packed": lib.attpc_sim_run_traces.argtypes[:-2] + [C.POINTER(TracePackedOut), C.POINTER(RunStats)],
-        "attpc_det_run_traces_packed": lib.attpc_det_run_traces.argtypes[:-2] + [C.POINTER(TracePackedOut), C.POINTER(RunStats)],
-        "attpc_traces_packed_at": lib.attpc_traces_at.argtypes[:-1] + [C.POINTER(TracePackedOut)],
-        "attpc_trace_pack": [ctxp, C.c_int64, i16p, i64p, u8p, C.c_int64, i64p],
-        "attpc_trace_pack_host": [C.c_int64, i16p, i64p, u8p, C.c_int64, i64p],
-        "attpc_trace_unpack": [u8p, C.c_int64, i64p, C.c_int64, i16p, C.c_int32],
-    }
-    no_trace_pack = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in TRACE_PACK_SYMBOLS)
-    for name, argtypes in trace_pack.items():
-        if not no_trace_pack:
-            getattr(lib, name).argtypes = argtypes
-    maps = {
-        "attpc_maps_configure": [ctxp, C.POINTER(MapsDesc)],
-        "attpc_sim_run_maps": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-                               C.POINTER(C.c_int32), C.POINTER(SummaryOut), u8p, C.POINTER(MapsOut), C.POINTER(RunStats)],
-        "attpc_det_run_maps": [ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp,
-                               C.POINTER(SummaryOut), u8p, C.POINTER(MapsOut), C.POINTER(RunStats)],
-        "attpc_cloud_maps": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(SummaryOut), u8p,
-                             C.POINTER(MapsOut)],
-    }
-    no_maps = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in MAPS_SYMBOLS)
-    for name, argtypes in maps.items():
-        if not no_maps:
-            getattr(lib, name).argtypes = argtypes
-    estimates = {
-        "attpc_trace_configure_estimates": [ctxp, C.POINTER(EstimateDesc)],
-        "attpc_estimates_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(TrackEstimate)],
-        "attpc_rows_estimate": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
-                                C.POINTER(TrackEstimate)],
-    }
-    no_estimates = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in ESTIMATE_SYMBOLS)
-    for name, argtypes in estimates.items():
-        if not no_estimates:
-            getattr(lib, name).argtypes = argtypes
-    thinning = {
-        "attpc_trace_configure_thinning": [ctxp, C.POINTER(ThinDesc)],
-        "attpc_rows_thin": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(ThinDesc), C.c_int64, i64p, _dp,
-                            i64p, C.POINTER(ThinInfo), i64p],
-    }
-    no_thinning = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in THIN_SYMBOLS)
-    for name, argtypes in thinning.items():
-        if not no_thinning:
-            getattr(lib, name).argtypes = argtypes
-    no_straggling = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in STRAGGLE_SYMBOLS)
-    if not no_straggling:
-        lib.attpc_det_configure_straggling.argtypes = [ctxp, C.POINTER(StraggleDesc)]
-    circle = {
-        "attpc_trace_configure_circle": [ctxp, C.POINTER(CircleDesc)],
-        "attpc_rows_estimate_circle": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
-                                       C.POINTER(CircleDesc), C.POINTER(TrackEstimate)],
-    }
-    no_circle = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in CIRCLE_SYMBOLS)
-    for name, argtypes in circle.items():
-        if not no_circle:
-            getattr(lib, name).argtypes = argtypes
-    helix = {
-        "attpc_trace_configure_helix": [ctxp, C.POINTER(HelixDesc)],
-        "attpc_rows_estimate_helix": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
-                                      C.POINTER(CircleDesc), C.POINTER(HelixDesc), C.POINTER(TrackEstimate)],
-    }
-    no_helix = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in HELIX_SYMBOLS)
-    for name, argtypes in helix.items():
-        if not no_helix:
-            getattr(lib, name).argtypes = argtypes
-    distortion = {
-        "attpc_det_configure_distortion": [ctxp, C.POINTER(DistortDesc)],
-        "attpc_samples_distort": [ctxp, C.c_int64, _dp, C.POINTER(DistortDesc), _dp],
-    }
-    no_distortion = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in DISTORT_SYMBOLS)
-    for name, argtypes in distortion.items():
-        if not no_distortion:
-            getattr(lib, name).argtypes = argtypes
-    correction = {
-        "attpc_trace_configure_correction": [ctxp, C.POINTER(UndistortDesc)],
-        "attpc_correction_last": [ctxp, C.POINTER(UndistortInfo)],
-        "attpc_rows_undistort": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(UndistortDesc), _dp, i64p, i64p,
-                                 C.POINTER(UndistortInfo)],
-    }
-    no_correction = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in UNDISTORT_SYMBOLS)
-    for name, argtypes in correction.items():
-        if not no_correction:
-            getattr(lib, name).argtypes = argtypes
-    fit = {
-        "attpc_trace_configure_fit": [ctxp, C.POINTER(FitDesc)],
-        "attpc_fits_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(TrackFit)],
-        "attpc_rows_fit": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
-                           C.POINTER(TrackEstimate), _dp, C.POINTER(FitDesc), C.POINTER(TrackFit)],
-    }
-    no_fit = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in FIT_SYMBOLS)
-    for name, argtypes in fit.items():
-        if not no_fit:
-            getattr(lib, name).argtypes = argtypes
-    clustering = {
-        "attpc_trace_configure_clustering": [ctxp, C.POINTER(ClusterDesc)],
-        "attpc_clusters_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(ClusterEvent), C.POINTER(ClusterRecord)],
-        "attpc_cluster_labels_last": [ctxp, C.c_int64, C.c_int64, i64p],
-        "attpc_rows_cluster": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(ClusterDesc), i64p,
-                               C.POINTER(ClusterEvent), C.POINTER(ClusterRecord)],
-    }
-    no_clustering = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in CLUSTER_SYMBOLS)
-    for name, argtypes in clustering.items():
-        if not no_clustering:
-            getattr(lib, name).argtypes = argtypes
-    joining = {
-        "attpc_trace_configure_cluster_join": [ctxp, C.POINTER(JoinDesc)],
-        "attpc_joins_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(JoinEvent), C.POINTER(JoinRecord)],
-        "attpc_rows_cluster_join": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(ClusterDesc),
-                                    C.POINTER(JoinDesc), i64p, C.POINTER(ClusterEvent), C.POINTER(ClusterRecord),
-                                    C.POINTER(JoinEvent), C.POINTER(JoinRecord)],
-    }
-    no_joining = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in JOIN_SYMBOLS)
-    for name, argtypes in joining.items():
-        if not no_joining:
-            getattr(lib, name).argtypes = argtypes
-    pid = {
-        "attpc_trace_configure_pid": [ctxp, C.POINTER(PidDesc)],
-        "attpc_pid_last": [ctxp, C.c_int64, C.c_int64, C.POINTER(PidRecord)],
-        "attpc_estimates_pid": [ctxp, C.c_int64, C.c_int32, C.POINTER(TrackEstimate), C.POINTER(PidDesc),
-                                C.POINTER(PidRecord)],
-        "attpc_rows_fit_pid": [ctxp, C.c_int64, i64p, _dp, i64p, C.POINTER(EventLayout), C.POINTER(EstimateDesc),
-                               C.POINTER(TrackEstimate), _dp, C.POINTER(FitDesc), C.POINTER(PidRecord), C.POINTER(TrackFit)],
-    }
-    no_pid = bool(os.environ.get("ATTPC_HIP_LIBRARY")) and not any(hasattr(lib, name) for name in PID_SYMBOLS)
-    for name, argtypes in pid.items():
-        if not no_pid:
+    absent = set()  # the symbols of the groups a library named by ATTPC_HIP_LIBRARY lacks altogether
+    for group in SYMBOL_GROUPS.values():
+        if os.environ.get("ATTPC_HIP_LIBRARY") and not any(hasattr(lib, name) for name in group):
+            absent.update(group)
+            continue
+        for name, argtypes in group.items():
             getattr(lib, name).argtypes = argtypes
     lib.attpc_det_tracks.argtypes = [
         ctxp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EventLayout), _dp, _dp, C.c_int64,
@@ -902,16 +762,7 @@ def load_library() -> C.CDLL:
         ctxp, C.c_int64, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, _dp,
     ]
     for name in EXPORTED_SYMBOLS:
-        if ((older and name in TRACE_ROW_SYMBOLS) or (no_summary and name in SUMMARY_SYMBOLS)
-                or (no_select and name in SELECT_SYMBOLS) or (no_baseline and name in BASELINE_SYMBOLS)
-                or (no_trigger and name in TRIGGER_SYMBOLS) or (no_gain and name in GAIN_SYMBOLS)
-                or (no_common and name in COMMON_SYMBOLS) or (no_trace_pack and name in TRACE_PACK_SYMBOLS)
-                or (no_maps and name in MAPS_SYMBOLS) or (no_estimates and name in ESTIMATE_SYMBOLS)
-                or (no_thinning and name in THIN_SYMBOLS) or (no_straggling and name in STRAGGLE_SYMBOLS)
-                or (no_circle and name in CIRCLE_SYMBOLS) or (no_helix and name in HELIX_SYMBOLS)
-                or (no_distortion and name in DISTORT_SYMBOLS) or (no_correction and name in UNDISTORT_SYMBOLS)
-                or (no_fit and name in FIT_SYMBOLS) or (no_clustering and name in CLUSTER_SYMBOLS)
-                or (no_joining and name in JOIN_SYMBOLS) or (no_pid and name in PID_SYMBOLS)):
+        if name in absent:
             continue
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default -> int32 status

@@ -411,6 +411,30 @@ int32_t stage_out(attpc_ctx* ctx, T* host, const T* dev, size_t n) {
   return ATTPC_OK;
 }
 
+// What a stage behind the trace rows reads of a chunk of events: their CSR starts and the rows and labels these name.
+struct ChunkRows {
+  const int64_t* ev_start;  // [events + 1]
+  const double* rows;       // [rows][8]
+  const int64_t* labels;    // [rows], or nullptr: none
+  template <typename Args>
+  void into(Args& a) const { a.ev_start = ev_start; a.rows = rows; a.labels = labels; }
+};
+
+// Events e0 .. e1 of a host-row operator staged as its next chunk: their starts in scratch slot 2 (also left in
+// `start`), their rows in slot 0 and their labels in slot 1, each slot with room for one row at least.  Labels that are
+// nullptr: with `optional_labels` the operator works without them and reads nullptr; otherwise it has refused a call
+// with rows and no labels, so no chunk has a row, and the slot is there all the same.
+inline ChunkRows stage_rows(attpc_ctx* ctx, const int64_t* offsets, int64_t e0, int64_t e1, const double* rows,
+                            const int64_t* labels, std::vector<int64_t>* start, int32_t& rc, bool optional_labels = false) {
+  const size_t n_rows = (size_t)(offsets[e1] - offsets[e0]);
+  chunk_starts(offsets, e0, e1, start);
+  ChunkRows in{};
+  in.ev_start = stage_in(ctx, 2, start->data(), (size_t)(e1 - e0) + 1, rc);
+  in.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
+  if (labels || !optional_labels) in.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
+  return in;
+}
+
 // grow-only pinned host array: at least `n` elements, re-allocated at `alloc` (with headroom, if larger) when it grows;
 // the caller makes sure no copy in flight uses it then
 template <typename T>
@@ -483,6 +507,32 @@ int32_t begin_configure(attpc_ctx* ctx) {
 // ATTPC_E_INVALID for what a check of host_args.hpp found (a refusal without a text leaves the last error as it was)
 int32_t refuse(attpc_ctx* ctx, const ArgError& bad) {
   return bad.text.empty() ? ATTPC_E_INVALID : fail(ctx, ATTPC_E_INVALID, "%s", bad.text.c_str());
+}
+
+// attpc_trace_configure_* of a stage that is a flag and a descriptor of the context (`on`, `stored`): `d` checked by
+// `desc_error` (its refusals start with `what`), nothing in flight, then stored; nullptr turns the stage off.
+template <typename Desc>
+int32_t configure_desc(attpc_ctx* ctx, const Desc* d, const char* (*desc_error)(const Desc&), const char* what,
+                       bool attpc_ctx::*on, Desc attpc_ctx::*stored) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "%s: %s", what, bad);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->*on = d != nullptr;
+  if (d) ctx->*stored = *d;
+  return ATTPC_OK;
+}
+
+// attpc_*_last under the name `func`: records first .. first + count of a call of `events` events, `per_event` of them
+// per event, from the call's pinned array `src` to `dst` (nullptr: refused if `required`, else not wanted)
+template <typename Record>
+int32_t copy_last(attpc_ctx* ctx, const char* func, int64_t first, int64_t count, int64_t events, size_t per_event,
+                  const Record* src, Record* dst, bool required = true) {
+  if (const ArgError bad = records_range_error(func, first, count, events)) return refuse(ctx, bad);
+  if (count == 0 || per_event == 0) return ATTPC_OK;
+  if (!dst) return required ? ATTPC_E_INVALID : ATTPC_OK;
+  std::memcpy(dst, src + (size_t)first * per_event, (size_t)count * per_event * sizeof(Record));
+  return ATTPC_OK;
 }
 
 // A first track batch queued ahead for a call that does not come (another entry point, other events, a new
@@ -1239,6 +1289,27 @@ int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout
   return ATTPC_OK;
 }
 
+// What the reconstruction stages and the delivery read of the chunk in `as`: the starts of its events and its rows and
+// truth labels, the corrected ones with the drift correction on (rows and labels nullptr: no event of it has a row).
+ChunkRows chunk_rows(const attpc_ctx* ctx, const AsmSet& as) {
+  const bool corrected = ctx->correction_on;
+  return {static_cast<const int64_t*>(as.pk_ev_start.p), static_cast<const double*>(corrected ? as.uc_rows.p : as.sp_rows.p),
+          static_cast<const int64_t*>(corrected ? as.uc_labels.p : as.sp_labels.p)};
+}
+
+// The estimate kernel of n events of `a`: of raw rows or of `thinned` points, with the geometric `circle` fit, with the
+// `helix` slope.
+void launch_estimate_kernel(hipStream_t stream, uint32_t n, const EstimateArgs& a, bool thinned, bool circle, bool helix) {
+  if (helix)
+    launch_helix_estimates(stream, n, a, thinned, circle);
+  else if (circle)
+    launch_circle_estimates(stream, n, a, thinned);
+  else if (thinned)
+    launch_point_estimates(stream, n, a);
+  else
+    launch_estimates(stream, n, a);
+}
+
 // The track estimates of the chunk in `as` (n events, rows written: directly behind launch_peak_rows) on S, as.traced
 // recorded again behind them, and the copy of the records to events first_local .. of the call's pinned array on C.
 // With thinning on the rows are thinned first (thin.hip) and the estimates are those of the points; with the geometric
@@ -1254,10 +1325,7 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   }
   EstimateArgs a{};
   estimate_settings(ctx->estimates, &a);
-  a.ev_start = static_cast<const int64_t*>(as.pk_ev_start.p);
-  // (may be nullptr: then no event of the chunk has a row; with the drift correction on its rows and labels)
-  a.rows = static_cast<const double*>(ctx->correction_on ? as.uc_rows.p : as.sp_rows.p);
-  a.labels = static_cast<const int64_t*>(ctx->correction_on ? as.uc_labels.p : as.sp_labels.p);
+  chunk_rows(ctx, as).into(a);
   if (ctx->cluster_call_events >= 0) a.labels = static_cast<const int64_t*>(as.cl_labels.p);  // (clustering on: its labels)
   a.records = static_cast<attpc_track_estimate*>(as.est_records.p);
   std::memcpy(a.slot_label, ctx->est_slot_label, sizeof a.slot_label);
@@ -1278,15 +1346,8 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
     a.thin_info = t.info;
   }
   if (ctx->circle_on) circle_settings(ctx->circle, &a);
-  if (ctx->helix_on) {
-    a.helix_regressor = ctx->helix.regressor;
-    launch_helix_estimates(ctx->stream, n, a, ctx->thinning_on, ctx->circle_on);
-  } else if (ctx->circle_on)
-    launch_circle_estimates(ctx->stream, n, a, ctx->thinning_on);
-  else if (ctx->thinning_on)
-    launch_point_estimates(ctx->stream, n, a);
-  else
-    launch_estimates(ctx->stream, n, a);
+  if (ctx->helix_on) a.helix_regressor = ctx->helix.regressor;
+  launch_estimate_kernel(ctx->stream, n, a, ctx->thinning_on, ctx->circle_on, ctx->helix_on);
   HIP_TRY(ctx, hipGetLastError());
   const attpc_pid_record* pid = nullptr;
   if (ctx->pid_call) {
@@ -1378,9 +1439,7 @@ int32_t enqueue_clustering(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
   if ((rc = ensure(ctx, ctx->cl_scratch, cap * CLUSTER_SCRATCH_WORDS * sizeof(int32_t)))) return rc;
   ClusterArgs a{};
   a.s = ctx->cluster_call;
-  a.ev_start = static_cast<const int64_t*>(as.pk_ev_start.p);
-  a.rows = static_cast<const double*>(ctx->correction_on ? as.uc_rows.p : as.sp_rows.p);  // (nullptr: no event has a row)
-  a.labels = static_cast<const int64_t*>(ctx->correction_on ? as.uc_labels.p : as.sp_labels.p);
+  chunk_rows(ctx, as).into(a);
   a.scratch = static_cast<int32_t*>(ctx->cl_scratch.p);
   a.out_labels = static_cast<int64_t*>(as.cl_labels.p);
   a.events = static_cast<attpc_cluster_event*>(as.cl_events.p);
@@ -1869,13 +1928,12 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
     }
   }
   if (total > 0 && fits) {
-    const void* d_rows = ctx->correction_on ? as.uc_rows.p : as.sp_rows.p;
-    const void* d_labels = ctx->correction_on ? as.uc_labels.p : as.sp_labels.p;
+    const ChunkRows made = chunk_rows(ctx, as);
     if (o.cloud->points)
-      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->points + base * 8, d_rows, (size_t)total * 8 * sizeof(double), hipMemcpyDeviceToHost,
+      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->points + base * 8, made.rows, (size_t)total * 8 * sizeof(double), hipMemcpyDeviceToHost,
                                   ctx->stream_c));
     if (o.cloud->labels)
-      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->labels + base, d_labels, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost,
+      HIP_TRY(ctx, hipMemcpyAsync(o.cloud->labels + base, made.labels, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost,
                                   ctx->stream_c));
   }
   if (ctx->est_call_events >= 0 && (rc = enqueue_estimates(ctx, as, n, first_local))) return rc;
@@ -3088,10 +3146,7 @@ int32_t attpc_rows_undistort(attpc_ctx* ctx, int64_t n_events, const int64_t* of
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
     const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
     if (!n_rows) continue;  // (empty events: nothing to count)
-    chunk_starts(offsets, e0, e1, &start);
-    a.ev_start = stage_in(ctx, 2, start.data(), m + 1, rc);
-    a.rows = stage_in(ctx, 0, rows + offsets[e0] * 8, n_rows * 8, rc);
-    a.labels = labels ? stage_in(ctx, 1, labels + offsets[e0], n_rows, rc) : nullptr;
+    stage_rows(ctx, offsets, e0, e1, rows, labels, &start, rc, true).into(a);
     a.out_rows = stage<double>(ctx, 3, cap * 8, rc);
     a.out_labels = labels ? stage<int64_t>(ctx, 4, cap, rc) : nullptr;
     a.order = order ? stage<int64_t>(ctx, 5, cap, rc) : nullptr;
@@ -3902,11 +3957,7 @@ int32_t attpc_trigger_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_t
   if (!ctx) return ATTPC_E_INVALID;
   if (ctx->trigger_call_events < 0)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trigger_last: no trigger was configured for the last trace call");
-  if (const ArgError bad = records_range_error(__func__, first, count, ctx->trigger_call_events)) return refuse(ctx, bad);
-  if (count == 0) return ATTPC_OK;
-  if (!out) return ATTPC_E_INVALID;
-  std::memcpy(out, ctx->h_trigger.p + first, (size_t)count * sizeof(attpc_trigger_record));
-  return ATTPC_OK;
+  return copy_last(ctx, __func__, first, count, ctx->trigger_call_events, 1, ctx->h_trigger.p, out);
 }
 
 int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const int32_t* pads, const int16_t* samples,
@@ -3956,25 +4007,14 @@ int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int64_t* offs
 
 // ---- track estimates of the trace rows (estimate.hip; the contract is in include/attpc_engine.h) ----
 int32_t attpc_trace_configure_estimates(attpc_ctx* ctx, const attpc_estimate_desc* d) {
-  if (!ctx) return ATTPC_E_INVALID;
-  if (d)
-    if (const char* bad = estimate_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
-  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
-  ctx->estimates_on = d != nullptr;
-  if (d) ctx->estimates = *d;
-  return ATTPC_OK;
+  return configure_desc(ctx, d, estimate_desc_error, "estimates", &attpc_ctx::estimates_on, &attpc_ctx::estimates);
 }
 
 int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_estimate* out) {
   if (!ctx) return ATTPC_E_INVALID;
   if (ctx->est_call_events < 0)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_estimates_last: the last trace-row call made no track estimates");
-  if (const ArgError bad = records_range_error(__func__, first, count, ctx->est_call_events)) return refuse(ctx, bad);
-  const size_t n_sim = (size_t)ctx->est_call_n_sim;
-  if (count == 0 || n_sim == 0) return ATTPC_OK;
-  if (!out) return ATTPC_E_INVALID;
-  std::memcpy(out, ctx->h_estimates.p + (size_t)first * n_sim, (size_t)count * n_sim * sizeof(attpc_track_estimate));
-  return ATTPC_OK;
+  return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_estimates.p, out);
 }
 
 namespace {
@@ -4009,19 +4049,11 @@ int32_t rows_estimate(attpc_ctx* ctx, const char* func, int64_t n_events, const 
   std::vector<int64_t> start;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
-    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]);
-    chunk_starts(offsets, e0, e1, &start);
-    a.ev_start = stage_in(ctx, 2, start.data(), m + 1, rc);
-    a.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
-    a.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
+    const size_t m = (size_t)(e1 - e0);
+    stage_rows(ctx, offsets, e0, e1, rows, labels, &start, rc).into(a);
     a.records = stage<attpc_track_estimate>(ctx, 3, m * n_sim, rc);
     if (rc) return rc;
-    if (helix)
-      launch_helix_estimates(ctx->stream, (uint32_t)m, a, false, circle != nullptr);
-    else if (circle)
-      launch_circle_estimates(ctx->stream, (uint32_t)m, a, false);
-    else
-      launch_estimates(ctx->stream, (uint32_t)m, a);
+    launch_estimate_kernel(ctx->stream, (uint32_t)m, a, false, circle != nullptr, helix != nullptr);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = stage_out(ctx, out + (size_t)e0 * n_sim, a.records, m * n_sim))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -4037,13 +4069,7 @@ int32_t attpc_rows_estimate(attpc_ctx* ctx, int64_t n_events, const int64_t* off
 
 // ---- geometric circle fit (estimate.hip; the contract is in include/attpc_engine.h) ----
 int32_t attpc_trace_configure_circle(attpc_ctx* ctx, const attpc_circle_desc* d) {
-  if (!ctx) return ATTPC_E_INVALID;
-  if (d)
-    if (const char* bad = circle_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "circle: %s", bad);
-  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
-  ctx->circle_on = d != nullptr;
-  if (d) ctx->circle = *d;
-  return ATTPC_OK;
+  return configure_desc(ctx, d, circle_desc_error, "circle", &attpc_ctx::circle_on, &attpc_ctx::circle);
 }
 
 int32_t attpc_rows_estimate_circle(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
@@ -4055,13 +4081,7 @@ int32_t attpc_rows_estimate_circle(attpc_ctx* ctx, int64_t n_events, const int64
 
 // ---- helix slope (estimate.hip; the contract is in include/attpc_engine.h) ----
 int32_t attpc_trace_configure_helix(attpc_ctx* ctx, const attpc_helix_desc* d) {
-  if (!ctx) return ATTPC_E_INVALID;
-  if (d)
-    if (const char* bad = helix_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "helix: %s", bad);
-  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
-  ctx->helix_on = d != nullptr;
-  if (d) ctx->helix = *d;
-  return ATTPC_OK;
+  return configure_desc(ctx, d, helix_desc_error, "helix", &attpc_ctx::helix_on, &attpc_ctx::helix);
 }
 
 int32_t attpc_rows_estimate_helix(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
@@ -4073,13 +4093,7 @@ int32_t attpc_rows_estimate_helix(attpc_ctx* ctx, int64_t n_events, const int64_
 
 // ---- clustering (cluster.hip, cluster_host.hpp; the contract is in include/attpc_engine.h) ----
 int32_t attpc_trace_configure_clustering(attpc_ctx* ctx, const attpc_cluster_desc* d) {
-  if (!ctx) return ATTPC_E_INVALID;
-  if (d)
-    if (const char* bad = cluster_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "clustering: %s", bad);
-  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
-  ctx->cluster_on = d != nullptr;
-  if (d) ctx->cluster = *d;
-  return ATTPC_OK;
+  return configure_desc(ctx, d, cluster_desc_error, "clustering", &attpc_ctx::cluster_on, &attpc_ctx::cluster);
 }
 
 int32_t attpc_clusters_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_cluster_event* events,
@@ -4087,12 +4101,9 @@ int32_t attpc_clusters_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_
   if (!ctx) return ATTPC_E_INVALID;
   if (ctx->cluster_call_events < 0)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_clusters_last: the clustering was off for the last trace-row call");
-  if (const ArgError bad = records_range_error(__func__, first, count, ctx->cluster_call_events)) return refuse(ctx, bad);
-  if (count == 0) return ATTPC_OK;
-  if (events) std::memcpy(events, ctx->h_cl_events.p + (size_t)first, (size_t)count * sizeof(attpc_cluster_event));
-  if (records)
-    std::memcpy(records, ctx->h_cl_records.p + (size_t)first * ATTPC_MAX_SIM, (size_t)count * ATTPC_MAX_SIM * sizeof(attpc_cluster_record));
-  return ATTPC_OK;
+  if (const int32_t rc = copy_last(ctx, __func__, first, count, ctx->cluster_call_events, 1, ctx->h_cl_events.p, events, false))
+    return rc;
+  return copy_last(ctx, __func__, first, count, ctx->cluster_call_events, ATTPC_MAX_SIM, ctx->h_cl_records.p, records, false);
 }
 
 int32_t attpc_cluster_labels_last(attpc_ctx* ctx, int64_t first_row, int64_t count, int64_t* out) {
@@ -4136,10 +4147,7 @@ int32_t rows_cluster(attpc_ctx* ctx, const char* func, int64_t n_events, const i
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
     const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
-    chunk_starts(offsets, e0, e1, &start);
-    a.ev_start = stage_in(ctx, 2, start.data(), m + 1, rc);
-    a.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
-    a.labels = labels ? stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1) : nullptr;
+    stage_rows(ctx, offsets, e0, e1, rows, labels, &start, rc, true).into(a);
     a.out_labels = stage<int64_t>(ctx, 3, cap, rc);
     a.events = stage<attpc_cluster_event>(ctx, 4, m, rc);
     a.records = stage<attpc_cluster_record>(ctx, 5, m * ATTPC_MAX_SIM, rc);
@@ -4178,25 +4186,16 @@ int32_t attpc_rows_cluster(attpc_ctx* ctx, int64_t n_events, const int64_t* offs
 
 // ---- cluster joining (cluster_join.hip, join_host.hpp; the contract is in include/attpc_engine.h) ----
 int32_t attpc_trace_configure_cluster_join(attpc_ctx* ctx, const attpc_join_desc* d) {
-  if (!ctx) return ATTPC_E_INVALID;
-  if (d)
-    if (const char* bad = join_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "cluster joining: %s", bad);
-  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
-  ctx->join_on = d != nullptr;
-  if (d) ctx->join = *d;
-  return ATTPC_OK;
+  return configure_desc(ctx, d, join_desc_error, "cluster joining", &attpc_ctx::join_on, &attpc_ctx::join);
 }
 
 int32_t attpc_joins_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_join_event* events, attpc_join_record* records) {
   if (!ctx) return ATTPC_E_INVALID;
   if (ctx->cluster_call_events < 0 || !ctx->join_call)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_joins_last: the cluster joining or the clustering was off for the last trace-row call");
-  if (const ArgError bad = records_range_error(__func__, first, count, ctx->cluster_call_events)) return refuse(ctx, bad);
-  if (count == 0) return ATTPC_OK;
-  if (events) std::memcpy(events, ctx->h_jn_events.p + (size_t)first, (size_t)count * sizeof(attpc_join_event));
-  if (records)
-    std::memcpy(records, ctx->h_jn_records.p + (size_t)first * ATTPC_MAX_SIM, (size_t)count * ATTPC_MAX_SIM * sizeof(attpc_join_record));
-  return ATTPC_OK;
+  if (const int32_t rc = copy_last(ctx, __func__, first, count, ctx->cluster_call_events, 1, ctx->h_jn_events.p, events, false))
+    return rc;
+  return copy_last(ctx, __func__, first, count, ctx->cluster_call_events, ATTPC_MAX_SIM, ctx->h_jn_records.p, records, false);
 }
 
 int32_t attpc_rows_cluster_join(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
@@ -4210,25 +4209,14 @@ int32_t attpc_rows_cluster_join(attpc_ctx* ctx, int64_t n_events, const int64_t*
 
 // ---- track fit (fit.hip; the contract is in include/attpc_engine.h) ----
 int32_t attpc_trace_configure_fit(attpc_ctx* ctx, const attpc_fit_desc* d) {
-  if (!ctx) return ATTPC_E_INVALID;
-  if (d)
-    if (const char* bad = fit_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "fit: %s", bad);
-  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
-  ctx->fit_on = d != nullptr;
-  if (d) ctx->fit = *d;
-  return ATTPC_OK;
+  return configure_desc(ctx, d, fit_desc_error, "fit", &attpc_ctx::fit_on, &attpc_ctx::fit);
 }
 
 int32_t attpc_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_fit* out) {
   if (!ctx) return ATTPC_E_INVALID;
   if (ctx->est_call_events < 0 || !ctx->fit_call)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_fits_last: the last trace-row call made no track fits");
-  if (const ArgError bad = records_range_error(__func__, first, count, ctx->est_call_events)) return refuse(ctx, bad);
-  const size_t n_sim = (size_t)ctx->est_call_n_sim;
-  if (count == 0 || n_sim == 0) return ATTPC_OK;
-  if (!out) return ATTPC_E_INVALID;
-  std::memcpy(out, ctx->h_fits.p + (size_t)first * n_sim, (size_t)count * n_sim * sizeof(attpc_track_fit));
-  return ATTPC_OK;
+  return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_fits.p, out);
 }
 
 namespace {
@@ -4268,11 +4256,8 @@ int32_t rows_fit(attpc_ctx* ctx, const char* func, int64_t n_events, const int64
   std::vector<int64_t> first;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
-    const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]);
-    chunk_starts(offsets, e0, e1, &first);
-    a.ev_start = stage_in(ctx, 2, first.data(), m + 1, rc);
-    a.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
-    a.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
+    const size_t m = (size_t)(e1 - e0);
+    stage_rows(ctx, offsets, e0, e1, rows, labels, &first, rc).into(a);
     a.records = const_cast<attpc_track_estimate*>(stage_in(ctx, 3, estimates_in + (size_t)e0 * n_sim, m * n_sim, rc));
     const double* d_start = start ? stage_in(ctx, 4, start + (size_t)e0 * n_sim * 6, m * n_sim * 6, rc) : nullptr;
     attpc_track_fit* d_out = stage<attpc_track_fit>(ctx, 5, m * n_sim, rc);
@@ -4325,12 +4310,7 @@ int32_t attpc_pid_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_pid_r
   if (!ctx) return ATTPC_E_INVALID;
   if (ctx->est_call_events < 0 || !ctx->pid_call)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_pid_last: the last trace-row call made no particle identification");
-  if (const ArgError bad = records_range_error(__func__, first, count, ctx->est_call_events)) return refuse(ctx, bad);
-  const size_t n_sim = (size_t)ctx->est_call_n_sim;
-  if (count == 0 || n_sim == 0) return ATTPC_OK;
-  if (!out) return ATTPC_E_INVALID;
-  std::memcpy(out, ctx->h_pid.p + (size_t)first * n_sim, (size_t)count * n_sim * sizeof(attpc_pid_record));
-  return ATTPC_OK;
+  return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_pid.p, out);
 }
 
 int32_t attpc_estimates_pid(attpc_ctx* ctx, int64_t n_events, int32_t n_sim, const attpc_track_estimate* estimates,
@@ -4360,13 +4340,7 @@ int32_t attpc_estimates_pid(attpc_ctx* ctx, int64_t n_events, int32_t n_sim, con
 
 // ---- thinned track points (thin.hip; the contract is in include/attpc_engine.h) ----
 int32_t attpc_trace_configure_thinning(attpc_ctx* ctx, const attpc_thin_desc* d) {
-  if (!ctx) return ATTPC_E_INVALID;
-  if (d)
-    if (const char* bad = thin_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "thinning: %s", bad);
-  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
-  ctx->thinning_on = d != nullptr;
-  if (d) ctx->thinning = *d;
-  return ATTPC_OK;
+  return configure_desc(ctx, d, thin_desc_error, "thinning", &attpc_ctx::thinning_on, &attpc_ctx::thinning);
 }
 
 int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
@@ -4402,10 +4376,7 @@ int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
     const size_t m = (size_t)(e1 - e0), n_rows = (size_t)(offsets[e1] - offsets[e0]), cap = std::max<size_t>(n_rows, 1);
-    chunk_starts(offsets, e0, e1, &start);
-    a.ev_start = stage_in(ctx, 2, start.data(), m + 1, rc);
-    a.rows = stage_in(ctx, 0, n_rows ? rows + offsets[e0] * 8 : nullptr, n_rows * 8, rc, 8);
-    a.labels = stage_in(ctx, 1, n_rows ? labels + offsets[e0] : nullptr, n_rows, rc, 1);
+    stage_rows(ctx, offsets, e0, e1, rows, labels, &start, rc).into(a);
     a.points = stage<ThinPoint>(ctx, 3, cap, rc);
     a.info = stage<attpc_thin_info>(ctx, 4, m * n_sim, rc);
     if (rc) return rc;

@@ -15,7 +15,7 @@ import numpy as np
 from .. import _abi
 from .._abi import (CIRCLE_DEFAULT_EVALUATIONS, CIRCLE_DEFAULT_TOLERANCE, CIRCLE_MAX_EVALUATIONS,  # noqa: F401
                     CIRCLE_MIN_EVALUATIONS, EST_NOT_CONVERGED)
-from .traces import configure_stage
+from .stage import checked, configure_stage
 
 
 class CircleFitSettings:
@@ -43,18 +43,12 @@ class CircleFitSettings:
         return _abi.CircleDesc(self.tolerance, self.max_evaluations, 0)
 
 
-def _checked(circle):
-    if circle is not None and not isinstance(circle, CircleFitSettings):
-        raise TypeError(f"circle must be a CircleFitSettings or None, got {type(circle).__name__}")
-    return circle
-
-
 def configure_circle(ctx: _abi.Context, circle: CircleFitSettings | None) -> None:
     """``attpc_trace_configure_circle`` unless this ctx already holds the same settings (``None``: the stage off)."""
-    configure_stage(ctx, CircleFitSettings, _checked(circle))
+    configure_stage(ctx, CircleFitSettings, checked(CircleFitSettings, circle, "circle"))
 
 
-def circle_result(ctx: _abi.Context) -> dict:
+def circle_result(ctx: _abi.Context, n_events: int = 0, n_sim: int = 0, n_rows=None) -> dict:
     """``{"circle": "geometric"}`` if the ctx holds both the estimates and the circle fit -- the circles of its last
     trace-row call are then the refined ones --, else {}."""
     return {"circle": "geometric"} if ctx._tokens["circle"] is not None and ctx._tokens["estimates"] is not None else {}

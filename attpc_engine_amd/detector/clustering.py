@@ -16,7 +16,8 @@ import numpy as np
 
 from .. import _abi
 from .._abi import CLUSTER_CAPPED, CLUSTER_DTYPE, CLUSTER_EVENT_DTYPE, CLUSTER_INTERNAL  # noqa: F401
-from .traces import configure_stage
+from .stage import checked, configure_stage, host_rows
+from .stage import layout as _layout
 
 STATUS_BITS = {"CAPPED": CLUSTER_CAPPED, "INTERNAL": CLUSTER_INTERNAL}
 MATCH = {"truth": _abi.CLUSTER_MATCH_TRUTH, "rank": _abi.CLUSTER_MATCH_RANK}
@@ -68,15 +69,9 @@ class ClusterSettings:
                                 MATCH[self.match])
 
 
-def _checked(clustering):
-    if clustering is not None and not isinstance(clustering, ClusterSettings):
-        raise TypeError(f"clustering must be a ClusterSettings or None, got {type(clustering).__name__}")
-    return clustering
-
-
 def configure_clustering(ctx: _abi.Context, clustering: ClusterSettings | None) -> None:
     """``attpc_trace_configure_clustering`` unless this ctx already holds the same settings (``None``: the stage off)."""
-    configure_stage(ctx, ClusterSettings, _checked(clustering))
+    configure_stage(ctx, ClusterSettings, checked(ClusterSettings, clustering, "clustering"))
 
 
 def clusters_last(ctx: _abi.Context, n_events: int):
@@ -98,7 +93,7 @@ def cluster_labels_last(ctx: _abi.Context, n_rows: int) -> np.ndarray:
     return labels
 
 
-def clustering_result(ctx: _abi.Context, n_events: int, n_rows: int | None = None) -> dict:
+def clustering_result(ctx: _abi.Context, n_events: int, n_sim: int = 0, n_rows: int | None = None) -> dict:
     """``{"clusters": (events, records)}`` of ctx's last trace-row call if the ctx holds the stage, else {}; with
     ``n_rows`` (the rows the call fetched) also ``"cluster_labels"`` [n_rows]."""
     if ctx._tokens["clustering"] is None:
@@ -115,22 +110,10 @@ def rows_to_clusters(offsets, rows, labels, indices, settings: ClusterSettings, 
     nondecreasing z: ValueError otherwise, from the library), labels [R] the truth labels or None (then nobody votes),
     ``indices`` (the nucleus of every track position, or an ``_abi.EventLayout``) -> (cluster_labels [R], events [n]
     ``CLUSTER_EVENT_DTYPE``, records [n, 8] ``CLUSTER_DTYPE``).  Rows outside offsets[0] .. offsets[n] get -1."""
-    from .estimate import _layout
-
     if not isinstance(settings, ClusterSettings):
         raise TypeError("rows_to_clusters needs a ClusterSettings")
-    layout = indices if isinstance(indices, _abi.EventLayout) else _layout(indices)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    if offsets.ndim != 1 or len(offsets) < 1 or np.any(np.diff(offsets) < 0) or offsets[0] < 0:
-        raise ValueError("offsets must be n + 1 non-decreasing row numbers >= 0")
-    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 8)
-    if labels is not None:
-        labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
-        if len(rows) != len(labels):
-            raise ValueError(f"{len(rows)} rows, {len(labels)} labels")
-    if int(offsets[-1]) > len(rows):
-        raise ValueError(f"{len(rows)} rows, offsets up to {int(offsets[-1])}")
-    n = len(offsets) - 1
+    layout = _layout(indices)
+    offsets, rows, labels, n = host_rows(offsets, rows, labels, optional_labels=True)
     out = np.full(len(rows), -1, dtype=np.int64)
     events = np.zeros(n, dtype=CLUSTER_EVENT_DTYPE)
     records = np.zeros((n, _abi.MAX_SIM), dtype=CLUSTER_DTYPE)

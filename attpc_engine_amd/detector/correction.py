@@ -16,6 +16,7 @@ import numpy as np
 
 from .. import _abi
 from .distortion import DistortionMap
+from .stage import checked, host_rows
 
 MAX_ITERATIONS = 64
 COUNTS = ("n_rows", "n_skipped", "n_unconverged", "n_moved")
@@ -74,24 +75,18 @@ class CorrectionSettings:
         return _abi.UndistortDesc(self.map.desc(config), win, mm, length, self.iterations, self.tolerance_xy, self.tolerance_tb)
 
 
-def _checked(correction):
-    if correction is not None and not isinstance(correction, CorrectionSettings):
-        raise TypeError(f"correction must be a CorrectionSettings or None, got {type(correction).__name__}")
-    return correction
-
-
 def configure_correction(ctx: _abi.Context, correction: CorrectionSettings | None, config=None) -> None:
     """``attpc_trace_configure_correction`` unless this ctx already holds the same settings in the same drift (``None``,
     or a map that is zero everywhere: the stage off).  ``config``: the run's Config, whose time-bucket edges and length
     place the map's nodes and give a corrected time its z."""
-    correction = _checked(correction)
+    correction = checked(CorrectionSettings, correction, "correction")
     token = None
     if correction is not None and correction.on:
         token = correction.token(config)
     ctx.configure(CorrectionSettings.slot, token, CorrectionSettings.call, None if token is None else correction.desc(config))
 
 
-def correction_result(ctx: _abi.Context) -> dict:
+def correction_result(ctx: _abi.Context, n_events: int = 0, n_sim: int = 0, n_rows=None) -> dict:
     """``{"correction": {n_rows, n_skipped, n_unconverged, n_moved}}`` of the ctx's last trace-row call if it holds the
     stage, else {}."""
     return {"correction": ctx.correction_last()} if ctx._tokens["correction"] is not None else {}
@@ -103,17 +98,10 @@ def rows_to_correction(offsets, rows, labels, correction: CorrectionSettings, co
     (rows [R,8] corrected and, per event, in ascending corrected z, labels [R] moved with them, order [R] = the input row
     of every output row, {n_rows, n_skipped, n_unconverged, n_moved}).  A map that shifts nothing runs like any other.
     It leaves the configured stage of ``ctx`` as it is."""
-    if _checked(correction) is None:
+    if checked(CorrectionSettings, correction, "correction") is None:
         raise TypeError("rows_to_correction needs a CorrectionSettings")
     desc = correction.desc(config)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    if offsets.ndim != 1 or len(offsets) < 1 or np.any(np.diff(offsets) < 0) or offsets[0] < 0:
-        raise ValueError("offsets must be n + 1 non-decreasing row numbers >= 0")
-    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 8)
-    labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
-    if len(rows) != len(labels) or int(offsets[-1]) > len(rows):
-        raise ValueError(f"{len(rows)} rows, {len(labels)} labels, offsets up to {int(offsets[-1])}")
-    n = len(offsets) - 1
+    offsets, rows, labels, n = host_rows(offsets, rows, labels)
     # (rows outside offsets[0] .. offsets[n] belong to no event: they come back as they are, in their place)
     out_rows, out_labels = rows.copy(), labels.copy()
     order = np.arange(len(rows), dtype=np.int64)

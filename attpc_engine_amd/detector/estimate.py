@@ -17,7 +17,9 @@ import numpy as np
 from .. import _abi
 from .._abi import (ESTIMATE_DTYPE, EST_CAPPED, EST_EMPTY, EST_FEW, EST_MAX_FIT, EST_NOT_CONVERGED, EST_NO_CIRCLE,  # noqa: F401
                     EST_NO_HELIX, EST_NO_SLOPE, EST_ON_AXIS, EST_RANGE)
-from .traces import configure_stage
+from .circle import CircleFitSettings
+from .stage import checked, configure_stage, host_rows
+from .stage import layout as _layout
 
 STATUS_BITS = {"EMPTY": EST_EMPTY, "FEW": EST_FEW, "RANGE": EST_RANGE, "CAPPED": EST_CAPPED, "NO_CIRCLE": EST_NO_CIRCLE,
                "ON_AXIS": EST_ON_AXIS, "NO_SLOPE": EST_NO_SLOPE, "NOT_CONVERGED": EST_NOT_CONVERGED}
@@ -63,34 +65,17 @@ class EstimateSettings:
         return _abi.EstimateDesc(*self.token(), 0)
 
 
-def _checked(estimates):
-    if estimates is not None and not isinstance(estimates, EstimateSettings):
-        raise TypeError(f"estimates must be an EstimateSettings or None, got {type(estimates).__name__}")
-    return estimates
-
-
 def configure_estimates(ctx: _abi.Context, estimates: EstimateSettings | None, config=None) -> None:
     """``attpc_trace_configure_estimates`` unless this ctx already holds the same settings (``None``: the stage off);
     the field is ``config.det_params.bfield`` unless the settings carry one."""
-    if _checked(estimates) is not None and config is not None:
+    if checked(EstimateSettings, estimates, "estimates") is not None and config is not None:
         estimates = estimates.for_field(config.det_params.bfield)
     configure_stage(ctx, EstimateSettings, estimates)
 
 
-def estimates_result(ctx: _abi.Context, n_events: int, n_sim: int) -> dict:
+def estimates_result(ctx: _abi.Context, n_events: int, n_sim: int, n_rows=None) -> dict:
     """``{"estimates": records [n_events, n_sim]}`` of ctx's last trace-row call if the ctx holds the stage, else {}."""
     return {"estimates": ctx.estimates_last(n_events, n_sim)} if ctx._tokens["estimates"] is not None else {}
-
-
-def _layout(indices) -> _abi.EventLayout:
-    indices = [int(i) for i in indices]
-    if len(indices) > _abi.MAX_SIM or any(not 0 <= i < _abi.MAX_ROWS for i in indices):
-        raise ValueError(f"indices must be at most {_abi.MAX_SIM} rows in 0 .. {_abi.MAX_ROWS - 1}, got {indices}")
-    layout = _abi.EventLayout()
-    layout.n_rows, layout.n_sim = _abi.MAX_ROWS, len(indices)
-    for s, i in enumerate(indices):
-        layout.indices[s] = i
-    return layout
 
 
 def rows_to_estimates(offsets, rows, labels, indices, settings: EstimateSettings, ctx: _abi.Context | None = None,
@@ -102,25 +87,17 @@ def rows_to_estimates(offsets, rows, labels, indices, settings: EstimateSettings
     off): the geometric circle fit behind the Kasa circle (``attpc_rows_estimate_circle``).  ``helix`` (a
     ``detector.helix.HelixSlopeSettings``; None = off): the helix slope behind the circle, with or without ``circle``
     (``attpc_rows_estimate_helix``)."""
-    from .circle import _checked as _checked_circle
-    from .helix import _checked as _checked_helix
+    from .helix import HelixSlopeSettings  # (that module reads the STATUS_BITS of this one)
 
     if not isinstance(settings, EstimateSettings):
         raise TypeError("settings must be an EstimateSettings")
-    _checked_circle(circle)
-    _checked_helix(helix)
+    checked(CircleFitSettings, circle, "circle")
+    checked(HelixSlopeSettings, helix, "helix")
     if config is not None:
         settings = settings.for_field(config.det_params.bfield)
     desc = settings.desc()
     layout = _layout(indices)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    if offsets.ndim != 1 or len(offsets) < 1 or np.any(np.diff(offsets) < 0) or offsets[0] < 0:
-        raise ValueError("offsets must be n + 1 non-decreasing row numbers >= 0")
-    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 8)
-    labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
-    if len(rows) != len(labels) or int(offsets[-1]) > len(rows):
-        raise ValueError(f"{len(rows)} rows, {len(labels)} labels, offsets up to {int(offsets[-1])}")
-    n = len(offsets) - 1
+    offsets, rows, labels, n = host_rows(offsets, rows, labels)
     records = np.empty((n, layout.n_sim), dtype=ESTIMATE_DTYPE)
     ctx = ctx or _abi.default_context()
     if helix is not None:

@@ -14,7 +14,9 @@ import numpy as np
 from .. import _abi
 from .._abi import (FIT_CAPPED, FIT_DTYPE, FIT_EMPTY, FIT_FEW, FIT_NO_START, FIT_NOT_CONVERGED, FIT_SINGULAR,  # noqa: F401
                     FIT_STEP_CAP)
-from .traces import configure_stage
+from .estimate import EstimateSettings
+from .stage import checked, configure_stage, host_rows
+from .stage import layout as _layout
 
 STATUS_BITS = {"EMPTY": FIT_EMPTY, "FEW": FIT_FEW, "CAPPED": FIT_CAPPED, "NO_START": FIT_NO_START,
                "SINGULAR": FIT_SINGULAR, "STEP_CAP": FIT_STEP_CAP, "NOT_CONVERGED": FIT_NOT_CONVERGED}
@@ -61,9 +63,7 @@ class TrackFitSettings:
 
 
 def _checked(fit):
-    if fit is not None and not isinstance(fit, TrackFitSettings):
-        raise TypeError(f"fit must be a TrackFitSettings or None, got {type(fit).__name__}")
-    return fit
+    return checked(TrackFitSettings, fit, "fit")
 
 
 def configure_track_fit(ctx: _abi.Context, fit: TrackFitSettings | None) -> None:
@@ -78,28 +78,12 @@ def fits_last(ctx: _abi.Context, n_events: int, n_sim: int) -> np.ndarray:
     return records
 
 
-def fit_result(ctx: _abi.Context, n_events: int, n_sim: int) -> dict:
+def fit_result(ctx: _abi.Context, n_events: int, n_sim: int, n_rows=None) -> dict:
     """``{"fits": records [n_events, n_sim]}`` of ctx's last trace-row call if the ctx holds both the estimates and the
     track fit, else {}."""
     if ctx._tokens["fit"] is None or ctx._tokens["estimates"] is None:
         return {}
     return {"fits": fits_last(ctx, n_events, n_sim)}
-
-
-def _layout(indices, species_of_row) -> _abi.EventLayout:
-    if isinstance(indices, _abi.EventLayout):
-        return indices
-    if species_of_row is None:
-        raise ValueError("rows_to_fit needs an EventLayout, or indices with species_of_row")
-    from .estimate import _layout as estimate_layout
-
-    layout = estimate_layout(indices)
-    species = [int(v) for v in species_of_row]
-    if len(species) > _abi.MAX_ROWS:
-        raise ValueError(f"species_of_row holds at most {_abi.MAX_ROWS} rows")
-    for row in range(_abi.MAX_ROWS):
-        layout.species_of_row[row] = species[row] if row < len(species) else -1
-    return layout
 
 
 def rows_to_fit(offsets, rows, labels, indices, estimates, ctx: _abi.Context, settings: TrackFitSettings, start=None, *,
@@ -113,8 +97,6 @@ def rows_to_fit(offsets, rows, labels, indices, estimates, ctx: _abi.Context, se
     ``detector.pid.estimates_to_pid`` on the same estimates): the fit behind the particle identification
     (``attpc_rows_fit_pid``) -- slot k is fitted as the nucleus of position ``pid["position"][e, k]``, and a slot without
     a position gets the record without a fit, ``FIT_NO_PID``."""
-    from .estimate import EstimateSettings
-
     if not isinstance(settings, TrackFitSettings):
         raise TypeError("settings must be a TrackFitSettings")
     estimate_settings = estimate_settings or EstimateSettings(magnetic_field=0.0)
@@ -122,15 +104,10 @@ def rows_to_fit(offsets, rows, labels, indices, estimates, ctx: _abi.Context, se
         raise TypeError("estimate_settings must be an EstimateSettings")
     if estimate_settings.magnetic_field is None:
         estimate_settings = estimate_settings.for_field(0.0)  # (the fit reads the field of the detector, not this one)
+    if species_of_row is None and not isinstance(indices, _abi.EventLayout):
+        raise ValueError("rows_to_fit needs an EventLayout, or indices with species_of_row")
     layout = _layout(indices, species_of_row)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    if offsets.ndim != 1 or len(offsets) < 1 or np.any(np.diff(offsets) < 0) or offsets[0] < 0:
-        raise ValueError("offsets must be n + 1 non-decreasing row numbers >= 0")
-    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 8)
-    labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
-    if len(rows) != len(labels) or int(offsets[-1]) > len(rows):
-        raise ValueError(f"{len(rows)} rows, {len(labels)} labels, offsets up to {int(offsets[-1])}")
-    n = len(offsets) - 1
+    offsets, rows, labels, n = host_rows(offsets, rows, labels)
     estimates = np.ascontiguousarray(estimates, dtype=_abi.ESTIMATE_DTYPE)
     if estimates.shape != (n, layout.n_sim):
         raise ValueError(f"estimates must be [{n}, {layout.n_sim}], got {estimates.shape}")

@@ -13,9 +13,8 @@ import numpy as np
 
 from .. import _abi
 from .._abi import EST_NO_HELIX, HELIX_AUTO, HELIX_PATH_ON_Z, HELIX_Z_ON_PATH  # noqa: F401
-from .traces import configure_stage
-
 from .estimate import STATUS_BITS as _ESTIMATE_BITS
+from .stage import checked, configure_stage
 
 REGRESSORS = {"auto": HELIX_AUTO, "z_on_path": HELIX_Z_ON_PATH, "path_on_z": HELIX_PATH_ON_Z}
 # the status bits of a record made with the stage on: those of ``detector.estimate.STATUS_BITS`` and NO_HELIX
@@ -47,18 +46,12 @@ class HelixSlopeSettings:
         return _abi.HelixDesc(self.regressor, 0)
 
 
-def _checked(helix):
-    if helix is not None and not isinstance(helix, HelixSlopeSettings):
-        raise TypeError(f"helix must be a HelixSlopeSettings or None, got {type(helix).__name__}")
-    return helix
-
-
 def configure_helix(ctx: _abi.Context, helix: HelixSlopeSettings | None) -> None:
     """``attpc_trace_configure_helix`` unless this ctx already holds the same settings (``None``: the stage off)."""
-    configure_stage(ctx, HelixSlopeSettings, _checked(helix))
+    configure_stage(ctx, HelixSlopeSettings, checked(HelixSlopeSettings, helix, "helix"))
 
 
-def helix_result(ctx: _abi.Context) -> dict:
+def helix_result(ctx: _abi.Context, n_events: int = 0, n_sim: int = 0, n_rows=None) -> dict:
     """``{"slope": "helix"}`` if the ctx holds both the estimates and the helix slope -- the slopes of its last
     trace-row call are then the helix's --, else {}."""
     return {"slope": "helix"} if ctx._tokens["helix"] is not None and ctx._tokens["estimates"] is not None else {}

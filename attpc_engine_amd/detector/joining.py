@@ -18,7 +18,8 @@ import numpy as np
 from .. import _abi
 from .._abi import JOIN_CAPPED, JOIN_DTYPE, JOIN_EVENT_DTYPE, JOIN_NOT_CLUSTERED  # noqa: F401
 from .clustering import ClusterSettings
-from .traces import configure_stage
+from .stage import checked, configure_stage, host_rows
+from .stage import layout as _layout
 
 STATUS_BITS = {"CAPPED": JOIN_CAPPED, "NOT_CLUSTERED": JOIN_NOT_CLUSTERED}
 RADIUS_MIN, RADIUS_MAX = 1.0 / 16.0, 5000.0  # mm
@@ -63,15 +64,9 @@ class JoinSettings:
                              self.max_clusters)
 
 
-def _checked(join):
-    if join is not None and not isinstance(join, JoinSettings):
-        raise TypeError(f"join must be a JoinSettings or None, got {type(join).__name__}")
-    return join
-
-
 def configure_cluster_join(ctx: _abi.Context, join: JoinSettings | None) -> None:
     """``attpc_trace_configure_cluster_join`` unless this ctx already holds the same settings (``None``: the stage off)."""
-    configure_stage(ctx, JoinSettings, _checked(join))
+    configure_stage(ctx, JoinSettings, checked(JoinSettings, join, "join"))
 
 
 def joins_last(ctx: _abi.Context, n_events: int):
@@ -84,7 +79,7 @@ def joins_last(ctx: _abi.Context, n_events: int):
     return events, records
 
 
-def join_result(ctx: _abi.Context, n_events: int) -> dict:
+def join_result(ctx: _abi.Context, n_events: int, n_sim: int = 0, n_rows=None) -> dict:
     """``{"joins": (events, records)}`` of ctx's last trace-row call if the ctx holds this stage and the clustering,
     else {}."""
     if ctx._tokens["cluster_join"] is None or ctx._tokens["clustering"] is None:
@@ -98,24 +93,12 @@ def rows_to_joined_clusters(offsets, rows, labels, indices, clustering: ClusterS
     the fused path, no other configuration needed), arguments as ``rows_to_clusters`` -> (cluster_labels [R], events [n]
     ``CLUSTER_EVENT_DTYPE``, records [n, 8] ``CLUSTER_DTYPE``, join_events [n] ``JOIN_EVENT_DTYPE``, join_records [n, 8]
     ``JOIN_DTYPE``).  Rows outside offsets[0] .. offsets[n] get -1."""
-    from .estimate import _layout
-
     if not isinstance(clustering, ClusterSettings):
         raise TypeError("rows_to_joined_clusters needs a ClusterSettings")
     if not isinstance(join, JoinSettings):
         raise TypeError("rows_to_joined_clusters needs a JoinSettings")
-    layout = indices if isinstance(indices, _abi.EventLayout) else _layout(indices)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    if offsets.ndim != 1 or len(offsets) < 1 or np.any(np.diff(offsets) < 0) or offsets[0] < 0:
-        raise ValueError("offsets must be n + 1 non-decreasing row numbers >= 0")
-    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 8)
-    if labels is not None:
-        labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
-        if len(rows) != len(labels):
-            raise ValueError(f"{len(rows)} rows, {len(labels)} labels")
-    if int(offsets[-1]) > len(rows):
-        raise ValueError(f"{len(rows)} rows, offsets up to {int(offsets[-1])}")
-    n = len(offsets) - 1
+    layout = _layout(indices)
+    offsets, rows, labels, n = host_rows(offsets, rows, labels, optional_labels=True)
     out = np.full(len(rows), -1, dtype=np.int64)
     events = np.zeros(n, dtype=_abi.CLUSTER_EVENT_DTYPE)
     records = np.zeros((n, _abi.MAX_SIM), dtype=_abi.CLUSTER_DTYPE)

@@ -20,6 +20,7 @@ import numpy as np
 from .. import _abi
 from ..outputs import SummaryArrays
 from .parameters import Config
+from .stage import configure_stage
 
 OTHER_LABELS = 1 << _abi.MAX_SIM            # the mask bit of rows whose label is in no position of ``indices``
 FULL_MASK = (OTHER_LABELS << 1) - 1         # every position and the other labels
@@ -114,8 +115,6 @@ class RunMaps:
 def configure_maps(ctx: _abi.Context, maps: MapsSettings | None = None, **parameters) -> MapsSettings | None:
     """``attpc_maps_configure`` unless this ctx already holds the same settings (decided on their content): a
     ``MapsSettings`` or its keywords; neither turns the mode off."""
-    from .traces import configure_stage
-
     if maps is not None and parameters:
         raise TypeError("give a MapsSettings or its keywords, not both")
     if parameters:

@@ -17,7 +17,7 @@ import numpy as np
 from .. import _abi
 from .._abi import (FIT_NO_PID, PID_AMBIGUOUS, PID_ANY, PID_DTYPE, PID_MAX_VERTICES, PID_NO_ESTIMATE, PID_NONE,  # noqa: F401
                     PID_OWN, PID_TAKEN)
-from .traces import configure_stage
+from .stage import checked, configure_stage
 
 STATUS_BITS = {"NO_ESTIMATE": PID_NO_ESTIMATE, "NONE": PID_NONE, "TAKEN": PID_TAKEN, "AMBIGUOUS": PID_AMBIGUOUS}
 MODES = {"any": PID_ANY, "own": PID_OWN}
@@ -153,15 +153,9 @@ class PidSettings:
         return desc
 
 
-def _checked(pid):
-    if pid is not None and not isinstance(pid, PidSettings):
-        raise TypeError(f"pid must be a PidSettings or None, got {type(pid).__name__}")
-    return pid
-
-
 def configure_pid(ctx: _abi.Context, pid: PidSettings | None) -> None:
     """``attpc_trace_configure_pid`` unless this ctx already holds the same settings (``None``: the stage off)."""
-    configure_stage(ctx, PidSettings, _checked(pid))
+    configure_stage(ctx, PidSettings, checked(PidSettings, pid, "pid"))
 
 
 def pid_last(ctx: _abi.Context, n_events: int, n_sim: int) -> np.ndarray:
@@ -172,7 +166,7 @@ def pid_last(ctx: _abi.Context, n_events: int, n_sim: int) -> np.ndarray:
     return records
 
 
-def pid_result(ctx: _abi.Context, n_events: int, n_sim: int) -> dict:
+def pid_result(ctx: _abi.Context, n_events: int, n_sim: int, n_rows=None) -> dict:
     """``{"pid": records [n_events, n_sim]}`` of ctx's last trace-row call if the ctx holds both the estimates and this
     stage, else {}."""
     if ctx._tokens["pid"] is None or ctx._tokens["estimates"] is None:

@@ -17,7 +17,7 @@ import numpy as np
 
 from .. import _abi
 from .constants import AVOGADRO
-from .traces import configure_stage
+from .stage import configure_stage
 
 
 def _number(what: str, value) -> float:

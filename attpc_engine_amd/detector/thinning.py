@@ -13,8 +13,8 @@ import numpy as np
 
 from .. import _abi
 from .._abi import THIN_INFO_DTYPE, THIN_MAX_RUN  # noqa: F401
-from .estimate import _layout
-from .traces import configure_stage
+from .stage import checked, configure_stage, host_rows
+from .stage import layout as _layout
 
 
 class ThinSettings:
@@ -37,18 +37,12 @@ class ThinSettings:
         return _abi.ThinDesc(self.z_step, 0, 0)
 
 
-def _checked(thinning):
-    if thinning is not None and not isinstance(thinning, ThinSettings):
-        raise TypeError(f"thinning must be a ThinSettings or None, got {type(thinning).__name__}")
-    return thinning
-
-
 def configure_thinning(ctx: _abi.Context, thinning: ThinSettings | None) -> None:
     """``attpc_trace_configure_thinning`` unless this ctx already holds the same settings (``None``: the stage off)."""
-    configure_stage(ctx, ThinSettings, _checked(thinning))
+    configure_stage(ctx, ThinSettings, checked(ThinSettings, thinning, "thinning"))
 
 
-def thinning_result(ctx: _abi.Context) -> dict:
+def thinning_result(ctx: _abi.Context, n_events: int = 0, n_sim: int = 0, n_rows=None) -> dict:
     """``{"thinning": z_step}`` if the ctx holds both the estimates and the thinning -- the records of its last
     trace-row call are then those of thinned points --, else {}."""
     token = ctx._tokens["thinning"]
@@ -65,14 +59,7 @@ def rows_to_points(offsets, rows, labels, indices, settings: ThinSettings, ctx: 
         raise TypeError("settings must be a ThinSettings")
     desc = settings.desc()
     layout = _layout(indices)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    if offsets.ndim != 1 or len(offsets) < 1 or np.any(np.diff(offsets) < 0) or offsets[0] < 0:
-        raise ValueError("offsets must be n + 1 non-decreasing row numbers >= 0")
-    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 8)
-    labels = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
-    if len(rows) != len(labels) or int(offsets[-1]) > len(rows):
-        raise ValueError(f"{len(rows)} rows, {len(labels)} labels, offsets up to {int(offsets[-1])}")
-    n = len(offsets) - 1
+    offsets, rows, labels, n = host_rows(offsets, rows, labels)
     capacity = int(offsets[-1] - offsets[0])  # (a label has no more points than rows)
     point_offsets = np.zeros(n + 1, dtype=np.int64)
     points = np.empty((capacity, 8), dtype=np.float64)

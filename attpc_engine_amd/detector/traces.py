@@ -46,13 +46,19 @@ noise, which lifts a whole chip or board over a threshold in the same sample.  T
 (include/attpc_engine.h; ``tests/common_mode_reference.py`` restates it).  ``common_mode_values`` is that stage alone.
 
 Every stage is a settings class with its context slot (``slot``), its C call (``call``), ``token()`` -- its content,
-None when the stage changes nothing -- and ``desc()``, the call's descriptor; ``configure_stage`` applies any of them.
-``TraceChain`` is one whole trace configuration, validated once: the entry points build it from their keywords, the
-writers hold one, the runs configure it in one order.  Adding a trace stage: such a settings class, one field of the
-chain, and one line in ``TraceChain.configure``.
+None when the stage changes nothing -- and ``desc()``, the call's descriptor; ``detector.stage.configure_stage`` applies
+any of them.  ``TraceChain`` is one whole trace configuration, validated once: the entry points build it from their
+keywords, the writers hold one, the runs configure it in the order of ``STAGES`` and collect their results with
+``stage_results``.  Adding a trace stage: its own module (the settings class, its configure and result functions, its
+host-row operator), one row of ``STAGES`` here, one group of ``_abi.SYMBOL_GROUPS`` (with its slot in
+``_abi.CONFIGURE_SLOTS`` and its descriptor structs), and its own functions in csrc/abi.hip and include/attpc_engine.h.
+Its keyword is then spelt out where it is public API: in the signatures of ``TraceChain``, ``configure_trace_rows`` and
+``simulate_batch_trace_rows``, each of which hands it on by name, and in ``REPLACE_FIELDS``; ``Engine`` has a documented
+``configure_*`` method per stage.  tests/test_trace_chain_cpu.py holds every row of ``STAGES`` to these places.
 """
 from __future__ import annotations
 
+import collections
 import copy
 import math
 import statistics
@@ -61,7 +67,17 @@ import numpy as np
 
 from .. import _abi
 from ..outputs import PackedTraceArrays, RowArrays, TraceArrays, call_with_capacity  # noqa: F401 (TraceArrays stays importable from here)
+from .circle import CircleFitSettings, circle_result, configure_circle
+from .clustering import ClusterSettings, clustering_result, configure_clustering
+from .correction import CorrectionSettings, configure_correction, correction_result
+from .estimate import EstimateSettings, configure_estimates, estimates_result
+from .fit import TrackFitSettings, configure_track_fit, fit_result
+from .helix import HelixSlopeSettings, configure_helix, helix_result
+from .joining import JoinSettings, configure_cluster_join, join_result
 from .parameters import Config
+from .pid import PidSettings, configure_pid, pid_result
+from .stage import checked, configure_stage  # noqa: F401 (configure_stage stays importable from here)
+from .thinning import ThinSettings, configure_thinning, thinning_result
 
 
 def trace_settings(config: Config, response=None, threshold=None, offset: int = 0):
@@ -94,14 +110,6 @@ def gaussian_noise_table(sigma: float) -> tuple[np.ndarray, int]:
     lower = [max(1, round(0.5 * math.erfc((half - k - 0.5) / scale) * 2.0 ** 32)) for k in range(half)]
     cdf = lower + [(1 << 32) - c for c in reversed(lower)]
     return np.array(cdf, dtype=np.uint32), -half
-
-
-def configure_stage(ctx: _abi.Context, stage, settings) -> None:
-    """``lib.<stage.call>`` with the descriptor of ``settings`` (an instance of the settings class ``stage``) unless the
-    ctx's ``stage.slot`` already holds the same content; None, or settings that change nothing (``token()`` None): the
-    stage off, a NULL descriptor, which is also what a new context holds."""
-    token = None if settings is None else settings.token()
-    ctx.configure(stage.slot, token, stage.call, None if token is None else settings.desc())
 
 
 def _noise_table(what: str, sigma, table):
@@ -220,70 +228,10 @@ class CommonModeSettings:
                                     self.n_levels, self.min_level, self.stream, 0)
 
 
-def _checked_estimates(estimates):
-    from .estimate import _checked
-
-    return _checked(estimates)
-
-
-def _checked_thinning(thinning):
-    from .thinning import _checked
-
-    return _checked(thinning)
-
-
-def _checked_circle(circle):
-    from .circle import _checked
-
-    return _checked(circle)
-
-
-def _checked_fit(fit):
-    from .fit import _checked
-
-    return _checked(fit)
-
-
-def _checked_clustering(clustering):
-    from .clustering import _checked
-
-    return _checked(clustering)
-
-
-def _checked_join(join):
-    from .joining import _checked
-
-    return _checked(join)
-
-
-def _checked_pid(pid):
-    from .pid import _checked
-
-    return _checked(pid)
-
-
-def _checked_helix(helix):
-    from .helix import _checked
-
-    return _checked(helix)
-
-
-def _checked_correction(correction):
-    from .correction import _checked
-
-    return _checked(correction)
-
-
-def _checked_common_mode(common_mode):
-    if common_mode is not None and not isinstance(common_mode, CommonModeSettings):
-        raise TypeError("common_mode must be a CommonModeSettings or None")
-    return common_mode
-
-
 def configure_common_mode(ctx: _abi.Context, common_mode: CommonModeSettings | None) -> None:
     """``attpc_trace_configure_common_mode`` unless this ctx already holds the same setting (``None``, or one without
     effect: off)."""
-    configure_stage(ctx, CommonModeSettings, _checked_common_mode(common_mode))
+    configure_stage(ctx, CommonModeSettings, checked(CommonModeSettings, common_mode, "common_mode"))
 
 
 def common_mode_values(n_events: int, common_mode: CommonModeSettings, seed: int = 0, first_event: int = 0,
@@ -410,7 +358,7 @@ def expected_noise_pads(noise_table, threshold: float, readout_pads=None, pedest
     else:
         p_draw = 1.0 if kind == "always" else 0.0
     p_draw = np.full(_abi.NUM_PADS, p_draw)
-    if _checked_common_mode(common_mode) is not None and common_mode.on:
+    if checked(CommonModeSettings, common_mode, "common_mode") is not None and common_mode.on:
         levels, mass = _level_masses(noise.cdf, noise.min_level) if noise.n_levels else (np.zeros(1, dtype=np.int64), np.ones(1))
         c_levels, c_mass = common_mode.level_masses()
         over = (levels[:, None] + c_levels[None, :]) > thr
@@ -423,181 +371,6 @@ def expected_noise_pads(noise_table, threshold: float, readout_pads=None, pedest
 
 TRACE_KWARGS = ("response", "threshold", "offset", "noise_sigma", "noise_table", "pedestals", "noise_stream", "readout",
                 "readout_pads")
-
-
-class TraceChain:
-    """One trace configuration, validated here, before any library call: ``config``, the ``response`` [512] f64,
-    ``threshold`` and ``offset`` with their defaults filled in (``trace_settings``), the ``noise`` (a ``NoiseSettings``;
-    None = off) and the ``readout`` (a ``ReadoutSettings``; None = hit pads), and the stages that are None when off:
-    ``gain``, ``peaks`` (trace rows; None = ``PeakSettings()``), ``baseline``, ``trigger``, ``common_mode``,
-    ``estimates`` (trace rows: a ``detector.estimate.EstimateSettings``), ``thinning`` (the rows in front of the
-    estimates: a ``detector.thinning.ThinSettings``), ``circle`` (the geometric circle fit behind them: a
-    ``detector.circle.CircleFitSettings``), ``helix`` (the helix slope behind the circle: a
-    ``detector.helix.HelixSlopeSettings``) and ``correction`` (trace rows: the drift correction of the rows, in front
-    of the thinning, the estimates and the delivery: a ``detector.correction.CorrectionSettings``), ``fit`` (the
-    track fit behind the estimates: a ``detector.fit.TrackFitSettings``) and ``clustering`` (trace rows: the cluster
-    labels the thinning, the estimates and the fit match in place of the truth labels: a
-    ``detector.clustering.ClusterSettings``) with ``join`` (the cluster joining between the clustering's size cut and
-    its ranking: a ``detector.joining.JoinSettings``; it does nothing without the clustering) and ``pid`` (the particle
-    identification between the estimates and the track fit: a ``detector.pid.PidSettings``; it does nothing without
-    the estimates)."""
-
-    def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
-                 gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
-                 thinning=None, circle=None, helix=None, correction=None, fit=None, clustering=None, join=None,
-                 pid=None):
-        self.config, self._given = config, (response, threshold)
-        self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
-        self.noise, self.readout = noise or NoiseSettings(), readout or ReadoutSettings()
-        self.gain, self.peaks, self.baseline, self.trigger = _checked_gain(gain), peaks, baseline, trigger
-        self.common_mode = _checked_common_mode(common_mode)
-        self.estimates, self.thinning = _checked_estimates(estimates), _checked_thinning(thinning)
-        self.circle = _checked_circle(circle)
-        self.helix = _checked_helix(helix)
-        self.correction = _checked_correction(correction)
-        self.fit = _checked_fit(fit)
-        self.clustering = _checked_clustering(clustering)
-        self.join = _checked_join(join)
-        self.pid = _checked_pid(pid)
-
-    @classmethod
-    def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
-        """The chain of the trace settings a caller passes on as keywords (TRACE_KWARGS, as ``configure_traces``
-        describes them): TypeError for any other name, ValueError for a value that is refused."""
-        unknown = set(trace_kwargs) - set(TRACE_KWARGS)
-        if unknown:
-            raise TypeError(f"unexpected trace settings {sorted(unknown)}: configure_traces takes {list(TRACE_KWARGS)}")
-        get = trace_kwargs.get
-        return cls(config, get("response"), get("threshold"), get("offset", 0),
-                   NoiseSettings(get("noise_sigma", 0.0), get("noise_table"), get("pedestals"), get("noise_stream", 0)),
-                   ReadoutSettings(get("readout", "hit"), get("readout_pads")))
-
-    def replace(self, **fields) -> "TraceChain":
-        """The same chain with the given fields (config, gain, peaks, baseline, trigger, common_mode, estimates, thinning,
-        circle, helix, correction, fit, clustering, join, pid; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold the chain was built without."""
-        unknown = set(fields) - {"config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix", "correction", "fit", "clustering", "join", "pid"}
-        if unknown:
-            raise TypeError(f"TraceChain.replace takes config, gain, peaks, baseline, trigger, common_mode, estimates, thinning, circle, helix, correction, fit, clustering, join and pid, not {sorted(unknown)}")
-        chain = copy.copy(self)
-        vars(chain).update(fields)
-        if "config" in fields:
-            chain.response, chain.threshold, _ = trace_settings(chain.config, *self._given, self.offset)
-        _checked_gain(chain.gain)
-        _checked_common_mode(chain.common_mode)
-        _checked_estimates(chain.estimates)
-        _checked_thinning(chain.thinning)
-        _checked_circle(chain.circle)
-        _checked_helix(chain.helix)
-        _checked_correction(chain.correction)
-        _checked_fit(chain.fit)
-        _checked_clustering(chain.clustering)
-        _checked_join(chain.join)
-        _checked_pid(chain.pid)
-        return chain
-
-    def configure(self, ctx: _abi.Context, rows: bool = False, keep=()) -> None:
-        """Every configure call of the chain, each skipped when the ctx already holds the same content, in this order:
-        trace, noise, common-mode noise, readout; with ``rows`` (trace rows) the geometry of the rows (``configure_spyral``), peaks and
-        baseline; trigger; gain; with ``rows`` the drift correction of the rows, the track estimates, the thinning in front of them, the circle fit behind them, the helix slope behind that, the particle identification and the track fit behind the estimates, and the clustering in front of them all, the cluster joining with it.  A stage that is
-        off is turned off, whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode"
-        "estimates" (the thinning, the circle fit, the helix slope, the particle identification and the track fit with them) "correction" and "clustering" (the cluster joining with it) that ``keep`` names, which stay as the ctx holds them."""
-        from .simulator import configure_spyral
-
-        ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
-                      _abi.TraceDesc(_abi.dptr(self.response), self.threshold, self.offset, 0))
-        configure_noise(ctx, self.noise)
-        if "common_mode" not in keep:
-            configure_common_mode(ctx, self.common_mode)
-        configure_readout(ctx, self.readout)
-        if rows:
-            configure_spyral(self.config, ctx)
-            configure_peaks(ctx, PeakSettings() if self.peaks is None else self.peaks)
-            configure_baseline(ctx, self.baseline)
-        if "trigger" not in keep:
-            configure_trigger(ctx, self.trigger)
-        if "gain" not in keep:
-            configure_gain(ctx, self.gain)
-        if rows and "correction" not in keep:
-            from .correction import configure_correction
-
-            configure_correction(ctx, self.correction, self.config)
-        if rows and "clustering" not in keep:
-            from .clustering import configure_clustering
-
-            configure_clustering(ctx, self.clustering)
-            from .joining import configure_cluster_join
-
-            configure_cluster_join(ctx, self.join)
-        if rows and "estimates" not in keep:
-            from .circle import configure_circle
-            from .estimate import configure_estimates
-            from .fit import configure_track_fit
-            from .helix import configure_helix
-            from .pid import configure_pid
-            from .thinning import configure_thinning
-
-            configure_estimates(ctx, self.estimates, self.config)
-            configure_thinning(ctx, self.thinning)
-            configure_circle(ctx, self.circle)
-            configure_helix(ctx, self.helix)
-            configure_track_fit(ctx, self.fit)
-            configure_pid(ctx, self.pid)
-
-    def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
-                  ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False,
-                  straggling=None, distortion=None):
-        """simulate() + this chain on the device for n events: what ``simulate_batch_trace_rows`` (``rows``) or
-        ``simulate_batch_traces`` returns (``capacity_per_event``: None = the default of that entry point; ``packed``:
-        the traces as packed records, ``attpc_det_run_traces_packed``; ``straggling``: the track straggling, a
-        ``detector.straggling.StragglingSettings`` or None = off; ``distortion``: the drift distortion, a
-        ``detector.distortion.DistortionMap`` or None = off)."""
-        from .simulator import run_batch
-
-        ctx = ctx or _abi.default_context()
-        packed = _packed_flag(packed)
-        if packed and rows:
-            raise ValueError("packed applies to traces, not to trace rows")
-
-        def configure(c):
-            self.configure(c, rows)
-            return 0 if rows else c._trace_readout_rows  # traces in full readout: |S| rows per event
-
-        per_event = (2048 if rows else 1024) if capacity_per_event is None else capacity_per_event
-        how = dict(holder=RowArrays, width=8, slack=1024) if rows else {}
-        if packed:
-            how = dict(holder=PackedTraceArrays, byte_capacity=PACKED_BYTES_PER_ROW * max(1024, int(per_event) * len(momenta)))
-        arrays, stats = run_batch("attpc_det_run_trace_rows" if rows else "attpc_det_run_traces_packed" if packed
-                                  else "attpc_det_run_traces", momenta, vertices,
-                                  proton_numbers, mass_numbers, self.config, seed, indices, first_event, ctx,
-                                  per_event, configure, straggling=straggling, distortion=distortion, **how)
-        extra = trigger_result(ctx, len(arrays.offsets) - 1)
-        if rows:
-            from .circle import circle_result
-            from .estimate import estimates_result
-            from .helix import helix_result
-            from .thinning import thinning_result
-
-            extra.update(estimates_result(ctx, len(arrays.offsets) - 1, len(indices)))
-            extra.update(thinning_result(ctx))
-            extra.update(circle_result(ctx))
-            extra.update(helix_result(ctx))
-            from .correction import correction_result
-
-            extra.update(correction_result(ctx))
-            from .fit import fit_result
-
-            extra.update(fit_result(ctx, len(arrays.offsets) - 1, len(indices)))
-            from .clustering import clustering_result
-
-            extra.update(clustering_result(ctx, len(arrays.offsets) - 1, int(arrays.offsets[-1])))
-            from .joining import join_result
-
-            extra.update(join_result(ctx, len(arrays.offsets) - 1))
-            from .pid import pid_result
-
-            extra.update(pid_result(ctx, len(arrays.offsets) - 1, len(indices)))
-        sums = ctx.trace_rows_last() if rows else arrays.sums()
-        return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
 
 
 def configure_traces(config: Config, ctx: _abi.Context, response=None, threshold=None, offset: int = 0,
@@ -620,7 +393,7 @@ def validate_trace_kwargs(config: Config, trace_kwargs: dict, gain=None) -> None
     """The trace settings a caller passes on as keywords (``configure_traces``'s, TRACE_KWARGS), checked before any
     library call: TypeError for a name configure_traces does not take, ValueError for a value it would refuse.
     ``gain``: the ``GainSettings`` that goes with them (or None), TypeError for anything else."""
-    _checked_gain(gain)
+    checked(GainSettings, gain, "gain")
     TraceChain.from_kwargs(config, **trace_kwargs)
 
 
@@ -935,7 +708,7 @@ def configure_trigger(ctx: _abi.Context, trigger: TriggerSettings | None) -> Non
     configure_stage(ctx, TriggerSettings, trigger)
 
 
-def trigger_result(ctx: _abi.Context, n_events: int) -> dict:
+def trigger_result(ctx: _abi.Context, n_events: int, n_sim: int = 0, n_rows=None) -> dict:
     """``{"trigger": records [n_events]}`` of ctx's last trace or trace-row call if the ctx holds a trigger, else {}."""
     return {"trigger": ctx.trigger_last(n_events)} if ctx._tokens["trigger"] is not None else {}
 
@@ -1051,15 +824,9 @@ class GainSettings:
         return _abi.TraceGainDesc(self.rel_variance, _abi.dptr(self.pad_gain), _abi.dptr(self.quantiles), self.stream, 0)
 
 
-def _checked_gain(gain):
-    if gain is not None and not isinstance(gain, GainSettings):
-        raise TypeError("gain must be a GainSettings or None")
-    return gain
-
-
 def configure_gain(ctx: _abi.Context, gain: GainSettings | None) -> None:
     """``attpc_trace_configure_gain`` unless this ctx already holds the same gain (``None``, or one without effect: off)."""
-    configure_stage(ctx, GainSettings, _checked_gain(gain))
+    configure_stage(ctx, GainSettings, checked(GainSettings, gain, "gain"))
 
 
 def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, seed: int = 0, first_event: int = 0,
@@ -1074,6 +841,177 @@ def clouds_to_gain(offsets: np.ndarray, points: np.ndarray, ctx: _abi.Context, s
     ctx.check(ctx.lib.attpc_gain_rows(ctx.handle, seed, first_event, n, _abi.iptr(offsets, _abi.C.c_int64),
                                       _abi.dptr(points), _abi.dptr(gained)), "attpc_gain_rows")
     return gained
+
+
+# One row per stage of the chain, in the order the chain configures them: ``field`` (the field of ``TraceChain`` and the
+# keyword of the entry points), ``settings`` (its class: ``slot`` and ``call``), ``configure`` (ctx, settings -- and,
+# with ``config``, the chain's config), ``result`` (ctx, n_events, n_sim, n_rows -> what the stage adds to the result of
+# a run, or None), ``keep`` (the name of ``TraceChain.configure``'s ``keep`` that leaves the stage as the ctx holds it),
+# ``rows`` (a stage of the trace rows only), ``default`` (what None means, if not "off"), ``replace`` (a field that
+# ``TraceChain.replace`` takes).
+Stage = collections.namedtuple("Stage", "field settings configure result keep rows default config replace",
+                               defaults=(None, None, False, None, False, True))
+STAGES = (
+    Stage("noise", NoiseSettings, configure_noise, default=NoiseSettings, replace=False),
+    Stage("common_mode", CommonModeSettings, configure_common_mode, keep="common_mode"),
+    Stage("readout", ReadoutSettings, configure_readout, default=ReadoutSettings, replace=False),
+    Stage("peaks", PeakSettings, configure_peaks, rows=True, default=PeakSettings),
+    Stage("baseline", BaselineSettings, configure_baseline, rows=True),
+    Stage("trigger", TriggerSettings, configure_trigger, trigger_result, keep="trigger"),
+    Stage("gain", GainSettings, configure_gain, keep="gain"),
+    Stage("correction", CorrectionSettings, configure_correction, correction_result, "correction", True, config=True),
+    Stage("clustering", ClusterSettings, configure_clustering, clustering_result, "clustering", True),
+    Stage("join", JoinSettings, configure_cluster_join, join_result, "clustering", True),
+    Stage("estimates", EstimateSettings, configure_estimates, estimates_result, "estimates", True, config=True),
+    Stage("thinning", ThinSettings, configure_thinning, thinning_result, "estimates", True),
+    Stage("circle", CircleFitSettings, configure_circle, circle_result, "estimates", True),
+    Stage("helix", HelixSlopeSettings, configure_helix, helix_result, "estimates", True),
+    Stage("fit", TrackFitSettings, configure_track_fit, fit_result, "estimates", True),
+    Stage("pid", PidSettings, configure_pid, pid_result, "estimates", True),
+)
+
+
+def stage_results(ctx: _abi.Context, n_events: int, n_sim: int, n_rows: int | None = None) -> dict:
+    """What the stages the ctx holds add to the result of its last trace-row call of ``n_events`` events and ``n_sim``
+    track positions, each under its own keys (``trigger``, ``correction``, ``clusters``, ``joins``, ``estimates``,
+    ``thinning``, ``circle``, ``slope``, ``fits``, ``pid``); with ``n_rows`` (the rows the call fetched) the
+    ``cluster_labels`` of those rows too."""
+    results = {}
+    for stage in STAGES:
+        if stage.result is not None:
+            results.update(stage.result(ctx, n_events, n_sim, n_rows))
+    return results
+
+
+class TraceChain:
+    """One trace configuration, validated here, before any library call: ``config``, the ``response`` [512] f64,
+    ``threshold`` and ``offset`` with their defaults filled in (``trace_settings``), the ``noise`` (a ``NoiseSettings``;
+    None = off) and the ``readout`` (a ``ReadoutSettings``; None = hit pads), and the stages that are None when off:
+    ``gain``, ``peaks`` (trace rows; None = ``PeakSettings()``), ``baseline``, ``trigger``, ``common_mode``,
+    ``estimates`` (trace rows: a ``detector.estimate.EstimateSettings``), ``thinning`` (the rows in front of the
+    estimates: a ``detector.thinning.ThinSettings``), ``circle`` (the geometric circle fit behind them: a
+    ``detector.circle.CircleFitSettings``), ``helix`` (the helix slope behind the circle: a
+    ``detector.helix.HelixSlopeSettings``) and ``correction`` (trace rows: the drift correction of the rows, in front
+    of the thinning, the estimates and the delivery: a ``detector.correction.CorrectionSettings``), ``fit`` (the
+    track fit behind the estimates: a ``detector.fit.TrackFitSettings``) and ``clustering`` (trace rows: the cluster
+    labels the thinning, the estimates and the fit match in place of the truth labels: a
+    ``detector.clustering.ClusterSettings``) with ``join`` (the cluster joining between the clustering's size cut and
+    its ranking: a ``detector.joining.JoinSettings``; it does nothing without the clustering) and ``pid`` (the particle
+    identification between the estimates and the track fit: a ``detector.pid.PidSettings``; it does nothing without
+    the estimates).  TypeError for a stage that is not of the class its row of ``STAGES`` names."""
+
+    def __init__(self, config: Config, response=None, threshold=None, offset: int = 0, noise=None, readout=None,
+                 gain=None, peaks=None, baseline=None, trigger=None, common_mode=None, estimates=None,
+                 thinning=None, circle=None, helix=None, correction=None, fit=None, clustering=None, join=None,
+                 pid=None):
+        given = dict(noise=noise, readout=readout, gain=gain, peaks=peaks, baseline=baseline, trigger=trigger,
+                     common_mode=common_mode, estimates=estimates, thinning=thinning, circle=circle, helix=helix,
+                     correction=correction, fit=fit, clustering=clustering, join=join, pid=pid)
+        self.config, self._given = config, (response, threshold)
+        self.response, self.threshold, self.offset = trace_settings(config, response, threshold, offset)
+        for stage in STAGES:
+            setattr(self, stage.field, checked(stage.settings, given[stage.field], stage.field))
+        self.noise, self.readout = self.noise or NoiseSettings(), self.readout or ReadoutSettings()
+
+    @classmethod
+    def from_kwargs(cls, config: Config, **trace_kwargs) -> "TraceChain":
+        """The chain of the trace settings a caller passes on as keywords (TRACE_KWARGS, as ``configure_traces``
+        describes them): TypeError for any other name, ValueError for a value that is refused."""
+        unknown = set(trace_kwargs) - set(TRACE_KWARGS)
+        if unknown:
+            raise TypeError(f"unexpected trace settings {sorted(unknown)}: configure_traces takes {list(TRACE_KWARGS)}")
+        get = trace_kwargs.get
+        return cls(config, get("response"), get("threshold"), get("offset", 0),
+                   NoiseSettings(get("noise_sigma", 0.0), get("noise_table"), get("pedestals"), get("noise_stream", 0)),
+                   ReadoutSettings(get("readout", "hit"), get("readout_pads")))
+
+    def replace(self, **fields) -> "TraceChain":
+        """The same chain with the given fields (``REPLACE_FIELDS``: config and the stages the entry points take as
+        keywords; TypeError for any other) replaced.  A new ``config`` fills in again the response and the threshold
+        the chain was built without."""
+        unknown = set(fields) - set(REPLACE_FIELDS)
+        if unknown:
+            raise TypeError(f"TraceChain.replace takes {', '.join(REPLACE_FIELDS[:-1])} and {REPLACE_FIELDS[-1]}, "
+                            f"not {sorted(unknown)}")
+        chain = copy.copy(self)
+        vars(chain).update(fields)
+        if "config" in fields:
+            chain.response, chain.threshold, _ = trace_settings(chain.config, *self._given, self.offset)
+        for stage in STAGES:
+            checked(stage.settings, getattr(chain, stage.field), stage.field)
+        return chain
+
+    def configure(self, ctx: _abi.Context, rows: bool = False, keep=(), but=()) -> None:
+        """Every configure call of the chain, each skipped when the ctx already holds the same content: the trace, then
+        the stages in the order of ``STAGES`` -- noise, common-mode noise, readout; with ``rows`` (trace rows) the
+        geometry of the rows (``configure_spyral``), peaks and baseline; trigger; gain; with ``rows`` the drift
+        correction of the rows, the clustering and the cluster joining, the track estimates, the thinning, the circle
+        fit, the helix slope, the track fit and the particle identification.  A stage that is off is turned off,
+        whatever an earlier use of the ctx left -- except those of "trigger", "gain", "common_mode", "estimates" (the
+        thinning, the circle fit, the helix slope, the track fit and the particle identification with them),
+        "correction" and "clustering" (the cluster joining with it) that ``keep`` names, which stay as the ctx holds
+        them, unless ``but`` names the stage's own field."""
+        from .simulator import configure_spyral
+
+        ctx.configure("trace", (self.response.tobytes(), self.threshold, self.offset), "attpc_trace_configure",
+                      _abi.TraceDesc(_abi.dptr(self.response), self.threshold, self.offset, 0))
+        for stage in STAGES:
+            if (stage.rows and not rows) or (stage.keep in keep and stage.field not in but):
+                continue
+            if stage.field == "peaks":  # the first stage of the rows: their geometry goes in front of it
+                configure_spyral(self.config, ctx)
+            settings = getattr(self, stage.field)
+            if settings is None and stage.default is not None:
+                settings = stage.default()
+            stage.configure(ctx, settings, *((self.config,) if stage.config else ()))
+
+    def run_batch(self, rows: bool, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event: int = 0,
+                  ctx: _abi.Context | None = None, capacity_per_event: int | None = None, packed: bool = False,
+                  straggling=None, distortion=None):
+        """simulate() + this chain on the device for n events: what ``simulate_batch_trace_rows`` (``rows``) or
+        ``simulate_batch_traces`` returns (``capacity_per_event``: None = the default of that entry point; ``packed``:
+        the traces as packed records, ``attpc_det_run_traces_packed``; ``straggling``: the track straggling, a
+        ``detector.straggling.StragglingSettings`` or None = off; ``distortion``: the drift distortion, a
+        ``detector.distortion.DistortionMap`` or None = off)."""
+        from .simulator import run_batch
+
+        ctx = ctx or _abi.default_context()
+        packed = _packed_flag(packed)
+        if packed and rows:
+            raise ValueError("packed applies to traces, not to trace rows")
+
+        def configure(c):
+            self.configure(c, rows)
+            return 0 if rows else c._trace_readout_rows  # traces in full readout: |S| rows per event
+
+        per_event = (2048 if rows else 1024) if capacity_per_event is None else capacity_per_event
+        how = dict(holder=RowArrays, width=8, slack=1024) if rows else {}
+        if packed:
+            how = dict(holder=PackedTraceArrays, byte_capacity=PACKED_BYTES_PER_ROW * max(1024, int(per_event) * len(momenta)))
+        arrays, stats = run_batch("attpc_det_run_trace_rows" if rows else "attpc_det_run_traces_packed" if packed
+                                  else "attpc_det_run_traces", momenta, vertices,
+                                  proton_numbers, mass_numbers, self.config, seed, indices, first_event, ctx,
+                                  per_event, configure, straggling=straggling, distortion=distortion, **how)
+        n_events = len(arrays.offsets) - 1
+        if rows:
+            extra = stage_results(ctx, n_events, len(indices), int(arrays.offsets[-1]))
+        else:
+            extra = trigger_result(ctx, n_events)
+        sums = ctx.trace_rows_last() if rows else arrays.sums()
+        return (*arrays.result(), arrays.event_points, {**stats.as_dict(), **sums, **extra})
+
+
+# the fields ``TraceChain.replace`` takes, in the order ``TraceChain`` takes them (and its TypeError names them)
+REPLACE_FIELDS = ("config", "gain", "peaks", "baseline", "trigger", "common_mode", "estimates", "thinning", "circle", "helix",
+                  "correction", "fit", "clustering", "join", "pid")
+
+
+def _checked_join(join):  # (tests import this name and the next)
+    return checked(JoinSettings, join, "join")
+
+
+def _checked_pid(pid):
+    return checked(PidSettings, pid, "pid")
 
 
 def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings | None = None,
@@ -1091,39 +1029,11 @@ def configure_trace_rows(config: Config, ctx: _abi.Context, peaks: PeakSettings 
     ``detector.clustering.ClusterSettings``) and ``join`` (the cluster joining behind it, a
     ``detector.joining.JoinSettings``) and ``pid`` (the particle identification behind the estimates, a
     ``detector.pid.PidSettings``)."""
-    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, gain=gain,
-                                                                   common_mode=common_mode, thinning=thinning, circle=circle,
-                                                                   helix=helix, correction=correction, clustering=clustering,
-                                                                   join=join, pid=pid)
-    chain.configure(ctx, rows=True, keep=("trigger", "estimates", "correction", "clustering"))
-    if pid is not None:
-        from .pid import configure_pid
-
-        configure_pid(ctx, chain.pid)
-    if clustering is not None:
-        from .clustering import configure_clustering
-
-        configure_clustering(ctx, chain.clustering)
-    if join is not None:
-        from .joining import configure_cluster_join
-
-        configure_cluster_join(ctx, chain.join)
-    if correction is not None:
-        from .correction import configure_correction
-
-        configure_correction(ctx, chain.correction, config)
-    if thinning is not None:
-        from .thinning import configure_thinning
-
-        configure_thinning(ctx, chain.thinning)
-    if circle is not None:
-        from .circle import configure_circle
-
-        configure_circle(ctx, chain.circle)
-    if helix is not None:
-        from .helix import configure_helix
-
-        configure_helix(ctx, chain.helix)
+    stages = dict(peaks=peaks, baseline=baseline, gain=gain, common_mode=common_mode, thinning=thinning, circle=circle,
+                  helix=helix, correction=correction, clustering=clustering, join=join, pid=pid)
+    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(**stages)
+    chain.configure(ctx, rows=True, keep=("trigger", "estimates", "correction", "clustering"),
+                    but=[field for field, settings in stages.items() if settings is not None])
 
 
 def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_numbers, mass_numbers, config: Config,
@@ -1157,11 +1067,9 @@ def simulate_batch_trace_rows(momenta: np.ndarray, vertices: np.ndarray, proton_
     ``"joins"``.  With ``pid`` (a ``detector.pid.PidSettings``; None = off) beside the estimates, every (event, slot)
     is assigned a position by the gates on its estimate record's dE/dx against B rho, the fit uses that position's
     species, and the records [n, len(indices)] come under ``"pid"``."""
-    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(peaks=peaks, baseline=baseline, trigger=trigger, gain=gain,
-                                                                   common_mode=common_mode, estimates=estimates,
-                                                                   thinning=thinning, circle=circle, helix=helix,
-                                                                   correction=correction, fit=fit, clustering=clustering,
-                                                                   join=join, pid=pid)
+    chain = TraceChain.from_kwargs(config, **trace_kwargs).replace(
+        peaks=peaks, baseline=baseline, trigger=trigger, gain=gain, common_mode=common_mode, estimates=estimates,
+        thinning=thinning, circle=circle, helix=helix, correction=correction, fit=fit, clustering=clustering, join=join, pid=pid)
     return chain.run_batch(True, momenta, vertices, proton_numbers, mass_numbers, seed, indices, first_event, ctx,
                            capacity_per_event, straggling=straggling, distortion=distortion)
 

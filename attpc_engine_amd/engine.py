@@ -16,18 +16,18 @@ from .detector.luts import build_det_desc, build_layout, species_for
 from .detector.simulator import default_indices, deliver_events, fired_events, plan_delivery, selected_events, writer_packed
 from .detector.traces import (BaselineSettings, CommonModeSettings, GainSettings, PackedRows, PeakSettings, TriggerSettings,
                               configure_baseline, configure_common_mode, configure_gain, configure_peaks, configure_traces,
-                              configure_trigger, trigger_result)
-from .detector.estimate import EstimateSettings, configure_estimates, estimates_result
-from .detector.circle import CircleFitSettings, circle_result, configure_circle
-from .detector.fit import TrackFitSettings, configure_track_fit, fit_result
-from .detector.clustering import ClusterSettings, clustering_result, configure_clustering
-from .detector.joining import JoinSettings, configure_cluster_join, join_result
-from .detector.pid import PidSettings, configure_pid, pid_result
-from .detector.helix import HelixSlopeSettings, configure_helix, helix_result
-from .detector.thinning import ThinSettings, configure_thinning, thinning_result
+                              configure_trigger, stage_results, trigger_result)
+from .detector.estimate import EstimateSettings, configure_estimates
+from .detector.circle import CircleFitSettings, configure_circle
+from .detector.fit import TrackFitSettings, configure_track_fit
+from .detector.clustering import ClusterSettings, configure_clustering
+from .detector.joining import JoinSettings, configure_cluster_join
+from .detector.pid import PidSettings, configure_pid
+from .detector.helix import HelixSlopeSettings, configure_helix
+from .detector.thinning import ThinSettings, configure_thinning
 from .detector.straggling import StragglingSettings, configure_straggling
 from .detector.distortion import DistortionMap, configure_distortion
-from .detector.correction import CorrectionSettings, configure_correction, correction_result
+from .detector.correction import CorrectionSettings, configure_correction
 from .outputs import PackedTraceArrays, RowArrays, SelectedArrays, SummaryArrays, call_with_capacity
 
 
@@ -321,19 +321,13 @@ class Engine:
             stats, out = _abi.RunStats(), _abi.CloudOut()
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
-            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
-                    **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
-                    **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices)),
-                    **clustering_result(ctx, n_events), **join_result(ctx, n_events),
-                **pid_result(ctx, n_events, len(self.indices))}
+            return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(),
+                    **stage_results(ctx, n_events, len(self.indices))}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
-        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events),
-                **estimates_result(ctx, n_events, len(self.indices)), **thinning_result(ctx), **circle_result(ctx),
-                    **helix_result(ctx), **correction_result(ctx), **fit_result(ctx, n_events, len(self.indices)),
-                    **clustering_result(ctx, n_events, int(arrays.offsets[-1])), **join_result(ctx, n_events),
-                **pid_result(ctx, n_events, len(self.indices))}
+        return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(),
+                **stage_results(ctx, n_events, len(self.indices), int(arrays.offsets[-1]))}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -430,13 +424,8 @@ class Engine:
         ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                    _abi.dptr(p4), _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32),
                                                    out, stats), "attpc_sim_run_trace_rows")
-        return {"estimates": ctx.estimates_last(n_events, len(self.indices)), "indices": list(self.indices),
-                "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
-                "trace_rows": ctx.trace_rows_last(), **trigger_result(ctx, n_events), **thinning_result(ctx),
-                **circle_result(ctx), **helix_result(ctx), **correction_result(ctx),
-                **fit_result(ctx, n_events, len(self.indices)), **clustering_result(ctx, n_events),
-                **join_result(ctx, n_events),
-                **pid_result(ctx, n_events, len(self.indices))}
+        return {"indices": list(self.indices), "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
+                "trace_rows": ctx.trace_rows_last(), **stage_results(ctx, n_events, len(self.indices))}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run
