@@ -303,6 +303,33 @@ PID_DTYPE = np.dtype([("position", "<i4"), ("species", "<i4"), ("held", "<i4"), 
 assert C.sizeof(PidDesc) == 4136 and PID_DTYPE.itemsize == C.sizeof(PidRecord) == 16
 assert all(PID_DTYPE.fields[name][1] == getattr(PidRecord, name).offset for name, _ in PidRecord._fields_)
 
+# ATTPC_REACTION_*: the sources, the bits of ReactionRecord.status and the limits of the bins and of the table
+REACTION_FROM_FIT, REACTION_FROM_ESTIMATE = 0, 1
+REACTION_NO_TRACK, REACTION_OUTSIDE_TARGET, REACTION_UNPHYSICAL, REACTION_NO_TRUTH = 1, 2, 4, 8
+REACTION_MAX_EX, REACTION_MAX_THETA, REACTION_MAX_ELOSS = 256, 180, 65536
+
+
+class ReactionDesc(C.Structure):  # attpc_reaction_desc
+    _fields_ = [("masses", C.c_double * 4), ("beam_energy", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double),
+                ("ex_lo", C.c_double), ("ex_hi", C.c_double), ("ex_inv_width", C.c_double), ("theta_inv_width", C.c_double),
+                ("eloss", C.POINTER(C.c_double)), ("eloss_len", C.c_int32), ("has_target", C.c_int32), ("charge", C.c_int32),
+                ("track", C.c_int32), ("observed_row", C.c_int32), ("source", C.c_int32), ("n_ex", C.c_int32),
+                ("n_theta", C.c_int32), ("reserved", C.c_int64)]
+
+
+class ReactionRecord(C.Structure):  # attpc_reaction_record
+    _fields_ = [("status", C.c_int32), ("slot", C.c_int32), ("beam_ke", C.c_double), ("ex", C.c_double),
+                ("theta_cm", C.c_double), ("truth_beam_ke", C.c_double), ("truth_ex", C.c_double),
+                ("truth_theta_cm", C.c_double), ("reserved", C.c_double)]
+
+
+# the reaction records as a numpy structured dtype: itemsize and field offsets are those of include/attpc_engine.h
+REACTION_DTYPE = np.dtype([("status", "<i4"), ("slot", "<i4"), ("beam_ke", "<f8"), ("ex", "<f8"), ("theta_cm", "<f8"),
+                           ("truth_beam_ke", "<f8"), ("truth_ex", "<f8"), ("truth_theta_cm", "<f8"), ("reserved", "<f8")],
+                          align=True)
+assert C.sizeof(ReactionDesc) == 136 and REACTION_DTYPE.itemsize == C.sizeof(ReactionRecord) == 64
+assert all(REACTION_DTYPE.fields[name][1] == getattr(ReactionRecord, name).offset for name, _ in ReactionRecord._fields_)
+
 
 class ThinDesc(C.Structure):
     _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
@@ -549,6 +576,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_clustering", "attpc_clusters_last", "attpc_cluster_labels_last", "attpc_rows_cluster",
     "attpc_trace_configure_cluster_join", "attpc_joins_last", "attpc_rows_cluster_join",
     "attpc_trace_configure_pid", "attpc_pid_last", "attpc_estimates_pid", "attpc_rows_fit_pid",
+    "attpc_reaction_configure", "attpc_reaction_last", "attpc_reaction_spectra_last", "attpc_reaction_records",
 )
 
 # The entry points added under ABI version 3 (additive), group by group in the order they were added:
@@ -675,10 +703,19 @@ SYMBOL_GROUPS = {
         "attpc_rows_fit_pid": _rows_in + [C.POINTER(EventLayout), C.POINTER(EstimateDesc), C.POINTER(TrackEstimate), _dp,
                                           C.POINTER(FitDesc), C.POINTER(PidRecord), C.POINTER(TrackFit)],
     },
+    "reaction": {
+        "attpc_reaction_configure": [_ctxp, C.POINTER(ReactionDesc)],
+        "attpc_reaction_last": [_ctxp, C.c_int64, C.c_int64, C.POINTER(ReactionRecord)],
+        "attpc_reaction_spectra_last": [_ctxp, C.c_int64, C.POINTER(C.c_uint64)],
+        "attpc_reaction_records": [_ctxp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ReactionDesc), C.POINTER(TrackFit),
+                                   C.POINTER(TrackEstimate), C.POINTER(PidRecord), _dp, _dp, _i32p,
+                                   C.POINTER(ReactionRecord), C.c_int64, C.POINTER(C.c_uint64)],
+    },
 }
 (TRACE_ROW_SYMBOLS, SUMMARY_SYMBOLS, SELECT_SYMBOLS, BASELINE_SYMBOLS, TRIGGER_SYMBOLS, GAIN_SYMBOLS, COMMON_SYMBOLS,
  TRACE_PACK_SYMBOLS, MAPS_SYMBOLS, ESTIMATE_SYMBOLS, THIN_SYMBOLS, STRAGGLE_SYMBOLS, CIRCLE_SYMBOLS, HELIX_SYMBOLS,
- DISTORT_SYMBOLS, UNDISTORT_SYMBOLS, FIT_SYMBOLS, CLUSTER_SYMBOLS, JOIN_SYMBOLS, PID_SYMBOLS) = (
+ DISTORT_SYMBOLS, UNDISTORT_SYMBOLS, FIT_SYMBOLS, CLUSTER_SYMBOLS, JOIN_SYMBOLS, PID_SYMBOLS,
+ REACTION_SYMBOLS) = (
      tuple(group) for group in SYMBOL_GROUPS.values())
 
 _lib = None
@@ -772,7 +809,8 @@ def load_library() -> C.CDLL:
 
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
-                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit", "clustering", "cluster_join", "pid")
+                   "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit", "clustering", "cluster_join", "pid",
+                   "reaction")
 
 
 class Context:

@@ -39,6 +39,7 @@
 #include "circle_host.hpp"
 #include "fit_host.hpp"
 #include "pid_host.hpp"
+#include "reaction_host.hpp"
 #include "helix_host.hpp"
 #include "estimate_host.hpp"
 #include "thin_host.hpp"
@@ -112,6 +113,7 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf tg_row_pass;          // ... with its gate, trace rows: fired of every kept trace row's event, uint8 [traces]
   DevBuf fit_records;          // track fit on (fit.hip): the chunk's records, attpc_track_fit [events][n_sim]
   DevBuf pid_records;          // particle identification on (pid.hip): the chunk's records, attpc_pid_record [events][n_sim]
+  DevBuf rx_records;           // reaction reconstruction on (reaction.hip): the chunk's records, attpc_reaction_record [events]
   DevBuf est_records;          // track estimates on (estimate.hip): the chunk's records, attpc_track_estimate [events][n_sim]
   DevBuf thin_points;          // ... of thinned points (thin.hip): one ThinPoint per trace row (pk_cap)
   DevBuf thin_info;            // ... and the attpc_thin_info of every (event, position)
@@ -164,6 +166,8 @@ struct attpc_ctx {
   int32_t chunk_events = 65536;
   int opt_variant = 0;             // 0 auto, 1 small, 2 big, 3 wide (u64 sums)
   bool opt_tiny = false;
+  bool opt_spectra_only = false;   // option "reaction_spectra_only": a trace-row call with the reaction reconstruction copies no records to the host
+  bool records_call = true;        // the trace-row call in progress copies its stages' records (attpc_*_last answer for it)
   int opt_compact = 2;             // delivered clouds cross PCIe as 8-byte (2) / 16-byte (1) records and are expanded
                                    // by host threads, or in the reference's dtypes (0)
   int opt_unpack_threads = 0;      // 0: min(32, half of the hardware threads)
@@ -283,6 +287,18 @@ struct attpc_ctx {
   int32_t pid_species[ATTPC_MAX_SIM] = {};  // the species of the positions of the trace-row call in progress
   Pinned<attpc_pid_record> h_pid;  // records of the last trace-row call, as h_estimates
   bool pid_call = false;           // that call made them
+  bool reaction_on = false;        // attpc_reaction_configure (inert while its source is off)
+  attpc_reaction_desc reaction{};  // (eloss: nullptr, the table is in rx_eloss)
+  DevBuf rx_eloss;                 // the table on the device, filled by the configure call
+  DevBuf rx_cells;                 // the spectra of the trace-row call in progress, u64 [reaction_cells]
+  Pinned<attpc_reaction_record> h_reaction;  // records of the last trace-row call, [events] in its event order
+  std::vector<uint64_t> h_rx_cells;          // its spectra
+  bool reaction_call = false;      // that call made them
+  const double* rx_p4 = nullptr;   // the truth of the track batch in progress on the device: p4 [events][rx_n_rows][4],
+  const double* rx_vertex = nullptr;         // vertex [events][3],
+  const int32_t* rx_status = nullptr;        // the kinematics status [events] (nullptr: host kinematics, all 0);
+  uint64_t rx_batch_first = 0;     // the batch's first event in the call's order
+  int32_t rx_n_rows = 0;
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -1261,30 +1277,70 @@ int32_t enqueue_pid(attpc_ctx* ctx, const attpc_track_estimate* estimates, uint3
   return ATTPC_OK;
 }
 
+// The table of a checked desc on the device, in `buf` (nothing without a target).
+int32_t upload_reaction_eloss(attpc_ctx* ctx, DevBuf& buf, const attpc_reaction_desc& d) {
+  if (!d.has_target) return ATTPC_OK;
+  const int32_t rc = ensure(ctx, buf, (size_t)d.eloss_len * sizeof(double));
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpy(buf.p, d.eloss, (size_t)d.eloss_len * sizeof(double), hipMemcpyHostToDevice));
+  return ATTPC_OK;
+}
+
+// The reaction reconstruction of `n` > 0 events on S: the source records and the truth of `a` (everything but the
+// settings filled in by the caller) with the settings `d`, whose table is in `eloss` (upload_reaction_eloss).
+int32_t enqueue_reaction(attpc_ctx* ctx, ReactionArgs a, const attpc_reaction_desc& d, const DevBuf& eloss) {
+  a.c = reaction_params(d);
+  a.eloss = d.has_target ? static_cast<const double*>(eloss.p) : nullptr;
+  if (d.source == ATTPC_REACTION_FROM_FIT) a.estimates = nullptr; else a.fits = nullptr;
+  launch_reaction(ctx->stream, a);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
 // The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none and makes no records):
 // room for its track estimates (attpc_estimates_last), if the stage is on.  Nothing of an earlier call is in flight.
 int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay) {
   ctx->est_call_events = -1;
   ctx->fit_call = false;
   ctx->pid_call = false;
+  ctx->reaction_call = false;
+  ctx->records_call = true;
   if (!ctx->estimates_on || !lay) return ATTPC_OK;
-  const int32_t rc = ensure_pinned(ctx, ctx->h_estimates, std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1));
+  // (the reconstruction does nothing without its source; what it cannot read is refused before the call has any state)
+  const bool reaction = ctx->reaction_on && (ctx->reaction.source == ATTPC_REACTION_FROM_ESTIMATE || ctx->fit_on);
+  if (reaction && (ctx->reaction.track >= lay->n_sim || lay->n_rows < 4))
+    return fail(ctx, ATTPC_E_INVALID, "reaction: track %d and rows 0 .. 3 need a layout of more than %d positions and %d rows",
+                ctx->reaction.track, lay->n_sim, lay->n_rows);
+  if (reaction && lay->indices[ctx->reaction.track] != ctx->reaction.observed_row)
+    return fail(ctx, ATTPC_E_INVALID, "reaction: position %d of the layout is row %d, observed_row is %d", ctx->reaction.track,
+                lay->indices[ctx->reaction.track], ctx->reaction.observed_row);
+  // a spectra-only call (option reaction_spectra_only) keeps every record on the device: no pinned room, no copy
+  ctx->records_call = !(reaction && ctx->opt_spectra_only);
+  const size_t room = ctx->records_call ? std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1) : 0;
+  const int32_t rc = ensure_pinned(ctx, ctx->h_estimates, room);
   if (rc) return rc;
   estimate_positions(*lay, ctx->est_slot_label);
   ctx->est_call_n_sim = lay->n_sim;
   ctx->est_call_events = (int64_t)n;
   if (ctx->fit_on) {
-    const int32_t rc2 = ensure_pinned(ctx, ctx->h_fits, std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1));
+    const int32_t rc2 = ensure_pinned(ctx, ctx->h_fits, room);
     if (rc2) return rc2;
     fit_positions(ctx->det, *lay, ctx->fit_position);
     ctx->fit_call = true;
   }
   if (ctx->pid_on) {  // (the identification does nothing without the estimates)
-    const int32_t rc2 = ensure_pinned(ctx, ctx->h_pid, std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1));
+    const int32_t rc2 = ensure_pinned(ctx, ctx->h_pid, room);
     if (rc2) return rc2;
     if (!ctx->fit_on) fit_positions(ctx->det, *lay, ctx->fit_position);
     for (int s = 0; s < ATTPC_MAX_SIM; ++s) ctx->pid_species[s] = ctx->fit_position[s].table;
     ctx->pid_call = true;
+  }
+  if (reaction) {
+    const int32_t rc2 = ensure_pinned(ctx, ctx->h_reaction, ctx->records_call ? std::max<size_t>((size_t)n, 1) : 0);
+    if (rc2) return rc2;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->rx_cells.p, 0, ctx->rx_cells.bytes, ctx->stream));
+    ctx->rx_n_rows = lay->n_rows;
+    ctx->reaction_call = true;
   }
   return ATTPC_OK;
 }
@@ -1362,8 +1418,29 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
     if ((rc = enqueue_fit(ctx, a, n, ctx->fit, ctx->fit_position, nullptr, pid, static_cast<attpc_track_fit*>(as.fit_records.p))))
       return rc;
   }
+  if (ctx->reaction_call) {  // behind the last of the estimate, pid and fit kernels
+    if ((rc = ensure(ctx, as.rx_records, (size_t)n * sizeof(attpc_reaction_record)))) return rc;
+    const size_t b = (size_t)(first_local - ctx->rx_batch_first);  // the chunk's first event in its track batch
+    ReactionArgs r{};
+    r.fits = static_cast<const attpc_track_fit*>(as.fit_records.p);
+    r.estimates = a.records;
+    r.pid = pid;
+    r.p4 = ctx->rx_p4 + b * (size_t)ctx->rx_n_rows * 4;
+    r.vertex = ctx->rx_vertex + b * 3;
+    r.kin_status = ctx->rx_status ? ctx->rx_status + b : nullptr;
+    r.records = static_cast<attpc_reaction_record*>(as.rx_records.p);
+    r.cells = static_cast<unsigned long long*>(ctx->rx_cells.p);
+    r.n_events = n;
+    r.n_sim = a.n_sim;
+    r.n_rows = ctx->rx_n_rows;
+    if ((rc = enqueue_reaction(ctx, r, ctx->reaction, ctx->rx_eloss))) return rc;
+  }
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
+  if (!ctx->records_call) return ATTPC_OK;  // (a spectra-only call: the chunk's records stay where they are)
+  if (ctx->reaction_call)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_reaction.p + first_local, as.rx_records.p, (size_t)n * sizeof(attpc_reaction_record),
+                                hipMemcpyDeviceToHost, ctx->stream_c));
   if (ctx->fit_call)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fits.p + first_local * n_sim, as.fit_records.p, (size_t)n * n_sim * sizeof(attpc_track_fit),
                                 hipMemcpyDeviceToHost, ctx->stream_c));
@@ -1909,7 +1986,7 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
   if (clustered && (rc = enqueue_clustering(ctx, as, n))) return rc;  // (an event without rows has a record too)
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
-  if (clustered) {
+  if (clustered && ctx->records_call) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_events.p + first_local, as.cl_events.p, (size_t)n * sizeof(attpc_cluster_event),
                                 hipMemcpyDeviceToHost, ctx->stream_c));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_records.p + first_local * ATTPC_MAX_SIM, as.cl_records.p,
@@ -2540,6 +2617,12 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
     if (sink.status) HIP_TRY(ctx, hipMemcpyAsync(sink.status + b0, ts.status.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (sink.p4) HIP_TRY(ctx, hipMemcpyAsync(sink.p4 + b0 * n_rows * 4, ts.p4.p, (size_t)nb * n_rows * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (sink.vertex) HIP_TRY(ctx, hipMemcpyAsync(sink.vertex + b0 * 3, ts.vertex.p, (size_t)nb * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->reaction_call) {  // the truth of this batch, for the reaction reconstruction behind its chunks
+      ctx->rx_p4 = static_cast<const double*>(ts.p4.p);
+      ctx->rx_vertex = static_cast<const double*>(ts.vertex.p);
+      ctx->rx_status = src.from_kernel ? static_cast<const int32_t*>(ts.status.p) : nullptr;
+      ctx->rx_batch_first = b0;
+    }
     if ((rc = run_batch_chunks(ctx, lay, trk, seed, first_event + b0, b0, nb, o, &st, queue_next))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // this set's readers are done before it is refilled
     b0 = next_b0;
@@ -2559,6 +2642,11 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   if (o.mode == OutMode::trace_rows) {
     st.n_points = (uint64_t)o.rows;  // the rows of the call, as in the Spyral mode
     if ((rc = read_peak_sums(ctx, o))) return rc;
+    if (ctx->reaction_call) {  // the spectra of the call, read like the checksum: once, when the call has ended
+      ctx->h_rx_cells.resize(ctx->rx_cells.bytes / sizeof(uint64_t));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rx_cells.data(), ctx->rx_cells.p, ctx->rx_cells.bytes, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
   }
   st.n_buffer_growths = ctx->n_growths - growths_before;
   st.device_bytes = ctx->device_bytes;
@@ -2703,6 +2791,10 @@ int32_t attpc_set_option(attpc_ctx* ctx, const char* name, int64_t value) {
   if (key == "scatter_variant") {
     if (value < 0 || value > 3) return fail(ctx, ATTPC_E_INVALID, "scatter_variant must be 0, 1, 2 or 3");
     ctx->opt_variant = (int)value;
+  } else if (key == "reaction_spectra_only") {
+    // != 0: a trace-row call in which the reaction reconstruction runs copies no stage records to the host (estimates,
+    // fits, pid, reaction, clusters, joins): attpc_*_last answer ATTPC_E_NOTCONFIGURED for it, the spectra are read as ever
+    ctx->opt_spectra_only = value != 0;
   } else if (key == "tiny_buffers") {
     ctx->opt_tiny = value != 0;
   } else if (key == "compact_transfer") {
@@ -4012,8 +4104,8 @@ int32_t attpc_trace_configure_estimates(attpc_ctx* ctx, const attpc_estimate_des
 
 int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_estimate* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->est_call_events < 0)
-    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_estimates_last: the last trace-row call made no track estimates");
+  if (ctx->est_call_events < 0 || !ctx->records_call)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_estimates_last: the last trace-row call made no track estimates, or kept them on the device");
   return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_estimates.p, out);
 }
 
@@ -4099,7 +4191,7 @@ int32_t attpc_trace_configure_clustering(attpc_ctx* ctx, const attpc_cluster_des
 int32_t attpc_clusters_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_cluster_event* events,
                             attpc_cluster_record* records) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->cluster_call_events < 0)
+  if (ctx->cluster_call_events < 0 || !ctx->records_call)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_clusters_last: the clustering was off for the last trace-row call");
   if (const int32_t rc = copy_last(ctx, __func__, first, count, ctx->cluster_call_events, 1, ctx->h_cl_events.p, events, false))
     return rc;
@@ -4191,7 +4283,7 @@ int32_t attpc_trace_configure_cluster_join(attpc_ctx* ctx, const attpc_join_desc
 
 int32_t attpc_joins_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_join_event* events, attpc_join_record* records) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->cluster_call_events < 0 || !ctx->join_call)
+  if (ctx->cluster_call_events < 0 || !ctx->join_call || !ctx->records_call)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_joins_last: the cluster joining or the clustering was off for the last trace-row call");
   if (const int32_t rc = copy_last(ctx, __func__, first, count, ctx->cluster_call_events, 1, ctx->h_jn_events.p, events, false))
     return rc;
@@ -4214,7 +4306,7 @@ int32_t attpc_trace_configure_fit(attpc_ctx* ctx, const attpc_fit_desc* d) {
 
 int32_t attpc_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_fit* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->est_call_events < 0 || !ctx->fit_call)
+  if (ctx->est_call_events < 0 || !ctx->fit_call || !ctx->records_call)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_fits_last: the last trace-row call made no track fits");
   return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_fits.p, out);
 }
@@ -4308,7 +4400,7 @@ int32_t attpc_trace_configure_pid(attpc_ctx* ctx, const attpc_pid_desc* d) {
 
 int32_t attpc_pid_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_pid_record* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->est_call_events < 0 || !ctx->pid_call)
+  if (ctx->est_call_events < 0 || !ctx->pid_call || !ctx->records_call)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_pid_last: the last trace-row call made no particle identification");
   return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_pid.p, out);
 }
@@ -4335,6 +4427,91 @@ int32_t attpc_estimates_pid(attpc_ctx* ctx, int64_t n_events, int32_t n_sim, con
     if ((rc = stage_out(ctx, out + (size_t)e0 * (size_t)n_sim, d_out, m * (size_t)n_sim))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
+  return ATTPC_OK;
+}
+
+// ---- reaction reconstruction (reaction.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_reaction_configure(attpc_ctx* ctx, const attpc_reaction_desc* d) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (d)
+    if (const char* bad = reaction_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "reaction: %s", bad);
+  { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
+  ctx->reaction_on = false;
+  ctx->reaction_call = false;
+  for (DevBuf* b : {&ctx->rx_eloss, &ctx->rx_cells}) {  // (off, or other bins: the buffers go)
+    if (b->p) ctx->device_bytes -= b->bytes;
+    *b = DevBuf{};
+  }
+  if (!d) return ATTPC_OK;
+  int32_t rc;
+  if ((rc = upload_reaction_eloss(ctx, ctx->rx_eloss, *d))) return rc;
+  if ((rc = ensure(ctx, ctx->rx_cells, (size_t)reaction_cells(d->n_ex, d->n_theta) * sizeof(uint64_t)))) return rc;
+  ctx->reaction = *d;
+  ctx->reaction.eloss = nullptr;
+  ctx->reaction_on = true;
+  return ATTPC_OK;
+}
+
+int32_t attpc_reaction_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_reaction_record* out) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->est_call_events < 0 || !ctx->reaction_call || !ctx->records_call)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_reaction_last: the last trace-row call made no reaction reconstruction");
+  return copy_last(ctx, __func__, first, count, ctx->est_call_events, 1, ctx->h_reaction.p, out);
+}
+
+int32_t attpc_reaction_spectra_last(attpc_ctx* ctx, int64_t n_cells, uint64_t* cells) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->est_call_events < 0 || !ctx->reaction_call)
+    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_reaction_spectra_last: the last trace-row call made no reaction reconstruction");
+  if (n_cells != (int64_t)ctx->h_rx_cells.size() || !cells)
+    return fail(ctx, ATTPC_E_INVALID, "%s: %lld cells, the spectra have %zu", __func__, (long long)n_cells, ctx->h_rx_cells.size());
+  std::memcpy(cells, ctx->h_rx_cells.data(), ctx->h_rx_cells.size() * sizeof(uint64_t));
+  return ATTPC_OK;
+}
+
+int32_t attpc_reaction_records(attpc_ctx* ctx, int64_t n_events, int32_t n_sim, int32_t n_rows, const attpc_reaction_desc* d,
+                               const attpc_track_fit* fits, const attpc_track_estimate* estimates, const attpc_pid_record* pid,
+                               const double* p4, const double* vertex, const int32_t* kin_status,
+                               attpc_reaction_record* records, int64_t n_cells, uint64_t* cells) {
+  if (!ctx || n_events < 0 || !d) return ATTPC_E_INVALID;
+  if (const char* bad = reaction_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "reaction: %s", bad);
+  if (n_sim < 1 || n_sim > ATTPC_MAX_SIM) return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 1 .. %d", __func__, n_sim, ATTPC_MAX_SIM);
+  if (n_rows < 4 || n_rows > ATTPC_MAX_ROWS) return fail(ctx, ATTPC_E_INVALID, "%s: n_rows %d outside 4 .. %d", __func__, n_rows, ATTPC_MAX_ROWS);
+  if (!pid && d->track >= n_sim) return fail(ctx, ATTPC_E_INVALID, "%s: track %d with n_sim %d", __func__, d->track, n_sim);
+  if (n_cells != reaction_cells(d->n_ex, d->n_theta) || !cells)
+    return fail(ctx, ATTPC_E_INVALID, "%s: %lld cells, the bins have %lld", __func__, (long long)n_cells,
+                (long long)reaction_cells(d->n_ex, d->n_theta));
+  const bool from_fit = d->source == ATTPC_REACTION_FROM_FIT;
+  if (n_events > 0 && (!(from_fit ? (const void*)fits : (const void*)estimates) || !p4 || !vertex || !records)) return ATTPC_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int32_t rc;
+  if ((rc = sync_all(ctx))) return rc;
+  uint64_t* d_cells = stage<uint64_t>(ctx, 6, (size_t)n_cells, rc);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(d_cells, 0, (size_t)n_cells * sizeof(uint64_t), ctx->stream));
+  if ((rc = upload_reaction_eloss(ctx, ctx->scratch[7], *d))) return rc;
+  constexpr int64_t CHUNK_EVENTS = 1 << 20;
+  for (int64_t e0 = 0; e0 < n_events; e0 += CHUNK_EVENTS) {
+    const size_t m = (size_t)std::min<int64_t>(CHUNK_EVENTS, n_events - e0), per = (size_t)n_sim;
+    ReactionArgs a{};
+    if (from_fit) a.fits = stage_in(ctx, 0, fits + (size_t)e0 * per, m * per, rc);
+    else a.estimates = stage_in(ctx, 0, estimates + (size_t)e0 * per, m * per, rc);
+    a.pid = pid ? stage_in(ctx, 1, pid + (size_t)e0 * per, m * per, rc) : nullptr;
+    a.p4 = stage_in(ctx, 2, p4 + (size_t)e0 * (size_t)n_rows * 4, m * (size_t)n_rows * 4, rc);
+    a.vertex = stage_in(ctx, 3, vertex + (size_t)e0 * 3, m * 3, rc);
+    a.kin_status = kin_status ? stage_in(ctx, 4, kin_status + e0, m, rc) : nullptr;
+    a.records = stage<attpc_reaction_record>(ctx, 5, m, rc);
+    if (rc) return rc;
+    a.cells = reinterpret_cast<unsigned long long*>(d_cells);
+    a.n_events = (uint32_t)m;
+    a.n_sim = n_sim;
+    a.n_rows = n_rows;
+    if ((rc = enqueue_reaction(ctx, a, *d, ctx->scratch[7]))) return rc;
+    if ((rc = stage_out(ctx, records + e0, a.records, m))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  if ((rc = stage_out(ctx, cells, d_cells, (size_t)n_cells))) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return ATTPC_OK;
 }
 

@@ -8,6 +8,7 @@ from . import fit as _fit
 from . import maps as _maps
 from . import parameters as _parameters
 from . import pid as _pid
+from . import reaction as _reaction
 from . import selection as _selection
 from . import simulator as _simulator
 from . import straggling as _straggling
@@ -35,6 +36,8 @@ _EXPORTS = {
     _clustering: ("ClusterSettings", "configure_clustering", "rows_to_clusters", "cluster_scores"),
     _joining: ("JoinSettings", "configure_cluster_join", "joins_last", "rows_to_joined_clusters"),
     _pid: ("Gate", "PidSettings", "configure_pid", "pid_last", "estimates_to_pid", "by_position", "PID_DTYPE"),
+    _reaction: ("ReactionSettings", "ReactionSpectra", "configure_reaction", "reaction_last", "records_to_reaction",
+                "REACTION_DTYPE"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

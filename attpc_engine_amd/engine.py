@@ -23,6 +23,7 @@ from .detector.fit import TrackFitSettings, configure_track_fit
 from .detector.clustering import ClusterSettings, configure_clustering
 from .detector.joining import JoinSettings, configure_cluster_join
 from .detector.pid import PidSettings, configure_pid
+from .detector.reaction import ReactionSettings, configure_reaction, reaction_result, source_on
 from .detector.helix import HelixSlopeSettings, configure_helix
 from .detector.thinning import ThinSettings, configure_thinning
 from .detector.straggling import StragglingSettings, configure_straggling
@@ -46,6 +47,7 @@ class Engine:
         self._spyral_configured = self._traces_configured = self._peaks_configured = self._summary_configured = False
         self._selection = None  # the Selection configure_selection uploaded
         self._maps = None  # the MapsSettings configure_maps uploaded
+        self._reaction = None  # the ReactionSettings configure_reaction uploaded
         ctx = self.ctx
         kin, keep_k = pipeline.device_desc()
         ctx.check(ctx.lib.attpc_kin_configure(ctx.handle, kin), "attpc_kin_configure")
@@ -57,6 +59,7 @@ class Engine:
         ctx.forget("det")  # (what configure_detector last uploaded is no longer what the device holds)
         configure_straggling(ctx, None)  # a new engine starts without the track straggling an earlier one configured
         configure_distortion(ctx, None)  # ... and without its drift distortion
+        configure_reaction(ctx, None)  # ... and without its reaction reconstruction, which was that engine's reaction
         self.layout = build_layout(self.z, self.a, self.indices, self.species)
         if chunk_events:
             ctx.check(ctx.lib.attpc_set_chunk_events(ctx.handle, int(chunk_events)), "attpc_set_chunk_events")
@@ -316,18 +319,20 @@ class Engine:
         n_skipped, n_unconverged, n_moved)."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         self._trace_rows_defaults()
+        self._apply_reaction()
         ctx = self.ctx
         if not fetch:
             stats, out = _abi.RunStats(), _abi.CloudOut()
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(),
-                    **stage_results(ctx, n_events, len(self.indices))}
+                    **stage_results(ctx, n_events, len(self.indices)), **reaction_result(ctx, self._reaction, n_events)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(),
-                **stage_results(ctx, n_events, len(self.indices), int(arrays.offsets[-1]))}
+                **stage_results(ctx, n_events, len(self.indices), int(arrays.offsets[-1])),
+                **reaction_result(ctx, self._reaction, n_events)}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -407,6 +412,52 @@ class Engine:
         settings = gates if gates is None or isinstance(gates, PidSettings) else PidSettings(gates, mode)
         configure_pid(self.ctx, settings)
 
+    def configure_reaction(self, settings=None, **keywords) -> None:
+        """The reaction reconstruction behind the track estimates and the track fit (include/attpc_engine.h, "reaction
+        reconstruction"): a ``detector.reaction.ReactionSettings``, or the keywords of
+        ``ReactionSettings.from_pipeline`` for this engine's pipeline and indices (track, source, ex_range, ex_bins,
+        theta_bins), turns it on -- ``run_trace_rows`` and ``run_estimates`` then carry ``reaction`` [n]
+        (``detector.reaction.REACTION_DTYPE``: excitation energy and centre-of-mass angle from the observed track of
+        position ``track``, and from the truth) and ``spectra`` (a ``detector.reaction.ReactionSpectra``), and
+        ``run_spectra`` returns the spectra alone --, neither turns it off (the default).  Without its source (the
+        estimates, and for source "fit" the track fit) it does nothing.  ``run_fused``, ``run_simulation``,
+        ``simulate_batch_trace_rows`` and the writers do not take it."""
+        if settings is None and keywords:
+            settings = ReactionSettings.from_pipeline(self.pipeline, indices=self.indices, **keywords)
+        elif settings is not None and keywords:
+            raise TypeError("give a ReactionSettings or the keywords of ReactionSettings.from_pipeline, not both")
+        if isinstance(settings, ReactionSettings):
+            settings.check_indices(self.indices)
+        configure_reaction(self.ctx, settings)
+        self._reaction = settings
+
+    def run_spectra(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
+        """``run_trace_rows(fetch=False)`` for the spectra of the reaction reconstruction alone: ``spectra`` (a
+        ``detector.reaction.ReactionSpectra``, 8 bytes per cell whatever the number of events) and the cloud's
+        ``stats``; the estimate, fit, pid, reaction and cluster records of the call stay on the device (the library's
+        option ``reaction_spectra_only``), so nothing that grows with ``n_events`` crosses the link.  The spectra of disjoint id ranges add (``ReactionSpectra.__add__``).  Raises if
+        the reaction reconstruction or its source is not configured."""
+        seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
+        self._apply_reaction()
+        if not source_on(self.ctx, self._reaction):
+            raise RuntimeError("run_spectra needs the reaction reconstruction and its source: call configure_reaction, "
+                               "configure_estimates and (for source 'fit') configure_track_fit first")
+        self._trace_rows_defaults()
+        ctx, stats, out = self.ctx, _abi.RunStats(), _abi.CloudOut()
+        ctx.check(ctx.lib.attpc_set_option(ctx.handle, b"reaction_spectra_only", 1), "attpc_set_option")
+        try:  # (no stage record of the call is copied to the host: only the spectra cross the link)
+            ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
+                                                       None, None, None, out, stats), "attpc_sim_run_trace_rows")
+        finally:
+            ctx.check(ctx.lib.attpc_set_option(ctx.handle, b"reaction_spectra_only", 0), "attpc_set_option")
+        return {"stats": stats.as_dict(), **reaction_result(ctx, self._reaction, n_events, records=False)}
+
+    def _apply_reaction(self) -> None:
+        """This engine's reaction reconstruction on the context (another engine of the same context, or a file-driven
+        entry point, may have replaced or removed it since ``configure_reaction``); no call if it is what the context
+        holds."""
+        configure_reaction(self.ctx, self._reaction)
+
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
         128 bytes per track cross PCIe (``estimates`` [n, n_sim], ``detector.estimate.ESTIMATE_DTYPE``), beside the
@@ -417,6 +468,7 @@ class Engine:
         if self.ctx._tokens["estimates"] is None:
             raise RuntimeError("run_estimates needs the estimates: call configure_estimates first")
         self._trace_rows_defaults()
+        self._apply_reaction()
         ctx, stats, out = self.ctx, _abi.RunStats(), _abi.CloudOut()
         p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
         vertex = np.empty((n_events, 3), dtype=np.float64)
@@ -425,7 +477,8 @@ class Engine:
                                                    _abi.dptr(p4), _abi.dptr(vertex), _abi.iptr(status, _abi.C.c_int32),
                                                    out, stats), "attpc_sim_run_trace_rows")
         return {"indices": list(self.indices), "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
-                "trace_rows": ctx.trace_rows_last(), **stage_results(ctx, n_events, len(self.indices))}
+                "trace_rows": ctx.trace_rows_last(), **stage_results(ctx, n_events, len(self.indices)),
+                **reaction_result(ctx, self._reaction, n_events)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

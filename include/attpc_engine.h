@@ -255,7 +255,13 @@ ATTPC_API int32_t attpc_sync(attpc_ctx* ctx);
  *                      as many as the tracks need, up to "track_blocks_per_cu" per compute unit.  A test hook: with one
  *                      workgroup a few hundred tracks make every lane take several tracks, and every wave several
  *                      batches of track ids and pools of arena blocks.  Scheduling only: results do not depend on it
- *   "chunk_events"     as attpc_set_chunk_events */
+ *   "chunk_events"     as attpc_set_chunk_events
+ *   "reaction_spectra_only"  != 0: a trace-row call in which the reaction reconstruction runs ("reaction
+ *                      reconstruction" below) copies none of its stages' records to the host -- estimates, fits, pid,
+ *                      reaction, clusters, joins stay in the chunk buffers, no pinned room is made for them, and the
+ *                      attpc_*_last readers of those records answer ATTPC_E_NOTCONFIGURED for that call -- so that only
+ *                      the spectra (attpc_reaction_spectra_last) cross the link, whatever the number of events.  The
+ *                      spectra do not depend on it.  A call without the reaction reconstruction ignores it.  Default 0 */
 ATTPC_API int32_t attpc_set_option(attpc_ctx* ctx, const char* name, int64_t value);
 /* Page-locked host memory for output buffers (point clouds are PCIe bound on their way to the host:
  * copies into pinned memory run at the link rate, copies into pageable memory at a fraction of it).
@@ -2150,6 +2156,140 @@ ATTPC_API int32_t attpc_rows_fit_pid(attpc_ctx* ctx, int64_t n_events, const int
                                      const attpc_estimate_desc* estimate_desc, const attpc_track_estimate* estimates_in,
                                      const double* start, const attpc_fit_desc* fit_desc, const attpc_pid_record* pid,
                                      attpc_track_fit* out);
+
+/* ---- reaction reconstruction (opt-in: off by default, and with it off every output, kernel and buffer of every entry
+ * point is what it is without this section; inert while its source -- the track estimates, and for the fit source the
+ * track fit -- is off; the entry points are additions under ABI version 3) ----
+ * The chain above ends at a fitted momentum and vertex per track.  This stage takes it to the observable the simulation
+ * is run for: per event the excitation energy Ex of the unobserved partner (missing mass) and the centre-of-mass angle
+ * theta_cm of the ejectile of the two-body first step, from ONE observed track, next to the same two numbers made by
+ * the same code from the event's truth 4-vector and truth vertex -- and, over the call, the spectra that give the
+ * resolution and the efficiency in (Ex, theta_cm).  It is not a row of the trace-row chain: it needs the reaction, which
+ * that chain does not know, so it is configured on the context like the summary, the selection and the maps.
+ * tests/reaction_reference.py restates this contract in numpy; csrc/reaction_host.hpp holds it as one piece of code for
+ * the device and the host.
+ *
+ * Settings (attpc_reaction_desc, self-contained: the configured kinematics are not read).  masses[0 .. 3]: target,
+ * projectile, ejectile, residual in MeV, finite and > 0.  beam_energy (MeV, > 0), has_target (0 or 1); with a target
+ * z_min < z_max (m) and eloss [eloss_len], 2 .. ATTPC_REACTION_MAX_ELOSS finite nodes, the projectile's energy loss as
+ * attpc_kin_desc.eloss; without one eloss_len is 0.  observed_row is 2 (the ejectile is observed) or 3 (the residual),
+ * charge >= 1 the charge number of that nucleus, track the layout position whose track is read, source
+ * ATTPC_REACTION_FROM_FIT or ATTPC_REACTION_FROM_ESTIMATE.  Bins: n_ex in 1 .. 256 from ex_lo to ex_hi (finite, lo < hi),
+ * n_theta in 1 .. 180 from 0 to PI = 3.141592653589793; ex_inv_width and theta_inv_width are computed ONCE, by the
+ * caller, as (double)n_ex / (ex_hi - ex_lo) and (double)n_theta / PI, and are refused if they are anything else.
+ * reserved is 0.  Anything else, a NaN included, is ATTPC_E_INVALID.
+ *
+ * Arithmetic: f64 only, every operation rounded once in the order written, nothing contracted into a fused
+ * multiply-add; + - * / and sqrt, floor in the two places named, and atan2w = the written arctangent of "helix slope".
+ *
+ * Beam energy at a vertex z (m).  Without a target T_b = beam_energy.  With one
+ *   t = (z - z_min) / (z_max - z_min) * (double)(eloss_len - 1),
+ *   i = floor(t) held to 0 .. eloss_len - 2 (a t that is not >= 0 gives 0),   f = t - (double)i,
+ *   T_b = beam_energy - (eloss[i] + f * (eloss[i + 1] - eloss[i])):
+ * the look-up of the kinematics kernel, linear in the table and extrapolating beyond both ends.
+ *
+ * Momentum of the observed nucleus, MeV/c, with m_e = masses[observed_row] and m_r = masses[5 - observed_row].
+ *   From a fit record f:       (px, py, pz) = (m_e * g[0], m_e * g[1], m_e * g[2]),   z = vertex[2] / 1000.
+ *   From an estimate record e: pmag = 299.792458 * (double)charge * brho,   w = sqrt(1 + slope * slope),
+ *                              st = 1 / w,  ct = slope / w  (as the start of the track fit makes them),
+ *                              (px, py, pz) = (pmag * st, 0, pmag * ct),   z = vz / 1000.
+ *   From the truth:            (px, py, pz) of the event's p4 row observed_row,   z = the truth vertex z.
+ *
+ * Value(T_b, px, py, pz), m_t = masses[0], m_p = masses[1]:
+ *   E   = (T_b + m_p) + m_t                     pb2 = T_b * (T_b + 2 * m_p)          pb = sqrt(pb2)
+ *   pt2 = px * px + py * py                     p2  = pt2 + pz * pz                  E_e = sqrt(p2 + m_e * m_e)
+ *   dE  = E - E_e                               M2  = dE * dE - ((pb2 + p2) - (2 * pb) * pz)
+ *   Ex  = sqrt(M2) - m_r
+ *   beta = pb / E                               gamma = E / sqrt(E * E - pb2)        pt = sqrt(pt2)
+ *   th  = atan2w(pt, gamma * (pz - beta * E_e))
+ *   theta_cm = th for observed_row 2, PI - th for observed_row 3
+ * theta_cm is the EJECTILE's polar angle in the centre-of-mass frame in both cases, as Reaction.calculate of the
+ * reference defines it.  The value is physical iff M2 > 0 and Ex and theta_cm are finite; otherwise both are NaN.
+ * The cancellation is in M2: |delta Ex| is of the order of 2^-53 E^2 / m_r (DESIGN section 6 has the measured
+ * constant).
+ *
+ * Slot.  With the particle identification on (the call made pid records): the FIRST slot s with pid[s].position ==
+ * track; none: no slot.  Otherwise slot = track.
+ *
+ * attpc_reaction_record per event (64 bytes): status, slot (-1: none), beam_ke, ex, theta_cm from the source record,
+ * truth_beam_ke, truth_ex, truth_theta_cm from the truth, reserved 0.  status bits:
+ *   NO_TRACK        no slot; or its fit record has EMPTY, FEW, NO_START or NO_PID (its estimate record: EMPTY or FEW);
+ *                   or px, py, pz or z is not finite.  beam_ke, ex and theta_cm are NaN.
+ *   OUTSIDE_TARGET  with a target, z is not in z_min .. z_max (both ends inside).  The value is still computed.
+ *   UNPHYSICAL      the value of the source record is not physical; ex and theta_cm are NaN, beam_ke stays.
+ *   NO_TRUTH        the kinematics status is not 0, or the value of the truth is not physical.  The three truth fields
+ *                   are NaN.  (Host kinematics without a status, attpc_det_run_trace_rows, count as status 0.)
+ *
+ * Spectra of a call: u64 cells, reaction_cells = 3 n_ex n_theta + n_ex n_ex + 3 of them, in this order:
+ *   truth               [n_ex][n_theta]  every event without NO_TRUTH, at the truth values;
+ *   truth_reconstructed [n_ex][n_theta]  those of `truth` whose status is 0, at the truth values (their ratio is the
+ *                                        efficiency);
+ *   reconstructed       [n_ex][n_theta]  status 0, at the reconstructed values;
+ *   ex_response         [n_ex truth][n_ex reconstructed]  status 0;
+ *   outside [3]         the events of truth / reconstructed / ex_response one of whose two values is outside its bins.
+ * Bin of v in n bins from lo: outside iff not (v >= lo and v < hi) -- below lo, at or above hi, NaN --, otherwise
+ * floor((v - lo) * inv_width), and n - 1 where that product rounds up to n.  Every term is an integer: the spectra of
+ * disjoint id ranges add, and the chunking of a call cannot change them. */
+#define ATTPC_REACTION_FROM_FIT 0
+#define ATTPC_REACTION_FROM_ESTIMATE 1
+#define ATTPC_REACTION_NO_TRACK 1
+#define ATTPC_REACTION_OUTSIDE_TARGET 2
+#define ATTPC_REACTION_UNPHYSICAL 4
+#define ATTPC_REACTION_NO_TRUTH 8
+#define ATTPC_REACTION_MAX_EX 256
+#define ATTPC_REACTION_MAX_THETA 180
+#define ATTPC_REACTION_MAX_ELOSS 65536
+
+typedef struct attpc_reaction_desc {
+  double masses[4];        /* MeV: target, projectile, ejectile, residual */
+  double beam_energy;      /* MeV */
+  double z_min, z_max;     /* m */
+  double ex_lo, ex_hi;     /* MeV */
+  double ex_inv_width;     /* (double)n_ex / (ex_hi - ex_lo) */
+  double theta_inv_width;  /* (double)n_theta / 3.141592653589793 */
+  const double* eloss;     /* [eloss_len], host memory; copied by the call */
+  int32_t eloss_len;
+  int32_t has_target;
+  int32_t charge;          /* Z of the observed nucleus */
+  int32_t track;           /* layout position */
+  int32_t observed_row;    /* 2 or 3 */
+  int32_t source;          /* ATTPC_REACTION_FROM_* */
+  int32_t n_ex, n_theta;
+  int64_t reserved;        /* 0 */
+} attpc_reaction_desc;  /* 136 bytes */
+
+typedef struct attpc_reaction_record {
+  int32_t status;  /* ATTPC_REACTION_* bits */
+  int32_t slot;    /* -1: none */
+  double beam_ke, ex, theta_cm;
+  double truth_beam_ke, truth_ex, truth_theta_cm;
+  double reserved; /* 0 */
+} attpc_reaction_record;  /* 64 bytes */
+
+/* desc == NULL turns the stage off (the default): no kernel is launched and no buffer is held then.  ATTPC_E_INVALID
+ * for anything the section above rules out.  Independent of every other configure call.  With the stage and its source
+ * on, attpc_sim_run_trace_rows and attpc_det_run_trace_rows launch reaction_kernel behind the last of every chunk's
+ * estimate, pid and fit kernels on the same stream, also when the rows stay on the device; such a call is refused with
+ * ATTPC_E_INVALID if track is not a position of its layout, if the layout has fewer than 4 rows, or if
+ * layout->indices[track] is not observed_row (the track of one nucleus would be read with the mass and the truth row of
+ * another).  With the option "reaction_spectra_only" (attpc_set_option) such a call copies no record to the host.  It holds the table
+ * and the spectra's cells on the device (8 bytes per cell). */
+ATTPC_API int32_t attpc_reaction_configure(attpc_ctx* ctx, const attpc_reaction_desc* desc);
+/* Records [count] of the context's last trace-row call, as attpc_fits_last.  ATTPC_E_NOTCONFIGURED if this stage or
+ * its source was off for that call. */
+ATTPC_API int32_t attpc_reaction_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_reaction_record* out);
+/* The spectra of that call: n_cells must be the reaction_cells of the configured bins. */
+ATTPC_API int32_t attpc_reaction_spectra_last(attpc_ctx* ctx, int64_t n_cells, uint64_t* cells);
+/* The stage alone on host arrays, through the same kernel: fits (source fit) or estimates (source estimate)
+ * [n_events][n_sim], the other may be NULL; pid [n_events][n_sim] or NULL; p4 [n_events][n_rows][4] with n_rows in
+ * 4 .. ATTPC_MAX_ROWS, vertex [n_events][3] in m, kin_status [n_events] or NULL (all 0).  n_sim in 1 .. ATTPC_MAX_SIM
+ * (without pid: > track).  records [n_events] and cells [n_cells] (overwritten, not added to) are the outputs.  Needs
+ * no other configure call and leaves the configured stage as it is. */
+ATTPC_API int32_t attpc_reaction_records(attpc_ctx* ctx, int64_t n_events, int32_t n_sim, int32_t n_rows,
+                                         const attpc_reaction_desc* desc, const attpc_track_fit* fits,
+                                         const attpc_track_estimate* estimates, const attpc_pid_record* pid,
+                                         const double* p4, const double* vertex, const int32_t* kin_status,
+                                         attpc_reaction_record* records, int64_t n_cells, uint64_t* cells);
 
 #ifdef __cplusplus
 }
