@@ -57,6 +57,7 @@ constexpr int64_t DELIVER_CHUNK_ROWS = 96ll << 20;  // cloud rows of a chunk who
 constexpr int64_t TRACE_CHUNK_ROWS = 4ll << 20;     // kept pad rows of a chunk of a trace run (4 GiB of samples)
                                                     // (readout modes too: their first chunk is sized by |S| per event)
 constexpr uint64_t ARENA_BUDGET_BYTES = 24ull << 30;
+constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk of an operator on host rows: whole events up to these (at least one)
 
 struct DevBuf {  // grow-only device buffer (ensure()), freed with its owner
   void* p = nullptr;
@@ -76,6 +77,19 @@ struct Pinned {  // page-locked host array of the library, grow-only (ensure_pin
   Pinned& operator=(const Pinned&) = delete;
   ~Pinned() { if (p) (void)hipHostFree(p); }
   T& operator[](size_t i) const { return p[i]; }
+};
+
+// The records a stage leaves per event of a trace or trace-row call, for its attpc_*_last: the call's pinned array
+// [events][per] in its event order, and which call it answers for (begin_records, chunk_room, copy_chunk, records_last;
+// a chunk's records on the device are a DevBuf of its AsmSet: two chunks are in flight).
+template <typename T>
+struct CallRecords {
+  Pinned<T> h;
+  size_t per = 0;        // records per event of that call
+  int64_t events = -1;   // its events; -1: the call in progress, or the last one, did not make the stream
+  bool to_host = false;  // its records are copied to `h` (a spectra-only call keeps them on the device)
+  bool made() const { return events >= 0; }
+  void off() { events = -1; }
 };
 
 struct DevAllocs {  // the device allocations of one configure call (upload()): freed on clear() and with their owner
@@ -153,6 +167,23 @@ struct UnpackJob {  // one chunk's records in pinned staging -> the caller's arr
   std::vector<int64_t> offsets;
 };
 
+// What a trace-row call settles at its start (begin_trace_row_call) for the stages behind its rows, and the truth of
+// the track batch in progress that the reaction reconstruction reads.  No buffers: the streams hold those.
+struct TraceRowCall {
+  int32_t n_sim = 0;                             // positions of the call's layout (0: it has none)
+  int64_t est_slot_label[ATTPC_MAX_SIM] = {};    // their labels (EstimateArgs)
+  FitPosition fit_position[ATTPC_MAX_SIM] = {};  // their nuclei
+  int32_t pid_species[ATTPC_MAX_SIM] = {};       // their species
+  ClusterSettings cluster{};                     // the clustering's settings with the call's layout
+  JoinSettings join{};                           // the joining's
+  int64_t cluster_rows = -1;       // the delivered rows whose cluster labels are in h_cl_labels so far (-1: it fetches none)
+  const double *rx_p4 = nullptr, *rx_vertex = nullptr;  // the truth of the track batch in progress on the device: p4
+                                   // [events][rx_n_rows][4], vertex [events][3],
+  const int32_t* rx_status = nullptr;  // the kinematics status [events] (nullptr: host kinematics, all 0);
+  uint64_t rx_batch_first = 0;     // the batch's first event in the call's order
+  int32_t rx_n_rows = 0;
+};
+
 }  // namespace
 
 struct attpc_ctx {
@@ -167,7 +198,6 @@ struct attpc_ctx {
   int opt_variant = 0;             // 0 auto, 1 small, 2 big, 3 wide (u64 sums)
   bool opt_tiny = false;
   bool opt_spectra_only = false;   // option "reaction_spectra_only": a trace-row call with the reaction reconstruction copies no records to the host
-  bool records_call = true;        // the trace-row call in progress copies its stages' records (attpc_*_last answer for it)
   int opt_compact = 2;             // delivered clouds cross PCIe as 8-byte (2) / 16-byte (1) records and are expanded
                                    // by host threads, or in the reference's dtypes (0)
   int opt_unpack_threads = 0;      // 0: min(32, half of the hardware threads)
@@ -261,14 +291,11 @@ struct attpc_ctx {
   bool trigger_gate = false;
   DevBuf tg_groups;                // [ATTPC_NUM_PADS] the configured group map (trigger.groups points here, or is nullptr)
   DevBuf tg_op_groups;             // [ATTPC_NUM_PADS] the map of attpc_trigger_rows' last call
-  Pinned<attpc_trigger_record> h_trigger;  // records of the last trace or trace-row call, in its event order
-  int64_t trigger_call_events = -1;        // events of that call, -1: it had no trigger configured (or there was none)
+  CallRecords<attpc_trigger_record> tg_records;  // of the last trace or trace-row call, [events]
   bool estimates_on = false;       // attpc_trace_configure_estimates
   attpc_estimate_desc estimates{};
-  int64_t est_slot_label[ATTPC_MAX_SIM] = {};  // the labels of the positions of the trace-row call in progress (EstimateArgs)
-  Pinned<attpc_track_estimate> h_estimates;    // records of the last trace-row call, [events][n_sim] in its event order
-  int64_t est_call_events = -1;    // events of that call, -1: it made no records (the stage was off, or there was no layout)
-  int32_t est_call_n_sim = 0;      // positions of its layout
+  TraceRowCall call;               // the trace-row call in progress, or the last one
+  CallRecords<attpc_track_estimate> est_records;  // of the last trace-row call, [events][n_sim], as are the streams below
   bool thinning_on = false;        // attpc_trace_configure_thinning (inert while the estimates are off)
   attpc_thin_desc thinning{};
   bool circle_on = false;          // attpc_trace_configure_circle (inert while the estimates are off)
@@ -277,28 +304,18 @@ struct attpc_ctx {
   attpc_helix_desc helix{};
   bool fit_on = false;             // attpc_trace_configure_fit (inert while the estimates are off)
   attpc_fit_desc fit{};
-  FitPosition fit_position[ATTPC_MAX_SIM] = {};  // the nuclei of the positions of the trace-row call in progress
-  Pinned<attpc_track_fit> h_fits;  // records of the last trace-row call, as h_estimates
-  bool fit_call = false;           // that call made them
+  CallRecords<attpc_track_fit> fit_records;  // [events][n_sim]
   DevBuf fit_scratch;              // the trials' residuals (FitArgs::scratch), shared by the chunks: they run in stream order
   bool pid_on = false;             // attpc_trace_configure_pid (inert while the estimates are off)
   attpc_pid_desc pid{};
   DevBuf pid_gates;                // the gates on the device (PidGates), filled by the configure call
-  int32_t pid_species[ATTPC_MAX_SIM] = {};  // the species of the positions of the trace-row call in progress
-  Pinned<attpc_pid_record> h_pid;  // records of the last trace-row call, as h_estimates
-  bool pid_call = false;           // that call made them
+  CallRecords<attpc_pid_record> pid_records;  // [events][n_sim]
   bool reaction_on = false;        // attpc_reaction_configure (inert while its source is off)
   attpc_reaction_desc reaction{};  // (eloss: nullptr, the table is in rx_eloss)
   DevBuf rx_eloss;                 // the table on the device, filled by the configure call
   DevBuf rx_cells;                 // the spectra of the trace-row call in progress, u64 [reaction_cells]
-  Pinned<attpc_reaction_record> h_reaction;  // records of the last trace-row call, [events] in its event order
+  CallRecords<attpc_reaction_record> rx_records;  // [events] (made and not to_host: the call left its spectra alone)
   std::vector<uint64_t> h_rx_cells;          // its spectra
-  bool reaction_call = false;      // that call made them
-  const double* rx_p4 = nullptr;   // the truth of the track batch in progress on the device: p4 [events][rx_n_rows][4],
-  const double* rx_vertex = nullptr;         // vertex [events][3],
-  const int32_t* rx_status = nullptr;        // the kinematics status [events] (nullptr: host kinematics, all 0);
-  uint64_t rx_batch_first = 0;     // the batch's first event in the call's order
-  int32_t rx_n_rows = 0;
   bool summary_on = false;         // attpc_summary_configure
   double summary_min = 0.0;        // min_electrons (kept: q >= it)
   const double* summary_centers = nullptr;  // [n_pads][2] on the device, the mode's own copy
@@ -326,18 +343,13 @@ struct attpc_ctx {
   bool cluster_on = false;         // attpc_trace_configure_clustering
   attpc_cluster_desc cluster{};
   DevBuf cl_scratch;               // [rows][CLUSTER_SCRATCH_WORDS] the per-row state of the chunk being clustered (cluster.hip)
-  int64_t cluster_call_events = -1;  // attpc_clusters_last: events of the last trace-row call, -1: the stage was off for it
-  ClusterSettings cluster_call{};  // ... its settings with the call's layout
-  Pinned<attpc_cluster_event> h_cl_events;    // ... and its records, as h_estimates
-  Pinned<attpc_cluster_record> h_cl_records;
-  Pinned<int64_t> h_cl_labels;     // attpc_cluster_labels_last: the cluster labels of the call's delivered rows,
-  int64_t cluster_call_rows = -1;  // ... how many (-1: the call did not fetch its rows)
+  CallRecords<attpc_cluster_event> cl_events;     // [events]
+  CallRecords<attpc_cluster_record> cl_records;   // [events][ATTPC_MAX_SIM]
+  Pinned<int64_t> h_cl_labels;     // attpc_cluster_labels_last: the cluster labels of the call's delivered rows (call.cluster_rows)
   bool join_on = false;            // attpc_trace_configure_cluster_join
   attpc_join_desc join{};
-  bool join_call = false;          // attpc_joins_last: the last trace-row call joined its clusters (cluster_call_events of them)
-  JoinSettings join_call_settings{};  // ... with these settings
-  Pinned<attpc_join_event> h_jn_events;    // ... and its join records, as h_cl_events
-  Pinned<attpc_join_record> h_jn_records;
+  CallRecords<attpc_join_event> jn_events;     // [events]
+  CallRecords<attpc_join_record> jn_records;   // [events][ATTPC_MAX_SIM]
   int64_t last_rows = 0;           // attpc_trace_rows_last: rows and row checksum of the last trace-row call
   uint64_t last_row_checksum = 0;
   double trace_rows_per_event = 0.0;  // observed kept pad rows per event (bounds the chunks of a trace run)
@@ -397,6 +409,12 @@ int32_t ensure(attpc_ctx* ctx, DevBuf& b, size_t bytes) {
   b.bytes = bytes;
   ctx->device_bytes += bytes;
   return ATTPC_OK;
+}
+
+// ... given back (a stage turned off): nothing in flight uses it
+void release(attpc_ctx* ctx, DevBuf& b) {
+  ctx->device_bytes -= b.bytes;
+  b = DevBuf{};
 }
 
 // Staging of an operator on host arrays: scratch slot `k` as `n` elements of T, grow-only like ensure() -- the byte count
@@ -539,6 +557,12 @@ int32_t configure_desc(attpc_ctx* ctx, const Desc* d, const char* (*desc_error)(
   return ATTPC_OK;
 }
 
+// ATTPC_E_INVALID under the name `func` for a number of track positions outside 0 .. ATTPC_MAX_SIM
+int32_t n_sim_range(attpc_ctx* ctx, const char* func, int32_t n_sim) {
+  if (n_sim >= 0 && n_sim <= ATTPC_MAX_SIM) return ATTPC_OK;
+  return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", func, n_sim, ATTPC_MAX_SIM);
+}
+
 // attpc_*_last under the name `func`: records first .. first + count of a call of `events` events, `per_event` of them
 // per event, from the call's pinned array `src` to `dst` (nullptr: refused if `required`, else not wanted)
 template <typename Record>
@@ -549,6 +573,45 @@ int32_t copy_last(attpc_ctx* ctx, const char* func, int64_t first, int64_t count
   if (!dst) return required ? ATTPC_E_INVALID : ATTPC_OK;
   std::memcpy(dst, src + (size_t)first * per_event, (size_t)count * per_event * sizeof(Record));
   return ATTPC_OK;
+}
+
+// The start of a call of `n` events that makes the stream `r`, `per` records per event: pinned room for them (none if
+// they stay on the device), then the stream is the call's.  Nothing of an earlier call is in flight.
+template <typename T>
+int32_t begin_records(attpc_ctx* ctx, CallRecords<T>& r, uint64_t n, size_t per, bool to_host = true) {
+  r.off();
+  const int32_t rc = ensure_pinned(ctx, r.h, to_host ? std::max<size_t>((size_t)n * per, 1) : 0);
+  if (rc) return rc;
+  r.per = per;
+  r.events = (int64_t)n;
+  r.to_host = to_host;
+  return ATTPC_OK;
+}
+
+// Room for the records of a chunk of `n` events of the stream in `dev`, the set's buffer for them (`rc` as stage()).
+template <typename T>
+T* chunk_room(attpc_ctx* ctx, const CallRecords<T>& r, DevBuf& dev, uint32_t n, int32_t& rc) {
+  if (!rc) rc = ensure(ctx, dev, (size_t)n * r.per * sizeof(T));
+  return rc ? nullptr : static_cast<T*>(dev.p);
+}
+
+// ... and their copy to events first_local .. of the call's pinned array, on C (the caller has made C wait for them):
+// nothing if the call does not make the stream or keeps it on the device.
+template <typename T>
+int32_t copy_chunk(attpc_ctx* ctx, const CallRecords<T>& r, const DevBuf& dev, uint64_t first_local, uint32_t n) {
+  if (!r.made() || !r.to_host || !n) return ATTPC_OK;
+  HIP_TRY(ctx, hipMemcpyAsync(r.h.p + (size_t)first_local * r.per, dev.p, (size_t)n * r.per * sizeof(T), hipMemcpyDeviceToHost,
+                              ctx->stream_c));
+  return ATTPC_OK;
+}
+
+// attpc_*_last under the name `func`: records first .. first + count of the stream to `out` (copy_last), or
+// ATTPC_E_NOTCONFIGURED with `why` if the last call did not make the stream or kept it on the device.
+template <typename T>
+int32_t records_last(attpc_ctx* ctx, const CallRecords<T>& r, const char* func, const char* why, int64_t first, int64_t count,
+                     T* out, bool required = true) {
+  if (!r.made() || !r.to_host) return fail(ctx, ATTPC_E_NOTCONFIGURED, "%s: %s", func, why);
+  return copy_last(ctx, func, first, count, r.events, r.per, r.h.p, out, required);
 }
 
 // A first track batch queued ahead for a call that does not come (another entry point, other events, a new
@@ -1174,12 +1237,8 @@ int32_t enqueue_trace_write(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t tota
 // The start of a trace or trace-row call of `n` events: room for its trigger records (attpc_trigger_last), if a trigger
 // is configured.  Nothing of an earlier call is in flight.
 int32_t begin_trigger_call(attpc_ctx* ctx, uint64_t n) {
-  ctx->trigger_call_events = -1;
-  if (!ctx->trigger_on) return ATTPC_OK;
-  const int32_t rc = ensure_pinned(ctx, ctx->h_trigger, std::max<size_t>((size_t)n, 1));
-  if (rc) return rc;
-  ctx->trigger_call_events = (int64_t)n;
-  return ATTPC_OK;
+  ctx->tg_records.off();
+  return ctx->trigger_on ? begin_records(ctx, ctx->tg_records, n, 1) : ATTPC_OK;
 }
 
 // The positions of `lay` as the estimate kernel takes them: the label of every position, -1 for a later position of a
@@ -1297,17 +1356,24 @@ int32_t enqueue_reaction(attpc_ctx* ctx, ReactionArgs a, const attpc_reaction_de
   return ATTPC_OK;
 }
 
-// The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none and makes no records):
-// room for its track estimates (attpc_estimates_last), if the stage is on.  Nothing of an earlier call is in flight.
-int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay) {
-  ctx->est_call_events = -1;
-  ctx->fit_call = false;
-  ctx->pid_call = false;
-  ctx->reaction_call = false;
-  ctx->records_call = true;
-  if (!ctx->estimates_on || !lay) return ATTPC_OK;
-  // (the reconstruction does nothing without its source; what it cannot read is refused before the call has any state)
-  const bool reaction = ctx->reaction_on && (ctx->reaction.source == ATTPC_REACTION_FROM_ESTIMATE || ctx->fit_on);
+// The streams of a trace-row call turned off: none answers for any call.
+void trace_row_records_off(attpc_ctx* ctx) {
+  auto off = [](auto&... r) { (r.off(), ...); };
+  off(ctx->est_records, ctx->fit_records, ctx->pid_records, ctx->rx_records, ctx->cl_events, ctx->cl_records, ctx->jn_events, ctx->jn_records);
+}
+
+// The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none, makes no records and
+// is not clustered) that fetches `row_capacity` rows (-1: none): every stream of an earlier call off and a fresh call
+// state, then what the call cannot do refused, then the streams of the stages that are on -- with their pinned room --
+// and what these stages read of the layout.  Nothing of an earlier call is in flight.
+int32_t begin_trace_row_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay, int64_t row_capacity) {
+  trace_row_records_off(ctx);
+  TraceRowCall& call = ctx->call = TraceRowCall{};
+  if (!lay) return ATTPC_OK;
+  call.n_sim = lay->n_sim;
+  // (the fit, the identification and the reconstruction do nothing without the estimates, the reconstruction nothing
+  //  without its source; what it cannot read is refused before the call has any stream)
+  const bool reaction = ctx->estimates_on && ctx->reaction_on && (ctx->reaction.source == ATTPC_REACTION_FROM_ESTIMATE || ctx->fit_on);
   if (reaction && (ctx->reaction.track >= lay->n_sim || lay->n_rows < 4))
     return fail(ctx, ATTPC_E_INVALID, "reaction: track %d and rows 0 .. 3 need a layout of more than %d positions and %d rows",
                 ctx->reaction.track, lay->n_sim, lay->n_rows);
@@ -1315,34 +1381,48 @@ int32_t begin_estimate_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout
     return fail(ctx, ATTPC_E_INVALID, "reaction: position %d of the layout is row %d, observed_row is %d", ctx->reaction.track,
                 lay->indices[ctx->reaction.track], ctx->reaction.observed_row);
   // a spectra-only call (option reaction_spectra_only) keeps every record on the device: no pinned room, no copy
-  ctx->records_call = !(reaction && ctx->opt_spectra_only);
-  const size_t room = ctx->records_call ? std::max<size_t>((size_t)n * (size_t)lay->n_sim, 1) : 0;
-  const int32_t rc = ensure_pinned(ctx, ctx->h_estimates, room);
-  if (rc) return rc;
-  estimate_positions(*lay, ctx->est_slot_label);
-  ctx->est_call_n_sim = lay->n_sim;
-  ctx->est_call_events = (int64_t)n;
-  if (ctx->fit_on) {
-    const int32_t rc2 = ensure_pinned(ctx, ctx->h_fits, room);
-    if (rc2) return rc2;
-    fit_positions(ctx->det, *lay, ctx->fit_position);
-    ctx->fit_call = true;
-  }
-  if (ctx->pid_on) {  // (the identification does nothing without the estimates)
-    const int32_t rc2 = ensure_pinned(ctx, ctx->h_pid, room);
-    if (rc2) return rc2;
-    if (!ctx->fit_on) fit_positions(ctx->det, *lay, ctx->fit_position);
-    for (int s = 0; s < ATTPC_MAX_SIM; ++s) ctx->pid_species[s] = ctx->fit_position[s].table;
-    ctx->pid_call = true;
+  const bool to_host = !(reaction && ctx->opt_spectra_only);
+  const size_t n_sim = (size_t)lay->n_sim;
+  int32_t rc;
+  if (ctx->estimates_on) {
+    if ((rc = begin_records(ctx, ctx->est_records, n, n_sim, to_host))) return rc;
+    estimate_positions(*lay, call.est_slot_label);
+    if (ctx->fit_on || ctx->pid_on) {
+      fit_positions(ctx->det, *lay, call.fit_position);
+      for (int s = 0; s < ATTPC_MAX_SIM; ++s) call.pid_species[s] = call.fit_position[s].table;
+    }
+    if (ctx->fit_on && (rc = begin_records(ctx, ctx->fit_records, n, n_sim, to_host))) return rc;
+    if (ctx->pid_on && (rc = begin_records(ctx, ctx->pid_records, n, n_sim, to_host))) return rc;
   }
   if (reaction) {
-    const int32_t rc2 = ensure_pinned(ctx, ctx->h_reaction, ctx->records_call ? std::max<size_t>((size_t)n, 1) : 0);
-    if (rc2) return rc2;
+    if ((rc = begin_records(ctx, ctx->rx_records, n, 1, to_host))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->rx_cells.p, 0, ctx->rx_cells.bytes, ctx->stream));
-    ctx->rx_n_rows = lay->n_rows;
-    ctx->reaction_call = true;
+    call.rx_n_rows = lay->n_rows;
+  }
+  if (!ctx->cluster_on) return ATTPC_OK;  // (the joining does nothing without the clustering)
+  if ((rc = begin_records(ctx, ctx->cl_events, n, 1, to_host))) return rc;
+  if ((rc = begin_records(ctx, ctx->cl_records, n, ATTPC_MAX_SIM, to_host))) return rc;
+  call.cluster = cluster_settings(ctx->cluster, *lay);
+  if (ctx->join_on) {
+    if ((rc = begin_records(ctx, ctx->jn_events, n, 1, to_host))) return rc;
+    if ((rc = begin_records(ctx, ctx->jn_records, n, ATTPC_MAX_SIM, to_host))) return rc;
+    call.join = join_settings(ctx->join);
+  }
+  if (row_capacity >= 0) {
+    if ((rc = ensure_pinned(ctx, ctx->h_cl_labels, std::max<size_t>((size_t)row_capacity, 1)))) return rc;
+    call.cluster_rows = 0;
   }
   return ATTPC_OK;
+}
+
+// The start of a trace (`rows` false) or trace-row call: begin_trace_row_call and begin_trigger_call.  A call that
+// either refuses leaves every stream it would have reset turned off.
+int32_t begin_record_streams(attpc_ctx* ctx, bool rows, uint64_t n, const attpc_event_layout* lay, int64_t row_capacity) {
+  int32_t rc = rows ? begin_trace_row_call(ctx, n, lay, row_capacity) : ATTPC_OK;
+  if (!rc) rc = begin_trigger_call(ctx, n);
+  if (rc) ctx->tg_records.off();
+  if (rc && rows) trace_row_records_off(ctx);
+  return rc;
 }
 
 // What the reconstruction stages and the delivery read of the chunk in `as`: the starts of its events and its rows and
@@ -1371,20 +1451,21 @@ void launch_estimate_kernel(hipStream_t stream, uint32_t n, const EstimateArgs& 
 // With thinning on the rows are thinned first (thin.hip) and the estimates are those of the points; with the geometric
 // circle fit on the estimate kernel is its refining instantiation, with the helix slope on the one with its third pass.
 int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first_local) {
-  const size_t n_sim = (size_t)ctx->est_call_n_sim;
+  const TraceRowCall& call = ctx->call;
+  const size_t n_sim = (size_t)call.n_sim;
   if (!n || !n_sim) return ATTPC_OK;
-  int32_t rc;
-  if ((rc = ensure(ctx, as.est_records, (size_t)n * n_sim * sizeof(attpc_track_estimate)))) return rc;
+  int32_t rc = ATTPC_OK;
+  EstimateArgs a{};
+  a.records = chunk_room(ctx, ctx->est_records, as.est_records, n, rc);
+  if (rc) return rc;
   if (ctx->thinning_on) {  // (a point per trace row is room enough: pk_cap is what sp_rows holds)
     if ((rc = ensure(ctx, as.thin_points, std::max<size_t>(as.pk_cap, 1) * sizeof(ThinPoint)))) return rc;
     if ((rc = ensure(ctx, as.thin_info, (size_t)n * n_sim * sizeof(attpc_thin_info)))) return rc;
   }
-  EstimateArgs a{};
   estimate_settings(ctx->estimates, &a);
   chunk_rows(ctx, as).into(a);
-  if (ctx->cluster_call_events >= 0) a.labels = static_cast<const int64_t*>(as.cl_labels.p);  // (clustering on: its labels)
-  a.records = static_cast<attpc_track_estimate*>(as.est_records.p);
-  std::memcpy(a.slot_label, ctx->est_slot_label, sizeof a.slot_label);
+  if (ctx->cl_events.made()) a.labels = static_cast<const int64_t*>(as.cl_labels.p);  // (clustering on: its labels)
+  std::memcpy(a.slot_label, call.est_slot_label, sizeof a.slot_label);
   a.n_sim = (int32_t)n_sim;
   if (ctx->thinning_on) {
     ThinArgs t{};
@@ -1406,50 +1487,37 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   launch_estimate_kernel(ctx->stream, n, a, ctx->thinning_on, ctx->circle_on, ctx->helix_on);
   HIP_TRY(ctx, hipGetLastError());
   const attpc_pid_record* pid = nullptr;
-  if (ctx->pid_call) {
-    if ((rc = ensure(ctx, as.pid_records, (size_t)n * n_sim * sizeof(attpc_pid_record)))) return rc;
-    if ((rc = enqueue_pid(ctx, a.records, n, a.n_sim, ctx->pid_gates, ctx->pid.mode, ctx->pid_species,
-                          static_cast<attpc_pid_record*>(as.pid_records.p))))
-      return rc;
-    pid = static_cast<const attpc_pid_record*>(as.pid_records.p);
+  if (ctx->pid_records.made()) {
+    attpc_pid_record* records = chunk_room(ctx, ctx->pid_records, as.pid_records, n, rc);
+    if (rc || (rc = enqueue_pid(ctx, a.records, n, a.n_sim, ctx->pid_gates, ctx->pid.mode, call.pid_species, records))) return rc;
+    pid = records;
   }
-  if (ctx->fit_call) {
-    if ((rc = ensure(ctx, as.fit_records, (size_t)n * n_sim * sizeof(attpc_track_fit)))) return rc;
-    if ((rc = enqueue_fit(ctx, a, n, ctx->fit, ctx->fit_position, nullptr, pid, static_cast<attpc_track_fit*>(as.fit_records.p))))
-      return rc;
+  if (ctx->fit_records.made()) {
+    attpc_track_fit* records = chunk_room(ctx, ctx->fit_records, as.fit_records, n, rc);
+    if (rc || (rc = enqueue_fit(ctx, a, n, ctx->fit, call.fit_position, nullptr, pid, records))) return rc;
   }
-  if (ctx->reaction_call) {  // behind the last of the estimate, pid and fit kernels
-    if ((rc = ensure(ctx, as.rx_records, (size_t)n * sizeof(attpc_reaction_record)))) return rc;
-    const size_t b = (size_t)(first_local - ctx->rx_batch_first);  // the chunk's first event in its track batch
+  if (ctx->rx_records.made()) {  // behind the last of the estimate, pid and fit kernels
+    const size_t b = (size_t)(first_local - call.rx_batch_first);  // the chunk's first event in its track batch
     ReactionArgs r{};
     r.fits = static_cast<const attpc_track_fit*>(as.fit_records.p);
     r.estimates = a.records;
     r.pid = pid;
-    r.p4 = ctx->rx_p4 + b * (size_t)ctx->rx_n_rows * 4;
-    r.vertex = ctx->rx_vertex + b * 3;
-    r.kin_status = ctx->rx_status ? ctx->rx_status + b : nullptr;
-    r.records = static_cast<attpc_reaction_record*>(as.rx_records.p);
+    r.p4 = call.rx_p4 + b * (size_t)call.rx_n_rows * 4;
+    r.vertex = call.rx_vertex + b * 3;
+    r.kin_status = call.rx_status ? call.rx_status + b : nullptr;
+    r.records = chunk_room(ctx, ctx->rx_records, as.rx_records, n, rc);
     r.cells = static_cast<unsigned long long*>(ctx->rx_cells.p);
     r.n_events = n;
     r.n_sim = a.n_sim;
-    r.n_rows = ctx->rx_n_rows;
-    if ((rc = enqueue_reaction(ctx, r, ctx->reaction, ctx->rx_eloss))) return rc;
+    r.n_rows = call.rx_n_rows;
+    if (rc || (rc = enqueue_reaction(ctx, r, ctx->reaction, ctx->rx_eloss))) return rc;
   }
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
-  if (!ctx->records_call) return ATTPC_OK;  // (a spectra-only call: the chunk's records stay where they are)
-  if (ctx->reaction_call)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_reaction.p + first_local, as.rx_records.p, (size_t)n * sizeof(attpc_reaction_record),
-                                hipMemcpyDeviceToHost, ctx->stream_c));
-  if (ctx->fit_call)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_fits.p + first_local * n_sim, as.fit_records.p, (size_t)n * n_sim * sizeof(attpc_track_fit),
-                                hipMemcpyDeviceToHost, ctx->stream_c));
-  if (ctx->pid_call)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pid.p + first_local * n_sim, as.pid_records.p, (size_t)n * n_sim * sizeof(attpc_pid_record),
-                                hipMemcpyDeviceToHost, ctx->stream_c));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_estimates.p + first_local * n_sim, as.est_records.p,
-                              (size_t)n * n_sim * sizeof(attpc_track_estimate), hipMemcpyDeviceToHost, ctx->stream_c));
-  return ATTPC_OK;
+  if ((rc = copy_chunk(ctx, ctx->rx_records, as.rx_records, first_local, n))) return rc;
+  if ((rc = copy_chunk(ctx, ctx->fit_records, as.fit_records, first_local, n))) return rc;
+  if ((rc = copy_chunk(ctx, ctx->pid_records, as.pid_records, first_local, n))) return rc;
+  return copy_chunk(ctx, ctx->est_records, as.est_records, first_local, n);
 }
 
 // The drift correction of the chunk in `as` (n events, rows written: directly behind launch_peak_rows, which is done
@@ -1477,32 +1545,6 @@ int32_t enqueue_correction(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
   return ATTPC_OK;
 }
 
-// The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none and is not clustered):
-// room for its cluster records and, if the call fetches its rows (`row_capacity` of them, -1: it does not), for their
-// cluster labels.  Nothing of an earlier call is in flight.
-int32_t begin_cluster_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layout* lay, int64_t row_capacity) {
-  ctx->cluster_call_events = -1;
-  ctx->cluster_call_rows = -1;
-  ctx->join_call = false;
-  if (!ctx->cluster_on || !lay) return ATTPC_OK;
-  int32_t rc;
-  if (ctx->join_on) {  // (the joining does nothing without the clustering)
-    if ((rc = ensure_pinned(ctx, ctx->h_jn_events, std::max<size_t>((size_t)n, 1)))) return rc;
-    if ((rc = ensure_pinned(ctx, ctx->h_jn_records, std::max<size_t>((size_t)n * ATTPC_MAX_SIM, 1)))) return rc;
-    ctx->join_call_settings = join_settings(ctx->join);
-    ctx->join_call = true;
-  }
-  if ((rc = ensure_pinned(ctx, ctx->h_cl_events, std::max<size_t>((size_t)n, 1)))) return rc;
-  if ((rc = ensure_pinned(ctx, ctx->h_cl_records, std::max<size_t>((size_t)n * ATTPC_MAX_SIM, 1)))) return rc;
-  if (row_capacity >= 0) {
-    if ((rc = ensure_pinned(ctx, ctx->h_cl_labels, std::max<size_t>((size_t)row_capacity, 1)))) return rc;
-    ctx->cluster_call_rows = 0;
-  }
-  ctx->cluster_call = cluster_settings(ctx->cluster, *lay);
-  ctx->cluster_call_events = (int64_t)n;
-  return ATTPC_OK;
-}
-
 // The clustering of the chunk in `as` (n events; rows written, and corrected if the drift correction is on) on S: the
 // rows and truth labels every later stage would read -> as.cl_labels, the labels the thinning, the estimates and the
 // fit read instead, and the chunk's records.
@@ -1511,26 +1553,23 @@ int32_t enqueue_clustering(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
   const size_t cap = std::max<size_t>(as.pk_cap, 1);
   int32_t rc;
   if ((rc = ensure(ctx, as.cl_labels, cap * sizeof(int64_t)))) return rc;
-  if ((rc = ensure(ctx, as.cl_events, (size_t)n * sizeof(attpc_cluster_event)))) return rc;
-  if ((rc = ensure(ctx, as.cl_records, (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_cluster_record)))) return rc;
-  if ((rc = ensure(ctx, ctx->cl_scratch, cap * CLUSTER_SCRATCH_WORDS * sizeof(int32_t)))) return rc;
   ClusterArgs a{};
-  a.s = ctx->cluster_call;
+  a.events = chunk_room(ctx, ctx->cl_events, as.cl_events, n, rc);
+  a.records = chunk_room(ctx, ctx->cl_records, as.cl_records, n, rc);
+  if (rc || (rc = ensure(ctx, ctx->cl_scratch, cap * CLUSTER_SCRATCH_WORDS * sizeof(int32_t)))) return rc;
+  a.s = ctx->call.cluster;
   chunk_rows(ctx, as).into(a);
   a.scratch = static_cast<int32_t*>(ctx->cl_scratch.p);
   a.out_labels = static_cast<int64_t*>(as.cl_labels.p);
-  a.events = static_cast<attpc_cluster_event*>(as.cl_events.p);
-  a.records = static_cast<attpc_cluster_record*>(as.cl_records.p);
   launch_cluster(ctx->stream, n, a);
   HIP_TRY(ctx, hipGetLastError());
-  if (ctx->join_call) {  // right behind the clustering on S: it reads the scratch that kernel left
-    if ((rc = ensure(ctx, as.jn_events, (size_t)n * sizeof(attpc_join_event)))) return rc;
-    if ((rc = ensure(ctx, as.jn_records, (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_join_record)))) return rc;
+  if (ctx->jn_events.made()) {  // right behind the clustering on S: it reads the scratch that kernel left
     ClusterJoinArgs j{};
     j.c = a;
-    j.j = ctx->join_call_settings;
-    j.join_events = static_cast<attpc_join_event*>(as.jn_events.p);
-    j.join_records = static_cast<attpc_join_record*>(as.jn_records.p);
+    j.j = ctx->call.join;
+    j.join_events = chunk_room(ctx, ctx->jn_events, as.jn_events, n, rc);
+    j.join_records = chunk_room(ctx, ctx->jn_records, as.jn_records, n, rc);
+    if (rc) return rc;
     launch_cluster_join(ctx->stream, n, j);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -1542,24 +1581,22 @@ int32_t enqueue_clustering(attpc_ctx* ctx, AsmSet& as, uint32_t n) {
 // to events first_local .. of the call's pinned array on C.
 int32_t enqueue_trigger(attpc_ctx* ctx, AsmSet& as, uint32_t n, int64_t total, uint64_t first_local, bool gate) {
   if (!n) return ATTPC_OK;
-  int32_t rc;
-  if ((rc = ensure(ctx, as.tg_records, (size_t)n * sizeof(attpc_trigger_record)))) return rc;
-  if (gate && (rc = ensure(ctx, as.tg_row_pass, std::max<size_t>(as.tr_cap, (size_t)std::max<int64_t>(total, 1))))) return rc;
+  int32_t rc = ATTPC_OK;
   TriggerArgs a{};
+  a.records = chunk_room(ctx, ctx->tg_records, as.tg_records, n, rc);
+  if (rc) return rc;
+  if (gate && (rc = ensure(ctx, as.tg_row_pass, std::max<size_t>(as.tr_cap, (size_t)std::max<int64_t>(total, 1))))) return rc;
   a.tg = ctx->trigger;
   a.pedestals = ctx->noise_on ? ctx->noise.pedestals : nullptr;
   a.kept_start = static_cast<const int64_t*>(as.kept_start.p);
   a.pads = static_cast<const int32_t*>(as.tr_pads.p);
   a.samples = static_cast<const int16_t*>(as.tr_samples.p);
-  a.records = static_cast<attpc_trigger_record*>(as.tg_records.p);
   a.row_pass = gate ? static_cast<uint8_t*>(as.tg_row_pass.p) : nullptr;
   launch_trigger(ctx->stream, n, a);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_trigger.p + first_local, as.tg_records.p, (size_t)n * sizeof(attpc_trigger_record),
-                              hipMemcpyDeviceToHost, ctx->stream_c));
-  return ATTPC_OK;
+  return copy_chunk(ctx, ctx->tg_records, as.tg_records, first_local, n);
 }
 
 // Queue the copies of the written traces of `as` (rows base .. base + total of the caller's arrays; any array may be
@@ -1881,21 +1918,28 @@ int32_t copy_rows(attpc_ctx* ctx, AsmSet& as, uint32_t n, const RunOut& o, int64
 int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t first_local, uint64_t seed,
                            uint64_t first_global);
 
+// The row cursor of `o` past the chunk of `n` events in `as` whose CSR offsets are `start` [n + 1]: its offsets and
+// event_points into the caller's arrays; false, and o.over, if the caller's capacity does not hold its rows.
+bool advance_rows(RunOut& o, const AsmSet& as, const Pinned<int64_t>& start, uint32_t n, uint64_t first_local) {
+  if (int64_t* offsets = o.offsets())
+    for (uint32_t i = 0; i <= n; ++i) offsets[first_local + i] = o.rows + start[i];
+  if (int64_t* event_points = o.event_points())
+    for (uint32_t i = 0; i < n; ++i) event_points[first_local + i] = (int64_t)as.h_ev_rows[i];
+  o.rows += start[n];
+  const bool fits = !o.bounded() || o.rows <= o.capacity();
+  if (!fits) o.over = true;
+  return fits;
+}
+
 int32_t deliver(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, uint64_t first_local, uint64_t seed, uint64_t first_global) {
   if (o.mode == OutMode::trace_rows) return deliver_trace_rows(ctx, o, as, n, first_local, seed, first_global);
   const int64_t base = o.rows, total = as.h_start[n];
-  if (int64_t* offsets = o.offsets())
-    for (uint32_t i = 0; i <= n; ++i) offsets[first_local + i] = base + as.h_start[i];
-  if (int64_t* event_points = o.event_points())
-    for (uint32_t i = 0; i < n; ++i) event_points[first_local + i] = (int64_t)as.h_ev_rows[i];
-  o.rows = base + total;
-  const bool fits = !o.bounded() || o.rows <= o.capacity();
-  if (!fits) o.over = true;
+  const bool fits = advance_rows(o, as, as.h_start, n, first_local);
   if (o.mode != OutMode::traces) return copy_rows(ctx, as, n, o, base, total, fits, seed, first_global);
   if (n) ctx->trace_rows_per_event = std::max((double)total / (double)n, 1.0e-3);
   int32_t rc;
   if ((rc = enqueue_trace_write(ctx, as, n, total, seed, first_global))) return rc;
-  if (ctx->trigger_on && (rc = enqueue_trigger(ctx, as, n, total, first_local, false))) return rc;
+  if (ctx->tg_records.made() && (rc = enqueue_trigger(ctx, as, n, total, first_local, false))) return rc;
   if (o.tpacked) return deliver_packed_traces(ctx, o, as, total, base, fits);
   return copy_traces(ctx, as, total, base, o.trace, fits);
 }
@@ -1910,8 +1954,8 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
   if (n) ctx->trace_rows_per_event = std::max((double)traces / (double)n, 1.0e-3);
   int32_t rc;
   if ((rc = enqueue_trace_write(ctx, as, n, traces, seed, first_global))) return rc;
-  const bool gated = ctx->trigger_on && ctx->trigger_gate;
-  if (ctx->trigger_on && (rc = enqueue_trigger(ctx, as, n, traces, first_local, gated))) return rc;
+  const bool gated = ctx->tg_records.made() && ctx->trigger_gate;
+  if (ctx->tg_records.made() && (rc = enqueue_trigger(ctx, as, n, traces, first_local, gated))) return rc;
   const uint8_t* row_pass = gated ? static_cast<const uint8_t*>(as.tg_row_pass.p) : nullptr;
   const size_t tr = (size_t)std::max<int64_t>(traces, 1);
   if ((rc = ensure(ctx, as.pk_maps, tr * 64))) return rc;
@@ -1955,13 +1999,7 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
   HIP_TRY(ctx, hipEventRecord(as.counted, ctx->stream));
   HIP_TRY(ctx, hipEventSynchronize(as.counted));
   const int64_t total = as.h_pk_start[n];
-  if (int64_t* offsets = o.offsets())
-    for (uint32_t i = 0; i <= n; ++i) offsets[first_local + i] = base + as.h_pk_start[i];
-  if (int64_t* event_points = o.event_points())
-    for (uint32_t i = 0; i < n; ++i) event_points[first_local + i] = (int64_t)as.h_ev_rows[i];
-  o.rows = base + total;
-  const bool fits = !o.bounded() || o.rows <= o.capacity();
-  if (!fits) o.over = true;
+  const bool fits = advance_rows(o, as, as.h_pk_start, n, first_local);
   if (total > 0) {
     if ((size_t)total > as.pk_cap) as.pk_cap = (size_t)total + (size_t)total / 8;
     if ((rc = ensure(ctx, as.pk_records, as.pk_cap * sizeof(uint4)))) return rc;
@@ -1982,27 +2020,19 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->correction_on && (rc = enqueue_correction(ctx, as, n))) return rc;
   }
-  const bool clustered = ctx->cluster_call_events >= 0 && n > 0;
+  const bool clustered = ctx->cl_events.made() && n > 0;
   if (clustered && (rc = enqueue_clustering(ctx, as, n))) return rc;  // (an event without rows has a record too)
   HIP_TRY(ctx, hipEventRecord(as.traced, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream_c, as.traced, 0));
-  if (clustered && ctx->records_call) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_events.p + first_local, as.cl_events.p, (size_t)n * sizeof(attpc_cluster_event),
-                                hipMemcpyDeviceToHost, ctx->stream_c));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_records.p + first_local * ATTPC_MAX_SIM, as.cl_records.p,
-                                (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_cluster_record), hipMemcpyDeviceToHost, ctx->stream_c));
-    if (ctx->join_call) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_jn_events.p + first_local, as.jn_events.p, (size_t)n * sizeof(attpc_join_event),
+  if ((rc = copy_chunk(ctx, ctx->cl_events, as.cl_events, first_local, n))) return rc;
+  if ((rc = copy_chunk(ctx, ctx->cl_records, as.cl_records, first_local, n))) return rc;
+  if ((rc = copy_chunk(ctx, ctx->jn_events, as.jn_events, first_local, n))) return rc;
+  if ((rc = copy_chunk(ctx, ctx->jn_records, as.jn_records, first_local, n))) return rc;
+  if (clustered && ctx->cl_events.to_host && ctx->call.cluster_rows >= 0 && fits && o.cloud->points) {
+    if (total > 0)
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_labels.p + base, as.cl_labels.p, (size_t)total * sizeof(int64_t),
                                   hipMemcpyDeviceToHost, ctx->stream_c));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_jn_records.p + first_local * ATTPC_MAX_SIM, as.jn_records.p,
-                                  (size_t)n * ATTPC_MAX_SIM * sizeof(attpc_join_record), hipMemcpyDeviceToHost, ctx->stream_c));
-    }
-    if (ctx->cluster_call_rows >= 0 && fits && o.cloud->points) {
-      if (total > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_cl_labels.p + base, as.cl_labels.p, (size_t)total * sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, ctx->stream_c));
-      ctx->cluster_call_rows = base + total;
-    }
+    ctx->call.cluster_rows = base + total;
   }
   if (total > 0 && fits) {
     const ChunkRows made = chunk_rows(ctx, as);
@@ -2013,7 +2043,7 @@ int32_t deliver_trace_rows(attpc_ctx* ctx, RunOut& o, AsmSet& as, uint32_t n, ui
       HIP_TRY(ctx, hipMemcpyAsync(o.cloud->labels + base, made.labels, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost,
                                   ctx->stream_c));
   }
-  if (ctx->est_call_events >= 0 && (rc = enqueue_estimates(ctx, as, n, first_local))) return rc;
+  if (ctx->est_records.made() && (rc = enqueue_estimates(ctx, as, n, first_local))) return rc;
   HIP_TRY(ctx, hipEventRecord(as.copied, ctx->stream_c));
   return ATTPC_OK;
 }
@@ -2516,10 +2546,8 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   int32_t rc;
   if ((rc = validate_id_range(ctx, first_event, n_events))) return rc;
   if (makes_traces(o.mode) && (rc = reset_trace_sums(ctx, o.mode))) return rc;
-  if (makes_traces(o.mode) && (rc = begin_trigger_call(ctx, n_events))) return rc;
-  if (o.mode == OutMode::trace_rows && (rc = begin_estimate_call(ctx, n_events, &lay))) return rc;
-  if (o.mode == OutMode::trace_rows &&
-      (rc = begin_cluster_call(ctx, n_events, &lay, o.cloud && o.cloud->points ? o.cloud->capacity : -1)))
+  if (makes_traces(o.mode) && (rc = begin_record_streams(ctx, o.mode == OutMode::trace_rows, n_events, &lay,
+                                                          o.cloud && o.cloud->points ? o.cloud->capacity : -1)))
     return rc;
   // a readout run sizes its trace chunks for |S| rows per event until it has seen its own rate: the rate of an earlier
   // run says nothing once the threshold, the noise or the workload has changed (hit mode keeps the context's rate)
@@ -2617,11 +2645,11 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
     if (sink.status) HIP_TRY(ctx, hipMemcpyAsync(sink.status + b0, ts.status.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (sink.p4) HIP_TRY(ctx, hipMemcpyAsync(sink.p4 + b0 * n_rows * 4, ts.p4.p, (size_t)nb * n_rows * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (sink.vertex) HIP_TRY(ctx, hipMemcpyAsync(sink.vertex + b0 * 3, ts.vertex.p, (size_t)nb * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->reaction_call) {  // the truth of this batch, for the reaction reconstruction behind its chunks
-      ctx->rx_p4 = static_cast<const double*>(ts.p4.p);
-      ctx->rx_vertex = static_cast<const double*>(ts.vertex.p);
-      ctx->rx_status = src.from_kernel ? static_cast<const int32_t*>(ts.status.p) : nullptr;
-      ctx->rx_batch_first = b0;
+    if (ctx->rx_records.made()) {  // the truth of this batch, for the reaction reconstruction behind its chunks
+      ctx->call.rx_p4 = static_cast<const double*>(ts.p4.p);
+      ctx->call.rx_vertex = static_cast<const double*>(ts.vertex.p);
+      ctx->call.rx_status = src.from_kernel ? static_cast<const int32_t*>(ts.status.p) : nullptr;
+      ctx->call.rx_batch_first = b0;
     }
     if ((rc = run_batch_chunks(ctx, lay, trk, seed, first_event + b0, b0, nb, o, &st, queue_next))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // this set's readers are done before it is refilled
@@ -2642,7 +2670,7 @@ int32_t run_events(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, uint64_t
   if (o.mode == OutMode::trace_rows) {
     st.n_points = (uint64_t)o.rows;  // the rows of the call, as in the Spyral mode
     if ((rc = read_peak_sums(ctx, o))) return rc;
-    if (ctx->reaction_call) {  // the spectra of the call, read like the checksum: once, when the call has ended
+    if (ctx->rx_records.made()) {  // the spectra of the call, read like the checksum: once, when the call has ended
       ctx->h_rx_cells.resize(ctx->rx_cells.bytes / sizeof(uint64_t));
       HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rx_cells.data(), ctx->rx_cells.p, ctx->rx_cells.bytes, hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3232,7 +3260,6 @@ int32_t attpc_rows_undistort(attpc_ctx* ctx, int64_t n_events, const int64_t* of
   if (rc) return rc;
   HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, 4 * sizeof(unsigned long long), ctx->stream));
   a.counts = d_counts;
-  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> start;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
@@ -3422,9 +3449,7 @@ int32_t host_cloud_run(attpc_ctx* ctx, uint64_t seed, uint64_t first_event, int6
   if ((rc = drop_prefetch(ctx))) return rc;
   if ((rc = sync_all(ctx))) return rc;
   if ((rc = reset_trace_sums(ctx, o.mode))) return rc;
-  if ((rc = begin_trigger_call(ctx, n))) return rc;
-  if (o.mode == OutMode::trace_rows && (rc = begin_estimate_call(ctx, n, nullptr))) return rc;  // (no layout: no records)
-  if (o.mode == OutMode::trace_rows && (rc = begin_cluster_call(ctx, n, nullptr, -1))) return rc;  // (... and no clusters)
+  if ((rc = begin_record_streams(ctx, o.mode == OutMode::trace_rows, n, nullptr, -1))) return rc;  // (no layout: the trigger's records alone)
   const double keep = ctx->trace_rows_per_event;  // a host cloud says nothing about the configured workload
   rc = trace_host_events(ctx, o, 0, n, offsets, points, labels, seed, first_event);
   ctx->trace_rows_per_event = keep;
@@ -4047,9 +4072,7 @@ int32_t attpc_trace_configure_trigger(attpc_ctx* ctx, const attpc_trigger_desc* 
 
 int32_t attpc_trigger_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_trigger_record* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->trigger_call_events < 0)
-    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_trigger_last: no trigger was configured for the last trace call");
-  return copy_last(ctx, __func__, first, count, ctx->trigger_call_events, 1, ctx->h_trigger.p, out);
+  return records_last(ctx, ctx->tg_records, __func__, "no trigger was configured for the last trace call", first, count, out);
 }
 
 int32_t attpc_trigger_rows(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const int32_t* pads, const int16_t* samples,
@@ -4104,9 +4127,8 @@ int32_t attpc_trace_configure_estimates(attpc_ctx* ctx, const attpc_estimate_des
 
 int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_estimate* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->est_call_events < 0 || !ctx->records_call)
-    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_estimates_last: the last trace-row call made no track estimates, or kept them on the device");
-  return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_estimates.p, out);
+  return records_last(ctx, ctx->est_records, __func__, "the last trace-row call made no track estimates, or kept them on the device",
+                      first, count, out);
 }
 
 namespace {
@@ -4116,8 +4138,7 @@ int32_t rows_estimate(attpc_ctx* ctx, const char* func, int64_t n_events, const 
                       const int64_t* labels, const attpc_event_layout* layout, const attpc_estimate_desc* d,
                       const attpc_circle_desc* circle, attpc_track_estimate* out, const attpc_helix_desc* helix = nullptr) {
   if (!ctx || n_events < 0 || !d || !layout) return ATTPC_E_INVALID;
-  if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
-    return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", func, layout->n_sim, ATTPC_MAX_SIM);
+  if (const int32_t bad = n_sim_range(ctx, func, layout->n_sim)) return bad;
   if (const char* bad = estimate_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
   if (circle)
     if (const char* bad = circle_desc_error(*circle)) return fail(ctx, ATTPC_E_INVALID, "circle: %s", bad);
@@ -4137,7 +4158,6 @@ int32_t rows_estimate(attpc_ctx* ctx, const char* func, int64_t n_events, const 
   a.n_sim = (int32_t)n_sim;
   if (circle) circle_settings(*circle, &a);
   if (helix) a.helix_regressor = helix->regressor;
-  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> start;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
@@ -4191,20 +4211,18 @@ int32_t attpc_trace_configure_clustering(attpc_ctx* ctx, const attpc_cluster_des
 int32_t attpc_clusters_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_cluster_event* events,
                             attpc_cluster_record* records) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->cluster_call_events < 0 || !ctx->records_call)
-    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_clusters_last: the clustering was off for the last trace-row call");
-  if (const int32_t rc = copy_last(ctx, __func__, first, count, ctx->cluster_call_events, 1, ctx->h_cl_events.p, events, false))
-    return rc;
-  return copy_last(ctx, __func__, first, count, ctx->cluster_call_events, ATTPC_MAX_SIM, ctx->h_cl_records.p, records, false);
+  const char* why = "the clustering was off for the last trace-row call";
+  if (const int32_t rc = records_last(ctx, ctx->cl_events, __func__, why, first, count, events, false)) return rc;
+  return records_last(ctx, ctx->cl_records, __func__, why, first, count, records, false);
 }
 
 int32_t attpc_cluster_labels_last(attpc_ctx* ctx, int64_t first_row, int64_t count, int64_t* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->cluster_call_events < 0 || ctx->cluster_call_rows < 0)
+  if (!ctx->cl_events.made() || ctx->call.cluster_rows < 0)
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_cluster_labels_last: the last trace-row call made no cluster labels or did not fetch its rows");
-  if (first_row < 0 || count < 0 || first_row > ctx->cluster_call_rows || count > ctx->cluster_call_rows - first_row)
-    return fail(ctx, ATTPC_E_INVALID, "attpc_cluster_labels_last: rows %lld .. + %lld of %lld", (long long)first_row, (long long)count,
-                (long long)ctx->cluster_call_rows);
+  const int64_t rows = ctx->call.cluster_rows;
+  if (first_row < 0 || count < 0 || first_row > rows || count > rows - first_row)
+    return fail(ctx, ATTPC_E_INVALID, "attpc_cluster_labels_last: rows %lld .. + %lld of %lld", (long long)first_row, (long long)count, (long long)rows);
   if (count == 0) return ATTPC_OK;
   if (!out) return ATTPC_E_INVALID;
   std::memcpy(out, ctx->h_cl_labels.p + (size_t)first_row, (size_t)count * sizeof(int64_t));
@@ -4234,7 +4252,6 @@ int32_t rows_cluster(attpc_ctx* ctx, const char* func, int64_t n_events, const i
   if (n_events == 0) return ATTPC_OK;
   ClusterArgs a{};
   a.s = cluster_settings(*d, *layout);
-  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> start;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
@@ -4283,11 +4300,9 @@ int32_t attpc_trace_configure_cluster_join(attpc_ctx* ctx, const attpc_join_desc
 
 int32_t attpc_joins_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_join_event* events, attpc_join_record* records) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->cluster_call_events < 0 || !ctx->join_call || !ctx->records_call)
-    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_joins_last: the cluster joining or the clustering was off for the last trace-row call");
-  if (const int32_t rc = copy_last(ctx, __func__, first, count, ctx->cluster_call_events, 1, ctx->h_jn_events.p, events, false))
-    return rc;
-  return copy_last(ctx, __func__, first, count, ctx->cluster_call_events, ATTPC_MAX_SIM, ctx->h_jn_records.p, records, false);
+  const char* why = "the cluster joining or the clustering was off for the last trace-row call";
+  if (const int32_t rc = records_last(ctx, ctx->jn_events, __func__, why, first, count, events, false)) return rc;
+  return records_last(ctx, ctx->jn_records, __func__, why, first, count, records, false);
 }
 
 int32_t attpc_rows_cluster_join(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows, const int64_t* labels,
@@ -4306,9 +4321,7 @@ int32_t attpc_trace_configure_fit(attpc_ctx* ctx, const attpc_fit_desc* d) {
 
 int32_t attpc_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_fit* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->est_call_events < 0 || !ctx->fit_call || !ctx->records_call)
-    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_fits_last: the last trace-row call made no track fits");
-  return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_fits.p, out);
+  return records_last(ctx, ctx->fit_records, __func__, "the last trace-row call made no track fits", first, count, out);
 }
 
 namespace {
@@ -4319,8 +4332,7 @@ int32_t rows_fit(attpc_ctx* ctx, const char* func, int64_t n_events, const int64
                  const attpc_track_estimate* estimates_in, const double* start, const attpc_fit_desc* fd,
                  const attpc_pid_record* pid, bool with_pid, attpc_track_fit* out) {
   if (!ctx || n_events < 0 || !ed || !fd || !layout) return ATTPC_E_INVALID;
-  if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
-    return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", func, layout->n_sim, ATTPC_MAX_SIM);
+  if (const int32_t bad = n_sim_range(ctx, func, layout->n_sim)) return bad;
   if (layout->n_rows < 0 || layout->n_rows > ATTPC_MAX_ROWS)
     return fail(ctx, ATTPC_E_INVALID, "%s: n_rows %d outside 0 .. %d", func, layout->n_rows, ATTPC_MAX_ROWS);
   if (const char* bad = estimate_desc_error(*ed)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
@@ -4344,7 +4356,6 @@ int32_t rows_fit(attpc_ctx* ctx, const char* func, int64_t n_events, const int64
   a.n_sim = (int32_t)n_sim;
   FitPosition position[ATTPC_MAX_SIM];
   fit_positions(ctx->det, *layout, position);
-  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> first;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
@@ -4385,10 +4396,7 @@ int32_t attpc_trace_configure_pid(attpc_ctx* ctx, const attpc_pid_desc* d) {
   { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
   ctx->pid_on = false;
   if (!d) {  // (off: the gates' buffer goes too)
-    if (ctx->pid_gates.p) {
-      ctx->device_bytes -= ctx->pid_gates.bytes;
-      ctx->pid_gates = DevBuf{};
-    }
+    release(ctx, ctx->pid_gates);
     return ATTPC_OK;
   }
   const int32_t rc = upload_pid_gates(ctx, ctx->pid_gates, *d);
@@ -4400,16 +4408,13 @@ int32_t attpc_trace_configure_pid(attpc_ctx* ctx, const attpc_pid_desc* d) {
 
 int32_t attpc_pid_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_pid_record* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->est_call_events < 0 || !ctx->pid_call || !ctx->records_call)
-    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_pid_last: the last trace-row call made no particle identification");
-  return copy_last(ctx, __func__, first, count, ctx->est_call_events, (size_t)ctx->est_call_n_sim, ctx->h_pid.p, out);
+  return records_last(ctx, ctx->pid_records, __func__, "the last trace-row call made no particle identification", first, count, out);
 }
 
 int32_t attpc_estimates_pid(attpc_ctx* ctx, int64_t n_events, int32_t n_sim, const attpc_track_estimate* estimates,
                             const attpc_pid_desc* d, attpc_pid_record* out) {
   if (!ctx || n_events < 0 || !d) return ATTPC_E_INVALID;
-  if (n_sim < 0 || n_sim > ATTPC_MAX_SIM)
-    return fail(ctx, ATTPC_E_INVALID, "%s: n_sim %d outside 0 .. %d", __func__, n_sim, ATTPC_MAX_SIM);
+  if (const int32_t bad = n_sim_range(ctx, __func__, n_sim)) return bad;
   if (const char* bad = pid_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "pid: %s", bad);
   if (n_events > 0 && n_sim && (!estimates || !out)) return ATTPC_E_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -4437,11 +4442,9 @@ int32_t attpc_reaction_configure(attpc_ctx* ctx, const attpc_reaction_desc* d) {
     if (const char* bad = reaction_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "reaction: %s", bad);
   { int32_t rc0 = begin_configure(ctx); if (rc0) return rc0; }
   ctx->reaction_on = false;
-  ctx->reaction_call = false;
-  for (DevBuf* b : {&ctx->rx_eloss, &ctx->rx_cells}) {  // (off, or other bins: the buffers go)
-    if (b->p) ctx->device_bytes -= b->bytes;
-    *b = DevBuf{};
-  }
+  ctx->rx_records.off();
+  release(ctx, ctx->rx_eloss);  // (off, or other bins: the buffers go)
+  release(ctx, ctx->rx_cells);
   if (!d) return ATTPC_OK;
   int32_t rc;
   if ((rc = upload_reaction_eloss(ctx, ctx->rx_eloss, *d))) return rc;
@@ -4454,14 +4457,12 @@ int32_t attpc_reaction_configure(attpc_ctx* ctx, const attpc_reaction_desc* d) {
 
 int32_t attpc_reaction_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_reaction_record* out) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->est_call_events < 0 || !ctx->reaction_call || !ctx->records_call)
-    return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_reaction_last: the last trace-row call made no reaction reconstruction");
-  return copy_last(ctx, __func__, first, count, ctx->est_call_events, 1, ctx->h_reaction.p, out);
+  return records_last(ctx, ctx->rx_records, __func__, "the last trace-row call made no reaction reconstruction", first, count, out);
 }
 
 int32_t attpc_reaction_spectra_last(attpc_ctx* ctx, int64_t n_cells, uint64_t* cells) {
   if (!ctx) return ATTPC_E_INVALID;
-  if (ctx->est_call_events < 0 || !ctx->reaction_call)
+  if (!ctx->rx_records.made())
     return fail(ctx, ATTPC_E_NOTCONFIGURED, "attpc_reaction_spectra_last: the last trace-row call made no reaction reconstruction");
   if (n_cells != (int64_t)ctx->h_rx_cells.size() || !cells)
     return fail(ctx, ATTPC_E_INVALID, "%s: %lld cells, the spectra have %zu", __func__, (long long)n_cells, ctx->h_rx_cells.size());
@@ -4524,8 +4525,7 @@ int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets
                         const attpc_event_layout* layout, const attpc_thin_desc* d, int64_t capacity, int64_t* point_offsets,
                         double* points, int64_t* point_labels, attpc_thin_info* info, int64_t* needed) {
   if (!ctx || n_events < 0 || !d || !layout || capacity < 0 || !needed) return ATTPC_E_INVALID;
-  if (layout->n_sim < 0 || layout->n_sim > ATTPC_MAX_SIM)
-    return fail(ctx, ATTPC_E_INVALID, "attpc_rows_thin: n_sim %d outside 0 .. %d", layout->n_sim, ATTPC_MAX_SIM);
+  if (const int32_t bad = n_sim_range(ctx, __func__, layout->n_sim)) return bad;
   if (const char* bad = thin_desc_error(*d)) return fail(ctx, ATTPC_E_INVALID, "thinning: %s", bad);
   const size_t n_sim = (size_t)layout->n_sim;
   if (!point_offsets || (n_events > 0 && n_sim && !info)) return ATTPC_E_INVALID;
@@ -4546,7 +4546,6 @@ int32_t attpc_rows_thin(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets
   estimate_positions(*layout, a.slot_label);
   a.n_sim = (int32_t)n_sim;
   a.step = thin_step_units(d->z_step);
-  constexpr int64_t CHUNK_ROWS = 1 << 20, CHUNK_EVENTS = 65536;  // a chunk: whole events up to these (at least one event)
   std::vector<int64_t> start;
   std::vector<ThinPoint> sparse;  // the chunk's point buffer: the regions of its (event, position)s
   int64_t total = 0;              // points so far

@@ -1312,7 +1312,9 @@ typedef struct attpc_track_estimate {
 ATTPC_API int32_t attpc_trace_configure_estimates(attpc_ctx* ctx, const attpc_estimate_desc* desc);
 /* Records [count][layout->n_sim] of events first .. first + count - 1 of the context's last trace-row call, in the
  * call's event order (a call repeated after ATTPC_E_CAPACITY overwrites them).  ATTPC_E_NOTCONFIGURED if the stage was
- * off for that call, ATTPC_E_INVALID for a range outside it. */
+ * off for that call, ATTPC_E_INVALID for a range outside it.  A trace or trace-row call that is refused at its start
+ * leaves nothing to read: every attpc_*_last reader of the records that call would have replaced (for a trace call
+ * attpc_trigger_last alone) answers ATTPC_E_NOTCONFIGURED until the next such call that succeeds. */
 ATTPC_API int32_t attpc_estimates_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_track_estimate* out);
 /* The stage alone on any host rows in CSR form, through the same kernel (what attpc_trigger_rows is to the trigger):
  * offsets [n_events + 1], rows [R][8] as the trace-row and Spyral-row entry points deliver them, labels [R] -> out
