@@ -330,6 +330,25 @@ REACTION_DTYPE = np.dtype([("status", "<i4"), ("slot", "<i4"), ("beam_ke", "<f8"
 assert C.sizeof(ReactionDesc) == 136 and REACTION_DTYPE.itemsize == C.sizeof(ReactionRecord) == 64
 assert all(REACTION_DTYPE.fields[name][1] == getattr(ReactionRecord, name).offset for name, _ in ReactionRecord._fields_)
 
+# ATTPC_HYP_*: the bits of FitHypothesis.status
+HYP_NO_CANDIDATE, HYP_NO_FIT, HYP_TAKEN, HYP_DISPLACED = 1, 2, 4, 8
+
+
+class HypothesisDesc(C.Structure):  # attpc_hypothesis_desc
+    _fields_ = [("candidates", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FitHypothesis(C.Structure):  # attpc_fit_hypothesis
+    _fields_ = [("position", C.c_int32), ("species", C.c_int32), ("tried", C.c_int32), ("fitted", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32), ("f", C.c_double * MAX_SIM), ("f_next", C.c_double)]
+
+
+# the hypothesis records as a numpy structured dtype: itemsize and field offsets are those of include/attpc_engine.h
+HYPOTHESIS_DTYPE = np.dtype([("position", "<i4"), ("species", "<i4"), ("tried", "<i4"), ("fitted", "<i4"), ("status", "<i4"),
+                             ("reserved", "<i4"), ("f", "<f8", (MAX_SIM,)), ("f_next", "<f8")], align=True)
+assert C.sizeof(HypothesisDesc) == 8 and HYPOTHESIS_DTYPE.itemsize == C.sizeof(FitHypothesis) == 96
+assert all(HYPOTHESIS_DTYPE.fields[name][1] == getattr(FitHypothesis, name).offset for name, _ in FitHypothesis._fields_)
+
 
 class ThinDesc(C.Structure):
     _fields_ = [("z_step", C.c_double), ("reserved", C.c_int32), ("pad", C.c_int32)]
@@ -577,6 +596,7 @@ EXPORTED_SYMBOLS = (
     "attpc_trace_configure_cluster_join", "attpc_joins_last", "attpc_rows_cluster_join",
     "attpc_trace_configure_pid", "attpc_pid_last", "attpc_estimates_pid", "attpc_rows_fit_pid",
     "attpc_reaction_configure", "attpc_reaction_last", "attpc_reaction_spectra_last", "attpc_reaction_records",
+    "attpc_trace_configure_hypotheses", "attpc_hypotheses_last", "attpc_hypothesis_fits_last", "attpc_rows_fit_hypotheses",
 )
 
 # The entry points added under ABI version 3 (additive), group by group in the order they were added:
@@ -711,11 +731,19 @@ SYMBOL_GROUPS = {
                                    C.POINTER(TrackEstimate), C.POINTER(PidRecord), _dp, _dp, _i32p,
                                    C.POINTER(ReactionRecord), C.c_int64, C.POINTER(C.c_uint64)],
     },
+    "hypotheses": {
+        "attpc_trace_configure_hypotheses": [_ctxp, C.POINTER(HypothesisDesc)],
+        "attpc_hypotheses_last": [_ctxp, C.c_int64, C.c_int64, C.POINTER(FitHypothesis)],
+        "attpc_hypothesis_fits_last": [_ctxp, C.c_int64, C.c_int64, _i32p, C.POINTER(TrackFit)],
+        "attpc_rows_fit_hypotheses": _rows_in + [C.POINTER(EventLayout), C.POINTER(EstimateDesc), C.POINTER(TrackEstimate), _dp,
+                                                 C.POINTER(FitDesc), C.POINTER(HypothesisDesc), C.POINTER(PidRecord),
+                                                 C.POINTER(FitHypothesis), C.POINTER(TrackFit), C.POINTER(TrackFit), _i32p, _i32p],
+    },
 }
 (TRACE_ROW_SYMBOLS, SUMMARY_SYMBOLS, SELECT_SYMBOLS, BASELINE_SYMBOLS, TRIGGER_SYMBOLS, GAIN_SYMBOLS, COMMON_SYMBOLS,
  TRACE_PACK_SYMBOLS, MAPS_SYMBOLS, ESTIMATE_SYMBOLS, THIN_SYMBOLS, STRAGGLE_SYMBOLS, CIRCLE_SYMBOLS, HELIX_SYMBOLS,
  DISTORT_SYMBOLS, UNDISTORT_SYMBOLS, FIT_SYMBOLS, CLUSTER_SYMBOLS, JOIN_SYMBOLS, PID_SYMBOLS,
- REACTION_SYMBOLS) = (
+ REACTION_SYMBOLS, HYPOTHESIS_SYMBOLS) = (
      tuple(group) for group in SYMBOL_GROUPS.values())
 
 _lib = None
@@ -810,7 +838,7 @@ def load_library() -> C.CDLL:
 
 CONFIGURE_SLOTS = ("det", "spyral", "trace", "trace_noise", "trace_common", "trace_readout", "trace_gain", "peaks", "baseline", "trigger", "summary",
                    "select", "maps", "estimates", "thinning", "straggling", "circle", "helix", "distortion", "correction", "fit", "clustering", "cluster_join", "pid",
-                   "reaction")
+                   "reaction", "hypotheses")
 
 
 class Context:

@@ -127,6 +127,9 @@ struct AsmSet {  // one chunk's cloud in event order, or its Spyral rows, or its
   DevBuf tg_row_pass;          // ... with its gate, trace rows: fired of every kept trace row's event, uint8 [traces]
   DevBuf fit_records;          // track fit on (fit.hip): the chunk's records, attpc_track_fit [events][n_sim]
   DevBuf pid_records;          // particle identification on (pid.hip): the chunk's records, attpc_pid_record [events][n_sim]
+  DevBuf hyp_records;          // fit hypotheses on (hypothesis.hip): the chunk's records, attpc_fit_hypothesis [events][n_sim],
+  DevBuf hyp_fits;             // ... the fits of every hypothesis, attpc_track_fit [events][n_sim][H],
+  DevBuf hyp_assigned;         // ... and, for the reaction reconstruction, the positions as attpc_pid_record [events][n_sim]
   DevBuf rx_records;           // reaction reconstruction on (reaction.hip): the chunk's records, attpc_reaction_record [events]
   DevBuf est_records;          // track estimates on (estimate.hip): the chunk's records, attpc_track_estimate [events][n_sim]
   DevBuf thin_points;          // ... of thinned points (thin.hip): one ThinPoint per trace row (pk_cap)
@@ -174,6 +177,7 @@ struct TraceRowCall {
   int64_t est_slot_label[ATTPC_MAX_SIM] = {};    // their labels (EstimateArgs)
   FitPosition fit_position[ATTPC_MAX_SIM] = {};  // their nuclei
   int32_t pid_species[ATTPC_MAX_SIM] = {};       // their species
+  HypLayout hyp{};                               // the fit hypotheses of the layout (n == 0: the stage does not run)
   ClusterSettings cluster{};                     // the clustering's settings with the call's layout
   JoinSettings join{};                           // the joining's
   int64_t cluster_rows = -1;       // the delivered rows whose cluster labels are in h_cl_labels so far (-1: it fetches none)
@@ -310,6 +314,10 @@ struct attpc_ctx {
   attpc_pid_desc pid{};
   DevBuf pid_gates;                // the gates on the device (PidGates), filled by the configure call
   CallRecords<attpc_pid_record> pid_records;  // [events][n_sim]
+  bool hyp_on = false;             // attpc_trace_configure_hypotheses (inert while the estimates or the fit are off)
+  attpc_hypothesis_desc hyp{};
+  CallRecords<attpc_fit_hypothesis> hyp_records;  // [events][n_sim]
+  CallRecords<attpc_track_fit> hyp_fits;          // [events][n_sim * H]
   bool reaction_on = false;        // attpc_reaction_configure (inert while its source is off)
   attpc_reaction_desc reaction{};  // (eloss: nullptr, the table is in rx_eloss)
   DevBuf rx_eloss;                 // the table on the device, filled by the configure call
@@ -599,7 +607,7 @@ T* chunk_room(attpc_ctx* ctx, const CallRecords<T>& r, DevBuf& dev, uint32_t n, 
 // nothing if the call does not make the stream or keeps it on the device.
 template <typename T>
 int32_t copy_chunk(attpc_ctx* ctx, const CallRecords<T>& r, const DevBuf& dev, uint64_t first_local, uint32_t n) {
-  if (!r.made() || !r.to_host || !n) return ATTPC_OK;
+  if (!r.made() || !r.to_host || !n || !r.per) return ATTPC_OK;
   HIP_TRY(ctx, hipMemcpyAsync(r.h.p + (size_t)first_local * r.per, dev.p, (size_t)n * r.per * sizeof(T), hipMemcpyDeviceToHost,
                               ctx->stream_c));
   return ATTPC_OK;
@@ -1280,9 +1288,11 @@ void fit_positions(const DetDev& det, const attpc_event_layout& lay, FitPosition
 
 // The track fit of `n` events behind their estimates on S: the arguments the estimates had, their records, and room
 // for the trials.
+// With `hyp` (n >= 1) the launch is the instantiation over (track, hypothesis) pairs: records is [n][n_sim][hyp->n], pid
+// may be nullptr.
 int32_t enqueue_fit(attpc_ctx* ctx, const EstimateArgs& e, uint32_t n, const attpc_fit_desc& d, const FitPosition* position,
-                    const double* start, const attpc_pid_record* pid, attpc_track_fit* records) {
-  const uint32_t workgroups = fit_workgroups(n, e.n_sim);
+                    const double* start, const attpc_pid_record* pid, attpc_track_fit* records, const HypLayout* hyp = nullptr) {
+  const uint32_t workgroups = fit_workgroups(n, e.n_sim, hyp ? hyp->n : 1);
   const int32_t rc = ensure(ctx, ctx->fit_scratch, (size_t)workgroups * FIT_SCRATCH_PER_WORKGROUP);
   if (rc) return rc;
   FitArgs a{};
@@ -1303,7 +1313,27 @@ int32_t enqueue_fit(attpc_ctx* ctx, const EstimateArgs& e, uint32_t n, const att
   a.rb2 = e.rb2;
   a.n_events = n;
   a.n_sim = e.n_sim;
-  launch_fit(ctx->stream, a, pid);
+  if (hyp) launch_fit_hypotheses(ctx->stream, a, *hyp, pid);
+  else launch_fit(ctx->stream, a, pid);
+  HIP_TRY(ctx, hipGetLastError());
+  return ATTPC_OK;
+}
+
+// The selection of the fit hypotheses of `n` > 0 events behind their fits (enqueue_fit with `hyp`) on S.
+int32_t enqueue_hypothesis_select(attpc_ctx* ctx, const HypLayout& hyp, uint32_t n, int32_t n_sim, const attpc_track_fit* all,
+                                  const attpc_pid_record* pid, const attpc_track_estimate* estimates,
+                                  attpc_fit_hypothesis* records, attpc_track_fit* fits, attpc_pid_record* assigned) {
+  HypothesisArgs a{};
+  a.l = hyp;
+  a.all = all;
+  a.pid = pid;
+  a.estimates = estimates;
+  a.records = records;
+  a.fits = fits;
+  a.assigned = assigned;
+  a.n_events = n;
+  a.n_sim = n_sim;
+  launch_hypothesis_select(ctx->stream, a);
   HIP_TRY(ctx, hipGetLastError());
   return ATTPC_OK;
 }
@@ -1359,7 +1389,7 @@ int32_t enqueue_reaction(attpc_ctx* ctx, ReactionArgs a, const attpc_reaction_de
 // The streams of a trace-row call turned off: none answers for any call.
 void trace_row_records_off(attpc_ctx* ctx) {
   auto off = [](auto&... r) { (r.off(), ...); };
-  off(ctx->est_records, ctx->fit_records, ctx->pid_records, ctx->rx_records, ctx->cl_events, ctx->cl_records, ctx->jn_events, ctx->jn_records);
+  off(ctx->est_records, ctx->fit_records, ctx->pid_records, ctx->hyp_records, ctx->hyp_fits, ctx->rx_records, ctx->cl_events, ctx->cl_records, ctx->jn_events, ctx->jn_records);
 }
 
 // The start of a trace-row call of `n` events with the layout `lay` (nullptr: the call has none, makes no records and
@@ -1393,6 +1423,11 @@ int32_t begin_trace_row_call(attpc_ctx* ctx, uint64_t n, const attpc_event_layou
     }
     if (ctx->fit_on && (rc = begin_records(ctx, ctx->fit_records, n, n_sim, to_host))) return rc;
     if (ctx->pid_on && (rc = begin_records(ctx, ctx->pid_records, n, n_sim, to_host))) return rc;
+    if (ctx->fit_on && ctx->hyp_on) {
+      call.hyp = hypothesis_layout(call.pid_species, lay->n_sim, ctx->hyp.candidates);
+      if ((rc = begin_records(ctx, ctx->hyp_records, n, n_sim, to_host))) return rc;
+      if ((rc = begin_records(ctx, ctx->hyp_fits, n, n_sim * (size_t)call.hyp.n, to_host))) return rc;
+    }
   }
   if (reaction) {
     if ((rc = begin_records(ctx, ctx->rx_records, n, 1, to_host))) return rc;
@@ -1494,9 +1529,18 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   }
   if (ctx->fit_records.made()) {
     attpc_track_fit* records = chunk_room(ctx, ctx->fit_records, as.fit_records, n, rc);
-    if (rc || (rc = enqueue_fit(ctx, a, n, ctx->fit, call.fit_position, nullptr, pid, records))) return rc;
+    if (ctx->hyp_records.made()) {  // fit hypotheses: in the place of the plain or pid fit launch, never beside it
+      const bool any = call.hyp.n > 0;  // (no position of the layout has a species: nothing to integrate, nothing is read)
+      attpc_track_fit* all = any ? chunk_room(ctx, ctx->hyp_fits, as.hyp_fits, n, rc) : nullptr;
+      attpc_fit_hypothesis* chosen = chunk_room(ctx, ctx->hyp_records, as.hyp_records, n, rc);
+      if (!rc && ctx->rx_records.made()) rc = ensure(ctx, as.hyp_assigned, (size_t)n * n_sim * sizeof(attpc_pid_record));
+      attpc_pid_record* assigned = ctx->rx_records.made() ? static_cast<attpc_pid_record*>(as.hyp_assigned.p) : nullptr;
+      if (rc || (any && (rc = enqueue_fit(ctx, a, n, ctx->fit, call.fit_position, nullptr, pid, all, &call.hyp)))) return rc;
+      if ((rc = enqueue_hypothesis_select(ctx, call.hyp, n, a.n_sim, all, pid, a.records, chosen, records, assigned))) return rc;
+      if (assigned) pid = assigned;  // (what the reaction reconstruction's slot rule reads)
+    } else if (rc || (rc = enqueue_fit(ctx, a, n, ctx->fit, call.fit_position, nullptr, pid, records))) return rc;
   }
-  if (ctx->rx_records.made()) {  // behind the last of the estimate, pid and fit kernels
+  if (ctx->rx_records.made()) {  // behind the last of the estimate, pid, fit and hypothesis kernels
     const size_t b = (size_t)(first_local - call.rx_batch_first);  // the chunk's first event in its track batch
     ReactionArgs r{};
     r.fits = static_cast<const attpc_track_fit*>(as.fit_records.p);
@@ -1517,6 +1561,8 @@ int32_t enqueue_estimates(attpc_ctx* ctx, AsmSet& as, uint32_t n, uint64_t first
   if ((rc = copy_chunk(ctx, ctx->rx_records, as.rx_records, first_local, n))) return rc;
   if ((rc = copy_chunk(ctx, ctx->fit_records, as.fit_records, first_local, n))) return rc;
   if ((rc = copy_chunk(ctx, ctx->pid_records, as.pid_records, first_local, n))) return rc;
+  if ((rc = copy_chunk(ctx, ctx->hyp_records, as.hyp_records, first_local, n))) return rc;
+  if ((rc = copy_chunk(ctx, ctx->hyp_fits, as.hyp_fits, first_local, n))) return rc;
   return copy_chunk(ctx, ctx->est_records, as.est_records, first_local, n);
 }
 
@@ -4326,36 +4372,54 @@ int32_t attpc_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_trac
 
 namespace {
 
-// attpc_rows_fit (pid == nullptr) and attpc_rows_fit_pid
+struct RowsFitHypotheses {  // what attpc_rows_fit_hypotheses has beyond attpc_rows_fit_pid
+  const attpc_hypothesis_desc* desc;
+  attpc_fit_hypothesis* records;  // [n_events][n_sim]
+  attpc_track_fit* all;           // [n_events][n_sim][H], or nullptr
+  int32_t* n;                     // H, or nullptr
+  int32_t* species;               // [ATTPC_MAX_SIM], or nullptr
+};
+
+// attpc_rows_fit (pid == nullptr), attpc_rows_fit_pid and, with `hyp`, attpc_rows_fit_hypotheses (pid optional)
 int32_t rows_fit(attpc_ctx* ctx, const char* func, int64_t n_events, const int64_t* offsets, const double* rows,
                  const int64_t* labels, const attpc_event_layout* layout, const attpc_estimate_desc* ed,
                  const attpc_track_estimate* estimates_in, const double* start, const attpc_fit_desc* fd,
-                 const attpc_pid_record* pid, bool with_pid, attpc_track_fit* out) {
-  if (!ctx || n_events < 0 || !ed || !fd || !layout) return ATTPC_E_INVALID;
+                 const attpc_pid_record* pid, bool with_pid, attpc_track_fit* out, const RowsFitHypotheses* hyp = nullptr) {
+  if (!ctx || n_events < 0 || !ed || !fd || !layout || (hyp && !hyp->desc)) return ATTPC_E_INVALID;
   if (const int32_t bad = n_sim_range(ctx, func, layout->n_sim)) return bad;
   if (layout->n_rows < 0 || layout->n_rows > ATTPC_MAX_ROWS)
     return fail(ctx, ATTPC_E_INVALID, "%s: n_rows %d outside 0 .. %d", func, layout->n_rows, ATTPC_MAX_ROWS);
   if (const char* bad = estimate_desc_error(*ed)) return fail(ctx, ATTPC_E_INVALID, "estimates: %s", bad);
   if (const char* bad = fit_desc_error(*fd)) return fail(ctx, ATTPC_E_INVALID, "fit: %s", bad);
+  if (hyp)
+    if (const char* bad = hypothesis_desc_error(*hyp->desc)) return fail(ctx, ATTPC_E_INVALID, "hypotheses: %s", bad);
   if (!ctx->det_ready) return fail(ctx, ATTPC_E_NOTCONFIGURED, "%s: no detector is configured", func);
   const size_t n_sim = (size_t)layout->n_sim;
-  if (n_events > 0 && n_sim && (!out || !estimates_in || (with_pid && !pid))) return ATTPC_E_INVALID;
+  if (n_events > 0 && n_sim && (!out || !estimates_in || (with_pid && !pid) || (hyp && !hyp->records))) return ATTPC_E_INVALID;
   if (const ArgError bad = csr_error(func, n_events, offsets)) return refuse(ctx, bad);
   if (n_events > 0 && offsets[n_events] > offsets[0] && (!rows || !labels)) return ATTPC_E_INVALID;
-  if (with_pid)
+  if (with_pid && !hyp)  // (the hypotheses read held, not position)
     for (size_t i = 0; i < (size_t)n_events * n_sim; ++i)
       if (pid[i].position < -1 || pid[i].position >= layout->n_sim)
         return fail(ctx, ATTPC_E_INVALID, "%s: pid[%zu].position %d outside -1 .. %d", func, i, pid[i].position, layout->n_sim - 1);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int32_t rc;
   if ((rc = sync_all(ctx))) return rc;
+  FitPosition position[ATTPC_MAX_SIM];
+  fit_positions(ctx->det, *layout, position);
+  HypLayout hl{};
+  if (hyp) {
+    int32_t species[ATTPC_MAX_SIM];
+    for (int s = 0; s < ATTPC_MAX_SIM; ++s) species[s] = position[s].table;
+    hl = hypothesis_layout(species, layout->n_sim, hyp->desc->candidates);
+    if (hyp->n) *hyp->n = hl.n;
+    for (int h = 0; h < ATTPC_MAX_SIM && hyp->species; ++h) hyp->species[h] = h < hl.n ? hl.species[hl.first[h]] : -1;
+  }
   if (n_events == 0 || n_sim == 0) return ATTPC_OK;
   EstimateArgs a{};
   estimate_settings(*ed, &a);
   estimate_positions(*layout, a.slot_label);
   a.n_sim = (int32_t)n_sim;
-  FitPosition position[ATTPC_MAX_SIM];
-  fit_positions(ctx->det, *layout, position);
   std::vector<int64_t> first;
   for (int64_t e0 = 0, e1; e0 < n_events; e0 = e1) {
     e1 = chunk_end(offsets, n_events, e0, CHUNK_ROWS, CHUNK_EVENTS);
@@ -4365,8 +4429,18 @@ int32_t rows_fit(attpc_ctx* ctx, const char* func, int64_t n_events, const int64
     const double* d_start = start ? stage_in(ctx, 4, start + (size_t)e0 * n_sim * 6, m * n_sim * 6, rc) : nullptr;
     attpc_track_fit* d_out = stage<attpc_track_fit>(ctx, 5, m * n_sim, rc);
     const attpc_pid_record* d_pid = with_pid ? stage_in(ctx, 6, pid + (size_t)e0 * n_sim, m * n_sim, rc) : nullptr;
+    // (hypotheses: the fits of every hypothesis and, behind them, the chosen records share slot 7)
+    const size_t n_all = hyp ? m * n_sim * (size_t)hl.n : 0;
+    char* d_hyp = hyp ? stage<char>(ctx, 7, n_all * sizeof(attpc_track_fit) + m * n_sim * sizeof(attpc_fit_hypothesis), rc) : nullptr;
     if (rc) return rc;
-    if ((rc = enqueue_fit(ctx, a, (uint32_t)m, *fd, position, d_start, d_pid, d_out))) return rc;
+    if (hyp) {
+      attpc_track_fit* d_all = reinterpret_cast<attpc_track_fit*>(d_hyp);
+      attpc_fit_hypothesis* d_records = reinterpret_cast<attpc_fit_hypothesis*>(d_hyp + n_all * sizeof(attpc_track_fit));
+      if (hl.n > 0 && (rc = enqueue_fit(ctx, a, (uint32_t)m, *fd, position, d_start, d_pid, d_all, &hl))) return rc;
+      if ((rc = enqueue_hypothesis_select(ctx, hl, (uint32_t)m, a.n_sim, d_all, d_pid, a.records, d_records, d_out, nullptr))) return rc;
+      if ((rc = stage_out(ctx, hyp->records + (size_t)e0 * n_sim, d_records, m * n_sim))) return rc;
+      if (hyp->all && n_all && (rc = stage_out(ctx, hyp->all + (size_t)e0 * n_sim * (size_t)hl.n, d_all, n_all))) return rc;
+    } else if ((rc = enqueue_fit(ctx, a, (uint32_t)m, *fd, position, d_start, d_pid, d_out))) return rc;
     if ((rc = stage_out(ctx, out + (size_t)e0 * n_sim, d_out, m * n_sim))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
@@ -4387,6 +4461,31 @@ int32_t attpc_rows_fit_pid(attpc_ctx* ctx, int64_t n_events, const int64_t* offs
                            const attpc_track_estimate* estimates_in, const double* start, const attpc_fit_desc* fd,
                            const attpc_pid_record* pid, attpc_track_fit* out) {
   return rows_fit(ctx, __func__, n_events, offsets, rows, labels, layout, ed, estimates_in, start, fd, pid, true, out);
+}
+
+// ---- fit hypotheses (fit.hip, hypothesis.hip; the contract is in include/attpc_engine.h) ----
+int32_t attpc_trace_configure_hypotheses(attpc_ctx* ctx, const attpc_hypothesis_desc* d) {
+  return configure_desc(ctx, d, hypothesis_desc_error, "hypotheses", &attpc_ctx::hyp_on, &attpc_ctx::hyp);
+}
+
+int32_t attpc_hypotheses_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_fit_hypothesis* out) {
+  if (!ctx) return ATTPC_E_INVALID;
+  return records_last(ctx, ctx->hyp_records, __func__, "the last trace-row call made no fit hypotheses", first, count, out);
+}
+
+int32_t attpc_hypothesis_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, int32_t* n_hypotheses, attpc_track_fit* out) {
+  if (!ctx) return ATTPC_E_INVALID;
+  if (ctx->hyp_fits.made() && ctx->hyp_fits.to_host && n_hypotheses) *n_hypotheses = ctx->call.hyp.n;
+  return records_last(ctx, ctx->hyp_fits, __func__, "the last trace-row call made no fit hypotheses", first, count, out);
+}
+
+int32_t attpc_rows_fit_hypotheses(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                  const int64_t* labels, const attpc_event_layout* layout, const attpc_estimate_desc* ed,
+                                  const attpc_track_estimate* estimates_in, const double* start, const attpc_fit_desc* fd,
+                                  const attpc_hypothesis_desc* d, const attpc_pid_record* pid, attpc_fit_hypothesis* records,
+                                  attpc_track_fit* fits, attpc_track_fit* all_fits, int32_t* n_hypotheses, int32_t* species) {
+  const RowsFitHypotheses hyp{d, records, all_fits, n_hypotheses, species};
+  return rows_fit(ctx, __func__, n_events, offsets, rows, labels, layout, ed, estimates_in, start, fd, pid, pid != nullptr, fits, &hyp);
 }
 
 int32_t attpc_trace_configure_pid(attpc_ctx* ctx, const attpc_pid_desc* d) {

@@ -3,7 +3,8 @@
 // fit_host.hpp, shared with the host).
 //
 // Eight lanes per track, eight tracks per wave, one wave per workgroup; a workgroup takes every gridDim.x-th group of
-// eight tracks.  Lane k = 0 .. 6 of a track integrates trial k of an evaluation (q, and q with parameter k - 1
+// eight tracks (in the instantiation of the fit hypotheses the eight items of a wave are (track, hypothesis) pairs, each
+// with its own scratch regions).  Lane k = 0 .. 6 of a track integrates trial k of an evaluation (q, and q with parameter k - 1
 // displaced); lane 7 has no trial.  Everything else -- the gather of the points, the 28 sums, the 6x6 step, the
 // accept / stop rule -- all eight lanes of the track do together, and the iteration is uniform over them, since every
 // lane holds the same sums.
@@ -68,24 +69,39 @@ __device__ __forceinline__ double fit_group_add(double v) {
 
 }  // namespace
 
+// the argument block of an instantiation without the hypotheses
+template <bool PID>
+using FitSlotArgs = std::conditional_t<PID, FitPidArgs, FitArgs>;
+
 // fit_kernel<false> is the fit of "track fit"; fit_kernel<true> is the same body behind the particle identification
 // ("particle identification" in the header): the nucleus of slot s is that of the position its pid record names, and a
-// slot without one gets the record without a fit, NO_PID.
-template <bool PID>
-__global__ __launch_bounds__(64) void fit_kernel(std::conditional_t<PID, FitPidArgs, FitArgs> a) {
+// slot without one gets the record without a fit, NO_PID.  fit_kernel<false, true> is the same body over the (track,
+// hypothesis) pairs of "fit hypotheses": item = track * H + h is fitted as the nucleus of hypothesis h, so the eight
+// groups of a wave hold the hypotheses of neighbouring tracks over the same points; an item that is no candidate of
+// its slot gets the record without a fit, NO_PID, and leaves.
+template <bool PID, bool HYP = false>
+__global__ __launch_bounds__(64) void fit_kernel(std::conditional_t<HYP, FitHypArgs, FitSlotArgs<PID>> a) {
   const int lane = (int)threadIdx.x, k = lane & 7, group = lane & ~7;
   const uint32_t below = (1u << k) - 1u;
-  const uint64_t n_tracks = (uint64_t)a.n_events * (uint64_t)a.n_sim;
-  for (uint64_t first = (uint64_t)blockIdx.x * 8; first < n_tracks; first += (uint64_t)gridDim.x * 8) {
-    const uint64_t track = first + (uint64_t)(lane >> 3);
-    if (track >= n_tracks) continue;  // (the eight lanes of a track together)
+  uint64_t n_items = (uint64_t)a.n_events * (uint64_t)a.n_sim;
+  if constexpr (HYP) n_items *= (uint64_t)a.hyp.n;
+  for (uint64_t first = (uint64_t)blockIdx.x * 8; first < n_items; first += (uint64_t)gridDim.x * 8) {
+    const uint64_t item = first + (uint64_t)(lane >> 3);
+    if (item >= n_items) continue;  // (the eight lanes of an item together)
+    uint64_t track = item;
+    if constexpr (HYP) track = item / (uint64_t)a.hyp.n;
     const uint32_t e = (uint32_t)(track / (uint64_t)a.n_sim);
     const int s = (int)(track - (uint64_t)e * (uint64_t)a.n_sim);
-    attpc_track_fit* out = a.records + track;
+    attpc_track_fit* out = a.records + item;
     const attpc_track_estimate est = a.estimates[track];
     int at = s;  // the position whose nucleus the track is taken for
-    if constexpr (PID) {
-      at = a.pid[track].position;
+    if constexpr (PID) at = a.pid[track].position;
+    if constexpr (HYP) {
+      const int h = (int)(item - track * (uint64_t)a.hyp.n);
+      const bool candidate = (hypothesis_tried(a.hyp, a.pid ? a.pid + track : nullptr) & a.hyp.positions[h]) != 0;
+      at = candidate ? a.hyp.first[h] : -1;
+    }
+    if constexpr (PID || HYP) {
       if (at < 0 || at >= a.n_sim) {
         attpc_track_fit none;
         fit_no_fit(ATTPC_FIT_NO_PID, est.n_used < ATTPC_FIT_MAX_POINTS ? est.n_used : ATTPC_FIT_MAX_POINTS, &none);
@@ -161,9 +177,17 @@ __global__ __launch_bounds__(64) void fit_kernel(std::conditional_t<PID, FitPidA
   }
 }
 
-uint32_t fit_workgroups(uint32_t n_events, int32_t n_sim) {
-  const uint64_t groups = ((uint64_t)n_events * (uint64_t)n_sim + 7) / 8;
+uint32_t fit_workgroups(uint32_t n_events, int32_t n_sim, int32_t n_hyp) {
+  const uint64_t groups = ((uint64_t)n_events * (uint64_t)n_sim * (uint64_t)n_hyp + 7) / 8;
   return (uint32_t)(groups < FIT_MAX_WORKGROUPS ? groups : FIT_MAX_WORKGROUPS);
+}
+
+void launch_fit_hypotheses(hipStream_t s, const FitArgs& a, const HypLayout& hyp, const attpc_pid_record* pid) {
+  FitHypArgs with;
+  static_cast<FitArgs&>(with) = a;
+  with.pid = pid;
+  with.hyp = hyp;
+  hipLaunchKernelGGL((fit_kernel<false, true>), dim3(fit_workgroups(a.n_events, a.n_sim, hyp.n)), dim3(64), 0, s, with);
 }
 
 void launch_fit(hipStream_t s, const FitArgs& a, const attpc_pid_record* pid) {

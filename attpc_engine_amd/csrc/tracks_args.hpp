@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "cluster_host.hpp"  // (behind the HIP runtime header)
 #include "distort_host.hpp"
+#include "hypothesis_host.hpp"
 #include "join_host.hpp"
 #include "undistort_host.hpp"
 #include "unpack_host.hpp"
@@ -331,12 +332,21 @@ struct FitArgs {
 struct FitPidArgs : FitArgs {       // fit_kernel<true>: behind the particle identification (pid.hip), the nucleus of
   const attpc_pid_record* pid;      // slot s is that of position pid[e][s].position; [n_events][n_sim]
 };
+struct FitHypArgs : FitArgs {       // fit_kernel<false, true>: the fit hypotheses (hypothesis_host.hpp).  Its work items
+  const attpc_pid_record* pid;      // are (track, hypothesis) pairs, item = track * hyp.n + h: slot s is fitted as the
+  HypLayout hyp;                    // nucleus of position hyp.first[h] if a position of h is a candidate of the slot
+};                                  // (pid: [n_events][n_sim] or nullptr); records is [n_events][n_sim][hyp.n]
 constexpr uint32_t FIT_MAX_WORKGROUPS = 1024;
 constexpr size_t FIT_SCRATCH_PER_WORKGROUP = (size_t)8 * 8 * ATTPC_FIT_MAX_POINTS * 3 * sizeof(double);
-// the workgroups (one wave of eight tracks each) for n_events * n_sim tracks; a.scratch holds that many regions
-uint32_t fit_workgroups(uint32_t n_events, int32_t n_sim);
+// the workgroups (one wave of eight items each) for n_events * n_sim tracks of n_hyp items each (1: an item is a
+// track); a.scratch holds that many regions
+uint32_t fit_workgroups(uint32_t n_events, int32_t n_sim, int32_t n_hyp = 1);
 // fit_kernel<false>, or with `pid` fit_kernel<true> (FitPidArgs)
 void launch_fit(hipStream_t s, const FitArgs& a, const attpc_pid_record* pid = nullptr);
+// fit_kernel<false, true> (FitHypArgs): `hyp` with n >= 1, `pid` or nullptr
+void launch_fit_hypotheses(hipStream_t s, const FitArgs& a, const HypLayout& hyp, const attpc_pid_record* pid);
+// hypothesis_selection_kernel (hypothesis.hip), a lane per event, behind launch_fit_hypotheses on the same stream
+void launch_hypothesis_select(hipStream_t s, const HypothesisArgs& a);
 
 // particle identification (pid.hip; attpc_trace_configure_pid, the contract is in include/attpc_engine.h)
 struct PidGates {                   // the gates of an attpc_pid_desc as the device holds them

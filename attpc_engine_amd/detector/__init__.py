@@ -5,6 +5,7 @@ from . import joining as _joining
 from . import correction as _correction
 from . import distortion as _distortion
 from . import fit as _fit
+from . import hypothesis as _hypothesis
 from . import maps as _maps
 from . import parameters as _parameters
 from . import pid as _pid
@@ -38,6 +39,8 @@ _EXPORTS = {
     _pid: ("Gate", "PidSettings", "configure_pid", "pid_last", "estimates_to_pid", "by_position", "PID_DTYPE"),
     _reaction: ("ReactionSettings", "ReactionSpectra", "configure_reaction", "reaction_last", "records_to_reaction",
                 "REACTION_DTYPE"),
+    _hypothesis: ("HypothesisSettings", "configure_fit_hypotheses", "hypotheses_last", "hypothesis_fits_last",
+                  "rows_to_fit_hypotheses", "HYPOTHESIS_DTYPE"),
     _writer: ("SimulationWriter", "SpyralWriter", "TraceWriter", "read_traces"),
 }
 __all__ = []

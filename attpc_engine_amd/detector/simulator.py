@@ -94,6 +94,7 @@ def run_batch(call: str, momenta, vertices, proton_numbers, mass_numbers, config
     ``detector.distortion.DistortionMap``; None = off): the drift distortion of the call's track samples, in the drift of
     ``config``."""
     from .distortion import configure_distortion
+    from .hypothesis import configure_fit_hypotheses
     from .reaction import configure_reaction
     from .straggling import configure_straggling
 
@@ -106,6 +107,7 @@ def run_batch(call: str, momenta, vertices, proton_numbers, mass_numbers, config
     configure_straggling(ctx, straggling, config)
     configure_distortion(ctx, distortion, config)
     configure_reaction(ctx, None)  # (an Engine's reaction reconstruction on this context: the entry points here do not take it)
+    configure_fit_hypotheses(ctx, None)  # (nor its fit hypotheses)
     known = configure(ctx) if configure else None
     per_event = max(int(capacity_per_event), known or 0)
     layout = build_layout(proton_numbers, mass_numbers, indices, keys)

@@ -23,6 +23,7 @@ from .detector.fit import TrackFitSettings, configure_track_fit
 from .detector.clustering import ClusterSettings, configure_clustering
 from .detector.joining import JoinSettings, configure_cluster_join
 from .detector.pid import PidSettings, configure_pid
+from .detector.hypothesis import HypothesisSettings, configure_fit_hypotheses, hypotheses_result
 from .detector.reaction import ReactionSettings, configure_reaction, reaction_result, source_on
 from .detector.helix import HelixSlopeSettings, configure_helix
 from .detector.thinning import ThinSettings, configure_thinning
@@ -48,6 +49,7 @@ class Engine:
         self._selection = None  # the Selection configure_selection uploaded
         self._maps = None  # the MapsSettings configure_maps uploaded
         self._reaction = None  # the ReactionSettings configure_reaction uploaded
+        self._hypotheses = None  # the HypothesisSettings configure_fit_hypotheses uploaded
         ctx = self.ctx
         kin, keep_k = pipeline.device_desc()
         ctx.check(ctx.lib.attpc_kin_configure(ctx.handle, kin), "attpc_kin_configure")
@@ -60,6 +62,7 @@ class Engine:
         configure_straggling(ctx, None)  # a new engine starts without the track straggling an earlier one configured
         configure_distortion(ctx, None)  # ... and without its drift distortion
         configure_reaction(ctx, None)  # ... and without its reaction reconstruction, which was that engine's reaction
+        configure_fit_hypotheses(ctx, None)  # ... and without its fit hypotheses
         self.layout = build_layout(self.z, self.a, self.indices, self.species)
         if chunk_events:
             ctx.check(ctx.lib.attpc_set_chunk_events(ctx.handle, int(chunk_events)), "attpc_set_chunk_events")
@@ -316,23 +319,26 @@ class Engine:
         slope configured (``configure_helix_slope``) their slope, vz and B rho come from the turning angle about the
         circle's centre, and ``slope`` is "helix"; with the drift correction configured (``configure_correction``) the
         rows, labels and estimates are those of the corrected rows, and ``correction`` holds its counts (n_rows,
-        n_skipped, n_unconverged, n_moved)."""
+        n_skipped, n_unconverged, n_moved); with the fit hypotheses configured (``configure_fit_hypotheses``) beside the
+        estimates and the track fit, their records [n, n_sim] under ``hypotheses``, and ``fits`` are the chosen species'."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         self._trace_rows_defaults()
         self._apply_reaction()
+        self._apply_hypotheses()
         ctx = self.ctx
         if not fetch:
             stats, out = _abi.RunStats(), _abi.CloudOut()
             ctx.check(ctx.lib.attpc_sim_run_trace_rows(ctx.handle, int(seed), int(first_event), int(n_events), self.layout,
                                                        None, None, None, out, stats), "attpc_sim_run_trace_rows")
             return {"stats": stats.as_dict(), "trace_rows": ctx.trace_rows_last(),
-                    **stage_results(ctx, n_events, len(self.indices)), **reaction_result(ctx, self._reaction, n_events)}
+                    **stage_results(ctx, n_events, len(self.indices)), **hypotheses_result(ctx, n_events, len(self.indices)),
+                    **reaction_result(ctx, self._reaction, n_events)}
         per_event = max(int(capacity_per_event), 4 * ctx._trace_readout_rows)
         arrays, res = self._deliver("attpc_sim_run_trace_rows", n_events, seed, first_event, max(1024, per_event * n_events),
                                     pinned, holder=RowArrays, width=8, slack=1024)
         return {**res, "rows": arrays.result()[1], "trace_rows": ctx.trace_rows_last(),
                 **stage_results(ctx, n_events, len(self.indices), int(arrays.offsets[-1])),
-                **reaction_result(ctx, self._reaction, n_events)}
+                **hypotheses_result(ctx, n_events, len(self.indices)), **reaction_result(ctx, self._reaction, n_events)}
 
     # ---------------------------------------------------------------- track estimates of the trace rows
     def configure_estimates(self, estimates=None, **parameters) -> None:
@@ -439,6 +445,7 @@ class Engine:
         the reaction reconstruction or its source is not configured."""
         seed, first_event, n_events = _abi.check_id_range(seed, first_event, n_events)
         self._apply_reaction()
+        self._apply_hypotheses()
         if not source_on(self.ctx, self._reaction):
             raise RuntimeError("run_spectra needs the reaction reconstruction and its source: call configure_reaction, "
                                "configure_estimates and (for source 'fit') configure_track_fit first")
@@ -458,6 +465,22 @@ class Engine:
         holds."""
         configure_reaction(self.ctx, self._reaction)
 
+    def configure_fit_hypotheses(self, settings=None, **parameters) -> None:
+        """The fit hypotheses behind the track fit (include/attpc_engine.h, "fit hypotheses"): a
+        ``detector.hypothesis.HypothesisSettings`` or its keyword (candidates: a bit mask or a sequence of positions,
+        default all) turns them on -- with the estimates and the track fit on, every slot of ``run_trace_rows`` /
+        ``run_estimates`` is then fitted once per candidate species of the layout and takes the free position of the
+        lowest objective ``f``; the results carry ``hypotheses`` [n, n_sim] (``detector.hypothesis.HYPOTHESIS_DTYPE``),
+        ``fits`` are the chosen species' records, and the reaction reconstruction reads this stage's positions; with the
+        particle identification on, its gates only narrow the candidates --, neither turns them off (the default).
+        ``simulate_batch*``, ``run_fused``, ``run_simulation`` and the writers do not take it."""
+        self._hypotheses = _settings(HypothesisSettings, settings, parameters)
+        configure_fit_hypotheses(self.ctx, self._hypotheses)
+
+    def _apply_hypotheses(self) -> None:
+        """This engine's fit hypotheses on the context, as ``_apply_reaction``."""
+        configure_fit_hypotheses(self.ctx, self._hypotheses)
+
     def run_estimates(self, n_events: int, seed: int = 0, first_event: int = 0) -> dict:
         """``run_trace_rows(fetch=False)`` for its track estimates: the rows are made, estimated and left on the device,
         128 bytes per track cross PCIe (``estimates`` [n, n_sim], ``detector.estimate.ESTIMATE_DTYPE``), beside the
@@ -469,6 +492,7 @@ class Engine:
             raise RuntimeError("run_estimates needs the estimates: call configure_estimates first")
         self._trace_rows_defaults()
         self._apply_reaction()
+        self._apply_hypotheses()
         ctx, stats, out = self.ctx, _abi.RunStats(), _abi.CloudOut()
         p4 = np.empty((n_events, self.n_rows, 4), dtype=np.float64)
         vertex = np.empty((n_events, 3), dtype=np.float64)
@@ -478,7 +502,7 @@ class Engine:
                                                    out, stats), "attpc_sim_run_trace_rows")
         return {"indices": list(self.indices), "vertex": vertex, "p4": p4, "status": status, "stats": stats.as_dict(),
                 "trace_rows": ctx.trace_rows_last(), **stage_results(ctx, n_events, len(self.indices)),
-                **reaction_result(ctx, self._reaction, n_events)}
+                **hypotheses_result(ctx, n_events, len(self.indices)), **reaction_result(ctx, self._reaction, n_events)}
 
 
     # ---------------------------------------------------------------- event and track summaries of a resident run

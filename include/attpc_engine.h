@@ -2293,6 +2293,103 @@ ATTPC_API int32_t attpc_reaction_records(attpc_ctx* ctx, int64_t n_events, int32
                                          const double* p4, const double* vertex, const int32_t* kin_status,
                                          attpc_reaction_record* records, int64_t n_cells, uint64_t* cells);
 
+/* ---- fit hypotheses (opt-in: off by default, and with it off every output, kernel and buffer of every entry point is
+ * what it is without this section; inert while the track estimates or the track fit are off; the entry points are
+ * additions under ABI version 3) ----
+ * The particle identification above gates on the two most biased numbers of the chain.  The track fit itself holds the
+ * quantity that separates species: a trial integrated with the wrong stopping-power table cannot have the curvature and
+ * the range of the data at once, and a data point beyond the trial's end costs its full distance ("track fit",
+ * Residuals (iii)).  This stage fits every slot once per candidate species and gives every slot the position of the
+ * lowest f.  It is not a row of the trace-row chain: it is configured on the context, like the reaction reconstruction.
+ * tests/hypothesis_reference.py restates this contract in numpy; csrc/hypothesis_host.hpp holds the candidate test, the
+ * fitted test, the walk and the record as one piece of code for the device and the host.
+ *
+ * Hypotheses.  Two positions p, p' < n_sim of the call's layout are the same hypothesis iff they have the same detector
+ * species (species_of_row[indices[p]], where the context's detector has it with Z > 0 and a mass: the species of
+ * attpc_pid_record); a position without one is no candidate.  The H <= ATTPC_MAX_SIM hypotheses are numbered in the
+ * order of their first position.  The host works them out once per call.
+ *
+ * Candidates of slot k: tried[k] = candidates (the settings' bit mask of positions) AND the positions p < n_sim with a
+ * species AND, if the call makes pid records, pid.held of the slot.  With the particle identification on the gates only
+ * narrow the choice, and the fit decides among what they hold.
+ *
+ * Fits.  For every (slot k, hypothesis h) with a position of h in tried[k]: the record "track fit" defines with "the
+ * position's nucleus" replaced by the species of h; everything else it reads (rows, cluster labels, thinned points, the
+ * estimate record as the start, a given start) is slot k's.  It is byte for byte the record of attpc_rows_fit_pid with
+ * pid.position of the slot forced to a position of h.  Every other (slot, hypothesis) pair is not integrated: its
+ * record is the record without a fit with ATTPC_FIT_NO_PID alone, as "particle identification" defines it.
+ *
+ * Selection per event.  Position p of tried[k] is FITTED for slot k iff the record of (k, hypothesis of p) has none of
+ * EMPTY, FEW, NO_START and its f is finite; fitted[k] is their bit mask, f[p] the f of that record (NaN for p outside
+ * tried[k]).  The slots are walked in ascending k (with the clustering on this is rank order): slot k takes the fitted
+ * position with the lowest f that no earlier slot took; f is compared with < only and the positions are tested in
+ * ascending order, so a tie goes to the lowest position -- two positions of one species go to two slots in position
+ * order.  Comparisons and copies only: no arithmetic on f.
+ *
+ * attpc_fit_hypothesis per (event, slot), 96 bytes: position (-1: none); species, the detector species of that position
+ * (-1: none); tried; fitted; status; reserved 0; f[ATTPC_MAX_SIM]; f_next, the lowest f among the fitted positions of a
+ * species other than the chosen one (taken or not), NaN if there is none or no position was chosen -- a caller cuts on
+ * f_next / f[position] on the host.  status bits:
+ *   NO_CANDIDATE  tried == 0;
+ *   NO_FIT        fitted == 0 (set beside NO_CANDIDATE too);
+ *   TAKEN         there are fitted positions, but all of them are taken (position -1);
+ *   DISPLACED     a position was assigned whose f is greater than the lowest f of the fitted positions: the best one
+ *                 was taken.  (A free position of the same f as the taken best one is not a displacement.)
+ *
+ * Outputs.  fits[e][k] (attpc_fits_last) is a copy of the record of (k, hypothesis of the chosen position); for a slot
+ * without a position it is the record without a fit with ATTPC_FIT_NO_PID alone.  The pid records stay what the gates
+ * made them.  With this stage on, the "Slot" rule of the reaction reconstruction reads this stage's position where it
+ * read pid.position.  A record is a pure function of the event's rows, its estimate records, the tables, the settings
+ * and, with the particle identification on, the gates, whatever the chunking. */
+#define ATTPC_HYP_NO_CANDIDATE 1
+#define ATTPC_HYP_NO_FIT 2
+#define ATTPC_HYP_TAKEN 4
+#define ATTPC_HYP_DISPLACED 8
+
+typedef struct attpc_hypothesis_desc {
+  int32_t candidates;  /* bit p: position p may be chosen; not 0, no bit at or above ATTPC_MAX_SIM */
+  int32_t reserved;    /* 0 */
+} attpc_hypothesis_desc;  /* 8 bytes */
+
+typedef struct attpc_fit_hypothesis {
+  int32_t position;  /* -1: none */
+  int32_t species;   /* -1: none */
+  int32_t tried;     /* bit p: position p was a candidate */
+  int32_t fitted;    /* bit p: ... and its species' fit can be compared */
+  int32_t status;    /* ATTPC_HYP_* bits */
+  int32_t reserved;  /* 0 */
+  double f[ATTPC_MAX_SIM];  /* by position; NaN outside tried */
+  double f_next;
+} attpc_fit_hypothesis;  /* 96 bytes */
+
+/* desc == NULL turns the stage off (the default): no kernel is launched and no buffer is held then.  ATTPC_E_INVALID
+ * for a candidates mask of 0, for bits at or above ATTPC_MAX_SIM and for a reserved field that is not 0.  Independent of
+ * every other configure call; without the track estimates and the track fit it does nothing.  With all three on,
+ * attpc_sim_run_trace_rows and attpc_det_run_trace_rows launch, in the place of every chunk's fit kernel, its
+ * instantiation over (track, hypothesis) pairs -- item = track * H + h, eight lanes per item, [events][n_sim][H]
+ * records in a buffer of the chunk -- and behind it hypothesis_selection_kernel, a lane per event, in front of
+ * reaction_kernel on the same stream, also when the rows stay on the device. */
+ATTPC_API int32_t attpc_trace_configure_hypotheses(attpc_ctx* ctx, const attpc_hypothesis_desc* desc);
+/* Records [count][layout->n_sim] of the context's last trace-row call, as attpc_fits_last.  ATTPC_E_NOTCONFIGURED if
+ * this stage, the track fit or the estimates were off for that call. */
+ATTPC_API int32_t attpc_hypotheses_last(attpc_ctx* ctx, int64_t first, int64_t count, attpc_fit_hypothesis* out);
+/* The fit records of every hypothesis of that call, [count][layout->n_sim][H], and H itself (n_hypotheses, may be NULL;
+ * written also when count is 0); out holds count * n_sim * ATTPC_MAX_SIM records at the most.  For tests and studies. */
+ATTPC_API int32_t attpc_hypothesis_fits_last(attpc_ctx* ctx, int64_t first, int64_t count, int32_t* n_hypotheses,
+                                             attpc_track_fit* out);
+/* attpc_rows_fit_pid with this stage, through the same two kernels as the fused path: desc not NULL; pid
+ * [n_events][n_sim] or NULL (of which held is read); records [n_events][n_sim], fits [n_events][n_sim], all_fits
+ * [n_events][n_sim][H] with room for ATTPC_MAX_SIM hypotheses per slot, or NULL: not wanted; n_hypotheses (H) and
+ * species [ATTPC_MAX_SIM] (the detector species of hypothesis h, -1 behind H) may be NULL. */
+ATTPC_API int32_t attpc_rows_fit_hypotheses(attpc_ctx* ctx, int64_t n_events, const int64_t* offsets, const double* rows,
+                                            const int64_t* labels, const attpc_event_layout* layout,
+                                            const attpc_estimate_desc* estimate_desc,
+                                            const attpc_track_estimate* estimates_in, const double* start,
+                                            const attpc_fit_desc* fit_desc, const attpc_hypothesis_desc* desc,
+                                            const attpc_pid_record* pid, attpc_fit_hypothesis* records,
+                                            attpc_track_fit* fits, attpc_track_fit* all_fits, int32_t* n_hypotheses,
+                                            int32_t* species);
+
 #ifdef __cplusplus
 }
 #endif
